@@ -11,7 +11,11 @@ distance -> ordered hits [-> RCCL all-gather of hits when N > 1]) over the rank'
 the queries already resident in HBM.  N > 1: one process per GPU, index replicated, queries
 sharded (weak scaling: 100 k queries per GPU), hits all-gathered.
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel over its HIP-event time
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times exactly --steps steps and reports them
+(`value`, `ms_per_step`, and the per-phase, roofline and index figures the library records for those steps);
+`--full` adds the measurements that take runs of their own: radius recall and recall@10, the PCIe-inclusive
+rate, `cpu_baseline`, `general_centres` and `secondary`.  `--dump-outputs DIR` writes the hits of the last timed
+step (dump_outputs).  `roofline` prices the dominant kernel over its HIP-event time
 (events on the library's stream): with the bucket join on (the default) that is hs_join8x_kernel
 (k = 21..25, with hs_join8r_kernel beside it for segments of few probing queries; hs_join8xw_kernel for
 k <= 20; hs_join8w_kernel for k = 26..50), an int8 MFMA GEMM of depth 128 (192 for
@@ -25,7 +29,7 @@ the same workload: `value` is the MEASURED rate at the sample's N; the figure sc
 reported beside it and labelled as an extrapolation.  `general_centres`: the same step with centres that are
 no k-mers (jittered), the path of the reference's family centroids.
 
-`secondary` (default on where the HBM holds it): BASELINE.json configs[2], the north-star target -- 10^8
+`secondary` (with --full, where the HBM holds it): BASELINE.json configs[2], the north-star target -- 10^8
 25-mers, L = 32, K = 20, W = 160 from its own recall sweep, 10^6 queries -- as a STRONG-scaling job: one
 query set sharded over the ranks, every rank one batch, the index replicated; `value` = 10^6 / the slowest
 rank's pass.  At N = 1 it also times the 125 000-query pass that is one GPU's share of the 8-GPU job
@@ -109,7 +113,15 @@ def parse():
     ap.add_argument("--general-jitter", type=float, default=0.05)
     ap.add_argument("--pcie-steps", type=int, default=5,
                     help="steps of the PCIe-inclusive measurement of hs_query / hs_query_codes (0: skip)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (recall, PCIe-inclusive rate, CPU baseline, "
+                         "general_centres, the secondary block); the options above that skip or size them apply here")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the hits of the last timed step as DIR/<q|id|table|dist>.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def workload_label(args):
@@ -203,6 +215,28 @@ def cpu_baseline(args, a, b, codes, centers):
         "value_scaled_to_bench_n": q_mt / t_mt * n_s / codes.shape[0],
         "hits": int(len(res_mt["q"])), "seconds": t_mt}
     return out
+
+
+DUMP_MAX_BYTES = 60 << 20         # below 64 MB with the .npy headers
+DUMP_SAMPLE_SEED = 2029
+
+
+def dump_outputs(out_dir, hits):
+    """--dump-outputs: what the timed step hands its caller -- the hit list (query, DB id, table of first sight,
+    exact distance) of all ranks in the reference's order -- as out_dir/<q|id|table|dist>.npy, float64 (query
+    numbers and ids are exact there).  Above DUMP_MAX_BYTES in all, a fixed seeded sample of the hits, in order,
+    with the rows it kept in out_dir/sample_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    cols = {name: t.cpu().numpy().astype(np.float64) for name, t in zip(("q", "id", "table", "dist"), hits)}
+    n = len(cols["q"])
+    row_bytes = 8 * (len(cols) + 1)
+    if n * 8 * len(cols) > DUMP_MAX_BYTES:
+        rng = np.random.Generator(np.random.MT19937(DUMP_SAMPLE_SEED))
+        keep = np.sort(rng.choice(n, size=DUMP_MAX_BYTES // row_bytes, replace=False))
+        cols = {name: v[keep] for name, v in cols.items()}
+        cols["sample_rows"] = keep.astype(np.float64)
+    for name, v in cols.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 def planted_family_recall(args, eng, codes, a, b, device):
@@ -348,7 +382,7 @@ class Workload:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         acc.update(dt=dt, jstat=jstat, qproj=qproj, join_rows=join_rows, cand=cand, hits_local=hits_local,
-                   total_hits=int(gathered[0].numel()) if gathered is not None else 0)
+                   total_hits=int(gathered[0].numel()) if gathered is not None else 0, last_hits=gathered)
         return acc
 
     def roofline(self, m, steps, traffic=None, traffic_src=None):
@@ -723,6 +757,10 @@ def main():
     k, K, L, W, R = args.k, args.K, args.L, args.W, args.R
     wl = Workload(args, dev_index, dev, rank, synth, Engine, torch, workload_label(args))
     m = wl.timed(args.steps, args.warmup, hdist, HsError, use_dist, fence, dist, backend)
+    last_hits = m.pop("last_hits")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_hits)
+    del last_hits
     line = None
     if rank == 0:
         steps = max(args.steps, 1)
@@ -772,7 +810,7 @@ def main():
             "queries_recognised_as_kmers_per_step": m["recognised"] / steps,
             "index": index,
         }
-        nr = min(args.recall_queries, args.nq)
+        nr = min(args.recall_queries, args.nq) if args.full else 0
         if nr > 0:
             line.update(wl.recall(nr))
         if nr > 0 and args.planted_members > 0:
@@ -785,12 +823,12 @@ def main():
                                     "points": [{"W": r["W"], "radius_recall": round(r["radius_recall"], 4),
                                                 "candidates_per_query": round(r["candidates_per_query"])}
                                                for r in sj["sweep"]]}
-        if world == 1 and args.pcie_steps > 0:
+        if args.full and world == 1 and args.pcie_steps > 0:
             # the boundary's host-pointer entry points, PCIe inside the timed region; never `value`
             line["value_pcie_inclusive"] = wl.pcie_inclusive(args.pcie_steps)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, wl.a, wl.b, wl.codes, wl.centers)
-    if world == 1 and args.general_steps > 0:
+    if args.full and world == 1 and args.general_steps > 0:
         # centres that are NOT k-mers (the reference's real centres are family centroids,
         # centerDistanceSmapling.cpp:67-78): the same queries with Gaussian noise on every coordinate, so that
         # hs_query_dev recognises nothing and every per-query quantity comes from the point rows
@@ -808,9 +846,9 @@ def main():
     wl.close()
     del wl
 
-    # ---- the north star's own target as a second block of the same line (secondary_block).  Run when the
-    # primary line is the default workload and every rank's GPU has the room (index: 157 GB).
-    want_secondary = (not args.no_secondary and args.verify_mode == "auto" and
+    # ---- the north star's own target as a second block of the same line (secondary_block).  Run with --full when
+    # the primary line is the default workload and every rank's GPU has the room (index: 157 GB).
+    want_secondary = (args.full and not args.no_secondary and args.verify_mode == "auto" and
                       ((args.n, args.k, args.K, args.L) == (10_000_000, 25, 16, 8) or args.force_secondary))
     if want_secondary:
         torch.cuda.empty_cache()

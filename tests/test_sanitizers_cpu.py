@@ -27,7 +27,10 @@ def test_host_layer_and_oracle_under_asan_ubsan(tmp_path):
         "HS_ORACLE_LIB": os.path.join(ROOT, "oracle", "libhs_oracle_san.so"),
         "HS_HOST_BIN_DIR": os.path.join(ROOT, "hsearch_amd", "bin_san"),
     })
+    # --rootdir: without it pytest roots the child's collection at the common ancestor of its working directory
+    # (tmp_path) and the test files, which may be a directory this user cannot list
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "not gpu", "-p", "no:cacheprovider",
+                        "--rootdir", ROOT,
                         os.path.join(ROOT, "tests", "test_oracle_golden.py"),
                         os.path.join(ROOT, "tests", "test_host_cli.py"),
                         os.path.join(ROOT, "tests", "test_tables.py")],

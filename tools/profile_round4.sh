@@ -25,5 +25,5 @@ python3 tools/pmc_secondary.py $OUT/pmc_${TAG}_sec 1000000 160 > $OUT/${TAG}_pmc
 cp profiles/traffic_latest.json $OUT/${TAG}_traffic_latest.json
 cp profiles/traffic_secondary.json $OUT/${TAG}_traffic_secondary.json
 rm -rf $OUT/pmc_$TAG/p*/ $OUT/pmc_${TAG}_sec/p*/
-python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 tail -c 600 $OUT/${TAG}_pmc_secondary.txt
