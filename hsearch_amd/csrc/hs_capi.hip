@@ -105,6 +105,35 @@ struct Knobs {
 #endif
 };
 
+// One query call's queries and what it asks (run_query, query_batch, probe_tabs)
+struct QueryCall {
+  const double* centers = nullptr;
+  const uint8_t* codes = nullptr;  // queries given as residue codes [nq][k] (hs_query_codes); centers unused
+  double R = 0.0;
+  bool brute = false;
+  uint32_t self_first = HS_NO_SELF;  // self-join: DB id of query 0
+  bool sqrt_test = false;            // hit test sqrt(d2) <= R (hclust2.cpp:119-120) instead of d2 <= R*R
+};
+
+// What a handle learns from its batches to steer the next ones (plan_batch, the join launch); written by
+// learn_from_batch alone, forgotten with the index (drop_index)
+struct BatchHistory {
+  // work items of the last joined batch x 1.25: with it the next batch sizes its descriptor array
+  // without asking the device (the kernels clamp to the real count; an overflow repeats the batch)
+  uint32_t item_cap_hint = 0;
+  double pairs_per_item = 0.0;  // average of the previous batch's join work items (0: none yet)
+  // share of the last joined batch's work items that lay in segments with few probing queries (the
+  // query-resident kernel's class); < 0: unknown.  That kernel pays when the class is the bulk of the items
+  // (configs[2]'s shape: 90 %); where it is a minority (configs[1]: the extra launch costs more than the
+  // class's items cost in the streaming kernel) the next batch runs everything through the streaming kernel
+  double resident_share = -1.0;
+  uint32_t resident_age = 0;  // joined batches since it was measured (measured again every 64)
+  uint32_t resident_nq = 0;   // ... on a batch of this many queries (a batch half / twice that size measures anew)
+  // the last batch that ordered its hits itself had to fall back to the sort, at this radius
+  bool order_failed = false;
+  double order_failed_R = 0.0;
+};
+
 }  // namespace
 
 struct hs_handle {
@@ -178,9 +207,7 @@ struct hs_handle {
   bool wide8_ok = false;         // the 8-column table is usable (wide rows on demand for k = 21..25)
   uint32_t* pin_cnt = nullptr;   // 64 pinned words: where a batch's counters land (three small device ->
                                  // host copies into PAGEABLE memory cost ~ 50 us of host staging per batch)
-  double pairs_per_item = 0.0;   // average of the previous batch's join work items (0: none yet)
-  bool order_failed = false;     // the last batch that ordered its hits itself had to fall back to the sort
-  double order_failed_R = 0.0;   // ... at this radius
+  BatchHistory hist;
   Knobs knobs;
   bool wide8 = false;            // short k-mers: int8 rows over all 8 coordinate columns (hs_join8.hip)
   // segment routing thresholds (HS_JOIN_MIN_Q / _M): segments with fewer probing queries or members
@@ -188,16 +215,6 @@ struct hs_handle {
   // persistent waves leave no room for a kernel beside it, and the per-pair filter run before it
   // cost 0.3 ms at C2 (a chain of dependent loads per probe) against 0.06 ms of extra join time
   uint32_t join_min_q = 1, join_min_m = 1;
-  // work items of the last joined batch x 1.25: with it the next batch sizes its descriptor array
-  // without asking the device (the kernels clamp to the real count; an overflow repeats the batch)
-  uint32_t item_cap_hint = 0;
-  // share of the last joined batch's work items that lay in segments with few probing queries (the
-  // query-resident kernel's class); < 0: unknown.  That kernel pays when the class is the bulk of the items
-  // (configs[2]'s shape: 90 %); where it is a minority (configs[1]: the extra launch costs more than the
-  // class's items cost in the streaming kernel) the next batch runs everything through the streaming kernel
-  double resident_share = -1.0;
-  uint32_t resident_age = 0;     // joined batches since it was measured (measured again every 64)
-  uint32_t resident_nq = 0;      // ... on a batch of this many queries (a batch half / twice that size measures anew)
   int join_blocks_per_cu = 2;                // resident workgroups of hs_join_kernel per CU
   DevBuf jtab, c16, seg_keys, seg_keys_sorted, seg_vals, sorted_ql, seg_key, seg_cnt, seg_qoff,
       seg_items, item_off, seg_n;
@@ -211,8 +228,6 @@ struct hs_handle {
   double proj_eps_scale = 1.0;
   double proj_est = 0.0;        // typical half-width of the bound, in bucket units
   DevBuf proj_aq_all, proj_aq_tab, proj_fn, proj_tab, proj_stats, proj_flags[3], proj_cnt, proj_xq, proj_xmeta;
-  bool sqrt_test = false;       // hit test sqrt(d2) <= R (hclust2.cpp:119-120) instead of d2 <= R*R
-  uint32_t self_first = HS_NO_SELF;  // self-join: DB id of query 0 of the current run_query
   bool join_tables_ok = false;  // fp16 can carry the coordinate table
   int verify_mode = 0;          // 0 auto, 1 streaming kernel, 2 bucket join
   std::string err;
@@ -259,14 +274,11 @@ float filter_bound(double r2) {
 void drop_index(hs_handle* h) {
   h->built = false;
   h->rec8w_ready = false;
-  h->order_failed = false;
-  h->order_failed_R = 0.0;
-  h->item_cap_hint = 0;
-  h->pairs_per_item = 0.0;
-  h->resident_share = -1.0;
-  h->resident_age = 0;
-  h->resident_nq = 0;
+  h->hist = {};
 }
+
+// Queries per batch at most: the probe numbers (query x table) carry a flag in bit 31
+uint32_t max_query_batch(const hs_handle* h) { return (uint32_t)((1ull << 31) / h->p.L) - 1; }
 
 hs_status ensure_device(hs_handle* h) {
   HS_HIP(h, hipSetDevice(h->p.device));
@@ -680,7 +692,7 @@ hs_status hs_set_option(hs_handle* h, int option, int64_t value) {
   };
   switch (option) {
     case HS_OPT_QUERY_BATCH:
-      if (value < 0 || value >= (1ll << 27)) break;
+      if (value < 0 || value >= (1ll << 27) || value > (int64_t)max_query_batch(h)) break;
       kn.query_batch = (uint32_t)value;
       return HS_OK;
     case HS_OPT_SEG_MODE:
@@ -1225,16 +1237,16 @@ static hs_status build_tables(hs_handle* h, uint32_t seed, bool* collided) {
 }
 
 // the tables as the probe kernel gets them: without the directory records when the option says so
-static hs_tables_dev probe_tabs(const hs_handle* h, uint32_t q_first, const uint32_t* probe_list = nullptr,
-                                uint32_t n_list = 0) {
+static hs_tables_dev probe_tabs(const hs_handle* h, const QueryCall& c, uint32_t q_first,
+                                const uint32_t* probe_list = nullptr, uint32_t n_list = 0) {
   hs_tables_dev t = h->tabs;
   t.q_first = q_first;
   t.probe_list = probe_list;
   t.n_list = n_list;
   if (h->knobs.no_probe_records)
     for (int l = 0; l < HS_MAX_L; ++l) t.t[l].dir_rec = nullptr;
-  t.part = h->self_first == HS_NO_SELF ? h->bucket_part : 0u;  // (searches only, not the self-joins)
-  t.n_parts = h->self_first == HS_NO_SELF ? h->bucket_parts : 1u;
+  t.part = c.self_first == HS_NO_SELF ? h->bucket_part : 0u;  // (searches only, not the self-joins)
+  t.n_parts = c.self_first == HS_NO_SELF ? h->bucket_parts : 1u;
   return t;
 }
 
@@ -2107,6 +2119,9 @@ struct BatchOut {
 // [20] hits not ordered on the device, [21] HS_CNT_SURVIVOR_OVERFLOW, [32] the join's item counter.
 // Internal status: the batch's filters passed more pairs than the 32-bit survivor counter holds.
 static const hs_status HS_SPLIT_BATCH = (hs_status)1000;
+// Internal status: a batch that left its item count on the device found it over the capacity hint, or a
+// query row the join cannot carry; the batch runs again with the count read back first.
+static const hs_status HS_SYNC_ITEMS = (hs_status)1001;
 // Wide int8 rows (all 8 coordinate columns) for this call?  Always for short k-mers (the index's
 // member records are wide then).  For k = 21..25 when the radius is large for the k-mer length: the
 // 4-column squared distance of two random k-mers is ~ N(k m, k v) (m, v: one residue pair), and once
@@ -2134,7 +2149,7 @@ static hs_status ensure_rec8w(hs_handle* h) {
   return HS_OK;
 }
 
-// May a self-join at radius R run from the residue codes alone (query_batch's self_codes)?  Only when
+// May a self-join at radius R run from the residue codes alone (the plan's self_codes)?  Only when
 // nothing on its way can need the embedded centres: the int8 join and its thin-segment filter must
 // apply, and no query row may be unrepresentable -- for a k-mer of the coordinate table the one way
 // is -gamma overflowing its 13 base-127 digits, bounded here from R and the scale alone.
@@ -2149,458 +2164,500 @@ static bool self_codes_ok(const hs_handle* h, double R) {
   return s > 0.0 && 0.5 * s * s * r2 + (wide ? 508.0 : 254.0) * k + 3.0 < 127.0 * 127.0 * 13.0;
 }
 
-// d_qcodes_ext != null: the queries are k-mers given as residue codes [nq][k] (hs_query_codes) -- rows of
-// the coordinate table like the DB's -- and d_centers is unused.
-static hs_status query_batch(hs_handle* h, const double* d_centers, const uint8_t* d_qcodes_ext, uint32_t nq,
-                             uint32_t q_base, double R, bool brute, uint64_t* d_cand, uint32_t* n_batch_hits,
-                             BatchOut* bout = nullptr, bool allow_async = true) {
-  const int K = (int)h->p.K, L = brute ? 1 : (int)h->p.L, k = (int)h->p.k;
-  const uint32_t nql = nq * (uint32_t)L;
-  const double r2 = R * R;  // motif_both_points.cpp:204
-  const float r2_hi = filter_bound(r2);
-  const int n_blocks = h->n_cu * 8;
-  uint32_t* d_cnt = h->counters.as<uint32_t>();
-  HS_HIP(h, hipMemsetAsync(d_cnt, 0, 256, h->stream));  // incl. the join's item counter (d_cnt + 32)
-  HS_HIP(h, hipEventRecord(h->ev[0], h->stream));
+// How a batch runs, decided by plan_batch before its first launch from the handle's switches, the call
+// and the batch history.  demote() alone changes it afterwards, when a query row is unsafe.
+struct BatchPlan {
+  bool can16 = false;       // the fp16 form of the join filter exists (k <= 25): int8's fallback
+  bool use_join = false;    // bucket join (fp16 or int8 rows) in front of the exact decision; streaming otherwise
+  bool use_i8 = false;      // ... in its int8 form (hs_join8.hip)
+  int wide = 0;             // ... over all 8 coordinate columns (want_wide)
+  bool refine = false;      // the int8 join's survivors pass an 8-column int8 bound (hs_refine8_kernel)
+  bool self_codes = false;  // self-join whose per-query quantities all come from the indexed codes
+  bool ext_codes = false;   // queries given as codes that never become centres
+  bool seg_sparse = false;  // probes grouped by a sort of the probes, not a counting sort over the buckets
+  bool parted = false;      // bucket partition: only this part's probes are fingerprinted and grouped
+  bool all_joined = false;  // every segment goes to the join (HS_OPT_JOIN_MIN_Q / _M at 1)
+  bool use_r = false;       // segments with few probing queries through hs_join8r_kernel
+  uint32_t jm = HS_JM_BLOCK;  // members per join work item
+  bool async_items = false;   // the item count stays on the device; the descriptors are sized by item_cap
+  uint32_t item_cap = 0;
+  bool order_here = false;    // the batch orders its hits per query itself (no sort afterwards)
+  int xcd_run = -1;           // chunks per XCD-local run of join items (-1: by the query tiles' size)
+  bool resident_stale = false;  // the history's resident share was measured on a batch of another size
+};
+
+// Precedence, first rule first: the filter form (verify mode, k, radius, the tables' representability), then
+// what follows from it (wide rows, refinement, queries from codes, item size, the resident kernel), then the
+// grouping -- a bucket partition always sorts its probes (the counting sort needs the rank of every probe,
+// which the part's owned-probe list never writes), HS_OPT_SEG_MODE next, the bucket : probe ratio last.
+static BatchPlan plan_batch(const hs_handle* h, const QueryCall& c, uint32_t nq, bool allow_async, bool ordered_out) {
+  BatchPlan p;
+  const BatchHistory& m = h->hist;
+  const int k = (int)h->p.k;
+  const double r2 = c.R * c.R;
   // fp16 form: k <= 25 only; int8 form (hs_join8.hip): k <= 50 (6 or 8 k-steps for two packed words)
-  const bool can16 = h->join_tables_ok && k <= 25;
+  p.can16 = h->join_tables_ok && k <= 25;
   const bool can8 = h->join8_tables_ok && k <= 50 && h->verify_mode != 3;
-  bool use_join = !brute && h->verify_mode != 1 && r2 < 30000.0 && (can16 || can8);
-  // int8 form of the join filter unless forced to fp16 (mode 3) or not representable
-  bool use_i8 = use_join && can8;
-  // survivors of the int8 join's 4-column bound pass an 8-column int8 bound before the exact
-  // decision (hs_refine8_kernel); HS_NO_REFINE8 switches it off
+  p.use_join = h->verify_mode != 1 && r2 < 30000.0 && (p.can16 || can8);
+  p.use_i8 = p.use_join && can8;
+  p.wide = (p.use_i8 && want_wide(h, c.R)) ? 1 : 0;
   // (wide rows already hold all 8 columns: nothing to refine)
-  const int wide = (use_i8 && want_wide(h, R)) ? 1 : 0;
-  if (wide) HS_CHECK(ensure_rec8w(h));
-  const uint4* const rec8 = (wide && !h->wide8) ? h->t_rec8w.as<uint4>() : h->t_rec8.as<uint4>();
-  const void* const jtab_rows = wide ? (const void*)(h->jtab8.as<char>() + 1536) : (const void*)h->jtab8.p;
-  const bool refine = use_i8 && !wide && !h->knobs.no_refine8;
-  uint32_t* d_unsafe = d_cnt + 8;
+  p.refine = p.use_i8 && !p.wide && !h->knobs.no_refine8;
   // Self-join (the queries are the indexed k-mers self_first + q_base ..): every per-query quantity
   // comes from the residue codes and the tables -- no embedded centres, no hashing, no directory
   // search (a k-mer probes the bucket it sits in).  Needs the int8 join with its thin-segment filter,
-  // the only filters that work without per-query distance tables.
+  // the only filters that work without per-query distance tables.  Queries given as codes likewise.
+  const bool codes_ok = p.use_i8 && self_codes_ok(h, c.R);
+  p.self_codes = codes_ok && c.self_first != HS_NO_SELF;
+  p.ext_codes = codes_ok && c.codes;
   // how the probes are grouped by bucket in front of the join: a counting sort over the bucket slots,
-  // or -- when those far outnumber the probes -- a sort of the probes (HS_OPT_SEG_MODE forces one)
+  // or -- when those far outnumber the probes -- a sort of the probes
   // (measured at the configs[2] shape, 10^6 queries x 32 tables against 1.3e8 bucket slots -- a ratio of 4:
   // 11.3 ms for the whole probe + segment chain with the sort, 15.0 with the counting sort)
-  bool seg_sparse = (uint64_t)h->nb_total > 2ull * nql;
-  // bucket partition: 1/n_parts of the probes find their bucket; those are compacted before the grouping,
-  // which then is the sort of the probes whatever the number of buckets
-  const bool parted = h->bucket_parts > 1 && h->self_first == HS_NO_SELF;  // (searches only, not the self-joins)
-  if (parted) seg_sparse = true;
-  uint32_t nqs = nql;  // probes the grouping works on (bucket partition: the ones that found a bucket)
-  const uint32_t* owned_list = nullptr;  // bucket partition: the probes of this part, ascending (device)
+  p.parted = p.use_join && h->bucket_parts > 1 && c.self_first == HS_NO_SELF;  // (searches only)
+  p.seg_sparse = p.parted || (h->knobs.seg_mode ? h->knobs.seg_mode == 1 : (uint64_t)h->nb_total > 2ull * nq * h->p.L);
+  p.all_joined = h->join_min_q == 1 && h->join_min_m == 1;
+  // work items: one wave's 128 members for the wave-independent int8 join, 512 otherwise
+  p.jm = p.use_i8 ? hs_join8_members_per_item(k, p.wide) : HS_JM_BLOCK;
+  // k <= 25 with 4-column rows: segments probed by at most HS_JR_MAXQ queries of the batch go to the
+  // query-resident kernel (hs_join8r_kernel), as the tail of the item list
+  p.resident_stale = p.use_join && m.resident_nq && (nq > 2 * m.resident_nq || 2 * nq < m.resident_nq);
+  const double share = p.resident_stale ? -1.0 : m.resident_share;
+  p.use_r = p.use_i8 && !p.wide && k <= 25 && h->alphabet <= HS_JR_MAX_ALPHABET && !h->knobs.no_join_r &&
+            (h->knobs.force_join_r || share < 0.0 || share >= 0.5 || m.resident_age >= 64);
+  // No host round trip when the int8 join takes every segment and the previous batch left a
+  // capacity hint: the item count stays on the device (item_off[nqs]); join legality and the
+  // capacity are checked with the batch's final read-back, a violation repeats the batch the
+  // slow way.  Otherwise one round trip: join legality, item count, streaming slices.
+  p.async_items = allow_async && p.use_i8 && p.all_joined && m.item_cap_hint && !h->knobs.sync_items;
+  p.item_cap = p.async_items ? m.item_cap_hint : 0;
+  // the batch orders its hits itself (bucket by query, no sort, no host count); not tried again at a
+  // radius at which the previous batch had a query with too many hits for it (the attempt costs 10 % of
+  // such a batch -- k = 15 at the C2 sizes, 545 hits per query)
+  p.order_here = ordered_out && !h->knobs.sort_hits && !(m.order_failed && m.order_failed_R == c.R);
+  p.xcd_run = h->knobs.join_xcd_run;
+  return p;
+}
+
+// One batch's queries and the device arrays and counts the stages hand on to each other.
+struct Batch {
+  uint32_t nq = 0, q_base = 0, nql = 0;
+  uint32_t nqs = 0;                  // probes the grouping works on (bucket partition: the ones that found a bucket)
+  double r2 = 0.0;                   // R * R (motif_both_points.cpp:204)
+  const double* centers = nullptr;   // the call's centres, or the embedded query codes
+  uint64_t* d_cand = nullptr;
+  const uint8_t* qcodes = nullptr;   // from-codes batches: the codes every per-query quantity comes from
+  const uint32_t* owned = nullptr;   // bucket partition: the probes of this part, ascending (device)
   uint32_t n_owned = 0;
-  if (h->knobs.seg_mode) seg_sparse = h->knobs.seg_mode == 1;
-  const bool self_codes = h->self_first != HS_NO_SELF && !brute && use_i8 && self_codes_ok(h, R);
-  const uint8_t* d_qcodes =
-      self_codes ? h->codes.as<uint8_t>() + ((uint64_t)h->self_first + q_base) * k : nullptr;
-  // Queries given as codes (hs_query_codes): a checked copy first (a code outside the alphabet is
-  // reported with the batch's counters and replaced by 0, so no kernel indexes a table with it).  When
-  // every filter on the way works from codes (self_codes_ok: the int8 join and its thin-segment filter)
-  // no embedded centre exists at any point: 25 bytes per query instead of 1600 -- hash, query rows and
-  // the exact decision all read the table rows the DB's k-mers read.  Otherwise the codes are embedded
-  // here, on the device, and the batch runs as for any other centres.
-  bool ext_codes = false;
-  if (d_qcodes_ext) {
-    HS_HIP(h, h->qcodes_buf.reserve(std::max<size_t>(16, (size_t)nq * k)));
-    HS_HIP(h, hs_launch_check_codes(d_qcodes_ext, (uint64_t)nq * k, h->alphabet, h->qcodes_buf.as<uint8_t>(),
-                                    d_cnt + HS_CNT_BAD_QUERY_CODE, h->stream));
-    if (!brute && use_i8 && self_codes_ok(h, R)) {
-      ext_codes = true;
-      d_qcodes = h->qcodes_buf.as<uint8_t>();
+  uint32_t n_items = 0, n_slices = 1;
+};
+
+// The join filter's query rows, on stream s: from the codes, int8 from the centres, or fp16
+static hipError_t launch_qrows(hs_handle* h, const BatchPlan& p, const Batch& b, hipStream_t s) {
+  const int k = (int)h->p.k;
+  uint32_t* const d_unsafe = h->counters.as<uint32_t>() + 8;
+  if (p.self_codes || p.ext_codes)
+    return hs_launch_qprep8_codes(b.qcodes, b.nq, k, p.wide, b.r2, h->coords.as<double>(), h->jtab8.p,
+                                  h->jtab8.as<char>() + 1024, h->jtab8.as<char>() + 1536, h->jtab8.as<float>() + 128,
+                                  h->c16.p, p.refine ? h->c8b.p : nullptr, s);
+  if (p.use_i8)
+    return hs_launch_qprep8(b.centers, b.nq, k, p.wide, b.r2, h->jtab8.as<float>() + 128, h->c16.p, d_unsafe,
+                            p.refine ? h->c8b.p : nullptr, s);
+  return hs_launch_qprep(b.centers, b.nq, k, b.r2, h->c16.p, d_unsafe, s);
+}
+
+// The query rows gathered into segment order (c16s)
+static hipError_t gather_qrows(hs_handle* h, const BatchPlan& p, const Batch& b) {
+  if (p.use_i8)
+    return hs_launch_gather_c8t(h->c16.p, h->sorted_ql.as<uint32_t>(), h->seg_qoff.as<uint32_t>(),
+                                h->seg_of.as<uint32_t>(), b.nqs, (int)h->p.L, (int)h->p.k, p.wide, h->c16s.p, h->stream);
+  return hs_launch_gather_c16(h->c16.p, h->sorted_ql.as<uint32_t>(), b.nqs, (int)h->p.L, h->c16s.p, h->stream);
+}
+
+// The probe of the batch's (query, table) pairs (bucket partition: the part's listed ones).  With a join
+// ahead it also numbers each probe's bucket, and ranks it inside for the counting sort (hs_launch_seg_group).
+static hipError_t launch_probe(hs_handle* h, const QueryCall& c, const BatchPlan& p, const Batch& b) {
+  uint32_t* const qbucket = p.use_join ? h->seg_keys.as<uint32_t>() : nullptr;
+  uint32_t* const bucket_count = p.use_join && !p.seg_sparse ? h->bucket_work.as<uint32_t>() : nullptr;
+  uint32_t* const qrank = bucket_count ? qbucket + ((size_t)b.nql + 1) : nullptr;
+  unsigned long long* const d_cand_total = reinterpret_cast<unsigned long long*>(h->counters.as<uint32_t>() + 2);
+  if (p.self_codes)
+    return hs_launch_self_probe(h->tabs, c.self_first + b.q_base, b.nq, (int)h->p.L, h->qstart.as<uint32_t>(),
+                                h->qcount.as<uint32_t>(), h->nslices.as<uint32_t>(), b.d_cand, d_cand_total,
+                                h->dir_base.as<uint32_t>(), h->nb_total, bucket_count, qbucket, qrank, h->stream);
+  return hs_launch_probe(probe_tabs(h, c, b.q_base, b.owned, b.n_owned), h->qints.as<int32_t>(), b.nq, (int)h->p.K,
+                         (int)h->p.L, h->key_seed, h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(),
+                         h->nslices.as<uint32_t>(), b.d_cand, d_cand_total, h->probe_slow.as<uint32_t>(),
+                         h->dir_base.as<uint32_t>(), h->nb_total, bucket_count, qbucket, qrank, h->stream);
+}
+
+// Work items of the plan's size from the segments, the resident kernel's class as their tail
+static hs_status cut_plan_items(hs_handle* h, const BatchPlan& p, const Batch& b) {
+  unsigned long long* const d_jstats = reinterpret_cast<unsigned long long*>(h->counters.as<uint32_t>() + 10);
+  return cut_items(h, b.nqs, p.jm, d_jstats, p.use_r ? HS_JR_MAXQ : 0u, b.nql);
+}
+
+// Where every probe's slices start in the streaming filter's grid (every segment joined -- the default --:
+// all slice counts are zero by now, and so is their scan)
+static hipError_t slice_offsets(hs_handle* h, const BatchPlan& p, const Batch& b) {
+  if (p.use_join && p.all_joined) return hipMemsetAsync(h->slice_off.p, 0, ((size_t)b.nql + 1) * 4, h->stream);
+  return hs_exclusive_scan_u32(h->temp.p, h->temp.cap, h->nslices.as<uint32_t>(), h->slice_off.as<uint32_t>(),
+                               (size_t)b.nql + 1, h->stream);
+}
+
+// Stage 1: the queries.  Given as codes (hs_query_codes): a checked copy first (a code outside the alphabet
+// is reported with the batch's counters and replaced by 0, so no kernel indexes a table with it).  When
+// every filter on the way works from codes (self_codes_ok) no embedded centre exists at any point: 25 bytes
+// per query instead of 1600 -- hash, query rows and the exact decision all read the table rows the DB's
+// k-mers read.  Otherwise the codes are embedded here, on the device, and the batch runs as for any other
+// centres.  The join filter's query rows depend on the queries only: quantised on the side stream while
+// the main stream hashes and probes (both passes stream the same 8d bytes per query).
+static hs_status prepare_queries(hs_handle* h, const QueryCall& c, const BatchPlan& p, Batch& b) {
+  const int k = (int)h->p.k;
+  if (p.wide) HS_CHECK(ensure_rec8w(h));
+  if (p.self_codes) b.qcodes = h->codes.as<uint8_t>() + ((uint64_t)c.self_first + b.q_base) * k;
+  if (c.codes) {
+    HS_HIP(h, h->qcodes_buf.reserve(std::max<size_t>(16, (size_t)b.nq * k)));
+    HS_HIP(h, hs_launch_check_codes(c.codes, (uint64_t)b.nq * k, h->alphabet, h->qcodes_buf.as<uint8_t>(),
+                                    h->counters.as<uint32_t>() + HS_CNT_BAD_QUERY_CODE, h->stream));
+    if (p.ext_codes) {
+      b.qcodes = h->qcodes_buf.as<uint8_t>();
     } else {
-      HS_HIP(h, h->qembed.reserve(std::max<size_t>(16, (size_t)nq * h->d * 8)));
-      HS_HIP(h, hs_launch_embed(h->qcodes_buf.as<uint8_t>(), nq, k, h->coords.as<double>(), h->qembed.as<double>(),
-                                h->stream));
-      d_centers = h->qembed.as<double>();
+      HS_HIP(h, h->qembed.reserve(std::max<size_t>(16, (size_t)b.nq * h->d * 8)));
+      HS_HIP(h, hs_launch_embed(h->qcodes_buf.as<uint8_t>(), b.nq, k, h->coords.as<double>(),
+                                h->qembed.as<double>(), h->stream));
+      b.centers = h->qembed.as<double>();
     }
   }
-  const bool from_codes = self_codes || ext_codes;  // no centres: every per-query quantity from the codes
-  if (use_join) {
-    // the join filter's query rows depend on the centres only: quantised on the side stream while
-    // the main stream hashes and probes (both passes stream the same 8d bytes per query)
-    HS_HIP(h, h->c16.reserve((size_t)nq * 208 * 2));
-    if (refine) HS_HIP(h, h->c8b.reserve((size_t)nq * hs_join8_row_bytes(k, wide)));
+  if (p.use_join) {
+    HS_HIP(h, h->c16.reserve((size_t)b.nq * 208 * 2));
+    if (p.refine) HS_HIP(h, h->c8b.reserve((size_t)b.nq * hs_join8_row_bytes(k, p.wide)));
     HS_HIP(h, hipEventRecord(h->evx[EV_FORK], h->stream));
     HS_HIP(h, hipStreamWaitEvent(h->stream2, h->evx[EV_FORK], 0));
-    if (from_codes)
-      HS_HIP(h, hs_launch_qprep8_codes(d_qcodes, nq, k, wide, r2, h->coords.as<double>(), h->jtab8.p,
-                                       h->jtab8.as<char>() + 1024, h->jtab8.as<char>() + 1536,
-                                       h->jtab8.as<float>() + 128, h->c16.p, refine ? h->c8b.p : nullptr,
-                                       h->stream2));
-    else if (use_i8)
-      HS_HIP(h, hs_launch_qprep8(d_centers, nq, k, wide, r2, h->jtab8.as<float>() + 128, h->c16.p, d_unsafe,
-                                 refine ? h->c8b.p : nullptr, h->stream2));
-    else
-      HS_HIP(h, hs_launch_qprep(d_centers, nq, k, r2, h->c16.p, d_unsafe, h->stream2));
+    HS_HIP(h, launch_qrows(h, p, b, h->stream2));
     HS_HIP(h, hipEventRecord(h->evx[EV_JOIN], h->stream2));
   }
-  if (!brute) {
-    HS_HIP(h, h->qints.reserve((size_t)nq * h->LK * 4));
-    HS_HIP(h, h->qstart.reserve(((size_t)nql + HS_QRANGE_PAD) * 4));
-    HS_HIP(h, h->qcount.reserve(((size_t)nql + HS_QRANGE_PAD) * 4));
-    HS_HIP(h, h->nslices.reserve(((size_t)nql + 1) * 4));
-    HS_HIP(h, h->probe_slow.reserve(((size_t)nql + 1) * 4));
-    HS_HIP(h, h->slice_off.reserve(((size_t)nql + 1) * 4));
-    HS_HIP(h, h->temp.reserve(hs_scan_u32_temp((size_t)nql + 1) + 256));
-    if (ext_codes)
-      HS_CHECK(hash_dispatch(h, d_qcodes, nullptr, nq, -1, h->qints.as<int32_t>(), h->LK, 2, h->stream));
-    else if (!self_codes)
-      HS_CHECK(hash_dispatch(h, nullptr, d_centers, nq, -1, h->qints.as<int32_t>(), h->LK, 2, h->stream));
-  }
+  return HS_OK;
+}
+
+// Stage 2: hash and probe.  Bucket partition: the part's own probes (by their bucket ints alone) are listed
+// first, and only those -- 1 / n_parts of the batch -- pay for a fingerprint and a walk of the directory.
+static hs_status hash_and_probe(hs_handle* h, const QueryCall& c, const BatchPlan& p, Batch& b) {
+  const size_t n1 = (size_t)b.nql + 1;
+  HS_HIP(h, h->qints.reserve((size_t)b.nq * h->LK * 4));
+  HS_HIP(h, h->qstart.reserve(((size_t)b.nql + HS_QRANGE_PAD) * 4));
+  HS_HIP(h, h->qcount.reserve(((size_t)b.nql + HS_QRANGE_PAD) * 4));
+  for (DevBuf* d : {&h->nslices, &h->probe_slow, &h->slice_off}) HS_HIP(h, d->reserve(n1 * 4));
+  HS_HIP(h, h->temp.reserve(hs_scan_u32_temp(n1) + 256));
+  if (p.ext_codes)
+    HS_CHECK(hash_dispatch(h, b.qcodes, nullptr, b.nq, -1, h->qints.as<int32_t>(), h->LK, 2, h->stream));
+  else if (!p.self_codes)
+    HS_CHECK(hash_dispatch(h, nullptr, b.centers, b.nq, -1, h->qints.as<int32_t>(), h->LK, 2, h->stream));
   HS_HIP(h, hipEventRecord(h->ev[1], h->stream));
-  // Bucket join when fp16 / int8 can carry the data (decided above); the streaming kernel otherwise
-  // (and for brute force).  Both append survivors to one list in front of the same exact decision.
-  if (!brute) {
-    // with a join ahead, the probe also numbers each probe's bucket and ranks it inside (the
-    // grouping of the probes by bucket is then a counting sort: hs_launch_seg_group)
-    uint32_t *bucket_count = nullptr, *qbucket = nullptr, *qrank = nullptr;
-    if (use_join) {
-      HS_HIP(h, h->seg_keys.reserve(((size_t)nql + 1) * 8));
-      qbucket = h->seg_keys.as<uint32_t>();
-      if (seg_sparse) {
-        // buckets far outnumber probes: the probes are sorted on their bucket number instead (no
-        // ranks, no pass over the bucket slots: hs_launch_seg_group_sparse)
-        HS_HIP(h, h->bucket_work.reserve(4 * ((size_t)nql + 1) * 4));
-      } else {
-        HS_HIP(h, h->bucket_work.reserve(4 * ((size_t)h->nb_total + 2) * 4));
-        bucket_count = h->bucket_work.as<uint32_t>();
-        qrank = qbucket + ((size_t)nql + 1);
-      }
-    }
-    HS_HIP(h, hs_launch_set_u32(h->nslices.as<uint32_t>() + nql, 0u, h->stream));
-    if (self_codes)
-      HS_HIP(h, hs_launch_self_probe(h->tabs, h->self_first + q_base, nq, L, h->qstart.as<uint32_t>(),
-                                     h->qcount.as<uint32_t>(), h->nslices.as<uint32_t>(), d_cand,
-                                     reinterpret_cast<unsigned long long*>(d_cnt + 2),
-                                     h->dir_base.as<uint32_t>(), h->nb_total, bucket_count, qbucket, qrank,
-                                     h->stream));
-    else {
-      // bucket partition with a join ahead: the part's own probes (by their bucket ints alone) are listed first,
-      // and only those -- 1 / n_parts of the batch -- pay for a fingerprint and a walk of the directory
-      if (parted && use_join) {
-        const size_t n1 = (size_t)nql + 1;
-        HS_HIP(h, h->part_work.reserve(5 * n1 * 4));
-        uint32_t* const pw = h->part_work.as<uint32_t>();
-        HS_HIP(h, hs_launch_part_owned(probe_tabs(h, q_base), h->qints.as<int32_t>(), nq, K, L, h->nb_total, pw,
-                                       h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(), h->nslices.as<uint32_t>(),
-                                       d_cand, qbucket, h->stream));
-        HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, pw, pw + n1, n1, h->stream));
-        HS_HIP(h, hs_launch_flagged_list(pw, pw + n1, nql, pw + 4 * n1, h->stream));
-        HS_HIP(h, hipMemcpyAsync(&n_owned, pw + n1 + nql, 4, hipMemcpyDeviceToHost, h->stream));
-        HS_HIP(h, hipStreamSynchronize(h->stream));
-        owned_list = pw + 4 * n1;
-      }
-      HS_HIP(h, hs_launch_probe(probe_tabs(h, q_base, owned_list, n_owned), h->qints.as<int32_t>(), nq, K, L, h->key_seed,
-                                h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(),
-                                h->nslices.as<uint32_t>(), d_cand,
-                                reinterpret_cast<unsigned long long*>(d_cnt + 2),
-                                h->probe_slow.as<uint32_t>(), h->dir_base.as<uint32_t>(), h->nb_total,
-                                bucket_count, qbucket, qrank, h->stream));
-    }
-  }
-  unsigned long long* d_jstats = reinterpret_cast<unsigned long long*>(d_cnt + 10);
-  uint32_t n_items = 0, n_slices = 1, jm = HS_JM_BLOCK;
-  bool async_items = false, use_r = false;
-  const int seg_shift = seg_shift_of(h);
-  if (use_join) {
-    const size_t n1 = (size_t)nql + 1;
-    HS_HIP(h, h->c16s.reserve(((size_t)nql + 64) * 208 * 2));
+  if (p.use_join) {
     HS_HIP(h, h->seg_keys.reserve(n1 * 8));
-    HS_HIP(h, h->seg_keys_sorted.reserve(n1 * 8));
-    HS_HIP(h, h->seg_vals.reserve(n1 * 4));
-    HS_HIP(h, h->sorted_ql.reserve(n1 * 4));
-    HS_HIP(h, h->seg_key.reserve(n1 * 8));
-    HS_HIP(h, h->seg_cnt.reserve(n1 * 4));
-    HS_HIP(h, h->seg_qoff.reserve(n1 * 4));
-    HS_HIP(h, h->seg_items.reserve(n1 * 4));
-    HS_HIP(h, h->item_off.reserve(n1 * 4));
-    HS_HIP(h, h->seg_n.reserve(64));
-    HS_HIP(h, h->seg_of.reserve(n1 * 4));
-    HS_HIP(h, h->temp.reserve(std::max(hs_scan_u32_temp(n1), hs_scan_u32_temp((size_t)h->nb_total + 2)) + 256));
-    // (the query rows of the join filter were quantised on the side stream, beside hash and probe)
-    HS_HIP(h, hipStreamWaitEvent(h->stream, h->evx[EV_JOIN], 0));
-    HS_HIP(h, hipMemsetAsync(h->seg_cnt.p, 0, n1 * 4, h->stream));
-    if (seg_sparse) {
-      HS_HIP(h, h->temp.reserve(std::max(hs_sort_pairs_u32_u32_temp(nql), hs_scan_u32_temp(n1)) + 256));
-      const uint32_t* keys_in = h->seg_keys.as<uint32_t>();
-      const uint32_t* probes_in = nullptr;
-      if (parted) {
-        HS_HIP(h, h->part_work.reserve(5 * n1 * 4));
-        uint32_t* const pw = h->part_work.as<uint32_t>();
-        const uint32_t n_cand = owned_list ? n_owned : nql;  // (the part's own probes, listed ahead of the probe kernel)
-        uint32_t n_found = 0;
-        if (n_cand) {
-          HS_HIP(h, hs_launch_found_probes(h->seg_keys.as<uint32_t>(), n_cand, h->nb_total, h->temp.p, h->temp.cap, pw,
-                                           pw + n1, pw + 2 * n1, pw + 3 * n1, h->stream, owned_list));
-          HS_HIP(h, hipMemcpyAsync(&n_found, pw + n1 + n_cand, 4, hipMemcpyDeviceToHost, h->stream));
-        }
-        HS_HIP(h, hipStreamSynchronize(h->stream));
-        if (n_found) {  // (none at all: the batch goes on as one of probes that found nothing)
-          nqs = n_found;
-          keys_in = pw + 2 * n1;
-          probes_in = pw + 3 * n1;
-        }
-      }
-      HS_HIP(h, hs_launch_seg_group_sparse(h->tabs, h->dir_base.as<uint32_t>(), L, seg_shift, h->nb_total,
-                                           h->temp.p, h->temp.cap, keys_in,
-                                           h->seg_keys.as<uint32_t>() + n1, h->seg_vals.as<uint32_t>(),
-                                           h->bucket_work.as<uint32_t>(), nqs, h->sorted_ql.as<uint32_t>(),
-                                           h->seg_key.as<uint64_t>(), h->seg_cnt.as<uint32_t>(),
-                                           h->seg_n.as<uint32_t>(), h->seg_of.as<uint32_t>(), h->stream, probes_in));
-    } else
-    HS_HIP(h, hs_launch_seg_group(h->tabs, h->dir_base.as<uint32_t>(), L, seg_shift, h->nb_total,
-                                  h->bucket_work.as<uint32_t>(),
-                                  h->bucket_work.as<uint32_t>() + ((size_t)h->nb_total + 2), h->temp.p,
-                                  h->temp.cap, h->seg_keys.as<uint32_t>(),
-                                  h->seg_keys.as<uint32_t>() + n1, nql, h->sorted_ql.as<uint32_t>(),
-                                  h->seg_key.as<uint64_t>(), h->seg_cnt.as<uint32_t>(),
-                                  h->seg_n.as<uint32_t>(), h->seg_of.as<uint32_t>(), h->stream));
-    HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, h->seg_cnt.as<uint32_t>(),
-                                    h->seg_qoff.as<uint32_t>(), (size_t)nqs + 1, h->stream));
-    // work items: one wave's 128 members for the wave-independent int8 join, 512 otherwise
-    jm = use_i8 ? hs_join8_members_per_item(k, wide) : HS_JM_BLOCK;
-    // k <= 25 with 4-column rows: segments probed by at most HS_JR_MAXQ queries of the batch go to the
-    // query-resident kernel (hs_join8r_kernel), as the tail of the item list
-    if (h->resident_nq && (nq > 2 * h->resident_nq || 2 * nq < h->resident_nq)) h->resident_share = -1.0;
-    use_r = use_i8 && !wide && k <= 25 && h->alphabet <= HS_JR_MAX_ALPHABET && !h->knobs.no_join_r &&
-            (h->knobs.force_join_r || h->resident_share < 0.0 || h->resident_share >= 0.5 || h->resident_age >= 64);
-    HS_CHECK(cut_items(h, nqs, jm, d_jstats, use_r ? HS_JR_MAXQ : 0u, nql));
-    if (use_i8)
-      HS_HIP(h, hs_launch_gather_c8t(h->c16.p, h->sorted_ql.as<uint32_t>(), h->seg_qoff.as<uint32_t>(),
-                                     h->seg_of.as<uint32_t>(), nqs, L, k, wide, h->c16s.p, h->stream));
-    else
-      HS_HIP(h, hs_launch_gather_c16(h->c16.p, h->sorted_ql.as<uint32_t>(), nqs, L, h->c16s.p, h->stream));
+    // (the sort of the probes needs no ranks and no pass over the bucket slots: hs_launch_seg_group_sparse)
+    HS_HIP(h, h->bucket_work.reserve(4 * (p.seg_sparse ? n1 : (size_t)h->nb_total + 2) * 4));
   }
-  if (!brute) {
-    // (every segment joined -- the default --: all slice counts are zero by now, and so is their scan)
-    if (use_join && h->join_min_q == 1 && h->join_min_m == 1)
-      HS_HIP(h, hipMemsetAsync(h->slice_off.p, 0, ((size_t)nql + 1) * 4, h->stream));
-    else
-      HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, h->nslices.as<uint32_t>(),
-                                      h->slice_off.as<uint32_t>(), (size_t)nql + 1, h->stream));
-    // No host round trip when the int8 join takes every segment and the previous batch left a
-    // capacity hint: the item count stays on the device (item_off[nql]); join legality and the
-    // capacity are checked with the batch's final read-back, a violation repeats the batch the
-    // slow way.  Otherwise one round trip: join legality, item count, streaming slices.
-    async_items = allow_async && use_i8 && h->join_min_q == 1 && h->join_min_m == 1 && h->item_cap_hint &&
-                  !h->knobs.sync_items;
-    uint32_t unsafe = 0;
-    if (async_items) {
-      n_items = h->item_cap_hint;
-      n_slices = 0;
-    } else if (use_join) {
-      HS_HIP(h, hipMemcpyAsync(&unsafe, d_unsafe, 4, hipMemcpyDeviceToHost, h->stream));
-      HS_HIP(h, hipMemcpyAsync(&n_items, h->item_off.as<uint32_t>() + nqs, 4, hipMemcpyDeviceToHost,
-                               h->stream));
-    }
-    if (!async_items) {
-      HS_HIP(h, hipMemcpyAsync(&n_slices, h->slice_off.as<uint32_t>() + nql, 4, hipMemcpyDeviceToHost,
-                               h->stream));
+  HS_HIP(h, hs_launch_set_u32(h->nslices.as<uint32_t>() + b.nql, 0u, h->stream));
+  if (p.parted) {
+    HS_HIP(h, h->part_work.reserve(5 * n1 * 4));
+    uint32_t* const pw = h->part_work.as<uint32_t>();
+    HS_HIP(h, hs_launch_part_owned(probe_tabs(h, c, b.q_base), h->qints.as<int32_t>(), b.nq, (int)h->p.K,
+                                   (int)h->p.L, h->nb_total, pw, h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(),
+                                   h->nslices.as<uint32_t>(), b.d_cand, h->seg_keys.as<uint32_t>(), h->stream));
+    HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, pw, pw + n1, n1, h->stream));
+    HS_HIP(h, hs_launch_flagged_list(pw, pw + n1, b.nql, pw + 4 * n1, h->stream));
+    HS_HIP(h, hipMemcpyAsync(&b.n_owned, pw + n1 + b.nql, 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    b.owned = pw + 4 * n1;
+  }
+  HS_HIP(h, launch_probe(h, c, p, b));
+  return HS_OK;
+}
+
+// Stage 3: the probes grouped by bucket into segments, the segments cut into work items, the query rows
+// gathered in segment order.  Bucket partition: only the part's probes that found a bucket are grouped.
+static hs_status group_segments(hs_handle* h, const BatchPlan& p, Batch& b) {
+  if (!p.use_join) return HS_OK;
+  const size_t n1 = (size_t)b.nql + 1;
+  HS_HIP(h, h->c16s.reserve(((size_t)b.nql + 64) * 208 * 2));
+  for (DevBuf* d : {&h->seg_keys, &h->seg_keys_sorted, &h->seg_key}) HS_HIP(h, d->reserve(n1 * 8));
+  for (DevBuf* d : {&h->seg_vals, &h->sorted_ql, &h->seg_cnt, &h->seg_qoff, &h->seg_items, &h->item_off, &h->seg_of})
+    HS_HIP(h, d->reserve(n1 * 4));
+  HS_HIP(h, h->seg_n.reserve(64));
+  HS_HIP(h, h->temp.reserve(std::max(hs_scan_u32_temp(n1), hs_scan_u32_temp((size_t)h->nb_total + 2)) + 256));
+  // (the query rows of the join filter were quantised on the side stream, beside hash and probe)
+  HS_HIP(h, hipStreamWaitEvent(h->stream, h->evx[EV_JOIN], 0));
+  HS_HIP(h, hipMemsetAsync(h->seg_cnt.p, 0, n1 * 4, h->stream));
+  const int L = (int)h->p.L, seg_shift = seg_shift_of(h);
+  if (p.seg_sparse) {
+    HS_HIP(h, h->temp.reserve(std::max(hs_sort_pairs_u32_u32_temp(b.nql), hs_scan_u32_temp(n1)) + 256));
+    const uint32_t* keys_in = h->seg_keys.as<uint32_t>();
+    const uint32_t* probes_in = nullptr;
+    if (p.parted) {
+      uint32_t* const pw = h->part_work.as<uint32_t>();
+      uint32_t n_found = 0;
+      if (b.n_owned) {
+        HS_HIP(h, hs_launch_found_probes(h->seg_keys.as<uint32_t>(), b.n_owned, h->nb_total, h->temp.p, h->temp.cap,
+                                         pw, pw + n1, pw + 2 * n1, pw + 3 * n1, h->stream, b.owned));
+        HS_HIP(h, hipMemcpyAsync(&n_found, pw + n1 + b.n_owned, 4, hipMemcpyDeviceToHost, h->stream));
+      }
       HS_HIP(h, hipStreamSynchronize(h->stream));
+      if (n_found) {  // (none at all: the batch goes on as one of probes that found nothing)
+        b.nqs = n_found;
+        keys_in = pw + 2 * n1;
+        probes_in = pw + 3 * n1;
+      }
     }
-    if (from_codes && unsafe) return fail(h, HS_ERR_STATE, "queries from codes: a query row marked unsafe");
-    if (use_i8 && unsafe && !can16) {
-      // a query int8 cannot carry and no fp16 form for this k: the batch streams (below)
-      use_i8 = false;
-    } else if (use_i8 && unsafe) {
-      // a query int8 cannot carry: redo the query rows in fp16 (segments and items are shared)
-      use_i8 = false;
-      HS_HIP(h, hipMemsetAsync(d_unsafe, 0, 4, h->stream));
-      HS_HIP(h, hs_launch_qprep(d_centers, nq, k, r2, h->c16.p, d_unsafe, h->stream));
-      HS_HIP(h, hs_launch_gather_c16(h->c16.p, h->sorted_ql.as<uint32_t>(), nqs, L, h->c16s.p, h->stream));
-      HS_HIP(h, hipMemcpyAsync(&unsafe, d_unsafe, 4, hipMemcpyDeviceToHost, h->stream));
-      if (jm != HS_JM_BLOCK) {  // the fp16 kernel works on 512-member items: cut the segments again
-        jm = HS_JM_BLOCK;
-        use_r = false;
-        HS_HIP(h, hipMemsetAsync(d_jstats, 0, 16, h->stream));
-        HS_CHECK(cut_items(h, nqs, jm, d_jstats, 0u, nql));
-        HS_HIP(h, hipMemcpyAsync(&n_items, h->item_off.as<uint32_t>() + nqs, 4, hipMemcpyDeviceToHost,
+    HS_HIP(h, hs_launch_seg_group_sparse(h->tabs, h->dir_base.as<uint32_t>(), L, seg_shift, h->nb_total, h->temp.p,
+                                         h->temp.cap, keys_in, h->seg_keys.as<uint32_t>() + n1,
+                                         h->seg_vals.as<uint32_t>(), h->bucket_work.as<uint32_t>(), b.nqs,
+                                         h->sorted_ql.as<uint32_t>(), h->seg_key.as<uint64_t>(),
+                                         h->seg_cnt.as<uint32_t>(), h->seg_n.as<uint32_t>(), h->seg_of.as<uint32_t>(),
+                                         h->stream, probes_in));
+  } else {
+    HS_HIP(h, hs_launch_seg_group(h->tabs, h->dir_base.as<uint32_t>(), L, seg_shift, h->nb_total,
+                                  h->bucket_work.as<uint32_t>(), h->bucket_work.as<uint32_t>() + ((size_t)h->nb_total + 2),
+                                  h->temp.p, h->temp.cap, h->seg_keys.as<uint32_t>(), h->seg_keys.as<uint32_t>() + n1,
+                                  b.nql, h->sorted_ql.as<uint32_t>(), h->seg_key.as<uint64_t>(),
+                                  h->seg_cnt.as<uint32_t>(), h->seg_n.as<uint32_t>(), h->seg_of.as<uint32_t>(),
+                                  h->stream));
+  }
+  HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, h->seg_cnt.as<uint32_t>(), h->seg_qoff.as<uint32_t>(),
+                                  (size_t)b.nqs + 1, h->stream));
+  HS_CHECK(cut_plan_items(h, p, b));
+  HS_HIP(h, gather_qrows(h, p, b));
+  return HS_OK;
+}
+
+// A query row the plan's form cannot carry (found by the item read-back): the batch goes on one form down --
+// int8 -> fp16 (the query rows again; the items again if their size changes), fp16 -> the streaming filter
+// (the probes again, without the join's outputs, and their slices) -- re-issuing only what the new form needs.
+static hs_status demote(hs_handle* h, const QueryCall& c, BatchPlan& p, Batch& b, uint32_t unsafe) {
+  if (p.self_codes || p.ext_codes) return fail(h, HS_ERR_STATE, "queries from codes: a query row marked unsafe");
+  uint32_t* const d_cnt = h->counters.as<uint32_t>();
+  if (p.use_i8) {
+    p.use_i8 = p.refine = false;
+    if (p.can16) {
+      HS_HIP(h, hipMemsetAsync(d_cnt + 8, 0, 4, h->stream));
+      HS_HIP(h, launch_qrows(h, p, b, h->stream));
+      HS_HIP(h, gather_qrows(h, p, b));
+      HS_HIP(h, hipMemcpyAsync(&unsafe, d_cnt + 8, 4, hipMemcpyDeviceToHost, h->stream));
+      if (p.jm != HS_JM_BLOCK) {  // the fp16 kernel works on 512-member items: cut the segments again
+        p.jm = HS_JM_BLOCK;
+        p.use_r = false;
+        HS_HIP(h, hipMemsetAsync(d_cnt + 10, 0, 16, h->stream));
+        HS_CHECK(cut_plan_items(h, p, b));
+        HS_HIP(h, hipMemcpyAsync(&b.n_items, h->item_off.as<uint32_t>() + b.nqs, 4, hipMemcpyDeviceToHost,
                                  h->stream));
       }
       HS_HIP(h, hipStreamSynchronize(h->stream));
     }
-    if (use_join && unsafe) {
-      // a query fp16 cannot carry: this batch streams entirely (re-derive the slice counts)
-      use_join = false;
-      n_items = 0;
-      HS_HIP(h, hipMemsetAsync(d_cnt + 2, 0, 8, h->stream));
-      HS_HIP(h, hs_launch_probe(probe_tabs(h, q_base), h->qints.as<int32_t>(), nq, K, L, h->key_seed,
-                                h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(),
-                                h->nslices.as<uint32_t>(), d_cand,
-                                reinterpret_cast<unsigned long long*>(d_cnt + 2),
-                                h->probe_slow.as<uint32_t>(), nullptr, 0, nullptr, nullptr, nullptr,
-                                h->stream));
-      HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, h->nslices.as<uint32_t>(),
-                                      h->slice_off.as<uint32_t>(), (size_t)nql + 1, h->stream));
-      n_slices = 1;
+  }
+  if (unsafe) {
+    p.use_join = false;
+    b.n_items = 0;
+    b.owned = nullptr;  // (every probe again)
+    b.n_owned = 0;
+    HS_HIP(h, hipMemsetAsync(d_cnt + 2, 0, 8, h->stream));
+    HS_HIP(h, launch_probe(h, c, p, b));
+    HS_HIP(h, slice_offsets(h, p, b));
+    b.n_slices = 1;
+  }
+  return HS_OK;
+}
+
+// Stage 4: the item count, join legality and the streaming slices, in one round trip -- or none when the
+// plan leaves the item count on the device -- then the work item descriptors.
+static hs_status read_items(hs_handle* h, const QueryCall& c, BatchPlan& p, Batch& b) {
+  HS_HIP(h, slice_offsets(h, p, b));
+  uint32_t unsafe = 0;
+  if (p.async_items) {
+    b.n_items = p.item_cap;
+    b.n_slices = 0;
+  } else {
+    if (p.use_join) {
+      HS_HIP(h, hipMemcpyAsync(&unsafe, h->counters.as<uint32_t>() + 8, 4, hipMemcpyDeviceToHost, h->stream));
+      HS_HIP(h, hipMemcpyAsync(&b.n_items, h->item_off.as<uint32_t>() + b.nqs, 4, hipMemcpyDeviceToHost, h->stream));
     }
-    if (n_items) {
-      HS_HIP(h, h->item_desc.reserve((size_t)n_items * 32));
-      HS_HIP(h, hs_launch_item_desc(h->tabs, h->seg_key.as<uint64_t>(), h->seg_cnt.as<uint32_t>(),
-                                    h->seg_qoff.as<uint32_t>(), h->item_off.as<uint32_t>(), nqs,
-                                    h->sorted_ql.as<uint32_t>(), h->qcount.as<uint32_t>(), n_items, jm,
-                                    seg_shift, h->seg_vals.as<uint32_t>(), h->PW,
-                                    async_items ? h->item_off.as<uint32_t>() + nqs : nullptr,
-                                    h->item_desc.as<uint4>(), h->stream));
-    }
+    HS_HIP(h, hipMemcpyAsync(&b.n_slices, h->slice_off.as<uint32_t>() + b.nql, 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  if (unsafe) HS_CHECK(demote(h, c, p, b, unsafe));
+  if (b.n_items) {
+    HS_HIP(h, h->item_desc.reserve((size_t)b.n_items * 32));
+    HS_HIP(h, hs_launch_item_desc(h->tabs, h->seg_key.as<uint64_t>(), h->seg_cnt.as<uint32_t>(),
+                                  h->seg_qoff.as<uint32_t>(), h->item_off.as<uint32_t>(), b.nqs,
+                                  h->sorted_ql.as<uint32_t>(), h->qcount.as<uint32_t>(), b.n_items, p.jm,
+                                  seg_shift_of(h), h->seg_vals.as<uint32_t>(), h->PW,
+                                  p.async_items ? h->item_off.as<uint32_t>() + b.nqs : nullptr,
+                                  h->item_desc.as<uint4>(), h->stream));
   }
   // segments routed away from the join (HS_OPT_JOIN_MIN_Q / _M; none by default) go through the streaming
   // filter and its per-query distance tables, on the side stream beside the join
-  const bool side = !brute && n_items && n_slices;
-  if (brute || n_slices) {
-    HS_HIP(h, h->tq.reserve((size_t)nq * k * HS_TROW * 4));
-    if (!side)
-      HS_HIP(h, hs_launch_qtables(d_centers, nq, k, h->coords.as<double>(), h->alphabet,
+  if (b.n_slices) {
+    HS_HIP(h, h->tq.reserve((size_t)b.nq * h->p.k * HS_TROW * 4));
+    if (!b.n_items)
+      HS_HIP(h, hs_launch_qtables(b.centers, b.nq, (int)h->p.k, h->coords.as<double>(), h->alphabet,
                                   h->tq.as<float>(), h->stream));
   }
-  HS_HIP(h, hipEventRecord(h->ev[2], h->stream));
-  bool tables_done = !side;
+  return HS_OK;
+}
+
+// Stage 5: the filters, into one survivor list of prov_cap entries: the join (int8: the query-streaming kernel
+// over the head of the item list, the query-resident one over its tail; fp16), and the streaming filter for
+// the probes' slices -- beside the join on the side stream when both have work.
+static hs_status launch_filters(hs_handle* h, const BatchPlan& p, const Batch& b, uint32_t prov_cap, bool again) {
+  const int k = (int)h->p.k, L = (int)h->p.L;
+  const float r2_hi = filter_bound(b.r2);
+  uint32_t* const d_cnt = h->counters.as<uint32_t>();
+  const int n_blocks = h->n_cu * 8, join_blocks = h->n_cu * h->join_blocks_per_cu;
+  const bool side = b.n_items && b.n_slices;
+  auto verify = [&](hipStream_t s) {
+    return hs_launch_verify(h->tabs, h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(), h->slice_off.as<uint32_t>(),
+                            b.nql, h->tq.as<float>(), k, L, r2_hi, d_cnt, prov_cap, h->prov.as<uint2>(), n_blocks, s);
+  };
+  if (side) {
+    HS_HIP(h, hipEventRecord(h->evx[EV_FORK], h->stream));
+    HS_HIP(h, hipStreamWaitEvent(h->stream2, h->evx[EV_FORK], 0));
+    if (!again)  // (the streaming filter's query tables: beside the join too, once)
+      HS_HIP(h, hs_launch_qtables(b.centers, b.nq, k, h->coords.as<double>(), h->alphabet, h->tq.as<float>(),
+                                  h->stream2));
+    HS_HIP(h, verify(h->stream2));
+    HS_HIP(h, hipEventRecord(h->evx[EV_JOIN], h->stream2));
+  }
+  HS_HIP(h, hipEventRecord(h->ev[11], h->stream));  // the join kernel alone: ev[11] .. ev[10]
+  if (b.n_items && p.use_i8) {
+    // (split == the item count when no segment qualifies for the resident kernel or use_r is off)
+    const uint32_t* const d_split = h->seg_n.as<uint32_t>() + 2;
+    const uint4* const rec8 = (p.wide && !h->wide8) ? h->t_rec8w.as<uint4>() : h->t_rec8.as<uint4>();
+    const void* const rows = p.wide ? (const void*)(h->jtab8.as<char>() + 1536) : (const void*)h->jtab8.p;
+    // XCD-local runs of items where the batch's query tiles do not stay in every XCD's L2 anyway
+    // (d_cnt + 40 .. 47: the per-XCD chunk counters)
+    const uint64_t tile_bytes = (uint64_t)b.nqs * (uint64_t)hs_join8_row_bytes(k, p.wide);
+    const uint32_t xcd_run = p.xcd_run >= 0 ? (uint32_t)p.xcd_run : (tile_bytes > (64ull << 20) ? 128u : 0u);
+    HS_HIP(h, hs_launch_join8w(h->item_desc.as<uint4>(), b.n_items, h->tabs.t[0].packed, rec8, h->c16s.p, rows, k,
+                               p.wide, d_cnt, prov_cap, h->prov.as<uint2>(), d_cnt + 32, join_blocks,
+                               p.use_r ? d_split : (p.async_items ? h->item_off.as<uint32_t>() + b.nqs : nullptr),
+                               h->hist.pairs_per_item, xcd_run, h->stream, h->knobs.join_chunk));
+    if (p.use_r)
+      HS_HIP(h, hs_launch_join8r(h->item_desc.as<uint4>(), b.n_items, d_split, h->tabs.t[0].packed,
+                                 h->t_rho.as<uint32_t>(), h->c16s.p, rows, h->alphabet, d_cnt, prov_cap,
+                                 h->prov.as<uint2>(), d_cnt + 33, join_blocks, h->hist.pairs_per_item, h->stream));
+  } else if (b.n_items) {
+    HS_HIP(h, hs_launch_join(h->item_desc.as<uint4>(), b.n_items, h->tabs.t[0].packed, h->sorted_ql.as<uint32_t>(),
+                             h->c16s.p, h->jtab.p, reinterpret_cast<const float*>(h->jtab.as<char>() + 512), k, d_cnt,
+                             prov_cap, h->prov.as<uint2>(), join_blocks, h->stream));
+  }
+  HS_HIP(h, hipEventRecord(h->ev[10], h->stream));
+  if (side)
+    HS_HIP(h, hipStreamWaitEvent(h->stream, h->evx[EV_JOIN], 0));
+  else if (b.n_slices)
+    HS_HIP(h, verify(h->stream));
+  return HS_OK;
+}
+
+// Stage 6: the exact decision on the survivors (after the int8 join's 8-column refinement), and the hits
+// ordered per query into the caller's arrays when the plan says so.
+static hs_status finalize_hits(hs_handle* h, const QueryCall& c, const BatchPlan& p, const Batch& b,
+                               uint32_t prov_cap, uint32_t hit_cap, BatchOut* bout) {
+  const int k = (int)h->p.k, L = (int)h->p.L;
+  uint32_t* const d_cnt = h->counters.as<uint32_t>();
+  const uint2* fin_list = h->prov.as<uint2>();
+  const uint32_t* fin_count = d_cnt;
+  if (p.refine && b.n_items) {
+    HS_HIP(h, h->prov2.reserve((size_t)prov_cap * 8));
+    HS_HIP(h, hipMemsetAsync(d_cnt + 4, 0, 4, h->stream));
+    HS_HIP(h, hs_launch_refine8(h->tabs, h->prov.as<uint2>(), d_cnt, prov_cap, h->sorted_ql.as<uint32_t>(), h->c16.p,
+                                h->c8b.p, h->jtab8.as<char>() + 1024, h->jtab8.as<float>() + 128, k, L,
+                                h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(), h->prov2.as<uint2>(), d_cnt + 4,
+                                h->stream));
+    fin_list = h->prov2.as<uint2>();
+    fin_count = d_cnt + 4;
+  }
+  const uint4* d_qpacked = nullptr;
+  if (b.qcodes && k <= 75) {  // the queries are k-mers: packed like the members, for the exact pass
+    HS_HIP(h, h->qpacked.reserve(std::max<size_t>(16, (size_t)b.nq * h->PW * 16)));
+    HS_HIP(h, hs_launch_pack(b.qcodes, b.nq, k, h->alphabet, h->qpacked.as<uint4>(), d_cnt + HS_CNT_BAD_QUERY_CODE,
+                             h->stream));
+    d_qpacked = h->qpacked.as<uint4>();
+  }
+  uint32_t* const qcnt = p.order_here ? h->qhits.as<uint32_t>() : nullptr;
+  HS_HIP(h, hs_launch_finalize(h->tabs, h->codes.as<uint8_t>(), b.centers, b.qcodes, h->coords.as<double>(),
+                               h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(), fin_list, fin_count, prov_cap,
+                               h->sorted_ql.as<uint32_t>(), k, L, b.r2, c.sqrt_test ? c.R : (double)NAN, b.q_base,
+                               c.self_first, d_cnt + 1, hit_cap, h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(),
+                               qcnt, h->alphabet, d_qpacked, p.order_here ? h->hit_rank.as<uint32_t>() : nullptr,
+                               h->stream));
+  if (p.order_here) {
+    const size_t n1q = (size_t)b.nq + 1;
+    uint32_t* const qoff = qcnt + n1q;
+    HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, qcnt, qoff, n1q, h->stream));
+    HS_HIP(h, hs_launch_hit_order(h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(), d_cnt + 1, hit_cap, b.q_base,
+                                  b.nq, qoff, h->hit_rank.as<uint32_t>(), h->hit_kv.p, d_cnt + 20, qoff + 2 * n1q,
+                                  bout->q, bout->id, bout->table, bout->dist, bout->room, h->n_cu, h->stream));
+  }
+  return HS_OK;
+}
+
+// One pass of a search batch's filters and exact decision; the counters and what the accounting and the
+// history need read back behind them.
+static hs_status search_pass(hs_handle* h, const QueryCall& c, const BatchPlan& p, Batch& b, uint32_t prov_cap,
+                             uint32_t hit_cap, bool again, BatchOut* bout) {
+  uint32_t* const d_cnt = h->counters.as<uint32_t>();
+  if (p.order_here) {
+    const size_t n1q = (size_t)b.nq + 1;
+    HS_HIP(h, h->qhits.reserve((6 * n1q + 8) * 4));
+    // per-query hit counts, offsets, fill, and behind them the lists of the queries a block orders
+    HS_HIP(h, hipMemsetAsync(h->qhits.p, 0, (3 * n1q + 8) * 4, h->stream));
+    if (again) HS_HIP(h, hipMemsetAsync(d_cnt + 20, 0, 4, h->stream));  // the "too many hits" flag
+    HS_HIP(h, h->hit_kv.reserve((size_t)hit_cap * 16));
+    HS_HIP(h, h->hit_rank.reserve((size_t)hit_cap * 4));
+    HS_HIP(h, h->temp.reserve(hs_scan_u32_temp(n1q) + 256));
+  }
+  HS_HIP(h, hipEventRecord(h->ev[3], h->stream));
+  if (again) HS_HIP(h, hipMemsetAsync(d_cnt + 32, 0, 64, h->stream));  // the item counters again
+  HS_CHECK(launch_filters(h, p, b, prov_cap, again));
+  HS_HIP(h, hipEventRecord(h->ev[4], h->stream));
+  HS_CHECK(finalize_hits(h, c, p, b, prov_cap, hit_cap, bout));
+  HS_HIP(h, hipEventRecord(h->ev[5], h->stream));
+  // [0] survivors [1] hits [2..3] candidates ... [10..13] join statistics [20] order fallback
+  HS_HIP(h, hipMemcpyAsync(h->pin_cnt, d_cnt, 96, hipMemcpyDeviceToHost, h->stream));
+  if (!p.self_codes && use_projection(h))  // [32..33] MFMA projection of the queries: {slots reserved, values flagged}
+    HS_HIP(h, hipMemcpyAsync(h->pin_cnt + 32, h->proj_cnt.as<uint32_t>() + 4, 8, hipMemcpyDeviceToHost, h->stream));
+  if (p.async_items)  // [40] the real item count
+    HS_HIP(h, hipMemcpyAsync(h->pin_cnt + 40, h->item_off.as<uint32_t>() + b.nqs, 4, hipMemcpyDeviceToHost, h->stream));
+  if (p.use_join && p.use_i8 && b.n_items)  // [41] first item of the few-query class, [42] items (cut_items)
+    HS_HIP(h, hipMemcpyAsync(h->pin_cnt + 41, h->seg_n.as<uint32_t>() + 2, 8, hipMemcpyDeviceToHost, h->stream));
+  return HS_OK;
+}
+
+// The survivor-capacity loop of a batch: pass(prov_cap, hit_cap, again) issues the filters and the exact
+// decision, recording ev[3] / ev[4] / ev[5] around them (ev[11] .. ev[10] around the join when join_timed), and
+// the counters' read-back; it runs again with a longer survivor list while the filters pass more than the
+// list holds.  item_cap > 0: the batch left its item count on the device with room for that many items.
+// On success: the timings, the survivors and the hit count (*n_hits) accounted.
+extern "C++" template <class Pass>
+static hs_status filter_passes(hs_handle* h, uint32_t nq, uint32_t item_cap, bool join_timed, uint32_t* n_hits,
+                               Pass pass) {
+  uint32_t* const d_cnt = h->counters.as<uint32_t>();
   uint32_t prov_cap = (uint32_t)std::max<size_t>(h->prov.cap / 8, std::max<size_t>(1u << 20, 16ull * nq));
-  if (!h->pin_cnt) {
+  if (!h->pin_cnt) {  // (three small device -> host copies into pageable memory cost ~ 50 us per batch)
     HS_HIP(h, hipHostMalloc(reinterpret_cast<void**>(&h->pin_cnt), 64 * 4, hipHostMallocDefault));
     memset(h->pin_cnt, 0, 64 * 4);
   }
-  // [0] survivors [1] hits [2..3] candidates ... [10..13] join statistics [20] order fallback
-  uint32_t* const host_cnt = h->pin_cnt;
-  uint32_t* const host_proj = h->pin_cnt + 32;  // MFMA projection of the queries: {slots reserved, values flagged}
-  uint32_t& n_items_real = h->pin_cnt[40];
+  const uint32_t* const host_cnt = h->pin_cnt;
   memset(h->pin_cnt, 0, 64 * 4);
-  const bool proj_stats = !brute && !self_codes && use_projection(h);
   double ms_verify = 0, ms_final = 0, ms_join = 0;
   uint32_t launches = 0;
-  for (;;) {  // retried only when a workspace capacity was exceeded
+  for (;;) {
     HS_HIP(h, h->prov.reserve((size_t)prov_cap * 8));
-    uint32_t hit_cap = (uint32_t)std::max<size_t>(h->hit_key.cap / 8, prov_cap);
+    const uint32_t hit_cap = (uint32_t)std::max<size_t>(h->hit_key.cap / 8, prov_cap);
     HS_HIP(h, h->hit_key.reserve((size_t)hit_cap * 8));
     HS_HIP(h, h->hit_val.reserve((size_t)hit_cap * 8));
     HS_HIP(h, hipMemsetAsync(d_cnt, 0, 8, h->stream));
-    // the batch orders its hits itself (bucket by query, no sort, no host count) unless brute force
-    // (not tried again at a radius at which the previous batch had a query with too many hits for it:
-    // the attempt costs 10 % of such a batch -- k = 15 at the C2 sizes, 545 hits per query)
-    const bool order_here = bout && !brute && !h->knobs.sort_hits && !(h->order_failed && h->order_failed_R == R);
-    uint32_t *qcnt = nullptr, *qoff = nullptr, *qfill = nullptr;
-    if (order_here) {
-      const size_t n1q = (size_t)nq + 1;
-      HS_HIP(h, h->qhits.reserve((6 * n1q + 8) * 4));
-      qcnt = h->qhits.as<uint32_t>();
-      qoff = qcnt + n1q;
-      qfill = qoff + n1q;  // (and behind it the lists of the queries a block orders: 8 + 3 nq words)
-      HS_HIP(h, hipMemsetAsync(qcnt, 0, (3 * n1q + 8) * 4, h->stream));
-      if (launches) HS_HIP(h, hipMemsetAsync(d_cnt + 20, 0, 4, h->stream));  // retry: the "too many hits" flag
-      HS_HIP(h, h->hit_kv.reserve((size_t)hit_cap * 16));
-      HS_HIP(h, h->hit_rank.reserve((size_t)hit_cap * 4));
-      HS_HIP(h, h->temp.reserve(hs_scan_u32_temp(n1q) + 256));
-    }
-    HS_HIP(h, hipEventRecord(h->ev[3], h->stream));
-    if (launches) HS_HIP(h, hipMemsetAsync(d_cnt + 32, 0, 64, h->stream));  // retry: the item counters again
-    if (side) {
-      HS_HIP(h, hipEventRecord(h->evx[EV_FORK], h->stream));
-      HS_HIP(h, hipStreamWaitEvent(h->stream2, h->evx[EV_FORK], 0));
-      if (!tables_done)
-        HS_HIP(h, hs_launch_qtables(d_centers, nq, k, h->coords.as<double>(), h->alphabet,
-                                    h->tq.as<float>(), h->stream2));
-      tables_done = true;
-      HS_HIP(h, hs_launch_verify(h->tabs, h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(),
-                                 h->slice_off.as<uint32_t>(), nql, h->tq.as<float>(), k, L, r2_hi,
-                                 d_cnt, prov_cap, h->prov.as<uint2>(), n_blocks, h->stream2));
-      HS_HIP(h, hipEventRecord(h->evx[EV_JOIN], h->stream2));
-    }
-    if (brute) {
-      HS_HIP(h, hs_launch_bruteforce(h->packed_all.as<uint4>(), (uint32_t)h->n, h->tq.as<float>(),
-                                     nq, k, r2_hi, d_cnt, prov_cap, h->prov.as<uint2>(), nullptr,
-                                     nullptr, n_blocks, h->stream));
-    } else {
-      HS_HIP(h, hipEventRecord(h->ev[11], h->stream));  // the join kernel alone: ev[11] .. ev[10]
-      if (n_items && use_i8) {
-        // the head [0, split) of the item list through the query-streaming kernel, the tail through the
-        // query-resident one (split == the item count when no segment qualifies or use_r is off)
-        const uint32_t* const d_split = h->seg_n.as<uint32_t>() + 2;
-        // XCD-local runs of items where the batch's query tiles do not stay in every XCD's L2 anyway
-        // (d_cnt + 40 .. 47: the per-XCD chunk counters)
-        const uint64_t tile_bytes = (uint64_t)nqs * (uint64_t)hs_join8_row_bytes(k, wide);
-        const uint32_t xcd_run = h->knobs.join_xcd_run >= 0 ? (uint32_t)h->knobs.join_xcd_run
-                                                            : (tile_bytes > (64ull << 20) ? 128u : 0u);
-        HS_HIP(h, hs_launch_join8w(h->item_desc.as<uint4>(), n_items, h->tabs.t[0].packed,
-                                   rec8, h->c16s.p, jtab_rows, k, wide, d_cnt, prov_cap,
-                                   h->prov.as<uint2>(), d_cnt + 32, h->n_cu * h->join_blocks_per_cu,
-                                   use_r ? d_split : (async_items ? h->item_off.as<uint32_t>() + nqs : nullptr),
-                                   h->pairs_per_item, xcd_run, h->stream, h->knobs.join_chunk));
-        if (use_r)
-          HS_HIP(h, hs_launch_join8r(h->item_desc.as<uint4>(), n_items, d_split, h->tabs.t[0].packed,
-                                     h->t_rho.as<uint32_t>(),
-                                     h->c16s.p, jtab_rows, h->alphabet, d_cnt, prov_cap, h->prov.as<uint2>(),
-                                     d_cnt + 33, h->n_cu * h->join_blocks_per_cu, h->pairs_per_item, h->stream));
-      }
-      else if (n_items)
-        HS_HIP(h, hs_launch_join(h->item_desc.as<uint4>(), n_items, h->tabs.t[0].packed,
-                                 h->sorted_ql.as<uint32_t>(),
-                                 h->c16s.p, h->jtab.p,
-                                 reinterpret_cast<const float*>(h->jtab.as<char>() + 512), k, d_cnt,
-                                 prov_cap, h->prov.as<uint2>(), h->n_cu * h->join_blocks_per_cu, h->stream));
-      HS_HIP(h, hipEventRecord(h->ev[10], h->stream));
-      if (side)
-        HS_HIP(h, hipStreamWaitEvent(h->stream, h->evx[EV_JOIN], 0));
-      else if (n_slices)
-        HS_HIP(h, hs_launch_verify(h->tabs, h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(),
-                                   h->slice_off.as<uint32_t>(), nql, h->tq.as<float>(), k, L, r2_hi,
-                                   d_cnt, prov_cap, h->prov.as<uint2>(), n_blocks, h->stream));
-    }
-    HS_HIP(h, hipEventRecord(h->ev[4], h->stream));
-    if (brute) {
-      HS_HIP(h, hs_launch_bf_finalize(h->codes.as<uint8_t>(), d_centers, h->coords.as<double>(),
-                                      h->prov.as<uint2>(), d_cnt, prov_cap, k, R, q_base, d_cnt + 1,
-                                      hit_cap, h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(),
-                                      h->stream));
-    } else {
-      const uint2* fin_list = h->prov.as<uint2>();
-      const uint32_t* fin_count = d_cnt;
-      if (refine && use_i8 && n_items) {
-        // use_i8 may have been dropped after the readback (fp16 fallback): then no second row exists
-        HS_HIP(h, h->prov2.reserve((size_t)prov_cap * 8));
-        HS_HIP(h, hipMemsetAsync(d_cnt + 4, 0, 4, h->stream));
-        HS_HIP(h, hs_launch_refine8(h->tabs, h->prov.as<uint2>(), d_cnt, prov_cap,
-                                    h->sorted_ql.as<uint32_t>(), h->c16.p, h->c8b.p,
-                                    h->jtab8.as<char>() + 1024, h->jtab8.as<float>() + 128, k, L,
-                                    h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(),
-                                    h->prov2.as<uint2>(), d_cnt + 4, h->stream));
-        fin_list = h->prov2.as<uint2>();
-        fin_count = d_cnt + 4;
-      }
-      const uint4* d_qpacked = nullptr;
-      if (d_qcodes && k <= 75) {  // the queries are k-mers: packed like the members, for the exact pass
-        HS_HIP(h, h->qpacked.reserve(std::max<size_t>(16, (size_t)nq * h->PW * 16)));
-        HS_HIP(h, hs_launch_pack(d_qcodes, nq, k, h->alphabet, h->qpacked.as<uint4>(),
-                                 d_cnt + HS_CNT_BAD_QUERY_CODE, h->stream));
-        d_qpacked = h->qpacked.as<uint4>();
-      }
-      HS_HIP(h, hs_launch_finalize(h->tabs, h->codes.as<uint8_t>(), d_centers, d_qcodes, h->coords.as<double>(),
-                                   h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(),
-                                   fin_list, fin_count, prov_cap, h->sorted_ql.as<uint32_t>(),
-                                   k, L, r2, h->sqrt_test ? R : (double)NAN, q_base, h->self_first, d_cnt + 1,
-                                   hit_cap, h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(), qcnt,
-                                   h->alphabet, d_qpacked, order_here ? h->hit_rank.as<uint32_t>() : nullptr,
-                                   h->stream));
-      if (order_here) {
-        const size_t n1q_ = (size_t)nq + 1;
-        HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, qcnt, qoff, (size_t)nq + 1, h->stream));
-        HS_HIP(h, hs_launch_hit_order(h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(), d_cnt + 1, hit_cap,
-                                      q_base, nq, qoff, h->hit_rank.as<uint32_t>(), h->hit_kv.p, d_cnt + 20, qfill + n1q_, bout->q, bout->id,
-                                      bout->table, bout->dist, bout->room, h->n_cu, h->stream));
-      }
-    }
-    HS_HIP(h, hipEventRecord(h->ev[5], h->stream));
-    HS_HIP(h, hipMemcpyAsync(host_cnt, d_cnt, 96, hipMemcpyDeviceToHost, h->stream));
-    if (proj_stats)
-      HS_HIP(h, hipMemcpyAsync(host_proj, h->proj_cnt.as<uint32_t>() + 4, 8, hipMemcpyDeviceToHost, h->stream));
-    if (async_items)
-      HS_HIP(h, hipMemcpyAsync(&n_items_real, h->item_off.as<uint32_t>() + nqs, 4, hipMemcpyDeviceToHost,
-                               h->stream));
-    if (use_join && use_i8 && n_items)  // [41] first item of the few-query class, [42] items (cut_items)
-      HS_HIP(h, hipMemcpyAsync(h->pin_cnt + 41, h->seg_n.as<uint32_t>() + 2, 8, hipMemcpyDeviceToHost, h->stream));
+    HS_CHECK(pass(prov_cap, hit_cap, launches != 0));
     HS_HIP(h, hipStreamSynchronize(h->stream));
     // > ~4e9 survivors: run_query halves the batch (HS_TEST_SPLIT_ABOVE=n: as if every batch of more
     // than n queries had overflowed -- the tests' handle on the splitting logic)
@@ -2610,100 +2667,166 @@ static hs_status query_batch(hs_handle* h, const double* d_centers, const uint8_
 #endif
     if (host_cnt[HS_CNT_BAD_QUERY_CODE])
       return fail(h, HS_ERR_INVALID, "residue code outside the alphabet in the queries");
-    if (async_items && (host_cnt[8] /* join legality */ || n_items_real > n_items)) {
-      ++h->prof.join_async_retries;  // (measurements can exclude such a call: its join ran twice)
-      return query_batch(h, d_centers, d_qcodes_ext, nq, q_base, R, brute, d_cand, n_batch_hits, bout, false);
-    }
+    if (item_cap && (host_cnt[8] /* join legality */ || host_cnt[40] > item_cap)) return HS_SYNC_ITEMS;
     ms_verify += ev_ms(h, 3, 4);
-    if (!brute && n_items) ms_join += ev_ms(h, 11, 10);
+    if (join_timed) ms_join += ev_ms(h, 11, 10);
     ms_final += ev_ms(h, 4, 5);
     ++launches;
     if (h->knobs.debug_refine)
       fprintf(stderr, "survivors %u -> refined %u -> hits %u\n", host_cnt[0], host_cnt[4], host_cnt[1]);
-    if (host_cnt[0] > prov_cap) {
-      // the survivor list was too short: once more with room for what the filters reported (64-bit
-      // arithmetic: the count may sit just under the overflow flag's 0xF0000000).  The six lists of the
-      // exact pass are sized from it -- 48 bytes per entry -- so beyond 2^30 entries, or when the device
-      // has no room for them, the batch is cut in halves like a counter overflow instead.
-      const uint64_t need = (uint64_t)host_cnt[0] + host_cnt[0] / 8 + 1024;
-      if (need > (1ull << 30) && nq > 1) return HS_SPLIT_BATCH;
-      if (need > 0xffffffffull) return fail(h, HS_ERR_CAPACITY, "the filter survivors of one query exceed the survivor list");
-      const uint64_t have = prov_cap;
-      prov_cap = (uint32_t)need;
-      if (nq > 1) {  // can the lists grow?  (a failed reserve keeps the old buffer's size at 0: re-reserved below)
-        const size_t bytes = (size_t)prov_cap * 8;
-        if (h->prov.reserve(bytes) != hipSuccess || h->hit_key.reserve(bytes) != hipSuccess ||
-            h->hit_val.reserve(bytes) != hipSuccess) {
-          (void)hipGetLastError();
-          prov_cap = (uint32_t)have;
-          return HS_SPLIT_BATCH;
-        }
+    if (host_cnt[0] <= prov_cap) break;  // hit_count <= prov_count <= prov_cap <= hit_cap
+    // the survivor list was too short: once more with room for what the filters reported (64-bit
+    // arithmetic: the count may sit just under the overflow flag's 0xF0000000).  The six lists of the
+    // exact pass are sized from it -- 48 bytes per entry -- so beyond 2^30 entries, or when the device
+    // has no room for them, the batch is cut in halves like a counter overflow instead.
+    const uint64_t need = (uint64_t)host_cnt[0] + host_cnt[0] / 8 + 1024;
+    if (need > (1ull << 30) && nq > 1) return HS_SPLIT_BATCH;
+    if (need > 0xffffffffull) return fail(h, HS_ERR_CAPACITY, "the filter survivors of one query exceed the survivor list");
+    const uint64_t have = prov_cap;
+    prov_cap = (uint32_t)need;
+    if (nq > 1) {  // can the lists grow?  (a failed reserve keeps the old buffer's size at 0: re-reserved below)
+      const size_t bytes = (size_t)prov_cap * 8;
+      if (h->prov.reserve(bytes) != hipSuccess || h->hit_key.reserve(bytes) != hipSuccess ||
+          h->hit_val.reserve(bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        prov_cap = (uint32_t)have;
+        return HS_SPLIT_BATCH;
       }
-      continue;
     }
-    if (bout) bout->ordered = order_here && !host_cnt[20];
-    if (order_here) {
-      h->order_failed = host_cnt[20] != 0;
-      h->order_failed_R = R;
-    }
-    break;  // hit_count <= prov_count <= prov_cap <= hit_cap
   }
   h->prof.ms_hash += ev_ms(h, 0, 1);
-  if (proj_stats) {
-    h->prof.hash_values += (uint64_t)nq * h->LK;
-    h->prof.hash_flagged += host_proj[1];
-  }
   h->prof.ms_probe += ev_ms(h, 1, 2);
   h->prof.ms_verify += ms_verify;
   h->prof.ms_finalize += ms_final;
-  h->prof.verify_launches += launches;
-  uint64_t cand_total;
-  memcpy(&cand_total, host_cnt + 2, 8);
-  h->prof.candidates += brute ? (uint64_t)nq * h->n : cand_total;
-  h->prof.provisional += host_cnt[0];
-  h->prof.join_batches += n_items ? 1 : 0;
-  h->prof.join_i8_batches += (n_items && use_i8) ? 1 : 0;
-  if (n_items && use_i8) {
-    h->prof.join_row_bytes = (uint32_t)hs_join8_row_bytes(k, wide);
-    h->prof.join_wide = (uint32_t)wide;
-  }
   h->prof.ms_join += ms_join;
-  if (async_items) n_items = n_items_real;
-  h->prof.join_items += n_items;
-  if (use_i8 && n_items) h->item_cap_hint = n_items + n_items / 4 + 4096;
-  if (use_i8 && n_items) ++h->resident_age;
-  if (use_i8 && n_items && use_r && h->pin_cnt[42]) {
-    h->resident_age = 0;
-    h->resident_nq = nq;
-    h->resident_share = (double)(h->pin_cnt[42] - h->pin_cnt[41]) / (double)h->pin_cnt[42];
-    h->prof.join_items_resident += h->pin_cnt[42] - h->pin_cnt[41];
-  }
-  if (use_i8 && n_items) {  // sizes the next batch's counter chunks (hs_launch_join8w)
-    unsigned long long issued = 0;
-    memcpy(&issued, host_cnt + 10, 8);
-    h->pairs_per_item = (double)issued / (double)n_items;
-  }
-  if (use_join) {
-    unsigned long long js[2] = {0, 0};
-    memcpy(js, host_cnt + 10, 16);  // d_jstats = d_cnt + 10, read back with the counters
-    h->prof.join_pairs_issued += js[0];
-    h->prof.join_pairs += js[1];
-  }
-  *n_batch_hits = host_cnt[1];
+  h->prof.verify_launches += launches;
+  h->prof.provisional += host_cnt[0];
+  *n_hits = host_cnt[1];
   return HS_OK;
 }
 
-static hs_status run_query(hs_handle* h, const double* d_centers, const uint8_t* d_qcodes, uint64_t nq, double R, bool brute,
-                           uint32_t* d_hit_q, uint32_t* d_hit_id, uint32_t* d_hit_table,
-                           double* d_hit_dist, uint64_t cap, uint64_t* n_hits, uint64_t* d_cand) {
+// Brute force: every query against every indexed k-mer (packed_all) through the streaming filter's tables
+static hs_status brute_batch(hs_handle* h, const QueryCall& c, uint32_t nq, uint32_t q_base, uint32_t* n_hits) {
+  const int k = (int)h->p.k;
+  const double r2 = c.R * c.R;  // motif_both_points.cpp:204
+  const float r2_hi = filter_bound(r2);
+  uint32_t* const d_cnt = h->counters.as<uint32_t>();
+  HS_HIP(h, hipMemsetAsync(d_cnt, 0, 256, h->stream));
+  HS_HIP(h, hipEventRecord(h->ev[0], h->stream));
+  HS_HIP(h, hipEventRecord(h->ev[1], h->stream));
+  HS_HIP(h, h->tq.reserve((size_t)nq * k * HS_TROW * 4));
+  HS_HIP(h, hs_launch_qtables(c.centers, nq, k, h->coords.as<double>(), h->alphabet, h->tq.as<float>(), h->stream));
+  HS_HIP(h, hipEventRecord(h->ev[2], h->stream));
+  HS_CHECK(filter_passes(h, nq, 0, false, n_hits, [&](uint32_t prov_cap, uint32_t hit_cap, bool again) -> hs_status {
+    HS_HIP(h, hipEventRecord(h->ev[3], h->stream));
+    if (again) HS_HIP(h, hipMemsetAsync(d_cnt + 32, 0, 64, h->stream));
+    HS_HIP(h, hs_launch_bruteforce(h->packed_all.as<uint4>(), (uint32_t)h->n, h->tq.as<float>(), nq, k, r2_hi, d_cnt,
+                                   prov_cap, h->prov.as<uint2>(), nullptr, nullptr, h->n_cu * 8, h->stream));
+    HS_HIP(h, hipEventRecord(h->ev[4], h->stream));
+    HS_HIP(h, hs_launch_bf_finalize(h->codes.as<uint8_t>(), c.centers, h->coords.as<double>(), h->prov.as<uint2>(),
+                                    d_cnt, prov_cap, k, c.R, q_base, d_cnt + 1, hit_cap, h->hit_key.as<uint64_t>(),
+                                    h->hit_val.as<uint64_t>(), h->stream));
+    HS_HIP(h, hipEventRecord(h->ev[5], h->stream));
+    HS_HIP(h, hipMemcpyAsync(h->pin_cnt, d_cnt, 96, hipMemcpyDeviceToHost, h->stream));
+    return HS_OK;
+  }));
+  h->prof.candidates += (uint64_t)nq * h->n;
+  return HS_OK;
+}
+
+// Stage 7: a finished search batch's counters into the profile
+static void account_batch(hs_handle* h, const BatchPlan& p, Batch& b) {
+  const uint32_t* const cnt = h->pin_cnt;
+  if (!p.self_codes && use_projection(h)) {
+    h->prof.hash_values += (uint64_t)b.nq * h->LK;
+    h->prof.hash_flagged += cnt[33];
+  }
+  uint64_t cand_total;
+  memcpy(&cand_total, cnt + 2, 8);
+  h->prof.candidates += cand_total;
+  h->prof.join_batches += b.n_items ? 1 : 0;
+  h->prof.join_i8_batches += (b.n_items && p.use_i8) ? 1 : 0;
+  if (b.n_items && p.use_i8) {
+    h->prof.join_row_bytes = (uint32_t)hs_join8_row_bytes((int)h->p.k, p.wide);
+    h->prof.join_wide = (uint32_t)p.wide;
+  }
+  if (p.async_items) b.n_items = cnt[40];
+  h->prof.join_items += b.n_items;
+  if (p.use_i8 && b.n_items && p.use_r && cnt[42]) h->prof.join_items_resident += cnt[42] - cnt[41];
+  if (p.use_join) {
+    unsigned long long js[2] = {0, 0};
+    memcpy(js, cnt + 10, 16);  // the join statistics (d_cnt + 10), read back with the counters
+    h->prof.join_pairs_issued += js[0];
+    h->prof.join_pairs += js[1];
+  }
+}
+
+// What a batch leaves for the next ones (BatchHistory): written here alone, after its counters are back.
+static void learn_from_batch(hs_handle* h, const QueryCall& c, const BatchPlan& p, const Batch& b, hs_status st) {
+  BatchHistory& m = h->hist;
+  if (p.resident_stale) m.resident_share = -1.0;
+  if (st != HS_OK) return;
+  const uint32_t* const cnt = h->pin_cnt;
+  if (p.order_here) {
+    m.order_failed = cnt[20] != 0;
+    m.order_failed_R = c.R;
+  }
+  if (!p.use_i8 || !b.n_items) return;
+  m.item_cap_hint = b.n_items + b.n_items / 4 + 4096;
+  ++m.resident_age;
+  if (p.use_r && cnt[42]) {
+    m.resident_age = 0;
+    m.resident_nq = b.nq;
+    m.resident_share = (double)(cnt[42] - cnt[41]) / (double)cnt[42];
+  }
+  unsigned long long issued = 0;
+  memcpy(&issued, cnt + 10, 8);
+  m.pairs_per_item = (double)issued / (double)b.n_items;
+}
+
+// One batch of a call: brute force, or the search stages in order.  A batch that left its item count on the
+// device and found it too small runs once more with the count read back first.
+static hs_status query_batch(hs_handle* h, const QueryCall& c, uint32_t nq, uint32_t q_base, uint64_t* d_cand,
+                             uint32_t* n_hits, BatchOut* bout) {
+  if (c.brute) return brute_batch(h, c, nq, q_base, n_hits);
+  for (bool allow_async = true;; allow_async = false) {
+    BatchPlan p = plan_batch(h, c, nq, allow_async, bout != nullptr);
+    const uint32_t nql = nq * (uint32_t)h->p.L;
+    Batch b{nq, q_base, nql, nql, c.R * c.R, c.centers, d_cand};
+    HS_HIP(h, hipMemsetAsync(h->counters.p, 0, 256, h->stream));  // incl. the join's item counter (d_cnt + 32)
+    HS_HIP(h, hipEventRecord(h->ev[0], h->stream));
+    HS_CHECK(prepare_queries(h, c, p, b));
+    HS_CHECK(hash_and_probe(h, c, p, b));
+    HS_CHECK(group_segments(h, p, b));
+    HS_CHECK(read_items(h, c, p, b));
+    HS_HIP(h, hipEventRecord(h->ev[2], h->stream));
+    const hs_status st = filter_passes(h, nq, p.item_cap, b.n_items != 0, n_hits,
+                                       [&](uint32_t prov_cap, uint32_t hit_cap, bool again) {
+                                         return search_pass(h, c, p, b, prov_cap, hit_cap, again, bout);
+                                       });
+    if (st == HS_SYNC_ITEMS) {
+      ++h->prof.join_async_retries;  // (measurements can exclude such a call: its join ran twice)
+      continue;
+    }
+    if (st == HS_OK) {
+      account_batch(h, p, b);
+      if (bout) bout->ordered = p.order_here && !h->pin_cnt[20];
+    }
+    learn_from_batch(h, c, p, b, st);
+    return st;
+  }
+}
+
+static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_hit_q, uint32_t* d_hit_id,
+                           uint32_t* d_hit_table, double* d_hit_dist, uint64_t cap, uint64_t* n_hits, uint64_t* d_cand) {
   if (!h || !n_hits) return HS_ERR_INVALID;
   *n_hits = 0;
   if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
   if (nq >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nq must be < 2^27 per call");
   // (a self-join that runs from the residue codes passes no centres)
-  if (nq && !d_centers && !d_qcodes && !(h->self_first != HS_NO_SELF && self_codes_ok(h, R))) return HS_ERR_INVALID;
+  if (nq && !c.centers && !c.codes && !(c.self_first != HS_NO_SELF && self_codes_ok(h, c.R))) return HS_ERR_INVALID;
   if (cap && (!d_hit_q || !d_hit_id || !d_hit_dist)) return HS_ERR_INVALID;
-  if (!(R == R)) return fail(h, HS_ERR_INVALID, "R is NaN");
+  if (!(c.R == c.R)) return fail(h, HS_ERR_INVALID, "R is NaN");
   hs_status st = ensure_device(h);
   if (st) return st;
   memset(&h->prof, 0, sizeof(h->prof));
@@ -2712,28 +2835,28 @@ static hs_status run_query(hs_handle* h, const double* d_centers, const uint8_t*
   // Centres that are k-mers (every 8 doubles a row of the coordinate table, bit for bit -- what the
   // reference's centres files hold) run from their residue codes, as hs_query_codes's do: the same
   // results from k bytes per query where the point rows are 64 k.  One small kernel and one wait per call.
-  if (d_centers && !d_qcodes && nq && h->n && !brute && !h->knobs.no_recognise && h->p.k <= 75) {
+  if (c.centers && !c.codes && nq && h->n && !c.brute && !h->knobs.no_recognise && h->p.k <= 75) {
     const size_t cb = ((size_t)nq * h->p.k + 15) & ~(size_t)15;
     HS_HIP(h, h->rec_codes.reserve(cb + 16));
     uint32_t* const d_bad = reinterpret_cast<uint32_t*>(h->rec_codes.as<uint8_t>() + cb);
     HS_HIP(h, hipMemsetAsync(d_bad, 0, 4, h->stream));
-    HS_HIP(h, hs_launch_recognise_kmers(d_centers, nq, h->p.k, h->coords.as<double>(), h->alphabet,
+    HS_HIP(h, hs_launch_recognise_kmers(c.centers, nq, h->p.k, h->coords.as<double>(), h->alphabet,
                                         h->rec_codes.as<uint8_t>(), d_bad, h->stream));
     uint32_t bad = 1;
     HS_HIP(h, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, h->stream));
     HS_HIP(h, hipStreamSynchronize(h->stream));
     if (!bad) {
-      d_qcodes = h->rec_codes.as<uint8_t>();
-      d_centers = nullptr;
+      c.codes = h->rec_codes.as<uint8_t>();
+      c.centers = nullptr;
       h->prof.queries_recognised = nq;
     }
   }
   uint64_t total = 0;
-  if (nq && h->n && !(brute && R < 0)) {
+  if (nq && h->n && !(c.brute && c.R < 0)) {
     // queries per batch: bounds the workspace, which grows with nq * L (2^17 at L >= 8; with few
     // tables -- the one-table indexes of Clustering() -- larger batches, fewer fixed costs)
     uint32_t QB = std::max(1u << 17, std::min(1u << 20, (1u << 20) / h->p.L));
-    if (nq > QB && !brute && !h->knobs.query_batch) {
+    if (nq > QB && !c.brute && !h->knobs.query_batch) {
       // More queries than one such batch: as many per batch as a third of the free HBM carries, up to 2^20.
       // The pairs of a batch are (bucket members) x (queries probing the bucket), so the join's operand reuse
       // grows with the batch: at 10^8 k-mers x 32 tables a segment sees ~19 of 125 k queries, ~150 of 10^6.
@@ -2744,24 +2867,20 @@ static hs_status run_query(hs_handle* h, const double* d_centers, const uint8_t*
         const size_t per_q = (size_t)h->p.L * (4 * ((size_t)h->p.K + 27) + 416 + 64) + 416 + 3 * (size_t)h->d + 768;
         const size_t fit = free_b / 3 / per_q;
         QB = (uint32_t)std::max<size_t>(QB, std::min<size_t>((size_t)1 << 20, fit));
-        QB = std::min(QB, (uint32_t)((1ull << 31) / h->p.L) - 1);  // probe numbers carry a flag in bit 31
       }
     }
     if (h->knobs.query_batch) QB = h->knobs.query_batch;  // hs_set_option(HS_OPT_QUERY_BATCH) / HS_QUERY_BATCH
+    QB = std::min(QB, max_query_batch(h));
     uint32_t nqb = 0;
     for (uint64_t q0 = 0; q0 < nq; q0 += nqb) {
       nqb = (uint32_t)std::min<uint64_t>(QB, nq - q0);
       uint32_t nh = 0;
-      BatchOut bout;
       const uint64_t at = std::min<uint64_t>(total, cap);
-      bout.q = d_hit_q + at;
-      bout.id = d_hit_id + at;
-      bout.table = d_hit_table ? d_hit_table + at : nullptr;
-      bout.dist = d_hit_dist + at;
-      bout.room = cap - at;
-      st = query_batch(h, d_centers ? d_centers + q0 * h->d : nullptr, d_qcodes ? d_qcodes + q0 * h->p.k : nullptr,
-                       nqb, (uint32_t)q0, R, brute,
-                       d_cand ? d_cand + q0 * h->p.L : nullptr, &nh, cap ? &bout : nullptr);
+      BatchOut bout{d_hit_q + at, d_hit_id + at, d_hit_table ? d_hit_table + at : nullptr, d_hit_dist + at, cap - at};
+      QueryCall bc = c;
+      bc.centers = c.centers ? c.centers + q0 * h->d : nullptr;
+      bc.codes = c.codes ? c.codes + q0 * h->p.k : nullptr;
+      st = query_batch(h, bc, nqb, (uint32_t)q0, d_cand ? d_cand + q0 * h->p.L : nullptr, &nh, cap ? &bout : nullptr);
       if (st == HS_SPLIT_BATCH) {
         // more filter survivors than the 32-bit list counter holds (a radius near the typical
         // distance of bucket mates): the same queries again in batches half the size
@@ -2793,7 +2912,7 @@ static hs_status run_query(hs_handle* h, const double* d_centers, const uint8_t*
       }
       total += nh;
     }
-  } else if (d_cand && nq && !brute) {
+  } else if (d_cand && nq && !c.brute) {
     HS_HIP(h, hipMemsetAsync(d_cand, 0, (size_t)nq * h->p.L * 8, h->stream));
   }
   HS_HIP(h, hipEventRecord(h->ev[9], h->stream));
@@ -2808,16 +2927,14 @@ static hs_status run_query(hs_handle* h, const double* d_centers, const uint8_t*
 hs_status hs_query_dev(hs_handle* h, const double* d_centers, uint64_t nq, double R,
                        uint32_t* d_hit_q, uint32_t* d_hit_id, uint32_t* d_hit_table,
                        double* d_hit_dist, uint64_t cap, uint64_t* n_hits, uint64_t* d_cand) {
-  return run_query(h, d_centers, nullptr, nq, R, false, d_hit_q, d_hit_id, d_hit_table, d_hit_dist, cap,
-                   n_hits, d_cand);
+  return run_query(h, {d_centers, nullptr, R}, nq, d_hit_q, d_hit_id, d_hit_table, d_hit_dist, cap, n_hits, d_cand);
 }
 
 hs_status hs_query_codes_dev(hs_handle* h, const uint8_t* d_qcodes, uint64_t nq, double R,
                              uint32_t* d_hit_q, uint32_t* d_hit_id, uint32_t* d_hit_table,
                              double* d_hit_dist, uint64_t cap, uint64_t* n_hits, uint64_t* d_cand) {
   if (nq && !d_qcodes) return HS_ERR_INVALID;
-  return run_query(h, nullptr, d_qcodes, nq, R, false, d_hit_q, d_hit_id, d_hit_table, d_hit_dist, cap,
-                   n_hits, d_cand);
+  return run_query(h, {nullptr, d_qcodes, R}, nq, d_hit_q, d_hit_id, d_hit_table, d_hit_dist, cap, n_hits, d_cand);
 }
 
 static hs_status host_query(hs_handle* h, const double* centers, const uint8_t* qcodes, uint64_t nq, double R,
@@ -2838,8 +2955,8 @@ static hs_status host_query(hs_handle* h, const double* centers, const uint8_t* 
   if (cand) HS_HIP(h, h->io_cand.reserve(std::max<size_t>(16, (size_t)nq * h->p.L * 8)));
   if (cbytes) HS_HIP(h, hipMemcpyAsync(h->io_centers.p, centers, cbytes, hipMemcpyHostToDevice, h->stream));
   if (kbytes) HS_HIP(h, hipMemcpyAsync(h->io_codes.p, qcodes, kbytes, hipMemcpyHostToDevice, h->stream));
-  st = run_query(h, qcodes ? nullptr : h->io_centers.as<double>(), qcodes ? h->io_codes.as<uint8_t>() : nullptr, nq,
-                 R, brute, h->io_q.as<uint32_t>(),
+  st = run_query(h, {qcodes ? nullptr : h->io_centers.as<double>(), qcodes ? h->io_codes.as<uint8_t>() : nullptr, R, brute},
+                 nq, h->io_q.as<uint32_t>(),
                  h->io_id.as<uint32_t>(), h->io_table.as<uint32_t>(), h->io_dist.as<double>(), cap,
                  n_hits, cand ? h->io_cand.as<uint64_t>() : nullptr);
   if (st != HS_OK) return st;
@@ -2958,18 +3075,16 @@ hs_status hs_self_join_range(hs_handle* h, uint64_t first, uint64_t count, doubl
       HS_HIP(h, hs_launch_embed(h->codes.as<uint8_t>() + q0 * h->p.k, nq, (int)h->p.k,
                                 h->coords.as<double>(), centers.as<double>(), h->stream));
     }
+    // (the pair of a k-mer with itself is dropped on the device)
+    const QueryCall call{from_codes ? nullptr : centers.as<double>(), nullptr, R, false, (uint32_t)q0, sqrt_test != 0};
     uint64_t hcap = std::max<uint64_t>(dq.cap / 4, 3 * nq + 1024), nh = 0;
     for (;;) {
       HS_HIP(h, dq.reserve(hcap * 4));
       HS_HIP(h, did.reserve(hcap * 4));
       HS_HIP(h, dt.reserve(hcap * 4));
       HS_HIP(h, dd.reserve(hcap * 8));
-      h->sqrt_test = sqrt_test != 0;
-      h->self_first = (uint32_t)q0;  // the pair of a k-mer with itself is dropped on the device
-      st = run_query(h, from_codes ? nullptr : centers.as<double>(), nullptr, nq, R, false, dq.as<uint32_t>(), did.as<uint32_t>(),
-                     dt.as<uint32_t>(), dd.as<double>(), hcap, &nh, nullptr);
-      h->sqrt_test = false;
-      h->self_first = HS_NO_SELF;
+      st = run_query(h, call, nq, dq.as<uint32_t>(), did.as<uint32_t>(), dt.as<uint32_t>(), dd.as<double>(), hcap,
+                     &nh, nullptr);
       if (st == HS_ERR_CAPACITY) {
         hcap = nh + nh / 8 + 1024;
         continue;

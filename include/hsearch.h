@@ -144,7 +144,8 @@ HS_API hs_status hs_set_hash_mode(hs_handle* h, int mode, double eps_scale);
  * equivalent paths (the tests run both and compare) or sizes a batch.  Unknown option / value out of range:
  * HS_ERR_INVALID.  Options that shape the index (HS_OPT_BUILD_GROUPING) take effect at the next build. */
 typedef enum hs_option {
-  HS_OPT_QUERY_BATCH = 1,    /* queries per internal batch of a query call; 0 (default) = by L and free HBM */
+  HS_OPT_QUERY_BATCH = 1,    /* queries per internal batch of a query call; 0 (default) = by L and free HBM;
+                                at most 2^31 / L - 1 (a probe's number carries a flag in bit 31) */
   HS_OPT_SEG_MODE = 2,       /* grouping of the probes by bucket: 0 by the bucket : probe ratio, 1 sort the
                                 probes, 2 counting sort over the bucket slots */
   HS_OPT_JOIN_RESIDENT = 3,  /* segments with few probing queries through hs_join8r_kernel: 0 by their share of

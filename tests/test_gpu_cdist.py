@@ -272,6 +272,14 @@ def test_bucket_partitioned_search_equals_the_unpartitioned_search(world):
         cand += got["cand"]
         parts.append(got)
     assert np.array_equal(cand, want["cand"])                    # ... and to some part
+    for mode in (1, 2):     # a partition groups its probes the same way whatever HS_OPT_SEG_MODE says
+        one.set_option("seg_mode", mode)
+        for r in range(world):
+            one.set_bucket_partition(r, world)
+            got = one.query(centers, R)
+            for f in ("q", "id", "table", "dist", "cand"):
+                assert np.array_equal(got[f], parts[r][f]), (mode, r, f)
+    one.set_option("seg_mode", 0)
     with pytest.raises(capi.HsError):
         one.set_bucket_partition(world, world)
     one.set_bucket_partition(0, 1)

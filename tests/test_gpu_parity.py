@@ -444,6 +444,83 @@ def test_multi_batch_queries_and_rebuild(oracle):
     eng.close()
 
 
+def test_one_handle_through_a_sequence_of_batches():
+    """One long-lived handle through a seeded sequence of calls that vary the batch count, the radius (wide
+    rows by radius once), points / codes / k-mer centres, the path switches, the bucket partition, with a
+    self-join and a rebuild in between: every call equals the same call on a fresh handle with the same
+    switches.  What a batch leaves for the next ones (capacity hint, resident share, pairs per item, the
+    hit-order fallback) may steer them, never change a result."""
+    k, K, L, W = 25, 6, 5, 140.0
+    a, b = synth.make_planes(k, K, L, W, seed=31)
+    rng = np.random.default_rng(35)
+    dbs = [synth.make_db(30000, k, seed=32), synth.make_db(22000, k, seed=33)]
+    for db in dbs:      # copies: pairs within every radius for the self-joins
+        db[rng.choice(len(db), 2000, replace=False)] = db[rng.choice(len(db), 2000)]
+    switches = ("join_resident", "seg_mode", "sync_items", "sort_hits", "recognise_kmers")
+    default = dict(join_resident=0, seg_mode=0, sync_items=0, sort_hits=0, recognise_kmers=1)
+    # (what, nq, R, switches, bucket partition); what: kmers (centres that are k-mers), points, codes,
+    # self (a self-join), rebuild (the other DB)
+    calls = [("kmers", 1, 40.0, {}, None),
+             ("codes", 300, 42.0, dict(join_resident=2), None),
+             ("points", 2500, 40.0, dict(seg_mode=1), None),
+             ("kmers", 2500, 58.0, {}, None),
+             ("self", 0, 40.0, {}, None),
+             ("kmers", 300, 40.0, dict(recognise_kmers=0, sync_items=1), None),
+             ("codes", 2500, 42.0, dict(seg_mode=2, sort_hits=1), None),
+             ("kmers", 1200, 40.0, dict(join_resident=1), (1, 3)),
+             ("codes", 1200, 42.0, dict(seg_mode=2), (2, 3)),
+             ("rebuild", 0, 0.0, {}, None),
+             ("points", 2500, 40.0, dict(seg_mode=2, join_resident=2), None),
+             ("codes", 1, 45.0, {}, None),
+             ("self", 0, 42.0, dict(join_resident=1), None),
+             ("kmers", 300, 40.0, dict(sort_hits=1), (0, 2)),
+             ("kmers", 2500, 40.0, {}, None)]
+    eng = Engine(k, K, L, W, a, b, options=dict(query_batch=700))
+    db = dbs[0]
+    eng.index_build(db)
+    for n_call, (what, nq, R, sw, part) in enumerate(calls):
+        if what == "rebuild":
+            db = dbs[1]
+            eng.index_build(db)
+            continue
+        opts = dict(default, **sw)
+        for name in switches:
+            eng.set_option(name, opts[name])
+        eng.set_bucket_partition(*(part or (0, 1)))
+        fresh = Engine(k, K, L, W, a, b, options=dict(query_batch=700, **opts))
+        fresh.index_build(db)
+        fresh.set_bucket_partition(*(part or (0, 1)))
+        if what == "self":
+            got, want, fields = eng.self_join(R), fresh.self_join(R), ("i", "j", "table", "dist")
+        else:
+            qcodes, _ = synth.make_query_codes(db, nq, seed=40 + n_call)
+            centers = synth.embed(qcodes)
+            if what == "points":
+                centers, _ = synth.make_queries(db, nq, seed=40 + n_call, jitter=0.2)
+
+            def run(e):
+                return e.query_codes(qcodes, R) if what == "codes" else e.query(centers, R)
+            got, want, fields = run(eng), run(fresh), ("q", "id", "table", "dist", "cand")
+        assert nq == 1 or len(want[fields[0]]) > 0, n_call
+        fresh.close()
+        for f in fields:
+            assert np.array_equal(got[f], want[f]), (n_call, what, f)
+    eng.close()
+
+
+def test_query_batch_option_bounded_by_the_probe_numbers():
+    """HS_OPT_QUERY_BATCH takes at most 2^31 / L - 1 queries: a batch's probe numbers carry a flag in bit 31."""
+    from hsearch_amd import capi
+    k, K, L, W = 25, 2, 32, 100.0
+    a, b = synth.make_planes(k, K, L, W)
+    eng = Engine(k, K, L, W, a, b)
+    eng.set_option("query_batch", (1 << 26) - 1)
+    for bad in (1 << 26, (1 << 27) - 1):
+        with pytest.raises(capi.HsError):
+            eng.set_option("query_batch", bad)
+    eng.close()
+
+
 def test_windows_build_matches_explicit_kmers(oracle):
     """the DB given as a concatenated residue buffer + sequence starts; the
     windows are enumerated on the device (kmer_search.cpp:64-83 order).  Must equal the index over
