@@ -15,7 +15,7 @@ _STATUS = ["HS_OK", "HS_ERR_INVALID", "HS_ERR_NO_DEVICE", "HS_ERR_HIP", "HS_ERR_
 _ALPHABET = "ARNDCQEGHILKMFPSTWYV"
 
 EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get_params", "hs_version",
-           "hs_set_verify_mode", "hs_set_hash_mode", "hs_set_option", "hs_set_bucket_partition", "hs_wait_event", "hs_set_planes", "hs_self_join", "hs_self_join_range", "hs_clustering",
+           "hs_set_verify_mode", "hs_set_hash_mode", "hs_set_option", "hs_set_bucket_partition", "hs_set_multiprobe", "hs_probe_buckets", "hs_wait_event", "hs_set_planes", "hs_self_join", "hs_self_join_range", "hs_clustering",
            "hs_clustering_begin", "hs_clustering_table_edges", "hs_clustering_table_apply",
            "hs_clustering_end",
            "hs_embed_codes", "hs_hash_codes", "hs_hash_points", "hs_key_string", "hs_key_fingerprint",
@@ -192,6 +192,7 @@ class Engine:
         self._lib = load(hooks)
         self.k, self.K, self.L, self.W = int(k), int(K), int(L), float(W)
         self.d = 8 * self.k
+        self.T = 0  # hs_set_multiprobe
         a = np.ascontiguousarray(a, dtype=np.float64)
         b = np.ascontiguousarray(b, dtype=np.float64)
         assert a.shape == (self.L, self.K, self.d), a.shape
@@ -240,6 +241,22 @@ class Engine:
     def set_bucket_partition(self, part, n_parts):
         """hs_set_bucket_partition: the handle's searches probe only the buckets of `part` of `n_parts` (1: all)."""
         self._check(self._lib.hs_set_bucket_partition(self._h, C.c_uint32(part), C.c_uint32(n_parts)))
+
+    def set_multiprobe(self, T):
+        """hs_set_multiprobe: the handle's searches also probe the T neighbouring buckets per table (0: one probe)."""
+        self._check(self._lib.hs_set_multiprobe(self._h, C.c_uint32(int(T))))
+        self.T = int(T)
+
+    def probe_buckets(self, centers):
+        """hs_probe_buckets: (buckets int32 [nq][L][1+T][K], valid uint8 [nq][L][1+T]) under the handle's T."""
+        centers = np.ascontiguousarray(centers, dtype=np.float64)
+        n = centers.shape[0]
+        assert centers.shape == (n, self.d)
+        P = self.T + 1
+        buckets = np.empty((n, self.L, P, self.K), dtype=np.int32)
+        valid = np.empty((n, self.L, P), dtype=np.uint8)
+        self._check(self._lib.hs_probe_buckets(self._h, _vp(centers), C.c_uint64(n), _vp(buckets), _vp(valid)))
+        return buckets, valid
 
     def wait_event(self, event_handle):
         """hs_wait_event: the library's stream waits for a hipEvent_t (int handle, e.g. torch.cuda.Event.cuda_event)."""

@@ -113,6 +113,10 @@ struct QueryCall {
   bool brute = false;
   uint32_t self_first = HS_NO_SELF;  // self-join: DB id of query 0
   bool sqrt_test = false;            // hit test sqrt(d2) <= R (hclust2.cpp:119-120) instead of d2 <= R*R
+  // multi-probe (mp_query): every row is one probe of a query, its bucket ints given ([nq][L][K], device) in
+  // place of the hash, and pre_valid[q L + l] == 0 an empty probe
+  const int32_t* pre_ints = nullptr;
+  const uint8_t* pre_valid = nullptr;
 };
 
 // What a handle learns from its batches to steer the next ones (plan_batch, the join launch); written by
@@ -183,6 +187,11 @@ struct hs_handle {
   // query workspace (grown on demand, reused across calls)
   DevBuf qints, qstart, qcount, nslices, slice_off, tq, prov, hit_key, hit_val, hit_key2, hit_val2,
       counters, temp, io_centers, io_q, io_id, io_table, io_dist, io_cand, io_codes, io_misc;
+  // multi-probe (hs_set_multiprobe): extra probes per table; a chunk's exact projections and fractions, its
+  // probes' bucket ints and flags, its queries once per probe, the probe rows' hits and candidate counts
+  uint32_t mp_T = 0;
+  uint64_t mp_room = 0;
+  DevBuf mp_pts, mp_codes, mp_ints, mp_frac, mp_vints, mp_valid, mp_rows, mp_q, mp_id, mp_table, mp_dist, mp_cand;
   DevBuf qcodes_buf, qembed;  // hs_query_codes: a batch's checked copy of the query codes; their embedding
                               // when no from-codes path applies
   HostBuf sj_host;  // hs_self_join_range: hits of one chunk on their way to the edge lists
@@ -776,7 +785,9 @@ void hs_destroy(hs_handle* h) {
                     &h->bs_keys2[1], &h->bs_iota2[0], &h->bs_iota2[1], &h->bs_keys_sorted, &h->bs_rle_unique,
                     &h->bs_rle_counts, &h->bs_small, &h->bs_sort_temp, &h->bs_slow_q, &h->all_codes,
                     &h->subset_ids, &h->qcodes_buf, &h->qembed, &h->seg_res, &h->seg_of, &h->t_rho, &h->rec_codes, &h->qpacked, &h->hit_rank, &h->hit_kv, &h->bs_fptab, &h->bs_blk,
-                    &h->bs_dk, &h->bs_hist, &h->bs_rank};
+                    &h->bs_dk, &h->bs_hist, &h->bs_rank, &h->mp_pts, &h->mp_codes, &h->mp_ints, &h->mp_frac,
+                    &h->mp_vints, &h->mp_valid, &h->mp_rows, &h->mp_q, &h->mp_id, &h->mp_table, &h->mp_dist,
+                    &h->mp_cand};
   for (DevBuf* bf : bufs) bf->release();
   h->sj_host.release();
   h->t_dirjump.release();
@@ -1247,6 +1258,7 @@ static hs_tables_dev probe_tabs(const hs_handle* h, const QueryCall& c, uint32_t
     for (int l = 0; l < HS_MAX_L; ++l) t.t[l].dir_rec = nullptr;
   t.part = c.self_first == HS_NO_SELF ? h->bucket_part : 0u;  // (searches only, not the self-joins)
   t.n_parts = c.self_first == HS_NO_SELF ? h->bucket_parts : 1u;
+  t.probe_valid = c.pre_valid;
   return t;
 }
 
@@ -2349,7 +2361,9 @@ static hs_status hash_and_probe(hs_handle* h, const QueryCall& c, const BatchPla
   HS_HIP(h, h->qcount.reserve(((size_t)b.nql + HS_QRANGE_PAD) * 4));
   for (DevBuf* d : {&h->nslices, &h->probe_slow, &h->slice_off}) HS_HIP(h, d->reserve(n1 * 4));
   HS_HIP(h, h->temp.reserve(hs_scan_u32_temp(n1) + 256));
-  if (p.ext_codes)
+  if (c.pre_ints)
+    HS_HIP(h, hipMemcpyAsync(h->qints.p, c.pre_ints, (size_t)b.nq * h->LK * 4, hipMemcpyDeviceToDevice, h->stream));
+  else if (p.ext_codes)
     HS_CHECK(hash_dispatch(h, b.qcodes, nullptr, b.nq, -1, h->qints.as<int32_t>(), h->LK, 2, h->stream));
   else if (!p.self_codes)
     HS_CHECK(hash_dispatch(h, nullptr, b.centers, b.nq, -1, h->qints.as<int32_t>(), h->LK, 2, h->stream));
@@ -2817,6 +2831,9 @@ static hs_status query_batch(hs_handle* h, const QueryCall& c, uint32_t nq, uint
   }
 }
 
+static hs_status mp_query(hs_handle* h, const QueryCall& c, uint64_t nq, uint32_t* d_hit_q, uint32_t* d_hit_id,
+                          uint32_t* d_hit_table, double* d_hit_dist, uint64_t cap, uint64_t* n_hits, uint64_t* d_cand);
+
 static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_hit_q, uint32_t* d_hit_id,
                            uint32_t* d_hit_table, double* d_hit_dist, uint64_t cap, uint64_t* n_hits, uint64_t* d_cand) {
   if (!h || !n_hits) return HS_ERR_INVALID;
@@ -2829,6 +2846,8 @@ static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_h
   if (!(c.R == c.R)) return fail(h, HS_ERR_INVALID, "R is NaN");
   hs_status st = ensure_device(h);
   if (st) return st;
+  if (h->mp_T && !c.brute && c.self_first == HS_NO_SELF && !c.pre_ints)
+    return mp_query(h, c, nq, d_hit_q, d_hit_id, d_hit_table, d_hit_dist, cap, n_hits, d_cand);
   memset(&h->prof, 0, sizeof(h->prof));
   HS_HIP(h, h->counters.reserve(256));
   HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
@@ -2869,7 +2888,8 @@ static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_h
         QB = (uint32_t)std::max<size_t>(QB, std::min<size_t>((size_t)1 << 20, fit));
       }
     }
-    if (h->knobs.query_batch) QB = h->knobs.query_batch;  // hs_set_option(HS_OPT_QUERY_BATCH) / HS_QUERY_BATCH
+    // hs_set_option(HS_OPT_QUERY_BATCH) / HS_QUERY_BATCH (multi-probe: in queries, each 1 + T probe rows here)
+    if (h->knobs.query_batch) QB = (uint32_t)std::min<uint64_t>((uint64_t)h->knobs.query_batch * (c.pre_ints ? h->mp_T + 1 : 1), 1u << 30);
     QB = std::min(QB, max_query_batch(h));
     uint32_t nqb = 0;
     for (uint64_t q0 = 0; q0 < nq; q0 += nqb) {
@@ -2880,6 +2900,8 @@ static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_h
       QueryCall bc = c;
       bc.centers = c.centers ? c.centers + q0 * h->d : nullptr;
       bc.codes = c.codes ? c.codes + q0 * h->p.k : nullptr;
+      bc.pre_ints = c.pre_ints ? c.pre_ints + q0 * h->LK : nullptr;
+      bc.pre_valid = c.pre_valid ? c.pre_valid + q0 * h->p.L : nullptr;
       st = query_batch(h, bc, nqb, (uint32_t)q0, d_cand ? d_cand + q0 * h->p.L : nullptr, &nh, cap ? &bout : nullptr);
       if (st == HS_SPLIT_BATCH) {
         // more filter survivors than the 32-bit list counter holds (a radius near the typical
@@ -2921,6 +2943,171 @@ static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_h
   h->prof.hits = total;
   *n_hits = total;
   if (total > cap) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
+  return HS_OK;
+}
+
+// The profile of a multi-probe call: the sum of its chunks' (the shape fields of the last one)
+static void add_profile(hs_profile& a, const hs_profile& b) {
+  a.ms_hash += b.ms_hash;
+  a.ms_sort += b.ms_sort;
+  a.ms_gather += b.ms_gather;
+  a.ms_probe += b.ms_probe;
+  a.ms_verify += b.ms_verify;
+  a.ms_finalize += b.ms_finalize;
+  a.ms_total += b.ms_total;
+  a.candidates += b.candidates;
+  a.provisional += b.provisional;
+  a.verify_launches += b.verify_launches;
+  a.join_batches += b.join_batches;
+  a.ms_join += b.ms_join;
+  a.join_items += b.join_items;
+  a.join_pairs += b.join_pairs;
+  a.join_pairs_issued += b.join_pairs_issued;
+  a.join_i8_batches += b.join_i8_batches;
+  a.hash_values += b.hash_values;
+  a.hash_flagged += b.hash_flagged;
+  a.join_row_bytes = b.join_row_bytes;
+  a.join_wide = b.join_wide;
+  a.join_items_resident += b.join_items_resident;
+  a.join_async_retries += b.join_async_retries;
+  a.queries_recognised += b.queries_recognised;
+}
+
+// The 1 + T probes of every (query, table) of n points (device): exact projections, then the probe sets, into
+// mp_vints / mp_valid at slot q sq + l sl + t st.  On the handle's stream.
+static hs_status mp_probes(hs_handle* h, const double* d_pts, uint64_t n, uint64_t sq, uint32_t sl, uint32_t st) {
+  const uint32_t P = h->mp_T + 1;
+  HS_HIP(h, h->mp_ints.reserve(std::max<size_t>(16, (size_t)n * h->LK * 4)));
+  HS_HIP(h, h->mp_frac.reserve(std::max<size_t>(16, (size_t)n * h->LK * 8)));
+  HS_HIP(h, h->mp_vints.reserve(std::max<size_t>(16, (size_t)n * P * h->LK * 4)));
+  HS_HIP(h, h->mp_valid.reserve(std::max<size_t>(16, (size_t)n * P * h->p.L)));
+  HS_HIP(h, hs_launch_mp_hash(d_pts, n, (int)h->p.k, h->aT.as<double>(), h->LK, h->b.as<double>(), h->p.W,
+                              h->mp_ints.as<int32_t>(), h->mp_frac.as<double>(), h->stream));
+  HS_HIP(h, hs_launch_mp_probe_sets(h->mp_ints.as<int32_t>(), h->mp_frac.as<double>(), n, (int)h->p.K, (int)h->p.L,
+                                    (int)h->mp_T, h->mp_vints.as<int32_t>(), h->mp_valid.as<uint8_t>(), sq, sl, st,
+                                    h->stream));
+  return HS_OK;
+}
+
+// A search with T extra probes per table.  The queries run in chunks; in a chunk every query becomes 1 + T
+// probe rows (row q P + t: probe t of every table), which the one-probe search below takes like queries of their
+// own -- bucket ints given, empty probes flagged -- so every filter, grouping and partition applies unchanged.  A
+// row reports an id at the smallest table whose probe t holds it; the rows' hits, mapped back to their query,
+// keep per (query, id) the smallest table (hs_merge_first_table_dev): the first-seen rule over all (table, probe)
+// pairs, in the order (query, table, id).
+static hs_status mp_query(hs_handle* h, const QueryCall& c, uint64_t nq, uint32_t* d_hit_q, uint32_t* d_hit_id,
+                          uint32_t* d_hit_table, double* d_hit_dist, uint64_t cap, uint64_t* n_hits, uint64_t* d_cand) {
+  const uint32_t P = h->mp_T + 1, L = h->p.L;
+  const int k = (int)h->p.k, d = h->d;
+  hs_profile acc;
+  memset(&acc, 0, sizeof(acc));
+  uint64_t total = 0;
+  const uint64_t NC = std::max<uint64_t>(1, (1u << 19) / P);  // queries per chunk: 2^19 probe rows
+  uint64_t nc = 0;
+  for (uint64_t q0 = 0; q0 < nq; q0 += nc) {
+    nc = std::min(NC, nq - q0);
+    const uint64_t nv = nc * P;
+    HS_HIP(h, hipEventRecord(h->ev[0], h->stream));
+    const double* pts = c.centers ? c.centers + q0 * d : nullptr;
+    if (c.codes) {
+      // (a checked copy: the embedding indexes the coordinate table; the search below reports bad codes itself)
+      HS_HIP(h, h->mp_codes.reserve((size_t)nc * k + 16));
+      HS_HIP(h, h->mp_pts.reserve((size_t)nc * d * 8));
+      uint32_t* const d_bad = reinterpret_cast<uint32_t*>(h->mp_codes.as<uint8_t>() + (((size_t)nc * k + 3) & ~(size_t)3));
+      HS_HIP(h, hs_launch_check_codes(c.codes + q0 * k, (uint64_t)nc * k, h->alphabet, h->mp_codes.as<uint8_t>(), d_bad,
+                                      h->stream));
+      HS_HIP(h, hs_launch_embed(h->mp_codes.as<uint8_t>(), nc, k, h->coords.as<double>(), h->mp_pts.as<double>(),
+                                h->stream));
+      pts = h->mp_pts.as<double>();
+    }
+    HS_CHECK(mp_probes(h, pts, nc, (uint64_t)P * L, 1, L));
+    HS_HIP(h, hipEventRecord(h->ev[1], h->stream));
+    QueryCall vc = c;
+    if (c.codes) {
+      HS_HIP(h, h->mp_rows.reserve((size_t)nv * k));
+      HS_HIP(h, hs_launch_mp_repeat_u8(c.codes + q0 * k, nv, (uint32_t)k, P, h->mp_rows.as<uint8_t>(), h->stream));
+      vc.codes = h->mp_rows.as<uint8_t>();
+    } else {
+      HS_HIP(h, h->mp_rows.reserve((size_t)nv * d * 8));
+      HS_HIP(h, hs_launch_mp_repeat_f64(c.centers + q0 * d, nv, (uint32_t)d, P, h->mp_rows.as<double>(), h->stream));
+      vc.centers = h->mp_rows.as<double>();
+    }
+    vc.pre_ints = h->mp_vints.as<int32_t>();
+    vc.pre_valid = h->mp_valid.as<uint8_t>();
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    const float ms_probes = ev_ms(h, 0, 1);
+    if (d_cand) HS_HIP(h, h->mp_cand.reserve((size_t)nv * L * 8));
+    uint64_t nh = 0;
+    h->mp_room = std::max<uint64_t>(h->mp_room, 1u << 16);
+    for (;;) {
+      HS_HIP(h, h->mp_q.reserve(h->mp_room * 4));
+      HS_HIP(h, h->mp_id.reserve(h->mp_room * 4));
+      HS_HIP(h, h->mp_table.reserve(h->mp_room * 4));
+      HS_HIP(h, h->mp_dist.reserve(h->mp_room * 8));
+      const hs_status st = run_query(h, vc, nv, h->mp_q.as<uint32_t>(), h->mp_id.as<uint32_t>(),
+                                     h->mp_table.as<uint32_t>(), h->mp_dist.as<double>(), h->mp_room, &nh,
+                                     d_cand ? h->mp_cand.as<uint64_t>() : nullptr);
+      if (st == HS_ERR_CAPACITY && nh > h->mp_room) {
+        h->mp_room = nh + nh / 4;
+        continue;
+      }
+      if (st) return st;
+      break;
+    }
+    add_profile(acc, h->prof);
+    acc.ms_hash += ms_probes;
+    acc.ms_total += ms_probes;
+    HS_HIP(h, hs_launch_mp_map_q(h->mp_q.as<uint32_t>(), nh, P, (uint32_t)q0, h->stream));
+    uint64_t kept = 0;
+    HS_CHECK(hs_merge_first_table_dev(h, h->mp_q.as<uint32_t>(), h->mp_id.as<uint32_t>(), h->mp_table.as<uint32_t>(),
+                                      h->mp_dist.as<double>(), nh, &kept));
+    if (kept && total + kept <= cap) {
+      HS_HIP(h, hipMemcpyAsync(d_hit_q + total, h->mp_q.p, kept * 4, hipMemcpyDeviceToDevice, h->stream));
+      HS_HIP(h, hipMemcpyAsync(d_hit_id + total, h->mp_id.p, kept * 4, hipMemcpyDeviceToDevice, h->stream));
+      if (d_hit_table)
+        HS_HIP(h, hipMemcpyAsync(d_hit_table + total, h->mp_table.p, kept * 4, hipMemcpyDeviceToDevice, h->stream));
+      HS_HIP(h, hipMemcpyAsync(d_hit_dist + total, h->mp_dist.p, kept * 8, hipMemcpyDeviceToDevice, h->stream));
+    }
+    total += kept;
+    if (d_cand) HS_HIP(h, hs_launch_mp_cand(h->mp_cand.as<uint64_t>(), nc, L, P, d_cand + q0 * L, h->stream));
+  }
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  acc.hits = total;
+  h->prof = acc;
+  *n_hits = total;
+  if (total > cap) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
+  return HS_OK;
+}
+
+hs_status hs_set_multiprobe(hs_handle* h, uint32_t extra_probes) {
+  if (!h) return HS_ERR_INVALID;
+  if (extra_probes > 63) return fail(h, HS_ERR_INVALID, "hs_set_multiprobe: at most 63 extra probes");
+  uint64_t sets = 1;  // 3^K - 1 valid perturbation sets exist
+  for (uint32_t j = 0; j < h->p.K && sets <= 64; ++j) sets *= 3;
+  if (sets - 1 < extra_probes)
+    return fail(h, HS_ERR_INVALID, "hs_set_multiprobe: more extra probes than the 3^K - 1 perturbation sets of K");
+  h->mp_T = extra_probes;
+  return HS_OK;
+}
+
+hs_status hs_probe_buckets(hs_handle* h, const double* centers, uint64_t nq, int32_t* buckets, uint8_t* valid) {
+  if (!h || (nq && (!centers || !buckets || !valid))) return HS_ERR_INVALID;
+  if (!nq) return HS_OK;
+  if (nq >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nq must be < 2^27 per call");
+  hs_status st = ensure_device(h);
+  if (st) return st;
+  const uint32_t P = h->mp_T + 1, L = h->p.L;
+  const size_t in_bytes = (size_t)nq * h->d * 8;
+  HS_HIP(h, h->io_centers.reserve(in_bytes));
+  HS_HIP(h, hipMemcpyAsync(h->io_centers.p, centers, in_bytes, hipMemcpyHostToDevice, h->stream));
+  HS_HIP(h, hipEventRecord(h->ev[0], h->stream));
+  HS_CHECK(mp_probes(h, h->io_centers.as<double>(), nq, (uint64_t)L * P, P, 1));
+  HS_HIP(h, hipEventRecord(h->ev[1], h->stream));
+  HS_HIP(h, hipMemcpyAsync(buckets, h->mp_vints.p, (size_t)nq * L * P * h->p.K * 4, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipMemcpyAsync(valid, h->mp_valid.p, (size_t)nq * L * P, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  memset(&h->prof, 0, sizeof(h->prof));
+  h->prof.ms_hash = h->prof.ms_total = ev_ms(h, 0, 1);
   return HS_OK;
 }
 

@@ -148,6 +148,8 @@ struct hs_tables_dev {
   uint32_t part, n_parts, q_first;
   const uint32_t* probe_list;
   uint32_t n_list;
+  // multi-probe (hs_set_multiprobe): probe_valid[ql] == 0 marks an empty probe, which finds no bucket; null: all valid
+  const uint8_t* probe_valid = nullptr;
 };
 // A cheap hash of a probe's K bucket ints (t[0], t[stride], ...): what decides the part of a probe.  (Not the
 // key fingerprint: that one walks the decimal characters of every int, ~ 10 x the instructions, and seven
@@ -276,6 +278,27 @@ hipError_t hs_launch_proj_fix(const uint8_t* d_codes, const double* d_pts, uint6
                               int ldf, const double* d_b, int F, double W, const double* d_coords,
                               int32_t* d_out, int out_stride, const uint2* d_flags, uint32_t flag_cap,
                               const uint32_t* d_flag_count, hipStream_t s);
+
+// ---- multi-probe (hs_multiprobe.hip) ----------------------------------------------------------------
+// the exact projections of n points: d_ints[i][f] = floor(v), d_frac[i][f] = v - floor(v), v = (dot + b) / W in the
+// reference's order; d_aT = the transposed planes [8k][F]
+hipError_t hs_launch_mp_hash(const double* d_pts, uint64_t n, int k, const double* d_aT, int F, const double* d_b,
+                             double W, int32_t* d_ints, double* d_frac, hipStream_t s);
+// every (point, table)'s 1 + T probes (include/hsearch.h hs_probe_buckets): probe t of (q, l) goes to slot
+// o = q sq + l sl + t st, its K ints at d_out[o K ..], its flag at d_valid[o]
+hipError_t hs_launch_mp_probe_sets(const int32_t* d_ints, const double* d_frac, uint64_t n, int K, int L, int T,
+                                   int32_t* d_out, uint8_t* d_valid, uint64_t sq, uint32_t sl, uint32_t st,
+                                   hipStream_t s);
+// d_out[r][:] = d_in[r / P][:], row elements per row
+hipError_t hs_launch_mp_repeat_f64(const double* d_in, uint64_t n_out_rows, uint32_t row, uint32_t P, double* d_out,
+                                   hipStream_t s);
+hipError_t hs_launch_mp_repeat_u8(const uint8_t* d_in, uint64_t n_out_rows, uint32_t row, uint32_t P, uint8_t* d_out,
+                                  hipStream_t s);
+// d_q[i] = q_base + d_q[i] / P
+hipError_t hs_launch_mp_map_q(uint32_t* d_q, uint64_t n, uint32_t P, uint32_t q_base, hipStream_t s);
+// d_cand[q][l] = sum over t < P of d_vcand[q P + t][l]
+hipError_t hs_launch_mp_cand(const uint64_t* d_vcand, uint64_t nq, uint32_t L, uint32_t P, uint64_t* d_cand,
+                             hipStream_t s);
 
 // ---- kernel launchers (hs_kernels.hip) -----------------------------------------------------------
 hipError_t hs_launch_embed(const uint8_t* d_codes, uint64_t n, int k, const double* d_coords,

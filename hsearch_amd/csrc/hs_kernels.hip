@@ -401,6 +401,7 @@ __global__ __launch_bounds__(256) void hs_probe_kernel(hs_tables_dev tabs,
       const bool giant = glo < tb.n_giant && tb.giant_key[glo] == th;
       mine = hs_probe_part(th, giant, tabs.q_first + ql / (uint32_t)L, tabs.n_parts) == tabs.part;
     }
+    if (tabs.probe_valid && !tabs.probe_valid[ql]) mine = false;  // an empty multi-probe slot
     uint64_t hk = hs_key_init(seed);
     for (int j = 0; j < K; ++j) hk = hs_key_put_int(hk, t[256 * j]);
     const uint64_t key = hs_key_fin(hk);

@@ -117,6 +117,8 @@ struct HandleCloser {
 // how the rank threads exchange hits (SetShardTransport) and what a rank holds (SetShardPartition)
 ShardTransport g_shard_transport = kTransportRccl;
 ShardPartition g_shard_partition = kPartitionQueries;
+// T extra probes per table of the running Search / SearchSharded call (hs_set_multiprobe)
+uint32_t g_probes = 0;
 
 // Cost of every table for the table-partitioned layout, from a sample of the DB's k-mers: the sum over the
 // table's buckets of (sample k-mers in the bucket)^2 -- for queries distributed like the DB, proportional to
@@ -200,6 +202,10 @@ int RunSearch(hs_params prm, const Planes& planes, const double* coords,
     }
     if (st != HS_OK) {
       *msg = std::string("hs_create: ") + (*h ? hs_last_error(*h) : "no usable gfx950 device");
+      hs_destroy(*h);
+      *h = nullptr;
+    } else if (g_probes && (st = hs_set_multiprobe(*h, g_probes)) != HS_OK) {
+      *msg = std::string("hs_set_multiprobe: ") + hs_last_error(*h);
       hs_destroy(*h);
       *h = nullptr;
     }
@@ -347,9 +353,9 @@ int Search(const std::vector<Point>& kmers, const std::vector<Point>& centers,
            const std::vector<std::string>& kmer_names, const std::vector<std::string>& center_names,
            const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
            const double& hash_R, const std::string& output_file, const Planes& planes, int device,
-           std::string* err, std::vector<uint64_t>* table_sizes) {
+           std::string* err, std::vector<uint64_t>* table_sizes, uint32_t probes) {
   return SearchSharded(kmers, centers, kmer_names, center_names, hash_K, hash_L, hash_W, hash_R, output_file,
-                       planes, std::vector<int>(1, device), false, err, table_sizes);
+                       planes, std::vector<int>(1, device), false, err, table_sizes, probes);
 }
 
 int SearchSharded(const std::vector<Point>& kmers, const std::vector<Point>& centers,
@@ -357,7 +363,11 @@ int SearchSharded(const std::vector<Point>& kmers, const std::vector<Point>& cen
                   const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
                   const double& hash_R, const std::string& output_file, const Planes& planes,
                   const std::vector<int>& devices, bool use_comm, std::string* err,
-                  std::vector<uint64_t>* table_sizes) {
+                  std::vector<uint64_t>* table_sizes, uint32_t probes) {
+  struct ProbesScope {
+    explicit ProbesScope(uint32_t t) { g_probes = t; }
+    ~ProbesScope() { g_probes = 0; }
+  } probes_scope(probes);
   const uint32_t dim = planes.dim;
   if (dim == 0 || dim % 8 != 0 || planes.K != hash_K || planes.L != hash_L || planes.W != hash_W) {
     if (err) *err = "planes do not match (dim, K, L, W)";

@@ -58,7 +58,7 @@ int Search(const std::vector<Point>& kmers, const std::vector<Point>& centers,
            const std::vector<std::string>& kmer_names, const std::vector<std::string>& center_names,
            const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
            const double& hash_R, const std::string& output_file, const Planes& planes, int device,
-           std::string* err, std::vector<uint64_t>* table_sizes = nullptr);
+           std::string* err, std::vector<uint64_t>* table_sizes = nullptr, uint32_t probes = 0);
 
 // How the rank threads of the *Sharded() functions exchange their hits: RCCL over xGMI (one rank per
 // GPU; the default), or host memory between rank threads whose `devices` may repeat -- the whole rank
@@ -79,6 +79,8 @@ void SetShardTransport(ShardTransport t);
 enum ShardPartition { kPartitionQueries = 0, kPartitionTables = 1, kPartitionBuckets = 2 };
 void SetShardPartition(ShardPartition p);
 
+// probes (Search, SearchSharded): T extra buckets per table (hs_set_multiprobe, multi-probe LSH); 0 = the
+// reference's one probe.  Every partition passes it to every rank's handle.
 // Search() spread over the GPUs `devices` of this node: one host thread and one handle
 // per GPU, the index replicated (built on every GPU), centre i searched by the rank owning its
 // contiguous block (hs_shard_bounds), the hits all-gathered over RCCL (include/hsearch_dist.h) and
@@ -89,7 +91,7 @@ int SearchSharded(const std::vector<Point>& kmers, const std::vector<Point>& cen
                   const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
                   const double& hash_R, const std::string& output_file, const Planes& planes,
                   const std::vector<int>& devices, bool use_comm, std::string* err,
-                  std::vector<uint64_t>* table_sizes = nullptr);
+                  std::vector<uint64_t>* table_sizes = nullptr, uint32_t probes = 0);
 
 // The planes file `--planes-out` writes and `--planes` reads: binary doubles a[L][K][dim], b[L][K].
 bool ReadPlanesFile(const std::string& path, uint32_t dim, uint32_t K, uint32_t L, double W, Planes* planes,

@@ -55,6 +55,7 @@ const Opt kOpts[] = {
     {"device", 'G', "GPU ordinal (the first one with --gpus) [0]", false},
     {"gpus", 'N', "shard the centres over this many GPUs, hits all-gathered over RCCL [off: one GPU, no communicator]", false},
     {"partition", 'Y', "with --gpus: queries (every GPU the whole index and a block of the centres, the default), tables (every GPU a subset of the L tables over all k-mers and all centres) or buckets (every GPU the whole index, all centres and its share of the buckets); same output", false},
+    {"probes", 'M', "multi-probe LSH: look in this many extra buckets per table, 0..63 (points database only) [0]", false},
     {"transport", 'X', "with --gpus: rccl (one rank per GPU, the default) or loopback (host memory between the rank threads, all ranks on --device: the rank protocol on a box with fewer GPUs)", false},
     {"centers-as-points", 'E', "k-mer centres over a FASTA database: send them embedded (8k doubles each) instead of as residue codes [0]", false},
     {"planes", 'p', "read the planes from this file (as written by --planes-out) instead of drawing them", false},
@@ -224,6 +225,15 @@ int main(int argc, const char* argv[]) {
       printf("gpus = %d (%d ranks on device %d, hits exchanged through host memory)\n", n_gpus, n_gpus, device);
     else if (use_comm)
       printf("gpus = %d (devices %d..%d, RCCL all-gather of hits)\n", n_gpus, device, device + n_gpus - 1);
+    const int probes = val.count("probes") ? atoi(val["probes"].c_str()) : 0;
+    if (probes < 0 || probes > 63) {
+      fprintf(stderr, "ERROR: --probes must be 0..63\n");
+      return EXIT_FAILURE;
+    }
+    if (probes && fasta_db) {
+      fprintf(stderr, "ERROR: --probes needs a points database\n");
+      return EXIT_FAILURE;
+    }
     struct timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     std::string err;
@@ -241,7 +251,7 @@ int main(int argc, const char* argv[]) {
                                                       ? nullptr : &center_codes)
                  : hsearch::SearchSharded(kmers, centers, kmer_names, center_names, hash_K, hash_L, hash_W,
                                           hash_R, val["output"], planes, devices, use_comm, &err,
-                                          &table_sizes);
+                                          &table_sizes, (uint32_t)probes);
     if (fasta_db && st == 0) std::cout << "number of kmers " << n_windows << std::endl;
     if (st != 0) {
       fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), st);

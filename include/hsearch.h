@@ -191,6 +191,28 @@ HS_API hs_status hs_set_option(hs_handle* h, int option, int64_t value);
  * each meets 1/n of the probes with all the queries there are per bucket (hs_comm_query_buckets in
  * include/hsearch_dist.h).  n_parts = 1 (part 0): everything, the default. */
 HS_API hs_status hs_set_bucket_partition(hs_handle* h, uint32_t part, uint32_t n_parts);
+/* Multi-probe LSH (Lv et al., VLDB 2007) -- like the bucket partition this CHANGES what a query call returns.  With
+ * extra_probes = T > 0 the searches of this handle (hs_query*, hs_query_dev, hs_query_codes*; NOT hs_self_join*,
+ * hs_clustering* or hs_bruteforce*, which ignore the setting) look, in every table, in the query's own bucket and
+ * in the T neighbouring buckets it is most likely to have neighbours in:
+ *   1. v_j = (dot_j + b_j) / W in the reference's fp64 order (lsh.hpp:33-49), h_j = floor(v_j), x_j = v_j - h_j;
+ *   2. the 2K boundary distances z(j,-1) = x_j, z(j,+1) = 1 - x_j, sorted ascending by (z, j, delta);
+ *   3. a perturbation set A (sorted indices, a 64-bit mask) scores sum of z_i * z_i over A in ascending i, each
+ *      product and sum rounded; it is valid unless it holds both deltas of one j;
+ *   4. a min-heap on (score, mask) starts with {0}; a pop with largest element m pushes shift (m -> m + 1) and
+ *      expand (m + 1 added) while m + 1 < 2K, and a valid pop is emitted; generation ends after T emitted sets or
+ *      4 (T + 1) pops.  Slots left over are empty probes, which find no bucket;
+ *   5. probe 0 is the home bucket h, probe t >= 1 is h + delta over the t-th emitted set.
+ * A hit is (q, id) with id in any probed bucket and d2 <= R*R, reported with the smallest table l in which some
+ * probe of q holds it, in the order (query, table, id); cand[q][l] sums the sizes of table l's probed buckets.
+ * With T > 0 the queries' bucket ints come from the exact fp64 pass whatever hs_set_hash_mode says.  0 <= T <= 63
+ * and T <= 3^K - 1, else HS_ERR_INVALID.  The setting belongs to the handle: 0 by default, kept across
+ * hs_index_build / hs_index_load / hs_set_planes, never written into index files.  T = 0 is the one-probe search. */
+HS_API hs_status hs_set_multiprobe(hs_handle* h, uint32_t extra_probes);
+/* The probe sequence of nq points (host pointers, centers [nq][d]) under the handle's T (P = 1 + T):
+ * buckets[nq][L][P][K] the bucket ints each probe looks up, in probe order; valid[nq][L][P] 0 for the empty slots
+ * of rule 4 (their ints repeat the home bucket's).  With T = 0 buckets equals hs_hash_points. */
+HS_API hs_status hs_probe_buckets(hs_handle* h, const double* centers, uint64_t nq, int32_t* buckets, uint8_t* valid);
 /* The library's work after this call starts only once `hip_event` (a hipEvent_t the caller has recorded on a
  * stream of its own) has completed: the device-side alternative to draining that stream before a _dev call. */
 HS_API hs_status hs_wait_event(hs_handle* h, void* hip_event);
