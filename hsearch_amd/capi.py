@@ -22,7 +22,8 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_key_strings_equal", "hs_index_build", "hs_index_build_subset", "hs_index_build_windows", "hs_index_shard_begin", "hs_index_shard_hash_dev", "hs_index_shard_group_dev",
            "hs_index_shard_tuples_dev", "hs_index_shard_finish_dev", "hs_index_shard_end", "hs_index_save", "hs_index_load", "hs_index_file_check", "hs_klsh_draw_planes", "hs_klsh_codes",
            "hs_index_info_get", "hs_query", "hs_query_dev", "hs_query_codes", "hs_query_codes_dev", "hs_bruteforce",
-           "hs_bruteforce_topk", "hs_merge_first_table_dev"]
+           "hs_bruteforce_topk", "hs_merge_first_table_dev", "hs_query_radii", "hs_query_radii_dev",
+           "hs_bruteforce_radii"]
 
 
 class HsError(RuntimeError):
@@ -94,6 +95,16 @@ def load(hooks=False):
         lib.hs_key_string.restype = C.c_uint32
         lib.hs_key_fingerprint.restype = C.c_uint64
         lib.hs_key_strings_equal.restype = C.c_int
+        # per-query radii: (h, centers, qcodes, nq, radii, hit_q, hit_id, hit_table, hit_dist, cap, n_hits, cand)
+        # (HSEARCH_AMD_LIB may name an older build without them: its calls then fail by name, not here)
+        if hasattr(lib, "hs_query_radii"):
+            for fn in (lib.hs_query_radii, lib.hs_query_radii_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
+            lib.hs_bruteforce_radii.restype = C.c_int
+            lib.hs_bruteforce_radii.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         _libs[hooks] = lib
     return _libs[hooks]
 
@@ -472,6 +483,45 @@ class Engine:
         self._check(st)
         return int(n.value)
 
+    def query_radii(self, queries, radii, codes=False, cap=None, want_cand=True):
+        """hs_query_radii: query q searched at radii[q]; queries are points [nq][d], or with codes=True residue
+        codes [nq][k].  The same result dict as query()."""
+        queries = np.ascontiguousarray(queries, dtype=np.uint8 if codes else np.float64)
+        radii = np.ascontiguousarray(radii, dtype=np.float64)
+        nq = queries.shape[0]
+        assert queries.shape == (nq, self.k if codes else self.d) and radii.shape == (nq,)
+        cap = int(cap) if cap is not None else max(1024, 64 * nq)
+        while True:
+            hq = np.empty(cap, dtype=np.uint32)
+            hid = np.empty(cap, dtype=np.uint32)
+            ht = np.empty(cap, dtype=np.uint32)
+            hd = np.empty(cap, dtype=np.float64)
+            cand = np.zeros((nq, self.L), dtype=np.uint64) if want_cand else None
+            n = C.c_uint64(0)
+            st = self._lib.hs_query_radii(self._h, None if codes else _vp(queries), _vp(queries) if codes else None,
+                                          nq, _vp(radii), _vp(hq), _vp(hid), _vp(ht), _vp(hd), cap, C.byref(n),
+                                          _vp(cand) if want_cand else None)
+            if st == HS_ERR_CAPACITY:
+                cap = int(n.value)
+                continue
+            self._check(st)
+            n = int(n.value)
+            return dict(q=hq[:n], id=hid[:n], table=ht[:n], dist=hd[:n], cand=cand)
+
+    def query_radii_dev(self, d_queries_ptr, nq, d_radii_ptr, d_q, d_id, d_table, d_dist, cap, d_cand=None,
+                        codes=False):
+        """hs_query_radii_dev (device pointers as ints); as query_dev, with float64 radii [nq] on the device."""
+        n = C.c_uint64(0)
+        st = self._lib.hs_query_radii_dev(self._h, None if codes else d_queries_ptr, d_queries_ptr if codes else None,
+                                          nq, d_radii_ptr, d_q, d_id, d_table, d_dist, cap, C.byref(n),
+                                          d_cand if d_cand else None)
+        if st == HS_ERR_CAPACITY:
+            e = HsError(st, self._lib.hs_last_error(self._h).decode())
+            e.needed = int(n.value)
+            raise e
+        self._check(st)
+        return int(n.value)
+
     def merge_first_table_dev(self, d_q, d_id, d_table, d_dist, n):
         """hs_merge_first_table_dev (device pointers as ints; in place): the number of tuples kept."""
         n_out = C.c_uint64(0)
@@ -491,6 +541,27 @@ class Engine:
             n = C.c_uint64(0)
             st = self._lib.hs_bruteforce(self._h, _vp(centers), C.c_uint64(nq), C.c_double(R),
                                          _vp(hq), _vp(hid), _vp(hd), C.c_uint64(cap), C.byref(n))
+            if st == HS_ERR_CAPACITY:
+                cap = int(n.value)
+                continue
+            self._check(st)
+            n = int(n.value)
+            return dict(q=hq[:n], id=hid[:n], dist=hd[:n])
+
+    def bruteforce_radii(self, centers, radii, cap=None):
+        """hs_bruteforce_radii: brute force with centre q searched at radii[q]."""
+        centers = np.ascontiguousarray(centers, dtype=np.float64)
+        radii = np.ascontiguousarray(radii, dtype=np.float64)
+        nq = centers.shape[0]
+        assert centers.shape == (nq, self.d) and radii.shape == (nq,)
+        cap = int(cap) if cap is not None else max(1024, 64 * nq)
+        while True:
+            hq = np.empty(cap, dtype=np.uint32)
+            hid = np.empty(cap, dtype=np.uint32)
+            hd = np.empty(cap, dtype=np.float64)
+            n = C.c_uint64(0)
+            st = self._lib.hs_bruteforce_radii(self._h, _vp(centers), nq, _vp(radii), _vp(hq), _vp(hid), _vp(hd),
+                                               cap, C.byref(n))
             if st == HS_ERR_CAPACITY:
                 cap = int(n.value)
                 continue

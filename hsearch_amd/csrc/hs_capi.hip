@@ -109,7 +109,7 @@ struct Knobs {
 struct QueryCall {
   const double* centers = nullptr;
   const uint8_t* codes = nullptr;  // queries given as residue codes [nq][k] (hs_query_codes); centers unused
-  double R = 0.0;
+  double R = 0.0;                  // with radii: the largest |radii[q]| of the call, what plan_batch decides from
   bool brute = false;
   uint32_t self_first = HS_NO_SELF;  // self-join: DB id of query 0
   bool sqrt_test = false;            // hit test sqrt(d2) <= R (hclust2.cpp:119-120) instead of d2 <= R*R
@@ -117,6 +117,8 @@ struct QueryCall {
   // place of the hash, and pre_valid[q L + l] == 0 an empty probe
   const int32_t* pre_ints = nullptr;
   const uint8_t* pre_valid = nullptr;
+  // hs_query_radii: every query's own radius ([nq], device); null: R for all.  Searches and brute force only.
+  const double* radii = nullptr;
 };
 
 // What a handle learns from its batches to steer the next ones (plan_batch, the join launch); written by
@@ -133,7 +135,8 @@ struct BatchHistory {
   double resident_share = -1.0;
   uint32_t resident_age = 0;  // joined batches since it was measured (measured again every 64)
   uint32_t resident_nq = 0;   // ... on a batch of this many queries (a batch half / twice that size measures anew)
-  // the last batch that ordered its hits itself had to fall back to the sort, at this radius
+  // the last batch that ordered its hits itself had to fall back to the sort, at this radius (NaN after a
+  // batch with per-query radii: such a batch neither leaves a radius to match nor matches one)
   bool order_failed = false;
   double order_failed_R = 0.0;
 };
@@ -192,6 +195,8 @@ struct hs_handle {
   uint32_t mp_T = 0;
   uint64_t mp_room = 0;
   DevBuf mp_pts, mp_codes, mp_ints, mp_frac, mp_vints, mp_valid, mp_rows, mp_q, mp_id, mp_table, mp_dist, mp_cand;
+  DevBuf mp_radii;   // ... and, for a call with per-query radii, the probe rows' radii
+  DevBuf io_radii;   // hs_query_radii: the radii on the device; hs_query_radii_dev: {max |radius|, NaN flag}
   DevBuf qcodes_buf, qembed;  // hs_query_codes: a batch's checked copy of the query codes; their embedding
                               // when no from-codes path applies
   HostBuf sj_host;  // hs_self_join_range: hits of one chunk on their way to the edge lists
@@ -270,12 +275,7 @@ float ev_ms(hs_handle* h, int i0, int i1) {
 }
 
 // smallest float >= x (x >= 0), then one more ulp: the fp32 filter bound must never undercut.
-float filter_bound(double r2) {
-  double hi = r2 * (1.0 + 1e-5) + 1e-30;
-  float f = (float)hi;
-  if ((double)f < hi) f = nextafterf(f, INFINITY);
-  return nextafterf(f, INFINITY);
-}
+float filter_bound(double r2) { return hs_filter_bound(r2); }
 
 // The index is about to change (or go): nothing learnt from batches against the old one may size or
 // steer batches against the new one (a stale capacity hint made the first batches after a rebuild to
@@ -787,7 +787,7 @@ void hs_destroy(hs_handle* h) {
                     &h->subset_ids, &h->qcodes_buf, &h->qembed, &h->seg_res, &h->seg_of, &h->t_rho, &h->rec_codes, &h->qpacked, &h->hit_rank, &h->hit_kv, &h->bs_fptab, &h->bs_blk,
                     &h->bs_dk, &h->bs_hist, &h->bs_rank, &h->mp_pts, &h->mp_codes, &h->mp_ints, &h->mp_frac,
                     &h->mp_vints, &h->mp_valid, &h->mp_rows, &h->mp_q, &h->mp_id, &h->mp_table, &h->mp_dist,
-                    &h->mp_cand};
+                    &h->mp_cand, &h->mp_radii, &h->io_radii};
   for (DevBuf* bf : bufs) bf->release();
   h->sj_host.release();
   h->t_dirjump.release();
@@ -2246,7 +2246,7 @@ static BatchPlan plan_batch(const hs_handle* h, const QueryCall& c, uint32_t nq,
   // the batch orders its hits itself (bucket by query, no sort, no host count); not tried again at a
   // radius at which the previous batch had a query with too many hits for it (the attempt costs 10 % of
   // such a batch -- k = 15 at the C2 sizes, 545 hits per query)
-  p.order_here = ordered_out && !h->knobs.sort_hits && !(m.order_failed && m.order_failed_R == c.R);
+  p.order_here = ordered_out && !h->knobs.sort_hits && !(m.order_failed && !c.radii && m.order_failed_R == c.R);
   p.xcd_run = h->knobs.join_xcd_run;
   return p;
 }
@@ -2262,6 +2262,7 @@ struct Batch {
   const uint32_t* owned = nullptr;   // bucket partition: the probes of this part, ascending (device)
   uint32_t n_owned = 0;
   uint32_t n_items = 0, n_slices = 1;
+  const double* radii = nullptr;     // the batch's slice of the call's per-query radii (device), or null: r2 for all
 };
 
 // The join filter's query rows, on stream s: from the codes, int8 from the centres, or fp16
@@ -2271,11 +2272,11 @@ static hipError_t launch_qrows(hs_handle* h, const BatchPlan& p, const Batch& b,
   if (p.self_codes || p.ext_codes)
     return hs_launch_qprep8_codes(b.qcodes, b.nq, k, p.wide, b.r2, h->coords.as<double>(), h->jtab8.p,
                                   h->jtab8.as<char>() + 1024, h->jtab8.as<char>() + 1536, h->jtab8.as<float>() + 128,
-                                  h->c16.p, p.refine ? h->c8b.p : nullptr, s);
+                                  h->c16.p, p.refine ? h->c8b.p : nullptr, s, b.radii);
   if (p.use_i8)
     return hs_launch_qprep8(b.centers, b.nq, k, p.wide, b.r2, h->jtab8.as<float>() + 128, h->c16.p, d_unsafe,
-                            p.refine ? h->c8b.p : nullptr, s);
-  return hs_launch_qprep(b.centers, b.nq, k, b.r2, h->c16.p, d_unsafe, s);
+                            p.refine ? h->c8b.p : nullptr, s, b.radii);
+  return hs_launch_qprep(b.centers, b.nq, k, b.r2, h->c16.p, d_unsafe, s, b.radii);
 }
 
 // The query rows gathered into segment order (c16s)
@@ -2530,7 +2531,8 @@ static hs_status launch_filters(hs_handle* h, const BatchPlan& p, const Batch& b
   const bool side = b.n_items && b.n_slices;
   auto verify = [&](hipStream_t s) {
     return hs_launch_verify(h->tabs, h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(), h->slice_off.as<uint32_t>(),
-                            b.nql, h->tq.as<float>(), k, L, r2_hi, d_cnt, prov_cap, h->prov.as<uint2>(), n_blocks, s);
+                            b.nql, h->tq.as<float>(), k, L, r2_hi, d_cnt, prov_cap, h->prov.as<uint2>(), n_blocks, s,
+                            b.radii);
   };
   if (side) {
     HS_HIP(h, hipEventRecord(h->evx[EV_FORK], h->stream));
@@ -2603,7 +2605,7 @@ static hs_status finalize_hits(hs_handle* h, const QueryCall& c, const BatchPlan
                                h->sorted_ql.as<uint32_t>(), k, L, b.r2, c.sqrt_test ? c.R : (double)NAN, b.q_base,
                                c.self_first, d_cnt + 1, hit_cap, h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(),
                                qcnt, h->alphabet, d_qpacked, p.order_here ? h->hit_rank.as<uint32_t>() : nullptr,
-                               h->stream));
+                               h->stream, b.radii));
   if (p.order_here) {
     const size_t n1q = (size_t)b.nq + 1;
     uint32_t* const qoff = qcnt + n1q;
@@ -2735,11 +2737,11 @@ static hs_status brute_batch(hs_handle* h, const QueryCall& c, uint32_t nq, uint
     HS_HIP(h, hipEventRecord(h->ev[3], h->stream));
     if (again) HS_HIP(h, hipMemsetAsync(d_cnt + 32, 0, 64, h->stream));
     HS_HIP(h, hs_launch_bruteforce(h->packed_all.as<uint4>(), (uint32_t)h->n, h->tq.as<float>(), nq, k, r2_hi, d_cnt,
-                                   prov_cap, h->prov.as<uint2>(), nullptr, nullptr, h->n_cu * 8, h->stream));
+                                   prov_cap, h->prov.as<uint2>(), nullptr, nullptr, h->n_cu * 8, h->stream, c.radii));
     HS_HIP(h, hipEventRecord(h->ev[4], h->stream));
     HS_HIP(h, hs_launch_bf_finalize(h->codes.as<uint8_t>(), c.centers, h->coords.as<double>(), h->prov.as<uint2>(),
                                     d_cnt, prov_cap, k, c.R, q_base, d_cnt + 1, hit_cap, h->hit_key.as<uint64_t>(),
-                                    h->hit_val.as<uint64_t>(), h->stream));
+                                    h->hit_val.as<uint64_t>(), h->stream, c.radii));
     HS_HIP(h, hipEventRecord(h->ev[5], h->stream));
     HS_HIP(h, hipMemcpyAsync(h->pin_cnt, d_cnt, 96, hipMemcpyDeviceToHost, h->stream));
     return HS_OK;
@@ -2783,7 +2785,7 @@ static void learn_from_batch(hs_handle* h, const QueryCall& c, const BatchPlan& 
   const uint32_t* const cnt = h->pin_cnt;
   if (p.order_here) {
     m.order_failed = cnt[20] != 0;
-    m.order_failed_R = c.R;
+    m.order_failed_R = c.radii ? (double)NAN : c.R;
   }
   if (!p.use_i8 || !b.n_items) return;
   m.item_cap_hint = b.n_items + b.n_items / 4 + 4096;
@@ -2807,6 +2809,7 @@ static hs_status query_batch(hs_handle* h, const QueryCall& c, uint32_t nq, uint
     BatchPlan p = plan_batch(h, c, nq, allow_async, bout != nullptr);
     const uint32_t nql = nq * (uint32_t)h->p.L;
     Batch b{nq, q_base, nql, nql, c.R * c.R, c.centers, d_cand};
+    b.radii = c.radii;
     HS_HIP(h, hipMemsetAsync(h->counters.p, 0, 256, h->stream));  // incl. the join's item counter (d_cnt + 32)
     HS_HIP(h, hipEventRecord(h->ev[0], h->stream));
     HS_CHECK(prepare_queries(h, c, p, b));
@@ -2871,7 +2874,7 @@ static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_h
     }
   }
   uint64_t total = 0;
-  if (nq && h->n && !(c.brute && c.R < 0)) {
+  if (nq && h->n && !(c.brute && c.R < 0 && !c.radii)) {
     // queries per batch: bounds the workspace, which grows with nq * L (2^17 at L >= 8; with few
     // tables -- the one-table indexes of Clustering() -- larger batches, fewer fixed costs)
     uint32_t QB = std::max(1u << 17, std::min(1u << 20, (1u << 20) / h->p.L));
@@ -2902,6 +2905,7 @@ static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_h
       bc.codes = c.codes ? c.codes + q0 * h->p.k : nullptr;
       bc.pre_ints = c.pre_ints ? c.pre_ints + q0 * h->LK : nullptr;
       bc.pre_valid = c.pre_valid ? c.pre_valid + q0 * h->p.L : nullptr;
+      bc.radii = c.radii ? c.radii + q0 : nullptr;
       st = query_batch(h, bc, nqb, (uint32_t)q0, d_cand ? d_cand + q0 * h->p.L : nullptr, &nh, cap ? &bout : nullptr);
       if (st == HS_SPLIT_BATCH) {
         // more filter survivors than the 32-bit list counter holds (a radius near the typical
@@ -3032,6 +3036,11 @@ static hs_status mp_query(hs_handle* h, const QueryCall& c, uint64_t nq, uint32_
       HS_HIP(h, hs_launch_mp_repeat_f64(c.centers + q0 * d, nv, (uint32_t)d, P, h->mp_rows.as<double>(), h->stream));
       vc.centers = h->mp_rows.as<double>();
     }
+    if (c.radii) {  // probe row q P + t searches at its query's radius
+      HS_HIP(h, h->mp_radii.reserve(nv * 8));
+      HS_HIP(h, hs_launch_mp_repeat_f64(c.radii + q0, nv, 1u, P, h->mp_radii.as<double>(), h->stream));
+      vc.radii = h->mp_radii.as<double>();
+    }
     vc.pre_ints = h->mp_vints.as<int32_t>();
     vc.pre_valid = h->mp_valid.as<uint8_t>();
     HS_HIP(h, hipStreamSynchronize(h->stream));
@@ -3124,11 +3133,27 @@ hs_status hs_query_codes_dev(hs_handle* h, const uint8_t* d_qcodes, uint64_t nq,
   return run_query(h, {nullptr, d_qcodes, R}, nq, d_hit_q, d_hit_id, d_hit_table, d_hit_dist, cap, n_hits, d_cand);
 }
 
+// What a radii call's plan is decided from: the largest |radii[q]| (0 for none); false: one of them is a NaN
+static bool radii_max_host(const double* radii, uint64_t nq, double* out) {
+  double m = 0.0;
+  for (uint64_t q = 0; q < nq; ++q) {
+    if (!(radii[q] == radii[q])) return false;
+    m = std::max(m, fabs(radii[q]));
+  }
+  *out = m;
+  return true;
+}
+
+// radii != null: every query at its own radius (hs_query_radii, hs_bruteforce_radii), R unused
 static hs_status host_query(hs_handle* h, const double* centers, const uint8_t* qcodes, uint64_t nq, double R,
                             bool brute, uint32_t* hit_q, uint32_t* hit_id, uint32_t* hit_table, double* hit_dist,
-                            uint64_t cap, uint64_t* n_hits, uint64_t* cand) {
+                            uint64_t cap, uint64_t* n_hits, uint64_t* cand, const double* radii = nullptr) {
   if (!h || !n_hits) return HS_ERR_INVALID;
   if (nq && !centers && !qcodes) return HS_ERR_INVALID;
+  if (radii && !radii_max_host(radii, nq, &R)) {
+    *n_hits = 0;
+    return fail(h, HS_ERR_INVALID, "a radius is NaN");
+  }
   hs_status st = ensure_device(h);
   if (st) return st;
   // centres: 8d bytes per query over PCIe; codes: k bytes
@@ -3142,7 +3167,13 @@ static hs_status host_query(hs_handle* h, const double* centers, const uint8_t* 
   if (cand) HS_HIP(h, h->io_cand.reserve(std::max<size_t>(16, (size_t)nq * h->p.L * 8)));
   if (cbytes) HS_HIP(h, hipMemcpyAsync(h->io_centers.p, centers, cbytes, hipMemcpyHostToDevice, h->stream));
   if (kbytes) HS_HIP(h, hipMemcpyAsync(h->io_codes.p, qcodes, kbytes, hipMemcpyHostToDevice, h->stream));
-  st = run_query(h, {qcodes ? nullptr : h->io_centers.as<double>(), qcodes ? h->io_codes.as<uint8_t>() : nullptr, R, brute},
+  QueryCall call{qcodes ? nullptr : h->io_centers.as<double>(), qcodes ? h->io_codes.as<uint8_t>() : nullptr, R, brute};
+  if (radii) {
+    HS_HIP(h, h->io_radii.reserve(std::max<size_t>(16, (size_t)nq * 8)));
+    if (nq) HS_HIP(h, hipMemcpyAsync(h->io_radii.p, radii, (size_t)nq * 8, hipMemcpyHostToDevice, h->stream));
+    call.radii = h->io_radii.as<double>();
+  }
+  st = run_query(h, call,
                  nq, h->io_q.as<uint32_t>(),
                  h->io_id.as<uint32_t>(), h->io_table.as<uint32_t>(), h->io_dist.as<double>(), cap,
                  n_hits, cand ? h->io_cand.as<uint64_t>() : nullptr);
@@ -3172,6 +3203,57 @@ hs_status hs_query_codes(hs_handle* h, const uint8_t* qcodes, uint64_t nq, doubl
                          uint64_t* n_hits, uint64_t* cand) {
   if (nq && !qcodes) return HS_ERR_INVALID;
   return host_query(h, nullptr, qcodes, nq, R, false, hit_q, hit_id, hit_table, hit_dist, cap, n_hits, cand);
+}
+
+hs_status hs_query_radii(hs_handle* h, const double* centers, const uint8_t* qcodes, uint64_t nq, const double* radii,
+                         uint32_t* hit_q, uint32_t* hit_id, uint32_t* hit_table, double* hit_dist, uint64_t cap,
+                         uint64_t* n_hits, uint64_t* cand) {
+  if (!h || !n_hits) return HS_ERR_INVALID;
+  *n_hits = 0;
+  if ((centers != nullptr) == (qcodes != nullptr))
+    return fail(h, HS_ERR_INVALID, "hs_query_radii: exactly one of centers and qcodes must be given");
+  if (nq && !radii) return fail(h, HS_ERR_INVALID, "hs_query_radii: radii is null");
+  static const double none = 0.0;  // (nq = 0: the array may be null)
+  return host_query(h, centers, qcodes, nq, 0.0, false, hit_q, hit_id, hit_table, hit_dist, cap, n_hits, cand,
+                    radii ? radii : &none);
+}
+
+hs_status hs_bruteforce_radii(hs_handle* h, const double* centers, uint64_t nq, const double* radii, uint32_t* hit_q,
+                              uint32_t* hit_id, double* hit_dist, uint64_t cap, uint64_t* n_hits) {
+  if (!h || !n_hits) return HS_ERR_INVALID;
+  *n_hits = 0;
+  if (nq && (!centers || !radii)) return fail(h, HS_ERR_INVALID, "hs_bruteforce_radii: centers or radii is null");
+  static const double none = 0.0;
+  return host_query(h, centers, nullptr, nq, 0.0, true, hit_q, hit_id, nullptr, hit_dist, cap, n_hits, nullptr,
+                    radii ? radii : &none);
+}
+
+// The radii stay where they are; what the plan needs of them -- the largest |radius|, and whether one is a NaN --
+// comes from one small reduction and one read-back per call, before anything is written.
+hs_status hs_query_radii_dev(hs_handle* h, const double* d_centers, const uint8_t* d_qcodes, uint64_t nq,
+                             const double* d_radii, uint32_t* d_hit_q, uint32_t* d_hit_id, uint32_t* d_hit_table,
+                             double* d_hit_dist, uint64_t cap, uint64_t* n_hits, uint64_t* d_cand) {
+  if (!h || !n_hits) return HS_ERR_INVALID;
+  *n_hits = 0;
+  if ((d_centers != nullptr) == (d_qcodes != nullptr))
+    return fail(h, HS_ERR_INVALID, "hs_query_radii_dev: exactly one of d_centers and d_qcodes must be given");
+  if (nq && !d_radii) return fail(h, HS_ERR_INVALID, "hs_query_radii_dev: d_radii is null");
+  if (nq >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nq must be < 2^27 per call");
+  hs_status st = ensure_device(h);
+  if (st) return st;
+  unsigned long long red[2] = {0ull, 0ull};
+  HS_HIP(h, h->io_radii.reserve(16));
+  if (nq) {
+    HS_HIP(h, hipMemsetAsync(h->io_radii.p, 0, 16, h->stream));
+    HS_HIP(h, hs_launch_radii_max(d_radii, nq, h->io_radii.as<unsigned long long>(), h->stream));
+    HS_HIP(h, hipMemcpyAsync(red, h->io_radii.p, 16, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  if (red[1]) return fail(h, HS_ERR_INVALID, "a radius is NaN");
+  QueryCall call{d_centers, d_qcodes, 0.0};
+  memcpy(&call.R, &red[0], 8);
+  call.radii = nq ? d_radii : h->io_radii.as<double>();  // (nq = 0: no kernel reads the array)
+  return run_query(h, call, nq, d_hit_q, d_hit_id, d_hit_table, d_hit_dist, cap, n_hits, d_cand);
 }
 
 // The merge step of the TABLE-partitioned multi-GPU layout (include/hsearch.h): in place on n gathered tuples.

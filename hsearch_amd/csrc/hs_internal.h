@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/hsearch.h"
 
@@ -174,6 +175,26 @@ __host__ __device__ inline uint32_t hs_probe_part(uint64_t tuple_hash, bool gian
 }
 // more members than this make a bucket a giant (n = k-mers of the index)
 static inline uint32_t hs_giant_threshold(uint64_t n) { return (uint32_t)(n / 1024 > 4096 ? n / 1024 : 4096); }
+
+// ---- per-query radii (hs_query_radii) ----------------------------------------------------------------
+// The fp32 filters' bound for a squared radius r2 >= 0: the smallest float >= r2 (1 + 1e-5), then one more
+// ulp -- one-sided, the bound must never undercut.  The same value on the host (a call's one radius) and on the
+// device (a query's own radius).
+__host__ __device__ inline float hs_filter_bound(double r2) {
+  const double hi = r2 * (1.0 + 1e-5) + 1e-30;
+  float f = (float)hi;  // (round to nearest; +inf from 2^128 on)
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  if ((double)f < hi) ++u;      // f >= 0 and finite here: the next float up is the next bit pattern
+  if (u < 0x7f800000u) ++u;
+  memcpy(&f, &u, 4);
+  return f;
+}
+// The squared radius of query q: radii == null, the call's one R * R (r2); else radii[q] * radii[q], rounded
+// once like it (motif_both_points.cpp:204)
+__host__ __device__ inline double hs_r2_of(const double* radii, uint32_t q, double r2) {
+  return radii ? radii[q] * radii[q] : r2;
+}
 
 // 16-byte words per packed k-mer
 // 25 residues x 5 bits per 16-byte word
@@ -424,7 +445,8 @@ hipError_t hs_launch_qtables(const double* d_centers, uint32_t nq, int k, const 
 hipError_t hs_launch_verify(const hs_tables_dev& tabs, const uint32_t* d_qstart,
                             const uint32_t* d_qcount, const uint32_t* d_slice_off, uint32_t nql,
                             const float* d_tq, int k, int L, float r2_hi, uint32_t* d_prov_count,
-                            uint32_t prov_cap, uint2* d_prov, int n_blocks, hipStream_t s);
+                            uint32_t prov_cap, uint2* d_prov, int n_blocks, hipStream_t s,
+                            const double* d_radii = nullptr /* [nq] or null: the bound from every query's own radius */);
 // d_qcodes != null: the queries are indexed k-mers given as codes [nq][k] (self-join), d_centers unused
 hipError_t hs_launch_finalize(const hs_tables_dev& tabs, const uint8_t* d_codes,
                               const double* d_centers, const uint8_t* d_qcodes, const double* d_coords,
@@ -436,7 +458,7 @@ hipError_t hs_launch_finalize(const hs_tables_dev& tabs, const uint8_t* d_codes,
                               uint32_t* d_qcnt /* [nq] hits per query, or null */, int alphabet,
                               const uint4* d_qpacked /* the queries as packed k-mers (with d_qcodes), or null */,
                               uint32_t* d_hit_rank /* with d_qcnt: the hit's number among its query's hits */,
-                              hipStream_t s);
+                              hipStream_t s, const double* d_radii = nullptr /* [nq] or null: r2 = radii[q]^2 */);
 #ifdef __HIPCC__
 // First-seen rule (label[], motif_both_points.cpp:233): a hit's id was already reported if an EARLIER
 // table's probed bucket holds it, i.e. if its sorted position in that table falls inside the bucket's
@@ -497,12 +519,13 @@ hipError_t hs_launch_unpack_hits(const uint64_t* d_key, const uint64_t* d_val, u
 hipError_t hs_launch_bruteforce(const uint4* d_packed_all, uint32_t n, const float* d_tq,
                                 uint32_t nq, int k, float r2_hi, uint32_t* d_prov_count,
                                 uint32_t prov_cap, uint2* d_prov, const float* d_q_thr,
-                                float* d_slice_min, int n_blocks, hipStream_t s);
+                                float* d_slice_min, int n_blocks, hipStream_t s, const double* d_radii = nullptr);
 // bucket join (hs_join.hip)
 hipError_t hs_launch_jtables(const double* d_coords, int alphabet, void* d_tab16, float* d_rownorm,
                              uint32_t* d_unsafe, hipStream_t s);
+// d_radii (here and in the two int8 forms below): null, or every query's own radius [nq] in place of r2
 hipError_t hs_launch_qprep(const double* d_centers, uint32_t nq, int k, double r2, void* d_c16,
-                           uint32_t* d_unsafe, hipStream_t s);
+                           uint32_t* d_unsafe, hipStream_t s, const double* d_radii = nullptr);
 // items[j] for joined segments (>= min_q probing queries and >= min_m members), 0 otherwise, and
 // nslices[ql] = 0 for the probes of joined segments; stats[0] += MFMA pairs issued, [1] += real pairs
 hipError_t hs_launch_seg_route(const uint64_t* d_seg_key, const uint32_t* d_seg_cnt,
@@ -562,10 +585,10 @@ hipError_t hs_launch_jtables8(const double* d_coords, int alphabet, void* d_tab8
 hipError_t hs_launch_qprep8_codes(const uint8_t* d_qcodes, uint32_t nq, int k, int wide, double r2,
                                   const double* d_coords, const void* d_tab8, const void* d_tabR,
                                   const void* d_tabW, const float* d_scale, void* d_c8, void* d_c8b,
-                                  hipStream_t s);
+                                  hipStream_t s, const double* d_radii = nullptr);
 hipError_t hs_launch_qprep8(const double* d_centers, uint32_t nq, int k, int wide, double r2,
                             const float* d_scale, void* d_c8, uint32_t* d_unsafe, void* d_c8b,
-                            hipStream_t s);
+                            hipStream_t s, const double* d_radii = nullptr);
 // survivors of the 4-column bound -> those that also pass the 8-column bound (compacted, direct form)
 hipError_t hs_launch_refine8(const hs_tables_dev& tabs, const uint2* d_prov, const uint32_t* d_prov_count,
                              uint32_t prov_cap, const uint32_t* d_sorted_ql, const void* d_c8,
@@ -610,6 +633,10 @@ hipError_t hs_launch_bf_finalize(const uint8_t* d_codes, const double* d_centers
                                  const double* d_coords, const uint2* d_prov,
                                  const uint32_t* d_prov_count, uint32_t prov_cap, int k, double R,
                                  uint32_t q_base, uint32_t* d_hit_count, uint32_t hit_cap,
-                                 uint64_t* d_hit_key, uint64_t* d_hit_val, hipStream_t s);
+                                 uint64_t* d_hit_key, uint64_t* d_hit_val, hipStream_t s,
+                                 const double* d_radii = nullptr /* [nq] or null: R = radii[q] */);
+// per-query radii of a call (hs_query_radii_dev): d_out[0] = the bits of max |radii[q]| as a double (0 for n = 0),
+// d_out[1] = 1 if one of them is a NaN; d_out zeroed by the caller
+hipError_t hs_launch_radii_max(const double* d_radii, uint64_t n, unsigned long long* d_out, hipStream_t s);
 
 #endif

@@ -52,10 +52,12 @@ __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 // wavefront per query.  unsafe |= 1 when fp16 cannot carry the query (the caller then uses the
 // streaming kernel for the batch).
 __global__ __launch_bounds__(256) void hs_qprep_kernel(const double* __restrict__ centers, uint32_t nq,
-                                                       int k, double r2, _Float16* __restrict__ c16,
-                                                       uint32_t* __restrict__ unsafe) {
+                                                       int k, double r2_call, _Float16* __restrict__ c16,
+                                                       uint32_t* __restrict__ unsafe,
+                                                       const double* __restrict__ radii) {
   const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (q >= nq) return;
+  const double r2 = hs_r2_of(radii, q, r2_call);
   const int lane = lane_id();
   const double* c = centers + (uint64_t)q * 8 * k;
   _Float16* out = c16 + (uint64_t)q * JK;
@@ -650,9 +652,9 @@ hipError_t hs_launch_jtables(const double* d_coords, int alphabet, void* d_tab16
 }
 
 hipError_t hs_launch_qprep(const double* d_centers, uint32_t nq, int k, double r2, void* d_c16,
-                           uint32_t* d_unsafe, hipStream_t s) {
+                           uint32_t* d_unsafe, hipStream_t s, const double* d_radii) {
   if (!nq) return hipSuccess;
-  hs_qprep_kernel<<<blocks_for(nq, 4), 256, 0, s>>>(d_centers, nq, k, r2, (_Float16*)d_c16, d_unsafe);
+  hs_qprep_kernel<<<blocks_for(nq, 4), 256, 0, s>>>(d_centers, nq, k, r2, (_Float16*)d_c16, d_unsafe, d_radii);
   return hipGetLastError();
 }
 

@@ -207,12 +207,14 @@ __global__ void hs_jtables8_kernel(const double* __restrict__ coords, int alphab
 // byte ROW - 29; the last 28 bytes: (-127 x11, -1), 0, 0, then the 14 digits of -gamma.
 template <bool WIDE>
 __global__ __launch_bounds__(256) void hs_qprep8_kernel(const double* __restrict__ centers, uint32_t nq,
-                                                        int k, double r2, const float* __restrict__ scale,
+                                                        int k, double r2_call, const float* __restrict__ scale,
                                                         int8_t* __restrict__ c8,
                                                         uint32_t* __restrict__ unsafe,
-                                                        int8_t* __restrict__ c8b) {
+                                                        int8_t* __restrict__ c8b,
+                                                        const double* __restrict__ radii) {
   const uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (q >= nq) return;
+  const double r2 = hs_r2_of(radii, q, r2_call);  // the radius enters gamma and the refinement's slot, nothing else
   const int lane = lane_id();
   const int ROW = 32 * ks_of(k, WIDE), TAIL = ROW - 28;
   // WIDE: one row, all 8 columns on one scale, byte 8 pos + j
@@ -305,13 +307,14 @@ __global__ __launch_bounds__(256) void hs_qprep8_kernel(const double* __restrict
 // doubles.  One thread per query.
 template <bool WIDE>
 __global__ __launch_bounds__(256) void hs_qprep8_codes_kernel(const uint8_t* __restrict__ qcodes, uint32_t nq,
-                                                              int k, double r2,
+                                                              int k, double r2_call,
                                                               const double* __restrict__ coords,
                                                               const uint4* __restrict__ tab8,
                                                               const uint4* __restrict__ tabR,
                                                               const uint4* __restrict__ tabW,
                                                               const float* __restrict__ scale,
-                                                              int8_t* __restrict__ c8, int8_t* __restrict__ c8b) {
+                                                              int8_t* __restrict__ c8, int8_t* __restrict__ c8b,
+                                                              const double* __restrict__ radii) {
   __shared__ uint32_t sA[32], sB[32], sL1[32];
   __shared__ double sNA[32], sNB[32];
   if (threadIdx.x < 32) {
@@ -331,6 +334,7 @@ __global__ __launch_bounds__(256) void hs_qprep8_codes_kernel(const uint8_t* __r
   __syncthreads();
   const uint32_t q = blockIdx.x * 256 + threadIdx.x;
   if (q >= nq) return;
+  const double r2 = hs_r2_of(radii, q, r2_call);
   const int ROW = 32 * ks_of(k, WIDE), TAIL = ROW - 28;
   const uint8_t* code = qcodes + (uint64_t)q * k;
   uint32_t* outA = reinterpret_cast<uint32_t*>(c8 + (uint64_t)q * ROW);
@@ -2156,30 +2160,30 @@ hipError_t hs_launch_jtables8(const double* d_coords, int alphabet, void* d_tab8
 
 hipError_t hs_launch_qprep8(const double* d_centers, uint32_t nq, int k, int wide, double r2,
                             const float* d_scale, void* d_c8, uint32_t* d_unsafe, void* d_c8b,
-                            hipStream_t s) {
+                            hipStream_t s, const double* d_radii) {
   if (!nq) return hipSuccess;
   if (wide)
     hs_qprep8_kernel<true><<<blocks_for(nq, 4), 256, 0, s>>>(d_centers, nq, k, r2, d_scale, (int8_t*)d_c8,
-                                                             d_unsafe, nullptr);
+                                                             d_unsafe, nullptr, d_radii);
   else
     hs_qprep8_kernel<false><<<blocks_for(nq, 4), 256, 0, s>>>(d_centers, nq, k, r2, d_scale, (int8_t*)d_c8,
-                                                              d_unsafe, (int8_t*)d_c8b);
+                                                              d_unsafe, (int8_t*)d_c8b, d_radii);
   return hipGetLastError();
 }
 
 hipError_t hs_launch_qprep8_codes(const uint8_t* d_qcodes, uint32_t nq, int k, int wide, double r2,
                                   const double* d_coords, const void* d_tab8, const void* d_tabR,
                                   const void* d_tabW, const float* d_scale, void* d_c8, void* d_c8b,
-                                  hipStream_t s) {
+                                  hipStream_t s, const double* d_radii) {
   if (!nq) return hipSuccess;
   if (wide)
     hs_qprep8_codes_kernel<true><<<blocks_for(nq), 256, 0, s>>>(d_qcodes, nq, k, r2, d_coords, (const uint4*)d_tab8,
                                                                 (const uint4*)d_tabR, (const uint4*)d_tabW,
-                                                                d_scale, (int8_t*)d_c8, nullptr);
+                                                                d_scale, (int8_t*)d_c8, nullptr, d_radii);
   else
     hs_qprep8_codes_kernel<false><<<blocks_for(nq), 256, 0, s>>>(d_qcodes, nq, k, r2, d_coords, (const uint4*)d_tab8,
                                                                  (const uint4*)d_tabR, (const uint4*)d_tabW,
-                                                                 d_scale, (int8_t*)d_c8, (int8_t*)d_c8b);
+                                                                 d_scale, (int8_t*)d_c8, (int8_t*)d_c8b, d_radii);
   return hipGetLastError();
 }
 

@@ -650,7 +650,7 @@ __global__ __launch_bounds__(256) void hs_qtables_kernel(const double* __restric
 // grid-stride from the scanned slice counts.  The query's distance table lives in 25*PW VGPRs
 // spread across lanes (lane aa holds T[pos][aa]); a candidate's squared distance is 25*PW
 // ds_bpermute lookups + adds on one coalesced 16-byte load per lane.  Survivors of the fp32 filter
-// (d2 <= R^2 (1 + 1e-5)) are compacted with a wave ballot; hs_finalize_kernel decides them exactly.
+// (d2 <= R^2 (1 + 1e-5), R the call's or the query's own) are compacted with a wave ballot; hs_finalize_kernel decides them exactly.
 template <int PW, bool BRUTE>
 __global__ __launch_bounds__(256) void hs_verify_kernel(hs_tables_dev tabs,
                                                         const uint4* __restrict__ brute_packed,
@@ -663,7 +663,8 @@ __global__ __launch_bounds__(256) void hs_verify_kernel(hs_tables_dev tabs,
                                                         uint32_t* __restrict__ prov_count,
                                                         uint32_t prov_cap, uint2* __restrict__ prov,
                                                         const float* __restrict__ q_thr,
-                                                        float* __restrict__ slice_min) {
+                                                        float* __restrict__ slice_min,
+                                                        const double* __restrict__ radii) {
   const int lane = lane_id();
   const uint32_t waves_per_block = blockDim.x / WAVE;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * waves_per_block + (threadIdx.x >> 6));
@@ -698,7 +699,8 @@ __global__ __launch_bounds__(256) void hs_verify_kernel(hs_tables_dev tabs,
     for (int p = 0; p < 25 * PW; ++p) T[p] = p < k ? trow[p * HS_TROW] : 0.f;
     const uint32_t iters = (cnt + WAVE - 1) / WAVE;
     // brute-force top-k support: per-query thresholds, or a pure min pass over the slice
-    const float thr = (BRUTE && q_thr) ? q_thr[q] : r2_hi;
+    // (radii: every query's own radius, hs_query_radii -- the same one-sided bound from radii[q]^2)
+    const float thr = (BRUTE && q_thr) ? q_thr[q] : radii ? hs_filter_bound(hs_r2_of(radii, q, 0.0)) : r2_hi;
     float run_min = INFINITY;
     for (uint32_t it = 0; it < iters; ++it) {
       const uint32_t i = it * WAVE + lane;
@@ -860,7 +862,8 @@ __global__ __launch_bounds__(256) void hs_finalize_kernel(hs_tables_dev tabs,
                                                           uint64_t* __restrict__ hit_key,
                                                           uint64_t* __restrict__ hit_val,
                                                           uint32_t* __restrict__ qcnt,
-                                                          uint32_t* __restrict__ hit_rank) {
+                                                          uint32_t* __restrict__ hit_rank,
+                                                          const double* __restrict__ radii) {
   // One wave = 64 survivors, one per lane.  The exact d2 is a serial fp64 chain per survivor, but
   // its inputs -- 8k doubles of the query's centre row -- are fetched by the WAVE: per position,
   // the 64 rows' 64-byte pieces go through LDS (4 lanes x 16 B per row: every byte fetched is
@@ -1016,8 +1019,9 @@ __global__ __launch_bounds__(256) void hs_finalize_kernel(hs_tables_dev tabs,
 #undef HS_FIN_LOAD
     }
     // Search(): d2 <= R*R (motif_both_points.cpp:239); Clustering(): sqrt(d2) <= R
-    // (hclust2.cpp:64-71,119-120), selected by a non-NaN r_sqrt.
-    bool hit = live && ((r_sqrt == r_sqrt) ? (__dsqrt_rn(d2) <= r_sqrt) : (d2 <= r2));
+    // (hclust2.cpp:64-71,119-120), selected by a non-NaN r_sqrt.  radii != null (hs_query_radii): the first
+    // form with the query's own radii[q] * radii[q] (dead lanes read query 0's).
+    bool hit = live && ((r_sqrt == r_sqrt) ? (__dsqrt_rn(d2) <= r_sqrt) : (d2 <= hs_r2_of(radii, q, r2)));
     // the self-join drops a k-mer's pair with itself (Clustering() never compares a k-mer with
     // itself: its id is not in `centers` yet when it is visited, hclust2.cpp:116-131); an equal
     // k-mer under another id stays
@@ -1080,7 +1084,8 @@ __global__ __launch_bounds__(64 * HS_FINC_WAVES) void hs_finalize_codes_kernel(h
                                                                 uint64_t* __restrict__ hit_key,
                                                                 uint64_t* __restrict__ hit_val,
                                                                 uint32_t* __restrict__ qcnt,
-                                                                uint32_t* __restrict__ hit_rank) {
+                                                                uint32_t* __restrict__ hit_rank,
+                                                                const double* __restrict__ radii) {
   // [alphabet][alphabet] rows of 8 doubles at a stride of 10: with 64-byte rows the 16 lanes of one pass of a
   // 16-byte read meet in 4 bank groups (4-way conflicts on average), with 80-byte rows in 16
   extern __shared__ __attribute__((aligned(16))) double s_sq[];
@@ -1169,7 +1174,7 @@ __global__ __launch_bounds__(64 * HS_FINC_WAVES) void hs_finalize_codes_kernel(h
         }
       }
     }
-    bool hit = live && ((r_sqrt == r_sqrt) ? (__dsqrt_rn(d2) <= r_sqrt) : (d2 <= r2));
+    bool hit = live && ((r_sqrt == r_sqrt) ? (__dsqrt_rn(d2) <= r_sqrt) : (d2 <= hs_r2_of(radii, q, r2)));
     if (self_first != HS_NO_SELF && self_first + q_base + q == id) hit = false;
     if (__ballot(hit && l > 0)) hit = hit && !seen_in_earlier_table(tabs, qstart, qcount, q, l, L, id, hit);
     const unsigned long long hm = __ballot(hit);
@@ -1380,13 +1385,14 @@ __global__ __launch_bounds__(256) void hs_bf_finalize_kernel(const uint8_t* __re
                                                              uint32_t* __restrict__ hit_count,
                                                              uint32_t hit_cap,
                                                              uint64_t* __restrict__ hit_key,
-                                                             uint64_t* __restrict__ hit_val) {
+                                                             uint64_t* __restrict__ hit_val,
+                                                             const double* __restrict__ radii) {
   const uint32_t n = min(*prov_count, prov_cap);
   for (uint32_t e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) {
     const uint32_t q = prov[e].x, id = prov[e].y;
     const double d2 = exact_dist2(codes + (uint64_t)id * k, centers + (uint64_t)q * 8 * k, coords, k);
     const double dis = __dsqrt_rn(d2);
-    if (!(dis > R)) {
+    if (!(dis > (radii ? radii[q] : R))) {
       const uint32_t idx = atomicAdd(hit_count, 1u);
       if (idx < hit_cap) {
         hit_key[idx] = ((uint64_t)(q_base + q) << 37) | id;
@@ -1974,13 +1980,14 @@ hipError_t hs_launch_qtables(const double* d_centers, uint32_t nq, int k, const 
 hipError_t hs_launch_verify(const hs_tables_dev& tabs, const uint32_t* d_qstart,
                             const uint32_t* d_qcount, const uint32_t* d_slice_off, uint32_t nql,
                             const float* d_tq, int k, int L, float r2_hi, uint32_t* d_prov_count,
-                            uint32_t prov_cap, uint2* d_prov, int n_blocks, hipStream_t s) {
+                            uint32_t prov_cap, uint2* d_prov, int n_blocks, hipStream_t s,
+                            const double* d_radii) {
   if (!nql) return hipSuccess;
   const int PW = hs_packed_words(k);
 #define HS_VERIFY(P)                                                                              \
   hs_verify_kernel<P, false><<<n_blocks, 256, 0, s>>>(tabs, nullptr, 0u, d_qstart, d_qcount,      \
                                                       d_slice_off, nql, d_tq, k, L, r2_hi,         \
-                                                      d_prov_count, prov_cap, d_prov, nullptr, nullptr)
+                                                      d_prov_count, prov_cap, d_prov, nullptr, nullptr, d_radii)
   if (PW == 1) HS_VERIFY(1);
   else if (PW == 2) HS_VERIFY(2);
   else if (PW == 3) HS_VERIFY(3);
@@ -1992,14 +1999,14 @@ hipError_t hs_launch_verify(const hs_tables_dev& tabs, const uint32_t* d_qstart,
 hipError_t hs_launch_bruteforce(const uint4* d_packed_all, uint32_t n, const float* d_tq,
                                 uint32_t nq, int k, float r2_hi, uint32_t* d_prov_count,
                                 uint32_t prov_cap, uint2* d_prov, const float* d_q_thr,
-                                float* d_slice_min, int n_blocks, hipStream_t s) {
+                                float* d_slice_min, int n_blocks, hipStream_t s, const double* d_radii) {
   if (!nq || !n) return hipSuccess;
   const int PW = hs_packed_words(k);
   hs_tables_dev none = {};
 #define HS_BRUTE(P)                                                                               \
   hs_verify_kernel<P, true><<<n_blocks, 256, 0, s>>>(none, d_packed_all, n, nullptr, nullptr,      \
                                                      nullptr, nq, d_tq, k, 1, r2_hi, d_prov_count, \
-                                                     prov_cap, d_prov, d_q_thr, d_slice_min)
+                                                     prov_cap, d_prov, d_q_thr, d_slice_min, d_radii)
   if (PW == 1) HS_BRUTE(1);
   else if (PW == 2) HS_BRUTE(2);
   else if (PW == 3) HS_BRUTE(3);
@@ -2015,7 +2022,8 @@ hipError_t hs_launch_finalize(const hs_tables_dev& tabs, const uint8_t* d_codes,
                               const uint32_t* d_sorted_ql, int k, int L, double r2, double r_sqrt,
                               uint32_t q_base, uint32_t self_first, uint32_t* d_hit_count,
                               uint32_t hit_cap, uint64_t* d_hit_key, uint64_t* d_hit_val, uint32_t* d_qcnt,
-                              int alphabet, const uint4* d_qpacked, uint32_t* d_hit_rank, hipStream_t s) {
+                              int alphabet, const uint4* d_qpacked, uint32_t* d_hit_rank, hipStream_t s,
+                              const double* d_radii) {
   if (d_qpacked && alphabet <= HS_FIN_TABLE_ALPHABET) {  // the queries are k-mers: terms from a table
     static bool lds_granted = false;  // (static + dynamic LDS above 64 KB: ask once per process)
     if (!lds_granted) {
@@ -2027,17 +2035,17 @@ hipError_t hs_launch_finalize(const hs_tables_dev& tabs, const uint8_t* d_codes,
     }
     hs_finalize_codes_kernel<<<512, 64 * HS_FINC_WAVES, (size_t)alphabet * alphabet * 80, s>>>(
         tabs, d_qpacked, d_coords, alphabet, d_qstart, d_qcount, d_prov, d_prov_count, prov_cap, d_sorted_ql, k, L, r2,
-        r_sqrt, q_base, self_first, d_hit_count, hit_cap, d_hit_key, d_hit_val, d_qcnt, d_hit_rank);
+        r_sqrt, q_base, self_first, d_hit_count, hit_cap, d_hit_key, d_hit_val, d_qcnt, d_hit_rank, d_radii);
   } else if (d_qcodes)  // ... with a large alphabet: centre rows from the coordinate table
     hs_finalize_kernel<true><<<1024, 256, 0, s>>>(tabs, d_codes, nullptr, d_qcodes, d_coords, d_qstart, d_qcount,
                                                   d_prov, d_prov_count, prov_cap, d_sorted_ql, k, L, r2,
                                                   r_sqrt, q_base, self_first, d_hit_count, hit_cap,
-                                                  d_hit_key, d_hit_val, d_qcnt, d_hit_rank);
+                                                  d_hit_key, d_hit_val, d_qcnt, d_hit_rank, d_radii);
   else
     hs_finalize_kernel<false><<<1024, 256, 0, s>>>(tabs, d_codes, d_centers, nullptr, d_coords, d_qstart,
                                                    d_qcount, d_prov, d_prov_count, prov_cap, d_sorted_ql, k, L,
                                                    r2, r_sqrt, q_base, self_first, d_hit_count, hit_cap,
-                                                   d_hit_key, d_hit_val, d_qcnt, d_hit_rank);
+                                                   d_hit_key, d_hit_val, d_qcnt, d_hit_rank, d_radii);
   return hipGetLastError();
 }
 hipError_t hs_launch_hit_order(const uint64_t* d_key, const uint64_t* d_val, const uint32_t* d_hit_count,
@@ -2238,10 +2246,37 @@ hipError_t hs_launch_bf_finalize(const uint8_t* d_codes, const double* d_centers
                                  const double* d_coords, const uint2* d_prov,
                                  const uint32_t* d_prov_count, uint32_t prov_cap, int k, double R,
                                  uint32_t q_base, uint32_t* d_hit_count, uint32_t hit_cap,
-                                 uint64_t* d_hit_key, uint64_t* d_hit_val, hipStream_t s) {
+                                 uint64_t* d_hit_key, uint64_t* d_hit_val, hipStream_t s,
+                                 const double* d_radii) {
   hs_bf_finalize_kernel<<<1024, 256, 0, s>>>(d_codes, d_centers, d_coords, d_prov, d_prov_count,
                                              prov_cap, k, R, q_base, d_hit_count, hit_cap, d_hit_key,
-                                             d_hit_val);
+                                             d_hit_val, d_radii);
+  return hipGetLastError();
+}
+
+// The largest |radius| of a radii call and whether one is a NaN, without bringing the array to the host:
+// non-negative doubles order like their bit patterns, so the maximum is one 64-bit atomicMax per wave.
+__global__ __launch_bounds__(256) void hs_radii_max_kernel(const double* __restrict__ radii, uint64_t n,
+                                                           unsigned long long* __restrict__ out) {
+  double m = 0.0;
+  bool nan = false;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+    const double r = radii[i];
+    nan = nan || !(r == r);
+    if (r == r) m = fmax(m, fabs(r));
+  }
+  for (int off = 32; off; off >>= 1) m = fmax(m, __shfl_xor(m, off));
+  const bool any_nan = __ballot(nan) != 0;
+  if (lane_id() == 0) {
+    atomicMax(out, (unsigned long long)__double_as_longlong(m));
+    if (any_nan) atomicOr(out + 1, 1ull);
+  }
+}
+
+hipError_t hs_launch_radii_max(const double* d_radii, uint64_t n, unsigned long long* d_out, hipStream_t s) {
+  if (!n) return hipSuccess;
+  const unsigned blocks = (unsigned)std::min<uint64_t>(blocks_for(n), 1024u);
+  hs_radii_max_kernel<<<blocks, 256, 0, s>>>(d_radii, n, d_out);
   return hipGetLastError();
 }
 

@@ -8,7 +8,10 @@
 // <dir>/<o>ramdom_protein_centers_0.txt (the centre x database distances on the GPU).  Additions:
 // -format points writes the centroids as a points file <o>hclust.format.txt instead
 // (cluster2datapoint, :110-136 -- the `-c` input of motif_both_points; no database needed, no GPU
-// work), -m <min family size> [50], -D <dir> [./pro2centerdis], -G <GPU ordinal>.
+// work) and beside it <o>hclust.radii.txt, per family the radius that makes every member a hit of its
+// own centroid (the `--radii` input of motif_both_points; -q <quantile in (0,1]> takes that quantile of
+// the members' distances instead of the largest), -m <min family size> [50], -D <dir> [./pro2centerdis],
+// -G <GPU ordinal>.
 #include <iostream>
 #include <string>
 #include <vector>
@@ -24,6 +27,7 @@ int main(int argc, const char* argv[]) {
       {"output", 'o', "output file name", true},
       {"format", 'f', "distances (default) | points", false},
       {"minsize", 'm', "smallest family kept [50]", false},
+      {"quantile", 'q', "-format points: the radii file covers this share of a family's members, (0,1] [1]", false},
       {"dir", 'D', "directory of the distance files [./pro2centerdis]", false},
       {"device", 'G', "GPU ordinal [0]", false},
   };
@@ -52,6 +56,16 @@ int main(int argc, const char* argv[]) {
     if (format == "points") {
       if (!hsearch::Cluster2DataPoint(families, centers, val["output"])) {
         fprintf(stderr, "cannot write %shclust.format.txt\n", val["output"].c_str());
+        return EXIT_FAILURE;
+      }
+      double quantile = 1.0;
+      if (val.count("quantile")) {
+        char* end = nullptr;
+        quantile = strtod(val["quantile"].c_str(), &end);
+        if (end == val["quantile"].c_str() || *end != '\0') quantile = -1.0;
+      }
+      if (!hsearch::FamilyRadii(families, len, val["output"], quantile, &err)) {
+        fprintf(stderr, "ERROR: %s\n", err.c_str());
         return EXIT_FAILURE;
       }
       return EXIT_SUCCESS;

@@ -163,10 +163,14 @@ int RunSearch(hs_params prm, const Planes& planes, const double* coords,
               const std::function<hs_status(hs_handle*, uint32_t rank)>& build, const double* flat,
               const uint8_t* qcodes, uint64_t nq, double R, const std::vector<int>& devices, bool sharded,
               SearchHits* out, std::string* err, std::vector<uint64_t>* table_sizes,
-              const uint8_t* db_sample = nullptr, uint64_t n_db_sample = 0) {
+              const uint8_t* db_sample = nullptr, uint64_t n_db_sample = 0, const double* radii = nullptr) {
   const uint32_t world = (uint32_t)devices.size();
   if (!world) {
     if (err) *err = "no device given";
+    return HS_ERR_INVALID;
+  }
+  if (radii && sharded) {  // (hs_comm_query* take one radius)
+    if (err) *err = "per-centre radii are not supported together with the multi-GPU exchange";
     return HS_ERR_INVALID;
   }
   // table partition: rank r holds the tables tabs[r] (global numbers, ascending) of ALL k-mers
@@ -237,6 +241,10 @@ int RunSearch(hs_params prm, const Planes& planes, const double* coords,
       out->id.resize(cap);
       out->table.resize(cap);
       out->dist.resize(cap);
+      if (radii)  // every centre at its own radius
+        st = hs_query_radii(h, qcodes ? nullptr : flat, qcodes, nq, radii, out->q.data(), out->id.data(),
+                            out->table.data(), out->dist.data(), cap, &out->n, nullptr);
+      else
       st = qcodes ? hs_query_codes(h, qcodes, nq, R, out->q.data(), out->id.data(), out->table.data(),
                                    out->dist.data(), cap, &out->n, nullptr)
                   : hs_query(h, flat, nq, R, out->q.data(), out->id.data(), out->table.data(), out->dist.data(),
@@ -332,6 +340,13 @@ int RunSearch(hs_params prm, const Planes& planes, const double* coords,
   return HS_OK;
 }
 
+// radii (optional argument of the Search functions): one per centre
+bool RadiiMatch(const std::vector<double>* radii, size_t n_centers, std::string* err) {
+  if (!radii || radii->size() == n_centers) return true;
+  if (err) *err = "radii: one radius per centre is needed";
+  return false;
+}
+
 bool FlattenCenters(const std::vector<Point>& centers, uint32_t dim, std::vector<double>* flat, std::string* err) {
   flat->resize((size_t)centers.size() * dim);
   for (size_t i = 0; i < centers.size(); ++i) {
@@ -353,9 +368,9 @@ int Search(const std::vector<Point>& kmers, const std::vector<Point>& centers,
            const std::vector<std::string>& kmer_names, const std::vector<std::string>& center_names,
            const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
            const double& hash_R, const std::string& output_file, const Planes& planes, int device,
-           std::string* err, std::vector<uint64_t>* table_sizes, uint32_t probes) {
+           std::string* err, std::vector<uint64_t>* table_sizes, uint32_t probes, const std::vector<double>* radii) {
   return SearchSharded(kmers, centers, kmer_names, center_names, hash_K, hash_L, hash_W, hash_R, output_file,
-                       planes, std::vector<int>(1, device), false, err, table_sizes, probes);
+                       planes, std::vector<int>(1, device), false, err, table_sizes, probes, radii);
 }
 
 int SearchSharded(const std::vector<Point>& kmers, const std::vector<Point>& centers,
@@ -363,7 +378,8 @@ int SearchSharded(const std::vector<Point>& kmers, const std::vector<Point>& cen
                   const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
                   const double& hash_R, const std::string& output_file, const Planes& planes,
                   const std::vector<int>& devices, bool use_comm, std::string* err,
-                  std::vector<uint64_t>* table_sizes, uint32_t probes) {
+                  std::vector<uint64_t>* table_sizes, uint32_t probes, const std::vector<double>* radii) {
+  if (!RadiiMatch(radii, centers.size(), err)) return HS_ERR_INVALID;
   struct ProbesScope {
     explicit ProbesScope(uint32_t t) { g_probes = t; }
     ~ProbesScope() { g_probes = 0; }
@@ -389,7 +405,8 @@ int SearchSharded(const std::vector<Point>& kmers, const std::vector<Point>& cen
   const int st = RunSearch(prm, planes, table.data(),
                            [&](hs_handle* h, uint32_t) { return hs_index_build(h, codes.data(), kmers.size()); },
                            flat.data(), nullptr, centers.size(), hash_R, devices, use_comm || devices.size() > 1,
-                           &hits, err, table_sizes, codes.data(), std::min<uint64_t>(kmers.size(), 32768));
+                           &hits, err, table_sizes, codes.data(), std::min<uint64_t>(kmers.size(), 32768),
+                           radii ? radii->data() : nullptr);
   if (st != HS_OK) return st;
   std::ofstream fout(output_file.c_str());
   for (uint64_t i = 0; i < hits.n; ++i)  // :240-241
@@ -431,10 +448,11 @@ int SearchProteins(const ProteinDB& db, uint32_t kmer_length, const std::vector<
                    const std::vector<std::string>& center_names, const uint32_t& hash_K,
                    const uint32_t& hash_L, const double& hash_W, const double& hash_R,
                    const std::string& output_file, const Planes& planes, int device, std::string* err,
-                   std::vector<uint64_t>* table_sizes, uint64_t* n_windows, bool best_per_position) {
+                   std::vector<uint64_t>* table_sizes, uint64_t* n_windows, bool best_per_position,
+                   const std::vector<double>* radii) {
   return SearchProteinsSharded(db, kmer_length, centers, center_names, hash_K, hash_L, hash_W, hash_R,
                                output_file, planes, std::vector<int>(1, device), false, err, table_sizes,
-                               n_windows, best_per_position);
+                               n_windows, best_per_position, nullptr, radii);
 }
 
 int SearchProteinsSharded(const ProteinDB& db, uint32_t kmer_length, const std::vector<Point>& centers,
@@ -443,8 +461,9 @@ int SearchProteinsSharded(const ProteinDB& db, uint32_t kmer_length, const std::
                           const std::string& output_file, const Planes& planes,
                           const std::vector<int>& devices, bool use_comm, std::string* err,
                           std::vector<uint64_t>* table_sizes, uint64_t* n_windows, bool best_per_position,
-                          const std::vector<uint8_t>* center_codes) {
+                          const std::vector<uint8_t>* center_codes, const std::vector<double>* radii) {
   const uint32_t dim = 8 * kmer_length;
+  if (!RadiiMatch(radii, centers.size(), err)) return HS_ERR_INVALID;
   if (center_codes && center_codes->size() != centers.size() * (size_t)kmer_length) {
     if (err) *err = "centre codes do not match the centres";
     return HS_ERR_INVALID;
@@ -494,7 +513,7 @@ int SearchProteinsSharded(const ProteinDB& db, uint32_t kmer_length, const std::
         return bst;
       },
       flat.data(), center_codes ? center_codes->data() : nullptr, centers.size(), hash_R, devices,
-      use_comm || devices.size() > 1, &hits, err, table_sizes);
+      use_comm || devices.size() > 1, &hits, err, table_sizes, nullptr, 0, radii ? radii->data() : nullptr);
   if (rst != HS_OK) return rst;
   if (n_windows) *n_windows = n_win;
   const uint64_t n_hits = hits.n;
@@ -908,8 +927,10 @@ struct ScanEngine {
     return st;
   }
   // all (centre, point) pairs of centres [c0, c0 + nc) with !(dist > R), centre-major
+  // radii != null: centre c0 + i at radii[i] instead of R
   int Scan(const std::vector<Point>& centers, size_t c0, size_t nc, double R, std::vector<uint32_t>* hq,
-           std::vector<uint32_t>* hid, std::vector<double>* hd, uint64_t* n_hits, std::string* err) {
+           std::vector<uint32_t>* hid, std::vector<double>* hd, uint64_t* n_hits, std::string* err,
+           const double* radii = nullptr) {
     std::vector<double> flat(nc * dim);
     for (size_t i = 0; i < nc; ++i) {
       if (centers[c0 + i].data.size() != dim) {
@@ -923,7 +944,9 @@ struct ScanEngine {
       hq->resize(cap);
       hid->resize(cap);
       hd->resize(cap);
-      const hs_status st = hs_bruteforce(h, flat.data(), nc, R, hq->data(), hid->data(), hd->data(), cap, n_hits);
+      const hs_status st =
+          radii ? hs_bruteforce_radii(h, flat.data(), nc, radii, hq->data(), hid->data(), hd->data(), cap, n_hits)
+                : hs_bruteforce(h, flat.data(), nc, R, hq->data(), hid->data(), hd->data(), cap, n_hits);
       if (st == HS_ERR_CAPACITY) {
         cap = *n_hits;
         continue;
@@ -940,7 +963,8 @@ int SearchBruteForce(const std::vector<Point>& kmers, const std::vector<Point>& 
                      const std::vector<std::string>& kmer_names,
                      const std::vector<std::string>& center_names, const double& hash_R,
                      const std::string& output_file, int device, std::string* err,
-                     bool write_not_less_than) {
+                     bool write_not_less_than, const std::vector<double>* radii) {
+  if (!RadiiMatch(radii, centers.size(), err)) return HS_ERR_INVALID;
   if (kmers.empty() || kmers[0].data.empty() || kmers[0].data.size() % 8 != 0) {
     if (err) *err = "no database points (or dimension not a multiple of 8)";
     return HS_ERR_INVALID;
@@ -963,10 +987,13 @@ int SearchBruteForce(const std::vector<Point>& kmers, const std::vector<Point>& 
   for (size_t c0 = 0; c0 < centers.size(); c0 += block) {
     const size_t nc = std::min(block, centers.size() - c0);
     uint64_t n_hits = 0;
-    st = eng.Scan(centers, c0, nc, R, &hq, &hid, &hd, &n_hits, err);
+    // (with the second file every pair comes back whatever the radii, and is split here)
+    st = eng.Scan(centers, c0, nc, R, &hq, &hid, &hd, &n_hits, err,
+                  radii && !write_not_less_than ? radii->data() + c0 : nullptr);
     if (st != HS_OK) return st;
     for (uint64_t i = 0; i < n_hits; ++i) {
-      std::ofstream& f = (write_not_less_than && hd[i] > hash_R) ? fnot : fout;
+      const double r_i = radii ? (*radii)[c0 + hq[i]] : hash_R;
+      std::ofstream& f = (write_not_less_than && hd[i] > r_i) ? fnot : fout;
       f << center_names[c0 + hq[i]] << " " << kmer_names[hid[i]] << " " << hd[i] << std::endl;
     }
   }
@@ -1094,6 +1121,114 @@ bool Cluster2DataPoint(const std::vector<MotifFamily>& families, const std::vect
     for (size_t q = 1; q < centers[p].data.size(); ++q) fout << " " << centers[p].data[q];
     fout << std::endl;
   }
+  return true;
+}
+
+double RadiusCovering(double d2) {
+  double r = sqrt(d2);
+  if (r * r < d2) r = nextafter(r, std::numeric_limits<double>::infinity());
+  return r;
+}
+
+bool FamilyRadii(const std::vector<MotifFamily>& families, uint32_t kmer_length, const std::string& output_file,
+                 double quantile, std::string* err) {
+  const uint32_t dim = 8 * kmer_length;
+  if (!(quantile > 0.0 && quantile <= 1.0)) {
+    if (err) *err = "the quantile must lie in (0, 1]";
+    return false;
+  }
+  // the centroids as the points file holds them (6 significant digits): what a search is given as its centres
+  std::vector<std::string> names;
+  std::vector<Point> written;
+  if (!ReadPointsFile(output_file + "hclust.format.txt", dim, &names, &written) || written.size() != families.size()) {
+    if (err) *err = "cannot read " + output_file + "hclust.format.txt back";
+    return false;
+  }
+  std::ofstream fout((output_file + "hclust.radii.txt").c_str());
+  if (!fout) {
+    if (err) *err = "cannot write " + output_file + "hclust.radii.txt";
+    return false;
+  }
+  for (size_t f = 0; f < families.size(); ++f) {
+    const std::vector<std::string>& seqs = families[f].seqs;
+    std::vector<double> d2s;
+    for (size_t m = 0; m < seqs.size(); ++m) {  // (letters and lengths were checked by FamilyCenters)
+      double d2 = 0.0;  // PairwiseDistance_square: left to right
+      for (uint32_t p = 0; p < kmer_length; ++p) {
+        const int row = HS_LETTER_TO_CODE[seqs[m][p] - 'A'];
+        for (uint32_t j = 0; j < 8; ++j) {
+          const double r = HS_AA_COORDS[row][j] - written[f].data[8 * p + j];
+          d2 += r * r;
+        }
+      }
+      d2s.push_back(d2);
+    }
+    std::sort(d2s.begin(), d2s.end());
+    // nearest rank: the smallest member distance that at least quantile x n of the members do not exceed
+    size_t rank = (size_t)ceil(quantile * (double)d2s.size());
+    rank = std::min(std::max<size_t>(rank, 1), d2s.size());
+    char num[64];
+    snprintf(num, sizeof(num), "%.17g", RadiusCovering(d2s[rank - 1]));
+    fout << families[f].name << " " << num << std::endl;
+  }
+  return true;
+}
+
+bool ReadRadiiFile(const std::string& path, const std::vector<std::string>& center_names,
+                   std::vector<double>* radii, std::string* err) {
+  std::ifstream fin(path.c_str());
+  if (!fin) {
+    if (err) *err = "cannot open " + path;
+    return false;
+  }
+  std::unordered_map<std::string, size_t> index;
+  for (size_t i = 0; i < center_names.size(); ++i)
+    if (!index.insert(std::make_pair(center_names[i], i)).second) {
+      if (err) *err = "radii: centre name '" + center_names[i] + "' is not unique in the centres file";
+      return false;
+    }
+  radii->assign(center_names.size(), 0.0);
+  std::vector<char> seen(center_names.size(), 0);
+  std::string line;
+  size_t line_no = 0;
+  const char* ws = " \t\r";
+  while (std::getline(fin, line)) {
+    ++line_no;
+    const size_t last = line.find_last_not_of(ws);
+    if (last == std::string::npos) continue;  // blank line
+    line.erase(last + 1);
+    const std::string where = path + ":" + std::to_string(line_no) + ": ";
+    const size_t gap = line.find_last_of(ws);
+    const size_t name_end = gap == std::string::npos ? std::string::npos : line.find_last_not_of(ws, gap);
+    if (name_end == std::string::npos) {
+      if (err) *err = where + "expected '<centre name> <radius>'";
+      return false;
+    }
+    const std::string name = line.substr(0, name_end + 1), number = line.substr(gap + 1);
+    char* end = nullptr;
+    errno = 0;
+    const double r = strtod(number.c_str(), &end);
+    if (end == number.c_str() || *end != '\0' || !(r == r)) {
+      if (err) *err = where + "'" + number + "' is not a radius";
+      return false;
+    }
+    const auto it = index.find(name);
+    if (it == index.end()) {
+      if (err) *err = where + "'" + name + "' is not a centre";
+      return false;
+    }
+    if (seen[it->second]) {
+      if (err) *err = where + "centre '" + name + "' has a radius already";
+      return false;
+    }
+    seen[it->second] = 1;
+    (*radii)[it->second] = r;
+  }
+  for (size_t i = 0; i < seen.size(); ++i)
+    if (!seen[i]) {
+      if (err) *err = path + ": no radius for centre '" + center_names[i] + "'";
+      return false;
+    }
   return true;
 }
 

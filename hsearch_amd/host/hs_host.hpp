@@ -58,7 +58,11 @@ int Search(const std::vector<Point>& kmers, const std::vector<Point>& centers,
            const std::vector<std::string>& kmer_names, const std::vector<std::string>& center_names,
            const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
            const double& hash_R, const std::string& output_file, const Planes& planes, int device,
-           std::string* err, std::vector<uint64_t>* table_sizes = nullptr, uint32_t probes = 0);
+           std::string* err, std::vector<uint64_t>* table_sizes = nullptr, uint32_t probes = 0,
+           const std::vector<double>* radii = nullptr);
+// radii (Search, SearchProteins, SearchBruteForce and the one-GPU form of their *Sharded() versions): one radius
+// per centre in place of hash_R -- centre i's lines are those of a run with hash_R = (*radii)[i]
+// (hs_query_radii); the multi-GPU exchange takes one radius and refuses them.
 
 // How the rank threads of the *Sharded() functions exchange their hits: RCCL over xGMI (one rank per
 // GPU; the default), or host memory between rank threads whose `devices` may repeat -- the whole rank
@@ -91,7 +95,8 @@ int SearchSharded(const std::vector<Point>& kmers, const std::vector<Point>& cen
                   const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
                   const double& hash_R, const std::string& output_file, const Planes& planes,
                   const std::vector<int>& devices, bool use_comm, std::string* err,
-                  std::vector<uint64_t>* table_sizes = nullptr, uint32_t probes = 0);
+                  std::vector<uint64_t>* table_sizes = nullptr, uint32_t probes = 0,
+                  const std::vector<double>* radii = nullptr);
 
 // The planes file `--planes-out` writes and `--planes` reads: binary doubles a[L][K][dim], b[L][K].
 bool ReadPlanesFile(const std::string& path, uint32_t dim, uint32_t K, uint32_t L, double W, Planes* planes,
@@ -131,14 +136,15 @@ int SearchProteins(const ProteinDB& db, uint32_t kmer_length, const std::vector<
                    const uint32_t& hash_L, const double& hash_W, const double& hash_R,
                    const std::string& output_file, const Planes& planes, int device, std::string* err,
                    std::vector<uint64_t>* table_sizes = nullptr, uint64_t* n_windows = nullptr,
-                   bool best_per_position = false);
+                   bool best_per_position = false, const std::vector<double>* radii = nullptr);
 int SearchProteinsSharded(const ProteinDB& db, uint32_t kmer_length, const std::vector<Point>& centers,
                           const std::vector<std::string>& center_names, const uint32_t& hash_K,
                           const uint32_t& hash_L, const double& hash_W, const double& hash_R,
                           const std::string& output_file, const Planes& planes,
                           const std::vector<int>& devices, bool use_comm, std::string* err,
                           std::vector<uint64_t>* table_sizes = nullptr, uint64_t* n_windows = nullptr,
-                          bool best_per_position = false, const std::vector<uint8_t>* center_codes = nullptr);
+                          bool best_per_position = false, const std::vector<uint8_t>* center_codes = nullptr,
+                          const std::vector<double>* radii = nullptr);
 // center_codes (CentersFromKmers): the centres are k-mers of the exact table -- the one a FASTA
 // database is embedded from -- and travel to the GPU as residue codes (hs_query_codes: k bytes per
 // centre instead of 64 k); the hits are those of the embedded centres, bit for bit.
@@ -205,7 +211,16 @@ int SearchBruteForce(const std::vector<Point>& kmers, const std::vector<Point>& 
                      const std::vector<std::string>& kmer_names,
                      const std::vector<std::string>& center_names, const double& hash_R,
                      const std::string& output_file, int device, std::string* err,
-                     bool write_not_less_than = false);
+                     bool write_not_less_than = false, const std::vector<double>* radii = nullptr);
+
+// The radii file of `--radii`: lines "<centre name> <radius>", any order, matched by name against the centres.
+// A centre without a line, a name given twice, a name that is no centre's or a radius that is not one finite
+// number is an error (*err says which).  radii[i] belongs to center_names[i].
+bool ReadRadiiFile(const std::string& path, const std::vector<std::string>& center_names,
+                   std::vector<double>* radii, std::string* err);
+// The per-family radius hs_center_distance_sampling writes: the smallest double R with R * R >= d2 (the hit
+// rule squares R).
+double RadiusCovering(double d2);
 
 // ---- evaluation tooling ------------------------------------------------------
 // evaluate2.cpp as it runs (:73-95): the hits file sorted by (motif, protein) and written
@@ -235,6 +250,14 @@ bool FamilyCenters(const std::vector<MotifFamily>& families, uint32_t kmer_lengt
 // (family name line, then the coordinates), i.e. the `-c` input of motif_both_points.
 bool Cluster2DataPoint(const std::vector<MotifFamily>& families, const std::vector<Point>& centers,
                        const std::string& output_file);
+// Beside it <output_file>hclust.radii.txt, "<family name> <radius>" per family (the `--radii` input of
+// motif_both_points): the radius that makes the family's members hits of its own centroid -- the reference's
+// cluster.radius (hclust.cpp:217-222, the largest member-to-centre distance) taken against the centroid AS
+// WRITTEN to hclust.format.txt (read back: it is printed at 6 significant digits), d2 summed left to right like
+// PairwiseDistance_square, R = RadiusCovering(d2), printed with 17 significant digits.  quantile in (0, 1]: the
+// nearest-rank quantile of the members' d2 in place of the maximum (1).  Call after Cluster2DataPoint.
+bool FamilyRadii(const std::vector<MotifFamily>& families, uint32_t kmer_length, const std::string& output_file,
+                 double quantile, std::string* err);
 // sequencedatabase2centers() (:138-190), the function main() runs: all centre-to-centre distances
 // (i < j) to <dir>/<output_file>innercenter_protein_centers_0.txt, and the distance of each of
 // the first min(100000, N) database points to each centre (centre-major) to

@@ -17,12 +17,17 @@
 // then embedded exactly from the table.  -d may also name a protein FASTA file (the
 // database kmer_search.cpp:180-181 takes): every length-k window of every sequence is then a DB
 // k-mer, enumerated on the device; --ref-compat-eq-swap reproduces the reference's E <-> Q exchange
-// on that path.
+// on that path.  --radii <file> (lines "<centre name> <radius>", any order, matched by name against the
+// centres): every centre is searched at its own radius (hs_query_radii); -T is then not needed, and ignored
+// with a notice if given; one GPU only.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
 
+#include <math.h>
+
+#include <algorithm>
 #include <fstream>
 #include <iostream>
 #include <map>
@@ -48,7 +53,8 @@ const Opt kOpts[] = {
     {"hash_K", 'K', "number of random lines [4]", false},
     {"hash_L", 'L', "number of hash tables [4]", false},
     {"window", 'W', "bucket width", true},
-    {"threshold", 'T', "kmer threshold", true},
+    {"threshold", 'T', "kmer threshold [REQUIRED unless --radii]", false},
+    {"radii", 'r', "file of '<centre name> <radius>' lines: every centre at its own radius (one GPU)", false},
     {"groundtruth", 'g', "groundtruth (sorted brute-force hits); optional", false},
     {"output", 'o', "output file name", true},
     {"seed", 's', "seed of the LSH planes [random_device]", false},
@@ -126,11 +132,22 @@ int main(int argc, const char* argv[]) {
       Help(argv[0]);
       return EXIT_SUCCESS;  // as the reference: option_missing() -> message, EXIT_SUCCESS
     }
+  const bool with_radii = val.count("radii") != 0;
+  if (!with_radii && !val.count("threshold")) {
+    fprintf(stderr, "missing required option -T\n");
+    Help(argv[0]);
+    return EXIT_SUCCESS;
+  }
+  if (with_radii && val.count("gpus") && atoi(val["gpus"].c_str()) > 1) {
+    fprintf(stderr, "ERROR: --radii runs on one GPU: it cannot be combined with --gpus %s\n", val["gpus"].c_str());
+    return EXIT_FAILURE;
+  }
+  if (with_radii && val.count("threshold")) fprintf(stderr, "--radii given: -T is ignored\n");
   const uint32_t kmer_length = (uint32_t)strtoul(val["len"].c_str(), nullptr, 10);
   const uint32_t hash_K = val.count("hash_K") ? (uint32_t)strtoul(val["hash_K"].c_str(), nullptr, 10) : 4;
   const uint32_t hash_L = val.count("hash_L") ? (uint32_t)strtoul(val["hash_L"].c_str(), nullptr, 10) : 4;
   const double hash_W = strtod(val["window"].c_str(), nullptr);
-  const double hash_R = strtod(val["threshold"].c_str(), nullptr);
+  double hash_R = with_radii ? 0.0 : strtod(val["threshold"].c_str(), nullptr);
   const int device = val.count("device") ? atoi(val["device"].c_str()) : 0;
   const uint32_t dim = 8 * kmer_length;
   uint32_t seed;
@@ -178,6 +195,16 @@ int main(int argc, const char* argv[]) {
       fprintf(stderr, "cannot open %s\n", val["center"].c_str());
       return EXIT_FAILURE;
     }
+    std::vector<double> radii;
+    if (with_radii) {
+      std::string rerr;
+      if (!hsearch::ReadRadiiFile(val["radii"], center_names, &radii, &rerr)) {
+        fprintf(stderr, "ERROR: %s\n", rerr.c_str());
+        return EXIT_FAILURE;
+      }
+      // (the evaluation step -g checks a hit's distance against the radius: the largest one here)
+      for (double r : radii) hash_R = std::max(hash_R, fabs(r));
+    }
     if (!fasta_db) std::cout << "number of kmers " << kmers.size() << std::endl;
     std::cout << "number of centers " << centers.size() << std::endl;
     hsearch::Planes planes;
@@ -190,7 +217,7 @@ int main(int argc, const char* argv[]) {
     } else {
       planes = hsearch::DrawPlanes(dim, hash_K, hash_L, hash_W, seed);
     }
-    const bool use_comm = val.count("gpus") != 0;
+    const bool use_comm = val.count("gpus") != 0 && !with_radii;  // (--radii --gpus 1: the one-GPU path)
     const int n_gpus = use_comm ? atoi(val["gpus"].c_str()) : 1;
     if (n_gpus < 1 || n_gpus > 64) {
       fprintf(stderr, "ERROR: --gpus must be 1..64\n");
@@ -248,10 +275,11 @@ int main(int argc, const char* argv[]) {
                                                   // k-mer centres over a FASTA database share its exact
                                                   // table: they go to the GPU as codes (hs_query_codes)
                                                   center_codes.empty() || val.count("centers-as-points")
-                                                      ? nullptr : &center_codes)
+                                                      ? nullptr : &center_codes,
+                                                  with_radii ? &radii : nullptr)
                  : hsearch::SearchSharded(kmers, centers, kmer_names, center_names, hash_K, hash_L, hash_W,
                                           hash_R, val["output"], planes, devices, use_comm, &err,
-                                          &table_sizes, (uint32_t)probes);
+                                          &table_sizes, (uint32_t)probes, with_radii ? &radii : nullptr);
     if (fasta_db && st == 0) std::cout << "number of kmers " << n_windows << std::endl;
     if (st != 0) {
       fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), st);

@@ -383,6 +383,40 @@ HS_API hs_status hs_query_codes_dev(hs_handle* h, const uint8_t* d_qcodes, uint6
 HS_API hs_status hs_merge_first_table_dev(hs_handle* h, uint32_t* d_q, uint32_t* d_id, uint32_t* d_table,
                                           double* d_dist, uint64_t n, uint64_t* n_out);
 
+/* ---- per-query radii ------------------------------------------------------------------------------ */
+
+/* A search in which every centre has its own radius (the centroids of motif families are not equally tight:
+ * hclust.cpp keeps cluster.radius per cluster).  Exactly one of centers [nq][d] / qcodes [nq][k] is non-NULL;
+ * radii [nq].
+ *
+ * Contract: the output is the concatenation, for q = 0 .. nq-1, of what the scalar call (hs_query /
+ * hs_query_codes / hs_bruteforce) returns for query q alone at R = radii[q], with hit_q = q; cand[q][l]
+ * likewise.  So: the hit test is d2 <= radii[q] * radii[q] in fp64 with the product rounded once (brute force:
+ * !(sqrt(d2) > radii[q])), the order is (query, table of first sight, id), distances are bit-identical, a
+ * negative radius behaves as it does in the scalar call, the handle's multi-probe setting and bucket partition
+ * apply as they do to the scalar call, and recognised k-mer centres and queries given as codes give the same
+ * bits as embedded points.  A NaN radius anywhere in the call is HS_ERR_INVALID -- for the _dev form detected on
+ * the device -- before any output is written.  Capacity follows the two-call pattern of hs_query.
+ *
+ * One call joins every bucket's members against ALL the queries that probe it, whatever their radii: the join
+ * kernels never see a radius (it lives in each query row's gamma, in the refinement's |c|^2 - R^2 slot and in
+ * the fp16 row's last column); the streaming / brute-force filters and the exact decision read radii[q].  What
+ * is decided per CALL -- 8-column rows (HS_OPT_WIDE_ROWS), the join's legality, the digit bound of -gamma -- is
+ * decided from the largest |radii[q]|, the conservative side of each rule.  The scalar entry points run as
+ * before, launch for launch. */
+HS_API hs_status hs_query_radii(hs_handle* h, const double* centers, const uint8_t* qcodes, uint64_t nq,
+                                const double* radii, uint32_t* hit_q, uint32_t* hit_id, uint32_t* hit_table,
+                                double* hit_dist, uint64_t cap, uint64_t* n_hits, uint64_t* cand);
+/* ... all pointers device pointers (n_hits: host); one small reduction over d_radii and one read-back per call */
+HS_API hs_status hs_query_radii_dev(hs_handle* h, const double* d_centers, const uint8_t* d_qcodes, uint64_t nq,
+                                    const double* d_radii, uint32_t* d_hit_q, uint32_t* d_hit_id,
+                                    uint32_t* d_hit_table, double* d_hit_dist, uint64_t cap, uint64_t* n_hits,
+                                    uint64_t* d_cand);
+/* hs_bruteforce with radii [nq] */
+HS_API hs_status hs_bruteforce_radii(hs_handle* h, const double* centers, uint64_t nq, const double* radii,
+                                     uint32_t* hit_q, uint32_t* hit_id, double* hit_dist, uint64_t cap,
+                                     uint64_t* n_hits);
+
 /* ---- brute force (row a11) ---------------------------------------------------------------------- */
 
 /* Replaces Search() of motif_both_points_noLSH.cpp:36-56: every (q, j) with !(sqrt(d2) > R),
