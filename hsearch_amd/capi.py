@@ -23,7 +23,7 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_index_shard_tuples_dev", "hs_index_shard_finish_dev", "hs_index_shard_end", "hs_index_save", "hs_index_load", "hs_index_file_check", "hs_klsh_draw_planes", "hs_klsh_codes",
            "hs_index_info_get", "hs_query", "hs_query_dev", "hs_query_codes", "hs_query_codes_dev", "hs_bruteforce",
            "hs_bruteforce_topk", "hs_merge_first_table_dev", "hs_query_radii", "hs_query_radii_dev",
-           "hs_bruteforce_radii"]
+           "hs_bruteforce_radii", "hs_annotate", "hs_annotate_dev", "hs_merge_best"]
 
 
 class HsError(RuntimeError):
@@ -105,6 +105,15 @@ def load(hooks=False):
             lib.hs_bruteforce_radii.restype = C.c_int
             lib.hs_bruteforce_radii.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        # annotation: (h, centers, qcodes, nq, R, radii, out_id, out_q, out_table, out_dist, cap, n_out)
+        if hasattr(lib, "hs_annotate"):
+            for fn in (lib.hs_annotate, lib.hs_annotate_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+            lib.hs_merge_best.restype = C.c_int
+            lib.hs_merge_best.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         _libs[hooks] = lib
     return _libs[hooks]
 
@@ -148,6 +157,33 @@ def key_strings_equal(x, y):
 
 def _vp(arr):
     return arr.ctypes.data_as(C.c_void_p)
+
+
+def merge_best(id, q, table, dist, cap=None):
+    """hs_merge_best (host only, no GPU): of n tuples in any order, per distinct id the one smallest under
+    (dist, table, q), rows in ascending id -- the rule of Engine.annotate, for merging several annotations or
+    reducing a raw hit list.  cap=None: as many rows as needed; a given cap that is too small raises
+    HsError(HS_ERR_CAPACITY) with the required size in .needed."""
+    id = np.ascontiguousarray(id, dtype=np.uint32)
+    q = np.ascontiguousarray(q, dtype=np.uint32)
+    table = np.ascontiguousarray(table, dtype=np.uint32)
+    dist = np.ascontiguousarray(dist, dtype=np.float64)
+    n = len(id)
+    assert id.shape == q.shape == table.shape == dist.shape == (n,)
+    room = n if cap is None else int(cap)
+    oid = np.empty(room, dtype=np.uint32)
+    oq = np.empty(room, dtype=np.uint32)
+    ot = np.empty(room, dtype=np.uint32)
+    od = np.empty(room, dtype=np.float64)
+    n_out = C.c_uint64(0)
+    st = load().hs_merge_best(_vp(id), _vp(q), _vp(table), _vp(dist), n, _vp(oid), _vp(oq), _vp(ot), _vp(od), room,
+                              C.byref(n_out))
+    if st != HS_OK:
+        e = HsError(st, "hs_merge_best")
+        e.needed = int(n_out.value)
+        raise e
+    m = int(n_out.value)
+    return dict(id=oid[:m], q=oq[:m], table=ot[:m], dist=od[:m])
 
 
 def index_file_check(path):
@@ -515,6 +551,51 @@ class Engine:
         st = self._lib.hs_query_radii_dev(self._h, None if codes else d_queries_ptr, d_queries_ptr if codes else None,
                                           nq, d_radii_ptr, d_q, d_id, d_table, d_dist, cap, C.byref(n),
                                           d_cand if d_cand else None)
+        if st == HS_ERR_CAPACITY:
+            e = HsError(st, self._lib.hs_last_error(self._h).decode())
+            e.needed = int(n.value)
+            raise e
+        self._check(st)
+        return int(n.value)
+
+    def annotate(self, queries, R=None, radii=None, codes=False, cap=None):
+        """hs_annotate: per DB k-mer reached, the nearest centre -- of the hits query() / query_codes() (R) or
+        query_radii() (radii) would return, per distinct id the one smallest under (dist, table, q), in ascending
+        id.  queries are points [nq][d], or with codes=True residue codes [nq][k].  cap=None: sized by the index."""
+        queries = np.ascontiguousarray(queries, dtype=np.uint8 if codes else np.float64)
+        nq = queries.shape[0]
+        assert queries.shape == (nq, self.k if codes else self.d)
+        assert (R is None) != (radii is None), "exactly one of R and radii"
+        if radii is not None:
+            radii = np.ascontiguousarray(radii, dtype=np.float64)
+            assert radii.shape == (nq,)
+        if cap is None:  # the index's n always suffices
+            info = _IndexInfo()
+            cap = max(1024, int(info.n)) if self._lib.hs_index_info_get(self._h, C.byref(info)) == HS_OK else 1024
+        cap = int(cap)
+        while True:
+            oid = np.empty(cap, dtype=np.uint32)
+            oq = np.empty(cap, dtype=np.uint32)
+            ot = np.empty(cap, dtype=np.uint32)
+            od = np.empty(cap, dtype=np.float64)
+            n = C.c_uint64(0)
+            st = self._lib.hs_annotate(self._h, None if codes else _vp(queries), _vp(queries) if codes else None, nq,
+                                       0.0 if R is None else float(R), None if radii is None else _vp(radii),
+                                       _vp(oid), _vp(oq), _vp(ot), _vp(od), cap, C.byref(n))
+            if st == HS_ERR_CAPACITY:
+                cap = int(n.value)
+                continue
+            self._check(st)
+            n = int(n.value)
+            return dict(id=oid[:n], q=oq[:n], table=ot[:n], dist=od[:n])
+
+    def annotate_dev(self, d_queries_ptr, nq, R, d_radii_ptr, d_id, d_q, d_table, d_dist, cap, codes=False):
+        """hs_annotate_dev (device pointers as ints; d_radii_ptr None or 0: every query at R).  Returns the number
+        of rows; raises HsError(HS_ERR_CAPACITY) with the required size in .needed when cap is too small."""
+        n = C.c_uint64(0)
+        st = self._lib.hs_annotate_dev(self._h, None if codes else d_queries_ptr, d_queries_ptr if codes else None,
+                                       nq, float(R), d_radii_ptr if d_radii_ptr else None, d_id, d_q, d_table, d_dist,
+                                       cap, C.byref(n))
         if st == HS_ERR_CAPACITY:
             e = HsError(st, self._lib.hs_last_error(self._h).decode())
             e.needed = int(n.value)

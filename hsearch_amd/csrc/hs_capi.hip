@@ -119,6 +119,9 @@ struct QueryCall {
   const uint8_t* pre_valid = nullptr;
   // hs_query_radii: every query's own radius ([nq], device); null: R for all.  Searches and brute force only.
   const double* radii = nullptr;
+  // hs_annotate: the batches' hits are not ordered or handed out but reduced to the nearest centre per DB id
+  // (annot_reduce); the call passes no output arrays (cap = 0)
+  bool annotate = false;
 };
 
 // What a handle learns from its batches to steer the next ones (plan_batch, the join launch); written by
@@ -196,6 +199,12 @@ struct hs_handle {
   uint64_t mp_room = 0;
   DevBuf mp_pts, mp_codes, mp_ints, mp_frac, mp_vints, mp_valid, mp_rows, mp_q, mp_id, mp_table, mp_dist, mp_cand;
   DevBuf mp_radii;   // ... and, for a call with per-query radii, the probe rows' radii
+  // hs_annotate (hs_annotate.hip): smallest distance and its (table, q) per DB id, the ids touched by the call and
+  // their count, the touched ids sorted.  ann_clean: slots [0, ann_clean) of ann_dist are known to be empty;
+  // ann_open: a call is (or ended early while) reducing -- the next one empties all slots first
+  DevBuf ann_dist, ann_tq, ann_touched, ann_sorted, ann_cnt;
+  uint64_t ann_clean = 0;
+  bool ann_open = false;
   DevBuf io_radii;   // hs_query_radii: the radii on the device; hs_query_radii_dev: {max |radius|, NaN flag}
   DevBuf qcodes_buf, qembed;  // hs_query_codes: a batch's checked copy of the query codes; their embedding
                               // when no from-codes path applies
@@ -787,7 +796,8 @@ void hs_destroy(hs_handle* h) {
                     &h->subset_ids, &h->qcodes_buf, &h->qembed, &h->seg_res, &h->seg_of, &h->t_rho, &h->rec_codes, &h->qpacked, &h->hit_rank, &h->hit_kv, &h->bs_fptab, &h->bs_blk,
                     &h->bs_dk, &h->bs_hist, &h->bs_rank, &h->mp_pts, &h->mp_codes, &h->mp_ints, &h->mp_frac,
                     &h->mp_vints, &h->mp_valid, &h->mp_rows, &h->mp_q, &h->mp_id, &h->mp_table, &h->mp_dist,
-                    &h->mp_cand, &h->mp_radii, &h->io_radii};
+                    &h->mp_cand, &h->mp_radii, &h->io_radii, &h->ann_dist, &h->ann_tq, &h->ann_touched,
+                    &h->ann_sorted, &h->ann_cnt};
   for (DevBuf* bf : bufs) bf->release();
   h->sj_host.release();
   h->t_dirjump.release();
@@ -2837,6 +2847,16 @@ static hs_status query_batch(hs_handle* h, const QueryCall& c, uint32_t nq, uint
 static hs_status mp_query(hs_handle* h, const QueryCall& c, uint64_t nq, uint32_t* d_hit_q, uint32_t* d_hit_id,
                           uint32_t* d_hit_table, double* d_hit_dist, uint64_t cap, uint64_t* n_hits, uint64_t* d_cand);
 
+// hs_annotate: n hits -- a batch's (key, value) pairs, or with d_key == null the four arrays of a merged list --
+// into the handle's nearest-centre state (annot_begin has prepared it), on the handle's stream
+static hs_status annot_reduce(hs_handle* h, const uint64_t* d_key, const uint64_t* d_val, const uint32_t* d_q,
+                              const uint32_t* d_id, const uint32_t* d_table, const double* d_dist, uint64_t n) {
+  HS_HIP(h, hs_launch_annot_reduce(d_key, d_val, d_q, d_id, d_table, d_dist, (uint32_t)n, h->ann_dist.as<uint64_t>(),
+                                   h->ann_tq.as<uint32_t>(), (uint32_t)h->n, h->ann_touched.as<uint32_t>(),
+                                   h->ann_cnt.as<uint32_t>(), h->stream));
+  return HS_OK;
+}
+
 static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_hit_q, uint32_t* d_hit_id,
                            uint32_t* d_hit_table, double* d_hit_dist, uint64_t cap, uint64_t* n_hits, uint64_t* d_cand) {
   if (!h || !n_hits) return HS_ERR_INVALID;
@@ -2916,6 +2936,15 @@ static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_h
         continue;
       }
       if (st) return st;
+      if (c.annotate) {
+        // Only a batch that came through whole is reduced: one cut in halves (HS_SPLIT_BATCH) has handed nothing on
+        // yet, and its halves bring each hit once.  (Reducing a hit twice would be harmless all the same: both
+        // steps of the reduction are idempotent.)
+        HS_CHECK(annot_reduce(h, h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(), nullptr, nullptr, nullptr,
+                              nullptr, nh));
+        total += nh;
+        continue;
+      }
       if (nh && !bout.ordered) {
         // (brute force, a query with very many hits, HS_SORT_HITS) order of the reference's output
         // by a radix sort on (query, table of first sight, id)
@@ -2946,7 +2975,7 @@ static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_h
   h->prof.ms_total = ev_ms(h, 8, 9);
   h->prof.hits = total;
   *n_hits = total;
-  if (total > cap) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
+  if (total > cap && !c.annotate) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
   return HS_OK;
 }
 
@@ -3027,6 +3056,7 @@ static hs_status mp_query(hs_handle* h, const QueryCall& c, uint64_t nq, uint32_
     HS_CHECK(mp_probes(h, pts, nc, (uint64_t)P * L, 1, L));
     HS_HIP(h, hipEventRecord(h->ev[1], h->stream));
     QueryCall vc = c;
+    vc.annotate = false;  // (the probe rows' hits come back as a list: a row's table is final only once merged)
     if (c.codes) {
       HS_HIP(h, h->mp_rows.reserve((size_t)nv * k));
       HS_HIP(h, hs_launch_mp_repeat_u8(c.codes + q0 * k, nv, (uint32_t)k, P, h->mp_rows.as<uint8_t>(), h->stream));
@@ -3070,7 +3100,10 @@ static hs_status mp_query(hs_handle* h, const QueryCall& c, uint64_t nq, uint32_
     uint64_t kept = 0;
     HS_CHECK(hs_merge_first_table_dev(h, h->mp_q.as<uint32_t>(), h->mp_id.as<uint32_t>(), h->mp_table.as<uint32_t>(),
                                       h->mp_dist.as<double>(), nh, &kept));
-    if (kept && total + kept <= cap) {
+    if (c.annotate) {  // the chunk's merged list -- bounded by the chunk -- is reduced where it lies
+      HS_CHECK(annot_reduce(h, nullptr, nullptr, h->mp_q.as<uint32_t>(), h->mp_id.as<uint32_t>(),
+                            h->mp_table.as<uint32_t>(), h->mp_dist.as<double>(), kept));
+    } else if (kept && total + kept <= cap) {
       HS_HIP(h, hipMemcpyAsync(d_hit_q + total, h->mp_q.p, kept * 4, hipMemcpyDeviceToDevice, h->stream));
       HS_HIP(h, hipMemcpyAsync(d_hit_id + total, h->mp_id.p, kept * 4, hipMemcpyDeviceToDevice, h->stream));
       if (d_hit_table)
@@ -3084,7 +3117,7 @@ static hs_status mp_query(hs_handle* h, const QueryCall& c, uint64_t nq, uint32_
   acc.hits = total;
   h->prof = acc;
   *n_hits = total;
-  if (total > cap) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
+  if (total > cap && !c.annotate) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
   return HS_OK;
 }
 
@@ -3254,6 +3287,140 @@ hs_status hs_query_radii_dev(hs_handle* h, const double* d_centers, const uint8_
   memcpy(&call.R, &red[0], 8);
   call.radii = nq ? d_radii : h->io_radii.as<double>();  // (nq = 0: no kernel reads the array)
   return run_query(h, call, nq, d_hit_q, d_hit_id, d_hit_table, d_hit_dist, cap, n_hits, d_cand);
+}
+
+// ---- hs_annotate: the nearest centre of every DB k-mer (kernels and the rule: hs_annotate.hip) ----
+// The handle's state ready for a call: slots sized by the index and empty, no id touched.  The slots come back
+// empty from the call that used them (the gather empties what it reads); all n are cleared only when they are new
+// or a call ended before its gather.
+static hs_status annot_begin(hs_handle* h) {
+  const size_t n = std::max<uint64_t>(h->n, 1);
+  if (h->ann_dist.cap < n * 8) h->ann_clean = 0;
+  HS_HIP(h, h->ann_dist.reserve(n * 8));
+  HS_HIP(h, h->ann_tq.reserve(n * 4));
+  HS_HIP(h, h->ann_touched.reserve(n * 4));
+  HS_HIP(h, h->ann_cnt.reserve(16));
+  if (h->ann_open || h->ann_clean < h->n) {
+    HS_HIP(h, hipMemsetAsync(h->ann_dist.p, 0xff, n * 8, h->stream));
+    h->ann_clean = h->n;
+  }
+  HS_HIP(h, hipMemsetAsync(h->ann_cnt.p, 0, 16, h->stream));
+  h->ann_open = true;
+  return HS_OK;
+}
+
+// The search with the reduction in place of the hit list; on success *cnt ids were touched and ann_sorted holds
+// them ascending.  d_radii: the call's radii on the device (R then the largest |radius|), or null.
+static hs_status annot_search(hs_handle* h, const double* d_centers, const uint8_t* d_qcodes, uint64_t nq, double R,
+                              const double* d_radii, uint32_t* cnt) {
+  *cnt = 0;
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
+  if (nq >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nq must be < 2^27 per call");
+  if (!(R == R)) return fail(h, HS_ERR_INVALID, "R is NaN");
+  HS_CHECK(annot_begin(h));
+  QueryCall call{d_centers, d_qcodes, R};
+  call.radii = d_radii;
+  call.annotate = true;
+  uint64_t n_hits = 0;
+  HS_CHECK(run_query(h, call, nq, nullptr, nullptr, nullptr, nullptr, 0, &n_hits, nullptr));
+  HS_HIP(h, hipMemcpyAsync(cnt, h->ann_cnt.p, 4, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  if (*cnt > h->n) return fail(h, HS_ERR_HIP, "hs_annotate: more ids touched than the index holds");
+  if (*cnt) {
+    HS_HIP(h, h->ann_sorted.reserve((size_t)*cnt * 4));
+    HS_HIP(h, h->temp.reserve(hs_sort_keys_u32_temp(*cnt) + 256));
+    HS_HIP(h, hs_sort_keys_u32(h->temp.p, h->temp.cap, h->ann_touched.as<uint32_t>(), h->ann_sorted.as<uint32_t>(), *cnt,
+                               std::max(1, bit_width_u32((uint32_t)(h->n - 1))), h->stream));
+  }
+  return HS_OK;
+}
+
+// The rows into device arrays (null: the caller's capacity is too small, no rows) and the slots empty again
+static hs_status annot_finish(hs_handle* h, uint32_t cnt, uint32_t* d_id, uint32_t* d_q, uint32_t* d_table,
+                              double* d_dist) {
+  HS_HIP(h, hs_launch_annot_gather(h->ann_sorted.as<uint32_t>(), cnt, h->ann_dist.as<uint64_t>(),
+                                   h->ann_tq.as<uint32_t>(), (uint32_t)h->n, d_id, d_q, d_table, d_dist, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  h->ann_open = false;
+  return HS_OK;
+}
+
+hs_status hs_annotate_dev(hs_handle* h, const double* d_centers, const uint8_t* d_qcodes, uint64_t nq, double R,
+                          const double* d_radii, uint32_t* d_out_id, uint32_t* d_out_q, uint32_t* d_out_table,
+                          double* d_out_dist, uint64_t cap, uint64_t* n_out) {
+  if (!h || !n_out) return HS_ERR_INVALID;
+  *n_out = 0;
+  if ((d_centers != nullptr) == (d_qcodes != nullptr))
+    return fail(h, HS_ERR_INVALID, "hs_annotate_dev: exactly one of d_centers and d_qcodes must be given");
+  if (cap && (!d_out_id || !d_out_q || !d_out_table || !d_out_dist)) return HS_ERR_INVALID;
+  hs_status st = ensure_device(h);
+  if (st) return st;
+  if (d_radii && nq && nq < (1ull << 27)) {  // the largest |radius| and the NaN test, as hs_query_radii_dev makes them
+    unsigned long long red[2] = {0ull, 0ull};
+    HS_HIP(h, h->io_radii.reserve(16));
+    HS_HIP(h, hipMemsetAsync(h->io_radii.p, 0, 16, h->stream));
+    HS_HIP(h, hs_launch_radii_max(d_radii, nq, h->io_radii.as<unsigned long long>(), h->stream));
+    HS_HIP(h, hipMemcpyAsync(red, h->io_radii.p, 16, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    if (red[1]) return fail(h, HS_ERR_INVALID, "a radius is NaN");
+    memcpy(&R, &red[0], 8);
+  } else if (d_radii) {
+    R = 0.0;
+  }
+  uint32_t cnt = 0;
+  HS_CHECK(annot_search(h, d_centers, d_qcodes, nq, R, nq ? d_radii : nullptr, &cnt));
+  *n_out = cnt;
+  const bool fits = cnt <= cap;
+  HS_CHECK(annot_finish(h, cnt, fits ? d_out_id : nullptr, d_out_q, d_out_table, d_out_dist));
+  return fits ? HS_OK : fail(h, HS_ERR_CAPACITY, "annotation buffers too small; see *n_out");
+}
+
+hs_status hs_annotate(hs_handle* h, const double* centers, const uint8_t* qcodes, uint64_t nq, double R,
+                      const double* radii, uint32_t* out_id, uint32_t* out_q, uint32_t* out_table, double* out_dist,
+                      uint64_t cap, uint64_t* n_out) {
+  if (!h || !n_out) return HS_ERR_INVALID;
+  *n_out = 0;
+  if ((centers != nullptr) == (qcodes != nullptr))
+    return fail(h, HS_ERR_INVALID, "hs_annotate: exactly one of centers and qcodes must be given");
+  if (cap && (!out_id || !out_q || !out_table || !out_dist)) return HS_ERR_INVALID;
+  if (nq >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nq must be < 2^27 per call");
+  if (radii && !radii_max_host(radii, nq, &R)) return fail(h, HS_ERR_INVALID, "a radius is NaN");
+  hs_status st = ensure_device(h);
+  if (st) return st;
+  const size_t cbytes = qcodes ? 0 : (size_t)nq * h->d * 8, kbytes = qcodes ? (size_t)nq * h->p.k : 0;
+  HS_HIP(h, h->io_centers.reserve(std::max<size_t>(16, cbytes)));
+  HS_HIP(h, h->io_codes.reserve(std::max<size_t>(16, kbytes)));
+  if (cbytes) HS_HIP(h, hipMemcpyAsync(h->io_centers.p, centers, cbytes, hipMemcpyHostToDevice, h->stream));
+  if (kbytes) HS_HIP(h, hipMemcpyAsync(h->io_codes.p, qcodes, kbytes, hipMemcpyHostToDevice, h->stream));
+  const double* d_radii = nullptr;
+  if (radii && nq) {
+    HS_HIP(h, h->io_radii.reserve(std::max<size_t>(16, (size_t)nq * 8)));
+    HS_HIP(h, hipMemcpyAsync(h->io_radii.p, radii, (size_t)nq * 8, hipMemcpyHostToDevice, h->stream));
+    d_radii = h->io_radii.as<double>();
+  }
+  uint32_t cnt = 0;
+  HS_CHECK(annot_search(h, qcodes ? nullptr : h->io_centers.as<double>(), qcodes ? h->io_codes.as<uint8_t>() : nullptr,
+                        nq, R, d_radii, &cnt));
+  *n_out = cnt;
+  if (cnt > cap) {
+    HS_CHECK(annot_finish(h, cnt, nullptr, nullptr, nullptr, nullptr));
+    return fail(h, HS_ERR_CAPACITY, "annotation buffers too small; see *n_out");
+  }
+  // the rows are staged on the device at their own size: 16 bytes per annotated k-mer cross PCIe
+  HS_HIP(h, h->io_q.reserve(std::max<size_t>(16, (size_t)cnt * 4)));
+  HS_HIP(h, h->io_id.reserve(std::max<size_t>(16, (size_t)cnt * 4)));
+  HS_HIP(h, h->io_table.reserve(std::max<size_t>(16, (size_t)cnt * 4)));
+  HS_HIP(h, h->io_dist.reserve(std::max<size_t>(16, (size_t)cnt * 8)));
+  HS_CHECK(annot_finish(h, cnt, h->io_id.as<uint32_t>(), h->io_q.as<uint32_t>(), h->io_table.as<uint32_t>(),
+                        h->io_dist.as<double>()));
+  if (cnt) {
+    HS_HIP(h, hipMemcpyAsync(out_id, h->io_id.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_q, h->io_q.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_table, h->io_table.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_dist, h->io_dist.p, (size_t)cnt * 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return HS_OK;
 }
 
 // The merge step of the TABLE-partitioned multi-GPU layout (include/hsearch.h): in place on n gathered tuples.

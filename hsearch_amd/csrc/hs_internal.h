@@ -211,6 +211,9 @@ hipError_t hs_sort_pairs_u64_u32(void* temp, size_t temp_bytes, const uint64_t* 
 size_t hs_sort_pairs_u32_u32_temp(size_t n);
 hipError_t hs_sort_pairs_u32_u32(void* temp, size_t temp_bytes, const uint32_t* kin, uint32_t* kout,
                                  const uint32_t* vin, uint32_t* vout, size_t n, int end_bit, hipStream_t s);
+size_t hs_sort_keys_u32_temp(size_t n);
+hipError_t hs_sort_keys_u32(void* temp, size_t temp_bytes, const uint32_t* kin, uint32_t* kout, size_t n, int end_bit,
+                            hipStream_t s);
 size_t hs_sort_pairs_u64_u64_temp(size_t n);
 hipError_t hs_sort_pairs_u64_u64(void* temp, size_t temp_bytes, const uint64_t* kin, uint64_t* kout,
                                  const uint64_t* vin, uint64_t* vout, size_t n, int end_bit,
@@ -515,6 +518,18 @@ hipError_t hs_launch_merge_compact(const uint64_t* d_key, const uint64_t* d_val,
 hipError_t hs_launch_unpack_hits(const uint64_t* d_key, const uint64_t* d_val, uint32_t n,
                                  uint32_t* d_q, uint32_t* d_id, uint32_t* d_table, double* d_dist,
                                  hipStream_t s);
+// nearest centre per DB id (hs_annotate.hip): a batch's hits -- (d_key, d_val) as the exact pass leaves them, or,
+// with d_key == null, the four arrays of a merged list -- reduced into best_dist / best_tq [n_slots]; ids whose
+// slot was HS_ANNOT_EMPTY are appended to d_touched (*d_n_touched counts them).  The gather writes row i from the
+// slot of d_sorted_id[i] (d_out_id == null: no rows) and empties the slot.
+#define HS_ANNOT_EMPTY 0xffffffffffffffffull
+hipError_t hs_launch_annot_reduce(const uint64_t* d_key, const uint64_t* d_val, const uint32_t* d_q,
+                                  const uint32_t* d_id, const uint32_t* d_table, const double* d_dist,
+                                  uint32_t n_hits, uint64_t* d_best_dist, uint32_t* d_best_tq, uint32_t n_slots,
+                                  uint32_t* d_touched, uint32_t* d_n_touched, hipStream_t s);
+hipError_t hs_launch_annot_gather(const uint32_t* d_sorted_id, uint32_t cnt, uint64_t* d_best_dist,
+                                  const uint32_t* d_best_tq, uint32_t n_slots, uint32_t* d_out_id, uint32_t* d_out_q,
+                                  uint32_t* d_out_table, double* d_out_dist, hipStream_t s);
 // brute force
 hipError_t hs_launch_bruteforce(const uint4* d_packed_all, uint32_t n, const float* d_tq,
                                 uint32_t nq, int k, float r2_hi, uint32_t* d_prov_count,

@@ -159,11 +159,47 @@ std::vector<double> TableCosts(hs_params prm, const Planes& planes, const double
 // every rank -- rank 0 writes the file -- holds all hits in the reference's order.
 // qcodes != null: the centres are k-mers of the handle's coordinate table, given as residue codes
 // [nq][k]; they cross PCIe as k bytes each (hs_query_codes) and `flat` is unused.
+// annotate: `out` receives, instead of the hits, per DB k-mer reached its nearest centre in ascending id (the rule
+// of hs_annotate, include/hsearch.h).  One GPU: hs_annotate, no hit list anywhere.  Query blocks over several
+// GPUs: every rank annotates its block, nothing is exchanged between them, and the ranks' lists -- query numbers
+// made global -- are merged by hs_merge_best.  Table and bucket partitions gather the hits as before; the gathered
+// list is reduced by hs_merge_best.
+
+// hs_annotate into `out` through the two-call pattern (a first capacity of 1 / 64 of the index)
+hs_status AnnotateInto(hs_handle* h, const double* flat, const uint8_t* qcodes, uint64_t nq, double R,
+                       const double* radii, SearchHits* out) {
+  hs_index_info info;
+  hs_status st = hs_index_info_get(h, &info);
+  if (st != HS_OK) return st;
+  uint64_t cap = std::max<uint64_t>(1024, info.n / 64);
+  for (;;) {
+    out->q.resize(cap);
+    out->id.resize(cap);
+    out->table.resize(cap);
+    out->dist.resize(cap);
+    st = hs_annotate(h, qcodes ? nullptr : flat, qcodes, nq, R, radii, out->id.data(), out->q.data(),
+                     out->table.data(), out->dist.data(), cap, &out->n);
+    if (st != HS_ERR_CAPACITY) return st;
+    cap = out->n;
+  }
+}
+
+// hs_merge_best over the first in.n tuples of `in`
+hs_status MergeBestInto(const SearchHits& in, SearchHits* out) {
+  out->q.resize(in.n);
+  out->id.resize(in.n);
+  out->table.resize(in.n);
+  out->dist.resize(in.n);
+  return hs_merge_best(in.id.data(), in.q.data(), in.table.data(), in.dist.data(), in.n, out->id.data(),
+                       out->q.data(), out->table.data(), out->dist.data(), in.n, &out->n);
+}
+
 int RunSearch(hs_params prm, const Planes& planes, const double* coords,
               const std::function<hs_status(hs_handle*, uint32_t rank)>& build, const double* flat,
               const uint8_t* qcodes, uint64_t nq, double R, const std::vector<int>& devices, bool sharded,
               SearchHits* out, std::string* err, std::vector<uint64_t>* table_sizes,
-              const uint8_t* db_sample = nullptr, uint64_t n_db_sample = 0, const double* radii = nullptr) {
+              const uint8_t* db_sample = nullptr, uint64_t n_db_sample = 0, const double* radii = nullptr,
+              bool annotate = false) {
   const uint32_t world = (uint32_t)devices.size();
   if (!world) {
     if (err) *err = "no device given";
@@ -235,6 +271,11 @@ int RunSearch(hs_params prm, const Planes& planes, const double* coords,
       return st;
     }
     sizes(h);
+    if (annotate) {
+      st = AnnotateInto(h, flat, qcodes, nq, R, radii, out);
+      if (st != HS_OK && err) *err = std::string("hs_annotate: ") + hs_last_error(h);
+      return st;
+    }
     uint64_t cap = std::max<uint64_t>(1024, 16 * nq);
     for (;;) {
       out->q.resize(cap);
@@ -270,6 +311,8 @@ int RunSearch(hs_params prm, const Planes& planes, const double* coords,
   std::vector<hs_status> status(world, HS_OK);
   std::vector<std::string> msgs(world);
   std::vector<int> built(world, 0);
+  const bool annotate_blocks = annotate && !by_tables && !by_buckets;
+  std::vector<SearchHits> rank_rows(annotate_blocks ? world : 0);
   auto rank_main = [&](uint32_t r) {
     hs_handle* h = nullptr;
     hs_status st = open(devices[r], &h, &msgs[r], r);
@@ -292,6 +335,15 @@ int RunSearch(hs_params prm, const Planes& planes, const double* coords,
     if (r == 0 && !by_tables) sizes(h);
     uint64_t lo = 0, hi = 0;
     hs_shard_bounds(nq, world, r, &lo, &hi);
+    if (annotate_blocks) {  // this rank's block, annotated; merged below once every rank is done
+      SearchHits& rows = rank_rows[r];
+      st = AnnotateInto(h, qcodes ? nullptr : flat + lo * d, qcodes ? qcodes + lo * prm.k : nullptr, hi - lo, R, nullptr,
+                        &rows);
+      if (st != HS_OK) msgs[r] = std::string("hs_annotate: ") + hs_last_error(h);
+      for (uint64_t i = 0; st == HS_OK && i < rows.n; ++i) rows.q[i] += (uint32_t)lo;
+      status[r] = st;
+      return;
+    }
     SearchHits mine;  // ranks other than 0 drop theirs
     SearchHits* dst = r == 0 ? out : &mine;
     uint64_t cap = std::max<uint64_t>(1024, 16 * nq);
@@ -337,6 +389,29 @@ int RunSearch(hs_params prm, const Planes& planes, const double* coords,
       if (err) *err = "GPU " + std::to_string(devices[r]) + ": " + msgs[r];
       return status[r];
     }
+  if (annotate) {
+    SearchHits all;
+    if (annotate_blocks) {
+      for (const SearchHits& rows : rank_rows) {
+        all.q.insert(all.q.end(), rows.q.begin(), rows.q.begin() + rows.n);
+        all.id.insert(all.id.end(), rows.id.begin(), rows.id.begin() + rows.n);
+        all.table.insert(all.table.end(), rows.table.begin(), rows.table.begin() + rows.n);
+        all.dist.insert(all.dist.end(), rows.dist.begin(), rows.dist.begin() + rows.n);
+        all.n += rows.n;
+      }
+    } else {
+      all.q.swap(out->q);
+      all.id.swap(out->id);
+      all.table.swap(out->table);
+      all.dist.swap(out->dist);
+      all.n = out->n;
+    }
+    const hs_status mst = MergeBestInto(all, out);
+    if (mst != HS_OK) {
+      if (err) *err = "hs_merge_best failed";
+      return mst;
+    }
+  }
   return HS_OK;
 }
 
@@ -368,9 +443,11 @@ int Search(const std::vector<Point>& kmers, const std::vector<Point>& centers,
            const std::vector<std::string>& kmer_names, const std::vector<std::string>& center_names,
            const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
            const double& hash_R, const std::string& output_file, const Planes& planes, int device,
-           std::string* err, std::vector<uint64_t>* table_sizes, uint32_t probes, const std::vector<double>* radii) {
+           std::string* err, std::vector<uint64_t>* table_sizes, uint32_t probes, const std::vector<double>* radii,
+           bool best_per_position) {
   return SearchSharded(kmers, centers, kmer_names, center_names, hash_K, hash_L, hash_W, hash_R, output_file,
-                       planes, std::vector<int>(1, device), false, err, table_sizes, probes, radii);
+                       planes, std::vector<int>(1, device), false, err, table_sizes, probes, radii,
+                       best_per_position);
 }
 
 int SearchSharded(const std::vector<Point>& kmers, const std::vector<Point>& centers,
@@ -378,7 +455,8 @@ int SearchSharded(const std::vector<Point>& kmers, const std::vector<Point>& cen
                   const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
                   const double& hash_R, const std::string& output_file, const Planes& planes,
                   const std::vector<int>& devices, bool use_comm, std::string* err,
-                  std::vector<uint64_t>* table_sizes, uint32_t probes, const std::vector<double>* radii) {
+                  std::vector<uint64_t>* table_sizes, uint32_t probes, const std::vector<double>* radii,
+                  bool best_per_position) {
   if (!RadiiMatch(radii, centers.size(), err)) return HS_ERR_INVALID;
   struct ProbesScope {
     explicit ProbesScope(uint32_t t) { g_probes = t; }
@@ -406,10 +484,13 @@ int SearchSharded(const std::vector<Point>& kmers, const std::vector<Point>& cen
                            [&](hs_handle* h, uint32_t) { return hs_index_build(h, codes.data(), kmers.size()); },
                            flat.data(), nullptr, centers.size(), hash_R, devices, use_comm || devices.size() > 1,
                            &hits, err, table_sizes, codes.data(), std::min<uint64_t>(kmers.size(), 32768),
-                           radii ? radii->data() : nullptr);
+                           radii ? radii->data() : nullptr, best_per_position);
   if (st != HS_OK) return st;
   std::ofstream fout(output_file.c_str());
-  for (uint64_t i = 0; i < hits.n; ++i)  // :240-241
+  for (uint64_t i = 0; i < hits.n; ++i)  // :240-241; best_per_position: one line per k-mer reached, k-mers ascending
+    if (best_per_position)
+      fout << kmer_names[hits.id[i]] << " " << center_names[hits.q[i]] << " " << hits.dist[i] << std::endl;
+    else
     fout << center_names[hits.q[i]] << " " << kmer_names[hits.id[i]] << " " << hits.dist[i] << std::endl;
   fout.close();
   return HS_OK;
@@ -513,33 +594,20 @@ int SearchProteinsSharded(const ProteinDB& db, uint32_t kmer_length, const std::
         return bst;
       },
       flat.data(), center_codes ? center_codes->data() : nullptr, centers.size(), hash_R, devices,
-      use_comm || devices.size() > 1, &hits, err, table_sizes, nullptr, 0, radii ? radii->data() : nullptr);
+      use_comm || devices.size() > 1, &hits, err, table_sizes, nullptr, 0, radii ? radii->data() : nullptr,
+      best_per_position);
   if (rst != HS_OK) return rst;
   if (n_windows) *n_windows = n_win;
   const uint64_t n_hits = hits.n;
-  const std::vector<uint32_t>&hq = hits.q, &hid = hits.id, &ht = hits.table;
+  const std::vector<uint32_t>&hq = hits.q, &hid = hits.id;
   const std::vector<double>& hd = hits.dist;
   // the letter whose embedding is the stored row: with the E <-> Q exchange an input E is shown as
   // Q, which is what the reference's ProteinDB stores and prints
   const char* letters = HS_CODE_TO_LETTER;
   std::ofstream fout(output_file.c_str());
-  std::vector<uint64_t> order(n_hits);
-  for (uint64_t i = 0; i < n_hits; ++i) order[i] = i;
-  if (best_per_position) {
-    // kmer_search.cpp:96-121: visit order (table, centre); `it2->second.second > dis` replaces
-    std::sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) {
-      if (hid[x] != hid[y]) return hid[x] < hid[y];
-      if (hd[x] != hd[y]) return hd[x] < hd[y];
-      if (ht[x] != ht[y]) return ht[x] < ht[y];
-      return hq[x] < hq[y];
-    });
-    uint64_t kept = 0;
-    for (uint64_t i = 0; i < n_hits; ++i)
-      if (i == 0 || hid[order[i]] != hid[order[i - 1]]) order[kept++] = order[i];
-    order.resize(kept);
-  }
-  for (uint64_t oi = 0; oi < order.size(); ++oi) {
-    const uint64_t i = order[oi];
+  // best_per_position: the list is the annotation already (kmer_search.cpp:96-121 -- visit order (table, centre),
+  // `it2->second.second > dis` replaces -- reduced on the device: hs_annotate), windows ascending
+  for (uint64_t i = 0; i < n_hits; ++i) {
     const uint64_t pos = win_pos[hid[i]];
     // sequence of the window: largest s with start[s] <= pos
     const size_t s = (size_t)(std::upper_bound(db.start.begin(), db.start.end() - 1, pos) - db.start.begin()) - 1;

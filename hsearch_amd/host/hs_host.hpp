@@ -59,7 +59,7 @@ int Search(const std::vector<Point>& kmers, const std::vector<Point>& centers,
            const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
            const double& hash_R, const std::string& output_file, const Planes& planes, int device,
            std::string* err, std::vector<uint64_t>* table_sizes = nullptr, uint32_t probes = 0,
-           const std::vector<double>* radii = nullptr);
+           const std::vector<double>* radii = nullptr, bool best_per_position = false);
 // radii (Search, SearchProteins, SearchBruteForce and the one-GPU form of their *Sharded() versions): one radius
 // per centre in place of hash_R -- centre i's lines are those of a run with hash_R = (*radii)[i]
 // (hs_query_radii); the multi-GPU exchange takes one radius and refuses them.
@@ -96,7 +96,11 @@ int SearchSharded(const std::vector<Point>& kmers, const std::vector<Point>& cen
                   const double& hash_R, const std::string& output_file, const Planes& planes,
                   const std::vector<int>& devices, bool use_comm, std::string* err,
                   std::vector<uint64_t>* table_sizes = nullptr, uint32_t probes = 0,
-                  const std::vector<double>* radii = nullptr);
+                  const std::vector<double>* radii = nullptr, bool best_per_position = false);
+// best_per_position (Search, SearchSharded; SearchProteins* below): instead of the hits, one line per database
+// k-mer reached, "<kmer name> <center> <dist>" with its nearest centre, k-mers ascending -- hs_annotate on one
+// GPU; with query blocks over several GPUs every rank annotates its block and the lists are merged by
+// hs_merge_best; the table and bucket partitions gather the hits as before and reduce them by hs_merge_best.
 
 // The planes file `--planes-out` writes and `--planes` reads: binary doubles a[L][K][dim], b[L][K].
 bool ReadPlanesFile(const std::string& path, uint32_t dim, uint32_t K, uint32_t L, double W, Planes* planes,

@@ -19,7 +19,8 @@
 // k-mer, enumerated on the device; --ref-compat-eq-swap reproduces the reference's E <-> Q exchange
 // on that path.  --radii <file> (lines "<centre name> <radius>", any order, matched by name against the
 // centres): every centre is searched at its own radius (hs_query_radii); -T is then not needed, and ignored
-// with a notice if given; one GPU only.
+// with a notice if given; one GPU only.  --best-per-position 1: instead of the hits, one line per database k-mer
+// reached, "<kmer name> <centre> <dist>" with its nearest centre (hs_annotate), k-mers ascending.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -67,7 +68,7 @@ const Opt kOpts[] = {
     {"planes", 'p', "read the planes from this file (as written by --planes-out) instead of drawing them", false},
     {"planes-out", 'P', "write the planes (binary doubles a[L][K][d] then b[L][K])", false},
     {"ref-compat-eq-swap", 'Q', "FASTA database: exchange E and Q like the reference's ProteinDB [0]", false},
-    {"best-per-position", 'B', "FASTA database: one line per matched window, its nearest centre (kmer_search) [0]", false},
+    {"best-per-position", 'B', "one line per matched database k-mer (FASTA: window), its nearest centre (kmer_search) [0]", false},
 };
 
 // A points file has a line of numbers after its first name line; a FASTA file has residue letters.
@@ -266,12 +267,12 @@ int main(int argc, const char* argv[]) {
     std::string err;
     std::vector<uint64_t> table_sizes;
     uint64_t n_windows = 0;
+    const bool best_per_position = val.count("best-per-position") && atoi(val["best-per-position"].c_str()) != 0;
     const int st =
         fasta_db ? hsearch::SearchProteinsSharded(prodb, kmer_length, centers, center_names, hash_K, hash_L,
                                                   hash_W, hash_R, val["output"], planes, devices, use_comm,
                                                   &err, &table_sizes, &n_windows,
-                                                  val.count("best-per-position") &&
-                                                      atoi(val["best-per-position"].c_str()) != 0,
+                                                  best_per_position,
                                                   // k-mer centres over a FASTA database share its exact
                                                   // table: they go to the GPU as codes (hs_query_codes)
                                                   center_codes.empty() || val.count("centers-as-points")
@@ -279,7 +280,8 @@ int main(int argc, const char* argv[]) {
                                                   with_radii ? &radii : nullptr)
                  : hsearch::SearchSharded(kmers, centers, kmer_names, center_names, hash_K, hash_L, hash_W,
                                           hash_R, val["output"], planes, devices, use_comm, &err,
-                                          &table_sizes, (uint32_t)probes, with_radii ? &radii : nullptr);
+                                          &table_sizes, (uint32_t)probes, with_radii ? &radii : nullptr,
+                                          best_per_position);
     if (fasta_db && st == 0) std::cout << "number of kmers " << n_windows << std::endl;
     if (st != 0) {
       fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), st);

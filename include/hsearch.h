@@ -417,6 +417,43 @@ HS_API hs_status hs_bruteforce_radii(hs_handle* h, const double* centers, uint64
                                      uint32_t* hit_q, uint32_t* hit_id, double* hit_dist, uint64_t cap,
                                      uint64_t* n_hits);
 
+/* ---- nearest centre of every DB k-mer (annotation) ------------------------------------------------- */
+
+/* Which centre does every DB k-mer belong to: what kmer_search.cpp's Search() accumulates in `matches`
+ * (:90, :113-121), reduced on the device instead of from the hit list.  Exactly one of centers [nq][d] /
+ * qcodes [nq][k] is non-NULL; radii == NULL: every query is searched at R; else radii [nq] and R is ignored.
+ *
+ * Contract: let H be the hit list hs_query / hs_query_codes (radii == NULL) or hs_query_radii returns for the same
+ * arguments on the same handle -- so the handle's multi-probe setting and bucket partition apply as they do there,
+ * and recognised k-mer centres and queries given as codes give the same bits as embedded points.  The output has one
+ * row per distinct id of H: the hit of H with that id that is smallest under (dist, table, q), dist compared as
+ * doubles, table and q as integers -- tables ascending, centres ascending within a table, replaced only by a
+ * strictly smaller distance.  Rows are in ascending id; out_dist is bit-identical to that hit's hit_dist.
+ * A NaN radius, a query code outside the alphabet, an unbuilt index and nq >= 2^27 are errors exactly as in the
+ * underlying call, reported before any output is written.  Capacity follows the two-call pattern, and
+ * *n_out <= n (the index's k-mers) always: buffers sized once at n hold every call's result.
+ *
+ * The hit list is never materialised across the call's batches nor ordered per query: every batch's exact hits are
+ * reduced where they lie, into state of the handle that is sized by the index (16 bytes per DB k-mer plus the list of
+ * the ids touched), and the call's cost beyond the search grows with the hits and the touched ids, never with n.
+ * hs_query* calls run as before, launch for launch. */
+HS_API hs_status hs_annotate(hs_handle* h, const double* centers, const uint8_t* qcodes, uint64_t nq, double R,
+                             const double* radii, uint32_t* out_id, uint32_t* out_q, uint32_t* out_table,
+                             double* out_dist, uint64_t cap, uint64_t* n_out);
+/* ... every pointer but n_out in device memory (streams: as hs_query_dev); with radii one small reduction over
+ * them and one read-back per call, as in hs_query_radii_dev */
+HS_API hs_status hs_annotate_dev(hs_handle* h, const double* d_centers, const uint8_t* d_qcodes, uint64_t nq, double R,
+                                 const double* d_radii, uint32_t* d_out_id, uint32_t* d_out_q, uint32_t* d_out_table,
+                                 double* d_out_dist, uint64_t cap, uint64_t* n_out);
+/* The same rule on the host (no GPU, no handle) for ANY concatenation of n tuples in any order -- a raw hit list,
+ * several ranks' annotations of their query blocks (query numbers made global first), the parts of a bucket
+ * partition: per distinct id the tuple smallest under (dist, table, q), rows in ascending id.  The result does not
+ * depend on the order of the input; merging annotations gives the annotation of the union of the hit lists.
+ * Capacity as above (*n_out = distinct ids).  The outputs must not overlap the inputs. */
+HS_API hs_status hs_merge_best(const uint32_t* id, const uint32_t* q, const uint32_t* table, const double* dist,
+                               uint64_t n, uint32_t* out_id, uint32_t* out_q, uint32_t* out_table, double* out_dist,
+                               uint64_t cap, uint64_t* n_out);
+
 /* ---- brute force (row a11) ---------------------------------------------------------------------- */
 
 /* Replaces Search() of motif_both_points_noLSH.cpp:36-56: every (q, j) with !(sqrt(d2) > R),
