@@ -12,6 +12,7 @@ import pytest
 
 import hsearch_amd
 from hsearch_amd import capi, synth
+from tests.onradius_ref import covering_radius
 from tests.test_host_cli import _tool
 
 
@@ -31,15 +32,6 @@ def parse_radii(path):
         assert name not in out
         out[name] = float(num)
     return out
-
-
-def covering_radius(d2):
-    """The smallest double R with R * R >= d2: sqrt, one step up if the product falls short."""
-    r = math.sqrt(d2)
-    if r * r < d2:
-        r = math.nextafter(r, math.inf)
-    assert r * r >= d2 and (r == 0.0 or math.nextafter(r, 0.0) ** 2 < d2)
-    return r
 
 
 def member_d2(points_text, names, families):
