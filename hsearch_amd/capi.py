@@ -23,7 +23,8 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_index_shard_tuples_dev", "hs_index_shard_finish_dev", "hs_index_shard_end", "hs_index_save", "hs_index_load", "hs_index_file_check", "hs_klsh_draw_planes", "hs_klsh_codes",
            "hs_index_info_get", "hs_query", "hs_query_dev", "hs_query_codes", "hs_query_codes_dev", "hs_bruteforce",
            "hs_bruteforce_topk", "hs_merge_first_table_dev", "hs_query_radii", "hs_query_radii_dev",
-           "hs_bruteforce_radii", "hs_annotate", "hs_annotate_dev", "hs_merge_best"]
+           "hs_bruteforce_radii", "hs_annotate", "hs_annotate_dev", "hs_merge_best", "hs_components", "hs_components_dev",
+           "hs_components_range", "hs_components_range_dev", "hs_components_merge"]
 
 
 class HsError(RuntimeError):
@@ -114,6 +115,18 @@ def load(hooks=False):
             lib.hs_merge_best.restype = C.c_int
             lib.hs_merge_best.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        # components: (h, [first, count,] R, sqrt_test, label, n_components, n_edges); merge: (labels, m, n, out, n_out)
+        if hasattr(lib, "hs_components"):
+            for fn in (lib.hs_components, lib.hs_components_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_uint64),
+                               C.POINTER(C.c_uint64)]
+            for fn in (lib.hs_components_range, lib.hs_components_range_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_double, C.c_int, C.c_void_p,
+                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+            lib.hs_components_merge.restype = C.c_int
+            lib.hs_components_merge.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]
         _libs[hooks] = lib
     return _libs[hooks]
 
@@ -184,6 +197,23 @@ def merge_best(id, q, table, dist, cap=None):
         raise e
     m = int(n_out.value)
     return dict(id=oid[:m], q=oq[:m], table=ot[:m], dist=od[:m])
+
+
+def components_merge(labels, out=None):
+    """hs_components_merge (host only, no GPU): labels [m][n] uint32, m label arrays over the same n vertices as
+    Engine.components returns them (one per range of a partition, in any order) -> dict(label, n_components) of the
+    union of the m forests.  out: a uint32 [n] array to write into (it stays untouched when the input is invalid)."""
+    labels = np.ascontiguousarray(labels, dtype=np.uint32)
+    assert labels.ndim == 2
+    m, n = labels.shape
+    if out is None:
+        out = np.empty(n, dtype=np.uint32)
+    assert out.dtype == np.uint32 and out.shape == (n,) and out.flags["C_CONTIGUOUS"]
+    nc = C.c_uint64(0)
+    st = load().hs_components_merge(_vp(labels), m, n, _vp(out), C.byref(nc))
+    if st != HS_OK:
+        raise HsError(st, "hs_components_merge")
+    return dict(label=out, n_components=int(nc.value))
 
 
 def index_file_check(path):
@@ -683,6 +713,26 @@ class Engine:
             self._check(st)
             n = int(n.value)
             return dict(i=ei[:n], j=ej[:n], table=et[:n], dist=ed[:n])
+
+    def components(self, R, sqrt_test=True, first=0, count=None):
+        """hs_components / hs_components_range: the connected components of the graph self_join(R, sqrt_test, first,
+        count) returns, united on the device: dict(label uint32 [n] = the smallest id of every k-mer's component,
+        n_components, n_edges = len(self_join(...)["i"]))."""
+        info = _IndexInfo()
+        n = int(info.n) if self._lib.hs_index_info_get(self._h, C.byref(info)) == HS_OK else 0
+        count = n - first if count is None else count
+        label = np.empty(n, dtype=np.uint32)
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.hs_components_range(self._h, first, count, float(R), 1 if sqrt_test else 0, _vp(label),
+                                                  C.byref(nc), C.byref(ne)))
+        return dict(label=label, n_components=int(nc.value), n_edges=int(ne.value))
+
+    def components_dev(self, d_label_ptr, R, sqrt_test=True):
+        """hs_components_dev: the labels into uint32 [n] device memory (pointer as int); (n_components, n_edges)."""
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.hs_components_dev(self._h, float(R), 1 if sqrt_test else 0, d_label_ptr, C.byref(nc),
+                                                C.byref(ne)))
+        return int(nc.value), int(ne.value)
 
 
 def clustering(k, K, L, W, a, b, codes, R, device=0, coords=None):

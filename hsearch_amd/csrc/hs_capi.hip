@@ -122,6 +122,9 @@ struct QueryCall {
   // hs_annotate: the batches' hits are not ordered or handed out but reduced to the nearest centre per DB id
   // (annot_reduce); the call passes no output arrays (cap = 0)
   bool annotate = false;
+  // hs_components: a self-join whose batches' pairs are not ordered or handed out but united in the handle's
+  // union-find forest (cc_union); the call passes no output arrays (cap = 0)
+  bool components = false;
 };
 
 // What a handle learns from its batches to steer the next ones (plan_batch, the join launch); written by
@@ -205,6 +208,9 @@ struct hs_handle {
   DevBuf ann_dist, ann_tq, ann_touched, ann_sorted, ann_cnt;
   uint64_t ann_clean = 0;
   bool ann_open = false;
+  // hs_components (hs_components.hip): the union-find forest over the indexed k-mers (parent[x] <= x), the
+  // call's two 64-bit counts {ordered pairs, roots}, and the labels of a host-pointer call on their way out
+  DevBuf cc_parent, cc_cnt, cc_label;
   DevBuf io_radii;   // hs_query_radii: the radii on the device; hs_query_radii_dev: {max |radius|, NaN flag}
   DevBuf qcodes_buf, qembed;  // hs_query_codes: a batch's checked copy of the query codes; their embedding
                               // when no from-codes path applies
@@ -797,7 +803,7 @@ void hs_destroy(hs_handle* h) {
                     &h->bs_dk, &h->bs_hist, &h->bs_rank, &h->mp_pts, &h->mp_codes, &h->mp_ints, &h->mp_frac,
                     &h->mp_vints, &h->mp_valid, &h->mp_rows, &h->mp_q, &h->mp_id, &h->mp_table, &h->mp_dist,
                     &h->mp_cand, &h->mp_radii, &h->io_radii, &h->ann_dist, &h->ann_tq, &h->ann_touched,
-                    &h->ann_sorted, &h->ann_cnt};
+                    &h->ann_sorted, &h->ann_cnt, &h->cc_parent, &h->cc_cnt, &h->cc_label};
   for (DevBuf* bf : bufs) bf->release();
   h->sj_host.release();
   h->t_dirjump.release();
@@ -2936,6 +2942,13 @@ static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_h
         continue;
       }
       if (st) return st;
+      if (c.components) {
+        // as below: only a batch that came through whole hands its pairs on, and a pair united twice changes nothing
+        HS_HIP(h, hs_launch_cc_union(h->hit_key.as<uint64_t>(), nh, c.self_first, h->cc_parent.as<uint32_t>(),
+                                     (uint32_t)h->n, h->cc_cnt.as<uint64_t>(), h->stream));
+        total += nh;
+        continue;
+      }
       if (c.annotate) {
         // Only a batch that came through whole is reduced: one cut in halves (HS_SPLIT_BATCH) has handed nothing on
         // yet, and its halves bring each hit once.  (Reducing a hit twice would be harmless all the same: both
@@ -2975,7 +2988,7 @@ static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_h
   h->prof.ms_total = ev_ms(h, 8, 9);
   h->prof.hits = total;
   *n_hits = total;
-  if (total > cap && !c.annotate) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
+  if (total > cap && !c.annotate && !c.components) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
   return HS_OK;
 }
 
@@ -3568,6 +3581,94 @@ hs_status hs_self_join_range(hs_handle* h, uint64_t first, uint64_t count, doubl
   *n_edges = total;
   if (total > cap) return fail(h, HS_ERR_CAPACITY, "edge buffers too small; see *n_edges");
   return HS_OK;
+}
+
+// ---- hs_components: connected components of the self-join's graph (kernels and the invariant: hs_components.hip) ----
+// The self-join of [first, first + count) with every batch's pairs united where finalize_hits leaves them: no
+// per-query ordering, no edge arrays, no copies to the host.  d_label [n] (device) receives the labels.
+static hs_status components_run(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test,
+                                uint32_t* d_label, uint64_t* n_components, uint64_t* n_edges) {
+  if (!(R == R)) return fail(h, HS_ERR_INVALID, "R is NaN");
+  const uint32_t n_all = (uint32_t)h->n;
+  HS_HIP(h, h->cc_parent.reserve(std::max<size_t>(16, (size_t)n_all * 4)));
+  HS_HIP(h, h->cc_cnt.reserve(16));
+  HS_HIP(h, hs_launch_cc_begin(h->cc_parent.as<uint32_t>(), n_all, h->cc_cnt.as<uint64_t>(), h->stream));
+  const uint64_t end = first + count;
+  const uint32_t CH = 1u << 20;  // queries per chunk, as in hs_self_join_range
+  hs_profile acc;
+  memset(&acc, 0, sizeof(acc));
+  for (uint64_t q0 = first; q0 < end; q0 += CH) {
+    const uint64_t nq = std::min<uint64_t>(CH, end - q0);
+    const bool from_codes = self_codes_ok(h, R);
+    if (!from_codes) {
+      HS_HIP(h, h->io_centers.reserve((size_t)nq * h->d * 8));
+      HS_HIP(h, hs_launch_embed(h->codes.as<uint8_t>() + q0 * h->p.k, nq, (int)h->p.k, h->coords.as<double>(),
+                                h->io_centers.as<double>(), h->stream));
+    }
+    QueryCall call{from_codes ? nullptr : h->io_centers.as<double>(), nullptr, R, false, (uint32_t)q0, sqrt_test != 0};
+    call.components = true;
+    uint64_t nh = 0;
+    HS_CHECK(run_query(h, call, nq, nullptr, nullptr, nullptr, nullptr, 0, &nh, nullptr));
+    acc.ms_hash += h->prof.ms_hash; acc.ms_probe += h->prof.ms_probe; acc.ms_verify += h->prof.ms_verify;
+    acc.ms_join += h->prof.ms_join; acc.ms_finalize += h->prof.ms_finalize; acc.ms_total += h->prof.ms_total;
+    acc.candidates += h->prof.candidates; acc.provisional += h->prof.provisional;
+    acc.join_pairs += h->prof.join_pairs; acc.join_pairs_issued += h->prof.join_pairs_issued;
+    acc.join_items += h->prof.join_items; acc.join_batches += h->prof.join_batches;
+    acc.join_items_resident += h->prof.join_items_resident;
+    acc.verify_launches += h->prof.verify_launches;
+    acc.hash_values += h->prof.hash_values; acc.hash_flagged += h->prof.hash_flagged;
+  }
+  HS_HIP(h, hs_launch_cc_flatten(h->cc_parent.as<uint32_t>(), n_all, d_label, h->cc_cnt.as<uint64_t>(), h->stream));
+  uint64_t counts[2] = {0, 0};
+  HS_HIP(h, hipMemcpyAsync(counts, h->cc_cnt.p, 16, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  h->prof = acc;
+  h->prof.hits = counts[0];
+  *n_components = counts[1];
+  if (n_edges) *n_edges = counts[0];
+  return HS_OK;
+}
+
+static hs_status components_check(hs_handle* h, uint64_t first, uint64_t count, const uint32_t* label,
+                                  uint64_t* n_components, uint64_t* n_edges) {
+  if (!h || !n_components) return HS_ERR_INVALID;
+  *n_components = 0;
+  if (n_edges) *n_edges = 0;
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
+  if (h->n && !label) return HS_ERR_INVALID;
+  HS_CHECK(ensure_device(h));
+  if (first > h->n || count > h->n - first) return fail(h, HS_ERR_INVALID, "range outside the indexed k-mers");
+  return HS_OK;
+}
+
+hs_status hs_components_range_dev(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test,
+                                  uint32_t* d_label, uint64_t* n_components, uint64_t* n_edges) {
+  HS_CHECK(components_check(h, first, count, d_label, n_components, n_edges));
+  return components_run(h, first, count, R, sqrt_test, d_label, n_components, n_edges);
+}
+
+hs_status hs_components_dev(hs_handle* h, double R, int sqrt_test, uint32_t* d_label, uint64_t* n_components,
+                            uint64_t* n_edges) {
+  if (!h) return HS_ERR_INVALID;
+  return hs_components_range_dev(h, 0, h->n, R, sqrt_test, d_label, n_components, n_edges);
+}
+
+hs_status hs_components_range(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test, uint32_t* label,
+                              uint64_t* n_components, uint64_t* n_edges) {
+  HS_CHECK(components_check(h, first, count, label, n_components, n_edges));
+  HS_HIP(h, h->cc_label.reserve(std::max<size_t>(16, (size_t)h->n * 4)));
+  HS_CHECK(components_run(h, first, count, R, sqrt_test, h->cc_label.as<uint32_t>(), n_components, n_edges));
+  if (h->n) {  // 4 bytes per k-mer cross PCIe, whatever the number of edges
+    HS_HIP(h, hipMemcpyAsync(label, h->cc_label.p, (size_t)h->n * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return HS_OK;
+}
+
+hs_status hs_components(hs_handle* h, double R, int sqrt_test, uint32_t* label, uint64_t* n_components,
+                        uint64_t* n_edges) {
+  if (!h) return HS_ERR_INVALID;
+  return hs_components_range(h, 0, h->n, R, sqrt_test, label, n_components, n_edges);
 }
 
 hs_status hs_bruteforce_topk(hs_handle* h, const double* centers, uint64_t nq, uint32_t topk,

@@ -530,6 +530,14 @@ hipError_t hs_launch_annot_reduce(const uint64_t* d_key, const uint64_t* d_val, 
 hipError_t hs_launch_annot_gather(const uint32_t* d_sorted_id, uint32_t cnt, uint64_t* d_best_dist,
                                   const uint32_t* d_best_tq, uint32_t n_slots, uint32_t* d_out_id, uint32_t* d_out_q,
                                   uint32_t* d_out_table, double* d_out_dist, hipStream_t s);
+// connected components of the self-join's graph (hs_components.hip): d_parent [n] is a union-find forest with
+// parent[x] <= x, d_counts two 64-bit words {ordered pairs united, roots}.  begin: the identity and zero counts;
+// union: a batch's pairs (self_first + (key >> 37), (uint32_t)key) as the exact pass leaves them in d_key, the
+// pair of an id with itself skipped; flatten: d_label[i] = the root of i = the smallest id of i's component.
+hipError_t hs_launch_cc_begin(uint32_t* d_parent, uint32_t n, uint64_t* d_counts, hipStream_t s);
+hipError_t hs_launch_cc_union(const uint64_t* d_key, uint32_t n_hits, uint32_t self_first, uint32_t* d_parent,
+                              uint32_t n, uint64_t* d_counts, hipStream_t s);
+hipError_t hs_launch_cc_flatten(uint32_t* d_parent, uint32_t n, uint32_t* d_label, uint64_t* d_counts, hipStream_t s);
 // brute force
 hipError_t hs_launch_bruteforce(const uint4* d_packed_all, uint32_t n, const float* d_tq,
                                 uint32_t nq, int k, float r2_hi, uint32_t* d_prov_count,

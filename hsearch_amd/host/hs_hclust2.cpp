@@ -5,7 +5,8 @@
 // (also -kmers/-len/-hash_K/-hash_L/-window/-threshold/-output) and its exit behaviour (missing
 // option -> help, exit 0, :223-226; runtime error -> stderr, exit 1).  Additions: --seed (planes
 // drawn like the reference's LSH constructor, table l seeded seed + l; default random_device as
-// the reference) and --device.
+// the reference), --device, and -linkage greedy|single (-M): `single` writes the connected components of the
+// near-neighbour graph (hsearch::Components) in place of the greedy leader clusters; the default is the reference's.
 #include <stdio.h>
 #include <stdlib.h>
 #include <time.h>
@@ -35,6 +36,7 @@ const Opt kOpts[] = {
     {"output", 'o', "output file name", true},
     {"seed", 's', "seed of the LSH planes [random_device]", false},
     {"device", 'G', "GPU ordinal [0]", false},
+    {"linkage", 'M', "greedy (the reference's leader clusters) | single (connected components) [greedy]", false},
 };
 void Help(const char* prog) {
   fprintf(stderr, "Usage: %s [OPTIONS]\n\nOptions:\n", prog);
@@ -90,6 +92,11 @@ int main(int argc, const char* argv[]) {
   const double hash_W = strtod(val["window"].c_str(), nullptr);
   const double hash_R = strtod(val["threshold"].c_str(), nullptr);
   const int device = val.count("device") ? atoi(val["device"].c_str()) : 0;
+  const std::string linkage = val.count("linkage") ? val["linkage"] : "greedy";
+  if (linkage != "greedy" && linkage != "single") {
+    fprintf(stderr, "ERROR: -linkage must be greedy or single, not '%s'\n", linkage.c_str());
+    return EXIT_FAILURE;
+  }
   uint32_t seed;
   if (val.count("seed")) {
     seed = (uint32_t)strtoul(val["seed"].c_str(), nullptr, 10);
@@ -110,8 +117,11 @@ int main(int argc, const char* argv[]) {
     std::cout << "Clustering... " << std::endl;
     std::string err;
     uint64_t n_clusters = 0;
-    const int st = hsearch::Clustering(kmers, hash_K, hash_L, hash_W, hash_R, val["output"], planes,
-                                       device, seed, &err, &n_clusters);
+    const int st = linkage == "single"
+                       ? hsearch::Components(kmers, hash_K, hash_L, hash_W, hash_R, val["output"], planes, device, &err,
+                                             &n_clusters, seed)
+                       : hsearch::Clustering(kmers, hash_K, hash_L, hash_W, hash_R, val["output"], planes, device, seed,
+                                             &err, &n_clusters);
     if (st != 0) {
       fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), st);
       return EXIT_FAILURE;

@@ -806,17 +806,19 @@ bool CentersFromKmers(const std::vector<Kmer>& kmers, uint32_t kmer_length, std:
   return true;
 }
 
-int Clustering(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L,
-               const double& hash_W, const double& hash_R, const std::string& output_file,
-               const Planes& planes, int device, uint32_t unknown_seed, std::string* err,
-               uint64_t* n_clusters) {
+namespace {
+
+// The residue codes of hclust2's k-mers (KmerToCoordinates, hclust2.cpp:49-62), after the check that the planes
+// are the ones the options name: 0, or HS_ERR_INVALID with *err set.
+int ClusterCodes(const std::vector<Kmer>& kmers, uint32_t hash_K, uint32_t hash_L, double hash_W, const Planes& planes,
+                 uint32_t unknown_seed, std::vector<uint8_t>* codes, std::string* err) {
   const uint32_t dim = planes.dim, k = dim / 8;
   if (dim == 0 || dim % 8 != 0 || planes.K != hash_K || planes.L != hash_L || planes.W != hash_W) {
     if (err) *err = "planes do not match (dim, K, L, W)";
     return HS_ERR_INVALID;
   }
   const size_t n = kmers.size();
-  std::vector<uint8_t> codes(n * (size_t)k);
+  codes->resize(n * (size_t)k);
   std::minstd_rand unknown(unknown_seed);
   for (size_t i = 0; i < n; ++i) {
     if (kmers[i].seq.size() != k) {
@@ -827,9 +829,74 @@ int Clustering(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uin
       const int c = kmers[i].seq[p] - 'A';
       int code = (c >= 0 && c < 26) ? HS_LETTER_TO_CODE[c] : -1;  // base[], util.hpp:92
       if (code < 0) code = (int)(unknown() % 20);
-      codes[i * k + p] = (uint8_t)code;
+      (*codes)[i * k + p] = (uint8_t)code;
     }
   }
+  return HS_OK;
+}
+
+}  // namespace
+
+int Components(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
+               const double& hash_R, const std::string& output_file, const Planes& planes, int device,
+               std::string* err, uint64_t* n_clusters, uint32_t unknown_seed) {
+  std::vector<uint8_t> codes;
+  const int cs = ClusterCodes(kmers, hash_K, hash_L, hash_W, planes, unknown_seed, &codes, err);
+  if (cs != HS_OK) return cs;
+  const size_t n = kmers.size();
+  hs_params prm;
+  memset(&prm, 0, sizeof(prm));
+  prm.k = planes.dim / 8;
+  prm.K = hash_K;
+  prm.L = hash_L;
+  prm.W = hash_W;
+  prm.device = device;
+  hs_handle* h = nullptr;
+  hs_status st = hs_create(&prm, planes.a.data(), planes.b.data(), nullptr, &h);
+  std::vector<uint32_t> label(n);
+  uint64_t n_comp = 0;
+  const char* what = "hs_create";
+  if (st == HS_OK) {
+    what = "hs_index_build";
+    st = hs_index_build(h, codes.data(), n);
+  }
+  if (st == HS_OK) {
+    what = "hs_components";
+    st = hs_components(h, hash_R, 1, label.data(), &n_comp, nullptr);  // hclust2's test: sqrt(d2) <= R
+  }
+  if (st != HS_OK) {
+    if (err) *err = std::string(what) + ": " + (h ? hs_last_error(h) : "no handle");
+    if (h) hs_destroy(h);
+    return st;
+  }
+  hs_destroy(h);
+  // a cluster per root in ascending id (= ascending smallest member), members in ascending id
+  std::vector<uint32_t> size(n, 0), start(n + 1, 0), slot(n);
+  for (size_t i = 0; i < n; ++i) ++size[label[i]];
+  for (size_t i = 0; i < n; ++i) start[i + 1] = start[i] + size[i];
+  std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+  for (size_t i = 0; i < n; ++i) slot[fill[label[i]]++] = (uint32_t)i;
+  std::ofstream fout(output_file.c_str());
+  uint32_t cluster_id = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (label[i] != i) continue;
+    fout << "#clusterid:" << cluster_id++ << ":size" << size[i] << std::endl;
+    for (uint32_t t = start[i]; t < start[i + 1]; ++t) fout << kmers[slot[t]].name << std::endl;
+  }
+  fout.close();
+  if (n_clusters) *n_clusters = cluster_id;
+  return HS_OK;
+}
+
+int Clustering(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L,
+               const double& hash_W, const double& hash_R, const std::string& output_file,
+               const Planes& planes, int device, uint32_t unknown_seed, std::string* err,
+               uint64_t* n_clusters) {
+  std::vector<uint8_t> codes;
+  const int cs = ClusterCodes(kmers, hash_K, hash_L, hash_W, planes, unknown_seed, &codes, err);
+  if (cs != HS_OK) return cs;
+  const size_t n = kmers.size();
+  const uint32_t k = planes.dim / 8;
   hs_params prm;
   memset(&prm, 0, sizeof(prm));
   prm.k = k;

@@ -200,6 +200,14 @@ int Clustering(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uin
                const double& hash_W, const double& hash_R, const std::string& output_file,
                const Planes& planes, int device, uint32_t unknown_seed, std::string* err,
                uint64_t* n_clusters = nullptr);
+// Single linkage at radius R in place of the greedy leader pass: the clusters are the connected components of
+// the graph of all k-mer pairs that share a bucket in one of the L tables and lie within R (sqrt(d2) <= R, the
+// test of hclust2.cpp:64-71), which do not depend on the order of the k-mers.  One handle with all L tables, one
+// index build, one hs_components: no edge list anywhere.  The same clusters-file format, clusters in ascending
+// smallest member, members in ascending index; a k-mer without a neighbour is a cluster of size 1.
+int Components(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
+               const double& hash_R, const std::string& output_file, const Planes& planes, int device,
+               std::string* err, uint64_t* n_clusters = nullptr, uint32_t unknown_seed = 0);
 
 // evaulate() (:100-165) with weight() (:67-87): weighted recall of a hits file against a ground
 // truth file sorted by (motif, protein); also writes <output_file>.accuracy.txt.  Returns NaN

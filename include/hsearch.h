@@ -484,6 +484,47 @@ HS_API hs_status hs_self_join_range(hs_handle* h, uint64_t first, uint64_t count
                                     uint32_t* edge_table, double* edge_dist, uint64_t cap,
                                     uint64_t* n_edges);
 
+/* ---- connected components of the near-neighbour graph (single linkage at radius R) ------------------ */
+
+/* The families of the graph the self-join returns, reduced on the device instead of from the edge list (the
+ * clustering pcluster's UnionFind was meant for: its clustering step is an empty stub).
+ *
+ * Contract: let G be the undirected graph on the indexed k-mers 0 .. n-1 whose edges are exactly the pairs
+ * hs_self_join(h, R, sqrt_test, ...) returns on the same handle -- the same bucket rule over all L tables, the same
+ * exact fp64 test (sqrt_test selects sqrt(d2) <= R or d2 <= R*R), self pairs dropped; the handle's multi-probe
+ * setting and bucket partition are ignored, as the self-joins ignore them.  label[i] is the smallest id in i's
+ * component of G: label[i] <= i, and label[i] == i for exactly one k-mer per component; *n_components is the number
+ * of such i; *n_edges (may be NULL) is what hs_self_join* puts into *n_edges for the same arguments (ORDERED pairs).
+ * The result is a pure function of the index, R and sqrt_test: batch sizes, filter paths, options and the order in
+ * which the device happens to unite the pairs do not show in it.
+ * hs_components_range: the labels, over all n vertices, of the subgraph whose edges are those
+ * hs_self_join_range(first, count) returns; a k-mer without such an edge labels itself.  It is one rank's share
+ * when the i side is cut in blocks, and hs_components_merge joins the shares.
+ * Errors as in hs_self_join_range: an unbuilt index is HS_ERR_STATE, a range outside the index HS_ERR_INVALID.
+ * There is no capacity protocol: the output is always n labels.
+ *
+ * The edge list is never materialised, ordered per query or copied to the host: every batch's exact pairs are
+ * united where they lie, in a union-find forest of the handle that takes 4 bytes per indexed k-mer and nothing
+ * per edge (allocated by the first such call, kept with the handle).  n labels cross PCIe (none for the _dev
+ * forms).  hs_self_join*, hs_query*, hs_annotate* and hs_clustering* run as before, launch for launch. */
+HS_API hs_status hs_components(hs_handle* h, double R, int sqrt_test, uint32_t* label, uint64_t* n_components,
+                               uint64_t* n_edges);
+HS_API hs_status hs_components_range(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test,
+                                     uint32_t* label, uint64_t* n_components, uint64_t* n_edges);
+/* ... d_label [n] in device memory, the counts on the host (streams: as hs_query_dev) */
+HS_API hs_status hs_components_dev(hs_handle* h, double R, int sqrt_test, uint32_t* d_label, uint64_t* n_components,
+                                   uint64_t* n_edges);
+HS_API hs_status hs_components_range_dev(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test,
+                                         uint32_t* d_label, uint64_t* n_components, uint64_t* n_edges);
+/* The merge of such shares on the host (no GPU, no handle).  labels [m][n]: m label arrays over the same n
+ * vertices, each a forest given by its labels; out_label [n]: the labels (smallest id per component) of the union
+ * of the m forests.  Merging the shares of any partition of 0 .. n-1 into ranges gives hs_components' labels.
+ * The result does not depend on the order of the m arrays; the merge is idempotent and m = 1 returns its input
+ * (m = 0: every vertex labels itself).  An input with label[i] > i or label[label[i]] != label[i] is
+ * HS_ERR_INVALID, reported before anything is written.  out_label may be one of the inputs. */
+HS_API hs_status hs_components_merge(const uint32_t* labels, uint64_t m, uint64_t n, uint32_t* out_label,
+                                     uint64_t* n_components);
+
 /* Replaces Clustering() (hclust2.cpp:86-151) with explicit planes a[L][K][d], b[L][K]: table by
  * table, an LSH table over the not-yet-absorbed k-mers, then greedy leader clustering inside every
  * bucket in ascending id order.  The distance work runs on the GPU (hs_self_join per table), the
