@@ -24,7 +24,10 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_index_info_get", "hs_query", "hs_query_dev", "hs_query_codes", "hs_query_codes_dev", "hs_bruteforce",
            "hs_bruteforce_topk", "hs_merge_first_table_dev", "hs_query_radii", "hs_query_radii_dev",
            "hs_bruteforce_radii", "hs_annotate", "hs_annotate_dev", "hs_merge_best", "hs_components", "hs_components_dev",
-           "hs_components_range", "hs_components_range_dev", "hs_components_merge"]
+           "hs_components_range", "hs_components_range_dev", "hs_components_merge", "hs_degrees", "hs_degrees_dev",
+           "hs_degrees_range", "hs_degrees_range_dev", "hs_dbscan", "hs_dbscan_dev", "hs_dbscan_edges"]
+
+NOISE = 0xffffffff   # HS_NOISE: the label of a k-mer that is neither core nor border (hs_dbscan)
 
 
 class HsError(RuntimeError):
@@ -54,6 +57,11 @@ class _Profile(C.Structure):
 class _IndexInfo(C.Structure):
     _fields_ = [("n", C.c_uint64), ("device_bytes", C.c_uint64), ("n_buckets", C.c_uint64 * 32),
                 ("max_bucket", C.c_uint64 * 32), ("key_seed", C.c_uint32)]
+
+
+class _DbscanCounts(C.Structure):
+    _fields_ = [("n_clusters", C.c_uint64), ("n_core", C.c_uint64), ("n_border", C.c_uint64),
+                ("n_noise", C.c_uint64), ("n_edges", C.c_uint64)]
 
 
 profile_fields = [f[0] for f in _Profile._fields_]
@@ -127,6 +135,23 @@ def load(hooks=False):
                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
             lib.hs_components_merge.restype = C.c_int
             lib.hs_components_merge.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]
+        # degrees: (h, [first, count,] R, sqrt_test, degree, n_edges); dbscan: (h, R, sqrt_test, min_pts, label,
+        # degree, counts); dbscan_edges: (ei, ej, n_edges, n, min_pts, label, degree, counts)
+        if hasattr(lib, "hs_dbscan"):
+            for fn in (lib.hs_degrees, lib.hs_degrees_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]
+            for fn in (lib.hs_degrees_range, lib.hs_degrees_range_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_double, C.c_int, C.c_void_p,
+                               C.POINTER(C.c_uint64)]
+            for fn in (lib.hs_dbscan, lib.hs_dbscan_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p,
+                               C.POINTER(_DbscanCounts)]
+            lib.hs_dbscan_edges.restype = C.c_int
+            lib.hs_dbscan_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p,
+                                            C.c_void_p, C.POINTER(_DbscanCounts)]
         _libs[hooks] = lib
     return _libs[hooks]
 
@@ -214,6 +239,31 @@ def components_merge(labels, out=None):
     if st != HS_OK:
         raise HsError(st, "hs_components_merge")
     return dict(label=out, n_components=int(nc.value))
+
+
+def _counts_dict(c):
+    return {f[0]: int(getattr(c, f[0])) for f in _DbscanCounts._fields_}
+
+
+def dbscan_edges(ei, ej, n, min_pts, want_degree=False):
+    """hs_dbscan_edges (host only, no GPU): the rule of Engine.dbscan applied to any list of pairs (ei[t], ej[t]) over
+    n vertices -- either or both directions, repeated, in any order, self pairs ignored -> dict(label uint32 [n] with
+    NOISE for noise, degree if asked, n_clusters, n_core, n_border, n_noise, n_edges = the sum of the degrees)."""
+    ei = np.ascontiguousarray(ei, dtype=np.uint32)
+    ej = np.ascontiguousarray(ej, dtype=np.uint32)
+    assert ei.ndim == 1 and ei.shape == ej.shape
+    n = int(n)
+    label = np.empty(n, dtype=np.uint32)
+    degree = np.empty(n, dtype=np.uint32) if want_degree else None
+    c = _DbscanCounts()
+    st = load().hs_dbscan_edges(_vp(ei), _vp(ej), len(ei), n, int(min_pts), _vp(label),
+                                _vp(degree) if want_degree else None, C.byref(c))
+    if st != HS_OK:
+        raise HsError(st, "hs_dbscan_edges")
+    res = dict(label=label, **_counts_dict(c))
+    if want_degree:
+        res["degree"] = degree
+    return res
 
 
 def index_file_check(path):
@@ -733,6 +783,53 @@ class Engine:
         self._check(self._lib.hs_components_dev(self._h, float(R), 1 if sqrt_test else 0, d_label_ptr, C.byref(nc),
                                                 C.byref(ne)))
         return int(nc.value), int(ne.value)
+
+    def _n(self):
+        info = _IndexInfo()
+        return int(info.n) if self._lib.hs_index_info_get(self._h, C.byref(info)) == HS_OK else 0
+
+    def degrees(self, R, sqrt_test=True, first=0, count=None):
+        """hs_degrees / hs_degrees_range: uint32 [n], the number of distinct neighbours of every k-mer in the graph
+        self_join(R, sqrt_test, first, count) returns, counted on the device: np.bincount(self_join(...)["i"])."""
+        n = self._n()
+        count = n - first if count is None else count
+        degree = np.empty(n, dtype=np.uint32)
+        ne = C.c_uint64(0)
+        self._check(self._lib.hs_degrees_range(self._h, first, count, float(R), 1 if sqrt_test else 0, _vp(degree),
+                                               C.byref(ne)))
+        return degree
+
+    def degrees_dev(self, d_degree_ptr, R, sqrt_test=True, first=0, count=None):
+        """hs_degrees_range_dev: the degrees into uint32 [n] device memory (pointer as int); returns n_edges."""
+        count = self._n() - first if count is None else count
+        ne = C.c_uint64(0)
+        self._check(self._lib.hs_degrees_range_dev(self._h, first, count, float(R), 1 if sqrt_test else 0,
+                                                   d_degree_ptr, C.byref(ne)))
+        return int(ne.value)
+
+    def dbscan(self, R, min_pts, sqrt_test=True, want_degree=False):
+        """hs_dbscan: the density clusters of the graph self_join(R, sqrt_test) returns, reduced on the device:
+        dict(label uint32 [n] -- the smallest core id of the cluster, capi.NOISE for noise --, degree if asked,
+        n_clusters, n_core, n_border, n_noise, n_edges).  A k-mer is core with degree + 1 >= min_pts; a border
+        k-mer takes the label of its core neighbour with the smallest id."""
+        n = self._n()
+        label = np.empty(n, dtype=np.uint32)
+        degree = np.empty(n, dtype=np.uint32) if want_degree else None
+        c = _DbscanCounts()
+        self._check(self._lib.hs_dbscan(self._h, float(R), 1 if sqrt_test else 0, int(min_pts), _vp(label),
+                                        _vp(degree) if want_degree else None, C.byref(c)))
+        res = dict(label=label, **_counts_dict(c))
+        if want_degree:
+            res["degree"] = degree
+        return res
+
+    def dbscan_dev(self, d_label_ptr, R, min_pts, sqrt_test=True, d_degree_ptr=None):
+        """hs_dbscan_dev: the labels (and, with d_degree_ptr, the degrees) into uint32 [n] device memory (pointers as
+        ints); returns the dict of the five counts."""
+        c = _DbscanCounts()
+        self._check(self._lib.hs_dbscan_dev(self._h, float(R), 1 if sqrt_test else 0, int(min_pts), d_label_ptr,
+                                            d_degree_ptr, C.byref(c)))
+        return _counts_dict(c)
 
 
 def clustering(k, K, L, W, a, b, codes, R, device=0, coords=None):

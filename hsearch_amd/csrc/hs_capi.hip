@@ -125,6 +125,11 @@ struct QueryCall {
   // hs_components: a self-join whose batches' pairs are not ordered or handed out but united in the handle's
   // union-find forest (cc_union); the call passes no output arrays (cap = 0)
   bool components = false;
+  // hs_degrees / hs_dbscan (hs_dbscan.hip): a self-join of the same kind whose batches' pairs are counted into the
+  // handle's degree array (DB_DEGREE, pass 1) or, the degrees known, united and anchored at db_min_pts (DB_UNITE)
+  enum { DB_NONE = 0, DB_DEGREE, DB_UNITE };
+  int dbscan = DB_NONE;
+  uint32_t db_min_pts = 1;
 };
 
 // What a handle learns from its batches to steer the next ones (plan_batch, the join launch); written by
@@ -211,6 +216,9 @@ struct hs_handle {
   // hs_components (hs_components.hip): the union-find forest over the indexed k-mers (parent[x] <= x), the
   // call's two 64-bit counts {ordered pairs, roots}, and the labels of a host-pointer call on their way out
   DevBuf cc_parent, cc_cnt, cc_label;
+  // hs_degrees / hs_dbscan (hs_dbscan.hip): the degree and the smallest core neighbour per indexed k-mer (the forest
+  // is cc_parent: every call starts it from the identity), and the call's five 64-bit counts
+  DevBuf db_deg, db_anchor, db_cnt;
   DevBuf io_radii;   // hs_query_radii: the radii on the device; hs_query_radii_dev: {max |radius|, NaN flag}
   DevBuf qcodes_buf, qembed;  // hs_query_codes: a batch's checked copy of the query codes; their embedding
                               // when no from-codes path applies
@@ -803,7 +811,8 @@ void hs_destroy(hs_handle* h) {
                     &h->bs_dk, &h->bs_hist, &h->bs_rank, &h->mp_pts, &h->mp_codes, &h->mp_ints, &h->mp_frac,
                     &h->mp_vints, &h->mp_valid, &h->mp_rows, &h->mp_q, &h->mp_id, &h->mp_table, &h->mp_dist,
                     &h->mp_cand, &h->mp_radii, &h->io_radii, &h->ann_dist, &h->ann_tq, &h->ann_touched,
-                    &h->ann_sorted, &h->ann_cnt, &h->cc_parent, &h->cc_cnt, &h->cc_label};
+                    &h->ann_sorted, &h->ann_cnt, &h->cc_parent, &h->cc_cnt, &h->cc_label,
+                    &h->db_deg, &h->db_anchor, &h->db_cnt};
   for (DevBuf* bf : bufs) bf->release();
   h->sj_host.release();
   h->t_dirjump.release();
@@ -2949,6 +2958,25 @@ static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_h
         total += nh;
         continue;
       }
+      if (c.dbscan == QueryCall::DB_DEGREE) {
+        // NOT idempotent, unlike the reductions above and below: a pair counted twice is a wrong degree.  This
+        // holds because (1) only a batch that came through whole hands its pairs on -- one cut in halves
+        // (HS_SPLIT_BATCH) has `continue`d above before handing anything on, and its halves bring each pair once --
+        // and (2) hit_key holds each ordered pair once (the first-seen rule across the tables has run; the tests pin
+        // n_edges == len(self_join)).  The kernel is launched from this place and no other.
+        HS_HIP(h, hs_launch_db_degree(h->hit_key.as<uint64_t>(), nh, c.self_first, h->db_deg.as<uint32_t>(),
+                                      (uint32_t)h->n, h->db_cnt.as<uint64_t>(), h->stream));
+        total += nh;
+        continue;
+      }
+      if (c.dbscan == QueryCall::DB_UNITE) {
+        // the degrees are final (pass 1 ended at a kernel boundary); union and min are idempotent
+        HS_HIP(h, hs_launch_db_unite(h->hit_key.as<uint64_t>(), nh, c.self_first, h->db_deg.as<uint32_t>(),
+                                     c.db_min_pts, h->cc_parent.as<uint32_t>(), h->db_anchor.as<uint32_t>(),
+                                     (uint32_t)h->n, h->stream));
+        total += nh;
+        continue;
+      }
       if (c.annotate) {
         // Only a batch that came through whole is reduced: one cut in halves (HS_SPLIT_BATCH) has handed nothing on
         // yet, and its halves bring each hit once.  (Reducing a hit twice would be harmless all the same: both
@@ -2988,7 +3016,7 @@ static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_h
   h->prof.ms_total = ev_ms(h, 8, 9);
   h->prof.hits = total;
   *n_hits = total;
-  if (total > cap && !c.annotate && !c.components) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
+  if (total > cap && !c.annotate && !c.components && !c.dbscan) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
   return HS_OK;
 }
 
@@ -3583,20 +3611,15 @@ hs_status hs_self_join_range(hs_handle* h, uint64_t first, uint64_t count, doubl
   return HS_OK;
 }
 
-// ---- hs_components: connected components of the self-join's graph (kernels and the invariant: hs_components.hip) ----
-// The self-join of [first, first + count) with every batch's pairs united where finalize_hits leaves them: no
-// per-query ordering, no edge arrays, no copies to the host.  d_label [n] (device) receives the labels.
-static hs_status components_run(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test,
-                                uint32_t* d_label, uint64_t* n_components, uint64_t* n_edges) {
-  if (!(R == R)) return fail(h, HS_ERR_INVALID, "R is NaN");
-  const uint32_t n_all = (uint32_t)h->n;
-  HS_HIP(h, h->cc_parent.reserve(std::max<size_t>(16, (size_t)n_all * 4)));
-  HS_HIP(h, h->cc_cnt.reserve(16));
-  HS_HIP(h, hs_launch_cc_begin(h->cc_parent.as<uint32_t>(), n_all, h->cc_cnt.as<uint64_t>(), h->stream));
+// ---- self-joins reduced on the device (hs_components, hs_degrees, hs_dbscan) ----------------------------
+// The self-join of [first, first + count) with every batch's pairs reduced where finalize_hits leaves them, as `what`
+// says (components / dbscan): no per-query ordering, no edge arrays, no copies to the host.  The chunks' profiles
+// are added to *acc.
+static hs_status reduced_self_join(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test,
+                                   const QueryCall& what, hs_profile* acc_out) {
+  hs_profile& acc = *acc_out;
   const uint64_t end = first + count;
   const uint32_t CH = 1u << 20;  // queries per chunk, as in hs_self_join_range
-  hs_profile acc;
-  memset(&acc, 0, sizeof(acc));
   for (uint64_t q0 = first; q0 < end; q0 += CH) {
     const uint64_t nq = std::min<uint64_t>(CH, end - q0);
     const bool from_codes = self_codes_ok(h, R);
@@ -3606,7 +3629,9 @@ static hs_status components_run(hs_handle* h, uint64_t first, uint64_t count, do
                                 h->io_centers.as<double>(), h->stream));
     }
     QueryCall call{from_codes ? nullptr : h->io_centers.as<double>(), nullptr, R, false, (uint32_t)q0, sqrt_test != 0};
-    call.components = true;
+    call.components = what.components;
+    call.dbscan = what.dbscan;
+    call.db_min_pts = what.db_min_pts;
     uint64_t nh = 0;
     HS_CHECK(run_query(h, call, nq, nullptr, nullptr, nullptr, nullptr, 0, &nh, nullptr));
     acc.ms_hash += h->prof.ms_hash; acc.ms_probe += h->prof.ms_probe; acc.ms_verify += h->prof.ms_verify;
@@ -3618,6 +3643,23 @@ static hs_status components_run(hs_handle* h, uint64_t first, uint64_t count, do
     acc.verify_launches += h->prof.verify_launches;
     acc.hash_values += h->prof.hash_values; acc.hash_flagged += h->prof.hash_flagged;
   }
+  return HS_OK;
+}
+
+// ---- hs_components: connected components of the self-join's graph (kernels and the invariant: hs_components.hip) ----
+// reduced_self_join with every batch's pairs united; d_label [n] (device) receives the labels.
+static hs_status components_run(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test,
+                                uint32_t* d_label, uint64_t* n_components, uint64_t* n_edges) {
+  if (!(R == R)) return fail(h, HS_ERR_INVALID, "R is NaN");
+  const uint32_t n_all = (uint32_t)h->n;
+  HS_HIP(h, h->cc_parent.reserve(std::max<size_t>(16, (size_t)n_all * 4)));
+  HS_HIP(h, h->cc_cnt.reserve(16));
+  HS_HIP(h, hs_launch_cc_begin(h->cc_parent.as<uint32_t>(), n_all, h->cc_cnt.as<uint64_t>(), h->stream));
+  hs_profile acc;
+  memset(&acc, 0, sizeof(acc));
+  QueryCall what;
+  what.components = true;
+  HS_CHECK(reduced_self_join(h, first, count, R, sqrt_test, what, &acc));
   HS_HIP(h, hs_launch_cc_flatten(h->cc_parent.as<uint32_t>(), n_all, d_label, h->cc_cnt.as<uint64_t>(), h->stream));
   uint64_t counts[2] = {0, 0};
   HS_HIP(h, hipMemcpyAsync(counts, h->cc_cnt.p, 16, hipMemcpyDeviceToHost, h->stream));
@@ -3669,6 +3711,118 @@ hs_status hs_components(hs_handle* h, double R, int sqrt_test, uint32_t* label, 
                         uint64_t* n_edges) {
   if (!h) return HS_ERR_INVALID;
   return hs_components_range(h, 0, h->n, R, sqrt_test, label, n_components, n_edges);
+}
+
+// ---- hs_degrees / hs_dbscan: density clusters of the self-join's graph (kernels and the rule: hs_dbscan.hip) ----
+// Pass 1 over [first, first + count) into db_deg and, with min_pts != 0, pass 2 and the labels into d_label (device).
+// counts: {ordered pairs, clusters, core, border, noise}.  h->prof accumulates over both passes.
+static hs_status dbscan_run(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test, uint32_t min_pts,
+                            uint32_t* d_label, uint64_t counts[5]) {
+  if (!(R == R)) return fail(h, HS_ERR_INVALID, "R is NaN");
+  const uint32_t n_all = (uint32_t)h->n;
+  const size_t bytes = std::max<size_t>(16, (size_t)n_all * 4);
+  HS_HIP(h, h->db_deg.reserve(bytes));
+  HS_HIP(h, h->cc_parent.reserve(bytes));
+  HS_HIP(h, h->db_anchor.reserve(bytes));
+  HS_HIP(h, h->db_cnt.reserve(64));
+  HS_HIP(h, hs_launch_db_begin(h->db_deg.as<uint32_t>(), h->cc_parent.as<uint32_t>(), h->db_anchor.as<uint32_t>(), n_all,
+                               h->db_cnt.as<uint64_t>(), h->stream));
+  hs_profile acc;
+  memset(&acc, 0, sizeof(acc));
+  QueryCall what;
+  what.dbscan = QueryCall::DB_DEGREE;
+  HS_CHECK(reduced_self_join(h, first, count, R, sqrt_test, what, &acc));
+  if (min_pts) {
+    what.dbscan = QueryCall::DB_UNITE;
+    what.db_min_pts = min_pts;
+    HS_CHECK(reduced_self_join(h, first, count, R, sqrt_test, what, &acc));
+    HS_HIP(h, hs_launch_db_finish(h->cc_parent.as<uint32_t>(), h->db_deg.as<uint32_t>(), h->db_anchor.as<uint32_t>(),
+                                  min_pts, n_all, d_label, h->db_cnt.as<uint64_t>(), h->stream));
+  }
+  HS_HIP(h, hipMemcpyAsync(counts, h->db_cnt.p, 40, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  h->prof = acc;
+  h->prof.hits = counts[0];
+  return HS_OK;
+}
+
+// the n words of db_deg / cc_label to the caller: host memory or, on the handle's stream, device memory
+static hs_status dbscan_copy_out(hs_handle* h, uint32_t* dst, const DevBuf& src, bool to_device) {
+  if (!h->n || !dst) return HS_OK;
+  HS_HIP(h, hipMemcpyAsync(dst, src.p, (size_t)h->n * 4, to_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                           h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return HS_OK;
+}
+
+static hs_status degrees_any(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test, uint32_t* degree,
+                             uint64_t* n_edges, bool dev) {
+  if (!h) return HS_ERR_INVALID;
+  if (n_edges) *n_edges = 0;
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
+  if (h->n && !degree) return HS_ERR_INVALID;
+  HS_CHECK(ensure_device(h));
+  if (first > h->n || count > h->n - first) return fail(h, HS_ERR_INVALID, "range outside the indexed k-mers");
+  uint64_t counts[5] = {0, 0, 0, 0, 0};
+  HS_CHECK(dbscan_run(h, first, count, R, sqrt_test, 0, nullptr, counts));
+  HS_CHECK(dbscan_copy_out(h, degree, h->db_deg, dev));
+  if (n_edges) *n_edges = counts[0];
+  return HS_OK;
+}
+
+static hs_status dbscan_any(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, uint32_t* label, uint32_t* degree,
+                            hs_dbscan_counts* out, bool dev) {
+  if (!h || !out) return HS_ERR_INVALID;
+  memset(out, 0, sizeof(*out));
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
+  if (h->n && !label) return HS_ERR_INVALID;
+  if (!min_pts) return fail(h, HS_ERR_INVALID, "min_pts must be at least 1");
+  HS_CHECK(ensure_device(h));
+  uint32_t* d_label = label;
+  if (!dev) {
+    HS_HIP(h, h->cc_label.reserve(std::max<size_t>(16, (size_t)h->n * 4)));
+    d_label = h->cc_label.as<uint32_t>();
+  }
+  uint64_t counts[5] = {0, 0, 0, 0, 0};
+  HS_CHECK(dbscan_run(h, 0, h->n, R, sqrt_test, min_pts, d_label, counts));
+  if (!dev) HS_CHECK(dbscan_copy_out(h, label, h->cc_label, false));  // 4 (8 with the degrees) bytes per k-mer cross PCIe
+  HS_CHECK(dbscan_copy_out(h, degree, h->db_deg, dev));
+  out->n_edges = counts[0];
+  out->n_clusters = counts[1];
+  out->n_core = counts[2];
+  out->n_border = counts[3];
+  out->n_noise = counts[4];
+  return HS_OK;
+}
+
+hs_status hs_degrees_range(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test, uint32_t* degree,
+                           uint64_t* n_edges) {
+  return degrees_any(h, first, count, R, sqrt_test, degree, n_edges, false);
+}
+
+hs_status hs_degrees_range_dev(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test,
+                               uint32_t* d_degree, uint64_t* n_edges) {
+  return degrees_any(h, first, count, R, sqrt_test, d_degree, n_edges, true);
+}
+
+hs_status hs_degrees(hs_handle* h, double R, int sqrt_test, uint32_t* degree, uint64_t* n_edges) {
+  if (!h) return HS_ERR_INVALID;
+  return degrees_any(h, 0, h->n, R, sqrt_test, degree, n_edges, false);
+}
+
+hs_status hs_degrees_dev(hs_handle* h, double R, int sqrt_test, uint32_t* d_degree, uint64_t* n_edges) {
+  if (!h) return HS_ERR_INVALID;
+  return degrees_any(h, 0, h->n, R, sqrt_test, d_degree, n_edges, true);
+}
+
+hs_status hs_dbscan(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, uint32_t* label, uint32_t* degree,
+                    hs_dbscan_counts* out) {
+  return dbscan_any(h, R, sqrt_test, min_pts, label, degree, out, false);
+}
+
+hs_status hs_dbscan_dev(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, uint32_t* d_label, uint32_t* d_degree,
+                        hs_dbscan_counts* out) {
+  return dbscan_any(h, R, sqrt_test, min_pts, d_label, d_degree, out, true);
 }
 
 hs_status hs_bruteforce_topk(hs_handle* h, const double* centers, uint64_t nq, uint32_t topk,

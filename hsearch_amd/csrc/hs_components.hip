@@ -31,36 +31,9 @@
 #include <hip/hip_runtime.h>
 
 #include "hs_internal.h"
+#include "hs_unionfind.h"  // cc_find, cc_unite, cc_count: shared with hs_dbscan.hip
 
 namespace {
-
-inline unsigned cc_blocks(uint32_t n) { return (n + 255u) / 256u; }
-
-__device__ __forceinline__ uint32_t cc_load(const uint32_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void cc_store(uint32_t* p, uint32_t v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// the root of x, halving the path on the way (parent[x] <= x: every step descends)
-__device__ __forceinline__ uint32_t cc_find(uint32_t* __restrict__ parent, uint32_t x) {
-  for (;;) {
-    const uint32_t p = cc_load(parent + x);
-    if (p >= x) return x;  // (== x: a root; > x cannot be, and would end the walk rather than prolong it)
-    const uint32_t g = cc_load(parent + p);
-    if (g >= p) return p;
-    cc_store(parent + x, g);
-    x = g;
-  }
-}
-
-// one 64-bit add per wave of the number of lanes with `flag` (all lanes of the wave must call)
-__device__ __forceinline__ void cc_count(bool flag, unsigned long long* __restrict__ counter) {
-  const unsigned long long m = __ballot(flag);
-  if (m && (threadIdx.x & 63u) == (unsigned)(__ffsll((long long)m) - 1))
-    atomicAdd(counter, (unsigned long long)__popcll(m));
-}
 
 __global__ __launch_bounds__(256) void hs_cc_union_kernel(const uint64_t* __restrict__ key, uint32_t n_hits,
                                                           uint32_t self_first, uint32_t* __restrict__ parent,
@@ -76,13 +49,7 @@ __global__ __launch_bounds__(256) void hs_cc_union_kernel(const uint64_t* __rest
   }
   cc_count(live, n_pairs);
   if (!live) return;
-  for (;;) {
-    a = cc_find(parent, a);
-    b = cc_find(parent, b);
-    if (a == b) return;
-    const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
-    if (atomicCAS(parent + hi, hi, lo) == hi) return;
-  }
+  cc_unite(parent, a, b);
 }
 
 __global__ __launch_bounds__(256) void hs_cc_iota_kernel(uint32_t* __restrict__ parent, uint32_t n) {

@@ -538,6 +538,19 @@ hipError_t hs_launch_cc_begin(uint32_t* d_parent, uint32_t n, uint64_t* d_counts
 hipError_t hs_launch_cc_union(const uint64_t* d_key, uint32_t n_hits, uint32_t self_first, uint32_t* d_parent,
                               uint32_t n, uint64_t* d_counts, hipStream_t s);
 hipError_t hs_launch_cc_flatten(uint32_t* d_parent, uint32_t n, uint32_t* d_label, uint64_t* d_counts, hipStream_t s);
+// density clusters of the self-join's graph (hs_dbscan.hip): d_deg, d_parent, d_anchor [n], d_counts five 64-bit
+// words {ordered pairs, clusters, core, border, noise}.  begin: zero degrees, the identity, no anchors, zero counts;
+// degree (pass 1): deg[a] += 1 per pair (a, b) of a batch as the exact pass leaves them in d_key -- NOT idempotent,
+// every ordered pair must come exactly once; unite (pass 2, behind the kernel boundary of the last degree): cores
+// (deg + 1 >= min_pts) united, anchor[a] = the smallest core neighbour of a non-core a; finish: the labels and counts.
+hipError_t hs_launch_db_begin(uint32_t* d_deg, uint32_t* d_parent, uint32_t* d_anchor, uint32_t n, uint64_t* d_counts,
+                              hipStream_t s);
+hipError_t hs_launch_db_degree(const uint64_t* d_key, uint32_t n_hits, uint32_t self_first, uint32_t* d_deg, uint32_t n,
+                               uint64_t* d_counts, hipStream_t s);
+hipError_t hs_launch_db_unite(const uint64_t* d_key, uint32_t n_hits, uint32_t self_first, const uint32_t* d_deg,
+                              uint32_t min_pts, uint32_t* d_parent, uint32_t* d_anchor, uint32_t n, hipStream_t s);
+hipError_t hs_launch_db_finish(uint32_t* d_parent, const uint32_t* d_deg, const uint32_t* d_anchor, uint32_t min_pts,
+                               uint32_t n, uint32_t* d_label, uint64_t* d_counts, hipStream_t s);
 // brute force
 hipError_t hs_launch_bruteforce(const uint4* d_packed_all, uint32_t n, const float* d_tq,
                                 uint32_t nq, int k, float r2_hi, uint32_t* d_prov_count,

@@ -5,8 +5,9 @@
 // (also -kmers/-len/-hash_K/-hash_L/-window/-threshold/-output) and its exit behaviour (missing
 // option -> help, exit 0, :223-226; runtime error -> stderr, exit 1).  Additions: --seed (planes
 // drawn like the reference's LSH constructor, table l seeded seed + l; default random_device as
-// the reference), --device, and -linkage greedy|single (-M): `single` writes the connected components of the
-// near-neighbour graph (hsearch::Components) in place of the greedy leader clusters; the default is the reference's.
+// the reference), --device, and -linkage greedy|single|dbscan (-M): `single` writes the connected components of the
+// near-neighbour graph (hsearch::Components) in place of the greedy leader clusters, `dbscan` its density clusters
+// (hsearch::Dbscan) at -minpts M (-p; required with dbscan, an error without it); the default is the reference's.
 #include <stdio.h>
 #include <stdlib.h>
 #include <time.h>
@@ -36,7 +37,9 @@ const Opt kOpts[] = {
     {"output", 'o', "output file name", true},
     {"seed", 's', "seed of the LSH planes [random_device]", false},
     {"device", 'G', "GPU ordinal [0]", false},
-    {"linkage", 'M', "greedy (the reference's leader clusters) | single (connected components) [greedy]", false},
+    {"linkage", 'M', "greedy (the reference's leader clusters) | single (connected components) | dbscan (density "
+                     "clusters, needs -minpts) [greedy]", false},
+    {"minpts", 'p', "dbscan: neighbours within the threshold, the k-mer itself counted, that make a k-mer dense", false},
 };
 void Help(const char* prog) {
   fprintf(stderr, "Usage: %s [OPTIONS]\n\nOptions:\n", prog);
@@ -93,9 +96,24 @@ int main(int argc, const char* argv[]) {
   const double hash_R = strtod(val["threshold"].c_str(), nullptr);
   const int device = val.count("device") ? atoi(val["device"].c_str()) : 0;
   const std::string linkage = val.count("linkage") ? val["linkage"] : "greedy";
-  if (linkage != "greedy" && linkage != "single") {
-    fprintf(stderr, "ERROR: -linkage must be greedy or single, not '%s'\n", linkage.c_str());
+  if (linkage != "greedy" && linkage != "single" && linkage != "dbscan") {
+    fprintf(stderr, "ERROR: -linkage must be greedy, single or dbscan, not '%s'\n", linkage.c_str());
     return EXIT_FAILURE;
+  }
+  if ((linkage == "dbscan") != (val.count("minpts") != 0)) {
+    fprintf(stderr, linkage == "dbscan" ? "ERROR: -linkage dbscan needs -minpts\n"
+                                        : "ERROR: -minpts goes with -linkage dbscan only\n");
+    return EXIT_FAILURE;
+  }
+  uint32_t min_pts = 0;
+  if (linkage == "dbscan") {
+    char* end = nullptr;
+    const unsigned long long m = strtoull(val["minpts"].c_str(), &end, 10);
+    if (end == val["minpts"].c_str() || *end || m < 1 || m > 0xffffffffull || val["minpts"][0] == '-') {
+      fprintf(stderr, "ERROR: -minpts must be a whole number of at least 1, not '%s'\n", val["minpts"].c_str());
+      return EXIT_FAILURE;
+    }
+    min_pts = (uint32_t)m;
   }
   uint32_t seed;
   if (val.count("seed")) {
@@ -117,7 +135,10 @@ int main(int argc, const char* argv[]) {
     std::cout << "Clustering... " << std::endl;
     std::string err;
     uint64_t n_clusters = 0;
-    const int st = linkage == "single"
+    const int st = linkage == "dbscan"
+                       ? hsearch::Dbscan(kmers, hash_K, hash_L, hash_W, hash_R, min_pts, val["output"], planes, device,
+                                         &err, &n_clusters, seed)
+                   : linkage == "single"
                        ? hsearch::Components(kmers, hash_K, hash_L, hash_W, hash_R, val["output"], planes, device, &err,
                                              &n_clusters, seed)
                        : hsearch::Clustering(kmers, hash_K, hash_L, hash_W, hash_R, val["output"], planes, device, seed,

@@ -888,6 +888,71 @@ int Components(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uin
   return HS_OK;
 }
 
+int Dbscan(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
+           const double& hash_R, const uint32_t& min_pts, const std::string& output_file, const Planes& planes, int device,
+           std::string* err, uint64_t* n_clusters, uint32_t unknown_seed) {
+  std::vector<uint8_t> codes;
+  const int cs = ClusterCodes(kmers, hash_K, hash_L, hash_W, planes, unknown_seed, &codes, err);
+  if (cs != HS_OK) return cs;
+  const size_t n = kmers.size();
+  hs_params prm;
+  memset(&prm, 0, sizeof(prm));
+  prm.k = planes.dim / 8;
+  prm.K = hash_K;
+  prm.L = hash_L;
+  prm.W = hash_W;
+  prm.device = device;
+  hs_handle* h = nullptr;
+  hs_status st = hs_create(&prm, planes.a.data(), planes.b.data(), nullptr, &h);
+  std::vector<uint32_t> label(n);
+  hs_dbscan_counts counts;
+  memset(&counts, 0, sizeof(counts));
+  const char* what = "hs_create";
+  if (st == HS_OK) {
+    what = "hs_index_build";
+    st = hs_index_build(h, codes.data(), n);
+  }
+  if (st == HS_OK) {
+    what = "hs_dbscan";
+    st = hs_dbscan(h, hash_R, 1, min_pts, label.data(), nullptr, &counts);  // hclust2's test: sqrt(d2) <= R
+  }
+  if (st != HS_OK) {
+    if (err) *err = std::string(what) + ": " + (h ? hs_last_error(h) : "no handle");
+    if (h) hs_destroy(h);
+    return st;
+  }
+  hs_destroy(h);
+  // a cluster per label in ascending id (a label is a core k-mer of its cluster, not always its smallest member:
+  // a border k-mer may have a smaller id), members in ascending id; the noise last
+  std::vector<uint32_t> size(n, 0), start(n + 1, 0), slot(n);
+  uint64_t noise = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (label[i] == HS_NOISE)
+      ++noise;
+    else
+      ++size[label[i]];
+  }
+  for (size_t i = 0; i < n; ++i) start[i + 1] = start[i] + size[i];
+  std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+  for (size_t i = 0; i < n; ++i)
+    if (label[i] != HS_NOISE) slot[fill[label[i]]++] = (uint32_t)i;
+  std::ofstream fout(output_file.c_str());
+  uint32_t cluster_id = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (!size[i]) continue;
+    fout << "#clusterid:" << cluster_id++ << ":size" << size[i] << std::endl;
+    for (uint32_t t = start[i]; t < start[i + 1]; ++t) fout << kmers[slot[t]].name << std::endl;
+  }
+  if (noise) {
+    fout << "#noise:size" << noise << std::endl;
+    for (size_t i = 0; i < n; ++i)
+      if (label[i] == HS_NOISE) fout << kmers[i].name << std::endl;
+  }
+  fout.close();
+  if (n_clusters) *n_clusters = cluster_id;
+  return HS_OK;
+}
+
 int Clustering(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L,
                const double& hash_W, const double& hash_R, const std::string& output_file,
                const Planes& planes, int device, uint32_t unknown_seed, std::string* err,

@@ -208,6 +208,15 @@ int Clustering(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uin
 int Components(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
                const double& hash_R, const std::string& output_file, const Planes& planes, int device,
                std::string* err, uint64_t* n_clusters = nullptr, uint32_t unknown_seed = 0);
+// Density clusters (DBSCAN, hs_dbscan in include/hsearch.h) of the same graph: only k-mers with at least min_pts
+// neighbours within R (themselves counted) join clusters together, so that one stray k-mer between two families no
+// longer fuses them; a sparse k-mer goes to the cluster of its dense neighbour with the smallest index or is noise.
+// The format of Components: clusters in ascending label (a cluster's label is its smallest dense member), members
+// in ascending index; then, only if there is noise, one block "#noise:size<N>" with the noise k-mers' names in
+// ascending index.  *n_clusters does not count that block.
+int Dbscan(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
+           const double& hash_R, const uint32_t& min_pts, const std::string& output_file, const Planes& planes, int device,
+           std::string* err, uint64_t* n_clusters = nullptr, uint32_t unknown_seed = 0);
 
 // evaulate() (:100-165) with weight() (:67-87): weighted recall of a hits file against a ground
 // truth file sorted by (motif, protein); also writes <output_file>.accuracy.txt.  Returns NaN

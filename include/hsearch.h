@@ -525,6 +525,63 @@ HS_API hs_status hs_components_range_dev(hs_handle* h, uint64_t first, uint64_t 
 HS_API hs_status hs_components_merge(const uint32_t* labels, uint64_t m, uint64_t n, uint32_t* out_label,
                                      uint64_t* n_components);
 
+/* ---- density clusters of the near-neighbour graph (DBSCAN at radius R) ------------------------------- */
+
+/* Single linkage chains: one stray k-mer within R of two families fuses them.  DBSCAN lets only k-mers with at
+ * least min_pts neighbours join clusters together; sparse k-mers attach to a cluster or are noise.
+ *
+ * Contract: let G be the graph of hs_self_join(h, R, sqrt_test, ...) on the same handle, as in hs_components -- the
+ * same bucket rule over all L tables, the same exact fp64 test, self pairs dropped; the handle's multi-probe setting
+ * and bucket partition are ignored, as the self-joins ignore them.
+ *   degree[i]  the number of distinct j != i adjacent to i: the density of i at radius R, what one looks at to
+ *              choose min_pts and R.  The degrees sum to the self-join's *n_edges (ORDERED pairs).
+ *   core       i is core iff degree[i] + 1 >= min_pts (the point counts itself, as in Ester et al. 1996).
+ *              min_pts >= 1; 0 is HS_ERR_INVALID.
+ *   cluster    a connected component of the subgraph induced on the core vertices; its label is its smallest core
+ *              id, so label[i] <= i for a core i.
+ *   border     a non-core vertex with at least one core neighbour.  It takes the label of its core neighbour with
+ *              the SMALLEST ID.  Classical DBSCAN leaves this choice to the visiting order; this rule does not
+ *              depend on any order and costs one 32-bit atomic min per pair.  ("The smallest adjacent cluster
+ *              label" would need a third pass over the edges -- a third more time for a choice as arbitrary.)
+ *   noise      every other vertex: label[i] = HS_NOISE.
+ * The result is a pure function of the index, R, sqrt_test and min_pts.  min_pts = 1 gives exactly hs_components'
+ * labels; min_pts = 2 gives them with the singletons turned into noise.
+ *
+ * hs_degrees_range: degree [n], non-zero only for i in [first, first + count) -- the `i` side of
+ * hs_self_join_range; the shares of a partition add up to hs_degrees.  *n_edges (may be NULL) as in hs_components.
+ * hs_dbscan: label [n], degree [n] (may be NULL), *out the counts: n_core + n_border + n_noise = n, and n_edges is
+ * the self-join's.  Errors as in hs_components: an unbuilt index is HS_ERR_STATE; a NaN R, a
+ * range outside the index and min_pts = 0 are HS_ERR_INVALID; the counts are zeroed first.  There is no capacity
+ * protocol: the outputs are always n words.
+ *
+ * Nothing per edge is kept or copied: hs_degrees is one self-join whose batches' pairs are counted where they lie,
+ * hs_dbscan a second one with the same arguments that unites the cores and finds the anchors, in state of the
+ * handle that takes 12 bytes per indexed k-mer (allocated by the first such call, kept with the handle).
+ * hs_self_join*, hs_components*, hs_query* and hs_annotate* run as before, launch for launch. */
+#define HS_NOISE 0xffffffffu
+typedef struct hs_dbscan_counts {
+  uint64_t n_clusters, n_core, n_border, n_noise, n_edges;
+} hs_dbscan_counts;
+HS_API hs_status hs_degrees(hs_handle* h, double R, int sqrt_test, uint32_t* degree, uint64_t* n_edges);
+HS_API hs_status hs_degrees_range(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test,
+                                  uint32_t* degree, uint64_t* n_edges);
+HS_API hs_status hs_dbscan(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, uint32_t* label, uint32_t* degree,
+                           hs_dbscan_counts* out);
+/* ... d_degree / d_label [n] in device memory, the counts on the host (streams: as hs_query_dev) */
+HS_API hs_status hs_degrees_dev(hs_handle* h, double R, int sqrt_test, uint32_t* d_degree, uint64_t* n_edges);
+HS_API hs_status hs_degrees_range_dev(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test,
+                                      uint32_t* d_degree, uint64_t* n_edges);
+HS_API hs_status hs_dbscan_dev(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, uint32_t* d_label,
+                               uint32_t* d_degree, hs_dbscan_counts* out);
+/* The same rule on the host (no GPU, no handle) for ANY list of n_edges pairs (ei[t], ej[t]) over the vertices
+ * 0 .. n-1: a pair may appear in either or both directions, repeated, and in any order; self pairs are ignored.  The
+ * graph is the set of unordered pairs, the degree counts distinct neighbours, and out->n_edges is the sum of the
+ * degrees (twice the distinct unordered pairs).  An id >= n is HS_ERR_INVALID, reported before anything is written;
+ * so are min_pts = 0 and a NULL label (n > 0) or out.  This is the multi-GPU route: gather the ranks'
+ * hs_self_join_range edges, then call it. */
+HS_API hs_status hs_dbscan_edges(const uint32_t* ei, const uint32_t* ej, uint64_t n_edges, uint64_t n,
+                                 uint32_t min_pts, uint32_t* label, uint32_t* degree, hs_dbscan_counts* out);
+
 /* Replaces Clustering() (hclust2.cpp:86-151) with explicit planes a[L][K][d], b[L][K]: table by
  * table, an LSH table over the not-yet-absorbed k-mers, then greedy leader clustering inside every
  * bucket in ascending id order.  The distance work runs on the GPU (hs_self_join per table), the
