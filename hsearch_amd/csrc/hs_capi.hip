@@ -105,6 +105,18 @@ struct Knobs {
 #endif
 };
 
+// What becomes of a batch's hits once the batch has come through whole (run_query, reduce_batch).  LIST: ordered and
+// handed out in the call's output arrays.  Every other sink reduces them where finalize_hits leaves them -- no
+// ordering, no output arrays (cap = 0), no capacity verdict:
+//   ANNOTATE   hs_annotate: the nearest centre per DB id (annot_reduce)
+//   CC_UNION   hs_components: a self-join's pairs united in the handle's union-find forest
+//   DB_DEGREE  hs_degrees / hs_dbscan pass 1 (hs_dbscan.hip): a self-join's pairs counted into the degree array
+//   DB_UNITE   hs_dbscan pass 2: the degrees known, the pairs united and anchored at min_pts
+struct HitSink {
+  enum Kind { LIST, ANNOTATE, CC_UNION, DB_DEGREE, DB_UNITE } kind = LIST;
+  uint32_t min_pts = 1;
+};
+
 // One query call's queries and what it asks (run_query, query_batch, probe_tabs)
 struct QueryCall {
   const double* centers = nullptr;
@@ -119,17 +131,7 @@ struct QueryCall {
   const uint8_t* pre_valid = nullptr;
   // hs_query_radii: every query's own radius ([nq], device); null: R for all.  Searches and brute force only.
   const double* radii = nullptr;
-  // hs_annotate: the batches' hits are not ordered or handed out but reduced to the nearest centre per DB id
-  // (annot_reduce); the call passes no output arrays (cap = 0)
-  bool annotate = false;
-  // hs_components: a self-join whose batches' pairs are not ordered or handed out but united in the handle's
-  // union-find forest (cc_union); the call passes no output arrays (cap = 0)
-  bool components = false;
-  // hs_degrees / hs_dbscan (hs_dbscan.hip): a self-join of the same kind whose batches' pairs are counted into the
-  // handle's degree array (DB_DEGREE, pass 1) or, the degrees known, united and anchored at db_min_pts (DB_UNITE)
-  enum { DB_NONE = 0, DB_DEGREE, DB_UNITE };
-  int dbscan = DB_NONE;
-  uint32_t db_min_pts = 1;
+  HitSink sink;
 };
 
 // What a handle learns from its batches to steer the next ones (plan_batch, the join launch); written by
@@ -2872,6 +2874,102 @@ static hs_status annot_reduce(hs_handle* h, const uint64_t* d_key, const uint64_
   return HS_OK;
 }
 
+// The one place a batch's hits leave for a sink other than LIST: the nh (key, value) pairs finalize_hits left in
+// hit_key / hit_val, on the handle's stream.  The kernels below are launched from here and nowhere else (annot_reduce
+// once more by mp_query, on a chunk's merged list: its probe rows run with the LIST sink).  The rule for every
+// sink: it sees each batch's hits exactly once, and only after the batch succeeded.  run_query keeps it --
+// a batch cut in halves (HS_SPLIT_BATCH) has `continue`d before handing anything on, and its halves bring each hit
+// once -- and hit_key holds each ordered pair once (the first-seen rule across the tables has run; the tests pin
+// n_edges == len(self_join)).  DB_DEGREE depends on it: it is NOT idempotent, a pair counted twice is a wrong
+// degree.  The other three would forgive a repeat (union, min and the nearest-centre steps are idempotent).
+static hs_status reduce_batch(hs_handle* h, const QueryCall& c, uint32_t nh) {
+  const uint64_t* const pairs = h->hit_key.as<uint64_t>();
+  const uint32_t n = (uint32_t)h->n;
+  switch (c.sink.kind) {
+    case HitSink::LIST:
+      break;
+    case HitSink::ANNOTATE:
+      return annot_reduce(h, pairs, h->hit_val.as<uint64_t>(), nullptr, nullptr, nullptr, nullptr, nh);
+    case HitSink::CC_UNION:
+      HS_HIP(h, hs_launch_cc_union(pairs, nh, c.self_first, h->cc_parent.as<uint32_t>(), n, h->cc_cnt.as<uint64_t>(),
+                                   h->stream));
+      break;
+    case HitSink::DB_DEGREE:
+      HS_HIP(h, hs_launch_db_degree(pairs, nh, c.self_first, h->db_deg.as<uint32_t>(), n, h->db_cnt.as<uint64_t>(),
+                                    h->stream));
+      break;
+    case HitSink::DB_UNITE:  // the degrees are final (pass 1 ended at a kernel boundary)
+      HS_HIP(h, hs_launch_db_unite(pairs, nh, c.self_first, h->db_deg.as<uint32_t>(), c.sink.min_pts,
+                                   h->cc_parent.as<uint32_t>(), h->db_anchor.as<uint32_t>(), n, h->stream));
+      break;
+  }
+  return HS_OK;
+}
+
+// Centres that are k-mers (every 8 doubles a row of the coordinate table, bit for bit -- what the
+// reference's centres files hold) run from their residue codes, as hs_query_codes's do: the same
+// results from k bytes per query where the point rows are 64 k.  One small kernel and one wait per call.
+static hs_status recognise_kmers(hs_handle* h, QueryCall& c, uint64_t nq) {
+  if (!c.centers || c.codes || !nq || !h->n || c.brute || h->knobs.no_recognise || h->p.k > 75) return HS_OK;
+  const size_t cb = ((size_t)nq * h->p.k + 15) & ~(size_t)15;
+  HS_HIP(h, h->rec_codes.reserve(cb + 16));
+  uint32_t* const d_bad = reinterpret_cast<uint32_t*>(h->rec_codes.as<uint8_t>() + cb);
+  HS_HIP(h, hipMemsetAsync(d_bad, 0, 4, h->stream));
+  HS_HIP(h, hs_launch_recognise_kmers(c.centers, nq, h->p.k, h->coords.as<double>(), h->alphabet,
+                                      h->rec_codes.as<uint8_t>(), d_bad, h->stream));
+  uint32_t bad = 1;
+  HS_HIP(h, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  if (!bad) {
+    c.codes = h->rec_codes.as<uint8_t>();
+    c.centers = nullptr;
+    h->prof.queries_recognised = nq;
+  }
+  return HS_OK;
+}
+
+// Queries per batch of a call of nq queries
+static uint32_t choose_query_batch(const hs_handle* h, const QueryCall& c, uint64_t nq) {
+  // bounds the workspace, which grows with nq * L (2^17 at L >= 8; with few
+  // tables -- the one-table indexes of Clustering() -- larger batches, fewer fixed costs)
+  uint32_t QB = std::max(1u << 17, std::min(1u << 20, (1u << 20) / h->p.L));
+  if (nq > QB && !c.brute && !h->knobs.query_batch) {
+    // More queries than one such batch: as many per batch as a third of the free HBM carries, up to 2^20.
+    // The pairs of a batch are (bucket members) x (queries probing the bucket), so the join's operand reuse
+    // grows with the batch: at 10^8 k-mers x 32 tables a segment sees ~19 of 125 k queries, ~150 of 10^6.
+    // Workspace per query: L x (K + 5 + 18 + 4) words of probe / segment arrays, L x 416 B of gathered
+    // query rows + 32 B per work item (~ 1 per probe at worst), its own rows, 16 x 48 B of survivor lists.
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+      const size_t per_q = (size_t)h->p.L * (4 * ((size_t)h->p.K + 27) + 416 + 64) + 416 + 3 * (size_t)h->d + 768;
+      const size_t fit = free_b / 3 / per_q;
+      QB = (uint32_t)std::max<size_t>(QB, std::min<size_t>((size_t)1 << 20, fit));
+    }
+  }
+  // hs_set_option(HS_OPT_QUERY_BATCH) / HS_QUERY_BATCH (multi-probe: in queries, each 1 + T probe rows here)
+  if (h->knobs.query_batch) QB = (uint32_t)std::min<uint64_t>((uint64_t)h->knobs.query_batch * (c.pre_ints ? h->mp_T + 1 : 1), 1u << 30);
+  return std::min(QB, max_query_batch(h));
+}
+
+// (brute force, a query with very many hits, HS_SORT_HITS) A batch that did not order its nh hits itself: the order
+// of the reference's output by a radix sort on (query, table of first sight, id) -- q_bits bits of query number --
+// and, where they fit, the hits into out's arrays
+static hs_status sort_batch_hits(hs_handle* h, uint32_t nh, int q_bits, const BatchOut& out) {
+  HS_HIP(h, h->hit_key2.reserve((size_t)nh * 8));
+  HS_HIP(h, h->hit_val2.reserve((size_t)nh * 8));
+  HS_HIP(h, h->temp.reserve(hs_sort_pairs_u64_u64_temp(nh) + 256));
+  HS_HIP(h, hipEventRecord(h->ev[6], h->stream));
+  HS_HIP(h, hs_sort_pairs_u64_u64(h->temp.p, h->temp.cap, h->hit_key.as<uint64_t>(), h->hit_key2.as<uint64_t>(),
+                                  h->hit_val.as<uint64_t>(), h->hit_val2.as<uint64_t>(), nh, 37 + q_bits, h->stream));
+  if (nh <= out.room)
+    HS_HIP(h, hs_launch_unpack_hits(h->hit_key2.as<uint64_t>(), h->hit_val2.as<uint64_t>(), nh, out.q, out.id,
+                                    out.table, out.dist, h->stream));
+  HS_HIP(h, hipEventRecord(h->ev[7], h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  h->prof.ms_finalize += ev_ms(h, 6, 7);
+  return HS_OK;
+}
+
 static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_hit_q, uint32_t* d_hit_id,
                            uint32_t* d_hit_table, double* d_hit_dist, uint64_t cap, uint64_t* n_hits, uint64_t* d_cand) {
   if (!h || !n_hits) return HS_ERR_INVALID;
@@ -2880,7 +2978,7 @@ static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_h
   if (nq >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nq must be < 2^27 per call");
   // (a self-join that runs from the residue codes passes no centres)
   if (nq && !c.centers && !c.codes && !(c.self_first != HS_NO_SELF && self_codes_ok(h, c.R))) return HS_ERR_INVALID;
-  if (cap && (!d_hit_q || !d_hit_id || !d_hit_dist)) return HS_ERR_INVALID;
+  if (cap && (c.sink.kind != HitSink::LIST || !d_hit_q || !d_hit_id || !d_hit_dist)) return HS_ERR_INVALID;
   if (!(c.R == c.R)) return fail(h, HS_ERR_INVALID, "R is NaN");
   hs_status st = ensure_device(h);
   if (st) return st;
@@ -2889,46 +2987,10 @@ static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_h
   memset(&h->prof, 0, sizeof(h->prof));
   HS_HIP(h, h->counters.reserve(256));
   HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
-  // Centres that are k-mers (every 8 doubles a row of the coordinate table, bit for bit -- what the
-  // reference's centres files hold) run from their residue codes, as hs_query_codes's do: the same
-  // results from k bytes per query where the point rows are 64 k.  One small kernel and one wait per call.
-  if (c.centers && !c.codes && nq && h->n && !c.brute && !h->knobs.no_recognise && h->p.k <= 75) {
-    const size_t cb = ((size_t)nq * h->p.k + 15) & ~(size_t)15;
-    HS_HIP(h, h->rec_codes.reserve(cb + 16));
-    uint32_t* const d_bad = reinterpret_cast<uint32_t*>(h->rec_codes.as<uint8_t>() + cb);
-    HS_HIP(h, hipMemsetAsync(d_bad, 0, 4, h->stream));
-    HS_HIP(h, hs_launch_recognise_kmers(c.centers, nq, h->p.k, h->coords.as<double>(), h->alphabet,
-                                        h->rec_codes.as<uint8_t>(), d_bad, h->stream));
-    uint32_t bad = 1;
-    HS_HIP(h, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipStreamSynchronize(h->stream));
-    if (!bad) {
-      c.codes = h->rec_codes.as<uint8_t>();
-      c.centers = nullptr;
-      h->prof.queries_recognised = nq;
-    }
-  }
+  HS_CHECK(recognise_kmers(h, c, nq));
   uint64_t total = 0;
   if (nq && h->n && !(c.brute && c.R < 0 && !c.radii)) {
-    // queries per batch: bounds the workspace, which grows with nq * L (2^17 at L >= 8; with few
-    // tables -- the one-table indexes of Clustering() -- larger batches, fewer fixed costs)
-    uint32_t QB = std::max(1u << 17, std::min(1u << 20, (1u << 20) / h->p.L));
-    if (nq > QB && !c.brute && !h->knobs.query_batch) {
-      // More queries than one such batch: as many per batch as a third of the free HBM carries, up to 2^20.
-      // The pairs of a batch are (bucket members) x (queries probing the bucket), so the join's operand reuse
-      // grows with the batch: at 10^8 k-mers x 32 tables a segment sees ~19 of 125 k queries, ~150 of 10^6.
-      // Workspace per query: L x (K + 5 + 18 + 4) words of probe / segment arrays, L x 416 B of gathered
-      // query rows + 32 B per work item (~ 1 per probe at worst), its own rows, 16 x 48 B of survivor lists.
-      size_t free_b = 0, total_b = 0;
-      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const size_t per_q = (size_t)h->p.L * (4 * ((size_t)h->p.K + 27) + 416 + 64) + 416 + 3 * (size_t)h->d + 768;
-        const size_t fit = free_b / 3 / per_q;
-        QB = (uint32_t)std::max<size_t>(QB, std::min<size_t>((size_t)1 << 20, fit));
-      }
-    }
-    // hs_set_option(HS_OPT_QUERY_BATCH) / HS_QUERY_BATCH (multi-probe: in queries, each 1 + T probe rows here)
-    if (h->knobs.query_batch) QB = (uint32_t)std::min<uint64_t>((uint64_t)h->knobs.query_batch * (c.pre_ints ? h->mp_T + 1 : 1), 1u << 30);
-    QB = std::min(QB, max_query_batch(h));
+    uint32_t QB = choose_query_batch(h, c, nq);
     uint32_t nqb = 0;
     for (uint64_t q0 = 0; q0 < nq; q0 += nqb) {
       nqb = (uint32_t)std::min<uint64_t>(QB, nq - q0);
@@ -2951,61 +3013,13 @@ static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_h
         continue;
       }
       if (st) return st;
-      if (c.components) {
-        // as below: only a batch that came through whole hands its pairs on, and a pair united twice changes nothing
-        HS_HIP(h, hs_launch_cc_union(h->hit_key.as<uint64_t>(), nh, c.self_first, h->cc_parent.as<uint32_t>(),
-                                     (uint32_t)h->n, h->cc_cnt.as<uint64_t>(), h->stream));
+      // the batch came through whole (a split one has `continue`d above): its hits go on, once (reduce_batch)
+      if (c.sink.kind != HitSink::LIST) {
+        HS_CHECK(reduce_batch(h, c, nh));
         total += nh;
         continue;
       }
-      if (c.dbscan == QueryCall::DB_DEGREE) {
-        // NOT idempotent, unlike the reductions above and below: a pair counted twice is a wrong degree.  This
-        // holds because (1) only a batch that came through whole hands its pairs on -- one cut in halves
-        // (HS_SPLIT_BATCH) has `continue`d above before handing anything on, and its halves bring each pair once --
-        // and (2) hit_key holds each ordered pair once (the first-seen rule across the tables has run; the tests pin
-        // n_edges == len(self_join)).  The kernel is launched from this place and no other.
-        HS_HIP(h, hs_launch_db_degree(h->hit_key.as<uint64_t>(), nh, c.self_first, h->db_deg.as<uint32_t>(),
-                                      (uint32_t)h->n, h->db_cnt.as<uint64_t>(), h->stream));
-        total += nh;
-        continue;
-      }
-      if (c.dbscan == QueryCall::DB_UNITE) {
-        // the degrees are final (pass 1 ended at a kernel boundary); union and min are idempotent
-        HS_HIP(h, hs_launch_db_unite(h->hit_key.as<uint64_t>(), nh, c.self_first, h->db_deg.as<uint32_t>(),
-                                     c.db_min_pts, h->cc_parent.as<uint32_t>(), h->db_anchor.as<uint32_t>(),
-                                     (uint32_t)h->n, h->stream));
-        total += nh;
-        continue;
-      }
-      if (c.annotate) {
-        // Only a batch that came through whole is reduced: one cut in halves (HS_SPLIT_BATCH) has handed nothing on
-        // yet, and its halves bring each hit once.  (Reducing a hit twice would be harmless all the same: both
-        // steps of the reduction are idempotent.)
-        HS_CHECK(annot_reduce(h, h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(), nullptr, nullptr, nullptr,
-                              nullptr, nh));
-        total += nh;
-        continue;
-      }
-      if (nh && !bout.ordered) {
-        // (brute force, a query with very many hits, HS_SORT_HITS) order of the reference's output
-        // by a radix sort on (query, table of first sight, id)
-        HS_HIP(h, h->hit_key2.reserve((size_t)nh * 8));
-        HS_HIP(h, h->hit_val2.reserve((size_t)nh * 8));
-        HS_HIP(h, h->temp.reserve(hs_sort_pairs_u64_u64_temp(nh) + 256));
-        HS_HIP(h, hipEventRecord(h->ev[6], h->stream));
-        HS_HIP(h, hs_sort_pairs_u64_u64(h->temp.p, h->temp.cap, h->hit_key.as<uint64_t>(),
-                                        h->hit_key2.as<uint64_t>(), h->hit_val.as<uint64_t>(),
-                                        h->hit_val2.as<uint64_t>(), nh,
-                                        37 + bit_width_u32((uint32_t)(q0 + nqb)), h->stream));
-        if (total + nh <= cap)
-          HS_HIP(h, hs_launch_unpack_hits(h->hit_key2.as<uint64_t>(), h->hit_val2.as<uint64_t>(), nh,
-                                          d_hit_q + total, d_hit_id + total,
-                                          d_hit_table ? d_hit_table + total : nullptr,
-                                          d_hit_dist + total, h->stream));
-        HS_HIP(h, hipEventRecord(h->ev[7], h->stream));
-        HS_HIP(h, hipStreamSynchronize(h->stream));
-        h->prof.ms_finalize += ev_ms(h, 6, 7);
-      }
+      if (nh && !bout.ordered) HS_CHECK(sort_batch_hits(h, nh, bit_width_u32((uint32_t)(q0 + nqb)), bout));
       total += nh;
     }
   } else if (d_cand && nq && !c.brute) {
@@ -3016,11 +3030,12 @@ static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_h
   h->prof.ms_total = ev_ms(h, 8, 9);
   h->prof.hits = total;
   *n_hits = total;
-  if (total > cap && !c.annotate && !c.components && !c.dbscan) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
+  if (total > cap && c.sink.kind == HitSink::LIST) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
   return HS_OK;
 }
 
-// The profile of a multi-probe call: the sum of its chunks' (the shape fields of the last one)
+// The profile of a call made of several run_query calls (multi-probe, the self-joins): the sum of its chunks' (the
+// shape fields of the last one)
 static void add_profile(hs_profile& a, const hs_profile& b) {
   a.ms_hash += b.ms_hash;
   a.ms_sort += b.ms_sort;
@@ -3073,8 +3088,7 @@ static hs_status mp_query(hs_handle* h, const QueryCall& c, uint64_t nq, uint32_
                           uint32_t* d_hit_table, double* d_hit_dist, uint64_t cap, uint64_t* n_hits, uint64_t* d_cand) {
   const uint32_t P = h->mp_T + 1, L = h->p.L;
   const int k = (int)h->p.k, d = h->d;
-  hs_profile acc;
-  memset(&acc, 0, sizeof(acc));
+  hs_profile acc = {};
   uint64_t total = 0;
   const uint64_t NC = std::max<uint64_t>(1, (1u << 19) / P);  // queries per chunk: 2^19 probe rows
   uint64_t nc = 0;
@@ -3097,7 +3111,7 @@ static hs_status mp_query(hs_handle* h, const QueryCall& c, uint64_t nq, uint32_
     HS_CHECK(mp_probes(h, pts, nc, (uint64_t)P * L, 1, L));
     HS_HIP(h, hipEventRecord(h->ev[1], h->stream));
     QueryCall vc = c;
-    vc.annotate = false;  // (the probe rows' hits come back as a list: a row's table is final only once merged)
+    vc.sink = HitSink();  // (the probe rows' hits come back as a list: a row's table is final only once merged)
     if (c.codes) {
       HS_HIP(h, h->mp_rows.reserve((size_t)nv * k));
       HS_HIP(h, hs_launch_mp_repeat_u8(c.codes + q0 * k, nv, (uint32_t)k, P, h->mp_rows.as<uint8_t>(), h->stream));
@@ -3141,7 +3155,7 @@ static hs_status mp_query(hs_handle* h, const QueryCall& c, uint64_t nq, uint32_
     uint64_t kept = 0;
     HS_CHECK(hs_merge_first_table_dev(h, h->mp_q.as<uint32_t>(), h->mp_id.as<uint32_t>(), h->mp_table.as<uint32_t>(),
                                       h->mp_dist.as<double>(), nh, &kept));
-    if (c.annotate) {  // the chunk's merged list -- bounded by the chunk -- is reduced where it lies
+    if (c.sink.kind == HitSink::ANNOTATE) {  // the chunk's merged list -- bounded by the chunk -- is reduced where it lies
       HS_CHECK(annot_reduce(h, nullptr, nullptr, h->mp_q.as<uint32_t>(), h->mp_id.as<uint32_t>(),
                             h->mp_table.as<uint32_t>(), h->mp_dist.as<double>(), kept));
     } else if (kept && total + kept <= cap) {
@@ -3158,7 +3172,7 @@ static hs_status mp_query(hs_handle* h, const QueryCall& c, uint64_t nq, uint32_
   acc.hits = total;
   h->prof = acc;
   *n_hits = total;
-  if (total > cap && !c.annotate) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
+  if (total > cap && c.sink.kind == HitSink::LIST) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
   return HS_OK;
 }
 
@@ -3218,6 +3232,25 @@ static bool radii_max_host(const double* radii, uint64_t nq, double* out) {
   return true;
 }
 
+// Host queries onto the device, on the handle's stream: centres (8d bytes per query over PCIe) or codes (k bytes)
+// into io_centers / io_codes and, where given, the radii into io_radii; the call's pointers set to them
+static hs_status stage_queries(hs_handle* h, const double* centers, const uint8_t* qcodes, const double* radii,
+                               uint64_t nq, QueryCall* call) {
+  const size_t cbytes = qcodes ? 0 : (size_t)nq * h->d * 8, kbytes = qcodes ? (size_t)nq * h->p.k : 0;
+  HS_HIP(h, h->io_centers.reserve(std::max<size_t>(16, cbytes)));
+  HS_HIP(h, h->io_codes.reserve(std::max<size_t>(16, kbytes)));
+  if (cbytes) HS_HIP(h, hipMemcpyAsync(h->io_centers.p, centers, cbytes, hipMemcpyHostToDevice, h->stream));
+  if (kbytes) HS_HIP(h, hipMemcpyAsync(h->io_codes.p, qcodes, kbytes, hipMemcpyHostToDevice, h->stream));
+  call->centers = qcodes ? nullptr : h->io_centers.as<double>();
+  call->codes = qcodes ? h->io_codes.as<uint8_t>() : nullptr;
+  if (radii) {
+    HS_HIP(h, h->io_radii.reserve(std::max<size_t>(16, (size_t)nq * 8)));
+    if (nq) HS_HIP(h, hipMemcpyAsync(h->io_radii.p, radii, (size_t)nq * 8, hipMemcpyHostToDevice, h->stream));
+    call->radii = h->io_radii.as<double>();
+  }
+  return HS_OK;
+}
+
 // radii != null: every query at its own radius (hs_query_radii, hs_bruteforce_radii), R unused
 static hs_status host_query(hs_handle* h, const double* centers, const uint8_t* qcodes, uint64_t nq, double R,
                             bool brute, uint32_t* hit_q, uint32_t* hit_id, uint32_t* hit_table, double* hit_dist,
@@ -3230,27 +3263,15 @@ static hs_status host_query(hs_handle* h, const double* centers, const uint8_t* 
   }
   hs_status st = ensure_device(h);
   if (st) return st;
-  // centres: 8d bytes per query over PCIe; codes: k bytes
-  const size_t cbytes = qcodes ? 0 : (size_t)nq * h->d * 8, kbytes = qcodes ? (size_t)nq * h->p.k : 0;
-  HS_HIP(h, h->io_centers.reserve(std::max<size_t>(16, cbytes)));
-  HS_HIP(h, h->io_codes.reserve(std::max<size_t>(16, kbytes)));
   HS_HIP(h, h->io_q.reserve(std::max<size_t>(16, cap * 4)));
   HS_HIP(h, h->io_id.reserve(std::max<size_t>(16, cap * 4)));
   HS_HIP(h, h->io_table.reserve(std::max<size_t>(16, cap * 4)));
   HS_HIP(h, h->io_dist.reserve(std::max<size_t>(16, cap * 8)));
   if (cand) HS_HIP(h, h->io_cand.reserve(std::max<size_t>(16, (size_t)nq * h->p.L * 8)));
-  if (cbytes) HS_HIP(h, hipMemcpyAsync(h->io_centers.p, centers, cbytes, hipMemcpyHostToDevice, h->stream));
-  if (kbytes) HS_HIP(h, hipMemcpyAsync(h->io_codes.p, qcodes, kbytes, hipMemcpyHostToDevice, h->stream));
-  QueryCall call{qcodes ? nullptr : h->io_centers.as<double>(), qcodes ? h->io_codes.as<uint8_t>() : nullptr, R, brute};
-  if (radii) {
-    HS_HIP(h, h->io_radii.reserve(std::max<size_t>(16, (size_t)nq * 8)));
-    if (nq) HS_HIP(h, hipMemcpyAsync(h->io_radii.p, radii, (size_t)nq * 8, hipMemcpyHostToDevice, h->stream));
-    call.radii = h->io_radii.as<double>();
-  }
-  st = run_query(h, call,
-                 nq, h->io_q.as<uint32_t>(),
-                 h->io_id.as<uint32_t>(), h->io_table.as<uint32_t>(), h->io_dist.as<double>(), cap,
-                 n_hits, cand ? h->io_cand.as<uint64_t>() : nullptr);
+  QueryCall call{nullptr, nullptr, R, brute};
+  HS_CHECK(stage_queries(h, centers, qcodes, radii, nq, &call));
+  st = run_query(h, call, nq, h->io_q.as<uint32_t>(), h->io_id.as<uint32_t>(), h->io_table.as<uint32_t>(),
+                 h->io_dist.as<double>(), cap, n_hits, cand ? h->io_cand.as<uint64_t>() : nullptr);
   if (st != HS_OK) return st;
   const uint64_t nh = *n_hits;
   if (nh) {
@@ -3302,8 +3323,20 @@ hs_status hs_bruteforce_radii(hs_handle* h, const double* centers, uint64_t nq, 
                     radii ? radii : &none);
 }
 
-// The radii stay where they are; what the plan needs of them -- the largest |radius|, and whether one is a NaN --
-// comes from one small reduction and one read-back per call, before anything is written.
+// Radii on the device stay where they are; what the plan needs of them -- the largest |radius|, and whether one is
+// a NaN (HS_ERR_INVALID) -- comes from one small reduction and one read-back per call, before anything is written.
+static hs_status radii_max_dev(hs_handle* h, const double* d_radii, uint64_t nq, double* out) {
+  unsigned long long red[2] = {0ull, 0ull};
+  HS_HIP(h, h->io_radii.reserve(16));
+  HS_HIP(h, hipMemsetAsync(h->io_radii.p, 0, 16, h->stream));
+  HS_HIP(h, hs_launch_radii_max(d_radii, nq, h->io_radii.as<unsigned long long>(), h->stream));
+  HS_HIP(h, hipMemcpyAsync(red, h->io_radii.p, 16, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  if (red[1]) return fail(h, HS_ERR_INVALID, "a radius is NaN");
+  memcpy(out, &red[0], 8);
+  return HS_OK;
+}
+
 hs_status hs_query_radii_dev(hs_handle* h, const double* d_centers, const uint8_t* d_qcodes, uint64_t nq,
                              const double* d_radii, uint32_t* d_hit_q, uint32_t* d_hit_id, uint32_t* d_hit_table,
                              double* d_hit_dist, uint64_t cap, uint64_t* n_hits, uint64_t* d_cand) {
@@ -3315,17 +3348,9 @@ hs_status hs_query_radii_dev(hs_handle* h, const double* d_centers, const uint8_
   if (nq >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nq must be < 2^27 per call");
   hs_status st = ensure_device(h);
   if (st) return st;
-  unsigned long long red[2] = {0ull, 0ull};
-  HS_HIP(h, h->io_radii.reserve(16));
-  if (nq) {
-    HS_HIP(h, hipMemsetAsync(h->io_radii.p, 0, 16, h->stream));
-    HS_HIP(h, hs_launch_radii_max(d_radii, nq, h->io_radii.as<unsigned long long>(), h->stream));
-    HS_HIP(h, hipMemcpyAsync(red, h->io_radii.p, 16, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipStreamSynchronize(h->stream));
-  }
-  if (red[1]) return fail(h, HS_ERR_INVALID, "a radius is NaN");
   QueryCall call{d_centers, d_qcodes, 0.0};
-  memcpy(&call.R, &red[0], 8);
+  HS_HIP(h, h->io_radii.reserve(16));
+  if (nq) HS_CHECK(radii_max_dev(h, d_radii, nq, &call.R));
   call.radii = nq ? d_radii : h->io_radii.as<double>();  // (nq = 0: no kernel reads the array)
   return run_query(h, call, nq, d_hit_q, d_hit_id, d_hit_table, d_hit_dist, cap, n_hits, d_cand);
 }
@@ -3351,17 +3376,14 @@ static hs_status annot_begin(hs_handle* h) {
 }
 
 // The search with the reduction in place of the hit list; on success *cnt ids were touched and ann_sorted holds
-// them ascending.  d_radii: the call's radii on the device (R then the largest |radius|), or null.
-static hs_status annot_search(hs_handle* h, const double* d_centers, const uint8_t* d_qcodes, uint64_t nq, double R,
-                              const double* d_radii, uint32_t* cnt) {
+// them ascending.  call: the queries on the device, with radii its R their largest |radius|.
+static hs_status annot_search(hs_handle* h, QueryCall call, uint64_t nq, uint32_t* cnt) {
   *cnt = 0;
   if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
   if (nq >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nq must be < 2^27 per call");
-  if (!(R == R)) return fail(h, HS_ERR_INVALID, "R is NaN");
+  if (!(call.R == call.R)) return fail(h, HS_ERR_INVALID, "R is NaN");
   HS_CHECK(annot_begin(h));
-  QueryCall call{d_centers, d_qcodes, R};
-  call.radii = d_radii;
-  call.annotate = true;
+  call.sink.kind = HitSink::ANNOTATE;
   uint64_t n_hits = 0;
   HS_CHECK(run_query(h, call, nq, nullptr, nullptr, nullptr, nullptr, 0, &n_hits, nullptr));
   HS_HIP(h, hipMemcpyAsync(cnt, h->ann_cnt.p, 4, hipMemcpyDeviceToHost, h->stream));
@@ -3396,20 +3418,11 @@ hs_status hs_annotate_dev(hs_handle* h, const double* d_centers, const uint8_t* 
   if (cap && (!d_out_id || !d_out_q || !d_out_table || !d_out_dist)) return HS_ERR_INVALID;
   hs_status st = ensure_device(h);
   if (st) return st;
-  if (d_radii && nq && nq < (1ull << 27)) {  // the largest |radius| and the NaN test, as hs_query_radii_dev makes them
-    unsigned long long red[2] = {0ull, 0ull};
-    HS_HIP(h, h->io_radii.reserve(16));
-    HS_HIP(h, hipMemsetAsync(h->io_radii.p, 0, 16, h->stream));
-    HS_HIP(h, hs_launch_radii_max(d_radii, nq, h->io_radii.as<unsigned long long>(), h->stream));
-    HS_HIP(h, hipMemcpyAsync(red, h->io_radii.p, 16, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipStreamSynchronize(h->stream));
-    if (red[1]) return fail(h, HS_ERR_INVALID, "a radius is NaN");
-    memcpy(&R, &red[0], 8);
-  } else if (d_radii) {
-    R = 0.0;
-  }
+  QueryCall call{d_centers, d_qcodes, d_radii ? 0.0 : R};
+  if (d_radii && nq && nq < (1ull << 27)) HS_CHECK(radii_max_dev(h, d_radii, nq, &call.R));
+  call.radii = nq ? d_radii : nullptr;
   uint32_t cnt = 0;
-  HS_CHECK(annot_search(h, d_centers, d_qcodes, nq, R, nq ? d_radii : nullptr, &cnt));
+  HS_CHECK(annot_search(h, call, nq, &cnt));
   *n_out = cnt;
   const bool fits = cnt <= cap;
   HS_CHECK(annot_finish(h, cnt, fits ? d_out_id : nullptr, d_out_q, d_out_table, d_out_dist));
@@ -3428,20 +3441,10 @@ hs_status hs_annotate(hs_handle* h, const double* centers, const uint8_t* qcodes
   if (radii && !radii_max_host(radii, nq, &R)) return fail(h, HS_ERR_INVALID, "a radius is NaN");
   hs_status st = ensure_device(h);
   if (st) return st;
-  const size_t cbytes = qcodes ? 0 : (size_t)nq * h->d * 8, kbytes = qcodes ? (size_t)nq * h->p.k : 0;
-  HS_HIP(h, h->io_centers.reserve(std::max<size_t>(16, cbytes)));
-  HS_HIP(h, h->io_codes.reserve(std::max<size_t>(16, kbytes)));
-  if (cbytes) HS_HIP(h, hipMemcpyAsync(h->io_centers.p, centers, cbytes, hipMemcpyHostToDevice, h->stream));
-  if (kbytes) HS_HIP(h, hipMemcpyAsync(h->io_codes.p, qcodes, kbytes, hipMemcpyHostToDevice, h->stream));
-  const double* d_radii = nullptr;
-  if (radii && nq) {
-    HS_HIP(h, h->io_radii.reserve(std::max<size_t>(16, (size_t)nq * 8)));
-    HS_HIP(h, hipMemcpyAsync(h->io_radii.p, radii, (size_t)nq * 8, hipMemcpyHostToDevice, h->stream));
-    d_radii = h->io_radii.as<double>();
-  }
+  QueryCall call{nullptr, nullptr, R};
+  HS_CHECK(stage_queries(h, centers, qcodes, nq ? radii : nullptr, nq, &call));
   uint32_t cnt = 0;
-  HS_CHECK(annot_search(h, qcodes ? nullptr : h->io_centers.as<double>(), qcodes ? h->io_codes.as<uint8_t>() : nullptr,
-                        nq, R, d_radii, &cnt));
+  HS_CHECK(annot_search(h, call, nq, &cnt));
   *n_out = cnt;
   if (cnt > cap) {
     HS_CHECK(annot_finish(h, cnt, nullptr, nullptr, nullptr, nullptr));
@@ -3507,6 +3510,43 @@ hs_status hs_bruteforce(hs_handle* h, const double* centers, uint64_t nq, double
   return host_query(h, centers, nullptr, nq, R, true, hit_q, hit_id, nullptr, hit_dist, cap, n_hits, nullptr);
 }
 
+// What every self-join entry point asks first: the index built, its own arguments in order (args_ok), the device
+// ready, [first, first + count) inside the indexed k-mers
+static hs_status self_join_check(hs_handle* h, uint64_t first, uint64_t count, bool args_ok) {
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
+  if (!args_ok) return HS_ERR_INVALID;
+  HS_CHECK(ensure_device(h));
+  if (first > h->n || count > h->n - first) return fail(h, HS_ERR_INVALID, "range outside the indexed k-mers");
+  return HS_OK;
+}
+
+// The self-join of the k-mers [first, first + count) against the index, in chunks of whole run_query batches.  Every
+// chunk's QueryCall -- its hits for `sink` -- goes to per_chunk(call, q0, nq), which runs it (run_query) and takes
+// what it hands out; the chunks' profiles are added to *acc.
+extern "C++" template <class PerChunk>
+static hs_status self_join_chunks(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test, HitSink sink,
+                                  hs_profile* acc, PerChunk per_chunk) {
+  const uint64_t end = first + count;
+  const uint32_t CH = 1u << 20;  // queries embedded per chunk (8k doubles each)
+  for (uint64_t q0 = first; q0 < end; q0 += CH) {
+    const uint64_t nq = std::min<uint64_t>(CH, end - q0);
+    // from the residue codes when every filter on the way can (query_batch's self_codes); embedded
+    // centres as for any other query otherwise
+    const bool from_codes = self_codes_ok(h, R);
+    if (!from_codes) {
+      HS_HIP(h, h->io_centers.reserve((size_t)nq * h->d * 8));
+      HS_HIP(h, hs_launch_embed(h->codes.as<uint8_t>() + q0 * h->p.k, nq, (int)h->p.k, h->coords.as<double>(),
+                                h->io_centers.as<double>(), h->stream));
+    }
+    // (the pair of a k-mer with itself is dropped on the device)
+    QueryCall call{from_codes ? nullptr : h->io_centers.as<double>(), nullptr, R, false, (uint32_t)q0, sqrt_test != 0};
+    call.sink = sink;
+    HS_CHECK(per_chunk(call, q0, nq));
+    add_profile(*acc, h->prof);
+  }
+  return HS_OK;
+}
+
 hs_status hs_self_join(hs_handle* h, double R, int sqrt_test, uint32_t* edge_i, uint32_t* edge_j,
                        uint32_t* edge_table, double* edge_dist, uint64_t cap, uint64_t* n_edges) {
   if (!h) return HS_ERR_INVALID;
@@ -3519,20 +3559,13 @@ hs_status hs_self_join_range(hs_handle* h, uint64_t first, uint64_t count, doubl
                              double* edge_dist, uint64_t cap, uint64_t* n_edges) {
   if (!h || !n_edges) return HS_ERR_INVALID;
   *n_edges = 0;
-  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
-  if (cap && (!edge_i || !edge_j || !edge_dist)) return HS_ERR_INVALID;
-  hs_status st = ensure_device(h);
-  if (st) return st;
-  if (first > h->n || count > h->n - first) return fail(h, HS_ERR_INVALID, "range outside the indexed k-mers");
-  const uint64_t n = first + count;
-  const uint32_t CH = 1u << 20;  // queries embedded per chunk (8k doubles each): whole batches of run_query
+  HS_CHECK(self_join_check(h, first, count, !cap || (edge_i && edge_j && edge_dist)));
   uint64_t total = 0;
-  hs_profile acc;
-  memset(&acc, 0, sizeof(acc));
+  hs_profile acc = {};
   // the handle's I/O buffers (host-pointer queries use them the same way) and a pinned staging
   // area: Clustering() calls this once per table, reallocating 1.6 GB of centres and faulting in
   // fresh host vectors every time cost more than the join itself
-  DevBuf &centers = h->io_centers, &dq = h->io_q, &did = h->io_id, &dt = h->io_table, &dd = h->io_dist;
+  DevBuf &dq = h->io_q, &did = h->io_id, &dt = h->io_table, &dd = h->io_dist;
   const bool sj_timing = h->knobs.cluster_timing;
   auto sj_t0 = std::chrono::steady_clock::now();
   auto sj_lap = [&](const char* what) {
@@ -3541,43 +3574,22 @@ hs_status hs_self_join_range(hs_handle* h, uint64_t first, uint64_t count, doubl
     fprintf(stderr, "    sj %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - sj_t0).count());
     sj_t0 = now;
   };
-  for (uint64_t q0 = first; q0 < n; q0 += CH) {
-    const uint64_t nq = std::min<uint64_t>(CH, n - q0);
-    // from the residue codes when every filter on the way can (query_batch's self_codes); embedded
-    // centres as for any other query otherwise
-    const bool from_codes = self_codes_ok(h, R);
-    if (!from_codes) {
-      HS_HIP(h, centers.reserve((size_t)nq * h->d * 8));
-      sj_lap("centers");
-      HS_HIP(h, hs_launch_embed(h->codes.as<uint8_t>() + q0 * h->p.k, nq, (int)h->p.k,
-                                h->coords.as<double>(), centers.as<double>(), h->stream));
-    }
-    // (the pair of a k-mer with itself is dropped on the device)
-    const QueryCall call{from_codes ? nullptr : centers.as<double>(), nullptr, R, false, (uint32_t)q0, sqrt_test != 0};
+  HS_CHECK(self_join_chunks(h, first, count, R, sqrt_test, HitSink(), &acc,
+                            [&](const QueryCall& call, uint64_t q0, uint64_t nq) -> hs_status {
+    if (call.centers) sj_lap("centers");  // (the chunk was embedded: reserve and launch)
     uint64_t hcap = std::max<uint64_t>(dq.cap / 4, 3 * nq + 1024), nh = 0;
     for (;;) {
       HS_HIP(h, dq.reserve(hcap * 4));
       HS_HIP(h, did.reserve(hcap * 4));
       HS_HIP(h, dt.reserve(hcap * 4));
       HS_HIP(h, dd.reserve(hcap * 8));
-      st = run_query(h, call, nq, dq.as<uint32_t>(), did.as<uint32_t>(), dt.as<uint32_t>(), dd.as<double>(), hcap,
-                     &nh, nullptr);
-      if (st == HS_ERR_CAPACITY) {
-        hcap = nh + nh / 8 + 1024;
-        continue;
-      }
-      break;
+      const hs_status st = run_query(h, call, nq, dq.as<uint32_t>(), did.as<uint32_t>(), dt.as<uint32_t>(),
+                                     dd.as<double>(), hcap, &nh, nullptr);
+      if (st == HS_OK) break;
+      if (st != HS_ERR_CAPACITY) return st;
+      hcap = nh + nh / 8 + 1024;
     }
-    if (st != HS_OK) return st;
     sj_lap("run_query");
-    acc.ms_hash += h->prof.ms_hash; acc.ms_probe += h->prof.ms_probe; acc.ms_verify += h->prof.ms_verify;
-    acc.ms_join += h->prof.ms_join; acc.ms_finalize += h->prof.ms_finalize; acc.ms_total += h->prof.ms_total;
-    acc.candidates += h->prof.candidates; acc.provisional += h->prof.provisional;
-    acc.join_pairs += h->prof.join_pairs; acc.join_pairs_issued += h->prof.join_pairs_issued;
-    acc.join_items += h->prof.join_items; acc.join_batches += h->prof.join_batches;
-    acc.join_items_resident += h->prof.join_items_resident;
-    acc.verify_launches += h->prof.verify_launches;
-    acc.hash_values += h->prof.hash_values; acc.hash_flagged += h->prof.hash_flagged;
     HS_HIP(h, h->sj_host.reserve(std::max<size_t>(64, (nh + nh / 8 + 1024) * 20)));
     sj_lap("host buf");
     double* const hd = h->sj_host.as<double>();                       // [nh] doubles first: aligned
@@ -3603,7 +3615,8 @@ hs_status hs_self_join_range(hs_handle* h, uint64_t first, uint64_t count, doubl
       }
       ++total;
     }
-  }
+    return HS_OK;
+  }));
   h->prof = acc;
   h->prof.hits = total;
   *n_edges = total;
@@ -3612,38 +3625,14 @@ hs_status hs_self_join_range(hs_handle* h, uint64_t first, uint64_t count, doubl
 }
 
 // ---- self-joins reduced on the device (hs_components, hs_degrees, hs_dbscan) ----------------------------
-// The self-join of [first, first + count) with every batch's pairs reduced where finalize_hits leaves them, as `what`
-// says (components / dbscan): no per-query ordering, no edge arrays, no copies to the host.  The chunks' profiles
-// are added to *acc.
-static hs_status reduced_self_join(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test,
-                                   const QueryCall& what, hs_profile* acc_out) {
-  hs_profile& acc = *acc_out;
-  const uint64_t end = first + count;
-  const uint32_t CH = 1u << 20;  // queries per chunk, as in hs_self_join_range
-  for (uint64_t q0 = first; q0 < end; q0 += CH) {
-    const uint64_t nq = std::min<uint64_t>(CH, end - q0);
-    const bool from_codes = self_codes_ok(h, R);
-    if (!from_codes) {
-      HS_HIP(h, h->io_centers.reserve((size_t)nq * h->d * 8));
-      HS_HIP(h, hs_launch_embed(h->codes.as<uint8_t>() + q0 * h->p.k, nq, (int)h->p.k, h->coords.as<double>(),
-                                h->io_centers.as<double>(), h->stream));
-    }
-    QueryCall call{from_codes ? nullptr : h->io_centers.as<double>(), nullptr, R, false, (uint32_t)q0, sqrt_test != 0};
-    call.components = what.components;
-    call.dbscan = what.dbscan;
-    call.db_min_pts = what.db_min_pts;
+// The self-join of [first, first + count) with every batch's pairs reduced where finalize_hits leaves them, as
+// `sink` says: no per-query ordering, no edge arrays, no copies to the host.  The chunks' profiles are added to *acc.
+static hs_status reduced_self_join(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test, HitSink sink,
+                                   hs_profile* acc) {
+  return self_join_chunks(h, first, count, R, sqrt_test, sink, acc, [h](const QueryCall& call, uint64_t, uint64_t nq) {
     uint64_t nh = 0;
-    HS_CHECK(run_query(h, call, nq, nullptr, nullptr, nullptr, nullptr, 0, &nh, nullptr));
-    acc.ms_hash += h->prof.ms_hash; acc.ms_probe += h->prof.ms_probe; acc.ms_verify += h->prof.ms_verify;
-    acc.ms_join += h->prof.ms_join; acc.ms_finalize += h->prof.ms_finalize; acc.ms_total += h->prof.ms_total;
-    acc.candidates += h->prof.candidates; acc.provisional += h->prof.provisional;
-    acc.join_pairs += h->prof.join_pairs; acc.join_pairs_issued += h->prof.join_pairs_issued;
-    acc.join_items += h->prof.join_items; acc.join_batches += h->prof.join_batches;
-    acc.join_items_resident += h->prof.join_items_resident;
-    acc.verify_launches += h->prof.verify_launches;
-    acc.hash_values += h->prof.hash_values; acc.hash_flagged += h->prof.hash_flagged;
-  }
-  return HS_OK;
+    return run_query(h, call, nq, nullptr, nullptr, nullptr, nullptr, 0, &nh, nullptr);
+  });
 }
 
 // ---- hs_components: connected components of the self-join's graph (kernels and the invariant: hs_components.hip) ----
@@ -3655,11 +3644,8 @@ static hs_status components_run(hs_handle* h, uint64_t first, uint64_t count, do
   HS_HIP(h, h->cc_parent.reserve(std::max<size_t>(16, (size_t)n_all * 4)));
   HS_HIP(h, h->cc_cnt.reserve(16));
   HS_HIP(h, hs_launch_cc_begin(h->cc_parent.as<uint32_t>(), n_all, h->cc_cnt.as<uint64_t>(), h->stream));
-  hs_profile acc;
-  memset(&acc, 0, sizeof(acc));
-  QueryCall what;
-  what.components = true;
-  HS_CHECK(reduced_self_join(h, first, count, R, sqrt_test, what, &acc));
+  hs_profile acc = {};
+  HS_CHECK(reduced_self_join(h, first, count, R, sqrt_test, {HitSink::CC_UNION}, &acc));
   HS_HIP(h, hs_launch_cc_flatten(h->cc_parent.as<uint32_t>(), n_all, d_label, h->cc_cnt.as<uint64_t>(), h->stream));
   uint64_t counts[2] = {0, 0};
   HS_HIP(h, hipMemcpyAsync(counts, h->cc_cnt.p, 16, hipMemcpyDeviceToHost, h->stream));
@@ -3676,11 +3662,7 @@ static hs_status components_check(hs_handle* h, uint64_t first, uint64_t count, 
   if (!h || !n_components) return HS_ERR_INVALID;
   *n_components = 0;
   if (n_edges) *n_edges = 0;
-  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
-  if (h->n && !label) return HS_ERR_INVALID;
-  HS_CHECK(ensure_device(h));
-  if (first > h->n || count > h->n - first) return fail(h, HS_ERR_INVALID, "range outside the indexed k-mers");
-  return HS_OK;
+  return self_join_check(h, first, count, !h->n || label);
 }
 
 hs_status hs_components_range_dev(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test,
@@ -3727,15 +3709,10 @@ static hs_status dbscan_run(hs_handle* h, uint64_t first, uint64_t count, double
   HS_HIP(h, h->db_cnt.reserve(64));
   HS_HIP(h, hs_launch_db_begin(h->db_deg.as<uint32_t>(), h->cc_parent.as<uint32_t>(), h->db_anchor.as<uint32_t>(), n_all,
                                h->db_cnt.as<uint64_t>(), h->stream));
-  hs_profile acc;
-  memset(&acc, 0, sizeof(acc));
-  QueryCall what;
-  what.dbscan = QueryCall::DB_DEGREE;
-  HS_CHECK(reduced_self_join(h, first, count, R, sqrt_test, what, &acc));
+  hs_profile acc = {};
+  HS_CHECK(reduced_self_join(h, first, count, R, sqrt_test, {HitSink::DB_DEGREE}, &acc));
   if (min_pts) {
-    what.dbscan = QueryCall::DB_UNITE;
-    what.db_min_pts = min_pts;
-    HS_CHECK(reduced_self_join(h, first, count, R, sqrt_test, what, &acc));
+    HS_CHECK(reduced_self_join(h, first, count, R, sqrt_test, {HitSink::DB_UNITE, min_pts}, &acc));
     HS_HIP(h, hs_launch_db_finish(h->cc_parent.as<uint32_t>(), h->db_deg.as<uint32_t>(), h->db_anchor.as<uint32_t>(),
                                   min_pts, n_all, d_label, h->db_cnt.as<uint64_t>(), h->stream));
   }
@@ -3759,10 +3736,7 @@ static hs_status degrees_any(hs_handle* h, uint64_t first, uint64_t count, doubl
                              uint64_t* n_edges, bool dev) {
   if (!h) return HS_ERR_INVALID;
   if (n_edges) *n_edges = 0;
-  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
-  if (h->n && !degree) return HS_ERR_INVALID;
-  HS_CHECK(ensure_device(h));
-  if (first > h->n || count > h->n - first) return fail(h, HS_ERR_INVALID, "range outside the indexed k-mers");
+  HS_CHECK(self_join_check(h, first, count, !h->n || degree));
   uint64_t counts[5] = {0, 0, 0, 0, 0};
   HS_CHECK(dbscan_run(h, first, count, R, sqrt_test, 0, nullptr, counts));
   HS_CHECK(dbscan_copy_out(h, degree, h->db_deg, dev));
@@ -3774,10 +3748,8 @@ static hs_status dbscan_any(hs_handle* h, double R, int sqrt_test, uint32_t min_
                             hs_dbscan_counts* out, bool dev) {
   if (!h || !out) return HS_ERR_INVALID;
   memset(out, 0, sizeof(*out));
-  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
-  if (h->n && !label) return HS_ERR_INVALID;
+  HS_CHECK(self_join_check(h, 0, h->n, !h->n || label));
   if (!min_pts) return fail(h, HS_ERR_INVALID, "min_pts must be at least 1");
-  HS_CHECK(ensure_device(h));
   uint32_t* d_label = label;
   if (!dev) {
     HS_HIP(h, h->cc_label.reserve(std::max<size_t>(16, (size_t)h->n * 4)));

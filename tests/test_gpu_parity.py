@@ -247,6 +247,83 @@ def test_batches_split_when_the_survivor_counter_would_overflow(oracle, monkeypa
         assert np.array_equal(split[key], plain[key])
 
 
+@pytest.mark.parametrize("db", ["uniform", "planted"])
+def test_reducing_calls_see_each_pair_once_when_batches_split(monkeypatch, db):
+    """A reducing call (annotate, components, degrees, dbscan) hands a batch's hits to its reduction exactly once,
+    and only after the batch came through whole (hs_capi.hip run_query): a batch cut in halves has handed nothing
+    on, and its halves bring each hit once.  The degree count is the reduction that would show a hit handed on
+    twice.  With HS_TEST_SPLIT_ABOVE=150 on the TEST build every array and count is that of the unsplit product
+    library.  That the batches were split shows in verify_launches, the counter the test above uses: only a batch
+    that succeeds adds to it, at least 1 (filter_passes), and none above 150 queries succeeds, so a pass over the n
+    k-mers counts >= n // 150 = 133 (dbscan, two passes: 266) and annotate's nq centres >= nq // 150 = 8.
+    The counter and the bounds follow from that code, which the sinks left as it was.  db "uniform" is the database
+    of the test above: its random k-mers have no neighbour within R, so the self-joins reduce no pair and only
+    annotate has hits to hand on.  "planted" is the same database with its first 2000 k-mers replaced by 80 families
+    of 25 (a random k-mer, up to 8 substitutions per member), so that degrees, unions and anchors have pairs (by
+    the CPU oracle: 34916 ordered pairs, degrees 0 .. 24, at min_pts = 3 core, border and noise k-mers among them)."""
+    import torch
+    k, K, L, W, R, n, nq = 25, 4, 5, 150.0, 45.0, 20011, 1203
+    a, b = synth.make_planes(k, K, L, W, seed=35)
+    codes = synth.make_db(n, k, seed=36)
+    if db == "planted":
+        rng = np.random.default_rng(38)
+        fam = np.repeat(rng.integers(0, 20, size=(80, k), dtype=np.uint8), 25, axis=0)
+        n_sub = rng.integers(0, 9, size=len(fam))
+        for t in range(8):  # substitution t + 1 of the members that have that many
+            sel = np.nonzero(n_sub > t)[0]
+            fam[sel, rng.integers(0, k, size=len(sel))] = rng.integers(0, 20, size=len(sel), dtype=np.uint8)
+        codes[:len(fam)] = fam
+    centers, _ = synth.make_queries(codes, nq, seed=37, jitter=0.2)
+
+    def calls(eng):
+        out, prof = {}, {}
+        d_degree = torch.zeros(n, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        for name, call in (("self_join", lambda: eng.self_join(R, sqrt_test=True)),
+                           ("components", lambda: eng.components(R, sqrt_test=True)),
+                           ("degrees", lambda: dict(degree=eng.degrees(R, sqrt_test=True))),
+                           ("degrees_dev", lambda: dict(n_edges=eng.degrees_dev(d_degree.data_ptr(), R, sqrt_test=True))),
+                           ("dbscan", lambda: eng.dbscan(R, min_pts=3, sqrt_test=True)),
+                           ("annotate", lambda: eng.annotate(centers, R))):
+            out[name] = call()
+            prof[name] = eng.profile()
+        out["degrees_dev"]["degree"] = d_degree.cpu().numpy().view(np.uint32)
+        return out, prof
+
+    eng = Engine(k, K, L, W, a, b)
+    eng.index_build(codes)
+    plain, _ = calls(eng)
+    eng.close()
+    monkeypatch.setenv("HS_TEST_SPLIT_ABOVE", "150")
+    eng = Engine(k, K, L, W, a, b, hooks=True)
+    eng.index_build(codes)
+    split, prof = calls(eng)
+    eng.close()
+    print({name: (p["verify_launches"], p["join_batches"]) for name, p in prof.items()})
+    for name in ("self_join", "components", "degrees", "degrees_dev"):
+        assert prof[name]["verify_launches"] >= n // 150, name
+    assert prof["dbscan"]["verify_launches"] >= 2 * (n // 150)
+    assert prof["annotate"]["verify_launches"] >= nq // 150
+    for name, want in plain.items():
+        assert sorted(split[name]) == sorted(want), name
+        for key, value in want.items():
+            if isinstance(value, np.ndarray):
+                assert split[name][key].dtype == value.dtype and np.array_equal(split[name][key], value), (name, key)
+            else:
+                assert split[name][key] == value, (name, key)
+    n_edges = len(plain["self_join"]["i"])
+    print(db, "edges", n_edges, "largest degree", int(plain["degrees"]["degree"].max()), "annotated",
+          len(plain["annotate"]["id"]), {f: plain["dbscan"][f] for f in ("n_clusters", "n_core", "n_border", "n_noise")})
+    assert len(plain["annotate"]["id"]) > 0
+    if db == "planted":  # the degree count and both branches of the unite kernel had work
+        assert n_edges > 0 and plain["degrees"]["degree"].max() >= 2
+        assert plain["dbscan"]["n_core"] > 0 and plain["dbscan"]["n_border"] > 0
+    for name in ("components", "degrees_dev", "dbscan"):
+        assert split[name]["n_edges"] == n_edges and plain[name]["n_edges"] == n_edges, name
+    assert int(split["degrees"]["degree"].sum(dtype=np.uint64)) == n_edges
+    assert np.array_equal(split["degrees"]["degree"], split["degrees_dev"]["degree"])
+
+
 def test_join_with_many_queries_per_bucket(oracle):
     """Coarse keys (K=2, large W): a handful of huge buckets, each probed by hundreds of queries --
     multi-chunk, multi-tile work items of the bucket join, plus ragged tile/chunk remainders."""
