@@ -25,7 +25,9 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_bruteforce_topk", "hs_merge_first_table_dev", "hs_query_radii", "hs_query_radii_dev",
            "hs_bruteforce_radii", "hs_annotate", "hs_annotate_dev", "hs_merge_best", "hs_components", "hs_components_dev",
            "hs_components_range", "hs_components_range_dev", "hs_components_merge", "hs_degrees", "hs_degrees_dev",
-           "hs_degrees_range", "hs_degrees_range_dev", "hs_dbscan", "hs_dbscan_dev", "hs_dbscan_edges"]
+           "hs_degrees_range", "hs_degrees_range_dev", "hs_dbscan", "hs_dbscan_dev", "hs_dbscan_edges",
+           "hs_cluster_profile", "hs_cluster_profile_dev", "hs_cluster_radii", "hs_cluster_radii_dev",
+           "hs_cluster_summary_codes"]
 
 NOISE = 0xffffffff   # HS_NOISE: the label of a k-mer that is neither core nor border (hs_dbscan)
 
@@ -152,6 +154,22 @@ def load(hooks=False):
             lib.hs_dbscan_edges.restype = C.c_int
             lib.hs_dbscan_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p,
                                             C.c_void_p, C.POINTER(_DbscanCounts)]
+        # cluster summaries: profile (h, label, min_size, out_label, out_size, counts, centroid, cap, n_out); radii
+        # (h, label, min_size, centers, n_rows, max_d2, radius, medoid); summary_codes: see include/hsearch.h
+        if hasattr(lib, "hs_cluster_profile"):
+            for fn in (lib.hs_cluster_profile, lib.hs_cluster_profile_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_uint64, C.POINTER(C.c_uint64)]
+            for fn in (lib.hs_cluster_radii, lib.hs_cluster_radii_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                               C.c_void_p]
+            lib.hs_cluster_summary_codes.restype = C.c_int
+            lib.hs_cluster_summary_codes.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                     C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         _libs[hooks] = lib
     return _libs[hooks]
 
@@ -266,6 +284,53 @@ def dbscan_edges(ei, ej, n, min_pts, want_degree=False):
     return res
 
 
+def cluster_summary_codes(codes, label, min_size=1, coords=None, centers=None, want_counts=False, want_radii=True,
+                          cap=None):
+    """hs_cluster_summary_codes (host only, no GPU): the rules of Engine.cluster_profile and Engine.cluster_radii for
+    codes uint8 [n][k], label uint32 [n] (NOISE or a value < n) and coords [alphabet][8] (None: the default table)
+    -> dict(label, size, centroid [rows][8k], counts [rows][k][alphabet] if asked, and with want_radii max_d2, radius,
+    medoid -- against centers [rows][8k], or against the centroids when centers is None).  Rows: the clusters of at
+    least min_size members in ascending label.  cap=None: as many rows as needed; a given cap that is too small
+    raises HsError(HS_ERR_CAPACITY) with the required size in .needed."""
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    label = np.ascontiguousarray(label, dtype=np.uint32)
+    assert codes.ndim == 2 and label.shape == (codes.shape[0],)
+    n, k = codes.shape
+    alpha = 20
+    if coords is not None:
+        coords = np.ascontiguousarray(coords, dtype=np.float64)
+        assert coords.ndim == 2 and coords.shape[1] == 8
+        alpha = coords.shape[0]
+    room = n // max(1, int(min_size)) if cap is None else int(cap)
+    if centers is not None:
+        centers = np.ascontiguousarray(centers, dtype=np.float64)
+        assert centers.ndim == 2 and centers.shape[1] == 8 * k
+    ol = np.empty(room, dtype=np.uint32)
+    osz = np.empty(room, dtype=np.uint32)
+    cen = np.empty((room, 8 * k), dtype=np.float64)
+    cnt = np.empty((room, k, alpha), dtype=np.uint32) if want_counts else None
+    mx = np.empty(room, dtype=np.float64) if want_radii else None
+    rad = np.empty(room, dtype=np.float64) if want_radii else None
+    med = np.empty(room, dtype=np.uint32) if want_radii else None
+    n_out = C.c_uint64(0)
+    opt = lambda a: None if a is None else _vp(a)
+    st = load().hs_cluster_summary_codes(_vp(codes), n, k, opt(coords), alpha if coords is not None else 0, _vp(label),
+                                         int(min_size), opt(centers), 0 if centers is None else centers.shape[0],
+                                         _vp(ol), _vp(osz), opt(cnt), _vp(cen), opt(mx), opt(rad), opt(med), room,
+                                         C.byref(n_out))
+    if st != HS_OK:
+        e = HsError(st, "hs_cluster_summary_codes")
+        e.needed = int(n_out.value)
+        raise e
+    m = int(n_out.value)
+    res = dict(label=ol[:m], size=osz[:m], centroid=cen[:m])
+    if want_counts:
+        res["counts"] = cnt[:m]
+    if want_radii:
+        res.update(max_d2=mx[:m], radius=rad[:m], medoid=med[:m])
+    return res
+
+
 def index_file_check(path):
     """Host-only check of an index file (hs_index_file_check): header, payload length + hash and the
     content rules hs_index_load enforces on the device.  Raises HsError(HS_ERR_IO) naming the fault."""
@@ -359,7 +424,7 @@ class Engine:
     OPTIONS = {"query_batch": 1, "seg_mode": 2, "join_resident": 3, "recognise_kmers": 4, "build_grouping": 5,
                "wide_rows": 6, "refine8": 7, "self_codes": 8, "sort_hits": 10, "sync_items": 11,
                "join_min_q": 12, "join_min_m": 13, "sort_from_bit": 14, "build_serial": 15,
-               "join_xcd_run": 16, "probe_records": 17, "join_chunk": 18}
+               "join_xcd_run": 16, "probe_records": 17, "join_chunk": 18, "summary_chunk": 19, "summary_rows": 20}
 
     def set_option(self, name, value):
         """hs_set_option (include/hsearch.h hs_option): path selection / batch sizing; never changes a result."""
@@ -830,6 +895,73 @@ class Engine:
         self._check(self._lib.hs_dbscan_dev(self._h, float(R), 1 if sqrt_test else 0, int(min_pts), d_label_ptr,
                                             d_degree_ptr, C.byref(c)))
         return _counts_dict(c)
+
+    def cluster_profile(self, label, min_size=1, want_counts=False, cap=None):
+        """hs_cluster_profile: the clusters of label uint32 [n] (NOISE or a value < n: the labels of components(),
+        dbscan() or clustering()'s owner) with at least min_size members, in ascending label, summarised on the
+        device: dict(label, size, centroid float64 [rows][d], counts uint32 [rows][k][alphabet] if asked)."""
+        label = np.ascontiguousarray(label, dtype=np.uint32)
+        n = self._n()
+        assert label.shape == (n,)
+        p = _Params()
+        self._check(self._lib.hs_get_params(self._h, C.byref(p)))
+        cap = n // max(1, int(min_size)) if cap is None else int(cap)
+        ol = np.empty(cap, dtype=np.uint32)
+        osz = np.empty(cap, dtype=np.uint32)
+        cen = np.empty((cap, self.d), dtype=np.float64)
+        cnt = np.empty((cap, self.k, int(p.alphabet)), dtype=np.uint32) if want_counts else None
+        n_out = C.c_uint64(0)
+        st = self._lib.hs_cluster_profile(self._h, _vp(label), int(min_size), _vp(ol), _vp(osz),
+                                          _vp(cnt) if want_counts else None, _vp(cen), cap, C.byref(n_out))
+        if st == HS_ERR_CAPACITY:
+            e = HsError(st, self._lib.hs_last_error(self._h).decode())
+            e.needed = int(n_out.value)
+            raise e
+        self._check(st)
+        m = int(n_out.value)
+        res = dict(label=ol[:m], size=osz[:m], centroid=cen[:m])
+        if want_counts:
+            res["counts"] = cnt[:m]
+        return res
+
+    def cluster_radii(self, label, centers, min_size=1):
+        """hs_cluster_radii: per row of cluster_profile(label, min_size) and its centre centers[row] (any points
+        [rows][d]): dict(max_d2 = the largest member d2, radius = the smallest double whose square covers it, medoid =
+        the member smallest under (d2, id))."""
+        label = np.ascontiguousarray(label, dtype=np.uint32)
+        centers = np.ascontiguousarray(centers, dtype=np.float64)
+        rows = centers.shape[0]
+        assert label.shape == (self._n(),) and centers.shape == (rows, self.d)
+        mx = np.empty(rows, dtype=np.float64)
+        rad = np.empty(rows, dtype=np.float64)
+        med = np.empty(rows, dtype=np.uint32)
+        self._check(self._lib.hs_cluster_radii(self._h, _vp(label), int(min_size), _vp(centers), rows, _vp(mx),
+                                               _vp(rad), _vp(med)))
+        return dict(max_d2=mx, radius=rad, medoid=med)
+
+    def cluster_summary(self, label, min_size=1, want_counts=False):
+        """cluster_profile, then cluster_radii against its centroids, as one dict."""
+        res = self.cluster_profile(label, min_size, want_counts=want_counts)
+        res.update(self.cluster_radii(label, res["centroid"], min_size))
+        return res
+
+    def cluster_profile_dev(self, d_label_ptr, min_size, d_out_label, d_out_size, d_counts, d_centroid, cap):
+        """hs_cluster_profile_dev (device pointers as ints; d_counts None or 0: no counts).  Returns the number of
+        rows; raises HsError(HS_ERR_CAPACITY) with the required size in .needed when cap is too small."""
+        n_out = C.c_uint64(0)
+        st = self._lib.hs_cluster_profile_dev(self._h, d_label_ptr, int(min_size), d_out_label, d_out_size,
+                                              d_counts if d_counts else None, d_centroid, cap, C.byref(n_out))
+        if st == HS_ERR_CAPACITY:
+            e = HsError(st, self._lib.hs_last_error(self._h).decode())
+            e.needed = int(n_out.value)
+            raise e
+        self._check(st)
+        return int(n_out.value)
+
+    def cluster_radii_dev(self, d_label_ptr, min_size, d_centers, n_rows, d_max_d2, d_radius, d_medoid):
+        """hs_cluster_radii_dev (device pointers as ints)."""
+        self._check(self._lib.hs_cluster_radii_dev(self._h, d_label_ptr, int(min_size), d_centers, int(n_rows),
+                                                   d_max_d2, d_radius, d_medoid))
 
 
 def clustering(k, K, L, W, a, b, codes, R, device=0, coords=None):

@@ -99,6 +99,8 @@ struct Knobs {
   int seg_mode = 0;                // HS_OPT_SEG_MODE: 1 sparse / 2 dense; 0 = by the bucket : probe ratio
   int sort_from_bit = 16;          // HS_OPT_SORT_FROM_BIT: lowest fingerprint bit the build's sort looks at
   uint32_t query_batch = 0;        // HS_OPT_QUERY_BATCH: queries per batch (0: by L and the free HBM)
+  uint32_t summary_chunk = 0;      // HS_OPT_SUMMARY_CHUNK: member slots per work item of hs_summary.hip (0: 512)
+  uint32_t summary_rows = 0;       // HS_OPT_SUMMARY_ROWS: rows per batch of hs_cluster_profile (0: by the scratch budget)
 #ifdef HS_TEST_HOOKS
   uint32_t test_split_above = 0;   // HS_TEST_SPLIT_ABOVE: batches above this size report a survivor overflow
   bool test_group_fallback = false;  // HS_TEST_GROUP_FALLBACK: the build's fingerprint table reports itself full
@@ -221,6 +223,13 @@ struct hs_handle {
   // hs_degrees / hs_dbscan (hs_dbscan.hip): the degree and the smallest core neighbour per indexed k-mer (the forest
   // is cc_parent: every call starts it from the identity), and the call's five 64-bit counts
   DevBuf db_deg, db_anchor, db_cnt;
+  // hs_cluster_profile / hs_cluster_radii (hs_summary.hip: the state listed at its head), the counts of a row batch
+  // when the caller wants none, and the arrays of a host-pointer call on their way in and out
+  DevBuf sm_size, sm_tmp, sm_row_of, sm_off_of, sm_row_label, sm_row_off, sm_member, sm_d2, sm_err, sm_counts;
+  // host-pointer calls: the labels in; out, hs_cluster_profile: sm_io_a = out_label, sm_io_b = out_size, sm_io_counts,
+  // sm_io_f64 = centroid; hs_cluster_radii (centres in through io_centers, as the searches' are): sm_io_f64 = max_d2,
+  // sm_io_f64b = radius, sm_io_a = medoid
+  DevBuf sm_io_label, sm_io_a, sm_io_b, sm_io_counts, sm_io_f64, sm_io_f64b;
   DevBuf io_radii;   // hs_query_radii: the radii on the device; hs_query_radii_dev: {max |radius|, NaN flag}
   DevBuf qcodes_buf, qembed;  // hs_query_codes: a batch's checked copy of the query codes; their embedding
                               // when no from-codes path applies
@@ -476,7 +485,7 @@ const struct { const char* name; int option; } kOptionNames[] = {
     {"sort_hits", HS_OPT_SORT_HITS}, {"sync_items", HS_OPT_SYNC_ITEMS}, {"join_min_q", HS_OPT_JOIN_MIN_Q},
     {"join_min_m", HS_OPT_JOIN_MIN_M}, {"sort_from_bit", HS_OPT_SORT_FROM_BIT}, {"build_serial", HS_OPT_BUILD_SERIAL},
     {"join_xcd_run", HS_OPT_JOIN_XCD_RUN}, {"probe_records", HS_OPT_PROBE_RECORDS},
-    {"join_chunk", HS_OPT_JOIN_CHUNK}};
+    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS}};
 
 void read_knobs(hs_handle* h) {
   Knobs& kn = h->knobs;
@@ -774,6 +783,14 @@ hs_status hs_set_option(hs_handle* h, int option, int64_t value) {
       if (value != 0 && (value < 2 || value > 64)) break;
       kn.join_chunk = (uint32_t)value;
       return HS_OK;
+    case HS_OPT_SUMMARY_CHUNK:
+      if (value < 0 || value > (1ll << 20)) break;
+      kn.summary_chunk = (uint32_t)value;
+      return HS_OK;
+    case HS_OPT_SUMMARY_ROWS:
+      if (value < 0 || value >= (1ll << 31)) break;
+      kn.summary_rows = (uint32_t)value;
+      return HS_OK;
     case HS_OPT_JOIN_XCD_RUN:
       if (value < -1 || value > 4096 || (value > 0 && (value & (value - 1)))) break;  // a power of two
       kn.join_xcd_run = (int)value;
@@ -814,7 +831,9 @@ void hs_destroy(hs_handle* h) {
                     &h->mp_vints, &h->mp_valid, &h->mp_rows, &h->mp_q, &h->mp_id, &h->mp_table, &h->mp_dist,
                     &h->mp_cand, &h->mp_radii, &h->io_radii, &h->ann_dist, &h->ann_tq, &h->ann_touched,
                     &h->ann_sorted, &h->ann_cnt, &h->cc_parent, &h->cc_cnt, &h->cc_label,
-                    &h->db_deg, &h->db_anchor, &h->db_cnt};
+                    &h->db_deg, &h->db_anchor, &h->db_cnt, &h->sm_size, &h->sm_tmp, &h->sm_row_of, &h->sm_off_of,
+                    &h->sm_row_label, &h->sm_row_off, &h->sm_member, &h->sm_d2, &h->sm_err, &h->sm_counts,
+                    &h->sm_io_label, &h->sm_io_a, &h->sm_io_b, &h->sm_io_counts, &h->sm_io_f64, &h->sm_io_f64b};
   for (DevBuf* bf : bufs) bf->release();
   h->sj_host.release();
   h->t_dirjump.release();
@@ -3795,6 +3814,164 @@ hs_status hs_dbscan(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, uin
 hs_status hs_dbscan_dev(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, uint32_t* d_label, uint32_t* d_degree,
                         hs_dbscan_counts* out) {
   return dbscan_any(h, R, sqrt_test, min_pts, d_label, d_degree, out, true);
+}
+
+// ---- hs_cluster_profile / hs_cluster_radii: clusters of a label array summarised (kernels and state: hs_summary.hip) ----
+// Steps 1-3: sizes and validation, rows, grouping.  d_label [n] (device).  HS_ERR_INVALID for a label that is neither
+// HS_NOISE nor < n, detected on the device and reported before anything else is written.
+static hs_status summary_group(hs_handle* h, const uint32_t* d_label, uint32_t min_size, uint32_t* n_rows,
+                               uint32_t* n_kept) {
+  const uint32_t n = (uint32_t)h->n;
+  const size_t words = ((size_t)n + 1) * 4;
+  HS_HIP(h, h->sm_size.reserve(words));
+  HS_HIP(h, h->sm_tmp.reserve(words));
+  HS_HIP(h, h->sm_row_of.reserve(words));
+  HS_HIP(h, h->sm_off_of.reserve(words));
+  HS_HIP(h, h->sm_row_label.reserve(words));
+  HS_HIP(h, h->sm_row_off.reserve(words));
+  HS_HIP(h, h->sm_member.reserve(words));
+  HS_HIP(h, h->sm_err.reserve(16));
+  HS_HIP(h, h->temp.reserve(hs_scan_u32_temp((size_t)n + 1) + 256));
+  HS_HIP(h, hs_launch_sm_group(d_label, n, min_size, h->sm_size.as<uint32_t>(), h->sm_tmp.as<uint32_t>(),
+                               h->sm_row_of.as<uint32_t>(), h->sm_off_of.as<uint32_t>(), h->temp.p, h->temp.cap,
+                               h->sm_err.as<uint32_t>(), h->stream));
+  uint32_t back[3] = {0, 0, 0};
+  HS_HIP(h, hipMemcpyAsync(&back[0], h->sm_err.p, 4, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipMemcpyAsync(&back[1], h->sm_row_of.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipMemcpyAsync(&back[2], h->sm_off_of.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  if (back[0]) return fail(h, HS_ERR_INVALID, "a label is neither HS_NOISE nor below the number of indexed k-mers");
+  if (back[1] > n || back[2] > n) return fail(h, HS_ERR_HIP, "cluster summary: more rows or members than k-mers");
+  HS_HIP(h, hs_launch_sm_members(d_label, n, min_size, h->sm_size.as<uint32_t>(), h->sm_row_of.as<uint32_t>(),
+                                 h->sm_off_of.as<uint32_t>(), h->sm_row_label.as<uint32_t>(),
+                                 h->sm_row_off.as<uint32_t>(), h->sm_member.as<uint32_t>(), h->stream));
+  *n_rows = back[1];
+  *n_kept = back[2];
+  return HS_OK;
+}
+
+static hs_status summary_check(hs_handle* h, const uint32_t* label, uint32_t min_size) {
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
+  if (!min_size) return fail(h, HS_ERR_INVALID, "min_size must be at least 1");
+  if (h->n && !label) return fail(h, HS_ERR_INVALID, "label is null");
+  return ensure_device(h);
+}
+
+static uint32_t summary_chunk(const hs_handle* h) { return h->knobs.summary_chunk ? h->knobs.summary_chunk : 512u; }
+
+hs_status hs_cluster_profile_dev(hs_handle* h, const uint32_t* d_label, uint32_t min_size, uint32_t* d_out_label,
+                                 uint32_t* d_out_size, uint32_t* d_counts, double* d_centroid, uint64_t cap,
+                                 uint64_t* n_out) {
+  if (!h || !n_out) return HS_ERR_INVALID;
+  *n_out = 0;
+  HS_CHECK(summary_check(h, d_label, min_size));
+  if (cap && (!d_out_label || !d_out_size || !d_centroid)) return fail(h, HS_ERR_INVALID, "an output array is null");
+  memset(&h->prof, 0, sizeof(h->prof));
+  uint32_t n_rows = 0, n_kept = 0;
+  HS_CHECK(summary_group(h, d_label, min_size, &n_rows, &n_kept));
+  *n_out = n_rows;
+  if (n_rows > cap) return fail(h, HS_ERR_CAPACITY, "profile buffers too small; see *n_out");
+  const int k = (int)h->p.k;
+  const size_t cells = (size_t)k * h->alphabet;
+  // rows per batch: the scratch for the counts nobody asked for holds 32 MB whatever the number of rows
+  uint32_t batch = h->knobs.summary_rows;
+  if (!batch) batch = (uint32_t)std::max<size_t>(1, ((size_t)32 << 20) / (cells * 4));
+  if (!d_counts) HS_HIP(h, h->sm_counts.reserve(std::min<size_t>(batch, std::max<uint32_t>(n_rows, 1)) * cells * 4));
+  HS_HIP(h, hs_launch_sm_head(h->sm_row_label.as<uint32_t>(), h->sm_row_off.as<uint32_t>(), n_rows, d_out_label,
+                              d_out_size, h->stream));
+  for (uint32_t r0 = 0; r0 < n_rows; r0 += batch) {
+    const uint32_t r1 = (uint32_t)std::min<uint64_t>(n_rows, (uint64_t)r0 + batch);
+    uint32_t* const cnt = d_counts ? d_counts + (size_t)r0 * cells : h->sm_counts.as<uint32_t>();
+    HS_HIP(h, hs_launch_sm_profile(h->codes.as<uint8_t>(), k, h->alphabet, d_label, h->sm_row_of.as<uint32_t>(),
+                                   h->sm_row_off.as<uint32_t>(), h->sm_member.as<uint32_t>(), r0, r1, summary_chunk(h),
+                                   n_kept, cnt, h->n_cu, h->stream));
+    HS_HIP(h, hs_launch_sm_centroid(cnt, h->coords.as<double>(), k, h->alphabet, h->sm_row_off.as<uint32_t>(), r0, r1,
+                                    d_centroid, h->stream));
+  }
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return HS_OK;
+}
+
+hs_status hs_cluster_radii_dev(hs_handle* h, const uint32_t* d_label, uint32_t min_size, const double* d_centers,
+                               uint64_t n_rows_given, double* d_max_d2, double* d_radius, uint32_t* d_medoid) {
+  if (!h) return HS_ERR_INVALID;
+  HS_CHECK(summary_check(h, d_label, min_size));
+  if (n_rows_given && (!d_centers || !d_max_d2 || !d_radius || !d_medoid))
+    return fail(h, HS_ERR_INVALID, "the centres or an output array is null");
+  memset(&h->prof, 0, sizeof(h->prof));
+  uint32_t n_rows = 0, n_kept = 0;
+  HS_CHECK(summary_group(h, d_label, min_size, &n_rows, &n_kept));
+  if (n_rows != n_rows_given) return fail(h, HS_ERR_INVALID, "the labels do not give as many rows as there are centres");
+  HS_HIP(h, h->sm_d2.reserve(std::max<size_t>(16, (size_t)h->n * 8)));
+  HS_HIP(h, hs_launch_sm_radii(h->codes.as<uint8_t>(), (int)h->p.k, h->alphabet, h->coords.as<double>(), d_label,
+                               h->sm_row_of.as<uint32_t>(), h->sm_row_off.as<uint32_t>(), h->sm_member.as<uint32_t>(),
+                               n_rows, n_kept, summary_chunk(h), d_centers, h->sm_d2.as<uint64_t>(), d_max_d2, d_radius,
+                               d_medoid, h->n_cu, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return HS_OK;
+}
+
+// the labels of a host-pointer call on the device
+static hs_status summary_labels_in(hs_handle* h, const uint32_t* label) {
+  HS_HIP(h, h->sm_io_label.reserve(std::max<size_t>(16, (size_t)h->n * 4)));
+  if (h->n) HS_HIP(h, hipMemcpyAsync(h->sm_io_label.p, label, (size_t)h->n * 4, hipMemcpyHostToDevice, h->stream));
+  return HS_OK;
+}
+
+hs_status hs_cluster_profile(hs_handle* h, const uint32_t* label, uint32_t min_size, uint32_t* out_label,
+                             uint32_t* out_size, uint32_t* counts, double* centroid, uint64_t cap, uint64_t* n_out) {
+  if (!h || !n_out) return HS_ERR_INVALID;
+  *n_out = 0;
+  HS_CHECK(summary_check(h, label, min_size));
+  if (cap && (!out_label || !out_size || !centroid)) return fail(h, HS_ERR_INVALID, "an output array is null");
+  HS_CHECK(summary_labels_in(h, label));
+  // the device arrays are sized by what the call can return: min(cap, n / min_size) rows
+  const uint64_t room = std::min<uint64_t>(cap, h->n / min_size);
+  const size_t cells = (size_t)h->p.k * h->alphabet, d = (size_t)h->d;
+  HS_HIP(h, h->sm_io_a.reserve(std::max<size_t>(16, room * 4)));
+  HS_HIP(h, h->sm_io_b.reserve(std::max<size_t>(16, room * 4)));
+  HS_HIP(h, h->sm_io_f64.reserve(std::max<size_t>(16, room * d * 8)));
+  if (counts) HS_HIP(h, h->sm_io_counts.reserve(std::max<size_t>(16, room * cells * 4)));
+  uint64_t rows = 0;
+  const hs_status st = hs_cluster_profile_dev(h, h->sm_io_label.as<uint32_t>(), min_size, h->sm_io_a.as<uint32_t>(),
+                                              h->sm_io_b.as<uint32_t>(), counts ? h->sm_io_counts.as<uint32_t>() : nullptr,
+                                              h->sm_io_f64.as<double>(), room, &rows);
+  *n_out = rows;
+  if (st == HS_ERR_CAPACITY && rows <= cap) return fail(h, HS_ERR_HIP, "cluster profile: more rows than n / min_size");
+  HS_CHECK(st);
+  if (rows) {
+    HS_HIP(h, hipMemcpyAsync(out_label, h->sm_io_a.p, rows * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_size, h->sm_io_b.p, rows * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(centroid, h->sm_io_f64.p, rows * d * 8, hipMemcpyDeviceToHost, h->stream));
+    if (counts) HS_HIP(h, hipMemcpyAsync(counts, h->sm_io_counts.p, rows * cells * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return HS_OK;
+}
+
+hs_status hs_cluster_radii(hs_handle* h, const uint32_t* label, uint32_t min_size, const double* centers,
+                           uint64_t n_rows, double* max_d2, double* radius, uint32_t* medoid) {
+  if (!h) return HS_ERR_INVALID;
+  HS_CHECK(summary_check(h, label, min_size));
+  if (n_rows && (!centers || !max_d2 || !radius || !medoid))
+    return fail(h, HS_ERR_INVALID, "the centres or an output array is null");
+  if (n_rows > h->n / min_size) return fail(h, HS_ERR_INVALID, "the labels do not give as many rows as there are centres");
+  HS_CHECK(summary_labels_in(h, label));
+  const size_t d = (size_t)h->d;
+  HS_HIP(h, h->io_centers.reserve(std::max<size_t>(16, n_rows * d * 8)));
+  HS_HIP(h, h->sm_io_f64.reserve(std::max<size_t>(16, n_rows * 8)));
+  HS_HIP(h, h->sm_io_f64b.reserve(std::max<size_t>(16, n_rows * 8)));
+  HS_HIP(h, h->sm_io_a.reserve(std::max<size_t>(16, n_rows * 4)));
+  if (n_rows) HS_HIP(h, hipMemcpyAsync(h->io_centers.p, centers, n_rows * d * 8, hipMemcpyHostToDevice, h->stream));
+  HS_CHECK(hs_cluster_radii_dev(h, h->sm_io_label.as<uint32_t>(), min_size, h->io_centers.as<double>(), n_rows,
+                                h->sm_io_f64.as<double>(), h->sm_io_f64b.as<double>(), h->sm_io_a.as<uint32_t>()));
+  if (n_rows) {
+    HS_HIP(h, hipMemcpyAsync(max_d2, h->sm_io_f64.p, n_rows * 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(radius, h->sm_io_f64b.p, n_rows * 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(medoid, h->sm_io_a.p, n_rows * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return HS_OK;
 }
 
 hs_status hs_bruteforce_topk(hs_handle* h, const double* centers, uint64_t nq, uint32_t topk,

@@ -551,6 +551,33 @@ hipError_t hs_launch_db_unite(const uint64_t* d_key, uint32_t n_hits, uint32_t s
                               uint32_t min_pts, uint32_t* d_parent, uint32_t* d_anchor, uint32_t n, hipStream_t s);
 hipError_t hs_launch_db_finish(uint32_t* d_parent, const uint32_t* d_deg, const uint32_t* d_anchor, uint32_t min_pts,
                                uint32_t n, uint32_t* d_label, uint64_t* d_counts, hipStream_t s);
+// cluster profiles and radii from a label array (hs_summary.hip; the arrays are the state listed at its head).
+// group: sizes, validation (*d_err |= 1: a label that is neither HS_NOISE nor < n) and the two scans -- the caller
+// reads d_err[0], d_row_of[n] (rows) and d_off_of[n] (kept members) back before it goes on; members: the rows' labels
+// and offsets and the ids grouped by row; head: out_label / out_size of the rows.
+hipError_t hs_launch_sm_group(const uint32_t* d_label, uint32_t n, uint32_t min_size, uint32_t* d_size, uint32_t* d_tmp,
+                              uint32_t* d_row_of, uint32_t* d_off_of, void* d_temp, size_t temp_bytes, uint32_t* d_err,
+                              hipStream_t s);
+hipError_t hs_launch_sm_members(const uint32_t* d_label, uint32_t n, uint32_t min_size, const uint32_t* d_size,
+                                const uint32_t* d_row_of, uint32_t* d_off_of, uint32_t* d_row_label,
+                                uint32_t* d_row_off, uint32_t* d_member, hipStream_t s);
+hipError_t hs_launch_sm_head(const uint32_t* d_row_label, const uint32_t* d_row_off, uint32_t n_rows,
+                             uint32_t* d_out_label, uint32_t* d_out_size, hipStream_t s);
+// the batch of rows [r0, r1): d_counts [(r1 - r0)][k][alphabet] (row r0 first), then its centroids into
+// d_centroid [n_rows][8k] (indexed by the row itself).  ch: member slots per work item.
+hipError_t hs_launch_sm_profile(const uint8_t* d_codes, int k, int alphabet, const uint32_t* d_label,
+                                const uint32_t* d_row_of, const uint32_t* d_row_off, const uint32_t* d_member,
+                                uint32_t r0, uint32_t r1, uint32_t ch, uint32_t n_kept, uint32_t* d_counts,
+                                int n_cu, hipStream_t s);
+hipError_t hs_launch_sm_centroid(const uint32_t* d_counts, const double* d_coords, int k, int alphabet,
+                                 const uint32_t* d_row_off, uint32_t r0, uint32_t r1, double* d_centroid,
+                                 hipStream_t s);
+// d_max_d2, d_radius [n_rows] f64, d_medoid [n_rows] u32 (the outputs; d_radius holds the rows' minima on the way)
+hipError_t hs_launch_sm_radii(const uint8_t* d_codes, int k, int alphabet, const double* d_coords,
+                              const uint32_t* d_label, const uint32_t* d_row_of, const uint32_t* d_row_off,
+                              const uint32_t* d_member, uint32_t n_rows, uint32_t n_kept, uint32_t ch,
+                              const double* d_centers, uint64_t* d_d2, double* d_max_d2, double* d_radius,
+                              uint32_t* d_medoid, int n_cu, hipStream_t s);
 // brute force
 hipError_t hs_launch_bruteforce(const uint4* d_packed_all, uint32_t n, const float* d_tq,
                                 uint32_t nq, int k, float r2_hi, uint32_t* d_prov_count,

@@ -8,6 +8,9 @@
 // the reference), --device, and -linkage greedy|single|dbscan (-M): `single` writes the connected components of the
 // near-neighbour graph (hsearch::Components) in place of the greedy leader clusters, `dbscan` its density clusters
 // (hsearch::Dbscan) at -minpts M (-p; required with dbscan, an error without it); the default is the reference's.
+// -centers 1 (-C; with -linkage single or dbscan only) writes beside the clusters file the centroids of the clusters
+// of at least -minsize m (-m, default 50: the reference's MIN_SIZE_CLUSTER) members as <o>hclust.format.txt and their
+// covering radii as <o>hclust.radii.txt (hsearch::ClusterCenters): the -c / --radii inputs of hs_motif_both_points.
 #include <stdio.h>
 #include <stdlib.h>
 #include <time.h>
@@ -40,6 +43,9 @@ const Opt kOpts[] = {
     {"linkage", 'M', "greedy (the reference's leader clusters) | single (connected components) | dbscan (density "
                      "clusters, needs -minpts) [greedy]", false},
     {"minpts", 'p', "dbscan: neighbours within the threshold, the k-mer itself counted, that make a k-mer dense", false},
+    {"centers", 'C', "1: also write <output>hclust.format.txt (centroids) and <output>hclust.radii.txt (covering radii) "
+                     "of the clusters; with -linkage single or dbscan [0]", false},
+    {"minsize", 'm', "centers: members a cluster needs to get a centre [50]", false},
 };
 void Help(const char* prog) {
   fprintf(stderr, "Usage: %s [OPTIONS]\n\nOptions:\n", prog);
@@ -115,6 +121,32 @@ int main(int argc, const char* argv[]) {
     }
     min_pts = (uint32_t)m;
   }
+  uint32_t centers_min_size = 0;  // 0: no centres
+  if (val.count("centers") && val["centers"] != "0" && val["centers"] != "1") {
+    fprintf(stderr, "ERROR: -centers takes 0 or 1, not '%s'\n", val["centers"].c_str());
+    return EXIT_FAILURE;
+  }
+  const bool centers = val.count("centers") && val["centers"] == "1";
+  if (centers && linkage == "greedy") {
+    fprintf(stderr, "ERROR: -centers goes with -linkage single or dbscan, not with the greedy leader clusters\n");
+    return EXIT_FAILURE;
+  }
+  if (val.count("minsize") && !centers) {
+    fprintf(stderr, "ERROR: -minsize goes with -centers 1 only\n");
+    return EXIT_FAILURE;
+  }
+  if (centers) {
+    centers_min_size = 50;  // MIN_SIZE_CLUSTER, centerDistanceSmapling.cpp:12
+    if (val.count("minsize")) {
+      char* end = nullptr;
+      const unsigned long long m = strtoull(val["minsize"].c_str(), &end, 10);
+      if (end == val["minsize"].c_str() || *end || m < 1 || m > 0xffffffffull || val["minsize"][0] == '-') {
+        fprintf(stderr, "ERROR: -minsize must be a whole number of at least 1, not '%s'\n", val["minsize"].c_str());
+        return EXIT_FAILURE;
+      }
+      centers_min_size = (uint32_t)m;
+    }
+  }
   uint32_t seed;
   if (val.count("seed")) {
     seed = (uint32_t)strtoul(val["seed"].c_str(), nullptr, 10);
@@ -137,10 +169,10 @@ int main(int argc, const char* argv[]) {
     uint64_t n_clusters = 0;
     const int st = linkage == "dbscan"
                        ? hsearch::Dbscan(kmers, hash_K, hash_L, hash_W, hash_R, min_pts, val["output"], planes, device,
-                                         &err, &n_clusters, seed)
+                                         &err, &n_clusters, seed, centers_min_size)
                    : linkage == "single"
                        ? hsearch::Components(kmers, hash_K, hash_L, hash_W, hash_R, val["output"], planes, device, &err,
-                                             &n_clusters, seed)
+                                             &n_clusters, seed, centers_min_size)
                        : hsearch::Clustering(kmers, hash_K, hash_L, hash_W, hash_R, val["output"], planes, device, seed,
                                              &err, &n_clusters);
     if (st != 0) {

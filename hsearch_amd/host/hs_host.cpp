@@ -837,9 +837,72 @@ int ClusterCodes(const std::vector<Kmer>& kmers, uint32_t hash_K, uint32_t hash_
 
 }  // namespace
 
+int ClusterCenters(hs_handle* h, const std::vector<Kmer>& kmers, const std::vector<uint32_t>& label, uint32_t min_size,
+                   const std::string& output_file, std::string* err, uint64_t* n_centers) {
+  hs_params prm;
+  if (!h || hs_get_params(h, &prm) != HS_OK || label.size() != kmers.size()) {
+    if (err) *err = "ClusterCenters: no handle, or not one label per k-mer";
+    return HS_ERR_INVALID;
+  }
+  const uint32_t dim = 8 * prm.k;
+  // one call: n / min_size rows hold every result (include/hsearch.h)
+  if (!min_size) {
+    if (err) *err = "ClusterCenters: min_size must be at least 1";
+    return HS_ERR_INVALID;
+  }
+  const uint64_t room = label.size() / min_size;
+  uint64_t rows = 0;
+  std::vector<uint32_t> row_label(room), row_size(room);
+  std::vector<double> centroid(room * dim);
+  const hs_status pst = hs_cluster_profile(h, label.data(), min_size, row_label.data(), row_size.data(), nullptr,
+                                           centroid.data(), room, &rows);
+  if (pst != HS_OK) {
+    if (err) *err = std::string("hs_cluster_profile: ") + hs_last_error(h);
+    return pst;
+  }
+  std::vector<uint32_t> medoid(rows);
+  std::vector<double> max_d2(rows), radius(rows);
+  std::vector<MotifFamily> families(rows);
+  std::vector<Point> centers(rows);
+  for (uint64_t r = 0; r < rows; ++r) {
+    families[r].name = kmers[row_label[r]].name + ":size" + std::to_string(row_size[r]);
+    centers[r].data.assign(centroid.begin() + r * dim, centroid.begin() + (r + 1) * dim);
+  }
+  if (!Cluster2DataPoint(families, centers, output_file)) {
+    if (err) *err = "cannot write " + output_file + "hclust.format.txt";
+    return HS_ERR_IO;
+  }
+  // the centroids as the points file holds them (6 significant digits): what a search is given as its centres
+  std::vector<std::string> names;
+  std::vector<Point> written;
+  if (!ReadPointsFile(output_file + "hclust.format.txt", dim, &names, &written) || written.size() != rows) {
+    if (err) *err = "cannot read " + output_file + "hclust.format.txt back";
+    return HS_ERR_IO;
+  }
+  std::vector<double> flat(rows * dim);
+  for (uint64_t r = 0; r < rows; ++r) std::copy(written[r].data.begin(), written[r].data.end(), flat.begin() + r * dim);
+  const hs_status st = hs_cluster_radii(h, label.data(), min_size, flat.data(), rows, max_d2.data(), radius.data(), medoid.data());
+  if (st != HS_OK) {
+    if (err) *err = std::string("hs_cluster_radii: ") + hs_last_error(h);
+    return st;
+  }
+  std::ofstream fout((output_file + "hclust.radii.txt").c_str());
+  if (!fout) {
+    if (err) *err = "cannot write " + output_file + "hclust.radii.txt";
+    return HS_ERR_IO;
+  }
+  for (uint64_t r = 0; r < rows; ++r) {
+    char num[64];
+    snprintf(num, sizeof(num), "%.17g", radius[r]);
+    fout << families[r].name << " " << num << std::endl;
+  }
+  if (n_centers) *n_centers = rows;
+  return HS_OK;
+}
+
 int Components(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
                const double& hash_R, const std::string& output_file, const Planes& planes, int device,
-               std::string* err, uint64_t* n_clusters, uint32_t unknown_seed) {
+               std::string* err, uint64_t* n_clusters, uint32_t unknown_seed, uint32_t centers_min_size) {
   std::vector<uint8_t> codes;
   const int cs = ClusterCodes(kmers, hash_K, hash_L, hash_W, planes, unknown_seed, &codes, err);
   if (cs != HS_OK) return cs;
@@ -869,6 +932,13 @@ int Components(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uin
     if (h) hs_destroy(h);
     return st;
   }
+  if (centers_min_size) {
+    const int cc = ClusterCenters(h, kmers, label, centers_min_size, output_file, err);
+    if (cc != HS_OK) {
+      hs_destroy(h);
+      return cc;
+    }
+  }
   hs_destroy(h);
   // a cluster per root in ascending id (= ascending smallest member), members in ascending id
   std::vector<uint32_t> size(n, 0), start(n + 1, 0), slot(n);
@@ -890,7 +960,7 @@ int Components(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uin
 
 int Dbscan(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
            const double& hash_R, const uint32_t& min_pts, const std::string& output_file, const Planes& planes, int device,
-           std::string* err, uint64_t* n_clusters, uint32_t unknown_seed) {
+           std::string* err, uint64_t* n_clusters, uint32_t unknown_seed, uint32_t centers_min_size) {
   std::vector<uint8_t> codes;
   const int cs = ClusterCodes(kmers, hash_K, hash_L, hash_W, planes, unknown_seed, &codes, err);
   if (cs != HS_OK) return cs;
@@ -920,6 +990,13 @@ int Dbscan(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_
     if (err) *err = std::string(what) + ": " + (h ? hs_last_error(h) : "no handle");
     if (h) hs_destroy(h);
     return st;
+  }
+  if (centers_min_size) {
+    const int cc = ClusterCenters(h, kmers, label, centers_min_size, output_file, err);
+    if (cc != HS_OK) {
+      hs_destroy(h);
+      return cc;
+    }
   }
   hs_destroy(h);
   // a cluster per label in ascending id (a label is a core k-mer of its cluster, not always its smallest member:

@@ -19,6 +19,8 @@
 #include <string>
 #include <vector>
 
+struct hs_handle;
+
 namespace hsearch {
 
 struct Point {
@@ -207,7 +209,8 @@ int Clustering(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uin
 // smallest member, members in ascending index; a k-mer without a neighbour is a cluster of size 1.
 int Components(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
                const double& hash_R, const std::string& output_file, const Planes& planes, int device,
-               std::string* err, uint64_t* n_clusters = nullptr, uint32_t unknown_seed = 0);
+               std::string* err, uint64_t* n_clusters = nullptr, uint32_t unknown_seed = 0,
+               uint32_t centers_min_size = 0);
 // Density clusters (DBSCAN, hs_dbscan in include/hsearch.h) of the same graph: only k-mers with at least min_pts
 // neighbours within R (themselves counted) join clusters together, so that one stray k-mer between two families no
 // longer fuses them; a sparse k-mer goes to the cluster of its dense neighbour with the smallest index or is noise.
@@ -216,7 +219,18 @@ int Components(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uin
 // ascending index.  *n_clusters does not count that block.
 int Dbscan(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
            const double& hash_R, const uint32_t& min_pts, const std::string& output_file, const Planes& planes, int device,
-           std::string* err, uint64_t* n_clusters = nullptr, uint32_t unknown_seed = 0);
+           std::string* err, uint64_t* n_clusters = nullptr, uint32_t unknown_seed = 0, uint32_t centers_min_size = 0);
+// centers_min_size != 0 (Components, Dbscan): beside the clusters file, ClusterCenters() of the labels just found.
+// From cluster labels to the `-c` / `--radii` inputs of motif_both_points, on the handle that holds the k-mers'
+// index: label [n] as hs_components / hs_dbscan return it (HS_NOISE or a value < n).  Per cluster of at least min_size
+// members, in ascending label, <output_file>hclust.format.txt receives its centroid (hs_cluster_profile) in
+// Cluster2DataPoint's format -- the name line is "<name of k-mer `label`>:size<members>" (ReadKmerFasta's names are
+// whitespace-free tokens, so the line holds no space and "<name> <radius>" splits at its only one) -- and
+// <output_file>hclust.radii.txt "<that name> <radius>" with 17 significant digits.  The radii are taken as FamilyRadii
+// takes them: against the centroids AS WRITTEN and read back (hs_cluster_radii with the read-back points), so that a
+// search given both files reports every member of every cluster.  Returns 0 or an hs_status with *err set.
+int ClusterCenters(hs_handle* h, const std::vector<Kmer>& kmers, const std::vector<uint32_t>& label, uint32_t min_size,
+                   const std::string& output_file, std::string* err, uint64_t* n_centers = nullptr);
 
 // evaulate() (:100-165) with weight() (:67-87): weighted recall of a hits file against a ground
 // truth file sorted by (motif, protein); also writes <output_file>.accuracy.txt.  Returns NaN

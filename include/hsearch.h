@@ -171,6 +171,9 @@ typedef enum hs_option {
                                 every bucket int of the table within 16 bits; 0: the directory arrays */
   HS_OPT_JOIN_CHUNK = 18,    /* work items a wave of hs_join8x_kernel takes per access to the item counters (2..64);
                                 0 (default): from the previous batch's pairs per item */
+  HS_OPT_SUMMARY_CHUNK = 19, /* hs_cluster_profile / hs_cluster_radii: member slots per work item (1 .. 2^20); 0 (default): 512 */
+  HS_OPT_SUMMARY_ROWS = 20,  /* hs_cluster_profile: rows per batch; 0 (default): as many as a fixed scratch budget of
+                                32 MB of counts holds */
   HS_OPT_JOIN_XCD_RUN = 16   /* hs_join8x_kernel's work items dealt in runs of this many chunks per XCD, each XCD's
                                 waves on their own runs (a run's items stream the same query tiles: one L2 fetches
                                 them instead of eight).  0: one counter for the chip; -1 (default): by the size
@@ -581,6 +584,76 @@ HS_API hs_status hs_dbscan_dev(hs_handle* h, double R, int sqrt_test, uint32_t m
  * hs_self_join_range edges, then call it. */
 HS_API hs_status hs_dbscan_edges(const uint32_t* ei, const uint32_t* ej, uint64_t n_edges, uint64_t n,
                                  uint32_t min_pts, uint32_t* label, uint32_t* degree, hs_dbscan_counts* out);
+
+/* ---- cluster profiles, centroids and covering radii from a label array ------------------------------------ */
+
+/* The step from cluster labels to what a search takes: per cluster its members' position frequency matrix, their
+ * centroid (Center(), centerDistanceSmapling.cpp:67-78) and the radius that makes every member a hit of a centre (the
+ * reference's cluster.radius, hclust.cpp:217-222), reduced on the device from the index's codes and a label array.
+ *
+ * Inputs: a built index (n k-mers) and label [n].  label[i] is HS_NOISE or a value < n; the value need not be a
+ * member's id nor the smallest one: the labels of hs_components, of hs_dbscan and owner[] of hs_clustering over the
+ * same codes are all legal.  Any other value is HS_ERR_INVALID, reported before any output is written (the _dev forms
+ * detect it on the device, as hs_query_radii_dev detects a NaN radius).  min_size >= 1; 0 is HS_ERR_INVALID.  An
+ * unbuilt index is HS_ERR_STATE.
+ *
+ * Clusters and rows: a cluster is the set of i with one label value.  The clusters with at least min_size members
+ * are the rows of the output, in ascending label value; *n_out is their number.  Capacity, counted in ROWS, follows
+ * the two-call pattern (HS_ERR_CAPACITY with *n_out set; cap = 0 with null arrays asks for the count), and
+ * *n_out <= n / min_size always.
+ *
+ * hs_cluster_profile, per row:
+ *   out_label, out_size
+ *   counts   [row][k][alphabet] uint32 (may be NULL): the number of members with code a at position p
+ *   centroid [row][d] fp64: the coordinate p * 8 + c is S / (double)size, where S starts at +0.0 and, for
+ *            a = 0 .. alphabet - 1 in ascending order, gains (double)count[p][a] * coords[a][c] -- every product and
+ *            every sum rounded to fp64, no contraction into FMA -- and one division follows.
+ * This is Center() with the member-order sum replaced by an order-free one: it agrees with hsearch::FamilyCenters
+ * only UP TO ROUNDING.  Both lie within gamma_m * M of the exact mean, m = size + alphabet,
+ * gamma_m = m 2^-53 / (1 - m 2^-53), M = max |coords|; they differ by at most 2 gamma_m M.
+ *
+ * hs_cluster_radii: the same labels and min_size plus centers [n_rows][d], any FINITE points -- the profile's
+ * centroids, the centroids as a points file holds them (6 significant digits), medoids' embeddings.  (Finite is a
+ * decision of this contract: max and min run on the d2 bit patterns, which order like the doubles only where no d2
+ * is a NaN.  A NaN or infinite coordinate in a centre leaves that row's max_d2, radius and medoid unspecified and
+ * every other row as it is.)  n_rows must be
+ * the row count the labels give, else HS_ERR_INVALID.  Per member d2 = sum over t of (x[t] - centre[t])^2, left to
+ * right in fp64 (PairwiseDistance_square, and the exact pass of the searches).  Per row:
+ *   max_d2   the largest member d2
+ *   radius   the smallest double r with r * r >= max_d2: r = sqrt(max_d2) correctly rounded, then the next double up
+ *            if r * r < max_d2 (hsearch::RadiusCovering).  With it hs_query_radii's d2 <= r * r and the sqrt tests
+ *            both accept the farthest member
+ *   medoid   the member smallest under (d2, id), d2 compared as doubles
+ * Counts are integers, max and min are order-free: every output is a pure function of (codes, labels, min_size,
+ * centres) and bit-reproducible, whatever HS_OPT_SUMMARY_CHUNK / HS_OPT_SUMMARY_ROWS say.
+ *
+ * State: 36 bytes per indexed k-mer in the handle (28 for hs_cluster_profile alone; allocated by the first such call,
+ * kept with the handle, reset at the start of every call), plus at most 32 MB of scratch for the counts of a batch of
+ * rows when counts == NULL -- never more, however many rows there are: rows are processed in batches.
+ * Every other entry point runs as before, launch for launch; the handle's multi-probe setting and bucket partition
+ * play no part here. */
+HS_API hs_status hs_cluster_profile(hs_handle* h, const uint32_t* label, uint32_t min_size, uint32_t* out_label,
+                                    uint32_t* out_size, uint32_t* counts, double* centroid, uint64_t cap,
+                                    uint64_t* n_out);
+HS_API hs_status hs_cluster_radii(hs_handle* h, const uint32_t* label, uint32_t min_size, const double* centers,
+                                  uint64_t n_rows, double* max_d2, double* radius, uint32_t* medoid);
+/* ... every array in device memory, the counts and statuses on the host (streams: as hs_query_dev) */
+HS_API hs_status hs_cluster_profile_dev(hs_handle* h, const uint32_t* d_label, uint32_t min_size, uint32_t* d_out_label,
+                                        uint32_t* d_out_size, uint32_t* d_counts, double* d_centroid, uint64_t cap,
+                                        uint64_t* n_out);
+HS_API hs_status hs_cluster_radii_dev(hs_handle* h, const uint32_t* d_label, uint32_t min_size, const double* d_centers,
+                                      uint64_t n_rows, double* d_max_d2, double* d_radius, uint32_t* d_medoid);
+/* Both rules on the host (no GPU, no handle) for codes [n][k], coords [alphabet][8] (NULL: the default table, alphabet
+ * 0 or 20) and label [n]: bit-identical to the device forms.  counts may be NULL; max_d2 / radius / medoid are all
+ * given or all NULL (no radii); centers == NULL: the radii are taken against the call's own centroids, else against
+ * centers [n_center_rows][d] (n_center_rows must be the row count).  A code >= alphabet, an illegal label, min_size 0,
+ * k outside 1 .. 75 are HS_ERR_INVALID, reported before anything is written.  This is the route for label shares
+ * gathered from several GPUs. */
+HS_API hs_status hs_cluster_summary_codes(const uint8_t* codes, uint64_t n, uint32_t k, const double* coords,
+                                          uint32_t alphabet, const uint32_t* label, uint32_t min_size,
+                                          const double* centers, uint64_t n_center_rows, uint32_t* out_label,
+                                          uint32_t* out_size, uint32_t* counts, double* centroid, double* max_d2,
+                                          double* radius, uint32_t* medoid, uint64_t cap, uint64_t* n_out);
 
 /* Replaces Clustering() (hclust2.cpp:86-151) with explicit planes a[L][K][d], b[L][K]: table by
  * table, an LSH table over the not-yet-absorbed k-mers, then greedy leader clustering inside every
