@@ -27,7 +27,7 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_components_range", "hs_components_range_dev", "hs_components_merge", "hs_degrees", "hs_degrees_dev",
            "hs_degrees_range", "hs_degrees_range_dev", "hs_dbscan", "hs_dbscan_dev", "hs_dbscan_edges",
            "hs_cluster_profile", "hs_cluster_profile_dev", "hs_cluster_radii", "hs_cluster_radii_dev",
-           "hs_cluster_summary_codes"]
+           "hs_cluster_summary_codes", "hs_msf", "hs_msf_dev", "hs_msf_edges", "hs_msf_cut"]
 
 NOISE = 0xffffffff   # HS_NOISE: the label of a k-mer that is neither core nor border (hs_dbscan)
 
@@ -64,6 +64,11 @@ class _IndexInfo(C.Structure):
 class _DbscanCounts(C.Structure):
     _fields_ = [("n_clusters", C.c_uint64), ("n_core", C.c_uint64), ("n_border", C.c_uint64),
                 ("n_noise", C.c_uint64), ("n_edges", C.c_uint64)]
+
+
+class _MsfInfo(C.Structure):
+    _fields_ = [("n_tree_edges", C.c_uint64), ("n_components", C.c_uint64), ("n_graph_edges", C.c_uint64),
+                ("rounds", C.c_uint32), ("resident", C.c_uint32)]
 
 
 profile_fields = [f[0] for f in _Profile._fields_]
@@ -170,6 +175,19 @@ def load(hooks=False):
                                                      C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        # spanning forest: msf (h, R, sqrt_test, lo, hi, dist, cap, label, info); msf_edges (ei, ej, dist, n_edges, n,
+        # out_lo, out_hi, out_dist, cap, label, info); msf_cut (lo, hi, dist, m, n, r, label, n_components)
+        if hasattr(lib, "hs_msf"):
+            for fn in (lib.hs_msf, lib.hs_msf_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                               C.c_void_p, C.POINTER(_MsfInfo)]
+            lib.hs_msf_edges.restype = C.c_int
+            lib.hs_msf_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(_MsfInfo)]
+            lib.hs_msf_cut.restype = C.c_int
+            lib.hs_msf_cut.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_double,
+                                       C.c_void_p, C.POINTER(C.c_uint64)]
         _libs[hooks] = lib
     return _libs[hooks]
 
@@ -282,6 +300,60 @@ def dbscan_edges(ei, ej, n, min_pts, want_degree=False):
     if want_degree:
         res["degree"] = degree
     return res
+
+
+def _msf_dict(info, lo, hi, dist, label):
+    m = int(info.n_tree_edges)
+    res = dict(lo=lo[:m], hi=hi[:m], dist=dist[:m], **{f[0]: int(getattr(info, f[0])) for f in _MsfInfo._fields_})
+    if label is not None:
+        res["label"] = label
+    return res
+
+
+def msf_edges(ei, ej, dist, n, want_label=False, cap=None):
+    """hs_msf_edges (host only, no GPU): the minimum spanning forest, under the order (dist, lo, hi), of any list of
+    weighted pairs (ei[t], ej[t], dist[t]) over n vertices -- either or both directions, repeated, in any order, self
+    pairs ignored -> dict(lo, hi, dist: the tree edges in ascending (dist, lo, hi) with lo < hi; label if asked;
+    n_tree_edges, n_components, n_graph_edges = twice the distinct pairs, rounds = resident = 0).  The forest of the
+    concatenation of several forests is the forest of the union of their graphs (the merge of ranks' results).
+    cap=None: room for every result; a given cap that is too small raises HsError(HS_ERR_CAPACITY) with .needed."""
+    ei = np.ascontiguousarray(ei, dtype=np.uint32)
+    ej = np.ascontiguousarray(ej, dtype=np.uint32)
+    dist = np.ascontiguousarray(dist, dtype=np.float64)
+    assert ei.ndim == 1 and ei.shape == ej.shape == dist.shape
+    n = int(n)
+    room = n if cap is None else int(cap)
+    lo = np.empty(room, dtype=np.uint32)
+    hi = np.empty(room, dtype=np.uint32)
+    od = np.empty(room, dtype=np.float64)
+    label = np.empty(n, dtype=np.uint32) if want_label else None
+    info = _MsfInfo()
+    st = load().hs_msf_edges(_vp(ei), _vp(ej), _vp(dist), len(ei), n, _vp(lo), _vp(hi), _vp(od), room,
+                             _vp(label) if want_label else None, C.byref(info))
+    if st != HS_OK:
+        e = HsError(st, "hs_msf_edges")
+        e.needed = int(info.n_tree_edges)
+        raise e
+    return _msf_dict(info, lo, hi, od, label)
+
+
+def msf_cut(tree, r, n=None, out=None):
+    """hs_msf_cut (host only, no GPU): tree = a dict with lo, hi, dist as Engine.msf / msf_edges return them (n from its
+    label, or given) -> dict(label uint32 [n] = the smallest id per component of the forest of the tree edges with
+    dist <= r, n_components).  out: a uint32 [n] array to write into (untouched when the input is invalid)."""
+    lo = np.ascontiguousarray(tree["lo"], dtype=np.uint32)
+    hi = np.ascontiguousarray(tree["hi"], dtype=np.uint32)
+    dist = np.ascontiguousarray(tree["dist"], dtype=np.float64)
+    assert lo.ndim == 1 and lo.shape == hi.shape == dist.shape
+    n = len(tree["label"]) if n is None else int(n)
+    if out is None:
+        out = np.empty(n, dtype=np.uint32)
+    assert out.dtype == np.uint32 and out.shape == (n,) and out.flags["C_CONTIGUOUS"]
+    nc = C.c_uint64(0)
+    st = load().hs_msf_cut(_vp(lo), _vp(hi), _vp(dist), len(lo), n, float(r), _vp(out), C.byref(nc))
+    if st != HS_OK:
+        raise HsError(st, "hs_msf_cut")
+    return dict(label=out, n_components=int(nc.value))
 
 
 def cluster_summary_codes(codes, label, min_size=1, coords=None, centers=None, want_counts=False, want_radii=True,
@@ -424,7 +496,8 @@ class Engine:
     OPTIONS = {"query_batch": 1, "seg_mode": 2, "join_resident": 3, "recognise_kmers": 4, "build_grouping": 5,
                "wide_rows": 6, "refine8": 7, "self_codes": 8, "sort_hits": 10, "sync_items": 11,
                "join_min_q": 12, "join_min_m": 13, "sort_from_bit": 14, "build_serial": 15,
-               "join_xcd_run": 16, "probe_records": 17, "join_chunk": 18, "summary_chunk": 19, "summary_rows": 20}
+               "join_xcd_run": 16, "probe_records": 17, "join_chunk": 18, "summary_chunk": 19, "summary_rows": 20,
+               "msf_edge_budget": 21}
 
     def set_option(self, name, value):
         """hs_set_option (include/hsearch.h hs_option): path selection / batch sizing; never changes a result."""
@@ -895,6 +968,35 @@ class Engine:
         self._check(self._lib.hs_dbscan_dev(self._h, float(R), 1 if sqrt_test else 0, int(min_pts), d_label_ptr,
                                             d_degree_ptr, C.byref(c)))
         return _counts_dict(c)
+
+    def msf(self, R, sqrt_test=True, want_label=False):
+        """hs_msf: the minimum spanning forest -- the single-linkage tree up to R -- of the graph self_join(R, sqrt_test)
+        returns, found on the device: dict(lo, hi, dist: the n - n_components tree edges in ascending (dist, lo, hi)
+        = the merge order, lo < hi; label (= components(R, sqrt_test)["label"]) if asked; n_tree_edges, n_components,
+        n_graph_edges = len(self_join(...)["i"]), rounds, resident).  capi.msf_cut(tree, r) cuts it at a radius."""
+        n = self._n()
+        lo = np.empty(n, dtype=np.uint32)
+        hi = np.empty(n, dtype=np.uint32)
+        dist = np.empty(n, dtype=np.float64)
+        label = np.empty(n, dtype=np.uint32) if want_label else None
+        info = _MsfInfo()
+        self._check(self._lib.hs_msf(self._h, float(R), 1 if sqrt_test else 0, _vp(lo), _vp(hi), _vp(dist), n,
+                                     _vp(label) if want_label else None, C.byref(info)))
+        return _msf_dict(info, lo, hi, dist, label)
+
+    def msf_dev(self, d_lo_ptr, d_hi_ptr, d_dist_ptr, cap, R, sqrt_test=True, d_label_ptr=None):
+        """hs_msf_dev: the tree edges into uint32 / uint32 / float64 [cap] device memory and, with d_label_ptr, the labels
+        into uint32 [n] (pointers as ints); returns the dict of the counts (n_tree_edges, ...).  A cap that is too small
+        raises HsError(HS_ERR_CAPACITY) with the required size in .needed; none of the arrays, the labels included, is
+        written then."""
+        info = _MsfInfo()
+        st = self._lib.hs_msf_dev(self._h, float(R), 1 if sqrt_test else 0, d_lo_ptr, d_hi_ptr, d_dist_ptr, int(cap),
+                                  d_label_ptr, C.byref(info))
+        if st != HS_OK:
+            e = HsError(st, self._lib.hs_last_error(self._h).decode())
+            e.needed = int(info.n_tree_edges)
+            raise e
+        return {f[0]: int(getattr(info, f[0])) for f in _MsfInfo._fields_}
 
     def cluster_profile(self, label, min_size=1, want_counts=False, cap=None):
         """hs_cluster_profile: the clusters of label uint32 [n] (NOISE or a value < n: the labels of components(),

@@ -101,6 +101,7 @@ struct Knobs {
   uint32_t query_batch = 0;        // HS_OPT_QUERY_BATCH: queries per batch (0: by L and the free HBM)
   uint32_t summary_chunk = 0;      // HS_OPT_SUMMARY_CHUNK: member slots per work item of hs_summary.hip (0: 512)
   uint32_t summary_rows = 0;       // HS_OPT_SUMMARY_ROWS: rows per batch of hs_cluster_profile (0: by the scratch budget)
+  int64_t msf_edge_budget = -1;    // HS_OPT_MSF_EDGE_BUDGET: bytes of HBM hs_msf may keep pairs in (0 never, -1 a share of the free)
 #ifdef HS_TEST_HOOKS
   uint32_t test_split_above = 0;   // HS_TEST_SPLIT_ABOVE: batches above this size report a survivor overflow
   bool test_group_fallback = false;  // HS_TEST_GROUP_FALLBACK: the build's fingerprint table reports itself full
@@ -114,8 +115,10 @@ struct Knobs {
 //   CC_UNION   hs_components: a self-join's pairs united in the handle's union-find forest
 //   DB_DEGREE  hs_degrees / hs_dbscan pass 1 (hs_dbscan.hip): a self-join's pairs counted into the degree array
 //   DB_UNITE   hs_dbscan pass 2: the degrees known, the pairs united and anchored at min_pts
+//   MSF_MIN_D, MSF_MIN_PAIR   hs_msf (hs_msf.hip): steps 1 and 2 of a Boruvka round over a self-join's pairs
+//   MSF_COLLECT               hs_msf's first pass: step 1, and the pairs appended to the list kept in HBM
 struct HitSink {
-  enum Kind { LIST, ANNOTATE, CC_UNION, DB_DEGREE, DB_UNITE } kind = LIST;
+  enum Kind { LIST, ANNOTATE, CC_UNION, DB_DEGREE, DB_UNITE, MSF_MIN_D, MSF_MIN_PAIR, MSF_COLLECT } kind = LIST;
   uint32_t min_pts = 1;
 };
 
@@ -223,6 +226,12 @@ struct hs_handle {
   // hs_degrees / hs_dbscan (hs_dbscan.hip): the degree and the smallest core neighbour per indexed k-mer (the forest
   // is cc_parent: every call starts it from the identity), and the call's five 64-bit counts
   DevBuf db_deg, db_anchor, db_cnt;
+  // hs_msf (hs_msf.hip: the state listed at its head; the forest is cc_parent): the components of the round, the two
+  // slots per component, the tree edges and their sorted copy, the call's counts; the list of pairs kept in HBM, the
+  // entries the call may keep (HS_OPT_MSF_EDGE_BUDGET) and whether the list could not grow to hold a batch
+  DevBuf msf_comp, msf_best_d, msf_best_pair, msf_out_pair, msf_out_d, msf_s_pair, msf_s_d, msf_cnt, msf_kept;
+  uint64_t msf_kept_budget = 0;
+  bool msf_kept_failed = false;
   // hs_cluster_profile / hs_cluster_radii (hs_summary.hip: the state listed at its head), the counts of a row batch
   // when the caller wants none, and the arrays of a host-pointer call on their way in and out
   DevBuf sm_size, sm_tmp, sm_row_of, sm_off_of, sm_row_label, sm_row_off, sm_member, sm_d2, sm_err, sm_counts;
@@ -485,7 +494,8 @@ const struct { const char* name; int option; } kOptionNames[] = {
     {"sort_hits", HS_OPT_SORT_HITS}, {"sync_items", HS_OPT_SYNC_ITEMS}, {"join_min_q", HS_OPT_JOIN_MIN_Q},
     {"join_min_m", HS_OPT_JOIN_MIN_M}, {"sort_from_bit", HS_OPT_SORT_FROM_BIT}, {"build_serial", HS_OPT_BUILD_SERIAL},
     {"join_xcd_run", HS_OPT_JOIN_XCD_RUN}, {"probe_records", HS_OPT_PROBE_RECORDS},
-    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS}};
+    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS},
+    {"msf_edge_budget", HS_OPT_MSF_EDGE_BUDGET}};
 
 void read_knobs(hs_handle* h) {
   Knobs& kn = h->knobs;
@@ -791,6 +801,10 @@ hs_status hs_set_option(hs_handle* h, int option, int64_t value) {
       if (value < 0 || value >= (1ll << 31)) break;
       kn.summary_rows = (uint32_t)value;
       return HS_OK;
+    case HS_OPT_MSF_EDGE_BUDGET:
+      if (value < -1) break;
+      kn.msf_edge_budget = value;
+      return HS_OK;
     case HS_OPT_JOIN_XCD_RUN:
       if (value < -1 || value > 4096 || (value > 0 && (value & (value - 1)))) break;  // a power of two
       kn.join_xcd_run = (int)value;
@@ -831,7 +845,8 @@ void hs_destroy(hs_handle* h) {
                     &h->mp_vints, &h->mp_valid, &h->mp_rows, &h->mp_q, &h->mp_id, &h->mp_table, &h->mp_dist,
                     &h->mp_cand, &h->mp_radii, &h->io_radii, &h->ann_dist, &h->ann_tq, &h->ann_touched,
                     &h->ann_sorted, &h->ann_cnt, &h->cc_parent, &h->cc_cnt, &h->cc_label,
-                    &h->db_deg, &h->db_anchor, &h->db_cnt, &h->sm_size, &h->sm_tmp, &h->sm_row_of, &h->sm_off_of,
+                    &h->db_deg, &h->db_anchor, &h->db_cnt, &h->msf_comp, &h->msf_best_d, &h->msf_best_pair,
+                    &h->msf_out_pair, &h->msf_out_d, &h->msf_s_pair, &h->msf_s_d, &h->msf_cnt, &h->msf_kept, &h->sm_size, &h->sm_tmp, &h->sm_row_of, &h->sm_off_of,
                     &h->sm_row_label, &h->sm_row_off, &h->sm_member, &h->sm_d2, &h->sm_err, &h->sm_counts,
                     &h->sm_io_label, &h->sm_io_a, &h->sm_io_b, &h->sm_io_counts, &h->sm_io_f64, &h->sm_io_f64b};
   for (DevBuf* bf : bufs) bf->release();
@@ -2901,6 +2916,40 @@ static hs_status annot_reduce(hs_handle* h, const uint64_t* d_key, const uint64_
 // once -- and hit_key holds each ordered pair once (the first-seen rule across the tables has run; the tests pin
 // n_edges == len(self_join)).  DB_DEGREE depends on it: it is NOT idempotent, a pair counted twice is a wrong
 // degree.  The other three would forgive a repeat (union, min and the nearest-centre steps are idempotent).
+// MSF_COLLECT: step 1 over the batch, its pairs with a < b appended to the kept list.  The list grows to hold them: the
+// batch brings at most nh entries on top of those counted so far (read back here: the stream is idle between
+// batches), never beyond the call's budget.  A list that cannot hold its pairs is not an error: the kernel stops
+// appending, the counter keeps running, and hs_msf goes on without the list.
+static hs_status msf_collect_batch(hs_handle* h, const QueryCall& c, uint32_t nh) {
+  if (!nh) return HS_OK;
+  uint64_t* const cnt = h->msf_cnt.as<uint64_t>();
+  uint64_t kept = 0;
+  HS_HIP(h, hipMemcpyAsync(&kept, cnt + 2, 8, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  const uint64_t budget = h->msf_kept_budget, have = h->msf_kept.cap / 16;
+  const uint64_t need = std::min<uint64_t>(budget, kept + nh);
+  if (need > have && kept <= have && !h->msf_kept_failed) {
+    DevBuf bigger;
+    const uint64_t entries = std::min<uint64_t>(budget, std::max<uint64_t>(need, 2 * have));
+    if (bigger.reserve((size_t)entries * 16) != hipSuccess) {
+      (void)hipGetLastError();
+      h->msf_kept_failed = true;
+    } else {
+      hipError_t e = hipSuccess;
+      if (kept) e = hipMemcpyAsync(bigger.p, h->msf_kept.p, (size_t)kept * 16, hipMemcpyDeviceToDevice, h->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+      if (e != hipSuccess) bigger.release();  // (DevBuf has no destructor)
+      HS_HIP(h, e);
+      h->msf_kept.release();
+      h->msf_kept = bigger;
+    }
+  }
+  HS_HIP(h, hs_launch_msf_min_d_hits(h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(), nh, c.self_first,
+                                     h->msf_comp.as<uint32_t>(), h->msf_best_d.as<uint64_t>(), (uint32_t)h->n, cnt,
+                                     h->msf_kept.p, std::min<uint64_t>(budget, h->msf_kept.cap / 16), h->stream));
+  return HS_OK;
+}
+
 static hs_status reduce_batch(hs_handle* h, const QueryCall& c, uint32_t nh) {
   const uint64_t* const pairs = h->hit_key.as<uint64_t>();
   const uint32_t n = (uint32_t)h->n;
@@ -2921,6 +2970,18 @@ static hs_status reduce_batch(hs_handle* h, const QueryCall& c, uint32_t nh) {
       HS_HIP(h, hs_launch_db_unite(pairs, nh, c.self_first, h->db_deg.as<uint32_t>(), c.sink.min_pts,
                                    h->cc_parent.as<uint32_t>(), h->db_anchor.as<uint32_t>(), n, h->stream));
       break;
+    case HitSink::MSF_MIN_D:
+      HS_HIP(h, hs_launch_msf_min_d_hits(pairs, h->hit_val.as<uint64_t>(), nh, c.self_first, h->msf_comp.as<uint32_t>(),
+                                         h->msf_best_d.as<uint64_t>(), n, h->msf_cnt.as<uint64_t>(), nullptr, 0,
+                                         h->stream));
+      break;
+    case HitSink::MSF_MIN_PAIR:  // the slots' distances are final (step 1 ended at a kernel boundary)
+      HS_HIP(h, hs_launch_msf_min_pair_hits(pairs, h->hit_val.as<uint64_t>(), nh, c.self_first,
+                                            h->msf_comp.as<uint32_t>(), h->msf_best_d.as<uint64_t>(),
+                                            h->msf_best_pair.as<uint64_t>(), n, h->stream));
+      break;
+    case HitSink::MSF_COLLECT:
+      return msf_collect_batch(h, c, nh);
   }
   return HS_OK;
 }
@@ -3814,6 +3875,130 @@ hs_status hs_dbscan(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, uin
 hs_status hs_dbscan_dev(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, uint32_t* d_label, uint32_t* d_degree,
                         hs_dbscan_counts* out) {
   return dbscan_any(h, R, sqrt_test, min_pts, d_label, d_degree, out, true);
+}
+
+// ---- hs_msf: the minimum spanning forest of the self-join's graph (kernels, the round and the invariant: hs_msf.hip) ----
+// Boruvka rounds over the pairs of the full self-join: kept in HBM by the first pass when the budget allows, from a
+// reduced self-join per pass otherwise.  The m <= n - 1 tree edges, ordered by (dist, lo, hi), go to d_lo / d_hi /
+// d_dist (device, room for cap), the labels to d_label (device, may be null).
+static hs_status msf_run(hs_handle* h, double R, int sqrt_test, uint32_t* d_lo, uint32_t* d_hi, double* d_dist,
+                         uint64_t cap, uint32_t* d_label, hs_msf_info* out) {
+  if (!(R == R)) return fail(h, HS_ERR_INVALID, "R is NaN");
+  const uint32_t n = (uint32_t)h->n;
+  const size_t w4 = std::max<size_t>(16, (size_t)n * 4), w8 = std::max<size_t>(16, (size_t)n * 8);
+  HS_HIP(h, h->msf_comp.reserve(w4));
+  HS_HIP(h, h->cc_parent.reserve(w4));
+  for (DevBuf* bf : {&h->msf_best_d, &h->msf_best_pair, &h->msf_out_pair, &h->msf_out_d, &h->msf_s_pair, &h->msf_s_d})
+    HS_HIP(h, bf->reserve(w8));
+  HS_HIP(h, h->msf_cnt.reserve(64));
+  uint32_t* const comp = h->msf_comp.as<uint32_t>();
+  uint32_t* const parent = h->cc_parent.as<uint32_t>();
+  uint64_t* const best_d = h->msf_best_d.as<uint64_t>();
+  uint64_t* const best_pair = h->msf_best_pair.as<uint64_t>();
+  uint64_t* const cnt = h->msf_cnt.as<uint64_t>();
+  // the entries the call may keep: the option's bytes, or a quarter of what is free now
+  uint64_t budget = 0;
+  if (h->knobs.msf_edge_budget < 0) {
+    size_t free_b = 0, total_b = 0;
+    HS_HIP(h, hipMemGetInfo(&free_b, &total_b));
+    budget = free_b / 4 / 16;
+  } else {
+    budget = (uint64_t)h->knobs.msf_edge_budget / 16;
+  }
+  h->msf_kept_budget = budget;
+  h->msf_kept_failed = false;
+  HS_HIP(h, hs_launch_msf_begin(comp, parent, best_d, best_pair, n, cnt, h->stream));
+  hs_profile acc = {};
+  HS_CHECK(reduced_self_join(h, 0, n, R, sqrt_test, {budget ? HitSink::MSF_COLLECT : HitSink::MSF_MIN_D}, &acc));
+  uint64_t c[5] = {0, 0, 0, 0, 0};
+  HS_HIP(h, hipMemcpyAsync(c, cnt, 40, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  const uint64_t n_pairs = c[0];
+  const bool resident = budget && !h->msf_kept_failed && c[2] <= std::min<uint64_t>(budget, h->msf_kept.cap / 16);
+  const uint64_t n_kept = resident ? c[2] : 0;
+  if (!resident) h->msf_kept.release();  // (a list that overflowed is dropped; the call goes on from the self-joins)
+  uint32_t rounds = 0;
+  for (uint64_t cross = c[1]; cross;) {
+    if (rounds == HS_MSF_MAX_ROUNDS)
+      return fail(h, HS_ERR_STATE, "hs_msf: pairs still cross components after 34 rounds (internal error)");
+    if (resident)
+      HS_HIP(h, hs_launch_msf_min_pair_kept(h->msf_kept.p, n_kept, comp, best_d, best_pair, n, h->stream));
+    else
+      HS_CHECK(reduced_self_join(h, 0, n, R, sqrt_test, {HitSink::MSF_MIN_PAIR}, &acc));
+    HS_HIP(h, hs_launch_msf_select(comp, parent, best_d, best_pair, n, h->msf_out_pair.as<uint64_t>(),
+                                   h->msf_out_d.as<uint64_t>(), cnt, h->stream));
+    ++rounds;
+    HS_HIP(h, hipMemsetAsync(cnt, 0, 16, h->stream));
+    if (resident)
+      HS_HIP(h, hs_launch_msf_min_d_kept(h->msf_kept.p, n_kept, comp, best_d, n, cnt, h->stream));
+    else
+      HS_CHECK(reduced_self_join(h, 0, n, R, sqrt_test, {HitSink::MSF_MIN_D}, &acc));
+    HS_HIP(h, hipMemcpyAsync(&cross, cnt + 1, 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  // the roots counted; the caller's labels are written behind the capacity verdict only
+  HS_HIP(h, hs_launch_msf_finish(comp, n, nullptr, cnt, h->stream));
+  HS_HIP(h, hipMemcpyAsync(c, cnt, 40, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  const uint64_t m = c[3];
+  h->prof = acc;
+  h->prof.hits = n_pairs;
+  if (m + c[4] != n) return fail(h, HS_ERR_STATE, "hs_msf: tree edges and components do not add up (internal error)");
+  out->n_tree_edges = m;
+  out->n_components = c[4];
+  out->n_graph_edges = n_pairs;
+  out->rounds = rounds;
+  out->resident = resident ? 1u : 0u;
+  if (m > cap) return fail(h, HS_ERR_CAPACITY, "edge buffers too small; see out->n_tree_edges");
+  if (d_label && n) HS_HIP(h, hipMemcpyAsync(d_label, comp, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
+  if (m) {
+    // (dist, lo, hi): two stable 64-bit radix sorts over all 64 bits -- by pair, then by the distance bits
+    uint64_t* const op = h->msf_out_pair.as<uint64_t>();
+    uint64_t* const od = h->msf_out_d.as<uint64_t>();
+    uint64_t* const sp = h->msf_s_pair.as<uint64_t>();
+    uint64_t* const sd = h->msf_s_d.as<uint64_t>();
+    HS_HIP(h, h->temp.reserve(hs_sort_pairs_u64_u64_temp(m) + 256));
+    HS_HIP(h, hs_sort_pairs_u64_u64(h->temp.p, h->temp.cap, op, sp, od, sd, m, 64, h->stream));
+    HS_HIP(h, hs_sort_pairs_u64_u64(h->temp.p, h->temp.cap, sd, od, sp, op, m, 64, h->stream));
+    HS_HIP(h, hs_launch_msf_unpack(op, od, (uint32_t)m, d_lo, d_hi, d_dist, h->stream));
+  }
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return HS_OK;
+}
+
+static hs_status msf_any(hs_handle* h, double R, int sqrt_test, uint32_t* edge_lo, uint32_t* edge_hi, double* edge_dist,
+                         uint64_t cap, uint32_t* label, hs_msf_info* out, bool dev) {
+  if (!h || !out) return HS_ERR_INVALID;
+  memset(out, 0, sizeof(*out));
+  HS_CHECK(self_join_check(h, 0, h->n, !cap || (edge_lo && edge_hi && edge_dist)));
+  if (dev) return msf_run(h, R, sqrt_test, edge_lo, edge_hi, edge_dist, cap, label, out);
+  // host pointers: through the handle's I/O buffers; 16 bytes per tree edge and 4 per label cross PCIe
+  const size_t room = (size_t)std::min<uint64_t>(cap, h->n);
+  HS_HIP(h, h->io_q.reserve(std::max<size_t>(16, room * 4)));
+  HS_HIP(h, h->io_id.reserve(std::max<size_t>(16, room * 4)));
+  HS_HIP(h, h->io_dist.reserve(std::max<size_t>(16, room * 8)));
+  if (label) HS_HIP(h, h->cc_label.reserve(std::max<size_t>(16, (size_t)h->n * 4)));
+  HS_CHECK(msf_run(h, R, sqrt_test, h->io_q.as<uint32_t>(), h->io_id.as<uint32_t>(), h->io_dist.as<double>(), room,
+                   label ? h->cc_label.as<uint32_t>() : nullptr, out));
+  const size_t m = (size_t)out->n_tree_edges;
+  if (m) {
+    HS_HIP(h, hipMemcpyAsync(edge_lo, h->io_q.p, m * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(edge_hi, h->io_id.p, m * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(edge_dist, h->io_dist.p, m * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (label && h->n) HS_HIP(h, hipMemcpyAsync(label, h->cc_label.p, (size_t)h->n * 4, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return HS_OK;
+}
+
+hs_status hs_msf(hs_handle* h, double R, int sqrt_test, uint32_t* edge_lo, uint32_t* edge_hi, double* edge_dist,
+                 uint64_t cap, uint32_t* label, hs_msf_info* out) {
+  return msf_any(h, R, sqrt_test, edge_lo, edge_hi, edge_dist, cap, label, out, false);
+}
+
+hs_status hs_msf_dev(hs_handle* h, double R, int sqrt_test, uint32_t* d_edge_lo, uint32_t* d_edge_hi,
+                     double* d_edge_dist, uint64_t cap, uint32_t* d_label, hs_msf_info* out) {
+  return msf_any(h, R, sqrt_test, d_edge_lo, d_edge_hi, d_edge_dist, cap, d_label, out, true);
 }
 
 // ---- hs_cluster_profile / hs_cluster_radii: clusters of a label array summarised (kernels and state: hs_summary.hip) ----

@@ -551,6 +551,34 @@ hipError_t hs_launch_db_unite(const uint64_t* d_key, uint32_t n_hits, uint32_t s
                               uint32_t min_pts, uint32_t* d_parent, uint32_t* d_anchor, uint32_t n, hipStream_t s);
 hipError_t hs_launch_db_finish(uint32_t* d_parent, const uint32_t* d_deg, const uint32_t* d_anchor, uint32_t min_pts,
                                uint32_t n, uint32_t* d_label, uint64_t* d_counts, hipStream_t s);
+// minimum spanning forest of the self-join's graph (hs_msf.hip; the state, the round and the invariant are written at
+// its head).  d_counts: eight 64-bit words, of which five are used {ordered pairs of the pass, pairs that cross two
+// components, entries appended to the kept list, tree edges, roots}.  begin: comp and parent the identity, the slots
+// empty, zero counts.  min_d_hits / min_pair_hits: steps 1 and 2 over a batch's pairs as the exact pass leaves them in
+// (d_key, d_val); with d_kept != null step 1 also appends the pairs with a < b to d_kept[kept_cap] (16 bytes each:
+// lo << 32 | hi, distance bits) while there is room -- counts[2] keeps running.  min_d_kept / min_pair_kept: the same
+// steps over that list.  select: step 3, then comp[i] = find(i) and the slots emptied.  finish: d_label (may be null)
+// = comp, the roots counted.  unpack: the sorted (pair, bits) into the three output arrays.
+#define HS_MSF_MAX_ROUNDS 34u
+hipError_t hs_launch_msf_begin(uint32_t* d_comp, uint32_t* d_parent, uint64_t* d_best_d, uint64_t* d_best_pair,
+                               uint32_t n, uint64_t* d_counts, hipStream_t s);
+hipError_t hs_launch_msf_min_d_hits(const uint64_t* d_key, const uint64_t* d_val, uint32_t n_hits, uint32_t self_first,
+                                    const uint32_t* d_comp, uint64_t* d_best_d, uint32_t n, uint64_t* d_counts,
+                                    void* d_kept, uint64_t kept_cap, hipStream_t s);
+hipError_t hs_launch_msf_min_pair_hits(const uint64_t* d_key, const uint64_t* d_val, uint32_t n_hits,
+                                       uint32_t self_first, const uint32_t* d_comp, const uint64_t* d_best_d,
+                                       uint64_t* d_best_pair, uint32_t n, hipStream_t s);
+hipError_t hs_launch_msf_min_d_kept(const void* d_kept, uint64_t n_kept, const uint32_t* d_comp, uint64_t* d_best_d,
+                                    uint32_t n, uint64_t* d_counts, hipStream_t s);
+hipError_t hs_launch_msf_min_pair_kept(const void* d_kept, uint64_t n_kept, const uint32_t* d_comp,
+                                       const uint64_t* d_best_d, uint64_t* d_best_pair, uint32_t n, hipStream_t s);
+hipError_t hs_launch_msf_select(uint32_t* d_comp, uint32_t* d_parent, uint64_t* d_best_d, uint64_t* d_best_pair,
+                                uint32_t n, uint64_t* d_out_pair, uint64_t* d_out_d, uint64_t* d_counts,
+                                hipStream_t s);
+hipError_t hs_launch_msf_finish(const uint32_t* d_comp, uint32_t n, uint32_t* d_label, uint64_t* d_counts,
+                                hipStream_t s);
+hipError_t hs_launch_msf_unpack(const uint64_t* d_pair, const uint64_t* d_d, uint32_t m, uint32_t* d_lo, uint32_t* d_hi,
+                                double* d_dist, hipStream_t s);
 // cluster profiles and radii from a label array (hs_summary.hip; the arrays are the state listed at its head).
 // group: sizes, validation (*d_err |= 1: a label that is neither HS_NOISE nor < n) and the two scans -- the caller
 // reads d_err[0], d_row_of[n] (rows) and d_off_of[n] (kept members) back before it goes on; members: the rows' labels

@@ -11,6 +11,8 @@
 // -centers 1 (-C; with -linkage single or dbscan only) writes beside the clusters file the centroids of the clusters
 // of at least -minsize m (-m, default 50: the reference's MIN_SIZE_CLUSTER) members as <o>hclust.format.txt and their
 // covering radii as <o>hclust.radii.txt (hsearch::ClusterCenters): the -c / --radii inputs of hs_motif_both_points.
+// -tree 1 (-t; with -linkage single only) writes beside the clusters file the single-linkage tree up to the threshold
+// as <o>hclust.tree.txt (hsearch::SingleLinkageTree): one line per merge, in merge order.
 #include <stdio.h>
 #include <stdlib.h>
 #include <time.h>
@@ -46,6 +48,8 @@ const Opt kOpts[] = {
     {"centers", 'C', "1: also write <output>hclust.format.txt (centroids) and <output>hclust.radii.txt (covering radii) "
                      "of the clusters; with -linkage single or dbscan [0]", false},
     {"minsize", 'm', "centers: members a cluster needs to get a centre [50]", false},
+    {"tree", 't', "1: also write <output>hclust.tree.txt, the single-linkage tree up to the threshold, one line per "
+                  "merge in merge order: two k-mer names and the distance; with -linkage single [0]", false},
 };
 void Help(const char* prog) {
   fprintf(stderr, "Usage: %s [OPTIONS]\n\nOptions:\n", prog);
@@ -147,6 +151,15 @@ int main(int argc, const char* argv[]) {
       centers_min_size = (uint32_t)m;
     }
   }
+  if (val.count("tree") && val["tree"] != "0" && val["tree"] != "1") {
+    fprintf(stderr, "ERROR: -tree takes 0 or 1, not '%s'\n", val["tree"].c_str());
+    return EXIT_FAILURE;
+  }
+  const bool tree = val.count("tree") && val["tree"] == "1";
+  if (tree && linkage != "single") {
+    fprintf(stderr, "ERROR: -tree goes with -linkage single only: the tree is the single-linkage tree\n");
+    return EXIT_FAILURE;
+  }
   uint32_t seed;
   if (val.count("seed")) {
     seed = (uint32_t)strtoul(val["seed"].c_str(), nullptr, 10);
@@ -170,6 +183,9 @@ int main(int argc, const char* argv[]) {
     const int st = linkage == "dbscan"
                        ? hsearch::Dbscan(kmers, hash_K, hash_L, hash_W, hash_R, min_pts, val["output"], planes, device,
                                          &err, &n_clusters, seed, centers_min_size)
+                   : tree
+                       ? hsearch::SingleLinkageTree(kmers, hash_K, hash_L, hash_W, hash_R, val["output"], planes, device,
+                                                    &err, &n_clusters, nullptr, seed, centers_min_size)
                    : linkage == "single"
                        ? hsearch::Components(kmers, hash_K, hash_L, hash_W, hash_R, val["output"], planes, device, &err,
                                              &n_clusters, seed, centers_min_size)

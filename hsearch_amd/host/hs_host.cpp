@@ -900,9 +900,12 @@ int ClusterCenters(hs_handle* h, const std::vector<Kmer>& kmers, const std::vect
   return HS_OK;
 }
 
-int Components(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
-               const double& hash_R, const std::string& output_file, const Planes& planes, int device,
-               std::string* err, uint64_t* n_clusters, uint32_t unknown_seed, uint32_t centers_min_size) {
+// Components and SingleLinkageTree: the same clusters file; tree: the labels come from hs_msf, whose tree edges go to
+// <output_file>hclust.tree.txt
+static int ComponentsOrTree(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L,
+                            const double& hash_W, const double& hash_R, const std::string& output_file,
+                            const Planes& planes, int device, std::string* err, uint64_t* n_clusters,
+                            uint32_t unknown_seed, uint32_t centers_min_size, bool tree, uint64_t* n_tree_edges) {
   std::vector<uint8_t> codes;
   const int cs = ClusterCodes(kmers, hash_K, hash_L, hash_W, planes, unknown_seed, &codes, err);
   if (cs != HS_OK) return cs;
@@ -923,9 +926,23 @@ int Components(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uin
     what = "hs_index_build";
     st = hs_index_build(h, codes.data(), n);
   }
-  if (st == HS_OK) {
+  std::vector<uint32_t> tree_lo, tree_hi;
+  std::vector<double> tree_dist;
+  if (st == HS_OK && !tree) {
     what = "hs_components";
     st = hs_components(h, hash_R, 1, label.data(), &n_comp, nullptr);  // hclust2's test: sqrt(d2) <= R
+  }
+  if (st == HS_OK && tree) {
+    what = "hs_msf";
+    tree_lo.resize(n);  // at most n - 1 tree edges: sized once
+    tree_hi.resize(n);
+    tree_dist.resize(n);
+    hs_msf_info info;
+    st = hs_msf(h, hash_R, 1, tree_lo.data(), tree_hi.data(), tree_dist.data(), n, label.data(), &info);
+    if (st == HS_OK) {
+      n_comp = info.n_components;
+      tree_lo.resize(info.n_tree_edges);
+    }
   }
   if (st != HS_OK) {
     if (err) *err = std::string(what) + ": " + (h ? hs_last_error(h) : "no handle");
@@ -955,7 +972,37 @@ int Components(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uin
   }
   fout.close();
   if (n_clusters) *n_clusters = cluster_id;
+  if (tree) {
+    // one line per tree edge in merge order; %.17g reads back to the same double
+    std::ofstream ftree((output_file + "hclust.tree.txt").c_str());
+    if (!ftree) {
+      if (err) *err = "cannot write " + output_file + "hclust.tree.txt";
+      return HS_ERR_IO;
+    }
+    for (size_t t = 0; t < tree_lo.size(); ++t) {
+      char num[64];
+      snprintf(num, sizeof(num), "%.17g", tree_dist[t]);
+      ftree << kmers[tree_lo[t]].name << " " << kmers[tree_hi[t]].name << " " << num << "\n";
+    }
+    ftree.close();
+    if (n_tree_edges) *n_tree_edges = tree_lo.size();
+  }
   return HS_OK;
+}
+
+int Components(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
+               const double& hash_R, const std::string& output_file, const Planes& planes, int device,
+               std::string* err, uint64_t* n_clusters, uint32_t unknown_seed, uint32_t centers_min_size) {
+  return ComponentsOrTree(kmers, hash_K, hash_L, hash_W, hash_R, output_file, planes, device, err, n_clusters,
+                          unknown_seed, centers_min_size, false, nullptr);
+}
+
+int SingleLinkageTree(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L,
+                      const double& hash_W, const double& hash_R, const std::string& output_file, const Planes& planes,
+                      int device, std::string* err, uint64_t* n_clusters, uint64_t* n_tree_edges, uint32_t unknown_seed,
+                      uint32_t centers_min_size) {
+  return ComponentsOrTree(kmers, hash_K, hash_L, hash_W, hash_R, output_file, planes, device, err, n_clusters,
+                          unknown_seed, centers_min_size, true, n_tree_edges);
 }
 
 int Dbscan(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,

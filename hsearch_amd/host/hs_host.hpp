@@ -211,6 +211,16 @@ int Components(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uin
                const double& hash_R, const std::string& output_file, const Planes& planes, int device,
                std::string* err, uint64_t* n_clusters = nullptr, uint32_t unknown_seed = 0,
                uint32_t centers_min_size = 0);
+// Components, and beside the clusters file the single-linkage tree up to R (hs_msf in include/hsearch.h: the minimum
+// spanning forest of the same graph under the order (distance, smaller index, larger index)) as
+// <output_file>hclust.tree.txt: one line per tree edge in merge order, "<name> <name> <distance>" -- the k-mer with
+// the smaller index first, the distance with 17 significant digits, so that it reads back bit for bit.  Cutting the
+// list after its first n - c lines gives c clusters; the lines with a distance <= r give the clusters at radius r.
+// The clusters file is the one Components writes (the labels are hs_msf's, equal to hs_components').
+int SingleLinkageTree(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L,
+                      const double& hash_W, const double& hash_R, const std::string& output_file, const Planes& planes,
+                      int device, std::string* err, uint64_t* n_clusters = nullptr, uint64_t* n_tree_edges = nullptr,
+                      uint32_t unknown_seed = 0, uint32_t centers_min_size = 0);
 // Density clusters (DBSCAN, hs_dbscan in include/hsearch.h) of the same graph: only k-mers with at least min_pts
 // neighbours within R (themselves counted) join clusters together, so that one stray k-mer between two families no
 // longer fuses them; a sparse k-mer goes to the cluster of its dense neighbour with the smallest index or is noise.

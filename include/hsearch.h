@@ -174,6 +174,10 @@ typedef enum hs_option {
   HS_OPT_SUMMARY_CHUNK = 19, /* hs_cluster_profile / hs_cluster_radii: member slots per work item (1 .. 2^20); 0 (default): 512 */
   HS_OPT_SUMMARY_ROWS = 20,  /* hs_cluster_profile: rows per batch; 0 (default): as many as a fixed scratch budget of
                                 32 MB of counts holds */
+  HS_OPT_MSF_EDGE_BUDGET = 21, /* hs_msf: bytes of HBM a call may spend on keeping the self-join's pairs (16 per
+                                unordered pair) for its rounds.  0: never keep them (every pass is a self-join);
+                                -1 (default): a quarter of the HBM that is free when the call starts.  The list grows
+                                with the pairs, so a call takes what its graph needs, not the budget */
   HS_OPT_JOIN_XCD_RUN = 16   /* hs_join8x_kernel's work items dealt in runs of this many chunks per XCD, each XCD's
                                 waves on their own runs (a run's items stream the same query tiles: one L2 fetches
                                 them instead of eight).  0: one counter for the chip; -1 (default): by the size
@@ -584,6 +588,73 @@ HS_API hs_status hs_dbscan_dev(hs_handle* h, double R, int sqrt_test, uint32_t m
  * hs_self_join_range edges, then call it. */
 HS_API hs_status hs_dbscan_edges(const uint32_t* ei, const uint32_t* ej, uint64_t n_edges, uint64_t n,
                                  uint32_t min_pts, uint32_t* label, uint32_t* degree, hs_dbscan_counts* out);
+
+/* ---- single-linkage tree: the minimum spanning forest of the near-neighbour graph ---------------------------- */
+
+/* hs_components answers at ONE radius.  The minimum spanning forest (MSF) of the graph at radius R is the single-
+ * linkage dendrogram up to R: at most n - 1 edges, and cutting it at any r <= R gives the components at r, so one call
+ * replaces a ladder of hs_components calls and says at which distance two families merge.
+ *
+ * Contract: let G be the graph of hs_self_join(h, R, sqrt_test, ...) on the same handle, as in hs_components -- the
+ * same bucket rule over all L tables, the same exact fp64 test, self pairs dropped; the handle's multi-probe setting
+ * and bucket partition are ignored.  The WEIGHT of {a, b} is the edge_dist the self-join reports for the pair.  It is
+ * the same bits in both directions: every term (x_t - c_t)^2 is symmetric in IEEE arithmetic and the summation order
+ * over t is the same.  Edges are totally ordered by (dist as a double, lo, hi) with lo < hi; under a strict total
+ * order the MSF is unique, so the result is a pure function of the index, R and sqrt_test: batch sizes, filter paths,
+ * options and the device's scheduling do not show in it.
+ *
+ * hs_msf: the n - n_components tree edges in ascending (dist, lo, hi), edge_lo[t] < edge_hi[t]: the merge order of
+ * single linkage, the distances the merge heights.  Cutting into c clusters (n_components <= c <= n) is taking the
+ * first n - c edges of the list; it needs no function.  Capacity follows the two-call pattern: HS_ERR_CAPACITY with
+ * out->n_tree_edges (and the rest of *out) set and nothing else written -- neither the edge arrays nor label, in
+ * the _dev form either; the count is at most n - 1, so buffers sized once at n hold every result.  label [n] (may be NULL) is bit for bit what hs_components(h, R, sqrt_test) writes.
+ * out->n_graph_edges is hs_self_join's *n_edges (ORDERED pairs); out->rounds the Boruvka rounds that united something
+ * (the call makes rounds + 1 passes over the pairs that look for crossing edges; a graph without edges: 0 rounds,
+ * one pass); out->resident 1 if the pairs were kept in HBM, 0 if every pass was a self-join.  Errors as in
+ * hs_components: an unbuilt index is HS_ERR_STATE, a NaN R HS_ERR_INVALID; *out is zeroed first.
+ *
+ * The two paths (an option selects a path, never a result).  Re-join: every pass is a self-join whose batches' pairs
+ * are reduced where they lie -- no memory per edge, 2 rounds + 1 self-joins.  Resident (the default when it fits):
+ * the first self-join also appends every pair once (lo < hi) with its distance bits to a list in HBM, 16 bytes per
+ * unordered pair, and all later passes read that list -- one self-join.  HS_OPT_MSF_EDGE_BUDGET bounds the list; a
+ * graph that outgrows it drops the list and continues on the re-join path, which the caller sees in out->resident
+ * alone.  State of the handle: 56 bytes per indexed k-mer (components, forest, two 64-bit slots per component, the
+ * edge list and its sorted copy; allocated by the first such call, kept with the handle).  THE KEPT LIST STAYS WITH
+ * THE HANDLE TOO after a resident call returns -- 16 bytes per unordered pair of the last graph, rounded up by the
+ * doubling (275 MB for 17 M pairs), at most the budget -- so that the next call grows nothing; it is freed by the
+ * next hs_msf that does not end resident (HS_OPT_MSF_EDGE_BUDGET = 0 followed by a call is the way to give it back)
+ * and by hs_destroy.
+ * Every existing entry point runs as before, launch for launch.
+ *
+ * hs_msf_edges (host only, no GPU, no handle): the same rule for ANY list of n_edges weighted pairs (ei[t], ej[t],
+ * dist[t]) over the vertices 0 .. n-1: a pair may appear in either or both directions, repeated, and in any order;
+ * self pairs are ignored.  An id >= n, a NaN or negative distance, and two occurrences of one unordered pair with
+ * different distance bits are HS_ERR_INVALID, reported before any output is written.  out->n_graph_edges is twice
+ * the distinct unordered pairs; rounds and resident are 0.  This is the multi-GPU route: over the gathered
+ * hs_self_join_range edges of the ranks (as with hs_dbscan_edges), or as the MERGE of several ranks' forests --
+ * the MSF of a union of MSFs of edge subsets is the MSF of the whole (an edge that is not in the MSF of its subset
+ * is the largest of a cycle there, hence of a cycle in the whole, hence in no MSF of the whole under a strict order).
+ *
+ * hs_msf_cut (host only): label [n] = the smallest id per component of the forest made of the given tree edges with
+ * dist <= r.  With sqrt_test != 0 and r <= R the labels of hs_msf's tree cut at r equal hs_components(h, r, 1)
+ * exactly: sqrt(d2) <= r is the edge test of both.  With sqrt_test == 0 the equality is only guaranteed for the
+ * full forest against hs_components(h, R, 0): d2 <= r*r and sqrt(d2) <= r may differ in the last bit.  An input
+ * that is not a forest over 0 .. n-1 (an id >= n, a self pair, a NaN distance, an edge that closes a cycle) or a NaN
+ * r is HS_ERR_INVALID. */
+typedef struct hs_msf_info {
+  uint64_t n_tree_edges, n_components, n_graph_edges; /* n_graph_edges: ordered pairs, = hs_self_join's *n_edges */
+  uint32_t rounds, resident;                          /* resident 1: the pairs were kept in HBM, 0: re-joined per pass */
+} hs_msf_info;
+HS_API hs_status hs_msf(hs_handle* h, double R, int sqrt_test, uint32_t* edge_lo, uint32_t* edge_hi, double* edge_dist,
+                        uint64_t cap, uint32_t* label, hs_msf_info* out);
+/* ... the arrays in device memory, *out on the host (streams: as hs_query_dev) */
+HS_API hs_status hs_msf_dev(hs_handle* h, double R, int sqrt_test, uint32_t* d_edge_lo, uint32_t* d_edge_hi,
+                            double* d_edge_dist, uint64_t cap, uint32_t* d_label, hs_msf_info* out);
+HS_API hs_status hs_msf_edges(const uint32_t* ei, const uint32_t* ej, const double* dist, uint64_t n_edges, uint64_t n,
+                              uint32_t* out_lo, uint32_t* out_hi, double* out_dist, uint64_t cap, uint32_t* label,
+                              hs_msf_info* out);
+HS_API hs_status hs_msf_cut(const uint32_t* lo, const uint32_t* hi, const double* dist, uint64_t m, uint64_t n,
+                            double r, uint32_t* label, uint64_t* n_components);
 
 /* ---- cluster profiles, centroids and covering radii from a label array ------------------------------------ */
 

@@ -43,15 +43,8 @@ def make_codes(np):
     if args.db == "uniform":
         from hsearch_amd import synth
         return synth.make_db(args.n, args.k)
-    rng = np.random.default_rng(17)
-    fams = args.n // args.per_family
-    rows = np.repeat(rng.integers(0, 20, size=(fams, args.k), dtype=np.uint8), args.per_family, axis=0)
-    n_sub = rng.integers(0, 5, size=len(rows))
-    for t in range(4):  # substitution t + 1 of the rows that have that many
-        sel = np.nonzero(n_sub > t)[0]
-        rows[sel, rng.integers(0, args.k, size=len(sel))] = rng.integers(0, 20, size=len(sel), dtype=np.uint8)
-    rng.shuffle(rows)
-    return rows
+    from tools.sweep_dbs import planted_families
+    return planted_families(np, args.n, args.k, args.per_family)
 
 
 def host_labels(np, n, ei, ej):
