@@ -27,7 +27,9 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_components_range", "hs_components_range_dev", "hs_components_merge", "hs_degrees", "hs_degrees_dev",
            "hs_degrees_range", "hs_degrees_range_dev", "hs_dbscan", "hs_dbscan_dev", "hs_dbscan_edges",
            "hs_cluster_profile", "hs_cluster_profile_dev", "hs_cluster_radii", "hs_cluster_radii_dev",
-           "hs_cluster_summary_codes", "hs_msf", "hs_msf_dev", "hs_msf_edges", "hs_msf_cut"]
+           "hs_cluster_summary_codes", "hs_msf", "hs_msf_dev", "hs_msf_edges", "hs_msf_cut", "hs_core_distance",
+           "hs_core_distance_dev", "hs_density_tree", "hs_density_tree_dev", "hs_density_tree_edges",
+           "hs_density_tree_cut"]
 
 NOISE = 0xffffffff   # HS_NOISE: the label of a k-mer that is neither core nor border (hs_dbscan)
 
@@ -69,6 +71,12 @@ class _DbscanCounts(C.Structure):
 class _MsfInfo(C.Structure):
     _fields_ = [("n_tree_edges", C.c_uint64), ("n_components", C.c_uint64), ("n_graph_edges", C.c_uint64),
                 ("rounds", C.c_uint32), ("resident", C.c_uint32)]
+
+
+class _DensityInfo(C.Structure):
+    _fields_ = [("n_tree_edges", C.c_uint64), ("n_clusters", C.c_uint64), ("n_core", C.c_uint64),
+                ("n_graph_edges", C.c_uint64), ("rounds", C.c_uint32), ("resident", C.c_uint32),
+                ("self_joins", C.c_uint32)]
 
 
 profile_fields = [f[0] for f in _Profile._fields_]
@@ -188,6 +196,25 @@ def load(hooks=False):
             lib.hs_msf_cut.restype = C.c_int
             lib.hs_msf_cut.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_double,
                                        C.c_void_p, C.POINTER(C.c_uint64)]
+        # density tree: core_distance (h, R, sqrt_test, min_pts, core, n_core, n_edges); density_tree (h, R, sqrt_test,
+        # min_pts, lo, hi, w, cap, label, core, info); density_tree_edges (ei, ej, dist, n_edges, n, min_pts, out_lo,
+        # out_hi, out_w, cap, label, core, info); density_tree_cut (lo, hi, w, m, core, n, r, label, n_clusters)
+        if hasattr(lib, "hs_density_tree"):
+            for fn in (lib.hs_core_distance, lib.hs_core_distance_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64),
+                               C.POINTER(C.c_uint64)]
+            for fn in (lib.hs_density_tree, lib.hs_density_tree_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(_DensityInfo)]
+            lib.hs_density_tree_edges.restype = C.c_int
+            lib.hs_density_tree_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(_DensityInfo)]
+            lib.hs_density_tree_cut.restype = C.c_int
+            lib.hs_density_tree_cut.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                C.c_double, C.c_void_p, C.POINTER(C.c_uint64)]
         _libs[hooks] = lib
     return _libs[hooks]
 
@@ -354,6 +381,65 @@ def msf_cut(tree, r, n=None, out=None):
     if st != HS_OK:
         raise HsError(st, "hs_msf_cut")
     return dict(label=out, n_components=int(nc.value))
+
+
+def _density_dict(info, lo, hi, w, label, core):
+    m = int(info.n_tree_edges)
+    res = dict(lo=lo[:m], hi=hi[:m], w=w[:m], **{f[0]: int(getattr(info, f[0])) for f in _DensityInfo._fields_})
+    if label is not None:
+        res["label"] = label
+    if core is not None:
+        res["core"] = core
+    return res
+
+
+def density_tree_edges(ei, ej, dist, n, min_pts, want_label=True, cap=None):
+    """hs_density_tree_edges (host only, no GPU): the density tree -- the minimum spanning forest under (w, lo, hi),
+    w = max(core[a], core[b], dist) -- of any list of weighted pairs over n vertices, presented as msf_edges accepts
+    them -> dict(lo, hi, w: the n_core - n_clusters tree edges in ascending (w, lo, hi); core float64 [n] (inf: fewer
+    than min_pts - 1 neighbours); label if asked (NOISE where core is inf); n_tree_edges, n_clusters, n_core,
+    n_graph_edges, rounds = resident = self_joins = 0).  cap as in msf_edges."""
+    ei = np.ascontiguousarray(ei, dtype=np.uint32)
+    ej = np.ascontiguousarray(ej, dtype=np.uint32)
+    dist = np.ascontiguousarray(dist, dtype=np.float64)
+    assert ei.ndim == 1 and ei.shape == ej.shape == dist.shape
+    n = int(n)
+    room = n if cap is None else int(cap)
+    lo = np.empty(room, dtype=np.uint32)
+    hi = np.empty(room, dtype=np.uint32)
+    w = np.empty(room, dtype=np.float64)
+    label = np.empty(n, dtype=np.uint32) if want_label else None
+    core = np.empty(n, dtype=np.float64)
+    info = _DensityInfo()
+    st = load().hs_density_tree_edges(_vp(ei), _vp(ej), _vp(dist), len(ei), n, int(min_pts), _vp(lo), _vp(hi), _vp(w),
+                                      room, _vp(label) if want_label else None, _vp(core), C.byref(info))
+    if st != HS_OK:
+        e = HsError(st, "hs_density_tree_edges")
+        e.needed = int(info.n_tree_edges)
+        raise e
+    return _density_dict(info, lo, hi, w, label, core)
+
+
+def density_tree_cut(tree, r, n=None, out=None):
+    """hs_density_tree_cut (host only, no GPU): tree = a dict with lo, hi, w, core as Engine.density_tree /
+    density_tree_edges return them -> dict(label uint32 [n]: NOISE where core > r or core is inf, else the smallest id per component
+    of the tree edges with w <= r; n_clusters).  out: a uint32 [n] array to write into (untouched when the input is
+    invalid)."""
+    lo = np.ascontiguousarray(tree["lo"], dtype=np.uint32)
+    hi = np.ascontiguousarray(tree["hi"], dtype=np.uint32)
+    w = np.ascontiguousarray(tree["w"], dtype=np.float64)
+    core = np.ascontiguousarray(tree["core"], dtype=np.float64)
+    assert lo.ndim == 1 and lo.shape == hi.shape == w.shape and core.ndim == 1
+    n = len(core) if n is None else int(n)
+    assert len(core) == n
+    if out is None:
+        out = np.empty(n, dtype=np.uint32)
+    assert out.dtype == np.uint32 and out.shape == (n,) and out.flags["C_CONTIGUOUS"]
+    nc = C.c_uint64(0)
+    st = load().hs_density_tree_cut(_vp(lo), _vp(hi), _vp(w), len(lo), _vp(core), n, float(r), _vp(out), C.byref(nc))
+    if st != HS_OK:
+        raise HsError(st, "hs_density_tree_cut")
+    return dict(label=out, n_clusters=int(nc.value))
 
 
 def cluster_summary_codes(codes, label, min_size=1, coords=None, centers=None, want_counts=False, want_radii=True,
@@ -997,6 +1083,57 @@ class Engine:
             e.needed = int(info.n_tree_edges)
             raise e
         return {f[0]: int(getattr(info, f[0])) for f in _MsfInfo._fields_}
+
+    def core_distance(self, R, min_pts, sqrt_test=True):
+        """hs_core_distance: dict(core float64 [n] -- the (min_pts - 1)-th smallest neighbour distance of every k-mer in
+        the graph self_join(R, sqrt_test) returns, with multiplicity; 0 for min_pts = 1, inf with fewer neighbours --,
+        n_core = the finite ones, n_edges), settled on the device in one self-join."""
+        n = self._n()
+        core = np.empty(n, dtype=np.float64)
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.hs_core_distance(self._h, float(R), 1 if sqrt_test else 0, int(min_pts), _vp(core),
+                                               C.byref(nc), C.byref(ne)))
+        return dict(core=core, n_core=int(nc.value), n_edges=int(ne.value))
+
+    def core_distance_dev(self, d_core_ptr, R, min_pts, sqrt_test=True):
+        """hs_core_distance_dev: the core distances into float64 [n] device memory (pointer as int); (n_core, n_edges)."""
+        nc, ne = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.hs_core_distance_dev(self._h, float(R), 1 if sqrt_test else 0, int(min_pts), d_core_ptr,
+                                                   C.byref(nc), C.byref(ne)))
+        return int(nc.value), int(ne.value)
+
+    def density_tree(self, R, min_pts, sqrt_test=True, want_label=True):
+        """hs_density_tree: DBSCAN* at every radius up to R -- the minimum spanning forest of the graph self_join(R,
+        sqrt_test) under the mutual-reachability weight w = max(core[a], core[b], dist), found on the device:
+        dict(lo, hi, w: the n_core - n_clusters tree edges in ascending (w, lo, hi); core float64 [n]; label if asked
+        (= dbscan(R, min_pts)'s on its core k-mers, capi.NOISE elsewhere: border k-mers are noise); n_tree_edges,
+        n_clusters, n_core, n_graph_edges, rounds, resident, self_joins).  capi.density_tree_cut(tree, r) cuts it."""
+        n = self._n()
+        lo = np.empty(n, dtype=np.uint32)
+        hi = np.empty(n, dtype=np.uint32)
+        w = np.empty(n, dtype=np.float64)
+        core = np.empty(n, dtype=np.float64)
+        label = np.empty(n, dtype=np.uint32) if want_label else None
+        info = _DensityInfo()
+        self._check(self._lib.hs_density_tree(self._h, float(R), 1 if sqrt_test else 0, int(min_pts), _vp(lo), _vp(hi),
+                                              _vp(w), n, _vp(label) if want_label else None, _vp(core),
+                                              C.byref(info)))
+        return _density_dict(info, lo, hi, w, label, core)
+
+    def density_tree_dev(self, d_lo_ptr, d_hi_ptr, d_w_ptr, cap, R, min_pts, sqrt_test=True, d_label_ptr=None,
+                         d_core_ptr=None):
+        """hs_density_tree_dev: the tree edges into uint32 / uint32 / float64 [cap] device memory and, where given, the
+        labels into uint32 [n] and the core distances into float64 [n] (pointers as ints); returns the dict of the
+        counts.  A cap that is too small raises HsError(HS_ERR_CAPACITY) with the required size in .needed; none of
+        the arrays is written then."""
+        info = _DensityInfo()
+        st = self._lib.hs_density_tree_dev(self._h, float(R), 1 if sqrt_test else 0, int(min_pts), d_lo_ptr, d_hi_ptr,
+                                           d_w_ptr, int(cap), d_label_ptr, d_core_ptr, C.byref(info))
+        if st != HS_OK:
+            e = HsError(st, self._lib.hs_last_error(self._h).decode())
+            e.needed = int(info.n_tree_edges)
+            raise e
+        return {f[0]: int(getattr(info, f[0])) for f in _DensityInfo._fields_}
 
     def cluster_profile(self, label, min_size=1, want_counts=False, cap=None):
         """hs_cluster_profile: the clusters of label uint32 [n] (NOISE or a value < n: the labels of components(),

@@ -117,8 +117,12 @@ struct Knobs {
 //   DB_UNITE   hs_dbscan pass 2: the degrees known, the pairs united and anchored at min_pts
 //   MSF_MIN_D, MSF_MIN_PAIR   hs_msf (hs_msf.hip): steps 1 and 2 of a Boruvka round over a self-join's pairs
 //   MSF_COLLECT               hs_msf's first pass: step 1, and the pairs appended to the list kept in HBM
+//   DT_CORE, DT_CORE_COLLECT  hs_core_distance / hs_density_tree (hs_density.hip): the core pass -- the threshold
+//                             rounds over the batch's hits at min_pts; COLLECT: and the pairs appended to the kept list
+//   DT_MIN_D, DT_MIN_PAIR     hs_density_tree: steps 1 and 2 of a Boruvka round under the mutual-reachability weight
 struct HitSink {
-  enum Kind { LIST, ANNOTATE, CC_UNION, DB_DEGREE, DB_UNITE, MSF_MIN_D, MSF_MIN_PAIR, MSF_COLLECT } kind = LIST;
+  enum Kind { LIST, ANNOTATE, CC_UNION, DB_DEGREE, DB_UNITE, MSF_MIN_D, MSF_MIN_PAIR, MSF_COLLECT, DT_CORE,
+              DT_CORE_COLLECT, DT_MIN_D, DT_MIN_PAIR } kind = LIST;
   uint32_t min_pts = 1;
 };
 
@@ -232,6 +236,9 @@ struct hs_handle {
   DevBuf msf_comp, msf_best_d, msf_best_pair, msf_out_pair, msf_out_d, msf_s_pair, msf_s_d, msf_cnt, msf_kept;
   uint64_t msf_kept_budget = 0;
   bool msf_kept_failed = false;
+  // hs_core_distance / hs_density_tree (hs_density.hip: the state listed at its head; the rest is hs_msf's): the core
+  // distance bits, the threshold and the round's minimum per indexed k-mer, the neighbours counted
+  DevBuf dt_core, dt_thr, dt_next, dt_cnt;
   // hs_cluster_profile / hs_cluster_radii (hs_summary.hip: the state listed at its head), the counts of a row batch
   // when the caller wants none, and the arrays of a host-pointer call on their way in and out
   DevBuf sm_size, sm_tmp, sm_row_of, sm_off_of, sm_row_label, sm_row_off, sm_member, sm_d2, sm_err, sm_counts;
@@ -846,7 +853,8 @@ void hs_destroy(hs_handle* h) {
                     &h->mp_cand, &h->mp_radii, &h->io_radii, &h->ann_dist, &h->ann_tq, &h->ann_touched,
                     &h->ann_sorted, &h->ann_cnt, &h->cc_parent, &h->cc_cnt, &h->cc_label,
                     &h->db_deg, &h->db_anchor, &h->db_cnt, &h->msf_comp, &h->msf_best_d, &h->msf_best_pair,
-                    &h->msf_out_pair, &h->msf_out_d, &h->msf_s_pair, &h->msf_s_d, &h->msf_cnt, &h->msf_kept, &h->sm_size, &h->sm_tmp, &h->sm_row_of, &h->sm_off_of,
+                    &h->msf_out_pair, &h->msf_out_d, &h->msf_s_pair, &h->msf_s_d, &h->msf_cnt, &h->msf_kept, &h->dt_core, &h->dt_thr,
+                    &h->dt_next, &h->dt_cnt, &h->sm_size, &h->sm_tmp, &h->sm_row_of, &h->sm_off_of,
                     &h->sm_row_label, &h->sm_row_off, &h->sm_member, &h->sm_d2, &h->sm_err, &h->sm_counts,
                     &h->sm_io_label, &h->sm_io_a, &h->sm_io_b, &h->sm_io_counts, &h->sm_io_f64, &h->sm_io_f64b};
   for (DevBuf* bf : bufs) bf->release();
@@ -2920,8 +2928,7 @@ static hs_status annot_reduce(hs_handle* h, const uint64_t* d_key, const uint64_
 // batch brings at most nh entries on top of those counted so far (read back here: the stream is idle between
 // batches), never beyond the call's budget.  A list that cannot hold its pairs is not an error: the kernel stops
 // appending, the counter keeps running, and hs_msf goes on without the list.
-static hs_status msf_collect_batch(hs_handle* h, const QueryCall& c, uint32_t nh) {
-  if (!nh) return HS_OK;
+static hs_status msf_grow_kept(hs_handle* h, uint32_t nh) {
   uint64_t* const cnt = h->msf_cnt.as<uint64_t>();
   uint64_t kept = 0;
   HS_HIP(h, hipMemcpyAsync(&kept, cnt + 2, 8, hipMemcpyDeviceToHost, h->stream));
@@ -2944,13 +2951,47 @@ static hs_status msf_collect_batch(hs_handle* h, const QueryCall& c, uint32_t nh
       h->msf_kept = bigger;
     }
   }
+  return HS_OK;
+}
+
+static hs_status msf_collect_batch(hs_handle* h, const QueryCall& c, uint32_t nh) {
+  if (!nh) return HS_OK;
+  HS_CHECK(msf_grow_kept(h, nh));
+  uint64_t* const cnt = h->msf_cnt.as<uint64_t>();
+  const uint64_t budget = h->msf_kept_budget;
   HS_HIP(h, hs_launch_msf_min_d_hits(h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(), nh, c.self_first,
                                      h->msf_comp.as<uint32_t>(), h->msf_best_d.as<uint64_t>(), (uint32_t)h->n, cnt,
                                      h->msf_kept.p, std::min<uint64_t>(budget, h->msf_kept.cap / 16), h->stream));
   return HS_OK;
 }
 
-static hs_status reduce_batch(hs_handle* h, const QueryCall& c, uint32_t nh) {
+// hs_density.hip's core pass over one batch: its queries are the k-mers [first, first + count), and ALL hits of such a
+// k-mer lie in this batch's nh (run_query batches by query and hands a batch on once, whole), each ordered pair once.
+// The pairs are counted (and, collecting, kept with their raw distance); then at most min_pts - 1 threshold rounds,
+// the count of k-mers still open read back after each (the stream is idle between batches) and zero ending them.
+static hs_status dt_core_batch(hs_handle* h, const QueryCall& c, uint32_t nh, uint32_t first, uint32_t count) {
+  uint64_t* const cnt = h->msf_cnt.as<uint64_t>();
+  const uint32_t n = (uint32_t)h->n;
+  const bool collect = c.sink.kind == HitSink::DT_CORE_COLLECT;
+  if (collect && nh) HS_CHECK(msf_grow_kept(h, nh));
+  HS_HIP(h, hs_launch_dt_pairs(h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(), nh, c.self_first, n, cnt,
+                               collect ? h->msf_kept.p : nullptr,
+                               std::min<uint64_t>(h->msf_kept_budget, h->msf_kept.cap / 16), h->stream));
+  for (uint32_t round = 1; round < c.sink.min_pts; ++round) {
+    HS_HIP(h, hipMemsetAsync(cnt + 6, 0, 8, h->stream));
+    HS_HIP(h, hs_launch_dt_round(h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(), nh, c.self_first, n, first, count,
+                                 c.sink.min_pts, h->dt_core.as<uint64_t>(), h->dt_thr.as<uint64_t>(),
+                                 h->dt_next.as<uint64_t>(), h->dt_cnt.as<uint32_t>(), cnt, h->stream));
+    uint64_t open = 0;
+    HS_HIP(h, hipMemcpyAsync(&open, cnt + 6, 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    if (!open) break;
+  }
+  return HS_OK;
+}
+
+// first, count: the batch's queries within the call (for a self-join the k-mers c.self_first + first ...)
+static hs_status reduce_batch(hs_handle* h, const QueryCall& c, uint32_t nh, uint32_t first, uint32_t count) {
   const uint64_t* const pairs = h->hit_key.as<uint64_t>();
   const uint32_t n = (uint32_t)h->n;
   switch (c.sink.kind) {
@@ -2982,6 +3023,19 @@ static hs_status reduce_batch(hs_handle* h, const QueryCall& c, uint32_t nh) {
       break;
     case HitSink::MSF_COLLECT:
       return msf_collect_batch(h, c, nh);
+    case HitSink::DT_CORE:
+    case HitSink::DT_CORE_COLLECT:
+      return dt_core_batch(h, c, nh, c.self_first + first, count);
+    case HitSink::DT_MIN_D:
+      HS_HIP(h, hs_launch_dt_min_d_hits(pairs, h->hit_val.as<uint64_t>(), nh, c.self_first, h->dt_core.as<uint64_t>(),
+                                        h->msf_comp.as<uint32_t>(), h->msf_best_d.as<uint64_t>(), n,
+                                        h->msf_cnt.as<uint64_t>(), h->stream));
+      break;
+    case HitSink::DT_MIN_PAIR:
+      HS_HIP(h, hs_launch_dt_min_pair_hits(pairs, h->hit_val.as<uint64_t>(), nh, c.self_first,
+                                           h->dt_core.as<uint64_t>(), h->msf_comp.as<uint32_t>(),
+                                           h->msf_best_d.as<uint64_t>(), h->msf_best_pair.as<uint64_t>(), n, h->stream));
+      break;
   }
   return HS_OK;
 }
@@ -3095,7 +3149,7 @@ static hs_status run_query(hs_handle* h, QueryCall c, uint64_t nq, uint32_t* d_h
       if (st) return st;
       // the batch came through whole (a split one has `continue`d above): its hits go on, once (reduce_batch)
       if (c.sink.kind != HitSink::LIST) {
-        HS_CHECK(reduce_batch(h, c, nh));
+        HS_CHECK(reduce_batch(h, c, nh, (uint32_t)q0, nqb));
         total += nh;
         continue;
       }
@@ -3878,6 +3932,33 @@ hs_status hs_dbscan_dev(hs_handle* h, double R, int sqrt_test, uint32_t min_pts,
 }
 
 // ---- hs_msf: the minimum spanning forest of the self-join's graph (kernels, the round and the invariant: hs_msf.hip) ----
+// The entries hs_msf / hs_density_tree may keep: the option's bytes, or a quarter of what is free now.
+static hs_status msf_budget(hs_handle* h, uint64_t* budget) {
+  if (h->knobs.msf_edge_budget < 0) {
+    size_t free_b = 0, total_b = 0;
+    HS_HIP(h, hipMemGetInfo(&free_b, &total_b));
+    *budget = free_b / 4 / 16;
+  } else {
+    *budget = (uint64_t)h->knobs.msf_edge_budget / 16;
+  }
+  return HS_OK;
+}
+
+// The m tree edges in msf_out_pair / msf_out_d ordered by (weight, lo, hi) -- two stable 64-bit radix sorts over all 64
+// bits, by pair, then by the weight bits -- and unpacked into the three output arrays (device).
+static hs_status msf_sort_unpack(hs_handle* h, uint64_t m, uint32_t* d_lo, uint32_t* d_hi, double* d_dist) {
+  if (!m) return HS_OK;
+  uint64_t* const op = h->msf_out_pair.as<uint64_t>();
+  uint64_t* const od = h->msf_out_d.as<uint64_t>();
+  uint64_t* const sp = h->msf_s_pair.as<uint64_t>();
+  uint64_t* const sd = h->msf_s_d.as<uint64_t>();
+  HS_HIP(h, h->temp.reserve(hs_sort_pairs_u64_u64_temp(m) + 256));
+  HS_HIP(h, hs_sort_pairs_u64_u64(h->temp.p, h->temp.cap, op, sp, od, sd, m, 64, h->stream));
+  HS_HIP(h, hs_sort_pairs_u64_u64(h->temp.p, h->temp.cap, sd, od, sp, op, m, 64, h->stream));
+  HS_HIP(h, hs_launch_msf_unpack(op, od, (uint32_t)m, d_lo, d_hi, d_dist, h->stream));
+  return HS_OK;
+}
+
 // Boruvka rounds over the pairs of the full self-join: kept in HBM by the first pass when the budget allows, from a
 // reduced self-join per pass otherwise.  The m <= n - 1 tree edges, ordered by (dist, lo, hi), go to d_lo / d_hi /
 // d_dist (device, room for cap), the labels to d_label (device, may be null).
@@ -3896,15 +3977,8 @@ static hs_status msf_run(hs_handle* h, double R, int sqrt_test, uint32_t* d_lo, 
   uint64_t* const best_d = h->msf_best_d.as<uint64_t>();
   uint64_t* const best_pair = h->msf_best_pair.as<uint64_t>();
   uint64_t* const cnt = h->msf_cnt.as<uint64_t>();
-  // the entries the call may keep: the option's bytes, or a quarter of what is free now
   uint64_t budget = 0;
-  if (h->knobs.msf_edge_budget < 0) {
-    size_t free_b = 0, total_b = 0;
-    HS_HIP(h, hipMemGetInfo(&free_b, &total_b));
-    budget = free_b / 4 / 16;
-  } else {
-    budget = (uint64_t)h->knobs.msf_edge_budget / 16;
-  }
+  HS_CHECK(msf_budget(h, &budget));
   h->msf_kept_budget = budget;
   h->msf_kept_failed = false;
   HS_HIP(h, hs_launch_msf_begin(comp, parent, best_d, best_pair, n, cnt, h->stream));
@@ -3951,17 +4025,7 @@ static hs_status msf_run(hs_handle* h, double R, int sqrt_test, uint32_t* d_lo, 
   out->resident = resident ? 1u : 0u;
   if (m > cap) return fail(h, HS_ERR_CAPACITY, "edge buffers too small; see out->n_tree_edges");
   if (d_label && n) HS_HIP(h, hipMemcpyAsync(d_label, comp, (size_t)n * 4, hipMemcpyDeviceToDevice, h->stream));
-  if (m) {
-    // (dist, lo, hi): two stable 64-bit radix sorts over all 64 bits -- by pair, then by the distance bits
-    uint64_t* const op = h->msf_out_pair.as<uint64_t>();
-    uint64_t* const od = h->msf_out_d.as<uint64_t>();
-    uint64_t* const sp = h->msf_s_pair.as<uint64_t>();
-    uint64_t* const sd = h->msf_s_d.as<uint64_t>();
-    HS_HIP(h, h->temp.reserve(hs_sort_pairs_u64_u64_temp(m) + 256));
-    HS_HIP(h, hs_sort_pairs_u64_u64(h->temp.p, h->temp.cap, op, sp, od, sd, m, 64, h->stream));
-    HS_HIP(h, hs_sort_pairs_u64_u64(h->temp.p, h->temp.cap, sd, od, sp, op, m, 64, h->stream));
-    HS_HIP(h, hs_launch_msf_unpack(op, od, (uint32_t)m, d_lo, d_hi, d_dist, h->stream));
-  }
+  HS_CHECK(msf_sort_unpack(h, m, d_lo, d_hi, d_dist));
   HS_HIP(h, hipStreamSynchronize(h->stream));
   return HS_OK;
 }
@@ -3999,6 +4063,185 @@ hs_status hs_msf(hs_handle* h, double R, int sqrt_test, uint32_t* edge_lo, uint3
 hs_status hs_msf_dev(hs_handle* h, double R, int sqrt_test, uint32_t* d_edge_lo, uint32_t* d_edge_hi,
                      double* d_edge_dist, uint64_t cap, uint32_t* d_label, hs_msf_info* out) {
   return msf_any(h, R, sqrt_test, d_edge_lo, d_edge_hi, d_edge_dist, cap, d_label, out, true);
+}
+
+// ---- hs_core_distance / hs_density_tree: DBSCAN* at every radius up to R (kernels, the rule and the state: hs_density.hip) ----
+// The core pass: one self-join whose batches settle the core distances of their own k-mers (dt_core_batch); with
+// `collect` it also keeps the pairs.  Needs msf_cnt zeroed.  c8: the eight counts afterwards.
+static hs_status density_core_pass(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, bool collect,
+                                   hs_profile* acc, uint64_t c8[8]) {
+  const uint32_t n = (uint32_t)h->n;
+  const size_t w4 = std::max<size_t>(16, (size_t)n * 4), w8 = std::max<size_t>(16, (size_t)n * 8);
+  for (DevBuf* bf : {&h->dt_core, &h->dt_thr, &h->dt_next}) HS_HIP(h, bf->reserve(w8));
+  HS_HIP(h, h->dt_cnt.reserve(w4));
+  uint64_t* const cnt = h->msf_cnt.as<uint64_t>();
+  HS_HIP(h, hs_launch_dt_begin(h->dt_core.as<uint64_t>(), h->dt_thr.as<uint64_t>(), h->dt_next.as<uint64_t>(),
+                               h->dt_cnt.as<uint32_t>(), n, min_pts, h->stream));
+  HS_CHECK(reduced_self_join(h, 0, n, R, sqrt_test, {collect ? HitSink::DT_CORE_COLLECT : HitSink::DT_CORE, min_pts},
+                             acc));
+  HS_HIP(h, hs_launch_dt_core_finish(h->dt_core.as<uint64_t>(), n, cnt, h->stream));
+  HS_HIP(h, hipMemcpyAsync(c8, cnt, 64, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return HS_OK;
+}
+
+static hs_status core_distance_any(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, double* core,
+                                   uint64_t* n_core, uint64_t* n_edges, bool dev) {
+  if (!h || !n_core) return HS_ERR_INVALID;
+  *n_core = 0;
+  if (n_edges) *n_edges = 0;
+  HS_CHECK(self_join_check(h, 0, h->n, !h->n || core));
+  if (!min_pts) return fail(h, HS_ERR_INVALID, "min_pts must be at least 1");
+  if (!(R == R)) return fail(h, HS_ERR_INVALID, "R is NaN");
+  HS_HIP(h, h->msf_cnt.reserve(64));
+  HS_HIP(h, hipMemsetAsync(h->msf_cnt.p, 0, 64, h->stream));
+  hs_profile acc = {};
+  uint64_t c8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  HS_CHECK(density_core_pass(h, R, sqrt_test, min_pts, false, &acc, c8));
+  h->prof = acc;
+  h->prof.hits = c8[0];
+  if (h->n) {
+    HS_HIP(h, hipMemcpyAsync(core, h->dt_core.p, (size_t)h->n * 8, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                             h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  *n_core = c8[5];
+  if (n_edges) *n_edges = c8[0];
+  return HS_OK;
+}
+
+hs_status hs_core_distance(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, double* core, uint64_t* n_core,
+                           uint64_t* n_edges) {
+  return core_distance_any(h, R, sqrt_test, min_pts, core, n_core, n_edges, false);
+}
+
+hs_status hs_core_distance_dev(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, double* d_core, uint64_t* n_core,
+                               uint64_t* n_edges) {
+  return core_distance_any(h, R, sqrt_test, min_pts, d_core, n_core, n_edges, true);
+}
+
+// The core pass, then hs_msf's rounds under the mutual-reachability weight: from the kept list when the core pass could
+// keep it, from two reduced self-joins per round otherwise.  The tree edges, ordered by (w, lo, hi), go to d_lo / d_hi /
+// d_w (device, room for cap), the labels and core distances to d_label / d_core (device, may be null).
+static hs_status density_run(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, uint32_t* d_lo, uint32_t* d_hi,
+                             double* d_w, uint64_t cap, uint32_t* d_label, double* d_core, hs_density_info* out) {
+  if (!(R == R)) return fail(h, HS_ERR_INVALID, "R is NaN");
+  const uint32_t n = (uint32_t)h->n;
+  const size_t w4 = std::max<size_t>(16, (size_t)n * 4), w8 = std::max<size_t>(16, (size_t)n * 8);
+  HS_HIP(h, h->msf_comp.reserve(w4));
+  HS_HIP(h, h->cc_parent.reserve(w4));
+  for (DevBuf* bf : {&h->msf_best_d, &h->msf_best_pair, &h->msf_out_pair, &h->msf_out_d, &h->msf_s_pair, &h->msf_s_d})
+    HS_HIP(h, bf->reserve(w8));
+  HS_HIP(h, h->msf_cnt.reserve(64));
+  uint32_t* const comp = h->msf_comp.as<uint32_t>();
+  uint32_t* const parent = h->cc_parent.as<uint32_t>();
+  uint64_t* const best_d = h->msf_best_d.as<uint64_t>();
+  uint64_t* const best_pair = h->msf_best_pair.as<uint64_t>();
+  uint64_t* const cnt = h->msf_cnt.as<uint64_t>();
+  uint64_t budget = 0;
+  HS_CHECK(msf_budget(h, &budget));
+  h->msf_kept_budget = budget;
+  h->msf_kept_failed = false;
+  HS_HIP(h, hs_launch_msf_begin(comp, parent, best_d, best_pair, n, cnt, h->stream));
+  hs_profile acc = {};
+  uint64_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  HS_CHECK(density_core_pass(h, R, sqrt_test, min_pts, budget != 0, &acc, c));
+  uint32_t self_joins = 1;
+  const uint64_t n_pairs = c[0], n_core = c[5];
+  const bool resident = budget && !h->msf_kept_failed && c[2] <= std::min<uint64_t>(budget, h->msf_kept.cap / 16);
+  const uint64_t n_kept = resident ? c[2] : 0;
+  if (!resident) h->msf_kept.release();  // (a list that overflowed is dropped; the call goes on from the self-joins)
+  const uint64_t* const core = h->dt_core.as<uint64_t>();
+  // one pass of step 1 (into zeroed pair / cross counts) or step 2 over the pairs
+  auto pass = [&](bool min_d) -> hs_status {
+    if (min_d) HS_HIP(h, hipMemsetAsync(cnt, 0, 16, h->stream));
+    if (resident) {
+      if (min_d)
+        HS_HIP(h, hs_launch_dt_min_d_kept(h->msf_kept.p, n_kept, core, comp, best_d, n, cnt, h->stream));
+      else
+        HS_HIP(h, hs_launch_dt_min_pair_kept(h->msf_kept.p, n_kept, core, comp, best_d, best_pair, n, h->stream));
+      return HS_OK;
+    }
+    ++self_joins;
+    return reduced_self_join(h, 0, n, R, sqrt_test, {min_d ? HitSink::DT_MIN_D : HitSink::DT_MIN_PAIR}, &acc);
+  };
+  uint64_t cross = 0;
+  HS_CHECK(pass(true));
+  HS_HIP(h, hipMemcpyAsync(&cross, cnt + 1, 8, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  uint32_t rounds = 0;
+  while (cross) {
+    if (rounds == HS_MSF_MAX_ROUNDS)
+      return fail(h, HS_ERR_STATE, "hs_density_tree: pairs still cross components after 34 rounds (internal error)");
+    HS_CHECK(pass(false));
+    HS_HIP(h, hs_launch_msf_select(comp, parent, best_d, best_pair, n, h->msf_out_pair.as<uint64_t>(),
+                                   h->msf_out_d.as<uint64_t>(), cnt, h->stream));
+    ++rounds;
+    HS_CHECK(pass(true));
+    HS_HIP(h, hipMemcpyAsync(&cross, cnt + 1, 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  // the clusters counted; the caller's arrays are written behind the capacity verdict only
+  HS_HIP(h, hs_launch_dt_finish(comp, core, n, nullptr, cnt, h->stream));
+  HS_HIP(h, hipMemcpyAsync(c, cnt, 64, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  const uint64_t m = c[3];
+  h->prof = acc;
+  h->prof.hits = n_pairs;
+  if (m + c[4] != n_core)
+    return fail(h, HS_ERR_STATE, "hs_density_tree: tree edges and clusters do not add up (internal error)");
+  out->n_tree_edges = m;
+  out->n_clusters = c[4];
+  out->n_core = n_core;
+  out->n_graph_edges = n_pairs;
+  out->rounds = rounds;
+  out->resident = resident ? 1u : 0u;
+  out->self_joins = self_joins;
+  if (m > cap) return fail(h, HS_ERR_CAPACITY, "edge buffers too small; see out->n_tree_edges");
+  if (d_label) HS_HIP(h, hs_launch_dt_finish(comp, core, n, d_label, nullptr, h->stream));
+  if (d_core && n) HS_HIP(h, hipMemcpyAsync(d_core, core, (size_t)n * 8, hipMemcpyDeviceToDevice, h->stream));
+  HS_CHECK(msf_sort_unpack(h, m, d_lo, d_hi, d_w));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return HS_OK;
+}
+
+static hs_status density_any(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, uint32_t* edge_lo,
+                             uint32_t* edge_hi, double* edge_w, uint64_t cap, uint32_t* label, double* core,
+                             hs_density_info* out, bool dev) {
+  if (!h || !out) return HS_ERR_INVALID;
+  memset(out, 0, sizeof(*out));
+  HS_CHECK(self_join_check(h, 0, h->n, !cap || (edge_lo && edge_hi && edge_w)));
+  if (!min_pts) return fail(h, HS_ERR_INVALID, "min_pts must be at least 1");
+  if (dev) return density_run(h, R, sqrt_test, min_pts, edge_lo, edge_hi, edge_w, cap, label, core, out);
+  // host pointers: through the handle's I/O buffers; 16 bytes per tree edge, 4 per label and 8 per core distance cross PCIe
+  const size_t room = (size_t)std::min<uint64_t>(cap, h->n);
+  HS_HIP(h, h->io_q.reserve(std::max<size_t>(16, room * 4)));
+  HS_HIP(h, h->io_id.reserve(std::max<size_t>(16, room * 4)));
+  HS_HIP(h, h->io_dist.reserve(std::max<size_t>(16, room * 8)));
+  if (label) HS_HIP(h, h->cc_label.reserve(std::max<size_t>(16, (size_t)h->n * 4)));
+  HS_CHECK(density_run(h, R, sqrt_test, min_pts, h->io_q.as<uint32_t>(), h->io_id.as<uint32_t>(),
+                       h->io_dist.as<double>(), room, label ? h->cc_label.as<uint32_t>() : nullptr, nullptr, out));
+  const size_t m = (size_t)out->n_tree_edges;
+  if (m) {
+    HS_HIP(h, hipMemcpyAsync(edge_lo, h->io_q.p, m * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(edge_hi, h->io_id.p, m * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(edge_w, h->io_dist.p, m * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  if (label && h->n) HS_HIP(h, hipMemcpyAsync(label, h->cc_label.p, (size_t)h->n * 4, hipMemcpyDeviceToHost, h->stream));
+  if (core && h->n) HS_HIP(h, hipMemcpyAsync(core, h->dt_core.p, (size_t)h->n * 8, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return HS_OK;
+}
+
+hs_status hs_density_tree(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, uint32_t* edge_lo, uint32_t* edge_hi,
+                          double* edge_w, uint64_t cap, uint32_t* label, double* core, hs_density_info* out) {
+  return density_any(h, R, sqrt_test, min_pts, edge_lo, edge_hi, edge_w, cap, label, core, out, false);
+}
+
+hs_status hs_density_tree_dev(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, uint32_t* d_edge_lo,
+                              uint32_t* d_edge_hi, double* d_edge_w, uint64_t cap, uint32_t* d_label, double* d_core,
+                              hs_density_info* out) {
+  return density_any(h, R, sqrt_test, min_pts, d_edge_lo, d_edge_hi, d_edge_w, cap, d_label, d_core, out, true);
 }
 
 // ---- hs_cluster_profile / hs_cluster_radii: clusters of a label array summarised (kernels and state: hs_summary.hip) ----

@@ -579,6 +579,36 @@ hipError_t hs_launch_msf_finish(const uint32_t* d_comp, uint32_t n, uint32_t* d_
                                 hipStream_t s);
 hipError_t hs_launch_msf_unpack(const uint64_t* d_pair, const uint64_t* d_d, uint32_t m, uint32_t* d_lo, uint32_t* d_hi,
                                 double* d_dist, hipStream_t s);
+// the density tree of the self-join's graph (hs_density.hip; the rule, the state and the rounds of the core pass are
+// written at its head).  d_counts: hs_msf's eight 64-bit words, with [5] = k-mers with a finite core distance and
+// [6] = k-mers of the batch still open after a round.  begin: the state of a call (core = +0 for min_pts = 1, open
+// otherwise).  pairs: a batch's ordered pairs counted and, with d_kept != null, those with a < b appended as
+// hs_launch_msf_min_d_hits appends them.  round: one threshold round (next, count, settle) over a batch's hits for the
+// k-mers [first, first + count) -- a range outside 0 .. n is hipErrorInvalidValue, nothing launched.  core_finish: unsettled k-mers get +inf,
+// the finite ones are counted.  min_d_* / min_pair_*: steps 1 and 2 of hs_msf's round under the weight
+// max(d, core[a], core[b]); a pair with an infinite end is skipped.  finish: d_label (may be null) = comp where the
+// core distance is finite and HS_NOISE elsewhere; with d_counts != null the roots among the former are counted.
+hipError_t hs_launch_dt_begin(uint64_t* d_core, uint64_t* d_thr, uint64_t* d_next, uint32_t* d_cnt, uint32_t n,
+                              uint32_t min_pts, hipStream_t s);
+hipError_t hs_launch_dt_pairs(const uint64_t* d_key, const uint64_t* d_val, uint32_t n_hits, uint32_t self_first,
+                              uint32_t n, uint64_t* d_counts, void* d_kept, uint64_t kept_cap, hipStream_t s);
+hipError_t hs_launch_dt_round(const uint64_t* d_key, const uint64_t* d_val, uint32_t n_hits, uint32_t self_first,
+                              uint32_t n, uint32_t first, uint32_t count, uint32_t min_pts, uint64_t* d_core,
+                              uint64_t* d_thr, uint64_t* d_next, uint32_t* d_cnt, uint64_t* d_counts, hipStream_t s);
+hipError_t hs_launch_dt_core_finish(uint64_t* d_core, uint32_t n, uint64_t* d_counts, hipStream_t s);
+hipError_t hs_launch_dt_min_d_hits(const uint64_t* d_key, const uint64_t* d_val, uint32_t n_hits, uint32_t self_first,
+                                   const uint64_t* d_core, const uint32_t* d_comp, uint64_t* d_best_d, uint32_t n,
+                                   uint64_t* d_counts, hipStream_t s);
+hipError_t hs_launch_dt_min_pair_hits(const uint64_t* d_key, const uint64_t* d_val, uint32_t n_hits,
+                                      uint32_t self_first, const uint64_t* d_core, const uint32_t* d_comp,
+                                      const uint64_t* d_best_d, uint64_t* d_best_pair, uint32_t n, hipStream_t s);
+hipError_t hs_launch_dt_min_d_kept(const void* d_kept, uint64_t n_kept, const uint64_t* d_core, const uint32_t* d_comp,
+                                   uint64_t* d_best_d, uint32_t n, uint64_t* d_counts, hipStream_t s);
+hipError_t hs_launch_dt_min_pair_kept(const void* d_kept, uint64_t n_kept, const uint64_t* d_core,
+                                      const uint32_t* d_comp, const uint64_t* d_best_d, uint64_t* d_best_pair,
+                                      uint32_t n, hipStream_t s);
+hipError_t hs_launch_dt_finish(const uint32_t* d_comp, const uint64_t* d_core, uint32_t n, uint32_t* d_label,
+                               uint64_t* d_counts, hipStream_t s);
 // cluster profiles and radii from a label array (hs_summary.hip; the arrays are the state listed at its head).
 // group: sizes, validation (*d_err |= 1: a label that is neither HS_NOISE nor < n) and the two scans -- the caller
 // reads d_err[0], d_row_of[n] (rows) and d_off_of[n] (kept members) back before it goes on; members: the rows' labels

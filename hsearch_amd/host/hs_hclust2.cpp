@@ -5,7 +5,7 @@
 // (also -kmers/-len/-hash_K/-hash_L/-window/-threshold/-output) and its exit behaviour (missing
 // option -> help, exit 0, :223-226; runtime error -> stderr, exit 1).  Additions: --seed (planes
 // drawn like the reference's LSH constructor, table l seeded seed + l; default random_device as
-// the reference), --device, and -linkage greedy|single|dbscan (-M): `single` writes the connected components of the
+// the reference), --device, and -linkage greedy|single|dbscan|density (-M; density: the end of this comment): `single` writes the connected components of the
 // near-neighbour graph (hsearch::Components) in place of the greedy leader clusters, `dbscan` its density clusters
 // (hsearch::Dbscan) at -minpts M (-p; required with dbscan, an error without it); the default is the reference's.
 // -centers 1 (-C; with -linkage single or dbscan only) writes beside the clusters file the centroids of the clusters
@@ -13,6 +13,9 @@
 // covering radii as <o>hclust.radii.txt (hsearch::ClusterCenters): the -c / --radii inputs of hs_motif_both_points.
 // -tree 1 (-t; with -linkage single only) writes beside the clusters file the single-linkage tree up to the threshold
 // as <o>hclust.tree.txt (hsearch::SingleLinkageTree): one line per merge, in merge order.
+// -linkage density -minpts M (hsearch::DensityTree): the clusters file holds the DBSCAN* clusters at the threshold
+// (dbscan's without their border k-mers), <o>hclust.core.txt every k-mer's core distance; with it -tree 1 writes the
+// density tree -- DBSCAN at every radius up to the threshold -- in the same format, and -centers 1 works as for dbscan.
 #include <stdio.h>
 #include <stdlib.h>
 #include <time.h>
@@ -43,7 +46,8 @@ const Opt kOpts[] = {
     {"seed", 's', "seed of the LSH planes [random_device]", false},
     {"device", 'G', "GPU ordinal [0]", false},
     {"linkage", 'M', "greedy (the reference's leader clusters) | single (connected components) | dbscan (density "
-                     "clusters, needs -minpts) [greedy]", false},
+                     "clusters, needs -minpts) | density (the density tree: dbscan at every radius up to the "
+                     "threshold, needs -minpts; writes <output>hclust.core.txt) [greedy]", false},
     {"minpts", 'p', "dbscan: neighbours within the threshold, the k-mer itself counted, that make a k-mer dense", false},
     {"centers", 'C', "1: also write <output>hclust.format.txt (centroids) and <output>hclust.radii.txt (covering radii) "
                      "of the clusters; with -linkage single or dbscan [0]", false},
@@ -106,17 +110,22 @@ int main(int argc, const char* argv[]) {
   const double hash_R = strtod(val["threshold"].c_str(), nullptr);
   const int device = val.count("device") ? atoi(val["device"].c_str()) : 0;
   const std::string linkage = val.count("linkage") ? val["linkage"] : "greedy";
-  if (linkage != "greedy" && linkage != "single" && linkage != "dbscan") {
-    fprintf(stderr, "ERROR: -linkage must be greedy, single or dbscan, not '%s'\n", linkage.c_str());
+  const bool density = linkage == "density";
+  if (linkage != "greedy" && linkage != "single" && linkage != "dbscan" && !density) {
+    fprintf(stderr, "ERROR: -linkage must be greedy, single, dbscan or density, not '%s'\n", linkage.c_str());
     return EXIT_FAILURE;
   }
-  if ((linkage == "dbscan") != (val.count("minpts") != 0)) {
+  if (density && !val.count("minpts")) {
+    fprintf(stderr, "ERROR: -linkage density needs -minpts\n");
+    return EXIT_FAILURE;
+  }
+  if (!density && (linkage == "dbscan") != (val.count("minpts") != 0)) {
     fprintf(stderr, linkage == "dbscan" ? "ERROR: -linkage dbscan needs -minpts\n"
                                         : "ERROR: -minpts goes with -linkage dbscan only\n");
     return EXIT_FAILURE;
   }
   uint32_t min_pts = 0;
-  if (linkage == "dbscan") {
+  if (linkage == "dbscan" || density) {
     char* end = nullptr;
     const unsigned long long m = strtoull(val["minpts"].c_str(), &end, 10);
     if (end == val["minpts"].c_str() || *end || m < 1 || m > 0xffffffffull || val["minpts"][0] == '-') {
@@ -156,7 +165,7 @@ int main(int argc, const char* argv[]) {
     return EXIT_FAILURE;
   }
   const bool tree = val.count("tree") && val["tree"] == "1";
-  if (tree && linkage != "single") {
+  if (tree && linkage != "single" && !density) {
     fprintf(stderr, "ERROR: -tree goes with -linkage single only: the tree is the single-linkage tree\n");
     return EXIT_FAILURE;
   }
@@ -180,7 +189,10 @@ int main(int argc, const char* argv[]) {
     std::cout << "Clustering... " << std::endl;
     std::string err;
     uint64_t n_clusters = 0;
-    const int st = linkage == "dbscan"
+    const int st = density
+                       ? hsearch::DensityTree(kmers, hash_K, hash_L, hash_W, hash_R, min_pts, val["output"], planes,
+                                              device, &err, tree, &n_clusters, nullptr, seed, centers_min_size)
+                   : linkage == "dbscan"
                        ? hsearch::Dbscan(kmers, hash_K, hash_L, hash_W, hash_R, min_pts, val["output"], planes, device,
                                          &err, &n_clusters, seed, centers_min_size)
                    : tree

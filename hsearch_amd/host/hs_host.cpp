@@ -1005,9 +1005,14 @@ int SingleLinkageTree(const std::vector<Kmer>& kmers, const uint32_t& hash_K, co
                           unknown_seed, centers_min_size, true, n_tree_edges);
 }
 
-int Dbscan(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
-           const double& hash_R, const uint32_t& min_pts, const std::string& output_file, const Planes& planes, int device,
-           std::string* err, uint64_t* n_clusters, uint32_t unknown_seed, uint32_t centers_min_size) {
+// Dbscan and DensityTree: the same clusters file; density: the labels come from hs_density_tree (border k-mers are
+// noise), whose core distances go to <output_file>hclust.core.txt and, with tree, whose tree edges go to
+// <output_file>hclust.tree.txt
+static int DbscanOrDensity(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L,
+                           const double& hash_W, const double& hash_R, const uint32_t& min_pts,
+                           const std::string& output_file, const Planes& planes, int device, std::string* err,
+                           uint64_t* n_clusters, uint32_t unknown_seed, uint32_t centers_min_size, bool density,
+                           bool tree, uint64_t* n_tree_edges) {
   std::vector<uint8_t> codes;
   const int cs = ClusterCodes(kmers, hash_K, hash_L, hash_W, planes, unknown_seed, &codes, err);
   if (cs != HS_OK) return cs;
@@ -1029,9 +1034,22 @@ int Dbscan(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_
     what = "hs_index_build";
     st = hs_index_build(h, codes.data(), n);
   }
-  if (st == HS_OK) {
+  if (st == HS_OK && !density) {
     what = "hs_dbscan";
     st = hs_dbscan(h, hash_R, 1, min_pts, label.data(), nullptr, &counts);  // hclust2's test: sqrt(d2) <= R
+  }
+  std::vector<uint32_t> tree_lo, tree_hi;
+  std::vector<double> tree_w, core;
+  if (st == HS_OK && density) {
+    what = "hs_density_tree";
+    tree_lo.resize(n);  // at most n - 1 tree edges: sized once
+    tree_hi.resize(n);
+    tree_w.resize(n);
+    core.resize(n);
+    hs_density_info info;
+    st = hs_density_tree(h, hash_R, 1, min_pts, tree_lo.data(), tree_hi.data(), tree_w.data(), n, label.data(),
+                         core.data(), &info);
+    if (st == HS_OK) tree_lo.resize(info.n_tree_edges);
   }
   if (st != HS_OK) {
     if (err) *err = std::string(what) + ": " + (h ? hs_last_error(h) : "no handle");
@@ -1074,7 +1092,54 @@ int Dbscan(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_
   }
   fout.close();
   if (n_clusters) *n_clusters = cluster_id;
+  if (density) {
+    // one line per k-mer: its name and core distance ("inf": none); %.17g reads back to the same double
+    std::ofstream fcore((output_file + "hclust.core.txt").c_str());
+    if (!fcore) {
+      if (err) *err = "cannot write " + output_file + "hclust.core.txt";
+      return HS_ERR_IO;
+    }
+    for (size_t i = 0; i < n; ++i) {
+      char num[64];
+      if (core[i] < HUGE_VAL)
+        snprintf(num, sizeof(num), "%.17g", core[i]);
+      else
+        snprintf(num, sizeof(num), "inf");
+      fcore << kmers[i].name << " " << num << "\n";
+    }
+    fcore.close();
+  }
+  if (density && tree) {
+    // the format of SingleLinkageTree: one line per tree edge in merge order, the weight the merge height
+    std::ofstream ftree((output_file + "hclust.tree.txt").c_str());
+    if (!ftree) {
+      if (err) *err = "cannot write " + output_file + "hclust.tree.txt";
+      return HS_ERR_IO;
+    }
+    for (size_t t = 0; t < tree_lo.size(); ++t) {
+      char num[64];
+      snprintf(num, sizeof(num), "%.17g", tree_w[t]);
+      ftree << kmers[tree_lo[t]].name << " " << kmers[tree_hi[t]].name << " " << num << "\n";
+    }
+    ftree.close();
+  }
+  if (n_tree_edges) *n_tree_edges = tree_lo.size();
   return HS_OK;
+}
+
+int Dbscan(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
+           const double& hash_R, const uint32_t& min_pts, const std::string& output_file, const Planes& planes, int device,
+           std::string* err, uint64_t* n_clusters, uint32_t unknown_seed, uint32_t centers_min_size) {
+  return DbscanOrDensity(kmers, hash_K, hash_L, hash_W, hash_R, min_pts, output_file, planes, device, err, n_clusters,
+                         unknown_seed, centers_min_size, false, false, nullptr);
+}
+
+int DensityTree(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
+                const double& hash_R, const uint32_t& min_pts, const std::string& output_file, const Planes& planes,
+                int device, std::string* err, bool tree, uint64_t* n_clusters, uint64_t* n_tree_edges,
+                uint32_t unknown_seed, uint32_t centers_min_size) {
+  return DbscanOrDensity(kmers, hash_K, hash_L, hash_W, hash_R, min_pts, output_file, planes, device, err, n_clusters,
+                         unknown_seed, centers_min_size, true, tree, n_tree_edges);
 }
 
 int Clustering(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L,

@@ -230,7 +230,16 @@ int SingleLinkageTree(const std::vector<Kmer>& kmers, const uint32_t& hash_K, co
 int Dbscan(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
            const double& hash_R, const uint32_t& min_pts, const std::string& output_file, const Planes& planes, int device,
            std::string* err, uint64_t* n_clusters = nullptr, uint32_t unknown_seed = 0, uint32_t centers_min_size = 0);
-// centers_min_size != 0 (Components, Dbscan): beside the clusters file, ClusterCenters() of the labels just found.
+// The density tree (hs_density_tree in include/hsearch.h: DBSCAN at every radius up to R) of the same graph at min_pts.
+// The clusters file, in Dbscan's format, holds the DBSCAN* clusters at R: Dbscan's with their border k-mers moved to
+// the noise block.  <output_file>hclust.core.txt always: one line per k-mer, "<name> <core distance>", "inf" for none.
+// With tree, <output_file>hclust.tree.txt in SingleLinkageTree's format: one line per merge in merge order, the
+// mutual-reachability weight as the distance.  Numbers with 17 significant digits: they read back bit for bit.
+int DensityTree(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
+                const double& hash_R, const uint32_t& min_pts, const std::string& output_file, const Planes& planes,
+                int device, std::string* err, bool tree = false, uint64_t* n_clusters = nullptr,
+                uint64_t* n_tree_edges = nullptr, uint32_t unknown_seed = 0, uint32_t centers_min_size = 0);
+// centers_min_size != 0 (Components, Dbscan, DensityTree): beside the clusters file, ClusterCenters() of the labels just found.
 // From cluster labels to the `-c` / `--radii` inputs of motif_both_points, on the handle that holds the k-mers'
 // index: label [n] as hs_components / hs_dbscan return it (HS_NOISE or a value < n).  Per cluster of at least min_size
 // members, in ascending label, <output_file>hclust.format.txt receives its centroid (hs_cluster_profile) in

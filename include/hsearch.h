@@ -656,6 +656,92 @@ HS_API hs_status hs_msf_edges(const uint32_t* ei, const uint32_t* ej, const doub
 HS_API hs_status hs_msf_cut(const uint32_t* lo, const uint32_t* hi, const double* dist, uint64_t m, uint64_t n,
                             double r, uint32_t* label, uint64_t* n_components);
 
+/* ---- density tree: DBSCAN at every radius up to R (the DBSCAN* hierarchy) ----------------------------------- */
+
+/* hs_dbscan answers at ONE (R, min_pts); choosing R from the degrees is a ladder of hs_dbscan calls at two self-joins
+ * each.  The minimum spanning forest under the mutual-reachability distance (Campello, Moulavi, Sander 2013: the tree
+ * HDBSCAN is built on) holds the density clusters of every radius r <= R at one min_pts, as hs_msf holds the
+ * components of every radius.
+ *
+ * Contract: let G be the graph of hs_self_join(h, R, sqrt_test, ...) on the same handle, exactly as in hs_components,
+ * hs_dbscan and hs_msf -- the same bucket rule over all L tables, the same exact fp64 test, self pairs dropped; the
+ * handle's multi-probe setting and bucket partition are ignored.  d{a,b} is the edge_dist the self-join reports, the
+ * same bits in both directions (see hs_msf).
+ *   core distance     core[i], for min_pts >= 1 (0 is HS_ERR_INVALID).  min_pts == 1: +0.0.  Otherwise the
+ *                     (min_pts - 1)-th smallest value of the multiset { d{i,j} : j adjacent to i }, counted WITH
+ *                     multiplicity (three neighbours at distance 0 count three times); +infinity if degree[i] <
+ *                     min_pts - 1.  So core[i] <= r exactly when i is a core point of hs_dbscan(h, r, 1, min_pts), for
+ *                     every r <= R.
+ *   mutual reach.     w{a,b} = max(core[a], core[b], d{a,b}), compared as doubles.  A pair with an infinite end is not
+ *                     an edge.
+ *   density tree      the minimum spanning forest of G under the strict total order (w, lo, hi), lo < hi.  It is
+ *                     unique, hence a pure function of the index, R, sqrt_test and min_pts.  It has n_core - n_clusters
+ *                     edges (n_core: the k-mers with a finite core distance), returned in ascending (w, lo, hi): the
+ *                     merge order, w the merge height.
+ *   label [n]         (may be NULL) for a k-mer with a finite core distance the smallest id of its component: bit for
+ *                     bit hs_dbscan(h, R, sqrt_test, min_pts)'s label on the core k-mers.  For every other k-mer
+ *                     HS_NOISE.  This is DBSCAN*: BORDER K-MERS ARE NOISE.  The border rule of hs_dbscan ("the core
+ *                     neighbour with the smallest id") is a choice made per radius -- which neighbours are core, and
+ *                     which are within reach, changes with r -- and a tree of merges between core k-mers cannot carry
+ *                     it; a caller who wants borders at one r runs hs_dbscan there.
+ *   core [n]          (may be NULL) the core distances.
+ * min_pts == 1 gives hs_msf's edges, distances and labels bit for bit.
+ *
+ * hs_core_distance: core [n], *n_core (the finite ones), *n_edges (may be NULL) = hs_self_join's: one self-join.
+ * hs_density_tree: capacity follows the two-call pattern exactly as hs_msf -- HS_ERR_CAPACITY with *out set and
+ * nothing else written (neither edges nor label nor core, in the _dev form either); buffers sized once at n hold every
+ * result.  Errors as in hs_dbscan / hs_msf: an unbuilt index is HS_ERR_STATE, a NaN R or min_pts == 0 HS_ERR_INVALID;
+ * *out is zeroed first.  out->rounds as in hs_msf; out->self_joins the passes that ran the join.
+ *
+ * The passes.  core[b] of a later batch is unknown while an earlier one is reduced, so the core distances take a
+ * self-join of their own; then hs_msf's rounds run on w.  Resident (the default when it fits): that first self-join
+ * also keeps every pair once with its RAW distance, 16 bytes per unordered pair, and every later pass reads the list:
+ * 1 self-join.  Re-join: 1 + 1 + 2 rounds self-joins (the core pass, the first look for crossing pairs, two per
+ * round).  HS_OPT_MSF_EDGE_BUDGET governs the list as it does for hs_msf, and a list that outgrows it falls back to
+ * re-joining, visible in out->resident and out->self_joins alone.  An option selects a path, never a result.
+ * State of the handle: hs_msf's 56 bytes per indexed k-mer and 28 more (core distance, threshold and round minimum as
+ * 64-bit words, a 32-bit count), allocated by the first such call and kept with the handle; the kept list as hs_msf.
+ * Every existing entry point runs as before, launch for launch.
+ *
+ * hs_density_tree_edges (host only, no GPU, no handle): the same rule for ANY list of weighted pairs over the vertices
+ * 0 .. n-1.  It accepts what hs_msf_edges accepts -- either or both directions of a pair, repeats, any order, self
+ * pairs ignored -- and rejects what it rejects: an id >= n, a NaN or negative distance, two occurrences of one
+ * unordered pair with different bits, and min_pts == 0 are HS_ERR_INVALID, reported before anything is written.
+ * A distance of -0.0 is read as +0.0 (so -0.0 and +0.0 for one pair do not conflict, and no output carries a sign bit).
+ * out->n_graph_edges is twice the distinct unordered pairs; rounds, resident and self_joins are 0.  This is the
+ * multi-GPU route, over the gathered hs_self_join_range edges of the ranks.  (Unlike hs_msf_edges it is NOT a merge
+ * of forests: core distances need all edges of a vertex.)
+ *
+ * hs_density_tree_cut (host only): a k-mer with core[i] > r is HS_NOISE (and one without a core distance, +infinity,
+ * at every r, r = +infinity included); the rest are labelled with the smallest id
+ * per component of the tree edges with w <= r; *n_clusters counts those components.  With sqrt_test != 0 and r <= R
+ * the labels of hs_density_tree's tree cut at r equal hs_dbscan(h, r, 1, min_pts)'s on the k-mers that are core at r
+ * exactly: sqrt(d2) <= r is the edge test of both.  With sqrt_test == 0 the equality is only guaranteed for the full
+ * forest against hs_dbscan(h, R, 0, min_pts): d2 <= r*r and sqrt(d2) <= r may differ in the last bit.  An input that is
+ * not a forest over 0 .. n-1 (an id >= n, a self pair, a NaN weight, an edge that closes a cycle), a NaN r, a core
+ * entry that is NaN or negative, and a tree edge with w smaller than either end's core distance are HS_ERR_INVALID;
+ * label is not written then. */
+typedef struct hs_density_info {
+  uint64_t n_tree_edges, n_clusters, n_core, n_graph_edges; /* n_graph_edges = hs_self_join's *n_edges */
+  uint32_t rounds, resident, self_joins;                     /* self_joins: passes that ran the join */
+} hs_density_info;
+HS_API hs_status hs_core_distance(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, double* core,
+                                  uint64_t* n_core, uint64_t* n_edges);
+HS_API hs_status hs_core_distance_dev(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, double* d_core,
+                                      uint64_t* n_core, uint64_t* n_edges);
+HS_API hs_status hs_density_tree(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, uint32_t* edge_lo,
+                                 uint32_t* edge_hi, double* edge_w, uint64_t cap, uint32_t* label, double* core,
+                                 hs_density_info* out);
+/* ... the arrays in device memory, *out on the host (streams: as hs_query_dev) */
+HS_API hs_status hs_density_tree_dev(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, uint32_t* d_edge_lo,
+                                     uint32_t* d_edge_hi, double* d_edge_w, uint64_t cap, uint32_t* d_label,
+                                     double* d_core, hs_density_info* out);
+HS_API hs_status hs_density_tree_edges(const uint32_t* ei, const uint32_t* ej, const double* dist, uint64_t n_edges,
+                                       uint64_t n, uint32_t min_pts, uint32_t* out_lo, uint32_t* out_hi, double* out_w,
+                                       uint64_t cap, uint32_t* label, double* core, hs_density_info* out);
+HS_API hs_status hs_density_tree_cut(const uint32_t* lo, const uint32_t* hi, const double* w, uint64_t m,
+                                     const double* core, uint64_t n, double r, uint32_t* label, uint64_t* n_clusters);
+
 /* ---- cluster profiles, centroids and covering radii from a label array ------------------------------------ */
 
 /* The step from cluster labels to what a search takes: per cluster its members' position frequency matrix, their
