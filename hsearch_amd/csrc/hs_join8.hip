@@ -1003,6 +1003,27 @@ __device__ __forceinline__ uint32_t and_tree_x(const intx4 (&acc)[4][2]) {
   return a;
 }
 
+// The same test for hs_join8x_kernel's loop, ONE instruction at a time: the signed maximum of a group's 32
+// accumulators -- negative exactly when every one of them is, so its callers test (int)w[15] >= 0 like those of
+// and_tree_x -- on a tree of three-input maxima (v_max3_i32), 16 instructions of which the caller places step g in
+// the gap behind its g-th MFMA.  Steps 0..9 reduce the elements 3 g .. 3 g + 2 (element i = acc[i >> 3][(i >> 2) & 1]
+// [i & 3]: the order the MFMAs delivered them in), 10..12 the results of those, 13 the tenth result and the last
+// two elements, 14 and 15 what is left.  Only steps 13 and 15 need the result of the step right before them.
+// (As one expression the compiler forms a chain -- v_bitop3_b32 for the AND, the same 16 instructions -- and the
+// scheduler, asked for one of them per gap, left most of the chain in the first gaps of phase 1, three to a gap, and
+// behind the last MFMA of phase 2, where no MFMA of the wave hides them.)
+__device__ __forceinline__ void sign_step_x(int g, const intx4 (&acc)[4][2], int (&w)[16]) {
+  auto v = [&](int i) { return acc[i >> 3][(i >> 2) & 1][i & 3]; };
+  if (g < 10) w[g] = max(max(v(3 * g), v(3 * g + 1)), v(3 * g + 2));
+  else if (g < 13) w[g] = max(max(w[3 * (g - 10)], w[3 * (g - 10) + 1]), w[3 * (g - 10) + 2]);
+  else if (g == 13) w[13] = max(max(w[9], v(30)), v(31));
+  else if (g == 14) w[14] = max(max(w[10], w[11]), w[12]);
+  else w[15] = max(w[13], w[14]);
+  // the value is wanted HERE: without this the optimiser re-associates the maxima into a tree of its own and
+  // computes it behind the caller's last MFMA
+  asm volatile("" : "+v"(w[g]));
+}
+
 // Survivors of one group (row tiles T0 .. T0 + 3) against the 16 NCOL queries at segment-relative offset qc
 template <int NCOL = 2>
 __device__ __forceinline__ void emit_survivors_x(const intx4 (&acc)[4][2], int T0, uint32_t qc, uint32_t qoff,
@@ -1232,40 +1253,34 @@ __global__ __launch_bounds__(256, 2) void hs_join8x_kernel(
         const uint32_t qc = qc0 + 32u * (uint32_t)u;
         intx4 (&B)[2][2] = Bq[u];
         if (u == 0 || qc < q_end) {
-          // ---- phase 1: X <- row tiles 0..3 x B, beside the sign test of Y (previous query tile)
-          const uint32_t sY = and_tree_x(accY);
-#pragma unroll
-          for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-              for (int c = 0; c < 2; ++c)
-                accX[t][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[t][s], B[s][c],
-                                                                   s ? accX[t][c] : intx4{0, 0, 0, 0}, 0, 0, 0);
+          // ---- phase 1: X <- row tiles 0..3 x B, beside the sign test of Y (previous query tile): one step of
+          // the test behind every MFMA, the order pinned (8 cycles of vector issue for the MFMA + 4 for the
+          // step in a gap of 16)
+          int wY[16];
 #pragma unroll
           for (int g = 0; g < 16; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
+            const int s = g >> 3, t = (g >> 1) & 3, c = g & 1;
+            accX[t][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[t][s], B[s][c],
+                                                               s ? accX[t][c] : intx4{0, 0, 0, 0}, 0, 0, 0);
+            if (y_live) sign_step_x(g, accY, wY);  // (the item's first tile: Y holds nothing yet)
+            __builtin_amdgcn_sched_barrier(0);
           }
+          const uint32_t sY = y_live ? (uint32_t)wY[15] : 0x80000000u;
           if (y_live && __ballot((int)sY >= 0))
             emit_survivors_x(accY, 4, prev_qc, qoff, q_end, wbase, M, mstart, lane, res_base, res_used,
                              prov_count, prov_cap, prov);
           y_live = true;
           // ---- phase 2: Y <- row tiles 4..7 x B, beside the sign test of X
-#pragma unroll
-          for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-              for (int c = 0; c < 2; ++c)
-                accY[t][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[4 + t][s], B[s][c],
-                                                                   s ? accY[t][c] : intx4{0, 0, 0, 0}, 0, 0, 0);
-          const uint32_t sX = and_tree_x(accX);
+          int wX[16];
 #pragma unroll
           for (int g = 0; g < 16; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
+            const int s = g >> 3, t = (g >> 1) & 3, c = g & 1;
+            accY[t][c] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[4 + t][s], B[s][c],
+                                                               s ? accY[t][c] : intx4{0, 0, 0, 0}, 0, 0, 0);
+            sign_step_x(g, accX, wX);
+            __builtin_amdgcn_sched_barrier(0);
           }
+          const uint32_t sX = (uint32_t)wX[15];
           if (__ballot((int)sX >= 0))
             emit_survivors_x(accX, 0, qc, qoff, q_end, wbase, M, mstart, lane, res_base, res_used,
                              prov_count, prov_cap, prov);
