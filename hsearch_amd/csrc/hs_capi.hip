@@ -206,7 +206,7 @@ struct hs_handle {
   DevBuf t_pos;  // [L][n] sorted position of every DB id in every table (first-seen dedupe)
   DevBuf dir_base;       // [L + 1] first global bucket number of every table; [L] = nb_total
   uint32_t nb_total = 0;  // buckets of all tables
-  DevBuf bucket_work;    // per-batch: counts + 3 work arrays over the nb_total + 2 bucket slots
+  DevBuf bucket_work;    // per-batch: counts + their 64-bit double scan over the nb_total + 2 bucket slots
   hs_tables_dev tabs;
   hs_index_info info;
   // query workspace (grown on demand, reused across calls)
@@ -263,7 +263,7 @@ struct hs_handle {
   uint32_t shard_lo = 0, shard_cnt = 0, shard_seed = 0, shard_nb = 0;
   int shard_table = -1;
   DevBuf seg_of;    // query_batch: the segment of every sorted probe position
-  DevBuf seg_res;   // cut_items: flags + scan of the segments that go to the query-resident join kernel
+  DevBuf seg_res;   // cut_items: the scan of the segments' class flags (many queries | query-resident kernel)
   DevBuf c16s, item_desc, probe_slow, jtab8, qhits;  // qhits: per-query hit counts, offsets, fill
   DevBuf c8b, prov2;  // survivor refinement: second int8 row per query, the refined survivor list
   bool join8_tables_ok = false;  // int8 can carry the coordinate table
@@ -954,44 +954,32 @@ static inline int seg_shift_of(const hs_handle* h) {
 }
 
 // Segments -> work items of jm members x <= 2048 queries: routing (join or streaming), the item
-// numbering order (many-query segments first), item offsets.  Workspace reuse: seg_keys = flags and
-// their scan, seg_vals = order, seg_keys_sorted = item counts in that order (all free by now).
-// max_q_res > 0: segments with at most that many probing queries form the item list's tail, whose bounds
-// go to seg_n[2..3] (hs_join8r_kernel's share).
+// numbering order (many-query segments first), item offsets.  Workspace reuse: seg_keys = the class flags (two
+// to a 64-bit word), seg_res = their scan, seg_vals = order, seg_keys_sorted = item counts in that order (all free
+// by now).  max_q_res > 0: segments with at most that many probing queries form the item list's tail, whose bounds
+// hs_launch_item_desc leaves in seg_n[2..3] (hs_join8r_kernel's share) from the scan's last word.
+// clear_slices: the probes wrote slice counts although every segment is joined (bucket partition): cleared here.
 static hs_status cut_items(hs_handle* h, uint32_t nql, uint32_t jm, unsigned long long* d_jstats,
-                           uint32_t max_q_res, uint32_t n_probes) {
+                           uint32_t max_q_res, uint32_t n_probes, bool clear_slices) {
   const size_t n1 = (size_t)nql + 1;
   // every segment with a member goes to the join (the default): no probe keeps a slice for the streaming filter
   const bool all_joined = h->join_min_q == 1 && h->join_min_m == 1;
-  uint32_t* big = h->seg_keys.as<uint32_t>();
-  uint32_t* big_pos = big + n1;
+  uint64_t* cls = h->seg_keys.as<uint64_t>();
+  HS_HIP(h, h->seg_res.reserve(n1 * 8));
+  uint64_t* cls_pos = h->seg_res.as<uint64_t>();
   uint32_t* order = h->seg_vals.as<uint32_t>();
   uint32_t* items_ord = h->seg_keys_sorted.as<uint32_t>();
-  uint32_t *res = nullptr, *res_pos = nullptr;
-  if (max_q_res) {
-    HS_HIP(h, h->seg_res.reserve(2 * n1 * 4));
-    res = h->seg_res.as<uint32_t>();
-    res_pos = res + n1;
-  }
   HS_HIP(h, hs_launch_seg_route(h->seg_key.as<uint64_t>(), h->seg_cnt.as<uint32_t>(),
                                 h->seg_qoff.as<uint32_t>(), h->seg_n.as<uint32_t>(),
                                 h->sorted_ql.as<uint32_t>(), h->qcount.as<uint32_t>(), nql,
-                                h->join_min_q, h->join_min_m, jm, (int)h->p.L, seg_shift_of(h), max_q_res,
-                                h->seg_items.as<uint32_t>(), d_jstats, all_joined ? nullptr : h->nslices.as<uint32_t>(),
-                                h->seg_of.as<uint32_t>(), h->stream));
-  if (all_joined) HS_HIP(h, hipMemsetAsync(h->nslices.p, 0, (size_t)n_probes * 4, h->stream));
-  HS_HIP(h, hipMemsetAsync(big + nql, 0, 4, h->stream));
-  if (res) HS_HIP(h, hipMemsetAsync(res + nql, 0, 4, h->stream));
-  HS_HIP(h, hipMemsetAsync(items_ord + nql, 0, 4, h->stream));
-  HS_HIP(h, hs_launch_seg_big(h->seg_cnt.as<uint32_t>(), h->seg_items.as<uint32_t>(), nql, 512u, max_q_res, big,
-                              res, h->stream));
-  HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, big, big_pos, n1, h->stream));
-  if (res) HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, res, res_pos, n1, h->stream));
-  HS_HIP(h, hs_launch_seg_order(big_pos, res_pos, h->seg_items.as<uint32_t>(), nql, order, items_ord,
-                                h->stream));
+                                h->join_min_q, h->join_min_m, jm, (int)h->p.L, seg_shift_of(h), max_q_res, 512u,
+                                h->seg_items.as<uint32_t>(), cls, d_jstats,
+                                all_joined ? nullptr : h->nslices.as<uint32_t>(), h->seg_of.as<uint32_t>(), h->stream));
+  if (all_joined && clear_slices) HS_HIP(h, hipMemsetAsync(h->nslices.p, 0, (size_t)n_probes * 4, h->stream));
+  HS_HIP(h, hs_exclusive_scan_u64(h->temp.p, h->temp.cap, cls, cls_pos, n1, h->stream));
+  HS_HIP(h, hs_launch_seg_order(cls_pos, h->seg_items.as<uint32_t>(), nql, order, items_ord, h->stream));
   HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, items_ord, h->item_off.as<uint32_t>(), n1,
                                   h->stream));
-  HS_HIP(h, hs_launch_item_split(h->item_off.as<uint32_t>(), res_pos, nql, h->seg_n.as<uint32_t>() + 2, h->stream));
   return HS_OK;
 }
 
@@ -2258,6 +2246,7 @@ struct BatchPlan {
   bool seg_sparse = false;  // probes grouped by a sort of the probes, not a counting sort over the buckets
   bool parted = false;      // bucket partition: only this part's probes are fingerprinted and grouped
   bool all_joined = false;  // every segment goes to the join (HS_OPT_JOIN_MIN_Q / _M at 1)
+  bool no_slices = false;   // ... so the probes write no slice counts and the slice offsets stay the reset's zeros
   bool use_r = false;       // segments with few probing queries through hs_join8r_kernel
   uint32_t jm = HS_JM_BLOCK;  // members per join work item
   bool async_items = false;   // the item count stays on the device; the descriptors are sized by item_cap
@@ -2298,6 +2287,8 @@ static BatchPlan plan_batch(const hs_handle* h, const QueryCall& c, uint32_t nq,
   p.parted = p.use_join && h->bucket_parts > 1 && c.self_first == HS_NO_SELF;  // (searches only)
   p.seg_sparse = p.parted || (h->knobs.seg_mode ? h->knobs.seg_mode == 1 : (uint64_t)h->nb_total > 2ull * nq * h->p.L);
   p.all_joined = h->join_min_q == 1 && h->join_min_m == 1;
+  // (a bucket partition's list of owned probes is made by a kernel that writes the slice counts of all of them)
+  p.no_slices = p.use_join && p.all_joined && !p.parted;
   // work items: one wave's 128 members for the wave-independent int8 join, 512 otherwise
   p.jm = p.use_i8 ? hs_join8_members_per_item(k, p.wide) : HS_JM_BLOCK;
   // k <= 25 with 4-column rows: segments probed by at most HS_JR_MAXQ queries of the batch go to the
@@ -2363,25 +2354,27 @@ static hipError_t launch_probe(hs_handle* h, const QueryCall& c, const BatchPlan
   uint32_t* const bucket_count = p.use_join && !p.seg_sparse ? h->bucket_work.as<uint32_t>() : nullptr;
   uint32_t* const qrank = bucket_count ? qbucket + ((size_t)b.nql + 1) : nullptr;
   unsigned long long* const d_cand_total = reinterpret_cast<unsigned long long*>(h->counters.as<uint32_t>() + 2);
+  uint32_t* const nslices = (p.use_join && p.no_slices) ? nullptr : h->nslices.as<uint32_t>();
   if (p.self_codes)
     return hs_launch_self_probe(h->tabs, c.self_first + b.q_base, b.nq, (int)h->p.L, h->qstart.as<uint32_t>(),
-                                h->qcount.as<uint32_t>(), h->nslices.as<uint32_t>(), b.d_cand, d_cand_total,
+                                h->qcount.as<uint32_t>(), nslices, b.d_cand, d_cand_total,
                                 h->dir_base.as<uint32_t>(), h->nb_total, bucket_count, qbucket, qrank, h->stream);
   return hs_launch_probe(probe_tabs(h, c, b.q_base, b.owned, b.n_owned), h->qints.as<int32_t>(), b.nq, (int)h->p.K,
                          (int)h->p.L, h->key_seed, h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(),
-                         h->nslices.as<uint32_t>(), b.d_cand, d_cand_total, h->probe_slow.as<uint32_t>(),
+                         nslices, b.d_cand, d_cand_total, h->probe_slow.as<uint32_t>(),
                          h->dir_base.as<uint32_t>(), h->nb_total, bucket_count, qbucket, qrank, h->stream);
 }
 
 // Work items of the plan's size from the segments, the resident kernel's class as their tail
 static hs_status cut_plan_items(hs_handle* h, const BatchPlan& p, const Batch& b) {
   unsigned long long* const d_jstats = reinterpret_cast<unsigned long long*>(h->counters.as<uint32_t>() + 10);
-  return cut_items(h, b.nqs, p.jm, d_jstats, p.use_r ? HS_JR_MAXQ : 0u, b.nql);
+  return cut_items(h, b.nqs, p.jm, d_jstats, p.use_r ? HS_JR_MAXQ : 0u, b.nql, !p.no_slices);
 }
 
 // Where every probe's slices start in the streaming filter's grid (every segment joined -- the default --:
-// all slice counts are zero by now, and so is their scan)
+// all slice counts are zero, and so is their scan: the batch's reset left it so when no probe wrote a count)
 static hipError_t slice_offsets(hs_handle* h, const BatchPlan& p, const Batch& b) {
+  if (p.use_join && p.no_slices) return hipSuccess;
   if (p.use_join && p.all_joined) return hipMemsetAsync(h->slice_off.p, 0, ((size_t)b.nql + 1) * 4, h->stream);
   return hs_exclusive_scan_u32(h->temp.p, h->temp.cap, h->nslices.as<uint32_t>(), h->slice_off.as<uint32_t>(),
                                (size_t)b.nql + 1, h->stream);
@@ -2443,7 +2436,6 @@ static hs_status hash_and_probe(hs_handle* h, const QueryCall& c, const BatchPla
     // (the sort of the probes needs no ranks and no pass over the bucket slots: hs_launch_seg_group_sparse)
     HS_HIP(h, h->bucket_work.reserve(4 * (p.seg_sparse ? n1 : (size_t)h->nb_total + 2) * 4));
   }
-  HS_HIP(h, hs_launch_set_u32(h->nslices.as<uint32_t>() + b.nql, 0u, h->stream));
   if (p.parted) {
     HS_HIP(h, h->part_work.reserve(5 * n1 * 4));
     uint32_t* const pw = h->part_work.as<uint32_t>();
@@ -2473,7 +2465,6 @@ static hs_status group_segments(hs_handle* h, const BatchPlan& p, Batch& b) {
   HS_HIP(h, h->temp.reserve(std::max(hs_scan_u32_temp(n1), hs_scan_u32_temp((size_t)h->nb_total + 2)) + 256));
   // (the query rows of the join filter were quantised on the side stream, beside hash and probe)
   HS_HIP(h, hipStreamWaitEvent(h->stream, h->evx[EV_JOIN], 0));
-  HS_HIP(h, hipMemsetAsync(h->seg_cnt.p, 0, n1 * 4, h->stream));
   const int L = (int)h->p.L, seg_shift = seg_shift_of(h);
   if (p.seg_sparse) {
     HS_HIP(h, h->temp.reserve(std::max(hs_sort_pairs_u32_u32_temp(b.nql), hs_scan_u32_temp(n1)) + 256));
@@ -2502,7 +2493,8 @@ static hs_status group_segments(hs_handle* h, const BatchPlan& p, Batch& b) {
                                          h->stream, probes_in));
   } else {
     HS_HIP(h, hs_launch_seg_group(h->tabs, h->dir_base.as<uint32_t>(), L, seg_shift, h->nb_total,
-                                  h->bucket_work.as<uint32_t>(), h->bucket_work.as<uint32_t>() + ((size_t)h->nb_total + 2),
+                                  h->bucket_work.as<uint32_t>(),
+                                  h->bucket_work.as<uint32_t>() + (((size_t)h->nb_total + 3) & ~(size_t)1),
                                   h->temp.p, h->temp.cap, h->seg_keys.as<uint32_t>(), h->seg_keys.as<uint32_t>() + n1,
                                   b.nql, h->sorted_ql.as<uint32_t>(), h->seg_key.as<uint64_t>(),
                                   h->seg_cnt.as<uint32_t>(), h->seg_n.as<uint32_t>(), h->seg_of.as<uint32_t>(),
@@ -2545,6 +2537,7 @@ static hs_status demote(hs_handle* h, const QueryCall& c, BatchPlan& p, Batch& b
     b.owned = nullptr;  // (every probe again)
     b.n_owned = 0;
     HS_HIP(h, hipMemsetAsync(d_cnt + 2, 0, 8, h->stream));
+    HS_HIP(h, hipMemsetAsync(h->probe_slow.p, 0, 4, h->stream));  // (the list of the probes left to the slow kernel)
     HS_HIP(h, launch_probe(h, c, p, b));
     HS_HIP(h, slice_offsets(h, p, b));
     b.n_slices = 1;
@@ -2576,6 +2569,7 @@ static hs_status read_items(hs_handle* h, const QueryCall& c, BatchPlan& p, Batc
                                   h->sorted_ql.as<uint32_t>(), h->qcount.as<uint32_t>(), b.n_items, p.jm,
                                   seg_shift_of(h), h->seg_vals.as<uint32_t>(), h->PW,
                                   p.async_items ? h->item_off.as<uint32_t>() + b.nqs : nullptr,
+                                  h->seg_res.as<uint64_t>(), h->seg_n.as<uint32_t>() + 2,
                                   h->item_desc.as<uint4>(), h->stream));
   }
   // segments routed away from the join (HS_OPT_JOIN_MIN_Q / _M; none by default) go through the streaming
@@ -2646,14 +2640,14 @@ static hs_status launch_filters(hs_handle* h, const BatchPlan& p, const Batch& b
 // Stage 6: the exact decision on the survivors (after the int8 join's 8-column refinement), and the hits
 // ordered per query into the caller's arrays when the plan says so.
 static hs_status finalize_hits(hs_handle* h, const QueryCall& c, const BatchPlan& p, const Batch& b,
-                               uint32_t prov_cap, uint32_t hit_cap, BatchOut* bout) {
+                               uint32_t prov_cap, uint32_t hit_cap, bool again, BatchOut* bout) {
   const int k = (int)h->p.k, L = (int)h->p.L;
   uint32_t* const d_cnt = h->counters.as<uint32_t>();
   const uint2* fin_list = h->prov.as<uint2>();
   const uint32_t* fin_count = d_cnt;
   if (p.refine && b.n_items) {
     HS_HIP(h, h->prov2.reserve((size_t)prov_cap * 8));
-    HS_HIP(h, hipMemsetAsync(d_cnt + 4, 0, 4, h->stream));
+    if (again) HS_HIP(h, hipMemsetAsync(d_cnt + 4, 0, 4, h->stream));  // (first pass: the batch's reset)
     HS_HIP(h, hs_launch_refine8(h->tabs, h->prov.as<uint2>(), d_cnt, prov_cap, h->sorted_ql.as<uint32_t>(), h->c16.p,
                                 h->c8b.p, h->jtab8.as<char>() + 1024, h->jtab8.as<float>() + 128, k, L,
                                 h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(), h->prov2.as<uint2>(), d_cnt + 4,
@@ -2695,8 +2689,10 @@ static hs_status search_pass(hs_handle* h, const QueryCall& c, const BatchPlan& 
     const size_t n1q = (size_t)b.nq + 1;
     HS_HIP(h, h->qhits.reserve((6 * n1q + 8) * 4));
     // per-query hit counts, offsets, fill, and behind them the lists of the queries a block orders
-    HS_HIP(h, hipMemsetAsync(h->qhits.p, 0, (3 * n1q + 8) * 4, h->stream));
-    if (again) HS_HIP(h, hipMemsetAsync(d_cnt + 20, 0, 4, h->stream));  // the "too many hits" flag
+    if (again) {  // (first pass: the batch's reset)
+      HS_HIP(h, hipMemsetAsync(h->qhits.p, 0, (3 * n1q + 8) * 4, h->stream));
+      HS_HIP(h, hipMemsetAsync(d_cnt + 20, 0, 4, h->stream));  // the "too many hits" flag
+    }
     HS_HIP(h, h->hit_kv.reserve((size_t)hit_cap * 16));
     HS_HIP(h, h->hit_rank.reserve((size_t)hit_cap * 4));
     HS_HIP(h, h->temp.reserve(hs_scan_u32_temp(n1q) + 256));
@@ -2705,7 +2701,7 @@ static hs_status search_pass(hs_handle* h, const QueryCall& c, const BatchPlan& 
   if (again) HS_HIP(h, hipMemsetAsync(d_cnt + 32, 0, 64, h->stream));  // the item counters again
   HS_CHECK(launch_filters(h, p, b, prov_cap, again));
   HS_HIP(h, hipEventRecord(h->ev[4], h->stream));
-  HS_CHECK(finalize_hits(h, c, p, b, prov_cap, hit_cap, bout));
+  HS_CHECK(finalize_hits(h, c, p, b, prov_cap, hit_cap, again, bout));
   HS_HIP(h, hipEventRecord(h->ev[5], h->stream));
   // [0] survivors [1] hits [2..3] candidates ... [10..13] join statistics [20] order fallback
   HS_HIP(h, hipMemcpyAsync(h->pin_cnt, d_cnt, 96, hipMemcpyDeviceToHost, h->stream));
@@ -2741,7 +2737,8 @@ static hs_status filter_passes(hs_handle* h, uint32_t nq, uint32_t item_cap, boo
     const uint32_t hit_cap = (uint32_t)std::max<size_t>(h->hit_key.cap / 8, prov_cap);
     HS_HIP(h, h->hit_key.reserve((size_t)hit_cap * 8));
     HS_HIP(h, h->hit_val.reserve((size_t)hit_cap * 8));
-    HS_HIP(h, hipMemsetAsync(d_cnt, 0, 8, h->stream));
+    // (first pass: both callers have just cleared all the counters)
+    if (launches) HS_HIP(h, hipMemsetAsync(d_cnt, 0, 8, h->stream));
     HS_CHECK(pass(prov_cap, hit_cap, launches != 0));
     HS_HIP(h, hipStreamSynchronize(h->stream));
     // > ~4e9 survivors: run_query halves the batch (HS_TEST_SPLIT_ABOVE=n: as if every batch of more
@@ -2869,6 +2866,41 @@ static void learn_from_batch(hs_handle* h, const QueryCall& c, const BatchPlan& 
   m.pairs_per_item = (double)issued / (double)b.n_items;
 }
 
+// Everything of a batch that starts from zero and whose place and size are known before its first kernel, in ONE
+// launch at its head (they were a dozen fills of 5 us each, most of them 4 bytes long): the counters, the slow
+// probes' list, the closing word of the slice counts, and with a join ahead the segment counts, the bucket
+// counters of the counting sort, and the slice offsets where no probe writes a count; the per-query hit counts
+// where the batch orders its hits.  The stages reserve the same buffers again (no-ops).  What a later pass of
+// the same batch needs cleared again (`again`, demote, the HS_SYNC_ITEMS retry through here) is re-issued there.
+static hs_status reset_batch(hs_handle* h, const BatchPlan& p, const Batch& b) {
+  const size_t n1 = (size_t)b.nql + 1, n1q = (size_t)b.nq + 1;
+  hs_zero_ranges z{};
+  auto add = [&](void* ptr, uint64_t words) {
+    z.p[z.n] = static_cast<uint32_t*>(ptr);
+    z.words[z.n++] = words;
+  };
+  for (DevBuf* d : {&h->nslices, &h->probe_slow, &h->slice_off}) HS_HIP(h, d->reserve(n1 * 4));
+  add(h->counters.p, 64);  // incl. the join's item counter (d_cnt + 32)
+  add(h->probe_slow.p, 1);
+  add(h->nslices.as<uint32_t>() + b.nql, 1);
+  if (p.use_join) {
+    HS_HIP(h, h->seg_cnt.reserve(n1 * 4));
+    add(h->seg_cnt.p, n1);
+    if (p.no_slices) add(h->slice_off.p, n1);
+    if (!p.seg_sparse) {
+      HS_HIP(h, h->bucket_work.reserve(4 * ((size_t)h->nb_total + 2) * 4));
+      add(h->bucket_work.p, (uint64_t)h->nb_total + 2);
+    }
+  }
+  if (p.order_here) {
+    HS_HIP(h, h->qhits.reserve((6 * n1q + 8) * 4));
+    add(h->qhits.p, 3 * n1q + 8);
+  }
+  static_assert(HS_ZERO_RANGES >= 7, "reset_batch lists up to 7 ranges");
+  HS_HIP(h, hs_launch_zero_ranges(z, h->stream));
+  return HS_OK;
+}
+
 // One batch of a call: brute force, or the search stages in order.  A batch that left its item count on the
 // device and found it too small runs once more with the count read back first.
 static hs_status query_batch(hs_handle* h, const QueryCall& c, uint32_t nq, uint32_t q_base, uint64_t* d_cand,
@@ -2879,8 +2911,8 @@ static hs_status query_batch(hs_handle* h, const QueryCall& c, uint32_t nq, uint
     const uint32_t nql = nq * (uint32_t)h->p.L;
     Batch b{nq, q_base, nql, nql, c.R * c.R, c.centers, d_cand};
     b.radii = c.radii;
-    HS_HIP(h, hipMemsetAsync(h->counters.p, 0, 256, h->stream));  // incl. the join's item counter (d_cnt + 32)
-    HS_HIP(h, hipEventRecord(h->ev[0], h->stream));
+    HS_HIP(h, hipEventRecord(h->ev[0], h->stream));  // (the reset counts as part of the batch's first phase)
+    HS_CHECK(reset_batch(h, p, b));
     HS_CHECK(prepare_queries(h, c, p, b));
     HS_CHECK(hash_and_probe(h, c, p, b));
     HS_CHECK(group_segments(h, p, b));

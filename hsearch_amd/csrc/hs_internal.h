@@ -218,7 +218,13 @@ size_t hs_sort_pairs_u64_u64_temp(size_t n);
 hipError_t hs_sort_pairs_u64_u64(void* temp, size_t temp_bytes, const uint64_t* kin, uint64_t* kout,
                                  const uint64_t* vin, uint64_t* vout, size_t n, int end_bit,
                                  hipStream_t s);
-size_t hs_scan_u32_temp(size_t n);
+size_t hs_scan_u32_temp(size_t n);  // (workspace of any of the scans below over n elements)
+// two 32-bit scans in one: the halves of the 64-bit sums (the low one must stay below 2^32)
+hipError_t hs_exclusive_scan_u64(void* temp, size_t temp_bytes, const uint64_t* in, uint64_t* out, size_t n,
+                                 hipStream_t s);
+// out[i] = sum of in[j] | (number of in[j] != 0) << 32 over j < i
+hipError_t hs_exclusive_scan_count_flag(void* temp, size_t temp_bytes, const uint32_t* in, uint64_t* out, size_t n,
+                                        hipStream_t s);
 hipError_t hs_exclusive_scan_u32(void* temp, size_t temp_bytes, const uint32_t* in, uint32_t* out,
                                  size_t n, hipStream_t s);
 size_t hs_rle_u64_temp(size_t n);
@@ -355,6 +361,14 @@ hipError_t hs_launch_pack(const uint8_t* d_codes, uint64_t n, int k, int alphabe
 hipError_t hs_launch_gather_packed(const uint4* d_packed_all, const uint32_t* d_ids_sorted,
                                    uint64_t n, int PW, uint4* d_out, hipStream_t s);
 hipError_t hs_launch_set_u32(uint32_t* d_p, uint32_t v, hipStream_t s);
+// zeros over n <= HS_ZERO_RANGES ranges of 32-bit words, one launch
+#define HS_ZERO_RANGES 8
+struct hs_zero_ranges {
+  uint32_t* p[HS_ZERO_RANGES];
+  uint64_t words[HS_ZERO_RANGES];
+  uint32_t n;
+};
+hipError_t hs_launch_zero_ranges(const hs_zero_ranges& r, hipStream_t s);
 // d_out[i] = d_in[i] if it is a row of the table (< alphabet), else 0 and *d_bad |= 1
 hipError_t hs_launch_recognise_kmers(const double* d_centers, uint64_t nq, int k, const double* d_coords, int alphabet,
                                      uint8_t* d_out_codes, uint32_t* d_n_unrecognised, hipStream_t s);
@@ -408,9 +422,13 @@ hipError_t hs_launch_probe(const hs_tables_dev& tabs, const int32_t* d_qints, ui
                            uint32_t* d_slow /* [nq*L + 1] */, const uint32_t* d_dir_base,
                            uint32_t nb_total, uint32_t* d_bucket_count, uint32_t* d_qbucket,
                            uint32_t* d_qrank, hipStream_t s);
-// With d_bucket_count != null the probe also groups the probes by bucket for the join: global
+// The caller has zeroed d_slow[0] and, where given, d_bucket_count[0 .. nb_total + 2) (the batch's reset);
+// d_nslices == null: no slice counts (every segment goes to the join).
+// With d_qbucket != null the probe also numbers every probe's bucket for the join's grouping: global
 // bucket number d_qbucket[ql] = d_dir_base[table] + directory index (nb_total = the pseudo-bucket
-// of probes that found none) and d_qrank[ql] = arrival rank inside it (d_bucket_count[nb_total + 2]).
+// of probes that found none).  With d_bucket_count != null hs_rank_kernel follows: d_qrank[ql] = the probe's
+// rank inside its bucket -- any bijection of the bucket's probes onto [0, count) -- and d_bucket_count[bucket]
+// = count, from one global atomic per bucket and workgroup of 2048 queries of a table, not one per probe.
 // hs_launch_seg_group turns that into sorted_ql / seg_key / seg_cnt / n_seg (a counting sort: the
 // segments come out in bucket-number order, the pseudo-bucket last).
 // The same outputs when buckets far outnumber probes (the counting sort's passes over every bucket
@@ -432,7 +450,7 @@ hipError_t hs_launch_found_probes(const uint32_t* d_qbucket, uint32_t nql, uint3
                                   uint32_t* d_probes, hipStream_t s, const uint32_t* d_list = nullptr);
 hipError_t hs_launch_seg_group(const hs_tables_dev& tabs, const uint32_t* d_dir_base, int L, int shift,
                                uint32_t nb_total, const uint32_t* d_bucket_count,
-                               uint32_t* d_bucket_work /* 3 x (nb_total + 2) */, void* d_temp,
+                               uint32_t* d_bucket_work /* 2 x (nb_total + 2), 8-byte aligned */, void* d_temp,
                                size_t temp_bytes, const uint32_t* d_qbucket, const uint32_t* d_qrank,
                                uint32_t nql, uint32_t* d_sorted_ql, uint64_t* d_seg_key,
                                uint32_t* d_seg_cnt, uint32_t* d_n_seg, uint32_t* d_seg_of, hipStream_t s);
@@ -648,34 +666,36 @@ hipError_t hs_launch_jtables(const double* d_coords, int alphabet, void* d_tab16
 hipError_t hs_launch_qprep(const double* d_centers, uint32_t nq, int k, double r2, void* d_c16,
                            uint32_t* d_unsafe, hipStream_t s, const double* d_radii = nullptr);
 // items[j] for joined segments (>= min_q probing queries and >= min_m members), 0 otherwise, and
-// nslices[ql] = 0 for the probes of joined segments; stats[0] += MFMA pairs issued, [1] += real pairs
+// nslices[ql] = 0 for the probes of joined segments; stats[0] += MFMA pairs issued, [1] += real pairs.
+// Also the class flags of the item numbering order, n_max + 1 entries, the last 0: low half = joined with
+// >= big_min_q probing queries, high half = joined with <= max_q_resident of them (0: no such class).
 hipError_t hs_launch_seg_route(const uint64_t* d_seg_key, const uint32_t* d_seg_cnt,
                                const uint32_t* d_seg_qoff, const uint32_t* d_n_seg,
                                const uint32_t* d_sorted_ql, const uint32_t* d_qcount, uint32_t n_max,
                                uint32_t min_q, uint32_t min_m, uint32_t jm, int L, int shift,
                                uint32_t max_q_resident /* segments up to this many queries are issued in
                                16-query column tiles (hs_join8r_kernel); 0: none */,
-                               uint32_t* d_items, unsigned long long* d_stats, uint32_t* d_nslices,
-                               const uint32_t* d_seg_of, hipStream_t s);
+                               uint32_t big_min_q, uint32_t* d_items, uint64_t* d_class,
+                               unsigned long long* d_stats, uint32_t* d_nslices, const uint32_t* d_seg_of,
+                               hipStream_t s);
 hipError_t hs_launch_item_desc(const hs_tables_dev& tabs, const uint64_t* d_seg_key,
                                const uint32_t* d_seg_cnt,
                                const uint32_t* d_seg_qoff, const uint32_t* d_item_off, uint32_t n_max,
                                const uint32_t* d_sorted_ql, const uint32_t* d_qcount, uint32_t n_items,
                                uint32_t jm, int shift, const uint32_t* d_order, int PW,
                                const uint32_t* d_n_items /* null, or the device-side count: n_items is
-                               then the capacity */, uint4* d_desc, hipStream_t s);
+                               then the capacity */,
+                               const uint64_t* d_class_pos /* scan of the class flags, n_max + 1 entries */,
+                               uint32_t* d_split /* [2]: first item of the query-resident class, items */,
+                               uint4* d_desc, hipStream_t s);
 // item numbering order of the segments: many-query segments first (stable two-class partition):
-// d_big[n + 1] flags (last = 0) -> exclusive scan -> d_order[n], d_items_ordered[n]
+// class flags [n + 1] (last = 0; hs_launch_seg_route) -> hs_exclusive_scan_u64 -> d_class_pos [n + 1] ->
+// d_order[n], d_items_ordered[n + 1] (last = 0)
 // ... and LAST the segments with at most max_q_resident probing queries (d_res flags, null / 0: no such
-// class): their items are the tail [split[0], split[1]) of the item list, taken by the query-resident
-// join kernel (hs_join8r_kernel)
-hipError_t hs_launch_seg_big(const uint32_t* d_seg_cnt, const uint32_t* d_items, uint32_t n,
-                             uint32_t min_q, uint32_t max_q_resident, uint32_t* d_big, uint32_t* d_res,
-                             hipStream_t s);
-hipError_t hs_launch_seg_order(const uint32_t* d_big_pos, const uint32_t* d_res_pos, const uint32_t* d_items,
-                               uint32_t n, uint32_t* d_order, uint32_t* d_items_ordered, hipStream_t s);
-hipError_t hs_launch_item_split(const uint32_t* d_item_off, const uint32_t* d_res_pos, uint32_t n,
-                                uint32_t* d_split, hipStream_t s);
+// class): their items are the tail [split[0], split[1]) of the item list (hs_launch_item_desc), taken by the
+// query-resident join kernel (hs_join8r_kernel)
+hipError_t hs_launch_seg_order(const uint64_t* d_class_pos, const uint32_t* d_items, uint32_t n, uint32_t* d_order,
+                               uint32_t* d_items_ordered, hipStream_t s);
 // queries of a segment the query-resident join keeps in registers (two 32-query tiles: with three the
 // kernel spills at two waves per SIMD)
 #define HS_JR_MAXQ 64u

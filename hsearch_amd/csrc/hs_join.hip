@@ -117,49 +117,52 @@ __global__ void hs_jtables_kernel(const double* __restrict__ coords, int alphabe
   if (bad) atomicOr(unsafe, 1u);
 }
 
-// Probes -> segments by a counting sort on the global bucket number (hs_probe_kernel left, per
-// probe, its bucket and its arrival rank inside it):
-//   start = exclusive scan of the bucket counts;  sorted_ql[start[bucket] + rank] = probe;
+// Probes -> segments by a counting sort on the global bucket number (the probe kernels left every probe's
+// bucket, hs_rank_kernel its rank inside the bucket -- ANY bijection of the bucket's probes onto [0, count):
+// it orders the probes inside their segment and nothing else; no later stage may read more into it -- and the
+// buckets' probe counts; one global atomic per bucket and workgroup there, not one per probe):
+//   start = exclusive scan of the bucket counts (low half of start_pos; the high half numbers the non-empty
+//   buckets: both scans in one pass, hs_exclusive_scan_count_flag);  sorted_ql[start[bucket] + rank] = probe;
 //   the non-empty buckets, in bucket order, are the segments: key = (table << shift) | first sorted
 //   position of the bucket, count = probes.  The pseudo-bucket (probes of no bucket) comes last
 //   with table = L and is routed nowhere.
 // (+ seg_of[p] = segment of sorted position p: what the later per-probe passes index with)
+// What starts from zero -- the bucket counts, the segment counts behind the last segment -- is cleared by the
+// batch's one reset launch (hs_launch_zero_ranges), and the word that closes a scan's input is written by the
+// kernel that writes the input: the chain issues no fill of its own.  After the grouping: hs_seg_route_kernel
+// (items + the two class flags), their scans, hs_seg_order_kernel, the scan of the item counts, and
+// hs_item_desc_kernel, which also leaves the bounds of the query-resident class.
 __global__ __launch_bounds__(256) void hs_seg_scatter_kernel(const uint32_t* __restrict__ qbucket,
                                                              const uint32_t* __restrict__ qrank,
-                                                             const uint32_t* __restrict__ bucket_start,
-                                                             const uint32_t* __restrict__ flag_pos,
+                                                             const uint64_t* __restrict__ start_pos,
                                                              uint32_t nql,
                                                              uint32_t* __restrict__ sorted_ql,
                                                              uint32_t* __restrict__ seg_of) {
   const uint32_t ql = blockIdx.x * 256 + threadIdx.x;
   if (ql >= nql) return;
-  const uint32_t gb = qbucket[ql], p = bucket_start[gb] + qrank[ql];
+  const uint64_t sp = start_pos[qbucket[ql]];
+  const uint32_t p = (uint32_t)sp + qrank[ql];
   sorted_ql[p] = ql;
-  seg_of[p] = flag_pos[gb];
-}
-__global__ __launch_bounds__(256) void hs_seg_flag_kernel(const uint32_t* __restrict__ bucket_count,
-                                                          uint32_t n, uint32_t* __restrict__ flag) {
-  const uint32_t g = blockIdx.x * 256 + threadIdx.x;
-  if (g <= n) flag[g] = (g < n && bucket_count[g]) ? 1u : 0u;  // flag[n] = 0 closes the scan
+  seg_of[p] = (uint32_t)(sp >> 32);
 }
 __global__ __launch_bounds__(256) void hs_seg_emit_kernel(hs_tables_dev tabs,
                                                           const uint32_t* __restrict__ dir_base, int L,
                                                           int shift,
                                                           const uint32_t* __restrict__ bucket_count,
-                                                          const uint32_t* __restrict__ flag_pos,
+                                                          const uint64_t* __restrict__ start_pos,
                                                           uint32_t n /* buckets incl. the pseudo one */,
                                                           uint64_t* __restrict__ seg_key,
                                                           uint32_t* __restrict__ seg_cnt,
                                                           uint32_t* __restrict__ n_seg) {
   const uint32_t g = blockIdx.x * 256 + threadIdx.x;
-  if (g == 0) *n_seg = flag_pos[n];
+  if (g == 0) *n_seg = (uint32_t)(start_pos[n] >> 32);
   if (g >= n) return;
   const uint32_t c = bucket_count[g];
   if (!c) return;
   int l = 0;
   while (l < L && g >= dir_base[l + 1]) ++l;  // dir_base[L] = n - 1 = the pseudo-bucket: l = L
   const uint32_t mstart = l < L ? tabs.t[l].dir_start[g - dir_base[l]] : 0u;
-  const uint32_t j = flag_pos[g];
+  const uint32_t j = (uint32_t)(start_pos[g] >> 32);
   seg_key[j] = ((uint64_t)(uint32_t)l << shift) | mstart;
   seg_cnt[j] = c;
 }
@@ -210,6 +213,10 @@ __global__ __launch_bounds__(256) void hs_seg_counts_kernel(const uint32_t* __re
 // Routing: a segment (bucket x its probing queries) goes to the MFMA join when enough queries share
 // it, otherwise its queries stay with the streaming kernel (one wavefront per query and slice).
 // items[j] = member tiles x query groups for joined segments, 0 otherwise / past the end.
+// Also the two class flags the item numbering order is scanned from (see hs_seg_order_kernel), as the halves of
+// one 64-bit word so that one scan serves both: low = joined with >= big_min_q probing queries, high = joined with
+// at most max_q_resident (0: no such class).  Entry n_max of both arrays is 0: the kernel that owns an array
+// writes the word that closes its scan.
 __global__ __launch_bounds__(256) void hs_seg_route_kernel(const uint64_t* __restrict__ seg_key,
                                                            const uint32_t* __restrict__ seg_cnt,
                                                            const uint32_t* __restrict__ seg_qoff,
@@ -218,16 +225,17 @@ __global__ __launch_bounds__(256) void hs_seg_route_kernel(const uint64_t* __res
                                                            const uint32_t* __restrict__ qcount,
                                                            uint32_t n_max, uint32_t min_q,
                                                            uint32_t min_m, uint32_t jm, int L, int shift,
-                                                           uint32_t max_q_resident,
+                                                           uint32_t max_q_resident, uint32_t big_min_q,
                                                            uint32_t* __restrict__ items,
+                                                           uint64_t* __restrict__ cls,
                                                            unsigned long long* __restrict__ stats) {
   const uint32_t j = blockIdx.x * 256 + threadIdx.x;
-  uint32_t it = 0;
+  uint32_t it = 0, c = 0;
   unsigned long long issued = 0, real = 0;
   const uint32_t jqg = jm < HS_JM_BLOCK ? HS_JQG_WAVE : (uint32_t)JQG;
   if (j <= n_max && j < *n_seg && (seg_key[j] >> shift) < (uint64_t)L) {
     const uint32_t m = qcount[sorted_ql[seg_qoff[j]]];
-    const uint32_t nq = seg_cnt[j];
+    const uint32_t nq = c = seg_cnt[j];
     // thin segments (few probing queries or few members) go to the per-pair filter; a BIG bucket goes
     // to the join whatever its query count: its mostly empty query tile costs next to nothing there,
     // while the per-pair filter would walk its thousands of members in one chain of dependent loads
@@ -241,7 +249,12 @@ __global__ __launch_bounds__(256) void hs_seg_route_kernel(const uint64_t* __res
       real = (unsigned long long)m * nq;
     }
   }
-  if (j <= n_max) items[j] = it;
+  if (j <= n_max) {
+    items[j] = it;
+    const uint64_t big = (it && c >= big_min_q) ? 1u : 0u;
+    const uint64_t res = (it && c <= max_q_resident && c < big_min_q) ? 1u : 0u;  // (it != 0 implies c >= 1)
+    cls[j] = big | (res << 32);
+  }
   // the two statistics: one pair of global atomics per block (same-address atomics are slow)
   for (int off = 32; off; off >>= 1) {
     issued += __shfl_xor(issued, off);
@@ -280,45 +293,26 @@ __global__ __launch_bounds__(256) void hs_seg_unslice_kernel(const uint32_t* __r
 // segments with at most max_q_resident probing queries (0: no such class) -- their items form the tail
 // [split, total) of the item list, which the query-resident join kernel (hs_join8r_kernel) takes while
 // the head goes to the query-streaming one.
-__global__ __launch_bounds__(256) void hs_seg_big_kernel(const uint32_t* __restrict__ seg_cnt,
-                                                         const uint32_t* __restrict__ items,
-                                                         uint32_t n, uint32_t min_q, uint32_t max_q_resident,
-                                                         uint32_t* __restrict__ big,
-                                                         uint32_t* __restrict__ res) {
-  const uint32_t j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  const uint32_t c = seg_cnt[j];
-  const bool has = items[j] != 0u;
-  big[j] = (has && c >= min_q) ? 1u : 0u;
-  if (res) res[j] = (has && c <= max_q_resident && c < min_q) ? 1u : 0u;
-}
-// big_pos / res_pos have n + 1 entries: [n] = number of segments of the class (res_pos may be null)
-__global__ __launch_bounds__(256) void hs_seg_order_kernel(const uint32_t* __restrict__ big_pos,
-                                                           const uint32_t* __restrict__ res_pos,
+// class_pos = the scan of the class words, n + 1 entries: [n] = number of segments of each class (low: big, high:
+// query-resident)
+__global__ __launch_bounds__(256) void hs_seg_order_kernel(const uint64_t* __restrict__ class_pos,
                                                            const uint32_t* __restrict__ items,
                                                            uint32_t n, uint32_t* __restrict__ order,
                                                            uint32_t* __restrict__ items_ordered) {
   const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+  if (j == n) items_ordered[n] = 0u;  // closes the scan that makes the item offsets
   if (j >= n) return;
-  const bool big = big_pos[j + 1] != big_pos[j];
-  const bool res = res_pos && res_pos[j + 1] != res_pos[j];
-  const uint32_t n_big = big_pos[n], n_res = res_pos ? res_pos[n] : 0u;
-  const uint32_t before_res = res_pos ? res_pos[j] : 0u;
-  const uint32_t pos = big ? big_pos[j]
+  const uint64_t here = class_pos[j], next = class_pos[j + 1], all = class_pos[n];
+  const uint32_t before_big = (uint32_t)here, before_res = (uint32_t)(here >> 32);
+  const bool big = (uint32_t)next != before_big;
+  const bool res = (uint32_t)(next >> 32) != before_res;
+  const uint32_t n_big = (uint32_t)all, n_res = (uint32_t)(all >> 32);
+  const uint32_t pos = big ? before_big
                        : res ? (n - n_res) + before_res
-                             : n_big + (j - big_pos[j] - before_res);
+                             : n_big + (j - before_big - before_res);
   order[pos] = j;
   items_ordered[pos] = items[j];
 }
-// split[0] = first item of the query-resident class, split[1] = number of items
-__global__ void hs_item_split_kernel(const uint32_t* __restrict__ item_off, const uint32_t* __restrict__ res_pos,
-                                     uint32_t n, uint32_t* __restrict__ split) {
-  if (threadIdx.x || blockIdx.x) return;
-  const uint32_t n_res = res_pos ? res_pos[n] : 0u;
-  split[0] = item_off[n - n_res];
-  split[1] = item_off[n];
-}
-
 // One descriptor (2 x uint4) per work item:
 //   { offset of the bucket's first packed member from table 0's packed array (lo, hi), M, tile },
 //   { qoff, q_begin, q_end, first sorted position of the bucket }
@@ -329,6 +323,8 @@ __global__ void hs_item_split_kernel(const uint32_t* __restrict__ item_off, cons
 // thread searches there; a block whose items span more positions than the window holds (a run of zero-item
 // positions inside it) falls back to the search in memory.  (One thread per SEGMENT, writing its items in
 // a loop, was measured slower: 32-byte stores scattered over the descriptor array.)
+// The first thread also leaves split[0] = first item of the query-resident class (the tail of the item list:
+// the last class_pos[n_max] >> 32 positions of `order`), split[1] = number of items.
 __global__ __launch_bounds__(256) void hs_item_desc_kernel(hs_tables_dev tabs,
                                                            const uint64_t* __restrict__ seg_key,
                                                            const uint32_t* __restrict__ seg_cnt,
@@ -340,12 +336,18 @@ __global__ __launch_bounds__(256) void hs_item_desc_kernel(hs_tables_dev tabs,
                                                            uint32_t n_items, uint32_t jm, int shift,
                                                            const uint32_t* __restrict__ order, int PW,
                                                            const uint32_t* __restrict__ n_items_dev,
+                                                           const uint64_t* __restrict__ class_pos,
+                                                           uint32_t* __restrict__ split,
                                                            uint4* __restrict__ desc) {
   constexpr uint32_t WIN = 768;
   __shared__ uint32_t s_off[WIN + 1];
   __shared__ uint32_t s_first;
   const uint32_t item0 = blockIdx.x * 256, item = item0 + threadIdx.x;
   if (n_items_dev) n_items = min(n_items, *n_items_dev);  // n_items = capacity of desc then
+  if (item == 0) {
+    split[0] = item_off[n_max - (uint32_t)(class_pos[n_max] >> 32)];
+    split[1] = item_off[n_max];
+  }
   if (item0 >= n_items) return;
   if (threadIdx.x == 0) {
     uint32_t lo = 0, hi = n_max;  // largest j with item_off[j] <= item0
@@ -666,16 +668,12 @@ hipError_t hs_launch_seg_group(const hs_tables_dev& tabs, const uint32_t* d_dir_
                                uint32_t* d_n_seg, uint32_t* d_seg_of, hipStream_t s) {
   if (!nql) return hipSuccess;
   const uint32_t n = nb_total + 1;  // buckets incl. the pseudo one; arrays have n + 1 entries
-  uint32_t* start = d_bucket_work;
-  uint32_t* flag = d_bucket_work + (n + 1);
-  uint32_t* flag_pos = d_bucket_work + 2 * (size_t)(n + 1);
-  hipError_t e = hs_exclusive_scan_u32(d_temp, temp_bytes, d_bucket_count, start, (size_t)n + 1, s);
+  // (entry n of the counts -- slot nb_total + 1 -- is never counted into: it closes the scan)
+  uint64_t* start_pos = reinterpret_cast<uint64_t*>(d_bucket_work);
+  hipError_t e = hs_exclusive_scan_count_flag(d_temp, temp_bytes, d_bucket_count, start_pos, (size_t)n + 1, s);
   if (e != hipSuccess) return e;
-  hs_seg_flag_kernel<<<blocks_for((uint64_t)n + 1), 256, 0, s>>>(d_bucket_count, n, flag);
-  e = hs_exclusive_scan_u32(d_temp, temp_bytes, flag, flag_pos, (size_t)n + 1, s);
-  if (e != hipSuccess) return e;
-  hs_seg_scatter_kernel<<<blocks_for(nql), 256, 0, s>>>(d_qbucket, d_qrank, start, flag_pos, nql, d_sorted_ql, d_seg_of);
-  hs_seg_emit_kernel<<<blocks_for(n), 256, 0, s>>>(tabs, d_dir_base, L, shift, d_bucket_count, flag_pos,
+  hs_seg_scatter_kernel<<<blocks_for(nql), 256, 0, s>>>(d_qbucket, d_qrank, start_pos, nql, d_sorted_ql, d_seg_of);
+  hs_seg_emit_kernel<<<blocks_for(n), 256, 0, s>>>(tabs, d_dir_base, L, shift, d_bucket_count, start_pos,
                                                    n, d_seg_key, d_seg_cnt, d_n_seg);
   return hipGetLastError();
 }
@@ -744,11 +742,12 @@ hipError_t hs_launch_seg_route(const uint64_t* d_seg_key, const uint32_t* d_seg_
                                const uint32_t* d_seg_qoff, const uint32_t* d_n_seg,
                                const uint32_t* d_sorted_ql, const uint32_t* d_qcount, uint32_t n_max,
                                uint32_t min_q, uint32_t min_m, uint32_t jm, int L, int shift,
-                               uint32_t max_q_resident, uint32_t* d_items, unsigned long long* d_stats,
-                               uint32_t* d_nslices, const uint32_t* d_seg_of, hipStream_t s) {
+                               uint32_t max_q_resident, uint32_t big_min_q, uint32_t* d_items, uint64_t* d_class,
+                               unsigned long long* d_stats, uint32_t* d_nslices, const uint32_t* d_seg_of,
+                               hipStream_t s) {
   hs_seg_route_kernel<<<blocks_for((uint64_t)n_max + 1), 256, 0, s>>>(
       d_seg_key, d_seg_cnt, d_seg_qoff, d_n_seg, d_sorted_ql, d_qcount, n_max, min_q, min_m, jm, L,
-      shift, max_q_resident, d_items, d_stats);
+      shift, max_q_resident, big_min_q, d_items, d_class, d_stats);
   // (d_nslices == null: every segment with a member goes to the join -- min_q = min_m = 1 -- and the caller
   // clears the slice counts of ALL probes with one memset instead of this kernel's scattered stores)
   if (d_nslices)
@@ -756,20 +755,9 @@ hipError_t hs_launch_seg_route(const uint64_t* d_seg_key, const uint32_t* d_seg_
   return hipGetLastError();
 }
 
-hipError_t hs_launch_seg_big(const uint32_t* d_seg_cnt, const uint32_t* d_items, uint32_t n,
-                             uint32_t min_q, uint32_t max_q_resident, uint32_t* d_big, uint32_t* d_res,
-                             hipStream_t s) {
-  hs_seg_big_kernel<<<blocks_for(n), 256, 0, s>>>(d_seg_cnt, d_items, n, min_q, max_q_resident, d_big, d_res);
-  return hipGetLastError();
-}
-hipError_t hs_launch_seg_order(const uint32_t* d_big_pos, const uint32_t* d_res_pos, const uint32_t* d_items,
-                               uint32_t n, uint32_t* d_order, uint32_t* d_items_ordered, hipStream_t s) {
-  hs_seg_order_kernel<<<blocks_for(n), 256, 0, s>>>(d_big_pos, d_res_pos, d_items, n, d_order, d_items_ordered);
-  return hipGetLastError();
-}
-hipError_t hs_launch_item_split(const uint32_t* d_item_off, const uint32_t* d_res_pos, uint32_t n,
-                                uint32_t* d_split, hipStream_t s) {
-  hs_item_split_kernel<<<1, 64, 0, s>>>(d_item_off, d_res_pos, n, d_split);
+hipError_t hs_launch_seg_order(const uint64_t* d_class_pos, const uint32_t* d_items, uint32_t n, uint32_t* d_order,
+                               uint32_t* d_items_ordered, hipStream_t s) {
+  hs_seg_order_kernel<<<blocks_for((uint64_t)n + 1), 256, 0, s>>>(d_class_pos, d_items, n, d_order, d_items_ordered);
   return hipGetLastError();
 }
 
@@ -778,11 +766,12 @@ hipError_t hs_launch_item_desc(const hs_tables_dev& tabs, const uint64_t* d_seg_
                                const uint32_t* d_seg_qoff, const uint32_t* d_item_off, uint32_t n_max,
                                const uint32_t* d_sorted_ql, const uint32_t* d_qcount, uint32_t n_items,
                                uint32_t jm, int shift, const uint32_t* d_order, int PW,
-                               const uint32_t* d_n_items, uint4* d_desc, hipStream_t s) {
+                               const uint32_t* d_n_items, const uint64_t* d_class_pos, uint32_t* d_split,
+                               uint4* d_desc, hipStream_t s) {
   if (!n_items) return hipSuccess;
   hs_item_desc_kernel<<<blocks_for(n_items), 256, 0, s>>>(tabs, d_seg_key, d_seg_cnt, d_seg_qoff, d_item_off,
                                                           n_max, d_sorted_ql, d_qcount, n_items, jm, shift,
-                                                          d_order, PW, d_n_items, d_desc);
+                                                          d_order, PW, d_n_items, d_class_pos, d_split, d_desc);
   return hipGetLastError();
 }
 

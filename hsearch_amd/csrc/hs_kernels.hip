@@ -254,6 +254,15 @@ __global__ __launch_bounds__(256) void hs_dir_tuples_kernel(const uint32_t* __re
 // counts[nb] -> starts[nb+1] is done by the scan primitive; this fills the sentinel.
 __global__ void hs_set_u32_kernel(uint32_t* p, uint32_t v) { *p = v; }
 
+// Zeros over up to HS_ZERO_RANGES word ranges in one launch: block b works on range b % n, as block b / n of
+// the range's share of the grid (a batch's counters, closing words and per-probe arrays used to take a dozen fills)
+__global__ __launch_bounds__(256) void hs_zero_ranges_kernel(hs_zero_ranges r) {
+  const uint32_t i = blockIdx.x % r.n, blocks = gridDim.x / r.n;
+  uint32_t* const p = r.p[i];
+  for (uint64_t w = (uint64_t)(blockIdx.x / r.n) * 256 + threadIdx.x; w < r.words[i]; w += (uint64_t)blocks * 256)
+    p[w] = 0u;
+}
+
 __global__ __launch_bounds__(256) void hs_max_u32_kernel(const uint32_t* __restrict__ in, uint32_t n,
                                                          uint32_t* __restrict__ out) {
   uint32_t m = 0;
@@ -351,9 +360,7 @@ __global__ __launch_bounds__(256) void hs_probe_kernel(hs_tables_dev tabs,
                                                        uint32_t* __restrict__ slow,
                                                        const uint32_t* __restrict__ dir_base,
                                                        uint32_t nb_total,
-                                                       uint32_t* __restrict__ bucket_count,
-                                                       uint32_t* __restrict__ qbucket,
-                                                       uint32_t* __restrict__ qrank) {
+                                                       uint32_t* __restrict__ qbucket) {
   // The probe is a chain of dependent memory round trips (tuple, 17 directory steps, bucket tuple):
   // the K bucket ints of a probe are fetched with 16-byte loads, all in flight at once, and parked
   // in LDS (s_t[j][thread]: conflict-free), instead of K loads one after the other.
@@ -362,7 +369,7 @@ __global__ __launch_bounds__(256) void hs_probe_kernel(hs_tables_dev tabs,
   const uint32_t slot_ = blockIdx.x * 256 + threadIdx.x;
   const uint32_t ql = tabs.probe_list ? (slot_ < tabs.n_list ? tabs.probe_list[slot_] : 0xffffffffu) : slot_;
   uint32_t count = 0, start = 0;
-  // grouping of the probes by bucket (for the bucket join): global bucket number and arrival rank;
+  // grouping of the probes by bucket (for the bucket join): global bucket number;
   // nb_total = the pseudo-bucket of probes that found none
   uint32_t gb = nb_total;
   bool ranked = false;  // false: out of range, or left to hs_probe_slow_kernel
@@ -478,31 +485,12 @@ __global__ __launch_bounds__(256) void hs_probe_kernel(hs_tables_dev tabs,
     }  // (no directory records)
     qstart[ql] = start;
     qcount[ql] = count;
-    nslices[ql] = (count + HS_SLICE - 1) / HS_SLICE;
+    if (nslices) nslices[ql] = (count + HS_SLICE - 1) / HS_SLICE;
     if (cand_out) cand_out[ql] = count;
   }
-  // (bucket_count == null with qbucket set: the caller groups the probes by sorting them on their
-  // bucket number -- hs_launch_seg_group_sparse -- and needs no ranks)
-  if (!bucket_count && qbucket && ranked) qbucket[ql] = gb;
-  if (bucket_count) {
-    const bool pseudo = ranked && gb == nb_total;
-    // one counter access per BLOCK for the pseudo-bucket (same-address atomics are slow): ranks
-    // inside the block from an LDS counter, the block's base from the global one
-    __shared__ uint32_t s_pseudo, s_pbase;
-    if (threadIdx.x == 0) s_pseudo = 0;
-    __syncthreads();
-    uint32_t rank = 0;
-    if (pseudo) rank = atomicAdd(&s_pseudo, 1u);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_pseudo) s_pbase = atomicAdd(&bucket_count[nb_total], s_pseudo);
-    __syncthreads();
-    if (pseudo) rank += s_pbase;
-    if (ranked && !pseudo) rank = atomicAdd(&bucket_count[gb], 1u);
-    if (ranked) {
-      qbucket[ql] = gb;
-      qrank[ql] = rank;
-    }
-  }
+  // (the grouping works from the bucket numbers: the counting sort ranks them with hs_rank_kernel, the
+  // sort of the probes -- hs_launch_seg_group_sparse -- needs no ranks)
+  if (qbucket && ranked) qbucket[ql] = gb;
   // candidate total: one access to the global counter per BLOCK (same-address atomics deliver
   // ~100 per microsecond chip-wide: one per wave -- 12 500 of them -- was most of this kernel)
   unsigned long long c = count;
@@ -526,9 +514,7 @@ __global__ __launch_bounds__(256) void hs_self_probe_kernel(hs_tables_dev tabs, 
                                                             uint64_t* __restrict__ cand_out,
                                                             unsigned long long* __restrict__ cand_total,
                                                             const uint32_t* __restrict__ dir_base,
-                                                            uint32_t* __restrict__ bucket_count,
-                                                            uint32_t* __restrict__ qbucket,
-                                                            uint32_t* __restrict__ qrank) {
+                                                            uint32_t* __restrict__ qbucket) {
   const uint32_t ql = blockIdx.x * 256 + threadIdx.x;
   uint32_t count = 0;
   if (ql < nq * (uint32_t)L) {
@@ -545,15 +531,9 @@ __global__ __launch_bounds__(256) void hs_self_probe_kernel(hs_tables_dev tabs, 
     count = tb.dir_start[lo + 1] - start;
     qstart[ql] = start;
     qcount[ql] = count;
-    nslices[ql] = (count + HS_SLICE - 1) / HS_SLICE;
+    if (nslices) nslices[ql] = (count + HS_SLICE - 1) / HS_SLICE;
     if (cand_out) cand_out[ql] = count;
-    if (bucket_count) {
-      const uint32_t gb = dir_base[l] + lo;
-      qbucket[ql] = gb;
-      qrank[ql] = atomicAdd(&bucket_count[gb], 1u);
-    } else if (qbucket) {
-      qbucket[ql] = dir_base[l] + lo;
-    }
+    if (qbucket) qbucket[ql] = dir_base[l] + lo;
   }
   unsigned long long c = count;
   for (int off = 32; off; off >>= 1) c += __shfl_xor(c, off);
@@ -579,9 +559,7 @@ __global__ __launch_bounds__(256) void hs_probe_slow_kernel(hs_tables_dev tabs,
                                                             const uint32_t* __restrict__ slow,
                                                             const uint32_t* __restrict__ dir_base,
                                                             uint32_t nb_total,
-                                                            uint32_t* __restrict__ bucket_count,
-                                                            uint32_t* __restrict__ qbucket,
-                                                            uint32_t* __restrict__ qrank) {
+                                                            uint32_t* __restrict__ qbucket) {
   const uint32_t total = slow[0];
   for (uint32_t e = blockIdx.x * 256 + threadIdx.x; e < total; e += gridDim.x * 256) {
     const uint32_t ql = slow[1 + e];
@@ -602,19 +580,66 @@ __global__ __launch_bounds__(256) void hs_probe_slow_kernel(hs_tables_dev tabs,
         const uint32_t start = tb.dir_start[lo], count = tb.dir_start[lo + 1] - start;
         qstart[ql] = start;
         qcount[ql] = count;
-        nslices[ql] = (count + HS_SLICE - 1) / HS_SLICE;
+        if (nslices) nslices[ql] = (count + HS_SLICE - 1) / HS_SLICE;
         if (cand_out) cand_out[ql] = count;
         atomicAdd(cand_total, (unsigned long long)count);
         if (dir_base) gb = dir_base[l] + lo;
       }
     }
-    if (bucket_count) {
-      qbucket[ql] = gb;
-      qrank[ql] = atomicAdd(&bucket_count[gb], 1u);
-    } else if (qbucket) {
-      qbucket[ql] = gb;
-    }
+    if (qbucket) qbucket[ql] = gb;
   }
+}
+
+// Ranks for the counting sort of the probes on their bucket (hs_launch_seg_group): qrank[ql] = the probe's
+// place among the probes of bucket qbucket[ql], bucket_count[bucket] += its probes.
+// CONTRACT: within a bucket, ANY bijection of its probes onto [0, count) is a valid ranking -- it only fixes
+// the probes' order inside their segment, and nothing downstream may depend on more (the order of the hits
+// comes from the hit ordering at the end of the step).  It is the arrival order of the atomics below.
+// A hot bucket takes thousands of probes of one batch, and same-address atomics complete at ~100 per
+// microsecond chip-wide: one returning global atomic per probe serialised most of the probe kernel on a few
+// counters.  Here a workgroup takes HS_RANK_Q queries of ONE table (probe = query * L + table, so it reads
+// qbucket and writes qrank at a stride of L words), counts them per bucket in an LDS table keyed by bucket
+// number (open addressing; twice as many slots as probes, so it cannot fill up), and asks the global
+// counter once per distinct bucket: base + place in the workgroup.  The pseudo-bucket is a bucket like any other.
+constexpr uint32_t HS_RANK_THREADS = 1024, HS_RANK_PER_THREAD = 2, HS_RANK_Q = HS_RANK_THREADS * HS_RANK_PER_THREAD;
+constexpr uint32_t HS_RANK_SLOTS = 2 * HS_RANK_Q;
+__global__ __launch_bounds__(HS_RANK_THREADS) void hs_rank_kernel(const uint32_t* __restrict__ qbucket,
+                                                                  uint32_t nq, uint32_t L, uint32_t nb_total,
+                                                                  uint32_t* __restrict__ bucket_count,
+                                                                  uint32_t* __restrict__ qrank) {
+  constexpr uint32_t EMPTY = 0xffffffffu;  // (bucket numbers are <= nb_total)
+  __shared__ uint32_t s_key[HS_RANK_SLOTS], s_cnt[HS_RANK_SLOTS];
+  const uint32_t l = blockIdx.x % L, q0 = (blockIdx.x / L) * HS_RANK_Q;
+  for (uint32_t s = threadIdx.x; s < HS_RANK_SLOTS; s += HS_RANK_THREADS) {
+    s_key[s] = EMPTY;
+    s_cnt[s] = 0;
+  }
+  __syncthreads();
+  uint32_t slot[HS_RANK_PER_THREAD], place[HS_RANK_PER_THREAD];
+#pragma unroll
+  for (uint32_t i = 0; i < HS_RANK_PER_THREAD; ++i) {
+    const uint32_t q = q0 + i * HS_RANK_THREADS + threadIdx.x;
+    slot[i] = EMPTY;
+    if (q >= nq) continue;
+    const uint32_t gb = min(qbucket[q * L + l], nb_total);
+    uint32_t s = ((gb * 0x9e3779b1u) >> 16) & (HS_RANK_SLOTS - 1);
+    for (uint32_t tries = 0; tries < HS_RANK_SLOTS; ++tries) {  // (always ends at a free or an own slot)
+      const uint32_t seen = atomicCAS(&s_key[s], EMPTY, gb);
+      if (seen == EMPTY || seen == gb) break;
+      s = (s + 1) & (HS_RANK_SLOTS - 1);
+    }
+    slot[i] = s;
+    place[i] = atomicAdd(&s_cnt[s], 1u);
+  }
+  __syncthreads();
+  for (uint32_t s = threadIdx.x; s < HS_RANK_SLOTS; s += HS_RANK_THREADS) {
+    const uint32_t c = s_cnt[s];
+    if (c) s_cnt[s] = atomicAdd(&bucket_count[s_key[s]], c);  // count -> the workgroup's base in the bucket
+  }
+  __syncthreads();
+#pragma unroll
+  for (uint32_t i = 0; i < HS_RANK_PER_THREAD; ++i)
+    if (slot[i] != EMPTY) qrank[(q0 + i * HS_RANK_THREADS + threadIdx.x) * L + l] = s_cnt[slot[i]] + place[i];
 }
 
 // ---------------------------------------------------------------------------------------- qtables
@@ -1851,6 +1876,16 @@ hipError_t hs_launch_dir_tuples(const uint32_t* d_dir_start, const uint32_t* d_i
   return hipGetLastError();
 }
 
+hipError_t hs_launch_zero_ranges(const hs_zero_ranges& r, hipStream_t s) {
+  if (!r.n) return hipSuccess;
+  uint64_t most = 0;
+  for (uint32_t i = 0; i < r.n; ++i) most = std::max(most, r.words[i]);
+  // (a thread clears up to 16 words of the longest range; every block of the grid belongs to one range)
+  const unsigned per_range = (unsigned)std::min<uint64_t>(std::max<uint64_t>(1, (most + 4095) / 4096), 2048);
+  hs_zero_ranges_kernel<<<per_range * r.n, 256, 0, s>>>(r);
+  return hipGetLastError();
+}
+
 hipError_t hs_launch_set_u32(uint32_t* d_p, uint32_t v, hipStream_t s) {
   hs_set_u32_kernel<<<1, 1, 0, s>>>(d_p, v);
   return hipGetLastError();
@@ -1879,6 +1914,13 @@ hipError_t hs_launch_gather_packed(const uint4* d_packed_all, const uint32_t* d_
   return hipGetLastError();
 }
 
+// (every probe of the batch has its bucket number by now: the probe kernels wrote all nq * L of them)
+static void launch_rank(const uint32_t* d_qbucket, uint32_t nq, int L, uint32_t nb_total, uint32_t* d_bucket_count,
+                        uint32_t* d_qrank, hipStream_t s) {
+  hs_rank_kernel<<<blocks_for(nq, HS_RANK_Q) * (unsigned)L, HS_RANK_THREADS, 0, s>>>(d_qbucket, nq, (uint32_t)L, nb_total,
+                                                                                     d_bucket_count, d_qrank);
+}
+
 hipError_t hs_launch_probe(const hs_tables_dev& tabs, const int32_t* d_qints, uint32_t nq, int K,
                            int L, uint32_t seed, uint32_t* d_qstart, uint32_t* d_qcount,
                            uint32_t* d_nslices, uint64_t* d_cand_out,
@@ -1886,19 +1928,13 @@ hipError_t hs_launch_probe(const hs_tables_dev& tabs, const int32_t* d_qints, ui
                            const uint32_t* d_dir_base, uint32_t nb_total, uint32_t* d_bucket_count,
                            uint32_t* d_qbucket, uint32_t* d_qrank, hipStream_t s) {
   if (!nq) return hipSuccess;
-  hipError_t e = hipMemsetAsync(d_slow, 0, 4, s);
-  if (e != hipSuccess) return e;
-  if (d_bucket_count) {
-    e = hipMemsetAsync(d_bucket_count, 0, ((size_t)nb_total + 2) * 4, s);
-    if (e != hipSuccess) return e;
-  }
   if (tabs.probe_list && !tabs.n_list) return hipSuccess;  // (a part without a probe in this batch)
   hs_probe_kernel<<<blocks_for(tabs.probe_list ? (uint64_t)tabs.n_list : (uint64_t)nq * L), 256, 0, s>>>(
       tabs, d_qints, nq, K, L, seed, d_qstart, d_qcount, d_nslices, d_cand_out, d_cand_total, d_slow,
-      d_dir_base, nb_total, d_bucket_count, d_qbucket, d_qrank);
+      d_dir_base, nb_total, d_qbucket);
   hs_probe_slow_kernel<<<64, 256, 0, s>>>(tabs, d_qints, K, L, seed, d_qstart, d_qcount, d_nslices,
-                                          d_cand_out, d_cand_total, d_slow, d_dir_base, nb_total,
-                                          d_bucket_count, d_qbucket, d_qrank);
+                                          d_cand_out, d_cand_total, d_slow, d_dir_base, nb_total, d_qbucket);
+  if (d_bucket_count) launch_rank(d_qbucket, nq, L, nb_total, d_bucket_count, d_qrank, s);
   return hipGetLastError();
 }
 
@@ -1958,14 +1994,10 @@ hipError_t hs_launch_self_probe(const hs_tables_dev& tabs, uint32_t first_id, ui
                                 const uint32_t* d_dir_base, uint32_t nb_total, uint32_t* d_bucket_count,
                                 uint32_t* d_qbucket, uint32_t* d_qrank, hipStream_t s) {
   if (!nq) return hipSuccess;
-  if (d_bucket_count) {
-    hipError_t e = hipMemsetAsync(d_bucket_count, 0, ((size_t)nb_total + 2) * 4, s);
-    if (e != hipSuccess) return e;
-  }
   hs_self_probe_kernel<<<blocks_for((uint64_t)nq * L), 256, 0, s>>>(tabs, first_id, nq, L, d_qstart, d_qcount,
                                                                     d_nslices, d_cand_out, d_cand_total,
-                                                                    d_dir_base, d_bucket_count, d_qbucket,
-                                                                    d_qrank);
+                                                                    d_dir_base, d_qbucket);
+  if (d_bucket_count) launch_rank(d_qbucket, nq, L, nb_total, d_bucket_count, d_qrank, s);
   return hipGetLastError();
 }
 

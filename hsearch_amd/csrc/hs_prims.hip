@@ -7,6 +7,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_run_length_encode.hpp>
 #include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
 
 #include "hs_internal.h"
 
@@ -65,11 +66,28 @@ hipError_t hs_sort_pairs_u64_u64(void* temp, size_t temp_bytes, const uint64_t* 
   return rocprim::radix_sort_pairs(temp, temp_bytes, kin, kout, vin, vout, n, 0, end_bit, s);
 }
 
+// (room for the 64-bit scans below too: every scan of n elements takes its workspace from this figure)
 size_t hs_scan_u32_temp(size_t n) {
-  size_t bytes = 0;
+  size_t bytes = 0, bytes64 = 0;
   (void)rocprim::exclusive_scan(nullptr, bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0u, n,
                                 rocprim::plus<uint32_t>(), 0);
-  return bytes;
+  (void)rocprim::exclusive_scan(nullptr, bytes64, (const uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, n,
+                                rocprim::plus<uint64_t>(), 0);
+  return bytes > bytes64 ? bytes : bytes64;
+}
+// Two 32-bit scans in one pass: the halves of a 64-bit sum do not meet while the low one stays below 2^32
+hipError_t hs_exclusive_scan_u64(void* temp, size_t temp_bytes, const uint64_t* in, uint64_t* out, size_t n,
+                                 hipStream_t s) {
+  return rocprim::exclusive_scan(temp, temp_bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s);
+}
+// ... of counts and of their "is not zero" flags: out[i] = sum of in[j] (low half) | number of in[j] != 0 (high half), j < i
+struct hs_count_and_flag {
+  __host__ __device__ uint64_t operator()(uint32_t c) const { return (uint64_t)c | ((uint64_t)(c != 0u) << 32); }
+};
+hipError_t hs_exclusive_scan_count_flag(void* temp, size_t temp_bytes, const uint32_t* in, uint64_t* out, size_t n,
+                                        hipStream_t s) {
+  return rocprim::exclusive_scan(temp, temp_bytes, rocprim::make_transform_iterator(in, hs_count_and_flag()), out,
+                                 (uint64_t)0, n, rocprim::plus<uint64_t>(), s);
 }
 hipError_t hs_exclusive_scan_u32(void* temp, size_t temp_bytes, const uint32_t* in, uint32_t* out,
                                  size_t n, hipStream_t s) {
