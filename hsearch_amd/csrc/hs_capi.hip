@@ -269,8 +269,8 @@ struct hs_handle {
   bool join8_tables_ok = false;  // int8 can carry the coordinate table
   double join8_scale = 0.0, join8_scale_w = 0.0;  // quantisation scales: 4-column rows, wide rows
   bool wide8_ok = false;         // the 8-column table is usable (wide rows on demand for k = 21..25)
-  uint32_t* pin_cnt = nullptr;   // 64 pinned words: where a batch's counters land (three small device ->
-                                 // host copies into PAGEABLE memory cost ~ 50 us of host staging per batch)
+  uint32_t* pin_cnt = nullptr;   // HS_CNT_WORDS pinned words: where a pass's counter block lands, in one copy (small
+                                 // device -> host copies into PAGEABLE memory cost ~ 50 us of host staging per batch)
   BatchHistory hist;
   Knobs knobs;
   bool wide8 = false;            // short k-mers: int8 rows over all 8 coordinate columns (hs_join8.hip)
@@ -428,6 +428,7 @@ inline bool use_projection(const hs_handle* h) {
 // all of them (table < 0) -- for n points given as codes or as doubles, into out[i * out_stride + f - f0],
 // on stream s: the MFMA pass + exact recomputation of the flagged values, or the exact kernel alone.
 // set = which flag list / counter pair to use (two tables are in flight during a build).
+#define HS_PROJ_SET_BATCH 3  // flag list 2 with the counter pair of the batch's counter block (HS_CNT_PROJ)
 hs_status hash_dispatch(hs_handle* h, const uint8_t* d_codes, const double* d_pts, uint64_t n, int table,
                         int32_t* out, int out_stride, int set, hipStream_t s) {
   const int K = (int)h->p.K, k = (int)h->p.k;
@@ -446,6 +447,7 @@ hs_status hash_dispatch(hs_handle* h, const uint8_t* d_codes, const double* d_pt
   // fixed point cannot carry): at most 0xE0000000 / F points per pass
   const uint64_t n_max = 0xE0000000ull / (uint64_t)F;
   if (n > n_max) {
+    if (set == HS_PROJ_SET_BATCH) set = 2;  // (pieces count from zero each: set 2's pair, with its fill)
     for (uint64_t i0 = 0; i0 < n; i0 += n_max)
       HS_CHECK(hash_dispatch(h, d_codes ? d_codes + i0 * k : nullptr, d_pts ? d_pts + i0 * h->d : nullptr,
                              std::min(n_max, n - i0), table, out + i0 * out_stride, out_stride, set, s));
@@ -460,9 +462,13 @@ hs_status hash_dispatch(hs_handle* h, const uint8_t* d_codes, const double* d_pt
   // fix kernel recomputes everything, which is still correct
   const uint64_t want = (uint64_t)n * (uint64_t)F / 32 + (1u << 20);
   const uint32_t cap = (uint32_t)std::min<uint64_t>(want, 1ull << 28);
+  // set HS_PROJ_SET_BATCH: a search batch's queries (flag list of set 2) counting in the batch's counter block,
+  // which the batch's reset has just cleared: no fill here, no copy of its own after the pass
+  const bool in_block = set == HS_PROJ_SET_BATCH;
+  if (in_block) set = 2;
   HS_HIP(h, h->proj_flags[set].reserve((size_t)cap * 8));
-  uint32_t* cnt = h->proj_cnt.as<uint32_t>() + 2 * set;
-  HS_HIP(h, hipMemsetAsync(cnt, 0, 8, s));
+  uint32_t* cnt = in_block ? h->counters.as<uint32_t>() + HS_CNT_PROJ : h->proj_cnt.as<uint32_t>() + 2 * set;
+  if (!in_block) HS_HIP(h, hipMemsetAsync(cnt, 0, 8, s));
   if (!d_codes) {
     HS_HIP(h, h->proj_xq.reserve((size_t)n * S * 64));
     HS_HIP(h, h->proj_xmeta.reserve((size_t)n * 24));
@@ -2240,7 +2246,8 @@ struct BatchPlan {
   bool use_join = false;    // bucket join (fp16 or int8 rows) in front of the exact decision; streaming otherwise
   bool use_i8 = false;      // ... in its int8 form (hs_join8.hip)
   int wide = 0;             // ... over all 8 coordinate columns (want_wide)
-  bool refine = false;      // the int8 join's survivors pass an 8-column int8 bound (hs_refine8_kernel)
+  bool refine = false;      // the int8 join's survivors pass an 8-column bound: hs_refine_codes_kernel when the
+                            // queries are k-mers (b.qcodes), hs_refine8_kernel (int8 rows) otherwise
   bool self_codes = false;  // self-join whose per-query quantities all come from the indexed codes
   bool ext_codes = false;   // queries given as codes that never become centres
   bool seg_sparse = false;  // probes grouped by a sort of the probes, not a counting sort over the buckets
@@ -2329,10 +2336,10 @@ struct Batch {
 static hipError_t launch_qrows(hs_handle* h, const BatchPlan& p, const Batch& b, hipStream_t s) {
   const int k = (int)h->p.k;
   uint32_t* const d_unsafe = h->counters.as<uint32_t>() + 8;
-  if (p.self_codes || p.ext_codes)
+  if (p.self_codes || p.ext_codes)  // (no second row: these batches' survivors are refined from the codes)
     return hs_launch_qprep8_codes(b.qcodes, b.nq, k, p.wide, b.r2, h->coords.as<double>(), h->jtab8.p,
                                   h->jtab8.as<char>() + 1024, h->jtab8.as<char>() + 1536, h->jtab8.as<float>() + 128,
-                                  h->c16.p, p.refine ? h->c8b.p : nullptr, s, b.radii);
+                                  h->c16.p, nullptr, s, b.radii);
   if (p.use_i8)
     return hs_launch_qprep8(b.centers, b.nq, k, p.wide, b.r2, h->jtab8.as<float>() + 128, h->c16.p, d_unsafe,
                             p.refine ? h->c8b.p : nullptr, s, b.radii);
@@ -2406,7 +2413,7 @@ static hs_status prepare_queries(hs_handle* h, const QueryCall& c, const BatchPl
   }
   if (p.use_join) {
     HS_HIP(h, h->c16.reserve((size_t)b.nq * 208 * 2));
-    if (p.refine) HS_HIP(h, h->c8b.reserve((size_t)b.nq * hs_join8_row_bytes(k, p.wide)));
+    if (p.refine && !b.qcodes) HS_HIP(h, h->c8b.reserve((size_t)b.nq * hs_join8_row_bytes(k, p.wide)));
     HS_HIP(h, hipEventRecord(h->evx[EV_FORK], h->stream));
     HS_HIP(h, hipStreamWaitEvent(h->stream2, h->evx[EV_FORK], 0));
     HS_HIP(h, launch_qrows(h, p, b, h->stream2));
@@ -2427,9 +2434,9 @@ static hs_status hash_and_probe(hs_handle* h, const QueryCall& c, const BatchPla
   if (c.pre_ints)
     HS_HIP(h, hipMemcpyAsync(h->qints.p, c.pre_ints, (size_t)b.nq * h->LK * 4, hipMemcpyDeviceToDevice, h->stream));
   else if (p.ext_codes)
-    HS_CHECK(hash_dispatch(h, b.qcodes, nullptr, b.nq, -1, h->qints.as<int32_t>(), h->LK, 2, h->stream));
+    HS_CHECK(hash_dispatch(h, b.qcodes, nullptr, b.nq, -1, h->qints.as<int32_t>(), h->LK, HS_PROJ_SET_BATCH, h->stream));
   else if (!p.self_codes)
-    HS_CHECK(hash_dispatch(h, nullptr, b.centers, b.nq, -1, h->qints.as<int32_t>(), h->LK, 2, h->stream));
+    HS_CHECK(hash_dispatch(h, nullptr, b.centers, b.nq, -1, h->qints.as<int32_t>(), h->LK, HS_PROJ_SET_BATCH, h->stream));
   HS_HIP(h, hipEventRecord(h->ev[1], h->stream));
   if (p.use_join) {
     HS_HIP(h, h->seg_keys.reserve(n1 * 8));
@@ -2570,7 +2577,7 @@ static hs_status read_items(hs_handle* h, const QueryCall& c, BatchPlan& p, Batc
                                   seg_shift_of(h), h->seg_vals.as<uint32_t>(), h->PW,
                                   p.async_items ? h->item_off.as<uint32_t>() + b.nqs : nullptr,
                                   h->seg_res.as<uint64_t>(), h->seg_n.as<uint32_t>() + 2,
-                                  h->item_desc.as<uint4>(), h->stream));
+                                  h->counters.as<uint32_t>() + HS_CNT_SPLIT, h->item_desc.as<uint4>(), h->stream));
   }
   // segments routed away from the join (HS_OPT_JOIN_MIN_Q / _M; none by default) go through the streaming
   // filter and its per-query distance tables, on the side stream beside the join
@@ -2645,22 +2652,28 @@ static hs_status finalize_hits(hs_handle* h, const QueryCall& c, const BatchPlan
   uint32_t* const d_cnt = h->counters.as<uint32_t>();
   const uint2* fin_list = h->prov.as<uint2>();
   const uint32_t* fin_count = d_cnt;
-  if (p.refine && b.n_items) {
-    HS_HIP(h, h->prov2.reserve((size_t)prov_cap * 8));
-    if (again) HS_HIP(h, hipMemsetAsync(d_cnt + 4, 0, 4, h->stream));  // (first pass: the batch's reset)
-    HS_HIP(h, hs_launch_refine8(h->tabs, h->prov.as<uint2>(), d_cnt, prov_cap, h->sorted_ql.as<uint32_t>(), h->c16.p,
-                                h->c8b.p, h->jtab8.as<char>() + 1024, h->jtab8.as<float>() + 128, k, L,
-                                h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(), h->prov2.as<uint2>(), d_cnt + 4,
-                                h->stream));
-    fin_list = h->prov2.as<uint2>();
-    fin_count = d_cnt + 4;
-  }
   const uint4* d_qpacked = nullptr;
-  if (b.qcodes && k <= 75) {  // the queries are k-mers: packed like the members, for the exact pass
+  if (b.qcodes && k <= 75) {  // the queries are k-mers: packed like the members, for the refinement and the exact pass
     HS_HIP(h, h->qpacked.reserve(std::max<size_t>(16, (size_t)b.nq * h->PW * 16)));
     HS_HIP(h, hs_launch_pack(b.qcodes, b.nq, k, h->alphabet, h->qpacked.as<uint4>(), d_cnt + HS_CNT_BAD_QUERY_CODE,
                              h->stream));
     d_qpacked = h->qpacked.as<uint4>();
+  }
+  if (p.refine && b.n_items) {
+    HS_HIP(h, h->prov2.reserve((size_t)prov_cap * 8));
+    if (again) HS_HIP(h, hipMemsetAsync(d_cnt + 4, 0, 4, h->stream));  // (first pass: the batch's reset)
+    if (b.qcodes)  // (p.refine: the int8 join, k <= 50.  No second query row on this path: launch_qrows)
+      HS_HIP(h, hs_launch_refine_codes(h->tabs, h->prov.as<uint2>(), d_cnt, prov_cap, h->sorted_ql.as<uint32_t>(),
+                                       d_qpacked, h->coords.as<double>(), h->alphabet, k, L, b.r2, b.radii,
+                                       h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(), h->prov2.as<uint2>(),
+                                       d_cnt + 4, h->stream));
+    else
+      HS_HIP(h, hs_launch_refine8(h->tabs, h->prov.as<uint2>(), d_cnt, prov_cap, h->sorted_ql.as<uint32_t>(), h->c16.p,
+                                  h->c8b.p, h->jtab8.as<char>() + 1024, h->jtab8.as<float>() + 128, k, L,
+                                  h->qstart.as<uint32_t>(), h->qcount.as<uint32_t>(), h->prov2.as<uint2>(), d_cnt + 4,
+                                  h->stream));
+    fin_list = h->prov2.as<uint2>();
+    fin_count = d_cnt + 4;
   }
   uint32_t* const qcnt = p.order_here ? h->qhits.as<uint32_t>() : nullptr;
   HS_HIP(h, hs_launch_finalize(h->tabs, h->codes.as<uint8_t>(), b.centers, b.qcodes, h->coords.as<double>(),
@@ -2703,14 +2716,19 @@ static hs_status search_pass(hs_handle* h, const QueryCall& c, const BatchPlan& 
   HS_HIP(h, hipEventRecord(h->ev[4], h->stream));
   HS_CHECK(finalize_hits(h, c, p, b, prov_cap, hit_cap, again, bout));
   HS_HIP(h, hipEventRecord(h->ev[5], h->stream));
-  // [0] survivors [1] hits [2..3] candidates ... [10..13] join statistics [20] order fallback
-  HS_HIP(h, hipMemcpyAsync(h->pin_cnt, d_cnt, 96, hipMemcpyDeviceToHost, h->stream));
-  if (!p.self_codes && use_projection(h))  // [32..33] MFMA projection of the queries: {slots reserved, values flagged}
-    HS_HIP(h, hipMemcpyAsync(h->pin_cnt + 32, h->proj_cnt.as<uint32_t>() + 4, 8, hipMemcpyDeviceToHost, h->stream));
-  if (p.async_items)  // [40] the real item count
-    HS_HIP(h, hipMemcpyAsync(h->pin_cnt + 40, h->item_off.as<uint32_t>() + b.nqs, 4, hipMemcpyDeviceToHost, h->stream));
-  if (p.use_join && p.use_i8 && b.n_items)  // [41] first item of the few-query class, [42] items (cut_items)
-    HS_HIP(h, hipMemcpyAsync(h->pin_cnt + 41, h->seg_n.as<uint32_t>() + 2, 8, hipMemcpyDeviceToHost, h->stream));
+  // ONE copy of the whole block: [0] survivors [1] hits [2..3] candidates ... [10..13] join statistics [20] order
+  // fallback, [HS_CNT_PROJ] the projection of the queries, [HS_CNT_SPLIT] first item of the few-query class and
+  // the items -- under async_items the real item count -- both written there by their kernels
+  HS_HIP(h, hipMemcpyAsync(h->pin_cnt, d_cnt, HS_CNT_WORDS * 4, hipMemcpyDeviceToHost, h->stream));
+  return HS_OK;
+}
+
+// The pinned words a pass's counter block lands in (small device -> host copies into pageable memory cost ~ 50 us
+// per batch)
+static hs_status ensure_pin_cnt(hs_handle* h) {
+  if (h->pin_cnt) return HS_OK;
+  HS_HIP(h, hipHostMalloc(reinterpret_cast<void**>(&h->pin_cnt), HS_CNT_WORDS * 4, hipHostMallocDefault));
+  memset(h->pin_cnt, 0, HS_CNT_WORDS * 4);
   return HS_OK;
 }
 
@@ -2724,12 +2742,9 @@ static hs_status filter_passes(hs_handle* h, uint32_t nq, uint32_t item_cap, boo
                                Pass pass) {
   uint32_t* const d_cnt = h->counters.as<uint32_t>();
   uint32_t prov_cap = (uint32_t)std::max<size_t>(h->prov.cap / 8, std::max<size_t>(1u << 20, 16ull * nq));
-  if (!h->pin_cnt) {  // (three small device -> host copies into pageable memory cost ~ 50 us per batch)
-    HS_HIP(h, hipHostMalloc(reinterpret_cast<void**>(&h->pin_cnt), 64 * 4, hipHostMallocDefault));
-    memset(h->pin_cnt, 0, 64 * 4);
-  }
+  HS_CHECK(ensure_pin_cnt(h));
   const uint32_t* const host_cnt = h->pin_cnt;
-  memset(h->pin_cnt, 0, 64 * 4);
+  memset(h->pin_cnt, 0, HS_CNT_WORDS * 4);
   double ms_verify = 0, ms_final = 0, ms_join = 0;
   uint32_t launches = 0;
   for (;;) {
@@ -2749,7 +2764,7 @@ static hs_status filter_passes(hs_handle* h, uint32_t nq, uint32_t item_cap, boo
 #endif
     if (host_cnt[HS_CNT_BAD_QUERY_CODE])
       return fail(h, HS_ERR_INVALID, "residue code outside the alphabet in the queries");
-    if (item_cap && (host_cnt[8] /* join legality */ || host_cnt[40] > item_cap)) return HS_SYNC_ITEMS;
+    if (item_cap && (host_cnt[8] /* join legality */ || host_cnt[HS_CNT_SPLIT + 1] > item_cap)) return HS_SYNC_ITEMS;
     ms_verify += ev_ms(h, 3, 4);
     if (join_timed) ms_join += ev_ms(h, 11, 10);
     ms_final += ev_ms(h, 4, 5);
@@ -2821,7 +2836,7 @@ static void account_batch(hs_handle* h, const BatchPlan& p, Batch& b) {
   const uint32_t* const cnt = h->pin_cnt;
   if (!p.self_codes && use_projection(h)) {
     h->prof.hash_values += (uint64_t)b.nq * h->LK;
-    h->prof.hash_flagged += cnt[33];
+    h->prof.hash_flagged += cnt[HS_CNT_PROJ + 1];
   }
   uint64_t cand_total;
   memcpy(&cand_total, cnt + 2, 8);
@@ -2832,9 +2847,10 @@ static void account_batch(hs_handle* h, const BatchPlan& p, Batch& b) {
     h->prof.join_row_bytes = (uint32_t)hs_join8_row_bytes((int)h->p.k, p.wide);
     h->prof.join_wide = (uint32_t)p.wide;
   }
-  if (p.async_items) b.n_items = cnt[40];
+  if (p.async_items) b.n_items = cnt[HS_CNT_SPLIT + 1];
   h->prof.join_items += b.n_items;
-  if (p.use_i8 && b.n_items && p.use_r && cnt[42]) h->prof.join_items_resident += cnt[42] - cnt[41];
+  if (p.use_i8 && b.n_items && p.use_r && cnt[HS_CNT_SPLIT + 1])
+    h->prof.join_items_resident += cnt[HS_CNT_SPLIT + 1] - cnt[HS_CNT_SPLIT];
   if (p.use_join) {
     unsigned long long js[2] = {0, 0};
     memcpy(js, cnt + 10, 16);  // the join statistics (d_cnt + 10), read back with the counters
@@ -2856,10 +2872,10 @@ static void learn_from_batch(hs_handle* h, const QueryCall& c, const BatchPlan& 
   if (!p.use_i8 || !b.n_items) return;
   m.item_cap_hint = b.n_items + b.n_items / 4 + 4096;
   ++m.resident_age;
-  if (p.use_r && cnt[42]) {
+  if (p.use_r && cnt[HS_CNT_SPLIT + 1]) {
     m.resident_age = 0;
     m.resident_nq = b.nq;
-    m.resident_share = (double)(cnt[42] - cnt[41]) / (double)cnt[42];
+    m.resident_share = (double)(cnt[HS_CNT_SPLIT + 1] - cnt[HS_CNT_SPLIT]) / (double)cnt[HS_CNT_SPLIT + 1];
   }
   unsigned long long issued = 0;
   memcpy(&issued, cnt + 10, 8);
@@ -3074,7 +3090,8 @@ static hs_status reduce_batch(hs_handle* h, const QueryCall& c, uint32_t nh, uin
 
 // Centres that are k-mers (every 8 doubles a row of the coordinate table, bit for bit -- what the
 // reference's centres files hold) run from their residue codes, as hs_query_codes's do: the same
-// results from k bytes per query where the point rows are 64 k.  One small kernel and one wait per call.
+// results from k bytes per query where the point rows are 64 k.  One small kernel and one wait per call; the flag
+// comes back into pinned memory.
 static hs_status recognise_kmers(hs_handle* h, QueryCall& c, uint64_t nq) {
   if (!c.centers || c.codes || !nq || !h->n || c.brute || h->knobs.no_recognise || h->p.k > 75) return HS_OK;
   const size_t cb = ((size_t)nq * h->p.k + 15) & ~(size_t)15;
@@ -3083,10 +3100,14 @@ static hs_status recognise_kmers(hs_handle* h, QueryCall& c, uint64_t nq) {
   HS_HIP(h, hipMemsetAsync(d_bad, 0, 4, h->stream));
   HS_HIP(h, hs_launch_recognise_kmers(c.centers, nq, h->p.k, h->coords.as<double>(), h->alphabet,
                                       h->rec_codes.as<uint8_t>(), d_bad, h->stream));
-  uint32_t bad = 1;
-  HS_HIP(h, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, h->stream));
+  // (the flag lands in pinned memory, in the last word of the block a pass's counters land in: a copy into
+  // pageable memory costs tens of us)
+  HS_CHECK(ensure_pin_cnt(h));
+  volatile uint32_t* const bad = h->pin_cnt + (HS_CNT_WORDS - 1);
+  *bad = 1;
+  HS_HIP(h, hipMemcpyAsync(h->pin_cnt + (HS_CNT_WORDS - 1), d_bad, 4, hipMemcpyDeviceToHost, h->stream));
   HS_HIP(h, hipStreamSynchronize(h->stream));
-  if (!bad) {
+  if (!*bad) {
     c.codes = h->rec_codes.as<uint8_t>();
     c.centers = nullptr;
     h->prof.queries_recognised = nq;

@@ -116,6 +116,12 @@ __host__ __device__ inline bool hs_key_equal(const int32_t* x, const int32_t* y,
 #define HS_CNT_SURVIVOR_OVERFLOW 21
 // hs_query_codes: a query's residue code lay outside the alphabet (hs_check_codes_kernel)
 #define HS_CNT_BAD_QUERY_CODE 22
+// Words of the counter block that hold what the host reads after a pass and no kernel counts in: written by
+// the kernels that produce the values, so that ONE copy of the block brings everything back (they were four).
+// Behind the item counters (words 32..47), which a repeated pass clears; cleared by the batch's reset only.
+#define HS_CNT_PROJ 48   // [2] the MFMA projection of the batch's queries: {slots reserved, values flagged}
+#define HS_CNT_SPLIT 50  // [2] hs_item_desc_kernel: first item of the few-query class, items (the real count)
+#define HS_CNT_WORDS 64  // words of the block, all read back
 #ifdef __HIPCC__
 __device__ __forceinline__ uint32_t hs_reserve_survivors(uint32_t* prov_count, uint32_t n) {
   const uint32_t base = atomicAdd(prov_count, n);
@@ -687,6 +693,7 @@ hipError_t hs_launch_item_desc(const hs_tables_dev& tabs, const uint64_t* d_seg_
                                then the capacity */,
                                const uint64_t* d_class_pos /* scan of the class flags, n_max + 1 entries */,
                                uint32_t* d_split /* [2]: first item of the query-resident class, items */,
+                               uint32_t* d_split_copy /* null, or [2]: the same two words once more */,
                                uint4* d_desc, hipStream_t s);
 // item numbering order of the segments: many-query segments first (stable two-class partition):
 // class flags [n + 1] (last = 0; hs_launch_seg_route) -> hs_exclusive_scan_u64 -> d_class_pos [n + 1] ->
@@ -721,7 +728,8 @@ hipError_t hs_launch_join(const uint4* d_desc, uint32_t n_items, const uint4* d_
 // d_tabW, scale[4..6]); the launchers that take d_tab8 expect d_tabW in its place then
 hipError_t hs_launch_jtables8(const double* d_coords, int alphabet, void* d_tab8, float* d_scale,
                               uint32_t* d_unsafe, void* d_tabR, void* d_tabW, hipStream_t s);
-// d_c8b (may be null): the second row per query (columns 4..7 + the refinement's scalars)
+// d_c8b (may be null): the second row per query (columns 4..7 + the refinement's scalars), hs_refine8_kernel's
+// input -- null for queries from codes, whose survivors hs_refine_codes_kernel refines without query rows
 // the same rows for queries that are k-mers given as codes (self-join): x^ from the tables, no doubles
 hipError_t hs_launch_qprep8_codes(const uint8_t* d_qcodes, uint32_t nq, int k, int wide, double r2,
                                   const double* d_coords, const void* d_tab8, const void* d_tabR,
@@ -736,6 +744,13 @@ hipError_t hs_launch_refine8(const hs_tables_dev& tabs, const uint2* d_prov, con
                              const void* d_c8b, const void* d_tabR, const float* d_scale, int k, int L,
                              const uint32_t* d_qstart, const uint32_t* d_qcount,
                              uint2* d_out, uint32_t* d_out_count, hipStream_t s);
+// the same step for queries that are k-mers (k <= 50): from the members' and the queries' packed words
+// (d_qpacked, hs_launch_pack's) and an alphabet x alphabet table of squared distances -- no query rows
+hipError_t hs_launch_refine_codes(const hs_tables_dev& tabs, const uint2* d_prov, const uint32_t* d_prov_count,
+                                  uint32_t prov_cap, const uint32_t* d_sorted_ql, const uint4* d_qpacked,
+                                  const double* d_coords, int alphabet, int k, int L, double r2,
+                                  const double* d_radii, const uint32_t* d_qstart, const uint32_t* d_qcount,
+                                  uint2* d_out, uint32_t* d_out_count, hipStream_t s);
 hipError_t hs_launch_gather_c8t(const void* d_c8, const uint32_t* d_sorted_ql, const uint32_t* d_seg_qoff,
                                 const uint32_t* d_seg_of, uint32_t nql, int L, int k, int wide, void* d_out,
                                 hipStream_t s);

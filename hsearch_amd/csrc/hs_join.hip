@@ -323,7 +323,7 @@ __global__ __launch_bounds__(256) void hs_seg_order_kernel(const uint64_t* __res
 // thread searches there; a block whose items span more positions than the window holds (a run of zero-item
 // positions inside it) falls back to the search in memory.  (One thread per SEGMENT, writing its items in
 // a loop, was measured slower: 32-byte stores scattered over the descriptor array.)
-// The first thread also leaves split[0] = first item of the query-resident class (the tail of the item list:
+// The first thread also leaves (in split, and in split_copy when given) split[0] = first item of the query-resident class (the tail of the item list:
 // the last class_pos[n_max] >> 32 positions of `order`), split[1] = number of items.
 __global__ __launch_bounds__(256) void hs_item_desc_kernel(hs_tables_dev tabs,
                                                            const uint64_t* __restrict__ seg_key,
@@ -338,6 +338,7 @@ __global__ __launch_bounds__(256) void hs_item_desc_kernel(hs_tables_dev tabs,
                                                            const uint32_t* __restrict__ n_items_dev,
                                                            const uint64_t* __restrict__ class_pos,
                                                            uint32_t* __restrict__ split,
+                                                           uint32_t* __restrict__ split_copy,
                                                            uint4* __restrict__ desc) {
   constexpr uint32_t WIN = 768;
   __shared__ uint32_t s_off[WIN + 1];
@@ -345,8 +346,13 @@ __global__ __launch_bounds__(256) void hs_item_desc_kernel(hs_tables_dev tabs,
   const uint32_t item0 = blockIdx.x * 256, item = item0 + threadIdx.x;
   if (n_items_dev) n_items = min(n_items, *n_items_dev);  // n_items = capacity of desc then
   if (item == 0) {
-    split[0] = item_off[n_max - (uint32_t)(class_pos[n_max] >> 32)];
-    split[1] = item_off[n_max];
+    const uint32_t first_r = item_off[n_max - (uint32_t)(class_pos[n_max] >> 32)], all = item_off[n_max];
+    split[0] = first_r;
+    split[1] = all;
+    if (split_copy) {  // (the batch's counter block: what the host reads after the pass rides in its one copy)
+      split_copy[0] = first_r;
+      split_copy[1] = all;
+    }
   }
   if (item0 >= n_items) return;
   if (threadIdx.x == 0) {
@@ -767,11 +773,12 @@ hipError_t hs_launch_item_desc(const hs_tables_dev& tabs, const uint64_t* d_seg_
                                const uint32_t* d_sorted_ql, const uint32_t* d_qcount, uint32_t n_items,
                                uint32_t jm, int shift, const uint32_t* d_order, int PW,
                                const uint32_t* d_n_items, const uint64_t* d_class_pos, uint32_t* d_split,
-                               uint4* d_desc, hipStream_t s) {
+                               uint32_t* d_split_copy, uint4* d_desc, hipStream_t s) {
   if (!n_items) return hipSuccess;
   hs_item_desc_kernel<<<blocks_for(n_items), 256, 0, s>>>(tabs, d_seg_key, d_seg_cnt, d_seg_qoff, d_item_off,
                                                           n_max, d_sorted_ql, d_qcount, n_items, jm, shift,
-                                                          d_order, PW, d_n_items, d_class_pos, d_split, d_desc);
+                                                          d_order, PW, d_n_items, d_class_pos, d_split, d_split_copy,
+                                                          d_desc);
   return hipGetLastError();
 }
 

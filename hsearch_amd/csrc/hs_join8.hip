@@ -304,7 +304,8 @@ __global__ __launch_bounds__(256) void hs_qprep8_kernel(const double* __restrict
 
 // The same two rows for a query that IS a k-mer of the coordinate table (self-join), from its codes:
 // x^ = the table's quantised rows (what the members carry), no saturation, norms from the table's
-// doubles.  One thread per query.
+// doubles.  One thread per query.  (The search passes c8b = null: the survivors of queries from codes are
+// refined from the packed words, hs_refine_codes_kernel, and the second row has no reader.)
 template <bool WIDE>
 __global__ __launch_bounds__(256) void hs_qprep8_codes_kernel(const uint8_t* __restrict__ qcodes, uint32_t nq,
                                                               int k, double r2_call,
@@ -2162,6 +2163,130 @@ __global__ __launch_bounds__(256) void hs_refine8_kernel(hs_tables_dev tabs,
   }
 }
 
+// hs_refine8_kernel for queries that are k-mers of the coordinate table (b.qcodes: queries given as codes,
+// centres recognised as k-mers, self-joins from codes).  The exact 8-column distance of such a pair is a sum
+// of k entries of an alphabet x alphabet table, so the filter needs no quantised rows at all: the member's
+// and the query's packed words (16 bytes each per 25 positions -- the query's by hs_pack_kernel, the exact
+// pass's own input) and one 4-byte LDS lookup per position, against two 112-byte query rows, 25 16-byte
+// lookups and 50 dot products.  The second query row (c8b) has no reader on this path and is not written.
+//
+// The table, built here from `coords`: T[x][c] = sum_j (x_x[j] - x_c[j])^2 over all 8 columns in double,
+// converted to float TOWARD ZERO; entries of codes outside the alphabet are 0 (codes are masked with 31:
+// 32 x 32 floats = 4 KB).  s = sum_p T[x_p][c_p] in fp32, and a pair passes unless s > hs_filter_bound(r^2),
+// r^2 = hs_r2_of (a query's own radius where the call has them).
+//
+// One-sided -- it may pass a non-hit and never drops a hit.  With D the sum in real arithmetic, u = 2^-53:
+//   reference   d2 >= D (1 - (8k + 2) u)     two roundings per term, 8k - 1 additions of non-negative terms
+//   a hit has   d2 <= R * R = r^2, or sqrt(d2) <= R (Clustering()), which gives d2 <= r^2 (1 + 4u)
+//   entries     T <= double sum <= t (1 + 10 u)   (t the real entry; the conversion only lowers)
+//   fp32 sum    s <= (sum_p T) (1 + 2^-24)^(k-1) <= (sum_p T) (1 + 2.93e-6)    k <= 50, terms >= 0
+// so a hit has s <= r^2 (1 + 2.93e-6) (1 + (8k + 16) u) < r^2 (1 + 3e-6); the margin is the next power of
+// ten, 1e-5 -- hs_filter_bound's, the fp32 filters' common bound: the smallest float >= r^2 (1 + 1e-5), one
+// ulp up.  A NaN anywhere (coordinates, radius) fails no comparison: the pair passes, and the exact pass
+// decides as it always did.  First-seen rule and compaction as in hs_refine8_kernel.
+template <int PW>
+__global__ __launch_bounds__(256) void hs_refine_codes_kernel(hs_tables_dev tabs,
+                                                              const uint2* __restrict__ prov,
+                                                              const uint32_t* __restrict__ prov_count,
+                                                              uint32_t prov_cap,
+                                                              const uint32_t* __restrict__ sorted_ql,
+                                                              const uint4* __restrict__ qpacked,
+                                                              const double* __restrict__ coords, int alphabet,
+                                                              int k, int L, double r2_call,
+                                                              const double* __restrict__ radii,
+                                                              const uint32_t* __restrict__ qstart,
+                                                              const uint32_t* __restrict__ qcount,
+                                                              uint2* __restrict__ out,
+                                                              uint32_t* __restrict__ out_count) {
+  constexpr int NPOS = 25 * PW;  // positions a packed k-mer can hold
+  // A survivor's loads form a chain -- list entry, probe number, the two packed k-mers, then id and first-seen
+  // words for the few that pass -- and the kernel's time is that chain's latency, not its arithmetic: every
+  // thread takes U survivors per round and issues each link for all of them before it uses the first.
+  constexpr int U = 4;
+  __shared__ double s_x[32 * 8];
+  __shared__ float s_T[32 * 32];
+  __shared__ uint2 s_keep[256 * U];
+  __shared__ uint32_t s_n, s_base;
+  const int tid = threadIdx.x;
+  s_x[tid] = tid < alphabet * 8 ? coords[tid] : 0.0;
+  if (tid == 0) s_n = 0;
+  __syncthreads();
+  for (int e = tid; e < 32 * 32; e += 256) {
+    const int x = e >> 5, c = e & 31;
+    double t = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const double d = s_x[x * 8 + j] - s_x[c * 8 + j];
+      t += d * d;
+    }
+    s_T[e] = (x < alphabet && c < alphabet) ? __double2float_rz(t) : 0.f;
+  }
+  __syncthreads();
+  const uint32_t n = min(*prov_count, prov_cap);
+  const float thr_call = hs_filter_bound(r2_call);
+  for (uint32_t base = blockIdx.x * (256u * U); base < n; base += gridDim.x * (256u * U)) {
+    uint32_t ql[U], pos[U], fs_id[U];
+    bool live[U], pass[U];
+    uint4 pk[U][PW], qk[U][PW];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t e = base + (uint32_t)(u * 256 + tid);
+      const uint2 raw = e < n ? prov[e] : make_uint2(0xffffffffu, 0u);
+      ql[u] = raw.x;
+      pos[u] = raw.y;
+      live[u] = raw.x != 0xffffffffu;  // unused slot of a wave's reserved block
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (live[u] && (ql[u] & HS_PROV_INDIRECT)) ql[u] = sorted_ql[ql[u] & ~HS_PROV_INDIRECT];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t q = live[u] ? ql[u] / (uint32_t)L : 0u, l = live[u] ? ql[u] % (uint32_t)L : 0u;
+#pragma unroll
+      for (int w = 0; w < PW; ++w) {  // (dead lanes: entry 0 of table 0 and query 0, loads without a branch)
+        pk[u][w] = tabs.t[l].packed[(uint64_t)(live[u] ? pos[u] : 0u) * PW + w];
+        qk[u][w] = qpacked[(uint64_t)q * PW + w];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t q = live[u] ? ql[u] / (uint32_t)L : 0u, l = live[u] ? ql[u] % (uint32_t)L : 0u;
+      const Stream256 sm = stitch<PW>(pk[u][0], pk[u][PW - 1]), sq = stitch<PW>(qk[u][0], qk[u][PW - 1]);
+      const float thr = radii ? hs_filter_bound(hs_r2_of(radii, q, r2_call)) : thr_call;
+      float s = 0.f;
+#define HS_R(P) \
+  if ((P) < NPOS && (P) < k) s += s_T[(stream_at<5 * (P)>(sm) << 5) | stream_at<5 * (P)>(sq)];
+#define HS_R10(P) HS_R(P) HS_R(P + 1) HS_R(P + 2) HS_R(P + 3) HS_R(P + 4) HS_R(P + 5) HS_R(P + 6) HS_R(P + 7) HS_R(P + 8) HS_R(P + 9)
+      HS_R10(0) HS_R10(10) HS_R(20) HS_R(21) HS_R(22) HS_R(23) HS_R(24)
+      if constexpr (PW == 2) { HS_R10(25) HS_R10(35) HS_R(45) HS_R(46) HS_R(47) HS_R(48) HS_R(49) }
+#undef HS_R10
+#undef HS_R
+      pass[u] = live[u] && !(s > thr);
+      fs_id[u] = (pass[u] && l) ? tabs.t[l].ids[pos[u]] : 0u;
+    }
+    // first-seen rule (hs_refine8_kernel); the whole wave calls
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t q = live[u] ? ql[u] / (uint32_t)L : 0u;
+      const int l = live[u] ? (int)(ql[u] % (uint32_t)L) : 0;
+      if (__ballot(pass[u] && l > 0))
+        pass[u] = pass[u] && !seen_in_earlier_table(tabs, qstart, qcount, q, l, L, fs_id[u], pass[u]);
+    }
+    // block-level compaction, one access to the global counter per block and round (hs_refine8_kernel)
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (pass[u]) s_keep[atomicAdd(&s_n, 1u)] = make_uint2(ql[u], pos[u]);
+    __syncthreads();
+    const uint32_t kept = s_n;
+    if (tid == 0 && kept) s_base = atomicAdd(out_count, kept);
+    __syncthreads();
+    for (uint32_t i = (uint32_t)tid; i < kept; i += 256u) out[s_base + i] = s_keep[i];
+    __syncthreads();
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+  }
+}
+
 inline unsigned blocks_for(uint64_t n, unsigned per = 256) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace
@@ -2336,5 +2461,22 @@ hipError_t hs_launch_refine8(const hs_tables_dev& tabs, const uint2* d_prov, con
     hs_refine8_kernel<2><<<1024, 256, 0, s>>>(tabs, d_prov, d_prov_count, prov_cap, d_sorted_ql,
                                               (const int8_t*)d_c8, (const int8_t*)d_c8b, (const uint4*)d_tabR,
                                               d_scale, k, L, d_qstart, d_qcount, d_out, d_out_count);
+  return hipGetLastError();
+}
+
+hipError_t hs_launch_refine_codes(const hs_tables_dev& tabs, const uint2* d_prov, const uint32_t* d_prov_count,
+                                  uint32_t prov_cap, const uint32_t* d_sorted_ql, const uint4* d_qpacked,
+                                  const double* d_coords, int alphabet, int k, int L, double r2,
+                                  const double* d_radii, const uint32_t* d_qstart, const uint32_t* d_qcount,
+                                  uint2* d_out, uint32_t* d_out_count, hipStream_t s) {
+  if (alphabet < 1 || alphabet > HS_ALPHABET_PAD || k < 1 || k > 50 || !d_qpacked) return hipErrorInvalidValue;
+  if (k <= 25)
+    hs_refine_codes_kernel<1><<<1024, 256, 0, s>>>(tabs, d_prov, d_prov_count, prov_cap, d_sorted_ql, d_qpacked,
+                                                   d_coords, alphabet, k, L, r2, d_radii, d_qstart, d_qcount, d_out,
+                                                   d_out_count);
+  else
+    hs_refine_codes_kernel<2><<<1024, 256, 0, s>>>(tabs, d_prov, d_prov_count, prov_cap, d_sorted_ql, d_qpacked,
+                                                   d_coords, alphabet, k, L, r2, d_radii, d_qstart, d_qcount, d_out,
+                                                   d_out_count);
   return hipGetLastError();
 }

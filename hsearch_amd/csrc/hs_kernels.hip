@@ -1947,9 +1947,11 @@ __global__ __launch_bounds__(256) void hs_recognise_kmers_kernel(const double* _
                                                                  const double* __restrict__ coords, int alphabet,
                                                                  uint8_t* __restrict__ out_codes,
                                                                  uint32_t* __restrict__ n_unrecognised) {
-  __shared__ unsigned long long s_rows[HS_ALPHABET_PAD * 8];
+  // rows at a stride of RS = 10 doubles: lanes that read different rows meet in 16 bank groups, not in 4
+  constexpr int RS = 10;
+  __shared__ __attribute__((aligned(16))) unsigned long long s_rows[HS_ALPHABET_PAD * RS];
   for (int t = threadIdx.x; t < HS_ALPHABET_PAD * 8; t += 256)
-    s_rows[t] = t < alphabet * 8 ? (unsigned long long)__double_as_longlong(coords[t]) : 0ull;
+    s_rows[(t >> 3) * RS + (t & 7)] = t < alphabet * 8 ? (unsigned long long)__double_as_longlong(coords[t]) : 0ull;
   __syncthreads();
   const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= total) return;
@@ -1961,12 +1963,29 @@ __global__ __launch_bounds__(256) void hs_recognise_kmers_kernel(const double* _
     g[2 * j] = (unsigned long long)__double_as_longlong(v.x);
     g[2 * j + 1] = (unsigned long long)__double_as_longlong(v.y);
   }
-  int code = -1;
-  for (int c = alphabet - 1; c >= 0; --c) {
+  // The candidate row from ONE coordinate: the rows whose first double has the group's bit pattern (a read of
+  // one LDS address by the whole wave per row, against 8 reads per row for the full comparison: the kernel is
+  // to run at the rate of its input, 64 bytes per thread).  One such row: the other 7 doubles against it.
+  // Several -- a table with equal first coordinates --: the full scan, for this group.
+  int code = -1, first_col = 0;
+  for (int c = alphabet - 1; c >= 0; --c)
+    if (s_rows[c * RS] == g[0]) {
+      code = c;
+      ++first_col;
+    }
+  if (first_col == 1) {
     unsigned long long diff = 0;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) diff |= g[j] ^ s_rows[c * 8 + j];
-    if (!diff) code = c;
+    for (int j = 1; j < 8; ++j) diff |= g[j] ^ s_rows[code * RS + j];
+    if (diff) code = -1;
+  } else if (first_col > 1) {
+    code = -1;
+    for (int c = alphabet - 1; c >= 0; --c) {
+      unsigned long long diff = 0;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) diff |= g[j] ^ s_rows[c * RS + j];
+      if (!diff) code = c;
+    }
   }
   out_codes[t] = (uint8_t)(code < 0 ? 0 : code);
   if (code < 0) atomicAdd(n_unrecognised, 1u);
