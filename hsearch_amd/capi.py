@@ -29,8 +29,11 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_cluster_profile", "hs_cluster_profile_dev", "hs_cluster_radii", "hs_cluster_radii_dev",
            "hs_cluster_summary_codes", "hs_msf", "hs_msf_dev", "hs_msf_edges", "hs_msf_cut", "hs_core_distance",
            "hs_core_distance_dev", "hs_density_tree", "hs_density_tree_dev", "hs_density_tree_edges",
-           "hs_density_tree_cut"]
+           "hs_density_tree_cut", "hs_query_topk", "hs_query_topk_dev", "hs_self_knn", "hs_self_knn_range",
+           "hs_self_knn_dev", "hs_self_knn_range_dev", "hs_topk_merge"]
 
+TOPK_MAX = 64        # HS_TOPK_MAX: the widest row of query_topk / self_knn / topk_merge
+NO_ID = 0xffffffff   # the id and table of an unused entry of such a row (its distance is +inf)
 NOISE = 0xffffffff   # HS_NOISE: the label of a k-mer that is neither core nor border (hs_dbscan)
 
 
@@ -215,6 +218,25 @@ def load(hooks=False):
             lib.hs_density_tree_cut.restype = C.c_int
             lib.hs_density_tree_cut.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                                 C.c_double, C.c_void_p, C.POINTER(C.c_uint64)]
+        # top-k: query_topk (h, centers, qcodes, nq, R, radii, topk, nn_id, nn_table, nn_dist, nn_count, n_hits);
+        # self_knn (h, [first, count,] R, sqrt_test, topk, nn_id, nn_table, nn_dist, nn_count, n_edges); topk_merge
+        # (q, id, table, dist, n_tuples, nq, topk, nn_id, nn_table, nn_dist, nn_count)
+        if hasattr(lib, "hs_query_topk"):
+            for fn in (lib.hs_query_topk, lib.hs_query_topk_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_uint32,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+            for fn in (lib.hs_self_knn, lib.hs_self_knn_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.POINTER(C.c_uint64)]
+            for fn in (lib.hs_self_knn_range, lib.hs_self_knn_range_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_double, C.c_int, C.c_uint32, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+            lib.hs_topk_merge.restype = C.c_int
+            lib.hs_topk_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                          C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _libs[hooks] = lib
     return _libs[hooks]
 
@@ -285,6 +307,33 @@ def merge_best(id, q, table, dist, cap=None):
         raise e
     m = int(n_out.value)
     return dict(id=oid[:m], q=oq[:m], table=ot[:m], dist=od[:m])
+
+
+def topk_merge(q, id, table, dist, nq, topk, out=None):
+    """hs_topk_merge (host only, no GPU): of tuples (q, id, table, dist) in any order, per q the topk smallest under
+    (dist, id) -- the rule of Engine.query_topk / Engine.self_knn, for reducing a raw hit list or merging the rows of
+    the parts of a partition (flatten them: q = np.repeat(np.arange(nq), topk)).  Tuples with id == capi.NO_ID are
+    skipped; a (q, id) given several times counts once with its smallest table.  dict(id, table, dist [nq][topk],
+    count [nq]); count is the number of distinct ids given for q -- over rows already cut at topk only a lower bound of
+    the hit count.  table=None: no tables are known, the rows' tables are all capi.NO_ID.  out: such a dict to write
+    into (it stays untouched when the input is invalid)."""
+    q = np.ascontiguousarray(q, dtype=np.uint32).ravel()
+    id = np.ascontiguousarray(id, dtype=np.uint32).ravel()
+    if table is not None:
+        table = np.ascontiguousarray(table, dtype=np.uint32).ravel()
+    dist = np.ascontiguousarray(dist, dtype=np.float64).ravel()
+    n = len(q)
+    assert id.shape == dist.shape == (n,) and (table is None or table.shape == (n,))
+    nq, topk = int(nq), int(topk)
+    rows = max(0, min(topk, TOPK_MAX))  # (an invalid topk is the library's to refuse)
+    if out is None:
+        out = dict(id=np.empty((nq, rows), dtype=np.uint32), table=np.empty((nq, rows), dtype=np.uint32),
+                   dist=np.empty((nq, rows), dtype=np.float64), count=np.empty(nq, dtype=np.uint32))
+    st = load().hs_topk_merge(_vp(q), _vp(id), None if table is None else _vp(table), _vp(dist), n, nq, topk, _vp(out["id"]), _vp(out["table"]),
+                              _vp(out["dist"]), _vp(out["count"]))
+    if st != HS_OK:
+        raise HsError(st, "hs_topk_merge")
+    return out
 
 
 def components_merge(labels, out=None):
@@ -907,6 +956,40 @@ class Engine:
         self._check(st)
         return int(n.value)
 
+    def query_topk(self, queries, topk, R=None, radii=None, codes=False):
+        """hs_query_topk: per query the topk smallest, under (dist, id), of the hits query() / query_codes() (R) or
+        query_radii() (radii) would return, selected on the device: dict(id, table, dist [nq][topk] -- unused entries
+        capi.NO_ID, capi.NO_ID, inf --, count uint32 [nq] = the query's full hit count, n_hits = their sum).  queries are
+        points [nq][d], or with codes=True residue codes [nq][k]."""
+        queries = np.ascontiguousarray(queries, dtype=np.uint8 if codes else np.float64)
+        nq = queries.shape[0]
+        assert queries.shape == (nq, self.k if codes else self.d)
+        assert (R is None) != (radii is None), "exactly one of R and radii"
+        if radii is not None:
+            radii = np.ascontiguousarray(radii, dtype=np.float64)
+            assert radii.shape == (nq,)
+        topk = int(topk)
+        rows = max(0, min(topk, TOPK_MAX))
+        nid = np.empty((nq, rows), dtype=np.uint32)
+        nt = np.empty((nq, rows), dtype=np.uint32)
+        nd = np.empty((nq, rows), dtype=np.float64)
+        cnt = np.empty(nq, dtype=np.uint32)
+        n = C.c_uint64(0)
+        self._check(self._lib.hs_query_topk(self._h, None if codes else _vp(queries), _vp(queries) if codes else None,
+                                            nq, 0.0 if R is None else float(R), None if radii is None else _vp(radii),
+                                            topk, _vp(nid), _vp(nt), _vp(nd), _vp(cnt), C.byref(n)))
+        return dict(id=nid, table=nt, dist=nd, count=cnt, n_hits=int(n.value))
+
+    def query_topk_dev(self, d_queries_ptr, nq, topk, R, d_radii_ptr, d_id, d_table, d_dist, d_count, codes=False):
+        """hs_query_topk_dev (device pointers as ints; d_radii_ptr None or 0: every query at R; d_table may be None):
+        the rows into uint32 / uint32 / float64 [nq][topk] and the counts into uint32 [nq]; returns n_hits."""
+        n = C.c_uint64(0)
+        self._check(self._lib.hs_query_topk_dev(self._h, None if codes else d_queries_ptr,
+                                                d_queries_ptr if codes else None, nq, float(R),
+                                                d_radii_ptr if d_radii_ptr else None, int(topk), d_id,
+                                                d_table if d_table else None, d_dist, d_count, C.byref(n)))
+        return int(n.value)
+
     def merge_first_table_dev(self, d_q, d_id, d_table, d_dist, n):
         """hs_merge_first_table_dev (device pointers as ints; in place): the number of tuples kept."""
         n_out = C.c_uint64(0)
@@ -1101,6 +1184,32 @@ class Engine:
         self._check(self._lib.hs_core_distance_dev(self._h, float(R), 1 if sqrt_test else 0, int(min_pts), d_core_ptr,
                                                    C.byref(nc), C.byref(ne)))
         return int(nc.value), int(ne.value)
+
+    def self_knn(self, R, topk, sqrt_test=True, first=0, count=None):
+        """hs_self_knn / hs_self_knn_range: the k-nearest-neighbour graph within R -- per k-mer first + t the topk
+        smallest, under (dist, id), of its edges in self_join(R, sqrt_test, first, count), selected on the device:
+        dict(id, table, dist [count][topk] -- unused entries capi.NO_ID, capi.NO_ID, inf --, count uint32 [count] = the
+        k-mer's degree (degrees()), n_edges).  dist[:, m - 2] is core_distance(R, m)["core"] for 2 <= m <= topk + 1."""
+        count = self._n() - first if count is None else count
+        topk = int(topk)
+        rows = max(0, min(topk, TOPK_MAX))
+        nid = np.empty((count, rows), dtype=np.uint32)
+        nt = np.empty((count, rows), dtype=np.uint32)
+        nd = np.empty((count, rows), dtype=np.float64)
+        cnt = np.empty(count, dtype=np.uint32)
+        ne = C.c_uint64(0)
+        self._check(self._lib.hs_self_knn_range(self._h, first, count, float(R), 1 if sqrt_test else 0, topk, _vp(nid),
+                                                _vp(nt), _vp(nd), _vp(cnt), C.byref(ne)))
+        return dict(id=nid, table=nt, dist=nd, count=cnt, n_edges=int(ne.value))
+
+    def self_knn_dev(self, d_id, d_table, d_dist, d_count, R, topk, sqrt_test=True, first=0, count=None):
+        """hs_self_knn_range_dev: the rows into uint32 / uint32 / float64 [count][topk] and the degrees into uint32 [count]
+        device memory (pointers as ints; d_table may be None); returns n_edges."""
+        count = self._n() - first if count is None else count
+        ne = C.c_uint64(0)
+        self._check(self._lib.hs_self_knn_range_dev(self._h, first, count, float(R), 1 if sqrt_test else 0, int(topk),
+                                                    d_id, d_table if d_table else None, d_dist, d_count, C.byref(ne)))
+        return int(ne.value)
 
     def density_tree(self, R, min_pts, sqrt_test=True, want_label=True):
         """hs_density_tree: DBSCAN* at every radius up to R -- the minimum spanning forest of the graph self_join(R,

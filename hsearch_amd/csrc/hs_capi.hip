@@ -120,10 +120,18 @@ struct Knobs {
 //   DT_CORE, DT_CORE_COLLECT  hs_core_distance / hs_density_tree (hs_density.hip): the core pass -- the threshold
 //                             rounds over the batch's hits at min_pts; COLLECT: and the pairs appended to the kept list
 //   DT_MIN_D, DT_MIN_PAIR     hs_density_tree: steps 1 and 2 of a Boruvka round under the mutual-reachability weight
+//   TOPK       hs_query_topk / hs_self_knn (hs_knn.hip): per query of the batch the topk smallest hits under (dist, id),
+//              written as rows row0 + (the query's number in the call) of the four device arrays (topk_reduce)
 struct HitSink {
   enum Kind { LIST, ANNOTATE, CC_UNION, DB_DEGREE, DB_UNITE, MSF_MIN_D, MSF_MIN_PAIR, MSF_COLLECT, DT_CORE,
-              DT_CORE_COLLECT, DT_MIN_D, DT_MIN_PAIR } kind = LIST;
+              DT_CORE_COLLECT, DT_MIN_D, DT_MIN_PAIR, TOPK } kind = LIST;
   uint32_t min_pts = 1;
+  uint32_t topk = 0;
+  uint64_t row0 = 0;
+  uint32_t* nn_id = nullptr;
+  uint32_t* nn_table = nullptr;  // (may stay null)
+  double* nn_dist = nullptr;
+  uint32_t* nn_count = nullptr;
 };
 
 // One query call's queries and what it asks (run_query, query_batch, probe_tabs)
@@ -239,6 +247,9 @@ struct hs_handle {
   // hs_core_distance / hs_density_tree (hs_density.hip: the state listed at its head; the rest is hs_msf's): the core
   // distance bits, the threshold and the round's minimum per indexed k-mer, the neighbours counted
   DevBuf dt_core, dt_thr, dt_next, dt_cnt;
+  // hs_query_topk / hs_self_knn (hs_knn.hip: the scratch listed at its head, all sized by a batch): hits per query,
+  // their scan, the scatter's cursors, the call's 64-bit hit count; the counts of a host-pointer call on their way out
+  DevBuf knn_cnt, knn_off, knn_cur, knn_total, knn_io_count;
   // hs_cluster_profile / hs_cluster_radii (hs_summary.hip: the state listed at its head), the counts of a row batch
   // when the caller wants none, and the arrays of a host-pointer call on their way in and out
   DevBuf sm_size, sm_tmp, sm_row_of, sm_off_of, sm_row_label, sm_row_off, sm_member, sm_d2, sm_err, sm_counts;
@@ -860,7 +871,8 @@ void hs_destroy(hs_handle* h) {
                     &h->ann_sorted, &h->ann_cnt, &h->cc_parent, &h->cc_cnt, &h->cc_label,
                     &h->db_deg, &h->db_anchor, &h->db_cnt, &h->msf_comp, &h->msf_best_d, &h->msf_best_pair,
                     &h->msf_out_pair, &h->msf_out_d, &h->msf_s_pair, &h->msf_s_d, &h->msf_cnt, &h->msf_kept, &h->dt_core, &h->dt_thr,
-                    &h->dt_next, &h->dt_cnt, &h->sm_size, &h->sm_tmp, &h->sm_row_of, &h->sm_off_of,
+                    &h->dt_next, &h->dt_cnt, &h->knn_cnt, &h->knn_off, &h->knn_cur, &h->knn_total, &h->knn_io_count,
+                    &h->sm_size, &h->sm_tmp, &h->sm_row_of, &h->sm_off_of,
                     &h->sm_row_label, &h->sm_row_off, &h->sm_member, &h->sm_d2, &h->sm_err, &h->sm_counts,
                     &h->sm_io_label, &h->sm_io_a, &h->sm_io_b, &h->sm_io_counts, &h->sm_io_f64, &h->sm_io_f64b};
   for (DevBuf* bf : bufs) bf->release();
@@ -3038,6 +3050,32 @@ static hs_status dt_core_batch(hs_handle* h, const QueryCall& c, uint32_t nh, ui
   return HS_OK;
 }
 
+// hs_knn.hip over n hits -- a batch's (key, value) pairs, or with d_key == null the four arrays of a merged list --
+// whose queries are [first, first + count) of the call: ALL hits of such a query are among them, each once (a batch
+// and a multi-probe chunk are ranges of queries, handed on whole), so their rows are final.  hit_key2 / hit_val2 take
+// the hits grouped by query: only a batch that sorts its hit LIST uses them (sort_batch_hits), and a merged list has
+// left them.  On the handle's stream.
+static hs_status topk_reduce(hs_handle* h, const QueryCall& c, const uint64_t* d_key, const uint64_t* d_val,
+                             const uint32_t* d_q, const uint32_t* d_id, const uint32_t* d_table, const double* d_dist,
+                             uint64_t n, uint32_t first, uint32_t count) {
+  if (!count) return HS_OK;
+  if (n >= (1ull << 32)) return fail(h, HS_ERR_CAPACITY, "more than 2^32 - 1 hits in one batch");
+  const size_t words = ((size_t)count + 1) * 4;
+  HS_HIP(h, h->knn_cnt.reserve(words));
+  HS_HIP(h, h->knn_off.reserve(words));
+  HS_HIP(h, h->knn_cur.reserve(words));
+  HS_HIP(h, h->hit_key2.reserve(std::max<size_t>(16, (size_t)n * 8)));
+  HS_HIP(h, h->hit_val2.reserve(std::max<size_t>(16, (size_t)n * 8)));
+  HS_HIP(h, h->temp.reserve(hs_knn_temp(count) + 256));
+  const HitSink& k = c.sink;
+  HS_HIP(h, hs_launch_knn_batch(d_key, d_val, d_q, d_id, d_table, d_dist, (uint32_t)n, c.self_first, first, count,
+                                h->knn_cnt.as<uint32_t>(), h->knn_off.as<uint32_t>(), h->knn_cur.as<uint32_t>(),
+                                h->temp.p, h->temp.cap, h->hit_key2.as<uint64_t>(), h->hit_val2.as<uint64_t>(),
+                                h->knn_total.as<uint64_t>(), k.topk, k.row0, k.nn_id, k.nn_table, k.nn_dist, k.nn_count,
+                                h->stream));
+  return HS_OK;
+}
+
 // first, count: the batch's queries within the call (for a self-join the k-mers c.self_first + first ...)
 static hs_status reduce_batch(hs_handle* h, const QueryCall& c, uint32_t nh, uint32_t first, uint32_t count) {
   const uint64_t* const pairs = h->hit_key.as<uint64_t>();
@@ -3084,6 +3122,8 @@ static hs_status reduce_batch(hs_handle* h, const QueryCall& c, uint32_t nh, uin
                                            h->dt_core.as<uint64_t>(), h->msf_comp.as<uint32_t>(),
                                            h->msf_best_d.as<uint64_t>(), h->msf_best_pair.as<uint64_t>(), n, h->stream));
       break;
+    case HitSink::TOPK:
+      return topk_reduce(h, c, pairs, h->hit_val.as<uint64_t>(), nullptr, nullptr, nullptr, nullptr, nh, first, count);
   }
   return HS_OK;
 }
@@ -3345,6 +3385,9 @@ static hs_status mp_query(hs_handle* h, const QueryCall& c, uint64_t nq, uint32_
     if (c.sink.kind == HitSink::ANNOTATE) {  // the chunk's merged list -- bounded by the chunk -- is reduced where it lies
       HS_CHECK(annot_reduce(h, nullptr, nullptr, h->mp_q.as<uint32_t>(), h->mp_id.as<uint32_t>(),
                             h->mp_table.as<uint32_t>(), h->mp_dist.as<double>(), kept));
+    } else if (c.sink.kind == HitSink::TOPK) {  // ... and selected: the chunk is a range of queries, its list whole
+      HS_CHECK(topk_reduce(h, c, nullptr, nullptr, h->mp_q.as<uint32_t>(), h->mp_id.as<uint32_t>(),
+                           h->mp_table.as<uint32_t>(), h->mp_dist.as<double>(), kept, (uint32_t)q0, (uint32_t)nc));
     } else if (kept && total + kept <= cap) {
       HS_HIP(h, hipMemcpyAsync(d_hit_q + total, h->mp_q.p, kept * 4, hipMemcpyDeviceToDevice, h->stream));
       HS_HIP(h, hipMemcpyAsync(d_hit_id + total, h->mp_id.p, kept * 4, hipMemcpyDeviceToDevice, h->stream));
@@ -4171,6 +4214,170 @@ hs_status hs_core_distance(hs_handle* h, double R, int sqrt_test, uint32_t min_p
 hs_status hs_core_distance_dev(hs_handle* h, double R, int sqrt_test, uint32_t min_pts, double* d_core, uint64_t* n_core,
                                uint64_t* n_edges) {
   return core_distance_any(h, R, sqrt_test, min_pts, d_core, n_core, n_edges, true);
+}
+
+// ---- hs_query_topk / hs_self_knn: the topk best hits per query (kernels, the rule and the passes: hs_knn.hip) ----
+static bool topk_ok(uint32_t topk) { return topk >= 1 && topk <= HS_TOPK_MAX; }
+
+// The sink of a call whose rows go to the four device arrays; the call's hit count zeroed
+static hs_status topk_begin(hs_handle* h, uint32_t topk, uint32_t* d_id, uint32_t* d_table, double* d_dist,
+                            uint32_t* d_count, HitSink* sink) {
+  HS_HIP(h, h->knn_total.reserve(16));
+  HS_HIP(h, hipMemsetAsync(h->knn_total.p, 0, 16, h->stream));
+  sink->kind = HitSink::TOPK;
+  sink->topk = topk;
+  sink->nn_id = d_id;
+  sink->nn_table = d_table;
+  sink->nn_dist = d_dist;
+  sink->nn_count = d_count;
+  return HS_OK;
+}
+
+static hs_status topk_total(hs_handle* h, uint64_t* total) {
+  HS_HIP(h, hipMemcpyAsync(total, h->knn_total.p, 8, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return HS_OK;
+}
+
+// The search with the selection in place of the hit list.  call: the queries on the device, with radii its R their
+// largest |radius|.  Everything that can be refused from the arguments is refused before the first kernel writes.
+static hs_status topk_search(hs_handle* h, QueryCall call, uint64_t nq, uint32_t topk, uint32_t* d_id, uint32_t* d_table,
+                             double* d_dist, uint32_t* d_count, uint64_t* n_hits) {
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
+  if (nq >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nq must be < 2^27 per call");
+  if (!(call.R == call.R)) return fail(h, HS_ERR_INVALID, "R is NaN");
+  HS_CHECK(topk_begin(h, topk, d_id, d_table, d_dist, d_count, &call.sink));
+  // (an empty index runs no batch: nothing would write the rows)
+  if (!h->n) HS_HIP(h, hs_launch_knn_fill(nq, topk, d_id, d_table, d_dist, d_count, h->stream));
+  uint64_t nh = 0;
+  HS_CHECK(run_query(h, call, nq, nullptr, nullptr, nullptr, nullptr, 0, &nh, nullptr));
+  HS_CHECK(topk_total(h, n_hits));
+  h->prof.hits = *n_hits;
+  return HS_OK;
+}
+
+static hs_status topk_args(hs_handle* h, const void* centers, const void* qcodes, uint64_t nq, uint32_t topk,
+                           const void* nn_id, const void* nn_dist, const void* nn_count, uint64_t* n_hits) {
+  if (!h || !n_hits) return HS_ERR_INVALID;
+  *n_hits = 0;
+  if ((centers != nullptr) == (qcodes != nullptr))
+    return fail(h, HS_ERR_INVALID, "hs_query_topk: exactly one of centers and qcodes must be given");
+  if (!topk_ok(topk)) return fail(h, HS_ERR_INVALID, "hs_query_topk: topk must be 1 .. 64");
+  if (nq && (!nn_id || !nn_dist || !nn_count)) return HS_ERR_INVALID;
+  return HS_OK;
+}
+
+hs_status hs_query_topk_dev(hs_handle* h, const double* d_centers, const uint8_t* d_qcodes, uint64_t nq, double R,
+                            const double* d_radii, uint32_t topk, uint32_t* d_nn_id, uint32_t* d_nn_table,
+                            double* d_nn_dist, uint32_t* d_nn_count, uint64_t* n_hits) {
+  HS_CHECK(topk_args(h, d_centers, d_qcodes, nq, topk, d_nn_id, d_nn_dist, d_nn_count, n_hits));
+  HS_CHECK(ensure_device(h));
+  QueryCall call{d_centers, d_qcodes, d_radii ? 0.0 : R};
+  if (d_radii && nq && nq < (1ull << 27)) HS_CHECK(radii_max_dev(h, d_radii, nq, &call.R));
+  call.radii = nq ? d_radii : nullptr;
+  return topk_search(h, call, nq, topk, d_nn_id, d_nn_table, d_nn_dist, d_nn_count, n_hits);
+}
+
+// rows x topk entries and rows counts staged on the device for a host-pointer call (io_id, io_table, io_dist,
+// knn_io_count), and their way out
+static hs_status topk_stage_out(hs_handle* h, uint64_t rows, uint32_t topk) {
+  const size_t e = (size_t)rows * topk;
+  HS_HIP(h, h->io_id.reserve(std::max<size_t>(16, e * 4)));
+  HS_HIP(h, h->io_table.reserve(std::max<size_t>(16, e * 4)));
+  HS_HIP(h, h->io_dist.reserve(std::max<size_t>(16, e * 8)));
+  HS_HIP(h, h->knn_io_count.reserve(std::max<size_t>(16, (size_t)rows * 4)));
+  return HS_OK;
+}
+
+static hs_status topk_copy_out(hs_handle* h, uint64_t rows, uint32_t topk, uint32_t* nn_id, uint32_t* nn_table,
+                               double* nn_dist, uint32_t* nn_count) {
+  const size_t e = (size_t)rows * topk;
+  if (!e) return HS_OK;
+  HS_HIP(h, hipMemcpyAsync(nn_id, h->io_id.p, e * 4, hipMemcpyDeviceToHost, h->stream));
+  if (nn_table) HS_HIP(h, hipMemcpyAsync(nn_table, h->io_table.p, e * 4, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipMemcpyAsync(nn_dist, h->io_dist.p, e * 8, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipMemcpyAsync(nn_count, h->knn_io_count.p, (size_t)rows * 4, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return HS_OK;
+}
+
+hs_status hs_query_topk(hs_handle* h, const double* centers, const uint8_t* qcodes, uint64_t nq, double R,
+                        const double* radii, uint32_t topk, uint32_t* nn_id, uint32_t* nn_table, double* nn_dist,
+                        uint32_t* nn_count, uint64_t* n_hits) {
+  HS_CHECK(topk_args(h, centers, qcodes, nq, topk, nn_id, nn_dist, nn_count, n_hits));
+  if (nq >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nq must be < 2^27 per call");
+  if (radii && !radii_max_host(radii, nq, &R)) return fail(h, HS_ERR_INVALID, "a radius is NaN");
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
+  if (!(R == R)) return fail(h, HS_ERR_INVALID, "R is NaN");
+  HS_CHECK(ensure_device(h));
+  QueryCall call{nullptr, nullptr, R};
+  HS_CHECK(stage_queries(h, centers, qcodes, nq ? radii : nullptr, nq, &call));
+  HS_CHECK(topk_stage_out(h, nq, topk));
+  // the rows are selected on the device: topk x 12 (16 with the tables) + 4 bytes per query cross PCIe
+  HS_CHECK(topk_search(h, call, nq, topk, h->io_id.as<uint32_t>(), nn_table ? h->io_table.as<uint32_t>() : nullptr,
+                       h->io_dist.as<double>(), h->knn_io_count.as<uint32_t>(), n_hits));
+  return topk_copy_out(h, nq, topk, nn_id, nn_table, nn_dist, nn_count);
+}
+
+// The self-join of [first, first + count) with every batch's pairs selected per k-mer: row t of the device arrays is
+// k-mer first + t
+static hs_status self_knn_run(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test, uint32_t topk,
+                              uint32_t* d_id, uint32_t* d_table, double* d_dist, uint32_t* d_count, uint64_t* n_edges) {
+  HitSink sink;
+  HS_CHECK(topk_begin(h, topk, d_id, d_table, d_dist, d_count, &sink));
+  hs_profile acc = {};
+  HS_CHECK(self_join_chunks(h, first, count, R, sqrt_test, sink, &acc,
+                            [h, first](const QueryCall& call, uint64_t q0, uint64_t nq) -> hs_status {
+    QueryCall cc = call;
+    cc.sink.row0 = q0 - first;  // (the chunk's query 0 is k-mer q0)
+    uint64_t nh = 0;
+    return run_query(h, cc, nq, nullptr, nullptr, nullptr, nullptr, 0, &nh, nullptr);
+  }));
+  uint64_t total = 0;
+  HS_CHECK(topk_total(h, &total));
+  h->prof = acc;
+  h->prof.hits = total;
+  if (n_edges) *n_edges = total;
+  return HS_OK;
+}
+
+static hs_status self_knn_any(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test, uint32_t topk,
+                              uint32_t* nn_id, uint32_t* nn_table, double* nn_dist, uint32_t* nn_count,
+                              uint64_t* n_edges, bool dev) {
+  if (!h) return HS_ERR_INVALID;
+  if (n_edges) *n_edges = 0;
+  HS_CHECK(self_join_check(h, first, count, topk_ok(topk) && (!count || (nn_id && nn_dist && nn_count))));
+  if (!(R == R)) return fail(h, HS_ERR_INVALID, "R is NaN");
+  if (dev) return self_knn_run(h, first, count, R, sqrt_test, topk, nn_id, nn_table, nn_dist, nn_count, n_edges);
+  HS_CHECK(topk_stage_out(h, count, topk));
+  HS_CHECK(self_knn_run(h, first, count, R, sqrt_test, topk, h->io_id.as<uint32_t>(),
+                        nn_table ? h->io_table.as<uint32_t>() : nullptr, h->io_dist.as<double>(),
+                        h->knn_io_count.as<uint32_t>(), n_edges));
+  return topk_copy_out(h, count, topk, nn_id, nn_table, nn_dist, nn_count);
+}
+
+hs_status hs_self_knn(hs_handle* h, double R, int sqrt_test, uint32_t topk, uint32_t* nn_id, uint32_t* nn_table,
+                      double* nn_dist, uint32_t* nn_count, uint64_t* n_edges) {
+  if (!h) return HS_ERR_INVALID;
+  return self_knn_any(h, 0, h->n, R, sqrt_test, topk, nn_id, nn_table, nn_dist, nn_count, n_edges, false);
+}
+
+hs_status hs_self_knn_range(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test, uint32_t topk,
+                            uint32_t* nn_id, uint32_t* nn_table, double* nn_dist, uint32_t* nn_count,
+                            uint64_t* n_edges) {
+  return self_knn_any(h, first, count, R, sqrt_test, topk, nn_id, nn_table, nn_dist, nn_count, n_edges, false);
+}
+
+hs_status hs_self_knn_dev(hs_handle* h, double R, int sqrt_test, uint32_t topk, uint32_t* d_nn_id, uint32_t* d_nn_table,
+                          double* d_nn_dist, uint32_t* d_nn_count, uint64_t* n_edges) {
+  if (!h) return HS_ERR_INVALID;
+  return self_knn_any(h, 0, h->n, R, sqrt_test, topk, d_nn_id, d_nn_table, d_nn_dist, d_nn_count, n_edges, true);
+}
+
+hs_status hs_self_knn_range_dev(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test, uint32_t topk,
+                                uint32_t* d_nn_id, uint32_t* d_nn_table, double* d_nn_dist, uint32_t* d_nn_count,
+                                uint64_t* n_edges) {
+  return self_knn_any(h, first, count, R, sqrt_test, topk, d_nn_id, d_nn_table, d_nn_dist, d_nn_count, n_edges, true);
 }
 
 // The core pass, then hs_msf's rounds under the mutual-reachability weight: from the kept list when the core pass could

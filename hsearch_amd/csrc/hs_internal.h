@@ -554,6 +554,21 @@ hipError_t hs_launch_annot_reduce(const uint64_t* d_key, const uint64_t* d_val, 
 hipError_t hs_launch_annot_gather(const uint32_t* d_sorted_id, uint32_t cnt, uint64_t* d_best_dist,
                                   const uint32_t* d_best_tq, uint32_t n_slots, uint32_t* d_out_id, uint32_t* d_out_q,
                                   uint32_t* d_out_table, double* d_out_dist, hipStream_t s);
+// top-k hits per query (hs_knn.hip; the rule, the passes and the scratch are written at its head): the hits of one
+// batch -- (d_key, d_val), or with d_key == null the four arrays of a merged list -- whose queries are [first, first +
+// count) of the call, selected per query into rows row0 + first ... of the output arrays (d_nn_table may be null).
+// d_cnt, d_off [count + 1], d_cur [count], d_seg_d, d_seg_w [n_hits], d_temp of hs_knn_temp(count) bytes; *d_total
+// (64 bits) grows by the batch's hits.  self_first != HS_NO_SELF: the pair of a k-mer with itself is no hit.
+size_t hs_knn_temp(uint32_t count);
+hipError_t hs_launch_knn_batch(const uint64_t* d_key, const uint64_t* d_val, const uint32_t* d_q, const uint32_t* d_id,
+                               const uint32_t* d_table, const double* d_dist, uint32_t n_hits, uint32_t self_first,
+                               uint32_t first, uint32_t count, uint32_t* d_cnt, uint32_t* d_off, uint32_t* d_cur,
+                               void* d_temp, size_t temp_bytes, uint64_t* d_seg_d, uint64_t* d_seg_w, uint64_t* d_total,
+                               uint32_t topk, uint64_t row0, uint32_t* d_nn_id, uint32_t* d_nn_table, double* d_nn_dist,
+                               uint32_t* d_nn_count, hipStream_t s);
+// rows of padding with zero counts: a call that ran no batch
+hipError_t hs_launch_knn_fill(uint64_t rows, uint32_t topk, uint32_t* d_nn_id, uint32_t* d_nn_table, double* d_nn_dist,
+                              uint32_t* d_nn_count, hipStream_t s);
 // connected components of the self-join's graph (hs_components.hip): d_parent [n] is a union-find forest with
 // parent[x] <= x, d_counts two 64-bit words {ordered pairs united, roots}.  begin: the identity and zero counts;
 // union: a batch's pairs (self_first + (key >> 37), (uint32_t)key) as the exact pass leaves them in d_key, the

@@ -16,6 +16,9 @@
 // -linkage density -minpts M (hsearch::DensityTree): the clusters file holds the DBSCAN* clusters at the threshold
 // (dbscan's without their border k-mers), <o>hclust.core.txt every k-mer's core distance; with it -tree 1 writes the
 // density tree -- DBSCAN at every radius up to the threshold -- in the same format, and -centers 1 works as for dbscan.
+// -knn N (-n; 1..64, with -linkage single, dbscan or density) writes beside the clusters file the k-nearest-neighbour
+// graph within the threshold as <o>hclust.knn.txt (hsearch::KnnGraph): one line per k-mer -- its name, its degree, then
+// its at most N nearest neighbours as name / distance pairs.
 #include <stdio.h>
 #include <stdlib.h>
 #include <time.h>
@@ -54,6 +57,8 @@ const Opt kOpts[] = {
     {"minsize", 'm', "centers: members a cluster needs to get a centre [50]", false},
     {"tree", 't', "1: also write <output>hclust.tree.txt, the single-linkage tree up to the threshold, one line per "
                   "merge in merge order: two k-mer names and the distance; with -linkage single [0]", false},
+    {"knn", 'n', "N (1..64): also write <output>hclust.knn.txt, per k-mer its name, its number of neighbours within the "
+                 "threshold and its N nearest as name / distance pairs; with -linkage single, dbscan or density [off]", false},
 };
 void Help(const char* prog) {
   fprintf(stderr, "Usage: %s [OPTIONS]\n\nOptions:\n", prog);
@@ -169,6 +174,20 @@ int main(int argc, const char* argv[]) {
     fprintf(stderr, "ERROR: -tree goes with -linkage single only: the tree is the single-linkage tree\n");
     return EXIT_FAILURE;
   }
+  uint32_t knn = 0;  // 0: no graph file
+  if (val.count("knn")) {
+    if (linkage == "greedy") {
+      fprintf(stderr, "ERROR: -knn goes with -linkage single, dbscan or density, not with the greedy leader clusters\n");
+      return EXIT_FAILURE;
+    }
+    char* end = nullptr;
+    const unsigned long long m = strtoull(val["knn"].c_str(), &end, 10);
+    if (end == val["knn"].c_str() || *end || m < 1 || m > 64 || val["knn"][0] == '-') {
+      fprintf(stderr, "ERROR: -knn must be a whole number 1..64, not '%s'\n", val["knn"].c_str());
+      return EXIT_FAILURE;
+    }
+    knn = (uint32_t)m;
+  }
   uint32_t seed;
   if (val.count("seed")) {
     seed = (uint32_t)strtoul(val["seed"].c_str(), nullptr, 10);
@@ -206,6 +225,16 @@ int main(int argc, const char* argv[]) {
     if (st != 0) {
       fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), st);
       return EXIT_FAILURE;
+    }
+    if (knn) {
+      uint64_t n_edges = 0;
+      const int kst = hsearch::KnnGraph(kmers, hash_K, hash_L, hash_W, hash_R, knn, val["output"], planes, device, &err,
+                                        &n_edges, seed);
+      if (kst != 0) {
+        fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), kst);
+        return EXIT_FAILURE;
+      }
+      printf("knn_graph_edges = %llu\n", (unsigned long long)n_edges);
     }
     clock_gettime(CLOCK_MONOTONIC, &t1);
     printf("num_of_clusters = %llu\n", (unsigned long long)n_clusters);

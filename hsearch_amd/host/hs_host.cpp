@@ -199,10 +199,16 @@ int RunSearch(hs_params prm, const Planes& planes, const double* coords,
               const uint8_t* qcodes, uint64_t nq, double R, const std::vector<int>& devices, bool sharded,
               SearchHits* out, std::string* err, std::vector<uint64_t>* table_sizes,
               const uint8_t* db_sample = nullptr, uint64_t n_db_sample = 0, const double* radii = nullptr,
-              bool annotate = false) {
+              bool annotate = false, uint32_t topk = 0) {
   const uint32_t world = (uint32_t)devices.size();
   if (!world) {
     if (err) *err = "no device given";
+    return HS_ERR_INVALID;
+  }
+  if (topk && (sharded || annotate)) {  // (the exchange gathers hit lists; an annotation has one line per k-mer)
+    if (err)
+      *err = sharded ? "top-k hits per centre are not supported together with the multi-GPU exchange"
+                     : "top-k hits per centre are not supported together with best_per_position";
     return HS_ERR_INVALID;
   }
   if (radii && sharded) {  // (hs_comm_query* take one radius)
@@ -275,6 +281,26 @@ int RunSearch(hs_params prm, const Planes& planes, const double* coords,
       st = AnnotateInto(h, flat, qcodes, nq, R, radii, out);
       if (st != HS_OK && err) *err = std::string("hs_annotate: ") + hs_last_error(h);
       return st;
+    }
+    if (topk) {  // the rows selected on the device; `out` receives their entries, centre by centre, best first
+      std::vector<uint32_t> nn_id((size_t)nq * topk), nn_table((size_t)nq * topk), nn_count(nq);
+      std::vector<double> nn_dist((size_t)nq * topk);
+      uint64_t n_hits = 0;
+      st = hs_query_topk(h, qcodes ? nullptr : flat, qcodes, nq, R, radii, topk, nn_id.data(), nn_table.data(),
+                         nn_dist.data(), nn_count.data(), &n_hits);
+      if (st != HS_OK) {
+        if (err) *err = std::string("hs_query_topk: ") + hs_last_error(h);
+        return st;
+      }
+      for (uint64_t q = 0; q < nq; ++q)
+        for (uint32_t r = 0; r < topk && r < nn_count[q]; ++r) {
+          out->q.push_back((uint32_t)q);
+          out->id.push_back(nn_id[q * topk + r]);
+          out->table.push_back(nn_table[q * topk + r]);
+          out->dist.push_back(nn_dist[q * topk + r]);
+        }
+      out->n = out->q.size();
+      return HS_OK;
     }
     uint64_t cap = std::max<uint64_t>(1024, 16 * nq);
     for (;;) {
@@ -444,10 +470,10 @@ int Search(const std::vector<Point>& kmers, const std::vector<Point>& centers,
            const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
            const double& hash_R, const std::string& output_file, const Planes& planes, int device,
            std::string* err, std::vector<uint64_t>* table_sizes, uint32_t probes, const std::vector<double>* radii,
-           bool best_per_position) {
+           bool best_per_position, uint32_t topk) {
   return SearchSharded(kmers, centers, kmer_names, center_names, hash_K, hash_L, hash_W, hash_R, output_file,
                        planes, std::vector<int>(1, device), false, err, table_sizes, probes, radii,
-                       best_per_position);
+                       best_per_position, topk);
 }
 
 int SearchSharded(const std::vector<Point>& kmers, const std::vector<Point>& centers,
@@ -456,7 +482,7 @@ int SearchSharded(const std::vector<Point>& kmers, const std::vector<Point>& cen
                   const double& hash_R, const std::string& output_file, const Planes& planes,
                   const std::vector<int>& devices, bool use_comm, std::string* err,
                   std::vector<uint64_t>* table_sizes, uint32_t probes, const std::vector<double>* radii,
-                  bool best_per_position) {
+                  bool best_per_position, uint32_t topk) {
   if (!RadiiMatch(radii, centers.size(), err)) return HS_ERR_INVALID;
   struct ProbesScope {
     explicit ProbesScope(uint32_t t) { g_probes = t; }
@@ -484,7 +510,7 @@ int SearchSharded(const std::vector<Point>& kmers, const std::vector<Point>& cen
                            [&](hs_handle* h, uint32_t) { return hs_index_build(h, codes.data(), kmers.size()); },
                            flat.data(), nullptr, centers.size(), hash_R, devices, use_comm || devices.size() > 1,
                            &hits, err, table_sizes, codes.data(), std::min<uint64_t>(kmers.size(), 32768),
-                           radii ? radii->data() : nullptr, best_per_position);
+                           radii ? radii->data() : nullptr, best_per_position, topk);
   if (st != HS_OK) return st;
   std::ofstream fout(output_file.c_str());
   for (uint64_t i = 0; i < hits.n; ++i)  // :240-241; best_per_position: one line per k-mer reached, k-mers ascending
@@ -530,10 +556,10 @@ int SearchProteins(const ProteinDB& db, uint32_t kmer_length, const std::vector<
                    const uint32_t& hash_L, const double& hash_W, const double& hash_R,
                    const std::string& output_file, const Planes& planes, int device, std::string* err,
                    std::vector<uint64_t>* table_sizes, uint64_t* n_windows, bool best_per_position,
-                   const std::vector<double>* radii) {
+                   const std::vector<double>* radii, uint32_t topk) {
   return SearchProteinsSharded(db, kmer_length, centers, center_names, hash_K, hash_L, hash_W, hash_R,
                                output_file, planes, std::vector<int>(1, device), false, err, table_sizes,
-                               n_windows, best_per_position, nullptr, radii);
+                               n_windows, best_per_position, nullptr, radii, topk);
 }
 
 int SearchProteinsSharded(const ProteinDB& db, uint32_t kmer_length, const std::vector<Point>& centers,
@@ -542,7 +568,7 @@ int SearchProteinsSharded(const ProteinDB& db, uint32_t kmer_length, const std::
                           const std::string& output_file, const Planes& planes,
                           const std::vector<int>& devices, bool use_comm, std::string* err,
                           std::vector<uint64_t>* table_sizes, uint64_t* n_windows, bool best_per_position,
-                          const std::vector<uint8_t>* center_codes, const std::vector<double>* radii) {
+                          const std::vector<uint8_t>* center_codes, const std::vector<double>* radii, uint32_t topk) {
   const uint32_t dim = 8 * kmer_length;
   if (!RadiiMatch(radii, centers.size(), err)) return HS_ERR_INVALID;
   if (center_codes && center_codes->size() != centers.size() * (size_t)kmer_length) {
@@ -595,7 +621,7 @@ int SearchProteinsSharded(const ProteinDB& db, uint32_t kmer_length, const std::
       },
       flat.data(), center_codes ? center_codes->data() : nullptr, centers.size(), hash_R, devices,
       use_comm || devices.size() > 1, &hits, err, table_sizes, nullptr, 0, radii ? radii->data() : nullptr,
-      best_per_position);
+      best_per_position, topk);
   if (rst != HS_OK) return rst;
   if (n_windows) *n_windows = n_win;
   const uint64_t n_hits = hits.n;
@@ -1140,6 +1166,63 @@ int DensityTree(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const ui
                 uint32_t unknown_seed, uint32_t centers_min_size) {
   return DbscanOrDensity(kmers, hash_K, hash_L, hash_W, hash_R, min_pts, output_file, planes, device, err, n_clusters,
                          unknown_seed, centers_min_size, true, tree, n_tree_edges);
+}
+
+int KnnGraph(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
+             const double& hash_R, const uint32_t& topk, const std::string& output_file, const Planes& planes, int device,
+             std::string* err, uint64_t* n_edges, uint32_t unknown_seed) {
+  if (topk < 1 || topk > HS_TOPK_MAX) {
+    if (err) *err = "KnnGraph: topk must be 1 .. 64";
+    return HS_ERR_INVALID;
+  }
+  std::vector<uint8_t> codes;
+  const int cs = ClusterCodes(kmers, hash_K, hash_L, hash_W, planes, unknown_seed, &codes, err);
+  if (cs != HS_OK) return cs;
+  const size_t n = kmers.size();
+  hs_params prm;
+  memset(&prm, 0, sizeof(prm));
+  prm.k = planes.dim / 8;
+  prm.K = hash_K;
+  prm.L = hash_L;
+  prm.W = hash_W;
+  prm.device = device;
+  hs_handle* h = nullptr;
+  hs_status st = hs_create(&prm, planes.a.data(), planes.b.data(), nullptr, &h);
+  const char* what = "hs_create";
+  if (st == HS_OK) {
+    what = "hs_index_build";
+    st = hs_index_build(h, codes.data(), n);
+  }
+  std::vector<uint32_t> nn_id(n * topk), nn_count(n);
+  std::vector<double> nn_dist(n * topk);
+  uint64_t edges = 0;
+  if (st == HS_OK) {
+    what = "hs_self_knn";
+    st = hs_self_knn(h, hash_R, 1, topk, nn_id.data(), nullptr, nn_dist.data(), nn_count.data(), &edges);  // sqrt(d2) <= R
+  }
+  if (st != HS_OK) {
+    if (err) *err = std::string(what) + ": " + (h ? hs_last_error(h) : "no handle");
+    if (h) hs_destroy(h);
+    return st;
+  }
+  hs_destroy(h);
+  std::ofstream fout((output_file + "hclust.knn.txt").c_str());
+  if (!fout) {
+    if (err) *err = "cannot write " + output_file + "hclust.knn.txt";
+    return HS_ERR_IO;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    fout << kmers[i].name << " " << nn_count[i];
+    for (uint32_t r = 0; r < topk && r < nn_count[i]; ++r) {
+      char num[64];
+      snprintf(num, sizeof(num), "%.17g", nn_dist[i * topk + r]);
+      fout << " " << kmers[nn_id[i * topk + r]].name << " " << num;
+    }
+    fout << "\n";
+  }
+  fout.close();
+  if (n_edges) *n_edges = edges;
+  return HS_OK;
 }
 
 int Clustering(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L,

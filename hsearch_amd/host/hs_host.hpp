@@ -61,7 +61,11 @@ int Search(const std::vector<Point>& kmers, const std::vector<Point>& centers,
            const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
            const double& hash_R, const std::string& output_file, const Planes& planes, int device,
            std::string* err, std::vector<uint64_t>* table_sizes = nullptr, uint32_t probes = 0,
-           const std::vector<double>* radii = nullptr, bool best_per_position = false);
+           const std::vector<double>* radii = nullptr, bool best_per_position = false, uint32_t topk = 0);
+// topk != 0 (Search, SearchProteins and the one-GPU form of their *Sharded() versions): per centre only its topk best
+// hits, selected on the device (hs_query_topk in include/hsearch.h) -- the usual lines, per centre at most topk of
+// them, in ascending (distance, k-mer index) instead of (table, k-mer index).  It composes with radii and probes; the
+// multi-GPU exchange and best_per_position refuse it.
 // radii (Search, SearchProteins, SearchBruteForce and the one-GPU form of their *Sharded() versions): one radius
 // per centre in place of hash_R -- centre i's lines are those of a run with hash_R = (*radii)[i]
 // (hs_query_radii); the multi-GPU exchange takes one radius and refuses them.
@@ -98,7 +102,7 @@ int SearchSharded(const std::vector<Point>& kmers, const std::vector<Point>& cen
                   const double& hash_R, const std::string& output_file, const Planes& planes,
                   const std::vector<int>& devices, bool use_comm, std::string* err,
                   std::vector<uint64_t>* table_sizes = nullptr, uint32_t probes = 0,
-                  const std::vector<double>* radii = nullptr, bool best_per_position = false);
+                  const std::vector<double>* radii = nullptr, bool best_per_position = false, uint32_t topk = 0);
 // best_per_position (Search, SearchSharded; SearchProteins* below): instead of the hits, one line per database
 // k-mer reached, "<kmer name> <center> <dist>" with its nearest centre, k-mers ascending -- hs_annotate on one
 // GPU; with query blocks over several GPUs every rank annotates its block and the lists are merged by
@@ -142,7 +146,7 @@ int SearchProteins(const ProteinDB& db, uint32_t kmer_length, const std::vector<
                    const uint32_t& hash_L, const double& hash_W, const double& hash_R,
                    const std::string& output_file, const Planes& planes, int device, std::string* err,
                    std::vector<uint64_t>* table_sizes = nullptr, uint64_t* n_windows = nullptr,
-                   bool best_per_position = false, const std::vector<double>* radii = nullptr);
+                   bool best_per_position = false, const std::vector<double>* radii = nullptr, uint32_t topk = 0);
 int SearchProteinsSharded(const ProteinDB& db, uint32_t kmer_length, const std::vector<Point>& centers,
                           const std::vector<std::string>& center_names, const uint32_t& hash_K,
                           const uint32_t& hash_L, const double& hash_W, const double& hash_R,
@@ -150,7 +154,7 @@ int SearchProteinsSharded(const ProteinDB& db, uint32_t kmer_length, const std::
                           const std::vector<int>& devices, bool use_comm, std::string* err,
                           std::vector<uint64_t>* table_sizes = nullptr, uint64_t* n_windows = nullptr,
                           bool best_per_position = false, const std::vector<uint8_t>* center_codes = nullptr,
-                          const std::vector<double>* radii = nullptr);
+                          const std::vector<double>* radii = nullptr, uint32_t topk = 0);
 // center_codes (CentersFromKmers): the centres are k-mers of the exact table -- the one a FASTA
 // database is embedded from -- and travel to the GPU as residue codes (hs_query_codes: k bytes per
 // centre instead of 64 k); the hits are those of the embedded centres, bit for bit.
@@ -239,6 +243,14 @@ int DensityTree(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const ui
                 const double& hash_R, const uint32_t& min_pts, const std::string& output_file, const Planes& planes,
                 int device, std::string* err, bool tree = false, uint64_t* n_clusters = nullptr,
                 uint64_t* n_tree_edges = nullptr, uint32_t unknown_seed = 0, uint32_t centers_min_size = 0);
+// The k-nearest-neighbour graph within R of the same k-mers (hs_self_knn in include/hsearch.h; hclust2's test
+// sqrt(d2) <= R) as <output_file>hclust.knn.txt: one line per k-mer in input order, "<name> <degree>" and then, for its
+// min(topk, degree) nearest neighbours in ascending (distance, index), " <neighbour name> <distance>".  The degree is
+// the full number of neighbours within R; distances with 17 significant digits, so that they read back bit for bit.
+// It opens a handle and builds an index of its own.  Returns 0 or an hs_status with *err set.
+int KnnGraph(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
+             const double& hash_R, const uint32_t& topk, const std::string& output_file, const Planes& planes, int device,
+             std::string* err, uint64_t* n_edges = nullptr, uint32_t unknown_seed = 0);
 // centers_min_size != 0 (Components, Dbscan, DensityTree): beside the clusters file, ClusterCenters() of the labels just found.
 // From cluster labels to the `-c` / `--radii` inputs of motif_both_points, on the handle that holds the k-mers'
 // index: label [n] as hs_components / hs_dbscan return it (HS_NOISE or a value < n).  Per cluster of at least min_size

@@ -20,7 +20,10 @@
 // on that path.  --radii <file> (lines "<centre name> <radius>", any order, matched by name against the
 // centres): every centre is searched at its own radius (hs_query_radii); -T is then not needed, and ignored
 // with a notice if given; one GPU only.  --best-per-position 1: instead of the hits, one line per database k-mer
-// reached, "<kmer name> <centre> <dist>" with its nearest centre (hs_annotate), k-mers ascending.
+// reached, "<kmer name> <centre> <dist>" with its nearest centre (hs_annotate), k-mers ascending.  --topk N (1..64):
+// per centre only its N best hits, selected on the device (hs_query_topk): the usual lines, per centre at most N of
+// them, in ascending (distance, k-mer index); with points and FASTA databases, with --radii and -M; one GPU only, and
+// not with --best-per-position 1.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -69,6 +72,7 @@ const Opt kOpts[] = {
     {"planes-out", 'P', "write the planes (binary doubles a[L][K][d] then b[L][K])", false},
     {"ref-compat-eq-swap", 'Q', "FASTA database: exchange E and Q like the reference's ProteinDB [0]", false},
     {"best-per-position", 'B', "one line per matched database k-mer (FASTA: window), its nearest centre (kmer_search) [0]", false},
+    {"topk", 't', "per centre only its N best hits, 1..64, in ascending (distance, k-mer index) (one GPU) [off: all hits]", false},
 };
 
 // A points file has a line of numbers after its first name line; a FASTA file has residue letters.
@@ -144,6 +148,25 @@ int main(int argc, const char* argv[]) {
     return EXIT_FAILURE;
   }
   if (with_radii && val.count("threshold")) fprintf(stderr, "--radii given: -T is ignored\n");
+  uint32_t topk = 0;  // 0: all hits
+  if (val.count("topk")) {
+    char* end = nullptr;
+    const unsigned long long t = strtoull(val["topk"].c_str(), &end, 10);
+    if (end == val["topk"].c_str() || *end || t < 1 || t > 64 || val["topk"][0] == '-') {
+      fprintf(stderr, "ERROR: --topk must be a whole number 1..64, not '%s'\n", val["topk"].c_str());
+      return EXIT_FAILURE;
+    }
+    topk = (uint32_t)t;
+    if (val.count("gpus") && atoi(val["gpus"].c_str()) > 1) {
+      fprintf(stderr, "ERROR: --topk runs on one GPU: it cannot be combined with --gpus %s\n", val["gpus"].c_str());
+      return EXIT_FAILURE;
+    }
+    if (val.count("best-per-position") && atoi(val["best-per-position"].c_str()) != 0) {
+      fprintf(stderr, "ERROR: --topk cannot be combined with --best-per-position %s: an annotation has one line per "
+                      "k-mer\n", val["best-per-position"].c_str());
+      return EXIT_FAILURE;
+    }
+  }
   const uint32_t kmer_length = (uint32_t)strtoul(val["len"].c_str(), nullptr, 10);
   const uint32_t hash_K = val.count("hash_K") ? (uint32_t)strtoul(val["hash_K"].c_str(), nullptr, 10) : 4;
   const uint32_t hash_L = val.count("hash_L") ? (uint32_t)strtoul(val["hash_L"].c_str(), nullptr, 10) : 4;
@@ -218,7 +241,7 @@ int main(int argc, const char* argv[]) {
     } else {
       planes = hsearch::DrawPlanes(dim, hash_K, hash_L, hash_W, seed);
     }
-    const bool use_comm = val.count("gpus") != 0 && !with_radii;  // (--radii --gpus 1: the one-GPU path)
+    const bool use_comm = val.count("gpus") != 0 && !with_radii && !topk;  // (--radii / --topk --gpus 1: the one-GPU path)
     const int n_gpus = use_comm ? atoi(val["gpus"].c_str()) : 1;
     if (n_gpus < 1 || n_gpus > 64) {
       fprintf(stderr, "ERROR: --gpus must be 1..64\n");
@@ -277,11 +300,11 @@ int main(int argc, const char* argv[]) {
                                                   // table: they go to the GPU as codes (hs_query_codes)
                                                   center_codes.empty() || val.count("centers-as-points")
                                                       ? nullptr : &center_codes,
-                                                  with_radii ? &radii : nullptr)
+                                                  with_radii ? &radii : nullptr, topk)
                  : hsearch::SearchSharded(kmers, centers, kmer_names, center_names, hash_K, hash_L, hash_W,
                                           hash_R, val["output"], planes, devices, use_comm, &err,
                                           &table_sizes, (uint32_t)probes, with_radii ? &radii : nullptr,
-                                          best_per_position);
+                                          best_per_position, topk);
     if (fasta_db && st == 0) std::cout << "number of kmers " << n_windows << std::endl;
     if (st != 0) {
       fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), st);

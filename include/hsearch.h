@@ -742,6 +742,73 @@ HS_API hs_status hs_density_tree_edges(const uint32_t* ei, const uint32_t* ej, c
 HS_API hs_status hs_density_tree_cut(const uint32_t* lo, const uint32_t* hi, const double* w, uint64_t m,
                                      const double* core, uint64_t n, double r, uint32_t* label, uint64_t* n_clusters);
 
+/* ---- the topk best hits per query, and the k-nearest-neighbour graph --------------------------------------- */
+
+/* "The N best matches" of every query, selected on the device: the hit list never crosses PCIe and is never ordered
+ * as a whole.
+ *
+ * The rule.  Let H be the hit list of the UNDERLYING CALL on the same handle (named per entry point below).  For a
+ * query q, N(q) is the set of hits of H with hit_q == q (each id occurs once).  Row q of the result is the
+ * min(topk, |N(q)|) hits of N(q) that are smallest under (dist compared as doubles, id), in ascending order.  Each
+ * entry carries the id, the table of first sight exactly as H reports it, and the distance bit-identical to hit_dist.
+ * Unused entries of a row are id = 0xffffffff, table = 0xffffffff, dist = +inf (hs_bruteforce_topk's padding).
+ * nn_count[q] = |N(q)|: the FULL hit count, which may exceed topk; the counts sum to the underlying call's *n_hits,
+ * which is what *n_hits / *n_edges receive.  Ids within a query are distinct and no distance is a NaN or negative, so
+ * the order is strict and total and the result is a pure function of the index and the arguments: batch sizes, filter
+ * paths, options and scheduling do not show in it.  1 <= topk <= HS_TOPK_MAX (one entry per lane of a wave); anything
+ * else is HS_ERR_INVALID.
+ *
+ * All outputs have fixed shapes -- nn_id, nn_table, nn_dist [rows][topk], nn_count [rows] -- and there is no capacity
+ * protocol.  nn_table may be NULL everywhere.
+ *
+ * hs_query_topk: rows = nq.  Exactly one of centers [nq][d] / qcodes [nq][k] is non-NULL; radii == NULL: every query at
+ * R; else radii [nq] and R is ignored (as in hs_annotate).  The underlying call is hs_query / hs_query_codes /
+ * hs_query_radii: the handle's multi-probe setting and bucket partition apply as they do there, and recognised k-mer
+ * centres and codes give the same bits as points.  Errors are as in the underlying call (a NaN R or radius -- for the
+ * _dev form detected on the device --, an unbuilt index, nq >= 2^27) and are reported before any output is written; a
+ * query code outside the alphabet is found by the search itself: the host form writes nothing then, the _dev form
+ * may have written the rows of earlier batches.
+ *
+ * hs_self_knn / hs_self_knn_range: the k-nearest-neighbour graph within R.  rows = n, or count with row t = k-mer
+ * first + t.  The underlying call is hs_self_join / hs_self_join_range (multi-probe and partition are ignored, as
+ * there).  Two identities follow: nn_count == hs_degrees, and for 2 <= m <= topk + 1 nn_dist[i][m - 2] is bit for bit
+ * hs_core_distance(h, R, sqrt_test, m)[i] (+inf where the degree is below m - 1).  The shares of a partition of
+ * 0 .. n-1 into ranges concatenate to the whole.
+ *
+ * Every batch's hits are selected where they lie (all hits of one query lie in one batch); the scratch is sized by a
+ * batch, never by n.  Every other entry point launches what it launched. */
+#define HS_TOPK_MAX 64u
+HS_API hs_status hs_query_topk(hs_handle* h, const double* centers, const uint8_t* qcodes, uint64_t nq, double R,
+                               const double* radii, uint32_t topk, uint32_t* nn_id, uint32_t* nn_table, double* nn_dist,
+                               uint32_t* nn_count, uint64_t* n_hits);
+/* ... every pointer but n_hits in device memory (streams: as hs_query_dev) */
+HS_API hs_status hs_query_topk_dev(hs_handle* h, const double* d_centers, const uint8_t* d_qcodes, uint64_t nq, double R,
+                                   const double* d_radii, uint32_t topk, uint32_t* d_nn_id, uint32_t* d_nn_table,
+                                   double* d_nn_dist, uint32_t* d_nn_count, uint64_t* n_hits);
+HS_API hs_status hs_self_knn(hs_handle* h, double R, int sqrt_test, uint32_t topk, uint32_t* nn_id, uint32_t* nn_table,
+                             double* nn_dist, uint32_t* nn_count, uint64_t* n_edges);
+HS_API hs_status hs_self_knn_range(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test,
+                                   uint32_t topk, uint32_t* nn_id, uint32_t* nn_table, double* nn_dist,
+                                   uint32_t* nn_count, uint64_t* n_edges);
+HS_API hs_status hs_self_knn_dev(hs_handle* h, double R, int sqrt_test, uint32_t topk, uint32_t* d_nn_id,
+                                 uint32_t* d_nn_table, double* d_nn_dist, uint32_t* d_nn_count, uint64_t* n_edges);
+HS_API hs_status hs_self_knn_range_dev(hs_handle* h, uint64_t first, uint64_t count, double R, int sqrt_test,
+                                       uint32_t topk, uint32_t* d_nn_id, uint32_t* d_nn_table, double* d_nn_dist,
+                                       uint32_t* d_nn_count, uint64_t* n_edges);
+/* The same rule on the host (no GPU, no handle) for ANY concatenation of n_tuples (q, id, table, dist) in any order --
+ * a raw hit list, the rows of the parts of a bucket or table partition, several ranks' rows (flattened, with q the
+ * row number): rows [nq][topk] and nn_count [nq] as above.  Tuples whose id is 0xffffffff are skipped, so padded rows
+ * can be fed back in.  Several tuples with one (q, id) count once and keep the smallest table.  Two tuples of one
+ * (q, id) with different distance bits, q >= nq, a NaN or negative distance and a topk out of range are
+ * HS_ERR_INVALID, reported before anything is written.  -0.0 is read as +0.0.  nn_count[q] is the number of DISTINCT
+ * ids given for q: over raw hit lists that is the hit count; over rows that were already cut at topk it is only a
+ * LOWER BOUND of it.  The top-k of a union is the top-k of the union of the parts' top-k rows, so merging rows
+ * selected with the same topk loses nothing.  table may be NULL: every tuple then carries table 0xffffffff, and that
+ * is what nn_table (which may be NULL too, independently) receives.  Outputs must not overlap inputs. */
+HS_API hs_status hs_topk_merge(const uint32_t* q, const uint32_t* id, const uint32_t* table, const double* dist,
+                               uint64_t n_tuples, uint64_t nq, uint32_t topk, uint32_t* nn_id, uint32_t* nn_table,
+                               double* nn_dist, uint32_t* nn_count);
+
 /* ---- cluster profiles, centroids and covering radii from a label array ------------------------------------ */
 
 /* The step from cluster labels to what a search takes: per cluster its members' position frequency matrix, their
