@@ -30,7 +30,8 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_cluster_summary_codes", "hs_msf", "hs_msf_dev", "hs_msf_edges", "hs_msf_cut", "hs_core_distance",
            "hs_core_distance_dev", "hs_density_tree", "hs_density_tree_dev", "hs_density_tree_edges",
            "hs_density_tree_cut", "hs_query_topk", "hs_query_topk_dev", "hs_self_knn", "hs_self_knn_range",
-           "hs_self_knn_dev", "hs_self_knn_range_dev", "hs_topk_merge"]
+           "hs_self_knn_dev", "hs_self_knn_range_dev", "hs_topk_merge", "hs_seq_match", "hs_seq_match_dev",
+           "hs_window_id_start", "hs_seq_match_hits", "hs_seq_match_merge"]
 
 TOPK_MAX = 64        # HS_TOPK_MAX: the widest row of query_topk / self_knn / topk_merge
 NO_ID = 0xffffffff   # the id and table of an unused entry of such a row (its distance is +inf)
@@ -237,6 +238,24 @@ def load(hooks=False):
             lib.hs_topk_merge.restype = C.c_int
             lib.hs_topk_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                           C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        # seq_match (h, centers, qcodes, nq, R, radii, q_group, n_groups, q_off, id_start, n_seq, the nine row arrays, cap,
+        # n_out, n_hits); seq_match_hits (q, id, dist, n_tuples, nq, q_group, n_groups, q_off, id_start, n_seq, rows, cap,
+        # n_out); seq_match_merge (the nine arrays in, n_rows, the nine out, cap, n_out)
+        if hasattr(lib, "hs_seq_match"):
+            rows = [C.c_void_p] * 9
+            for fn in (lib.hs_seq_match, lib.hs_seq_match_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_void_p,
+                               C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64] + rows + [
+                                   C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+            lib.hs_window_id_start.restype = C.c_int
+            lib.hs_window_id_start.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
+            lib.hs_seq_match_hits.restype = C.c_int
+            lib.hs_seq_match_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                              C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64] + rows + [
+                                                  C.c_uint64, C.POINTER(C.c_uint64)]
+            lib.hs_seq_match_merge.restype = C.c_int
+            lib.hs_seq_match_merge.argtypes = rows + [C.c_uint64] + rows + [C.c_uint64, C.POINTER(C.c_uint64)]
         _libs[hooks] = lib
     return _libs[hooks]
 
@@ -334,6 +353,108 @@ def topk_merge(q, id, table, dist, nq, topk, out=None):
     if st != HS_OK:
         raise HsError(st, "hs_topk_merge")
     return out
+
+
+SEQ_MATCH_FIELDS = (("group", np.uint32), ("seq", np.uint32), ("diag", np.int32), ("count", np.uint32),
+                    ("best_dist", np.float64), ("best_q", np.uint32), ("best_id", np.uint32), ("lo", np.uint32),
+                    ("hi", np.uint32))
+
+
+def _seq_rows(cap):
+    return [np.empty(cap, dtype=t) for _, t in SEQ_MATCH_FIELDS]
+
+
+def _seq_dict(arrs, m):
+    return {name: a[:m] for (name, _), a in zip(SEQ_MATCH_FIELDS, arrs)}
+
+
+def _seq_keys(nq, q_group, n_groups, q_off, id_start):
+    """the three key arrays of seq_match as the library takes them, and (n_groups, n_seq)"""
+    if q_group is not None:
+        q_group = np.ascontiguousarray(q_group, dtype=np.uint32)
+        assert q_group.shape == (nq,) and n_groups is not None, "q_group [nq] comes with n_groups"
+    if q_off is not None:
+        q_off = np.ascontiguousarray(q_off, dtype=np.uint32)
+        assert q_off.shape == (nq,)
+    id_start = np.ascontiguousarray(id_start, dtype=np.uint64)
+    assert id_start.ndim == 1 and len(id_start) >= 1
+    return q_group, q_off, id_start, int(nq if n_groups is None else n_groups), len(id_start) - 1
+
+
+def window_id_start(seq_start, k):
+    """hs_window_id_start (host only): id_start [n_seq + 1] uint64 of an index built by Engine.index_build_windows over
+    seq_start at k-mer length k -- sequence s owns the window ids [id_start[s], id_start[s + 1])."""
+    seq_start = np.ascontiguousarray(seq_start, dtype=np.uint64)
+    assert seq_start.ndim == 1 and len(seq_start) >= 1
+    out = np.empty(len(seq_start), dtype=np.uint64)
+    st = load().hs_window_id_start(_vp(seq_start), len(seq_start) - 1, int(k), _vp(out))
+    if st != HS_OK:
+        raise HsError(st, "hs_window_id_start")
+    return out
+
+
+def protein_queries(residues, seq_start, k):
+    """Query proteins cut into windows on the host: residues uint8 codes, seq_start [n_prot + 1] ascending offsets ->
+    dict(qcodes [nq][k] uint8, q_group [nq] = the protein, q_off [nq] = the window's offset in it), windows numbered
+    protein-major as index_build_windows numbers a database's; proteins shorter than k contribute none.  What
+    Engine.seq_match takes with codes=True, n_groups = n_prot."""
+    residues = np.ascontiguousarray(residues, dtype=np.uint8)
+    seq_start = np.ascontiguousarray(seq_start, dtype=np.int64)
+    k = int(k)
+    lens = np.diff(seq_start)
+    nwin = np.maximum(lens - k + 1, 0)
+    q_group = np.repeat(np.arange(len(nwin), dtype=np.uint32), nwin)
+    first = np.concatenate([[0], np.cumsum(nwin)])[:-1]
+    q_off = (np.arange(int(nwin.sum()), dtype=np.int64) - np.repeat(first, nwin)).astype(np.uint32)
+    pos = np.repeat(seq_start[:-1], nwin) + q_off
+    qcodes = residues[pos[:, None] + np.arange(k)[None, :]] if len(pos) else np.empty((0, k), dtype=np.uint8)
+    return dict(qcodes=np.ascontiguousarray(qcodes, dtype=np.uint8), q_group=q_group, q_off=q_off)
+
+
+def seq_match_hits(q, id, dist, nq, id_start, q_group=None, n_groups=None, q_off=None, cap=None, out=None):
+    """hs_seq_match_hits (host only, no GPU): the rule of Engine.seq_match over ANY list of hits (q, id, dist) in any
+    order -- one row per distinct (group, sequence, diagonal): dict(group, seq, diag, count, best_dist, best_q, best_id,
+    lo, hi).  A (q, id) given twice counts once.  cap=None: as many rows as needed; a given cap that is too small
+    raises HsError(HS_ERR_CAPACITY) with the required size in .needed.  out: a list of the nine arrays to write into."""
+    q = np.ascontiguousarray(q, dtype=np.uint32).ravel()
+    id = np.ascontiguousarray(id, dtype=np.uint32).ravel()
+    dist = np.ascontiguousarray(dist, dtype=np.float64).ravel()
+    n = len(q)
+    assert id.shape == dist.shape == (n,)
+    q_group, q_off, id_start, n_groups, n_seq = _seq_keys(int(nq), q_group, n_groups, q_off, id_start)
+    room = n if cap is None else int(cap)
+    arrs = _seq_rows(room) if out is None else out
+    n_out = C.c_uint64(0)
+    st = load().hs_seq_match_hits(_vp(q), _vp(id), _vp(dist), n, int(nq), None if q_group is None else _vp(q_group),
+                                  n_groups, None if q_off is None else _vp(q_off), _vp(id_start), n_seq,
+                                  *[_vp(a) for a in arrs], room, C.byref(n_out))
+    if st != HS_OK:
+        e = HsError(st, "hs_seq_match_hits")
+        e.needed = int(n_out.value)
+        raise e
+    return _seq_dict(arrs, int(n_out.value))
+
+
+def seq_match_merge(rows, cap=None, out=None):
+    """hs_seq_match_merge (host only, no GPU): rows -- a dict as Engine.seq_match returns it, or a list of them that is
+    concatenated -- with equal (group, seq, diag) combined: counts add, best is the min, lo the min, hi the max.  Only
+    for parts whose hit lists are disjoint (query blocks, q and the groups made global first); parts that can report
+    one (q, id) twice go through seq_match_hits."""
+    if isinstance(rows, dict):
+        rows = [rows]
+    ins = [np.ascontiguousarray(np.concatenate([np.asarray(r[name], dtype=t) for r in rows]) if rows
+                                else np.empty(0, dtype=t), dtype=t) for name, t in SEQ_MATCH_FIELDS]
+    n = len(ins[0])
+    assert all(a.shape == (n,) for a in ins)
+    room = n if cap is None else int(cap)
+    arrs = _seq_rows(room) if out is None else out
+    n_out = C.c_uint64(0)
+    st = load().hs_seq_match_merge(*[_vp(a) for a in ins], n, *[_vp(a) for a in arrs], room, C.byref(n_out))
+    if st != HS_OK:
+        e = HsError(st, "hs_seq_match_merge")
+        e.needed = int(n_out.value)
+        raise e
+    return _seq_dict(arrs, int(n_out.value))
 
 
 def components_merge(labels, out=None):
@@ -989,6 +1110,57 @@ class Engine:
                                                 d_radii_ptr if d_radii_ptr else None, int(topk), d_id,
                                                 d_table if d_table else None, d_dist, d_count, C.byref(n)))
         return int(n.value)
+
+    def seq_match(self, queries, id_start, R=None, radii=None, codes=False, q_group=None, n_groups=None, q_off=None):
+        """hs_seq_match: the hits query() / query_codes() (R) or query_radii() (radii) would return, reduced on the
+        device per (query group, database sequence, diagonal): dict(group, seq, diag, count, best_dist, best_q, best_id,
+        lo, hi -- one row per distinct key, ascending --, n_hits).  id_start [n_seq + 1]: sequence s owns the ids
+        [id_start[s], id_start[s + 1]) (capi.window_id_start for a windows index).  q_group [nq] with n_groups (None:
+        every query its own group), q_off [nq] (None: no diagonals, diag = 0).  queries are points [nq][d], or with
+        codes=True residue codes [nq][k] (capi.protein_queries cuts proteins into them).  Two calls: the row count,
+        then the rows."""
+        queries = np.ascontiguousarray(queries, dtype=np.uint8 if codes else np.float64)
+        nq = queries.shape[0]
+        assert queries.shape == (nq, self.k if codes else self.d)
+        assert (R is None) != (radii is None), "exactly one of R and radii"
+        if radii is not None:
+            radii = np.ascontiguousarray(radii, dtype=np.float64)
+            assert radii.shape == (nq,)
+        q_group, q_off, id_start, n_groups, n_seq = _seq_keys(nq, q_group, n_groups, q_off, id_start)
+        cap = 0
+        while True:
+            arrs = _seq_rows(cap)
+            n, nh = C.c_uint64(0), C.c_uint64(0)
+            st = self._lib.hs_seq_match(self._h, None if codes else _vp(queries), _vp(queries) if codes else None, nq,
+                                        0.0 if R is None else float(R), None if radii is None else _vp(radii),
+                                        None if q_group is None else _vp(q_group), n_groups,
+                                        None if q_off is None else _vp(q_off), _vp(id_start), n_seq,
+                                        *[_vp(a) if cap else None for a in arrs], cap, C.byref(n), C.byref(nh))
+            if st == HS_ERR_CAPACITY and int(n.value) > cap:
+                cap = int(n.value)
+                continue
+            self._check(st)
+            res = _seq_dict(arrs, int(n.value))
+            res["n_hits"] = int(nh.value)
+            return res
+
+    def seq_match_dev(self, d_queries_ptr, nq, R, d_radii_ptr, d_q_group, n_groups, d_q_off, d_id_start, n_seq, d_rows,
+                      cap, codes=False):
+        """hs_seq_match_dev (device pointers as ints; d_radii_ptr / d_q_group / d_q_off None or 0: absent; d_rows: the
+        nine row arrays in the order of capi.SEQ_MATCH_FIELDS).  Returns (rows, n_hits); raises
+        HsError(HS_ERR_CAPACITY) with the required size in .needed when cap is too small."""
+        n, nh = C.c_uint64(0), C.c_uint64(0)
+        st = self._lib.hs_seq_match_dev(self._h, None if codes else d_queries_ptr, d_queries_ptr if codes else None,
+                                        nq, float(R), d_radii_ptr if d_radii_ptr else None,
+                                        d_q_group if d_q_group else None, int(n_groups), d_q_off if d_q_off else None,
+                                        d_id_start, int(n_seq), *[p if p else None for p in d_rows], cap, C.byref(n),
+                                        C.byref(nh))
+        if st == HS_ERR_CAPACITY:
+            e = HsError(st, self._lib.hs_last_error(self._h).decode())
+            e.needed = int(n.value)
+            raise e
+        self._check(st)
+        return int(n.value), int(nh.value)
 
     def merge_first_table_dev(self, d_q, d_id, d_table, d_dist, n):
         """hs_merge_first_table_dev (device pointers as ints; in place): the number of tuples kept."""

@@ -122,9 +122,19 @@ struct Knobs {
 //   DT_MIN_D, DT_MIN_PAIR     hs_density_tree: steps 1 and 2 of a Boruvka round under the mutual-reachability weight
 //   TOPK       hs_query_topk / hs_self_knn (hs_knn.hip): per query of the batch the topk smallest hits under (dist, id),
 //              written as rows row0 + (the query's number in the call) of the four device arrays (topk_reduce)
+//   SEQ_MATCH  hs_seq_match (hs_seqmatch.hip): the batch's hits reduced per (query group, sequence, diagonal) and the
+//              rows appended to the handle's list (seq_reduce); the list is reduced once more at the end of the call
+struct SeqMatchCall {
+  const uint32_t* q_group = nullptr;  // device; null: a query is its own group
+  const uint32_t* q_off = nullptr;    // device; null: no diagonals
+  const uint64_t* id_start = nullptr; // device, [n_seq + 1]
+  uint64_t n_groups = 0, n_seq = 0, max_qoff = 0;
+  int wg = 0, ws = 0, wd = 0;         // the key's field widths (include/hsearch.h)
+};
+
 struct HitSink {
   enum Kind { LIST, ANNOTATE, CC_UNION, DB_DEGREE, DB_UNITE, MSF_MIN_D, MSF_MIN_PAIR, MSF_COLLECT, DT_CORE,
-              DT_CORE_COLLECT, DT_MIN_D, DT_MIN_PAIR, TOPK } kind = LIST;
+              DT_CORE_COLLECT, DT_MIN_D, DT_MIN_PAIR, TOPK, SEQ_MATCH } kind = LIST;
   uint32_t min_pts = 1;
   uint32_t topk = 0;
   uint64_t row0 = 0;
@@ -132,6 +142,7 @@ struct HitSink {
   uint32_t* nn_table = nullptr;  // (may stay null)
   double* nn_dist = nullptr;
   uint32_t* nn_count = nullptr;
+  const SeqMatchCall* sm = nullptr;
 };
 
 // One query call's queries and what it asks (run_query, query_batch, probe_tabs)
@@ -250,6 +261,12 @@ struct hs_handle {
   // hs_query_topk / hs_self_knn (hs_knn.hip: the scratch listed at its head, all sized by a batch): hits per query,
   // their scan, the scatter's cursors, the call's 64-bit hit count; the counts of a host-pointer call on their way out
   DevBuf knn_cnt, knn_off, knn_cur, knn_total, knn_io_count;
+  // hs_seq_match (hs_seqmatch.hip: the scratch listed at its head): a batch's keys and hit indices, their sorted
+  // copies, the run heads and their scan, the waves' cut runs; the call's rows so far (sq_rows of them in a list of
+  // sq_acc.cap / 40) and their final reduction; the argument check's words; a host-pointer call's arrays in and out
+  DevBuf sq_key, sq_idx, sq_skey, sq_sidx, sq_head, sq_excl, sq_part, sq_acc, sq_fin, sq_chk, sq_in, sq_out;
+  uint64_t sq_rows = 0;
+  uint32_t sq_batches = 0;
   // hs_cluster_profile / hs_cluster_radii (hs_summary.hip: the state listed at its head), the counts of a row batch
   // when the caller wants none, and the arrays of a host-pointer call on their way in and out
   DevBuf sm_size, sm_tmp, sm_row_of, sm_off_of, sm_row_label, sm_row_off, sm_member, sm_d2, sm_err, sm_counts;
@@ -872,6 +889,8 @@ void hs_destroy(hs_handle* h) {
                     &h->db_deg, &h->db_anchor, &h->db_cnt, &h->msf_comp, &h->msf_best_d, &h->msf_best_pair,
                     &h->msf_out_pair, &h->msf_out_d, &h->msf_s_pair, &h->msf_s_d, &h->msf_cnt, &h->msf_kept, &h->dt_core, &h->dt_thr,
                     &h->dt_next, &h->dt_cnt, &h->knn_cnt, &h->knn_off, &h->knn_cur, &h->knn_total, &h->knn_io_count,
+                    &h->sq_key, &h->sq_idx, &h->sq_skey, &h->sq_sidx, &h->sq_head, &h->sq_excl, &h->sq_part, &h->sq_acc,
+                    &h->sq_fin, &h->sq_chk, &h->sq_in, &h->sq_out,
                     &h->sm_size, &h->sm_tmp, &h->sm_row_of, &h->sm_off_of,
                     &h->sm_row_label, &h->sm_row_off, &h->sm_member, &h->sm_d2, &h->sm_err, &h->sm_counts,
                     &h->sm_io_label, &h->sm_io_a, &h->sm_io_b, &h->sm_io_counts, &h->sm_io_f64, &h->sm_io_f64b};
@@ -3076,6 +3095,70 @@ static hs_status topk_reduce(hs_handle* h, const QueryCall& c, const uint64_t* d
   return HS_OK;
 }
 
+// hs_seqmatch.hip's passes over n sorted-to-be elements whose keys are in sq_key and indices in sq_idx: sort, run heads,
+// scan, the number of runs read back, then the runs reduced into rows row0 ... of the list `dst` (grown to hold them;
+// keep: its first row0 rows stay).  The source is a batch's hits (the five arrays) or the rows of `src`.
+static hs_status seq_rows_reduce(hs_handle* h, const SeqMatchCall& sm, uint32_t n, const uint64_t* d_key,
+                                 const uint64_t* d_val, const uint32_t* d_q, const uint32_t* d_id, const double* d_dist,
+                                 const DevBuf* src, DevBuf* dst, uint64_t row0, uint32_t* n_rows) {
+  HS_HIP(h, h->sq_skey.reserve((size_t)n * 8));
+  HS_HIP(h, h->sq_sidx.reserve((size_t)n * 4));
+  HS_HIP(h, h->sq_head.reserve(((size_t)n + 1) * 4));
+  HS_HIP(h, h->sq_excl.reserve(((size_t)n + 1) * 4));
+  HS_HIP(h, h->sq_part.reserve(hs_sm_part_bytes(n)));
+  HS_HIP(h, h->temp.reserve(std::max(hs_sort_pairs_u64_u32_temp(n), hs_scan_u32_temp((size_t)n + 1)) + 256));
+  HS_HIP(h, hs_sort_pairs_u64_u32(h->temp.p, h->temp.cap, h->sq_key.as<uint64_t>(), h->sq_skey.as<uint64_t>(),
+                                  h->sq_idx.as<uint32_t>(), h->sq_sidx.as<uint32_t>(), n, 0,
+                                  std::max(1, sm.wg + sm.ws + sm.wd), h->stream));
+  HS_HIP(h, hs_launch_sm_head(h->sq_skey.as<uint64_t>(), n, h->sq_head.as<uint32_t>(), h->stream));
+  HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, h->sq_head.as<uint32_t>(), h->sq_excl.as<uint32_t>(),
+                                  (size_t)n + 1, h->stream));
+  uint32_t rows = 0;
+  HS_HIP(h, hipMemcpyAsync(&rows, h->sq_excl.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  if (!rows || rows > n) return fail(h, HS_ERR_HIP, "hs_seq_match: the run count of a batch is out of range");
+  const uint64_t have = dst->cap / 40, need = row0 + rows;
+  if (need > have) {  // by doubling; the rows kept move to the new list's arrays
+    DevBuf bigger;
+    const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(need, 2 * have), 1024);
+    HS_HIP(h, bigger.reserve((size_t)cap * 40));
+    hipError_t e = hipSuccess;
+    static const int at[6] = {0, 8, 16, 24, 32, 36}, width[6] = {8, 8, 8, 8, 4, 4};
+    for (int a = 0; a < 6 && row0 && e == hipSuccess; ++a)
+      e = hipMemcpyAsync(static_cast<char*>(bigger.p) + cap * at[a], static_cast<char*>(dst->p) + have * at[a],
+                         (size_t)row0 * width[a], hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) bigger.release();  // (DevBuf has no destructor)
+    HS_HIP(h, e);
+    dst->release();
+    *dst = bigger;
+  }
+  HS_HIP(h, hs_launch_sm_reduce(h->sq_skey.as<uint64_t>(), h->sq_sidx.as<uint32_t>(), h->sq_excl.as<uint32_t>(),
+                                h->sq_head.as<uint32_t>(), n, d_key, d_val, d_q, d_id, d_dist, sm.id_start, sm.ws, sm.wd,
+                                src ? src->p : nullptr, src ? src->cap / 40 : 0, dst->p, dst->cap / 40, row0, rows,
+                                h->sq_part.p, h->stream));
+  *n_rows = rows;
+  return HS_OK;
+}
+
+// hs_seq_match: n hits -- a batch's (key, value) pairs, or with d_key == null the arrays of a merged list -- reduced to
+// rows and appended to the call's list (seq_begin has emptied it), on the handle's stream
+static hs_status seq_reduce(hs_handle* h, const QueryCall& c, const uint64_t* d_key, const uint64_t* d_val,
+                            const uint32_t* d_q, const uint32_t* d_id, const double* d_dist, uint64_t n) {
+  if (!n) return HS_OK;
+  if (n >= (1ull << 32)) return fail(h, HS_ERR_CAPACITY, "more than 2^32 - 1 hits in one batch");
+  const SeqMatchCall& sm = *c.sink.sm;
+  HS_HIP(h, h->sq_key.reserve((size_t)n * 8));
+  HS_HIP(h, h->sq_idx.reserve((size_t)n * 4));
+  HS_HIP(h, hs_launch_sm_key(d_key, d_val, d_q, d_id, d_dist, (uint32_t)n, sm.q_group, sm.q_off, sm.id_start, sm.n_seq,
+                             sm.ws, sm.wd, sm.max_qoff, h->sq_key.as<uint64_t>(), h->sq_idx.as<uint32_t>(), h->stream));
+  uint32_t rows = 0;
+  HS_CHECK(seq_rows_reduce(h, sm, (uint32_t)n, d_key, d_val, d_q, d_id, d_dist, nullptr, &h->sq_acc, h->sq_rows, &rows));
+  h->sq_rows += rows;
+  ++h->sq_batches;
+  return HS_OK;
+}
+
 // first, count: the batch's queries within the call (for a self-join the k-mers c.self_first + first ...)
 static hs_status reduce_batch(hs_handle* h, const QueryCall& c, uint32_t nh, uint32_t first, uint32_t count) {
   const uint64_t* const pairs = h->hit_key.as<uint64_t>();
@@ -3124,6 +3207,8 @@ static hs_status reduce_batch(hs_handle* h, const QueryCall& c, uint32_t nh, uin
       break;
     case HitSink::TOPK:
       return topk_reduce(h, c, pairs, h->hit_val.as<uint64_t>(), nullptr, nullptr, nullptr, nullptr, nh, first, count);
+    case HitSink::SEQ_MATCH:
+      return seq_reduce(h, c, pairs, h->hit_val.as<uint64_t>(), nullptr, nullptr, nullptr, nh);
   }
   return HS_OK;
 }
@@ -3388,6 +3473,9 @@ static hs_status mp_query(hs_handle* h, const QueryCall& c, uint64_t nq, uint32_
     } else if (c.sink.kind == HitSink::TOPK) {  // ... and selected: the chunk is a range of queries, its list whole
       HS_CHECK(topk_reduce(h, c, nullptr, nullptr, h->mp_q.as<uint32_t>(), h->mp_id.as<uint32_t>(),
                            h->mp_table.as<uint32_t>(), h->mp_dist.as<double>(), kept, (uint32_t)q0, (uint32_t)nc));
+    } else if (c.sink.kind == HitSink::SEQ_MATCH) {  // ... and reduced to rows: one (q, id) once, as a batch brings it
+      HS_CHECK(seq_reduce(h, c, nullptr, nullptr, h->mp_q.as<uint32_t>(), h->mp_id.as<uint32_t>(),
+                          h->mp_dist.as<double>(), kept));
     } else if (kept && total + kept <= cap) {
       HS_HIP(h, hipMemcpyAsync(d_hit_q + total, h->mp_q.p, kept * 4, hipMemcpyDeviceToDevice, h->stream));
       HS_HIP(h, hipMemcpyAsync(d_hit_id + total, h->mp_id.p, kept * 4, hipMemcpyDeviceToDevice, h->stream));
@@ -4317,6 +4405,160 @@ hs_status hs_query_topk(hs_handle* h, const double* centers, const uint8_t* qcod
   HS_CHECK(topk_search(h, call, nq, topk, h->io_id.as<uint32_t>(), nn_table ? h->io_table.as<uint32_t>() : nullptr,
                        h->io_dist.as<double>(), h->knn_io_count.as<uint32_t>(), n_hits));
   return topk_copy_out(h, nq, topk, nn_id, nn_table, nn_dist, nn_count);
+}
+
+// ---- hs_seq_match: hits per (query group, sequence, diagonal) (kernels, the rule and the passes: hs_seqmatch.hip) ----
+struct SeqMatchOut {
+  uint32_t *group, *seq;
+  int32_t* diag;
+  uint32_t* count;
+  double* best_dist;
+  uint32_t *best_q, *best_id, *lo, *hi;
+  bool all() const { return group && seq && diag && count && best_dist && best_q && best_id && lo && hi; }
+};
+
+// The whole call on device pointers.  Everything that can be refused from the arguments is refused before the first
+// kernel writes: the underlying call's checks, then one small reduction over q_group / q_off / id_start and one
+// read-back.  The rows go to `out` where they fit cap.
+static hs_status seq_match_run(hs_handle* h, QueryCall call, uint64_t nq, SeqMatchCall sm, const SeqMatchOut& out,
+                               uint64_t cap, uint64_t* n_out, uint64_t* n_hits) {
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
+  if (nq >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nq must be < 2^27 per call");
+  if (!(call.R == call.R)) return fail(h, HS_ERR_INVALID, "R is NaN");
+  if (!sm.id_start) return fail(h, HS_ERR_INVALID, "hs_seq_match: id_start is null");
+  if (!sm.q_group && sm.n_groups != nq)
+    return fail(h, HS_ERR_INVALID, "hs_seq_match: without q_group n_groups must equal nq");
+  if (sm.n_groups > (1ull << 32) || sm.n_seq > (1ull << 32))
+    return fail(h, HS_ERR_INVALID, "hs_seq_match: more than 2^32 groups or sequences");
+  uint64_t chk[3] = {0, 0, 0};
+  HS_HIP(h, h->sq_chk.reserve(32));
+  HS_HIP(h, hipMemsetAsync(h->sq_chk.p, 0, 32, h->stream));
+  HS_HIP(h, hs_launch_sm_check(sm.q_group, sm.q_off, nq, sm.n_groups, sm.id_start, sm.n_seq, h->n,
+                               h->sq_chk.as<uint64_t>(), h->stream));
+  HS_HIP(h, hipMemcpyAsync(chk, h->sq_chk.p, 24, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  if (chk[0] & 7) return fail(h, HS_ERR_INVALID, "hs_seq_match: id_start must ascend from 0 to the index's k-mers");
+  if (chk[0] & 8) return fail(h, HS_ERR_INVALID, "hs_seq_match: a q_group entry is >= n_groups");
+  sm.max_qoff = chk[1];
+  if (!hs_sm_widths(sm.n_groups, sm.n_seq, chk[2], sm.max_qoff, &sm.wg, &sm.ws, &sm.wd))
+    return fail(h, HS_ERR_INVALID, "hs_seq_match: group, sequence and diagonal need more than 64 key bits");
+  h->sq_rows = 0;
+  h->sq_batches = 0;
+  call.sink.kind = HitSink::SEQ_MATCH;
+  call.sink.sm = &sm;
+  HS_CHECK(run_query(h, call, nq, nullptr, nullptr, nullptr, nullptr, 0, n_hits, nullptr));
+  const hs_profile prof = h->prof;
+  const DevBuf* rows = &h->sq_acc;
+  uint64_t n_rows = h->sq_rows;
+  if (h->sq_batches > 1) {  // a row's hits may lie in several batches: the batches' rows reduced once more
+    if (n_rows >= (1ull << 32)) return fail(h, HS_ERR_CAPACITY, "hs_seq_match: more than 2^32 - 1 rows before the merge");
+    HS_HIP(h, h->sq_idx.reserve((size_t)n_rows * 4));
+    HS_HIP(h, h->sq_key.reserve((size_t)n_rows * 8));
+    HS_HIP(h, hipMemcpyAsync(h->sq_key.p, h->sq_acc.p, (size_t)n_rows * 8, hipMemcpyDeviceToDevice, h->stream));
+    HS_HIP(h, hs_launch_sm_iota((uint32_t)n_rows, h->sq_idx.as<uint32_t>(), h->stream));
+    uint32_t merged = 0;
+    HS_CHECK(seq_rows_reduce(h, sm, (uint32_t)n_rows, nullptr, nullptr, nullptr, nullptr, nullptr, &h->sq_acc, &h->sq_fin,
+                             0, &merged));
+    rows = &h->sq_fin;
+    n_rows = merged;
+  }
+  h->prof = prof;
+  *n_out = n_rows;
+  if (n_rows > cap) return fail(h, HS_ERR_CAPACITY, "row buffers too small; see *n_out");
+  uint32_t flag = 0;
+  HS_HIP(h, hipMemsetAsync(h->sq_chk.p, 0, 4, h->stream));
+  HS_HIP(h, hs_launch_sm_decode(rows->p, rows->cap / 40, (uint32_t)n_rows, sm.ws, sm.wd, sm.max_qoff, out.group, out.seq,
+                                out.diag, out.count, out.best_dist, out.best_q, out.best_id, out.lo, out.hi,
+                                h->sq_chk.as<uint32_t>(), h->stream));
+  HS_HIP(h, hipMemcpyAsync(&flag, h->sq_chk.p, 4, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  if (flag) return fail(h, HS_ERR_CAPACITY, "hs_seq_match: a row counts more than 2^32 - 1 hits");
+  return HS_OK;
+}
+
+static hs_status seq_match_args(hs_handle* h, const void* centers, const void* qcodes, const SeqMatchOut& out,
+                                uint64_t cap, uint64_t* n_out, uint64_t* n_hits) {
+  if (!h || !n_out || !n_hits) return HS_ERR_INVALID;
+  *n_out = 0;
+  *n_hits = 0;
+  if ((centers != nullptr) == (qcodes != nullptr))
+    return fail(h, HS_ERR_INVALID, "hs_seq_match: exactly one of centers and qcodes must be given");
+  if (cap && !out.all()) return HS_ERR_INVALID;
+  return HS_OK;
+}
+
+hs_status hs_seq_match_dev(hs_handle* h, const double* d_centers, const uint8_t* d_qcodes, uint64_t nq, double R,
+                           const double* d_radii, const uint32_t* d_q_group, uint64_t n_groups, const uint32_t* d_q_off,
+                           const uint64_t* d_id_start, uint64_t n_seq, uint32_t* d_out_group, uint32_t* d_out_seq,
+                           int32_t* d_out_diag, uint32_t* d_out_count, double* d_out_best_dist, uint32_t* d_out_best_q,
+                           uint32_t* d_out_best_id, uint32_t* d_out_lo, uint32_t* d_out_hi, uint64_t cap, uint64_t* n_out,
+                           uint64_t* n_hits) {
+  const SeqMatchOut out{d_out_group, d_out_seq, d_out_diag, d_out_count, d_out_best_dist,
+                        d_out_best_q, d_out_best_id, d_out_lo, d_out_hi};
+  HS_CHECK(seq_match_args(h, d_centers, d_qcodes, out, cap, n_out, n_hits));
+  HS_CHECK(ensure_device(h));
+  QueryCall call{d_centers, d_qcodes, d_radii ? 0.0 : R};
+  if (d_radii && nq && nq < (1ull << 27)) HS_CHECK(radii_max_dev(h, d_radii, nq, &call.R));
+  call.radii = nq ? d_radii : nullptr;
+  SeqMatchCall sm;
+  sm.q_group = d_q_group;
+  sm.q_off = d_q_off;
+  sm.id_start = d_id_start;
+  sm.n_groups = n_groups;
+  sm.n_seq = n_seq;
+  return seq_match_run(h, call, nq, sm, out, cap, n_out, n_hits);
+}
+
+hs_status hs_seq_match(hs_handle* h, const double* centers, const uint8_t* qcodes, uint64_t nq, double R,
+                       const double* radii, const uint32_t* q_group, uint64_t n_groups, const uint32_t* q_off,
+                       const uint64_t* id_start, uint64_t n_seq, uint32_t* out_group, uint32_t* out_seq,
+                       int32_t* out_diag, uint32_t* out_count, double* out_best_dist, uint32_t* out_best_q,
+                       uint32_t* out_best_id, uint32_t* out_lo, uint32_t* out_hi, uint64_t cap, uint64_t* n_out,
+                       uint64_t* n_hits) {
+  const SeqMatchOut out{out_group, out_seq, out_diag, out_count, out_best_dist, out_best_q, out_best_id, out_lo, out_hi};
+  HS_CHECK(seq_match_args(h, centers, qcodes, out, cap, n_out, n_hits));
+  if (nq >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nq must be < 2^27 per call");
+  if (radii && !radii_max_host(radii, nq, &R)) return fail(h, HS_ERR_INVALID, "a radius is NaN");
+  if (!id_start) return fail(h, HS_ERR_INVALID, "hs_seq_match: id_start is null");
+  if (n_seq > (1ull << 32)) return fail(h, HS_ERR_INVALID, "hs_seq_match: more than 2^32 groups or sequences");
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
+  HS_CHECK(ensure_device(h));
+  QueryCall call{nullptr, nullptr, R};
+  HS_CHECK(stage_queries(h, centers, qcodes, nq ? radii : nullptr, nq, &call));
+  // q_group, q_off and id_start follow the queries to the device (4 + 4 bytes per query, 8 per sequence)
+  const size_t gb = ((size_t)nq * 4 + 15) & ~(size_t)15, sb = ((size_t)n_seq + 1) * 8;
+  HS_HIP(h, h->sq_in.reserve(sb + 2 * gb + 16));
+  char* const in = h->sq_in.as<char>();
+  HS_HIP(h, hipMemcpyAsync(in, id_start, sb, hipMemcpyHostToDevice, h->stream));
+  if (q_group && nq) HS_HIP(h, hipMemcpyAsync(in + sb, q_group, (size_t)nq * 4, hipMemcpyHostToDevice, h->stream));
+  if (q_off && nq) HS_HIP(h, hipMemcpyAsync(in + sb + gb, q_off, (size_t)nq * 4, hipMemcpyHostToDevice, h->stream));
+  SeqMatchCall sm;
+  sm.id_start = reinterpret_cast<const uint64_t*>(in);
+  sm.q_group = q_group ? reinterpret_cast<const uint32_t*>(in + sb) : nullptr;
+  sm.q_off = q_off ? reinterpret_cast<const uint32_t*>(in + sb + gb) : nullptr;
+  sm.n_groups = n_groups;
+  sm.n_seq = n_seq;
+  // the rows are staged on the device at the caller's capacity: 40 bytes per row cross PCIe, never the hits
+  HS_HIP(h, h->sq_out.reserve(std::max<size_t>(64, (size_t)cap * 40)));
+  char* const o = h->sq_out.as<char>();
+  uint32_t* const w = reinterpret_cast<uint32_t*>(o + cap * 8);
+  const SeqMatchOut dev{w, w + cap, reinterpret_cast<int32_t*>(w + 2 * cap), w + 3 * cap, reinterpret_cast<double*>(o),
+                        w + 4 * cap, w + 5 * cap, w + 6 * cap, w + 7 * cap};
+  HS_CHECK(seq_match_run(h, call, nq, sm, dev, cap, n_out, n_hits));
+  const size_t m = (size_t)*n_out;
+  if (m) {
+    HS_HIP(h, hipMemcpyAsync(out_group, dev.group, m * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_seq, dev.seq, m * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_diag, dev.diag, m * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_count, dev.count, m * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_best_dist, dev.best_dist, m * 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_best_q, dev.best_q, m * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_best_id, dev.best_id, m * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_lo, dev.lo, m * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_hi, dev.hi, m * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return HS_OK;
 }
 
 // The self-join of [first, first + count) with every batch's pairs selected per k-mer: row t of the device arrays is

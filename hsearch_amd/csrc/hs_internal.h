@@ -569,6 +569,34 @@ hipError_t hs_launch_knn_batch(const uint64_t* d_key, const uint64_t* d_val, con
 // rows of padding with zero counts: a call that ran no batch
 hipError_t hs_launch_knn_fill(uint64_t rows, uint32_t topk, uint32_t* d_nn_id, uint32_t* d_nn_table, double* d_nn_dist,
                               uint32_t* d_nn_count, hipStream_t s);
+// hits per (query group, sequence, diagonal) (hs_seqmatch.hip; the rule, the passes and the scratch are written at its
+// head).  check: d_out [3] (zeroed) = {flags (non-zero: invalid), max q_off, max ids of a sequence}.  key: the 64-bit
+// key and the index of each hit of a batch -- (d_key, d_val), or with d_key == null the arrays of a merged list.
+// head: d_head [n + 1] over sorted keys.  reduce: the sorted elements (d_skey, d_sidx, the scan d_excl of d_head) whose
+// source is a batch's hits or, with d_src_rows != null, the rows of a list of capacity src_cap, into rows dst_row0 ...
+// dst_row0 + n_rows of the list d_dst_rows of capacity dst_cap (one allocation of 40 bytes per row of capacity);
+// d_part of hs_sm_part_bytes(n) bytes.  decode: a list's first n rows into the output arrays; *d_flag |= 1 where a
+// count passes 32 bits.
+bool hs_sm_widths(uint64_t n_groups, uint64_t n_seq, uint64_t max_len, uint64_t max_qoff, int* wg, int* ws, int* wd);
+hipError_t hs_launch_sm_check(const uint32_t* d_q_group, const uint32_t* d_q_off, uint64_t nq, uint64_t n_groups,
+                              const uint64_t* d_id_start, uint64_t n_seq, uint64_t n, uint64_t* d_out, hipStream_t s);
+hipError_t hs_launch_sm_key(const uint64_t* d_key, const uint64_t* d_val, const uint32_t* d_q, const uint32_t* d_id,
+                            const double* d_dist, uint32_t n_hits, const uint32_t* d_q_group, const uint32_t* d_q_off,
+                            const uint64_t* d_id_start, uint64_t n_seq, int ws, int wd, uint64_t max_qoff,
+                            uint64_t* d_out_key, uint32_t* d_out_idx, hipStream_t s);
+hipError_t hs_launch_sm_iota(uint32_t n, uint32_t* d_idx, hipStream_t s);
+hipError_t hs_launch_sm_head(const uint64_t* d_skey, uint32_t n, uint32_t* d_head, hipStream_t s);
+size_t hs_sm_part_bytes(uint32_t n);
+hipError_t hs_launch_sm_reduce(const uint64_t* d_skey, const uint32_t* d_sidx, const uint32_t* d_excl,
+                               const uint32_t* d_head, uint32_t n, const uint64_t* d_key, const uint64_t* d_val,
+                               const uint32_t* d_q, const uint32_t* d_id, const double* d_dist,
+                               const uint64_t* d_id_start, int ws, int wd, const void* d_src_rows, uint64_t src_cap,
+                               void* d_dst_rows, uint64_t dst_cap, uint64_t dst_row0, uint32_t n_rows, void* d_part,
+                               hipStream_t s);
+hipError_t hs_launch_sm_decode(const void* d_rows, uint64_t cap, uint32_t n, int ws, int wd, uint64_t max_qoff,
+                               uint32_t* d_group, uint32_t* d_seq, int32_t* d_diag, uint32_t* d_count,
+                               double* d_best_dist, uint32_t* d_best_q, uint32_t* d_best_id, uint32_t* d_lo,
+                               uint32_t* d_hi, uint32_t* d_flag, hipStream_t s);
 // connected components of the self-join's graph (hs_components.hip): d_parent [n] is a union-find forest with
 // parent[x] <= x, d_counts two 64-bit words {ordered pairs united, roots}.  begin: the identity and zero counts;
 // union: a batch's pairs (self_first + (key >> 37), (uint32_t)key) as the exact pass leaves them in d_key, the

@@ -655,6 +655,153 @@ int SearchProteinsSharded(const ProteinDB& db, uint32_t kmer_length, const std::
   return HS_OK;
 }
 
+// "<first token of the protein's name>#<its number>": how the search's k-mer names begin
+static std::string ProteinLabel(const ProteinDB& db, size_t s) {
+  std::string token;
+  if (s < db.name.size()) {
+    std::istringstream iss(db.name[s]);
+    iss >> token;
+  }
+  return token + "#" + std::to_string(s);
+}
+
+int SearchProteinsPerSequence(const ProteinDB& db, uint32_t kmer_length, const std::vector<Point>& centers,
+                              const std::vector<std::string>& center_names, const std::vector<uint8_t>* center_codes,
+                              const ProteinDB* query, const uint32_t& hash_K, const uint32_t& hash_L,
+                              const double& hash_W, const double& hash_R, const std::string& output_file,
+                              const Planes& planes, int device, std::string* err, std::vector<uint64_t>* table_sizes,
+                              uint64_t* n_windows, uint32_t probes, const std::vector<double>* radii) {
+  const uint32_t dim = 8 * kmer_length, k = kmer_length;
+  const size_t n_groups = query ? (query->start.empty() ? 0 : query->start.size() - 1) : centers.size();
+  if (!RadiiMatch(radii, n_groups, err)) return HS_ERR_INVALID;
+  if (!query && center_codes && center_codes->size() != centers.size() * (size_t)k) {
+    if (err) *err = "centre codes do not match the centres";
+    return HS_ERR_INVALID;
+  }
+  if (k < 2 || planes.dim != dim || planes.K != hash_K || planes.L != hash_L || planes.W != hash_W) {
+    if (err) *err = k < 2 ? "kmer length 1 is not supported on a FASTA database" : "planes do not match (dim, K, L, W)";
+    return HS_ERR_INVALID;
+  }
+  // sequences cut at unknown letters, as in SearchProteinsSharded: windows never cross a cut
+  std::vector<uint8_t> res(db.residues);
+  std::vector<uint64_t> seg;
+  const size_t n_seq = db.start.empty() ? 0 : db.start.size() - 1;
+  for (size_t s = 0; s < n_seq; ++s) {
+    seg.push_back(db.start[s]);
+    for (uint64_t p = db.start[s]; p < db.start[s + 1]; ++p)
+      if (res[p] == ProteinDB::kUnknown) {
+        res[p] = 0;
+        seg.push_back(p);
+        seg.push_back(p + 1);
+      }
+  }
+  seg.push_back(db.residues.size());
+  // the queries: the centres, every one its own group; or every window (free of unknown letters) of every query
+  // protein, grouped by protein, with its offset in the protein
+  std::vector<double> flat;
+  std::vector<uint8_t> qcodes;
+  std::vector<uint32_t> q_group, q_off;
+  std::vector<double> q_radii;
+  uint64_t nq = centers.size();
+  if (query) {
+    for (size_t g = 0; g < n_groups; ++g) {
+      const uint64_t a = query->start[g], b = query->start[g + 1];
+      uint64_t known = 0;  // residues since the last unknown letter
+      for (uint64_t p = a; p < b; ++p) {
+        known = query->residues[p] == ProteinDB::kUnknown ? 0 : known + 1;
+        if (known < k) continue;
+        qcodes.insert(qcodes.end(), query->residues.begin() + (p + 1 - k), query->residues.begin() + (p + 1));
+        q_group.push_back((uint32_t)g);
+        q_off.push_back((uint32_t)(p + 1 - k - a));
+        if (radii) q_radii.push_back((*radii)[g]);
+      }
+    }
+    nq = q_group.size();
+  } else if (center_codes) {
+    qcodes = *center_codes;
+  } else if (!FlattenCenters(centers, dim, &flat, err)) {
+    return HS_ERR_INVALID;
+  }
+  const double* rad = !radii ? nullptr : query ? q_radii.data() : radii->data();
+  static const double no_radius = 0.0;
+  if (radii && !nq) rad = &no_radius;
+  hs_params prm;
+  memset(&prm, 0, sizeof(prm));
+  prm.k = k;
+  prm.K = hash_K;
+  prm.L = hash_L;
+  prm.W = hash_W;
+  prm.alphabet = HS_ALPHABET;
+  prm.device = device;
+  hs_handle* h = nullptr;
+  hs_status st = hs_create(&prm, planes.a.data(), planes.b.data(), &HS_AA_COORDS[0][0], &h);
+  if (st != HS_OK) {
+    if (err) *err = std::string("hs_create: ") + (h ? hs_last_error(h) : "no usable gfx950 device");
+    hs_destroy(h);
+    return st;
+  }
+  HandleCloser closer = {h};
+  if (probes && (st = hs_set_multiprobe(h, probes)) != HS_OK) {
+    if (err) *err = std::string("hs_set_multiprobe: ") + hs_last_error(h);
+    return st;
+  }
+  uint64_t n_win = 0;
+  std::vector<uint32_t> win_pos(res.size() + 1);
+  st = hs_index_build_windows(h, res.data(), res.size(), seg.data(), seg.size() - 1, &n_win, win_pos.data());
+  if (st != HS_OK) {
+    if (err) *err = std::string("index build: ") + hs_last_error(h);
+    return st;
+  }
+  if (n_windows) *n_windows = n_win;
+  hs_index_info info;
+  if (table_sizes && hs_index_info_get(h, &info) == HS_OK) table_sizes->assign(info.n_buckets, info.n_buckets + prm.L);
+  // protein s owns the windows that start inside it: their ids are consecutive (windows are numbered by position)
+  std::vector<uint64_t> id_start(n_seq + 1);
+  for (size_t s = 0; s <= n_seq; ++s)
+    id_start[s] = (uint64_t)(std::lower_bound(win_pos.begin(), win_pos.begin() + n_win, db.start.empty() ? 0 : db.start[s]) -
+                             win_pos.begin());
+  id_start[n_seq] = n_win;
+  std::vector<uint32_t> o_group, o_seq, o_count, o_q, o_id, o_lo, o_hi;
+  std::vector<int32_t> o_diag;
+  std::vector<double> o_dist;
+  uint64_t n_rows = 0, n_hits = 0;
+  for (uint64_t cap = 0;;) {  // the row count, then the rows
+    for (std::vector<uint32_t>* v : {&o_group, &o_seq, &o_count, &o_q, &o_id, &o_lo, &o_hi}) v->resize(cap);
+    o_diag.resize(cap);
+    o_dist.resize(cap);
+    st = hs_seq_match(h, qcodes.empty() ? flat.data() : nullptr, qcodes.empty() ? nullptr : qcodes.data(), nq, hash_R,
+                      rad, query ? q_group.data() : nullptr, query ? n_groups : nq, query ? q_off.data() : nullptr,
+                      id_start.data(), n_seq, o_group.data(), o_seq.data(), o_diag.data(), o_count.data(),
+                      o_dist.data(), o_q.data(), o_id.data(), o_lo.data(), o_hi.data(), cap, &n_rows, &n_hits);
+    if (st == HS_ERR_CAPACITY && n_rows > cap) {
+      cap = n_rows;
+      continue;
+    }
+    break;
+  }
+  if (st != HS_OK) {
+    if (err) *err = std::string("hs_seq_match: ") + hs_last_error(h);
+    return st;
+  }
+  // one line per row: the group (centre, or query protein), the protein, the count, the residue offset of the best
+  // window, its distance (%.17g reads back to the same double), the first and the last matched offset; with query
+  // proteins the diagonal last
+  std::ofstream fout(output_file.c_str());
+  for (uint64_t i = 0; i < n_rows; ++i) {
+    const size_t s = o_seq[i];
+    const uint64_t base = db.start[s];
+    char num[40];
+    snprintf(num, sizeof(num), "%.17g", o_dist[i]);
+    fout << (query ? ProteinLabel(*query, o_group[i]) : center_names[o_group[i]]) << " " << ProteinLabel(db, s) << " "
+         << o_count[i] << " " << (win_pos[o_id[i]] - base) << " " << num << " "
+         << (win_pos[id_start[s] + o_lo[i]] - base) << " " << (win_pos[id_start[s] + o_hi[i]] - base);
+    if (query) fout << " " << o_diag[i];
+    fout << std::endl;
+  }
+  fout.close();
+  return HS_OK;
+}
+
 int64_t Protein2Datapoints(const ProteinDB& db, uint32_t kmer_length, uint32_t num_of_protein_out,
                            const std::string& output_file, uint32_t seed) {
   std::ofstream fout(output_file.c_str());

@@ -155,6 +155,24 @@ int SearchProteinsSharded(const ProteinDB& db, uint32_t kmer_length, const std::
                           std::vector<uint64_t>* table_sizes = nullptr, uint64_t* n_windows = nullptr,
                           bool best_per_position = false, const std::vector<uint8_t>* center_codes = nullptr,
                           const std::vector<double>* radii = nullptr, uint32_t topk = 0);
+// The per_sequence mode of SearchProteins: instead of the hits, one line per (centre, database protein) with a hit,
+// reduced on the device (hs_seq_match in include/hsearch.h; the hit list never reaches the host) --
+//   <centre name> <protein>#<its number> <hits> <offset of the best window> <its distance> <first> <last matched offset>
+// rows ascending in (centre, protein), offsets in residues of the protein, the distance printed with %.17g.  query
+// != nullptr: the queries are every length-k window of the proteins of `query` (centers, center_names and
+// center_codes unused), the groups are the query proteins and diagonals are kept: one line per (query protein,
+// database protein, diagonal), named <query protein>#<its number>, the best offset that of the database window, the
+// diagonal (database window number in its protein minus query offset) as the last field.  A protein with letters
+// outside the alphabet has no window across them; its window numbers, which the diagonal is made of, then run
+// behind its residue offsets.  radii: one per centre, or per query protein.  probes: multi-probe, as in Search().
+// One GPU.
+int SearchProteinsPerSequence(const ProteinDB& db, uint32_t kmer_length, const std::vector<Point>& centers,
+                              const std::vector<std::string>& center_names, const std::vector<uint8_t>* center_codes,
+                              const ProteinDB* query, const uint32_t& hash_K, const uint32_t& hash_L,
+                              const double& hash_W, const double& hash_R, const std::string& output_file,
+                              const Planes& planes, int device, std::string* err,
+                              std::vector<uint64_t>* table_sizes = nullptr, uint64_t* n_windows = nullptr,
+                              uint32_t probes = 0, const std::vector<double>* radii = nullptr);
 // center_codes (CentersFromKmers): the centres are k-mers of the exact table -- the one a FASTA
 // database is embedded from -- and travel to the GPU as residue codes (hs_query_codes: k bytes per
 // centre instead of 64 k); the hits are those of the embedded centres, bit for bit.

@@ -23,7 +23,12 @@
 // reached, "<kmer name> <centre> <dist>" with its nearest centre (hs_annotate), k-mers ascending.  --topk N (1..64):
 // per centre only its N best hits, selected on the device (hs_query_topk): the usual lines, per centre at most N of
 // them, in ascending (distance, k-mer index); with points and FASTA databases, with --radii and -M; one GPU only, and
-// not with --best-per-position 1.
+// not with --best-per-position 1.  --per-sequence 1 (FASTA database): instead of the hits, one line per (centre,
+// protein) with a hit -- "<centre> <protein>#<number> <hits> <best window's offset> <its distance> <first> <last matched
+// offset>" --, reduced on the device (hs_seq_match).  --query-fasta FILE in place of -c: the query proteins are cut
+// into windows with the database's residue mapping and swap option, the groups are the query proteins and the lines
+// are per (query protein, protein, diagonal), the diagonal last.  Both work with --radii (per centre, or per query
+// protein) and -M; one GPU only, and not with --topk or --best-per-position 1.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -72,6 +77,8 @@ const Opt kOpts[] = {
     {"planes-out", 'P', "write the planes (binary doubles a[L][K][d] then b[L][K])", false},
     {"ref-compat-eq-swap", 'Q', "FASTA database: exchange E and Q like the reference's ProteinDB [0]", false},
     {"best-per-position", 'B', "one line per matched database k-mer (FASTA: window), its nearest centre (kmer_search) [0]", false},
+    {"per-sequence", 'S', "FASTA database: one line per (centre, protein) with a hit: count, best window, span (one GPU) [0]", false},
+    {"query-fasta", 'q', "query proteins in place of -c: one line per (query protein, protein, diagonal) (implies --per-sequence 1)", false},
     {"topk", 't', "per centre only its N best hits, 1..64, in ascending (distance, k-mer index) (one GPU) [off: all hits]", false},
 };
 
@@ -131,8 +138,10 @@ int main(int argc, const char* argv[]) {
     Help(argv[0]);
     return EXIT_SUCCESS;
   }
+  const bool query_fasta = val.count("query-fasta") != 0;
+  const bool per_sequence = query_fasta || (val.count("per-sequence") && atoi(val["per-sequence"].c_str()) != 0);
   for (const Opt& o : kOpts)
-    if (o.required && !val.count(o.long_name)) {
+    if (o.required && !val.count(o.long_name) && !(query_fasta && std::string(o.long_name) == "center")) {
       fprintf(stderr, "missing required option -%c\n", o.short_name);
       Help(argv[0]);
       return EXIT_SUCCESS;  // as the reference: option_missing() -> message, EXIT_SUCCESS
@@ -164,6 +173,26 @@ int main(int argc, const char* argv[]) {
     if (val.count("best-per-position") && atoi(val["best-per-position"].c_str()) != 0) {
       fprintf(stderr, "ERROR: --topk cannot be combined with --best-per-position %s: an annotation has one line per "
                       "k-mer\n", val["best-per-position"].c_str());
+      return EXIT_FAILURE;
+    }
+  }
+  if (per_sequence) {
+    const char* flag = query_fasta ? "--query-fasta" : "--per-sequence";
+    if (query_fasta && val.count("center")) {
+      fprintf(stderr, "ERROR: --query-fasta takes the place of -c: give one of them\n");
+      return EXIT_FAILURE;
+    }
+    if (val.count("gpus") && atoi(val["gpus"].c_str()) > 1) {
+      fprintf(stderr, "ERROR: %s runs on one GPU: it cannot be combined with --gpus %s\n", flag, val["gpus"].c_str());
+      return EXIT_FAILURE;
+    }
+    if (topk) {
+      fprintf(stderr, "ERROR: %s cannot be combined with --topk %u: its lines are per protein, not per hit\n", flag, topk);
+      return EXIT_FAILURE;
+    }
+    if (val.count("best-per-position") && atoi(val["best-per-position"].c_str()) != 0) {
+      fprintf(stderr, "ERROR: %s cannot be combined with --best-per-position %s: an annotation has one line per k-mer\n",
+              flag, val["best-per-position"].c_str());
       return EXIT_FAILURE;
     }
   }
@@ -203,8 +232,24 @@ int main(int argc, const char* argv[]) {
         return EXIT_FAILURE;
       }
     }
+    if (per_sequence && !fasta_db) {
+      fprintf(stderr, "ERROR: --per-sequence / --query-fasta need a FASTA database: a points file names no proteins\n");
+      return EXIT_FAILURE;
+    }
+    hsearch::ProteinDB qrydb;
+    if (query_fasta) {
+      std::cout << "Read query proteins from " << val["query-fasta"] << std::endl;
+      if (!hsearch::ReadProteinFasta(val["query-fasta"], prodb.eq_swapped, &qrydb)) {
+        fprintf(stderr, "cannot open %s\n", val["query-fasta"].c_str());
+        return EXIT_FAILURE;
+      }
+      center_names = qrydb.name;  // (what --radii names)
+      center_names.resize(qrydb.start.size() - 1);
+    } else {
     std::cout << "Read Centers..." << std::endl;
-    if (LooksLikeFasta(val["center"])) {
+    }
+    if (query_fasta) {
+    } else if (LooksLikeFasta(val["center"])) {
       std::vector<hsearch::Kmer> ckmers;
       std::string cerr;
       if (!hsearch::ReadKmerFasta(val["center"], &ckmers)) {
@@ -230,6 +275,8 @@ int main(int argc, const char* argv[]) {
       for (double r : radii) hash_R = std::max(hash_R, fabs(r));
     }
     if (!fasta_db) std::cout << "number of kmers " << kmers.size() << std::endl;
+    if (query_fasta) std::cout << "number of query proteins " << center_names.size() << std::endl;
+    else
     std::cout << "number of centers " << centers.size() << std::endl;
     hsearch::Planes planes;
     if (val.count("planes")) {
@@ -281,7 +328,7 @@ int main(int argc, const char* argv[]) {
       fprintf(stderr, "ERROR: --probes must be 0..63\n");
       return EXIT_FAILURE;
     }
-    if (probes && fasta_db) {
+    if (probes && fasta_db && !per_sequence) {
       fprintf(stderr, "ERROR: --probes needs a points database\n");
       return EXIT_FAILURE;
     }
@@ -292,6 +339,12 @@ int main(int argc, const char* argv[]) {
     uint64_t n_windows = 0;
     const bool best_per_position = val.count("best-per-position") && atoi(val["best-per-position"].c_str()) != 0;
     const int st =
+        per_sequence ? hsearch::SearchProteinsPerSequence(prodb, kmer_length, centers, center_names,
+                                                          center_codes.empty() || val.count("centers-as-points")
+                                                              ? nullptr : &center_codes,
+                                                          query_fasta ? &qrydb : nullptr, hash_K, hash_L, hash_W, hash_R,
+                                                          val["output"], planes, device, &err, &table_sizes, &n_windows,
+                                                          (uint32_t)probes, with_radii ? &radii : nullptr) :
         fasta_db ? hsearch::SearchProteinsSharded(prodb, kmer_length, centers, center_names, hash_K, hash_L,
                                                   hash_W, hash_R, val["output"], planes, devices, use_comm,
                                                   &err, &table_sizes, &n_windows,

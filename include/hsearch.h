@@ -809,6 +809,98 @@ HS_API hs_status hs_topk_merge(const uint32_t* q, const uint32_t* id, const uint
                                uint64_t n_tuples, uint64_t nq, uint32_t topk, uint32_t* nn_id, uint32_t* nn_table,
                                double* nn_dist, uint32_t* nn_count);
 
+/* ---- hits per (query group, database sequence, diagonal) ---------------------------------------------------- */
+
+/* "Which proteins carry this motif, how often, and where is the best site", and with a protein as the query "which
+ * database proteins share runs of similar k-mers with it, and on which diagonal": what kmer_search.cpp's Search()
+ * accumulates per protein in `matches` and never reports, reduced on the device.  The hit list never crosses PCIe and
+ * is never ordered per query.
+ *
+ * The underlying hit list.  Exactly one of centers [nq][d] / qcodes [nq][k] is non-NULL; radii == NULL: every query at
+ * R; else radii [nq] and R is ignored (as in hs_annotate).  Let H be the hit list hs_query / hs_query_codes (radii ==
+ * NULL) or hs_query_radii returns for the same arguments on the same handle: the handle's multi-probe setting and
+ * bucket partition apply as they do there, and recognised k-mer centres and codes give the same bits as points.
+ *
+ * Sequences.  id_start [n_seq + 1] is ascending (equal neighbours allowed: a sequence without ids), id_start[0] == 0
+ * and id_start[n_seq] == n, the index's k-mers: sequence s owns the ids [id_start[s], id_start[s + 1]).  It is a
+ * statement about ids, so it serves any index; for an index built by hs_index_build_windows, hs_window_id_start
+ * computes it from the same seq_start (sequence s has max(0, len_s - k + 1) windows).
+ *
+ * The key of a hit (q, id): g = q_group[q] (q_group == NULL: g = q, and n_groups must equal nq); s = the sequence
+ * that owns id; off = id - id_start[s]; diag = off - q_off[q] (q_off == NULL: no diagonals are kept, diag is 0 for
+ * every hit).  The output has ONE ROW PER DISTINCT (g, s, diag) of H, rows ascending in (g, s, diag) with diag
+ * compared as the signed difference (out_diag receives its low 32 bits):
+ *   out_count                              the number of hits of H with that key
+ *   out_best_dist, out_best_q, out_best_id the hit smallest under (dist as double, q, id); the distance is
+ *                                          bit-identical to its hit_dist
+ *   out_lo, out_hi                         the smallest and the largest off among the row's hits: on a diagonal they
+ *                                          bound the run of seeds, without diagonals they span the matches in s
+ * *n_hits = the underlying call's *n_hits; the counts sum to it.  Capacity, counted in rows, follows the two-call
+ * pattern (HS_ERR_CAPACITY with *n_out set and nothing written; cap = 0 with NULL arrays asks for the count), and
+ * *n_out <= *n_hits always.  Every reduction is order-free -- integer sum, min and max on integers and on distance
+ * bit patterns; distances are >= +0 and never a NaN -- so the result is a pure function of the index and the
+ * arguments: batch sizes, filter paths, options and scheduling do not show in it.
+ *
+ * Key width, a stated limit of the entry point.  Let wg, ws, wd be the bits needed for n_groups - 1, n_seq - 1 and
+ * max_len + max_qoff - 1, where max_len is the largest id count of a sequence and max_qoff the largest q_off (0
+ * without q_off); the diagonal is kept as off - q_off + max_qoff.  A call with wg + ws + wd > 64 is HS_ERR_INVALID.
+ * What fits, for scale: 5 x 10^7 sequences x 10^3 query proteins x diagonals of 10^5 is 26 + 10 + 17 bits.  n_groups
+ * and n_seq are at most 2^32.
+ *
+ * Errors, reported before any output is written: everything the underlying call rejects (a NaN R or radius, an
+ * unbuilt index, nq >= 2^27); an id_start that does not ascend, does not start at 0 or does not end at n; a
+ * q_group[q] >= n_groups; the width rule.  The _dev form finds these on the device: one small reduction over q_group /
+ * q_off / id_start and one read-back per call, as hs_query_radii_dev does for the radii.  A query code outside the
+ * alphabet is found by the search itself, and nothing is written then.  A row that would count more than 2^32 - 1 hits
+ * is HS_ERR_CAPACITY.
+ *
+ * Every batch's exact hits (a multi-probe chunk's merged list likewise) are keyed, sorted and reduced where they lie,
+ * and the batch's rows appended to a list of the handle; at the end of a call to which several batches contributed the
+ * list is reduced once more.  Scratch is sized by a batch plus the rows found so far: never by n, by n_groups x n_seq
+ * or by the call's hits.  Every other entry point launches what it launched. */
+HS_API hs_status hs_seq_match(hs_handle* h, const double* centers, const uint8_t* qcodes, uint64_t nq, double R,
+                              const double* radii, const uint32_t* q_group, uint64_t n_groups, const uint32_t* q_off,
+                              const uint64_t* id_start, uint64_t n_seq, uint32_t* out_group, uint32_t* out_seq,
+                              int32_t* out_diag, uint32_t* out_count, double* out_best_dist, uint32_t* out_best_q,
+                              uint32_t* out_best_id, uint32_t* out_lo, uint32_t* out_hi, uint64_t cap, uint64_t* n_out,
+                              uint64_t* n_hits);
+/* ... every pointer but n_out / n_hits in device memory (streams: as hs_query_dev) */
+HS_API hs_status hs_seq_match_dev(hs_handle* h, const double* d_centers, const uint8_t* d_qcodes, uint64_t nq, double R,
+                                  const double* d_radii, const uint32_t* d_q_group, uint64_t n_groups,
+                                  const uint32_t* d_q_off, const uint64_t* d_id_start, uint64_t n_seq,
+                                  uint32_t* d_out_group, uint32_t* d_out_seq, int32_t* d_out_diag, uint32_t* d_out_count,
+                                  double* d_out_best_dist, uint32_t* d_out_best_q, uint32_t* d_out_best_id,
+                                  uint32_t* d_out_lo, uint32_t* d_out_hi, uint64_t cap, uint64_t* n_out,
+                                  uint64_t* n_hits);
+/* id_start [n_seq + 1] of an index built by hs_index_build_windows over seq_start [n_seq + 1] at k-mer length k (host
+ * only): sequence s has max(0, len_s - k + 1) windows, numbered sequence-major.  A seq_start that does not ascend and
+ * k == 0 are HS_ERR_INVALID. */
+HS_API hs_status hs_window_id_start(const uint64_t* seq_start, uint64_t n_seq, uint32_t k, uint64_t* id_start);
+/* The same rule on the host (no GPU, no handle) for ANY list of n_tuples hits (q, id, dist) in any order -- a raw hit
+ * list, or the lists of the parts of a table or bucket partition after their first-seen merge: rows and capacity as
+ * above.  A (q, id) given several times counts once and must carry one distance (different bits: HS_ERR_INVALID);
+ * -0.0 is read as +0.0.  q >= nq, an id >= id_start[n_seq], a NaN or negative distance and every error of the
+ * contract above (id_start here only has to ascend from 0) are HS_ERR_INVALID, reported before anything is
+ * written.  Outputs must not overlap inputs. */
+HS_API hs_status hs_seq_match_hits(const uint32_t* q, const uint32_t* id, const double* dist, uint64_t n_tuples,
+                                   uint64_t nq, const uint32_t* q_group, uint64_t n_groups, const uint32_t* q_off,
+                                   const uint64_t* id_start, uint64_t n_seq, uint32_t* out_group, uint32_t* out_seq,
+                                   int32_t* out_diag, uint32_t* out_count, double* out_best_dist, uint32_t* out_best_q,
+                                   uint32_t* out_best_id, uint32_t* out_lo, uint32_t* out_hi, uint64_t cap,
+                                   uint64_t* n_out);
+/* Rows combined (host only): rows with equal (group, seq, diag) become one -- counts add, best is the min under (dist,
+ * q, id), lo the min, hi the max --, rows ascending as above.  Valid ONLY for parts whose hit lists are DISJOINT: the
+ * query-block layout, with q (and the groups) made global first.  Parts that can report one (q, id) twice -- the
+ * table and bucket partitions -- would count it twice here: their hit lists go through hs_seq_match_hits instead.  A
+ * count that would pass 2^32 - 1, a zero count, lo > hi and a NaN or negative distance are HS_ERR_INVALID, reported
+ * before anything is written.  Outputs must not overlap inputs. */
+HS_API hs_status hs_seq_match_merge(const uint32_t* group, const uint32_t* seq, const int32_t* diag,
+                                    const uint32_t* count, const double* best_dist, const uint32_t* best_q,
+                                    const uint32_t* best_id, const uint32_t* lo, const uint32_t* hi, uint64_t n_rows,
+                                    uint32_t* out_group, uint32_t* out_seq, int32_t* out_diag, uint32_t* out_count,
+                                    double* out_best_dist, uint32_t* out_best_q, uint32_t* out_best_id, uint32_t* out_lo,
+                                    uint32_t* out_hi, uint64_t cap, uint64_t* n_out);
+
 /* ---- cluster profiles, centroids and covering radii from a label array ------------------------------------ */
 
 /* The step from cluster labels to what a search takes: per cluster its members' position frequency matrix, their
