@@ -31,7 +31,8 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_core_distance_dev", "hs_density_tree", "hs_density_tree_dev", "hs_density_tree_edges",
            "hs_density_tree_cut", "hs_query_topk", "hs_query_topk_dev", "hs_self_knn", "hs_self_knn_range",
            "hs_self_knn_dev", "hs_self_knn_range_dev", "hs_topk_merge", "hs_seq_match", "hs_seq_match_dev",
-           "hs_window_id_start", "hs_seq_match_hits", "hs_seq_match_merge"]
+           "hs_window_id_start", "hs_seq_match_hits", "hs_seq_match_merge", "hs_join6_tables", "hs_join6_thresholds",
+           "hs_join6_selftest"]
 
 TOPK_MAX = 64        # HS_TOPK_MAX: the widest row of query_topk / self_knn / topk_merge
 NO_ID = 0xffffffff   # the id and table of an unused entry of such a row (its distance is +inf)
@@ -59,7 +60,8 @@ class _Profile(C.Structure):
                 ("join_pairs_issued", C.c_uint64), ("join_i8_batches", C.c_uint64),
                 ("hash_values", C.c_uint64), ("hash_flagged", C.c_uint64),
                 ("join_row_bytes", C.c_uint32), ("join_wide", C.c_uint32), ("join_items_resident", C.c_uint64),
-                ("join_async_retries", C.c_uint64), ("queries_recognised", C.c_uint64)]
+                ("join_async_retries", C.c_uint64), ("queries_recognised", C.c_uint64),
+                ("join_f6_batches", C.c_uint64)]
 
 
 class _IndexInfo(C.Structure):
@@ -659,6 +661,50 @@ def cluster_summary_codes(codes, label, min_size=1, coords=None, centers=None, w
     return res
 
 
+def join6_tables(coords):
+    """The FP6 join filter's tables for a coordinate table ([alphabet][8] doubles), computed on the host (no GPU):
+    dict(s, codes [alphabet][4] six-bit e2m3 codes, e [alphabet], r [alphabet], pair [1024][2] dwords)."""
+    coords = np.ascontiguousarray(coords, dtype=np.float64)
+    A = coords.shape[0]
+    s = C.c_double(0.0)
+    codes = np.zeros((32, 4), dtype=np.uint8)
+    e, r = np.zeros(32), np.zeros(32)
+    pair = np.zeros((1024, 2), dtype=np.uint32)
+    lib = load()
+    st = lib.hs_join6_tables(_vp(coords), C.c_uint32(A), C.byref(s), _vp(codes), _vp(e), _vp(r), _vp(pair))
+    if st:
+        raise HsError(st, "hs_join6_tables")
+    return dict(s=s.value, codes=codes[:A], e=e[:A], r=r[:A], pair=pair)
+
+
+def join6_thresholds(coords, kmers, r2):
+    """What the FP6 join carries for k-mers ([n][k] codes) at squared radii r2 [n], in units of 2^-6, on the host:
+    dict(rho64 [n] a member's rho as its record encodes it, c64 [n] a query's C operand, rho0_64, rec [n][4])."""
+    coords = np.ascontiguousarray(coords, dtype=np.float64)
+    kmers = np.ascontiguousarray(kmers, dtype=np.uint8)
+    n, k = kmers.shape
+    r2 = np.ascontiguousarray(np.broadcast_to(np.asarray(r2, dtype=np.float64), (n,)))
+    rho64, c64 = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    rho0 = C.c_int64(0)
+    rec = np.zeros((n, 4), dtype=np.uint32)
+    st = load().hs_join6_thresholds(_vp(coords), C.c_uint32(coords.shape[0]), _vp(kmers), C.c_uint64(n), C.c_uint32(k),
+                                    _vp(r2), _vp(rho64), _vp(c64), C.byref(rho0), _vp(rec))
+    if st:
+        raise HsError(st, "hs_join6_thresholds")
+    return dict(rho64=rho64, c64=c64, rho0_64=rho0.value, rec=rec)
+
+
+def join6_selftest(device=0, variant=0):
+    """GPU: the FP6 join kernel's tile product against int64 arithmetic on rows at the format's extremes.
+    Returns (mismatches, first_bad) -- first_bad = (case, lane * 4 + register, float bits, expected in 64ths)."""
+    n = C.c_uint64(0)
+    bad = (C.c_uint32 * 4)()
+    st = load().hs_join6_selftest(C.c_int(device), C.c_int(variant), C.byref(n), bad)
+    if st:
+        raise HsError(st, "hs_join6_selftest")
+    return int(n.value), tuple(int(x) for x in bad)
+
+
 def index_file_check(path):
     """Host-only check of an index file (hs_index_file_check): header, payload length + hash and the
     content rules hs_index_load enforces on the device.  Raises HsError(HS_ERR_IO) naming the fault."""
@@ -753,7 +799,7 @@ class Engine:
                "wide_rows": 6, "refine8": 7, "self_codes": 8, "sort_hits": 10, "sync_items": 11,
                "join_min_q": 12, "join_min_m": 13, "sort_from_bit": 14, "build_serial": 15,
                "join_xcd_run": 16, "probe_records": 17, "join_chunk": 18, "summary_chunk": 19, "summary_rows": 20,
-               "msf_edge_budget": 21}
+               "msf_edge_budget": 21, "join_f6": 22}
 
     def set_option(self, name, value):
         """hs_set_option (include/hsearch.h hs_option): path selection / batch sizing; never changes a result."""

@@ -88,6 +88,7 @@ struct Knobs {
   bool force_wide = false;         // HS_OPT_WIDE_ROWS = 1: 8-column rows whatever the radius (k <= 25)
   bool no_wide_by_radius = false;  // HS_OPT_WIDE_ROWS >= 2: never choose 8-column rows by radius
   bool no_refine8 = false;         // HS_OPT_REFINE8 = 0: no 8-column refinement of the join's survivors
+  bool no_join_f6 = false;         // HS_OPT_JOIN_F6 = 0: k-mer queries never through the FP6 join (hs_join6.hip)
   bool no_self_codes = false;      // HS_OPT_SELF_CODES = 0: self-join from embedded centres, not from codes
   bool sort_hits = false;          // HS_OPT_SORT_HITS: order hits by the radix sort, not per query
   bool sync_items = false;         // HS_OPT_SYNC_ITEMS: read the join's item count back before launching it
@@ -221,6 +222,11 @@ struct hs_handle {
   // member records of the wide rows for k = 21..25 (built when a call's radius first asks for them)
   DevBuf t_rec8w;
   bool rec8w_ready = false;
+  // the FP6 join (hs_join6.hip): its tables, and the member records (16 bytes per entry and table), built on the
+  // first batch that can use them; rec6_state: 0 not built, 1 ready, -1 no room for them (int8 join for this index)
+  DevBuf jtab6, t_rec6;
+  int rec6_state = 0;
+  bool join6_tables_ok = false;
   double pair4_mean = 0.0, pair4_var = 0.0;  // 4-column squared distance of two random residues
   DevBuf t_pos;  // [L][n] sorted position of every DB id in every table (first-seen dedupe)
   DevBuf dir_base;       // [L + 1] first global bucket number of every table; [L] = nb_total
@@ -361,6 +367,7 @@ float filter_bound(double r2) { return hs_filter_bound(r2); }
 void drop_index(hs_handle* h) {
   h->built = false;
   h->rec8w_ready = false;
+  h->rec6_state = 0;
   h->hist = {};
 }
 
@@ -535,7 +542,7 @@ const struct { const char* name; int option; } kOptionNames[] = {
     {"sort_hits", HS_OPT_SORT_HITS}, {"sync_items", HS_OPT_SYNC_ITEMS}, {"join_min_q", HS_OPT_JOIN_MIN_Q},
     {"join_min_m", HS_OPT_JOIN_MIN_M}, {"sort_from_bit", HS_OPT_SORT_FROM_BIT}, {"build_serial", HS_OPT_BUILD_SERIAL},
     {"join_xcd_run", HS_OPT_JOIN_XCD_RUN}, {"probe_records", HS_OPT_PROBE_RECORDS},
-    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS},
+    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"join_f6", HS_OPT_JOIN_F6}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS},
     {"msf_edge_budget", HS_OPT_MSF_EDGE_BUDGET}};
 
 void read_knobs(hs_handle* h) {
@@ -700,12 +707,19 @@ hs_status hs_create(const hs_params* params, const double* a, const double* b, c
   HS_HIP(h, hs_launch_jtables8(h->coords.as<double>(), h->alphabet, h->jtab8.p, h->jtab8.as<float>() + 128,
                                reinterpret_cast<uint32_t*>(h->jtab8.as<char>() + 640),
                                h->jtab8.as<char>() + 1024, h->jtab8.as<char>() + 1536, h->stream));
+  // the FP6 join's tables (hs_join6_tables.h); their last word says whether the table has a usable scale
+  HS_HIP(h, h->jtab6.reserve(hs_join6_table_bytes()));
+  HS_HIP(h, hipMemsetAsync(h->jtab6.p, 0, hs_join6_table_bytes(), h->stream));
+  HS_HIP(h, hs_launch_jtables6(h->coords.as<double>(), h->alphabet, h->jtab6.p, h->stream));
+  int32_t ok6 = 0;
+  HS_HIP(h, hipMemcpyAsync(&ok6, h->jtab6.as<char>() + hs_join6_ok_offset(), 4, hipMemcpyDeviceToHost, h->stream));
   uint32_t unsafe8 = 1;
   float scale8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   HS_HIP(h, hipMemcpyAsync(&unsafe8, h->jtab8.as<char>() + 640, 4, hipMemcpyDeviceToHost, h->stream));
   HS_HIP(h, hipMemcpyAsync(scale8, h->jtab8.as<char>() + 512, 32, hipMemcpyDeviceToHost, h->stream));
   HS_HIP(h, hipStreamSynchronize(h->stream));
   h->join8_tables_ok = (unsafe8 == 0);
+  h->join6_tables_ok = ok6 != 0;
   // Short k-mers: R^2 is not far below the 4-column distance of bucket mates any more (k = 15: the
   // 4-column bound passes 4 % of random pairs), so their rows carry all 8 columns (hs_join8.hip)
   if (getenv("HS_BACKTRACE")) signal(SIGABRT, hs_abort_backtrace);
@@ -813,6 +827,7 @@ hs_status hs_set_option(hs_handle* h, int option, int64_t value) {
       return HS_OK;
     }
     case HS_OPT_REFINE8: return flag(&kn.no_refine8, true);
+    case HS_OPT_JOIN_F6: return flag(&kn.no_join_f6, true);
     case HS_OPT_SELF_CODES: return flag(&kn.no_self_codes, true);
     case HS_OPT_SORT_HITS: return flag(&kn.sort_hits, false);
     case HS_OPT_SYNC_ITEMS: return flag(&kn.sync_items, false);
@@ -875,7 +890,7 @@ void hs_destroy(hs_handle* h) {
                     &h->io_codes, &h->io_misc, &h->jtab, &h->c16, &h->seg_keys, &h->seg_keys_sorted,
                     &h->seg_vals, &h->sorted_ql, &h->seg_key, &h->seg_cnt, &h->seg_qoff,
                     &h->seg_items, &h->item_off, &h->seg_n, &h->c16s, &h->item_desc,
-                    &h->probe_slow, &h->jtab8, &h->c8b, &h->prov2, &h->t_packed, &h->t_rec8, &h->t_rec8w, &h->t_pos, &h->dir_base,
+                    &h->probe_slow, &h->jtab8, &h->c8b, &h->prov2, &h->t_packed, &h->t_rec8, &h->t_rec8w, &h->jtab6, &h->t_rec6, &h->t_pos, &h->dir_base,
                     &h->bucket_work, &h->proj_aq_all, &h->proj_aq_tab, &h->proj_fn, &h->proj_tab, &h->proj_stats,
                     &h->proj_flags[0], &h->proj_flags[1], &h->proj_flags[2], &h->proj_cnt, &h->proj_xq,
                     &h->proj_xmeta, &h->qhits, &h->bs_ints2[0], &h->bs_ints2[1], &h->bs_keys2[0],
@@ -1441,7 +1456,7 @@ static hs_status finish_index(hs_handle* h) {
       if (wide[l]) h->tabs.t[l].dir_rec = nullptr;  // a bucket int outside 16 bits: this table keeps the arrays
   }
   HS_HIP(h, hipStreamSynchronize(h->stream));
-  uint64_t bytes = h->codes.cap + h->packed_all.cap + h->t_packed.cap + h->t_rec8.cap + h->t_rec8w.cap + h->t_rho.cap +
+  uint64_t bytes = h->codes.cap + h->packed_all.cap + h->t_packed.cap + h->t_rec8.cap + h->t_rec8w.cap + h->t_rec6.cap + h->t_rho.cap +
                    h->t_pos.cap + h->t_dirrec.cap;
   for (uint32_t l = 0; l < h->p.L; ++l)
     bytes += h->t_dirkey[l].cap + h->t_dirstart[l].cap + h->t_dirtuple[l].cap + h->t_ids[l].cap;
@@ -2255,6 +2270,29 @@ static hs_status ensure_rec8w(hs_handle* h) {
   return HS_OK;
 }
 
+// The FP6 join's member records, built on the first batch that can use them.  false: no room for them (the
+// error is cleared; the index keeps the int8 join)
+static bool ensure_rec6(hs_handle* h) {
+  if (h->rec6_state) return h->rec6_state > 0;
+  const size_t n = h->n;
+  const int L = (int)h->p.L;
+  if (h->t_rec6.reserve(((size_t)L * n + HS_JM_WAVE) * 16) != hipSuccess) {
+    (void)hipGetLastError();
+    h->rec6_state = -1;
+    return false;
+  }
+  // (the pad behind the last entry is read by nobody: the kernel clamps a member index to its segment)
+  for (int l = 0; l < L; ++l)
+    if (hs_launch_gather_rec6(h->packed_all.as<uint4>(), h->tabs.t[l].ids, (uint32_t)n, (int)h->p.k, h->jtab6.p,
+                              h->t_rec6.as<uint4>() + (size_t)l * n, h->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      h->rec6_state = -1;
+      return false;
+    }
+  h->rec6_state = 1;
+  return true;
+}
+
 // May a self-join at radius R run from the residue codes alone (the plan's self_codes)?  Only when
 // nothing on its way can need the embedded centres: the int8 join and its thin-segment filter must
 // apply, and no query row may be unrepresentable -- for a k-mer of the coordinate table the one way
@@ -2286,6 +2324,7 @@ struct BatchPlan {
   bool all_joined = false;  // every segment goes to the join (HS_OPT_JOIN_MIN_Q / _M at 1)
   bool no_slices = false;   // ... so the probes write no slice counts and the slice offsets stay the reset's zeros
   bool use_r = false;       // segments with few probing queries through hs_join8r_kernel
+  bool f6 = false;          // the other segments through hs_join6x_kernel (FP6 rows) instead of hs_join8x_kernel
   uint32_t jm = HS_JM_BLOCK;  // members per join work item
   bool async_items = false;   // the item count stays on the device; the descriptors are sized by item_cap
   uint32_t item_cap = 0;
@@ -2335,6 +2374,10 @@ static BatchPlan plan_batch(const hs_handle* h, const QueryCall& c, uint32_t nq,
   const double share = p.resident_stale ? -1.0 : m.resident_share;
   p.use_r = p.use_i8 && !p.wide && k <= 25 && h->alphabet <= HS_JR_MAX_ALPHABET && !h->knobs.no_join_r &&
             (h->knobs.force_join_r || share < 0.0 || share >= 0.5 || m.resident_age >= 64);
+  // Queries that are k-mers, k = 21..25, 4-column rows: the FP6 form of the query-streaming kernel (its bound is a
+  // table over residue PAIRS, so centres that are no k-mers have none).  query_batch builds the member records.
+  p.f6 = (p.self_codes || p.ext_codes) && !p.wide && k >= 21 && k <= 25 && h->alphabet <= 32 && h->PW == 1 &&
+         h->join6_tables_ok && !h->knobs.no_join_f6 && h->rec6_state >= 0;
   // No host round trip when the int8 join takes every segment and the previous batch left a
   // capacity hint: the item count stays on the device (item_off[nqs]); join legality and the
   // capacity are checked with the batch's final read-back, a violation repeats the batch the
@@ -2367,6 +2410,11 @@ struct Batch {
 static hipError_t launch_qrows(hs_handle* h, const BatchPlan& p, const Batch& b, hipStream_t s) {
   const int k = (int)h->p.k;
   uint32_t* const d_unsafe = h->counters.as<uint32_t>() + 8;
+  if (p.f6) {  // FP6 rows behind the int8 rows' place; the int8 rows only where the resident kernel reads them
+    hipError_t e = hs_launch_qprep6_codes(b.qcodes, b.nq, k, b.r2, h->jtab6.p, h->c16.as<char>() + (size_t)b.nq * 128,
+                                          s, b.radii);
+    if (e != hipSuccess || !p.use_r) return e;
+  }
   if (p.self_codes || p.ext_codes)  // (no second row: these batches' survivors are refined from the codes)
     return hs_launch_qprep8_codes(b.qcodes, b.nq, k, p.wide, b.r2, h->coords.as<double>(), h->jtab8.p,
                                   h->jtab8.as<char>() + 1024, h->jtab8.as<char>() + 1536, h->jtab8.as<float>() + 128,
@@ -2377,8 +2425,17 @@ static hipError_t launch_qrows(hs_handle* h, const BatchPlan& p, const Batch& b,
   return hs_launch_qprep(b.centers, b.nq, k, b.r2, h->c16.p, d_unsafe, s, b.radii);
 }
 
+// Where the FP6 rows of a batch sit in segment order: behind the room of its int8 rows in c16s
+static char* c6t_of(hs_handle* h, const Batch& b) { return h->c16s.as<char>() + ((size_t)b.nql + 64) * 128; }
+
 // The query rows gathered into segment order (c16s)
 static hipError_t gather_qrows(hs_handle* h, const BatchPlan& p, const Batch& b) {
+  if (p.f6) {
+    hipError_t e = hs_launch_gather_c8t(h->c16.as<char>() + (size_t)b.nq * 128, h->sorted_ql.as<uint32_t>(),
+                                        h->seg_qoff.as<uint32_t>(), h->seg_of.as<uint32_t>(), b.nqs, (int)h->p.L,
+                                        (int)h->p.k, 0, c6t_of(h, b), h->stream, hs_join6_row_pieces());
+    if (e != hipSuccess || !p.use_r) return e;
+  }
   if (p.use_i8)
     return hs_launch_gather_c8t(h->c16.p, h->sorted_ql.as<uint32_t>(), h->seg_qoff.as<uint32_t>(),
                                 h->seg_of.as<uint32_t>(), b.nqs, (int)h->p.L, (int)h->p.k, p.wide, h->c16s.p, h->stream);
@@ -2654,10 +2711,19 @@ static hs_status launch_filters(hs_handle* h, const BatchPlan& p, const Batch& b
     // (d_cnt + 40 .. 47: the per-XCD chunk counters)
     const uint64_t tile_bytes = (uint64_t)b.nqs * (uint64_t)hs_join8_row_bytes(k, p.wide);
     const uint32_t xcd_run = p.xcd_run >= 0 ? (uint32_t)p.xcd_run : (tile_bytes > (64ull << 20) ? 128u : 0u);
-    HS_HIP(h, hs_launch_join8w(h->item_desc.as<uint4>(), b.n_items, h->tabs.t[0].packed, rec8, h->c16s.p, rows, k,
-                               p.wide, d_cnt, prov_cap, h->prov.as<uint2>(), d_cnt + 32, join_blocks,
-                               p.use_r ? d_split : (p.async_items ? h->item_off.as<uint32_t>() + b.nqs : nullptr),
-                               h->hist.pairs_per_item, xcd_run, h->stream, h->knobs.join_chunk));
+    const uint32_t* const d_n_items =
+        p.use_r ? d_split : (p.async_items ? h->item_off.as<uint32_t>() + b.nqs : nullptr);
+    if (p.f6)
+      HS_HIP(h, hs_launch_join6x(h->item_desc.as<uint4>(), b.n_items, h->tabs.t[0].packed, h->t_rec6.as<uint4>(),
+                                 c6t_of(h, b), h->jtab6.p, d_cnt, prov_cap, h->prov.as<uint2>(), d_cnt + 32,
+                                 join_blocks, d_n_items,
+                                 hs_join8_chunk_items(b.n_items, join_blocks, h->hist.pairs_per_item,
+                                                      h->knobs.join_chunk),
+                                 xcd_run, h->stream));
+    else
+      HS_HIP(h, hs_launch_join8w(h->item_desc.as<uint4>(), b.n_items, h->tabs.t[0].packed, rec8, h->c16s.p, rows, k,
+                                 p.wide, d_cnt, prov_cap, h->prov.as<uint2>(), d_cnt + 32, join_blocks, d_n_items,
+                                 h->hist.pairs_per_item, xcd_run, h->stream, h->knobs.join_chunk));
     if (p.use_r)
       HS_HIP(h, hs_launch_join8r(h->item_desc.as<uint4>(), b.n_items, d_split, h->tabs.t[0].packed,
                                  h->t_rho.as<uint32_t>(), h->c16s.p, rows, h->alphabet, d_cnt, prov_cap,
@@ -2874,6 +2940,8 @@ static void account_batch(hs_handle* h, const BatchPlan& p, Batch& b) {
   h->prof.candidates += cand_total;
   h->prof.join_batches += b.n_items ? 1 : 0;
   h->prof.join_i8_batches += (b.n_items && p.use_i8) ? 1 : 0;
+  // (an FP6 batch counts as an int8 one as well, with the same depth-128 row: what is priced is the GEMM)
+  h->prof.join_f6_batches += (b.n_items && p.use_i8 && p.f6) ? 1 : 0;
   if (b.n_items && p.use_i8) {
     h->prof.join_row_bytes = (uint32_t)hs_join8_row_bytes((int)h->p.k, p.wide);
     h->prof.join_wide = (uint32_t)p.wide;
@@ -2955,6 +3023,7 @@ static hs_status query_batch(hs_handle* h, const QueryCall& c, uint32_t nq, uint
   if (c.brute) return brute_batch(h, c, nq, q_base, n_hits);
   for (bool allow_async = true;; allow_async = false) {
     BatchPlan p = plan_batch(h, c, nq, allow_async, bout != nullptr);
+    if (p.f6 && !ensure_rec6(h)) p.f6 = false;
     const uint32_t nql = nq * (uint32_t)h->p.L;
     Batch b{nq, q_base, nql, nql, c.R * c.R, c.centers, d_cand};
     b.radii = c.radii;
@@ -3365,6 +3434,7 @@ static void add_profile(hs_profile& a, const hs_profile& b) {
   a.join_pairs += b.join_pairs;
   a.join_pairs_issued += b.join_pairs_issued;
   a.join_i8_batches += b.join_i8_batches;
+  a.join_f6_batches += b.join_f6_batches;
   a.hash_values += b.hash_values;
   a.hash_flagged += b.hash_flagged;
   a.join_row_bytes = b.join_row_bytes;

@@ -796,11 +796,28 @@ hipError_t hs_launch_refine_codes(const hs_tables_dev& tabs, const uint2* d_prov
                                   uint2* d_out, uint32_t* d_out_count, hipStream_t s);
 hipError_t hs_launch_gather_c8t(const void* d_c8, const uint32_t* d_sorted_ql, const uint32_t* d_seg_qoff,
                                 const uint32_t* d_seg_of, uint32_t nql, int L, int k, int wide, void* d_out,
-                                hipStream_t s);
+                                hipStream_t s, int pieces = 0 /* 16-byte pieces of a row; 0: the int8 row of k, wide */);
 // bytes of a quantised int8 row (32 per k-step: 128 for k <= 25, 192 for k <= 41 and for wide rows,
 // 256 for k <= 50) and the members of one work item of the wave-independent int8 join (128 / 64)
 int hs_join8_row_bytes(int k, int wide);
 uint32_t hs_join8_members_per_item(int k, int wide);
+uint32_t hs_join8_chunk_items(uint32_t n_items, int n_blocks, double pairs_per_item, uint32_t chunk);
+// hs_join6.hip: the FP6 (e2m3) form of the join for queries that are k-mers, k = 21..25, 4-column rows.
+// d_tab6: hs_join6_table_bytes() bytes (hs_j6_dev); query rows of hs_join6_row_pieces() 16-byte pieces, gathered
+// by hs_launch_gather_c8t with that piece count; member records (16 bytes per bucket entry) parallel to the
+// bucket-ordered packed copy.  G = items per counter access (hs_join8_chunk_items).
+size_t hs_join6_table_bytes();
+size_t hs_join6_ok_offset();  // of the int32 that says the tables are usable
+int hs_join6_row_pieces();
+hipError_t hs_launch_jtables6(const double* d_coords, int alphabet, void* d_tab6, hipStream_t s);
+hipError_t hs_launch_gather_rec6(const uint4* d_packed_all, const uint32_t* d_ids_sorted, uint32_t n, int k,
+                                 const void* d_tab6, uint4* d_out_rec, hipStream_t s);
+hipError_t hs_launch_qprep6_codes(const uint8_t* d_qcodes, uint32_t nq, int k, double r2, const void* d_tab6,
+                                  void* d_c6, hipStream_t s, const double* d_radii = nullptr);
+hipError_t hs_launch_join6x(const uint4* d_desc, uint32_t n_items, const uint4* d_packed_base,
+                            const uint4* d_rec_base, const void* d_c6t, const void* d_tab6, uint32_t* d_prov_count,
+                            uint32_t prov_cap, uint2* d_prov, uint32_t* d_item_counter, int n_blocks,
+                            const uint32_t* d_n_items, uint32_t G, uint32_t xcd_run, hipStream_t s);
 hipError_t hs_launch_join8w(const uint4* d_desc, uint32_t n_items, const uint4* d_packed_base,
                             const uint4* d_rec_base, const void* d_c8t, const void* d_tab8, int k, int wide,
                             uint32_t* d_prov_count, uint32_t prov_cap, uint2* d_prov,

@@ -1,0 +1,647 @@
+// hs_join6.hip -- the bucket-join filter for queries that are k-mers (k = 21..25, 4-column rows) on FP6 MFMA:
+// v_mfma_f32_16x16x128_f8f6f4 with e2m3 operands does the whole depth-128 row of a 16 x 16 tile in ONE
+// instruction where hs_join8x_kernel issues two v_mfma_i32_16x16x64_i8.
+//
+// The bound and its exactness: hs_join6_tables.h.  Here: the row layouts and the kernels.
+//
+// K layout (128 six-bit elements = 4 lane quarters x 32 elements = 4 x 24 bytes).  The operand of lane
+// (n = lane & 15, q = lane >> 4) is row / column n, elements 32 q .. 32 q + 31, element i at bit 6 i of the
+// lane's 192 bits (hs_join6_selftest checks this map and the accumulation with exact data).  Element 4 p + j =
+// coordinate j of position p: quarter q < 3 holds positions 8 q .. 8 q + 7, quarter 3 position 24 and 28 spare
+// slots.  Slots 0..16 of those carry -(rho - rho0): on the member side digits (hs_j6_record: 15 coarse, one
+// medium, one fine), on the query side the constant factors 7.5 / 0.5 / 0.125; slots 17..27 are zero.
+//
+// Member side: quarters 0..2 are built per work item from the packed k-mer through a pair table in LDS
+// (entry r1 << 5 | r0 = the 48 bits of two residues: four lookups per member and lane), quarter 3 IS the
+// member's 16-byte record (t_rec6, built on the first batch that can use it) + 8 zero bytes.
+//
+// Query side: a row of 112 bytes = 7 pieces of 16: piece q = dwords 0..3 of quarter q; piece 4 + (q >> 1),
+// bytes 8 (q & 1) .. + 7 = dwords 4, 5 of quarter q; piece 6 = the float C = -(gamma + rho0), then zeros.
+// The rows are gathered into tile-fragment order by hs_gather_c8t_kernel with 7 pieces per row.  C is the
+// MFMA's C operand: the accumulator's column is the lane's query, so it is one value per lane and column tile
+// and costs no slot.  Encoding and range of C: a multiple of 2^-6, |C| <= 2^17 (values beyond are clamped to
+// +-2^17, which changes nothing: the other terms stay below 2^13, so such a query passes or fails every member
+// either way); every partial sum is then a multiple of 2^-6 below 2^18 + 2^13: exact in fp32.  The filter
+// passes a pair iff the accumulator's sign bit is clear.
+#include <stddef.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "hs_internal.h"
+#include "hs_join6_tables.h"
+
+namespace {
+
+typedef int intx6 __attribute__((ext_vector_type(6)));
+typedef int intx8 __attribute__((ext_vector_type(8)));
+typedef float floatx4 __attribute__((ext_vector_type(4)));
+
+constexpr uint32_t JRES = 256;   // survivor slots a wave reserves per counter access (as hs_join8.hip)
+constexpr int PIECES = 7;        // 16-byte pieces of a query row
+
+__device__ __forceinline__ void close_reservation(uint2* __restrict__ prov, uint32_t res_base, uint32_t res_used,
+                                                  uint32_t prov_cap, int lane) {
+  for (uint32_t i = res_used + (uint32_t)lane; i < JRES; i += 64u)
+    if (res_base + i < prov_cap) prov[res_base + i] = make_uint2(0xffffffffu, 0u);
+}
+
+__device__ __forceinline__ uint4 uniform4(const uint4 v) {
+  return make_uint4(__builtin_amdgcn_readfirstlane(v.x), __builtin_amdgcn_readfirstlane(v.y),
+                    __builtin_amdgcn_readfirstlane(v.z), __builtin_amdgcn_readfirstlane(v.w));
+}
+
+// The tile product of the kernel and of its self-test: D = A (16 x 128, e2m3) x B (128 x 16, e2m3) + C.
+// SCALE = 0 in both block-scale operands selects the unscaled v_mfma_f32_16x16x128_f8f6f4 (one instruction).
+template <int SCALE = 0>
+__device__ __forceinline__ floatx4 tile_mfma6(const intx6 a, const intx6 b, const floatx4 c) {
+  const intx8 a8 = __builtin_shufflevector(a, a, 0, 1, 2, 3, 4, 5, -1, -1);
+  const intx8 b8 = __builtin_shufflevector(b, b, 0, 1, 2, 3, 4, 5, -1, -1);
+  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a8, b8, c, 2, 2, 0, SCALE, 0, SCALE);
+}
+
+// ------------------------------------------------------------------------------------ tables
+__global__ void hs_jtables6_kernel(const double* __restrict__ coords, int alphabet, hs_j6_dev* __restrict__ T) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) hs_j6_compute(coords, alphabet, T, nullptr, nullptr);
+}
+
+// ------------------------------------------------------------------------------------ member records
+__global__ __launch_bounds__(256) void hs_gather_rec6_kernel(const uint4* __restrict__ packed_all,
+                                                             const uint32_t* __restrict__ ids, uint32_t n, int k,
+                                                             const hs_j6_dev* __restrict__ T,
+                                                             uint4* __restrict__ out_rec) {
+  __shared__ double sR[32];
+  __shared__ uint32_t sBits[32];
+  if (threadIdx.x < 32) {
+    sR[threadIdx.x] = T->r[threadIdx.x];
+    sBits[threadIdx.x] = T->bits[threadIdx.x];
+  }
+  __syncthreads();
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= n) return;
+  const uint4 pk = packed_all[ids[t]];  // (k <= 25: one packed word)
+  const uint32_t w[4] = {pk.x, pk.y, pk.z, pk.w};
+  double rho = 0.0;
+  uint32_t pos24 = 0;
+#pragma unroll
+  for (int p = 0; p < 25; ++p) {
+    const int bit = 5 * p, wi = bit >> 5, sh = bit & 31;
+    uint32_t c = w[wi] >> sh;
+    if (sh > 27) c |= w[wi + 1] << (32 - sh);
+    c &= 31u;
+    if (p < k) {
+      rho += sR[c];
+      if (p == 24) pos24 = sBits[c];
+    }
+  }
+  uint32_t rec[4];
+  hs_j6_record(rho, k, T->rpos64, pos24, rec, nullptr);
+  out_rec[t] = make_uint4(rec[0], rec[1], rec[2], rec[3]);
+}
+
+// ------------------------------------------------------------------------------------ query rows
+// One thread per query: the 96 bytes of codes (quarter 3 with the constant factors of the rho slots) and C.
+__global__ __launch_bounds__(256) void hs_qprep6_codes_kernel(const uint8_t* __restrict__ qcodes, uint32_t nq, int k,
+                                                              double r2_call, const hs_j6_dev* __restrict__ T,
+                                                              uint32_t* __restrict__ out,
+                                                              const double* __restrict__ radii) {
+  __shared__ double sR[32];
+  __shared__ uint32_t sBits[32];
+  if (threadIdx.x < 32) {
+    sR[threadIdx.x] = T->r[threadIdx.x];
+    sBits[threadIdx.x] = T->bits[threadIdx.x];
+  }
+  __syncthreads();
+  const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= nq) return;
+  const double r2 = hs_r2_of(radii, q, r2_call);
+  const uint8_t* code = qcodes + (uint64_t)q * k;
+  uint32_t W[4][6];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int i = 0; i < 6; ++i) W[a][i] = 0u;
+  hs_j6_query_consts(W[3]);
+  double sum_r = 0.0;
+#pragma unroll
+  for (int p = 0; p < 25; ++p) {
+    if (p < k) {
+      const uint32_t c = code[p] & 31u;
+      sum_r += sR[c];
+      const uint32_t b = sBits[c];
+      const int qu = p >> 3, bit = 24 * (p & 7), wi = bit >> 5, sh = bit & 31;
+      W[qu][wi] |= b << sh;
+      if (sh > 8) W[qu][wi + 1] |= b >> (32 - sh);
+    }
+  }
+  int64_t c64 = hs_j6_query_c64(sum_r, T->s2_half, r2, k, T->rpos64);
+  c64 = c64 > HS_J6_CMAX ? HS_J6_CMAX : c64 < -HS_J6_CMAX ? -HS_J6_CMAX : c64;
+  if (!(r2 == r2)) c64 = -HS_J6_CMAX;  // (a NaN radius: no hit)
+  uint32_t* row = out + (uint64_t)q * (PIECES * 4);
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) row[4 * a + i] = W[a][i];
+    row[16 + 4 * (a >> 1) + 2 * (a & 1)] = W[a][4];
+    row[16 + 4 * (a >> 1) + 2 * (a & 1) + 1] = W[a][5];
+  }
+  row[24] = __float_as_uint((float)c64 * (1.0f / 64.0f));
+  row[25] = row[26] = row[27] = 0u;
+}
+
+// ------------------------------------------------------------------------------------ join
+// Query tile of nr rows at segment-order row row0 (hs_gather_c8t_kernel: piece g of row j at g nr + j): lane (n, q)
+// takes the 24 bytes of quarter q and C of row 16 c + n for column tile c.  Rows past the end repeat the last one
+// (masked when survivors are written).
+__device__ __forceinline__ void load_btile6(intx6 (&B)[2], float (&C)[2], const uint4* __restrict__ c6t,
+                                            uint32_t row0, uint32_t nr, int lane) {
+  const char* t0 = reinterpret_cast<const char*>(c6t + (uint64_t)row0 * PIECES);
+  const uint32_t n = (uint32_t)lane & 15u, q = (uint32_t)lane >> 4;
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const uint32_t row = min(16u * (uint32_t)c + n, nr - 1u);
+    const uint4 hi = *reinterpret_cast<const uint4*>(t0 + (q * nr + row) * 16u);
+    const uint2 lo = *reinterpret_cast<const uint2*>(t0 + ((4u + (q >> 1)) * nr + row) * 16u + 8u * (q & 1u));
+    C[c] = *reinterpret_cast<const float*>(t0 + (6u * nr + row) * 16u);
+    B[c] = intx6{(int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w, (int)lo.x, (int)lo.y};
+  }
+}
+
+// One step of the sign test of a group's 32 accumulators (hs_join8.hip sign_step_x, on the floats' bit patterns:
+// a float is negative, or -0, exactly when its pattern is a negative int): the signed maximum on a tree of
+// three-input maxima, 16 steps; the result w[15] is negative iff no pair of the group passed.
+__device__ __forceinline__ void sign_step6(int g, const floatx4 (&acc)[4][2], int (&w)[16]) {
+  auto v = [&](int i) { return __float_as_int(acc[i >> 3][(i >> 2) & 1][i & 3]); };
+  if (g < 10) w[g] = max(max(v(3 * g), v(3 * g + 1)), v(3 * g + 2));
+  else if (g < 13) w[g] = max(max(w[3 * (g - 10)], w[3 * (g - 10) + 1]), w[3 * (g - 10) + 2]);
+  else if (g == 13) w[13] = max(max(w[9], v(30)), v(31));
+  else if (g == 14) w[14] = max(max(w[10], w[11]), w[12]);
+  else w[15] = max(w[13], w[14]);
+  asm volatile("" : "+v"(w[g]));
+}
+
+__device__ __forceinline__ uint32_t and_tree6(const floatx4 (&acc)[4][2]) {
+  uint32_t a = 0xffffffffu;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a &= __float_as_uint(acc[t][c][i]);
+  return a;
+}
+
+// Survivors of one group (row tiles T0 .. T0 + 3) against the 32 queries at segment-relative offset qc
+__device__ __forceinline__ void emit_survivors6(const floatx4 (&acc)[4][2], int T0, uint32_t qc, uint32_t qoff,
+                                                uint32_t q_end, uint32_t wbase, uint32_t M, uint32_t mstart,
+                                                int lane, uint32_t& res_base, uint32_t& res_used,
+                                                uint32_t* __restrict__ prov_count, uint32_t prov_cap,
+                                                uint2* __restrict__ prov) {
+  const uint32_t n = (uint32_t)lane & 15u, q = (uint32_t)lane >> 4;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const uint32_t any = __float_as_uint(acc[t][c][0]) & __float_as_uint(acc[t][c][1]) &
+                           __float_as_uint(acc[t][c][2]) & __float_as_uint(acc[t][c][3]);
+      if (!__ballot((int)any >= 0)) continue;  // no survivor in this 16 x 16 tile
+      uint32_t mask = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) mask |= (__float_as_int(acc[t][c][i]) >= 0 ? 1u : 0u) << i;
+      const uint32_t col = qc + 16u * (uint32_t)c + n;
+      if (!(col < q_end)) mask = 0u;
+      const uint32_t ql = HS_PROV_INDIRECT | (qoff + col);
+      while (__ballot(mask != 0)) {
+        uint32_t idx = 0;
+        bool pass = false;
+        if (mask) {
+          const int i = __ffs((int)mask) - 1;
+          mask &= mask - 1;
+          idx = wbase + (uint32_t)(16 * (T0 + t)) + 4u * q + (uint32_t)i;
+          pass = idx < M;
+        }
+        const unsigned long long m = __ballot(pass);
+        if (m) {
+          const uint32_t cnt = (uint32_t)__popcll(m);
+          if (res_used + cnt > JRES) {
+            close_reservation(prov, res_base, res_used, prov_cap, lane);
+            uint32_t base = 0;
+            if (lane == 0) base = hs_reserve_survivors(prov_count, (uint32_t)JRES);
+            res_base = __builtin_amdgcn_readfirstlane(base);
+            res_used = 0;
+          }
+          if (pass) {
+            const uint32_t o = res_base + res_used + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            if (o < prov_cap) prov[o] = make_uint2(ql, mstart + idx);
+          }
+          res_used += cnt;
+        }
+      }
+    }
+}
+
+// The structure of hs_join8x_kernel (work items of 128 members owned by one wave, chunks of items from a global
+// counter or from per-XCD runs, three query tiles in flight, accumulator halves X / Y with the sign test of one in
+// the gaps of the other's MFMAs, the same survivor list), with 8 + 8 MFMAs per 32 queries instead of 16 + 16 and two
+// steps of the sign test behind each.
+__global__ __launch_bounds__(256, 2) void hs_join6x_kernel(
+    const uint4* __restrict__ desc, uint32_t n_items, const uint4* __restrict__ packed_base,
+    const uint4* __restrict__ rec_base, const uint4* __restrict__ c6t, const hs_j6_dev* __restrict__ T,
+    uint32_t* __restrict__ prov_count, uint32_t prov_cap, uint2* __restrict__ prov,
+    uint32_t* __restrict__ item_counter, uint32_t G, const uint32_t* __restrict__ n_items_dev, uint32_t xcd_run) {
+  if (n_items_dev) n_items = min(n_items, __builtin_amdgcn_readfirstlane(*n_items_dev));
+  constexpr int RT = 8;  // row tiles of 16 members per wave
+  __shared__ uint2 sPair[1024];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n = lane & 15, q = lane >> 4;
+  for (int e = tid; e < 1024; e += 256) sPair[e] = T->pair[e];
+  __syncthreads();  // the only one: the table is read-only from here on
+  // (the dealing of chunks: as hs_join8x_kernel, where it is explained)
+  const uint32_t xcd_sh = 31u - (uint32_t)__builtin_clz(xcd_run | 1u), xcd_mask = (1u << xcd_sh) - 1u;
+  uint32_t victim = __builtin_amdgcn_s_getreg(6164) & 7u;  // hwreg(HW_REG_XCC_ID, 0, 4)
+  uint32_t tried = 0;
+  const uint32_t first_dynamic = gridDim.x * 4u * G;
+  auto chunk_item = [&](uint32_t v) -> uint32_t {
+    if (!xcd_run) return first_dynamic + v;
+    for (;;) {
+      const uint32_t c = ((((v >> xcd_sh) << 3) + victim) << xcd_sh) + (v & xcd_mask);
+      const uint64_t it = (uint64_t)c * G;
+      if (it < (uint64_t)n_items) return (uint32_t)it;
+      if (++tried == 8u) return 0xf0000000u;
+      victim = (victim + 1u) & 7u;
+      uint32_t j = 0;
+      if (lane == 0) j = atomicAdd(item_counter + 8 + victim, 1u);
+      v = __builtin_amdgcn_readfirstlane(j);
+    }
+  };
+#define HS_TAKE_CHUNK() (xcd_run ? atomicAdd(item_counter + 8 + victim, 1u) : atomicAdd(item_counter, G))
+  uint32_t item = (blockIdx.x * 4u + (uint32_t)wave) * G;
+  if (xcd_run) {
+    uint32_t first = 0;
+    if (lane == 0) first = HS_TAKE_CHUNK();
+    item = chunk_item(__builtin_amdgcn_readfirstlane(first));
+  }
+  if (item >= n_items) return;
+  uint32_t res_base = 0, res_used = JRES;
+  uint32_t next_chunk_v = 0;
+  if (lane == 0) next_chunk_v = HS_TAKE_CHUNK();
+  uint32_t pf_item = item, pf_chunk_end = min(item + G, n_items);
+#define HS_ADVANCE_PF()                                                                  \
+  {                                                                                      \
+    ++pf_item;                                                                           \
+    if (pf_item == pf_chunk_end) {                                                       \
+      pf_item = chunk_item(__builtin_amdgcn_readfirstlane(next_chunk_v));                \
+      pf_chunk_end = pf_item < n_items ? min(pf_item + G, n_items) : pf_item + G;        \
+      if (lane == 0 && pf_item < n_items) next_chunk_v = HS_TAKE_CHUNK();                \
+    }                                                                                    \
+  }
+  uint4 d0 = uniform4(desc[2 * (uint64_t)item]), d1 = uniform4(desc[2 * (uint64_t)item + 1]);
+  HS_ADVANCE_PF()
+  uint32_t next_item = pf_item;
+  uint4 nd0 = d0, nd1 = d1;
+  if (next_item < n_items) {
+    nd0 = uniform4(desc[2 * (uint64_t)next_item]);
+    nd1 = uniform4(desc[2 * (uint64_t)next_item + 1]);
+  }
+  // lanes of quarters 0..2: packed member 16 t + n; quarter 3: its record
+  uint4 mk[RT];
+  constexpr int NB = 3;  // query tiles in flight per wave: the one in use + two prefetched
+  constexpr uint32_t GQ = 32 * NB;
+  intx6 Bq[NB][2];
+  float Cq[NB][2];
+#define HS_LOAD_MEMBERS(D0)                                                              \
+  {                                                                                      \
+    const int64_t off_ = (int64_t)(((uint64_t)(D0).y << 32) | (uint64_t)(D0).x);         \
+    const uint4* src_ = (q == 3 ? rec_base : packed_base) + off_;                        \
+    const uint32_t idx_ = (D0).w * 128u + (uint32_t)n;                                   \
+    _Pragma("unroll") for (int t = 0; t < RT; ++t)                                       \
+      mk[t] = src_[min(idx_ + 16 * t, (D0).z - 1)];                                      \
+  }
+  const uint32_t skew = ((blockIdx.x * 4u + (uint32_t)wave) * 40503u) & 0xffffu;
+#define HS_N_GROUPS(D1) (((D1).z - (D1).y + GQ - 1u) / GQ)
+#define HS_FIRST_Q(D1) ((D1).y + GQ * ((skew * HS_N_GROUPS(D1)) >> 16))
+#define HS_LOAD_GROUP(ROW, Q0, QEND)                                                             \
+  _Pragma("unroll") for (int u = 0; u < NB; ++u) {                                               \
+    const uint32_t qu_ = (Q0) + 32u * u < (QEND) ? (Q0) + 32u * u : (Q0);                        \
+    load_btile6(Bq[u], Cq[u], c6t, (ROW) + qu_, min(32u, (QEND) - qu_), lane);                   \
+  }
+  HS_LOAD_MEMBERS(d0)
+  {
+    const uint32_t q0 = HS_FIRST_Q(d1);
+    HS_LOAD_GROUP(d1.x, q0, d1.z)
+  }
+  // bits 40 q .. 40 q + 39 of the packed word = positions 8 q .. 8 q + 7 of quarter q < 3: dwords (q, q + 1)
+  // shifted down by 8 q (quarter 3 computes on its record and discards the result)
+  const uint32_t bs = 8u * (uint32_t)min(q, 2);
+  while (true) {
+    const uint32_t M = d0.z, mt = d0.w;
+    const uint32_t qoff = d1.x, q_begin = d1.y, q_end = d1.z, mstart = d1.w;
+    const uint32_t wbase = mt * 128u;
+    const bool has_next = next_item < n_items;
+    HS_ADVANCE_PF()  // pf_item = the item after next
+    uint4 nnd0 = nd0, nnd1 = nd1;
+    if (pf_item < n_items) {
+      nnd0 = uniform4(desc[2 * (uint64_t)pf_item]);
+      nnd1 = uniform4(desc[2 * (uint64_t)pf_item + 1]);
+    }
+    // ---- A operands of the item's 128 members
+    intx6 A[RT];
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+      const uint4 m = mk[t];
+      const uint32_t a = q == 0 ? m.x : q == 1 ? m.y : m.z, b = q == 0 ? m.y : q == 1 ? m.z : m.w;
+      const uint32_t lo = __funnelshift_r(a, b, bs), hi = b >> bs;
+      const uint2 e0 = sPair[lo & 1023u], e1 = sPair[(lo >> 10) & 1023u];
+      const uint2 e2 = sPair[(lo >> 20) & 1023u], e3 = sPair[__funnelshift_r(lo, hi, 30) & 1023u];
+      const intx6 lk = intx6{(int)e0.x, (int)(e0.y | (e1.x << 16)), (int)__funnelshift_r(e1.x, e1.y, 16),
+                             (int)e2.x, (int)(e2.y | (e3.x << 16)), (int)__funnelshift_r(e3.x, e3.y, 16)};
+      const intx6 own = intx6{(int)m.x, (int)m.y, (int)m.z, (int)m.w, 0, 0};
+      A[t] = q == 3 ? own : lk;
+    }
+    HS_LOAD_MEMBERS(nd0)
+    floatx4 accX[4][2], accY[4][2];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int c = 0; c < 2; ++c) accY[t][c] = __builtin_nondeterministic_value(accY[t][c]);
+    bool y_live = false;
+    uint32_t prev_qc = q_begin;
+    const uint32_t n_groups = HS_N_GROUPS(d1);
+    uint32_t qc0 = HS_FIRST_Q(d1);
+    auto do_group = [&](uint32_t gi) {
+      uint32_t nrow = qoff, nq0 = qc0 + GQ, nqend = q_end;
+      if (nq0 >= q_end) nq0 = q_begin;
+      if (gi + 1 == n_groups) {
+        nrow = nd1.x;
+        nq0 = HS_FIRST_Q(nd1);
+        nqend = nd1.z;
+      }
+#pragma unroll
+      for (int u = 0; u < NB; ++u) {
+        const uint32_t qc = qc0 + 32u * (uint32_t)u;
+        intx6 (&B)[2] = Bq[u];
+        if (u == 0 || qc < q_end) {
+          const floatx4 Cv[2] = {floatx4{Cq[u][0], Cq[u][0], Cq[u][0], Cq[u][0]},
+                                 floatx4{Cq[u][1], Cq[u][1], Cq[u][1], Cq[u][1]}};
+          // ---- phase 1: X <- row tiles 0..3 x B + C, beside the sign test of Y (previous query tile)
+          int wY[16];
+#pragma unroll
+          for (int g = 0; g < 8; ++g) {
+            const int t = g >> 1, c = g & 1;
+            accX[t][c] = tile_mfma6(A[t], B[c], Cv[c]);
+            if (y_live) {  // (the item's first tile: Y holds nothing yet)
+              sign_step6(2 * g, accY, wY);
+              sign_step6(2 * g + 1, accY, wY);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          const uint32_t sY = y_live ? (uint32_t)wY[15] : 0x80000000u;
+          if (y_live && __ballot((int)sY >= 0))
+            emit_survivors6(accY, 4, prev_qc, qoff, q_end, wbase, M, mstart, lane, res_base, res_used, prov_count,
+                            prov_cap, prov);
+          y_live = true;
+          // ---- phase 2: Y <- row tiles 4..7 x B + C, beside the sign test of X
+          int wX[16];
+#pragma unroll
+          for (int g = 0; g < 8; ++g) {
+            const int t = g >> 1, c = g & 1;
+            accY[t][c] = tile_mfma6(A[4 + t], B[c], Cv[c]);
+            sign_step6(2 * g, accX, wX);
+            sign_step6(2 * g + 1, accX, wX);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          const uint32_t sX = (uint32_t)wX[15];
+          if (__ballot((int)sX >= 0))
+            emit_survivors6(accX, 0, qc, qoff, q_end, wbase, M, mstart, lane, res_base, res_used, prov_count,
+                            prov_cap, prov);
+          prev_qc = qc;
+        }
+        const uint32_t nb = nq0 + 32u * (uint32_t)u < nqend ? nq0 + 32u * (uint32_t)u : nq0;
+        load_btile6(B, Cq[u], c6t, nrow + nb, min(32u, nqend - nb), lane);
+      }
+      qc0 = nq0;
+    };
+    do_group(0);
+    for (uint32_t gi = 1; gi < n_groups; ++gi) do_group(gi);
+    {  // the item's last Y group
+      const uint32_t sY = and_tree6(accY);
+      if (__ballot((int)sY >= 0))
+        emit_survivors6(accY, 4, prev_qc, qoff, q_end, wbase, M, mstart, lane, res_base, res_used, prov_count,
+                        prov_cap, prov);
+    }
+    if (!has_next) break;
+    item = next_item;
+    next_item = pf_item;
+    d0 = nd0;
+    d1 = nd1;
+    nd0 = nnd0;
+    nd1 = nnd1;
+  }
+#undef HS_ADVANCE_PF
+#undef HS_TAKE_CHUNK
+#undef HS_LOAD_GROUP
+#undef HS_N_GROUPS
+#undef HS_LOAD_MEMBERS
+#undef HS_FIRST_Q
+  close_reservation(prov, res_base, res_used, prov_cap, lane);
+}
+
+// ------------------------------------------------------------------------------------ self-test
+// Rows on the e2m3 grid, thresholds on the 2^-6 grid, through tile_mfma6 with the lane map the kernel relies on;
+// every accumulator against int64 arithmetic.  One wave per case:
+//   0  every element +7.5 on both sides, C = +2^17               (the largest sum, the largest threshold)
+//   1  A +7.5, B -7.5, C = -2^17
+//   2  A alternating +-7.5 along k, B +7.5, C = 2^17 - 2^-6       (cancellation beside a large threshold)
+//   3  A alternating +-7.5 along k and rows, B alternating along k, C = -(2^17 - 2^-6)
+//   4+ pseudo-random codes (asymmetric in row, column and k: a wrong lane map cannot pass), C random in +-2^17;
+//      odd cases keep position 24 / the slots' shape: elements 117..127 zero
+__device__ __forceinline__ uint32_t st_hash(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+__device__ __forceinline__ uint32_t st_code(uint32_t cs, uint32_t side, uint32_t row, uint32_t k) {
+  const uint32_t MAXP = 31u, MAXN = 63u;  // +7.5, -7.5
+  if (cs == 0) return MAXP;
+  if (cs == 1) return side ? MAXN : MAXP;
+  if (cs == 2) return side ? MAXP : ((k & 1u) ? MAXN : MAXP);
+  if (cs == 3) return ((k + (side ? 0u : row)) & 1u) ? MAXN : MAXP;
+  if ((cs & 1u) && k >= 117u) return 0u;
+  return st_hash(cs * 0x9e3779b9u + side * 0x85ebca6bu + row * 131u + k * 2654435761u) & 63u;
+}
+__device__ __forceinline__ int32_t st_c64(uint32_t cs, uint32_t col) {
+  const int32_t big = 1 << 23;  // 2^17 in 64ths
+  if (cs == 0) return big;
+  if (cs == 1) return -big;
+  if (cs == 2) return big - 1;
+  if (cs == 3) return -(big - 1);
+  return (int32_t)(st_hash(cs * 977u + col * 0x27d4eb2fu) % (uint32_t)(2 * big + 1)) - big;
+}
+template <int SCALE>
+__global__ __launch_bounds__(64) void hs_join6_selftest_kernel(uint32_t* __restrict__ mismatches,
+                                                               uint32_t* __restrict__ first_bad) {
+  const uint32_t cs = blockIdx.x, lane = threadIdx.x & 63u, n = lane & 15u, q = lane >> 4;
+  uint32_t a[6] = {0, 0, 0, 0, 0, 0}, b[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int i = 0; i < 32; ++i) {
+    const uint32_t ca = st_code(cs, 0u, n, 32u * q + (uint32_t)i), cb = st_code(cs, 1u, n, 32u * q + (uint32_t)i);
+    const int bit = 6 * i, wi = bit >> 5, sh = bit & 31;
+    a[wi] |= ca << sh;
+    b[wi] |= cb << sh;
+    if (sh > 26) {
+      a[wi + 1] |= ca >> (32 - sh);
+      b[wi + 1] |= cb >> (32 - sh);
+    }
+  }
+  const float cf = (float)st_c64(cs, n) * (1.0f / 64.0f);
+  const floatx4 d = tile_mfma6<SCALE>(intx6{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)a[4], (int)a[5]},
+                                      intx6{(int)b[0], (int)b[1], (int)b[2], (int)b[3], (int)b[4], (int)b[5]},
+                                      floatx4{cf, cf, cf, cf});
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t row = 4u * q + (uint32_t)i;  // result register i of lane (n, q) = row 4 q + i, column n
+    long long ref = (long long)st_c64(cs, n);
+    for (uint32_t k = 0; k < 128u; ++k)
+      ref += (long long)hs_e2m3_eighths(st_code(cs, 0u, row, k)) * (long long)hs_e2m3_eighths(st_code(cs, 1u, n, k));
+    const double got = (double)d[i] * 64.0;
+    if (!(got == (double)ref)) {
+      if (atomicAdd(mismatches, 1u) == 0u) {
+        first_bad[0] = cs;
+        first_bad[1] = lane * 4u + (uint32_t)i;
+        first_bad[2] = __float_as_uint(d[i]);
+        first_bad[3] = (uint32_t)(int32_t)ref;
+      }
+    }
+  }
+}
+
+inline unsigned blocks_for(uint64_t n, unsigned per = 256) { return (unsigned)((n + per - 1) / per); }
+
+}  // namespace
+
+hipError_t hs_launch_jtables6(const double* d_coords, int alphabet, void* d_tab6, hipStream_t s) {
+  hs_jtables6_kernel<<<1, 64, 0, s>>>(d_coords, alphabet, (hs_j6_dev*)d_tab6);
+  return hipGetLastError();
+}
+
+size_t hs_join6_table_bytes() { return sizeof(hs_j6_dev); }
+size_t hs_join6_ok_offset() { return offsetof(hs_j6_dev, ok); }
+int hs_join6_row_pieces() { return PIECES; }
+
+hipError_t hs_launch_gather_rec6(const uint4* d_packed_all, const uint32_t* d_ids_sorted, uint32_t n, int k,
+                                 const void* d_tab6, uint4* d_out_rec, hipStream_t s) {
+  if (!n) return hipSuccess;
+  hs_gather_rec6_kernel<<<blocks_for(n), 256, 0, s>>>(d_packed_all, d_ids_sorted, n, k, (const hs_j6_dev*)d_tab6,
+                                                      d_out_rec);
+  return hipGetLastError();
+}
+
+hipError_t hs_launch_qprep6_codes(const uint8_t* d_qcodes, uint32_t nq, int k, double r2, const void* d_tab6,
+                                  void* d_c6, hipStream_t s, const double* d_radii) {
+  if (!nq) return hipSuccess;
+  hs_qprep6_codes_kernel<<<blocks_for(nq), 256, 0, s>>>(d_qcodes, nq, k, r2, (const hs_j6_dev*)d_tab6,
+                                                        (uint32_t*)d_c6, d_radii);
+  return hipGetLastError();
+}
+
+hipError_t hs_launch_join6x(const uint4* d_desc, uint32_t n_items, const uint4* d_packed_base,
+                            const uint4* d_rec_base, const void* d_c6t, const void* d_tab6, uint32_t* d_prov_count,
+                            uint32_t prov_cap, uint2* d_prov, uint32_t* d_item_counter, int n_blocks,
+                            const uint32_t* d_n_items, uint32_t G, uint32_t xcd_run, hipStream_t s) {
+  if (!n_items) return hipSuccess;
+  hs_join6x_kernel<<<n_blocks, 256, 0, s>>>(d_desc, n_items, d_packed_base, d_rec_base, (const uint4*)d_c6t,
+                                            (const hs_j6_dev*)d_tab6, d_prov_count, prov_cap, d_prov, d_item_counter,
+                                            G, d_n_items, xcd_run);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------ exported
+extern "C" {
+
+// The FP6 filter's tables from a coordinate table ([alphabet][8] doubles), on the host: no GPU needed.
+// codes [32][4] six-bit e2m3 codes, e / r [32] doubles, pair [1024][2] dwords (hs_j6_dev::pair); *s the scale.
+HS_API hs_status hs_join6_tables(const double* coords, uint32_t alphabet, double* s, uint8_t* codes, double* e,
+                                 double* r, uint32_t* pair) {
+  if (!coords || alphabet < 1 || alphabet > 32) return HS_ERR_INVALID;
+  std::vector<hs_j6_dev> T(1);
+  double ee[32], ss = 0.0;
+  hs_j6_compute(coords, (int)alphabet, &T[0], ee, &ss);
+  if (!T[0].ok) return HS_ERR_INVALID;
+  if (s) *s = ss;
+  for (int a = 0; a < 32; ++a) {
+    if (codes)
+      for (int j = 0; j < 4; ++j) codes[a * 4 + j] = (uint8_t)((T[0].bits[a] >> (6 * j)) & 63u);
+    if (e) e[a] = ee[a];
+    if (r) r[a] = T[0].r[a];
+  }
+  if (pair) memcpy(pair, T[0].pair, sizeof(T[0].pair));
+  return HS_OK;
+}
+
+// The thresholds the kernels carry for n k-mers (codes [n][k]) at squared radii r2[n], in units of 2^-6:
+// rho64 = what a member's record stands for, c64 = a query's C operand (-(gamma + rho0)), rho0_64 = k * rpos64;
+// rec (optional) [n][4] the member records.  The filter value of member x and query c is
+// sum_p S[x_p][c_p] - (rho64[x] - rho0_64) / 64 + c64[c] / 64.  Host only.
+HS_API hs_status hs_join6_thresholds(const double* coords, uint32_t alphabet, const uint8_t* kmers, uint64_t n,
+                                     uint32_t k, const double* r2, int64_t* rho64, int64_t* c64, int64_t* rho0_64,
+                                     uint32_t* rec) {
+  if (!coords || alphabet < 1 || alphabet > 32 || !kmers || k < 1 || k > 25) return HS_ERR_INVALID;
+  std::vector<hs_j6_dev> T(1);
+  hs_j6_compute(coords, (int)alphabet, &T[0], nullptr, nullptr);
+  if (!T[0].ok) return HS_ERR_INVALID;
+  if (rho0_64) *rho0_64 = (int64_t)k * T[0].rpos64;
+  for (uint64_t i = 0; i < n; ++i) {
+    double sum = 0.0;
+    uint32_t pos24 = 0;
+    for (uint32_t p = 0; p < k; ++p) {
+      const uint32_t c = kmers[i * k + p];
+      if (c >= alphabet) return HS_ERR_INVALID;
+      sum += T[0].r[c];
+      if (p == 24) pos24 = T[0].bits[c];
+    }
+    uint32_t w[4];
+    int64_t enc = 0;
+    hs_j6_record(sum, (int)k, T[0].rpos64, pos24, w, &enc);
+    if (rho64) rho64[i] = enc;
+    if (rec) memcpy(rec + 4 * i, w, 16);
+    if (c64) {
+      int64_t c = hs_j6_query_c64(sum, T[0].s2_half, r2 ? r2[i] : 0.0, (int)k, T[0].rpos64);
+      c64[i] = c > HS_J6_CMAX ? HS_J6_CMAX : c < -HS_J6_CMAX ? -HS_J6_CMAX : c;
+    }
+  }
+  return HS_OK;
+}
+
+// GPU: the kernel's tile product against int64 arithmetic on rows at the format's extremes (see the kernel).
+// variant 0: the product as hs_join6x_kernel issues it; 1: the same with explicit block scales of 2^0.
+// *mismatches = accumulators that differ (0 = exact); first_bad (optional, 4 words): case, lane * 4 + register,
+// the float's bits, the expected value in 64ths.
+HS_API hs_status hs_join6_selftest(int device, int variant, uint64_t* mismatches, uint32_t* first_bad) {
+  if (!mismatches || variant < 0 || variant > 1) return HS_ERR_INVALID;
+  if (hipSetDevice(device) != hipSuccess) return HS_ERR_HIP;
+  uint32_t* d = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&d), 32) != hipSuccess) return HS_ERR_HIP;
+  uint32_t host[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  hipError_t e = hipMemset(d, 0, 32);
+  if (e == hipSuccess) {
+    constexpr int CASES = 64;
+    if (variant == 0) hs_join6_selftest_kernel<0><<<CASES, 64>>>(d, d + 1);
+    else hs_join6_selftest_kernel<127><<<CASES, 64>>>(d, d + 1);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(host, d, 32, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e != hipSuccess) return HS_ERR_HIP;
+  *mismatches = host[0];
+  if (first_bad) memcpy(first_bad, host + 1, 16);
+  return HS_OK;
+}
+
+}  // extern "C"

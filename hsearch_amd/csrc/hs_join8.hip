@@ -2337,11 +2337,22 @@ uint32_t hs_join8_members_per_item(int k, int wide) {
 
 hipError_t hs_launch_gather_c8t(const void* d_c8, const uint32_t* d_sorted_ql, const uint32_t* d_seg_qoff,
                                 const uint32_t* d_seg_of, uint32_t nql, int L, int k, int wide, void* d_out,
-                                hipStream_t s) {
+                                hipStream_t s, int pieces) {
   if (!nql) return hipSuccess;
   hs_gather_c8t_kernel<<<blocks_for((uint64_t)nql * 8), 256, 0, s>>>((const int8_t*)d_c8, d_sorted_ql, d_seg_qoff, d_seg_of, nql,
-                                                       L, 2 * ks_of(k, wide != 0), (uint4*)d_out);
+                                                       L, pieces ? pieces : 2 * ks_of(k, wide != 0), (uint4*)d_out);
   return hipGetLastError();
+}
+
+// Items per access to the item counters for a launch of n_blocks x 4 waves (the rules: hs_launch_join8w)
+uint32_t hs_join8_chunk_items(uint32_t n_items, int n_blocks, double pairs_per_item, uint32_t chunk) {
+  const uint32_t n_waves = (uint32_t)n_blocks * 4u;
+  uint32_t g_max = 8u;
+  if (pairs_per_item > 0.0) g_max = (uint32_t)std::max(8.0, std::min(48.0, 7.0e5 / pairs_per_item));
+  // up to 8: at least 8 chunks per wave; beyond: at least 64 (the balance at the end is paid in
+  // chunks: k = 39 at the C2 sizes, 576 items per wave, lost 3 % with chunks of 18)
+  const uint32_t g_small = std::min(8u, n_items / (n_waves * 8u));
+  return chunk ? chunk : std::max(2u, std::min(g_max, std::max(g_small, n_items / (n_waves * 64u))));
 }
 
 hipError_t hs_launch_join8w(const uint4* d_desc, uint32_t n_items, const uint4* d_packed_base,
@@ -2357,13 +2368,7 @@ hipError_t hs_launch_join8w(const uint4* d_desc, uint32_t n_items, const uint4* 
   // item, 1.7e7 items -- with chunks of 8 the counter alone took 2.1e6 / 88 = 24 ms of a 26 ms
   // kernel); bigger chunks than that cost balance at the end.  pairs_per_item = the previous
   // batch's average (0: unknown).  Fewer for small launches.
-  const uint32_t n_waves = (uint32_t)n_blocks * 4u;
-  uint32_t g_max = 8u;
-  if (pairs_per_item > 0.0) g_max = (uint32_t)std::max(8.0, std::min(48.0, 7.0e5 / pairs_per_item));
-  // up to 8: at least 8 chunks per wave; beyond: at least 64 (the balance at the end is paid in
-  // chunks: k = 39 at the C2 sizes, 576 items per wave, lost 3 % with chunks of 18)
-  const uint32_t g_small = std::min(8u, n_items / (n_waves * 8u));
-  const uint32_t G = chunk ? chunk : std::max(2u, std::min(g_max, std::max(g_small, n_items / (n_waves * 64u))));
+  const uint32_t G = hs_join8_chunk_items(n_items, n_blocks, pairs_per_item, chunk);
   // k <= 25: JT = 4 row tiles per wave (128 members), 4 k-steps, 2 waves per SIMD.  (JT = 2 at 4
   // waves per SIMD, with work items of 64 members, was measured 1.7x slower there: twice the B-tile
   // traffic and per-item work.)  k > 25: 64 members per wave over 6 or 8 k-steps -- the operands of

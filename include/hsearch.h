@@ -97,6 +97,9 @@ typedef struct hs_profile {
                                   (or illegal) and ran a second time: exclude such a call from kernel timings */
   uint64_t queries_recognised; /* hs_query / hs_query_dev: the call's centres were all k-mers (every 8 doubles a
                                   row of the coordinate table) and ran from their residue codes: this many */
+  uint64_t join_f6_batches;    /* of join_i8_batches: those whose query-streaming kernel was the FP6 form
+                                  (hs_join6x_kernel: queries that are k-mers, k = 21..25).  join_row_bytes stays
+                                  128 for them: the depth of the GEMM, not the bytes of an FP6 row (96) */
 } hs_profile;
 
 typedef struct hs_index_info {
@@ -178,12 +181,38 @@ typedef enum hs_option {
                                 unordered pair) for its rounds.  0: never keep them (every pass is a self-join);
                                 -1 (default): a quarter of the HBM that is free when the call starts.  The list grows
                                 with the pairs, so a call takes what its graph needs, not the budget */
+  HS_OPT_JOIN_F6 = 22,       /* 1 (default): batches whose queries are k-mers (codes, recognised centres, the
+                                self-join from codes), k = 21..25, 4-column rows, run the query-streaming join on
+                                FP6 MFMA (hs_join6x_kernel); 0: never (hs_join8x_kernel) */
   HS_OPT_JOIN_XCD_RUN = 16   /* hs_join8x_kernel's work items dealt in runs of this many chunks per XCD, each XCD's
                                 waves on their own runs (a run's items stream the same query tiles: one L2 fetches
                                 them instead of eight).  0: one counter for the chip; -1 (default): by the size
                                 of the batch's query-tile array */
 } hs_option;
 HS_API hs_status hs_set_option(hs_handle* h, int option, int64_t value);
+
+/* ---- the FP6 join filter (HS_OPT_JOIN_F6), as far as a caller can inspect it -------------------- */
+/* Its tables from a coordinate table ([alphabet][8] doubles), computed on the host (no GPU): *s = the scale
+ * 7.5 / max |x| over columns 0..3, codes [32][4] the six-bit e2m3 codes of s x, e / r [32] the per-residue error
+ * share and threshold (e[a] + e[b] >= s^2 x_a.x_b - X^[a].X^[b] for every residue pair; r[a] = s^2 |x_a|^2 / 2
+ * - e[a]), pair [1024][2] the kernel's lookup table (entry r1 << 5 | r0: the 2 x 24 code bits of both residues).
+ * Any output may be NULL. */
+HS_API hs_status hs_join6_tables(const double* coords, uint32_t alphabet, double* s, uint8_t* codes, double* e,
+                                 double* r, uint32_t* pair);
+/* What the kernels carry for n k-mers (kmers [n][k], k <= 25) at squared radii r2 [n], in units of 2^-6, on the
+ * host: rho64 = a member's rho as its 16-byte record encodes it (floor - 1, lower where its digits end), c64 = a
+ * query's accumulator start -(gamma + rho0), *rho0_64 = the offset rho is carried against, rec [n][4] the member
+ * records.  Filter value of member x and query c, in 64ths: sum_p X^[x_p].X^[c_p] * 64 - (rho64[x] - rho0_64) +
+ * c64[c]; a pair within the query's radius has it >= 1. */
+HS_API hs_status hs_join6_thresholds(const double* coords, uint32_t alphabet, const uint8_t* kmers, uint64_t n,
+                                     uint32_t k, const double* r2, int64_t* rho64, int64_t* c64, int64_t* rho0_64,
+                                     uint32_t* rec);
+/* GPU: hs_join6x_kernel's tile product (v_mfma_f32_16x16x128_f8f6f4, e2m3 operands, the kernel's lane map) on
+ * rows at the format's extremes -- all-maximum, alternating signs, thresholds of +-2^17, pseudo-random codes --
+ * against int64 arithmetic on the device.  variant 0: as the kernel issues it; 1: with explicit block scales of
+ * 2^0.  *mismatches = accumulators that differ (0: exact); first_bad (NULL or 4 words): case, lane * 4 +
+ * register, the float's bits, the expected value in 64ths. */
+HS_API hs_status hs_join6_selftest(int device, int variant, uint64_t* mismatches, uint32_t* first_bad);
 /* Bucket partition -- unlike the options above this CHANGES what a query call returns.  With n_parts > 1 the
  * searches of this handle (hs_query*, not the self-joins) probe only the buckets that fall to `part` of
  * `n_parts` (a fixed function of the probe's K bucket ints, the same on every handle; for the few buckets of
