@@ -32,7 +32,8 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_density_tree_cut", "hs_query_topk", "hs_query_topk_dev", "hs_self_knn", "hs_self_knn_range",
            "hs_self_knn_dev", "hs_self_knn_range_dev", "hs_topk_merge", "hs_seq_match", "hs_seq_match_dev",
            "hs_window_id_start", "hs_seq_match_hits", "hs_seq_match_merge", "hs_join6_tables", "hs_join6_thresholds",
-           "hs_join6_selftest"]
+           "hs_join6_selftest", "hs_index_append", "hs_index_append_dev", "hs_index_append_windows",
+           "hs_index_table_append"]
 
 TOPK_MAX = 64        # HS_TOPK_MAX: the widest row of query_topk / self_knn / topk_merge
 NO_ID = 0xffffffff   # the id and table of an unused entry of such a row (its distance is +inf)
@@ -61,7 +62,8 @@ class _Profile(C.Structure):
                 ("hash_values", C.c_uint64), ("hash_flagged", C.c_uint64),
                 ("join_row_bytes", C.c_uint32), ("join_wide", C.c_uint32), ("join_items_resident", C.c_uint64),
                 ("join_async_retries", C.c_uint64), ("queries_recognised", C.c_uint64),
-                ("join_f6_batches", C.c_uint64)]
+                ("join_f6_batches", C.c_uint64), ("append_rebuilds", C.c_uint64),
+                ("append_new_buckets", C.c_uint64)]
 
 
 class _IndexInfo(C.Structure):
@@ -258,6 +260,19 @@ def load(hooks=False):
                                                   C.c_uint64, C.POINTER(C.c_uint64)]
             lib.hs_seq_match_merge.restype = C.c_int
             lib.hs_seq_match_merge.argtypes = rows + [C.c_uint64] + rows + [C.c_uint64, C.POINTER(C.c_uint64)]
+        # index append: (h, codes, m); windows as hs_index_build_windows; table_append: see include/hsearch.h
+        if hasattr(lib, "hs_index_append"):
+            for fn in (lib.hs_index_append, lib.hs_index_append_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+            lib.hs_index_append_windows.restype = C.c_int
+            lib.hs_index_append_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                    C.POINTER(C.c_uint64), C.c_void_p]
+            lib.hs_index_table_append.restype = C.c_int
+            lib.hs_index_table_append.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                                  C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_uint32)]
         _libs[hooks] = lib
     return _libs[hooks]
 
@@ -714,6 +729,48 @@ def index_file_check(path):
         raise HsError(st, err.value.decode())
 
 
+def index_table_append(ids, dir_key, dir_start, dir_tuple, block_ints, seed=0, out=None):
+    """hs_index_table_append: one table (ids [n], dir_key [nb], dir_start [nb + 1], dir_tuple [nb][K], as hs_index_save
+    writes them) merged on the host with the bucket ints block_ints [m][K] of m appended k-mers.  Returns (ids [n + m],
+    dir_key, dir_start, dir_tuple) of the grown table, or None when a fingerprint is shared by two HashKey strings
+    (collided: nothing written).  out: the four arrays to write into (tests: they must stay untouched on a
+    collision); their directory capacity is len(out[1]).  An invalid table raises HsError(HS_ERR_INVALID)."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    dir_key = np.ascontiguousarray(dir_key, dtype=np.uint64)
+    dir_start = np.ascontiguousarray(dir_start, dtype=np.uint32)
+    dir_tuple = np.ascontiguousarray(dir_tuple, dtype=np.int32)
+    block_ints = np.ascontiguousarray(block_ints, dtype=np.int32)
+    n, nb, m = len(ids), len(dir_key), block_ints.shape[0]
+    K = block_ints.shape[1] if block_ints.ndim == 2 else dir_tuple.shape[1]
+    assert len(dir_start) == nb + 1 and dir_tuple.size == nb * K and block_ints.size == m * K
+    lib = load()
+    nb_out, collided = C.c_uint64(0), C.c_uint32(0)
+
+    def call(o_ids, o_key, o_start, o_tuple, cap):
+        return lib.hs_index_table_append(_vp(ids), _vp(dir_key), _vp(dir_start), _vp(dir_tuple), C.c_uint64(n),
+                                         C.c_uint64(nb), _vp(block_ints), C.c_uint64(m), C.c_uint32(K), C.c_uint32(seed),
+                                         o_ids, o_key, o_start, o_tuple, C.c_uint64(cap), C.byref(nb_out),
+                                         C.byref(collided))
+    if out is None:
+        st = call(None, None, None, None, 0)       # the two-call pattern: the count first
+        if st == HS_OK and collided.value:
+            return None
+        if st not in (HS_OK, HS_ERR_CAPACITY):
+            raise HsError(st, "hs_index_table_append")
+        cap = int(nb_out.value)
+        out = (np.empty(n + m, dtype=np.uint32), np.empty(cap, dtype=np.uint64), np.empty(cap + 1, dtype=np.uint32),
+               np.empty((cap, K), dtype=np.int32))
+    o_ids, o_key, o_start, o_tuple = out
+    assert len(o_ids) >= n + m and len(o_start) >= len(o_key) + 1 and o_tuple.size >= len(o_key) * K
+    st = call(_vp(o_ids), _vp(o_key), _vp(o_start), _vp(o_tuple), len(o_key))
+    if st != HS_OK:
+        raise HsError(st, "hs_index_table_append")
+    if collided.value:
+        return None
+    nbo = int(nb_out.value)
+    return o_ids[:n + m], o_key[:nbo], o_start[:nbo + 1], o_tuple.reshape(-1, K)[:nbo]
+
+
 KLSH_NONE = 0xffffffffffffffff
 _REDUCED_CLASS = {c: k for k, grp in enumerate(["AST", "RKEDQ", "NH", "C", "G", "IVLM", "FYW", "P"])
                   for c in grp}   # pcluster util.hpp:100-104 (include/hs_tables.h HS_REDUCED_CLASS)
@@ -948,6 +1005,43 @@ class Engine:
         self._check(self._lib.hs_index_build_windows(self._h, _vp(residues), C.c_uint64(len(residues)),
                                                      _vp(seq_start), C.c_uint64(n_seq), C.byref(n),
                                                      _vp(pos)))
+        assert int(n.value) == n_win
+        return self.index_info(), pos
+
+    def index_append(self, codes):
+        """hs_index_append: the built index grown by the k-mers `codes` (ids n .. n + m - 1), on the device; the
+        handle then equals one built over the concatenation, bit for bit.  Returns the index info."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        assert codes.ndim == 2 and codes.shape[1] == self.k
+        self._check(self._lib.hs_index_append(self._h, _vp(codes), C.c_uint64(codes.shape[0])))
+        return self.index_info()
+
+    def index_append_dev(self, tensor):
+        """hs_index_append_dev: the block as a uint8 tensor [m][k] on the handle's GPU (or (device pointer, m))."""
+        if isinstance(tensor, tuple):
+            ptr, m = int(tensor[0]), int(tensor[1])
+        else:
+            assert tensor.is_cuda and tensor.is_contiguous() and tensor.dim() == 2 and tensor.shape[1] == self.k
+            assert tensor.element_size() == 1
+            import torch
+            torch.cuda.current_stream(tensor.device).synchronize()   # complete when it is handed over
+            ptr, m = tensor.data_ptr(), tensor.shape[0]
+        self._check(self._lib.hs_index_append_dev(self._h, C.c_void_p(ptr), C.c_uint64(m)))
+        return self.index_info()
+
+    def index_append_windows(self, residues, seq_start):
+        """hs_index_append_windows: the windows of further sequences appended (index_build_windows' enumeration).
+        Returns (index info, window start positions [m] uint32 of the APPENDED windows, in `residues`)."""
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        seq_start = np.ascontiguousarray(seq_start, dtype=np.uint64)
+        n_seq = len(seq_start) - 1
+        assert n_seq >= 0 and int(seq_start[-1]) == len(residues)
+        lens = np.diff(seq_start.astype(np.int64))
+        n_win = int(np.maximum(lens - self.k + 1, 0).sum())
+        pos = np.empty(n_win, dtype=np.uint32)
+        n = C.c_uint64(0)
+        self._check(self._lib.hs_index_append_windows(self._h, _vp(residues), C.c_uint64(len(residues)),
+                                                      _vp(seq_start), C.c_uint64(n_seq), C.byref(n), _vp(pos)))
         assert int(n.value) == n_win
         return self.index_info(), pos
 

@@ -22,6 +22,7 @@
 
 #include "../../include/hs_tables.h"
 #include "hs_internal.h"
+#include "hs_table_append.h"
 
 namespace {
 
@@ -82,7 +83,7 @@ struct Knobs {
   int join_xcd_run = -1;           // HS_OPT_JOIN_XCD_RUN: chunks per XCD-local run of join items (0 off, -1 auto)
   bool no_probe_records = false;   // HS_OPT_PROBE_RECORDS = 0: the probe reads the directory arrays, not the records
   uint32_t join_chunk = 0;         // HS_OPT_JOIN_CHUNK: items per counter access of hs_join8x_kernel (0: by itself)
-  bool build_debug = false;        // HS_BUILD_DEBUG: say when a table is sorted a second time
+  bool build_debug = false;        // HS_BUILD_DEBUG: say when a table is sorted a second time; hs_index_append: its stages' host time
   bool cluster_timing = false;     // HS_CLUSTER_TIMING: phase times of hs_self_join_range on stderr
   bool debug_refine = false;       // HS_DEBUG_REFINE: survivor counts per batch on stderr
   bool force_wide = false;         // HS_OPT_WIDE_ROWS = 1: 8-column rows whatever the radius (k <= 25)
@@ -106,6 +107,7 @@ struct Knobs {
 #ifdef HS_TEST_HOOKS
   uint32_t test_split_above = 0;   // HS_TEST_SPLIT_ABOVE: batches above this size report a survivor overflow
   bool test_group_fallback = false;  // HS_TEST_GROUP_FALLBACK: the build's fingerprint table reports itself full
+  bool test_append_collision = false;  // HS_TEST_APPEND_COLLISION: hs_index_append's match step reports a collision
 #endif
 };
 
@@ -554,6 +556,7 @@ void read_knobs(hs_handle* h) {
 #ifdef HS_TEST_HOOKS
   if (const char* m = getenv("HS_TEST_SPLIT_ABOVE")) kn.test_split_above = (uint32_t)std::max(0, atoi(m));
   kn.test_group_fallback = on("HS_TEST_GROUP_FALLBACK");
+  kn.test_append_collision = on("HS_TEST_APPEND_COLLISION");
 #endif
   if (const char* m = getenv("HS_HASH_MODE")) {
     if (!strcmp(m, "exact")) h->hash_mode = 1;
@@ -1820,6 +1823,380 @@ hs_status hs_index_build_windows(hs_handle* h, const uint8_t* residues, uint64_t
   }
   *n_windows = n;
   return index_build_resident(h, n);
+}
+
+// ---- hs_index_append: a built index grown by a block of k-mers (hs_append.hip) ----------------------------------
+namespace {
+// the scratch of one append, carved out of one allocation: sized by the block (m) and by the largest directory
+struct AppendScratch {
+  int32_t *ints, *btuple;
+  uint64_t *keys, *keys_sorted, *bkey;
+  uint32_t *iota, *bids, *bcount, *bstart, *small, *slow_q, *pos, *is_new, *new_scan, *old_cnt, *map_blk, *base_blk,
+      *inc, *inc_scan, *map_old, *base_old, *out_count, *brho;
+  uint4 *bpacked, *brec;
+  void* sort_temp;
+  size_t sort_temp_bytes;
+};
+const uint32_t kAppendSlowCap = 1u << 16;
+size_t carve_append_scratch(AppendScratch& a, char* base, uint64_t m, int K, int PW, uint64_t nb_max) {
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    char* p = base ? base + at : nullptr;
+    at += (bytes + 255) & ~(size_t)255;
+    return p;
+  };
+  a.ints = (int32_t*)take(m * K * 4);
+  a.btuple = (int32_t*)take(m * K * 4);
+  a.keys = (uint64_t*)take(m * 8);
+  a.keys_sorted = (uint64_t*)take(m * 8);
+  a.bkey = (uint64_t*)take(m * 8);
+  a.iota = (uint32_t*)take(m * 4);
+  a.bids = (uint32_t*)take(m * 4);
+  a.bcount = (uint32_t*)take(m * 4);
+  a.bstart = (uint32_t*)take((m + 1) * 4);
+  a.small = (uint32_t*)take(64);
+  a.slow_q = (uint32_t*)take(((size_t)kAppendSlowCap + 1) * 4);
+  a.pos = (uint32_t*)take(m * 4);
+  a.is_new = (uint32_t*)take((m + 1) * 4);
+  a.new_scan = (uint32_t*)take((m + 1) * 4);
+  a.old_cnt = (uint32_t*)take(m * 4);
+  a.map_blk = (uint32_t*)take(m * 4);
+  a.base_blk = (uint32_t*)take(m * 4);
+  a.inc = (uint32_t*)take((nb_max + 1) * 4);
+  a.inc_scan = (uint32_t*)take((nb_max + 1) * 4);
+  a.map_old = (uint32_t*)take((nb_max + 1) * 4);
+  a.base_old = (uint32_t*)take((nb_max + 1) * 4);
+  a.out_count = (uint32_t*)take((nb_max + m + 1) * 4);
+  a.brho = (uint32_t*)take(m * 4);
+  a.bpacked = (uint4*)take(m * PW * 16);
+  a.brec = (uint4*)take(m * 16);
+  a.sort_temp_bytes = std::max(std::max(hs_sort_pairs_u64_u32_temp(m), hs_rle_u64_temp(m)),
+                               hs_scan_u32_temp(nb_max + m + 2)) + 256;
+  a.sort_temp = take(a.sort_temp_bytes);
+  return at;
+}
+struct BufGuard {
+  std::vector<DevBuf*> b;
+  ~BufGuard() { for (DevBuf* x : b) x->release(); }
+};
+}  // namespace
+
+// unbuilt index, n + m too large: from the arguments alone, before anything is touched
+static hs_status append_check(hs_handle* h, uint64_t m) {
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_append: no index to append to (hs_index_build has not been called)");
+  if (m >= (1ull << 31) || h->n + m >= (1ull << 31))
+    return fail(h, HS_ERR_INVALID, "hs_index_append: n + m must be < 2^31 (ids are 32-bit, as in the reference)");
+  return HS_OK;
+}
+
+// The L tables of the index merged with the block, whose codes are the last m of h->codes and whose packed k-mers
+// are d_blk_packed [m][PW]; h->n is still the old n.  On success the grown arrays are the handle's and the old ones
+// are gone (finish_index is the caller's); *collided: nothing of the handle's tables has changed.
+static hs_status append_tables(hs_handle* h, const uint4* d_blk_packed, uint64_t m, bool* collided) {
+  const uint64_t n = h->n, n2 = n + m;
+  const int K = (int)h->p.K, L = (int)h->p.L, k = (int)h->p.k, PW = h->PW;
+  const uint32_t seed = h->key_seed;
+  *collided = false;
+  const uint8_t* d_blk_codes = h->codes.as<uint8_t>() + (size_t)n * k;
+  const bool with_rec8 = h->join8_tables_ok && k <= 50;
+  const bool with_rho = with_rec8 && k <= 25 && !h->wide8;
+  DevBuf arena, npacked, nrec8, nrho, npos, nids[HS_MAX_L], nkey[HS_MAX_L], nstart[HS_MAX_L], ntuple[HS_MAX_L];
+  BufGuard guard;
+  guard.b = {&arena, &npacked, &nrec8, &nrho, &npos};
+  for (int l = 0; l < L; ++l) {
+    guard.b.push_back(&nids[l]);
+    guard.b.push_back(&nkey[l]);
+    guard.b.push_back(&nstart[l]);
+    guard.b.push_back(&ntuple[l]);
+  }
+  uint64_t nb_max = 0;
+  for (int l = 0; l < L; ++l) nb_max = std::max<uint64_t>(nb_max, h->info.n_buckets[l]);
+  AppendScratch a;
+  HS_HIP(h, arena.reserve(carve_append_scratch(a, nullptr, m, K, PW, nb_max)));
+  carve_append_scratch(a, arena.as<char>(), m, K, PW, nb_max);
+  // (the same padding behind the last table as the build leaves: hs_join8r_kernel's ragged last member tile)
+  HS_HIP(h, npacked.reserve(((size_t)L * n2 + HS_JM_WAVE) * PW * 16));
+  if (with_rec8) HS_HIP(h, nrec8.reserve(((size_t)L * n2 + HS_JM_WAVE) * 16));
+  if (with_rho) HS_HIP(h, nrho.reserve(((size_t)L * n2 + HS_JM_WAVE + 4) * 4));
+  HS_HIP(h, npos.reserve(std::max<size_t>(16, (size_t)L * n2 * 4)));
+  uint64_t new_nb[HS_MAX_L], new_max[HS_MAX_L], new_buckets = 0;
+  double ms_hash = 0, ms_sort = 0, ms_gather = 0;
+  for (int l = 0; l < L; ++l) {
+    const uint32_t nb = (uint32_t)h->info.n_buckets[l];
+    const hs_table_dev& tb = h->tabs.t[l];
+    HS_HIP(h, hipMemsetAsync(a.small, 0, 64, h->stream));
+    HS_HIP(h, hipEventRecord(h->ev[1], h->stream));
+    // 1. the block's bucket ints and fingerprints under the index's seed, grouped as the build's sorting path groups
+    HS_CHECK(hash_dispatch(h, d_blk_codes, nullptr, m, l, a.ints, K, 0, h->stream));
+    HS_HIP(h, hs_launch_keys(a.ints, m, K, K, seed, a.keys, a.iota, h->stream));
+    HS_HIP(h, hipEventRecord(h->ev[2], h->stream));
+    HS_HIP(h, hs_sort_pairs_u64_u32(a.sort_temp, a.sort_temp_bytes, a.keys, a.keys_sorted, a.iota, a.bids, m, 0, 64,
+                                    h->stream));
+    HS_HIP(h, hs_launch_check_runs(a.keys_sorted, a.bids, a.ints, m, K, a.small + 1, a.slow_q, kAppendSlowCap, false, 0,
+                                   h->stream));
+    HS_HIP(h, hs_rle_u64(a.sort_temp, a.sort_temp_bytes, a.keys_sorted, a.bkey, a.bcount, a.small, m, h->stream));
+    uint32_t host2[2] = {0, 0};  // {block buckets, flags}
+    HS_HIP(h, hipMemcpyAsync(host2, a.small, 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    const uint32_t nbB = host2[0];
+    uint32_t flag = host2[1];
+    if (flag & 2u) {  // very many aliased neighbours: every pair compared as strings (build_tables does the same)
+      HS_HIP(h, hipMemsetAsync(a.small + 1, 0, 4, h->stream));
+      HS_HIP(h, hs_launch_check_runs(a.keys_sorted, a.bids, a.ints, m, K, a.small + 1, a.slow_q, kAppendSlowCap, true, 0,
+                                     h->stream));
+      HS_HIP(h, hipMemcpyAsync(&flag, a.small + 1, 4, hipMemcpyDeviceToHost, h->stream));
+      HS_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    if (flag & 1u) {
+      *collided = true;
+      return HS_OK;
+    }
+    if (nbB > m || !nbB) return fail(h, HS_ERR_HIP, "hs_index_append: the block's run lengths are inconsistent");
+    HS_HIP(h, hs_exclusive_scan_u32(a.sort_temp, a.sort_temp_bytes, a.bcount, a.bstart, nbB, h->stream));
+    HS_HIP(h, hs_launch_set_u32(a.bstart + nbB, (uint32_t)m, h->stream));
+    HS_HIP(h, hs_launch_dir_tuples(a.bstart, a.bids, a.ints, nbB, K, a.btuple, h->stream));
+    // 2. match against the old directory
+    HS_HIP(h, hipMemsetAsync(a.inc, 0, ((size_t)nb + 1) * 4, h->stream));
+    HS_HIP(h, hipMemsetAsync(a.is_new + nbB, 0, 4, h->stream));
+    HS_HIP(h, hipMemsetAsync(a.small + 1, 0, 4, h->stream));
+    HS_HIP(h, hs_launch_append_match(a.bkey, a.btuple, nbB, K, tb.dir_key, tb.dir_tuple, tb.dir_jump, tb.jump_shift, nb,
+                                     a.pos, a.is_new, a.inc, a.small + 1, h->stream));
+    HS_HIP(h, hs_exclusive_scan_u32(a.sort_temp, a.sort_temp_bytes, a.is_new, a.new_scan, (size_t)nbB + 1, h->stream));
+    HS_HIP(h, hs_exclusive_scan_u32(a.sort_temp, a.sort_temp_bytes, a.inc, a.inc_scan, (size_t)nb + 1, h->stream));
+    uint32_t n_new = 0;
+    HS_HIP(h, hipMemcpyAsync(&flag, a.small + 1, 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(&n_new, a.new_scan + nbB, 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+#ifdef HS_TEST_HOOKS
+    if (h->knobs.test_append_collision && l == L - 1) flag |= 1u;  // (the last table: the others have merged by then)
+#endif
+    if (flag & 1u) {  // one fingerprint, two HashKey strings, the block's and the index's
+      *collided = true;
+      return HS_OK;
+    }
+    if (n_new > nbB) return fail(h, HS_ERR_HIP, "hs_index_append: the match counts are inconsistent");
+    // 3. the merged directory
+    const uint32_t nb2 = nb + n_new;
+    HS_HIP(h, nids[l].reserve(std::max<size_t>(16, (size_t)n2 * 4)));
+    HS_HIP(h, nkey[l].reserve(std::max<size_t>(16, (size_t)nb2 * 8)));
+    HS_HIP(h, nstart[l].reserve(((size_t)nb2 + 1) * 4));
+    HS_HIP(h, ntuple[l].reserve(std::max<size_t>(16, (size_t)nb2 * K * 4)));
+    HS_HIP(h, hs_launch_append_dir(tb.dir_key, tb.dir_start, tb.dir_tuple, nb, a.bkey, a.bstart, a.btuple, nbB, K, a.pos,
+                                   a.is_new, a.new_scan, a.inc, a.inc_scan, a.map_old, a.map_blk, a.old_cnt,
+                                   nkey[l].as<uint64_t>(), ntuple[l].as<int32_t>(), a.out_count, h->stream));
+    HS_HIP(h, hs_exclusive_scan_u32(a.sort_temp, a.sort_temp_bytes, a.out_count, nstart[l].as<uint32_t>(), nb2,
+                                    h->stream));
+    HS_HIP(h, hs_launch_set_u32(nstart[l].as<uint32_t>() + nb2, (uint32_t)n2, h->stream));
+    HS_HIP(h, hipMemsetAsync(a.small + 2, 0, 4, h->stream));
+    HS_HIP(h, hs_launch_max_u32(a.out_count, nb2, a.small + 2, h->stream));
+    HS_HIP(h, hs_launch_append_bases(nstart[l].as<uint32_t>(), tb.dir_start, a.map_old, nb, a.bstart, a.map_blk,
+                                     a.old_cnt, nbB, a.base_old, a.base_blk, h->stream));
+    HS_HIP(h, hipEventRecord(h->ev[3], h->stream));
+    // 4. the block's entries in block-bucket order, by the build's own record kernels; then the move
+    uint4* const dst_packed = npacked.as<uint4>() + (size_t)l * n2 * PW;
+    uint4* const dst_rec = with_rec8 ? nrec8.as<uint4>() + (size_t)l * n2 : nullptr;
+    uint32_t* const dst_rho = with_rho ? nrho.as<uint32_t>() + (size_t)l * n2 : nullptr;
+    if (with_rec8)
+      HS_HIP(h, hs_launch_gather_rec8(d_blk_packed, a.bids, (uint32_t)m, k, h->wide8, h->jtab8.p,
+                                      h->jtab8.as<char>() + 1536, h->jtab8.as<float>() + 128, a.bpacked, a.brec,
+                                      with_rho ? a.brho : nullptr, h->stream));
+    else
+      HS_HIP(h, hs_launch_gather_packed(d_blk_packed, a.bids, m, PW, a.bpacked, h->stream));
+    HS_HIP(h, hs_launch_append_move((uint32_t)n, tb.dir_start, nb, a.base_old, (uint32_t)n2, PW, tb.ids, 0u, tb.packed,
+                                    with_rec8 ? h->t_rec8.as<uint4>() + (size_t)l * n : nullptr,
+                                    with_rho ? h->t_rho.as<uint32_t>() + (size_t)l * n : nullptr,
+                                    nids[l].as<uint32_t>(), dst_packed, dst_rec, dst_rho, h->stream));
+    HS_HIP(h, hs_launch_append_move((uint32_t)m, a.bstart, nbB, a.base_blk, (uint32_t)n2, PW, a.bids, (uint32_t)n,
+                                    a.bpacked, with_rec8 ? a.brec : nullptr, with_rho ? a.brho : nullptr,
+                                    nids[l].as<uint32_t>(), dst_packed, dst_rec, dst_rho, h->stream));
+    HS_HIP(h, hs_launch_invert_perm(nids[l].as<uint32_t>(), (uint32_t)n2, npos.as<uint32_t>() + (size_t)l * n2,
+                                    h->stream));
+    HS_HIP(h, hipEventRecord(h->ev[4], h->stream));
+    uint32_t max_count = 0;
+    HS_HIP(h, hipMemcpyAsync(&max_count, a.small + 2, 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    ms_hash += ev_ms(h, 1, 2);
+    ms_sort += ev_ms(h, 2, 3);
+    ms_gather += ev_ms(h, 3, 4);
+    HS_CHECK(hash_account(h, m, K, 0));
+    new_nb[l] = nb2;
+    new_max[l] = max_count;
+    new_buckets += n_new;
+  }
+  // every table has merged: the grown arrays become the handle's (the guard frees the old ones)
+  std::swap(h->t_packed, npacked);
+  std::swap(h->t_rec8, nrec8);
+  std::swap(h->t_rho, nrho);
+  std::swap(h->t_pos, npos);
+  for (int l = 0; l < L; ++l) {
+    std::swap(h->t_ids[l], nids[l]);
+    std::swap(h->t_dirkey[l], nkey[l]);
+    std::swap(h->t_dirstart[l], nstart[l]);
+    std::swap(h->t_dirtuple[l], ntuple[l]);
+    hs_table_dev& tb = h->tabs.t[l];
+    tb.dir_key = h->t_dirkey[l].as<uint64_t>();
+    tb.dir_start = h->t_dirstart[l].as<uint32_t>();
+    tb.dir_tuple = h->t_dirtuple[l].as<int32_t>();
+    tb.packed = h->t_packed.as<uint4>() + (size_t)l * n2 * PW;
+    tb.ids = h->t_ids[l].as<uint32_t>();
+    tb.pos_of = h->t_pos.as<uint32_t>() + (size_t)l * n2;
+    tb.nb = (uint32_t)new_nb[l];
+    h->info.n_buckets[l] = new_nb[l];
+    h->info.max_bucket[l] = new_max[l];
+  }
+  h->prof.ms_hash = ms_hash;
+  h->prof.ms_sort = ms_sort;
+  h->prof.ms_gather = ms_gather;
+  h->prof.append_new_buckets = new_buckets;
+  return HS_OK;
+}
+
+// The block's codes are d_blk [m][k] on the device (m >= 1, append_check passed).  Validation first; from
+// drop_index on, every failure leaves the handle without an index.
+static hs_status index_append_resident(hs_handle* h, const uint8_t* d_blk, uint64_t m) {
+  const uint64_t n = h->n;
+  const int k = (int)h->p.k, PW = h->PW;
+  // HS_BUILD_DEBUG: host time of the call's stages on stderr (allocation and release are host work no event sees)
+  auto t_last = std::chrono::steady_clock::now();
+  auto stage = [&](const char* what) {
+    if (!h->knobs.build_debug) return;
+    const auto t = std::chrono::steady_clock::now();
+    fprintf(stderr, "hs_index_append: %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_last).count());
+    t_last = t;
+  };
+  DevBuf blk_packed, ncodes, npacked_all;
+  BufGuard guard;
+  guard.b = {&blk_packed, &ncodes, &npacked_all};
+  HS_HIP(h, h->counters.reserve(256));
+  HS_HIP(h, blk_packed.reserve((size_t)m * PW * 16));
+  HS_HIP(h, hipMemsetAsync(h->counters.p, 0, 256, h->stream));
+  HS_HIP(h, hs_launch_pack(d_blk, m, k, h->alphabet, blk_packed.as<uint4>(), h->counters.as<uint32_t>(), h->stream));
+  uint32_t bad = 0;
+  HS_HIP(h, hipMemcpyAsync(&bad, h->counters.p, 4, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  if (bad) return fail(h, HS_ERR_INVALID, "hs_index_append: residue code outside the alphabet in the block");
+  stage("block packed and checked");
+  // ---- the handle changes from here on
+  drop_index(h);
+  memset(&h->prof, 0, sizeof(h->prof));
+  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
+  // codes and packed k-mers in id order: old ones copied on the device, the block behind them
+  HS_HIP(h, ncodes.reserve(std::max<size_t>(16, (size_t)(n + m) * k)));
+  HS_HIP(h, npacked_all.reserve(std::max<size_t>(16, (size_t)(n + m) * PW * 16)));
+  if (n) {
+    HS_HIP(h, hipMemcpyAsync(ncodes.p, h->codes.p, (size_t)n * k, hipMemcpyDeviceToDevice, h->stream));
+    HS_HIP(h, hipMemcpyAsync(npacked_all.p, h->packed_all.p, (size_t)n * PW * 16, hipMemcpyDeviceToDevice, h->stream));
+  }
+  HS_HIP(h, hipMemcpyAsync(ncodes.as<char>() + (size_t)n * k, d_blk, (size_t)m * k, hipMemcpyDeviceToDevice, h->stream));
+  HS_HIP(h, hipMemcpyAsync(npacked_all.as<char>() + (size_t)n * PW * 16, blk_packed.p, (size_t)m * PW * 16,
+                           hipMemcpyDeviceToDevice, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));  // (d_blk may be the caller's)
+  std::swap(h->codes, ncodes);
+  std::swap(h->packed_all, npacked_all);
+  ncodes.release();
+  npacked_all.release();
+  stage("codes grown");
+  bool collided = false;
+  if (n) {
+    HS_CHECK(append_tables(h, blk_packed.as<uint4>(), m, &collided));
+    stage("tables merged, old ones freed");
+    if (!collided) {
+      h->n = n + m;
+      HS_HIP(h, hipEventRecord(h->ev[9], h->stream));
+      HS_HIP(h, hipStreamSynchronize(h->stream));
+      h->prof.ms_total = ev_ms(h, 8, 9);
+      const hs_status fst = finish_index(h);
+      stage("finish_index");
+      return fst;
+    }
+  }
+  // an empty index, or one fingerprint under two HashKey strings: the build loop over all the codes, resident
+  // already, from seed 0 -- where hs_index_build over the concatenation would have ended too
+  blk_packed.release();
+  h->n = n + m;
+  memset(&h->info, 0, sizeof(h->info));
+  const uint64_t rebuilds = collided ? 1 : 0;
+  hs_status st = index_build_resident(h, n + m);
+  h->prof.append_rebuilds = rebuilds;
+  return st;
+}
+
+hs_status hs_index_append_dev(hs_handle* h, const uint8_t* d_codes, uint64_t m) {
+  if (!h || (m && !d_codes)) return HS_ERR_INVALID;
+  HS_CHECK(append_check(h, m));
+  if (!m) return HS_OK;
+  HS_CHECK(ensure_device(h));
+  return index_append_resident(h, d_codes, m);
+}
+
+hs_status hs_index_append(hs_handle* h, const uint8_t* codes, uint64_t m) {
+  if (!h || (m && !codes)) return HS_ERR_INVALID;
+  HS_CHECK(append_check(h, m));
+  if (!m) return HS_OK;
+  HS_CHECK(ensure_device(h));
+  DevBuf d_blk;
+  BufGuard guard;
+  guard.b = {&d_blk};
+  HS_HIP(h, d_blk.reserve((size_t)m * h->p.k));
+  HS_HIP(h, hipMemcpyAsync(d_blk.p, codes, (size_t)m * h->p.k, hipMemcpyHostToDevice, h->stream));
+  return index_append_resident(h, d_blk.as<uint8_t>(), m);
+}
+
+hs_status hs_index_append_windows(hs_handle* h, const uint8_t* residues, uint64_t n_residues,
+                                  const uint64_t* seq_start, uint64_t n_seq, uint64_t* n_windows,
+                                  uint32_t* window_pos) {
+  if (!h || !n_windows || (n_seq && !seq_start) || (n_residues && !residues)) return HS_ERR_INVALID;
+  *n_windows = 0;
+  if (!h->built) return append_check(h, 0);
+  const uint64_t k = h->p.k;
+  if (n_residues >= (1ull << 32)) return fail(h, HS_ERR_INVALID, "n_residues must be < 2^32");
+  std::vector<uint32_t> starts((size_t)n_seq + 1), win_off((size_t)n_seq + 1);
+  uint64_t m = 0;
+  for (uint64_t s = 0; s < n_seq; ++s) {
+    if (seq_start[s] > seq_start[s + 1] || seq_start[s + 1] > n_residues)
+      return fail(h, HS_ERR_INVALID, "seq_start must be ascending and end at n_residues");
+    const uint64_t len = seq_start[s + 1] - seq_start[s];
+    starts[s] = (uint32_t)seq_start[s];
+    win_off[s] = (uint32_t)m;
+    m += len >= k ? len - k + 1 : 0;
+    if (m >= (1ull << 31)) return fail(h, HS_ERR_INVALID, "more than 2^31 - 1 windows");
+  }
+  starts[n_seq] = (uint32_t)(n_seq ? seq_start[n_seq] : 0);
+  win_off[n_seq] = (uint32_t)m;
+  HS_CHECK(append_check(h, m));
+  if (!m) return HS_OK;
+  HS_CHECK(ensure_device(h));
+  DevBuf d_res, d_starts, d_off, d_pos, d_blk;
+  BufGuard guard;
+  guard.b = {&d_res, &d_starts, &d_off, &d_pos, &d_blk};
+  HS_HIP(h, d_res.reserve((size_t)n_residues));
+  HS_HIP(h, d_starts.reserve(((size_t)n_seq + 1) * 4));
+  HS_HIP(h, d_off.reserve(((size_t)n_seq + 1) * 4));
+  HS_HIP(h, d_pos.reserve((size_t)m * 4));
+  HS_HIP(h, d_blk.reserve((size_t)m * k));
+  HS_HIP(h, hipMemcpyAsync(d_res.p, residues, (size_t)n_residues, hipMemcpyHostToDevice, h->stream));
+  HS_HIP(h, hipMemcpyAsync(d_starts.p, starts.data(), ((size_t)n_seq + 1) * 4, hipMemcpyHostToDevice, h->stream));
+  HS_HIP(h, hipMemcpyAsync(d_off.p, win_off.data(), ((size_t)n_seq + 1) * 4, hipMemcpyHostToDevice, h->stream));
+  HS_HIP(h, hs_launch_windows(d_res.as<uint8_t>(), (uint32_t)n_residues, d_starts.as<uint32_t>(), d_off.as<uint32_t>(),
+                              (uint32_t)n_seq, (int)k, d_blk.as<uint8_t>(), d_pos.as<uint32_t>(), h->stream));
+  // (window_pos is written only once the block has passed its checks: index_append_resident's first step)
+  hs_status st = index_append_resident(h, d_blk.as<uint8_t>(), m);
+  if (st != HS_OK) return st;
+  if (window_pos) {
+    HS_HIP(h, hipMemcpyAsync(window_pos, d_pos.p, (size_t)m * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  *n_windows = m;
+  return HS_OK;
+}
+
+hs_status hs_index_table_append(const uint32_t* ids, const uint64_t* dir_key, const uint32_t* dir_start,
+                                const int32_t* dir_tuple, uint64_t n, uint64_t nb, const int32_t* block_ints, uint64_t m,
+                                uint32_t K, uint32_t seed, uint32_t* out_ids, uint64_t* out_dir_key,
+                                uint32_t* out_dir_start, int32_t* out_dir_tuple, uint64_t dir_cap, uint64_t* nb_out,
+                                uint32_t* collided) {
+  return (hs_status)hs_table_append_host(ids, dir_key, dir_start, dir_tuple, n, nb, block_ints, m, K, seed, out_ids,
+                                         out_dir_key, out_dir_start, out_dir_tuple, dir_cap, nb_out, collided);
 }
 
 // ---- KLSH pre-grouping ------------------------------------------------------

@@ -19,93 +19,7 @@
 #define HS_SLICE 4096u      // candidates one wavefront scans per work item
 #define HS_KEY_CHARS (11 * HS_MAX_K + 1)
 
-// ---- key fingerprints ---------------------------------------------------------------------------
-// The reference keys a table by the STRING to_string(b_0)+...+to_string(b_{K-1}) (lsh.hpp:51-59).
-// The index keys by a 64-bit fingerprint of exactly that character stream (so tuples whose strings
-// alias, e.g. (1,23) and (12,3), share a fingerprint by construction) and verifies string equality
-// exactly: at build time for every sorted neighbour pair, at probe time against the bucket's tuple.
-__host__ __device__ inline uint64_t hs_key_init(uint32_t seed) {
-  return 0xcbf29ce484222325ull ^ ((uint64_t)(seed + 1) * 0x9e3779b97f4a7c15ull);
-}
-__host__ __device__ inline uint64_t hs_key_put(uint64_t h, uint32_t ch) {
-  return (h ^ ch) * 0x100000001b3ull;
-}
-__host__ __device__ inline uint64_t hs_key_put_int(uint64_t h, int32_t v) {
-  // the decimal characters of v, most significant first (std::to_string, lsh.hpp:51-59); divisions
-  // by constants only, short numbers (the usual bucket ints) first
-  uint32_t m;
-  if (v < 0) {
-    h = hs_key_put(h, '-');
-    m = 0u - (uint32_t)v;
-  } else {
-    m = (uint32_t)v;
-  }
-  if (m < 10u) return hs_key_put(h, '0' + m);
-  if (m < 100u) {
-    const uint32_t q = m / 10u;
-    h = hs_key_put(h, '0' + q);
-    return hs_key_put(h, '0' + (m - 10u * q));
-  }
-  bool started = false;
-#define HS_DIGIT(P)                            \
-  {                                            \
-    const uint32_t dgt = (m / (P)) % 10u;      \
-    started = started || dgt != 0u;            \
-    if (started) h = hs_key_put(h, '0' + dgt); \
-  }
-  HS_DIGIT(1000000000u) HS_DIGIT(100000000u) HS_DIGIT(10000000u) HS_DIGIT(1000000u) HS_DIGIT(100000u)
-  HS_DIGIT(10000u) HS_DIGIT(1000u) HS_DIGIT(100u) HS_DIGIT(10u) HS_DIGIT(1u)
-#undef HS_DIGIT
-  return h;
-}
-__host__ __device__ inline uint64_t hs_key_fin(uint64_t h) {
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
-  return h;
-}
-__host__ __device__ inline uint64_t hs_key_of(const int32_t* t, int K, uint32_t seed) {
-  uint64_t h = hs_key_init(seed);
-  for (int i = 0; i < K; ++i) h = hs_key_put_int(h, t[i]);
-  return hs_key_fin(h);
-}
-// Decimal characters of the concatenation; returns the length.
-__host__ __device__ inline int hs_key_chars(const int32_t* t, int K, char* out) {
-  int n = 0;
-  for (int i = 0; i < K; ++i) {
-    int32_t v = t[i];
-    uint32_t m;
-    if (v < 0) {
-      out[n++] = '-';
-      m = 0u - (uint32_t)v;
-    } else {
-      m = (uint32_t)v;
-    }
-    uint32_t p = 1;
-    while (m / p >= 10) p *= 10;
-    while (p) {
-      uint32_t dgt = m / p;
-      out[n++] = (char)('0' + dgt);
-      m -= dgt * p;
-      p /= 10;
-    }
-  }
-  return n;
-}
-// HashKey string equality of two K-tuples (fast path: identical tuples).
-__host__ __device__ inline bool hs_key_equal(const int32_t* x, const int32_t* y, int K) {
-  bool same = true;
-  for (int i = 0; i < K; ++i) same = same && (x[i] == y[i]);
-  if (same) return true;
-  char sx[HS_KEY_CHARS], sy[HS_KEY_CHARS];
-  int nx = hs_key_chars(x, K, sx), ny = hs_key_chars(y, K, sy);
-  if (nx != ny) return false;
-  for (int i = 0; i < nx; ++i)
-    if (sx[i] != sy[i]) return false;
-  return true;
-}
+#include "hs_key.h"
 
 // ---- device view of one hash table --------------------------------------------------------------
 // The survivor list's counter is 32 bits (the batch's counters block, word 0).  A batch whose filters
@@ -854,5 +768,33 @@ hipError_t hs_launch_bf_finalize(const uint8_t* d_codes, const double* d_centers
 // per-query radii of a call (hs_query_radii_dev): d_out[0] = the bits of max |radii[q]| as a double (0 for n = 0),
 // d_out[1] = 1 if one of them is a NaN; d_out zeroed by the caller
 hipError_t hs_launch_radii_max(const double* d_radii, uint64_t n, unsigned long long* d_out, hipStream_t s);
+
+// ---- hs_index_append (hs_append.hip: the rule, the steps and the scratch are written at its head) ----------------
+// match: per block bucket its place in the old directory -- d_pos = the bucket (d_is_new = 0; *d_flag |= 1 where the
+// tuples differ as HashKey strings) or the insertion rank (d_is_new = 1, ++d_inc[rank]; d_inc [nb + 1] zeroed).
+hipError_t hs_launch_append_match(const uint64_t* d_bkey, const int32_t* d_btuple, uint32_t nbB, int K,
+                                  const uint64_t* d_dir_key, const int32_t* d_dir_tuple, const uint32_t* d_dir_jump,
+                                  uint32_t jump_shift, uint32_t nb, uint32_t* d_pos, uint32_t* d_is_new,
+                                  uint32_t* d_inc, uint32_t* d_flag, hipStream_t s);
+// dir: the merged keys, tuples and COUNTS (d_new_scan / d_inc_scan: exclusive scans of d_is_new / d_inc), the maps old
+// bucket -> merged and block bucket -> merged, and per block bucket the old members of its merged bucket
+hipError_t hs_launch_append_dir(const uint64_t* d_dir_key, const uint32_t* d_dir_start, const int32_t* d_dir_tuple,
+                                uint32_t nb, const uint64_t* d_bkey, const uint32_t* d_bstart, const int32_t* d_btuple,
+                                uint32_t nbB, int K, const uint32_t* d_pos, const uint32_t* d_is_new,
+                                const uint32_t* d_new_scan, const uint32_t* d_inc, const uint32_t* d_inc_scan,
+                                uint32_t* d_map_old, uint32_t* d_map_blk, uint32_t* d_old_cnt, uint64_t* d_out_key,
+                                int32_t* d_out_tuple, uint32_t* d_out_count, hipStream_t s);
+// bases: destination = base[bucket] + source position, for the old table's entries and for the block's
+hipError_t hs_launch_append_bases(const uint32_t* d_out_start, const uint32_t* d_dir_start, const uint32_t* d_map_old,
+                                  uint32_t nb, const uint32_t* d_bstart, const uint32_t* d_map_blk,
+                                  const uint32_t* d_old_cnt, uint32_t nbB, uint32_t* d_base_old, uint32_t* d_base_blk,
+                                  hipStream_t s);
+// move: entry p of the source arrays (n_seg non-empty segments d_seg_start [n_seg + 1]) to d_base[segment of p] + p of
+// the destination arrays of n_dst entries; ids grow by id_add; d_dst_rec / d_dst_rho may be null
+hipError_t hs_launch_append_move(uint32_t n_src, const uint32_t* d_seg_start, uint32_t n_seg, const uint32_t* d_base,
+                                 uint32_t n_dst, int PW, const uint32_t* d_src_ids, uint32_t id_add,
+                                 const uint4* d_src_packed, const uint4* d_src_rec, const uint32_t* d_src_rho,
+                                 uint32_t* d_dst_ids, uint4* d_dst_packed, uint4* d_dst_rec, uint32_t* d_dst_rho,
+                                 hipStream_t s);
 
 #endif

@@ -551,25 +551,81 @@ bool ReadProteinFasta(const std::string& path, bool ref_compat_eq_swap, ProteinD
   return true;
 }
 
+// --db-append: the database followed by the sequences of every further one -- sequence numbers and names continue,
+// as in the concatenated FASTA file; part_end[i] = where part i ends in the joined residues
+static ProteinDB JoinProteinDBs(const ProteinDB& db, const std::vector<ProteinDB>& more, std::vector<uint64_t>* part_end) {
+  ProteinDB all = db;
+  if (all.start.empty()) all.start.push_back(0);
+  all.name.resize(all.start.size() - 1);
+  part_end->assign(1, all.residues.size());
+  for (const ProteinDB& m : more) {
+    const uint64_t base = all.residues.size();
+    const size_t n_seq = m.start.empty() ? 0 : m.start.size() - 1;
+    for (size_t s = 0; s < n_seq; ++s) {
+      all.name.push_back(s < m.name.size() ? m.name[s] : std::string());
+      all.start.push_back(base + m.start[s + 1]);
+    }
+    all.residues.insert(all.residues.end(), m.residues.begin(), m.residues.end());
+    part_end->push_back(all.residues.size());
+  }
+  return all;
+}
+
+// The index over the windows of `res` cut into the segments `seg` (seg.size() - 1 of them, ending at res.size()): built
+// from the segments of the first part and grown by those of every further part (hs_index_append_windows), which gives
+// the index hs_index_build_windows builds over all of them.  Parts end at sequence starts, which are segment starts.
+static hs_status BuildWindowsInParts(hs_handle* h, const std::vector<uint8_t>& res, const std::vector<uint64_t>& seg,
+                                     const std::vector<uint64_t>& part_end, uint64_t* n_win, uint32_t* win_pos) {
+  if (part_end.size() <= 1) return hs_index_build_windows(h, res.data(), res.size(), seg.data(), seg.size() - 1, n_win, win_pos);
+  *n_win = 0;
+  uint64_t lo = 0;
+  size_t at = 0;  // first segment of the part
+  for (size_t part = 0; part < part_end.size(); ++part) {
+    const uint64_t hi = part_end[part];
+    std::vector<uint64_t> local;
+    while (at + 1 < seg.size() && seg[at] < hi) local.push_back(seg[at++] - lo);
+    local.push_back(hi - lo);
+    uint64_t nw = 0;
+    uint32_t* const pos = win_pos ? win_pos + *n_win : nullptr;
+    const hs_status st = part == 0 ? hs_index_build_windows(h, res.data(), hi, local.data(), local.size() - 1, &nw, pos)
+                                   : hs_index_append_windows(h, res.data() + lo, hi - lo, local.data(), local.size() - 1, &nw, pos);
+    if (st != HS_OK) return st;
+    if (pos)
+      for (uint64_t i = 0; i < nw; ++i) pos[i] += (uint32_t)lo;
+    *n_win += nw;
+    lo = hi;
+  }
+  return HS_OK;
+}
+
 int SearchProteins(const ProteinDB& db, uint32_t kmer_length, const std::vector<Point>& centers,
                    const std::vector<std::string>& center_names, const uint32_t& hash_K,
                    const uint32_t& hash_L, const double& hash_W, const double& hash_R,
                    const std::string& output_file, const Planes& planes, int device, std::string* err,
                    std::vector<uint64_t>* table_sizes, uint64_t* n_windows, bool best_per_position,
-                   const std::vector<double>* radii, uint32_t topk) {
+                   const std::vector<double>* radii, uint32_t topk, const std::vector<ProteinDB>* more) {
   return SearchProteinsSharded(db, kmer_length, centers, center_names, hash_K, hash_L, hash_W, hash_R,
                                output_file, planes, std::vector<int>(1, device), false, err, table_sizes,
-                               n_windows, best_per_position, nullptr, radii, topk);
+                               n_windows, best_per_position, nullptr, radii, topk, more);
 }
 
-int SearchProteinsSharded(const ProteinDB& db, uint32_t kmer_length, const std::vector<Point>& centers,
+int SearchProteinsSharded(const ProteinDB& db_first, uint32_t kmer_length, const std::vector<Point>& centers,
                           const std::vector<std::string>& center_names, const uint32_t& hash_K,
                           const uint32_t& hash_L, const double& hash_W, const double& hash_R,
                           const std::string& output_file, const Planes& planes,
                           const std::vector<int>& devices, bool use_comm, std::string* err,
                           std::vector<uint64_t>* table_sizes, uint64_t* n_windows, bool best_per_position,
-                          const std::vector<uint8_t>* center_codes, const std::vector<double>* radii, uint32_t topk) {
+                          const std::vector<uint8_t>* center_codes, const std::vector<double>* radii, uint32_t topk,
+                          const std::vector<ProteinDB>* more) {
   const uint32_t dim = 8 * kmer_length;
+  const bool appended = more && !more->empty();
+  if (appended && devices.size() > 1) {
+    if (err) *err = "appended databases run on one GPU";
+    return HS_ERR_INVALID;
+  }
+  std::vector<uint64_t> part_end;
+  const ProteinDB joined = appended ? JoinProteinDBs(db_first, *more, &part_end) : ProteinDB();
+  const ProteinDB& db = appended ? joined : db_first;
   if (!RadiiMatch(radii, centers.size(), err)) return HS_ERR_INVALID;
   if (center_codes && center_codes->size() != centers.size() * (size_t)kmer_length) {
     if (err) *err = "centre codes do not match the centres";
@@ -614,8 +670,7 @@ int SearchProteinsSharded(const ProteinDB& db, uint32_t kmer_length, const std::
       prm, planes, &HS_AA_COORDS[0][0],
       [&](hs_handle* h, uint32_t rank) {
         uint64_t nw = 0;  // every rank enumerates the same windows; rank 0 keeps their positions
-        const hs_status bst = hs_index_build_windows(h, res.data(), res.size(), seg.data(), seg.size() - 1, &nw,
-                                                     rank == 0 ? win_pos.data() : nullptr);
+        const hs_status bst = BuildWindowsInParts(h, res, seg, part_end, &nw, rank == 0 ? win_pos.data() : nullptr);
         if (rank == 0) n_win = nw;
         return bst;
       },
@@ -665,13 +720,18 @@ static std::string ProteinLabel(const ProteinDB& db, size_t s) {
   return token + "#" + std::to_string(s);
 }
 
-int SearchProteinsPerSequence(const ProteinDB& db, uint32_t kmer_length, const std::vector<Point>& centers,
+int SearchProteinsPerSequence(const ProteinDB& db_first, uint32_t kmer_length, const std::vector<Point>& centers,
                               const std::vector<std::string>& center_names, const std::vector<uint8_t>* center_codes,
                               const ProteinDB* query, const uint32_t& hash_K, const uint32_t& hash_L,
                               const double& hash_W, const double& hash_R, const std::string& output_file,
                               const Planes& planes, int device, std::string* err, std::vector<uint64_t>* table_sizes,
-                              uint64_t* n_windows, uint32_t probes, const std::vector<double>* radii) {
+                              uint64_t* n_windows, uint32_t probes, const std::vector<double>* radii,
+                              const std::vector<ProteinDB>* more) {
   const uint32_t dim = 8 * kmer_length, k = kmer_length;
+  const bool appended = more && !more->empty();
+  std::vector<uint64_t> part_end;
+  const ProteinDB joined = appended ? JoinProteinDBs(db_first, *more, &part_end) : ProteinDB();
+  const ProteinDB& db = appended ? joined : db_first;
   const size_t n_groups = query ? (query->start.empty() ? 0 : query->start.size() - 1) : centers.size();
   if (!RadiiMatch(radii, n_groups, err)) return HS_ERR_INVALID;
   if (!query && center_codes && center_codes->size() != centers.size() * (size_t)k) {
@@ -747,7 +807,7 @@ int SearchProteinsPerSequence(const ProteinDB& db, uint32_t kmer_length, const s
   }
   uint64_t n_win = 0;
   std::vector<uint32_t> win_pos(res.size() + 1);
-  st = hs_index_build_windows(h, res.data(), res.size(), seg.data(), seg.size() - 1, &n_win, win_pos.data());
+  st = BuildWindowsInParts(h, res, seg, part_end, &n_win, win_pos.data());
   if (st != HS_OK) {
     if (err) *err = std::string("index build: ") + hs_last_error(h);
     return st;

@@ -146,7 +146,8 @@ int SearchProteins(const ProteinDB& db, uint32_t kmer_length, const std::vector<
                    const uint32_t& hash_L, const double& hash_W, const double& hash_R,
                    const std::string& output_file, const Planes& planes, int device, std::string* err,
                    std::vector<uint64_t>* table_sizes = nullptr, uint64_t* n_windows = nullptr,
-                   bool best_per_position = false, const std::vector<double>* radii = nullptr, uint32_t topk = 0);
+                   bool best_per_position = false, const std::vector<double>* radii = nullptr, uint32_t topk = 0,
+                   const std::vector<ProteinDB>* more = nullptr);
 int SearchProteinsSharded(const ProteinDB& db, uint32_t kmer_length, const std::vector<Point>& centers,
                           const std::vector<std::string>& center_names, const uint32_t& hash_K,
                           const uint32_t& hash_L, const double& hash_W, const double& hash_R,
@@ -154,7 +155,11 @@ int SearchProteinsSharded(const ProteinDB& db, uint32_t kmer_length, const std::
                           const std::vector<int>& devices, bool use_comm, std::string* err,
                           std::vector<uint64_t>* table_sizes = nullptr, uint64_t* n_windows = nullptr,
                           bool best_per_position = false, const std::vector<uint8_t>* center_codes = nullptr,
-                          const std::vector<double>* radii = nullptr, uint32_t topk = 0);
+                          const std::vector<double>* radii = nullptr, uint32_t topk = 0,
+                          const std::vector<ProteinDB>* more = nullptr);
+// more (SearchProteins* all three; one GPU): further databases appended in order -- the index is built over db's windows
+// and grown by each of theirs (hs_index_append_windows), sequence numbers and names continue; the output is that of
+// one database holding all the sequences.
 // The per_sequence mode of SearchProteins: instead of the hits, one line per (centre, database protein) with a hit,
 // reduced on the device (hs_seq_match in include/hsearch.h; the hit list never reaches the host) --
 //   <centre name> <protein>#<its number> <hits> <offset of the best window> <its distance> <first> <last matched offset>
@@ -172,7 +177,8 @@ int SearchProteinsPerSequence(const ProteinDB& db, uint32_t kmer_length, const s
                               const double& hash_W, const double& hash_R, const std::string& output_file,
                               const Planes& planes, int device, std::string* err,
                               std::vector<uint64_t>* table_sizes = nullptr, uint64_t* n_windows = nullptr,
-                              uint32_t probes = 0, const std::vector<double>* radii = nullptr);
+                              uint32_t probes = 0, const std::vector<double>* radii = nullptr,
+                              const std::vector<ProteinDB>* more = nullptr);
 // center_codes (CentersFromKmers): the centres are k-mers of the exact table -- the one a FASTA
 // database is embedded from -- and travel to the GPU as residue codes (hs_query_codes: k bytes per
 // centre instead of 64 k); the hits are those of the embedded centres, bit for bit.

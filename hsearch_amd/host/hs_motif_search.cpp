@@ -80,6 +80,7 @@ const Opt kOpts[] = {
     {"per-sequence", 'S', "FASTA database: one line per (centre, protein) with a hit: count, best window, span (one GPU) [0]", false},
     {"query-fasta", 'q', "query proteins in place of -c: one line per (query protein, protein, diagonal) (implies --per-sequence 1)", false},
     {"topk", 't', "per centre only its N best hits, 1..64, in ascending (distance, k-mer index) (one GPU) [off: all hits]", false},
+    {"db-append", 'A', "FASTA database: a further FASTA file whose sequences follow -d's, appended to the built index on the GPU; repeatable (one GPU)", false},
 };
 
 // A points file has a line of numbers after its first name line; a FASTA file has residue letters.
@@ -108,6 +109,7 @@ void Help(const char* prog) {
 int main(int argc, const char* argv[]) {
   bool help = false;
   std::map<std::string, std::string> val;
+  std::vector<std::string> db_append;  // --db-append, in order
   for (int i = 1; i < argc; ++i) {
     std::string arg = argv[i];
     if (arg == "-help" || arg == "--help" || arg == "-?" || arg == "-about") {
@@ -128,6 +130,7 @@ int main(int argc, const char* argv[]) {
       return EXIT_FAILURE;
     }
     val[hit->long_name] = argv[++i];
+    if (std::string(hit->long_name) == "db-append") db_append.push_back(argv[i]);
   }
   if (argc > 1 && !help) {
     fprintf(stdout, "[WELCOME TO HSEARCH v1.0 -- MI355X]\n[%s", argv[0]);
@@ -157,6 +160,10 @@ int main(int argc, const char* argv[]) {
     return EXIT_FAILURE;
   }
   if (with_radii && val.count("threshold")) fprintf(stderr, "--radii given: -T is ignored\n");
+  if (!db_append.empty() && val.count("gpus") && atoi(val["gpus"].c_str()) > 1) {
+    fprintf(stderr, "ERROR: --db-append runs on one GPU: it cannot be combined with --gpus %s\n", val["gpus"].c_str());
+    return EXIT_FAILURE;
+  }
   uint32_t topk = 0;  // 0: all hits
   if (val.count("topk")) {
     char* end = nullptr;
@@ -215,6 +222,10 @@ int main(int argc, const char* argv[]) {
     std::vector<hsearch::Point> kmers, centers;
     std::vector<uint8_t> center_codes;  // -c <k-mers.fa>: the centres as rows of the coordinate table
     const bool fasta_db = LooksLikeFasta(val["db"]);
+    if (!db_append.empty() && !fasta_db) {
+      fprintf(stderr, "ERROR: --db-append needs a FASTA database: a points database cannot be appended to\n");
+      return EXIT_FAILURE;
+    }
     hsearch::ProteinDB prodb;
     if (fasta_db) {
       std::cout << "Read protein sequences from " << val["db"] << std::endl;
@@ -229,6 +240,14 @@ int main(int argc, const char* argv[]) {
       std::cout << "Read Kmers..." << std::endl;
       if (!hsearch::ReadPointsFile(val["db"], dim, &kmer_names, &kmers)) {
         fprintf(stderr, "cannot open %s\n", val["db"].c_str());
+        return EXIT_FAILURE;
+      }
+    }
+    std::vector<hsearch::ProteinDB> more(db_append.size());
+    for (size_t i = 0; i < db_append.size(); ++i) {
+      std::cout << "Read appended protein sequences from " << db_append[i] << std::endl;
+      if (!LooksLikeFasta(db_append[i]) || !hsearch::ReadProteinFasta(db_append[i], prodb.eq_swapped, &more[i])) {
+        fprintf(stderr, "ERROR: --db-append %s: cannot open it, or it is no FASTA file\n", db_append[i].c_str());
         return EXIT_FAILURE;
       }
     }
@@ -344,7 +363,7 @@ int main(int argc, const char* argv[]) {
                                                               ? nullptr : &center_codes,
                                                           query_fasta ? &qrydb : nullptr, hash_K, hash_L, hash_W, hash_R,
                                                           val["output"], planes, device, &err, &table_sizes, &n_windows,
-                                                          (uint32_t)probes, with_radii ? &radii : nullptr) :
+                                                          (uint32_t)probes, with_radii ? &radii : nullptr, &more) :
         fasta_db ? hsearch::SearchProteinsSharded(prodb, kmer_length, centers, center_names, hash_K, hash_L,
                                                   hash_W, hash_R, val["output"], planes, devices, use_comm,
                                                   &err, &table_sizes, &n_windows,
@@ -353,7 +372,7 @@ int main(int argc, const char* argv[]) {
                                                   // table: they go to the GPU as codes (hs_query_codes)
                                                   center_codes.empty() || val.count("centers-as-points")
                                                       ? nullptr : &center_codes,
-                                                  with_radii ? &radii : nullptr, topk)
+                                                  with_radii ? &radii : nullptr, topk, &more)
                  : hsearch::SearchSharded(kmers, centers, kmer_names, center_names, hash_K, hash_L, hash_W,
                                           hash_R, val["output"], planes, devices, use_comm, &err,
                                           &table_sizes, (uint32_t)probes, with_radii ? &radii : nullptr,

@@ -100,6 +100,9 @@ typedef struct hs_profile {
   uint64_t join_f6_batches;    /* of join_i8_batches: those whose query-streaming kernel was the FP6 form
                                   (hs_join6x_kernel: queries that are k-mers, k = 21..25).  join_row_bytes stays
                                   128 for them: the depth of the GEMM, not the bytes of an FP6 row (96) */
+  uint64_t append_rebuilds;    /* hs_index_append*: 1 if the last append fell back to the full build over the
+                                  concatenated codes (a fingerprint shared by two HashKey strings), else 0 */
+  uint64_t append_new_buckets; /* hs_index_append*: buckets the block created, summed over the tables */
 } hs_profile;
 
 typedef struct hs_index_info {
@@ -350,6 +353,57 @@ HS_API hs_status hs_index_shard_end(hs_handle* h, uint32_t key_seed);
 HS_API hs_status hs_index_save(hs_handle* h, const char* path);
 HS_API hs_status hs_index_load(hs_handle* h, const char* path);
 HS_API hs_status hs_index_file_check(const char* path, char* err, uint32_t err_cap);
+
+/* SURVEY 8(f) row 2, second half -- a built (or loaded) index GROWS by a block of m further k-mers, on the
+ * device.  After hs_index_append(h, B, m) on a handle whose index holds the k-mers A in id order, the handle is
+ * indistinguishable from one on which hs_index_build(h, A ++ B, n + m) was called: the new k-mers take the ids
+ * n .. n + m - 1; hs_index_info_get gives the same n, n_buckets, max_bucket and key_seed (device_bytes may differ);
+ * hs_index_save writes the same file byte for byte; every other entry point gives the same results.  The
+ * handle's settings (multi-probe, bucket partition, options) survive, as they survive a build.
+ * What it does NOT do again: no old residue code crosses PCIe, no old k-mer is hashed or sorted.  Bucket ints
+ * depend on the k-mer alone and a table is its entries ordered by (fingerprint, id), so per table the block is
+ * hashed, fingerprinted under the index's key_seed and grouped as a build groups a table, its buckets are looked
+ * up in the old directory, the two sorted directories are merged (an old bucket keeps its tuple: its first member
+ * is still its smallest id) and the bucket-ordered arrays are moved once, the block's members behind the old
+ * members of their bucket (hsearch_amd/csrc/hs_append.hip).
+ * MEMORY: the grown arrays are new allocations that replace the old ones, so the peak extra HBM is one grown
+ * copy of the index's arrays plus scratch sized by the block and by one table's directory -- never the build's
+ * n-sized hash and sort scratch.
+ * FINGERPRINT SEED: if a block bucket's fingerprint equals that of an old bucket, or of another block bucket,
+ * under a different HashKey string, the call runs the full build loop over the concatenated codes (already on
+ * the device) from seed 0 -- which is what hs_index_build over A ++ B ends with (hs_profile.append_rebuilds = 1).
+ * m = 0 is a successful no-op; appending to an index of 0 k-mers equals a build.
+ * hs_index_append_dev: d_codes in device memory of the handle's GPU, complete when the call is made.
+ * hs_index_append_windows: the windows of further sequences, enumerated as hs_index_build_windows enumerates
+ * them; *n_windows and window_pos (optional) cover the APPENDED windows only (positions in `residues`).  The
+ * result equals hs_index_build_windows over both residue buffers concatenated with their seq_starts joined.
+ * ERRORS detected before anything of the handle changes (the old index goes on answering): an unbuilt index is
+ * HS_ERR_STATE; n + m >= 2^31, a residue code outside the alphabet in the block (the _dev form finds it on the
+ * device, before any table is touched) and a seq_start that does not ascend are HS_ERR_INVALID.  Any LATER
+ * failure (a HIP error, no memory, fingerprints that collide for every seed) leaves the handle WITHOUT an index,
+ * as after hs_set_planes: calls return HS_ERR_STATE until the next build or load -- never a half-merged table.
+ * hs_profile after the call: ms_hash (block hash + fingerprints), ms_sort (block grouping, match, directory
+ * merge), ms_gather (block records, the move, pos_of), ms_total, append_rebuilds, append_new_buckets. */
+HS_API hs_status hs_index_append(hs_handle* h, const uint8_t* codes, uint64_t m);
+HS_API hs_status hs_index_append_dev(hs_handle* h, const uint8_t* d_codes, uint64_t m);
+HS_API hs_status hs_index_append_windows(hs_handle* h, const uint8_t* residues, uint64_t n_residues,
+                                         const uint64_t* seq_start, uint64_t n_seq,
+                                         uint64_t* n_windows, uint32_t* window_pos);
+
+/* The same rule for ONE table on the host (no GPU, no handle): the table's four arrays as hs_index_save writes
+ * them (ids [n], dir_key [nb], dir_start [nb + 1], dir_tuple [nb][K]; fingerprint seed `seed`) merged with the
+ * bucket ints block_ints [m][K] of m appended k-mers (ids n .. n + m - 1) into out_ids [n + m] and the directory
+ * out_dir_key [*nb_out], out_dir_start [*nb_out + 1], out_dir_tuple [*nb_out][K].  The directory follows the
+ * two-call capacity pattern: *nb_out <= nb + m is always set; dir_cap < *nb_out gives HS_ERR_CAPACITY with nothing
+ * written.  *collided = 1 (HS_OK, nothing written): one fingerprint under two HashKey strings, inside the block or
+ * between the block and the table -- the caller rebuilds under another seed.  An input table that breaks the
+ * content rules of hs_index_file_check is HS_ERR_INVALID (the collision verdict comes first: a directory key that
+ * equals a block fingerprint under another tuple is a collision, whatever else it is). */
+HS_API hs_status hs_index_table_append(const uint32_t* ids, const uint64_t* dir_key, const uint32_t* dir_start,
+                                       const int32_t* dir_tuple, uint64_t n, uint64_t nb,
+                                       const int32_t* block_ints, uint64_t m, uint32_t K, uint32_t seed,
+                                       uint32_t* out_ids, uint64_t* out_dir_key, uint32_t* out_dir_start,
+                                       int32_t* out_dir_tuple, uint64_t dir_cap, uint64_t* nb_out, uint32_t* collided);
 
 /* SURVEY 8(f) row 3 -- Kernel-LSH pre-grouping of whole proteins (pcluster.cpp:11-81).
  * hs_klsh_draw_planes: the planes KLSH::KLSH draws (lsh.cpp:17-38) from its default-seeded
