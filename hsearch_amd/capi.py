@@ -32,7 +32,7 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_density_tree_cut", "hs_query_topk", "hs_query_topk_dev", "hs_self_knn", "hs_self_knn_range",
            "hs_self_knn_dev", "hs_self_knn_range_dev", "hs_topk_merge", "hs_seq_match", "hs_seq_match_dev",
            "hs_window_id_start", "hs_seq_match_hits", "hs_seq_match_merge", "hs_join6_tables", "hs_join6_thresholds",
-           "hs_join6_selftest", "hs_index_append", "hs_index_append_dev", "hs_index_append_windows",
+           "hs_join6_selftest", "hs_join6_tile_offset", "hs_index_append", "hs_index_append_dev", "hs_index_append_windows",
            "hs_index_table_append"]
 
 TOPK_MAX = 64        # HS_TOPK_MAX: the widest row of query_topk / self_knn / topk_merge
@@ -707,6 +707,14 @@ def join6_thresholds(coords, kmers, r2):
     if st:
         raise HsError(st, "hs_join6_thresholds")
     return dict(rho64=rho64, c64=c64, rho0_64=rho0.value, rec=rec)
+
+
+def join6_tile_offset(nr, row, piece):
+    """Byte offset of 16-byte piece `piece` (0..7) of row `row` inside a gathered query tile of nr <= 32 rows of the
+    FP6 join (hs_join6_tile_offset; no GPU)."""
+    f = load().hs_join6_tile_offset
+    f.restype = C.c_uint32
+    return int(f(C.c_uint32(nr), C.c_uint32(row), C.c_uint32(piece)))
 
 
 def join6_selftest(device=0, variant=0):

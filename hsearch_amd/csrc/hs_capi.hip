@@ -2783,6 +2783,10 @@ struct Batch {
   const double* radii = nullptr;     // the batch's slice of the call's per-query radii (device), or null: r2 for all
 };
 
+// Bytes reserved per query row, in c16 and (in segment order) c16s: the widest fp16 row (208 halves), or the 128
+// bytes of a k <= 25 int8 row with the FP6 row behind it
+static size_t qrow_room() { return std::max<size_t>(208 * 2, 128 + (size_t)hs_join6_row_bytes()); }
+
 // The join filter's query rows, on stream s: from the codes, int8 from the centres, or fp16
 static hipError_t launch_qrows(hs_handle* h, const BatchPlan& p, const Batch& b, hipStream_t s) {
   const int k = (int)h->p.k;
@@ -2802,15 +2806,16 @@ static hipError_t launch_qrows(hs_handle* h, const BatchPlan& p, const Batch& b,
   return hs_launch_qprep(b.centers, b.nq, k, b.r2, h->c16.p, d_unsafe, s, b.radii);
 }
 
-// Where the FP6 rows of a batch sit in segment order: behind the room of its int8 rows in c16s
+// Where the FP6 rows of a batch sit in segment order: behind the room of its int8 rows in c16s.  (The join reads
+// a whole 32-row tile at a segment's ragged end too: at most 31 rows past the last, inside the 64 spare rows.)
 static char* c6t_of(hs_handle* h, const Batch& b) { return h->c16s.as<char>() + ((size_t)b.nql + 64) * 128; }
 
 // The query rows gathered into segment order (c16s)
 static hipError_t gather_qrows(hs_handle* h, const BatchPlan& p, const Batch& b) {
   if (p.f6) {
-    hipError_t e = hs_launch_gather_c8t(h->c16.as<char>() + (size_t)b.nq * 128, h->sorted_ql.as<uint32_t>(),
+    hipError_t e = hs_launch_gather_c6t(h->c16.as<char>() + (size_t)b.nq * 128, h->sorted_ql.as<uint32_t>(),
                                         h->seg_qoff.as<uint32_t>(), h->seg_of.as<uint32_t>(), b.nqs, (int)h->p.L,
-                                        (int)h->p.k, 0, c6t_of(h, b), h->stream, hs_join6_row_pieces());
+                                        c6t_of(h, b), h->stream);
     if (e != hipSuccess || !p.use_r) return e;
   }
   if (p.use_i8)
@@ -2877,7 +2882,7 @@ static hs_status prepare_queries(hs_handle* h, const QueryCall& c, const BatchPl
     }
   }
   if (p.use_join) {
-    HS_HIP(h, h->c16.reserve((size_t)b.nq * 208 * 2));
+    HS_HIP(h, h->c16.reserve((size_t)b.nq * qrow_room()));
     if (p.refine && !b.qcodes) HS_HIP(h, h->c8b.reserve((size_t)b.nq * hs_join8_row_bytes(k, p.wide)));
     HS_HIP(h, hipEventRecord(h->evx[EV_FORK], h->stream));
     HS_HIP(h, hipStreamWaitEvent(h->stream2, h->evx[EV_FORK], 0));
@@ -2929,7 +2934,7 @@ static hs_status hash_and_probe(hs_handle* h, const QueryCall& c, const BatchPla
 static hs_status group_segments(hs_handle* h, const BatchPlan& p, Batch& b) {
   if (!p.use_join) return HS_OK;
   const size_t n1 = (size_t)b.nql + 1;
-  HS_HIP(h, h->c16s.reserve(((size_t)b.nql + 64) * 208 * 2));
+  HS_HIP(h, h->c16s.reserve(((size_t)b.nql + 64) * qrow_room()));
   for (DevBuf* d : {&h->seg_keys, &h->seg_keys_sorted, &h->seg_key}) HS_HIP(h, d->reserve(n1 * 8));
   for (DevBuf* d : {&h->seg_vals, &h->sorted_ql, &h->seg_cnt, &h->seg_qoff, &h->seg_items, &h->item_off, &h->seg_of})
     HS_HIP(h, d->reserve(n1 * 4));

@@ -710,19 +710,22 @@ hipError_t hs_launch_refine_codes(const hs_tables_dev& tabs, const uint2* d_prov
                                   uint2* d_out, uint32_t* d_out_count, hipStream_t s);
 hipError_t hs_launch_gather_c8t(const void* d_c8, const uint32_t* d_sorted_ql, const uint32_t* d_seg_qoff,
                                 const uint32_t* d_seg_of, uint32_t nql, int L, int k, int wide, void* d_out,
-                                hipStream_t s, int pieces = 0 /* 16-byte pieces of a row; 0: the int8 row of k, wide */);
+                                hipStream_t s);
 // bytes of a quantised int8 row (32 per k-step: 128 for k <= 25, 192 for k <= 41 and for wide rows,
 // 256 for k <= 50) and the members of one work item of the wave-independent int8 join (128 / 64)
 int hs_join8_row_bytes(int k, int wide);
 uint32_t hs_join8_members_per_item(int k, int wide);
 uint32_t hs_join8_chunk_items(uint32_t n_items, int n_blocks, double pairs_per_item, uint32_t chunk);
 // hs_join6.hip: the FP6 (e2m3) form of the join for queries that are k-mers, k = 21..25, 4-column rows.
-// d_tab6: hs_join6_table_bytes() bytes (hs_j6_dev); query rows of hs_join6_row_pieces() 16-byte pieces, gathered
-// by hs_launch_gather_c8t with that piece count; member records (16 bytes per bucket entry) parallel to the
-// bucket-ordered packed copy.  G = items per counter access (hs_join8_chunk_items).
+// d_tab6: hs_join6_table_bytes() bytes (hs_j6_dev); query rows of hs_join6_row_bytes() bytes, gathered into
+// segment order by hs_launch_gather_c6t (the tile layout: hs_j6_tile_offset, hs_join6_tables.h); member records
+// (16 bytes per bucket entry) parallel to the bucket-ordered packed copy.  G = items per counter access
+// (hs_join8_chunk_items).
 size_t hs_join6_table_bytes();
 size_t hs_join6_ok_offset();  // of the int32 that says the tables are usable
-int hs_join6_row_pieces();
+int hs_join6_row_bytes();
+hipError_t hs_launch_gather_c6t(const void* d_c6, const uint32_t* d_sorted_ql, const uint32_t* d_seg_qoff,
+                                const uint32_t* d_seg_of, uint32_t nql, int L, void* d_out, hipStream_t s);
 hipError_t hs_launch_jtables6(const double* d_coords, int alphabet, void* d_tab6, hipStream_t s);
 hipError_t hs_launch_gather_rec6(const uint4* d_packed_all, const uint32_t* d_ids_sorted, uint32_t n, int k,
                                  const void* d_tab6, uint4* d_out_rec, hipStream_t s);

@@ -15,14 +15,16 @@
 // (entry r1 << 5 | r0 = the 48 bits of two residues: four lookups per member and lane), quarter 3 IS the
 // member's 16-byte record (t_rec6, built on the first batch that can use it) + 8 zero bytes.
 //
-// Query side: a row of 112 bytes = 7 pieces of 16: piece q = dwords 0..3 of quarter q; piece 4 + (q >> 1),
-// bytes 8 (q & 1) .. + 7 = dwords 4, 5 of quarter q; piece 6 = the float C = -(gamma + rho0), then zeros.
-// The rows are gathered into tile-fragment order by hs_gather_c8t_kernel with 7 pieces per row.  C is the
-// MFMA's C operand: the accumulator's column is the lane's query, so it is one value per lane and column tile
-// and costs no slot.  Encoding and range of C: a multiple of 2^-6, |C| <= 2^17 (values beyond are clamped to
-// +-2^17, which changes nothing: the other terms stay below 2^13, so such a query passes or fails every member
-// either way); every partial sum is then a multiple of 2^-6 below 2^18 + 2^13: exact in fp32.  The filter
-// passes a pair iff the accumulator's sign bit is clear.
+// Query side: a row of 128 bytes = 8 pieces of 16: piece q = dwords 0..3 of quarter q; piece 4 + q = dwords 4, 5
+// of quarter q, then the float C = -(gamma + rho0) twice.  The rows are gathered into segment order by
+// hs_gather_c6t_kernel, a full tile of 32 rows in the kernel's lane order (hs_j6_tile_offset, hs_join6_tables.h):
+// a lane's two pieces of a column tile are two loads at 16 lane + a constant, they land in consecutive registers
+// that ARE the MFMA's B operand (the instruction reads the first 6; C rides in the seventh), and nothing is
+// computed or copied for them.  C stays OUT of the product: the MFMA's C operand is the constant
+// 0, the accumulator's column is the lane's query, and the filter passes a pair iff accumulator >= -C.
+// Encoding and range of C: a multiple of 2^-6, |C| <= 2^17 (values beyond are clamped to +-2^17, which changes
+// nothing: the other terms stay below 2^13, so such a query passes or fails every member either way; a NaN
+// radius gives -2^17).  The accumulators are multiples of 2^-6 below 2^13: exact in fp32, and so is the compare.
 #include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -36,12 +38,14 @@
 
 namespace {
 
+typedef int intx3 __attribute__((ext_vector_type(3)));
+typedef int intx4 __attribute__((ext_vector_type(4)));
 typedef int intx6 __attribute__((ext_vector_type(6)));
 typedef int intx8 __attribute__((ext_vector_type(8)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t JRES = 256;   // survivor slots a wave reserves per counter access (as hs_join8.hip)
-constexpr int PIECES = 7;        // 16-byte pieces of a query row
+constexpr int PIECES = HS_J6_ROW_BYTES / 16;  // 16-byte pieces of a query row
 
 __device__ __forceinline__ void close_reservation(uint2* __restrict__ prov, uint32_t res_base, uint32_t res_used,
                                                   uint32_t prov_cap, int lane) {
@@ -56,10 +60,10 @@ __device__ __forceinline__ uint4 uniform4(const uint4 v) {
 
 // The tile product of the kernel and of its self-test: D = A (16 x 128, e2m3) x B (128 x 16, e2m3) + C.
 // SCALE = 0 in both block-scale operands selects the unscaled v_mfma_f32_16x16x128_f8f6f4 (one instruction).
+// (the operands are 6 dwords; the kernel's B comes in the registers it was loaded into, C behind it unread)
 template <int SCALE = 0>
-__device__ __forceinline__ floatx4 tile_mfma6(const intx6 a, const intx6 b, const floatx4 c) {
+__device__ __forceinline__ floatx4 tile_mfma6(const intx6 a, const intx8 b8, const floatx4 c) {
   const intx8 a8 = __builtin_shufflevector(a, a, 0, 1, 2, 3, 4, 5, -1, -1);
-  const intx8 b8 = __builtin_shufflevector(b, b, 0, 1, 2, 3, 4, 5, -1, -1);
   return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a8, b8, c, 2, 2, 0, SCALE, 0, SCALE);
 }
 
@@ -140,64 +144,90 @@ __global__ __launch_bounds__(256) void hs_qprep6_codes_kernel(const uint8_t* __r
   int64_t c64 = hs_j6_query_c64(sum_r, T->s2_half, r2, k, T->rpos64);
   c64 = c64 > HS_J6_CMAX ? HS_J6_CMAX : c64 < -HS_J6_CMAX ? -HS_J6_CMAX : c64;
   if (!(r2 == r2)) c64 = -HS_J6_CMAX;  // (a NaN radius: no hit)
-  uint32_t* row = out + (uint64_t)q * (PIECES * 4);
+  const uint32_t cbits = __float_as_uint((float)c64 * (1.0f / 64.0f));
+  uint4* row = reinterpret_cast<uint4*>(out) + (uint64_t)q * PIECES;
 #pragma unroll
   for (int a = 0; a < 4; ++a) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) row[4 * a + i] = W[a][i];
-    row[16 + 4 * (a >> 1) + 2 * (a & 1)] = W[a][4];
-    row[16 + 4 * (a >> 1) + 2 * (a & 1) + 1] = W[a][5];
+    row[a] = make_uint4(W[a][0], W[a][1], W[a][2], W[a][3]);
+    row[4 + a] = make_uint4(W[a][4], W[a][5], cbits, cbits);
   }
-  row[24] = __float_as_uint((float)c64 * (1.0f / 64.0f));
-  row[25] = row[26] = row[27] = 0u;
+}
+
+// The rows into segment order, tile by tile in the layout of hs_j6_tile_offset.  EIGHT lanes per probe, one per
+// piece (hs_gather_c8t_kernel says why): a load of the wave reads 8 whole rows, and its stores fill 128-byte runs.
+__global__ __launch_bounds__(256) void hs_gather_c6t_kernel(const uint4* __restrict__ c6,
+                                                            const uint32_t* __restrict__ sorted_ql,
+                                                            const uint32_t* __restrict__ seg_qoff,
+                                                            const uint32_t* __restrict__ seg_of, uint32_t nql, int L,
+                                                            char* __restrict__ out) {
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+  const uint32_t p = t >> 3, g = t & 7u;
+  if (p >= nql) return;
+  const uint32_t lo = seg_of[p];
+  const uint32_t qoff = seg_qoff[lo], nQ = seg_qoff[lo + 1] - qoff;
+  const uint32_t local = p - qoff, tile = local >> 5, j = local & 31u;
+  const uint32_t nr = min(32u, nQ - (tile << 5));
+  const uint32_t q = sorted_ql[p] / (uint32_t)L;
+  char* dst = out + (uint64_t)(qoff + (tile << 5)) * HS_J6_ROW_BYTES + hs_j6_tile_offset(nr, j, g);
+  *reinterpret_cast<uint4*>(dst) = c6[(uint64_t)q * PIECES + g];
 }
 
 // ------------------------------------------------------------------------------------ join
-// Query tile of nr rows at segment-order row row0 (hs_gather_c8t_kernel: piece g of row j at g nr + j): lane (n, q)
-// takes the 24 bytes of quarter q and C of row 16 c + n for column tile c.  Rows past the end repeat the last one
-// (masked when survivors are written).
-__device__ __forceinline__ void load_btile6(intx6 (&B)[2], float (&C)[2], const uint4* __restrict__ c6t,
-                                            uint32_t row0, uint32_t nr, int lane) {
-  const char* t0 = reinterpret_cast<const char*>(c6t + (uint64_t)row0 * PIECES);
-  const uint32_t n = (uint32_t)lane & 15u, q = (uint32_t)lane >> 4;
+// Query tile of nr rows at segment-order row row0 (hs_j6_tile_offset): lane (n, q) takes the pieces q and 4 + q
+// of row 16 c + n for column tile c, 7 dwords that ARE the B operand with C behind it.  Four loads at the tile's
+// (scalar) base + 16 lane + 1024 (2 c + h): no address is computed per load.  What shapes the code:
+//   - The piece's last dword is not loaded.  A register nothing reads is handed to the sign test as scratch while
+//     its load is still in flight, and the wave then waits for every load at the top of the next tile.
+//   - The full-tile loads are issued for EVERY tile, and the ragged last tile of a segment (wave-uniform branch)
+//     loads its rows over them: rows past the end repeat the last one (masked when survivors are written).  The
+//     4 KB read at a ragged tile stay inside the rows' buffer (hs_capi.hip reserves 64 rows more than there are).
+//     As an if / else the two forms leave the compiler a path with neither load, the waits of the loop are then
+//     counted as if this tile's loads could be the newest, and every third tile waits for all loads in flight.
+__device__ __forceinline__ void load_btile6(intx8 (&B)[2], const char* __restrict__ c6t, uint32_t row0, uint32_t nr,
+                                            int lane) {
+  const char* t0 = c6t + (uint64_t)row0 * HS_J6_ROW_BYTES;
+  const char* base = t0 + 16 * lane;
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
-    const uint32_t row = min(16u * (uint32_t)c + n, nr - 1u);
-    const uint4 hi = *reinterpret_cast<const uint4*>(t0 + (q * nr + row) * 16u);
-    const uint2 lo = *reinterpret_cast<const uint2*>(t0 + ((4u + (q >> 1)) * nr + row) * 16u + 8u * (q & 1u));
-    C[c] = *reinterpret_cast<const float*>(t0 + (6u * nr + row) * 16u);
-    B[c] = intx6{(int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w, (int)lo.x, (int)lo.y};
+    const intx4 hi = *reinterpret_cast<const intx4*>(base + 2048 * c);
+    const intx3 lo = *reinterpret_cast<const intx3*>(base + 2048 * c + 1024);
+    B[c] = intx8{hi.x, hi.y, hi.z, hi.w, lo.x, lo.y, lo.z, 0};
+  }
+  if (__builtin_expect(nr != 32u, 0)) {
+    const uint32_t n = (uint32_t)lane & 15u, q = (uint32_t)lane >> 4;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const uint32_t row = min(16u * (uint32_t)c + n, nr - 1u);
+      const intx4 hi = *reinterpret_cast<const intx4*>(t0 + hs_j6_tile_offset(nr, row, q));
+      const intx3 lo = *reinterpret_cast<const intx3*>(t0 + hs_j6_tile_offset(nr, row, 4u + q));
+      B[c] = intx8{hi.x, hi.y, hi.z, hi.w, lo.x, lo.y, lo.z, 0};
+    }
   }
 }
 
-// One step of the sign test of a group's 32 accumulators (hs_join8.hip sign_step_x, on the floats' bit patterns:
-// a float is negative, or -0, exactly when its pattern is a negative int): the signed maximum on a tree of
-// three-input maxima, 16 steps; the result w[15] is negative iff no pair of the group passed.
-__device__ __forceinline__ void sign_step6(int g, const floatx4 (&acc)[4][2], int (&w)[16]) {
-  auto v = [&](int i) { return __float_as_int(acc[i >> 3][(i >> 2) & 1][i & 3]); };
-  if (g < 10) w[g] = max(max(v(3 * g), v(3 * g + 1)), v(3 * g + 2));
-  else if (g < 13) w[g] = max(max(w[3 * (g - 10)], w[3 * (g - 10) + 1]), w[3 * (g - 10) + 2]);
-  else if (g == 13) w[13] = max(max(w[9], v(30)), v(31));
-  else if (g == 14) w[14] = max(max(w[10], w[11]), w[12]);
-  else w[15] = max(w[13], w[14]);
+// One step of the test of a group's 32 accumulators against their queries' thresholds.  The 16 accumulators a
+// lane holds of column tile c belong to ONE query, so their maximum, on a tree of three-input maxima (8 steps per
+// column tile, the result in w[8 c + 7]), is compared with -C once: no pair of the group passed iff both fail.
+__device__ __forceinline__ float max3f(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
+__device__ __forceinline__ void sign_step6(int g, const floatx4 (&acc)[4][2], float (&w)[16]) {
+  const int c = g >> 3, s = g & 7, o = 8 * c;
+  auto v = [&](int i) { return acc[i >> 2][c][i & 3]; };
+  if (s < 5) w[g] = max3f(v(3 * s), v(3 * s + 1), v(3 * s + 2));
+  else if (s == 5) w[g] = max3f(w[o], w[o + 1], w[o + 2]);
+  else if (s == 6) w[g] = max3f(w[o + 3], w[o + 4], v(15));
+  else w[g] = max3f(w[o + 5], w[o + 6], v(15));  // (v(15) a second time: a two-input maximum of values the
+                                                 // compiler cannot trace costs two more instructions here)
   asm volatile("" : "+v"(w[g]));
 }
-
-__device__ __forceinline__ uint32_t and_tree6(const floatx4 (&acc)[4][2]) {
-  uint32_t a = 0xffffffffu;
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a &= __float_as_uint(acc[t][c][i]);
-  return a;
+__device__ __forceinline__ bool group_pass6(const float (&w)[16], const float (&C)[2]) {
+  return (w[7] >= -C[0]) | (w[15] >= -C[1]);
 }
 
 // Survivors of one group (row tiles T0 .. T0 + 3) against the 32 queries at segment-relative offset qc
 __device__ __forceinline__ void emit_survivors6(const floatx4 (&acc)[4][2], int T0, uint32_t qc, uint32_t qoff,
                                                 uint32_t q_end, uint32_t wbase, uint32_t M, uint32_t mstart,
-                                                int lane, uint32_t& res_base, uint32_t& res_used,
+                                                const float (&C)[2], int lane, uint32_t& res_base,
+                                                uint32_t& res_used,
                                                 uint32_t* __restrict__ prov_count, uint32_t prov_cap,
                                                 uint2* __restrict__ prov) {
   const uint32_t n = (uint32_t)lane & 15u, q = (uint32_t)lane >> 4;
@@ -205,12 +235,11 @@ __device__ __forceinline__ void emit_survivors6(const floatx4 (&acc)[4][2], int 
   for (int t = 0; t < 4; ++t)
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-      const uint32_t any = __float_as_uint(acc[t][c][0]) & __float_as_uint(acc[t][c][1]) &
-                           __float_as_uint(acc[t][c][2]) & __float_as_uint(acc[t][c][3]);
-      if (!__ballot((int)any >= 0)) continue;  // no survivor in this 16 x 16 tile
+      const float thr = -C[c];
       uint32_t mask = 0;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) mask |= (__float_as_int(acc[t][c][i]) >= 0 ? 1u : 0u) << i;
+      for (int i = 0; i < 4; ++i) mask |= (acc[t][c][i] >= thr ? 1u : 0u) << i;
+      if (!__ballot(mask != 0)) continue;  // no survivor in this 16 x 16 tile
       const uint32_t col = qc + 16u * (uint32_t)c + n;
       if (!(col < q_end)) mask = 0u;
       const uint32_t ql = HS_PROV_INDIRECT | (qoff + col);
@@ -249,7 +278,7 @@ __device__ __forceinline__ void emit_survivors6(const floatx4 (&acc)[4][2], int 
 // steps of the sign test behind each.
 __global__ __launch_bounds__(256, 2) void hs_join6x_kernel(
     const uint4* __restrict__ desc, uint32_t n_items, const uint4* __restrict__ packed_base,
-    const uint4* __restrict__ rec_base, const uint4* __restrict__ c6t, const hs_j6_dev* __restrict__ T,
+    const uint4* __restrict__ rec_base, const char* __restrict__ c6t, const hs_j6_dev* __restrict__ T,
     uint32_t* __restrict__ prov_count, uint32_t prov_cap, uint2* __restrict__ prov,
     uint32_t* __restrict__ item_counter, uint32_t G, const uint32_t* __restrict__ n_items_dev, uint32_t xcd_run) {
   if (n_items_dev) n_items = min(n_items, __builtin_amdgcn_readfirstlane(*n_items_dev));
@@ -311,8 +340,7 @@ __global__ __launch_bounds__(256, 2) void hs_join6x_kernel(
   uint4 mk[RT];
   constexpr int NB = 3;  // query tiles in flight per wave: the one in use + two prefetched
   constexpr uint32_t GQ = 32 * NB;
-  intx6 Bq[NB][2];
-  float Cq[NB][2];
+  intx8 Bq[NB][2];
 #define HS_LOAD_MEMBERS(D0)                                                              \
   {                                                                                      \
     const int64_t off_ = (int64_t)(((uint64_t)(D0).y << 32) | (uint64_t)(D0).x);         \
@@ -327,7 +355,7 @@ __global__ __launch_bounds__(256, 2) void hs_join6x_kernel(
 #define HS_LOAD_GROUP(ROW, Q0, QEND)                                                             \
   _Pragma("unroll") for (int u = 0; u < NB; ++u) {                                               \
     const uint32_t qu_ = (Q0) + 32u * u < (QEND) ? (Q0) + 32u * u : (Q0);                        \
-    load_btile6(Bq[u], Cq[u], c6t, (ROW) + qu_, min(32u, (QEND) - qu_), lane);                   \
+    load_btile6(Bq[u], c6t, (ROW) + qu_, min(32u, (QEND) - qu_), lane);                          \
   }
   HS_LOAD_MEMBERS(d0)
   {
@@ -369,6 +397,7 @@ __global__ __launch_bounds__(256, 2) void hs_join6x_kernel(
 #pragma unroll
       for (int c = 0; c < 2; ++c) accY[t][c] = __builtin_nondeterministic_value(accY[t][c]);
     bool y_live = false;
+    float Cy[2] = {0.0f, 0.0f};
     uint32_t prev_qc = q_begin;
     const uint32_t n_groups = HS_N_GROUPS(d1);
     uint32_t qc0 = HS_FIRST_Q(d1);
@@ -383,54 +412,57 @@ __global__ __launch_bounds__(256, 2) void hs_join6x_kernel(
 #pragma unroll
       for (int u = 0; u < NB; ++u) {
         const uint32_t qc = qc0 + 32u * (uint32_t)u;
-        intx6 (&B)[2] = Bq[u];
+        intx8 (&B)[2] = Bq[u];
         if (u == 0 || qc < q_end) {
-          const floatx4 Cv[2] = {floatx4{Cq[u][0], Cq[u][0], Cq[u][0], Cq[u][0]},
-                                 floatx4{Cq[u][1], Cq[u][1], Cq[u][1], Cq[u][1]}};
-          // ---- phase 1: X <- row tiles 0..3 x B + C, beside the sign test of Y (previous query tile)
-          int wY[16];
+          const floatx4 zero = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
+          const float Cx[2] = {__int_as_float(B[0][6]), __int_as_float(B[1][6])};
+          // ---- phase 1: X <- row tiles 0..3 x B, beside the test of Y (previous query tile, its C in Cy)
+          float wY[16];
 #pragma unroll
           for (int g = 0; g < 8; ++g) {
             const int t = g >> 1, c = g & 1;
-            accX[t][c] = tile_mfma6(A[t], B[c], Cv[c]);
+            accX[t][c] = tile_mfma6(A[t], B[c], zero);
             if (y_live) {  // (the item's first tile: Y holds nothing yet)
               sign_step6(2 * g, accY, wY);
               sign_step6(2 * g + 1, accY, wY);
             }
             __builtin_amdgcn_sched_barrier(0);
           }
-          const uint32_t sY = y_live ? (uint32_t)wY[15] : 0x80000000u;
-          if (y_live && __ballot((int)sY >= 0))
-            emit_survivors6(accY, 4, prev_qc, qoff, q_end, wbase, M, mstart, lane, res_base, res_used, prov_count,
-                            prov_cap, prov);
+          if (y_live && __ballot(group_pass6(wY, Cy)))
+            emit_survivors6(accY, 4, prev_qc, qoff, q_end, wbase, M, mstart, Cy, lane, res_base, res_used,
+                            prov_count, prov_cap, prov);
           y_live = true;
-          // ---- phase 2: Y <- row tiles 4..7 x B + C, beside the sign test of X
-          int wX[16];
+          // ---- phase 2: Y <- row tiles 4..7 x B, beside the test of X
+          float wX[16];
 #pragma unroll
           for (int g = 0; g < 8; ++g) {
             const int t = g >> 1, c = g & 1;
-            accY[t][c] = tile_mfma6(A[4 + t], B[c], Cv[c]);
+            accY[t][c] = tile_mfma6(A[4 + t], B[c], zero);
             sign_step6(2 * g, accX, wX);
             sign_step6(2 * g + 1, accX, wX);
             __builtin_amdgcn_sched_barrier(0);
           }
-          const uint32_t sX = (uint32_t)wX[15];
-          if (__ballot((int)sX >= 0))
-            emit_survivors6(accX, 0, qc, qoff, q_end, wbase, M, mstart, lane, res_base, res_used, prov_count,
+          if (__ballot(group_pass6(wX, Cx)))
+            emit_survivors6(accX, 0, qc, qoff, q_end, wbase, M, mstart, Cx, lane, res_base, res_used, prov_count,
                             prov_cap, prov);
           prev_qc = qc;
+          // (the tile's registers are loaded anew below and Y is tested a phase later: its C moves out of them
+          // here, in so many words -- left to itself the compiler loads every tile elsewhere and copies it)
+          asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=&v"(Cy[0]), "=v"(Cy[1]) : "v"(Cx[0]), "v"(Cx[1]));
         }
         const uint32_t nb = nq0 + 32u * (uint32_t)u < nqend ? nq0 + 32u * (uint32_t)u : nq0;
-        load_btile6(B, Cq[u], c6t, nrow + nb, min(32u, nqend - nb), lane);
+        load_btile6(B, c6t, nrow + nb, min(32u, nqend - nb), lane);
       }
       qc0 = nq0;
     };
     do_group(0);
     for (uint32_t gi = 1; gi < n_groups; ++gi) do_group(gi);
     {  // the item's last Y group
-      const uint32_t sY = and_tree6(accY);
-      if (__ballot((int)sY >= 0))
-        emit_survivors6(accY, 4, prev_qc, qoff, q_end, wbase, M, mstart, lane, res_base, res_used, prov_count,
+      float wY[16];
+#pragma unroll
+      for (int g = 0; g < 16; ++g) sign_step6(g, accY, wY);
+      if (__ballot(group_pass6(wY, Cy)))
+        emit_survivors6(accY, 4, prev_qc, qoff, q_end, wbase, M, mstart, Cy, lane, res_base, res_used, prov_count,
                         prov_cap, prov);
     }
     if (!has_next) break;
@@ -502,7 +534,8 @@ __global__ __launch_bounds__(64) void hs_join6_selftest_kernel(uint32_t* __restr
   }
   const float cf = (float)st_c64(cs, n) * (1.0f / 64.0f);
   const floatx4 d = tile_mfma6<SCALE>(intx6{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)a[4], (int)a[5]},
-                                      intx6{(int)b[0], (int)b[1], (int)b[2], (int)b[3], (int)b[4], (int)b[5]},
+                                      intx8{(int)b[0], (int)b[1], (int)b[2], (int)b[3], (int)b[4], (int)b[5],
+                                            __float_as_int(cf), __float_as_int(cf)},
                                       floatx4{cf, cf, cf, cf});
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -533,7 +566,15 @@ hipError_t hs_launch_jtables6(const double* d_coords, int alphabet, void* d_tab6
 
 size_t hs_join6_table_bytes() { return sizeof(hs_j6_dev); }
 size_t hs_join6_ok_offset() { return offsetof(hs_j6_dev, ok); }
-int hs_join6_row_pieces() { return PIECES; }
+int hs_join6_row_bytes() { return HS_J6_ROW_BYTES; }
+
+hipError_t hs_launch_gather_c6t(const void* d_c6, const uint32_t* d_sorted_ql, const uint32_t* d_seg_qoff,
+                                const uint32_t* d_seg_of, uint32_t nql, int L, void* d_out, hipStream_t s) {
+  if (!nql) return hipSuccess;
+  hs_gather_c6t_kernel<<<blocks_for((uint64_t)nql * PIECES), 256, 0, s>>>((const uint4*)d_c6, d_sorted_ql, d_seg_qoff,
+                                                                          d_seg_of, nql, L, (char*)d_out);
+  return hipGetLastError();
+}
 
 hipError_t hs_launch_gather_rec6(const uint4* d_packed_all, const uint32_t* d_ids_sorted, uint32_t n, int k,
                                  const void* d_tab6, uint4* d_out_rec, hipStream_t s) {
@@ -556,7 +597,7 @@ hipError_t hs_launch_join6x(const uint4* d_desc, uint32_t n_items, const uint4* 
                             uint32_t prov_cap, uint2* d_prov, uint32_t* d_item_counter, int n_blocks,
                             const uint32_t* d_n_items, uint32_t G, uint32_t xcd_run, hipStream_t s) {
   if (!n_items) return hipSuccess;
-  hs_join6x_kernel<<<n_blocks, 256, 0, s>>>(d_desc, n_items, d_packed_base, d_rec_base, (const uint4*)d_c6t,
+  hs_join6x_kernel<<<n_blocks, 256, 0, s>>>(d_desc, n_items, d_packed_base, d_rec_base, (const char*)d_c6t,
                                             (const hs_j6_dev*)d_tab6, d_prov_count, prov_cap, d_prov, d_item_counter,
                                             G, d_n_items, xcd_run);
   return hipGetLastError();
@@ -617,6 +658,12 @@ HS_API hs_status hs_join6_thresholds(const double* coords, uint32_t alphabet, co
     }
   }
   return HS_OK;
+}
+
+// The layout the gather writes and the kernel reads (hs_j6_tile_offset), for a test without a GPU
+HS_API uint32_t hs_join6_tile_offset(uint32_t nr, uint32_t row, uint32_t piece) {
+  if (nr < 1 || nr > 32 || row >= nr || piece >= (uint32_t)PIECES) return 0xffffffffu;
+  return hs_j6_tile_offset(nr, row, piece);
 }
 
 // GPU: the kernel's tile product against int64 arithmetic on rows at the format's extremes (see the kernel).

@@ -197,3 +197,17 @@ __host__ __device__ inline int64_t hs_j6_query_c64(double sum_r, double s2_half,
   const int64_t g64 = (int64_t)floor(g * 64.0) - 1;
   return -(g64 + (int64_t)k * rpos64);
 }
+
+// The query rows in segment order (hs_gather_c6t_kernel writes them, hs_join6x_kernel reads them).  A row is 8
+// pieces of 16 bytes: piece g < 4 = dwords 0..3 of lane quarter g, piece 4 + g = {dwords 4, 5 of quarter g, C, C}.
+// Tiles of 32 rows are densely packed, tile t of a segment at 128 bytes x (the segment's first row + 32 t); the
+// byte offset of piece g of row j inside a tile of nr rows:
+//   full (nr = 32)   four planes of 1 KB in the kernel's lane order: plane 2 c + (g >> 2) holds the piece of row
+//                    16 c + n, quarter q = g & 3 at byte 16 (16 q + n) -- lane 16 q + n loads its operand of
+//                    column tile c at 16 lane + 1024 (2 c) and + 1024 (2 c + 1), with no address arithmetic
+//   ragged (nr < 32) piece-major, piece g of row j at 16 (g nr + j): the last tile of a segment, nr x 128 bytes
+#define HS_J6_ROW_BYTES 128
+__host__ __device__ inline uint32_t hs_j6_tile_offset(uint32_t nr, uint32_t j, uint32_t g) {
+  if (nr == 32u) return ((2u * (j >> 4) + (g >> 2)) << 10) + 16u * (16u * (g & 3u) + (j & 15u));
+  return 16u * (g * nr + j);
+}

@@ -2337,10 +2337,10 @@ uint32_t hs_join8_members_per_item(int k, int wide) {
 
 hipError_t hs_launch_gather_c8t(const void* d_c8, const uint32_t* d_sorted_ql, const uint32_t* d_seg_qoff,
                                 const uint32_t* d_seg_of, uint32_t nql, int L, int k, int wide, void* d_out,
-                                hipStream_t s, int pieces) {
+                                hipStream_t s) {
   if (!nql) return hipSuccess;
   hs_gather_c8t_kernel<<<blocks_for((uint64_t)nql * 8), 256, 0, s>>>((const int8_t*)d_c8, d_sorted_ql, d_seg_qoff, d_seg_of, nql,
-                                                       L, pieces ? pieces : 2 * ks_of(k, wide != 0), (uint4*)d_out);
+                                                       L, 2 * ks_of(k, wide != 0), (uint4*)d_out);
   return hipGetLastError();
 }
 

@@ -210,6 +210,12 @@ HS_API hs_status hs_join6_tables(const double* coords, uint32_t alphabet, double
 HS_API hs_status hs_join6_thresholds(const double* coords, uint32_t alphabet, const uint8_t* kmers, uint64_t n,
                                      uint32_t k, const double* r2, int64_t* rho64, int64_t* c64, int64_t* rho0_64,
                                      uint32_t* rec);
+/* Where the gathered query rows of the FP6 join lie, on the host: a row is 8 pieces of 16 bytes (piece g < 4 =
+ * dwords 0..3 of the operand's lane quarter g, piece 4 + g = dwords 4, 5 of quarter g and the threshold C twice);
+ * the byte offset of piece `piece` of row `row` inside a tile of nr <= 32 rows (a full tile: four 1 KB planes in
+ * the kernel's lane order; the ragged last tile of a segment: piece-major).  A bijection onto nr * 128 bytes.
+ * 0xffffffff for arguments out of range. */
+HS_API uint32_t hs_join6_tile_offset(uint32_t nr, uint32_t row, uint32_t piece);
 /* GPU: hs_join6x_kernel's tile product (v_mfma_f32_16x16x128_f8f6f4, e2m3 operands, the kernel's lane map) on
  * rows at the format's extremes -- all-maximum, alternating signs, thresholds of +-2^17, pseudo-random codes --
  * against int64 arithmetic on the device.  variant 0: as the kernel issues it; 1: with explicit block scales of
