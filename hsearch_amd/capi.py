@@ -33,7 +33,8 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_self_knn_dev", "hs_self_knn_range_dev", "hs_topk_merge", "hs_seq_match", "hs_seq_match_dev",
            "hs_window_id_start", "hs_seq_match_hits", "hs_seq_match_merge", "hs_join6_tables", "hs_join6_thresholds",
            "hs_join6_selftest", "hs_join6_tile_offset", "hs_index_append", "hs_index_append_dev", "hs_index_append_windows",
-           "hs_index_table_append"]
+           "hs_index_table_append", "hs_index_remove", "hs_index_remove_dev", "hs_index_remove_ranges",
+           "hs_index_table_remove"]
 
 TOPK_MAX = 64        # HS_TOPK_MAX: the widest row of query_topk / self_knn / topk_merge
 NO_ID = 0xffffffff   # the id and table of an unused entry of such a row (its distance is +inf)
@@ -63,7 +64,8 @@ class _Profile(C.Structure):
                 ("join_row_bytes", C.c_uint32), ("join_wide", C.c_uint32), ("join_items_resident", C.c_uint64),
                 ("join_async_retries", C.c_uint64), ("queries_recognised", C.c_uint64),
                 ("join_f6_batches", C.c_uint64), ("append_rebuilds", C.c_uint64),
-                ("append_new_buckets", C.c_uint64)]
+                ("append_new_buckets", C.c_uint64), ("remove_rebuilds", C.c_uint64),
+                ("remove_dead_buckets", C.c_uint64), ("remove_retupled", C.c_uint64)]
 
 
 class _IndexInfo(C.Structure):
@@ -273,6 +275,18 @@ def load(hooks=False):
                                                   C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                                   C.POINTER(C.c_uint32)]
+        # index remove: (h, ids, m, new_id); ranges: (h, first, count, n_ranges, new_id); table_remove: include/hsearch.h
+        if hasattr(lib, "hs_index_remove"):
+            for fn in (lib.hs_index_remove, lib.hs_index_remove_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+            lib.hs_index_remove_ranges.restype = C.c_int
+            lib.hs_index_remove_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+            lib.hs_index_table_remove.restype = C.c_int
+            lib.hs_index_table_remove.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                                  C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_uint64)]
         _libs[hooks] = lib
     return _libs[hooks]
 
@@ -779,6 +793,50 @@ def index_table_append(ids, dir_key, dir_start, dir_tuple, block_ints, seed=0, o
     return o_ids[:n + m], o_key[:nbo], o_start[:nbo + 1], o_tuple.reshape(-1, K)[:nbo]
 
 
+def index_table_remove(ids, dir_key, dir_start, dir_tuple, dead_ids, ints, seed=0, out=None):
+    """hs_index_table_remove: one table (ids [n], dir_key [nb], dir_start [nb + 1], dir_tuple [nb][K], as hs_index_save
+    writes them) without the ids `dead_ids` (any order, duplicates allowed), on the host.  ints [n][K]: bucket ints by
+    OLD id (only the rows of k-mers that become a bucket's first member are read; None where there is none).  Returns
+    (ids [n'], dir_key, dir_start, dir_tuple) of the shrunken table.  out: the four arrays to write into; their
+    directory capacity is len(out[1]).  An id >= n or an invalid table raises HsError(HS_ERR_INVALID)."""
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    dir_key = np.ascontiguousarray(dir_key, dtype=np.uint64)
+    dir_start = np.ascontiguousarray(dir_start, dtype=np.uint32)
+    dir_tuple = np.ascontiguousarray(dir_tuple, dtype=np.int32)
+    dead_ids = np.ascontiguousarray(dead_ids, dtype=np.uint32).reshape(-1)
+    n, nb, m = len(ids), len(dir_key), len(dead_ids)
+    if ints is not None:
+        ints = np.ascontiguousarray(ints, dtype=np.int32)
+        K = ints.shape[1]
+        assert ints.shape[0] == n
+    else:
+        K = dir_tuple.shape[1]
+    assert len(dir_start) == nb + 1 and dir_tuple.size == nb * K
+    lib = load()
+    n_out, nb_out = C.c_uint64(0), C.c_uint64(0)
+
+    def call(o_ids, o_key, o_start, o_tuple, cap):
+        return lib.hs_index_table_remove(_vp(ids), _vp(dir_key), _vp(dir_start), _vp(dir_tuple), C.c_uint64(n),
+                                         C.c_uint64(nb), _vp(dead_ids), C.c_uint64(m),
+                                         None if ints is None else _vp(ints), C.c_uint32(K), C.c_uint32(seed),
+                                         o_ids, o_key, o_start, o_tuple, C.c_uint64(cap), C.byref(n_out),
+                                         C.byref(nb_out))
+    if out is None:
+        st = call(None, None, None, None, 0)       # the two-call pattern: the counts first
+        if st not in (HS_OK, HS_ERR_CAPACITY):
+            raise HsError(st, "hs_index_table_remove")
+        cap = int(nb_out.value)
+        out = (np.empty(n, dtype=np.uint32), np.empty(cap, dtype=np.uint64), np.empty(cap + 1, dtype=np.uint32),
+               np.empty((cap, K), dtype=np.int32))
+    o_ids, o_key, o_start, o_tuple = out
+    assert len(o_ids) >= n - min(m, n) and len(o_start) >= len(o_key) + 1 and o_tuple.size >= len(o_key) * K
+    st = call(_vp(o_ids), _vp(o_key), _vp(o_start), _vp(o_tuple), len(o_key))
+    if st != HS_OK:
+        raise HsError(st, "hs_index_table_remove")
+    n2, nbo = int(n_out.value), int(nb_out.value)
+    return o_ids[:n2], o_key[:nbo], o_start[:nbo + 1], o_tuple.reshape(-1, K)[:nbo]
+
+
 KLSH_NONE = 0xffffffffffffffff
 _REDUCED_CLASS = {c: k for k, grp in enumerate(["AST", "RKEDQ", "NH", "C", "G", "IVLM", "FYW", "P"])
                   for c in grp}   # pcluster util.hpp:100-104 (include/hs_tables.h HS_REDUCED_CLASS)
@@ -1052,6 +1110,44 @@ class Engine:
                                                       _vp(seq_start), C.c_uint64(n_seq), C.byref(n), _vp(pos)))
         assert int(n.value) == n_win
         return self.index_info(), pos
+
+    def index_remove(self, ids):
+        """hs_index_remove: the built index without the k-mers `ids` (any order, duplicates allowed), on the device;
+        the handle then equals one built over the surviving rows, bit for bit.  Returns new_id [old n] uint32: each
+        old id's new id, 0xffffffff for a removed one."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        new_id = np.empty(self._n(), dtype=np.uint32)
+        self._check(self._lib.hs_index_remove(self._h, _vp(ids), C.c_uint64(len(ids)), _vp(new_id)))
+        return new_id
+
+    def index_remove_dev(self, tensor, new_id=None):
+        """hs_index_remove_dev: the ids as an int32 / uint32 tensor [m] on the handle's GPU (or (device pointer, m));
+        new_id: an int32 tensor [old n] on the same GPU to receive the new ids (0xffffffff reads -1), or None."""
+        if isinstance(tensor, tuple):
+            ptr, m = int(tensor[0]), int(tensor[1])
+        else:
+            assert tensor.is_cuda and tensor.is_contiguous() and tensor.dim() == 1 and tensor.element_size() == 4
+            import torch
+            torch.cuda.current_stream(tensor.device).synchronize()   # complete when it is handed over
+            ptr, m = tensor.data_ptr(), tensor.shape[0]
+        out = None
+        if new_id is not None:
+            assert new_id.is_cuda and new_id.is_contiguous() and new_id.element_size() == 4
+            assert new_id.numel() >= self._n()
+            out = C.c_void_p(new_id.data_ptr())
+        self._check(self._lib.hs_index_remove_dev(self._h, C.c_void_p(ptr), C.c_uint64(m), out))
+        return self.index_info()
+
+    def index_remove_ranges(self, first, count):
+        """hs_index_remove_ranges: the ids [first[r], first[r] + count[r]) removed (ranges may overlap), marked on the
+        device; for a windows index window_id_start gives a sequence's range.  Returns new_id as index_remove."""
+        first = np.ascontiguousarray(first, dtype=np.uint64).reshape(-1)
+        count = np.ascontiguousarray(count, dtype=np.uint64).reshape(-1)
+        assert len(first) == len(count)
+        new_id = np.empty(self._n(), dtype=np.uint32)
+        self._check(self._lib.hs_index_remove_ranges(self._h, _vp(first), _vp(count), C.c_uint64(len(first)),
+                                                     _vp(new_id)))
+        return new_id
 
     def index_save(self, path):
         """write the built index (parameters, planes, table, codes, L tables)."""

@@ -23,6 +23,7 @@
 #include "../../include/hs_tables.h"
 #include "hs_internal.h"
 #include "hs_table_append.h"
+#include "hs_table_remove.h"
 
 namespace {
 
@@ -108,6 +109,7 @@ struct Knobs {
   uint32_t test_split_above = 0;   // HS_TEST_SPLIT_ABOVE: batches above this size report a survivor overflow
   bool test_group_fallback = false;  // HS_TEST_GROUP_FALLBACK: the build's fingerprint table reports itself full
   bool test_append_collision = false;  // HS_TEST_APPEND_COLLISION: hs_index_append's match step reports a collision
+  bool test_remove_reseed = false;     // HS_TEST_REMOVE_RESEED: hs_index_remove treats the index's seed as non-zero
 #endif
 };
 
@@ -557,6 +559,7 @@ void read_knobs(hs_handle* h) {
   if (const char* m = getenv("HS_TEST_SPLIT_ABOVE")) kn.test_split_above = (uint32_t)std::max(0, atoi(m));
   kn.test_group_fallback = on("HS_TEST_GROUP_FALLBACK");
   kn.test_append_collision = on("HS_TEST_APPEND_COLLISION");
+  kn.test_remove_reseed = on("HS_TEST_REMOVE_RESEED");
 #endif
   if (const char* m = getenv("HS_HASH_MODE")) {
     if (!strcmp(m, "exact")) h->hash_mode = 1;
@@ -2197,6 +2200,335 @@ hs_status hs_index_table_append(const uint32_t* ids, const uint64_t* dir_key, co
                                 uint32_t* collided) {
   return (hs_status)hs_table_append_host(ids, dir_key, dir_start, dir_tuple, n, nb, block_ints, m, K, seed, out_ids,
                                          out_dir_key, out_dir_start, out_dir_tuple, dir_cap, nb_out, collided);
+}
+
+// ---- hs_index_remove: a built index without a set of its k-mers (hs_remove.hip) -----------------------------------
+namespace {
+// the scratch of one removal, carved out of one allocation: 4 n bytes for new_id, n / 8 for the dead bitmap, 16 bytes
+// per 64 entries for the masks, counts and scans of the id order and as much for one table's, one table's directory
+struct RemoveScratch {
+  uint64_t *dead, *imask, *tmask;
+  uint32_t *icnt, *iscan, *tcnt, *tscan, *new_id, *alive, *alive_scan, *retuple, *retuple_scan, *out_count, *need_id,
+      *need_bucket, *small;
+  uint8_t* need_codes;
+  int32_t* need_ints;
+  void* scan_temp;
+  size_t scan_temp_bytes;
+};
+size_t carve_remove_scratch(RemoveScratch& r, char* base, uint64_t n, int k, int K, uint64_t nb_max) {
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    char* p = base ? base + at : nullptr;
+    at += (bytes + 255) & ~(size_t)255;
+    return p;
+  };
+  const uint64_t nw = (n + 63) / 64;
+  r.dead = (uint64_t*)take((nw + 1) * 8);
+  r.imask = (uint64_t*)take((nw + 1) * 8);
+  r.tmask = (uint64_t*)take((nw + 1) * 8);
+  r.icnt = (uint32_t*)take((nw + 1) * 4);
+  r.iscan = (uint32_t*)take((nw + 1) * 4);
+  r.tcnt = (uint32_t*)take((nw + 1) * 4);
+  r.tscan = (uint32_t*)take((nw + 1) * 4);
+  r.new_id = (uint32_t*)take(n * 4);
+  r.alive = (uint32_t*)take((nb_max + 1) * 4);
+  r.alive_scan = (uint32_t*)take((nb_max + 1) * 4);
+  r.retuple = (uint32_t*)take((nb_max + 1) * 4);
+  r.retuple_scan = (uint32_t*)take((nb_max + 1) * 4);
+  r.out_count = (uint32_t*)take((nb_max + 1) * 4);
+  r.need_id = (uint32_t*)take(nb_max * 4);
+  r.need_bucket = (uint32_t*)take(nb_max * 4);
+  r.small = (uint32_t*)take(64);
+  r.need_codes = (uint8_t*)take(nb_max * k);
+  r.need_ints = (int32_t*)take(nb_max * K * 4);
+  r.scan_temp_bytes = hs_scan_u32_temp(std::max(nw, nb_max) + 2) + 256;
+  r.scan_temp = take(r.scan_temp_bytes);
+  return at;
+}
+}  // namespace
+
+static hs_status remove_check(hs_handle* h) {
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_remove: no index to remove from (hs_index_build has not been called)");
+  return HS_OK;
+}
+
+// the scratch of a removal from the handle's index, the dead bitmap and the flag word (small[0]) zeroed
+static hs_status remove_begin(hs_handle* h, DevBuf& arena, RemoveScratch& r) {
+  const uint64_t n = h->n;
+  uint64_t nb_max = 0;
+  for (uint32_t l = 0; l < h->p.L; ++l) nb_max = std::max<uint64_t>(nb_max, h->info.n_buckets[l]);
+  HS_HIP(h, arena.reserve(carve_remove_scratch(r, nullptr, n, (int)h->p.k, (int)h->p.K, nb_max)));
+  carve_remove_scratch(r, arena.as<char>(), n, (int)h->p.k, (int)h->p.K, nb_max);
+  HS_HIP(h, hipMemsetAsync(r.dead, 0, ((n + 63) / 64 + 1) * 8, h->stream));
+  HS_HIP(h, hipMemsetAsync(r.small, 0, 64, h->stream));
+  return HS_OK;
+}
+
+// The L tables of the index compacted under the dead bitmap (r.dead, r.new_id; n2 survivors, 0 < n2 < n; h->n and
+// h->codes are still the old ones: the new first members' codes are read from there).  On success the shrunken arrays
+// are the handle's and the old ones are gone (finish_index is the caller's).
+static hs_status remove_tables(hs_handle* h, RemoveScratch& r, uint64_t n2) {
+  const uint64_t n = h->n, nw = (n + 63) / 64;
+  const int K = (int)h->p.K, L = (int)h->p.L, k = (int)h->p.k, PW = h->PW;
+  const bool with_rec8 = h->join8_tables_ok && k <= 50;
+  const bool with_rho = with_rec8 && k <= 25 && !h->wide8;
+  DevBuf npacked, nrec8, nrho, npos, nids[HS_MAX_L], nkey[HS_MAX_L], nstart[HS_MAX_L], ntuple[HS_MAX_L];
+  BufGuard guard;
+  guard.b = {&npacked, &nrec8, &nrho, &npos};
+  for (int l = 0; l < L; ++l) {
+    guard.b.push_back(&nids[l]);
+    guard.b.push_back(&nkey[l]);
+    guard.b.push_back(&nstart[l]);
+    guard.b.push_back(&ntuple[l]);
+  }
+  // (the same padding behind the last table as the build leaves: hs_join8r_kernel's ragged last member tile)
+  HS_HIP(h, npacked.reserve(((size_t)L * n2 + HS_JM_WAVE) * PW * 16));
+  if (with_rec8) HS_HIP(h, nrec8.reserve(((size_t)L * n2 + HS_JM_WAVE) * 16));
+  if (with_rho) HS_HIP(h, nrho.reserve(((size_t)L * n2 + HS_JM_WAVE + 4) * 4));
+  HS_HIP(h, npos.reserve(std::max<size_t>(16, (size_t)L * n2 * 4)));
+  uint64_t new_nb[HS_MAX_L], new_max[HS_MAX_L], dead_buckets = 0, retupled = 0;
+  double ms_hash = 0, ms_sort = 0, ms_gather = 0;
+  for (int l = 0; l < L; ++l) {
+    const uint32_t nb = (uint32_t)h->info.n_buckets[l];
+    const hs_table_dev& tb = h->tabs.t[l];
+    HS_HIP(h, hipEventRecord(h->ev[1], h->stream));
+    // 1. the keep masks in table order, the buckets that survive and those that need a tuple
+    HS_HIP(h, hs_launch_remove_masks_tab(tb.ids, r.dead, (uint32_t)n, r.tmask, r.tcnt, h->stream));
+    HS_HIP(h, hs_exclusive_scan_u32(r.scan_temp, r.scan_temp_bytes, r.tcnt, r.tscan, nw + 1, h->stream));
+    HS_HIP(h, hs_launch_remove_dir_flags(tb.dir_start, nb, r.tmask, r.tscan, r.alive, r.retuple, h->stream));
+    HS_HIP(h, hs_exclusive_scan_u32(r.scan_temp, r.scan_temp_bytes, r.alive, r.alive_scan, (size_t)nb + 1, h->stream));
+    HS_HIP(h, hs_exclusive_scan_u32(r.scan_temp, r.scan_temp_bytes, r.retuple, r.retuple_scan, (size_t)nb + 1, h->stream));
+    uint32_t nb2 = 0, n_need = 0, survivors = 0;
+    HS_HIP(h, hipMemcpyAsync(&nb2, r.alive_scan + nb, 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(&n_need, r.retuple_scan + nb, 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(&survivors, r.tscan + nw, 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    if (survivors != n2 || !nb2 || nb2 > nb || n_need > nb2)
+      return fail(h, HS_ERR_HIP, "hs_index_remove: the table's survivor counts are inconsistent");
+    // 2. the shrunken directory
+    HS_HIP(h, nids[l].reserve(std::max<size_t>(16, (size_t)n2 * 4)));
+    HS_HIP(h, nkey[l].reserve(std::max<size_t>(16, (size_t)nb2 * 8)));
+    HS_HIP(h, nstart[l].reserve(((size_t)nb2 + 1) * 4));
+    HS_HIP(h, ntuple[l].reserve(std::max<size_t>(16, (size_t)nb2 * K * 4)));
+    HS_HIP(h, hs_launch_remove_dir_write(tb.dir_key, tb.dir_start, tb.dir_tuple, tb.ids, nb, (uint32_t)n, K, r.tmask,
+                                         r.tscan, r.alive, r.alive_scan, r.retuple, r.retuple_scan, nb2,
+                                         nkey[l].as<uint64_t>(), ntuple[l].as<int32_t>(), r.out_count, r.need_id,
+                                         r.need_bucket, h->stream));
+    HS_HIP(h, hs_exclusive_scan_u32(r.scan_temp, r.scan_temp_bytes, r.out_count, nstart[l].as<uint32_t>(), nb2,
+                                    h->stream));
+    HS_HIP(h, hs_launch_set_u32(nstart[l].as<uint32_t>() + nb2, (uint32_t)n2, h->stream));
+    HS_HIP(h, hipMemsetAsync(r.small + 2, 0, 4, h->stream));
+    HS_HIP(h, hs_launch_max_u32(r.out_count, nb2, r.small + 2, h->stream));
+    HS_HIP(h, hipEventRecord(h->ev[2], h->stream));
+    // 3. the tuples of the buckets whose first member went: just those k-mers hashed, with this table's functions
+    if (n_need) {
+      HS_HIP(h, hs_launch_gather_rows(h->codes.as<uint8_t>(), r.need_id, n_need, k, r.need_codes, h->stream));
+      HS_CHECK(hash_dispatch(h, r.need_codes, nullptr, n_need, l, r.need_ints, K, 0, h->stream));
+      HS_HIP(h, hs_launch_remove_tuples_put(r.need_ints, r.need_bucket, n_need, K, nb2, ntuple[l].as<int32_t>(),
+                                            h->stream));
+    }
+    HS_HIP(h, hipEventRecord(h->ev[3], h->stream));
+    // 4. the move
+    HS_HIP(h, hs_launch_remove_move((uint32_t)n, (uint32_t)n2, r.tmask, r.tscan, r.new_id, PW, tb.ids, tb.packed,
+                                    with_rec8 ? h->t_rec8.as<uint4>() + (size_t)l * n : nullptr,
+                                    with_rho ? h->t_rho.as<uint32_t>() + (size_t)l * n : nullptr, nids[l].as<uint32_t>(),
+                                    npacked.as<uint4>() + (size_t)l * n2 * PW,
+                                    with_rec8 ? nrec8.as<uint4>() + (size_t)l * n2 : nullptr,
+                                    with_rho ? nrho.as<uint32_t>() + (size_t)l * n2 : nullptr, h->stream));
+    HS_HIP(h, hs_launch_invert_perm(nids[l].as<uint32_t>(), (uint32_t)n2, npos.as<uint32_t>() + (size_t)l * n2,
+                                    h->stream));
+    HS_HIP(h, hipEventRecord(h->ev[4], h->stream));
+    uint32_t max_count = 0;
+    HS_HIP(h, hipMemcpyAsync(&max_count, r.small + 2, 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    ms_sort += ev_ms(h, 1, 2);
+    ms_hash += ev_ms(h, 2, 3);
+    ms_gather += ev_ms(h, 3, 4);
+    if (n_need) HS_CHECK(hash_account(h, n_need, K, 0));
+    new_nb[l] = nb2;
+    new_max[l] = max_count;
+    dead_buckets += nb - nb2;
+    retupled += n_need;
+  }
+  // every table is compacted: the shrunken arrays become the handle's (the guard frees the old ones)
+  std::swap(h->t_packed, npacked);
+  std::swap(h->t_rec8, nrec8);
+  std::swap(h->t_rho, nrho);
+  std::swap(h->t_pos, npos);
+  for (int l = 0; l < L; ++l) {
+    std::swap(h->t_ids[l], nids[l]);
+    std::swap(h->t_dirkey[l], nkey[l]);
+    std::swap(h->t_dirstart[l], nstart[l]);
+    std::swap(h->t_dirtuple[l], ntuple[l]);
+    hs_table_dev& tb = h->tabs.t[l];
+    tb.dir_key = h->t_dirkey[l].as<uint64_t>();
+    tb.dir_start = h->t_dirstart[l].as<uint32_t>();
+    tb.dir_tuple = h->t_dirtuple[l].as<int32_t>();
+    tb.packed = h->t_packed.as<uint4>() + (size_t)l * n2 * PW;
+    tb.ids = h->t_ids[l].as<uint32_t>();
+    tb.pos_of = h->t_pos.as<uint32_t>() + (size_t)l * n2;
+    tb.nb = (uint32_t)new_nb[l];
+    h->info.n_buckets[l] = new_nb[l];
+    h->info.max_bucket[l] = new_max[l];
+  }
+  h->prof.ms_hash = ms_hash;
+  h->prof.ms_sort = ms_sort;
+  h->prof.ms_gather = ms_gather;
+  h->prof.remove_dead_buckets = dead_buckets;
+  h->prof.remove_retupled = retupled;
+  return HS_OK;
+}
+
+// The dead bitmap is marked (r.dead; r.small[0] != 0: an id >= n).  Validation and new_id first; from drop_index on,
+// every failure leaves the handle without an index.  new_id (optional): [n] of the old n, host or device memory.
+static hs_status index_remove_marked(hs_handle* h, DevBuf& arena, RemoveScratch& r, uint32_t* new_id, bool new_id_dev) {
+  const uint64_t n = h->n, nw = (n + 63) / 64;
+  const int k = (int)h->p.k, PW = h->PW;
+  HS_HIP(h, hs_launch_remove_masks_ids(r.dead, (uint32_t)n, r.imask, r.icnt, h->stream));
+  HS_HIP(h, hs_exclusive_scan_u32(r.scan_temp, r.scan_temp_bytes, r.icnt, r.iscan, nw + 1, h->stream));
+  HS_HIP(h, hs_launch_remove_new_id(r.imask, r.iscan, (uint32_t)n, r.new_id, h->stream));
+  uint32_t bad = 0, n2_32 = 0;
+  HS_HIP(h, hipMemcpyAsync(&bad, r.small, 4, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipMemcpyAsync(&n2_32, r.iscan + nw, 4, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  if (bad) return fail(h, HS_ERR_INVALID, "hs_index_remove: an id is not below the index's n");
+  const uint64_t n2 = n2_32;
+  if (n2 > n) return fail(h, HS_ERR_HIP, "hs_index_remove: the survivor count is inconsistent");
+  if (new_id && n) {
+    HS_HIP(h, hipMemcpyAsync(new_id, r.new_id, (size_t)n * 4, new_id_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                             h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  if (n2 == n) return HS_OK;  // nothing was marked: the index stays as it is
+  uint64_t nb_before = 0;
+  for (uint32_t l = 0; l < h->p.L; ++l) nb_before += h->info.n_buckets[l];
+  bool reseed = h->key_seed != 0;
+#ifdef HS_TEST_HOOKS
+  if (h->knobs.test_remove_reseed) reseed = true;
+#endif
+  // ---- the handle changes from here on
+  drop_index(h);
+  memset(&h->prof, 0, sizeof(h->prof));
+  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
+  DevBuf ncodes, npacked_all;
+  BufGuard guard;
+  guard.b = {&ncodes, &npacked_all};
+  const bool rebuild = reseed || !n2;
+  if (!rebuild) HS_CHECK(remove_tables(h, r, n2));
+  // codes and packed k-mers in id order (after the tables: their new first members were read from the old codes)
+  HS_HIP(h, ncodes.reserve(std::max<size_t>(16, (size_t)n2 * k)));
+  if (!rebuild) HS_HIP(h, npacked_all.reserve(std::max<size_t>(16, (size_t)n2 * PW * 16)));
+  HS_HIP(h, hs_launch_remove_compact_ids(h->codes.as<uint8_t>(), h->packed_all.as<uint4>(), n, k, PW, r.new_id,
+                                         (uint32_t)n2, ncodes.as<uint8_t>(), rebuild ? nullptr : npacked_all.as<uint4>(),
+                                         h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  std::swap(h->codes, ncodes);
+  ncodes.release();
+  if (!rebuild) {
+    std::swap(h->packed_all, npacked_all);
+    npacked_all.release();
+  }
+  arena.release();
+  h->n = n2;
+  if (!rebuild) {
+    h->info.n = n2;
+    HS_HIP(h, hipEventRecord(h->ev[9], h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    h->prof.ms_total = ev_ms(h, 8, 9);
+    return finish_index(h);
+  }
+  // a seed above 0, or nothing left: the build loop over the compacted codes, resident already, from seed 0 -- where
+  // hs_index_build over the survivors would have ended too
+  memset(&h->info, 0, sizeof(h->info));
+  hs_status st = index_build_resident(h, n2);
+  if (st != HS_OK) return st;
+  uint64_t nb_after = 0;
+  for (uint32_t l = 0; l < h->p.L; ++l) nb_after += h->info.n_buckets[l];
+  h->prof.remove_rebuilds = reseed && n2 ? 1 : 0;
+  h->prof.remove_dead_buckets = nb_before > nb_after ? nb_before - nb_after : 0;
+  return HS_OK;
+}
+
+hs_status hs_index_remove(hs_handle* h, const uint32_t* ids, uint64_t m, uint32_t* new_id) {
+  if (!h || (m && !ids)) return HS_ERR_INVALID;
+  HS_CHECK(remove_check(h));
+  const uint64_t n = h->n;
+  if (!m) {
+    if (new_id)
+      for (uint64_t i = 0; i < n; ++i) new_id[i] = (uint32_t)i;
+    return HS_OK;
+  }
+  HS_CHECK(ensure_device(h));
+  DevBuf arena, d_ids;
+  BufGuard guard;
+  guard.b = {&arena, &d_ids};
+  RemoveScratch r;
+  HS_HIP(h, d_ids.reserve((size_t)m * 4));
+  HS_CHECK(remove_begin(h, arena, r));
+  HS_HIP(h, hipMemcpyAsync(d_ids.p, ids, (size_t)m * 4, hipMemcpyHostToDevice, h->stream));
+  HS_HIP(h, hs_launch_remove_mark_ids(d_ids.as<uint32_t>(), m, (uint32_t)n, r.dead, r.small, h->stream));
+  return index_remove_marked(h, arena, r, new_id, false);
+}
+
+hs_status hs_index_remove_dev(hs_handle* h, const uint32_t* d_ids, uint64_t m, uint32_t* d_new_id) {
+  if (!h || (m && !d_ids)) return HS_ERR_INVALID;
+  HS_CHECK(remove_check(h));
+  HS_CHECK(ensure_device(h));
+  const uint64_t n = h->n;
+  if (!m) {
+    if (d_new_id && n) {
+      HS_HIP(h, hs_launch_iota_u32(d_new_id, (uint32_t)n, h->stream));
+      HS_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    return HS_OK;
+  }
+  DevBuf arena;
+  BufGuard guard;
+  guard.b = {&arena};
+  RemoveScratch r;
+  HS_CHECK(remove_begin(h, arena, r));
+  HS_HIP(h, hs_launch_remove_mark_ids(d_ids, m, (uint32_t)n, r.dead, r.small, h->stream));
+  return index_remove_marked(h, arena, r, d_new_id, true);
+}
+
+hs_status hs_index_remove_ranges(hs_handle* h, const uint64_t* first, const uint64_t* count, uint64_t n_ranges,
+                                 uint32_t* new_id) {
+  if (!h || (n_ranges && (!first || !count))) return HS_ERR_INVALID;
+  HS_CHECK(remove_check(h));
+  const uint64_t n = h->n;
+  uint64_t marked = 0;
+  for (uint64_t i = 0; i < n_ranges; ++i) {
+    if (first[i] > n || count[i] > n - first[i])
+      return fail(h, HS_ERR_INVALID, "hs_index_remove_ranges: a range ends beyond the index's n");
+    marked |= count[i];
+  }
+  if (!marked) {
+    if (new_id)
+      for (uint64_t i = 0; i < n; ++i) new_id[i] = (uint32_t)i;
+    return HS_OK;
+  }
+  HS_CHECK(ensure_device(h));
+  DevBuf arena, d_ranges;
+  BufGuard guard;
+  guard.b = {&arena, &d_ranges};
+  RemoveScratch r;
+  HS_HIP(h, d_ranges.reserve((size_t)n_ranges * 16));
+  HS_CHECK(remove_begin(h, arena, r));
+  uint64_t* const d_first = d_ranges.as<uint64_t>();
+  uint64_t* const d_count = d_first + n_ranges;
+  HS_HIP(h, hipMemcpyAsync(d_first, first, (size_t)n_ranges * 8, hipMemcpyHostToDevice, h->stream));
+  HS_HIP(h, hipMemcpyAsync(d_count, count, (size_t)n_ranges * 8, hipMemcpyHostToDevice, h->stream));
+  HS_HIP(h, hs_launch_remove_mark_ranges(d_first, d_count, n_ranges, (uint32_t)n, r.dead, h->stream));
+  return index_remove_marked(h, arena, r, new_id, false);
+}
+
+hs_status hs_index_table_remove(const uint32_t* ids, const uint64_t* dir_key, const uint32_t* dir_start,
+                                const int32_t* dir_tuple, uint64_t n, uint64_t nb, const uint32_t* dead_ids, uint64_t m,
+                                const int32_t* ints, uint32_t K, uint32_t seed, uint32_t* out_ids, uint64_t* out_dir_key,
+                                uint32_t* out_dir_start, int32_t* out_dir_tuple, uint64_t dir_cap, uint64_t* n_out,
+                                uint64_t* nb_out) {
+  return (hs_status)hs_table_remove_host(ids, dir_key, dir_start, dir_tuple, n, nb, dead_ids, m, ints, K, seed, out_ids,
+                                         out_dir_key, out_dir_start, out_dir_tuple, dir_cap, n_out, nb_out);
 }
 
 // ---- KLSH pre-grouping ------------------------------------------------------

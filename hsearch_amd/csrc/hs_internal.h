@@ -800,4 +800,43 @@ hipError_t hs_launch_append_move(uint32_t n_src, const uint32_t* d_seg_start, ui
                                  uint32_t* d_dst_ids, uint4* d_dst_packed, uint4* d_dst_rec, uint32_t* d_dst_rho,
                                  hipStream_t s);
 
+// ---- hs_index_remove (hs_remove.hip: the rule, the steps and the scratch are written at its head) ----------------
+// Keep masks: nw + 1 64-bit words for n positions (nw = ceil(n / 64); the last word is 0), counts [nw + 1]; the
+// caller's exclusive scan of the counts over nw + 1 elements gives d_scan, whose last element is the survivors.
+// mark: the dead bitmap d_dead [nw] (zeroed by the caller) from ids (*d_flag |= 1 for an id >= n) or from ranges
+// (device arrays; the caller has checked that each ends inside n)
+hipError_t hs_launch_remove_mark_ids(const uint32_t* d_ids, uint64_t m, uint32_t n, uint64_t* d_dead, uint32_t* d_flag,
+                                     hipStream_t s);
+hipError_t hs_launch_remove_mark_ranges(const uint64_t* d_first, const uint64_t* d_count, uint64_t n_ranges, uint32_t n,
+                                        uint64_t* d_dead, hipStream_t s);
+hipError_t hs_launch_remove_masks_ids(const uint64_t* d_dead, uint32_t n, uint64_t* d_mask, uint32_t* d_cnt,
+                                      hipStream_t s);
+hipError_t hs_launch_remove_new_id(const uint64_t* d_mask, const uint32_t* d_scan, uint32_t n, uint32_t* d_new_id,
+                                   hipStream_t s);
+hipError_t hs_launch_remove_masks_tab(const uint32_t* d_ids, const uint64_t* d_dead, uint32_t n, uint64_t* d_mask,
+                                      uint32_t* d_cnt, hipStream_t s);
+// dir_flags: d_alive / d_retuple [nb + 1] (the last 0).  dir_write: keys, counts and copied tuples of the nb_new alive
+// buckets; for a retupled one the OLD id of its new first member and its new number, at d_retuple_scan[b] of
+// d_need_id / d_need_bucket.  tuples_put: d_ints [n_need][K] to the listed buckets.
+hipError_t hs_launch_remove_dir_flags(const uint32_t* d_dir_start, uint32_t nb, const uint64_t* d_mask,
+                                      const uint32_t* d_scan, uint32_t* d_alive, uint32_t* d_retuple, hipStream_t s);
+hipError_t hs_launch_remove_dir_write(const uint64_t* d_dir_key, const uint32_t* d_dir_start, const int32_t* d_dir_tuple,
+                                      const uint32_t* d_ids, uint32_t nb, uint32_t n, int K, const uint64_t* d_mask,
+                                      const uint32_t* d_scan, const uint32_t* d_alive, const uint32_t* d_alive_scan,
+                                      const uint32_t* d_retuple, const uint32_t* d_retuple_scan, uint32_t nb_new,
+                                      uint64_t* d_out_key, int32_t* d_out_tuple, uint32_t* d_out_count,
+                                      uint32_t* d_need_id, uint32_t* d_need_bucket, hipStream_t s);
+hipError_t hs_launch_remove_tuples_put(const int32_t* d_ints, const uint32_t* d_need_bucket, uint32_t n_need, int K,
+                                       uint32_t nb_new, int32_t* d_out_tuple, hipStream_t s);
+// move: surviving entry p of a table's arrays to rank(p) of the shrunken ones (n_dst entries), its id renumbered
+// through d_new_id; d_dst_rec / d_dst_rho may be null
+hipError_t hs_launch_remove_move(uint32_t n, uint32_t n_dst, const uint64_t* d_mask, const uint32_t* d_scan,
+                                 const uint32_t* d_new_id, int PW, const uint32_t* d_src_ids, const uint4* d_src_packed,
+                                 const uint4* d_src_rec, const uint32_t* d_src_rho, uint32_t* d_dst_ids,
+                                 uint4* d_dst_packed, uint4* d_dst_rec, uint32_t* d_dst_rho, hipStream_t s);
+// the id-order arrays: row i of codes [n][k] and of packed_all [n][PW] (d_packed_out may be null) to row d_new_id[i]
+hipError_t hs_launch_remove_compact_ids(const uint8_t* d_codes, const uint4* d_packed_all, uint64_t n, int k, int PW,
+                                        const uint32_t* d_new_id, uint32_t n_dst, uint8_t* d_codes_out,
+                                        uint4* d_packed_out, hipStream_t s);
+
 #endif

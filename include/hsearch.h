@@ -103,6 +103,11 @@ typedef struct hs_profile {
   uint64_t append_rebuilds;    /* hs_index_append*: 1 if the last append fell back to the full build over the
                                   concatenated codes (a fingerprint shared by two HashKey strings), else 0 */
   uint64_t append_new_buckets; /* hs_index_append*: buckets the block created, summed over the tables */
+  uint64_t remove_rebuilds;    /* hs_index_remove*: 1 if the last removal ran the full build loop over the surviving
+                                  codes (the index's key_seed was above 0), else 0 */
+  uint64_t remove_dead_buckets; /* hs_index_remove*: buckets that lost all their members, summed over the tables */
+  uint64_t remove_retupled;    /* hs_index_remove*: buckets whose first member went while others stayed, so that
+                                  their tuple was recomputed from the new first member; summed over the tables */
 } hs_profile;
 
 typedef struct hs_index_info {
@@ -410,6 +415,58 @@ HS_API hs_status hs_index_table_append(const uint32_t* ids, const uint64_t* dir_
                                        const int32_t* block_ints, uint64_t m, uint32_t K, uint32_t seed,
                                        uint32_t* out_ids, uint64_t* out_dir_key, uint32_t* out_dir_start,
                                        int32_t* out_dir_tuple, uint64_t dir_cap, uint64_t* nb_out, uint32_t* collided);
+
+/* The other half of hs_index_append -- a built (or loaded) index SHRINKS by a set D of its ids, on the device.
+ * After hs_index_remove(h, D, m, new_id) on a handle whose index holds codes[0..n), the handle is indistinguishable
+ * from one on which hs_index_build ran over the surviving rows in their old order: the survivors take the ids
+ * 0 .. n' - 1 (n' = n - |D|); hs_index_info_get gives the same n, n_buckets, max_bucket and key_seed (device_bytes
+ * may differ); hs_index_save writes the same file byte for byte; every other entry point gives the same results.
+ * The handle's settings (multi-probe, bucket partition, options) survive, as they survive an append.  A bucket that
+ * loses all its members disappears; removing every k-mer gives what hs_index_build(h, codes, 0) gives.
+ * What it does NOT do again: no residue code crosses PCIe, no surviving k-mer is hashed, sorted or gathered.  A
+ * table is its entries ordered by (fingerprint, id) and removal keeps that order, so per table the bucket-ordered
+ * arrays and the directory are stream-compacted under 64-bit keep masks (hsearch_amd/csrc/hs_remove.hip).
+ * TUPLES: a bucket's tuple is the bucket ints of its member with the smallest id, and the members of a bucket share
+ * the HashKey string, not always the ints ((1,23) and (12,3)).  Where a bucket's first member goes and others stay,
+ * the tuple becomes the bucket ints of the new first member: just those k-mers are hashed again, with that table's
+ * functions.  Every other tuple is copied; the fingerprint belongs to the string and never changes.
+ * FINGERPRINT SEED: with key_seed 0 the remainder, a subset, cannot collide under seed 0 either, and the result has
+ * seed 0.  With key_seed s > 0 the build over the remainder may end at any seed <= s: the call then runs the full
+ * build loop from seed 0 over the compacted codes, already on the device (hs_profile.remove_rebuilds = 1).
+ * ids: any order, duplicates allowed.  new_id (optional, [n] of the OLD n): each old id's new id, or 0xffffffff for
+ * a removed one -- what a caller renumbers its own side tables with, id_start of hs_seq_match included.  m = 0 is a
+ * successful no-op, and new_id is then the identity.
+ * hs_index_remove_dev: d_ids and d_new_id in device memory of the handle's GPU, d_ids complete when the call is made.
+ * hs_index_remove_ranges: the ids [first[r], first[r] + count[r]) of n_ranges ranges (host arrays; ranges may
+ * overlap), marked on the device: whole sequences of an index built by hs_index_build_windows go without their ids
+ * being written out (hs_window_id_start gives the boundaries).  new_id is host memory.
+ * MEMORY: the shrunken arrays are new allocations that replace the old ones, so the peak extra HBM is one shrunken
+ * copy of the index's arrays plus scratch: 4 n bytes for new_id, n / 8 bytes for the dead bitmap, 32 bytes per 64
+ * entries for masks, counts and scans (id order and one table), and one table's directory -- never the build's
+ * n-sized bucket ints, fingerprints and sort buffers (but for the seed fall-back, which is a build).
+ * ERRORS detected before anything of the handle changes (the old index goes on answering): an unbuilt index is
+ * HS_ERR_STATE; an id >= n (the _dev form finds it on the device, with one read-back) or a range that ends beyond n
+ * is HS_ERR_INVALID.  Any LATER failure (a HIP error, no memory) leaves the handle WITHOUT an index, as after a
+ * failed append: calls return HS_ERR_STATE until the next build or load -- never a half-compacted table.
+ * hs_profile after the call: ms_hash (the re-hash of new first members), ms_sort (masks and the directory),
+ * ms_gather (the move, pos_of), ms_total, remove_rebuilds, remove_dead_buckets, remove_retupled. */
+HS_API hs_status hs_index_remove(hs_handle* h, const uint32_t* ids, uint64_t m, uint32_t* new_id);
+HS_API hs_status hs_index_remove_dev(hs_handle* h, const uint32_t* d_ids, uint64_t m, uint32_t* d_new_id);
+HS_API hs_status hs_index_remove_ranges(hs_handle* h, const uint64_t* first, const uint64_t* count, uint64_t n_ranges,
+                                        uint32_t* new_id);
+
+/* The same rule for ONE table on the host (no GPU, no handle): the table's four arrays as hs_index_save writes
+ * them (fingerprint seed `seed`) without the m ids dead_ids (any order, duplicates allowed), into out_ids [*n_out]
+ * (room for n) and the directory out_dir_key [*nb_out], out_dir_start [*nb_out + 1], out_dir_tuple [*nb_out][K].
+ * ints [n][K] are bucket ints indexed by OLD id; only the rows of k-mers that become the first member of a bucket
+ * are read (null is accepted where there is none).  The directory follows the two-call capacity pattern: *n_out and
+ * *nb_out <= nb are always set; dir_cap < *nb_out gives HS_ERR_CAPACITY with nothing written.  An id >= n, or an
+ * input table that breaks the content rules of hs_index_file_check, is HS_ERR_INVALID. */
+HS_API hs_status hs_index_table_remove(const uint32_t* ids, const uint64_t* dir_key, const uint32_t* dir_start,
+                                       const int32_t* dir_tuple, uint64_t n, uint64_t nb, const uint32_t* dead_ids,
+                                       uint64_t m, const int32_t* ints, uint32_t K, uint32_t seed, uint32_t* out_ids,
+                                       uint64_t* out_dir_key, uint32_t* out_dir_start, int32_t* out_dir_tuple,
+                                       uint64_t dir_cap, uint64_t* n_out, uint64_t* nb_out);
 
 /* SURVEY 8(f) row 3 -- Kernel-LSH pre-grouping of whole proteins (pcluster.cpp:11-81).
  * hs_klsh_draw_planes: the planes KLSH::KLSH draws (lsh.cpp:17-38) from its default-seeded
