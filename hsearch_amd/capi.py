@@ -34,7 +34,7 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_window_id_start", "hs_seq_match_hits", "hs_seq_match_merge", "hs_join6_tables", "hs_join6_thresholds",
            "hs_join6_selftest", "hs_join6_tile_offset", "hs_index_append", "hs_index_append_dev", "hs_index_append_windows",
            "hs_index_table_append", "hs_index_remove", "hs_index_remove_dev", "hs_index_remove_ranges",
-           "hs_index_table_remove"]
+           "hs_index_table_remove", "hs_pssm_scan", "hs_pssm_scan_dev", "hs_pssm_tables"]
 
 TOPK_MAX = 64        # HS_TOPK_MAX: the widest row of query_topk / self_knn / topk_merge
 NO_ID = 0xffffffff   # the id and table of an unused entry of such a row (its distance is +inf)
@@ -65,7 +65,9 @@ class _Profile(C.Structure):
                 ("join_async_retries", C.c_uint64), ("queries_recognised", C.c_uint64),
                 ("join_f6_batches", C.c_uint64), ("append_rebuilds", C.c_uint64),
                 ("append_new_buckets", C.c_uint64), ("remove_rebuilds", C.c_uint64),
-                ("remove_dead_buckets", C.c_uint64), ("remove_retupled", C.c_uint64)]
+                ("remove_dead_buckets", C.c_uint64), ("remove_retupled", C.c_uint64),
+                ("pssm_pairs", C.c_uint64), ("pssm_survivors", C.c_uint64), ("pssm_dead", C.c_uint64),
+                ("pssm_mfma_steps", C.c_uint64)]
 
 
 class _IndexInfo(C.Structure):
@@ -287,6 +289,15 @@ def load(hooks=False):
                                                   C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                                   C.POINTER(C.c_uint64)]
+        # PSSM scan: (h, S, t, nm, hit_m, hit_id, hit_score, cap, &n_hits, cnt); tables: include/hsearch.h
+        if hasattr(lib, "hs_pssm_scan"):
+            for fn in (lib.hs_pssm_scan, lib.hs_pssm_scan_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
+            lib.hs_pssm_tables.restype = C.c_int
+            lib.hs_pssm_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
         _libs[hooks] = lib
     return _libs[hooks]
 
@@ -723,6 +734,46 @@ def join6_thresholds(coords, kmers, r2):
     return dict(rho64=rho64, c64=c64, rho0_64=rho0.value, rec=rec)
 
 
+def pssm_tables(S, t):
+    """The PSSM scan filter's tables for profiles S [nm][k][alphabet] and thresholds t [nm], computed on the host (no
+    GPU; hs_pssm_tables): dict(code uint8 [nm][k][alphabet] six-bit e2m3 codes, tau [nm] on the 1/8 grid (-inf: the
+    profile passes every k-mer, +inf: dead), dead uint8 [nm]).  For every k-mer x whose rounded fp64 score reaches
+    t[m], the sum over p of E2M3[code[m][p][x_p]] is >= tau[m]."""
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    t = np.ascontiguousarray(t, dtype=np.float64)
+    assert S.ndim == 3 and t.shape == (S.shape[0],), (S.shape, t.shape)
+    nm, k, A = S.shape
+    code = np.zeros((nm, k, A), dtype=np.uint8)
+    tau = np.zeros(nm)
+    dead = np.zeros(nm, dtype=np.uint8)
+    st = load().hs_pssm_tables(_vp(S), _vp(t), C.c_uint64(nm), C.c_uint32(k), C.c_uint32(A), _vp(code), _vp(tau),
+                               _vp(dead))
+    if st:
+        raise HsError(st, "hs_pssm_tables")
+    return dict(code=code, tau=tau, dead=dead)
+
+
+def pssm_log_odds(counts, background=None, pseudo=1.0):
+    """Log-odds profiles from position frequency matrices (hs_cluster_profile's counts [rows][k][alphabet]):
+    S[r][p][a] = log2((count + pseudo * bg[a]) / (size + pseudo) / bg[a]), size = the row's members (the counts of a
+    position sum to it).  background: [alphabet] frequencies; default: the residue frequencies of the counts themselves,
+    summed over rows and positions (a residue that never occurs gets the smallest positive frequency seen, so that no
+    entry is infinite).  Plain numpy: a convenience, not a bit-exact contract."""
+    counts = np.asarray(counts, dtype=np.float64)
+    assert counts.ndim == 3
+    if background is None:
+        bg = counts.sum(axis=(0, 1))
+        if not bg.sum() > 0:
+            bg = np.ones(counts.shape[2])
+        bg = np.where(bg > 0, bg, bg[bg > 0].min())
+        bg = bg / bg.sum()
+    else:
+        bg = np.asarray(background, dtype=np.float64)
+        assert bg.shape == (counts.shape[2],) and (bg > 0).all()
+    size = counts.sum(axis=2, keepdims=True)
+    return np.log2((counts + pseudo * bg) / (size + pseudo) / bg)
+
+
 def join6_tile_offset(nr, row, piece):
     """Byte offset of 16-byte piece `piece` (0..7) of row `row` inside a gathered query tile of nr <= 32 rows of the
     FP6 join (hs_join6_tile_offset; no GPU)."""
@@ -922,7 +973,7 @@ class Engine:
                "wide_rows": 6, "refine8": 7, "self_codes": 8, "sort_hits": 10, "sync_items": 11,
                "join_min_q": 12, "join_min_m": 13, "sort_from_bit": 14, "build_serial": 15,
                "join_xcd_run": 16, "probe_records": 17, "join_chunk": 18, "summary_chunk": 19, "summary_rows": 20,
-               "msf_edge_budget": 21, "join_f6": 22}
+               "msf_edge_budget": 21, "join_f6": 22, "pssm_filter": 23}
 
     def set_option(self, name, value):
         """hs_set_option (include/hsearch.h hs_option): path selection / batch sizing; never changes a result."""
@@ -1431,6 +1482,50 @@ class Engine:
             self._check(st)
             n = int(n.value)
             return dict(q=hq[:n], id=hid[:n], dist=hd[:n])
+
+    def _alphabet(self):
+        p = _Params()
+        self._check(self._lib.hs_get_params(self._h, C.byref(p)))
+        return int(p.alphabet)
+
+    def pssm_scan(self, S, t, cap=None, want_counts=True):
+        """hs_pssm_scan: every indexed k-mer against the profiles S [nm][k][alphabet] at thresholds t [nm].
+        dict(m, id, score[, cnt]): the hits (score >= t[m], the fp64 left-to-right sum) in (m, id) order."""
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        nm = S.shape[0]
+        assert S.shape == (nm, self.k, self._alphabet()) and t.shape == (nm,), (S.shape, t.shape)
+        cap = int(cap) if cap is not None else max(1024, 64 * nm)
+        cnt = np.zeros(nm, dtype=np.uint64) if want_counts else None
+        while True:
+            hm = np.empty(cap, dtype=np.uint32)
+            hid = np.empty(cap, dtype=np.uint32)
+            hs = np.empty(cap, dtype=np.float64)
+            n = C.c_uint64(0)
+            st = self._lib.hs_pssm_scan(self._h, _vp(S), _vp(t), C.c_uint64(nm), _vp(hm), _vp(hid), _vp(hs),
+                                        C.c_uint64(cap), C.byref(n), _vp(cnt) if want_counts else None)
+            if st == HS_ERR_CAPACITY:
+                cap = int(n.value)
+                continue
+            self._check(st)
+            n = int(n.value)
+            res = dict(m=hm[:n], id=hid[:n], score=hs[:n])
+            if want_counts:
+                res["cnt"] = cnt
+            return res
+
+    def pssm_scan_dev(self, d_S, d_t, nm, d_m, d_id, d_score, cap, d_cnt=None):
+        """hs_pssm_scan_dev: device pointers (ints, e.g. tensor.data_ptr()); returns the hit count.  Raises HsError
+        with status HS_ERR_CAPACITY (its required capacity in .n_hits) when the hits exceed cap."""
+        n = C.c_uint64(0)
+        st = self._lib.hs_pssm_scan_dev(self._h, C.c_void_p(d_S), C.c_void_p(d_t), C.c_uint64(nm), C.c_void_p(d_m),
+                                        C.c_void_p(d_id), C.c_void_p(d_score), C.c_uint64(cap), C.byref(n),
+                                        C.c_void_p(d_cnt) if d_cnt else None)
+        if st != HS_OK:
+            err = HsError(st, self._lib.hs_last_error(self._h).decode())
+            err.n_hits = int(n.value)
+            raise err
+        return int(n.value)
 
     def bruteforce_radii(self, centers, radii, cap=None):
         """hs_bruteforce_radii: brute force with centre q searched at radii[q]."""

@@ -24,6 +24,7 @@
 #include "hs_internal.h"
 #include "hs_table_append.h"
 #include "hs_table_remove.h"
+#include "hs_pssm_tables.h"
 
 namespace {
 
@@ -91,6 +92,7 @@ struct Knobs {
   bool no_wide_by_radius = false;  // HS_OPT_WIDE_ROWS >= 2: never choose 8-column rows by radius
   bool no_refine8 = false;         // HS_OPT_REFINE8 = 0: no 8-column refinement of the join's survivors
   bool no_join_f6 = false;         // HS_OPT_JOIN_F6 = 0: k-mer queries never through the FP6 join (hs_join6.hip)
+  bool no_pssm_filter = false;     // HS_OPT_PSSM_FILTER = 0: hs_pssm_scan sends every pair to the exact pass (hs_pssm.hip)
   bool no_self_codes = false;      // HS_OPT_SELF_CODES = 0: self-join from embedded centres, not from codes
   bool sort_hits = false;          // HS_OPT_SORT_HITS: order hits by the radix sort, not per query
   bool sync_items = false;         // HS_OPT_SYNC_ITEMS: read the join's item count back before launching it
@@ -546,7 +548,7 @@ const struct { const char* name; int option; } kOptionNames[] = {
     {"sort_hits", HS_OPT_SORT_HITS}, {"sync_items", HS_OPT_SYNC_ITEMS}, {"join_min_q", HS_OPT_JOIN_MIN_Q},
     {"join_min_m", HS_OPT_JOIN_MIN_M}, {"sort_from_bit", HS_OPT_SORT_FROM_BIT}, {"build_serial", HS_OPT_BUILD_SERIAL},
     {"join_xcd_run", HS_OPT_JOIN_XCD_RUN}, {"probe_records", HS_OPT_PROBE_RECORDS},
-    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"join_f6", HS_OPT_JOIN_F6}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS},
+    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"join_f6", HS_OPT_JOIN_F6}, {"pssm_filter", HS_OPT_PSSM_FILTER}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS},
     {"msf_edge_budget", HS_OPT_MSF_EDGE_BUDGET}};
 
 void read_knobs(hs_handle* h) {
@@ -834,6 +836,7 @@ hs_status hs_set_option(hs_handle* h, int option, int64_t value) {
     }
     case HS_OPT_REFINE8: return flag(&kn.no_refine8, true);
     case HS_OPT_JOIN_F6: return flag(&kn.no_join_f6, true);
+    case HS_OPT_PSSM_FILTER: return flag(&kn.no_pssm_filter, true);
     case HS_OPT_SELF_CODES: return flag(&kn.no_self_codes, true);
     case HS_OPT_SORT_HITS: return flag(&kn.sort_hits, false);
     case HS_OPT_SYNC_ITEMS: return flag(&kn.sync_items, false);
@@ -5686,6 +5689,179 @@ hs_status hs_cluster_radii(hs_handle* h, const uint32_t* label, uint32_t min_siz
     HS_HIP(h, hipStreamSynchronize(h->stream));
   }
   return HS_OK;
+}
+
+// ---- hs_pssm_scan: every indexed k-mer against position-specific score matrices (kernels: hs_pssm.hip) ----
+// One batch of mb profiles (d_S, d_t: the batch's first; number m0 of the call) against the whole index: the tables
+// and the MFMA filter (or, with the filter off, nothing) and the exact pass, under filter_passes' survivor protocol.
+// On success the batch's nh hits lie unordered in hit_key / hit_val.
+static hs_status pssm_batch(hs_handle* h, const double* d_S, const double* d_t, uint32_t m0, uint32_t mb, bool filt,
+                            uint32_t* nh) {
+  const int k = (int)h->p.k;
+  const uint32_t steps = hs_pssm_steps(h->p.k, (uint32_t)h->alphabet), mb_pad = (mb + 15u) & ~15u;
+  uint32_t* const d_cnt = h->counters.as<uint32_t>();
+  enum { CNT_DEAD = 23 };  // word of the counter block hs_pssm_prep_kernel counts the dead profiles in
+  if (filt) {  // the batch's tables: parameters (seg_vals), tau (tq), B tiles (c16s)
+    HS_HIP(h, h->seg_vals.reserve((size_t)mb_pad * hs_pssm_prof_bytes(h->p.k)));
+    HS_HIP(h, h->tq.reserve((size_t)mb_pad * 4));
+    HS_HIP(h, h->c16s.reserve((size_t)(mb_pad / 16) * hs_pssm_tile_bytes(steps)));
+  }
+  HS_HIP(h, hipMemsetAsync(d_cnt, 0, 256, h->stream));
+  HS_HIP(h, hipEventRecord(h->ev[0], h->stream));
+  HS_HIP(h, hipEventRecord(h->ev[1], h->stream));
+  HS_HIP(h, hipEventRecord(h->ev[2], h->stream));
+  HS_CHECK(filter_passes(h, mb, 0, false, nh, [&](uint32_t prov_cap, uint32_t hit_cap, bool again) -> hs_status {
+    HS_HIP(h, hipEventRecord(h->ev[3], h->stream));
+    if (filt) {
+      if (!again)
+        HS_HIP(h, hs_launch_pssm_prep(d_S, d_t, mb, h->p.k, (uint32_t)h->alphabet, h->seg_vals.p, h->tq.as<float>(),
+                                      h->c16s.p, d_cnt + CNT_DEAD, h->stream));
+      HS_HIP(h, hs_launch_pssm_filter(h->packed_all.as<uint4>(), (uint32_t)h->n, k, h->alphabet, h->c16s.p,
+                                      h->tq.as<float>(), mb, d_cnt, prov_cap, h->prov.as<uint2>(), h->stream));
+    }
+    HS_HIP(h, hipEventRecord(h->ev[4], h->stream));
+    HS_HIP(h, hs_launch_pssm_exact(h->codes.as<uint8_t>(), d_S, d_t, k, h->alphabet, m0, mb, (uint32_t)h->n,
+                                   h->prov.as<uint2>(), d_cnt, prov_cap, !filt, hit_cap, h->hit_key.as<uint64_t>(),
+                                   h->hit_val.as<uint64_t>(), h->n_cu, h->stream));
+    HS_HIP(h, hipEventRecord(h->ev[5], h->stream));
+    HS_HIP(h, hipMemcpyAsync(h->pin_cnt, d_cnt, HS_CNT_WORDS * 4, hipMemcpyDeviceToHost, h->stream));
+    return HS_OK;
+  }));
+  const uint32_t dead = filt ? h->pin_cnt[CNT_DEAD] : 0u;
+  h->prof.pssm_dead += dead;
+  h->prof.pssm_pairs += (uint64_t)(mb - dead) * h->n;
+  h->prof.pssm_survivors += filt ? (uint64_t)h->pin_cnt[0] : (uint64_t)mb * h->n;
+  h->prof.pssm_mfma_steps = filt ? steps : 0;
+  return HS_OK;
+}
+
+// The scan with every array on the device; the callers have checked the arguments and the values.
+static hs_status pssm_core(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm, uint32_t* d_hit_m,
+                           uint32_t* d_hit_id, double* d_hit_score, uint64_t cap, uint64_t* n_hits, uint64_t* d_cnt_out) {
+  memset(&h->prof, 0, sizeof(h->prof));
+  HS_HIP(h, h->counters.reserve(256));
+  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
+  if (d_cnt_out && nm) HS_HIP(h, hipMemsetAsync(d_cnt_out, 0, nm * 8, h->stream));
+  const bool filt = !h->knobs.no_pssm_filter;
+  const size_t ka = (size_t)h->p.k * h->alphabet;
+  uint64_t total = 0;
+  if (nm && h->n) {
+    // profiles per batch: 4096 (256 tiles: 1.5 MB of B operands at 4 steps), or what HS_OPT_QUERY_BATCH says
+    uint32_t MB = h->knobs.query_batch ? h->knobs.query_batch : 4096u;
+    uint32_t mb = 0;
+    for (uint64_t m0 = 0; m0 < nm; m0 += mb) {
+      mb = (uint32_t)std::min<uint64_t>(MB, nm - m0);
+      uint32_t nh = 0;
+      const hs_status st = pssm_batch(h, d_S + m0 * ka, d_t + m0, (uint32_t)m0, mb, filt, &nh);
+      if (st == HS_SPLIT_BATCH) {  // (as run_query: the same profiles again in batches half the size)
+        if (mb == 1) return fail(h, HS_ERR_CAPACITY, "the filter survivors of one profile exceed 2^32");
+        MB = (mb + 1) / 2;
+        mb = 0;
+        continue;
+      }
+      if (st) return st;
+      if (nh) {
+        const uint64_t at = std::min<uint64_t>(total, cap);
+        const bool fits = nh <= cap - at;
+        const uint64_t *key = h->hit_key.as<uint64_t>(), *val = h->hit_val.as<uint64_t>();
+        HS_HIP(h, hipEventRecord(h->ev[6], h->stream));
+        if (fits) {  // the order (m, id): the 64-bit sort of the hit lists, on the key m << 32 | id
+          HS_HIP(h, h->hit_key2.reserve((size_t)nh * 8));
+          HS_HIP(h, h->hit_val2.reserve((size_t)nh * 8));
+          HS_HIP(h, h->temp.reserve(hs_sort_pairs_u64_u64_temp(nh) + 256));
+          HS_HIP(h, hs_sort_pairs_u64_u64(h->temp.p, h->temp.cap, key, h->hit_key2.as<uint64_t>(), val,
+                                          h->hit_val2.as<uint64_t>(), nh, 32 + bit_width_u32((uint32_t)(m0 + mb)),
+                                          h->stream));
+          key = h->hit_key2.as<uint64_t>();
+          val = h->hit_val2.as<uint64_t>();
+        }
+        HS_HIP(h, hs_launch_pssm_emit(key, val, nh, fits, fits ? d_hit_m + at : nullptr, fits ? d_hit_id + at : nullptr,
+                                      fits ? d_hit_score + at : nullptr, d_cnt_out, h->stream));
+        HS_HIP(h, hipEventRecord(h->ev[7], h->stream));
+        HS_HIP(h, hipStreamSynchronize(h->stream));
+        h->prof.ms_finalize += ev_ms(h, 6, 7);
+      }
+      total += nh;
+    }
+  }
+  HS_HIP(h, hipEventRecord(h->ev[9], h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  h->prof.ms_total = ev_ms(h, 8, 9);
+  h->prof.hits = total;
+  *n_hits = total;
+  if (total > cap) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
+  return HS_OK;
+}
+
+static hs_status pssm_args(hs_handle* h, const void* S, const void* t, uint64_t nm, const void* hit_m, const void* hit_id,
+                           const void* hit_score, uint64_t cap) {
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
+  if (nm >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nm must be < 2^27 per call");
+  if (nm && (!S || !t)) return fail(h, HS_ERR_INVALID, "hs_pssm_scan: S or t is null");
+  if (cap && (!hit_m || !hit_id || !hit_score)) return fail(h, HS_ERR_INVALID, "an output array is null");
+  return HS_OK;
+}
+
+hs_status hs_pssm_scan_dev(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm, uint32_t* d_hit_m,
+                           uint32_t* d_hit_id, double* d_hit_score, uint64_t cap, uint64_t* n_hits, uint64_t* d_cnt) {
+  if (!h || !n_hits) return HS_ERR_INVALID;
+  *n_hits = 0;
+  HS_CHECK(pssm_args(h, d_S, d_t, nm, d_hit_m, d_hit_id, d_hit_score, cap));
+  HS_CHECK(ensure_device(h));
+  if (nm) {  // the values, on the device: one small reduction and one read-back, before anything is written
+    uint32_t flag = 0;
+    HS_HIP(h, h->io_radii.reserve(16));
+    HS_HIP(h, hipMemsetAsync(h->io_radii.p, 0, 16, h->stream));
+    HS_HIP(h, hs_launch_pssm_check(d_S, nm * h->p.k * h->alphabet, d_t, nm, h->io_radii.as<uint32_t>(), h->stream));
+    HS_HIP(h, hipMemcpyAsync(&flag, h->io_radii.p, 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    if (flag & 1u) return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
+    if (flag & 2u) return fail(h, HS_ERR_INVALID, "a threshold is NaN or infinite");
+  }
+  return pssm_core(h, d_S, d_t, nm, d_hit_m, d_hit_id, d_hit_score, cap, n_hits, d_cnt);
+}
+
+hs_status hs_pssm_scan(hs_handle* h, const double* S, const double* t, uint64_t nm, uint32_t* hit_m, uint32_t* hit_id,
+                       double* hit_score, uint64_t cap, uint64_t* n_hits, uint64_t* cnt) {
+  if (!h || !n_hits) return HS_ERR_INVALID;
+  *n_hits = 0;
+  HS_CHECK(pssm_args(h, S, t, nm, hit_m, hit_id, hit_score, cap));
+  const size_t ka = (size_t)h->p.k * h->alphabet;
+  for (uint64_t i = 0; i < nm * ka; ++i)
+    if (hs_pssm_bad_value(S[i], HS_PSSM_MAX_ABS))
+      return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
+  for (uint64_t m = 0; m < nm; ++m)
+    if (hs_pssm_bad_value(t[m], 1.7976931348623157e308)) return fail(h, HS_ERR_INVALID, "a threshold is NaN or infinite");
+  HS_CHECK(ensure_device(h));
+  HS_HIP(h, h->io_centers.reserve(std::max<size_t>(16, nm * ka * 8)));
+  HS_HIP(h, h->io_radii.reserve(std::max<size_t>(16, nm * 8)));
+  HS_HIP(h, h->io_q.reserve(std::max<size_t>(16, cap * 4)));
+  HS_HIP(h, h->io_id.reserve(std::max<size_t>(16, cap * 4)));
+  HS_HIP(h, h->io_dist.reserve(std::max<size_t>(16, cap * 8)));
+  if (cnt) HS_HIP(h, h->io_cand.reserve(std::max<size_t>(16, nm * 8)));
+  if (nm) {
+    HS_HIP(h, hipMemcpyAsync(h->io_centers.p, S, nm * ka * 8, hipMemcpyHostToDevice, h->stream));
+    HS_HIP(h, hipMemcpyAsync(h->io_radii.p, t, nm * 8, hipMemcpyHostToDevice, h->stream));
+  }
+  const hs_status st = pssm_core(h, h->io_centers.as<double>(), h->io_radii.as<double>(), nm, h->io_q.as<uint32_t>(),
+                                 h->io_id.as<uint32_t>(), h->io_dist.as<double>(), cap, n_hits,
+                                 cnt ? h->io_cand.as<uint64_t>() : nullptr);
+  if (st != HS_OK && st != HS_ERR_CAPACITY) return st;
+  if (cnt && nm) HS_HIP(h, hipMemcpyAsync(cnt, h->io_cand.p, nm * 8, hipMemcpyDeviceToHost, h->stream));
+  const uint64_t nh = *n_hits;
+  if (st == HS_OK && nh) {
+    HS_HIP(h, hipMemcpyAsync(hit_m, h->io_q.p, nh * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(hit_id, h->io_id.p, nh * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(hit_score, h->io_dist.p, nh * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return st;
+}
+
+// The filter's tables on the host (hs_pssm_tables.h): no GPU, no handle
+hs_status hs_pssm_tables(const double* S, const double* t, uint64_t nm, uint32_t k, uint32_t alphabet, uint8_t* code,
+                         double* tau, uint8_t* dead) {
+  return hs_pssm_tables_host(S, t, nm, k, alphabet, code, tau, dead) ? HS_ERR_INVALID : HS_OK;
 }
 
 hs_status hs_bruteforce_topk(hs_handle* h, const double* centers, uint64_t nq, uint32_t topk,

@@ -839,4 +839,26 @@ hipError_t hs_launch_remove_compact_ids(const uint8_t* d_codes, const uint4* d_p
                                         const uint32_t* d_new_id, uint32_t n_dst, uint8_t* d_codes_out,
                                         uint4* d_packed_out, hipStream_t s);
 
+// ---- hs_pssm_scan (hs_pssm.hip: the filter, its layouts and the exact pass are written at its head) ---------------
+size_t hs_pssm_prof_bytes(uint32_t k);       // per profile slot of a batch: the parameters and offsets hs_pssm_prep_kernel keeps
+size_t hs_pssm_tile_bytes(uint32_t steps);   // per tile of 16 profiles: the B operands of all steps
+// flag |= 1: an entry NaN, infinite or beyond 2^100; |= 2: a threshold NaN or infinite
+hipError_t hs_launch_pssm_check(const double* d_S, uint64_t n_entries, const double* d_t, uint64_t nm, uint32_t* d_flag,
+                                hipStream_t s);
+// the batch's mb profiles (d_S, d_t: the batch's first) -> parameters and tau of ceil16(mb) slots, the B tiles, and
+// *d_n_dead += the profiles no k-mer can hit
+hipError_t hs_launch_pssm_prep(const double* d_S, const double* d_t, uint32_t mb, uint32_t k, uint32_t alphabet,
+                               void* d_prof, float* d_tau, void* d_btiles, uint32_t* d_n_dead, hipStream_t s);
+// survivors {profile of the batch, id} into d_prov through hs_reserve_survivors on d_prov_count
+hipError_t hs_launch_pssm_filter(const uint4* d_packed_all, uint32_t n, int k, int alphabet, const void* d_btiles,
+                                 const float* d_tau, uint32_t mb, uint32_t* d_prov_count, uint32_t prov_cap,
+                                 uint2* d_prov, hipStream_t s);
+// d_counters: the batch's counter block ([0] survivors, [1] hits); all_pairs: every pair of the batch, no list
+hipError_t hs_launch_pssm_exact(const uint8_t* d_codes, const double* d_S, const double* d_t, int k, int alphabet,
+                                uint32_t m_base, uint32_t mb, uint32_t n, const uint2* d_prov, uint32_t* d_counters,
+                                uint32_t prov_cap, bool all_pairs, uint32_t hit_cap, uint64_t* d_hit_key,
+                                uint64_t* d_hit_val, int n_cu, hipStream_t s);
+hipError_t hs_launch_pssm_emit(const uint64_t* d_key, const uint64_t* d_val, uint32_t nh, bool write, uint32_t* d_out_m,
+                               uint32_t* d_out_id, double* d_out_score, uint64_t* d_cnt, hipStream_t s);
+
 #endif

@@ -710,6 +710,146 @@ int SearchProteinsSharded(const ProteinDB& db_first, uint32_t kmer_length, const
   return HS_OK;
 }
 
+static std::string ProteinLabel(const ProteinDB& db, size_t s);
+
+bool ReadPssmFile(const std::string& path, uint32_t kmer_length, std::vector<std::string>* names,
+                  std::vector<double>* S, std::vector<double>* t, std::string* err) {
+  std::ifstream fin(path.c_str());
+  if (!fin) {
+    if (err) *err = "cannot open " + path;
+    return false;
+  }
+  names->clear();
+  S->clear();
+  t->clear();
+  std::map<std::string, int> seen;
+  std::string line;
+  uint32_t rows_left = 0;
+  size_t line_no = 0;
+  auto fail = [&](const std::string& what) {
+    if (err) *err = path + ":" + std::to_string(line_no) + ": " + what;
+    return false;
+  };
+  auto number = [](const std::string& tok, double* out) {
+    char* end = nullptr;
+    *out = strtod(tok.c_str(), &end);
+    return end != tok.c_str() && *end == 0;
+  };
+  while (std::getline(fin, line)) {
+    ++line_no;
+    std::istringstream iss(line);
+    std::vector<std::string> tok;
+    for (std::string w; iss >> w;) tok.push_back(w);
+    if (tok.empty()) continue;
+    if (tok[0][0] == '>') {
+      if (rows_left) return fail("a profile of fewer than " + std::to_string(kmer_length) + " rows ends here");
+      double thr = 0.0;
+      if (tok.size() != 2 || tok[0].size() < 2 || !number(tok[1], &thr)) return fail("expected '>name threshold'");
+      const std::string name = tok[0].substr(1);
+      if (seen[name]++) return fail("profile " + name + " is given twice");
+      names->push_back(name);
+      t->push_back(thr);
+      rows_left = kmer_length;
+      continue;
+    }
+    if (!rows_left) return fail(names->empty() ? "expected '>name threshold'" : "a profile of more rows than the kmer length");
+    if (tok.size() != HS_ALPHABET) return fail("expected " + std::to_string(HS_ALPHABET) + " numbers");
+    for (const std::string& w : tok) {
+      double v = 0.0;
+      if (!number(w, &v)) return fail("'" + w + "' is not a number");
+      S->push_back(v);
+    }
+    --rows_left;
+  }
+  ++line_no;
+  if (rows_left) return fail("a profile of fewer than " + std::to_string(kmer_length) + " rows ends here");
+  return true;
+}
+
+int ScanProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
+                 const std::vector<double>& S, const std::vector<double>& t, const std::string& output_file,
+                 int device, std::string* err, uint64_t* n_windows, uint64_t* n_hits_out) {
+  const uint32_t k = kmer_length;
+  const size_t nm = t.size();
+  if (k < 2 || names.size() != nm || S.size() != nm * (size_t)k * HS_ALPHABET) {
+    if (err) *err = k < 2 ? "kmer length 1 is not supported on a FASTA database" : "the profiles do not match the kmer length";
+    return HS_ERR_INVALID;
+  }
+  // sequences cut at unknown letters, as in SearchProteinsSharded: windows never cross a cut
+  std::vector<uint8_t> res(db.residues);
+  std::vector<uint64_t> seg;
+  const size_t n_seq = db.start.empty() ? 0 : db.start.size() - 1;
+  for (size_t s = 0; s < n_seq; ++s) {
+    seg.push_back(db.start[s]);
+    for (uint64_t p = db.start[s]; p < db.start[s + 1]; ++p)
+      if (res[p] == ProteinDB::kUnknown) {
+        res[p] = 0;
+        seg.push_back(p);
+        seg.push_back(p + 1);
+      }
+  }
+  seg.push_back(db.residues.size());
+  // no hash table takes part in a scan: the smallest family there is
+  const Planes planes = DrawPlanes(8 * k, 1, 1, 1.0, 0);
+  hs_params prm;
+  memset(&prm, 0, sizeof(prm));
+  prm.k = k;
+  prm.K = 1;
+  prm.L = 1;
+  prm.W = 1.0;
+  prm.alphabet = HS_ALPHABET;
+  prm.device = device;
+  hs_handle* h = nullptr;
+  hs_status st = hs_create(&prm, planes.a.data(), planes.b.data(), &HS_AA_COORDS[0][0], &h);
+  if (st != HS_OK) {
+    if (err) *err = std::string("hs_create: ") + (h ? hs_last_error(h) : "no usable gfx950 device");
+    hs_destroy(h);
+    return st;
+  }
+  HandleCloser closer = {h};
+  uint64_t n_win = 0;
+  std::vector<uint32_t> win_pos(res.size() + 1);
+  st = hs_index_build_windows(h, res.data(), res.size(), seg.data(), seg.size() - 1, &n_win, win_pos.data());
+  if (st != HS_OK) {
+    if (err) *err = std::string("index build: ") + hs_last_error(h);
+    return st;
+  }
+  if (n_windows) *n_windows = n_win;
+  std::vector<uint32_t> hm, hid;
+  std::vector<double> hs;
+  uint64_t n_hits = 0;
+  for (uint64_t cap = 0;;) {  // the hit count, then the hits
+    hm.resize(cap);
+    hid.resize(cap);
+    hs.resize(cap);
+    st = hs_pssm_scan(h, S.data(), t.data(), nm, hm.data(), hid.data(), hs.data(), cap, &n_hits, nullptr);
+    if (st == HS_ERR_CAPACITY && n_hits > cap) {
+      cap = n_hits;
+      continue;
+    }
+    break;
+  }
+  if (st != HS_OK) {
+    if (err) *err = std::string("hs_pssm_scan: ") + hs_last_error(h);
+    return st;
+  }
+  if (n_hits_out) *n_hits_out = n_hits;
+  const char* letters = HS_CODE_TO_LETTER;
+  std::ofstream fout(output_file.c_str());
+  char num[64];
+  for (uint64_t i = 0; i < n_hits; ++i) {
+    const uint64_t pos = win_pos[hid[i]];
+    const size_t s = (size_t)(std::upper_bound(db.start.begin(), db.start.end() - 1, pos) - db.start.begin()) - 1;
+    std::string kmer(k, '?');
+    for (uint32_t p = 0; p < k; ++p) kmer[p] = letters[db.residues[pos + p]];
+    snprintf(num, sizeof(num), "%.17g", hs[i]);
+    fout << names[hm[i]] << " " << ProteinLabel(db, s) << "$" << (pos - db.start[s]) << "@" << kmer << "*" << hid[i]
+         << " " << num << "\n";
+  }
+  fout.close();
+  return HS_OK;
+}
+
 // "<first token of the protein's name>#<its number>": how the search's k-mer names begin
 static std::string ProteinLabel(const ProteinDB& db, size_t s) {
   std::string token;

@@ -179,6 +179,19 @@ int SearchProteinsPerSequence(const ProteinDB& db, uint32_t kmer_length, const s
                               std::vector<uint64_t>* table_sizes = nullptr, uint64_t* n_windows = nullptr,
                               uint32_t probes = 0, const std::vector<double>* radii = nullptr,
                               const std::vector<ProteinDB>* more = nullptr);
+// `--pssm FILE`: position-specific score matrices over a FASTA database (hs_pssm_scan: every window of every protein
+// scored, exhaustively; no hash tables take part).  The file: per profile a line ">name threshold", then kmer_length
+// lines of 20 numbers, the columns in the coordinate table's residue order (HS_CODE_TO_LETTER).  A profile with
+// another shape, a number that is none, a name without a threshold or a name given twice is an error (*err).
+// S [nm][kmer_length][20], t [nm].
+bool ReadPssmFile(const std::string& path, uint32_t kmer_length, std::vector<std::string>* names,
+                  std::vector<double>* S, std::vector<double>* t, std::string* err);
+// The scan: one line per hit, "<profile name> <window name> <score>" with the window named as SearchProteins names
+// it and the score printed with 17 significant digits (it reads back bit for bit), in (profile, window) order.
+// Windows never cross a letter outside the alphabet.  One GPU.
+int ScanProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
+                 const std::vector<double>& S, const std::vector<double>& t, const std::string& output_file,
+                 int device, std::string* err, uint64_t* n_windows = nullptr, uint64_t* n_hits = nullptr);
 // center_codes (CentersFromKmers): the centres are k-mers of the exact table -- the one a FASTA
 // database is embedded from -- and travel to the GPU as residue codes (hs_query_codes: k bytes per
 // centre instead of 64 k); the hits are those of the embedded centres, bit for bit.

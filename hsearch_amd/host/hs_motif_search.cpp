@@ -29,6 +29,10 @@
 // into windows with the database's residue mapping and swap option, the groups are the query proteins and the lines
 // are per (query protein, protein, diagonal), the diagonal last.  Both work with --radii (per centre, or per query
 // protein) and -M; one GPU only, and not with --topk or --best-per-position 1.
+// --pssm FILE (FASTA database): no search at all -- every window of every protein scored against the position-
+// specific score matrices of FILE (hs_pssm_scan), one line per hit "<profile> <window name> <score>", the score with
+// 17 significant digits; -c, -W and -T are not needed, and -c, --radii, -M, --topk, --per-sequence,
+// --best-per-position, --query-fasta, --db-append and --gpus above 1 are refused.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -81,6 +85,7 @@ const Opt kOpts[] = {
     {"query-fasta", 'q', "query proteins in place of -c: one line per (query protein, protein, diagonal) (implies --per-sequence 1)", false},
     {"topk", 't', "per centre only its N best hits, 1..64, in ascending (distance, k-mer index) (one GPU) [off: all hits]", false},
     {"db-append", 'A', "FASTA database: a further FASTA file whose sequences follow -d's, appended to the built index on the GPU; repeatable (one GPU)", false},
+    {"pssm", 'm', "FASTA database: scan every window against the position-specific score matrices of this file ('>name threshold', then -l lines of 20 numbers) in place of a search: no -c, -W, -T (one GPU)", false},
 };
 
 // A points file has a line of numbers after its first name line; a FASTA file has residue letters.
@@ -102,6 +107,72 @@ void Help(const char* prog) {
     fprintf(stderr, "  -%c, -%-12s %s%s\n", o.short_name, o.long_name, o.descr,
             o.required ? " [REQUIRED]" : "");
   fprintf(stderr, "\nHelp options:\n  -?, -help   print this help message\n\ncluster kmers to motifs\n");
+}
+
+// --pssm: the scan of a FASTA database against position-specific score matrices (hsearch::ScanProfiles).  It is no
+// search: what selects, sizes or reduces a search is refused, not ignored.
+int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::string>& db_append) {
+  static const struct { const char* name; const char* flag; } kRefused[] = {
+      {"center", "-c"}, {"radii", "--radii"}, {"probes", "-M"}, {"topk", "--topk"}, {"per-sequence", "--per-sequence"},
+      {"best-per-position", "--best-per-position"}, {"query-fasta", "--query-fasta"}};
+  for (const auto& r : kRefused)
+    if (val.count(r.name)) {
+      fprintf(stderr, "ERROR: --pssm cannot be combined with %s: it scans every window against the profiles, it is "
+                      "no search\n", r.flag);
+      return EXIT_FAILURE;
+    }
+  if (val.count("gpus") && atoi(val["gpus"].c_str()) > 1) {
+    fprintf(stderr, "ERROR: --pssm runs on one GPU: it cannot be combined with --gpus %s\n", val["gpus"].c_str());
+    return EXIT_FAILURE;
+  }
+  if (!db_append.empty()) {
+    fprintf(stderr, "ERROR: --pssm cannot be combined with --db-append\n");
+    return EXIT_FAILURE;
+  }
+  const uint32_t kmer_length = (uint32_t)strtoul(val["len"].c_str(), nullptr, 10);
+  const int device = val.count("device") ? atoi(val["device"].c_str()) : 0;
+  try {
+    if (!LooksLikeFasta(val["db"])) {
+      fprintf(stderr, "ERROR: --pssm needs a FASTA database: a points database holds no residues\n");
+      return EXIT_FAILURE;
+    }
+    hsearch::ProteinDB prodb;
+    std::cout << "Read protein sequences from " << val["db"] << std::endl;
+    const bool swap = val.count("ref-compat-eq-swap") && atoi(val["ref-compat-eq-swap"].c_str()) != 0;
+    if (!hsearch::ReadProteinFasta(val["db"], swap, &prodb)) {
+      fprintf(stderr, "cannot open %s\n", val["db"].c_str());
+      return EXIT_FAILURE;
+    }
+    std::cout << "number of proteins " << prodb.start.size() - 1 << std::endl;
+    std::cout << "total length " << prodb.residues.size() << std::endl;
+    std::vector<std::string> names;
+    std::vector<double> S, t;
+    std::string err;
+    if (!hsearch::ReadPssmFile(val["pssm"], kmer_length, &names, &S, &t, &err)) {
+      fprintf(stderr, "ERROR: %s\n", err.c_str());
+      return EXIT_FAILURE;
+    }
+    std::cout << "number of profiles " << names.size() << std::endl;
+    struct timespec t0, t1;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    uint64_t n_windows = 0, n_hits = 0;
+    const int st = hsearch::ScanProfiles(prodb, kmer_length, names, S, t, val["output"], device, &err, &n_windows, &n_hits);
+    if (st != 0) {
+      fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), st);
+      return EXIT_FAILURE;
+    }
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    std::cout << "number of kmers " << n_windows << std::endl;
+    std::cout << "number of hits " << n_hits << std::endl;
+    printf("SCAN: %lf seconds\n", (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec));
+  } catch (const std::bad_alloc&) {
+    fprintf(stderr, "ERROR: could not allocate memory\n");
+    return EXIT_FAILURE;
+  } catch (const std::exception& e) {
+    fprintf(stderr, "%s\n", e.what());
+    return EXIT_FAILURE;
+  }
+  return EXIT_SUCCESS;
 }
 
 }  // namespace
@@ -142,13 +213,16 @@ int main(int argc, const char* argv[]) {
     return EXIT_SUCCESS;
   }
   const bool query_fasta = val.count("query-fasta") != 0;
+  const bool with_pssm = val.count("pssm") != 0;
   const bool per_sequence = query_fasta || (val.count("per-sequence") && atoi(val["per-sequence"].c_str()) != 0);
   for (const Opt& o : kOpts)
-    if (o.required && !val.count(o.long_name) && !(query_fasta && std::string(o.long_name) == "center")) {
+    if (o.required && !val.count(o.long_name) && !(query_fasta && std::string(o.long_name) == "center") &&
+        !(with_pssm && (std::string(o.long_name) == "center" || std::string(o.long_name) == "window"))) {
       fprintf(stderr, "missing required option -%c\n", o.short_name);
       Help(argv[0]);
       return EXIT_SUCCESS;  // as the reference: option_missing() -> message, EXIT_SUCCESS
     }
+  if (with_pssm) return PssmMain(val, db_append);
   const bool with_radii = val.count("radii") != 0;
   if (!with_radii && !val.count("threshold")) {
     fprintf(stderr, "missing required option -T\n");

@@ -108,6 +108,11 @@ typedef struct hs_profile {
   uint64_t remove_dead_buckets; /* hs_index_remove*: buckets that lost all their members, summed over the tables */
   uint64_t remove_retupled;    /* hs_index_remove*: buckets whose first member went while others stayed, so that
                                   their tuple was recomputed from the new first member; summed over the tables */
+  uint64_t pssm_pairs;         /* hs_pssm_scan*: (profile, k-mer) pairs of the profiles that were not dead: nm_live * n */
+  uint64_t pssm_survivors;     /* ... of which this many passed the MFMA filter and went to the exact pass (with
+                                  HS_OPT_PSSM_FILTER = 0: all of them) */
+  uint64_t pssm_dead;          /* ... profiles skipped because no k-mer can reach their threshold (filter on only) */
+  uint64_t pssm_mfma_steps;    /* ... MFMA depth steps per 16 x 16 tile: ceil(k * alphabet / 128) (0: filter off) */
 } hs_profile;
 
 typedef struct hs_index_info {
@@ -192,7 +197,9 @@ typedef enum hs_option {
   HS_OPT_JOIN_F6 = 22,       /* 1 (default): batches whose queries are k-mers (codes, recognised centres, the
                                 self-join from codes), k = 21..25, 4-column rows, run the query-streaming join on
                                 FP6 MFMA (hs_join6x_kernel); 0: never (hs_join8x_kernel) */
-  HS_OPT_JOIN_XCD_RUN = 16   /* hs_join8x_kernel's work items dealt in runs of this many chunks per XCD, each XCD's
+  HS_OPT_PSSM_FILTER = 23,   /* hs_pssm_scan: 1 (default): the FP6 MFMA filter in front of the exact pass; 0: no filter,
+                                every (profile, k-mer) pair goes to the exact pass */
+  HS_OPT_JOIN_XCD_RUN = 16  /* hs_join8x_kernel's work items dealt in runs of this many chunks per XCD, each XCD's
                                 waves on their own runs (a run's items stream the same query tiles: one L2 fetches
                                 them instead of eight).  0: one counter for the chip; -1 (default): by the size
                                 of the batch's query-tile array */
@@ -1116,6 +1123,51 @@ HS_API hs_status hs_cluster_summary_codes(const uint8_t* codes, uint64_t n, uint
                                           const double* centers, uint64_t n_center_rows, uint32_t* out_label,
                                           uint32_t* out_size, uint32_t* counts, double* centroid, double* max_d2,
                                           double* radius, uint32_t* medoid, uint64_t cap, uint64_t* n_out);
+
+/* ---- PSSM scan: every indexed k-mer scored against position-specific score matrices ------------------------- */
+
+/* What a cluster's position frequency matrix (hs_cluster_profile's counts) becomes when it is searched with: a
+ * position-specific score matrix -- log-odds per position and residue -- and a threshold per motif, over every k-mer
+ * of the index.  A windows index (hs_index_build_windows) makes it a scan of every protein position.  LSH cannot index
+ * this score; the scan is exhaustive.
+ *
+ * Inputs: S [nm][k][alphabet] fp64 (k and alphabet are the handle's), t [nm].  The scan runs over the built or loaded
+ * index of the handle; ids are the DB ids of every other call.
+ * Hit rule: score(m, x) = the sum over p = 0 .. k-1 of S[m][p][x_p], starting from +0.0, left to right, every sum
+ * rounded to fp64.  (m, id) is a hit iff score >= t[m].  hit_score is that double, bit for bit.
+ * Order: (m, id) ascending.  cnt [nm] (may be NULL): the hits per profile, valid on HS_OK and on HS_ERR_CAPACITY.
+ * Capacity: the two-call pattern of hs_query (HS_ERR_CAPACITY with *n_hits set; cap = 0 with NULL arrays asks for
+ * the count).  *n_hits is a uint64 and may exceed 2^32.
+ * Errors, reported before any output is written: an unbuilt index is HS_ERR_STATE; nm >= 2^27 is HS_ERR_INVALID; a
+ * NaN or infinite entry, an entry with |S| > 2^100, and a NaN or infinite threshold are HS_ERR_INVALID (the _dev form
+ * finds these on the device with one read-back, as hs_query_radii_dev finds a NaN radius).  The magnitude cap keeps
+ * every partial sum finite: 75 entries of at most 2^100 stay below 2^107, so no score is an infinity or a NaN and
+ * `>=` is a total order on what it compares.
+ * The handle's multi-probe setting and bucket partition play no part.  The result is a pure function of (codes, S, t):
+ * batch sizes (HS_OPT_QUERY_BATCH: profiles per batch here), HS_OPT_PSSM_FILTER and the survivor order on the device
+ * do not show in it.
+ *
+ * How: profiles in batches, each batch one pass over the index's packed codes.  A filter on FP6 MFMA (one-hot k-mer
+ * rows times the profiles' entries rounded UP onto the e2m3 grid, hs_pssm_tables below; hsearch_amd/csrc/hs_pssm.hip)
+ * passes every pair whose rounded fp64 score can reach t; the exact pass computes the contract's sum for what passed
+ * and alone decides.  hs_profile after the call: pssm_pairs, pssm_survivors, pssm_dead, pssm_mfma_steps, hits;
+ * ms_verify (tables + filter), ms_finalize (exact pass and ordering), ms_total.  Scratch is sized by a batch and
+ * comes from the handle's growable buffers.  Every other entry point runs as before, launch for launch.
+ * Out of scope: top-N per profile, a per-sequence reduction of profile hits, multi-GPU, an int8 form of the filter. */
+HS_API hs_status hs_pssm_scan(hs_handle* h, const double* S, const double* t, uint64_t nm, uint32_t* hit_m,
+                              uint32_t* hit_id, double* hit_score, uint64_t cap, uint64_t* n_hits, uint64_t* cnt);
+/* ... every pointer but n_hits in device memory (streams: as hs_query_dev) */
+HS_API hs_status hs_pssm_scan_dev(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm, uint32_t* d_hit_m,
+                                  uint32_t* d_hit_id, double* d_hit_score, uint64_t cap, uint64_t* n_hits,
+                                  uint64_t* d_cnt);
+/* The filter's tables on the host (no GPU, no handle), the same bits the device builds: code [nm][k][alphabet] the
+ * six-bit e2m3 code of every entry, tau [nm] the threshold on the 1/8 grid (-infinity: the profile passes every k-mer;
+ * +infinity: dead), dead [nm].  Any output may be NULL.  THE INVARIANT: for every k-mer x, if the contract's rounded
+ * score of x reaches t[m] then the sum over p of decode(code[m][p][x_p]) is >= tau[m]; dead[m] = 1 only if no k-mer
+ * can hit.  (A dead or pass-everything profile has all codes 0.)  k outside 1 .. 75, alphabet outside 1 .. 32,
+ * nm >= 2^27 and the values hs_pssm_scan refuses are HS_ERR_INVALID, with nothing written. */
+HS_API hs_status hs_pssm_tables(const double* S, const double* t, uint64_t nm, uint32_t k, uint32_t alphabet,
+                                uint8_t* code, double* tau, uint8_t* dead);
 
 /* Replaces Clustering() (hclust2.cpp:86-151) with explicit planes a[L][K][d], b[L][K]: table by
  * table, an LSH table over the not-yet-absorbed k-mers, then greedy leader clustering inside every
