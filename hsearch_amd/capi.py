@@ -34,7 +34,8 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_window_id_start", "hs_seq_match_hits", "hs_seq_match_merge", "hs_join6_tables", "hs_join6_thresholds",
            "hs_join6_selftest", "hs_join6_tile_offset", "hs_index_append", "hs_index_append_dev", "hs_index_append_windows",
            "hs_index_table_append", "hs_index_remove", "hs_index_remove_dev", "hs_index_remove_ranges",
-           "hs_index_table_remove", "hs_pssm_scan", "hs_pssm_scan_dev", "hs_pssm_tables"]
+           "hs_index_table_remove", "hs_pssm_scan", "hs_pssm_scan_dev", "hs_pssm_tables",
+           "hs_pssm_topk", "hs_pssm_topk_dev", "hs_pssm_topk_hits"]
 
 TOPK_MAX = 64        # HS_TOPK_MAX: the widest row of query_topk / self_knn / topk_merge
 NO_ID = 0xffffffff   # the id and table of an unused entry of such a row (its distance is +inf)
@@ -67,7 +68,7 @@ class _Profile(C.Structure):
                 ("append_new_buckets", C.c_uint64), ("remove_rebuilds", C.c_uint64),
                 ("remove_dead_buckets", C.c_uint64), ("remove_retupled", C.c_uint64),
                 ("pssm_pairs", C.c_uint64), ("pssm_survivors", C.c_uint64), ("pssm_dead", C.c_uint64),
-                ("pssm_mfma_steps", C.c_uint64)]
+                ("pssm_mfma_steps", C.c_uint64), ("pssm_topk_sample", C.c_uint64), ("pssm_topk_raised", C.c_uint64)]
 
 
 class _IndexInfo(C.Structure):
@@ -298,6 +299,15 @@ def load(hooks=False):
             lib.hs_pssm_tables.restype = C.c_int
             lib.hs_pssm_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
                                            C.c_void_p, C.c_void_p]
+        # PSSM top-N: (h, S, t_floor, nm, topk, top_id, top_score, top_count, t_used); hits: include/hsearch.h
+        if hasattr(lib, "hs_pssm_topk"):
+            for fn in (lib.hs_pssm_topk, lib.hs_pssm_topk_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p]
+            lib.hs_pssm_topk_hits.restype = C.c_int
+            lib.hs_pssm_topk_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]
         _libs[hooks] = lib
     return _libs[hooks]
 
@@ -753,6 +763,25 @@ def pssm_tables(S, t):
     return dict(code=code, tau=tau, dead=dead)
 
 
+def pssm_topk_hits(m, id, score, nm, topk):
+    """hs_pssm_topk's rule on the host for any list of (m, id, score) tuples (hs_pssm_topk_hits; no GPU): dict(id
+    uint32 [nm][topk] padded with NO_ID, score [nm][topk] padded with -inf, count uint32 [nm]).  Tuples with id == NO_ID
+    are skipped; a repeated (m, id) counts once if its score bits agree, else HsError."""
+    m = np.ascontiguousarray(m, dtype=np.uint32)
+    id = np.ascontiguousarray(id, dtype=np.uint32)
+    score = np.ascontiguousarray(score, dtype=np.float64)
+    assert m.ndim == 1 and m.shape == id.shape == score.shape, (m.shape, id.shape, score.shape)
+    rows = max(int(nm), 0) if 1 <= int(topk) <= TOPK_MAX else 0
+    tid = np.empty((rows, max(int(topk), 1)), dtype=np.uint32)
+    ts = np.empty((rows, max(int(topk), 1)), dtype=np.float64)
+    tc = np.empty(max(rows, 1), dtype=np.uint32)
+    st = load().hs_pssm_topk_hits(_vp(m), _vp(id), _vp(score), C.c_uint64(len(m)), C.c_uint64(int(nm)),
+                                  C.c_uint32(int(topk)), _vp(tid), _vp(ts), _vp(tc))
+    if st:
+        raise HsError(st, "hs_pssm_topk_hits")
+    return dict(id=tid, score=ts, count=tc[:rows])
+
+
 def pssm_log_odds(counts, background=None, pseudo=1.0):
     """Log-odds profiles from position frequency matrices (hs_cluster_profile's counts [rows][k][alphabet]):
     S[r][p][a] = log2((count + pseudo * bg[a]) / (size + pseudo) / bg[a]), size = the row's members (the counts of a
@@ -973,7 +1002,7 @@ class Engine:
                "wide_rows": 6, "refine8": 7, "self_codes": 8, "sort_hits": 10, "sync_items": 11,
                "join_min_q": 12, "join_min_m": 13, "sort_from_bit": 14, "build_serial": 15,
                "join_xcd_run": 16, "probe_records": 17, "join_chunk": 18, "summary_chunk": 19, "summary_rows": 20,
-               "msf_edge_budget": 21, "join_f6": 22, "pssm_filter": 23}
+               "msf_edge_budget": 21, "join_f6": 22, "pssm_filter": 23, "pssm_topk_sample": 24}
 
     def set_option(self, name, value):
         """hs_set_option (include/hsearch.h hs_option): path selection / batch sizing; never changes a result."""
@@ -1526,6 +1555,37 @@ class Engine:
             err.n_hits = int(n.value)
             raise err
         return int(n.value)
+
+    def pssm_topk(self, S, topk, t_floor=None, want_thresholds=False):
+        """hs_pssm_topk: the topk best indexed k-mers of every profile S [nm][k][alphabet] under (score descending, id
+        ascending), among those scoring >= t_floor[m] (None: no floor).  dict(id uint32 [nm][topk] padded with NO_ID,
+        score [nm][topk] padded with -inf, count uint32 [nm][, t_used [nm]: the thresholds the profiles were scanned
+        at -- the one output that depends on the "pssm_topk_sample" option])."""
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        nm = S.shape[0]
+        assert S.shape == (nm, self.k, self._alphabet()), S.shape
+        if t_floor is not None:
+            t_floor = np.ascontiguousarray(t_floor, dtype=np.float64)
+            assert t_floor.shape == (nm,), t_floor.shape
+        cols = int(topk) if 1 <= int(topk) <= TOPK_MAX else 1
+        tid = np.empty((nm, cols), dtype=np.uint32)
+        ts = np.empty((nm, cols), dtype=np.float64)
+        tc = np.empty(max(nm, 1), dtype=np.uint32)
+        tu = np.empty(max(nm, 1), dtype=np.float64) if want_thresholds else None
+        self._check(self._lib.hs_pssm_topk(self._h, _vp(S), _vp(t_floor) if t_floor is not None else None,
+                                           C.c_uint64(nm), C.c_uint32(int(topk)), _vp(tid), _vp(ts), _vp(tc),
+                                           _vp(tu) if want_thresholds else None))
+        res = dict(id=tid, score=ts, count=tc[:nm])
+        if want_thresholds:
+            res["t_used"] = tu[:nm]
+        return res
+
+    def pssm_topk_dev(self, d_S, d_t_floor, nm, topk, d_id, d_score, d_count, d_t_used=None):
+        """hs_pssm_topk_dev: device pointers (ints, e.g. tensor.data_ptr(); d_t_floor and d_t_used may be None)."""
+        self._check(self._lib.hs_pssm_topk_dev(self._h, C.c_void_p(d_S), C.c_void_p(d_t_floor) if d_t_floor else None,
+                                               C.c_uint64(nm), C.c_uint32(int(topk)), C.c_void_p(d_id),
+                                               C.c_void_p(d_score), C.c_void_p(d_count),
+                                               C.c_void_p(d_t_used) if d_t_used else None))
 
     def bruteforce_radii(self, centers, radii, cap=None):
         """hs_bruteforce_radii: brute force with centre q searched at radii[q]."""

@@ -25,6 +25,7 @@
 #include "hs_table_append.h"
 #include "hs_table_remove.h"
 #include "hs_pssm_tables.h"
+#include "hs_pssm_topk.h"
 
 namespace {
 
@@ -104,6 +105,7 @@ struct Knobs {
   int seg_mode = 0;                // HS_OPT_SEG_MODE: 1 sparse / 2 dense; 0 = by the bucket : probe ratio
   int sort_from_bit = 16;          // HS_OPT_SORT_FROM_BIT: lowest fingerprint bit the build's sort looks at
   uint32_t query_batch = 0;        // HS_OPT_QUERY_BATCH: queries per batch (0: by L and the free HBM)
+  uint32_t pssm_topk_sample = 262144;  // HS_OPT_PSSM_TOPK_SAMPLE: k-mers the sample pass of hs_pssm_topk scores per profile
   uint32_t summary_chunk = 0;      // HS_OPT_SUMMARY_CHUNK: member slots per work item of hs_summary.hip (0: 512)
   uint32_t summary_rows = 0;       // HS_OPT_SUMMARY_ROWS: rows per batch of hs_cluster_profile (0: by the scratch budget)
   int64_t msf_edge_budget = -1;    // HS_OPT_MSF_EDGE_BUDGET: bytes of HBM hs_msf may keep pairs in (0 never, -1 a share of the free)
@@ -273,6 +275,9 @@ struct hs_handle {
   // hs_query_topk / hs_self_knn (hs_knn.hip: the scratch listed at its head, all sized by a batch): hits per query,
   // their scan, the scatter's cursors, the call's 64-bit hit count; the counts of a host-pointer call on their way out
   DevBuf knn_cnt, knn_off, knn_cur, knn_total, knn_io_count;
+  // hs_pssm_topk (hs_pssm_topk.hip; the selection's scratch is hs_knn.hip's): a batch's thresholds when the caller
+  // wants none; the sample pass's lists when a profile's sample is split over several workgroups
+  DevBuf pt_tused, pt_parts;
   // hs_seq_match (hs_seqmatch.hip: the scratch listed at its head): a batch's keys and hit indices, their sorted
   // copies, the run heads and their scan, the waves' cut runs; the call's rows so far (sq_rows of them in a list of
   // sq_acc.cap / 40) and their final reduction; the argument check's words; a host-pointer call's arrays in and out
@@ -548,7 +553,7 @@ const struct { const char* name; int option; } kOptionNames[] = {
     {"sort_hits", HS_OPT_SORT_HITS}, {"sync_items", HS_OPT_SYNC_ITEMS}, {"join_min_q", HS_OPT_JOIN_MIN_Q},
     {"join_min_m", HS_OPT_JOIN_MIN_M}, {"sort_from_bit", HS_OPT_SORT_FROM_BIT}, {"build_serial", HS_OPT_BUILD_SERIAL},
     {"join_xcd_run", HS_OPT_JOIN_XCD_RUN}, {"probe_records", HS_OPT_PROBE_RECORDS},
-    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"join_f6", HS_OPT_JOIN_F6}, {"pssm_filter", HS_OPT_PSSM_FILTER}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS},
+    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"join_f6", HS_OPT_JOIN_F6}, {"pssm_filter", HS_OPT_PSSM_FILTER}, {"pssm_topk_sample", HS_OPT_PSSM_TOPK_SAMPLE}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS},
     {"msf_edge_budget", HS_OPT_MSF_EDGE_BUDGET}};
 
 void read_knobs(hs_handle* h) {
@@ -837,6 +842,10 @@ hs_status hs_set_option(hs_handle* h, int option, int64_t value) {
     case HS_OPT_REFINE8: return flag(&kn.no_refine8, true);
     case HS_OPT_JOIN_F6: return flag(&kn.no_join_f6, true);
     case HS_OPT_PSSM_FILTER: return flag(&kn.no_pssm_filter, true);
+    case HS_OPT_PSSM_TOPK_SAMPLE:
+      if (value < 1 || value > 0xffffffffll) break;
+      kn.pssm_topk_sample = (uint32_t)value;
+      return HS_OK;
     case HS_OPT_SELF_CODES: return flag(&kn.no_self_codes, true);
     case HS_OPT_SORT_HITS: return flag(&kn.sort_hits, false);
     case HS_OPT_SYNC_ITEMS: return flag(&kn.sync_items, false);
@@ -912,7 +921,7 @@ void hs_destroy(hs_handle* h) {
                     &h->ann_sorted, &h->ann_cnt, &h->cc_parent, &h->cc_cnt, &h->cc_label,
                     &h->db_deg, &h->db_anchor, &h->db_cnt, &h->msf_comp, &h->msf_best_d, &h->msf_best_pair,
                     &h->msf_out_pair, &h->msf_out_d, &h->msf_s_pair, &h->msf_s_d, &h->msf_cnt, &h->msf_kept, &h->dt_core, &h->dt_thr,
-                    &h->dt_next, &h->dt_cnt, &h->knn_cnt, &h->knn_off, &h->knn_cur, &h->knn_total, &h->knn_io_count,
+                    &h->dt_next, &h->dt_cnt, &h->knn_cnt, &h->knn_off, &h->knn_cur, &h->knn_total, &h->knn_io_count, &h->pt_tused, &h->pt_parts,
                     &h->sq_key, &h->sq_idx, &h->sq_skey, &h->sq_sidx, &h->sq_head, &h->sq_excl, &h->sq_part, &h->sq_acc,
                     &h->sq_fin, &h->sq_chk, &h->sq_in, &h->sq_out,
                     &h->sm_size, &h->sm_tmp, &h->sm_row_of, &h->sm_off_of,
@@ -5862,6 +5871,144 @@ hs_status hs_pssm_scan(hs_handle* h, const double* S, const double* t, uint64_t 
 hs_status hs_pssm_tables(const double* S, const double* t, uint64_t nm, uint32_t k, uint32_t alphabet, uint8_t* code,
                          double* tau, uint8_t* dead) {
   return hs_pssm_tables_host(S, t, nm, k, alphabet, code, tau, dead) ? HS_ERR_INVALID : HS_OK;
+}
+
+// ---- hs_pssm_topk: the topk best k-mers per profile (kernels, the argument and the three steps: hs_pssm_topk.hip) ----
+// The call with every array on the device; the callers have checked the arguments and the values.  d_floor, d_tused
+// may be null.
+static hs_status pssm_topk_core(hs_handle* h, const double* d_S, const double* d_floor, uint64_t nm, uint32_t topk,
+                                uint32_t* d_id, double* d_score, uint32_t* d_count, double* d_tused) {
+  memset(&h->prof, 0, sizeof(h->prof));
+  HS_HIP(h, h->counters.reserve(256));
+  HS_HIP(h, h->knn_total.reserve(16));
+  HS_HIP(h, hipMemsetAsync(h->knn_total.p, 0, 16, h->stream));  // the profiles raised above their floor
+  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
+  const bool filt = !h->knobs.no_pssm_filter;
+  const size_t ka = (size_t)h->p.k * h->alphabet;
+  const uint32_t n = (uint32_t)h->n, n_s = (uint32_t)std::min<uint64_t>(h->n, h->knobs.pssm_topk_sample);
+  uint64_t total = 0, raised = 0;
+  // (an empty index runs no batch: nothing would write the rows)
+  if (nm && !n) HS_HIP(h, hs_launch_pssm_topk_fill(nm, topk, d_floor, d_id, d_score, d_count, d_tused, h->stream));
+  if (nm && n) {
+    // profiles per batch: what HS_OPT_QUERY_BATCH says, or at most 4096 and few enough that the hits to expect --
+    // topk * n / n_s per profile -- stay within 2^24
+    const uint64_t per = std::max<uint64_t>(1, (uint64_t)topk * n / n_s);
+    uint32_t MB = h->knobs.query_batch ? h->knobs.query_batch
+                                       : (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(1, (1ull << 24) / per));
+    uint32_t mb = 0;
+    for (uint64_t m0 = 0; m0 < nm; m0 += mb) {
+      mb = (uint32_t)std::min<uint64_t>(MB, nm - m0);
+      if (!d_tused) HS_HIP(h, h->pt_tused.reserve((size_t)mb * 8));
+      HS_HIP(h, h->pt_parts.reserve(std::max<size_t>(16, hs_pssm_sample_part_bytes(mb, n_s))));
+      double* const tu = d_tused ? d_tused + m0 : h->pt_tused.as<double>();
+      const double* const fl = d_floor ? d_floor + m0 : nullptr;
+      HS_HIP(h, hipEventRecord(h->ev[10], h->stream));
+      HS_HIP(h, hs_launch_pssm_sample(h->codes.as<uint8_t>(), d_S + m0 * ka, fl, (int)h->p.k, h->alphabet, n, n_s, topk,
+                                      mb, h->pt_parts.p, tu, h->stream));
+      HS_HIP(h, hipEventRecord(h->ev[11], h->stream));
+      uint32_t nh = 0;
+      const hs_status st = pssm_batch(h, d_S + m0 * ka, tu, (uint32_t)m0, mb, filt, &nh);
+      if (st == HS_SPLIT_BATCH) {  // (as pssm_core: the same profiles again in batches half the size)
+        if (mb == 1) return fail(h, HS_ERR_CAPACITY, "the filter survivors of one profile exceed 2^32");
+        MB = (mb + 1) / 2;
+        mb = 0;
+        continue;
+      }
+      if (st) return st;
+      h->prof.ms_hash += ev_ms(h, 10, 11);
+      // the selection runs for a batch without hits too: it writes the rows
+      HS_HIP(h, hipEventRecord(h->ev[6], h->stream));
+      const size_t words = ((size_t)mb + 1) * 4;
+      HS_HIP(h, h->knn_cnt.reserve(words));
+      HS_HIP(h, h->knn_off.reserve(words));
+      HS_HIP(h, h->knn_cur.reserve(words));
+      HS_HIP(h, h->hit_key2.reserve(std::max<size_t>(16, (size_t)nh * 8)));
+      HS_HIP(h, h->hit_val2.reserve(std::max<size_t>(16, (size_t)nh * 8)));
+      HS_HIP(h, h->temp.reserve(hs_pssm_topk_temp(mb) + 256));
+      HS_HIP(h, hs_launch_pssm_topk_select(h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(), nh, (uint32_t)m0, mb,
+                                           h->knn_cnt.as<uint32_t>(), h->knn_off.as<uint32_t>(),
+                                           h->knn_cur.as<uint32_t>(), h->temp.p, h->temp.cap,
+                                           h->hit_key2.as<uint64_t>(), h->hit_val2.as<uint64_t>(), topk, fl, tu, d_id,
+                                           d_score, d_count, h->knn_total.as<uint64_t>(), h->stream));
+      HS_HIP(h, hipEventRecord(h->ev[7], h->stream));
+      HS_HIP(h, hipStreamSynchronize(h->stream));
+      h->prof.ms_finalize += ev_ms(h, 6, 7);
+      total += nh;
+    }
+    HS_HIP(h, hipMemcpyAsync(&raised, h->knn_total.p, 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  HS_HIP(h, hipEventRecord(h->ev[9], h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  h->prof.ms_total = ev_ms(h, 8, 9);
+  h->prof.hits = total;
+  h->prof.pssm_topk_sample = n_s;
+  h->prof.pssm_topk_raised = raised;
+  return HS_OK;
+}
+
+static hs_status pssm_topk_args(hs_handle* h, const void* S, uint64_t nm, uint32_t topk, const void* top_id,
+                                const void* top_score, const void* top_count) {
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
+  if (nm >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nm must be < 2^27 per call");
+  if (!topk_ok(topk)) return fail(h, HS_ERR_INVALID, "hs_pssm_topk: topk must be 1 .. 64");
+  if (nm && !S) return fail(h, HS_ERR_INVALID, "hs_pssm_topk: S is null");
+  if (nm && (!top_id || !top_score || !top_count)) return fail(h, HS_ERR_INVALID, "an output array is null");
+  return HS_OK;
+}
+
+hs_status hs_pssm_topk_dev(hs_handle* h, const double* d_S, const double* d_floor, uint64_t nm, uint32_t topk,
+                           uint32_t* d_top_id, double* d_top_score, uint32_t* d_top_count, double* d_t_used) {
+  if (!h) return HS_ERR_INVALID;
+  HS_CHECK(pssm_topk_args(h, d_S, nm, topk, d_top_id, d_top_score, d_top_count));
+  HS_CHECK(ensure_device(h));
+  if (nm) {  // the values, on the device: one small reduction and one read-back, before anything is written
+    uint32_t flag = 0;
+    HS_HIP(h, h->io_radii.reserve(16));
+    HS_HIP(h, hipMemsetAsync(h->io_radii.p, 0, 16, h->stream));
+    HS_HIP(h, hs_launch_pssm_check(d_S, nm * h->p.k * h->alphabet, d_floor, d_floor ? nm : 0, h->io_radii.as<uint32_t>(),
+                                   h->stream));
+    HS_HIP(h, hipMemcpyAsync(&flag, h->io_radii.p, 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    if (flag & 1u) return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
+    if (flag & 2u) return fail(h, HS_ERR_INVALID, "a floor is NaN or infinite");
+  }
+  return pssm_topk_core(h, d_S, d_floor, nm, topk, d_top_id, d_top_score, d_top_count, d_t_used);
+}
+
+hs_status hs_pssm_topk(hs_handle* h, const double* S, const double* t_floor, uint64_t nm, uint32_t topk,
+                       uint32_t* top_id, double* top_score, uint32_t* top_count, double* t_used) {
+  if (!h) return HS_ERR_INVALID;
+  HS_CHECK(pssm_topk_args(h, S, nm, topk, top_id, top_score, top_count));
+  const size_t ka = (size_t)h->p.k * h->alphabet;
+  for (uint64_t i = 0; i < nm * ka; ++i)
+    if (hs_pssm_bad_value(S[i], HS_PSSM_MAX_ABS))
+      return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
+  for (uint64_t m = 0; t_floor && m < nm; ++m)
+    if (hs_pssm_bad_value(t_floor[m], 1.7976931348623157e308)) return fail(h, HS_ERR_INVALID, "a floor is NaN or infinite");
+  HS_CHECK(ensure_device(h));
+  const size_t e = (size_t)nm * topk;
+  HS_HIP(h, h->io_centers.reserve(std::max<size_t>(16, nm * ka * 8)));
+  if (t_floor) HS_HIP(h, h->io_cand.reserve(std::max<size_t>(16, nm * 8)));
+  HS_HIP(h, h->io_id.reserve(std::max<size_t>(16, e * 4)));
+  HS_HIP(h, h->io_dist.reserve(std::max<size_t>(16, e * 8)));
+  HS_HIP(h, h->knn_io_count.reserve(std::max<size_t>(16, nm * 4)));
+  if (t_used) HS_HIP(h, h->io_radii.reserve(std::max<size_t>(16, nm * 8)));
+  if (nm) {
+    HS_HIP(h, hipMemcpyAsync(h->io_centers.p, S, nm * ka * 8, hipMemcpyHostToDevice, h->stream));
+    if (t_floor) HS_HIP(h, hipMemcpyAsync(h->io_cand.p, t_floor, nm * 8, hipMemcpyHostToDevice, h->stream));
+  }
+  // the rows are selected on the device: topk x 12 + 4 (+ 8) bytes per profile cross PCIe
+  HS_CHECK(pssm_topk_core(h, h->io_centers.as<double>(), t_floor ? h->io_cand.as<double>() : nullptr, nm, topk,
+                          h->io_id.as<uint32_t>(), h->io_dist.as<double>(), h->knn_io_count.as<uint32_t>(),
+                          t_used ? h->io_radii.as<double>() : nullptr));
+  if (nm) {
+    HS_HIP(h, hipMemcpyAsync(top_id, h->io_id.p, e * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(top_score, h->io_dist.p, e * 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(top_count, h->knn_io_count.p, nm * 4, hipMemcpyDeviceToHost, h->stream));
+    if (t_used) HS_HIP(h, hipMemcpyAsync(t_used, h->io_radii.p, nm * 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return HS_OK;
 }
 
 hs_status hs_bruteforce_topk(hs_handle* h, const double* centers, uint64_t nq, uint32_t topk,

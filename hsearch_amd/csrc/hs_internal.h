@@ -861,4 +861,25 @@ hipError_t hs_launch_pssm_exact(const uint8_t* d_codes, const double* d_S, const
 hipError_t hs_launch_pssm_emit(const uint64_t* d_key, const uint64_t* d_val, uint32_t nh, bool write, uint32_t* d_out_m,
                                uint32_t* d_out_id, double* d_out_score, uint64_t* d_cnt, hipStream_t s);
 
+// ---- hs_pssm_topk (hs_pssm_topk.hip: the three steps of a batch are written at its head) ---------------------------
+size_t hs_pssm_topk_temp(uint32_t count);    // the scan's workspace for a batch of `count` profiles
+// t_used [mb] = max(floor, the topk-th best exact score among the n_s sample k-mers floor(j * n / n_s)); d_S, d_floor
+// (may be null: no floor) and d_t_used are the batch's
+// d_part_lists: hs_pssm_sample_part_bytes(mb, n_s) bytes (0 with one workgroup per profile: may be null then)
+size_t hs_pssm_sample_part_bytes(uint32_t mb, uint32_t n_s);
+hipError_t hs_launch_pssm_sample(const uint8_t* d_codes, const double* d_S, const double* d_floor, int k, int alphabet,
+                                 uint32_t n, uint32_t n_s, uint32_t topk, uint32_t mb, void* d_part_lists,
+                                 double* d_t_used, hipStream_t s);
+// the batch's nh unordered hits (m << 32 | id, score bits) of profiles [first, first + count) -> rows first .. of the
+// call's arrays, whole rows with their padding, and top_count; d_cnt / d_off / d_cur [count + 1], d_seg_* [nh];
+// d_floor (may be null) and d_t_used are the batch's; *d_raised += the profiles with t_used above their floor
+hipError_t hs_launch_pssm_topk_select(const uint64_t* d_key, const uint64_t* d_val, uint32_t nh, uint32_t first,
+                                      uint32_t count, uint32_t* d_cnt, uint32_t* d_off, uint32_t* d_cur, void* d_temp,
+                                      size_t temp_bytes, uint64_t* d_seg_d, uint64_t* d_seg_w, uint32_t topk,
+                                      const double* d_floor, const double* d_t_used, uint32_t* d_top_id,
+                                      double* d_top_score, uint32_t* d_top_count, uint64_t* d_raised, hipStream_t s);
+// rows of padding, zero counts, t_used (may be null) = the floor: a call that ran no batch
+hipError_t hs_launch_pssm_topk_fill(uint64_t rows, uint32_t topk, const double* d_floor, uint32_t* d_top_id,
+                                    double* d_top_score, uint32_t* d_top_count, double* d_t_used, hipStream_t s);
+
 #endif

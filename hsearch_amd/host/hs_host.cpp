@@ -766,9 +766,12 @@ bool ReadPssmFile(const std::string& path, uint32_t kmer_length, std::vector<std
   return true;
 }
 
-int ScanProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
-                 const std::vector<double>& S, const std::vector<double>& t, const std::string& output_file,
-                 int device, std::string* err, uint64_t* n_windows, uint64_t* n_hits_out) {
+// ScanProfiles (topn == 0: every hit at or above t, hs_pssm_scan) and ScanProfilesTopN (topn >= 1: per profile the topn
+// best windows at or above t, hs_pssm_topk): the same index, the same lines
+static int ScanProfilesAny(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
+                           const std::vector<double>& S, const std::vector<double>& t, uint32_t topn,
+                           const std::string& output_file, int device, std::string* err, uint64_t* n_windows,
+                           uint64_t* n_hits_out) {
   const uint32_t k = kmer_length;
   const size_t nm = t.size();
   if (k < 2 || names.size() != nm || S.size() != nm * (size_t)k * HS_ALPHABET) {
@@ -818,7 +821,23 @@ int ScanProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<st
   std::vector<uint32_t> hm, hid;
   std::vector<double> hs;
   uint64_t n_hits = 0;
-  for (uint64_t cap = 0;;) {  // the hit count, then the hits
+  if (topn) {  // the rows, selected on the device, flattened into the scan's lists: (profile, rank) order
+    std::vector<uint32_t> top_id(nm * (size_t)topn), top_count(nm);
+    std::vector<double> top_score(nm * (size_t)topn);
+    st = hs_pssm_topk(h, S.data(), t.data(), nm, topn, top_id.data(), top_score.data(), top_count.data(), nullptr);
+    if (st != HS_OK) {
+      if (err) *err = std::string("hs_pssm_topk: ") + hs_last_error(h);
+      return st;
+    }
+    for (size_t m = 0; m < nm; ++m)
+      for (uint32_t r = 0; r < top_count[m]; ++r) {
+        hm.push_back((uint32_t)m);
+        hid.push_back(top_id[m * topn + r]);
+        hs.push_back(top_score[m * topn + r]);
+      }
+    n_hits = hm.size();
+  }
+  for (uint64_t cap = 0; !topn;) {  // the hit count, then the hits
     hm.resize(cap);
     hid.resize(cap);
     hs.resize(cap);
@@ -848,6 +867,23 @@ int ScanProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<st
   }
   fout.close();
   return HS_OK;
+}
+
+int ScanProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
+                 const std::vector<double>& S, const std::vector<double>& t, const std::string& output_file,
+                 int device, std::string* err, uint64_t* n_windows, uint64_t* n_hits_out) {
+  return ScanProfilesAny(db, kmer_length, names, S, t, 0, output_file, device, err, n_windows, n_hits_out);
+}
+
+int ScanProfilesTopN(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
+                     const std::vector<double>& S, const std::vector<double>& t_floor, uint32_t topn,
+                     const std::string& output_file, int device, std::string* err, uint64_t* n_windows,
+                     uint64_t* n_lines) {
+  if (topn < 1 || topn > HS_TOPK_MAX) {
+    if (err) *err = "top N must be 1 .. 64";
+    return HS_ERR_INVALID;
+  }
+  return ScanProfilesAny(db, kmer_length, names, S, t_floor, topn, output_file, device, err, n_windows, n_lines);
 }
 
 // "<first token of the protein's name>#<its number>": how the search's k-mer names begin

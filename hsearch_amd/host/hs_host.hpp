@@ -192,6 +192,13 @@ bool ReadPssmFile(const std::string& path, uint32_t kmer_length, std::vector<std
 int ScanProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
                  const std::vector<double>& S, const std::vector<double>& t, const std::string& output_file,
                  int device, std::string* err, uint64_t* n_windows = nullptr, uint64_t* n_hits = nullptr);
+// `--pssm FILE --pssm-top N`: per profile at most N lines, its N best windows among those scoring at or above the
+// file's threshold (the floor), selected on the device (hs_pssm_topk; 1 <= N <= 64).  The same lines as ScanProfiles
+// writes; profiles in file order, within a profile by descending score, then ascending window index.
+int ScanProfilesTopN(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
+                     const std::vector<double>& S, const std::vector<double>& t_floor, uint32_t topn,
+                     const std::string& output_file, int device, std::string* err, uint64_t* n_windows = nullptr,
+                     uint64_t* n_lines = nullptr);
 // center_codes (CentersFromKmers): the centres are k-mers of the exact table -- the one a FASTA
 // database is embedded from -- and travel to the GPU as residue codes (hs_query_codes: k bytes per
 // centre instead of 64 k); the hits are those of the embedded centres, bit for bit.

@@ -32,7 +32,9 @@
 // --pssm FILE (FASTA database): no search at all -- every window of every protein scored against the position-
 // specific score matrices of FILE (hs_pssm_scan), one line per hit "<profile> <window name> <score>", the score with
 // 17 significant digits; -c, -W and -T are not needed, and -c, --radii, -M, --topk, --per-sequence,
-// --best-per-position, --query-fasta, --db-append and --gpus above 1 are refused.
+// --best-per-position, --query-fasta, --db-append and --gpus above 1 are refused.  With --pssm-top N (1..64): per
+// profile at most N lines, its N best windows among those at or above the file's threshold (hs_pssm_topk), by
+// descending score, then ascending window index; --pssm-top without --pssm is refused.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -86,6 +88,7 @@ const Opt kOpts[] = {
     {"topk", 't', "per centre only its N best hits, 1..64, in ascending (distance, k-mer index) (one GPU) [off: all hits]", false},
     {"db-append", 'A', "FASTA database: a further FASTA file whose sequences follow -d's, appended to the built index on the GPU; repeatable (one GPU)", false},
     {"pssm", 'm', "FASTA database: scan every window against the position-specific score matrices of this file ('>name threshold', then -l lines of 20 numbers) in place of a search: no -c, -W, -T (one GPU)", false},
+    {"pssm-top", 'n', "with --pssm: per profile only its N best windows, 1..64, among those at or above the file's threshold, by descending score then window index [off: every hit]", false},
 };
 
 // A points file has a line of numbers after its first name line; a FASTA file has residue letters.
@@ -129,6 +132,16 @@ int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::str
     fprintf(stderr, "ERROR: --pssm cannot be combined with --db-append\n");
     return EXIT_FAILURE;
   }
+  uint32_t top_n = 0;  // 0: every hit
+  if (val.count("pssm-top")) {
+    char* end = nullptr;
+    const long v = strtol(val["pssm-top"].c_str(), &end, 10);
+    if (end == val["pssm-top"].c_str() || *end || v < 1 || v > 64) {
+      fprintf(stderr, "ERROR: --pssm-top takes a number of lines per profile, 1..64\n");
+      return EXIT_FAILURE;
+    }
+    top_n = (uint32_t)v;
+  }
   const uint32_t kmer_length = (uint32_t)strtoul(val["len"].c_str(), nullptr, 10);
   const int device = val.count("device") ? atoi(val["device"].c_str()) : 0;
   try {
@@ -156,7 +169,10 @@ int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::str
     struct timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     uint64_t n_windows = 0, n_hits = 0;
-    const int st = hsearch::ScanProfiles(prodb, kmer_length, names, S, t, val["output"], device, &err, &n_windows, &n_hits);
+    const int st = top_n ? hsearch::ScanProfilesTopN(prodb, kmer_length, names, S, t, top_n, val["output"], device, &err,
+                                                     &n_windows, &n_hits)
+                         : hsearch::ScanProfiles(prodb, kmer_length, names, S, t, val["output"], device, &err, &n_windows,
+                                                 &n_hits);
     if (st != 0) {
       fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), st);
       return EXIT_FAILURE;
@@ -214,6 +230,10 @@ int main(int argc, const char* argv[]) {
   }
   const bool query_fasta = val.count("query-fasta") != 0;
   const bool with_pssm = val.count("pssm") != 0;
+  if (val.count("pssm-top") && !with_pssm) {
+    fprintf(stderr, "ERROR: --pssm-top selects among the hits of --pssm: it cannot be given without it\n");
+    return EXIT_FAILURE;
+  }
   const bool per_sequence = query_fasta || (val.count("per-sequence") && atoi(val["per-sequence"].c_str()) != 0);
   for (const Opt& o : kOpts)
     if (o.required && !val.count(o.long_name) && !(query_fasta && std::string(o.long_name) == "center") &&

@@ -113,6 +113,8 @@ typedef struct hs_profile {
                                   HS_OPT_PSSM_FILTER = 0: all of them) */
   uint64_t pssm_dead;          /* ... profiles skipped because no k-mer can reach their threshold (filter on only) */
   uint64_t pssm_mfma_steps;    /* ... MFMA depth steps per 16 x 16 tile: ceil(k * alphabet / 128) (0: filter off) */
+  uint64_t pssm_topk_sample;   /* hs_pssm_topk*: the sample size n_s = min(n, HS_OPT_PSSM_TOPK_SAMPLE) the call used */
+  uint64_t pssm_topk_raised;   /* hs_pssm_topk*: profiles scanned at a threshold above their floor (t_used > floor) */
 } hs_profile;
 
 typedef struct hs_index_info {
@@ -199,6 +201,8 @@ typedef enum hs_option {
                                 FP6 MFMA (hs_join6x_kernel); 0: never (hs_join8x_kernel) */
   HS_OPT_PSSM_FILTER = 23,   /* hs_pssm_scan: 1 (default): the FP6 MFMA filter in front of the exact pass; 0: no filter,
                                 every (profile, k-mer) pair goes to the exact pass */
+  HS_OPT_PSSM_TOPK_SAMPLE = 24, /* hs_pssm_topk: k-mers of the index the sample pass scores per profile (>= 1, default
+                                262144 = 2^18; the index's size where it is smaller).  Shows in t_used only, never in a row */
   HS_OPT_JOIN_XCD_RUN = 16  /* hs_join8x_kernel's work items dealt in runs of this many chunks per XCD, each XCD's
                                 waves on their own runs (a run's items stream the same query tiles: one L2 fetches
                                 them instead of eight).  0: one counter for the chip; -1 (default): by the size
@@ -1153,7 +1157,8 @@ HS_API hs_status hs_cluster_summary_codes(const uint8_t* codes, uint64_t n, uint
  * and alone decides.  hs_profile after the call: pssm_pairs, pssm_survivors, pssm_dead, pssm_mfma_steps, hits;
  * ms_verify (tables + filter), ms_finalize (exact pass and ordering), ms_total.  Scratch is sized by a batch and
  * comes from the handle's growable buffers.  Every other entry point runs as before, launch for launch.
- * Out of scope: top-N per profile, a per-sequence reduction of profile hits, multi-GPU, an int8 form of the filter. */
+ * Out of scope: a per-sequence reduction of profile hits, multi-GPU, an int8 form of the filter.  (Top-N per profile:
+ * hs_pssm_topk below.) */
 HS_API hs_status hs_pssm_scan(hs_handle* h, const double* S, const double* t, uint64_t nm, uint32_t* hit_m,
                               uint32_t* hit_id, double* hit_score, uint64_t cap, uint64_t* n_hits, uint64_t* cnt);
 /* ... every pointer but n_hits in device memory (streams: as hs_query_dev) */
@@ -1168,6 +1173,52 @@ HS_API hs_status hs_pssm_scan_dev(hs_handle* h, const double* d_S, const double*
  * nm >= 2^27 and the values hs_pssm_scan refuses are HS_ERR_INVALID, with nothing written. */
 HS_API hs_status hs_pssm_tables(const double* S, const double* t, uint64_t nm, uint32_t k, uint32_t alphabet,
                                 uint8_t* code, double* tau, uint8_t* dead);
+
+/* ---- PSSM top-N: the topk best k-mers of every profile, without a threshold ------------------------------------- */
+
+/* "Show me the N best sites of each profile": hs_pssm_scan needs a threshold per profile, and log-odds thresholds do
+ * not transfer from one motif to the next.  Here the threshold is found on the device and the rows are selected there.
+ *
+ * Inputs: S [nm][k][alphabet] as for hs_pssm_scan; t_floor [nm], or NULL for no floor (every floor -DBL_MAX);
+ * 1 <= topk <= HS_TOPK_MAX.
+ * Score: hs_pssm_scan's, bit for bit -- from +0.0, left to right, every sum rounded to fp64.
+ * Row m: of the k-mers with score >= t_floor[m], the min(topk, their number) best under (score descending, id
+ * ascending).  top_id [nm][topk] padded with 0xffffffff, top_score [nm][topk] padded with -infinity, top_count [nm] =
+ * the valid entries of the row = min(topk, number of k-mers at or above the floor) -- deliberately not a hit count.
+ * The order is strict and total: a score is never a NaN, an infinity (the 2^100 cap) or -0.0 (the sum starts at +0.0),
+ * and ids are distinct (hsearch_amd/csrc/hs_pssm_topk.h states the argument and holds the key transform).
+ * Errors, reported before anything is written: hs_pssm_scan's (an unbuilt index is HS_ERR_STATE; nm >= 2^27, a bad
+ * entry, a NaN or infinite floor are HS_ERR_INVALID; the _dev form finds the values on the device), topk outside its
+ * range, a null output with nm > 0.  n == 0 or nm == 0: padded rows, zero counts.
+ * Purity: rows and counts are a pure function of (codes, S, t_floor, topk).  HS_OPT_PSSM_TOPK_SAMPLE, the profile batch
+ * (HS_OPT_QUERY_BATCH), HS_OPT_PSSM_FILTER, survivor splits and scheduling do not show in them.
+ *
+ * How, and why it is exact.  With n_s = min(n, HS_OPT_PSSM_TOPK_SAMPLE), the sample is the k-mers s_j = floor(j * n /
+ * n_s), j = 0 .. n_s - 1 (64-bit arithmetic).  t'[m] = the topk-th largest exact score of profile m over the sample,
+ * if n_s >= topk.  At least topk k-mers of the index score >= t', so every member of the row scores >= t', ties
+ * included: the scan of hs_pssm_scan at
+ *   t_used[m] = max(t_floor[m], t'[m])      (t_floor[m] where there is no t')
+ * returns a superset of the row, and a wave per profile selects the row from it.  t_used [nm] (may be NULL) is that
+ * threshold: a diagnostic, and the one output that DOES depend on the sample size.  No hit list crosses PCIe.
+ * Profiles per batch: HS_OPT_QUERY_BATCH if set; else at most 4096 and few enough that batch * topk * n / n_s, the
+ * hits to expect, stays within 2^24.  A constant profile ties every k-mer at t': n hits for it, and the right row.
+ * hs_profile after the call: the pssm_* fields as after a scan at t_used, pssm_topk_sample, pssm_topk_raised, hits
+ * (what the scans returned); ms_hash (sample pass), ms_verify (tables + filter), ms_finalize (exact pass + selection),
+ * ms_total.  Every other entry point runs as before, launch for launch.
+ * Out of scope: topk above 64, a threshold from the filter's own accumulators, a ladder of growing samples,
+ * multi-GPU drivers (hs_pssm_topk_hits is the merge). */
+HS_API hs_status hs_pssm_topk(hs_handle* h, const double* S, const double* t_floor, uint64_t nm, uint32_t topk,
+                              uint32_t* top_id, double* top_score, uint32_t* top_count, double* t_used);
+/* ... every pointer in device memory (streams: as hs_pssm_scan_dev) */
+HS_API hs_status hs_pssm_topk_dev(hs_handle* h, const double* d_S, const double* d_t_floor, uint64_t nm, uint32_t topk,
+                                  uint32_t* d_top_id, double* d_top_score, uint32_t* d_top_count, double* d_t_used);
+/* The same rule on the host (no GPU, no handle) for any list of (m, id, score) tuples: the merge of several GPUs' rows.
+ * Tuples with id == 0xffffffff are skipped (padding fed back in is harmless); a repeated (m, id) with the same score
+ * bits counts once, with different bits it is HS_ERR_INVALID; a NaN score, m >= nm, topk outside 1 .. HS_TOPK_MAX or a
+ * null output with nm > 0 are HS_ERR_INVALID, with nothing written.  top_count[m] = min(topk, distinct ids of m). */
+HS_API hs_status hs_pssm_topk_hits(const uint32_t* m, const uint32_t* id, const double* score, uint64_t n_tuples,
+                                   uint64_t nm, uint32_t topk, uint32_t* top_id, double* top_score,
+                                   uint32_t* top_count);
 
 /* Replaces Clustering() (hclust2.cpp:86-151) with explicit planes a[L][K][d], b[L][K]: table by
  * table, an LSH table over the not-yet-absorbed k-mers, then greedy leader clustering inside every
