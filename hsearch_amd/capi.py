@@ -35,7 +35,8 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_join6_selftest", "hs_join6_tile_offset", "hs_index_append", "hs_index_append_dev", "hs_index_append_windows",
            "hs_index_table_append", "hs_index_remove", "hs_index_remove_dev", "hs_index_remove_ranges",
            "hs_index_table_remove", "hs_pssm_scan", "hs_pssm_scan_dev", "hs_pssm_tables",
-           "hs_pssm_topk", "hs_pssm_topk_dev", "hs_pssm_topk_hits"]
+           "hs_pssm_topk", "hs_pssm_topk_dev", "hs_pssm_topk_hits", "hs_pssm_seq_scan", "hs_pssm_seq_scan_dev",
+           "hs_pssm_seq_hits"]
 
 TOPK_MAX = 64        # HS_TOPK_MAX: the widest row of query_topk / self_knn / topk_merge
 NO_ID = 0xffffffff   # the id and table of an unused entry of such a row (its distance is +inf)
@@ -68,7 +69,8 @@ class _Profile(C.Structure):
                 ("append_new_buckets", C.c_uint64), ("remove_rebuilds", C.c_uint64),
                 ("remove_dead_buckets", C.c_uint64), ("remove_retupled", C.c_uint64),
                 ("pssm_pairs", C.c_uint64), ("pssm_survivors", C.c_uint64), ("pssm_dead", C.c_uint64),
-                ("pssm_mfma_steps", C.c_uint64), ("pssm_topk_sample", C.c_uint64), ("pssm_topk_raised", C.c_uint64)]
+                ("pssm_mfma_steps", C.c_uint64), ("pssm_seq_rows", C.c_uint64), ("pssm_topk_sample", C.c_uint64),
+                ("pssm_topk_raised", C.c_uint64)]
 
 
 class _IndexInfo(C.Structure):
@@ -308,6 +310,17 @@ def load(hooks=False):
             lib.hs_pssm_topk_hits.restype = C.c_int
             lib.hs_pssm_topk_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32,
                                               C.c_void_p, C.c_void_p, C.c_void_p]
+        # PSSM hits per sequence: (h, S, t, nm, id_start, n_seq, 7 row arrays, cap, &n_out, &n_hits, cnt, seq_cnt);
+        # hits: (m, id, score, n_tuples, nm, id_start, n_seq, 7 row arrays, cap, &n_out)
+        if hasattr(lib, "hs_pssm_seq_scan"):
+            rows7 = [C.c_void_p] * 7
+            for fn in (lib.hs_pssm_seq_scan, lib.hs_pssm_seq_scan_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64] + rows7 + [
+                    C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]
+            lib.hs_pssm_seq_hits.restype = C.c_int
+            lib.hs_pssm_seq_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                             C.c_uint64] + rows7 + [C.c_uint64, C.POINTER(C.c_uint64)]
         _libs[hooks] = lib
     return _libs[hooks]
 
@@ -780,6 +793,44 @@ def pssm_topk_hits(m, id, score, nm, topk):
     if st:
         raise HsError(st, "hs_pssm_topk_hits")
     return dict(id=tid, score=ts, count=tc[:rows])
+
+
+PSSM_SEQ_FIELDS = (("m", np.uint32), ("seq", np.uint32), ("count", np.uint32), ("best_score", np.float64),
+                   ("best_id", np.uint32), ("lo", np.uint32), ("hi", np.uint32))
+
+
+def _pssm_seq_rows(cap):
+    return [np.empty(cap, dtype=t) for _, t in PSSM_SEQ_FIELDS]
+
+
+def _pssm_seq_dict(arrs, n):
+    return {name: a[:n] for (name, _), a in zip(PSSM_SEQ_FIELDS, arrs)}
+
+
+def pssm_seq_hits(m, id, score, nm, id_start, cap=None, out=None):
+    """hs_pssm_seq_hits (host only, no GPU): the rule of Engine.pssm_seq_scan over ANY list of hits (m, id, score) in
+    any order -- one row per distinct (profile, sequence): dict(m, seq, count, best_score, best_id, lo, hi).  A (m, id)
+    given twice with one score counts once.  cap=None: as many rows as needed; a given cap that is too small raises
+    HsError(HS_ERR_CAPACITY) with the required size in .needed.  out: a list of the seven arrays to write into."""
+    m = np.ascontiguousarray(m, dtype=np.uint32).ravel()
+    id = np.ascontiguousarray(id, dtype=np.uint32).ravel()
+    score = np.ascontiguousarray(score, dtype=np.float64).ravel()
+    n = len(m)
+    assert id.shape == score.shape == (n,)
+    if id_start is not None:
+        id_start = np.ascontiguousarray(id_start, dtype=np.uint64)
+        assert id_start.ndim == 1 and len(id_start) >= 1
+    room = n if cap is None else int(cap)
+    arrs = _pssm_seq_rows(room) if out is None else out
+    n_out = C.c_uint64(0)
+    st = load().hs_pssm_seq_hits(_vp(m), _vp(id), _vp(score), n, int(nm), None if id_start is None else _vp(id_start),
+                                 0 if id_start is None else len(id_start) - 1, *[_vp(a) for a in arrs], room,
+                                 C.byref(n_out))
+    if st != HS_OK:
+        e = HsError(st, "hs_pssm_seq_hits")
+        e.needed = int(n_out.value)
+        raise e
+    return _pssm_seq_dict(arrs, int(n_out.value))
 
 
 def pssm_log_odds(counts, background=None, pseudo=1.0):
@@ -1586,6 +1637,61 @@ class Engine:
                                                C.c_uint64(nm), C.c_uint32(int(topk)), C.c_void_p(d_id),
                                                C.c_void_p(d_score), C.c_void_p(d_count),
                                                C.c_void_p(d_t_used) if d_t_used else None))
+
+    def pssm_seq_scan(self, S, t, id_start, cap=None, want_counts=True):
+        """hs_pssm_seq_scan: the hits of pssm_scan(S, t) reduced on the device per (profile, database sequence):
+        dict(m, seq, count, best_score, best_id, lo, hi -- one row per distinct (m, seq), ascending --, n_hits[, cnt
+        [nm] the hits and seq_cnt [nm] the rows per profile]).  id_start [n_seq + 1]: sequence s owns the ids
+        [id_start[s], id_start[s + 1]) (capi.window_id_start for a windows index).  cap=None: two calls, the row count
+        then the rows; a given cap that is too small raises HsError(HS_ERR_CAPACITY) with .needed, .n_hits and, with
+        want_counts, .cnt and .seq_cnt."""
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        nm = S.shape[0]
+        assert S.shape == (nm, self.k, self._alphabet()) and t.shape == (nm,), (S.shape, t.shape)
+        if id_start is not None:
+            id_start = np.ascontiguousarray(id_start, dtype=np.uint64)
+            assert id_start.ndim == 1 and len(id_start) >= 1
+        n_seq = 0 if id_start is None else len(id_start) - 1
+        cnt = np.zeros(nm, dtype=np.uint64) if want_counts else None
+        seq_cnt = np.zeros(nm, dtype=np.uint64) if want_counts else None
+        room = 0 if cap is None else int(cap)
+        while True:
+            arrs = _pssm_seq_rows(room)
+            n, nh = C.c_uint64(0), C.c_uint64(0)
+            st = self._lib.hs_pssm_seq_scan(self._h, _vp(S), _vp(t), nm, None if id_start is None else _vp(id_start),
+                                            n_seq, *[_vp(a) if room else None for a in arrs], room, C.byref(n),
+                                            C.byref(nh), _vp(cnt) if want_counts else None,
+                                            _vp(seq_cnt) if want_counts else None)
+            if st == HS_ERR_CAPACITY:
+                if cap is None and int(n.value) > room:
+                    room = int(n.value)
+                    continue
+                e = HsError(st, self._lib.hs_last_error(self._h).decode())
+                e.needed, e.n_hits, e.cnt, e.seq_cnt = int(n.value), int(nh.value), cnt, seq_cnt
+                raise e
+            self._check(st)
+            res = _pssm_seq_dict(arrs, int(n.value))
+            res["n_hits"] = int(nh.value)
+            if want_counts:
+                res["cnt"], res["seq_cnt"] = cnt, seq_cnt
+            return res
+
+    def pssm_seq_scan_dev(self, d_S, d_t, nm, d_id_start, n_seq, d_rows, cap, d_cnt=None, d_seq_cnt=None):
+        """hs_pssm_seq_scan_dev: device pointers (ints, e.g. tensor.data_ptr(); d_rows: the seven row arrays in the
+        order of capi.PSSM_SEQ_FIELDS).  Returns (rows, n_hits); raises HsError(HS_ERR_CAPACITY) with the required size
+        in .needed and the hit count in .n_hits when cap is too small."""
+        n, nh = C.c_uint64(0), C.c_uint64(0)
+        st = self._lib.hs_pssm_seq_scan_dev(self._h, d_S if d_S else None, d_t if d_t else None, int(nm),
+                                            d_id_start if d_id_start else None, int(n_seq),
+                                            *[p if p else None for p in d_rows], int(cap), C.byref(n), C.byref(nh),
+                                            d_cnt if d_cnt else None, d_seq_cnt if d_seq_cnt else None)
+        if st == HS_ERR_CAPACITY:
+            e = HsError(st, self._lib.hs_last_error(self._h).decode())
+            e.needed, e.n_hits = int(n.value), int(nh.value)
+            raise e
+        self._check(st)
+        return int(n.value), int(nh.value)
 
     def bruteforce_radii(self, centers, radii, cap=None):
         """hs_bruteforce_radii: brute force with centre q searched at radii[q]."""

@@ -25,6 +25,7 @@
 #include "hs_table_append.h"
 #include "hs_table_remove.h"
 #include "hs_pssm_tables.h"
+#include "hs_pssm_seq.h"
 #include "hs_pssm_topk.h"
 
 namespace {
@@ -5744,13 +5745,11 @@ static hs_status pssm_batch(hs_handle* h, const double* d_S, const double* d_t, 
   return HS_OK;
 }
 
-// The scan with every array on the device; the callers have checked the arguments and the values.
-static hs_status pssm_core(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm, uint32_t* d_hit_m,
-                           uint32_t* d_hit_id, double* d_hit_score, uint64_t cap, uint64_t* n_hits, uint64_t* d_cnt_out) {
-  memset(&h->prof, 0, sizeof(h->prof));
-  HS_HIP(h, h->counters.reserve(256));
-  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
-  if (d_cnt_out && nm) HS_HIP(h, hipMemsetAsync(d_cnt_out, 0, nm * 8, h->stream));
+// The batch loop of a scan: sink(m0, mb, nh) takes every batch that has hits (profiles m0 .. m0 + mb - 1 of the call,
+// nh unordered hits in hit_key / hit_val) and queues its work on the stream; ms_finalize takes its time.
+extern "C++" template <class Sink>
+static hs_status pssm_batches(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm, uint64_t* n_hits,
+                              Sink&& sink) {
   const bool filt = !h->knobs.no_pssm_filter;
   const size_t ka = (size_t)h->p.k * h->alphabet;
   uint64_t total = 0;
@@ -5770,22 +5769,8 @@ static hs_status pssm_core(hs_handle* h, const double* d_S, const double* d_t, u
       }
       if (st) return st;
       if (nh) {
-        const uint64_t at = std::min<uint64_t>(total, cap);
-        const bool fits = nh <= cap - at;
-        const uint64_t *key = h->hit_key.as<uint64_t>(), *val = h->hit_val.as<uint64_t>();
         HS_HIP(h, hipEventRecord(h->ev[6], h->stream));
-        if (fits) {  // the order (m, id): the 64-bit sort of the hit lists, on the key m << 32 | id
-          HS_HIP(h, h->hit_key2.reserve((size_t)nh * 8));
-          HS_HIP(h, h->hit_val2.reserve((size_t)nh * 8));
-          HS_HIP(h, h->temp.reserve(hs_sort_pairs_u64_u64_temp(nh) + 256));
-          HS_HIP(h, hs_sort_pairs_u64_u64(h->temp.p, h->temp.cap, key, h->hit_key2.as<uint64_t>(), val,
-                                          h->hit_val2.as<uint64_t>(), nh, 32 + bit_width_u32((uint32_t)(m0 + mb)),
-                                          h->stream));
-          key = h->hit_key2.as<uint64_t>();
-          val = h->hit_val2.as<uint64_t>();
-        }
-        HS_HIP(h, hs_launch_pssm_emit(key, val, nh, fits, fits ? d_hit_m + at : nullptr, fits ? d_hit_id + at : nullptr,
-                                      fits ? d_hit_score + at : nullptr, d_cnt_out, h->stream));
+        HS_CHECK(sink((uint32_t)m0, mb, nh));
         HS_HIP(h, hipEventRecord(h->ev[7], h->stream));
         HS_HIP(h, hipStreamSynchronize(h->stream));
         h->prof.ms_finalize += ev_ms(h, 6, 7);
@@ -5798,8 +5783,194 @@ static hs_status pssm_core(hs_handle* h, const double* d_S, const double* d_t, u
   h->prof.ms_total = ev_ms(h, 8, 9);
   h->prof.hits = total;
   *n_hits = total;
-  if (total > cap) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
   return HS_OK;
+}
+
+// the order (m, id) of a batch's nh hits: the 64-bit sort of the hit lists on the key m << 32 | id, into hit_key2 /
+// hit_val2
+static hs_status pssm_sort_hits(hs_handle* h, uint32_t m0, uint32_t mb, uint32_t nh, size_t temp_also) {
+  HS_HIP(h, h->hit_key2.reserve((size_t)nh * 8));
+  HS_HIP(h, h->hit_val2.reserve((size_t)nh * 8));
+  HS_HIP(h, h->temp.reserve(std::max(hs_sort_pairs_u64_u64_temp(nh), temp_also) + 256));
+  HS_HIP(h, hs_sort_pairs_u64_u64(h->temp.p, h->temp.cap, h->hit_key.as<uint64_t>(), h->hit_key2.as<uint64_t>(),
+                                  h->hit_val.as<uint64_t>(), h->hit_val2.as<uint64_t>(), nh,
+                                  32 + bit_width_u32(m0 + mb), h->stream));
+  return HS_OK;
+}
+
+// The scan with every array on the device; the callers have checked the arguments and the values.
+static hs_status pssm_core(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm, uint32_t* d_hit_m,
+                           uint32_t* d_hit_id, double* d_hit_score, uint64_t cap, uint64_t* n_hits, uint64_t* d_cnt_out) {
+  memset(&h->prof, 0, sizeof(h->prof));
+  HS_HIP(h, h->counters.reserve(256));
+  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
+  if (d_cnt_out && nm) HS_HIP(h, hipMemsetAsync(d_cnt_out, 0, nm * 8, h->stream));
+  uint64_t total = 0;
+  HS_CHECK(pssm_batches(h, d_S, d_t, nm, n_hits, [&](uint32_t m0, uint32_t mb, uint32_t nh) -> hs_status {
+    const uint64_t at = std::min<uint64_t>(total, cap);
+    const bool fits = nh <= cap - at;
+    const uint64_t *key = h->hit_key.as<uint64_t>(), *val = h->hit_val.as<uint64_t>();
+    if (fits) {
+      HS_CHECK(pssm_sort_hits(h, m0, mb, nh, 0));
+      key = h->hit_key2.as<uint64_t>();
+      val = h->hit_val2.as<uint64_t>();
+    }
+    HS_HIP(h, hs_launch_pssm_emit(key, val, nh, fits, fits ? d_hit_m + at : nullptr, fits ? d_hit_id + at : nullptr,
+                                  fits ? d_hit_score + at : nullptr, d_cnt_out, h->stream));
+    total += nh;
+    return HS_OK;
+  }));
+  if (*n_hits > cap) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
+  return HS_OK;
+}
+
+// ---- hs_pssm_seq_scan: the scan's hits reduced per (profile, sequence) (kernels and the passes: hs_pssm_seq.hip) ----
+struct PssmSeqOut {
+  uint32_t *m, *seq, *count;
+  double* best_score;
+  uint32_t *best_id, *lo, *hi;
+  bool all() const { return m && seq && count && best_score && best_id && lo && hi; }
+};
+
+// The call with every array on the device; the callers have checked the arguments and the values.  A batch's rows are
+// final (every hit of a profile lies in its batch) and follow the rows of the batches before it.
+static hs_status pssm_seq_core(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm,
+                               const uint64_t* d_id_start, uint64_t n_seq, const PssmSeqOut& out, uint64_t cap,
+                               uint64_t* n_out, uint64_t* n_hits, uint64_t* d_cnt_out, uint64_t* d_seq_cnt_out) {
+  memset(&h->prof, 0, sizeof(h->prof));
+  HS_HIP(h, h->counters.reserve(256));
+  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
+  if (d_cnt_out && nm) HS_HIP(h, hipMemsetAsync(d_cnt_out, 0, nm * 8, h->stream));
+  if (d_seq_cnt_out && nm) HS_HIP(h, hipMemsetAsync(d_seq_cnt_out, 0, nm * 8, h->stream));
+  uint64_t total_rows = 0;
+  HS_CHECK(pssm_batches(h, d_S, d_t, nm, n_hits, [&](uint32_t m0, uint32_t mb, uint32_t nh) -> hs_status {
+    HS_CHECK(pssm_sort_hits(h, m0, mb, nh, hs_scan_u32_temp((size_t)nh + 1)));
+    const uint64_t *key = h->hit_key2.as<uint64_t>(), *val = h->hit_val2.as<uint64_t>();
+    HS_HIP(h, h->sq_sidx.reserve((size_t)nh * 4));  // the sequence of every hit
+    HS_HIP(h, h->sq_head.reserve(((size_t)nh + 1) * 4));
+    HS_HIP(h, h->sq_excl.reserve(((size_t)nh + 1) * 4));
+    HS_HIP(h, hs_launch_pssm_seq_head(key, nh, d_id_start, n_seq, h->sq_sidx.as<uint32_t>(), h->sq_head.as<uint32_t>(),
+                                      h->stream));
+    HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, h->sq_head.as<uint32_t>(), h->sq_excl.as<uint32_t>(),
+                                    (size_t)nh + 1, h->stream));
+    uint32_t rows = 0;
+    HS_HIP(h, hipMemcpyAsync(&rows, h->sq_excl.as<uint32_t>() + nh, 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    if (!rows || rows > nh) return fail(h, HS_ERR_HIP, "hs_pssm_seq_scan: the row count of a batch is out of range");
+    const uint64_t at = std::min<uint64_t>(total_rows, cap);
+    const bool fits = rows <= cap - at;
+    HS_HIP(h, h->sq_skey.reserve(((size_t)rows + 1) * 4));  // where every row's run starts
+    HS_HIP(h, h->sq_key.reserve((size_t)rows * 8));         // the rows' best score keys ...
+    HS_HIP(h, h->sq_idx.reserve((size_t)rows * 4));         // ... and ids
+    HS_HIP(h, h->sq_part.reserve(hs_pssm_seq_part_bytes(nh)));
+    HS_HIP(h, hs_launch_pssm_seq_rows(key, val, h->sq_sidx.as<uint32_t>(), h->sq_head.as<uint32_t>(),
+                                      h->sq_excl.as<uint32_t>(), nh, rows, d_id_start, fits, h->sq_skey.as<uint32_t>(),
+                                      h->sq_key.as<uint64_t>(), h->sq_idx.as<uint32_t>(), h->sq_part.p,
+                                      fits ? out.m + at : nullptr, fits ? out.seq + at : nullptr,
+                                      fits ? out.count + at : nullptr, fits ? out.best_score + at : nullptr,
+                                      fits ? out.best_id + at : nullptr, fits ? out.lo + at : nullptr,
+                                      fits ? out.hi + at : nullptr, d_cnt_out, d_seq_cnt_out, h->stream));
+    total_rows += rows;
+    return HS_OK;
+  }));
+  h->prof.pssm_seq_rows = total_rows;
+  *n_out = total_rows;
+  if (total_rows > cap) return fail(h, HS_ERR_CAPACITY, "row buffers too small; see *n_out");
+  return HS_OK;
+}
+
+// what both forms refuse from the arguments alone (hs_pssm_scan's refusals first)
+static hs_status pssm_seq_args(hs_handle* h, const void* S, const void* t, uint64_t nm, const void* id_start,
+                               uint64_t n_seq, const PssmSeqOut& out, uint64_t cap) {
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
+  if (nm >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nm must be < 2^27 per call");
+  if (nm && (!S || !t)) return fail(h, HS_ERR_INVALID, "hs_pssm_seq_scan: S or t is null");
+  if (cap && !out.all()) return fail(h, HS_ERR_INVALID, "an output array is null");
+  if (!id_start) return fail(h, HS_ERR_INVALID, "hs_pssm_seq_scan: id_start is null");
+  if (n_seq > (1ull << 32)) return fail(h, HS_ERR_INVALID, "hs_pssm_seq_scan: more than 2^32 sequences");
+  if (!n_seq && h->n) return fail(h, HS_ERR_INVALID, "hs_pssm_seq_scan: no sequence owns the index's k-mers");
+  return HS_OK;
+}
+
+hs_status hs_pssm_seq_scan_dev(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm,
+                               const uint64_t* d_id_start, uint64_t n_seq, uint32_t* d_out_m, uint32_t* d_out_seq,
+                               uint32_t* d_out_count, double* d_out_best_score, uint32_t* d_out_best_id,
+                               uint32_t* d_out_lo, uint32_t* d_out_hi, uint64_t cap, uint64_t* n_out, uint64_t* n_hits,
+                               uint64_t* d_cnt, uint64_t* d_seq_cnt) {
+  if (!h || !n_out || !n_hits) return HS_ERR_INVALID;
+  *n_out = 0;
+  *n_hits = 0;
+  const PssmSeqOut out{d_out_m, d_out_seq, d_out_count, d_out_best_score, d_out_best_id, d_out_lo, d_out_hi};
+  HS_CHECK(pssm_seq_args(h, d_S, d_t, nm, d_id_start, n_seq, out, cap));
+  HS_CHECK(ensure_device(h));
+  {  // the values, on the device: one small reduction each over the profiles and id_start, one read-back
+    uint64_t chk[5] = {0, 0, 0, 0, 0};
+    HS_HIP(h, h->sq_chk.reserve(64));
+    HS_HIP(h, hipMemsetAsync(h->sq_chk.p, 0, 64, h->stream));
+    if (nm)
+      HS_HIP(h, hs_launch_pssm_check(d_S, nm * h->p.k * h->alphabet, d_t, nm, h->sq_chk.as<uint32_t>() + 8, h->stream));
+    HS_HIP(h, hs_launch_sm_check(nullptr, nullptr, 0, 0, d_id_start, n_seq, h->n, h->sq_chk.as<uint64_t>(), h->stream));
+    HS_HIP(h, hipMemcpyAsync(chk, h->sq_chk.p, 40, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    if (chk[4] & 1u) return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
+    if (chk[4] & 2u) return fail(h, HS_ERR_INVALID, "a threshold is NaN or infinite");
+    if (chk[0] & 7) return fail(h, HS_ERR_INVALID, "hs_pssm_seq_scan: id_start must ascend from 0 to the index's k-mers");
+  }
+  return pssm_seq_core(h, d_S, d_t, nm, d_id_start, n_seq, out, cap, n_out, n_hits, d_cnt, d_seq_cnt);
+}
+
+hs_status hs_pssm_seq_scan(hs_handle* h, const double* S, const double* t, uint64_t nm, const uint64_t* id_start,
+                           uint64_t n_seq, uint32_t* out_m, uint32_t* out_seq, uint32_t* out_count,
+                           double* out_best_score, uint32_t* out_best_id, uint32_t* out_lo, uint32_t* out_hi,
+                           uint64_t cap, uint64_t* n_out, uint64_t* n_hits, uint64_t* cnt, uint64_t* seq_cnt) {
+  if (!h || !n_out || !n_hits) return HS_ERR_INVALID;
+  *n_out = 0;
+  *n_hits = 0;
+  const PssmSeqOut out{out_m, out_seq, out_count, out_best_score, out_best_id, out_lo, out_hi};
+  HS_CHECK(pssm_seq_args(h, S, t, nm, id_start, n_seq, out, cap));
+  const size_t ka = (size_t)h->p.k * h->alphabet;
+  for (uint64_t i = 0; i < nm * ka; ++i)
+    if (hs_pssm_bad_value(S[i], HS_PSSM_MAX_ABS))
+      return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
+  for (uint64_t m = 0; m < nm; ++m)
+    if (hs_pssm_bad_value(t[m], 1.7976931348623157e308)) return fail(h, HS_ERR_INVALID, "a threshold is NaN or infinite");
+  if (!hs_pssm_seq_id_start_ok(id_start, n_seq) || id_start[n_seq] != h->n)
+    return fail(h, HS_ERR_INVALID, "hs_pssm_seq_scan: id_start must ascend from 0 to the index's k-mers");
+  HS_CHECK(ensure_device(h));
+  // the rows are staged on the device at the caller's capacity: 32 bytes per row cross PCIe, never the hits
+  const size_t sb = ((size_t)n_seq + 1) * 8, cb = std::max<size_t>(16, nm * 8);
+  HS_HIP(h, h->io_centers.reserve(std::max<size_t>(16, nm * ka * 8)));
+  HS_HIP(h, h->io_radii.reserve(cb));
+  HS_HIP(h, h->sq_in.reserve(sb));
+  HS_HIP(h, h->sq_out.reserve(std::max<size_t>(64, (size_t)cap * 32)));
+  if (cnt || seq_cnt) HS_HIP(h, h->io_cand.reserve(2 * cb));
+  if (nm) {
+    HS_HIP(h, hipMemcpyAsync(h->io_centers.p, S, nm * ka * 8, hipMemcpyHostToDevice, h->stream));
+    HS_HIP(h, hipMemcpyAsync(h->io_radii.p, t, nm * 8, hipMemcpyHostToDevice, h->stream));
+  }
+  HS_HIP(h, hipMemcpyAsync(h->sq_in.p, id_start, sb, hipMemcpyHostToDevice, h->stream));
+  char* const o = h->sq_out.as<char>();
+  uint32_t* const w = reinterpret_cast<uint32_t*>(o + cap * 8);
+  const PssmSeqOut dev{w, w + cap, w + 2 * cap, reinterpret_cast<double*>(o), w + 3 * cap, w + 4 * cap, w + 5 * cap};
+  uint64_t* const d_cnt = cnt ? h->io_cand.as<uint64_t>() : nullptr;
+  uint64_t* const d_seq_cnt = seq_cnt ? reinterpret_cast<uint64_t*>(h->io_cand.as<char>() + cb) : nullptr;
+  const hs_status st = pssm_seq_core(h, h->io_centers.as<double>(), h->io_radii.as<double>(), nm,
+                                     h->sq_in.as<uint64_t>(), n_seq, dev, cap, n_out, n_hits, d_cnt, d_seq_cnt);
+  if (st != HS_OK && st != HS_ERR_CAPACITY) return st;
+  if (cnt && nm) HS_HIP(h, hipMemcpyAsync(cnt, d_cnt, nm * 8, hipMemcpyDeviceToHost, h->stream));
+  if (seq_cnt && nm) HS_HIP(h, hipMemcpyAsync(seq_cnt, d_seq_cnt, nm * 8, hipMemcpyDeviceToHost, h->stream));
+  const size_t r = (size_t)*n_out;
+  if (st == HS_OK && r) {
+    HS_HIP(h, hipMemcpyAsync(out_m, dev.m, r * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_seq, dev.seq, r * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_count, dev.count, r * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_best_score, dev.best_score, r * 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_best_id, dev.best_id, r * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_lo, dev.lo, r * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_hi, dev.hi, r * 4, hipMemcpyDeviceToHost, h->stream));
+  }
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return st;
 }
 
 static hs_status pssm_args(hs_handle* h, const void* S, const void* t, uint64_t nm, const void* hit_m, const void* hit_id,

@@ -882,4 +882,21 @@ hipError_t hs_launch_pssm_topk_select(const uint64_t* d_key, const uint64_t* d_v
 hipError_t hs_launch_pssm_topk_fill(uint64_t rows, uint32_t topk, const double* d_floor, uint32_t* d_top_id,
                                     double* d_top_score, uint32_t* d_top_count, double* d_t_used, hipStream_t s);
 
+// ---- hs_pssm_seq_scan (hs_pssm_seq.hip: the passes over a batch's sorted hits are written at its head) -------------
+// head: the n hits sorted by m << 32 | id -> d_seq [n] (the sequence of every hit) and d_head [n + 1] (row starts)
+hipError_t hs_launch_pssm_seq_head(const uint64_t* d_key, uint32_t n, const uint64_t* d_id_start, uint64_t n_seq,
+                                   uint32_t* d_seq, uint32_t* d_head, hipStream_t s);
+size_t hs_pssm_seq_part_bytes(uint32_t n);
+// rows: d_excl = the exclusive scan of d_head over n + 1 elements, n_rows its total.  Scratch: d_row_start [n_rows + 1],
+// d_row_key / d_row_id [n_rows], d_part of hs_pssm_seq_part_bytes(n) bytes.  write: the rows go to the seven output
+// arrays (the batch's: already at the call's running offset); else only the counts.  *d_cnt [m] += the hits of every
+// row of m, *d_seq_cnt [m] += its rows (either may be null).
+hipError_t hs_launch_pssm_seq_rows(const uint64_t* d_key, const uint64_t* d_val, const uint32_t* d_seq,
+                                   const uint32_t* d_head, const uint32_t* d_excl, uint32_t n, uint32_t n_rows,
+                                   const uint64_t* d_id_start, bool write, uint32_t* d_row_start, uint64_t* d_row_key,
+                                   uint32_t* d_row_id, void* d_part, uint32_t* d_out_m, uint32_t* d_out_seq,
+                                   uint32_t* d_out_count, double* d_out_best_score, uint32_t* d_out_best_id,
+                                   uint32_t* d_out_lo, uint32_t* d_out_hi, uint64_t* d_cnt, uint64_t* d_seq_cnt,
+                                   hipStream_t s);
+
 #endif

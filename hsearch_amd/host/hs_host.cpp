@@ -767,11 +767,12 @@ bool ReadPssmFile(const std::string& path, uint32_t kmer_length, std::vector<std
 }
 
 // ScanProfiles (topn == 0: every hit at or above t, hs_pssm_scan) and ScanProfilesTopN (topn >= 1: per profile the topn
-// best windows at or above t, hs_pssm_topk): the same index, the same lines
+// best windows at or above t, hs_pssm_topk): the same index, the same lines.  ScanProfilesPerSequence (n_rows_out
+// given): the same index, one line per (profile, protein) (hs_pssm_seq_scan).
 static int ScanProfilesAny(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
                            const std::vector<double>& S, const std::vector<double>& t, uint32_t topn,
                            const std::string& output_file, int device, std::string* err, uint64_t* n_windows,
-                           uint64_t* n_hits_out) {
+                           uint64_t* n_hits_out, uint64_t* n_rows_out = nullptr) {
   const uint32_t k = kmer_length;
   const size_t nm = t.size();
   if (k < 2 || names.size() != nm || S.size() != nm * (size_t)k * HS_ALPHABET) {
@@ -782,7 +783,9 @@ static int ScanProfilesAny(const ProteinDB& db, uint32_t kmer_length, const std:
   std::vector<uint8_t> res(db.residues);
   std::vector<uint64_t> seg;
   const size_t n_seq = db.start.empty() ? 0 : db.start.size() - 1;
+  std::vector<size_t> first_seg(n_seq + 1);  // the first segment of every protein
   for (size_t s = 0; s < n_seq; ++s) {
+    first_seg[s] = seg.size();
     seg.push_back(db.start[s]);
     for (uint64_t p = db.start[s]; p < db.start[s + 1]; ++p)
       if (res[p] == ProteinDB::kUnknown) {
@@ -791,6 +794,7 @@ static int ScanProfilesAny(const ProteinDB& db, uint32_t kmer_length, const std:
         seg.push_back(p + 1);
       }
   }
+  first_seg[n_seq] = seg.size();
   seg.push_back(db.residues.size());
   // no hash table takes part in a scan: the smallest family there is
   const Planes planes = DrawPlanes(8 * k, 1, 1, 1.0, 0);
@@ -818,6 +822,47 @@ static int ScanProfilesAny(const ProteinDB& db, uint32_t kmer_length, const std:
     return st;
   }
   if (n_windows) *n_windows = n_win;
+  if (n_rows_out) {
+    // a protein's segments follow one another, so its windows are one id range: the range of its first segment on
+    std::vector<uint64_t> seg_ids(seg.size()), id_start(n_seq + 1);
+    st = hs_window_id_start(seg.data(), seg.size() - 1, k, seg_ids.data());
+    if (st != HS_OK) {
+      if (err) *err = "hs_window_id_start refused the segments";
+      return st;
+    }
+    for (size_t s = 0; s <= n_seq; ++s) id_start[s] = seg_ids[first_seg[s]];
+    std::vector<uint32_t> rm, rs, rc, rid, rlo, rhi;
+    std::vector<double> rsc;
+    uint64_t n_rows = 0, n_hits = 0;
+    for (uint64_t cap = 0;;) {  // the row count, then the rows
+      for (std::vector<uint32_t>* v : {&rm, &rs, &rc, &rid, &rlo, &rhi}) v->resize(cap);
+      rsc.resize(cap);
+      st = hs_pssm_seq_scan(h, S.data(), t.data(), nm, id_start.data(), n_seq, rm.data(), rs.data(), rc.data(),
+                            rsc.data(), rid.data(), rlo.data(), rhi.data(), cap, &n_rows, &n_hits, nullptr, nullptr);
+      if (st == HS_ERR_CAPACITY && n_rows > cap) {
+        cap = n_rows;
+        continue;
+      }
+      break;
+    }
+    if (st != HS_OK) {
+      if (err) *err = std::string("hs_pssm_seq_scan: ") + hs_last_error(h);
+      return st;
+    }
+    if (n_hits_out) *n_hits_out = n_hits;
+    *n_rows_out = n_rows;
+    std::ofstream fout(output_file.c_str());
+    char num[64];
+    for (uint64_t i = 0; i < n_rows; ++i) {  // offsets are residue offsets in the protein, as the scan's window names
+      const size_t s = rs[i];
+      const uint64_t at = db.start[s], w0 = id_start[s];
+      snprintf(num, sizeof(num), "%.17g", rsc[i]);
+      fout << names[rm[i]] << " " << ProteinLabel(db, s) << " " << rc[i] << " " << (win_pos[rid[i]] - at) << " " << num
+           << " " << (win_pos[w0 + rlo[i]] - at) << " " << (win_pos[w0 + rhi[i]] - at) << "\n";
+    }
+    fout.close();
+    return HS_OK;
+  }
   std::vector<uint32_t> hm, hid;
   std::vector<double> hs;
   uint64_t n_hits = 0;
@@ -884,6 +929,15 @@ int ScanProfilesTopN(const ProteinDB& db, uint32_t kmer_length, const std::vecto
     return HS_ERR_INVALID;
   }
   return ScanProfilesAny(db, kmer_length, names, S, t_floor, topn, output_file, device, err, n_windows, n_lines);
+}
+
+int ScanProfilesPerSequence(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
+                            const std::vector<double>& S, const std::vector<double>& t, const std::string& output_file,
+                            int device, std::string* err, uint64_t* n_windows, uint64_t* n_hits, uint64_t* n_rows) {
+  uint64_t rows = 0;
+  const int st = ScanProfilesAny(db, kmer_length, names, S, t, 0, output_file, device, err, n_windows, n_hits, &rows);
+  if (n_rows) *n_rows = rows;
+  return st;
 }
 
 // "<first token of the protein's name>#<its number>": how the search's k-mer names begin

@@ -199,6 +199,14 @@ int ScanProfilesTopN(const ProteinDB& db, uint32_t kmer_length, const std::vecto
                      const std::vector<double>& S, const std::vector<double>& t_floor, uint32_t topn,
                      const std::string& output_file, int device, std::string* err, uint64_t* n_windows = nullptr,
                      uint64_t* n_lines = nullptr);
+// `--pssm FILE --pssm-per-sequence 1`: one line per (profile, protein) with a hit, reduced on the device
+// (hs_pssm_seq_scan): "<profile name> <protein>#<number> <hits> <offset of the best window> <its score> <first> <last
+// matched offset>", the offsets in residues from the protein's start, the score with 17 significant digits; profiles
+// in file order, proteins in database order.  *n_hits: the hits behind the rows, *n_rows: the lines.
+int ScanProfilesPerSequence(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
+                            const std::vector<double>& S, const std::vector<double>& t, const std::string& output_file,
+                            int device, std::string* err, uint64_t* n_windows = nullptr, uint64_t* n_hits = nullptr,
+                            uint64_t* n_rows = nullptr);
 // center_codes (CentersFromKmers): the centres are k-mers of the exact table -- the one a FASTA
 // database is embedded from -- and travel to the GPU as residue codes (hs_query_codes: k bytes per
 // centre instead of 64 k); the hits are those of the embedded centres, bit for bit.

@@ -34,7 +34,10 @@
 // 17 significant digits; -c, -W and -T are not needed, and -c, --radii, -M, --topk, --per-sequence,
 // --best-per-position, --query-fasta, --db-append and --gpus above 1 are refused.  With --pssm-top N (1..64): per
 // profile at most N lines, its N best windows among those at or above the file's threshold (hs_pssm_topk), by
-// descending score, then ascending window index; --pssm-top without --pssm is refused.
+// descending score, then ascending window index; --pssm-top without --pssm is refused.  With --pssm-per-sequence 1:
+// instead of the hits, one line per (profile, protein) with a hit -- "<profile> <protein>#<number> <hits> <best
+// window's offset> <its score> <first> <last matched offset>" --, reduced on the device (hs_pssm_seq_scan), profiles in
+// file order, proteins in database order; refused without --pssm and with --pssm-top.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -89,6 +92,7 @@ const Opt kOpts[] = {
     {"db-append", 'A', "FASTA database: a further FASTA file whose sequences follow -d's, appended to the built index on the GPU; repeatable (one GPU)", false},
     {"pssm", 'm', "FASTA database: scan every window against the position-specific score matrices of this file ('>name threshold', then -l lines of 20 numbers) in place of a search: no -c, -W, -T (one GPU)", false},
     {"pssm-top", 'n', "with --pssm: per profile only its N best windows, 1..64, among those at or above the file's threshold, by descending score then window index [off: every hit]", false},
+    {"pssm-per-sequence", 'e', "with --pssm: instead of the hits, one line per (profile, protein) with a hit: count, best window and its score, span; not with --pssm-top [0]", false},
 };
 
 // A points file has a line of numbers after its first name line; a FASTA file has residue letters.
@@ -142,6 +146,11 @@ int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::str
     }
     top_n = (uint32_t)v;
   }
+  const bool per_sequence = val.count("pssm-per-sequence") && atoi(val["pssm-per-sequence"].c_str()) != 0;
+  if (per_sequence && top_n) {
+    fprintf(stderr, "ERROR: --pssm-per-sequence reduces every hit of a profile: it cannot be combined with --pssm-top\n");
+    return EXIT_FAILURE;
+  }
   const uint32_t kmer_length = (uint32_t)strtoul(val["len"].c_str(), nullptr, 10);
   const int device = val.count("device") ? atoi(val["device"].c_str()) : 0;
   try {
@@ -168,11 +177,13 @@ int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::str
     std::cout << "number of profiles " << names.size() << std::endl;
     struct timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
-    uint64_t n_windows = 0, n_hits = 0;
-    const int st = top_n ? hsearch::ScanProfilesTopN(prodb, kmer_length, names, S, t, top_n, val["output"], device, &err,
-                                                     &n_windows, &n_hits)
-                         : hsearch::ScanProfiles(prodb, kmer_length, names, S, t, val["output"], device, &err, &n_windows,
-                                                 &n_hits);
+    uint64_t n_windows = 0, n_hits = 0, n_rows = 0;
+    const int st = per_sequence ? hsearch::ScanProfilesPerSequence(prodb, kmer_length, names, S, t, val["output"], device,
+                                                                   &err, &n_windows, &n_hits, &n_rows)
+                   : top_n ? hsearch::ScanProfilesTopN(prodb, kmer_length, names, S, t, top_n, val["output"], device, &err,
+                                                       &n_windows, &n_hits)
+                           : hsearch::ScanProfiles(prodb, kmer_length, names, S, t, val["output"], device, &err,
+                                                   &n_windows, &n_hits);
     if (st != 0) {
       fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), st);
       return EXIT_FAILURE;
@@ -180,6 +191,7 @@ int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::str
     clock_gettime(CLOCK_MONOTONIC, &t1);
     std::cout << "number of kmers " << n_windows << std::endl;
     std::cout << "number of hits " << n_hits << std::endl;
+    if (per_sequence) std::cout << "number of rows " << n_rows << std::endl;
     printf("SCAN: %lf seconds\n", (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec));
   } catch (const std::bad_alloc&) {
     fprintf(stderr, "ERROR: could not allocate memory\n");
@@ -232,6 +244,10 @@ int main(int argc, const char* argv[]) {
   const bool with_pssm = val.count("pssm") != 0;
   if (val.count("pssm-top") && !with_pssm) {
     fprintf(stderr, "ERROR: --pssm-top selects among the hits of --pssm: it cannot be given without it\n");
+    return EXIT_FAILURE;
+  }
+  if (val.count("pssm-per-sequence") && !with_pssm) {
+    fprintf(stderr, "ERROR: --pssm-per-sequence reduces the hits of --pssm: it cannot be given without it\n");
     return EXIT_FAILURE;
   }
   const bool per_sequence = query_fasta || (val.count("per-sequence") && atoi(val["per-sequence"].c_str()) != 0);

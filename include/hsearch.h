@@ -113,6 +113,7 @@ typedef struct hs_profile {
                                   HS_OPT_PSSM_FILTER = 0: all of them) */
   uint64_t pssm_dead;          /* ... profiles skipped because no k-mer can reach their threshold (filter on only) */
   uint64_t pssm_mfma_steps;    /* ... MFMA depth steps per 16 x 16 tile: ceil(k * alphabet / 128) (0: filter off) */
+  uint64_t pssm_seq_rows;      /* hs_pssm_seq_scan*: the (profile, sequence) rows the call found (its *n_out) */
   uint64_t pssm_topk_sample;   /* hs_pssm_topk*: the sample size n_s = min(n, HS_OPT_PSSM_TOPK_SAMPLE) the call used */
   uint64_t pssm_topk_raised;   /* hs_pssm_topk*: profiles scanned at a threshold above their floor (t_used > floor) */
 } hs_profile;
@@ -1157,8 +1158,8 @@ HS_API hs_status hs_cluster_summary_codes(const uint8_t* codes, uint64_t n, uint
  * and alone decides.  hs_profile after the call: pssm_pairs, pssm_survivors, pssm_dead, pssm_mfma_steps, hits;
  * ms_verify (tables + filter), ms_finalize (exact pass and ordering), ms_total.  Scratch is sized by a batch and
  * comes from the handle's growable buffers.  Every other entry point runs as before, launch for launch.
- * Out of scope: a per-sequence reduction of profile hits, multi-GPU, an int8 form of the filter.  (Top-N per profile:
- * hs_pssm_topk below.) */
+ * Out of scope: multi-GPU, an int8 form of the filter.  (Top-N per profile: hs_pssm_topk below; the hits reduced per
+ * protein: hs_pssm_seq_scan below.) */
 HS_API hs_status hs_pssm_scan(hs_handle* h, const double* S, const double* t, uint64_t nm, uint32_t* hit_m,
                               uint32_t* hit_id, double* hit_score, uint64_t cap, uint64_t* n_hits, uint64_t* cnt);
 /* ... every pointer but n_hits in device memory (streams: as hs_query_dev) */
@@ -1219,6 +1220,63 @@ HS_API hs_status hs_pssm_topk_dev(hs_handle* h, const double* d_S, const double*
 HS_API hs_status hs_pssm_topk_hits(const uint32_t* m, const uint32_t* id, const double* score, uint64_t n_tuples,
                                    uint64_t nm, uint32_t topk, uint32_t* top_id, double* top_score,
                                    uint32_t* top_count);
+
+/* ---- PSSM hits per sequence: which proteins carry the motif, how often, and where the best site is ---------------- */
+
+/* hs_pssm_scan answers "which k-mers match this profile"; over a protein database the question is which proteins, and
+ * the hit list that answers it through the host is large at the thresholds where it matters.  Here the list is reduced
+ * on the device and only the rows cross PCIe.
+ *
+ * Inputs: S, t, the score and the hit rule are hs_pssm_scan's, bit for bit.  Let H be the hit list hs_pssm_scan returns
+ * for the same arguments on the same handle.  id_start [n_seq + 1] follows hs_seq_match's rules: ascending (equal
+ * neighbours allowed: a sequence without ids), id_start[0] == 0, id_start[n_seq] == n (hs_window_id_start gives it for
+ * a windows index).  Sequence s owns the ids [id_start[s], id_start[s + 1]); an id lying at equal neighbours belongs to
+ * the LAST sequence that starts at or below it.
+ * Rows: one per distinct (m, s) of H, ascending in (m, s).  out_count: the hits of H with that key (ids are 32-bit, so
+ * it fits).  out_best_score, out_best_id: the best hit under (score descending, id ascending) -- hs_pssm_topk's order,
+ * through the key transform of hsearch_amd/csrc/hs_pssm_topk.h; the score is the hit's hit_score bit for bit.  out_lo,
+ * out_hi: the smallest and the largest id - id_start[s] among the row's hits.
+ * Counts: *n_hits is the scan's *n_hits; the row counts sum to it.  cnt [nm] (may be NULL): the hits per profile;
+ * seq_cnt [nm] (may be NULL): the rows per profile, the sequences it hits.  Both valid on HS_OK and HS_ERR_CAPACITY.
+ * Capacity: counted in ROWS, the two-call pattern: HS_ERR_CAPACITY comes with *n_out set (cap = 0 with NULL arrays
+ * asks for the count); *n_out <= *n_hits and *n_out <= nm * n_seq.  hs_pssm_seq_scan writes no row then; the _dev form
+ * may have written the rows of the batches that still fitted, as hs_pssm_scan_dev does with hits.
+ * Errors, reported before anything is written: everything hs_pssm_scan refuses; a null id_start; an id_start that does
+ * not ascend, does not start at 0 or does not end at n; n_seq == 0 with n > 0; n_seq > 2^32.  All HS_ERR_INVALID but
+ * the unbuilt index (HS_ERR_STATE).  The _dev form finds the value errors on the device: one small reduction over the
+ * profiles, hs_seq_match's over id_start, one read-back.
+ * Purity: the rows are a pure function of (codes, S, t, id_start).  The profile batch (HS_OPT_QUERY_BATCH),
+ * HS_OPT_PSSM_FILTER, survivor splits and scheduling do not show in them.
+ *
+ * How (hsearch_amd/csrc/hs_pssm_seq.hip): the scan's batches, tables, filter and exact pass as they are.  Batches are
+ * cut by profile and a sequence owns a contiguous id range, so after the scan's own (m, id) sort every row is one
+ * contiguous run in output order: the sequence of every hit by a search in id_start, run heads, their scan, a wave-wide
+ * segmented scan for the best hit, and the batch's rows written at the call's running offset.  No second sort, no row
+ * list on the handle, no merge.  Scratch is sized by a batch's hits and rows.
+ * hs_profile after the call: the pssm_* fields as after a scan, pssm_seq_rows, hits; ms_finalize covers the exact
+ * pass, the sort and the reduction.  Every other entry point runs as before, launch for launch.
+ * Out of scope: diagonals and query groups for profiles, top-N per (profile, protein), multi-GPU drivers
+ * (hs_pssm_seq_hits is the merge). */
+HS_API hs_status hs_pssm_seq_scan(hs_handle* h, const double* S, const double* t, uint64_t nm,
+                                  const uint64_t* id_start, uint64_t n_seq, uint32_t* out_m, uint32_t* out_seq,
+                                  uint32_t* out_count, double* out_best_score, uint32_t* out_best_id, uint32_t* out_lo,
+                                  uint32_t* out_hi, uint64_t cap, uint64_t* n_out, uint64_t* n_hits, uint64_t* cnt,
+                                  uint64_t* seq_cnt);
+/* ... every pointer but n_out / n_hits in device memory (streams: as hs_pssm_scan_dev) */
+HS_API hs_status hs_pssm_seq_scan_dev(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm,
+                                      const uint64_t* d_id_start, uint64_t n_seq, uint32_t* d_out_m,
+                                      uint32_t* d_out_seq, uint32_t* d_out_count, double* d_out_best_score,
+                                      uint32_t* d_out_best_id, uint32_t* d_out_lo, uint32_t* d_out_hi, uint64_t cap,
+                                      uint64_t* n_out, uint64_t* n_hits, uint64_t* d_cnt, uint64_t* d_seq_cnt);
+/* The same rule on the host (no GPU, no handle) for any list of (m, id, score) tuples in any order: the merge of several
+ * GPUs' hit lists.  A repeated (m, id) with equal score bits counts once, with different bits it is HS_ERR_INVALID; a
+ * NaN score, m >= nm, an id at or beyond id_start[n_seq], an id_start the scan refuses (its end is not compared with
+ * an index here) and a null output with cap > 0 are HS_ERR_INVALID, with nothing written.  HS_ERR_CAPACITY: *n_out
+ * set, no row written. */
+HS_API hs_status hs_pssm_seq_hits(const uint32_t* m, const uint32_t* id, const double* score, uint64_t n_tuples,
+                                  uint64_t nm, const uint64_t* id_start, uint64_t n_seq, uint32_t* out_m,
+                                  uint32_t* out_seq, uint32_t* out_count, double* out_best_score, uint32_t* out_best_id,
+                                  uint32_t* out_lo, uint32_t* out_hi, uint64_t cap, uint64_t* n_out);
 
 /* Replaces Clustering() (hclust2.cpp:86-151) with explicit planes a[L][K][d], b[L][K]: table by
  * table, an LSH table over the not-yet-absorbed k-mers, then greedy leader clustering inside every
