@@ -219,57 +219,73 @@ __device__ __forceinline__ void sign_step6(int g, const floatx4 (&acc)[4][2], fl
                                                  // compiler cannot trace costs two more instructions here)
   asm volatile("" : "+v"(w[g]));
 }
-__device__ __forceinline__ bool group_pass6(const float (&w)[16], const float (&C)[2]) {
-  return (w[7] >= -C[0]) | (w[15] >= -C[1]);
+// The wave's ballots of the two column tiles' maxima against their thresholds: no pair of the group passed iff
+// both are zero.
+__device__ __forceinline__ void group_pass6(const float (&w)[16], const float (&C)[2], uint64_t (&pass)[2]) {
+  pass[0] = __builtin_amdgcn_ballot_w64(w[7] >= -C[0]);
+  pass[1] = __builtin_amdgcn_ballot_w64(w[15] >= -C[1]);
 }
 
-// Survivors of one group (row tiles T0 .. T0 + 3) against the 32 queries at segment-relative offset qc
+// Survivors of one group (row tiles T0 .. T0 + 3) against the 32 queries at segment-relative offset qc.  A few
+// per cent of the phases come here, nearly all of them for ONE pair, so the path looks before it computes:
+//   - only a column tile whose maximum passed (colpass[c], wave-uniform) is looked at;
+//   - one compare per accumulator register, written to a scalar pair, is the wave's ballot for that register,
+//     and a register without a survivor costs that compare and a scalar branch;
+//   - per-lane masks and indices are formed for the registers that have one, and the list is written by one
+//     loop per column tile (bit 4 t + i of the mask = row 16 t + 4 q + i of the group).
 __device__ __forceinline__ void emit_survivors6(const floatx4 (&acc)[4][2], int T0, uint32_t qc, uint32_t qoff,
                                                 uint32_t q_end, uint32_t wbase, uint32_t M, uint32_t mstart,
-                                                const float (&C)[2], int lane, uint32_t& res_base,
-                                                uint32_t& res_used,
+                                                const float (&C)[2], const uint64_t (&colpass)[2], int lane,
+                                                uint32_t& res_base, uint32_t& res_used,
                                                 uint32_t* __restrict__ prov_count, uint32_t prov_cap,
                                                 uint2* __restrict__ prov) {
   const uint32_t n = (uint32_t)lane & 15u, q = (uint32_t)lane >> 4;
 #pragma unroll
-  for (int t = 0; t < 4; ++t)
+  for (int c = 0; c < 2; ++c) {
+    if (!colpass[c]) continue;
+    const float thr = -C[c];
+    uint32_t mask = 0;
 #pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const float thr = -C[c];
-      uint32_t mask = 0;
+    for (int t = 0; t < 4; ++t)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) mask |= (acc[t][c][i] >= thr ? 1u : 0u) << i;
-      if (!__ballot(mask != 0)) continue;  // no survivor in this 16 x 16 tile
-      const uint32_t col = qc + 16u * (uint32_t)c + n;
-      if (!(col < q_end)) mask = 0u;
-      const uint32_t ql = HS_PROV_INDIRECT | (qoff + col);
-      while (__ballot(mask != 0)) {
-        uint32_t idx = 0;
-        bool pass = false;
-        if (mask) {
-          const int i = __ffs((int)mask) - 1;
-          mask &= mask - 1;
-          idx = wbase + (uint32_t)(16 * (T0 + t)) + 4u * q + (uint32_t)i;
-          pass = idx < M;
-        }
-        const unsigned long long m = __ballot(pass);
-        if (m) {
-          const uint32_t cnt = (uint32_t)__popcll(m);
-          if (res_used + cnt > JRES) {
-            close_reservation(prov, res_base, res_used, prov_cap, lane);
-            uint32_t base = 0;
-            if (lane == 0) base = hs_reserve_survivors(prov_count, (uint32_t)JRES);
-            res_base = __builtin_amdgcn_readfirstlane(base);
-            res_used = 0;
-          }
-          if (pass) {
-            const uint32_t o = res_base + res_used + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            if (o < prov_cap) prov[o] = make_uint2(ql, mstart + idx);
-          }
-          res_used += cnt;
+      for (int i = 0; i < 4; ++i) {
+        const bool hit = acc[t][c][i] >= thr;
+        if (__builtin_amdgcn_ballot_w64(hit)) {
+          asm volatile("" : "+v"(mask));  // (keeps the branch: the compiler would else compute every mask bit)
+          mask |= (hit ? 1u : 0u) << (4 * t + i);
         }
       }
+    const uint32_t col = qc + 16u * (uint32_t)c + n;
+    if (!(col < q_end)) mask = 0u;
+    const uint32_t ql = HS_PROV_INDIRECT | (qoff + col);
+    const uint32_t row0 = wbase + (uint32_t)(16 * T0) + 4u * q;
+    while (__ballot(mask != 0)) {
+      uint32_t idx = 0;
+      bool pass = false;
+      if (mask) {
+        const uint32_t r = (uint32_t)__ffs((int)mask) - 1u;
+        mask &= mask - 1;
+        idx = row0 + ((r & 12u) << 2) + (r & 3u);
+        pass = idx < M;
+      }
+      const unsigned long long m = __ballot(pass);
+      if (m) {
+        const uint32_t cnt = (uint32_t)__popcll(m);
+        if (res_used + cnt > JRES) {
+          close_reservation(prov, res_base, res_used, prov_cap, lane);
+          uint32_t base = 0;
+          if (lane == 0) base = hs_reserve_survivors(prov_count, (uint32_t)JRES);
+          res_base = __builtin_amdgcn_readfirstlane(base);
+          res_used = 0;
+        }
+        if (pass) {
+          const uint32_t o = res_base + res_used + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+          if (o < prov_cap) prov[o] = make_uint2(ql, mstart + idx);
+        }
+        res_used += cnt;
+      }
     }
+  }
 }
 
 // The structure of hs_join8x_kernel (work items of 128 members owned by one wave, chunks of items from a global
@@ -428,9 +444,13 @@ __global__ __launch_bounds__(256, 2) void hs_join6x_kernel(
             }
             __builtin_amdgcn_sched_barrier(0);
           }
-          if (y_live && __ballot(group_pass6(wY, Cy)))
-            emit_survivors6(accY, 4, prev_qc, qoff, q_end, wbase, M, mstart, Cy, lane, res_base, res_used,
-                            prov_count, prov_cap, prov);
+          if (y_live) {
+            uint64_t pY[2];
+            group_pass6(wY, Cy, pY);
+            if (pY[0] | pY[1])
+              emit_survivors6(accY, 4, prev_qc, qoff, q_end, wbase, M, mstart, Cy, pY, lane, res_base, res_used,
+                              prov_count, prov_cap, prov);
+          }
           y_live = true;
           // ---- phase 2: Y <- row tiles 4..7 x B, beside the test of X
           float wX[16];
@@ -442,8 +462,10 @@ __global__ __launch_bounds__(256, 2) void hs_join6x_kernel(
             sign_step6(2 * g + 1, accX, wX);
             __builtin_amdgcn_sched_barrier(0);
           }
-          if (__ballot(group_pass6(wX, Cx)))
-            emit_survivors6(accX, 0, qc, qoff, q_end, wbase, M, mstart, Cx, lane, res_base, res_used, prov_count,
+          uint64_t pX[2];
+          group_pass6(wX, Cx, pX);
+          if (pX[0] | pX[1])
+            emit_survivors6(accX, 0, qc, qoff, q_end, wbase, M, mstart, Cx, pX, lane, res_base, res_used, prov_count,
                             prov_cap, prov);
           prev_qc = qc;
           // (the tile's registers are loaded anew below and Y is tested a phase later: its C moves out of them
@@ -461,8 +483,10 @@ __global__ __launch_bounds__(256, 2) void hs_join6x_kernel(
       float wY[16];
 #pragma unroll
       for (int g = 0; g < 16; ++g) sign_step6(g, accY, wY);
-      if (__ballot(group_pass6(wY, Cy)))
-        emit_survivors6(accY, 4, prev_qc, qoff, q_end, wbase, M, mstart, Cy, lane, res_base, res_used, prov_count,
+      uint64_t pY[2];
+      group_pass6(wY, Cy, pY);
+      if (pY[0] | pY[1])
+        emit_survivors6(accY, 4, prev_qc, qoff, q_end, wbase, M, mstart, Cy, pY, lane, res_base, res_used, prov_count,
                         prov_cap, prov);
     }
     if (!has_next) break;
