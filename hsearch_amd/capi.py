@@ -36,7 +36,8 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_index_table_append", "hs_index_remove", "hs_index_remove_dev", "hs_index_remove_ranges",
            "hs_index_table_remove", "hs_pssm_scan", "hs_pssm_scan_dev", "hs_pssm_tables",
            "hs_pssm_topk", "hs_pssm_topk_dev", "hs_pssm_topk_hits", "hs_pssm_seq_scan", "hs_pssm_seq_scan_dev",
-           "hs_pssm_seq_hits"]
+           "hs_pssm_seq_hits", "hs_pssm_hit_counts", "hs_pssm_hit_counts_dev", "hs_pssm_refine", "hs_pssm_count_hits",
+           "hs_pssm_log_odds", "hs_pssm_background"]
 
 TOPK_MAX = 64        # HS_TOPK_MAX: the widest row of query_topk / self_knn / topk_merge
 NO_ID = 0xffffffff   # the id and table of an unused entry of such a row (its distance is +inf)
@@ -69,7 +70,8 @@ class _Profile(C.Structure):
                 ("append_new_buckets", C.c_uint64), ("remove_rebuilds", C.c_uint64),
                 ("remove_dead_buckets", C.c_uint64), ("remove_retupled", C.c_uint64),
                 ("pssm_pairs", C.c_uint64), ("pssm_survivors", C.c_uint64), ("pssm_dead", C.c_uint64),
-                ("pssm_mfma_steps", C.c_uint64), ("pssm_seq_rows", C.c_uint64), ("pssm_topk_sample", C.c_uint64),
+                ("pssm_mfma_steps", C.c_uint64), ("pssm_seq_rows", C.c_uint64), ("pssm_count_sites", C.c_uint64),
+                ("pssm_count_items", C.c_uint64), ("pssm_topk_sample", C.c_uint64),
                 ("pssm_topk_raised", C.c_uint64)]
 
 
@@ -321,6 +323,26 @@ def load(hooks=False):
             lib.hs_pssm_seq_hits.restype = C.c_int
             lib.hs_pssm_seq_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                                              C.c_uint64] + rows7 + [C.c_uint64, C.POINTER(C.c_uint64)]
+        # PSSM hit counts: (h, S, t, nm, id_start, n_seq, counts, cnt, used, &n_hits); refine, count_hits, log_odds,
+        # background: include/hsearch.h
+        if hasattr(lib, "hs_pssm_hit_counts"):
+            for fn in (lib.hs_pssm_hit_counts, lib.hs_pssm_hit_counts_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+            lib.hs_pssm_refine.restype = C.c_int
+            lib.hs_pssm_refine.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                           C.c_void_p, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+            lib.hs_pssm_count_hits.restype = C.c_int
+            lib.hs_pssm_count_hits.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                               C.c_void_p]
+            lib.hs_pssm_log_odds.restype = C.c_int
+            lib.hs_pssm_log_odds.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_double,
+                                             C.c_void_p]
+            lib.hs_pssm_background.restype = C.c_int
+            lib.hs_pssm_background.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         _libs[hooks] = lib
     return _libs[hooks]
 
@@ -833,6 +855,60 @@ def pssm_seq_hits(m, id, score, nm, id_start, cap=None, out=None):
     return _pssm_seq_dict(arrs, int(n_out.value))
 
 
+def pssm_count_hits(codes, alphabet, m, id, score, nm, id_start=None):
+    """hs_pssm_count_hits (host only, no GPU): the rule of Engine.pssm_hit_counts over ANY list of hits (m, id, score)
+    in any order over codes [n][k]: dict(counts uint32 [nm][k][alphabet], used uint64 [nm]).  id_start=None: every
+    distinct (m, id) is a site; else one site per (profile, sequence), the best hit of capi.pssm_seq_hits' rows."""
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    assert codes.ndim == 2
+    n, k = codes.shape
+    m = np.ascontiguousarray(m, dtype=np.uint32).ravel()
+    id = np.ascontiguousarray(id, dtype=np.uint32).ravel()
+    score = np.ascontiguousarray(score, dtype=np.float64).ravel()
+    assert id.shape == score.shape == m.shape
+    if id_start is not None:
+        id_start = np.ascontiguousarray(id_start, dtype=np.uint64)
+        assert id_start.ndim == 1 and len(id_start) >= 1
+    rows = max(int(nm), 0)
+    counts = np.empty((rows, k, max(int(alphabet), 1)), dtype=np.uint32)
+    used = np.empty(max(rows, 1), dtype=np.uint64)
+    st = load().hs_pssm_count_hits(_vp(codes), n, k, int(alphabet), _vp(m), _vp(id), _vp(score), len(m), int(nm),
+                                   None if id_start is None else _vp(id_start),
+                                   0 if id_start is None else len(id_start) - 1, _vp(counts), _vp(used))
+    if st:
+        raise HsError(st, "hs_pssm_count_hits")
+    return dict(counts=counts, used=used[:rows])
+
+
+def pssm_log_odds_exact(counts, background, pseudo=1.0):
+    """hs_pssm_log_odds (host only): S[m][p][a] = log2((((double)c + pseudo * bg[a]) / ((double)size + pseudo)) /
+    bg[a]) for counts uint32 [nm][k][alphabet], every operation rounded to fp64 -- the function Engine.pssm_refine
+    applies, bit for bit."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    assert counts.ndim == 3
+    nm, k, A = counts.shape
+    bg = np.ascontiguousarray(background, dtype=np.float64)
+    assert bg.shape == (A,), bg.shape
+    S = np.empty((nm, k, A), dtype=np.float64)
+    st = load().hs_pssm_log_odds(_vp(counts), nm, k, A, _vp(bg), float(pseudo), _vp(S))
+    if st:
+        raise HsError(st, "hs_pssm_log_odds")
+    return S
+
+
+def pssm_background(counts_row):
+    """hs_pssm_background (host only): the residue frequencies [alphabet] of one profile's counts [k][alphabet]; a
+    residue that never occurs gets the smallest positive frequency, without renormalising."""
+    counts_row = np.ascontiguousarray(counts_row, dtype=np.uint32)
+    assert counts_row.ndim == 2
+    k, A = counts_row.shape
+    bg = np.empty(A, dtype=np.float64)
+    st = load().hs_pssm_background(_vp(counts_row), k, A, _vp(bg))
+    if st:
+        raise HsError(st, "hs_pssm_background")
+    return bg
+
+
 def pssm_log_odds(counts, background=None, pseudo=1.0):
     """Log-odds profiles from position frequency matrices (hs_cluster_profile's counts [rows][k][alphabet]):
     S[r][p][a] = log2((count + pseudo * bg[a]) / (size + pseudo) / bg[a]), size = the row's members (the counts of a
@@ -1053,7 +1129,8 @@ class Engine:
                "wide_rows": 6, "refine8": 7, "self_codes": 8, "sort_hits": 10, "sync_items": 11,
                "join_min_q": 12, "join_min_m": 13, "sort_from_bit": 14, "build_serial": 15,
                "join_xcd_run": 16, "probe_records": 17, "join_chunk": 18, "summary_chunk": 19, "summary_rows": 20,
-               "msf_edge_budget": 21, "join_f6": 22, "pssm_filter": 23, "pssm_topk_sample": 24}
+               "msf_edge_budget": 21, "join_f6": 22, "pssm_filter": 23, "pssm_topk_sample": 24,
+               "pssm_count_chunk": 25}
 
     def set_option(self, name, value):
         """hs_set_option (include/hsearch.h hs_option): path selection / batch sizing; never changes a result."""
@@ -1692,6 +1769,58 @@ class Engine:
             raise e
         self._check(st)
         return int(n.value), int(nh.value)
+
+    def _pssm_args(self, S, t, id_start):
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        nm = S.shape[0]
+        assert S.shape == (nm, self.k, self._alphabet()) and t.shape == (nm,), (S.shape, t.shape)
+        if id_start is not None:
+            id_start = np.ascontiguousarray(id_start, dtype=np.uint64)
+            assert id_start.ndim == 1 and len(id_start) >= 1
+        return S, t, nm, id_start, 0 if id_start is None else len(id_start) - 1
+
+    def pssm_hit_counts(self, S, t, id_start=None):
+        """hs_pssm_hit_counts: the position frequency matrices of pssm_scan(S, t)'s hits, reduced on the device:
+        dict(counts uint32 [nm][k][alphabet], cnt [nm] the hits and used [nm] the sites per profile, n_hits).
+        id_start=None: every hit is a site; id_start [n_seq + 1]: one site per (profile, sequence), the best hit of
+        pssm_seq_scan's rows."""
+        S, t, nm, id_start, n_seq = self._pssm_args(S, t, id_start)
+        counts = np.empty(S.shape, dtype=np.uint32)
+        cnt, used = np.empty(max(nm, 1), dtype=np.uint64), np.empty(max(nm, 1), dtype=np.uint64)
+        nh = C.c_uint64(0)
+        self._check(self._lib.hs_pssm_hit_counts(self._h, _vp(S), _vp(t), nm, None if id_start is None else _vp(id_start),
+                                                 n_seq, _vp(counts), _vp(cnt), _vp(used), C.byref(nh)))
+        return dict(counts=counts, cnt=cnt[:nm], used=used[:nm], n_hits=int(nh.value))
+
+    def pssm_hit_counts_dev(self, d_S, d_t, nm, d_counts, d_id_start=None, n_seq=0, d_cnt=None, d_used=None):
+        """hs_pssm_hit_counts_dev: device pointers (ints, e.g. tensor.data_ptr(); d_id_start, d_cnt and d_used may be
+        None).  Returns n_hits."""
+        nh = C.c_uint64(0)
+        self._check(self._lib.hs_pssm_hit_counts_dev(self._h, d_S if d_S else None, d_t if d_t else None, int(nm),
+                                                     d_id_start if d_id_start else None, int(n_seq),
+                                                     d_counts if d_counts else None, d_cnt if d_cnt else None,
+                                                     d_used if d_used else None, C.byref(nh)))
+        return int(nh.value)
+
+    def pssm_refine(self, S, t, n_iter, id_start=None, background=None, pseudo=1.0):
+        """hs_pssm_refine: scan, rebuild the profiles from the counts of their own hits (hs_pssm_log_odds), scan again
+        -- until two scans count the same or n_iter scans have run.  dict(S [nm][k][alphabet] the last profiles
+        computed, counts, used: of the last scan, iters, converged).  background=None: the residue composition of
+        the index (one extra scan).  A profile without hits keeps its matrix."""
+        S, t, nm, id_start, n_seq = self._pssm_args(S, t, id_start)
+        bg = None
+        if background is not None:
+            bg = np.ascontiguousarray(background, dtype=np.float64)
+            assert bg.shape == (self._alphabet(),), bg.shape
+        S_out = np.empty(S.shape, dtype=np.float64)
+        counts = np.empty(S.shape, dtype=np.uint32)
+        used = np.empty(max(nm, 1), dtype=np.uint64)
+        iters, conv = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.hs_pssm_refine(self._h, _vp(S), _vp(t), nm, None if id_start is None else _vp(id_start),
+                                             n_seq, None if bg is None else _vp(bg), float(pseudo), int(n_iter),
+                                             _vp(S_out), _vp(counts), _vp(used), C.byref(iters), C.byref(conv)))
+        return dict(S=S_out, counts=counts, used=used[:nm], iters=int(iters.value), converged=bool(conv.value))
 
     def bruteforce_radii(self, centers, radii, cap=None):
         """hs_bruteforce_radii: brute force with centre q searched at radii[q]."""

@@ -26,6 +26,7 @@
 #include "hs_table_remove.h"
 #include "hs_pssm_tables.h"
 #include "hs_pssm_seq.h"
+#include "hs_pssm_counts.h"
 #include "hs_pssm_topk.h"
 
 namespace {
@@ -107,6 +108,7 @@ struct Knobs {
   int sort_from_bit = 16;          // HS_OPT_SORT_FROM_BIT: lowest fingerprint bit the build's sort looks at
   uint32_t query_batch = 0;        // HS_OPT_QUERY_BATCH: queries per batch (0: by L and the free HBM)
   uint32_t pssm_topk_sample = 262144;  // HS_OPT_PSSM_TOPK_SAMPLE: k-mers the sample pass of hs_pssm_topk scores per profile
+  uint32_t pssm_count_chunk = 0;   // HS_OPT_PSSM_COUNT_CHUNK: sites per work item of hs_pssm_counts.hip (0: by the batch)
   uint32_t summary_chunk = 0;      // HS_OPT_SUMMARY_CHUNK: member slots per work item of hs_summary.hip (0: 512)
   uint32_t summary_rows = 0;       // HS_OPT_SUMMARY_ROWS: rows per batch of hs_cluster_profile (0: by the scratch budget)
   int64_t msf_edge_budget = -1;    // HS_OPT_MSF_EDGE_BUDGET: bytes of HBM hs_msf may keep pairs in (0 never, -1 a share of the free)
@@ -279,6 +281,10 @@ struct hs_handle {
   // hs_pssm_topk (hs_pssm_topk.hip; the selection's scratch is hs_knn.hip's): a batch's thresholds when the caller
   // wants none; the sample pass's lists when a profile's sample is split over several workgroups
   DevBuf pt_tused, pt_parts;
+  // hs_pssm_hit_counts (hs_pssm_counts.hip): a batch's sites as (m, id) words and their copies sorted on m, the
+  // profiles' run starts, chunk counts and their scan, the rows of the one-site-per-protein mode; a host-pointer
+  // call's counts, cnt and used on their way out
+  DevBuf pc_m, pc_id, pc_m2, pc_id2, pc_start, pc_nitem, pc_off, pc_rows, pc_out;
   // hs_seq_match (hs_seqmatch.hip: the scratch listed at its head): a batch's keys and hit indices, their sorted
   // copies, the run heads and their scan, the waves' cut runs; the call's rows so far (sq_rows of them in a list of
   // sq_acc.cap / 40) and their final reduction; the argument check's words; a host-pointer call's arrays in and out
@@ -554,7 +560,7 @@ const struct { const char* name; int option; } kOptionNames[] = {
     {"sort_hits", HS_OPT_SORT_HITS}, {"sync_items", HS_OPT_SYNC_ITEMS}, {"join_min_q", HS_OPT_JOIN_MIN_Q},
     {"join_min_m", HS_OPT_JOIN_MIN_M}, {"sort_from_bit", HS_OPT_SORT_FROM_BIT}, {"build_serial", HS_OPT_BUILD_SERIAL},
     {"join_xcd_run", HS_OPT_JOIN_XCD_RUN}, {"probe_records", HS_OPT_PROBE_RECORDS},
-    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"join_f6", HS_OPT_JOIN_F6}, {"pssm_filter", HS_OPT_PSSM_FILTER}, {"pssm_topk_sample", HS_OPT_PSSM_TOPK_SAMPLE}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS},
+    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"join_f6", HS_OPT_JOIN_F6}, {"pssm_filter", HS_OPT_PSSM_FILTER}, {"pssm_topk_sample", HS_OPT_PSSM_TOPK_SAMPLE}, {"pssm_count_chunk", HS_OPT_PSSM_COUNT_CHUNK}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS},
     {"msf_edge_budget", HS_OPT_MSF_EDGE_BUDGET}};
 
 void read_knobs(hs_handle* h) {
@@ -847,6 +853,10 @@ hs_status hs_set_option(hs_handle* h, int option, int64_t value) {
       if (value < 1 || value > 0xffffffffll) break;
       kn.pssm_topk_sample = (uint32_t)value;
       return HS_OK;
+    case HS_OPT_PSSM_COUNT_CHUNK:
+      if (value < 0 || value > (1ll << 20)) break;
+      kn.pssm_count_chunk = (uint32_t)value;
+      return HS_OK;
     case HS_OPT_SELF_CODES: return flag(&kn.no_self_codes, true);
     case HS_OPT_SORT_HITS: return flag(&kn.sort_hits, false);
     case HS_OPT_SYNC_ITEMS: return flag(&kn.sync_items, false);
@@ -923,6 +933,7 @@ void hs_destroy(hs_handle* h) {
                     &h->db_deg, &h->db_anchor, &h->db_cnt, &h->msf_comp, &h->msf_best_d, &h->msf_best_pair,
                     &h->msf_out_pair, &h->msf_out_d, &h->msf_s_pair, &h->msf_s_d, &h->msf_cnt, &h->msf_kept, &h->dt_core, &h->dt_thr,
                     &h->dt_next, &h->dt_cnt, &h->knn_cnt, &h->knn_off, &h->knn_cur, &h->knn_total, &h->knn_io_count, &h->pt_tused, &h->pt_parts,
+                    &h->pc_m, &h->pc_id, &h->pc_m2, &h->pc_id2, &h->pc_start, &h->pc_nitem, &h->pc_off, &h->pc_rows, &h->pc_out,
                     &h->sq_key, &h->sq_idx, &h->sq_skey, &h->sq_sidx, &h->sq_head, &h->sq_excl, &h->sq_part, &h->sq_acc,
                     &h->sq_fin, &h->sq_chk, &h->sq_in, &h->sq_out,
                     &h->sm_size, &h->sm_tmp, &h->sm_row_of, &h->sm_off_of,
@@ -5971,6 +5982,255 @@ hs_status hs_pssm_seq_scan(hs_handle* h, const double* S, const double* t, uint6
   }
   HS_HIP(h, hipStreamSynchronize(h->stream));
   return st;
+}
+
+// ---- hs_pssm_hit_counts / hs_pssm_refine: the position frequency matrices of a scan's hits (hs_pssm_counts.hip) ----
+// Sites per work item for a batch of ns sites: what HS_OPT_PSSM_COUNT_CHUNK says, else ns / 4096 within 256 .. 2048.
+// An item is one wave's serial walk over its sites (two dependent loads per step), so few long items leave a small
+// batch waiting on a handful of waves; 4096 items are 16 waves on every CU.  At 2048 sites the flush of at most 2400
+// bins is a twentieth of the item's 5 x 10^4 increments at k = 25.
+static uint32_t pssm_count_chunk(const hs_handle* h, uint32_t ns) {
+  if (h->knobs.pssm_count_chunk) return h->knobs.pssm_count_chunk;
+  return std::min(2048u, std::max(256u, (ns + 4095u) / 4096u));
+}
+
+// The call with every array on the device; the callers have checked the arguments and the values.  d_id_start null:
+// every hit is a site; else the sites are the best ids of the batch's (profile, sequence) rows.  Every hit of a
+// profile lies in one batch, so a batch finishes its profiles' counts.
+static hs_status pssm_counts_core(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm,
+                                  const uint64_t* d_id_start, uint64_t n_seq, uint32_t* d_counts, uint64_t* d_cnt_out,
+                                  uint64_t* d_used_out, uint64_t* n_hits) {
+  memset(&h->prof, 0, sizeof(h->prof));
+  HS_HIP(h, h->counters.reserve(256));
+  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
+  const int k = (int)h->p.k;
+  const size_t cells = (size_t)h->p.k * h->alphabet;
+  if (nm) HS_HIP(h, hipMemsetAsync(d_counts, 0, nm * cells * 4, h->stream));
+  if (d_cnt_out && nm) HS_HIP(h, hipMemsetAsync(d_cnt_out, 0, nm * 8, h->stream));
+  if (d_used_out && nm) HS_HIP(h, hipMemsetAsync(d_used_out, 0, nm * 8, h->stream));
+  uint64_t sites = 0, items = 0;
+  HS_CHECK(pssm_batches(h, d_S, d_t, nm, n_hits, [&](uint32_t m0, uint32_t mb, uint32_t nh) -> hs_status {
+    const uint32_t *site_m = nullptr, *site_id = nullptr;
+    uint32_t ns = 0;
+    const size_t scan_items = hs_scan_u32_temp((size_t)mb + 1);
+    if (!d_id_start) {  // the hits, ordered on their profile bits alone
+      HS_HIP(h, h->pc_m.reserve((size_t)nh * 4));
+      HS_HIP(h, h->pc_id.reserve((size_t)nh * 4));
+      HS_HIP(h, h->pc_m2.reserve((size_t)nh * 4));
+      HS_HIP(h, h->pc_id2.reserve((size_t)nh * 4));
+      HS_HIP(h, h->temp.reserve(std::max(hs_sort_pairs_u32_u32_temp(nh), scan_items) + 256));
+      HS_HIP(h, hs_launch_pssm_counts_split(h->hit_key.as<uint64_t>(), nh, h->pc_m.as<uint32_t>(),
+                                            h->pc_id.as<uint32_t>(), h->stream));
+      HS_HIP(h, hs_sort_pairs_u32_u32(h->temp.p, h->temp.cap, h->pc_m.as<uint32_t>(), h->pc_m2.as<uint32_t>(),
+                                      h->pc_id.as<uint32_t>(), h->pc_id2.as<uint32_t>(), nh, bit_width_u32(m0 + mb),
+                                      h->stream));
+      site_m = h->pc_m2.as<uint32_t>();
+      site_id = h->pc_id2.as<uint32_t>();
+      ns = nh;
+    } else {  // the rows of hs_pssm_seq_scan, kept on the device: their m and best_id are the sites
+      HS_CHECK(pssm_sort_hits(h, m0, mb, nh, std::max(hs_scan_u32_temp((size_t)nh + 1), scan_items)));
+      const uint64_t *key = h->hit_key2.as<uint64_t>(), *val = h->hit_val2.as<uint64_t>();
+      HS_HIP(h, h->sq_sidx.reserve((size_t)nh * 4));
+      HS_HIP(h, h->sq_head.reserve(((size_t)nh + 1) * 4));
+      HS_HIP(h, h->sq_excl.reserve(((size_t)nh + 1) * 4));
+      HS_HIP(h, hs_launch_pssm_seq_head(key, nh, d_id_start, n_seq, h->sq_sidx.as<uint32_t>(),
+                                        h->sq_head.as<uint32_t>(), h->stream));
+      HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, h->sq_head.as<uint32_t>(), h->sq_excl.as<uint32_t>(),
+                                      (size_t)nh + 1, h->stream));
+      uint32_t rows = 0;
+      HS_HIP(h, hipMemcpyAsync(&rows, h->sq_excl.as<uint32_t>() + nh, 4, hipMemcpyDeviceToHost, h->stream));
+      HS_HIP(h, hipStreamSynchronize(h->stream));
+      if (!rows || rows > nh) return fail(h, HS_ERR_HIP, "hs_pssm_hit_counts: the row count of a batch is out of range");
+      HS_HIP(h, h->sq_skey.reserve(((size_t)rows + 1) * 4));
+      HS_HIP(h, h->sq_key.reserve((size_t)rows * 8));
+      HS_HIP(h, h->sq_idx.reserve((size_t)rows * 4));
+      HS_HIP(h, h->sq_part.reserve(hs_pssm_seq_part_bytes(nh)));
+      HS_HIP(h, h->pc_rows.reserve((size_t)rows * 32));
+      char* const o = h->pc_rows.as<char>();
+      uint32_t* const w = reinterpret_cast<uint32_t*>(o + (size_t)rows * 8);
+      const size_t r = rows;
+      HS_HIP(h, hs_launch_pssm_seq_rows(key, val, h->sq_sidx.as<uint32_t>(), h->sq_head.as<uint32_t>(),
+                                        h->sq_excl.as<uint32_t>(), nh, rows, d_id_start, true,
+                                        h->sq_skey.as<uint32_t>(), h->sq_key.as<uint64_t>(), h->sq_idx.as<uint32_t>(),
+                                        h->sq_part.p, w, w + r, w + 2 * r, reinterpret_cast<double*>(o), w + 3 * r,
+                                        w + 4 * r, w + 5 * r, d_cnt_out, nullptr, h->stream));
+      site_m = w;
+      site_id = w + 3 * r;
+      ns = rows;
+    }
+    const uint32_t ch = pssm_count_chunk(h, ns);
+    HS_HIP(h, h->pc_start.reserve(((size_t)mb + 1) * 4));
+    HS_HIP(h, h->pc_nitem.reserve(((size_t)mb + 1) * 4));
+    HS_HIP(h, h->pc_off.reserve(((size_t)mb + 1) * 4));
+    HS_HIP(h, hs_launch_pssm_counts_items(site_m, ns, m0, mb, ch, h->pc_start.as<uint32_t>(),
+                                          h->pc_nitem.as<uint32_t>(), h->stream));
+    HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, h->pc_nitem.as<uint32_t>(), h->pc_off.as<uint32_t>(),
+                                    (size_t)mb + 1, h->stream));
+    uint32_t n_items = 0;
+    HS_HIP(h, hipMemcpyAsync(&n_items, h->pc_off.as<uint32_t>() + mb, 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    if (!n_items || n_items > (uint64_t)ns / ch + mb)
+      return fail(h, HS_ERR_HIP, "hs_pssm_hit_counts: the item count of a batch is out of range");
+    HS_HIP(h, hs_launch_pssm_counts(h->codes.as<uint8_t>(), k, h->alphabet, site_id, h->pc_start.as<uint32_t>(),
+                                    h->pc_off.as<uint32_t>(), m0, mb, ch, n_items, d_counts, h->stream));
+    HS_HIP(h, hs_launch_pssm_counts_used(d_counts + (size_t)m0 * cells, mb, k, h->alphabet,
+                                         d_used_out ? d_used_out + m0 : nullptr,
+                                         d_cnt_out && !d_id_start ? d_cnt_out + m0 : nullptr, h->stream));
+    sites += ns;
+    items += n_items;
+    return HS_OK;
+  }));
+  h->prof.pssm_count_sites = sites;
+  h->prof.pssm_count_items = items;
+  return HS_OK;
+}
+
+// what every form refuses from the arguments alone (hs_pssm_scan's refusals first); id_start null: every site counts
+static hs_status pssm_counts_args(hs_handle* h, const void* S, const void* t, uint64_t nm, const void* id_start,
+                                  uint64_t n_seq, const void* counts) {
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
+  if (nm >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nm must be < 2^27 per call");
+  if (nm && (!S || !t)) return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: S or t is null");
+  if (nm && !counts) return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: counts is null");
+  if (id_start && n_seq > (1ull << 32)) return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: more than 2^32 sequences");
+  if (id_start && !n_seq && h->n)
+    return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: no sequence owns the index's k-mers");
+  return HS_OK;
+}
+
+hs_status hs_pssm_hit_counts_dev(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm,
+                                 const uint64_t* d_id_start, uint64_t n_seq, uint32_t* d_counts, uint64_t* d_cnt,
+                                 uint64_t* d_used, uint64_t* n_hits) {
+  if (!h || !n_hits) return HS_ERR_INVALID;
+  *n_hits = 0;
+  HS_CHECK(pssm_counts_args(h, d_S, d_t, nm, d_id_start, n_seq, d_counts));
+  HS_CHECK(ensure_device(h));
+  if (nm || d_id_start) {  // the values, on the device: the reductions of hs_pssm_seq_scan_dev, one read-back
+    uint64_t chk[5] = {0, 0, 0, 0, 0};
+    HS_HIP(h, h->sq_chk.reserve(64));
+    HS_HIP(h, hipMemsetAsync(h->sq_chk.p, 0, 64, h->stream));
+    if (nm)
+      HS_HIP(h, hs_launch_pssm_check(d_S, nm * h->p.k * h->alphabet, d_t, nm, h->sq_chk.as<uint32_t>() + 8, h->stream));
+    if (d_id_start)
+      HS_HIP(h, hs_launch_sm_check(nullptr, nullptr, 0, 0, d_id_start, n_seq, h->n, h->sq_chk.as<uint64_t>(), h->stream));
+    HS_HIP(h, hipMemcpyAsync(chk, h->sq_chk.p, 40, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    if (chk[4] & 1u) return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
+    if (chk[4] & 2u) return fail(h, HS_ERR_INVALID, "a threshold is NaN or infinite");
+    if (chk[0] & 7) return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: id_start must ascend from 0 to the index's k-mers");
+  }
+  return pssm_counts_core(h, d_S, d_t, nm, d_id_start, n_seq, d_counts, d_cnt, d_used, n_hits);
+}
+
+// the values a host-pointer call refuses
+static hs_status pssm_counts_values(hs_handle* h, const double* S, const double* t, uint64_t nm, const uint64_t* id_start,
+                                    uint64_t n_seq) {
+  const size_t ka = (size_t)h->p.k * h->alphabet;
+  for (uint64_t i = 0; i < nm * ka; ++i)
+    if (hs_pssm_bad_value(S[i], HS_PSSM_MAX_ABS))
+      return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
+  for (uint64_t m = 0; m < nm; ++m)
+    if (hs_pssm_bad_value(t[m], 1.7976931348623157e308)) return fail(h, HS_ERR_INVALID, "a threshold is NaN or infinite");
+  if (id_start && (!hs_pssm_seq_id_start_ok(id_start, n_seq) || id_start[n_seq] != h->n))
+    return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: id_start must ascend from 0 to the index's k-mers");
+  return HS_OK;
+}
+
+// A checked host-pointer call: S and t up, counts (and cnt, used) down.  ids_resident: id_start already lies in sq_in
+// (the later iterations of hs_pssm_refine).
+static hs_status pssm_counts_host(hs_handle* h, const double* S, const double* t, uint64_t nm, const uint64_t* id_start,
+                                  uint64_t n_seq, bool ids_resident, uint32_t* counts, uint64_t* cnt, uint64_t* used,
+                                  uint64_t* n_hits) {
+  HS_CHECK(ensure_device(h));
+  const size_t ka = (size_t)h->p.k * h->alphabet;
+  const size_t sb = ((size_t)n_seq + 1) * 8, cb = std::max<size_t>(16, nm * 8), ob = std::max<size_t>(16, nm * ka * 4);
+  HS_HIP(h, h->io_centers.reserve(std::max<size_t>(16, nm * ka * 8)));
+  HS_HIP(h, h->io_radii.reserve(cb));
+  if (id_start) HS_HIP(h, h->sq_in.reserve(sb));
+  HS_HIP(h, h->pc_out.reserve(2 * cb + ob));
+  if (nm) {
+    HS_HIP(h, hipMemcpyAsync(h->io_centers.p, S, nm * ka * 8, hipMemcpyHostToDevice, h->stream));
+    HS_HIP(h, hipMemcpyAsync(h->io_radii.p, t, nm * 8, hipMemcpyHostToDevice, h->stream));
+  }
+  if (id_start && !ids_resident)
+    HS_HIP(h, hipMemcpyAsync(h->sq_in.p, id_start, sb, hipMemcpyHostToDevice, h->stream));
+  char* const o = h->pc_out.as<char>();
+  uint64_t* const d_cnt = cnt ? reinterpret_cast<uint64_t*>(o) : nullptr;
+  uint64_t* const d_used = used ? reinterpret_cast<uint64_t*>(o + cb) : nullptr;
+  uint32_t* const d_counts = reinterpret_cast<uint32_t*>(o + 2 * cb);
+  HS_CHECK(pssm_counts_core(h, h->io_centers.as<double>(), h->io_radii.as<double>(), nm,
+                            id_start ? h->sq_in.as<uint64_t>() : nullptr, n_seq, d_counts, d_cnt, d_used, n_hits));
+  if (nm) {
+    HS_HIP(h, hipMemcpyAsync(counts, d_counts, nm * ka * 4, hipMemcpyDeviceToHost, h->stream));
+    if (cnt) HS_HIP(h, hipMemcpyAsync(cnt, d_cnt, nm * 8, hipMemcpyDeviceToHost, h->stream));
+    if (used) HS_HIP(h, hipMemcpyAsync(used, d_used, nm * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return HS_OK;
+}
+
+hs_status hs_pssm_hit_counts(hs_handle* h, const double* S, const double* t, uint64_t nm, const uint64_t* id_start,
+                             uint64_t n_seq, uint32_t* counts, uint64_t* cnt, uint64_t* used, uint64_t* n_hits) {
+  if (!h || !n_hits) return HS_ERR_INVALID;
+  *n_hits = 0;
+  HS_CHECK(pssm_counts_args(h, S, t, nm, id_start, n_seq, counts));
+  HS_CHECK(pssm_counts_values(h, S, t, nm, id_start, n_seq));
+  return pssm_counts_host(h, S, t, nm, id_start, n_seq, false, counts, cnt, used, n_hits);
+}
+
+hs_status hs_pssm_refine(hs_handle* h, const double* S0, const double* t, uint64_t nm, const uint64_t* id_start,
+                         uint64_t n_seq, const double* bg, double pseudo, uint32_t n_iter, double* S_out,
+                         uint32_t* counts, uint64_t* used, uint32_t* iters, uint32_t* converged) {
+  if (!h || !iters || !converged) return HS_ERR_INVALID;
+  *iters = 0;
+  *converged = 0;
+  HS_CHECK(pssm_counts_args(h, S0, t, nm, id_start, n_seq, S_out));
+  if (n_iter < 1 || n_iter > 100) return fail(h, HS_ERR_INVALID, "hs_pssm_refine: n_iter must be 1 .. 100");
+  const uint32_t k = h->p.k, A = (uint32_t)h->alphabet;
+  double bgv[32];
+  if (!(pseudo > 0.0 && pseudo <= 1.7976931348623157e308) || (bg && !hs_pssm_bg_ok(bg, A, pseudo)))
+    return fail(h, HS_ERR_INVALID, "hs_pssm_refine: the background must be positive and finite, pseudo finite and > 0");
+  HS_CHECK(pssm_counts_values(h, S0, t, nm, id_start, n_seq));
+  const size_t cells = (size_t)k * A;
+  try {
+    uint64_t nh = 0;
+    if (bg) {
+      for (uint32_t a = 0; a < A; ++a) bgv[a] = bg[a];
+    } else {  // the residue composition of the index: one profile that hits everything, every site counted
+      const std::vector<double> zero(cells, 0.0);
+      std::vector<uint32_t> all(cells);
+      const double t0 = 0.0;
+      HS_CHECK(pssm_counts_host(h, zero.data(), &t0, 1, nullptr, 0, false, all.data(), nullptr, nullptr, &nh));
+      if (hs_pssm_background_host(all.data(), k, A, bgv))
+        return fail(h, HS_ERR_INVALID, "hs_pssm_refine: an empty index has no background");
+    }
+    std::vector<double> S(S0, S0 + nm * cells);
+    std::vector<uint32_t> C(nm * cells), prev;
+    std::vector<uint64_t> U(nm);
+    uint32_t done = 0, conv = 0;
+    for (uint32_t i = 0; i < n_iter; ++i) {
+      HS_CHECK(pssm_counts_host(h, S.data(), t, nm, id_start, n_seq, i > 0, C.data(), nullptr, U.data(), &nh));
+      ++done;
+      if (i > 0 && C == prev) {
+        conv = 1;
+        break;
+      }
+      for (uint64_t m = 0; m < nm; ++m)
+        if (U[m] && hs_pssm_log_odds_host(C.data() + m * cells, 1, k, A, bgv, pseudo, S.data() + m * cells))
+          return fail(h, HS_ERR_INVALID, "hs_pssm_refine: a log-odds entry is not finite");
+      prev = C;
+    }
+    for (size_t i = 0; i < S.size(); ++i) S_out[i] = S[i];
+    if (counts)
+      for (size_t i = 0; i < C.size(); ++i) counts[i] = C[i];
+    if (used)
+      for (uint64_t m = 0; m < nm; ++m) used[m] = U[m];
+    *iters = done;
+    *converged = conv;
+  } catch (const std::bad_alloc&) {
+    return fail(h, HS_ERR_NOMEM, "hs_pssm_refine: out of host memory");
+  }
+  return HS_OK;
 }
 
 static hs_status pssm_args(hs_handle* h, const void* S, const void* t, uint64_t nm, const void* hit_m, const void* hit_id,

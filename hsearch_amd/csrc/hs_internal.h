@@ -899,4 +899,20 @@ hipError_t hs_launch_pssm_seq_rows(const uint64_t* d_key, const uint64_t* d_val,
                                    uint32_t* d_out_lo, uint32_t* d_out_hi, uint64_t* d_cnt, uint64_t* d_seq_cnt,
                                    hipStream_t s);
 
+// ---- hs_pssm_hit_counts (hs_pssm_counts.hip: the passes over a batch's sites are written at its head) --------------
+// the batch's n hits m << 32 | id -> d_m [n], d_id [n]
+hipError_t hs_launch_pssm_counts_split(const uint64_t* d_key, uint32_t n, uint32_t* d_m, uint32_t* d_id, hipStream_t s);
+// d_site_m [ns] ascending, every m in [m0, m0 + mb) -> d_start [mb + 1] (the profiles' runs) and d_n_item [mb + 1]
+// (their chunks of ch sites; the last is 0)
+hipError_t hs_launch_pssm_counts_items(const uint32_t* d_site_m, uint32_t ns, uint32_t m0, uint32_t mb, uint32_t ch,
+                                       uint32_t* d_start, uint32_t* d_n_item, hipStream_t s);
+// d_off = the exclusive scan of d_n_item over mb + 1 elements, n_items its total; d_counts [nm][k][alphabet] is the
+// call's, zeroed before the first batch
+hipError_t hs_launch_pssm_counts(const uint8_t* d_codes, int k, int alphabet, const uint32_t* d_site_id,
+                                 const uint32_t* d_start, const uint32_t* d_off, uint32_t m0, uint32_t mb, uint32_t ch,
+                                 uint32_t n_items, uint32_t* d_counts, hipStream_t s);
+// d_used [nm], d_cnt [nm] (either may be null) = the sites of every profile, from the finished counts
+hipError_t hs_launch_pssm_counts_used(const uint32_t* d_counts, uint32_t nm, int k, int alphabet, uint64_t* d_used,
+                                      uint64_t* d_cnt, hipStream_t s);
+
 #endif

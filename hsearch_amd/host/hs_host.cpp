@@ -766,19 +766,11 @@ bool ReadPssmFile(const std::string& path, uint32_t kmer_length, std::vector<std
   return true;
 }
 
-// ScanProfiles (topn == 0: every hit at or above t, hs_pssm_scan) and ScanProfilesTopN (topn >= 1: per profile the topn
-// best windows at or above t, hs_pssm_topk): the same index, the same lines.  ScanProfilesPerSequence (n_rows_out
-// given): the same index, one line per (profile, protein) (hs_pssm_seq_scan).
-static int ScanProfilesAny(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
-                           const std::vector<double>& S, const std::vector<double>& t, uint32_t topn,
-                           const std::string& output_file, int device, std::string* err, uint64_t* n_windows,
-                           uint64_t* n_hits_out, uint64_t* n_rows_out = nullptr) {
-  const uint32_t k = kmer_length;
-  const size_t nm = t.size();
-  if (k < 2 || names.size() != nm || S.size() != nm * (size_t)k * HS_ALPHABET) {
-    if (err) *err = k < 2 ? "kmer length 1 is not supported on a FASTA database" : "the profiles do not match the kmer length";
-    return HS_ERR_INVALID;
-  }
+// The windows index every profile call runs on: the database's windows (never across a letter outside the alphabet)
+// under the smallest hash family there is -- no hash table takes part in a scan.  win_pos: where every window starts
+// in db.residues; id_start [proteins + 1]: the window ids every protein owns.  The caller destroys *h.
+static int OpenWindowsIndex(const ProteinDB& db, uint32_t k, int device, hs_handle** h_out, uint64_t* n_win,
+                            std::vector<uint32_t>* win_pos, std::vector<uint64_t>* id_start, std::string* err) {
   // sequences cut at unknown letters, as in SearchProteinsSharded: windows never cross a cut
   std::vector<uint8_t> res(db.residues);
   std::vector<uint64_t> seg;
@@ -796,7 +788,6 @@ static int ScanProfilesAny(const ProteinDB& db, uint32_t kmer_length, const std:
   }
   first_seg[n_seq] = seg.size();
   seg.push_back(db.residues.size());
-  // no hash table takes part in a scan: the smallest family there is
   const Planes planes = DrawPlanes(8 * k, 1, 1, 1.0, 0);
   hs_params prm;
   memset(&prm, 0, sizeof(prm));
@@ -808,29 +799,52 @@ static int ScanProfilesAny(const ProteinDB& db, uint32_t kmer_length, const std:
   prm.device = device;
   hs_handle* h = nullptr;
   hs_status st = hs_create(&prm, planes.a.data(), planes.b.data(), &HS_AA_COORDS[0][0], &h);
+  *h_out = h;
   if (st != HS_OK) {
     if (err) *err = std::string("hs_create: ") + (h ? hs_last_error(h) : "no usable gfx950 device");
-    hs_destroy(h);
     return st;
   }
-  HandleCloser closer = {h};
-  uint64_t n_win = 0;
-  std::vector<uint32_t> win_pos(res.size() + 1);
-  st = hs_index_build_windows(h, res.data(), res.size(), seg.data(), seg.size() - 1, &n_win, win_pos.data());
+  win_pos->assign(res.size() + 1, 0);
+  st = hs_index_build_windows(h, res.data(), res.size(), seg.data(), seg.size() - 1, n_win, win_pos->data());
   if (st != HS_OK) {
     if (err) *err = std::string("index build: ") + hs_last_error(h);
     return st;
   }
+  // a protein's segments follow one another, so its windows are one id range: the range of its first segment on
+  std::vector<uint64_t> seg_ids(seg.size());
+  st = hs_window_id_start(seg.data(), seg.size() - 1, k, seg_ids.data());
+  if (st != HS_OK) {
+    if (err) *err = "hs_window_id_start refused the segments";
+    return st;
+  }
+  id_start->resize(n_seq + 1);
+  for (size_t s = 0; s <= n_seq; ++s) (*id_start)[s] = seg_ids[first_seg[s]];
+  return HS_OK;
+}
+
+// ScanProfiles (topn == 0: every hit at or above t, hs_pssm_scan) and ScanProfilesTopN (topn >= 1: per profile the topn
+// best windows at or above t, hs_pssm_topk): the same index, the same lines.  ScanProfilesPerSequence (n_rows_out
+// given): the same index, one line per (profile, protein) (hs_pssm_seq_scan).
+static int ScanProfilesAny(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
+                           const std::vector<double>& S, const std::vector<double>& t, uint32_t topn,
+                           const std::string& output_file, int device, std::string* err, uint64_t* n_windows,
+                           uint64_t* n_hits_out, uint64_t* n_rows_out = nullptr) {
+  const uint32_t k = kmer_length;
+  const size_t nm = t.size();
+  if (k < 2 || names.size() != nm || S.size() != nm * (size_t)k * HS_ALPHABET) {
+    if (err) *err = k < 2 ? "kmer length 1 is not supported on a FASTA database" : "the profiles do not match the kmer length";
+    return HS_ERR_INVALID;
+  }
+  const size_t n_seq = db.start.empty() ? 0 : db.start.size() - 1;
+  hs_handle* h = nullptr;
+  uint64_t n_win = 0;
+  std::vector<uint32_t> win_pos;
+  std::vector<uint64_t> id_start;
+  hs_status st = (hs_status)OpenWindowsIndex(db, k, device, &h, &n_win, &win_pos, &id_start, err);
+  HandleCloser closer = {h};
+  if (st != HS_OK) return st;
   if (n_windows) *n_windows = n_win;
   if (n_rows_out) {
-    // a protein's segments follow one another, so its windows are one id range: the range of its first segment on
-    std::vector<uint64_t> seg_ids(seg.size()), id_start(n_seq + 1);
-    st = hs_window_id_start(seg.data(), seg.size() - 1, k, seg_ids.data());
-    if (st != HS_OK) {
-      if (err) *err = "hs_window_id_start refused the segments";
-      return st;
-    }
-    for (size_t s = 0; s <= n_seq; ++s) id_start[s] = seg_ids[first_seg[s]];
     std::vector<uint32_t> rm, rs, rc, rid, rlo, rhi;
     std::vector<double> rsc;
     uint64_t n_rows = 0, n_hits = 0;
@@ -938,6 +952,62 @@ int ScanProfilesPerSequence(const ProteinDB& db, uint32_t kmer_length, const std
   const int st = ScanProfilesAny(db, kmer_length, names, S, t, 0, output_file, device, err, n_windows, n_hits, &rows);
   if (n_rows) *n_rows = rows;
   return st;
+}
+
+bool WritePssmFile(const std::string& path, uint32_t kmer_length, const std::vector<std::string>& names,
+                   const std::vector<double>& S, const std::vector<double>& t, std::string* err) {
+  const size_t nm = t.size(), row = HS_ALPHABET;
+  if (names.size() != nm || S.size() != nm * (size_t)kmer_length * row) {
+    if (err) *err = "the profiles do not match the kmer length";
+    return false;
+  }
+  std::ofstream fout(path.c_str());
+  char num[64];
+  for (size_t m = 0; m < nm && fout; ++m) {
+    snprintf(num, sizeof(num), "%.17g", t[m]);
+    fout << ">" << names[m] << " " << num << "\n";
+    for (size_t p = 0; p < kmer_length; ++p)
+      for (size_t a = 0; a < row; ++a) {
+        snprintf(num, sizeof(num), "%.17g", S[(m * kmer_length + p) * row + a]);
+        fout << num << (a + 1 < row ? " " : "\n");
+      }
+  }
+  fout.close();
+  if (!fout) {
+    if (err) *err = "cannot write " + path;
+    return false;
+  }
+  return true;
+}
+
+int RefineProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<double>& S, const std::vector<double>& t,
+                   uint32_t n_iter, bool one_per_protein, double pseudo, int device, std::vector<double>* S_out,
+                   uint32_t* iters, bool* converged, std::string* err) {
+  const uint32_t k = kmer_length;
+  const size_t nm = t.size();
+  if (k < 2 || S.size() != nm * (size_t)k * HS_ALPHABET) {
+    if (err) *err = k < 2 ? "kmer length 1 is not supported on a FASTA database" : "the profiles do not match the kmer length";
+    return HS_ERR_INVALID;
+  }
+  const size_t n_seq = db.start.empty() ? 0 : db.start.size() - 1;
+  hs_handle* h = nullptr;
+  uint64_t n_win = 0;
+  std::vector<uint32_t> win_pos;
+  std::vector<uint64_t> id_start;
+  hs_status st = (hs_status)OpenWindowsIndex(db, k, device, &h, &n_win, &win_pos, &id_start, err);
+  HandleCloser closer = {h};
+  if (st != HS_OK) return st;
+  S_out->assign(S.size(), 0.0);
+  uint32_t done = 0, conv = 0;
+  st = hs_pssm_refine(h, S.data(), t.data(), nm, one_per_protein ? id_start.data() : nullptr, n_seq, nullptr, pseudo,
+                      n_iter, S_out->data(), nullptr, nullptr, &done, &conv);
+  if (st != HS_OK) {
+    if (err) *err = std::string("hs_pssm_refine: ") + hs_last_error(h);
+    return st;
+  }
+  if (iters) *iters = done;
+  if (converged) *converged = conv != 0;
+  return HS_OK;
 }
 
 // "<first token of the protein's name>#<its number>": how the search's k-mer names begin

@@ -207,6 +207,15 @@ int ScanProfilesPerSequence(const ProteinDB& db, uint32_t kmer_length, const std
                             const std::vector<double>& S, const std::vector<double>& t, const std::string& output_file,
                             int device, std::string* err, uint64_t* n_windows = nullptr, uint64_t* n_hits = nullptr,
                             uint64_t* n_rows = nullptr);
+// The file ReadPssmFile reads, every number printed as %.17g: it reads back bit for bit.
+bool WritePssmFile(const std::string& path, uint32_t kmer_length, const std::vector<std::string>& names,
+                   const std::vector<double>& S, const std::vector<double>& t, std::string* err);
+// `--pssm FILE --pssm-refine N`: the profiles rebuilt from their own hits over the database's windows (hs_pssm_refine:
+// scan, counts, log-odds against the database's residue composition, at most n_iter scans at the fixed thresholds t).
+// one_per_protein: only the best window of every protein counts.  S_out: the refined profiles.  One GPU.
+int RefineProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<double>& S, const std::vector<double>& t,
+                   uint32_t n_iter, bool one_per_protein, double pseudo, int device, std::vector<double>* S_out,
+                   uint32_t* iters, bool* converged, std::string* err);
 // center_codes (CentersFromKmers): the centres are k-mers of the exact table -- the one a FASTA
 // database is embedded from -- and travel to the GPU as residue codes (hs_query_codes: k bytes per
 // centre instead of 64 k); the hits are those of the embedded centres, bit for bit.

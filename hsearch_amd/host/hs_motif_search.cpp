@@ -38,6 +38,11 @@
 // instead of the hits, one line per (profile, protein) with a hit -- "<profile> <protein>#<number> <hits> <best
 // window's offset> <its score> <first> <last matched offset>" --, reduced on the device (hs_pssm_seq_scan), profiles in
 // file order, proteins in database order; refused without --pssm and with --pssm-top.
+// --pssm FILE --pssm-refine N --pssm-out FILE2 (N = 1..100): the profiles are first rebuilt from their own hits
+// (hs_pssm_refine: scan, counts, log-odds against the database's residue composition with --pssm-pseudo x [1] pseudo-
+// counts, at most N scans at the file's thresholds; --pssm-one-per-protein 1: only a protein's best window counts),
+// written to FILE2 with their names and thresholds, and -o then holds exactly what a run with --pssm FILE2 writes
+// (--pssm-top and --pssm-per-sequence included).  --pssm-refine without --pssm or without --pssm-out is refused.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -93,6 +98,10 @@ const Opt kOpts[] = {
     {"pssm", 'm', "FASTA database: scan every window against the position-specific score matrices of this file ('>name threshold', then -l lines of 20 numbers) in place of a search: no -c, -W, -T (one GPU)", false},
     {"pssm-top", 'n', "with --pssm: per profile only its N best windows, 1..64, among those at or above the file's threshold, by descending score then window index [off: every hit]", false},
     {"pssm-per-sequence", 'e', "with --pssm: instead of the hits, one line per (profile, protein) with a hit: count, best window and its score, span; not with --pssm-top [0]", false},
+    {"pssm-refine", 'R', "with --pssm and --pssm-out: first rebuild the profiles from their own hits, at most N scans, 1..100; -o then holds what --pssm with the refined file gives [off]", false},
+    {"pssm-out", 'O', "with --pssm-refine: write the refined profiles to this file, names and thresholds kept", false},
+    {"pssm-one-per-protein", 'I', "with --pssm-refine: only the best window of every protein counts [0]", false},
+    {"pssm-pseudo", 'u', "with --pssm-refine: pseudo-counts of the log-odds, > 0 [1]", false},
 };
 
 // A points file has a line of numbers after its first name line; a FASTA file has residue letters.
@@ -151,6 +160,29 @@ int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::str
     fprintf(stderr, "ERROR: --pssm-per-sequence reduces every hit of a profile: it cannot be combined with --pssm-top\n");
     return EXIT_FAILURE;
   }
+  uint32_t refine = 0;  // 0: the profiles as the file gives them
+  double pseudo = 1.0;
+  if (val.count("pssm-refine")) {
+    char* end = nullptr;
+    const long v = strtol(val["pssm-refine"].c_str(), &end, 10);
+    if (end == val["pssm-refine"].c_str() || *end || v < 1 || v > 100) {
+      fprintf(stderr, "ERROR: --pssm-refine takes a number of scans, 1..100\n");
+      return EXIT_FAILURE;
+    }
+    refine = (uint32_t)v;
+    if (!val.count("pssm-out")) {
+      fprintf(stderr, "ERROR: --pssm-refine needs --pssm-out: the file the refined profiles are written to\n");
+      return EXIT_FAILURE;
+    }
+    if (val.count("pssm-pseudo")) {
+      pseudo = strtod(val["pssm-pseudo"].c_str(), &end);
+      if (end == val["pssm-pseudo"].c_str() || *end || !(pseudo > 0.0) || !(pseudo <= 1.7976931348623157e308)) {
+        fprintf(stderr, "ERROR: --pssm-pseudo takes a finite number above 0\n");
+        return EXIT_FAILURE;
+      }
+    }
+  }
+  const bool one_per_protein = val.count("pssm-one-per-protein") && atoi(val["pssm-one-per-protein"].c_str()) != 0;
   const uint32_t kmer_length = (uint32_t)strtoul(val["len"].c_str(), nullptr, 10);
   const int device = val.count("device") ? atoi(val["device"].c_str()) : 0;
   try {
@@ -175,6 +207,23 @@ int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::str
       return EXIT_FAILURE;
     }
     std::cout << "number of profiles " << names.size() << std::endl;
+    if (refine) {
+      std::vector<double> refined;
+      uint32_t iters = 0;
+      bool converged = false;
+      const int rst = hsearch::RefineProfiles(prodb, kmer_length, S, t, refine, one_per_protein, pseudo, device, &refined,
+                                              &iters, &converged, &err);
+      if (rst != 0) {
+        fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), rst);
+        return EXIT_FAILURE;
+      }
+      S.swap(refined);
+      if (!hsearch::WritePssmFile(val["pssm-out"], kmer_length, names, S, t, &err)) {
+        fprintf(stderr, "ERROR: %s\n", err.c_str());
+        return EXIT_FAILURE;
+      }
+      std::cout << "refined in " << iters << " scans" << (converged ? " (converged)" : "") << std::endl;
+    }
     struct timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     uint64_t n_windows = 0, n_hits = 0, n_rows = 0;
@@ -250,6 +299,12 @@ int main(int argc, const char* argv[]) {
     fprintf(stderr, "ERROR: --pssm-per-sequence reduces the hits of --pssm: it cannot be given without it\n");
     return EXIT_FAILURE;
   }
+  for (const char* name : {"pssm-refine", "pssm-out", "pssm-one-per-protein", "pssm-pseudo"})
+    if (val.count(name) && !(with_pssm && val.count("pssm-refine"))) {
+      fprintf(stderr, "ERROR: --%s belongs to --pssm FILE --pssm-refine N --pssm-out FILE2: it cannot be given without them\n",
+              name);
+      return EXIT_FAILURE;
+    }
   const bool per_sequence = query_fasta || (val.count("per-sequence") && atoi(val["per-sequence"].c_str()) != 0);
   for (const Opt& o : kOpts)
     if (o.required && !val.count(o.long_name) && !(query_fasta && std::string(o.long_name) == "center") &&

@@ -114,6 +114,8 @@ typedef struct hs_profile {
   uint64_t pssm_dead;          /* ... profiles skipped because no k-mer can reach their threshold (filter on only) */
   uint64_t pssm_mfma_steps;    /* ... MFMA depth steps per 16 x 16 tile: ceil(k * alphabet / 128) (0: filter off) */
   uint64_t pssm_seq_rows;      /* hs_pssm_seq_scan*: the (profile, sequence) rows the call found (its *n_out) */
+  uint64_t pssm_count_sites;   /* hs_pssm_hit_counts*: the sites counted, the sum of used[] */
+  uint64_t pssm_count_items;   /* hs_pssm_hit_counts*: the (profile run, chunk) work items of the counting kernel */
   uint64_t pssm_topk_sample;   /* hs_pssm_topk*: the sample size n_s = min(n, HS_OPT_PSSM_TOPK_SAMPLE) the call used */
   uint64_t pssm_topk_raised;   /* hs_pssm_topk*: profiles scanned at a threshold above their floor (t_used > floor) */
 } hs_profile;
@@ -204,6 +206,8 @@ typedef enum hs_option {
                                 every (profile, k-mer) pair goes to the exact pass */
   HS_OPT_PSSM_TOPK_SAMPLE = 24, /* hs_pssm_topk: k-mers of the index the sample pass scores per profile (>= 1, default
                                 262144 = 2^18; the index's size where it is smaller).  Shows in t_used only, never in a row */
+  HS_OPT_PSSM_COUNT_CHUNK = 25, /* hs_pssm_hit_counts: sites per work item of the counting kernel (1 .. 2^20); 0 (default):
+                                a batch's sites / 4096, within 256 .. 2048.  Never shows in a count */
   HS_OPT_JOIN_XCD_RUN = 16  /* hs_join8x_kernel's work items dealt in runs of this many chunks per XCD, each XCD's
                                 waves on their own runs (a run's items stream the same query tiles: one L2 fetches
                                 them instead of eight).  0: one counter for the chip; -1 (default): by the size
@@ -1277,6 +1281,71 @@ HS_API hs_status hs_pssm_seq_hits(const uint32_t* m, const uint32_t* id, const d
                                   uint64_t nm, const uint64_t* id_start, uint64_t n_seq, uint32_t* out_m,
                                   uint32_t* out_seq, uint32_t* out_count, double* out_best_score, uint32_t* out_best_id,
                                   uint32_t* out_lo, uint32_t* out_hi, uint64_t cap, uint64_t* n_out);
+
+/* ---- PSSM hit counts and refinement: from a profile's hits back to a profile ------------------------------------- */
+
+/* The step that makes a profile search iterative: scan, rebuild the position frequency matrix from what was found, take
+ * log-odds, scan again (the PSI-BLAST loop; the hard-assignment EM step of a motif finder).  The counts are reduced on
+ * the device; the hit list never crosses PCIe.
+ *
+ * hs_pssm_hit_counts.  S, t, the score and the hit rule are hs_pssm_scan's, bit for bit; H is the hit list hs_pssm_scan
+ * returns for the same handle, S and t.
+ *   id_start == NULL (every site counts): counts[m][p][a] = the (m, id) in H with codes[id][p] == a.
+ *   id_start [n_seq + 1] given, under hs_pssm_seq_scan's rules (one site per protein): with Rows the rows
+ *   hs_pssm_seq_scan returns for the same arguments, counts[m][p][a] = the rows (m, s) with codes[best_id][p] == a.
+ * counts: uint32 [nm][k][alphabet], all of it written (zeros for a profile without hits); cnt [nm] (may be NULL): the
+ * hits per profile, hs_pssm_scan's cnt; used [nm] (may be NULL): the sites counted -- cnt without id_start,
+ * hs_pssm_seq_scan's seq_cnt with it; *n_hits: the scan's.  For every m and p the sum over a of counts[m][p][a] is
+ * used[m].  The output is dense: there is no capacity protocol.
+ * Errors, reported before anything is written: everything hs_pssm_scan refuses; with id_start given, everything
+ * hs_pssm_seq_scan refuses about it (n_seq == 0 with n > 0, n_seq > 2^32, an id_start that does not ascend from 0 to
+ * n); a null counts with nm > 0.  The _dev form finds the value errors on the device with one read-back.
+ * Purity: a pure function of (codes, S, t, id_start).  HS_OPT_QUERY_BATCH, HS_OPT_PSSM_FILTER,
+ * HS_OPT_PSSM_COUNT_CHUNK, survivor splits and scheduling do not show in it.
+ * How (hsearch_amd/csrc/hs_pssm_counts.hip): the scan's batches, tables, filter and exact pass as they are.  Every
+ * site: a batch's hits are ordered on their profile bits alone; one site per protein: the passes of hs_pssm_seq.hip
+ * give the rows' best ids.  Work items (profile run, chunk of HS_OPT_PSSM_COUNT_CHUNK sites) go one to a wave, which
+ * counts in an LDS histogram and stores it (a whole run) or adds its non-zero bins with integer atomics (a cut run).
+ * hs_profile after the call: the pssm_* fields as after a scan, pssm_count_sites, pssm_count_items, hits.
+ *
+ * hs_pssm_refine (host pointers).  S0 [nm][k][alphabet]; t [nm], fixed over the iterations; id_start or NULL as above;
+ * bg [alphabet] (NULL: hs_pssm_background of the counts of one all-zero profile at t = 0 without id_start -- the
+ * residue composition of the index, one extra scan; an empty index is HS_ERR_INVALID then); pseudo; 1 <= n_iter <= 100.
+ * Iteration i = 0, 1, ... computes C_i = hs_pssm_hit_counts(S_i, t).  If i > 0 and C_i equals C_{i-1} byte for byte the
+ * loop has converged and stops.  Otherwise S_{i+1}[m] = hs_pssm_log_odds(C_i[m]) where used_i[m] > 0, else S_i[m] (a
+ * profile that finds nothing keeps its matrix), and the loop stops after n_iter scans.  S_out: the last S computed
+ * (S_i on convergence at i, else S_{n_iter}); counts, used (may be NULL): of the last scan; *iters: the scans run, not
+ * counting the background's; *converged.  If it converged, hs_pssm_hit_counts(S_out, t) gives counts.  Per iteration
+ * only counts (down) and S (up) cross PCIe.  Nothing is written when the arguments or S0's values are refused.
+ * Out of scope: sequence weighting, a device log-odds (device log2 is not the host's bit for bit), a threshold update
+ * rule, multi-GPU drivers (hs_pssm_count_hits is the merge). */
+HS_API hs_status hs_pssm_hit_counts(hs_handle* h, const double* S, const double* t, uint64_t nm,
+                                    const uint64_t* id_start, uint64_t n_seq, uint32_t* counts, uint64_t* cnt,
+                                    uint64_t* used, uint64_t* n_hits);
+/* ... every pointer but n_hits in device memory (streams: as hs_pssm_scan_dev) */
+HS_API hs_status hs_pssm_hit_counts_dev(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm,
+                                        const uint64_t* d_id_start, uint64_t n_seq, uint32_t* d_counts, uint64_t* d_cnt,
+                                        uint64_t* d_used, uint64_t* n_hits);
+HS_API hs_status hs_pssm_refine(hs_handle* h, const double* S0, const double* t, uint64_t nm, const uint64_t* id_start,
+                                uint64_t n_seq, const double* bg, double pseudo, uint32_t n_iter, double* S_out,
+                                uint32_t* counts, uint64_t* used, uint32_t* iters, uint32_t* converged);
+/* The counting rule on the host (no GPU, no handle) for any list of (m, id, score) tuples in any order over codes
+ * [n][k]: the merge of several GPUs' shares.  A repeated (m, id) with equal score bits counts once, with different bits
+ * it is HS_ERR_INVALID (as hs_pssm_seq_hits); with id_start (which must ascend from 0 to n) the sites are the best
+ * hits of hs_pssm_seq_hits' rows.  m >= nm, id >= n, a NaN score, a counted code >= alphabet, alphabet > 32, k == 0 and
+ * a null counts with nm > 0 are HS_ERR_INVALID, with nothing written.  used may be NULL. */
+HS_API hs_status hs_pssm_count_hits(const uint8_t* codes, uint64_t n, uint32_t k, uint32_t alphabet, const uint32_t* m,
+                                    const uint32_t* id, const double* score, uint64_t n_tuples, uint64_t nm,
+                                    const uint64_t* id_start, uint64_t n_seq, uint32_t* counts, uint64_t* used);
+/* S[m][p][a] = log2((((double)c + pseudo * bg[a]) / ((double)size + pseudo)) / bg[a]), c = counts[m][p][a], size = the
+ * sum over a of counts[m][p][a]; every operation rounded to fp64, no FMA contraction, log2 the C library's.  bg[a] <= 0,
+ * a bg that is not finite and a pseudo that is not finite and > 0 are HS_ERR_INVALID, as is a bg so small that an entry
+ * would not be finite; nothing is written then.  Every entry written is finite and passes the scan's value check. */
+HS_API hs_status hs_pssm_log_odds(const uint32_t* counts, uint64_t nm, uint32_t k, uint32_t alphabet, const double* bg,
+                                  double pseudo, double* S_out);
+/* bg[a] = (the sum over p of counts_row[p][a]) / (the sum over p and a) for the counts [k][alphabet] of one profile; a
+ * zero is then replaced by the smallest positive entry, without renormalising.  All-zero counts: HS_ERR_INVALID. */
+HS_API hs_status hs_pssm_background(const uint32_t* counts_row, uint32_t k, uint32_t alphabet, double* bg_out);
 
 /* Replaces Clustering() (hclust2.cpp:86-151) with explicit planes a[L][K][d], b[L][K]: table by
  * table, an LSH table over the not-yet-absorbed k-mers, then greedy leader clustering inside every
