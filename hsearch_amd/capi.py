@@ -37,6 +37,7 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_index_table_remove", "hs_pssm_scan", "hs_pssm_scan_dev", "hs_pssm_tables",
            "hs_pssm_topk", "hs_pssm_topk_dev", "hs_pssm_topk_hits", "hs_pssm_seq_scan", "hs_pssm_seq_scan_dev",
            "hs_pssm_seq_hits", "hs_pssm_hit_counts", "hs_pssm_hit_counts_dev", "hs_pssm_refine", "hs_pssm_count_hits",
+           "hs_pssm_rank", "hs_pssm_rank_dev", "hs_pssm_rank_scores", "hs_pssm_rank_plan", "hs_pssm_refine_rank",
            "hs_pssm_log_odds", "hs_pssm_background"]
 
 TOPK_MAX = 64        # HS_TOPK_MAX: the widest row of query_topk / self_knn / topk_merge
@@ -71,7 +72,8 @@ class _Profile(C.Structure):
                 ("remove_dead_buckets", C.c_uint64), ("remove_retupled", C.c_uint64),
                 ("pssm_pairs", C.c_uint64), ("pssm_survivors", C.c_uint64), ("pssm_dead", C.c_uint64),
                 ("pssm_mfma_steps", C.c_uint64), ("pssm_seq_rows", C.c_uint64), ("pssm_count_sites", C.c_uint64),
-                ("pssm_count_items", C.c_uint64), ("pssm_topk_sample", C.c_uint64),
+                ("pssm_count_items", C.c_uint64), ("pssm_rank_sample", C.c_uint64),
+                ("pssm_rank_retries", C.c_uint64), ("pssm_topk_sample", C.c_uint64),
                 ("pssm_topk_raised", C.c_uint64)]
 
 
@@ -343,6 +345,22 @@ def load(hooks=False):
                                              C.c_void_p]
             lib.hs_pssm_background.restype = C.c_int
             lib.hs_pssm_background.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        # PSSM rank: (h, S, rank, nm, t_rank, cnt_ge, cnt_gt, t_scan, rounds); scores, plan, refine_rank:
+        # include/hsearch.h
+        if hasattr(lib, "hs_pssm_rank"):
+            for fn in (lib.hs_pssm_rank, lib.hs_pssm_rank_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p]
+            lib.hs_pssm_rank_scores.restype = C.c_int
+            lib.hs_pssm_rank_scores.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.hs_pssm_rank_plan.restype = C.c_int
+            lib.hs_pssm_rank_plan.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+            lib.hs_pssm_refine_rank.restype = C.c_int
+            lib.hs_pssm_refine_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                C.c_void_p, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         _libs[hooks] = lib
     return _libs[hooks]
 
@@ -880,6 +898,35 @@ def pssm_count_hits(codes, alphabet, m, id, score, nm, id_start=None):
     return dict(counts=counts, used=used[:rows])
 
 
+def pssm_rank_scores(codes, alphabet, S, rank):
+    """hs_pssm_rank_scores (host only, no GPU): the rule of Engine.pssm_rank over codes [n][k] -- every (profile, k-mer)
+    pair scored under pssm_scan's contract, then dict(t [nm] the rank-th largest score of each profile, cnt_ge, cnt_gt
+    uint64 [nm] the k-mers at or above and above it).  rank: a scalar or [nm]."""
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    assert codes.ndim == 2
+    n, k = codes.shape
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    nm = S.shape[0]
+    assert S.ndim == 3 and S.shape[1] == k and (S.shape[2] == int(alphabet) or not 1 <= int(alphabet) <= 32), S.shape
+    rank = np.ascontiguousarray(np.broadcast_to(np.asarray(rank, dtype=np.uint64), (nm,)))
+    t = np.empty(max(nm, 1), dtype=np.float64)
+    ge, gt = np.empty(max(nm, 1), dtype=np.uint64), np.empty(max(nm, 1), dtype=np.uint64)
+    st = load().hs_pssm_rank_scores(_vp(codes), n, k, int(alphabet), _vp(S), nm, _vp(rank), _vp(t), _vp(ge), _vp(gt))
+    if st:
+        raise HsError(st, "hs_pssm_rank_scores")
+    return dict(t=t[:nm], cnt_ge=ge[:nm], cnt_gt=gt[:nm])
+
+
+def pssm_rank_plan(rank, n, n_s, round=0):
+    """hs_pssm_rank_plan: the sample rank r_s that round `round` of Engine.pssm_rank takes its proposed threshold from,
+    for the wanted rank among n k-mers and a sample of n_s; n_s + 1 means beyond the sample (the scan at -DBL_MAX)."""
+    out = C.c_uint64(0)
+    st = load().hs_pssm_rank_plan(int(rank), int(n), int(n_s), int(round), C.byref(out))
+    if st:
+        raise HsError(st, "hs_pssm_rank_plan")
+    return int(out.value)
+
+
 def pssm_log_odds_exact(counts, background, pseudo=1.0):
     """hs_pssm_log_odds (host only): S[m][p][a] = log2((((double)c + pseudo * bg[a]) / ((double)size + pseudo)) /
     bg[a]) for counts uint32 [nm][k][alphabet], every operation rounded to fp64 -- the function Engine.pssm_refine
@@ -1129,7 +1176,7 @@ class Engine:
                "wide_rows": 6, "refine8": 7, "self_codes": 8, "sort_hits": 10, "sync_items": 11,
                "join_min_q": 12, "join_min_m": 13, "sort_from_bit": 14, "build_serial": 15,
                "join_xcd_run": 16, "probe_records": 17, "join_chunk": 18, "summary_chunk": 19, "summary_rows": 20,
-               "msf_edge_budget": 21, "join_f6": 22, "pssm_filter": 23, "pssm_topk_sample": 24,
+               "msf_edge_budget": 21, "join_f6": 22, "pssm_filter": 23, "pssm_topk_sample": 24, "pssm_rank_sample": 26,
                "pssm_count_chunk": 25}
 
     def set_option(self, name, value):
@@ -1821,6 +1868,66 @@ class Engine:
                                              n_seq, None if bg is None else _vp(bg), float(pseudo), int(n_iter),
                                              _vp(S_out), _vp(counts), _vp(used), C.byref(iters), C.byref(conv)))
         return dict(S=S_out, counts=counts, used=used[:nm], iters=int(iters.value), converged=bool(conv.value))
+
+    def _pssm_rank_args(self, S, rank):
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        nm = S.shape[0]
+        assert S.shape == (nm, self.k, self._alphabet()), S.shape
+        rank = np.ascontiguousarray(np.broadcast_to(np.asarray(rank, dtype=np.uint64), (nm,)))
+        return S, rank, nm
+
+    def pssm_rank(self, S, rank, want_diagnostics=False):
+        """hs_pssm_rank: for every profile S [nm][k][alphabet] the exact score of its rank-th best indexed k-mer (rank:
+        a scalar or [nm], each 1 .. n) -- the threshold at which pssm_scan returns the rank best k-mers and their
+        ties.  dict(t [nm], cnt_ge [nm] the k-mers scoring >= t (what pssm_scan at t returns), cnt_gt [nm] those
+        scoring > t[, t_scan [nm] and rounds [nm]: the threshold of the round that resolved the profile and the
+        retries before it -- the outputs that depend on the "pssm_rank_sample" option])."""
+        S, rank, nm = self._pssm_rank_args(S, rank)
+        t = np.empty(max(nm, 1), dtype=np.float64)
+        ge, gt = np.empty(max(nm, 1), dtype=np.uint64), np.empty(max(nm, 1), dtype=np.uint64)
+        ts = np.empty(max(nm, 1), dtype=np.float64) if want_diagnostics else None
+        ro = np.empty(max(nm, 1), dtype=np.uint32) if want_diagnostics else None
+        self._check(self._lib.hs_pssm_rank(self._h, _vp(S), _vp(rank), C.c_uint64(nm), _vp(t), _vp(ge), _vp(gt),
+                                           _vp(ts) if want_diagnostics else None,
+                                           _vp(ro) if want_diagnostics else None))
+        res = dict(t=t[:nm], cnt_ge=ge[:nm], cnt_gt=gt[:nm])
+        if want_diagnostics:
+            res["t_scan"], res["rounds"] = ts[:nm], ro[:nm]
+        return res
+
+    def pssm_rank_dev(self, d_S, d_rank, nm, d_t, d_cnt_ge, d_cnt_gt, d_t_scan=None, d_rounds=None):
+        """hs_pssm_rank_dev: device pointers (ints, e.g. tensor.data_ptr(); d_t_scan and d_rounds may be None)."""
+        self._check(self._lib.hs_pssm_rank_dev(self._h, d_S if d_S else None, d_rank if d_rank else None,
+                                               C.c_uint64(int(nm)), d_t if d_t else None,
+                                               d_cnt_ge if d_cnt_ge else None, d_cnt_gt if d_cnt_gt else None,
+                                               d_t_scan if d_t_scan else None, d_rounds if d_rounds else None))
+
+    def pssm_refine_rank(self, S, rank, n_iter, id_start=None, background=None, pseudo=1.0):
+        """hs_pssm_refine_rank: pssm_refine with the threshold rule -- every iteration scans at the threshold that admits
+        the rank best k-mers (and their ties) of the current matrix.  dict(S, t [nm] the threshold of the last scan,
+        counts, used: of the last scan, iters, converged).  used may exceed rank (ties); with id_start the rank still
+        counts k-mers, not proteins."""
+        S, rank, nm = self._pssm_rank_args(S, rank)
+        if id_start is not None:
+            id_start = np.ascontiguousarray(id_start, dtype=np.uint64)
+            assert id_start.ndim == 1 and len(id_start) >= 1
+        n_seq = 0 if id_start is None else len(id_start) - 1
+        bg = None
+        if background is not None:
+            bg = np.ascontiguousarray(background, dtype=np.float64)
+            assert bg.shape == (self._alphabet(),), bg.shape
+        S_out = np.empty(S.shape, dtype=np.float64)
+        t_out = np.empty(max(nm, 1), dtype=np.float64)
+        counts = np.empty(S.shape, dtype=np.uint32)
+        used = np.empty(max(nm, 1), dtype=np.uint64)
+        iters, conv = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.hs_pssm_refine_rank(self._h, _vp(S), _vp(rank), nm,
+                                                  None if id_start is None else _vp(id_start), n_seq,
+                                                  None if bg is None else _vp(bg), float(pseudo), int(n_iter),
+                                                  _vp(S_out), _vp(t_out), _vp(counts), _vp(used), C.byref(iters),
+                                                  C.byref(conv)))
+        return dict(S=S_out, t=t_out[:nm], counts=counts, used=used[:nm], iters=int(iters.value),
+                    converged=bool(conv.value))
 
     def bruteforce_radii(self, centers, radii, cap=None):
         """hs_bruteforce_radii: brute force with centre q searched at radii[q]."""

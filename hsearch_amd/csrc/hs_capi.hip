@@ -28,6 +28,7 @@
 #include "hs_pssm_seq.h"
 #include "hs_pssm_counts.h"
 #include "hs_pssm_topk.h"
+#include "hs_pssm_rank.h"
 
 namespace {
 
@@ -108,6 +109,7 @@ struct Knobs {
   int sort_from_bit = 16;          // HS_OPT_SORT_FROM_BIT: lowest fingerprint bit the build's sort looks at
   uint32_t query_batch = 0;        // HS_OPT_QUERY_BATCH: queries per batch (0: by L and the free HBM)
   uint32_t pssm_topk_sample = 262144;  // HS_OPT_PSSM_TOPK_SAMPLE: k-mers the sample pass of hs_pssm_topk scores per profile
+  uint32_t pssm_rank_sample = 262144;  // HS_OPT_PSSM_RANK_SAMPLE: k-mers the sample pass of hs_pssm_rank scores per profile
   uint32_t pssm_count_chunk = 0;   // HS_OPT_PSSM_COUNT_CHUNK: sites per work item of hs_pssm_counts.hip (0: by the batch)
   uint32_t summary_chunk = 0;      // HS_OPT_SUMMARY_CHUNK: member slots per work item of hs_summary.hip (0: 512)
   uint32_t summary_rows = 0;       // HS_OPT_SUMMARY_ROWS: rows per batch of hs_cluster_profile (0: by the scratch budget)
@@ -281,6 +283,10 @@ struct hs_handle {
   // hs_pssm_topk (hs_pssm_topk.hip; the selection's scratch is hs_knn.hip's): a batch's thresholds when the caller
   // wants none; the sample pass's lists when a profile's sample is split over several workgroups
   DevBuf pt_tused, pt_parts;
+  // hs_pssm_rank (hs_pssm_rank.hip; the hit selection's counts, offsets and cursors are hs_knn.hip's): a sub-batch's
+  // sample keys, their segment offsets, the select's state; the call's resolved flags, scan thresholds, and the word
+  // that counts a round's unresolved profiles; a host-pointer call's ranks in and outputs on their way out
+  DevBuf pr_keys, pr_off, pr_state, pr_resolved, pr_tscan, pr_unres, pr_rank, pr_out;
   // hs_pssm_hit_counts (hs_pssm_counts.hip): a batch's sites as (m, id) words and their copies sorted on m, the
   // profiles' run starts, chunk counts and their scan, the rows of the one-site-per-protein mode; a host-pointer
   // call's counts, cnt and used on their way out
@@ -560,7 +566,7 @@ const struct { const char* name; int option; } kOptionNames[] = {
     {"sort_hits", HS_OPT_SORT_HITS}, {"sync_items", HS_OPT_SYNC_ITEMS}, {"join_min_q", HS_OPT_JOIN_MIN_Q},
     {"join_min_m", HS_OPT_JOIN_MIN_M}, {"sort_from_bit", HS_OPT_SORT_FROM_BIT}, {"build_serial", HS_OPT_BUILD_SERIAL},
     {"join_xcd_run", HS_OPT_JOIN_XCD_RUN}, {"probe_records", HS_OPT_PROBE_RECORDS},
-    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"join_f6", HS_OPT_JOIN_F6}, {"pssm_filter", HS_OPT_PSSM_FILTER}, {"pssm_topk_sample", HS_OPT_PSSM_TOPK_SAMPLE}, {"pssm_count_chunk", HS_OPT_PSSM_COUNT_CHUNK}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS},
+    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"join_f6", HS_OPT_JOIN_F6}, {"pssm_filter", HS_OPT_PSSM_FILTER}, {"pssm_topk_sample", HS_OPT_PSSM_TOPK_SAMPLE}, {"pssm_rank_sample", HS_OPT_PSSM_RANK_SAMPLE}, {"pssm_count_chunk", HS_OPT_PSSM_COUNT_CHUNK}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS},
     {"msf_edge_budget", HS_OPT_MSF_EDGE_BUDGET}};
 
 void read_knobs(hs_handle* h) {
@@ -853,6 +859,10 @@ hs_status hs_set_option(hs_handle* h, int option, int64_t value) {
       if (value < 1 || value > 0xffffffffll) break;
       kn.pssm_topk_sample = (uint32_t)value;
       return HS_OK;
+    case HS_OPT_PSSM_RANK_SAMPLE:
+      if (value < 1 || value > 0xffffffffll) break;
+      kn.pssm_rank_sample = (uint32_t)value;
+      return HS_OK;
     case HS_OPT_PSSM_COUNT_CHUNK:
       if (value < 0 || value > (1ll << 20)) break;
       kn.pssm_count_chunk = (uint32_t)value;
@@ -933,6 +943,7 @@ void hs_destroy(hs_handle* h) {
                     &h->db_deg, &h->db_anchor, &h->db_cnt, &h->msf_comp, &h->msf_best_d, &h->msf_best_pair,
                     &h->msf_out_pair, &h->msf_out_d, &h->msf_s_pair, &h->msf_s_d, &h->msf_cnt, &h->msf_kept, &h->dt_core, &h->dt_thr,
                     &h->dt_next, &h->dt_cnt, &h->knn_cnt, &h->knn_off, &h->knn_cur, &h->knn_total, &h->knn_io_count, &h->pt_tused, &h->pt_parts,
+                    &h->pr_keys, &h->pr_off, &h->pr_state, &h->pr_resolved, &h->pr_tscan, &h->pr_unres, &h->pr_rank, &h->pr_out,
                     &h->pc_m, &h->pc_id, &h->pc_m2, &h->pc_id2, &h->pc_start, &h->pc_nitem, &h->pc_off, &h->pc_rows, &h->pc_out,
                     &h->sq_key, &h->sq_idx, &h->sq_skey, &h->sq_sidx, &h->sq_head, &h->sq_excl, &h->sq_part, &h->sq_acc,
                     &h->sq_fin, &h->sq_chk, &h->sq_in, &h->sq_out,
@@ -6438,6 +6449,237 @@ hs_status hs_pssm_topk(hs_handle* h, const double* S, const double* t_floor, uin
     HS_HIP(h, hipMemcpyAsync(top_count, h->knn_io_count.p, nm * 4, hipMemcpyDeviceToHost, h->stream));
     if (t_used) HS_HIP(h, hipMemcpyAsync(t_used, h->io_radii.p, nm * 8, hipMemcpyDeviceToHost, h->stream));
     HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return HS_OK;
+}
+
+// ---- hs_pssm_rank: the score of every profile's rank-th best k-mer (kernels, the argument, a round: hs_pssm_rank.hip) ----
+// The call with every array on the device; the callers have checked the arguments and the values (so n > 0 where
+// nm > 0) and know the largest rank.  d_tscan_out, d_rounds may be null.
+static hs_status pssm_rank_core(hs_handle* h, const double* d_S, const uint64_t* d_rank, uint64_t nm, uint64_t max_rank,
+                                double* d_t_rank, uint64_t* d_ge, uint64_t* d_gt, double* d_tscan_out,
+                                uint32_t* d_rounds) {
+  memset(&h->prof, 0, sizeof(h->prof));
+  HS_HIP(h, h->counters.reserve(256));
+  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
+  const bool filt = !h->knobs.no_pssm_filter;
+  const size_t ka = (size_t)h->p.k * h->alphabet;
+  const uint32_t n = (uint32_t)h->n, n_s = (uint32_t)std::min<uint64_t>(h->n, h->knobs.pssm_rank_sample);
+  uint64_t total = 0, retries = 0;
+  if (nm && n) {
+    HS_HIP(h, h->pr_resolved.reserve(nm * 4));
+    HS_HIP(h, h->pr_tscan.reserve(nm * 8));
+    HS_HIP(h, h->pr_unres.reserve(16));
+    uint32_t* const resolved = h->pr_resolved.as<uint32_t>();
+    uint32_t* const d_unres = h->pr_unres.as<uint32_t>();
+    double* const tscan = h->pr_tscan.as<double>();
+    HS_HIP(h, hs_launch_pssm_rank_init(nm, resolved, d_unres, h->stream));
+    const uint32_t SB = hs_pssm_rank_sample_batch(n_s);
+    for (uint32_t round = 0;; ++round) {
+      // 1. the sample pass and its select, in sub-batches of its own: the key buffer stays within 2^27 bytes
+      HS_HIP(h, hipEventRecord(h->ev[10], h->stream));
+      for (uint64_t m0 = 0; m0 < nm; m0 += SB) {
+        const uint32_t mb = (uint32_t)std::min<uint64_t>(SB, nm - m0);
+        HS_HIP(h, h->pr_keys.reserve((size_t)mb * n_s * 8));
+        HS_HIP(h, h->pr_off.reserve(((size_t)mb + 1) * 4));
+        HS_HIP(h, h->pr_state.reserve(hs_pssm_rank_state_bytes(mb)));
+        HS_HIP(h, hs_launch_pssm_rank_sample(h->codes.as<uint8_t>(), d_S, d_rank, resolved, (int)h->p.k, h->alphabet, n,
+                                             n_s, round, (uint32_t)m0, mb, h->pr_keys.as<uint64_t>(),
+                                             h->pr_off.as<uint32_t>(), h->pr_state.p, tscan, d_tscan_out, h->stream));
+      }
+      HS_HIP(h, hipEventRecord(h->ev[11], h->stream));
+      HS_HIP(h, hipMemsetAsync(d_unres, 0, 4, h->stream));
+      HS_HIP(h, hipStreamSynchronize(h->stream));
+      h->prof.ms_hash += ev_ms(h, 10, 11);
+      // 2. the scan.  Profiles per batch: what HS_OPT_QUERY_BATCH says, or at most 4096 and few enough that the hits
+      // to expect -- the largest rank's r_s * n / n_s per profile, n at the ladder's last rung -- stay within 2^24
+      uint64_t r_s = 0;
+      if (hs_pssm_rank_plan_rule(max_rank, n, n_s, round, &r_s)) return fail(h, HS_ERR_HIP, "hs_pssm_rank: no plan");
+      const uint64_t per = r_s > n_s ? n : std::max<uint64_t>(1, r_s * n / n_s);
+      uint32_t MB = h->knobs.query_batch ? h->knobs.query_batch
+                                         : (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(1, (1ull << 24) / per));
+      uint32_t mb = 0;
+      for (uint64_t m0 = 0; m0 < nm; m0 += mb) {
+        mb = (uint32_t)std::min<uint64_t>(MB, nm - m0);
+        uint32_t nh = 0;
+        const hs_status st = pssm_batch(h, d_S + m0 * ka, tscan + m0, (uint32_t)m0, mb, filt, &nh);
+        if (st == HS_SPLIT_BATCH) {  // (as pssm_core: the same profiles again in batches half the size)
+          if (mb == 1) return fail(h, HS_ERR_CAPACITY, "the filter survivors of one profile exceed 2^32");
+          MB = (mb + 1) / 2;
+          mb = 0;
+          continue;
+        }
+        if (st) return st;
+        // 3. the selection and the resolve step; they run for a batch without hits too: its profiles are counted
+        HS_HIP(h, hipEventRecord(h->ev[6], h->stream));
+        const size_t words = ((size_t)mb + 1) * 4;
+        HS_HIP(h, h->knn_cnt.reserve(words));
+        HS_HIP(h, h->knn_off.reserve(words));
+        HS_HIP(h, h->knn_cur.reserve(words));
+        HS_HIP(h, h->hit_key2.reserve(std::max<size_t>(16, (size_t)nh * 8)));
+        HS_HIP(h, h->pr_state.reserve(hs_pssm_rank_state_bytes(mb)));
+        HS_HIP(h, h->temp.reserve(hs_pssm_rank_temp(mb) + 256));
+        HS_HIP(h, hs_launch_pssm_rank_select(h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(), nh, (uint32_t)m0, mb,
+                                             h->knn_cnt.as<uint32_t>(), h->knn_off.as<uint32_t>(),
+                                             h->knn_cur.as<uint32_t>(), h->temp.p, h->temp.cap,
+                                             h->hit_key2.as<uint64_t>(), h->pr_state.p, d_rank, resolved, round, d_t_rank,
+                                             d_ge, d_gt, d_rounds, d_unres, h->stream));
+        HS_HIP(h, hipEventRecord(h->ev[7], h->stream));
+        HS_HIP(h, hipStreamSynchronize(h->stream));
+        h->prof.ms_finalize += ev_ms(h, 6, 7);
+        total += nh;
+      }
+      uint32_t unresolved = 0;
+      HS_HIP(h, hipMemcpyAsync(&unresolved, d_unres, 4, hipMemcpyDeviceToHost, h->stream));
+      HS_HIP(h, hipStreamSynchronize(h->stream));
+      if (!unresolved) break;
+      retries += unresolved;  // (each of them takes one more round)
+      // (the plan saturates beyond round 16: that round scans at -DBL_MAX and resolves everything)
+      if (round >= 17) return fail(h, HS_ERR_HIP, "hs_pssm_rank: profiles left after the ladder's last rung");
+    }
+  }
+  HS_HIP(h, hipEventRecord(h->ev[9], h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  h->prof.ms_total = ev_ms(h, 8, 9);
+  h->prof.hits = total;
+  h->prof.pssm_rank_sample = n_s;
+  h->prof.pssm_rank_retries = retries;
+  return HS_OK;
+}
+
+static hs_status pssm_rank_args(hs_handle* h, const void* S, const void* rank, uint64_t nm, const void* t_rank,
+                                const void* cnt_ge, const void* cnt_gt) {
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
+  if (nm >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nm must be < 2^27 per call");
+  if (nm && !S) return fail(h, HS_ERR_INVALID, "hs_pssm_rank: S is null");
+  if (nm && (!rank || !t_rank || !cnt_ge || !cnt_gt))
+    return fail(h, HS_ERR_INVALID, "hs_pssm_rank: rank or an output array is null");
+  return HS_OK;
+}
+
+hs_status hs_pssm_rank_dev(hs_handle* h, const double* d_S, const uint64_t* d_rank, uint64_t nm, double* d_t_rank,
+                           uint64_t* d_cnt_ge, uint64_t* d_cnt_gt, double* d_t_scan, uint32_t* d_rounds) {
+  if (!h) return HS_ERR_INVALID;
+  HS_CHECK(pssm_rank_args(h, d_S, d_rank, nm, d_t_rank, d_cnt_ge, d_cnt_gt));
+  HS_CHECK(ensure_device(h));
+  uint64_t chk[2] = {0, 0};  // the flags; the largest rank
+  if (nm) {  // the values, on the device: two small reductions and one read-back, before anything is written
+    HS_HIP(h, h->io_radii.reserve(16));
+    HS_HIP(h, hipMemsetAsync(h->io_radii.p, 0, 16, h->stream));
+    HS_HIP(h, hs_launch_pssm_check(d_S, nm * h->p.k * h->alphabet, nullptr, 0, h->io_radii.as<uint32_t>(), h->stream));
+    HS_HIP(h, hs_launch_pssm_rank_check(d_rank, nm, h->n, h->io_radii.as<uint32_t>(), h->io_radii.as<uint64_t>() + 1,
+                                        h->stream));
+    HS_HIP(h, hipMemcpyAsync(chk, h->io_radii.p, 16, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    if (chk[0] & 1u) return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
+    if (chk[0] & 4u) return fail(h, HS_ERR_INVALID, "hs_pssm_rank: a rank is 0 or above the index's k-mers");
+  }
+  return pssm_rank_core(h, d_S, d_rank, nm, chk[1], d_t_rank, d_cnt_ge, d_cnt_gt, d_t_scan, d_rounds);
+}
+
+hs_status hs_pssm_rank(hs_handle* h, const double* S, const uint64_t* rank, uint64_t nm, double* t_rank,
+                       uint64_t* cnt_ge, uint64_t* cnt_gt, double* t_scan, uint32_t* rounds) {
+  if (!h) return HS_ERR_INVALID;
+  HS_CHECK(pssm_rank_args(h, S, rank, nm, t_rank, cnt_ge, cnt_gt));
+  const size_t ka = (size_t)h->p.k * h->alphabet;
+  for (uint64_t i = 0; i < nm * ka; ++i)
+    if (hs_pssm_bad_value(S[i], HS_PSSM_MAX_ABS))
+      return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
+  uint64_t max_rank = 0;
+  for (uint64_t m = 0; m < nm; ++m) {
+    if (rank[m] < 1 || rank[m] > h->n)
+      return fail(h, HS_ERR_INVALID, "hs_pssm_rank: a rank is 0 or above the index's k-mers");
+    max_rank = std::max(max_rank, rank[m]);
+  }
+  HS_CHECK(ensure_device(h));
+  const size_t cb = std::max<size_t>(16, nm * 8);
+  HS_HIP(h, h->io_centers.reserve(std::max<size_t>(16, nm * ka * 8)));
+  HS_HIP(h, h->pr_rank.reserve(cb));
+  HS_HIP(h, h->pr_out.reserve(5 * cb));
+  if (nm) {
+    HS_HIP(h, hipMemcpyAsync(h->io_centers.p, S, nm * ka * 8, hipMemcpyHostToDevice, h->stream));
+    HS_HIP(h, hipMemcpyAsync(h->pr_rank.p, rank, nm * 8, hipMemcpyHostToDevice, h->stream));
+  }
+  // one double and two counts per profile (and the diagnostics) cross PCIe
+  char* const o = h->pr_out.as<char>();
+  double* const d_t = reinterpret_cast<double*>(o);
+  uint64_t* const d_ge = reinterpret_cast<uint64_t*>(o + cb);
+  uint64_t* const d_gt = reinterpret_cast<uint64_t*>(o + 2 * cb);
+  double* const d_ts = t_scan ? reinterpret_cast<double*>(o + 3 * cb) : nullptr;
+  uint32_t* const d_ro = rounds ? reinterpret_cast<uint32_t*>(o + 4 * cb) : nullptr;
+  HS_CHECK(pssm_rank_core(h, h->io_centers.as<double>(), h->pr_rank.as<uint64_t>(), nm, max_rank, d_t, d_ge, d_gt, d_ts,
+                          d_ro));
+  if (nm) {
+    HS_HIP(h, hipMemcpyAsync(t_rank, d_t, nm * 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(cnt_ge, d_ge, nm * 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(cnt_gt, d_gt, nm * 8, hipMemcpyDeviceToHost, h->stream));
+    if (t_scan) HS_HIP(h, hipMemcpyAsync(t_scan, d_ts, nm * 8, hipMemcpyDeviceToHost, h->stream));
+    if (rounds) HS_HIP(h, hipMemcpyAsync(rounds, d_ro, nm * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return HS_OK;
+}
+
+// hs_pssm_refine with the threshold rule: every iteration scans at the threshold that admits rank[m] k-mers of S_i
+hs_status hs_pssm_refine_rank(hs_handle* h, const double* S0, const uint64_t* rank, uint64_t nm,
+                              const uint64_t* id_start, uint64_t n_seq, const double* bg, double pseudo, uint32_t n_iter,
+                              double* S_out, double* t_out, uint32_t* counts, uint64_t* used, uint32_t* iters,
+                              uint32_t* converged) {
+  if (!h || !iters || !converged) return HS_ERR_INVALID;
+  *iters = 0;
+  *converged = 0;
+  HS_CHECK(pssm_counts_args(h, S0, rank, nm, id_start, n_seq, S_out));
+  if (nm && !t_out) return fail(h, HS_ERR_INVALID, "hs_pssm_refine_rank: t_out is null");
+  if (n_iter < 1 || n_iter > 100) return fail(h, HS_ERR_INVALID, "hs_pssm_refine: n_iter must be 1 .. 100");
+  const uint32_t k = h->p.k, A = (uint32_t)h->alphabet;
+  double bgv[32];
+  if (!(pseudo > 0.0 && pseudo <= 1.7976931348623157e308) || (bg && !hs_pssm_bg_ok(bg, A, pseudo)))
+    return fail(h, HS_ERR_INVALID, "hs_pssm_refine: the background must be positive and finite, pseudo finite and > 0");
+  const size_t cells = (size_t)k * A;
+  try {
+    std::vector<double> T(nm, 0.0);
+    HS_CHECK(pssm_counts_values(h, S0, T.data(), nm, id_start, n_seq));
+    for (uint64_t m = 0; m < nm; ++m)
+      if (rank[m] < 1 || rank[m] > h->n)
+        return fail(h, HS_ERR_INVALID, "hs_pssm_rank: a rank is 0 or above the index's k-mers");
+    uint64_t nh = 0;
+    if (bg) {
+      for (uint32_t a = 0; a < A; ++a) bgv[a] = bg[a];
+    } else {  // the residue composition of the index, as hs_pssm_refine takes it
+      const std::vector<double> zero(cells, 0.0);
+      std::vector<uint32_t> all(cells);
+      const double t0 = 0.0;
+      HS_CHECK(pssm_counts_host(h, zero.data(), &t0, 1, nullptr, 0, false, all.data(), nullptr, nullptr, &nh));
+      if (hs_pssm_background_host(all.data(), k, A, bgv))
+        return fail(h, HS_ERR_INVALID, "hs_pssm_refine: an empty index has no background");
+    }
+    std::vector<double> S(S0, S0 + nm * cells);
+    std::vector<uint32_t> C(nm * cells), prev;
+    std::vector<uint64_t> U(nm), ge(nm), gt(nm);
+    uint32_t done = 0, conv = 0;
+    for (uint32_t i = 0; i < n_iter; ++i) {
+      HS_CHECK(hs_pssm_rank(h, S.data(), rank, nm, T.data(), ge.data(), gt.data(), nullptr, nullptr));
+      HS_CHECK(pssm_counts_host(h, S.data(), T.data(), nm, id_start, n_seq, i > 0, C.data(), nullptr, U.data(), &nh));
+      ++done;
+      if (i > 0 && C == prev) {
+        conv = 1;
+        break;
+      }
+      for (uint64_t m = 0; m < nm; ++m)
+        if (U[m] && hs_pssm_log_odds_host(C.data() + m * cells, 1, k, A, bgv, pseudo, S.data() + m * cells))
+          return fail(h, HS_ERR_INVALID, "hs_pssm_refine: a log-odds entry is not finite");
+      prev = C;
+    }
+    for (size_t i = 0; i < S.size(); ++i) S_out[i] = S[i];
+    for (uint64_t m = 0; m < nm; ++m) t_out[m] = T[m];
+    if (counts)
+      for (size_t i = 0; i < C.size(); ++i) counts[i] = C[i];
+    if (used)
+      for (uint64_t m = 0; m < nm; ++m) used[m] = U[m];
+    *iters = done;
+    *converged = conv;
+  } catch (const std::bad_alloc&) {
+    return fail(h, HS_ERR_NOMEM, "hs_pssm_refine: out of host memory");
   }
   return HS_OK;
 }

@@ -882,6 +882,32 @@ hipError_t hs_launch_pssm_topk_select(const uint64_t* d_key, const uint64_t* d_v
 hipError_t hs_launch_pssm_topk_fill(uint64_t rows, uint32_t topk, const double* d_floor, uint32_t* d_top_id,
                                     double* d_top_score, uint32_t* d_top_count, double* d_t_used, hipStream_t s);
 
+// ---- hs_pssm_rank (hs_pssm_rank.hip: a round's three steps and the segmented radix select are written at its head) --
+size_t hs_pssm_rank_state_bytes(uint32_t count);  // the select's state for `count` segments
+size_t hs_pssm_rank_temp(uint32_t count);         // the scan's workspace for a batch of `count` profiles
+uint32_t hs_pssm_rank_sample_batch(uint32_t n_s); // profiles per sub-batch of the sample pass (keys within 2^27 bytes)
+// *d_flag |= 4 for a rank outside 1 .. n; *d_max_rank = max(*d_max_rank, the ranks)
+hipError_t hs_launch_pssm_rank_check(const uint64_t* d_rank, uint64_t nm, uint64_t n, uint32_t* d_flag,
+                                     uint64_t* d_max_rank, hipStream_t s);
+// d_resolved [nm] = 0, *d_unresolved = 0
+hipError_t hs_launch_pssm_rank_init(uint64_t nm, uint32_t* d_resolved, uint32_t* d_unresolved, hipStream_t s);
+// the sample pass and its select for profiles m0 .. m0 + mb - 1 (every array is the CALL's): d_t_scan [m] = the plan's
+// r_s-th largest sample score, -DBL_MAX beyond the sample, +DBL_MAX for a resolved profile; d_t_scan_out (may be null)
+// takes the unresolved profiles' values.  d_keys [mb * n_s] (< 2^32), d_off [mb + 1], d_state of
+// hs_pssm_rank_state_bytes(mb)
+hipError_t hs_launch_pssm_rank_sample(const uint8_t* d_codes, const double* d_S, const uint64_t* d_rank,
+                                      const uint32_t* d_resolved, int k, int alphabet, uint32_t n, uint32_t n_s,
+                                      uint32_t round, uint32_t m0, uint32_t mb, uint64_t* d_keys, uint32_t* d_off,
+                                      void* d_state, double* d_t_scan, double* d_t_scan_out, hipStream_t s);
+// the batch's nh unordered hits (m << 32 | id, score bits) of profiles [first, first + count): the unresolved profiles
+// with at least rank hits get t_rank, cnt_ge, cnt_gt, rounds (may be null) = round and are resolved; *d_unresolved +=
+// the others.  d_cnt / d_off / d_cur [count + 1], d_seg [max(1, nh)], d_state of hs_pssm_rank_state_bytes(count)
+hipError_t hs_launch_pssm_rank_select(const uint64_t* d_key, const uint64_t* d_val, uint32_t nh, uint32_t first,
+                                      uint32_t count, uint32_t* d_cnt, uint32_t* d_off, uint32_t* d_cur, void* d_temp,
+                                      size_t temp_bytes, uint64_t* d_seg, void* d_state, const uint64_t* d_rank,
+                                      uint32_t* d_resolved, uint32_t round, double* d_t_rank, uint64_t* d_cnt_ge,
+                                      uint64_t* d_cnt_gt, uint32_t* d_rounds, uint32_t* d_unresolved, hipStream_t s);
+
 // ---- hs_pssm_seq_scan (hs_pssm_seq.hip: the passes over a batch's sorted hits are written at its head) -------------
 // head: the n hits sorted by m << 32 | id -> d_seq [n] (the sequence of every hit) and d_head [n + 1] (row starts)
 hipError_t hs_launch_pssm_seq_head(const uint64_t* d_key, uint32_t n, const uint64_t* d_id_start, uint64_t n_seq,

@@ -1010,6 +1010,66 @@ int RefineProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<
   return HS_OK;
 }
 
+int RankThresholds(const ProteinDB& db, uint32_t kmer_length, const std::vector<double>& S,
+                   const std::vector<uint64_t>& rank, int device, std::vector<double>* t_out,
+                   std::vector<uint64_t>* cnt_ge, uint64_t* n_windows, std::string* err) {
+  const uint32_t k = kmer_length;
+  const size_t nm = rank.size();
+  if (k < 2 || S.size() != nm * (size_t)k * HS_ALPHABET) {
+    if (err) *err = k < 2 ? "kmer length 1 is not supported on a FASTA database" : "the profiles do not match the kmer length";
+    return HS_ERR_INVALID;
+  }
+  hs_handle* h = nullptr;
+  uint64_t n_win = 0;
+  std::vector<uint32_t> win_pos;
+  std::vector<uint64_t> id_start;
+  hs_status st = (hs_status)OpenWindowsIndex(db, k, device, &h, &n_win, &win_pos, &id_start, err);
+  HandleCloser closer = {h};
+  if (st != HS_OK) return st;
+  if (n_windows) *n_windows = n_win;
+  std::vector<uint64_t> ge(nm), gt(nm);
+  t_out->assign(nm, 0.0);
+  st = hs_pssm_rank(h, S.data(), rank.data(), nm, t_out->data(), ge.data(), gt.data(), nullptr, nullptr);
+  if (st != HS_OK) {
+    if (err) *err = std::string("hs_pssm_rank: ") + hs_last_error(h);
+    return st;
+  }
+  if (cnt_ge) cnt_ge->swap(ge);
+  return HS_OK;
+}
+
+int RefineProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<double>& S,
+                   const std::vector<uint64_t>& rank, uint32_t n_iter, bool one_per_protein, double pseudo, int device,
+                   std::vector<double>* S_out, std::vector<double>* t_out, uint32_t* iters, bool* converged,
+                   std::string* err) {
+  const uint32_t k = kmer_length;
+  const size_t nm = rank.size();
+  if (k < 2 || S.size() != nm * (size_t)k * HS_ALPHABET) {
+    if (err) *err = k < 2 ? "kmer length 1 is not supported on a FASTA database" : "the profiles do not match the kmer length";
+    return HS_ERR_INVALID;
+  }
+  const size_t n_seq = db.start.empty() ? 0 : db.start.size() - 1;
+  hs_handle* h = nullptr;
+  uint64_t n_win = 0;
+  std::vector<uint32_t> win_pos;
+  std::vector<uint64_t> id_start;
+  hs_status st = (hs_status)OpenWindowsIndex(db, k, device, &h, &n_win, &win_pos, &id_start, err);
+  HandleCloser closer = {h};
+  if (st != HS_OK) return st;
+  S_out->assign(S.size(), 0.0);
+  t_out->assign(nm, 0.0);
+  uint32_t done = 0, conv = 0;
+  st = hs_pssm_refine_rank(h, S.data(), rank.data(), nm, one_per_protein ? id_start.data() : nullptr, n_seq, nullptr,
+                           pseudo, n_iter, S_out->data(), t_out->data(), nullptr, nullptr, &done, &conv);
+  if (st != HS_OK) {
+    if (err) *err = std::string("hs_pssm_refine_rank: ") + hs_last_error(h);
+    return st;
+  }
+  if (iters) *iters = done;
+  if (converged) *converged = conv != 0;
+  return HS_OK;
+}
+
 // "<first token of the protein's name>#<its number>": how the search's k-mer names begin
 static std::string ProteinLabel(const ProteinDB& db, size_t s) {
   std::string token;

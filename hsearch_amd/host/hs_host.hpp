@@ -216,6 +216,18 @@ bool WritePssmFile(const std::string& path, uint32_t kmer_length, const std::vec
 int RefineProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<double>& S, const std::vector<double>& t,
                    uint32_t n_iter, bool one_per_protein, double pseudo, int device, std::vector<double>* S_out,
                    uint32_t* iters, bool* converged, std::string* err);
+// `--pssm FILE --pssm-rank N`: per profile the score of its rank-th best window over the database (hs_pssm_rank) -- the
+// threshold at which a scan returns the rank best windows and their ties.  rank [nm], each 1 .. the number of windows
+// (*n_windows; a rank outside is HS_ERR_INVALID).  t_out [nm]; cnt_ge (may be null): the windows at or above it.  One GPU.
+int RankThresholds(const ProteinDB& db, uint32_t kmer_length, const std::vector<double>& S,
+                   const std::vector<uint64_t>& rank, int device, std::vector<double>* t_out,
+                   std::vector<uint64_t>* cnt_ge, uint64_t* n_windows, std::string* err);
+// `--pssm FILE --pssm-rank N --pssm-refine I`: RefineProfiles with the threshold rule (hs_pssm_refine_rank): every scan
+// runs at the threshold that admits the rank[m] best windows of the current matrix.  t_out: the last scan's thresholds.
+int RefineProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<double>& S,
+                   const std::vector<uint64_t>& rank, uint32_t n_iter, bool one_per_protein, double pseudo, int device,
+                   std::vector<double>* S_out, std::vector<double>* t_out, uint32_t* iters, bool* converged,
+                   std::string* err);
 // center_codes (CentersFromKmers): the centres are k-mers of the exact table -- the one a FASTA
 // database is embedded from -- and travel to the GPU as residue codes (hs_query_codes: k bytes per
 // centre instead of 64 k); the hits are those of the embedded centres, bit for bit.

@@ -43,6 +43,11 @@
 // counts, at most N scans at the file's thresholds; --pssm-one-per-protein 1: only a protein's best window counts),
 // written to FILE2 with their names and thresholds, and -o then holds exactly what a run with --pssm FILE2 writes
 // (--pssm-top and --pssm-per-sequence included).  --pssm-refine without --pssm or without --pssm-out is refused.
+// --pssm FILE --pssm-rank N --pssm-out FILE2: every threshold of FILE is replaced by the score of the profile's N-th
+// best window over the database (hs_pssm_rank; N = 1 .. the number of windows), FILE2 is FILE with those thresholds,
+// and -o holds exactly what --pssm FILE2 writes.  With --pssm-refine I beside it the loop scans at that threshold in
+// every iteration (hs_pssm_refine_rank) and FILE2 holds the final matrices and the last scan's thresholds.
+// --pssm-rank without --pssm or without --pssm-out is refused.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -99,7 +104,8 @@ const Opt kOpts[] = {
     {"pssm-top", 'n', "with --pssm: per profile only its N best windows, 1..64, among those at or above the file's threshold, by descending score then window index [off: every hit]", false},
     {"pssm-per-sequence", 'e', "with --pssm: instead of the hits, one line per (profile, protein) with a hit: count, best window and its score, span; not with --pssm-top [0]", false},
     {"pssm-refine", 'R', "with --pssm and --pssm-out: first rebuild the profiles from their own hits, at most N scans, 1..100; -o then holds what --pssm with the refined file gives [off]", false},
-    {"pssm-out", 'O', "with --pssm-refine: write the refined profiles to this file, names and thresholds kept", false},
+    {"pssm-out", 'O', "with --pssm-refine or --pssm-rank: write the profiles (refined, with the rank's thresholds) to this file", false},
+    {"pssm-rank", 'k', "with --pssm and --pssm-out: replace every threshold by the score of the profile's N-th best window over the database, 1..windows; -o then holds what --pssm with that file gives [off]", false},
     {"pssm-one-per-protein", 'I', "with --pssm-refine: only the best window of every protein counts [0]", false},
     {"pssm-pseudo", 'u', "with --pssm-refine: pseudo-counts of the log-odds, > 0 [1]", false},
 };
@@ -182,6 +188,22 @@ int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::str
       }
     }
   }
+  uint64_t rank_n = 0;  // 0: the thresholds as the file gives them
+  if (val.count("pssm-rank")) {
+    const std::string& text = val["pssm-rank"];
+    char* end = nullptr;
+    const unsigned long long v = strtoull(text.c_str(), &end, 10);
+    if (text.empty() || text.find_first_not_of("0123456789") != std::string::npos || *end || v < 1 ||
+        v > 0xffffffffull) {
+      fprintf(stderr, "ERROR: --pssm-rank takes a whole number of windows, 1 .. the windows of the database\n");
+      return EXIT_FAILURE;
+    }
+    rank_n = v;
+    if (!val.count("pssm-out")) {
+      fprintf(stderr, "ERROR: --pssm-rank needs --pssm-out: the file the profiles and their new thresholds are written to\n");
+      return EXIT_FAILURE;
+    }
+  }
   const bool one_per_protein = val.count("pssm-one-per-protein") && atoi(val["pssm-one-per-protein"].c_str()) != 0;
   const uint32_t kmer_length = (uint32_t)strtoul(val["len"].c_str(), nullptr, 10);
   const int device = val.count("device") ? atoi(val["device"].c_str()) : 0;
@@ -207,12 +229,31 @@ int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::str
       return EXIT_FAILURE;
     }
     std::cout << "number of profiles " << names.size() << std::endl;
+    // (a rank above the database's windows is refused by the library, with nothing written)
+    const std::vector<uint64_t> ranks(names.size(), rank_n);
+    if (rank_n && !refine) {
+      std::vector<double> t_rank;
+      const int rst = hsearch::RankThresholds(prodb, kmer_length, S, ranks, device, &t_rank, nullptr, nullptr, &err);
+      if (rst != 0) {
+        fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), rst);
+        return EXIT_FAILURE;
+      }
+      t.swap(t_rank);
+      if (!hsearch::WritePssmFile(val["pssm-out"], kmer_length, names, S, t, &err)) {
+        fprintf(stderr, "ERROR: %s\n", err.c_str());
+        return EXIT_FAILURE;
+      }
+      std::cout << "thresholds set to the score of rank " << rank_n << std::endl;
+    }
     if (refine) {
-      std::vector<double> refined;
+      std::vector<double> refined, t_last;
       uint32_t iters = 0;
       bool converged = false;
-      const int rst = hsearch::RefineProfiles(prodb, kmer_length, S, t, refine, one_per_protein, pseudo, device, &refined,
-                                              &iters, &converged, &err);
+      const int rst = rank_n ? hsearch::RefineProfiles(prodb, kmer_length, S, ranks, refine, one_per_protein, pseudo,
+                                                       device, &refined, &t_last, &iters, &converged, &err)
+                             : hsearch::RefineProfiles(prodb, kmer_length, S, t, refine, one_per_protein, pseudo, device,
+                                                       &refined, &iters, &converged, &err);
+      if (rank_n && rst == 0) t.swap(t_last);
       if (rst != 0) {
         fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), rst);
         return EXIT_FAILURE;
@@ -299,8 +340,13 @@ int main(int argc, const char* argv[]) {
     fprintf(stderr, "ERROR: --pssm-per-sequence reduces the hits of --pssm: it cannot be given without it\n");
     return EXIT_FAILURE;
   }
+  if (val.count("pssm-rank") && !with_pssm) {
+    fprintf(stderr, "ERROR: --pssm-rank sets the thresholds of --pssm FILE: it cannot be given without it\n");
+    return EXIT_FAILURE;
+  }
   for (const char* name : {"pssm-refine", "pssm-out", "pssm-one-per-protein", "pssm-pseudo"})
-    if (val.count(name) && !(with_pssm && val.count("pssm-refine"))) {
+    if (val.count(name) && !(with_pssm && (val.count("pssm-refine") ||
+                                           (std::string(name) == "pssm-out" && val.count("pssm-rank"))))) {
       fprintf(stderr, "ERROR: --%s belongs to --pssm FILE --pssm-refine N --pssm-out FILE2: it cannot be given without them\n",
               name);
       return EXIT_FAILURE;

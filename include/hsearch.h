@@ -116,6 +116,8 @@ typedef struct hs_profile {
   uint64_t pssm_seq_rows;      /* hs_pssm_seq_scan*: the (profile, sequence) rows the call found (its *n_out) */
   uint64_t pssm_count_sites;   /* hs_pssm_hit_counts*: the sites counted, the sum of used[] */
   uint64_t pssm_count_items;   /* hs_pssm_hit_counts*: the (profile run, chunk) work items of the counting kernel */
+  uint64_t pssm_rank_sample;   /* hs_pssm_rank*: the sample size n_s = min(n, HS_OPT_PSSM_RANK_SAMPLE) the call used */
+  uint64_t pssm_rank_retries;  /* hs_pssm_rank*: the sum of rounds[]: profiles times the extra rounds they took */
   uint64_t pssm_topk_sample;   /* hs_pssm_topk*: the sample size n_s = min(n, HS_OPT_PSSM_TOPK_SAMPLE) the call used */
   uint64_t pssm_topk_raised;   /* hs_pssm_topk*: profiles scanned at a threshold above their floor (t_used > floor) */
 } hs_profile;
@@ -208,6 +210,8 @@ typedef enum hs_option {
                                 262144 = 2^18; the index's size where it is smaller).  Shows in t_used only, never in a row */
   HS_OPT_PSSM_COUNT_CHUNK = 25, /* hs_pssm_hit_counts: sites per work item of the counting kernel (1 .. 2^20); 0 (default):
                                 a batch's sites / 4096, within 256 .. 2048.  Never shows in a count */
+  HS_OPT_PSSM_RANK_SAMPLE = 26, /* hs_pssm_rank: k-mers of the index the sample pass scores per profile (>= 1, default
+                                262144 = 2^18; the index's size where it is smaller).  Shows in t_scan and rounds only */
   HS_OPT_JOIN_XCD_RUN = 16  /* hs_join8x_kernel's work items dealt in runs of this many chunks per XCD, each XCD's
                                 waves on their own runs (a run's items stream the same query tiles: one L2 fetches
                                 them instead of eight).  0: one counter for the chip; -1 (default): by the size
@@ -1317,8 +1321,8 @@ HS_API hs_status hs_pssm_seq_hits(const uint32_t* m, const uint32_t* id, const d
  * (S_i on convergence at i, else S_{n_iter}); counts, used (may be NULL): of the last scan; *iters: the scans run, not
  * counting the background's; *converged.  If it converged, hs_pssm_hit_counts(S_out, t) gives counts.  Per iteration
  * only counts (down) and S (up) cross PCIe.  Nothing is written when the arguments or S0's values are refused.
- * Out of scope: sequence weighting, a device log-odds (device log2 is not the host's bit for bit), a threshold update
- * rule, multi-GPU drivers (hs_pssm_count_hits is the merge). */
+ * Out of scope: sequence weighting, a device log-odds (device log2 is not the host's bit for bit), multi-GPU drivers
+ * (hs_pssm_count_hits is the merge).  (A threshold update rule: hs_pssm_refine_rank below.) */
 HS_API hs_status hs_pssm_hit_counts(hs_handle* h, const double* S, const double* t, uint64_t nm,
                                     const uint64_t* id_start, uint64_t n_seq, uint32_t* counts, uint64_t* cnt,
                                     uint64_t* used, uint64_t* n_hits);
@@ -1346,6 +1350,67 @@ HS_API hs_status hs_pssm_log_odds(const uint32_t* counts, uint64_t nm, uint32_t 
 /* bg[a] = (the sum over p of counts_row[p][a]) / (the sum over p and a) for the counts [k][alphabet] of one profile; a
  * zero is then replaced by the smallest positive entry, without renormalising.  All-zero counts: HS_ERR_INVALID. */
 HS_API hs_status hs_pssm_background(const uint32_t* counts_row, uint32_t k, uint32_t alphabet, double* bg_out);
+
+/* ---- PSSM rank: the threshold that admits a profile's N best k-mers ---------------------------------------------- */
+
+/* Every profile call above takes t [nm] in the units of the scores, and nobody has such a number for a log-odds matrix.
+ * This is the order statistic: for each profile the exact score of its rank-th best k-mer over the whole index, for any
+ * rank from 1 to n, found on the device.  "The 10 000 best windows" becomes a t that every call above accepts.
+ *
+ * Inputs: S [nm][k][alphabet] as for hs_pssm_scan, with the same value checks; rank [nm], each within 1 .. n.
+ * Score: hs_pssm_scan's, bit for bit -- from +0.0, left to right, every sum rounded to fp64.
+ * t_rank[m]: the rank[m]-th largest score of profile m over the index's n k-mers, counted with multiplicity: the bits
+ * of a score that occurs.  cnt_ge[m]: the k-mers with score >= t_rank[m]; at least rank[m], larger where scores tie at
+ * the threshold; hs_pssm_scan at t_rank returns exactly cnt_ge[m] hits for profile m.  cnt_gt[m]: the k-mers with score
+ * > t_rank[m]; below rank[m].  t_scan [nm], rounds [nm] (either may be NULL): diagnostics defined by the sample rule
+ * below, and the only outputs that depend on the sample size.
+ * Errors, reported before anything is written: everything hs_pssm_scan refuses about the handle, nm and S; a null rank,
+ * t_rank, cnt_ge or cnt_gt with nm > 0; a rank of 0 or above n (with n == 0 and nm > 0 every rank is refused).  The
+ * _dev form finds the value errors on the device with one read-back.  nm == 0 is HS_OK with nothing written.
+ * Purity: t_rank, cnt_ge and cnt_gt are a pure function of (codes, S, rank).  HS_OPT_PSSM_RANK_SAMPLE,
+ * HS_OPT_QUERY_BATCH, HS_OPT_PSSM_FILTER, survivor splits, scheduling and the number of rounds do not show in them.
+ *
+ * How, and why it is exact (hsearch_amd/csrc/hs_pssm_rank.hip; the rule in integers: hs_pssm_rank.h).  The N-th best of
+ * a sample bounds nothing above the sample's own rank, so the sample only proposes a threshold and the scan's hit count
+ * disposes.  n_s = min(n, HS_OPT_PSSM_RANK_SAMPLE); the sample is hs_pssm_topk's, the k-mers floor(j * n / n_s).
+ * q = ceil(rank * n_s / n), slack0 = 4 * ceil(sqrt(q)) + 8, and in round j = 0, 1, ... the sample rank is r_s = q +
+ * slack0 * 4^j (n_s == n: r_s = rank, round 0 is final).  t_scan = the r_s-th largest sample score, -DBL_MAX (every
+ * k-mer) once r_s > n_s.  A round scans the unresolved profiles at t_scan with hs_pssm_scan's tables, filter and exact
+ * pass; a profile is resolved iff its hits number at least rank[m] -- then every k-mer at or above the true t_rank is
+ * among them and a segmented radix select over their keys is exact.  The others go to round j + 1; the round at
+ * -DBL_MAX resolves everything.  t_scan[m] and rounds[m] report the round that resolved profile m (rounds counts the
+ * retries: 0 for the first round).  A retry reruns the batches with the resolved profiles at +DBL_MAX.
+ * The constant 8 and the sample's grain make small ranks cost several times their size in hits: ranks up to 64 are
+ * hs_pssm_topk's business.
+ * hs_profile after the call: the pssm_* scan fields and hits summed over every scan the call ran; pssm_rank_sample,
+ * pssm_rank_retries; ms_hash (sample pass + its select), ms_verify (tables + filter), ms_finalize (exact pass +
+ * select), ms_total.  Every other entry point runs as before, launch for launch.
+ * Out of scope: per-protein ranks, thresholds from a null model, multi-GPU drivers -- ranks do NOT merge from per-GPU
+ * thresholds (the rank-th best of a union is no function of the parts' rank-th bests). */
+HS_API hs_status hs_pssm_rank(hs_handle* h, const double* S, const uint64_t* rank, uint64_t nm, double* t_rank,
+                              uint64_t* cnt_ge, uint64_t* cnt_gt, double* t_scan, uint32_t* rounds);
+/* ... every pointer in device memory (streams: as hs_pssm_scan_dev) */
+HS_API hs_status hs_pssm_rank_dev(hs_handle* h, const double* d_S, const uint64_t* d_rank, uint64_t nm,
+                                  double* d_t_rank, uint64_t* d_cnt_ge, uint64_t* d_cnt_gt, double* d_t_scan,
+                                  uint32_t* d_rounds);
+/* The same rule on the host (no GPU, no handle): every (profile, k-mer) pair scored under the contract over codes
+ * [n][k], and the selection.  The refusals above, and k == 0, alphabet outside 1 .. 32, a code >= alphabet, n >= 2^32,
+ * nm >= 2^27, null codes with n > 0: HS_ERR_INVALID with nothing written.  The answer for an index that is on no GPU. */
+HS_API hs_status hs_pssm_rank_scores(const uint8_t* codes, uint64_t n, uint32_t k, uint32_t alphabet, const double* S,
+                                     uint64_t nm, const uint64_t* rank, double* t_rank, uint64_t* cnt_ge,
+                                     uint64_t* cnt_gt);
+/* The sample rule: *sample_rank = r_s of `round`, n_s + 1 where r_s lies beyond the sample (scan at -DBL_MAX).  rank
+ * outside 1 .. n, n_s outside 1 .. n, n >= 2^32 and a null output are HS_ERR_INVALID. */
+HS_API hs_status hs_pssm_rank_plan(uint64_t rank, uint64_t n, uint64_t n_s, uint32_t round, uint64_t* sample_rank);
+/* hs_pssm_refine's loop, rules, refusals and outputs with one change: iteration i first computes t_i = hs_pssm_rank(S_i,
+ * rank) and then C_i = hs_pssm_hit_counts(S_i, t_i), so the hit count stays at rank (and its ties) while the matrix
+ * moves.  rank [nm], each within 1 .. n; t_out [nm]: the threshold of the last scan.  Convergence is still C_i ==
+ * C_{i-1} byte for byte.  used may exceed rank (ties at the threshold); in the one-per-protein mode (id_start given)
+ * rank still counts k-mers, not proteins, so used is then at most cnt_ge.  An iteration is two scans. */
+HS_API hs_status hs_pssm_refine_rank(hs_handle* h, const double* S0, const uint64_t* rank, uint64_t nm,
+                                     const uint64_t* id_start, uint64_t n_seq, const double* bg, double pseudo,
+                                     uint32_t n_iter, double* S_out, double* t_out, uint32_t* counts, uint64_t* used,
+                                     uint32_t* iters, uint32_t* converged);
 
 /* Replaces Clustering() (hclust2.cpp:86-151) with explicit planes a[L][K][d], b[L][K]: table by
  * table, an LSH table over the not-yet-absorbed k-mers, then greedy leader clustering inside every
