@@ -11,6 +11,9 @@
 //     dir_key   [nb]        u64  sorted fingerprints of the distinct HashKey strings
 //     dir_start [nb+1]      u32  bucket boundaries
 //     dir_tuple [nb][K]     i32  bucket ints of each bucket (exact string check at probe time)
+//
+// struct hs_handle, its member types, HS_HIP / HS_CHECK and filter_passes: hs_handle.h.  The profile calls
+// (hs_pssm_*): hs_capi_pssm.hip.
 #include <math.h>
 #include <random>
 #include <string.h>
@@ -21,366 +24,37 @@
 #include <vector>
 
 #include "../../include/hs_tables.h"
-#include "hs_internal.h"
+#include "hs_handle.h"
 #include "hs_table_append.h"
 #include "hs_table_remove.h"
-#include "hs_pssm_tables.h"
-#include "hs_pssm_seq.h"
-#include "hs_pssm_counts.h"
-#include "hs_pssm_topk.h"
-#include "hs_pssm_rank.h"
 
-namespace {
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T>
-  T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-// host staging kept across calls (pageable: page-locking 40 MB took longer than a whole
-// Clustering() of 10^6 k-mers; what is saved is the fresh allocation + page faults per call)
-struct HostBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    free(p);
-    cap = 0;
-    p = malloc(bytes);
-    if (!p) return hipErrorOutOfMemory;
-    memset(p, 0, bytes);  // touch the pages here: a device -> host copy into untouched pages crawls
-    cap = bytes;
-    return hipSuccess;
-  }
-  void release() {
-    free(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T>
-  T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-enum { EV_COUNT = 12 };
-enum { EV_FORK = 0, EV_JOIN = 1, EVX_COUNT = 2 };
-
-// Switches of a handle (hs_set_option, include/hsearch.h; read_knobs for the few that come from the
-// environment).  None of them changes a result: each forces one of several equivalent paths (the tests run
-// both and compare), sizes a batch, or prints a diagnostic.  Fault injection (HS_TEST_SPLIT_ABOVE) exists only
-// in the test build of the library (-DHS_TEST_HOOKS: libhsearch_amd_hooks.so), never in libhsearch_amd.so.
-struct Knobs {
-  bool build_serial = false;       // HS_OPT_BUILD_SERIAL: no hash / sort overlap in the build (measurement)
-  int join_xcd_run = -1;           // HS_OPT_JOIN_XCD_RUN: chunks per XCD-local run of join items (0 off, -1 auto)
-  bool no_probe_records = false;   // HS_OPT_PROBE_RECORDS = 0: the probe reads the directory arrays, not the records
-  uint32_t join_chunk = 0;         // HS_OPT_JOIN_CHUNK: items per counter access of hs_join8x_kernel (0: by itself)
-  bool build_debug = false;        // HS_BUILD_DEBUG: say when a table is sorted a second time; hs_index_append: its stages' host time
-  bool cluster_timing = false;     // HS_CLUSTER_TIMING: phase times of hs_self_join_range on stderr
-  bool debug_refine = false;       // HS_DEBUG_REFINE: survivor counts per batch on stderr
-  bool force_wide = false;         // HS_OPT_WIDE_ROWS = 1: 8-column rows whatever the radius (k <= 25)
-  bool no_wide_by_radius = false;  // HS_OPT_WIDE_ROWS >= 2: never choose 8-column rows by radius
-  bool no_refine8 = false;         // HS_OPT_REFINE8 = 0: no 8-column refinement of the join's survivors
-  bool no_join_f6 = false;         // HS_OPT_JOIN_F6 = 0: k-mer queries never through the FP6 join (hs_join6.hip)
-  bool no_pssm_filter = false;     // HS_OPT_PSSM_FILTER = 0: hs_pssm_scan sends every pair to the exact pass (hs_pssm.hip)
-  bool no_self_codes = false;      // HS_OPT_SELF_CODES = 0: self-join from embedded centres, not from codes
-  bool sort_hits = false;          // HS_OPT_SORT_HITS: order hits by the radix sort, not per query
-  bool sync_items = false;         // HS_OPT_SYNC_ITEMS: read the join's item count back before launching it
-  bool no_join_r = false;          // HS_OPT_JOIN_RESIDENT = 1: every segment through the query-streaming join kernel
-  bool no_recognise = false;       // HS_OPT_RECOGNISE_KMERS = 0: centres that are k-mers are not looked for (run_query)
-  bool force_join_r = false;       // HS_OPT_JOIN_RESIDENT = 2: the query-resident kernel for its class whatever its share
-  bool build_sort = false;         // HS_OPT_BUILD_GROUPING = 1: group a table's k-mers by sorting (fingerprint, id) pairs
-                                   // (rocPRIM; rounds 1-2) instead of hs_group.hip's table + rank sort
-  int seg_mode = 0;                // HS_OPT_SEG_MODE: 1 sparse / 2 dense; 0 = by the bucket : probe ratio
-  int sort_from_bit = 16;          // HS_OPT_SORT_FROM_BIT: lowest fingerprint bit the build's sort looks at
-  uint32_t query_batch = 0;        // HS_OPT_QUERY_BATCH: queries per batch (0: by L and the free HBM)
-  uint32_t pssm_topk_sample = 262144;  // HS_OPT_PSSM_TOPK_SAMPLE: k-mers the sample pass of hs_pssm_topk scores per profile
-  uint32_t pssm_rank_sample = 262144;  // HS_OPT_PSSM_RANK_SAMPLE: k-mers the sample pass of hs_pssm_rank scores per profile
-  uint32_t pssm_count_chunk = 0;   // HS_OPT_PSSM_COUNT_CHUNK: sites per work item of hs_pssm_counts.hip (0: by the batch)
-  uint32_t summary_chunk = 0;      // HS_OPT_SUMMARY_CHUNK: member slots per work item of hs_summary.hip (0: 512)
-  uint32_t summary_rows = 0;       // HS_OPT_SUMMARY_ROWS: rows per batch of hs_cluster_profile (0: by the scratch budget)
-  int64_t msf_edge_budget = -1;    // HS_OPT_MSF_EDGE_BUDGET: bytes of HBM hs_msf may keep pairs in (0 never, -1 a share of the free)
-#ifdef HS_TEST_HOOKS
-  uint32_t test_split_above = 0;   // HS_TEST_SPLIT_ABOVE: batches above this size report a survivor overflow
-  bool test_group_fallback = false;  // HS_TEST_GROUP_FALLBACK: the build's fingerprint table reports itself full
-  bool test_append_collision = false;  // HS_TEST_APPEND_COLLISION: hs_index_append's match step reports a collision
-  bool test_remove_reseed = false;     // HS_TEST_REMOVE_RESEED: hs_index_remove treats the index's seed as non-zero
-#endif
-};
-
-// What becomes of a batch's hits once the batch has come through whole (run_query, reduce_batch).  LIST: ordered and
-// handed out in the call's output arrays.  Every other sink reduces them where finalize_hits leaves them -- no
-// ordering, no output arrays (cap = 0), no capacity verdict:
-//   ANNOTATE   hs_annotate: the nearest centre per DB id (annot_reduce)
-//   CC_UNION   hs_components: a self-join's pairs united in the handle's union-find forest
-//   DB_DEGREE  hs_degrees / hs_dbscan pass 1 (hs_dbscan.hip): a self-join's pairs counted into the degree array
-//   DB_UNITE   hs_dbscan pass 2: the degrees known, the pairs united and anchored at min_pts
-//   MSF_MIN_D, MSF_MIN_PAIR   hs_msf (hs_msf.hip): steps 1 and 2 of a Boruvka round over a self-join's pairs
-//   MSF_COLLECT               hs_msf's first pass: step 1, and the pairs appended to the list kept in HBM
-//   DT_CORE, DT_CORE_COLLECT  hs_core_distance / hs_density_tree (hs_density.hip): the core pass -- the threshold
-//                             rounds over the batch's hits at min_pts; COLLECT: and the pairs appended to the kept list
-//   DT_MIN_D, DT_MIN_PAIR     hs_density_tree: steps 1 and 2 of a Boruvka round under the mutual-reachability weight
-//   TOPK       hs_query_topk / hs_self_knn (hs_knn.hip): per query of the batch the topk smallest hits under (dist, id),
-//              written as rows row0 + (the query's number in the call) of the four device arrays (topk_reduce)
-//   SEQ_MATCH  hs_seq_match (hs_seqmatch.hip): the batch's hits reduced per (query group, sequence, diagonal) and the
-//              rows appended to the handle's list (seq_reduce); the list is reduced once more at the end of the call
-struct SeqMatchCall {
-  const uint32_t* q_group = nullptr;  // device; null: a query is its own group
-  const uint32_t* q_off = nullptr;    // device; null: no diagonals
-  const uint64_t* id_start = nullptr; // device, [n_seq + 1]
-  uint64_t n_groups = 0, n_seq = 0, max_qoff = 0;
-  int wg = 0, ws = 0, wd = 0;         // the key's field widths (include/hsearch.h)
-};
-
-struct HitSink {
-  enum Kind { LIST, ANNOTATE, CC_UNION, DB_DEGREE, DB_UNITE, MSF_MIN_D, MSF_MIN_PAIR, MSF_COLLECT, DT_CORE,
-              DT_CORE_COLLECT, DT_MIN_D, DT_MIN_PAIR, TOPK, SEQ_MATCH } kind = LIST;
-  uint32_t min_pts = 1;
-  uint32_t topk = 0;
-  uint64_t row0 = 0;
-  uint32_t* nn_id = nullptr;
-  uint32_t* nn_table = nullptr;  // (may stay null)
-  double* nn_dist = nullptr;
-  uint32_t* nn_count = nullptr;
-  const SeqMatchCall* sm = nullptr;
-};
-
-// One query call's queries and what it asks (run_query, query_batch, probe_tabs)
-struct QueryCall {
-  const double* centers = nullptr;
-  const uint8_t* codes = nullptr;  // queries given as residue codes [nq][k] (hs_query_codes); centers unused
-  double R = 0.0;                  // with radii: the largest |radii[q]| of the call, what plan_batch decides from
-  bool brute = false;
-  uint32_t self_first = HS_NO_SELF;  // self-join: DB id of query 0
-  bool sqrt_test = false;            // hit test sqrt(d2) <= R (hclust2.cpp:119-120) instead of d2 <= R*R
-  // multi-probe (mp_query): every row is one probe of a query, its bucket ints given ([nq][L][K], device) in
-  // place of the hash, and pre_valid[q L + l] == 0 an empty probe
-  const int32_t* pre_ints = nullptr;
-  const uint8_t* pre_valid = nullptr;
-  // hs_query_radii: every query's own radius ([nq], device); null: R for all.  Searches and brute force only.
-  const double* radii = nullptr;
-  HitSink sink;
-};
-
-// What a handle learns from its batches to steer the next ones (plan_batch, the join launch); written by
-// learn_from_batch alone, forgotten with the index (drop_index)
-struct BatchHistory {
-  // work items of the last joined batch x 1.25: with it the next batch sizes its descriptor array
-  // without asking the device (the kernels clamp to the real count; an overflow repeats the batch)
-  uint32_t item_cap_hint = 0;
-  double pairs_per_item = 0.0;  // average of the previous batch's join work items (0: none yet)
-  // share of the last joined batch's work items that lay in segments with few probing queries (the
-  // query-resident kernel's class); < 0: unknown.  That kernel pays when the class is the bulk of the items
-  // (configs[2]'s shape: 90 %); where it is a minority (configs[1]: the extra launch costs more than the
-  // class's items cost in the streaming kernel) the next batch runs everything through the streaming kernel
-  double resident_share = -1.0;
-  uint32_t resident_age = 0;  // joined batches since it was measured (measured again every 64)
-  uint32_t resident_nq = 0;   // ... on a batch of this many queries (a batch half / twice that size measures anew)
-  // the last batch that ordered its hits itself had to fall back to the sort, at this radius (NaN after a
-  // batch with per-query radii: such a batch neither leaves a radius to match nor matches one)
-  bool order_failed = false;
-  double order_failed_R = 0.0;
-};
-
-}  // namespace
-
-struct hs_handle {
-  hs_params p;
-  int d = 0, LK = 0, PW = 0, alphabet = HS_ALPHABET;
-  int n_cu = 256;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[EV_COUNT];
-  bool ev_ok = false;
-  // side stream: the streaming filter (and its per-query tables) runs beside the bucket join
-  hipStream_t stream2 = nullptr;
-  hipEvent_t evx[EVX_COUNT];
-  bool evx_ok = false;
-  DevBuf a, b, coords;
-  DevBuf aT;  // the planes transposed, [d][L*K]: what the hash kernels read
-  // index
-  bool built = false;
-  uint64_t n = 0;
-  uint32_t key_seed = 0;
-  DevBuf codes, packed_all;
-  DevBuf t_dirkey[HS_MAX_L], t_dirstart[HS_MAX_L], t_dirtuple[HS_MAX_L], t_ids[HS_MAX_L];
-  DevBuf t_dirjump;  // the jump tables of all directories, one allocation (a table's at its own offset)
-  DevBuf t_dirrec;   // the directory records of all tables (hs_table_dev::dir_rec), 64 bytes per bucket
-  DevBuf part_work;  // bucket partition: flags, positions, compacted (bucket, probe) pairs of a batch
-  DevBuf t_giant;    // the fingerprints of every table's giant buckets (hs_table_dev::giant_key), ascending
-  uint32_t bucket_part = 0, bucket_parts = 1;  // hs_set_bucket_partition
-  // bucket-ordered packed copies of all tables in ONE allocation ([L][n][PW]), and the int8 join's
-  // per-entry records ([L][n], k <= 50 only) at the same entry numbers
-  DevBuf t_packed, t_rec8;
-  // the records once more in four bytes per entry ([L][n]; k <= 25 with 4-column rows: what the
-  // query-resident join kernel reads instead of t_rec8 -- it is bound by the bytes it moves per member)
-  DevBuf t_rho;
-  DevBuf hit_kv;     // query_batch: the hits bucketed by query, (key, value) side by side
-  DevBuf hit_rank;   // query_batch: a hit's number among its query's hits (ordering without a sort)
-  DevBuf qpacked;    // query_batch: queries given as k-mers, packed like the members (exact pass)
-  DevBuf rec_codes;  // run_query: the residue codes of centres that turned out to be k-mers (+ the counter)
-  // member records of the wide rows for k = 21..25 (built when a call's radius first asks for them)
-  DevBuf t_rec8w;
-  bool rec8w_ready = false;
-  // the FP6 join (hs_join6.hip): its tables, and the member records (16 bytes per entry and table), built on the
-  // first batch that can use them; rec6_state: 0 not built, 1 ready, -1 no room for them (int8 join for this index)
-  DevBuf jtab6, t_rec6;
-  int rec6_state = 0;
-  bool join6_tables_ok = false;
-  double pair4_mean = 0.0, pair4_var = 0.0;  // 4-column squared distance of two random residues
-  DevBuf t_pos;  // [L][n] sorted position of every DB id in every table (first-seen dedupe)
-  DevBuf dir_base;       // [L + 1] first global bucket number of every table; [L] = nb_total
-  uint32_t nb_total = 0;  // buckets of all tables
-  DevBuf bucket_work;    // per-batch: counts + their 64-bit double scan over the nb_total + 2 bucket slots
-  hs_tables_dev tabs;
-  hs_index_info info;
-  // query workspace (grown on demand, reused across calls)
-  DevBuf qints, qstart, qcount, nslices, slice_off, tq, prov, hit_key, hit_val, hit_key2, hit_val2,
-      counters, temp, io_centers, io_q, io_id, io_table, io_dist, io_cand, io_codes, io_misc;
-  // multi-probe (hs_set_multiprobe): extra probes per table; a chunk's exact projections and fractions, its
-  // probes' bucket ints and flags, its queries once per probe, the probe rows' hits and candidate counts
-  uint32_t mp_T = 0;
-  uint64_t mp_room = 0;
-  DevBuf mp_pts, mp_codes, mp_ints, mp_frac, mp_vints, mp_valid, mp_rows, mp_q, mp_id, mp_table, mp_dist, mp_cand;
-  DevBuf mp_radii;   // ... and, for a call with per-query radii, the probe rows' radii
-  // hs_annotate (hs_annotate.hip): smallest distance and its (table, q) per DB id, the ids touched by the call and
-  // their count, the touched ids sorted.  ann_clean: slots [0, ann_clean) of ann_dist are known to be empty;
-  // ann_open: a call is (or ended early while) reducing -- the next one empties all slots first
-  DevBuf ann_dist, ann_tq, ann_touched, ann_sorted, ann_cnt;
-  uint64_t ann_clean = 0;
-  bool ann_open = false;
-  // hs_components (hs_components.hip): the union-find forest over the indexed k-mers (parent[x] <= x), the
-  // call's two 64-bit counts {ordered pairs, roots}, and the labels of a host-pointer call on their way out
-  DevBuf cc_parent, cc_cnt, cc_label;
-  // hs_degrees / hs_dbscan (hs_dbscan.hip): the degree and the smallest core neighbour per indexed k-mer (the forest
-  // is cc_parent: every call starts it from the identity), and the call's five 64-bit counts
-  DevBuf db_deg, db_anchor, db_cnt;
-  // hs_msf (hs_msf.hip: the state listed at its head; the forest is cc_parent): the components of the round, the two
-  // slots per component, the tree edges and their sorted copy, the call's counts; the list of pairs kept in HBM, the
-  // entries the call may keep (HS_OPT_MSF_EDGE_BUDGET) and whether the list could not grow to hold a batch
-  DevBuf msf_comp, msf_best_d, msf_best_pair, msf_out_pair, msf_out_d, msf_s_pair, msf_s_d, msf_cnt, msf_kept;
-  uint64_t msf_kept_budget = 0;
-  bool msf_kept_failed = false;
-  // hs_core_distance / hs_density_tree (hs_density.hip: the state listed at its head; the rest is hs_msf's): the core
-  // distance bits, the threshold and the round's minimum per indexed k-mer, the neighbours counted
-  DevBuf dt_core, dt_thr, dt_next, dt_cnt;
-  // hs_query_topk / hs_self_knn (hs_knn.hip: the scratch listed at its head, all sized by a batch): hits per query,
-  // their scan, the scatter's cursors, the call's 64-bit hit count; the counts of a host-pointer call on their way out
-  DevBuf knn_cnt, knn_off, knn_cur, knn_total, knn_io_count;
-  // hs_pssm_topk (hs_pssm_topk.hip; the selection's scratch is hs_knn.hip's): a batch's thresholds when the caller
-  // wants none; the sample pass's lists when a profile's sample is split over several workgroups
-  DevBuf pt_tused, pt_parts;
-  // hs_pssm_rank (hs_pssm_rank.hip; the hit selection's counts, offsets and cursors are hs_knn.hip's): a sub-batch's
-  // sample keys, their segment offsets, the select's state; the call's resolved flags, scan thresholds, and the word
-  // that counts a round's unresolved profiles; a host-pointer call's ranks in and outputs on their way out
-  DevBuf pr_keys, pr_off, pr_state, pr_resolved, pr_tscan, pr_unres, pr_rank, pr_out;
-  // hs_pssm_hit_counts (hs_pssm_counts.hip): a batch's sites as (m, id) words and their copies sorted on m, the
-  // profiles' run starts, chunk counts and their scan, the rows of the one-site-per-protein mode; a host-pointer
-  // call's counts, cnt and used on their way out
-  DevBuf pc_m, pc_id, pc_m2, pc_id2, pc_start, pc_nitem, pc_off, pc_rows, pc_out;
-  // hs_seq_match (hs_seqmatch.hip: the scratch listed at its head): a batch's keys and hit indices, their sorted
-  // copies, the run heads and their scan, the waves' cut runs; the call's rows so far (sq_rows of them in a list of
-  // sq_acc.cap / 40) and their final reduction; the argument check's words; a host-pointer call's arrays in and out
-  DevBuf sq_key, sq_idx, sq_skey, sq_sidx, sq_head, sq_excl, sq_part, sq_acc, sq_fin, sq_chk, sq_in, sq_out;
-  uint64_t sq_rows = 0;
-  uint32_t sq_batches = 0;
-  // hs_cluster_profile / hs_cluster_radii (hs_summary.hip: the state listed at its head), the counts of a row batch
-  // when the caller wants none, and the arrays of a host-pointer call on their way in and out
-  DevBuf sm_size, sm_tmp, sm_row_of, sm_off_of, sm_row_label, sm_row_off, sm_member, sm_d2, sm_err, sm_counts;
-  // host-pointer calls: the labels in; out, hs_cluster_profile: sm_io_a = out_label, sm_io_b = out_size, sm_io_counts,
-  // sm_io_f64 = centroid; hs_cluster_radii (centres in through io_centers, as the searches' are): sm_io_f64 = max_d2,
-  // sm_io_f64b = radius, sm_io_a = medoid
-  DevBuf sm_io_label, sm_io_a, sm_io_b, sm_io_counts, sm_io_f64, sm_io_f64b;
-  DevBuf io_radii;   // hs_query_radii: the radii on the device; hs_query_radii_dev: {max |radius|, NaN flag}
-  DevBuf qcodes_buf, qembed;  // hs_query_codes: a batch's checked copy of the query codes; their embedding
-                              // when no from-codes path applies
-  HostBuf sj_host;  // hs_self_join_range: hits of one chunk on their way to the edge lists
-  // bucket-join workspace
-  // hs_index_build_subset: the caller's whole code array, kept on the device across calls
-  DevBuf all_codes, subset_ids;
-  const uint8_t* all_codes_key = nullptr;
-  uint64_t all_codes_n = 0;
-  DevBuf bs_ints2[2], bs_keys2[2], bs_iota2[2], bs_keys_sorted, bs_rle_unique, bs_rle_counts, bs_small,
-      bs_sort_temp, bs_slow_q;  // index-build scratch (build_tables)
-  DevBuf bs_fptab, bs_blk, bs_dk, bs_hist, bs_rank;  // ... of the table + rank-sort grouping (hs_group.hip)
-  // hs_index_shard_*: the build with the hashing spread over ranks (this rank's block of the k-mers)
-  bool shard_open = false;
-  uint32_t shard_lo = 0, shard_cnt = 0, shard_seed = 0, shard_nb = 0;
-  int shard_table = -1;
-  DevBuf seg_of;    // query_batch: the segment of every sorted probe position
-  DevBuf seg_res;   // cut_items: the scan of the segments' class flags (many queries | query-resident kernel)
-  DevBuf c16s, item_desc, probe_slow, jtab8, qhits;  // qhits: per-query hit counts, offsets, fill
-  DevBuf c8b, prov2;  // survivor refinement: second int8 row per query, the refined survivor list
-  bool join8_tables_ok = false;  // int8 can carry the coordinate table
-  double join8_scale = 0.0, join8_scale_w = 0.0;  // quantisation scales: 4-column rows, wide rows
-  bool wide8_ok = false;         // the 8-column table is usable (wide rows on demand for k = 21..25)
-  uint32_t* pin_cnt = nullptr;   // HS_CNT_WORDS pinned words: where a pass's counter block lands, in one copy (small
-                                 // device -> host copies into PAGEABLE memory cost ~ 50 us of host staging per batch)
-  BatchHistory hist;
-  Knobs knobs;
-  bool wide8 = false;            // short k-mers: int8 rows over all 8 coordinate columns (hs_join8.hip)
-  // segment routing thresholds (HS_JOIN_MIN_Q / _M): segments with fewer probing queries or members
-  // go to the per-pair filters instead of the join.  1 / 1 = everything through the join: its
-  // persistent waves leave no room for a kernel beside it, and the per-pair filter run before it
-  // cost 0.3 ms at C2 (a chain of dependent loads per probe) against 0.06 ms of extra join time
-  uint32_t join_min_q = 1, join_min_m = 1;
-  int join_blocks_per_cu = 2;                // resident workgroups of hs_join_kernel per CU
-  DevBuf jtab, c16, seg_keys, seg_keys_sorted, seg_vals, sorted_ql, seg_key, seg_cnt, seg_qoff,
-      seg_items, item_off, seg_n;
-  // projection on the matrix cores (hs_proj.hip): quantised planes in both tilings, per-function
-  // constants, the quantised coordinate table, flag lists (0/1: the two tables in flight during a
-  // build, 2: queries and the hash entry points) and their counters {reserved, real} x 3
-  int proj_S = 0;               // k-steps the MFMA pass is compiled for (0: k too long)
-  bool proj_usable = false;     // S > 0 and the buffers below are filled for the current planes
-  bool proj_auto = false;       // ... and the error bound is narrow enough for the auto mode
-  int hash_mode = 0;            // 0 auto, 1 exact fp64 kernel, 2 MFMA pass wherever usable
-  double proj_eps_scale = 1.0;
-  double proj_est = 0.0;        // typical half-width of the bound, in bucket units
-  DevBuf proj_aq_all, proj_aq_tab, proj_fn, proj_tab, proj_stats, proj_flags[3], proj_cnt, proj_xq, proj_xmeta;
-  bool join_tables_ok = false;  // fp16 can carry the coordinate table
-  int verify_mode = 0;          // 0 auto, 1 streaming kernel, 2 bucket join
-  std::string err;
-  hs_profile prof;
-};
-
-namespace {
-
+// (declared in hs_handle.h: hs_capi_pssm.hip calls these four too)
 hs_status fail(hs_handle* h, hs_status st, const std::string& msg) {
   if (h) h->err = msg;
   return st;
 }
-
-#define HS_HIP(h, expr)                                                                      \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess)                                                                    \
-      return fail(h, e_ == hipErrorOutOfMemory ? HS_ERR_NOMEM : HS_ERR_HIP,                  \
-                  std::string(#expr) + ": " + hipGetErrorString(e_));                        \
-  } while (0)
-#define HS_CHECK(expr)                \
-  do {                                \
-    hs_status st_ = (expr);           \
-    if (st_ != HS_OK) return st_;     \
-  } while (0)
 
 float ev_ms(hs_handle* h, int i0, int i1) {
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, h->ev[i0], h->ev[i1]) != hipSuccess) return 0.f;
   return ms;
 }
+
+hs_status ensure_device(hs_handle* h) {
+  HS_HIP(h, hipSetDevice(h->p.device));
+  return HS_OK;
+}
+
+// The pinned words a pass's counter block lands in (small device -> host copies into pageable memory cost ~ 50 us
+// per batch)
+hs_status ensure_pin_cnt(hs_handle* h) {
+  if (h->pin_cnt) return HS_OK;
+  HS_HIP(h, hipHostMalloc(reinterpret_cast<void**>(&h->pin_cnt), HS_CNT_WORDS * 4, hipHostMallocDefault));
+  memset(h->pin_cnt, 0, HS_CNT_WORDS * 4);
+  return HS_OK;
+}
+
+namespace {
 
 // smallest float >= x (x >= 0), then one more ulp: the fp32 filter bound must never undercut.
 float filter_bound(double r2) { return hs_filter_bound(r2); }
@@ -397,11 +71,6 @@ void drop_index(hs_handle* h) {
 
 // Queries per batch at most: the probe numbers (query x table) carry a flag in bit 31
 uint32_t max_query_batch(const hs_handle* h) { return (uint32_t)((1ull << 31) / h->p.L) - 1; }
-
-hs_status ensure_device(hs_handle* h) {
-  HS_HIP(h, hipSetDevice(h->p.device));
-  return HS_OK;
-}
 
 
 // The device code of the library's kernels -- rocPRIM's sort / scan / run-length kernels in
@@ -1033,14 +702,6 @@ hs_status hs_hash_points(hs_handle* h, const double* points, uint64_t n, int32_t
   return hash_account(h, n, h->LK, 2);
 }
 
-static inline int bit_width_u32(uint32_t v) {
-  int b = 0;
-  while (v) {
-    ++b;
-    v >>= 1;
-  }
-  return b;
-}
 // bits of a sorted position inside one table (segment keys: hs_launch_seg_keys)
 static inline int seg_shift_of(const hs_handle* h) {
   return std::max(1, bit_width_u32((uint32_t)std::min<uint64_t>(h->n, 0xffffffffull)));
@@ -2980,13 +2641,6 @@ struct BatchOut {
   bool ordered = false;
 };
 
-// Counters block (h->counters): [0] prov_count u32, [1] hit_count u32, [2..3] cand_total u64, ...,
-// [20] hits not ordered on the device, [21] HS_CNT_SURVIVOR_OVERFLOW, [32] the join's item counter.
-// Internal status: the batch's filters passed more pairs than the 32-bit survivor counter holds.
-static const hs_status HS_SPLIT_BATCH = (hs_status)1000;
-// Internal status: a batch that left its item count on the device found it over the capacity hint, or a
-// query row the join cannot carry; the batch runs again with the count read back first.
-static const hs_status HS_SYNC_ITEMS = (hs_status)1001;
 // Wide int8 rows (all 8 coordinate columns) for this call?  Always for short k-mers (the index's
 // member records are wide then).  For k = 21..25 when the radius is large for the k-mer length: the
 // 4-column squared distance of two random k-mers is ~ N(k m, k v) (m, v: one residue pair), and once
@@ -3566,85 +3220,6 @@ static hs_status search_pass(hs_handle* h, const QueryCall& c, const BatchPlan& 
   // fallback, [HS_CNT_PROJ] the projection of the queries, [HS_CNT_SPLIT] first item of the few-query class and
   // the items -- under async_items the real item count -- both written there by their kernels
   HS_HIP(h, hipMemcpyAsync(h->pin_cnt, d_cnt, HS_CNT_WORDS * 4, hipMemcpyDeviceToHost, h->stream));
-  return HS_OK;
-}
-
-// The pinned words a pass's counter block lands in (small device -> host copies into pageable memory cost ~ 50 us
-// per batch)
-static hs_status ensure_pin_cnt(hs_handle* h) {
-  if (h->pin_cnt) return HS_OK;
-  HS_HIP(h, hipHostMalloc(reinterpret_cast<void**>(&h->pin_cnt), HS_CNT_WORDS * 4, hipHostMallocDefault));
-  memset(h->pin_cnt, 0, HS_CNT_WORDS * 4);
-  return HS_OK;
-}
-
-// The survivor-capacity loop of a batch: pass(prov_cap, hit_cap, again) issues the filters and the exact
-// decision, recording ev[3] / ev[4] / ev[5] around them (ev[11] .. ev[10] around the join when join_timed), and
-// the counters' read-back; it runs again with a longer survivor list while the filters pass more than the
-// list holds.  item_cap > 0: the batch left its item count on the device with room for that many items.
-// On success: the timings, the survivors and the hit count (*n_hits) accounted.
-extern "C++" template <class Pass>
-static hs_status filter_passes(hs_handle* h, uint32_t nq, uint32_t item_cap, bool join_timed, uint32_t* n_hits,
-                               Pass pass) {
-  uint32_t* const d_cnt = h->counters.as<uint32_t>();
-  uint32_t prov_cap = (uint32_t)std::max<size_t>(h->prov.cap / 8, std::max<size_t>(1u << 20, 16ull * nq));
-  HS_CHECK(ensure_pin_cnt(h));
-  const uint32_t* const host_cnt = h->pin_cnt;
-  memset(h->pin_cnt, 0, HS_CNT_WORDS * 4);
-  double ms_verify = 0, ms_final = 0, ms_join = 0;
-  uint32_t launches = 0;
-  for (;;) {
-    HS_HIP(h, h->prov.reserve((size_t)prov_cap * 8));
-    const uint32_t hit_cap = (uint32_t)std::max<size_t>(h->hit_key.cap / 8, prov_cap);
-    HS_HIP(h, h->hit_key.reserve((size_t)hit_cap * 8));
-    HS_HIP(h, h->hit_val.reserve((size_t)hit_cap * 8));
-    // (first pass: both callers have just cleared all the counters)
-    if (launches) HS_HIP(h, hipMemsetAsync(d_cnt, 0, 8, h->stream));
-    HS_CHECK(pass(prov_cap, hit_cap, launches != 0));
-    HS_HIP(h, hipStreamSynchronize(h->stream));
-    // > ~4e9 survivors: run_query halves the batch (HS_TEST_SPLIT_ABOVE=n: as if every batch of more
-    // than n queries had overflowed -- the tests' handle on the splitting logic)
-    if (host_cnt[HS_CNT_SURVIVOR_OVERFLOW]) return HS_SPLIT_BATCH;
-#ifdef HS_TEST_HOOKS
-    if (h->knobs.test_split_above && nq > h->knobs.test_split_above) return HS_SPLIT_BATCH;
-#endif
-    if (host_cnt[HS_CNT_BAD_QUERY_CODE])
-      return fail(h, HS_ERR_INVALID, "residue code outside the alphabet in the queries");
-    if (item_cap && (host_cnt[8] /* join legality */ || host_cnt[HS_CNT_SPLIT + 1] > item_cap)) return HS_SYNC_ITEMS;
-    ms_verify += ev_ms(h, 3, 4);
-    if (join_timed) ms_join += ev_ms(h, 11, 10);
-    ms_final += ev_ms(h, 4, 5);
-    ++launches;
-    if (h->knobs.debug_refine)
-      fprintf(stderr, "survivors %u -> refined %u -> hits %u\n", host_cnt[0], host_cnt[4], host_cnt[1]);
-    if (host_cnt[0] <= prov_cap) break;  // hit_count <= prov_count <= prov_cap <= hit_cap
-    // the survivor list was too short: once more with room for what the filters reported (64-bit
-    // arithmetic: the count may sit just under the overflow flag's 0xF0000000).  The six lists of the
-    // exact pass are sized from it -- 48 bytes per entry -- so beyond 2^30 entries, or when the device
-    // has no room for them, the batch is cut in halves like a counter overflow instead.
-    const uint64_t need = (uint64_t)host_cnt[0] + host_cnt[0] / 8 + 1024;
-    if (need > (1ull << 30) && nq > 1) return HS_SPLIT_BATCH;
-    if (need > 0xffffffffull) return fail(h, HS_ERR_CAPACITY, "the filter survivors of one query exceed the survivor list");
-    const uint64_t have = prov_cap;
-    prov_cap = (uint32_t)need;
-    if (nq > 1) {  // can the lists grow?  (a failed reserve keeps the old buffer's size at 0: re-reserved below)
-      const size_t bytes = (size_t)prov_cap * 8;
-      if (h->prov.reserve(bytes) != hipSuccess || h->hit_key.reserve(bytes) != hipSuccess ||
-          h->hit_val.reserve(bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        prov_cap = (uint32_t)have;
-        return HS_SPLIT_BATCH;
-      }
-    }
-  }
-  h->prof.ms_hash += ev_ms(h, 0, 1);
-  h->prof.ms_probe += ev_ms(h, 1, 2);
-  h->prof.ms_verify += ms_verify;
-  h->prof.ms_finalize += ms_final;
-  h->prof.ms_join += ms_join;
-  h->prof.verify_launches += launches;
-  h->prof.provisional += host_cnt[0];
-  *n_hits = host_cnt[1];
   return HS_OK;
 }
 
@@ -5124,7 +4699,6 @@ hs_status hs_core_distance_dev(hs_handle* h, double R, int sqrt_test, uint32_t m
 }
 
 // ---- hs_query_topk / hs_self_knn: the topk best hits per query (kernels, the rule and the passes: hs_knn.hip) ----
-static bool topk_ok(uint32_t topk) { return topk >= 1 && topk <= HS_TOPK_MAX; }
 
 // The sink of a call whose rows go to the four device arrays; the call's hit count zeroed
 static hs_status topk_begin(hs_handle* h, uint32_t topk, uint32_t* d_id, uint32_t* d_table, double* d_dist,
@@ -5719,967 +5293,6 @@ hs_status hs_cluster_radii(hs_handle* h, const uint32_t* label, uint32_t min_siz
     HS_HIP(h, hipMemcpyAsync(radius, h->sm_io_f64b.p, n_rows * 8, hipMemcpyDeviceToHost, h->stream));
     HS_HIP(h, hipMemcpyAsync(medoid, h->sm_io_a.p, n_rows * 4, hipMemcpyDeviceToHost, h->stream));
     HS_HIP(h, hipStreamSynchronize(h->stream));
-  }
-  return HS_OK;
-}
-
-// ---- hs_pssm_scan: every indexed k-mer against position-specific score matrices (kernels: hs_pssm.hip) ----
-// One batch of mb profiles (d_S, d_t: the batch's first; number m0 of the call) against the whole index: the tables
-// and the MFMA filter (or, with the filter off, nothing) and the exact pass, under filter_passes' survivor protocol.
-// On success the batch's nh hits lie unordered in hit_key / hit_val.
-static hs_status pssm_batch(hs_handle* h, const double* d_S, const double* d_t, uint32_t m0, uint32_t mb, bool filt,
-                            uint32_t* nh) {
-  const int k = (int)h->p.k;
-  const uint32_t steps = hs_pssm_steps(h->p.k, (uint32_t)h->alphabet), mb_pad = (mb + 15u) & ~15u;
-  uint32_t* const d_cnt = h->counters.as<uint32_t>();
-  enum { CNT_DEAD = 23 };  // word of the counter block hs_pssm_prep_kernel counts the dead profiles in
-  if (filt) {  // the batch's tables: parameters (seg_vals), tau (tq), B tiles (c16s)
-    HS_HIP(h, h->seg_vals.reserve((size_t)mb_pad * hs_pssm_prof_bytes(h->p.k)));
-    HS_HIP(h, h->tq.reserve((size_t)mb_pad * 4));
-    HS_HIP(h, h->c16s.reserve((size_t)(mb_pad / 16) * hs_pssm_tile_bytes(steps)));
-  }
-  HS_HIP(h, hipMemsetAsync(d_cnt, 0, 256, h->stream));
-  HS_HIP(h, hipEventRecord(h->ev[0], h->stream));
-  HS_HIP(h, hipEventRecord(h->ev[1], h->stream));
-  HS_HIP(h, hipEventRecord(h->ev[2], h->stream));
-  HS_CHECK(filter_passes(h, mb, 0, false, nh, [&](uint32_t prov_cap, uint32_t hit_cap, bool again) -> hs_status {
-    HS_HIP(h, hipEventRecord(h->ev[3], h->stream));
-    if (filt) {
-      if (!again)
-        HS_HIP(h, hs_launch_pssm_prep(d_S, d_t, mb, h->p.k, (uint32_t)h->alphabet, h->seg_vals.p, h->tq.as<float>(),
-                                      h->c16s.p, d_cnt + CNT_DEAD, h->stream));
-      HS_HIP(h, hs_launch_pssm_filter(h->packed_all.as<uint4>(), (uint32_t)h->n, k, h->alphabet, h->c16s.p,
-                                      h->tq.as<float>(), mb, d_cnt, prov_cap, h->prov.as<uint2>(), h->stream));
-    }
-    HS_HIP(h, hipEventRecord(h->ev[4], h->stream));
-    HS_HIP(h, hs_launch_pssm_exact(h->codes.as<uint8_t>(), d_S, d_t, k, h->alphabet, m0, mb, (uint32_t)h->n,
-                                   h->prov.as<uint2>(), d_cnt, prov_cap, !filt, hit_cap, h->hit_key.as<uint64_t>(),
-                                   h->hit_val.as<uint64_t>(), h->n_cu, h->stream));
-    HS_HIP(h, hipEventRecord(h->ev[5], h->stream));
-    HS_HIP(h, hipMemcpyAsync(h->pin_cnt, d_cnt, HS_CNT_WORDS * 4, hipMemcpyDeviceToHost, h->stream));
-    return HS_OK;
-  }));
-  const uint32_t dead = filt ? h->pin_cnt[CNT_DEAD] : 0u;
-  h->prof.pssm_dead += dead;
-  h->prof.pssm_pairs += (uint64_t)(mb - dead) * h->n;
-  h->prof.pssm_survivors += filt ? (uint64_t)h->pin_cnt[0] : (uint64_t)mb * h->n;
-  h->prof.pssm_mfma_steps = filt ? steps : 0;
-  return HS_OK;
-}
-
-// The batch loop of a scan: sink(m0, mb, nh) takes every batch that has hits (profiles m0 .. m0 + mb - 1 of the call,
-// nh unordered hits in hit_key / hit_val) and queues its work on the stream; ms_finalize takes its time.
-extern "C++" template <class Sink>
-static hs_status pssm_batches(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm, uint64_t* n_hits,
-                              Sink&& sink) {
-  const bool filt = !h->knobs.no_pssm_filter;
-  const size_t ka = (size_t)h->p.k * h->alphabet;
-  uint64_t total = 0;
-  if (nm && h->n) {
-    // profiles per batch: 4096 (256 tiles: 1.5 MB of B operands at 4 steps), or what HS_OPT_QUERY_BATCH says
-    uint32_t MB = h->knobs.query_batch ? h->knobs.query_batch : 4096u;
-    uint32_t mb = 0;
-    for (uint64_t m0 = 0; m0 < nm; m0 += mb) {
-      mb = (uint32_t)std::min<uint64_t>(MB, nm - m0);
-      uint32_t nh = 0;
-      const hs_status st = pssm_batch(h, d_S + m0 * ka, d_t + m0, (uint32_t)m0, mb, filt, &nh);
-      if (st == HS_SPLIT_BATCH) {  // (as run_query: the same profiles again in batches half the size)
-        if (mb == 1) return fail(h, HS_ERR_CAPACITY, "the filter survivors of one profile exceed 2^32");
-        MB = (mb + 1) / 2;
-        mb = 0;
-        continue;
-      }
-      if (st) return st;
-      if (nh) {
-        HS_HIP(h, hipEventRecord(h->ev[6], h->stream));
-        HS_CHECK(sink((uint32_t)m0, mb, nh));
-        HS_HIP(h, hipEventRecord(h->ev[7], h->stream));
-        HS_HIP(h, hipStreamSynchronize(h->stream));
-        h->prof.ms_finalize += ev_ms(h, 6, 7);
-      }
-      total += nh;
-    }
-  }
-  HS_HIP(h, hipEventRecord(h->ev[9], h->stream));
-  HS_HIP(h, hipStreamSynchronize(h->stream));
-  h->prof.ms_total = ev_ms(h, 8, 9);
-  h->prof.hits = total;
-  *n_hits = total;
-  return HS_OK;
-}
-
-// the order (m, id) of a batch's nh hits: the 64-bit sort of the hit lists on the key m << 32 | id, into hit_key2 /
-// hit_val2
-static hs_status pssm_sort_hits(hs_handle* h, uint32_t m0, uint32_t mb, uint32_t nh, size_t temp_also) {
-  HS_HIP(h, h->hit_key2.reserve((size_t)nh * 8));
-  HS_HIP(h, h->hit_val2.reserve((size_t)nh * 8));
-  HS_HIP(h, h->temp.reserve(std::max(hs_sort_pairs_u64_u64_temp(nh), temp_also) + 256));
-  HS_HIP(h, hs_sort_pairs_u64_u64(h->temp.p, h->temp.cap, h->hit_key.as<uint64_t>(), h->hit_key2.as<uint64_t>(),
-                                  h->hit_val.as<uint64_t>(), h->hit_val2.as<uint64_t>(), nh,
-                                  32 + bit_width_u32(m0 + mb), h->stream));
-  return HS_OK;
-}
-
-// The scan with every array on the device; the callers have checked the arguments and the values.
-static hs_status pssm_core(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm, uint32_t* d_hit_m,
-                           uint32_t* d_hit_id, double* d_hit_score, uint64_t cap, uint64_t* n_hits, uint64_t* d_cnt_out) {
-  memset(&h->prof, 0, sizeof(h->prof));
-  HS_HIP(h, h->counters.reserve(256));
-  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
-  if (d_cnt_out && nm) HS_HIP(h, hipMemsetAsync(d_cnt_out, 0, nm * 8, h->stream));
-  uint64_t total = 0;
-  HS_CHECK(pssm_batches(h, d_S, d_t, nm, n_hits, [&](uint32_t m0, uint32_t mb, uint32_t nh) -> hs_status {
-    const uint64_t at = std::min<uint64_t>(total, cap);
-    const bool fits = nh <= cap - at;
-    const uint64_t *key = h->hit_key.as<uint64_t>(), *val = h->hit_val.as<uint64_t>();
-    if (fits) {
-      HS_CHECK(pssm_sort_hits(h, m0, mb, nh, 0));
-      key = h->hit_key2.as<uint64_t>();
-      val = h->hit_val2.as<uint64_t>();
-    }
-    HS_HIP(h, hs_launch_pssm_emit(key, val, nh, fits, fits ? d_hit_m + at : nullptr, fits ? d_hit_id + at : nullptr,
-                                  fits ? d_hit_score + at : nullptr, d_cnt_out, h->stream));
-    total += nh;
-    return HS_OK;
-  }));
-  if (*n_hits > cap) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
-  return HS_OK;
-}
-
-// ---- hs_pssm_seq_scan: the scan's hits reduced per (profile, sequence) (kernels and the passes: hs_pssm_seq.hip) ----
-struct PssmSeqOut {
-  uint32_t *m, *seq, *count;
-  double* best_score;
-  uint32_t *best_id, *lo, *hi;
-  bool all() const { return m && seq && count && best_score && best_id && lo && hi; }
-};
-
-// The call with every array on the device; the callers have checked the arguments and the values.  A batch's rows are
-// final (every hit of a profile lies in its batch) and follow the rows of the batches before it.
-static hs_status pssm_seq_core(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm,
-                               const uint64_t* d_id_start, uint64_t n_seq, const PssmSeqOut& out, uint64_t cap,
-                               uint64_t* n_out, uint64_t* n_hits, uint64_t* d_cnt_out, uint64_t* d_seq_cnt_out) {
-  memset(&h->prof, 0, sizeof(h->prof));
-  HS_HIP(h, h->counters.reserve(256));
-  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
-  if (d_cnt_out && nm) HS_HIP(h, hipMemsetAsync(d_cnt_out, 0, nm * 8, h->stream));
-  if (d_seq_cnt_out && nm) HS_HIP(h, hipMemsetAsync(d_seq_cnt_out, 0, nm * 8, h->stream));
-  uint64_t total_rows = 0;
-  HS_CHECK(pssm_batches(h, d_S, d_t, nm, n_hits, [&](uint32_t m0, uint32_t mb, uint32_t nh) -> hs_status {
-    HS_CHECK(pssm_sort_hits(h, m0, mb, nh, hs_scan_u32_temp((size_t)nh + 1)));
-    const uint64_t *key = h->hit_key2.as<uint64_t>(), *val = h->hit_val2.as<uint64_t>();
-    HS_HIP(h, h->sq_sidx.reserve((size_t)nh * 4));  // the sequence of every hit
-    HS_HIP(h, h->sq_head.reserve(((size_t)nh + 1) * 4));
-    HS_HIP(h, h->sq_excl.reserve(((size_t)nh + 1) * 4));
-    HS_HIP(h, hs_launch_pssm_seq_head(key, nh, d_id_start, n_seq, h->sq_sidx.as<uint32_t>(), h->sq_head.as<uint32_t>(),
-                                      h->stream));
-    HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, h->sq_head.as<uint32_t>(), h->sq_excl.as<uint32_t>(),
-                                    (size_t)nh + 1, h->stream));
-    uint32_t rows = 0;
-    HS_HIP(h, hipMemcpyAsync(&rows, h->sq_excl.as<uint32_t>() + nh, 4, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipStreamSynchronize(h->stream));
-    if (!rows || rows > nh) return fail(h, HS_ERR_HIP, "hs_pssm_seq_scan: the row count of a batch is out of range");
-    const uint64_t at = std::min<uint64_t>(total_rows, cap);
-    const bool fits = rows <= cap - at;
-    HS_HIP(h, h->sq_skey.reserve(((size_t)rows + 1) * 4));  // where every row's run starts
-    HS_HIP(h, h->sq_key.reserve((size_t)rows * 8));         // the rows' best score keys ...
-    HS_HIP(h, h->sq_idx.reserve((size_t)rows * 4));         // ... and ids
-    HS_HIP(h, h->sq_part.reserve(hs_pssm_seq_part_bytes(nh)));
-    HS_HIP(h, hs_launch_pssm_seq_rows(key, val, h->sq_sidx.as<uint32_t>(), h->sq_head.as<uint32_t>(),
-                                      h->sq_excl.as<uint32_t>(), nh, rows, d_id_start, fits, h->sq_skey.as<uint32_t>(),
-                                      h->sq_key.as<uint64_t>(), h->sq_idx.as<uint32_t>(), h->sq_part.p,
-                                      fits ? out.m + at : nullptr, fits ? out.seq + at : nullptr,
-                                      fits ? out.count + at : nullptr, fits ? out.best_score + at : nullptr,
-                                      fits ? out.best_id + at : nullptr, fits ? out.lo + at : nullptr,
-                                      fits ? out.hi + at : nullptr, d_cnt_out, d_seq_cnt_out, h->stream));
-    total_rows += rows;
-    return HS_OK;
-  }));
-  h->prof.pssm_seq_rows = total_rows;
-  *n_out = total_rows;
-  if (total_rows > cap) return fail(h, HS_ERR_CAPACITY, "row buffers too small; see *n_out");
-  return HS_OK;
-}
-
-// what both forms refuse from the arguments alone (hs_pssm_scan's refusals first)
-static hs_status pssm_seq_args(hs_handle* h, const void* S, const void* t, uint64_t nm, const void* id_start,
-                               uint64_t n_seq, const PssmSeqOut& out, uint64_t cap) {
-  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
-  if (nm >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nm must be < 2^27 per call");
-  if (nm && (!S || !t)) return fail(h, HS_ERR_INVALID, "hs_pssm_seq_scan: S or t is null");
-  if (cap && !out.all()) return fail(h, HS_ERR_INVALID, "an output array is null");
-  if (!id_start) return fail(h, HS_ERR_INVALID, "hs_pssm_seq_scan: id_start is null");
-  if (n_seq > (1ull << 32)) return fail(h, HS_ERR_INVALID, "hs_pssm_seq_scan: more than 2^32 sequences");
-  if (!n_seq && h->n) return fail(h, HS_ERR_INVALID, "hs_pssm_seq_scan: no sequence owns the index's k-mers");
-  return HS_OK;
-}
-
-hs_status hs_pssm_seq_scan_dev(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm,
-                               const uint64_t* d_id_start, uint64_t n_seq, uint32_t* d_out_m, uint32_t* d_out_seq,
-                               uint32_t* d_out_count, double* d_out_best_score, uint32_t* d_out_best_id,
-                               uint32_t* d_out_lo, uint32_t* d_out_hi, uint64_t cap, uint64_t* n_out, uint64_t* n_hits,
-                               uint64_t* d_cnt, uint64_t* d_seq_cnt) {
-  if (!h || !n_out || !n_hits) return HS_ERR_INVALID;
-  *n_out = 0;
-  *n_hits = 0;
-  const PssmSeqOut out{d_out_m, d_out_seq, d_out_count, d_out_best_score, d_out_best_id, d_out_lo, d_out_hi};
-  HS_CHECK(pssm_seq_args(h, d_S, d_t, nm, d_id_start, n_seq, out, cap));
-  HS_CHECK(ensure_device(h));
-  {  // the values, on the device: one small reduction each over the profiles and id_start, one read-back
-    uint64_t chk[5] = {0, 0, 0, 0, 0};
-    HS_HIP(h, h->sq_chk.reserve(64));
-    HS_HIP(h, hipMemsetAsync(h->sq_chk.p, 0, 64, h->stream));
-    if (nm)
-      HS_HIP(h, hs_launch_pssm_check(d_S, nm * h->p.k * h->alphabet, d_t, nm, h->sq_chk.as<uint32_t>() + 8, h->stream));
-    HS_HIP(h, hs_launch_sm_check(nullptr, nullptr, 0, 0, d_id_start, n_seq, h->n, h->sq_chk.as<uint64_t>(), h->stream));
-    HS_HIP(h, hipMemcpyAsync(chk, h->sq_chk.p, 40, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipStreamSynchronize(h->stream));
-    if (chk[4] & 1u) return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
-    if (chk[4] & 2u) return fail(h, HS_ERR_INVALID, "a threshold is NaN or infinite");
-    if (chk[0] & 7) return fail(h, HS_ERR_INVALID, "hs_pssm_seq_scan: id_start must ascend from 0 to the index's k-mers");
-  }
-  return pssm_seq_core(h, d_S, d_t, nm, d_id_start, n_seq, out, cap, n_out, n_hits, d_cnt, d_seq_cnt);
-}
-
-hs_status hs_pssm_seq_scan(hs_handle* h, const double* S, const double* t, uint64_t nm, const uint64_t* id_start,
-                           uint64_t n_seq, uint32_t* out_m, uint32_t* out_seq, uint32_t* out_count,
-                           double* out_best_score, uint32_t* out_best_id, uint32_t* out_lo, uint32_t* out_hi,
-                           uint64_t cap, uint64_t* n_out, uint64_t* n_hits, uint64_t* cnt, uint64_t* seq_cnt) {
-  if (!h || !n_out || !n_hits) return HS_ERR_INVALID;
-  *n_out = 0;
-  *n_hits = 0;
-  const PssmSeqOut out{out_m, out_seq, out_count, out_best_score, out_best_id, out_lo, out_hi};
-  HS_CHECK(pssm_seq_args(h, S, t, nm, id_start, n_seq, out, cap));
-  const size_t ka = (size_t)h->p.k * h->alphabet;
-  for (uint64_t i = 0; i < nm * ka; ++i)
-    if (hs_pssm_bad_value(S[i], HS_PSSM_MAX_ABS))
-      return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
-  for (uint64_t m = 0; m < nm; ++m)
-    if (hs_pssm_bad_value(t[m], 1.7976931348623157e308)) return fail(h, HS_ERR_INVALID, "a threshold is NaN or infinite");
-  if (!hs_pssm_seq_id_start_ok(id_start, n_seq) || id_start[n_seq] != h->n)
-    return fail(h, HS_ERR_INVALID, "hs_pssm_seq_scan: id_start must ascend from 0 to the index's k-mers");
-  HS_CHECK(ensure_device(h));
-  // the rows are staged on the device at the caller's capacity: 32 bytes per row cross PCIe, never the hits
-  const size_t sb = ((size_t)n_seq + 1) * 8, cb = std::max<size_t>(16, nm * 8);
-  HS_HIP(h, h->io_centers.reserve(std::max<size_t>(16, nm * ka * 8)));
-  HS_HIP(h, h->io_radii.reserve(cb));
-  HS_HIP(h, h->sq_in.reserve(sb));
-  HS_HIP(h, h->sq_out.reserve(std::max<size_t>(64, (size_t)cap * 32)));
-  if (cnt || seq_cnt) HS_HIP(h, h->io_cand.reserve(2 * cb));
-  if (nm) {
-    HS_HIP(h, hipMemcpyAsync(h->io_centers.p, S, nm * ka * 8, hipMemcpyHostToDevice, h->stream));
-    HS_HIP(h, hipMemcpyAsync(h->io_radii.p, t, nm * 8, hipMemcpyHostToDevice, h->stream));
-  }
-  HS_HIP(h, hipMemcpyAsync(h->sq_in.p, id_start, sb, hipMemcpyHostToDevice, h->stream));
-  char* const o = h->sq_out.as<char>();
-  uint32_t* const w = reinterpret_cast<uint32_t*>(o + cap * 8);
-  const PssmSeqOut dev{w, w + cap, w + 2 * cap, reinterpret_cast<double*>(o), w + 3 * cap, w + 4 * cap, w + 5 * cap};
-  uint64_t* const d_cnt = cnt ? h->io_cand.as<uint64_t>() : nullptr;
-  uint64_t* const d_seq_cnt = seq_cnt ? reinterpret_cast<uint64_t*>(h->io_cand.as<char>() + cb) : nullptr;
-  const hs_status st = pssm_seq_core(h, h->io_centers.as<double>(), h->io_radii.as<double>(), nm,
-                                     h->sq_in.as<uint64_t>(), n_seq, dev, cap, n_out, n_hits, d_cnt, d_seq_cnt);
-  if (st != HS_OK && st != HS_ERR_CAPACITY) return st;
-  if (cnt && nm) HS_HIP(h, hipMemcpyAsync(cnt, d_cnt, nm * 8, hipMemcpyDeviceToHost, h->stream));
-  if (seq_cnt && nm) HS_HIP(h, hipMemcpyAsync(seq_cnt, d_seq_cnt, nm * 8, hipMemcpyDeviceToHost, h->stream));
-  const size_t r = (size_t)*n_out;
-  if (st == HS_OK && r) {
-    HS_HIP(h, hipMemcpyAsync(out_m, dev.m, r * 4, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipMemcpyAsync(out_seq, dev.seq, r * 4, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipMemcpyAsync(out_count, dev.count, r * 4, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipMemcpyAsync(out_best_score, dev.best_score, r * 8, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipMemcpyAsync(out_best_id, dev.best_id, r * 4, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipMemcpyAsync(out_lo, dev.lo, r * 4, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipMemcpyAsync(out_hi, dev.hi, r * 4, hipMemcpyDeviceToHost, h->stream));
-  }
-  HS_HIP(h, hipStreamSynchronize(h->stream));
-  return st;
-}
-
-// ---- hs_pssm_hit_counts / hs_pssm_refine: the position frequency matrices of a scan's hits (hs_pssm_counts.hip) ----
-// Sites per work item for a batch of ns sites: what HS_OPT_PSSM_COUNT_CHUNK says, else ns / 4096 within 256 .. 2048.
-// An item is one wave's serial walk over its sites (two dependent loads per step), so few long items leave a small
-// batch waiting on a handful of waves; 4096 items are 16 waves on every CU.  At 2048 sites the flush of at most 2400
-// bins is a twentieth of the item's 5 x 10^4 increments at k = 25.
-static uint32_t pssm_count_chunk(const hs_handle* h, uint32_t ns) {
-  if (h->knobs.pssm_count_chunk) return h->knobs.pssm_count_chunk;
-  return std::min(2048u, std::max(256u, (ns + 4095u) / 4096u));
-}
-
-// The call with every array on the device; the callers have checked the arguments and the values.  d_id_start null:
-// every hit is a site; else the sites are the best ids of the batch's (profile, sequence) rows.  Every hit of a
-// profile lies in one batch, so a batch finishes its profiles' counts.
-static hs_status pssm_counts_core(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm,
-                                  const uint64_t* d_id_start, uint64_t n_seq, uint32_t* d_counts, uint64_t* d_cnt_out,
-                                  uint64_t* d_used_out, uint64_t* n_hits) {
-  memset(&h->prof, 0, sizeof(h->prof));
-  HS_HIP(h, h->counters.reserve(256));
-  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
-  const int k = (int)h->p.k;
-  const size_t cells = (size_t)h->p.k * h->alphabet;
-  if (nm) HS_HIP(h, hipMemsetAsync(d_counts, 0, nm * cells * 4, h->stream));
-  if (d_cnt_out && nm) HS_HIP(h, hipMemsetAsync(d_cnt_out, 0, nm * 8, h->stream));
-  if (d_used_out && nm) HS_HIP(h, hipMemsetAsync(d_used_out, 0, nm * 8, h->stream));
-  uint64_t sites = 0, items = 0;
-  HS_CHECK(pssm_batches(h, d_S, d_t, nm, n_hits, [&](uint32_t m0, uint32_t mb, uint32_t nh) -> hs_status {
-    const uint32_t *site_m = nullptr, *site_id = nullptr;
-    uint32_t ns = 0;
-    const size_t scan_items = hs_scan_u32_temp((size_t)mb + 1);
-    if (!d_id_start) {  // the hits, ordered on their profile bits alone
-      HS_HIP(h, h->pc_m.reserve((size_t)nh * 4));
-      HS_HIP(h, h->pc_id.reserve((size_t)nh * 4));
-      HS_HIP(h, h->pc_m2.reserve((size_t)nh * 4));
-      HS_HIP(h, h->pc_id2.reserve((size_t)nh * 4));
-      HS_HIP(h, h->temp.reserve(std::max(hs_sort_pairs_u32_u32_temp(nh), scan_items) + 256));
-      HS_HIP(h, hs_launch_pssm_counts_split(h->hit_key.as<uint64_t>(), nh, h->pc_m.as<uint32_t>(),
-                                            h->pc_id.as<uint32_t>(), h->stream));
-      HS_HIP(h, hs_sort_pairs_u32_u32(h->temp.p, h->temp.cap, h->pc_m.as<uint32_t>(), h->pc_m2.as<uint32_t>(),
-                                      h->pc_id.as<uint32_t>(), h->pc_id2.as<uint32_t>(), nh, bit_width_u32(m0 + mb),
-                                      h->stream));
-      site_m = h->pc_m2.as<uint32_t>();
-      site_id = h->pc_id2.as<uint32_t>();
-      ns = nh;
-    } else {  // the rows of hs_pssm_seq_scan, kept on the device: their m and best_id are the sites
-      HS_CHECK(pssm_sort_hits(h, m0, mb, nh, std::max(hs_scan_u32_temp((size_t)nh + 1), scan_items)));
-      const uint64_t *key = h->hit_key2.as<uint64_t>(), *val = h->hit_val2.as<uint64_t>();
-      HS_HIP(h, h->sq_sidx.reserve((size_t)nh * 4));
-      HS_HIP(h, h->sq_head.reserve(((size_t)nh + 1) * 4));
-      HS_HIP(h, h->sq_excl.reserve(((size_t)nh + 1) * 4));
-      HS_HIP(h, hs_launch_pssm_seq_head(key, nh, d_id_start, n_seq, h->sq_sidx.as<uint32_t>(),
-                                        h->sq_head.as<uint32_t>(), h->stream));
-      HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, h->sq_head.as<uint32_t>(), h->sq_excl.as<uint32_t>(),
-                                      (size_t)nh + 1, h->stream));
-      uint32_t rows = 0;
-      HS_HIP(h, hipMemcpyAsync(&rows, h->sq_excl.as<uint32_t>() + nh, 4, hipMemcpyDeviceToHost, h->stream));
-      HS_HIP(h, hipStreamSynchronize(h->stream));
-      if (!rows || rows > nh) return fail(h, HS_ERR_HIP, "hs_pssm_hit_counts: the row count of a batch is out of range");
-      HS_HIP(h, h->sq_skey.reserve(((size_t)rows + 1) * 4));
-      HS_HIP(h, h->sq_key.reserve((size_t)rows * 8));
-      HS_HIP(h, h->sq_idx.reserve((size_t)rows * 4));
-      HS_HIP(h, h->sq_part.reserve(hs_pssm_seq_part_bytes(nh)));
-      HS_HIP(h, h->pc_rows.reserve((size_t)rows * 32));
-      char* const o = h->pc_rows.as<char>();
-      uint32_t* const w = reinterpret_cast<uint32_t*>(o + (size_t)rows * 8);
-      const size_t r = rows;
-      HS_HIP(h, hs_launch_pssm_seq_rows(key, val, h->sq_sidx.as<uint32_t>(), h->sq_head.as<uint32_t>(),
-                                        h->sq_excl.as<uint32_t>(), nh, rows, d_id_start, true,
-                                        h->sq_skey.as<uint32_t>(), h->sq_key.as<uint64_t>(), h->sq_idx.as<uint32_t>(),
-                                        h->sq_part.p, w, w + r, w + 2 * r, reinterpret_cast<double*>(o), w + 3 * r,
-                                        w + 4 * r, w + 5 * r, d_cnt_out, nullptr, h->stream));
-      site_m = w;
-      site_id = w + 3 * r;
-      ns = rows;
-    }
-    const uint32_t ch = pssm_count_chunk(h, ns);
-    HS_HIP(h, h->pc_start.reserve(((size_t)mb + 1) * 4));
-    HS_HIP(h, h->pc_nitem.reserve(((size_t)mb + 1) * 4));
-    HS_HIP(h, h->pc_off.reserve(((size_t)mb + 1) * 4));
-    HS_HIP(h, hs_launch_pssm_counts_items(site_m, ns, m0, mb, ch, h->pc_start.as<uint32_t>(),
-                                          h->pc_nitem.as<uint32_t>(), h->stream));
-    HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, h->pc_nitem.as<uint32_t>(), h->pc_off.as<uint32_t>(),
-                                    (size_t)mb + 1, h->stream));
-    uint32_t n_items = 0;
-    HS_HIP(h, hipMemcpyAsync(&n_items, h->pc_off.as<uint32_t>() + mb, 4, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipStreamSynchronize(h->stream));
-    if (!n_items || n_items > (uint64_t)ns / ch + mb)
-      return fail(h, HS_ERR_HIP, "hs_pssm_hit_counts: the item count of a batch is out of range");
-    HS_HIP(h, hs_launch_pssm_counts(h->codes.as<uint8_t>(), k, h->alphabet, site_id, h->pc_start.as<uint32_t>(),
-                                    h->pc_off.as<uint32_t>(), m0, mb, ch, n_items, d_counts, h->stream));
-    HS_HIP(h, hs_launch_pssm_counts_used(d_counts + (size_t)m0 * cells, mb, k, h->alphabet,
-                                         d_used_out ? d_used_out + m0 : nullptr,
-                                         d_cnt_out && !d_id_start ? d_cnt_out + m0 : nullptr, h->stream));
-    sites += ns;
-    items += n_items;
-    return HS_OK;
-  }));
-  h->prof.pssm_count_sites = sites;
-  h->prof.pssm_count_items = items;
-  return HS_OK;
-}
-
-// what every form refuses from the arguments alone (hs_pssm_scan's refusals first); id_start null: every site counts
-static hs_status pssm_counts_args(hs_handle* h, const void* S, const void* t, uint64_t nm, const void* id_start,
-                                  uint64_t n_seq, const void* counts) {
-  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
-  if (nm >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nm must be < 2^27 per call");
-  if (nm && (!S || !t)) return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: S or t is null");
-  if (nm && !counts) return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: counts is null");
-  if (id_start && n_seq > (1ull << 32)) return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: more than 2^32 sequences");
-  if (id_start && !n_seq && h->n)
-    return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: no sequence owns the index's k-mers");
-  return HS_OK;
-}
-
-hs_status hs_pssm_hit_counts_dev(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm,
-                                 const uint64_t* d_id_start, uint64_t n_seq, uint32_t* d_counts, uint64_t* d_cnt,
-                                 uint64_t* d_used, uint64_t* n_hits) {
-  if (!h || !n_hits) return HS_ERR_INVALID;
-  *n_hits = 0;
-  HS_CHECK(pssm_counts_args(h, d_S, d_t, nm, d_id_start, n_seq, d_counts));
-  HS_CHECK(ensure_device(h));
-  if (nm || d_id_start) {  // the values, on the device: the reductions of hs_pssm_seq_scan_dev, one read-back
-    uint64_t chk[5] = {0, 0, 0, 0, 0};
-    HS_HIP(h, h->sq_chk.reserve(64));
-    HS_HIP(h, hipMemsetAsync(h->sq_chk.p, 0, 64, h->stream));
-    if (nm)
-      HS_HIP(h, hs_launch_pssm_check(d_S, nm * h->p.k * h->alphabet, d_t, nm, h->sq_chk.as<uint32_t>() + 8, h->stream));
-    if (d_id_start)
-      HS_HIP(h, hs_launch_sm_check(nullptr, nullptr, 0, 0, d_id_start, n_seq, h->n, h->sq_chk.as<uint64_t>(), h->stream));
-    HS_HIP(h, hipMemcpyAsync(chk, h->sq_chk.p, 40, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipStreamSynchronize(h->stream));
-    if (chk[4] & 1u) return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
-    if (chk[4] & 2u) return fail(h, HS_ERR_INVALID, "a threshold is NaN or infinite");
-    if (chk[0] & 7) return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: id_start must ascend from 0 to the index's k-mers");
-  }
-  return pssm_counts_core(h, d_S, d_t, nm, d_id_start, n_seq, d_counts, d_cnt, d_used, n_hits);
-}
-
-// the values a host-pointer call refuses
-static hs_status pssm_counts_values(hs_handle* h, const double* S, const double* t, uint64_t nm, const uint64_t* id_start,
-                                    uint64_t n_seq) {
-  const size_t ka = (size_t)h->p.k * h->alphabet;
-  for (uint64_t i = 0; i < nm * ka; ++i)
-    if (hs_pssm_bad_value(S[i], HS_PSSM_MAX_ABS))
-      return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
-  for (uint64_t m = 0; m < nm; ++m)
-    if (hs_pssm_bad_value(t[m], 1.7976931348623157e308)) return fail(h, HS_ERR_INVALID, "a threshold is NaN or infinite");
-  if (id_start && (!hs_pssm_seq_id_start_ok(id_start, n_seq) || id_start[n_seq] != h->n))
-    return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: id_start must ascend from 0 to the index's k-mers");
-  return HS_OK;
-}
-
-// A checked host-pointer call: S and t up, counts (and cnt, used) down.  ids_resident: id_start already lies in sq_in
-// (the later iterations of hs_pssm_refine).
-static hs_status pssm_counts_host(hs_handle* h, const double* S, const double* t, uint64_t nm, const uint64_t* id_start,
-                                  uint64_t n_seq, bool ids_resident, uint32_t* counts, uint64_t* cnt, uint64_t* used,
-                                  uint64_t* n_hits) {
-  HS_CHECK(ensure_device(h));
-  const size_t ka = (size_t)h->p.k * h->alphabet;
-  const size_t sb = ((size_t)n_seq + 1) * 8, cb = std::max<size_t>(16, nm * 8), ob = std::max<size_t>(16, nm * ka * 4);
-  HS_HIP(h, h->io_centers.reserve(std::max<size_t>(16, nm * ka * 8)));
-  HS_HIP(h, h->io_radii.reserve(cb));
-  if (id_start) HS_HIP(h, h->sq_in.reserve(sb));
-  HS_HIP(h, h->pc_out.reserve(2 * cb + ob));
-  if (nm) {
-    HS_HIP(h, hipMemcpyAsync(h->io_centers.p, S, nm * ka * 8, hipMemcpyHostToDevice, h->stream));
-    HS_HIP(h, hipMemcpyAsync(h->io_radii.p, t, nm * 8, hipMemcpyHostToDevice, h->stream));
-  }
-  if (id_start && !ids_resident)
-    HS_HIP(h, hipMemcpyAsync(h->sq_in.p, id_start, sb, hipMemcpyHostToDevice, h->stream));
-  char* const o = h->pc_out.as<char>();
-  uint64_t* const d_cnt = cnt ? reinterpret_cast<uint64_t*>(o) : nullptr;
-  uint64_t* const d_used = used ? reinterpret_cast<uint64_t*>(o + cb) : nullptr;
-  uint32_t* const d_counts = reinterpret_cast<uint32_t*>(o + 2 * cb);
-  HS_CHECK(pssm_counts_core(h, h->io_centers.as<double>(), h->io_radii.as<double>(), nm,
-                            id_start ? h->sq_in.as<uint64_t>() : nullptr, n_seq, d_counts, d_cnt, d_used, n_hits));
-  if (nm) {
-    HS_HIP(h, hipMemcpyAsync(counts, d_counts, nm * ka * 4, hipMemcpyDeviceToHost, h->stream));
-    if (cnt) HS_HIP(h, hipMemcpyAsync(cnt, d_cnt, nm * 8, hipMemcpyDeviceToHost, h->stream));
-    if (used) HS_HIP(h, hipMemcpyAsync(used, d_used, nm * 8, hipMemcpyDeviceToHost, h->stream));
-  }
-  HS_HIP(h, hipStreamSynchronize(h->stream));
-  return HS_OK;
-}
-
-hs_status hs_pssm_hit_counts(hs_handle* h, const double* S, const double* t, uint64_t nm, const uint64_t* id_start,
-                             uint64_t n_seq, uint32_t* counts, uint64_t* cnt, uint64_t* used, uint64_t* n_hits) {
-  if (!h || !n_hits) return HS_ERR_INVALID;
-  *n_hits = 0;
-  HS_CHECK(pssm_counts_args(h, S, t, nm, id_start, n_seq, counts));
-  HS_CHECK(pssm_counts_values(h, S, t, nm, id_start, n_seq));
-  return pssm_counts_host(h, S, t, nm, id_start, n_seq, false, counts, cnt, used, n_hits);
-}
-
-hs_status hs_pssm_refine(hs_handle* h, const double* S0, const double* t, uint64_t nm, const uint64_t* id_start,
-                         uint64_t n_seq, const double* bg, double pseudo, uint32_t n_iter, double* S_out,
-                         uint32_t* counts, uint64_t* used, uint32_t* iters, uint32_t* converged) {
-  if (!h || !iters || !converged) return HS_ERR_INVALID;
-  *iters = 0;
-  *converged = 0;
-  HS_CHECK(pssm_counts_args(h, S0, t, nm, id_start, n_seq, S_out));
-  if (n_iter < 1 || n_iter > 100) return fail(h, HS_ERR_INVALID, "hs_pssm_refine: n_iter must be 1 .. 100");
-  const uint32_t k = h->p.k, A = (uint32_t)h->alphabet;
-  double bgv[32];
-  if (!(pseudo > 0.0 && pseudo <= 1.7976931348623157e308) || (bg && !hs_pssm_bg_ok(bg, A, pseudo)))
-    return fail(h, HS_ERR_INVALID, "hs_pssm_refine: the background must be positive and finite, pseudo finite and > 0");
-  HS_CHECK(pssm_counts_values(h, S0, t, nm, id_start, n_seq));
-  const size_t cells = (size_t)k * A;
-  try {
-    uint64_t nh = 0;
-    if (bg) {
-      for (uint32_t a = 0; a < A; ++a) bgv[a] = bg[a];
-    } else {  // the residue composition of the index: one profile that hits everything, every site counted
-      const std::vector<double> zero(cells, 0.0);
-      std::vector<uint32_t> all(cells);
-      const double t0 = 0.0;
-      HS_CHECK(pssm_counts_host(h, zero.data(), &t0, 1, nullptr, 0, false, all.data(), nullptr, nullptr, &nh));
-      if (hs_pssm_background_host(all.data(), k, A, bgv))
-        return fail(h, HS_ERR_INVALID, "hs_pssm_refine: an empty index has no background");
-    }
-    std::vector<double> S(S0, S0 + nm * cells);
-    std::vector<uint32_t> C(nm * cells), prev;
-    std::vector<uint64_t> U(nm);
-    uint32_t done = 0, conv = 0;
-    for (uint32_t i = 0; i < n_iter; ++i) {
-      HS_CHECK(pssm_counts_host(h, S.data(), t, nm, id_start, n_seq, i > 0, C.data(), nullptr, U.data(), &nh));
-      ++done;
-      if (i > 0 && C == prev) {
-        conv = 1;
-        break;
-      }
-      for (uint64_t m = 0; m < nm; ++m)
-        if (U[m] && hs_pssm_log_odds_host(C.data() + m * cells, 1, k, A, bgv, pseudo, S.data() + m * cells))
-          return fail(h, HS_ERR_INVALID, "hs_pssm_refine: a log-odds entry is not finite");
-      prev = C;
-    }
-    for (size_t i = 0; i < S.size(); ++i) S_out[i] = S[i];
-    if (counts)
-      for (size_t i = 0; i < C.size(); ++i) counts[i] = C[i];
-    if (used)
-      for (uint64_t m = 0; m < nm; ++m) used[m] = U[m];
-    *iters = done;
-    *converged = conv;
-  } catch (const std::bad_alloc&) {
-    return fail(h, HS_ERR_NOMEM, "hs_pssm_refine: out of host memory");
-  }
-  return HS_OK;
-}
-
-static hs_status pssm_args(hs_handle* h, const void* S, const void* t, uint64_t nm, const void* hit_m, const void* hit_id,
-                           const void* hit_score, uint64_t cap) {
-  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
-  if (nm >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nm must be < 2^27 per call");
-  if (nm && (!S || !t)) return fail(h, HS_ERR_INVALID, "hs_pssm_scan: S or t is null");
-  if (cap && (!hit_m || !hit_id || !hit_score)) return fail(h, HS_ERR_INVALID, "an output array is null");
-  return HS_OK;
-}
-
-hs_status hs_pssm_scan_dev(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm, uint32_t* d_hit_m,
-                           uint32_t* d_hit_id, double* d_hit_score, uint64_t cap, uint64_t* n_hits, uint64_t* d_cnt) {
-  if (!h || !n_hits) return HS_ERR_INVALID;
-  *n_hits = 0;
-  HS_CHECK(pssm_args(h, d_S, d_t, nm, d_hit_m, d_hit_id, d_hit_score, cap));
-  HS_CHECK(ensure_device(h));
-  if (nm) {  // the values, on the device: one small reduction and one read-back, before anything is written
-    uint32_t flag = 0;
-    HS_HIP(h, h->io_radii.reserve(16));
-    HS_HIP(h, hipMemsetAsync(h->io_radii.p, 0, 16, h->stream));
-    HS_HIP(h, hs_launch_pssm_check(d_S, nm * h->p.k * h->alphabet, d_t, nm, h->io_radii.as<uint32_t>(), h->stream));
-    HS_HIP(h, hipMemcpyAsync(&flag, h->io_radii.p, 4, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipStreamSynchronize(h->stream));
-    if (flag & 1u) return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
-    if (flag & 2u) return fail(h, HS_ERR_INVALID, "a threshold is NaN or infinite");
-  }
-  return pssm_core(h, d_S, d_t, nm, d_hit_m, d_hit_id, d_hit_score, cap, n_hits, d_cnt);
-}
-
-hs_status hs_pssm_scan(hs_handle* h, const double* S, const double* t, uint64_t nm, uint32_t* hit_m, uint32_t* hit_id,
-                       double* hit_score, uint64_t cap, uint64_t* n_hits, uint64_t* cnt) {
-  if (!h || !n_hits) return HS_ERR_INVALID;
-  *n_hits = 0;
-  HS_CHECK(pssm_args(h, S, t, nm, hit_m, hit_id, hit_score, cap));
-  const size_t ka = (size_t)h->p.k * h->alphabet;
-  for (uint64_t i = 0; i < nm * ka; ++i)
-    if (hs_pssm_bad_value(S[i], HS_PSSM_MAX_ABS))
-      return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
-  for (uint64_t m = 0; m < nm; ++m)
-    if (hs_pssm_bad_value(t[m], 1.7976931348623157e308)) return fail(h, HS_ERR_INVALID, "a threshold is NaN or infinite");
-  HS_CHECK(ensure_device(h));
-  HS_HIP(h, h->io_centers.reserve(std::max<size_t>(16, nm * ka * 8)));
-  HS_HIP(h, h->io_radii.reserve(std::max<size_t>(16, nm * 8)));
-  HS_HIP(h, h->io_q.reserve(std::max<size_t>(16, cap * 4)));
-  HS_HIP(h, h->io_id.reserve(std::max<size_t>(16, cap * 4)));
-  HS_HIP(h, h->io_dist.reserve(std::max<size_t>(16, cap * 8)));
-  if (cnt) HS_HIP(h, h->io_cand.reserve(std::max<size_t>(16, nm * 8)));
-  if (nm) {
-    HS_HIP(h, hipMemcpyAsync(h->io_centers.p, S, nm * ka * 8, hipMemcpyHostToDevice, h->stream));
-    HS_HIP(h, hipMemcpyAsync(h->io_radii.p, t, nm * 8, hipMemcpyHostToDevice, h->stream));
-  }
-  const hs_status st = pssm_core(h, h->io_centers.as<double>(), h->io_radii.as<double>(), nm, h->io_q.as<uint32_t>(),
-                                 h->io_id.as<uint32_t>(), h->io_dist.as<double>(), cap, n_hits,
-                                 cnt ? h->io_cand.as<uint64_t>() : nullptr);
-  if (st != HS_OK && st != HS_ERR_CAPACITY) return st;
-  if (cnt && nm) HS_HIP(h, hipMemcpyAsync(cnt, h->io_cand.p, nm * 8, hipMemcpyDeviceToHost, h->stream));
-  const uint64_t nh = *n_hits;
-  if (st == HS_OK && nh) {
-    HS_HIP(h, hipMemcpyAsync(hit_m, h->io_q.p, nh * 4, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipMemcpyAsync(hit_id, h->io_id.p, nh * 4, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipMemcpyAsync(hit_score, h->io_dist.p, nh * 8, hipMemcpyDeviceToHost, h->stream));
-  }
-  HS_HIP(h, hipStreamSynchronize(h->stream));
-  return st;
-}
-
-// The filter's tables on the host (hs_pssm_tables.h): no GPU, no handle
-hs_status hs_pssm_tables(const double* S, const double* t, uint64_t nm, uint32_t k, uint32_t alphabet, uint8_t* code,
-                         double* tau, uint8_t* dead) {
-  return hs_pssm_tables_host(S, t, nm, k, alphabet, code, tau, dead) ? HS_ERR_INVALID : HS_OK;
-}
-
-// ---- hs_pssm_topk: the topk best k-mers per profile (kernels, the argument and the three steps: hs_pssm_topk.hip) ----
-// The call with every array on the device; the callers have checked the arguments and the values.  d_floor, d_tused
-// may be null.
-static hs_status pssm_topk_core(hs_handle* h, const double* d_S, const double* d_floor, uint64_t nm, uint32_t topk,
-                                uint32_t* d_id, double* d_score, uint32_t* d_count, double* d_tused) {
-  memset(&h->prof, 0, sizeof(h->prof));
-  HS_HIP(h, h->counters.reserve(256));
-  HS_HIP(h, h->knn_total.reserve(16));
-  HS_HIP(h, hipMemsetAsync(h->knn_total.p, 0, 16, h->stream));  // the profiles raised above their floor
-  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
-  const bool filt = !h->knobs.no_pssm_filter;
-  const size_t ka = (size_t)h->p.k * h->alphabet;
-  const uint32_t n = (uint32_t)h->n, n_s = (uint32_t)std::min<uint64_t>(h->n, h->knobs.pssm_topk_sample);
-  uint64_t total = 0, raised = 0;
-  // (an empty index runs no batch: nothing would write the rows)
-  if (nm && !n) HS_HIP(h, hs_launch_pssm_topk_fill(nm, topk, d_floor, d_id, d_score, d_count, d_tused, h->stream));
-  if (nm && n) {
-    // profiles per batch: what HS_OPT_QUERY_BATCH says, or at most 4096 and few enough that the hits to expect --
-    // topk * n / n_s per profile -- stay within 2^24
-    const uint64_t per = std::max<uint64_t>(1, (uint64_t)topk * n / n_s);
-    uint32_t MB = h->knobs.query_batch ? h->knobs.query_batch
-                                       : (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(1, (1ull << 24) / per));
-    uint32_t mb = 0;
-    for (uint64_t m0 = 0; m0 < nm; m0 += mb) {
-      mb = (uint32_t)std::min<uint64_t>(MB, nm - m0);
-      if (!d_tused) HS_HIP(h, h->pt_tused.reserve((size_t)mb * 8));
-      HS_HIP(h, h->pt_parts.reserve(std::max<size_t>(16, hs_pssm_sample_part_bytes(mb, n_s))));
-      double* const tu = d_tused ? d_tused + m0 : h->pt_tused.as<double>();
-      const double* const fl = d_floor ? d_floor + m0 : nullptr;
-      HS_HIP(h, hipEventRecord(h->ev[10], h->stream));
-      HS_HIP(h, hs_launch_pssm_sample(h->codes.as<uint8_t>(), d_S + m0 * ka, fl, (int)h->p.k, h->alphabet, n, n_s, topk,
-                                      mb, h->pt_parts.p, tu, h->stream));
-      HS_HIP(h, hipEventRecord(h->ev[11], h->stream));
-      uint32_t nh = 0;
-      const hs_status st = pssm_batch(h, d_S + m0 * ka, tu, (uint32_t)m0, mb, filt, &nh);
-      if (st == HS_SPLIT_BATCH) {  // (as pssm_core: the same profiles again in batches half the size)
-        if (mb == 1) return fail(h, HS_ERR_CAPACITY, "the filter survivors of one profile exceed 2^32");
-        MB = (mb + 1) / 2;
-        mb = 0;
-        continue;
-      }
-      if (st) return st;
-      h->prof.ms_hash += ev_ms(h, 10, 11);
-      // the selection runs for a batch without hits too: it writes the rows
-      HS_HIP(h, hipEventRecord(h->ev[6], h->stream));
-      const size_t words = ((size_t)mb + 1) * 4;
-      HS_HIP(h, h->knn_cnt.reserve(words));
-      HS_HIP(h, h->knn_off.reserve(words));
-      HS_HIP(h, h->knn_cur.reserve(words));
-      HS_HIP(h, h->hit_key2.reserve(std::max<size_t>(16, (size_t)nh * 8)));
-      HS_HIP(h, h->hit_val2.reserve(std::max<size_t>(16, (size_t)nh * 8)));
-      HS_HIP(h, h->temp.reserve(hs_pssm_topk_temp(mb) + 256));
-      HS_HIP(h, hs_launch_pssm_topk_select(h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(), nh, (uint32_t)m0, mb,
-                                           h->knn_cnt.as<uint32_t>(), h->knn_off.as<uint32_t>(),
-                                           h->knn_cur.as<uint32_t>(), h->temp.p, h->temp.cap,
-                                           h->hit_key2.as<uint64_t>(), h->hit_val2.as<uint64_t>(), topk, fl, tu, d_id,
-                                           d_score, d_count, h->knn_total.as<uint64_t>(), h->stream));
-      HS_HIP(h, hipEventRecord(h->ev[7], h->stream));
-      HS_HIP(h, hipStreamSynchronize(h->stream));
-      h->prof.ms_finalize += ev_ms(h, 6, 7);
-      total += nh;
-    }
-    HS_HIP(h, hipMemcpyAsync(&raised, h->knn_total.p, 8, hipMemcpyDeviceToHost, h->stream));
-  }
-  HS_HIP(h, hipEventRecord(h->ev[9], h->stream));
-  HS_HIP(h, hipStreamSynchronize(h->stream));
-  h->prof.ms_total = ev_ms(h, 8, 9);
-  h->prof.hits = total;
-  h->prof.pssm_topk_sample = n_s;
-  h->prof.pssm_topk_raised = raised;
-  return HS_OK;
-}
-
-static hs_status pssm_topk_args(hs_handle* h, const void* S, uint64_t nm, uint32_t topk, const void* top_id,
-                                const void* top_score, const void* top_count) {
-  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
-  if (nm >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nm must be < 2^27 per call");
-  if (!topk_ok(topk)) return fail(h, HS_ERR_INVALID, "hs_pssm_topk: topk must be 1 .. 64");
-  if (nm && !S) return fail(h, HS_ERR_INVALID, "hs_pssm_topk: S is null");
-  if (nm && (!top_id || !top_score || !top_count)) return fail(h, HS_ERR_INVALID, "an output array is null");
-  return HS_OK;
-}
-
-hs_status hs_pssm_topk_dev(hs_handle* h, const double* d_S, const double* d_floor, uint64_t nm, uint32_t topk,
-                           uint32_t* d_top_id, double* d_top_score, uint32_t* d_top_count, double* d_t_used) {
-  if (!h) return HS_ERR_INVALID;
-  HS_CHECK(pssm_topk_args(h, d_S, nm, topk, d_top_id, d_top_score, d_top_count));
-  HS_CHECK(ensure_device(h));
-  if (nm) {  // the values, on the device: one small reduction and one read-back, before anything is written
-    uint32_t flag = 0;
-    HS_HIP(h, h->io_radii.reserve(16));
-    HS_HIP(h, hipMemsetAsync(h->io_radii.p, 0, 16, h->stream));
-    HS_HIP(h, hs_launch_pssm_check(d_S, nm * h->p.k * h->alphabet, d_floor, d_floor ? nm : 0, h->io_radii.as<uint32_t>(),
-                                   h->stream));
-    HS_HIP(h, hipMemcpyAsync(&flag, h->io_radii.p, 4, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipStreamSynchronize(h->stream));
-    if (flag & 1u) return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
-    if (flag & 2u) return fail(h, HS_ERR_INVALID, "a floor is NaN or infinite");
-  }
-  return pssm_topk_core(h, d_S, d_floor, nm, topk, d_top_id, d_top_score, d_top_count, d_t_used);
-}
-
-hs_status hs_pssm_topk(hs_handle* h, const double* S, const double* t_floor, uint64_t nm, uint32_t topk,
-                       uint32_t* top_id, double* top_score, uint32_t* top_count, double* t_used) {
-  if (!h) return HS_ERR_INVALID;
-  HS_CHECK(pssm_topk_args(h, S, nm, topk, top_id, top_score, top_count));
-  const size_t ka = (size_t)h->p.k * h->alphabet;
-  for (uint64_t i = 0; i < nm * ka; ++i)
-    if (hs_pssm_bad_value(S[i], HS_PSSM_MAX_ABS))
-      return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
-  for (uint64_t m = 0; t_floor && m < nm; ++m)
-    if (hs_pssm_bad_value(t_floor[m], 1.7976931348623157e308)) return fail(h, HS_ERR_INVALID, "a floor is NaN or infinite");
-  HS_CHECK(ensure_device(h));
-  const size_t e = (size_t)nm * topk;
-  HS_HIP(h, h->io_centers.reserve(std::max<size_t>(16, nm * ka * 8)));
-  if (t_floor) HS_HIP(h, h->io_cand.reserve(std::max<size_t>(16, nm * 8)));
-  HS_HIP(h, h->io_id.reserve(std::max<size_t>(16, e * 4)));
-  HS_HIP(h, h->io_dist.reserve(std::max<size_t>(16, e * 8)));
-  HS_HIP(h, h->knn_io_count.reserve(std::max<size_t>(16, nm * 4)));
-  if (t_used) HS_HIP(h, h->io_radii.reserve(std::max<size_t>(16, nm * 8)));
-  if (nm) {
-    HS_HIP(h, hipMemcpyAsync(h->io_centers.p, S, nm * ka * 8, hipMemcpyHostToDevice, h->stream));
-    if (t_floor) HS_HIP(h, hipMemcpyAsync(h->io_cand.p, t_floor, nm * 8, hipMemcpyHostToDevice, h->stream));
-  }
-  // the rows are selected on the device: topk x 12 + 4 (+ 8) bytes per profile cross PCIe
-  HS_CHECK(pssm_topk_core(h, h->io_centers.as<double>(), t_floor ? h->io_cand.as<double>() : nullptr, nm, topk,
-                          h->io_id.as<uint32_t>(), h->io_dist.as<double>(), h->knn_io_count.as<uint32_t>(),
-                          t_used ? h->io_radii.as<double>() : nullptr));
-  if (nm) {
-    HS_HIP(h, hipMemcpyAsync(top_id, h->io_id.p, e * 4, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipMemcpyAsync(top_score, h->io_dist.p, e * 8, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipMemcpyAsync(top_count, h->knn_io_count.p, nm * 4, hipMemcpyDeviceToHost, h->stream));
-    if (t_used) HS_HIP(h, hipMemcpyAsync(t_used, h->io_radii.p, nm * 8, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipStreamSynchronize(h->stream));
-  }
-  return HS_OK;
-}
-
-// ---- hs_pssm_rank: the score of every profile's rank-th best k-mer (kernels, the argument, a round: hs_pssm_rank.hip) ----
-// The call with every array on the device; the callers have checked the arguments and the values (so n > 0 where
-// nm > 0) and know the largest rank.  d_tscan_out, d_rounds may be null.
-static hs_status pssm_rank_core(hs_handle* h, const double* d_S, const uint64_t* d_rank, uint64_t nm, uint64_t max_rank,
-                                double* d_t_rank, uint64_t* d_ge, uint64_t* d_gt, double* d_tscan_out,
-                                uint32_t* d_rounds) {
-  memset(&h->prof, 0, sizeof(h->prof));
-  HS_HIP(h, h->counters.reserve(256));
-  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
-  const bool filt = !h->knobs.no_pssm_filter;
-  const size_t ka = (size_t)h->p.k * h->alphabet;
-  const uint32_t n = (uint32_t)h->n, n_s = (uint32_t)std::min<uint64_t>(h->n, h->knobs.pssm_rank_sample);
-  uint64_t total = 0, retries = 0;
-  if (nm && n) {
-    HS_HIP(h, h->pr_resolved.reserve(nm * 4));
-    HS_HIP(h, h->pr_tscan.reserve(nm * 8));
-    HS_HIP(h, h->pr_unres.reserve(16));
-    uint32_t* const resolved = h->pr_resolved.as<uint32_t>();
-    uint32_t* const d_unres = h->pr_unres.as<uint32_t>();
-    double* const tscan = h->pr_tscan.as<double>();
-    HS_HIP(h, hs_launch_pssm_rank_init(nm, resolved, d_unres, h->stream));
-    const uint32_t SB = hs_pssm_rank_sample_batch(n_s);
-    for (uint32_t round = 0;; ++round) {
-      // 1. the sample pass and its select, in sub-batches of its own: the key buffer stays within 2^27 bytes
-      HS_HIP(h, hipEventRecord(h->ev[10], h->stream));
-      for (uint64_t m0 = 0; m0 < nm; m0 += SB) {
-        const uint32_t mb = (uint32_t)std::min<uint64_t>(SB, nm - m0);
-        HS_HIP(h, h->pr_keys.reserve((size_t)mb * n_s * 8));
-        HS_HIP(h, h->pr_off.reserve(((size_t)mb + 1) * 4));
-        HS_HIP(h, h->pr_state.reserve(hs_pssm_rank_state_bytes(mb)));
-        HS_HIP(h, hs_launch_pssm_rank_sample(h->codes.as<uint8_t>(), d_S, d_rank, resolved, (int)h->p.k, h->alphabet, n,
-                                             n_s, round, (uint32_t)m0, mb, h->pr_keys.as<uint64_t>(),
-                                             h->pr_off.as<uint32_t>(), h->pr_state.p, tscan, d_tscan_out, h->stream));
-      }
-      HS_HIP(h, hipEventRecord(h->ev[11], h->stream));
-      HS_HIP(h, hipMemsetAsync(d_unres, 0, 4, h->stream));
-      HS_HIP(h, hipStreamSynchronize(h->stream));
-      h->prof.ms_hash += ev_ms(h, 10, 11);
-      // 2. the scan.  Profiles per batch: what HS_OPT_QUERY_BATCH says, or at most 4096 and few enough that the hits
-      // to expect -- the largest rank's r_s * n / n_s per profile, n at the ladder's last rung -- stay within 2^24
-      uint64_t r_s = 0;
-      if (hs_pssm_rank_plan_rule(max_rank, n, n_s, round, &r_s)) return fail(h, HS_ERR_HIP, "hs_pssm_rank: no plan");
-      const uint64_t per = r_s > n_s ? n : std::max<uint64_t>(1, r_s * n / n_s);
-      uint32_t MB = h->knobs.query_batch ? h->knobs.query_batch
-                                         : (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(1, (1ull << 24) / per));
-      uint32_t mb = 0;
-      for (uint64_t m0 = 0; m0 < nm; m0 += mb) {
-        mb = (uint32_t)std::min<uint64_t>(MB, nm - m0);
-        uint32_t nh = 0;
-        const hs_status st = pssm_batch(h, d_S + m0 * ka, tscan + m0, (uint32_t)m0, mb, filt, &nh);
-        if (st == HS_SPLIT_BATCH) {  // (as pssm_core: the same profiles again in batches half the size)
-          if (mb == 1) return fail(h, HS_ERR_CAPACITY, "the filter survivors of one profile exceed 2^32");
-          MB = (mb + 1) / 2;
-          mb = 0;
-          continue;
-        }
-        if (st) return st;
-        // 3. the selection and the resolve step; they run for a batch without hits too: its profiles are counted
-        HS_HIP(h, hipEventRecord(h->ev[6], h->stream));
-        const size_t words = ((size_t)mb + 1) * 4;
-        HS_HIP(h, h->knn_cnt.reserve(words));
-        HS_HIP(h, h->knn_off.reserve(words));
-        HS_HIP(h, h->knn_cur.reserve(words));
-        HS_HIP(h, h->hit_key2.reserve(std::max<size_t>(16, (size_t)nh * 8)));
-        HS_HIP(h, h->pr_state.reserve(hs_pssm_rank_state_bytes(mb)));
-        HS_HIP(h, h->temp.reserve(hs_pssm_rank_temp(mb) + 256));
-        HS_HIP(h, hs_launch_pssm_rank_select(h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(), nh, (uint32_t)m0, mb,
-                                             h->knn_cnt.as<uint32_t>(), h->knn_off.as<uint32_t>(),
-                                             h->knn_cur.as<uint32_t>(), h->temp.p, h->temp.cap,
-                                             h->hit_key2.as<uint64_t>(), h->pr_state.p, d_rank, resolved, round, d_t_rank,
-                                             d_ge, d_gt, d_rounds, d_unres, h->stream));
-        HS_HIP(h, hipEventRecord(h->ev[7], h->stream));
-        HS_HIP(h, hipStreamSynchronize(h->stream));
-        h->prof.ms_finalize += ev_ms(h, 6, 7);
-        total += nh;
-      }
-      uint32_t unresolved = 0;
-      HS_HIP(h, hipMemcpyAsync(&unresolved, d_unres, 4, hipMemcpyDeviceToHost, h->stream));
-      HS_HIP(h, hipStreamSynchronize(h->stream));
-      if (!unresolved) break;
-      retries += unresolved;  // (each of them takes one more round)
-      // (the plan saturates beyond round 16: that round scans at -DBL_MAX and resolves everything)
-      if (round >= 17) return fail(h, HS_ERR_HIP, "hs_pssm_rank: profiles left after the ladder's last rung");
-    }
-  }
-  HS_HIP(h, hipEventRecord(h->ev[9], h->stream));
-  HS_HIP(h, hipStreamSynchronize(h->stream));
-  h->prof.ms_total = ev_ms(h, 8, 9);
-  h->prof.hits = total;
-  h->prof.pssm_rank_sample = n_s;
-  h->prof.pssm_rank_retries = retries;
-  return HS_OK;
-}
-
-static hs_status pssm_rank_args(hs_handle* h, const void* S, const void* rank, uint64_t nm, const void* t_rank,
-                                const void* cnt_ge, const void* cnt_gt) {
-  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
-  if (nm >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nm must be < 2^27 per call");
-  if (nm && !S) return fail(h, HS_ERR_INVALID, "hs_pssm_rank: S is null");
-  if (nm && (!rank || !t_rank || !cnt_ge || !cnt_gt))
-    return fail(h, HS_ERR_INVALID, "hs_pssm_rank: rank or an output array is null");
-  return HS_OK;
-}
-
-hs_status hs_pssm_rank_dev(hs_handle* h, const double* d_S, const uint64_t* d_rank, uint64_t nm, double* d_t_rank,
-                           uint64_t* d_cnt_ge, uint64_t* d_cnt_gt, double* d_t_scan, uint32_t* d_rounds) {
-  if (!h) return HS_ERR_INVALID;
-  HS_CHECK(pssm_rank_args(h, d_S, d_rank, nm, d_t_rank, d_cnt_ge, d_cnt_gt));
-  HS_CHECK(ensure_device(h));
-  uint64_t chk[2] = {0, 0};  // the flags; the largest rank
-  if (nm) {  // the values, on the device: two small reductions and one read-back, before anything is written
-    HS_HIP(h, h->io_radii.reserve(16));
-    HS_HIP(h, hipMemsetAsync(h->io_radii.p, 0, 16, h->stream));
-    HS_HIP(h, hs_launch_pssm_check(d_S, nm * h->p.k * h->alphabet, nullptr, 0, h->io_radii.as<uint32_t>(), h->stream));
-    HS_HIP(h, hs_launch_pssm_rank_check(d_rank, nm, h->n, h->io_radii.as<uint32_t>(), h->io_radii.as<uint64_t>() + 1,
-                                        h->stream));
-    HS_HIP(h, hipMemcpyAsync(chk, h->io_radii.p, 16, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipStreamSynchronize(h->stream));
-    if (chk[0] & 1u) return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
-    if (chk[0] & 4u) return fail(h, HS_ERR_INVALID, "hs_pssm_rank: a rank is 0 or above the index's k-mers");
-  }
-  return pssm_rank_core(h, d_S, d_rank, nm, chk[1], d_t_rank, d_cnt_ge, d_cnt_gt, d_t_scan, d_rounds);
-}
-
-hs_status hs_pssm_rank(hs_handle* h, const double* S, const uint64_t* rank, uint64_t nm, double* t_rank,
-                       uint64_t* cnt_ge, uint64_t* cnt_gt, double* t_scan, uint32_t* rounds) {
-  if (!h) return HS_ERR_INVALID;
-  HS_CHECK(pssm_rank_args(h, S, rank, nm, t_rank, cnt_ge, cnt_gt));
-  const size_t ka = (size_t)h->p.k * h->alphabet;
-  for (uint64_t i = 0; i < nm * ka; ++i)
-    if (hs_pssm_bad_value(S[i], HS_PSSM_MAX_ABS))
-      return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
-  uint64_t max_rank = 0;
-  for (uint64_t m = 0; m < nm; ++m) {
-    if (rank[m] < 1 || rank[m] > h->n)
-      return fail(h, HS_ERR_INVALID, "hs_pssm_rank: a rank is 0 or above the index's k-mers");
-    max_rank = std::max(max_rank, rank[m]);
-  }
-  HS_CHECK(ensure_device(h));
-  const size_t cb = std::max<size_t>(16, nm * 8);
-  HS_HIP(h, h->io_centers.reserve(std::max<size_t>(16, nm * ka * 8)));
-  HS_HIP(h, h->pr_rank.reserve(cb));
-  HS_HIP(h, h->pr_out.reserve(5 * cb));
-  if (nm) {
-    HS_HIP(h, hipMemcpyAsync(h->io_centers.p, S, nm * ka * 8, hipMemcpyHostToDevice, h->stream));
-    HS_HIP(h, hipMemcpyAsync(h->pr_rank.p, rank, nm * 8, hipMemcpyHostToDevice, h->stream));
-  }
-  // one double and two counts per profile (and the diagnostics) cross PCIe
-  char* const o = h->pr_out.as<char>();
-  double* const d_t = reinterpret_cast<double*>(o);
-  uint64_t* const d_ge = reinterpret_cast<uint64_t*>(o + cb);
-  uint64_t* const d_gt = reinterpret_cast<uint64_t*>(o + 2 * cb);
-  double* const d_ts = t_scan ? reinterpret_cast<double*>(o + 3 * cb) : nullptr;
-  uint32_t* const d_ro = rounds ? reinterpret_cast<uint32_t*>(o + 4 * cb) : nullptr;
-  HS_CHECK(pssm_rank_core(h, h->io_centers.as<double>(), h->pr_rank.as<uint64_t>(), nm, max_rank, d_t, d_ge, d_gt, d_ts,
-                          d_ro));
-  if (nm) {
-    HS_HIP(h, hipMemcpyAsync(t_rank, d_t, nm * 8, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipMemcpyAsync(cnt_ge, d_ge, nm * 8, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipMemcpyAsync(cnt_gt, d_gt, nm * 8, hipMemcpyDeviceToHost, h->stream));
-    if (t_scan) HS_HIP(h, hipMemcpyAsync(t_scan, d_ts, nm * 8, hipMemcpyDeviceToHost, h->stream));
-    if (rounds) HS_HIP(h, hipMemcpyAsync(rounds, d_ro, nm * 4, hipMemcpyDeviceToHost, h->stream));
-    HS_HIP(h, hipStreamSynchronize(h->stream));
-  }
-  return HS_OK;
-}
-
-// hs_pssm_refine with the threshold rule: every iteration scans at the threshold that admits rank[m] k-mers of S_i
-hs_status hs_pssm_refine_rank(hs_handle* h, const double* S0, const uint64_t* rank, uint64_t nm,
-                              const uint64_t* id_start, uint64_t n_seq, const double* bg, double pseudo, uint32_t n_iter,
-                              double* S_out, double* t_out, uint32_t* counts, uint64_t* used, uint32_t* iters,
-                              uint32_t* converged) {
-  if (!h || !iters || !converged) return HS_ERR_INVALID;
-  *iters = 0;
-  *converged = 0;
-  HS_CHECK(pssm_counts_args(h, S0, rank, nm, id_start, n_seq, S_out));
-  if (nm && !t_out) return fail(h, HS_ERR_INVALID, "hs_pssm_refine_rank: t_out is null");
-  if (n_iter < 1 || n_iter > 100) return fail(h, HS_ERR_INVALID, "hs_pssm_refine: n_iter must be 1 .. 100");
-  const uint32_t k = h->p.k, A = (uint32_t)h->alphabet;
-  double bgv[32];
-  if (!(pseudo > 0.0 && pseudo <= 1.7976931348623157e308) || (bg && !hs_pssm_bg_ok(bg, A, pseudo)))
-    return fail(h, HS_ERR_INVALID, "hs_pssm_refine: the background must be positive and finite, pseudo finite and > 0");
-  const size_t cells = (size_t)k * A;
-  try {
-    std::vector<double> T(nm, 0.0);
-    HS_CHECK(pssm_counts_values(h, S0, T.data(), nm, id_start, n_seq));
-    for (uint64_t m = 0; m < nm; ++m)
-      if (rank[m] < 1 || rank[m] > h->n)
-        return fail(h, HS_ERR_INVALID, "hs_pssm_rank: a rank is 0 or above the index's k-mers");
-    uint64_t nh = 0;
-    if (bg) {
-      for (uint32_t a = 0; a < A; ++a) bgv[a] = bg[a];
-    } else {  // the residue composition of the index, as hs_pssm_refine takes it
-      const std::vector<double> zero(cells, 0.0);
-      std::vector<uint32_t> all(cells);
-      const double t0 = 0.0;
-      HS_CHECK(pssm_counts_host(h, zero.data(), &t0, 1, nullptr, 0, false, all.data(), nullptr, nullptr, &nh));
-      if (hs_pssm_background_host(all.data(), k, A, bgv))
-        return fail(h, HS_ERR_INVALID, "hs_pssm_refine: an empty index has no background");
-    }
-    std::vector<double> S(S0, S0 + nm * cells);
-    std::vector<uint32_t> C(nm * cells), prev;
-    std::vector<uint64_t> U(nm), ge(nm), gt(nm);
-    uint32_t done = 0, conv = 0;
-    for (uint32_t i = 0; i < n_iter; ++i) {
-      HS_CHECK(hs_pssm_rank(h, S.data(), rank, nm, T.data(), ge.data(), gt.data(), nullptr, nullptr));
-      HS_CHECK(pssm_counts_host(h, S.data(), T.data(), nm, id_start, n_seq, i > 0, C.data(), nullptr, U.data(), &nh));
-      ++done;
-      if (i > 0 && C == prev) {
-        conv = 1;
-        break;
-      }
-      for (uint64_t m = 0; m < nm; ++m)
-        if (U[m] && hs_pssm_log_odds_host(C.data() + m * cells, 1, k, A, bgv, pseudo, S.data() + m * cells))
-          return fail(h, HS_ERR_INVALID, "hs_pssm_refine: a log-odds entry is not finite");
-      prev = C;
-    }
-    for (size_t i = 0; i < S.size(); ++i) S_out[i] = S[i];
-    for (uint64_t m = 0; m < nm; ++m) t_out[m] = T[m];
-    if (counts)
-      for (size_t i = 0; i < C.size(); ++i) counts[i] = C[i];
-    if (used)
-      for (uint64_t m = 0; m < nm; ++m) used[m] = U[m];
-    *iters = done;
-    *converged = conv;
-  } catch (const std::bad_alloc&) {
-    return fail(h, HS_ERR_NOMEM, "hs_pssm_refine: out of host memory");
   }
   return HS_OK;
 }

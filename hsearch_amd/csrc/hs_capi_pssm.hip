@@ -1,0 +1,923 @@
+// hs_capi_pssm.hip -- the profile calls of include/hsearch.h: position-specific score matrices (PSSMs) against every
+// indexed k-mer.  The handle and filter_passes: hs_handle.h; the kernels and each call's rule: the hs_pssm*.hip named
+// at its section.
+//   hs_pssm_scan / _dev                  every hit (m, id, score) at the caller's thresholds        (hs_pssm.hip)
+//   hs_pssm_seq_scan / _dev              the hits reduced per (profile, sequence)                   (hs_pssm_seq.hip)
+//   hs_pssm_hit_counts / _dev            the position frequency matrices of the hits                (hs_pssm_counts.hip)
+//   hs_pssm_topk / _dev                  the topk best k-mers per profile, no threshold given       (hs_pssm_topk.hip)
+//   hs_pssm_rank / _dev                  the threshold that admits a profile's rank best k-mers     (hs_pssm_rank.hip)
+//   hs_pssm_refine, hs_pssm_refine_rank  profiles rebuilt from their own hits, iterated
+//   hs_pssm_tables                       the filter's tables on the host (no GPU, no handle)
+// What they share, each once:
+//   pssm_args_start, pssm_refuse with pssm_host_bad / pssm_rank_bad / pssm_id_start_bad / pssm_dev_check
+//                     what a call refuses: from its arguments, and from its values on the host or on the device
+//   pssm_stage_in     S and a per-profile array of a host-pointer call on their way up
+//   pssm_batch        one batch of profiles through the tables, the FP6 MFMA filter and the exact pass
+//   pssm_batch_loop   the call's profiles cut into batches, a batch halved when its survivors overflow; a step before
+//                     each scan and a sink after it.  pssm_call_end closes the call's profile; pssm_batches is the
+//                     two together for the calls that scan at thresholds given
+//   pssm_row_pass     a batch's hits reduced to (profile, sequence) rows
+//   pssm_refine       the refine loop under either threshold rule
+#include <vector>
+
+#include "hs_handle.h"
+#include "hs_pssm_tables.h"
+#include "hs_pssm_seq.h"
+#include "hs_pssm_counts.h"
+#include "hs_pssm_topk.h"
+#include "hs_pssm_rank.h"
+
+namespace {
+
+// ---- what a call refuses ----------------------------------------------------------------------------------------
+// how every *_args function starts; null_text: what to say when an input array is missing (null: none is)
+hs_status pssm_args_start(hs_handle* h, uint64_t nm, const char* null_text) {
+  if (!h->built) return fail(h, HS_ERR_STATE, "hs_index_build has not been called");
+  if (nm >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nm must be < 2^27 per call");
+  if (nm && null_text) return fail(h, HS_ERR_INVALID, null_text);
+  return HS_OK;
+}
+
+// The values a call refuses, as bits (those of hs_pssm_check_kernel and hs_pssm_rank_check_kernel; BAD_ID_START is
+// the host's own), and their texts in the order of refusal.  noun: what the per-profile array holds; name: the call.
+enum { BAD_S = 1, BAD_T = 2, BAD_RANK = 4, BAD_ID_START = 8 };
+
+hs_status pssm_refuse(hs_handle* h, uint32_t bad, const char* noun, const char* name) {
+  if (bad & BAD_S) return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
+  if (bad & BAD_T) return fail(h, HS_ERR_INVALID, std::string("a ") + noun + " is NaN or infinite");
+  if (bad & BAD_ID_START)
+    return fail(h, HS_ERR_INVALID, std::string(name) + ": id_start must ascend from 0 to the index's k-mers");
+  if (bad & BAD_RANK) return fail(h, HS_ERR_INVALID, "hs_pssm_rank: a rank is 0 or above the index's k-mers");
+  return HS_OK;
+}
+
+// host pointers: S [nm][k][alphabet] and a per-profile array of thresholds or floors (v null: none)
+uint32_t pssm_host_bad(const hs_handle* h, const double* S, const double* v, uint64_t nm) {
+  const size_t ka = (size_t)h->p.k * h->alphabet;
+  uint32_t bad = 0;
+  for (uint64_t i = 0; i < nm * ka && !bad; ++i)
+    if (hs_pssm_bad_value(S[i], HS_PSSM_MAX_ABS)) bad = BAD_S;
+  for (uint64_t m = 0; v && m < nm && !bad; ++m)
+    if (hs_pssm_bad_value(v[m], 1.7976931348623157e308)) bad = BAD_T;
+  return bad;
+}
+
+uint32_t pssm_rank_bad(const hs_handle* h, const uint64_t* rank, uint64_t nm, uint64_t* max_rank) {
+  *max_rank = 0;
+  for (uint64_t m = 0; m < nm; ++m) {
+    if (rank[m] < 1 || rank[m] > h->n) return BAD_RANK;
+    *max_rank = std::max(*max_rank, rank[m]);
+  }
+  return 0;
+}
+
+uint32_t pssm_id_start_bad(const hs_handle* h, const uint64_t* id_start, uint64_t n_seq) {
+  return hs_pssm_seq_id_start_ok(id_start, n_seq) && id_start[n_seq] == h->n ? 0u : (uint32_t)BAD_ID_START;
+}
+
+// Device pointers (d_v, d_rank, d_id_start null: none): one small reduction for each kind the call has, into the
+// words of sq_chk -- [0..3] hs_sm_check_kernel's, [4] the BAD_* bits, [5] the largest rank -- and one read-back,
+// before anything is written; then pssm_refuse.  max_rank may be null.
+hs_status pssm_dev_check(hs_handle* h, const double* d_S, const double* d_v, uint64_t nm, const uint64_t* d_rank,
+                         const uint64_t* d_id_start, uint64_t n_seq, const char* noun, const char* name,
+                         uint64_t* max_rank) {
+  uint64_t chk[6] = {0, 0, 0, 0, 0, 0};
+  if (nm || d_id_start) {
+    HS_HIP(h, h->sq_chk.reserve(64));
+    HS_HIP(h, hipMemsetAsync(h->sq_chk.p, 0, 64, h->stream));
+    uint64_t* const d_chk = h->sq_chk.as<uint64_t>();
+    uint32_t* const d_bits = h->sq_chk.as<uint32_t>() + 8;
+    if (nm) HS_HIP(h, hs_launch_pssm_check(d_S, nm * h->p.k * h->alphabet, d_v, d_v ? nm : 0, d_bits, h->stream));
+    if (nm && d_rank) HS_HIP(h, hs_launch_pssm_rank_check(d_rank, nm, h->n, d_bits, d_chk + 5, h->stream));
+    if (d_id_start) HS_HIP(h, hs_launch_sm_check(nullptr, nullptr, 0, 0, d_id_start, n_seq, h->n, d_chk, h->stream));
+    HS_HIP(h, hipMemcpyAsync(chk, h->sq_chk.p, sizeof(chk), hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  if (max_rank) *max_rank = chk[5];
+  return pssm_refuse(h, (uint32_t)chk[4] | (chk[0] & 7 ? (uint32_t)BAD_ID_START : 0u), noun, name);
+}
+
+// A host-pointer call's S into io_centers and its per-profile array of 8-byte words (v null: none) into vbuf
+hs_status pssm_stage_in(hs_handle* h, const double* S, const void* v, uint64_t nm, DevBuf& vbuf) {
+  const size_t sb = nm * h->p.k * h->alphabet * 8;
+  HS_HIP(h, h->io_centers.reserve(std::max<size_t>(16, sb)));
+  if (v) HS_HIP(h, vbuf.reserve(std::max<size_t>(16, nm * 8)));
+  if (nm) {
+    HS_HIP(h, hipMemcpyAsync(h->io_centers.p, S, sb, hipMemcpyHostToDevice, h->stream));
+    if (v) HS_HIP(h, hipMemcpyAsync(vbuf.p, v, nm * 8, hipMemcpyHostToDevice, h->stream));
+  }
+  return HS_OK;
+}
+
+// ---- a batch, and the loop over a call's batches (kernels: hs_pssm.hip) -------------------------------------------
+// One batch of mb profiles (d_S, d_t: the batch's first; number m0 of the call) against the whole index: the tables
+// and the MFMA filter (or, with the filter off, nothing) and the exact pass, under filter_passes' survivor protocol.
+// On success the batch's nh hits lie unordered in hit_key / hit_val.
+hs_status pssm_batch(hs_handle* h, const double* d_S, const double* d_t, uint32_t m0, uint32_t mb, bool filt,
+                     uint32_t* nh) {
+  const int k = (int)h->p.k;
+  const uint32_t steps = hs_pssm_steps(h->p.k, (uint32_t)h->alphabet), mb_pad = (mb + 15u) & ~15u;
+  uint32_t* const d_cnt = h->counters.as<uint32_t>();
+  enum { CNT_DEAD = 23 };  // word of the counter block hs_pssm_prep_kernel counts the dead profiles in
+  if (filt) {  // the batch's tables: parameters (seg_vals), tau (tq), B tiles (c16s)
+    HS_HIP(h, h->seg_vals.reserve((size_t)mb_pad * hs_pssm_prof_bytes(h->p.k)));
+    HS_HIP(h, h->tq.reserve((size_t)mb_pad * 4));
+    HS_HIP(h, h->c16s.reserve((size_t)(mb_pad / 16) * hs_pssm_tile_bytes(steps)));
+  }
+  HS_HIP(h, hipMemsetAsync(d_cnt, 0, 256, h->stream));
+  HS_HIP(h, hipEventRecord(h->ev[0], h->stream));
+  HS_HIP(h, hipEventRecord(h->ev[1], h->stream));
+  HS_HIP(h, hipEventRecord(h->ev[2], h->stream));
+  HS_CHECK(filter_passes(h, mb, 0, false, nh, [&](uint32_t prov_cap, uint32_t hit_cap, bool again) -> hs_status {
+    HS_HIP(h, hipEventRecord(h->ev[3], h->stream));
+    if (filt) {
+      if (!again)
+        HS_HIP(h, hs_launch_pssm_prep(d_S, d_t, mb, h->p.k, (uint32_t)h->alphabet, h->seg_vals.p, h->tq.as<float>(),
+                                      h->c16s.p, d_cnt + CNT_DEAD, h->stream));
+      HS_HIP(h, hs_launch_pssm_filter(h->packed_all.as<uint4>(), (uint32_t)h->n, k, h->alphabet, h->c16s.p,
+                                      h->tq.as<float>(), mb, d_cnt, prov_cap, h->prov.as<uint2>(), h->stream));
+    }
+    HS_HIP(h, hipEventRecord(h->ev[4], h->stream));
+    HS_HIP(h, hs_launch_pssm_exact(h->codes.as<uint8_t>(), d_S, d_t, k, h->alphabet, m0, mb, (uint32_t)h->n,
+                                   h->prov.as<uint2>(), d_cnt, prov_cap, !filt, hit_cap, h->hit_key.as<uint64_t>(),
+                                   h->hit_val.as<uint64_t>(), h->n_cu, h->stream));
+    HS_HIP(h, hipEventRecord(h->ev[5], h->stream));
+    HS_HIP(h, hipMemcpyAsync(h->pin_cnt, d_cnt, HS_CNT_WORDS * 4, hipMemcpyDeviceToHost, h->stream));
+    return HS_OK;
+  }));
+  const uint32_t dead = filt ? h->pin_cnt[CNT_DEAD] : 0u;
+  h->prof.pssm_dead += dead;
+  h->prof.pssm_pairs += (uint64_t)(mb - dead) * h->n;
+  h->prof.pssm_survivors += filt ? (uint64_t)h->pin_cnt[0] : (uint64_t)mb * h->n;
+  h->prof.pssm_mfma_steps = filt ? steps : 0;
+  return HS_OK;
+}
+
+// The batch loop of every profile call: profiles 0 .. nm - 1 (nm > 0, against a non-empty index) in batches of MB, or
+// of what HS_OPT_QUERY_BATCH says.  Per batch of profiles m0 .. m0 + mb - 1:
+//   pre(m0, mb, &d_t)  queues what must run before the scan and names the batch's thresholds (its first profile's);
+//                      pre_timed: it records ev[10] / ev[11] around that, which go into ms_hash once the batch has
+//                      come through (the repeated step of a batch that is halved is not counted)
+//   pssm_batch         the scan; when its survivors overflow the counter the same profiles run again -- pre
+//                      included -- in batches half the size, as run_query's queries do
+//   sink(m0, mb, nh)   queues the work on the batch's nh unordered hits in hit_key / hit_val, ev[6] / ev[7] around it
+//                      into ms_finalize; a batch without hits is skipped unless sink_empty
+// *total grows by the hits.
+template <class Pre, class Sink>
+hs_status pssm_batch_loop(hs_handle* h, const double* d_S, uint64_t nm, uint32_t MB, bool pre_timed, bool sink_empty,
+                          uint64_t* total, Pre&& pre, Sink&& sink) {
+  const bool filt = !h->knobs.no_pssm_filter;
+  const size_t ka = (size_t)h->p.k * h->alphabet;
+  if (h->knobs.query_batch) MB = h->knobs.query_batch;
+  uint32_t mb = 0;
+  for (uint64_t m0 = 0; m0 < nm; m0 += mb) {
+    mb = (uint32_t)std::min<uint64_t>(MB, nm - m0);
+    const double* d_t = nullptr;
+    HS_CHECK(pre((uint32_t)m0, mb, &d_t));
+    uint32_t nh = 0;
+    const hs_status st = pssm_batch(h, d_S + m0 * ka, d_t, (uint32_t)m0, mb, filt, &nh);
+    if (st == HS_SPLIT_BATCH) {
+      if (mb == 1) return fail(h, HS_ERR_CAPACITY, "the filter survivors of one profile exceed 2^32");
+      MB = (mb + 1) / 2;
+      mb = 0;
+      continue;
+    }
+    if (st) return st;
+    if (pre_timed) h->prof.ms_hash += ev_ms(h, 10, 11);
+    if (nh || sink_empty) {
+      HS_HIP(h, hipEventRecord(h->ev[6], h->stream));
+      HS_CHECK(sink((uint32_t)m0, mb, nh));
+      HS_HIP(h, hipEventRecord(h->ev[7], h->stream));
+      HS_HIP(h, hipStreamSynchronize(h->stream));
+      h->prof.ms_finalize += ev_ms(h, 6, 7);
+    }
+    *total += nh;
+  }
+  return HS_OK;
+}
+
+// the end of a call whose start recorded ev[8]
+hs_status pssm_call_end(hs_handle* h, uint64_t total) {
+  HS_HIP(h, hipEventRecord(h->ev[9], h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  h->prof.ms_total = ev_ms(h, 8, 9);
+  h->prof.hits = total;
+  return HS_OK;
+}
+
+// A whole scan at the thresholds d_t: the loop with nothing before a scan, sink(m0, mb, nh) for every batch that has
+// hits, and the call's end.  Profiles per batch: 4096 (256 tiles: 1.5 MB of B operands at 4 steps).
+template <class Sink>
+hs_status pssm_batches(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm, uint64_t* n_hits, Sink&& sink) {
+  uint64_t total = 0;
+  if (nm && h->n)
+    HS_CHECK(pssm_batch_loop(h, d_S, nm, 4096u, false, false, &total,
+                             [&](uint32_t m0, uint32_t, const double** t) -> hs_status {
+                               *t = d_t + m0;
+                               return HS_OK;
+                             },
+                             sink));
+  HS_CHECK(pssm_call_end(h, total));
+  *n_hits = total;
+  return HS_OK;
+}
+
+// the order (m, id) of a batch's nh hits: the 64-bit sort of the hit lists on the key m << 32 | id, into hit_key2 /
+// hit_val2
+hs_status pssm_sort_hits(hs_handle* h, uint32_t m0, uint32_t mb, uint32_t nh, size_t temp_also) {
+  HS_HIP(h, h->hit_key2.reserve((size_t)nh * 8));
+  HS_HIP(h, h->hit_val2.reserve((size_t)nh * 8));
+  HS_HIP(h, h->temp.reserve(std::max(hs_sort_pairs_u64_u64_temp(nh), temp_also) + 256));
+  HS_HIP(h, hs_sort_pairs_u64_u64(h->temp.p, h->temp.cap, h->hit_key.as<uint64_t>(), h->hit_key2.as<uint64_t>(),
+                                  h->hit_val.as<uint64_t>(), h->hit_val2.as<uint64_t>(), nh,
+                                  32 + bit_width_u32(m0 + mb), h->stream));
+  return HS_OK;
+}
+
+// ---- hs_pssm_scan: every indexed k-mer against position-specific score matrices (kernels: hs_pssm.hip) ----
+// The scan with every array on the device; the callers have checked the arguments and the values.
+hs_status pssm_core(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm, uint32_t* d_hit_m,
+                    uint32_t* d_hit_id, double* d_hit_score, uint64_t cap, uint64_t* n_hits, uint64_t* d_cnt_out) {
+  memset(&h->prof, 0, sizeof(h->prof));
+  HS_HIP(h, h->counters.reserve(256));
+  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
+  if (d_cnt_out && nm) HS_HIP(h, hipMemsetAsync(d_cnt_out, 0, nm * 8, h->stream));
+  uint64_t total = 0;
+  HS_CHECK(pssm_batches(h, d_S, d_t, nm, n_hits, [&](uint32_t m0, uint32_t mb, uint32_t nh) -> hs_status {
+    const uint64_t at = std::min<uint64_t>(total, cap);
+    const bool fits = nh <= cap - at;
+    const uint64_t *key = h->hit_key.as<uint64_t>(), *val = h->hit_val.as<uint64_t>();
+    if (fits) {
+      HS_CHECK(pssm_sort_hits(h, m0, mb, nh, 0));
+      key = h->hit_key2.as<uint64_t>();
+      val = h->hit_val2.as<uint64_t>();
+    }
+    HS_HIP(h, hs_launch_pssm_emit(key, val, nh, fits, fits ? d_hit_m + at : nullptr, fits ? d_hit_id + at : nullptr,
+                                  fits ? d_hit_score + at : nullptr, d_cnt_out, h->stream));
+    total += nh;
+    return HS_OK;
+  }));
+  if (*n_hits > cap) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
+  return HS_OK;
+}
+
+hs_status pssm_args(hs_handle* h, const void* S, const void* t, uint64_t nm, const void* hit_m, const void* hit_id,
+                    const void* hit_score, uint64_t cap) {
+  HS_CHECK(pssm_args_start(h, nm, S && t ? nullptr : "hs_pssm_scan: S or t is null"));
+  if (cap && (!hit_m || !hit_id || !hit_score)) return fail(h, HS_ERR_INVALID, "an output array is null");
+  return HS_OK;
+}
+
+// ---- hs_pssm_seq_scan: the scan's hits reduced per (profile, sequence) (kernels and the passes: hs_pssm_seq.hip) ----
+struct PssmSeqOut {
+  uint32_t *m = nullptr, *seq = nullptr, *count = nullptr;
+  double* best_score = nullptr;
+  uint32_t *best_id = nullptr, *lo = nullptr, *hi = nullptr;
+  bool all() const { return m && seq && count && best_score && best_id && lo && hi; }
+  PssmSeqOut at(uint64_t i) const {
+    return PssmSeqOut{m + i, seq + i, count + i, best_score + i, best_id + i, lo + i, hi + i};
+  }
+  // r rows in 32 r bytes of one buffer: the scores, then the six 32-bit arrays
+  static PssmSeqOut in(char* o, size_t r) {
+    uint32_t* const w = reinterpret_cast<uint32_t*>(o + r * 8);
+    return PssmSeqOut{w, w + r, w + 2 * r, reinterpret_cast<double*>(o), w + 3 * r, w + 4 * r, w + 5 * r};
+  }
+};
+
+// A batch's nh hits reduced to their (profile, sequence) rows under d_id_start [n_seq + 1]; *n_rows: how many.  out
+// given: they follow the `done` rows the call has so far in the caller's arrays of cap rows -- or are only counted
+// when they do not fit; out null: they go to pc_rows, laid out by PssmSeqOut::in.  temp_also: bytes of temp the
+// caller's next step wants; d_cnt_out, d_seq_cnt_out (either may be null): the profiles' hit and row counts; name:
+// the call, for the error text.
+hs_status pssm_row_pass(hs_handle* h, uint32_t m0, uint32_t mb, uint32_t nh, const uint64_t* d_id_start, uint64_t n_seq,
+                        size_t temp_also, const PssmSeqOut* out, uint64_t done, uint64_t cap, uint64_t* d_cnt_out,
+                        uint64_t* d_seq_cnt_out, const char* name, uint32_t* n_rows) {
+  HS_CHECK(pssm_sort_hits(h, m0, mb, nh, std::max(hs_scan_u32_temp((size_t)nh + 1), temp_also)));
+  const uint64_t *key = h->hit_key2.as<uint64_t>(), *val = h->hit_val2.as<uint64_t>();
+  HS_HIP(h, h->sq_sidx.reserve((size_t)nh * 4));  // the sequence of every hit
+  HS_HIP(h, h->sq_head.reserve(((size_t)nh + 1) * 4));
+  HS_HIP(h, h->sq_excl.reserve(((size_t)nh + 1) * 4));
+  HS_HIP(h, hs_launch_pssm_seq_head(key, nh, d_id_start, n_seq, h->sq_sidx.as<uint32_t>(), h->sq_head.as<uint32_t>(),
+                                    h->stream));
+  HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, h->sq_head.as<uint32_t>(), h->sq_excl.as<uint32_t>(),
+                                  (size_t)nh + 1, h->stream));
+  uint32_t rows = 0;
+  HS_HIP(h, hipMemcpyAsync(&rows, h->sq_excl.as<uint32_t>() + nh, 4, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  if (!rows || rows > nh) return fail(h, HS_ERR_HIP, std::string(name) + ": the row count of a batch is out of range");
+  HS_HIP(h, h->sq_skey.reserve(((size_t)rows + 1) * 4));  // where every row's run starts
+  HS_HIP(h, h->sq_key.reserve((size_t)rows * 8));         // the rows' best score keys ...
+  HS_HIP(h, h->sq_idx.reserve((size_t)rows * 4));         // ... and ids
+  HS_HIP(h, h->sq_part.reserve(hs_pssm_seq_part_bytes(nh)));
+  bool fits = true;
+  PssmSeqOut to;  // (all null when the rows do not fit)
+  if (out) {
+    const uint64_t at = std::min<uint64_t>(done, cap);
+    fits = rows <= cap - at;
+    if (fits) to = out->at(at);
+  } else {
+    HS_HIP(h, h->pc_rows.reserve((size_t)rows * 32));
+    to = PssmSeqOut::in(h->pc_rows.as<char>(), rows);
+  }
+  HS_HIP(h, hs_launch_pssm_seq_rows(key, val, h->sq_sidx.as<uint32_t>(), h->sq_head.as<uint32_t>(),
+                                    h->sq_excl.as<uint32_t>(), nh, rows, d_id_start, fits, h->sq_skey.as<uint32_t>(),
+                                    h->sq_key.as<uint64_t>(), h->sq_idx.as<uint32_t>(), h->sq_part.p, to.m, to.seq,
+                                    to.count, to.best_score, to.best_id, to.lo, to.hi, d_cnt_out, d_seq_cnt_out,
+                                    h->stream));
+  *n_rows = rows;
+  return HS_OK;
+}
+
+// The call with every array on the device; the callers have checked the arguments and the values.  A batch's rows are
+// final (every hit of a profile lies in its batch) and follow the rows of the batches before it.
+hs_status pssm_seq_core(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm, const uint64_t* d_id_start,
+                        uint64_t n_seq, const PssmSeqOut& out, uint64_t cap, uint64_t* n_out, uint64_t* n_hits,
+                        uint64_t* d_cnt_out, uint64_t* d_seq_cnt_out) {
+  memset(&h->prof, 0, sizeof(h->prof));
+  HS_HIP(h, h->counters.reserve(256));
+  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
+  if (d_cnt_out && nm) HS_HIP(h, hipMemsetAsync(d_cnt_out, 0, nm * 8, h->stream));
+  if (d_seq_cnt_out && nm) HS_HIP(h, hipMemsetAsync(d_seq_cnt_out, 0, nm * 8, h->stream));
+  uint64_t total_rows = 0;
+  HS_CHECK(pssm_batches(h, d_S, d_t, nm, n_hits, [&](uint32_t m0, uint32_t mb, uint32_t nh) -> hs_status {
+    uint32_t rows = 0;
+    HS_CHECK(pssm_row_pass(h, m0, mb, nh, d_id_start, n_seq, 0, &out, total_rows, cap, d_cnt_out, d_seq_cnt_out,
+                           "hs_pssm_seq_scan", &rows));
+    total_rows += rows;
+    return HS_OK;
+  }));
+  h->prof.pssm_seq_rows = total_rows;
+  *n_out = total_rows;
+  if (total_rows > cap) return fail(h, HS_ERR_CAPACITY, "row buffers too small; see *n_out");
+  return HS_OK;
+}
+
+// what both forms refuse from the arguments alone (hs_pssm_scan's refusals first)
+hs_status pssm_seq_args(hs_handle* h, const void* S, const void* t, uint64_t nm, const void* id_start, uint64_t n_seq,
+                        const PssmSeqOut& out, uint64_t cap) {
+  HS_CHECK(pssm_args_start(h, nm, S && t ? nullptr : "hs_pssm_seq_scan: S or t is null"));
+  if (cap && !out.all()) return fail(h, HS_ERR_INVALID, "an output array is null");
+  if (!id_start) return fail(h, HS_ERR_INVALID, "hs_pssm_seq_scan: id_start is null");
+  if (n_seq > (1ull << 32)) return fail(h, HS_ERR_INVALID, "hs_pssm_seq_scan: more than 2^32 sequences");
+  if (!n_seq && h->n) return fail(h, HS_ERR_INVALID, "hs_pssm_seq_scan: no sequence owns the index's k-mers");
+  return HS_OK;
+}
+
+// ---- hs_pssm_hit_counts / hs_pssm_refine: the position frequency matrices of a scan's hits (hs_pssm_counts.hip) ----
+// Sites per work item for a batch of ns sites: what HS_OPT_PSSM_COUNT_CHUNK says, else ns / 4096 within 256 .. 2048.
+// An item is one wave's serial walk over its sites (two dependent loads per step), so few long items leave a small
+// batch waiting on a handful of waves; 4096 items are 16 waves on every CU.  At 2048 sites the flush of at most 2400
+// bins is a twentieth of the item's 5 x 10^4 increments at k = 25.
+uint32_t pssm_count_chunk(const hs_handle* h, uint32_t ns) {
+  if (h->knobs.pssm_count_chunk) return h->knobs.pssm_count_chunk;
+  return std::min(2048u, std::max(256u, (ns + 4095u) / 4096u));
+}
+
+// The call with every array on the device; the callers have checked the arguments and the values.  d_id_start null:
+// every hit is a site; else the sites are the best ids of the batch's (profile, sequence) rows.  Every hit of a
+// profile lies in one batch, so a batch finishes its profiles' counts.
+hs_status pssm_counts_core(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm, const uint64_t* d_id_start,
+                           uint64_t n_seq, uint32_t* d_counts, uint64_t* d_cnt_out, uint64_t* d_used_out,
+                           uint64_t* n_hits) {
+  memset(&h->prof, 0, sizeof(h->prof));
+  HS_HIP(h, h->counters.reserve(256));
+  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
+  const int k = (int)h->p.k;
+  const size_t cells = (size_t)h->p.k * h->alphabet;
+  if (nm) HS_HIP(h, hipMemsetAsync(d_counts, 0, nm * cells * 4, h->stream));
+  if (d_cnt_out && nm) HS_HIP(h, hipMemsetAsync(d_cnt_out, 0, nm * 8, h->stream));
+  if (d_used_out && nm) HS_HIP(h, hipMemsetAsync(d_used_out, 0, nm * 8, h->stream));
+  uint64_t sites = 0, items = 0;
+  HS_CHECK(pssm_batches(h, d_S, d_t, nm, n_hits, [&](uint32_t m0, uint32_t mb, uint32_t nh) -> hs_status {
+    const uint32_t *site_m = nullptr, *site_id = nullptr;
+    uint32_t ns = 0;
+    const size_t scan_items = hs_scan_u32_temp((size_t)mb + 1);
+    if (!d_id_start) {  // the hits, ordered on their profile bits alone
+      HS_HIP(h, h->pc_m.reserve((size_t)nh * 4));
+      HS_HIP(h, h->pc_id.reserve((size_t)nh * 4));
+      HS_HIP(h, h->pc_m2.reserve((size_t)nh * 4));
+      HS_HIP(h, h->pc_id2.reserve((size_t)nh * 4));
+      HS_HIP(h, h->temp.reserve(std::max(hs_sort_pairs_u32_u32_temp(nh), scan_items) + 256));
+      HS_HIP(h, hs_launch_pssm_counts_split(h->hit_key.as<uint64_t>(), nh, h->pc_m.as<uint32_t>(),
+                                            h->pc_id.as<uint32_t>(), h->stream));
+      HS_HIP(h, hs_sort_pairs_u32_u32(h->temp.p, h->temp.cap, h->pc_m.as<uint32_t>(), h->pc_m2.as<uint32_t>(),
+                                      h->pc_id.as<uint32_t>(), h->pc_id2.as<uint32_t>(), nh, bit_width_u32(m0 + mb),
+                                      h->stream));
+      site_m = h->pc_m2.as<uint32_t>();
+      site_id = h->pc_id2.as<uint32_t>();
+      ns = nh;
+    } else {  // the rows of hs_pssm_seq_scan, kept on the device: their m and best_id are the sites
+      HS_CHECK(pssm_row_pass(h, m0, mb, nh, d_id_start, n_seq, scan_items, nullptr, 0, 0, d_cnt_out, nullptr,
+                             "hs_pssm_hit_counts", &ns));
+      const PssmSeqOut rows = PssmSeqOut::in(h->pc_rows.as<char>(), ns);
+      site_m = rows.m;
+      site_id = rows.best_id;
+    }
+    const uint32_t ch = pssm_count_chunk(h, ns);
+    HS_HIP(h, h->pc_start.reserve(((size_t)mb + 1) * 4));
+    HS_HIP(h, h->pc_nitem.reserve(((size_t)mb + 1) * 4));
+    HS_HIP(h, h->pc_off.reserve(((size_t)mb + 1) * 4));
+    HS_HIP(h, hs_launch_pssm_counts_items(site_m, ns, m0, mb, ch, h->pc_start.as<uint32_t>(),
+                                          h->pc_nitem.as<uint32_t>(), h->stream));
+    HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, h->pc_nitem.as<uint32_t>(), h->pc_off.as<uint32_t>(),
+                                    (size_t)mb + 1, h->stream));
+    uint32_t n_items = 0;
+    HS_HIP(h, hipMemcpyAsync(&n_items, h->pc_off.as<uint32_t>() + mb, 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    if (!n_items || n_items > (uint64_t)ns / ch + mb)
+      return fail(h, HS_ERR_HIP, "hs_pssm_hit_counts: the item count of a batch is out of range");
+    HS_HIP(h, hs_launch_pssm_counts(h->codes.as<uint8_t>(), k, h->alphabet, site_id, h->pc_start.as<uint32_t>(),
+                                    h->pc_off.as<uint32_t>(), m0, mb, ch, n_items, d_counts, h->stream));
+    HS_HIP(h, hs_launch_pssm_counts_used(d_counts + (size_t)m0 * cells, mb, k, h->alphabet,
+                                         d_used_out ? d_used_out + m0 : nullptr,
+                                         d_cnt_out && !d_id_start ? d_cnt_out + m0 : nullptr, h->stream));
+    sites += ns;
+    items += n_items;
+    return HS_OK;
+  }));
+  h->prof.pssm_count_sites = sites;
+  h->prof.pssm_count_items = items;
+  return HS_OK;
+}
+
+// what every form refuses from the arguments alone (hs_pssm_scan's refusals first); id_start null: every site counts
+hs_status pssm_counts_args(hs_handle* h, const void* S, const void* t, uint64_t nm, const void* id_start,
+                           uint64_t n_seq, const void* counts) {
+  HS_CHECK(pssm_args_start(h, nm, S && t ? nullptr : "hs_pssm_hit_counts: S or t is null"));
+  if (nm && !counts) return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: counts is null");
+  if (id_start && n_seq > (1ull << 32)) return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: more than 2^32 sequences");
+  if (id_start && !n_seq && h->n)
+    return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: no sequence owns the index's k-mers");
+  return HS_OK;
+}
+
+// the values a host-pointer call refuses (t null: the thresholds are the call's own)
+hs_status pssm_counts_values(hs_handle* h, const double* S, const double* t, uint64_t nm, const uint64_t* id_start,
+                             uint64_t n_seq) {
+  const uint32_t bad = pssm_host_bad(h, S, t, nm) | (id_start ? pssm_id_start_bad(h, id_start, n_seq) : 0u);
+  return pssm_refuse(h, bad, "threshold", "hs_pssm_hit_counts");
+}
+
+// A checked host-pointer call: S and t up, counts (and cnt, used) down.  ids_resident: id_start already lies in sq_in
+// (the later iterations of a refinement).
+hs_status pssm_counts_host(hs_handle* h, const double* S, const double* t, uint64_t nm, const uint64_t* id_start,
+                           uint64_t n_seq, bool ids_resident, uint32_t* counts, uint64_t* cnt, uint64_t* used,
+                           uint64_t* n_hits) {
+  HS_CHECK(ensure_device(h));
+  const size_t ka = (size_t)h->p.k * h->alphabet;
+  const size_t sb = ((size_t)n_seq + 1) * 8, cb = std::max<size_t>(16, nm * 8), ob = std::max<size_t>(16, nm * ka * 4);
+  HS_CHECK(pssm_stage_in(h, S, t, nm, h->io_radii));
+  if (id_start) HS_HIP(h, h->sq_in.reserve(sb));
+  HS_HIP(h, h->pc_out.reserve(2 * cb + ob));
+  if (id_start && !ids_resident)
+    HS_HIP(h, hipMemcpyAsync(h->sq_in.p, id_start, sb, hipMemcpyHostToDevice, h->stream));
+  char* const o = h->pc_out.as<char>();
+  uint64_t* const d_cnt = cnt ? reinterpret_cast<uint64_t*>(o) : nullptr;
+  uint64_t* const d_used = used ? reinterpret_cast<uint64_t*>(o + cb) : nullptr;
+  uint32_t* const d_counts = reinterpret_cast<uint32_t*>(o + 2 * cb);
+  HS_CHECK(pssm_counts_core(h, h->io_centers.as<double>(), h->io_radii.as<double>(), nm,
+                            id_start ? h->sq_in.as<uint64_t>() : nullptr, n_seq, d_counts, d_cnt, d_used, n_hits));
+  if (nm) {
+    HS_HIP(h, hipMemcpyAsync(counts, d_counts, nm * ka * 4, hipMemcpyDeviceToHost, h->stream));
+    if (cnt) HS_HIP(h, hipMemcpyAsync(cnt, d_cnt, nm * 8, hipMemcpyDeviceToHost, h->stream));
+    if (used) HS_HIP(h, hipMemcpyAsync(used, d_used, nm * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return HS_OK;
+}
+
+// ---- hs_pssm_topk: the topk best k-mers per profile (kernels, the argument and the three steps: hs_pssm_topk.hip) ----
+// The call with every array on the device; the callers have checked the arguments and the values.  d_floor, d_tused
+// may be null.
+hs_status pssm_topk_core(hs_handle* h, const double* d_S, const double* d_floor, uint64_t nm, uint32_t topk,
+                         uint32_t* d_id, double* d_score, uint32_t* d_count, double* d_tused) {
+  memset(&h->prof, 0, sizeof(h->prof));
+  HS_HIP(h, h->counters.reserve(256));
+  HS_HIP(h, h->knn_total.reserve(16));
+  HS_HIP(h, hipMemsetAsync(h->knn_total.p, 0, 16, h->stream));  // the profiles raised above their floor
+  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
+  const uint32_t n = (uint32_t)h->n, n_s = (uint32_t)std::min<uint64_t>(h->n, h->knobs.pssm_topk_sample);
+  uint64_t total = 0, raised = 0;
+  // (an empty index runs no batch: nothing would write the rows)
+  if (nm && !n) HS_HIP(h, hs_launch_pssm_topk_fill(nm, topk, d_floor, d_id, d_score, d_count, d_tused, h->stream));
+  if (nm && n) {
+    const size_t ka = (size_t)h->p.k * h->alphabet;
+    // profiles per batch: at most 4096 and few enough that the hits to expect -- topk * n / n_s per profile -- stay
+    // within 2^24
+    const uint64_t per = std::max<uint64_t>(1, (uint64_t)topk * n / n_s);
+    const uint32_t MB = (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(1, (1ull << 24) / per));
+    const double* fl = nullptr;  // the batch's floors and thresholds used: step 1 sets them for steps 2 and 3
+    double* tu = nullptr;
+    HS_CHECK(pssm_batch_loop(
+        h, d_S, nm, MB, true, true, &total,
+        [&](uint32_t m0, uint32_t mb, const double** d_t) -> hs_status {  // 1. the sample pass: ms_hash
+          if (!d_tused) HS_HIP(h, h->pt_tused.reserve((size_t)mb * 8));
+          HS_HIP(h, h->pt_parts.reserve(std::max<size_t>(16, hs_pssm_sample_part_bytes(mb, n_s))));
+          *d_t = tu = d_tused ? d_tused + m0 : h->pt_tused.as<double>();
+          fl = d_floor ? d_floor + m0 : nullptr;
+          HS_HIP(h, hipEventRecord(h->ev[10], h->stream));
+          HS_HIP(h, hs_launch_pssm_sample(h->codes.as<uint8_t>(), d_S + m0 * ka, fl, (int)h->p.k, h->alphabet, n, n_s,
+                                          topk, mb, h->pt_parts.p, tu, h->stream));
+          HS_HIP(h, hipEventRecord(h->ev[11], h->stream));
+          return HS_OK;
+        },
+        [&](uint32_t m0, uint32_t mb, uint32_t nh) -> hs_status {  // 3. the selection; it writes the rows
+          const size_t words = ((size_t)mb + 1) * 4;
+          HS_HIP(h, h->knn_cnt.reserve(words));
+          HS_HIP(h, h->knn_off.reserve(words));
+          HS_HIP(h, h->knn_cur.reserve(words));
+          HS_HIP(h, h->hit_key2.reserve(std::max<size_t>(16, (size_t)nh * 8)));
+          HS_HIP(h, h->hit_val2.reserve(std::max<size_t>(16, (size_t)nh * 8)));
+          HS_HIP(h, h->temp.reserve(hs_pssm_topk_temp(mb) + 256));
+          HS_HIP(h, hs_launch_pssm_topk_select(h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(), nh, m0, mb,
+                                               h->knn_cnt.as<uint32_t>(), h->knn_off.as<uint32_t>(),
+                                               h->knn_cur.as<uint32_t>(), h->temp.p, h->temp.cap,
+                                               h->hit_key2.as<uint64_t>(), h->hit_val2.as<uint64_t>(), topk, fl, tu, d_id,
+                                               d_score, d_count, h->knn_total.as<uint64_t>(), h->stream));
+          return HS_OK;
+        }));
+    HS_HIP(h, hipMemcpyAsync(&raised, h->knn_total.p, 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  HS_CHECK(pssm_call_end(h, total));
+  h->prof.pssm_topk_sample = n_s;
+  h->prof.pssm_topk_raised = raised;
+  return HS_OK;
+}
+
+hs_status pssm_topk_args(hs_handle* h, const void* S, uint64_t nm, uint32_t topk, const void* top_id,
+                         const void* top_score, const void* top_count) {
+  HS_CHECK(pssm_args_start(h, nm, nullptr));
+  if (!topk_ok(topk)) return fail(h, HS_ERR_INVALID, "hs_pssm_topk: topk must be 1 .. 64");
+  if (nm && !S) return fail(h, HS_ERR_INVALID, "hs_pssm_topk: S is null");
+  if (nm && (!top_id || !top_score || !top_count)) return fail(h, HS_ERR_INVALID, "an output array is null");
+  return HS_OK;
+}
+
+// ---- hs_pssm_rank: the score of every profile's rank-th best k-mer (kernels, the argument, a round: hs_pssm_rank.hip) ----
+// The call with every array on the device; the callers have checked the arguments and the values (so n > 0 where
+// nm > 0) and know the largest rank.  d_tscan_out, d_rounds may be null.
+hs_status pssm_rank_core(hs_handle* h, const double* d_S, const uint64_t* d_rank, uint64_t nm, uint64_t max_rank,
+                         double* d_t_rank, uint64_t* d_ge, uint64_t* d_gt, double* d_tscan_out, uint32_t* d_rounds) {
+  memset(&h->prof, 0, sizeof(h->prof));
+  HS_HIP(h, h->counters.reserve(256));
+  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
+  const uint32_t n = (uint32_t)h->n, n_s = (uint32_t)std::min<uint64_t>(h->n, h->knobs.pssm_rank_sample);
+  uint64_t total = 0, retries = 0;
+  if (nm && n) {
+    HS_HIP(h, h->pr_resolved.reserve(nm * 4));
+    HS_HIP(h, h->pr_tscan.reserve(nm * 8));
+    HS_HIP(h, h->pr_unres.reserve(16));
+    uint32_t* const resolved = h->pr_resolved.as<uint32_t>();
+    uint32_t* const d_unres = h->pr_unres.as<uint32_t>();
+    double* const tscan = h->pr_tscan.as<double>();
+    HS_HIP(h, hs_launch_pssm_rank_init(nm, resolved, d_unres, h->stream));
+    const uint32_t SB = hs_pssm_rank_sample_batch(n_s);
+    for (uint32_t round = 0;; ++round) {
+      // 1. the sample pass and its select, in sub-batches of its own: the key buffer stays within 2^27 bytes
+      HS_HIP(h, hipEventRecord(h->ev[10], h->stream));
+      for (uint64_t m0 = 0; m0 < nm; m0 += SB) {
+        const uint32_t mb = (uint32_t)std::min<uint64_t>(SB, nm - m0);
+        HS_HIP(h, h->pr_keys.reserve((size_t)mb * n_s * 8));
+        HS_HIP(h, h->pr_off.reserve(((size_t)mb + 1) * 4));
+        HS_HIP(h, h->pr_state.reserve(hs_pssm_rank_state_bytes(mb)));
+        HS_HIP(h, hs_launch_pssm_rank_sample(h->codes.as<uint8_t>(), d_S, d_rank, resolved, (int)h->p.k, h->alphabet, n,
+                                             n_s, round, (uint32_t)m0, mb, h->pr_keys.as<uint64_t>(),
+                                             h->pr_off.as<uint32_t>(), h->pr_state.p, tscan, d_tscan_out, h->stream));
+      }
+      HS_HIP(h, hipEventRecord(h->ev[11], h->stream));
+      HS_HIP(h, hipMemsetAsync(d_unres, 0, 4, h->stream));
+      HS_HIP(h, hipStreamSynchronize(h->stream));
+      h->prof.ms_hash += ev_ms(h, 10, 11);
+      // 2. the scan.  Profiles per batch: at most 4096 and few enough that the hits to expect -- the largest rank's
+      // r_s * n / n_s per profile, n at the ladder's last rung -- stay within 2^24
+      uint64_t r_s = 0;
+      if (hs_pssm_rank_plan_rule(max_rank, n, n_s, round, &r_s)) return fail(h, HS_ERR_HIP, "hs_pssm_rank: no plan");
+      const uint64_t per = r_s > n_s ? n : std::max<uint64_t>(1, r_s * n / n_s);
+      const uint32_t MB = (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(1, (1ull << 24) / per));
+      HS_CHECK(pssm_batch_loop(
+          h, d_S, nm, MB, false, true, &total,
+          [&](uint32_t m0, uint32_t, const double** d_t) -> hs_status {
+            *d_t = tscan + m0;
+            return HS_OK;
+          },
+          // 3. the selection and the resolve step; they run for a batch without hits too: its profiles are counted
+          [&](uint32_t m0, uint32_t mb, uint32_t nh) -> hs_status {
+            const size_t words = ((size_t)mb + 1) * 4;
+            HS_HIP(h, h->knn_cnt.reserve(words));
+            HS_HIP(h, h->knn_off.reserve(words));
+            HS_HIP(h, h->knn_cur.reserve(words));
+            HS_HIP(h, h->hit_key2.reserve(std::max<size_t>(16, (size_t)nh * 8)));
+            HS_HIP(h, h->pr_state.reserve(hs_pssm_rank_state_bytes(mb)));
+            HS_HIP(h, h->temp.reserve(hs_pssm_rank_temp(mb) + 256));
+            HS_HIP(h, hs_launch_pssm_rank_select(h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(), nh, m0, mb,
+                                                 h->knn_cnt.as<uint32_t>(), h->knn_off.as<uint32_t>(),
+                                                 h->knn_cur.as<uint32_t>(), h->temp.p, h->temp.cap,
+                                                 h->hit_key2.as<uint64_t>(), h->pr_state.p, d_rank, resolved, round,
+                                                 d_t_rank, d_ge, d_gt, d_rounds, d_unres, h->stream));
+            return HS_OK;
+          }));
+      uint32_t unresolved = 0;
+      HS_HIP(h, hipMemcpyAsync(&unresolved, d_unres, 4, hipMemcpyDeviceToHost, h->stream));
+      HS_HIP(h, hipStreamSynchronize(h->stream));
+      if (!unresolved) break;
+      retries += unresolved;  // (each of them takes one more round)
+      // (the plan saturates beyond round 16: that round scans at -DBL_MAX and resolves everything)
+      if (round >= 17) return fail(h, HS_ERR_HIP, "hs_pssm_rank: profiles left after the ladder's last rung");
+    }
+  }
+  HS_CHECK(pssm_call_end(h, total));
+  h->prof.pssm_rank_sample = n_s;
+  h->prof.pssm_rank_retries = retries;
+  return HS_OK;
+}
+
+hs_status pssm_rank_args(hs_handle* h, const void* S, const void* rank, uint64_t nm, const void* t_rank,
+                         const void* cnt_ge, const void* cnt_gt) {
+  HS_CHECK(pssm_args_start(h, nm, S ? nullptr : "hs_pssm_rank: S is null"));
+  if (nm && (!rank || !t_rank || !cnt_ge || !cnt_gt))
+    return fail(h, HS_ERR_INVALID, "hs_pssm_rank: rank or an output array is null");
+  return HS_OK;
+}
+
+// The refine loop of hs_pssm_refine (by_rank false: every iteration scans at the thresholds t) and
+// hs_pssm_refine_rank (by_rank: at the thresholds that admit rank[m] k-mers of the iteration's profiles, which
+// hs_pssm_rank finds and t_out hands out): counts of the hits, log-odds against the background, until the counts repeat.
+hs_status pssm_refine(hs_handle* h, const double* S0, const double* t, const uint64_t* rank, bool by_rank, uint64_t nm,
+                      const uint64_t* id_start, uint64_t n_seq, const double* bg, double pseudo, uint32_t n_iter,
+                      double* S_out, double* t_out, uint32_t* counts, uint64_t* used, uint32_t* iters,
+                      uint32_t* converged) {
+  if (!h || !iters || !converged) return HS_ERR_INVALID;
+  *iters = 0;
+  *converged = 0;
+  HS_CHECK(pssm_counts_args(h, S0, by_rank ? (const void*)rank : t, nm, id_start, n_seq, S_out));
+  if (by_rank && nm && !t_out) return fail(h, HS_ERR_INVALID, "hs_pssm_refine_rank: t_out is null");
+  if (n_iter < 1 || n_iter > 100) return fail(h, HS_ERR_INVALID, "hs_pssm_refine: n_iter must be 1 .. 100");
+  const uint32_t k = h->p.k, A = (uint32_t)h->alphabet;
+  double bgv[32];
+  if (!(pseudo > 0.0 && pseudo <= 1.7976931348623157e308) || (bg && !hs_pssm_bg_ok(bg, A, pseudo)))
+    return fail(h, HS_ERR_INVALID, "hs_pssm_refine: the background must be positive and finite, pseudo finite and > 0");
+  HS_CHECK(pssm_counts_values(h, S0, by_rank ? nullptr : t, nm, id_start, n_seq));
+  uint64_t max_rank = 0;
+  if (by_rank) HS_CHECK(pssm_refuse(h, pssm_rank_bad(h, rank, nm, &max_rank), "threshold", "hs_pssm_rank"));
+  const size_t cells = (size_t)k * A;
+  try {
+    uint64_t nh = 0;
+    if (bg) {
+      for (uint32_t a = 0; a < A; ++a) bgv[a] = bg[a];
+    } else {  // the residue composition of the index: one profile that hits everything, every site counted
+      const std::vector<double> zero(cells, 0.0);
+      std::vector<uint32_t> all(cells);
+      const double t0 = 0.0;
+      HS_CHECK(pssm_counts_host(h, zero.data(), &t0, 1, nullptr, 0, false, all.data(), nullptr, nullptr, &nh));
+      if (hs_pssm_background_host(all.data(), k, A, bgv))
+        return fail(h, HS_ERR_INVALID, "hs_pssm_refine: an empty index has no background");
+    }
+    std::vector<double> S(S0, S0 + nm * cells), T(by_rank ? nm : 0, 0.0);
+    std::vector<uint32_t> C(nm * cells), prev;
+    std::vector<uint64_t> U(nm), ge(T.size()), gt(T.size());
+    const double* const ti = by_rank ? T.data() : t;
+    uint32_t done = 0, conv = 0;
+    for (uint32_t i = 0; i < n_iter; ++i) {
+      if (by_rank) HS_CHECK(hs_pssm_rank(h, S.data(), rank, nm, T.data(), ge.data(), gt.data(), nullptr, nullptr));
+      HS_CHECK(pssm_counts_host(h, S.data(), ti, nm, id_start, n_seq, i > 0, C.data(), nullptr, U.data(), &nh));
+      ++done;
+      if (i > 0 && C == prev) {
+        conv = 1;
+        break;
+      }
+      for (uint64_t m = 0; m < nm; ++m)
+        if (U[m] && hs_pssm_log_odds_host(C.data() + m * cells, 1, k, A, bgv, pseudo, S.data() + m * cells))
+          return fail(h, HS_ERR_INVALID, "hs_pssm_refine: a log-odds entry is not finite");
+      prev = C;
+    }
+    for (size_t i = 0; i < S.size(); ++i) S_out[i] = S[i];
+    for (size_t m = 0; m < T.size(); ++m) t_out[m] = T[m];
+    if (counts)
+      for (size_t i = 0; i < C.size(); ++i) counts[i] = C[i];
+    if (used)
+      for (uint64_t m = 0; m < nm; ++m) used[m] = U[m];
+    *iters = done;
+    *converged = conv;
+  } catch (const std::bad_alloc&) {
+    return fail(h, HS_ERR_NOMEM, "hs_pssm_refine: out of host memory");
+  }
+  return HS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+hs_status hs_pssm_scan_dev(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm, uint32_t* d_hit_m,
+                           uint32_t* d_hit_id, double* d_hit_score, uint64_t cap, uint64_t* n_hits, uint64_t* d_cnt) {
+  if (!h || !n_hits) return HS_ERR_INVALID;
+  *n_hits = 0;
+  HS_CHECK(pssm_args(h, d_S, d_t, nm, d_hit_m, d_hit_id, d_hit_score, cap));
+  HS_CHECK(ensure_device(h));
+  HS_CHECK(pssm_dev_check(h, d_S, d_t, nm, nullptr, nullptr, 0, "threshold", "hs_pssm_scan", nullptr));
+  return pssm_core(h, d_S, d_t, nm, d_hit_m, d_hit_id, d_hit_score, cap, n_hits, d_cnt);
+}
+
+hs_status hs_pssm_scan(hs_handle* h, const double* S, const double* t, uint64_t nm, uint32_t* hit_m, uint32_t* hit_id,
+                       double* hit_score, uint64_t cap, uint64_t* n_hits, uint64_t* cnt) {
+  if (!h || !n_hits) return HS_ERR_INVALID;
+  *n_hits = 0;
+  HS_CHECK(pssm_args(h, S, t, nm, hit_m, hit_id, hit_score, cap));
+  HS_CHECK(pssm_refuse(h, pssm_host_bad(h, S, t, nm), "threshold", "hs_pssm_scan"));
+  HS_CHECK(ensure_device(h));
+  HS_CHECK(pssm_stage_in(h, S, t, nm, h->io_radii));
+  HS_HIP(h, h->io_q.reserve(std::max<size_t>(16, cap * 4)));
+  HS_HIP(h, h->io_id.reserve(std::max<size_t>(16, cap * 4)));
+  HS_HIP(h, h->io_dist.reserve(std::max<size_t>(16, cap * 8)));
+  if (cnt) HS_HIP(h, h->io_cand.reserve(std::max<size_t>(16, nm * 8)));
+  const hs_status st = pssm_core(h, h->io_centers.as<double>(), h->io_radii.as<double>(), nm, h->io_q.as<uint32_t>(),
+                                 h->io_id.as<uint32_t>(), h->io_dist.as<double>(), cap, n_hits,
+                                 cnt ? h->io_cand.as<uint64_t>() : nullptr);
+  if (st != HS_OK && st != HS_ERR_CAPACITY) return st;
+  if (cnt && nm) HS_HIP(h, hipMemcpyAsync(cnt, h->io_cand.p, nm * 8, hipMemcpyDeviceToHost, h->stream));
+  const uint64_t nh = *n_hits;
+  if (st == HS_OK && nh) {
+    HS_HIP(h, hipMemcpyAsync(hit_m, h->io_q.p, nh * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(hit_id, h->io_id.p, nh * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(hit_score, h->io_dist.p, nh * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return st;
+}
+
+// The filter's tables on the host (hs_pssm_tables.h): no GPU, no handle
+hs_status hs_pssm_tables(const double* S, const double* t, uint64_t nm, uint32_t k, uint32_t alphabet, uint8_t* code,
+                         double* tau, uint8_t* dead) {
+  return hs_pssm_tables_host(S, t, nm, k, alphabet, code, tau, dead) ? HS_ERR_INVALID : HS_OK;
+}
+
+hs_status hs_pssm_seq_scan_dev(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm,
+                               const uint64_t* d_id_start, uint64_t n_seq, uint32_t* d_out_m, uint32_t* d_out_seq,
+                               uint32_t* d_out_count, double* d_out_best_score, uint32_t* d_out_best_id,
+                               uint32_t* d_out_lo, uint32_t* d_out_hi, uint64_t cap, uint64_t* n_out, uint64_t* n_hits,
+                               uint64_t* d_cnt, uint64_t* d_seq_cnt) {
+  if (!h || !n_out || !n_hits) return HS_ERR_INVALID;
+  *n_out = 0;
+  *n_hits = 0;
+  const PssmSeqOut out{d_out_m, d_out_seq, d_out_count, d_out_best_score, d_out_best_id, d_out_lo, d_out_hi};
+  HS_CHECK(pssm_seq_args(h, d_S, d_t, nm, d_id_start, n_seq, out, cap));
+  HS_CHECK(ensure_device(h));
+  HS_CHECK(pssm_dev_check(h, d_S, d_t, nm, nullptr, d_id_start, n_seq, "threshold", "hs_pssm_seq_scan", nullptr));
+  return pssm_seq_core(h, d_S, d_t, nm, d_id_start, n_seq, out, cap, n_out, n_hits, d_cnt, d_seq_cnt);
+}
+
+hs_status hs_pssm_seq_scan(hs_handle* h, const double* S, const double* t, uint64_t nm, const uint64_t* id_start,
+                           uint64_t n_seq, uint32_t* out_m, uint32_t* out_seq, uint32_t* out_count,
+                           double* out_best_score, uint32_t* out_best_id, uint32_t* out_lo, uint32_t* out_hi,
+                           uint64_t cap, uint64_t* n_out, uint64_t* n_hits, uint64_t* cnt, uint64_t* seq_cnt) {
+  if (!h || !n_out || !n_hits) return HS_ERR_INVALID;
+  *n_out = 0;
+  *n_hits = 0;
+  const PssmSeqOut out{out_m, out_seq, out_count, out_best_score, out_best_id, out_lo, out_hi};
+  HS_CHECK(pssm_seq_args(h, S, t, nm, id_start, n_seq, out, cap));
+  HS_CHECK(pssm_refuse(h, pssm_host_bad(h, S, t, nm) | pssm_id_start_bad(h, id_start, n_seq), "threshold",
+                       "hs_pssm_seq_scan"));
+  HS_CHECK(ensure_device(h));
+  // the rows are staged on the device at the caller's capacity: 32 bytes per row cross PCIe, never the hits
+  const size_t sb = ((size_t)n_seq + 1) * 8, cb = std::max<size_t>(16, nm * 8);
+  HS_CHECK(pssm_stage_in(h, S, t, nm, h->io_radii));
+  HS_HIP(h, h->sq_in.reserve(sb));
+  HS_HIP(h, h->sq_out.reserve(std::max<size_t>(64, (size_t)cap * 32)));
+  if (cnt || seq_cnt) HS_HIP(h, h->io_cand.reserve(2 * cb));
+  HS_HIP(h, hipMemcpyAsync(h->sq_in.p, id_start, sb, hipMemcpyHostToDevice, h->stream));
+  const PssmSeqOut dev = PssmSeqOut::in(h->sq_out.as<char>(), cap);
+  uint64_t* const d_cnt = cnt ? h->io_cand.as<uint64_t>() : nullptr;
+  uint64_t* const d_seq_cnt = seq_cnt ? reinterpret_cast<uint64_t*>(h->io_cand.as<char>() + cb) : nullptr;
+  const hs_status st = pssm_seq_core(h, h->io_centers.as<double>(), h->io_radii.as<double>(), nm,
+                                     h->sq_in.as<uint64_t>(), n_seq, dev, cap, n_out, n_hits, d_cnt, d_seq_cnt);
+  if (st != HS_OK && st != HS_ERR_CAPACITY) return st;
+  if (cnt && nm) HS_HIP(h, hipMemcpyAsync(cnt, d_cnt, nm * 8, hipMemcpyDeviceToHost, h->stream));
+  if (seq_cnt && nm) HS_HIP(h, hipMemcpyAsync(seq_cnt, d_seq_cnt, nm * 8, hipMemcpyDeviceToHost, h->stream));
+  const size_t r = (size_t)*n_out;
+  if (st == HS_OK && r) {
+    HS_HIP(h, hipMemcpyAsync(out_m, dev.m, r * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_seq, dev.seq, r * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_count, dev.count, r * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_best_score, dev.best_score, r * 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_best_id, dev.best_id, r * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_lo, dev.lo, r * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_hi, dev.hi, r * 4, hipMemcpyDeviceToHost, h->stream));
+  }
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return st;
+}
+
+hs_status hs_pssm_hit_counts_dev(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm,
+                                 const uint64_t* d_id_start, uint64_t n_seq, uint32_t* d_counts, uint64_t* d_cnt,
+                                 uint64_t* d_used, uint64_t* n_hits) {
+  if (!h || !n_hits) return HS_ERR_INVALID;
+  *n_hits = 0;
+  HS_CHECK(pssm_counts_args(h, d_S, d_t, nm, d_id_start, n_seq, d_counts));
+  HS_CHECK(ensure_device(h));
+  HS_CHECK(pssm_dev_check(h, d_S, d_t, nm, nullptr, d_id_start, n_seq, "threshold", "hs_pssm_hit_counts", nullptr));
+  return pssm_counts_core(h, d_S, d_t, nm, d_id_start, n_seq, d_counts, d_cnt, d_used, n_hits);
+}
+
+hs_status hs_pssm_hit_counts(hs_handle* h, const double* S, const double* t, uint64_t nm, const uint64_t* id_start,
+                             uint64_t n_seq, uint32_t* counts, uint64_t* cnt, uint64_t* used, uint64_t* n_hits) {
+  if (!h || !n_hits) return HS_ERR_INVALID;
+  *n_hits = 0;
+  HS_CHECK(pssm_counts_args(h, S, t, nm, id_start, n_seq, counts));
+  HS_CHECK(pssm_counts_values(h, S, t, nm, id_start, n_seq));
+  return pssm_counts_host(h, S, t, nm, id_start, n_seq, false, counts, cnt, used, n_hits);
+}
+
+hs_status hs_pssm_topk_dev(hs_handle* h, const double* d_S, const double* d_floor, uint64_t nm, uint32_t topk,
+                           uint32_t* d_top_id, double* d_top_score, uint32_t* d_top_count, double* d_t_used) {
+  if (!h) return HS_ERR_INVALID;
+  HS_CHECK(pssm_topk_args(h, d_S, nm, topk, d_top_id, d_top_score, d_top_count));
+  HS_CHECK(ensure_device(h));
+  HS_CHECK(pssm_dev_check(h, d_S, d_floor, nm, nullptr, nullptr, 0, "floor", "hs_pssm_topk", nullptr));
+  return pssm_topk_core(h, d_S, d_floor, nm, topk, d_top_id, d_top_score, d_top_count, d_t_used);
+}
+
+hs_status hs_pssm_topk(hs_handle* h, const double* S, const double* t_floor, uint64_t nm, uint32_t topk,
+                       uint32_t* top_id, double* top_score, uint32_t* top_count, double* t_used) {
+  if (!h) return HS_ERR_INVALID;
+  HS_CHECK(pssm_topk_args(h, S, nm, topk, top_id, top_score, top_count));
+  HS_CHECK(pssm_refuse(h, pssm_host_bad(h, S, t_floor, nm), "floor", "hs_pssm_topk"));
+  HS_CHECK(ensure_device(h));
+  const size_t e = (size_t)nm * topk;
+  HS_CHECK(pssm_stage_in(h, S, t_floor, nm, h->io_cand));
+  HS_HIP(h, h->io_id.reserve(std::max<size_t>(16, e * 4)));
+  HS_HIP(h, h->io_dist.reserve(std::max<size_t>(16, e * 8)));
+  HS_HIP(h, h->knn_io_count.reserve(std::max<size_t>(16, nm * 4)));
+  if (t_used) HS_HIP(h, h->io_radii.reserve(std::max<size_t>(16, nm * 8)));
+  // the rows are selected on the device: topk x 12 + 4 (+ 8) bytes per profile cross PCIe
+  HS_CHECK(pssm_topk_core(h, h->io_centers.as<double>(), t_floor ? h->io_cand.as<double>() : nullptr, nm, topk,
+                          h->io_id.as<uint32_t>(), h->io_dist.as<double>(), h->knn_io_count.as<uint32_t>(),
+                          t_used ? h->io_radii.as<double>() : nullptr));
+  if (nm) {
+    HS_HIP(h, hipMemcpyAsync(top_id, h->io_id.p, e * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(top_score, h->io_dist.p, e * 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(top_count, h->knn_io_count.p, nm * 4, hipMemcpyDeviceToHost, h->stream));
+    if (t_used) HS_HIP(h, hipMemcpyAsync(t_used, h->io_radii.p, nm * 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return HS_OK;
+}
+
+hs_status hs_pssm_rank_dev(hs_handle* h, const double* d_S, const uint64_t* d_rank, uint64_t nm, double* d_t_rank,
+                           uint64_t* d_cnt_ge, uint64_t* d_cnt_gt, double* d_t_scan, uint32_t* d_rounds) {
+  if (!h) return HS_ERR_INVALID;
+  HS_CHECK(pssm_rank_args(h, d_S, d_rank, nm, d_t_rank, d_cnt_ge, d_cnt_gt));
+  HS_CHECK(ensure_device(h));
+  uint64_t max_rank = 0;
+  HS_CHECK(pssm_dev_check(h, d_S, nullptr, nm, d_rank, nullptr, 0, "threshold", "hs_pssm_rank", &max_rank));
+  return pssm_rank_core(h, d_S, d_rank, nm, max_rank, d_t_rank, d_cnt_ge, d_cnt_gt, d_t_scan, d_rounds);
+}
+
+hs_status hs_pssm_rank(hs_handle* h, const double* S, const uint64_t* rank, uint64_t nm, double* t_rank,
+                       uint64_t* cnt_ge, uint64_t* cnt_gt, double* t_scan, uint32_t* rounds) {
+  if (!h) return HS_ERR_INVALID;
+  HS_CHECK(pssm_rank_args(h, S, rank, nm, t_rank, cnt_ge, cnt_gt));
+  uint64_t max_rank = 0;
+  uint32_t bad = pssm_host_bad(h, S, nullptr, nm);
+  if (!bad) bad = pssm_rank_bad(h, rank, nm, &max_rank);
+  HS_CHECK(pssm_refuse(h, bad, "threshold", "hs_pssm_rank"));
+  HS_CHECK(ensure_device(h));
+  const size_t cb = std::max<size_t>(16, nm * 8);
+  HS_CHECK(pssm_stage_in(h, S, rank, nm, h->pr_rank));
+  HS_HIP(h, h->pr_out.reserve(5 * cb));
+  // one double and two counts per profile (and the diagnostics) cross PCIe
+  char* const o = h->pr_out.as<char>();
+  double* const d_t = reinterpret_cast<double*>(o);
+  uint64_t* const d_ge = reinterpret_cast<uint64_t*>(o + cb);
+  uint64_t* const d_gt = reinterpret_cast<uint64_t*>(o + 2 * cb);
+  double* const d_ts = t_scan ? reinterpret_cast<double*>(o + 3 * cb) : nullptr;
+  uint32_t* const d_ro = rounds ? reinterpret_cast<uint32_t*>(o + 4 * cb) : nullptr;
+  HS_CHECK(pssm_rank_core(h, h->io_centers.as<double>(), h->pr_rank.as<uint64_t>(), nm, max_rank, d_t, d_ge, d_gt, d_ts,
+                          d_ro));
+  if (nm) {
+    HS_HIP(h, hipMemcpyAsync(t_rank, d_t, nm * 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(cnt_ge, d_ge, nm * 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(cnt_gt, d_gt, nm * 8, hipMemcpyDeviceToHost, h->stream));
+    if (t_scan) HS_HIP(h, hipMemcpyAsync(t_scan, d_ts, nm * 8, hipMemcpyDeviceToHost, h->stream));
+    if (rounds) HS_HIP(h, hipMemcpyAsync(rounds, d_ro, nm * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return HS_OK;
+}
+
+hs_status hs_pssm_refine(hs_handle* h, const double* S0, const double* t, uint64_t nm, const uint64_t* id_start,
+                         uint64_t n_seq, const double* bg, double pseudo, uint32_t n_iter, double* S_out,
+                         uint32_t* counts, uint64_t* used, uint32_t* iters, uint32_t* converged) {
+  return pssm_refine(h, S0, t, nullptr, false, nm, id_start, n_seq, bg, pseudo, n_iter, S_out, nullptr, counts, used,
+                     iters, converged);
+}
+
+// hs_pssm_refine with the threshold rule: every iteration scans at the threshold that admits rank[m] k-mers of S_i
+hs_status hs_pssm_refine_rank(hs_handle* h, const double* S0, const uint64_t* rank, uint64_t nm,
+                              const uint64_t* id_start, uint64_t n_seq, const double* bg, double pseudo, uint32_t n_iter,
+                              double* S_out, double* t_out, uint32_t* counts, uint64_t* used, uint32_t* iters,
+                              uint32_t* converged) {
+  return pssm_refine(h, S0, nullptr, rank, true, nm, id_start, n_seq, bg, pseudo, n_iter, S_out, t_out, counts, used,
+                     iters, converged);
+}
+
+}  // extern "C"

@@ -9,13 +9,13 @@
 // decides, and a profile with fewer hits than its rank goes to the next round at a lower t.  The last rung of the
 // ladder is -DBL_MAX, which returns all n >= rank k-mers.  Nothing of the sample shows in the result.
 //
-// A round (hs_capi.hip pssm_rank_core):
+// A round (hs_capi_pssm.hip pssm_rank_core; the scan and the selection of a round run under its pssm_batch_loop):
 //   1. the sample    hs_pssm_rank_sample_kernel has hs_pssm_sample_kernel's structure (the profile's S block in LDS,
 //        sample j = k-mer floor(j * n / n_s), one exact contract score per lane from `codes`) but stores every
 //        descending key to keys[profile][n_s].  The pass runs in sub-batches of profiles so that the key buffer stays
 //        within 2^27 bytes (one profile's n_s keys if they alone exceed that).  The select below, segment = a profile's
 //        n_s keys, rank = the plan's r_s, gives t_scan; r_s > n_s gives -DBL_MAX without a select.
-//   2. the scan at t_scan     hs_pssm.hip's tables, filter and exact pass, unchanged (hs_capi.hip pssm_batch); the
+//   2. the scan at t_scan     hs_pssm.hip's tables, filter and exact pass, unchanged (hs_capi_pssm.hip pssm_batch); the
 //        resolved profiles ride along at +DBL_MAX, which no score reaches.
 //   3. the selection          the batch's unordered hits (m << 32 | id, score bits) are counted per profile, the counts
 //        scanned, the descending keys scattered by profile (the passes of hs_pssm_topk.hip restated, counting in

@@ -165,7 +165,7 @@ __host__ __device__ inline uint32_t hs_pssm_steps(uint32_t k, uint32_t alphabet)
 // an entry the contract refuses: NaN, infinite, or beyond 2^100 (thresholds: NaN or infinite only -- max_abs = inf)
 __host__ __device__ inline bool hs_pssm_bad_value(double v, double max_abs) { return !(fabs(v) <= max_abs) ; }
 
-// ---- host: the exported function's body (hs_capi.hip defines the symbol) ---------------------------------------
+// ---- host: the exported function's body (hs_capi_pssm.hip defines the symbol) ---------------------------------------
 // code [nm][k][alphabet] six-bit e2m3 codes, tau [nm] (+-infinity as above), dead [nm].  Returns 0, or 1 for an
 // argument the contract refuses (nothing is written then).
 inline int hs_pssm_tables_host(const double* S, const double* t, uint64_t nm, uint32_t k, uint32_t alphabet,

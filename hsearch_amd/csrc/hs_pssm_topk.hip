@@ -19,7 +19,7 @@
 //        hs_pssm_sample_merge_kernel, one wave per profile, merges them and writes t_used.  (One workgroup per
 //        profile took 1.9 ms for 16 profiles at n_s = 2^18.)  A list's entries below its topk-th need not be the
 //        range's best, but they are scores of the sample: merged lists have the sample's true topk-th entry.
-//   2. the scan at t_used     hs_pssm.hip's tables, filter and exact pass, unchanged (hs_capi.hip pssm_batch)
+//   2. the scan at t_used     hs_pssm.hip's tables, filter and exact pass, unchanged (hs_capi_pssm.hip pssm_batch)
 //   3. the selection           the batch's unordered hits (m << 32 | id, score bits): counted per profile, the counts
 //        scanned, the hits scattered by profile as (descending key, id); one wave per profile selects as
 //        hs_knn_select_kernel does, on the 128-bit key, and writes its whole row -- entries, padding -- and top_count.
