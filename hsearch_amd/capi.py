@@ -38,7 +38,9 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_pssm_topk", "hs_pssm_topk_dev", "hs_pssm_topk_hits", "hs_pssm_seq_scan", "hs_pssm_seq_scan_dev",
            "hs_pssm_seq_hits", "hs_pssm_hit_counts", "hs_pssm_hit_counts_dev", "hs_pssm_refine", "hs_pssm_count_hits",
            "hs_pssm_rank", "hs_pssm_rank_dev", "hs_pssm_rank_scores", "hs_pssm_rank_plan", "hs_pssm_refine_rank",
-           "hs_pssm_log_odds", "hs_pssm_background"]
+           "hs_pssm_log_odds", "hs_pssm_background", "hs_pssm_pvalue", "hs_pssm_pvalue_dev",
+           "hs_pssm_pvalue_threshold", "hs_pssm_pvalue_threshold_dev", "hs_pssm_null_tables", "hs_pssm_pvalue_host",
+           "hs_pssm_threshold_host"]
 
 TOPK_MAX = 64        # HS_TOPK_MAX: the widest row of query_topk / self_knn / topk_merge
 NO_ID = 0xffffffff   # the id and table of an unused entry of such a row (its distance is +inf)
@@ -72,7 +74,8 @@ class _Profile(C.Structure):
                 ("remove_dead_buckets", C.c_uint64), ("remove_retupled", C.c_uint64),
                 ("pssm_pairs", C.c_uint64), ("pssm_survivors", C.c_uint64), ("pssm_dead", C.c_uint64),
                 ("pssm_mfma_steps", C.c_uint64), ("pssm_seq_rows", C.c_uint64), ("pssm_count_sites", C.c_uint64),
-                ("pssm_count_items", C.c_uint64), ("pssm_rank_sample", C.c_uint64),
+                ("pssm_count_items", C.c_uint64), ("pssm_null_bins", C.c_uint64),
+                ("pssm_null_profiles", C.c_uint64), ("pssm_rank_sample", C.c_uint64),
                 ("pssm_rank_retries", C.c_uint64), ("pssm_topk_sample", C.c_uint64),
                 ("pssm_topk_raised", C.c_uint64)]
 
@@ -361,6 +364,24 @@ def load(hooks=False):
             lib.hs_pssm_refine_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                                 C.c_void_p, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        # PSSM p-values: (h, S, bg, t_lo, nm, hit_m, hit_score, n, p_hi, p_lo); (h, S, bg, t_lo, p, nm, t_p, p_hi, p_lo,
+        # flag); the host forms: include/hsearch.h
+        if hasattr(lib, "hs_pssm_pvalue"):
+            for fn in (lib.hs_pssm_pvalue, lib.hs_pssm_pvalue_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                               C.c_uint64, C.c_void_p, C.c_void_p]
+            for fn in (lib.hs_pssm_pvalue_threshold, lib.hs_pssm_pvalue_threshold_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p]
+            head = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
+            lib.hs_pssm_null_tables.restype = C.c_int
+            lib.hs_pssm_null_tables.argtypes = head + [C.c_void_p] * 6
+            lib.hs_pssm_pvalue_host.restype = C.c_int
+            lib.hs_pssm_pvalue_host.argtypes = head + [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+            lib.hs_pssm_threshold_host.restype = C.c_int
+            lib.hs_pssm_threshold_host.argtypes = head + [C.c_void_p] * 5
         _libs[hooks] = lib
     return _libs[hooks]
 
@@ -927,6 +948,82 @@ def pssm_rank_plan(rank, n, n_s, round=0):
     return int(out.value)
 
 
+def _pssm_null_args(S, bg, t_lo):
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    assert S.ndim == 3, S.shape
+    nm, k, A = S.shape
+    bg = np.ascontiguousarray(bg, dtype=np.float64)
+    assert bg.shape == (A,), bg.shape
+    if t_lo is not None:
+        t_lo = np.ascontiguousarray(np.broadcast_to(np.asarray(t_lo, dtype=np.float64), (nm,)))
+    return S, nm, k, A, bg, t_lo
+
+
+def _opt(a):
+    return None if a is None else _vp(a)
+
+
+def pssm_null_tables(S, bg, t_lo=None, bins=4096, want_lower=True):
+    """hs_pssm_null_tables (host only, no GPU): the tables Engine.pssm_pvalue builds on the device, bit for bit, for S
+    [nm][k][alphabet] under the null bg [alphabet] on a grid of `bins` bins from t_lo (None: 0; a scalar or [nm]) to
+    each profile's maximal score.  dict(q_dn, q_up uint16 [nm][k][alphabet], delta [nm], dead uint8 [nm], cdf_dn,
+    cdf_up [nm][bins]); want_lower=False leaves cdf_up out."""
+    S, nm, k, A, bg, t_lo = _pssm_null_args(S, bg, t_lo)
+    B = int(bins)
+    q_dn, q_up = np.empty((nm, k, A), np.uint16), np.empty((nm, k, A), np.uint16)
+    delta, dead = np.empty(max(nm, 1), np.float64), np.empty(max(nm, 1), np.uint8)
+    cdf_dn = np.empty((nm, max(B, 1)), np.float64)
+    cdf_up = np.empty((nm, max(B, 1)), np.float64) if want_lower else None
+    st = load().hs_pssm_null_tables(_vp(S), nm, k, A, _vp(bg), _opt(t_lo), B, _vp(q_dn), _vp(q_up), _vp(delta),
+                                    _vp(dead), _vp(cdf_dn), _opt(cdf_up))
+    if st:
+        raise HsError(st, "hs_pssm_null_tables")
+    res = dict(q_dn=q_dn, q_up=q_up, delta=delta[:nm], dead=dead[:nm], cdf_dn=cdf_dn)
+    if want_lower:
+        res["cdf_up"] = cdf_up
+    return res
+
+
+def pssm_pvalue_host(S, bg, hit_m, hit_score, t_lo=None, bins=4096, want_lower=True):
+    """hs_pssm_pvalue_host (host only, no GPU): the rule of Engine.pssm_pvalue -- dict(p_hi [n][, p_lo [n]]), the
+    bracket of P{score >= hit_score[i]} under the null bg for profile hit_m[i]."""
+    S, nm, k, A, bg, t_lo = _pssm_null_args(S, bg, t_lo)
+    hit_m = np.ascontiguousarray(hit_m, dtype=np.uint32)
+    hit_score = np.ascontiguousarray(hit_score, dtype=np.float64)
+    n = len(hit_m)
+    assert hit_m.shape == hit_score.shape == (n,)
+    p_hi = np.empty(max(n, 1), np.float64)
+    p_lo = np.empty(max(n, 1), np.float64) if want_lower else None
+    st = load().hs_pssm_pvalue_host(_vp(S), nm, k, A, _vp(bg), _opt(t_lo), int(bins), _vp(hit_m), _vp(hit_score), n,
+                                    _vp(p_hi), _opt(p_lo))
+    if st:
+        raise HsError(st, "hs_pssm_pvalue_host")
+    res = dict(p_hi=p_hi[:n])
+    if want_lower:
+        res["p_lo"] = p_lo[:n]
+    return res
+
+
+def pssm_threshold_host(S, bg, p, t_lo=None, bins=4096, want_lower=True):
+    """hs_pssm_threshold_host (host only, no GPU): the rule of Engine.pssm_pvalue_threshold -- dict(t [nm] the
+    threshold of the p-value p (a scalar or [nm], each in (0, 1]), p_hi [nm][, p_lo [nm]] the bracket at t, flag uint32
+    [nm]: 0 exact on the grid, 1 clipped at t_lo, 2 nothing admissible (t = +DBL_MAX))."""
+    S, nm, k, A, bg, t_lo = _pssm_null_args(S, bg, t_lo)
+    p = np.ascontiguousarray(np.broadcast_to(np.asarray(p, dtype=np.float64), (nm,)))
+    t = np.empty(max(nm, 1), np.float64)
+    p_hi = np.empty(max(nm, 1), np.float64)
+    p_lo = np.empty(max(nm, 1), np.float64) if want_lower else None
+    flag = np.empty(max(nm, 1), np.uint32)
+    st = load().hs_pssm_threshold_host(_vp(S), nm, k, A, _vp(bg), _opt(t_lo), int(bins), _vp(p), _vp(t), _vp(p_hi),
+                                       _opt(p_lo), _vp(flag))
+    if st:
+        raise HsError(st, "hs_pssm_threshold_host")
+    res = dict(t=t[:nm], p_hi=p_hi[:nm], flag=flag[:nm])
+    if want_lower:
+        res["p_lo"] = p_lo[:nm]
+    return res
+
+
 def pssm_log_odds_exact(counts, background, pseudo=1.0):
     """hs_pssm_log_odds (host only): S[m][p][a] = log2((((double)c + pseudo * bg[a]) / ((double)size + pseudo)) /
     bg[a]) for counts uint32 [nm][k][alphabet], every operation rounded to fp64 -- the function Engine.pssm_refine
@@ -1177,7 +1274,7 @@ class Engine:
                "join_min_q": 12, "join_min_m": 13, "sort_from_bit": 14, "build_serial": 15,
                "join_xcd_run": 16, "probe_records": 17, "join_chunk": 18, "summary_chunk": 19, "summary_rows": 20,
                "msf_edge_budget": 21, "join_f6": 22, "pssm_filter": 23, "pssm_topk_sample": 24, "pssm_rank_sample": 26,
-               "pssm_count_chunk": 25}
+               "pssm_count_chunk": 25, "pssm_null_bins": 27}
 
     def set_option(self, name, value):
         """hs_set_option (include/hsearch.h hs_option): path selection / batch sizing; never changes a result."""
@@ -1901,6 +1998,72 @@ class Engine:
                                                C.c_uint64(int(nm)), d_t if d_t else None,
                                                d_cnt_ge if d_cnt_ge else None, d_cnt_gt if d_cnt_gt else None,
                                                d_t_scan if d_t_scan else None, d_rounds if d_rounds else None))
+
+    def _pssm_null_in(self, S, bg, t_lo):
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        nm = S.shape[0]
+        assert S.shape == (nm, self.k, self._alphabet()), S.shape
+        if bg is not None:
+            bg = np.ascontiguousarray(bg, dtype=np.float64)
+            assert bg.shape == (self._alphabet(),), bg.shape
+        if t_lo is not None:
+            t_lo = np.ascontiguousarray(np.broadcast_to(np.asarray(t_lo, dtype=np.float64), (nm,)))
+        return S, nm, bg, t_lo
+
+    def pssm_pvalue(self, S, hit_m, hit_score, bg=None, t_lo=None, want_lower=True):
+        """hs_pssm_pvalue: for n hits (hit_m[i], hit_score[i]) of the profiles S [nm][k][alphabet] -- pssm_scan's, or
+        any list, in any order -- the bracket p_lo <= P{a random k-mer scores >= hit_score[i]} <= p_hi under the null
+        model bg [alphabet] (None: the index's residue composition, one extra scan) on a grid of "pssm_null_bins" bins
+        from t_lo (None: 0; a scalar or [nm]) to each profile's maximal score.  dict(p_hi [n][, p_lo [n]]);
+        want_lower=False runs the upper side alone, which halves the work."""
+        S, nm, bg, t_lo = self._pssm_null_in(S, bg, t_lo)
+        hit_m = np.ascontiguousarray(hit_m, dtype=np.uint32)
+        hit_score = np.ascontiguousarray(hit_score, dtype=np.float64)
+        n = len(hit_m)
+        assert hit_m.shape == hit_score.shape == (n,)
+        p_hi = np.empty(max(n, 1), np.float64)
+        p_lo = np.empty(max(n, 1), np.float64) if want_lower else None
+        self._check(self._lib.hs_pssm_pvalue(self._h, _vp(S), _opt(bg), _opt(t_lo), C.c_uint64(nm), _vp(hit_m),
+                                             _vp(hit_score), C.c_uint64(n), _vp(p_hi), _opt(p_lo)))
+        res = dict(p_hi=p_hi[:n])
+        if want_lower:
+            res["p_lo"] = p_lo[:n]
+        return res
+
+    def pssm_pvalue_dev(self, d_S, nm, d_hit_m, d_hit_score, n, d_p_hi, d_p_lo=None, d_bg=None, d_t_lo=None):
+        """hs_pssm_pvalue_dev: device pointers (ints, e.g. tensor.data_ptr(); d_p_lo, d_bg and d_t_lo may be None) --
+        the hit list pssm_scan_dev returns never crosses PCIe."""
+        self._check(self._lib.hs_pssm_pvalue_dev(self._h, d_S if d_S else None, d_bg if d_bg else None,
+                                                 d_t_lo if d_t_lo else None, C.c_uint64(int(nm)),
+                                                 d_hit_m if d_hit_m else None, d_hit_score if d_hit_score else None,
+                                                 C.c_uint64(int(n)), d_p_hi if d_p_hi else None,
+                                                 d_p_lo if d_p_lo else None))
+
+    def pssm_pvalue_threshold(self, S, p, bg=None, t_lo=None, want_lower=True):
+        """hs_pssm_pvalue_threshold: per profile the threshold t of the p-value p (a scalar or [nm], each in (0, 1]) under
+        the null model of pssm_pvalue: the smallest t whose p_hi is <= p on the grid -- a threshold every profile call
+        accepts.  dict(t [nm], p_hi [nm][, p_lo [nm]] the bracket at t, flag uint32 [nm]: 0 exact on the grid, 1 clipped
+        at t_lo (a lower t_lo might admit more), 2 nothing admissible: t = +DBL_MAX, which no k-mer reaches)."""
+        S, nm, bg, t_lo = self._pssm_null_in(S, bg, t_lo)
+        p = np.ascontiguousarray(np.broadcast_to(np.asarray(p, dtype=np.float64), (nm,)))
+        t = np.empty(max(nm, 1), np.float64)
+        p_hi = np.empty(max(nm, 1), np.float64)
+        p_lo = np.empty(max(nm, 1), np.float64) if want_lower else None
+        flag = np.empty(max(nm, 1), np.uint32)
+        self._check(self._lib.hs_pssm_pvalue_threshold(self._h, _vp(S), _opt(bg), _opt(t_lo), _vp(p), C.c_uint64(nm),
+                                                       _vp(t), _vp(p_hi), _opt(p_lo), _vp(flag)))
+        res = dict(t=t[:nm], p_hi=p_hi[:nm], flag=flag[:nm])
+        if want_lower:
+            res["p_lo"] = p_lo[:nm]
+        return res
+
+    def pssm_pvalue_threshold_dev(self, d_S, d_p, nm, d_t, d_p_hi, d_flag, d_p_lo=None, d_bg=None, d_t_lo=None):
+        """hs_pssm_pvalue_threshold_dev: device pointers (ints; d_p_lo, d_bg and d_t_lo may be None)."""
+        self._check(self._lib.hs_pssm_pvalue_threshold_dev(self._h, d_S if d_S else None, d_bg if d_bg else None,
+                                                           d_t_lo if d_t_lo else None, d_p if d_p else None,
+                                                           C.c_uint64(int(nm)), d_t if d_t else None,
+                                                           d_p_hi if d_p_hi else None, d_p_lo if d_p_lo else None,
+                                                           d_flag if d_flag else None))
 
     def pssm_refine_rank(self, S, rank, n_iter, id_start=None, background=None, pseudo=1.0):
         """hs_pssm_refine_rank: pssm_refine with the threshold rule -- every iteration scans at the threshold that admits

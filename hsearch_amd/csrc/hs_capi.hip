@@ -235,7 +235,7 @@ const struct { const char* name; int option; } kOptionNames[] = {
     {"sort_hits", HS_OPT_SORT_HITS}, {"sync_items", HS_OPT_SYNC_ITEMS}, {"join_min_q", HS_OPT_JOIN_MIN_Q},
     {"join_min_m", HS_OPT_JOIN_MIN_M}, {"sort_from_bit", HS_OPT_SORT_FROM_BIT}, {"build_serial", HS_OPT_BUILD_SERIAL},
     {"join_xcd_run", HS_OPT_JOIN_XCD_RUN}, {"probe_records", HS_OPT_PROBE_RECORDS},
-    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"join_f6", HS_OPT_JOIN_F6}, {"pssm_filter", HS_OPT_PSSM_FILTER}, {"pssm_topk_sample", HS_OPT_PSSM_TOPK_SAMPLE}, {"pssm_rank_sample", HS_OPT_PSSM_RANK_SAMPLE}, {"pssm_count_chunk", HS_OPT_PSSM_COUNT_CHUNK}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS},
+    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"join_f6", HS_OPT_JOIN_F6}, {"pssm_filter", HS_OPT_PSSM_FILTER}, {"pssm_topk_sample", HS_OPT_PSSM_TOPK_SAMPLE}, {"pssm_rank_sample", HS_OPT_PSSM_RANK_SAMPLE}, {"pssm_null_bins", HS_OPT_PSSM_NULL_BINS}, {"pssm_count_chunk", HS_OPT_PSSM_COUNT_CHUNK}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS},
     {"msf_edge_budget", HS_OPT_MSF_EDGE_BUDGET}};
 
 void read_knobs(hs_handle* h) {
@@ -531,6 +531,10 @@ hs_status hs_set_option(hs_handle* h, int option, int64_t value) {
     case HS_OPT_PSSM_RANK_SAMPLE:
       if (value < 1 || value > 0xffffffffll) break;
       kn.pssm_rank_sample = (uint32_t)value;
+      return HS_OK;
+    case HS_OPT_PSSM_NULL_BINS:
+      if (value < 64 || value > 8192) break;
+      kn.pssm_null_bins = (uint32_t)value;
       return HS_OK;
     case HS_OPT_PSSM_COUNT_CHUNK:
       if (value < 0 || value > (1ll << 20)) break;

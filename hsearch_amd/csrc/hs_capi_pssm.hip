@@ -8,6 +8,9 @@
 //   hs_pssm_rank / _dev                  the threshold that admits a profile's rank best k-mers     (hs_pssm_rank.hip)
 //   hs_pssm_refine, hs_pssm_refine_rank  profiles rebuilt from their own hits, iterated
 //   hs_pssm_tables                       the filter's tables on the host (no GPU, no handle)
+//   hs_pssm_pvalue / _dev, hs_pssm_pvalue_threshold / _dev   null-model p-values of hits and the thresholds of
+//                                        p-values; hs_pssm_null_tables, hs_pssm_pvalue_host, hs_pssm_threshold_host: the
+//                                        same rule on the host                                      (hs_pssm_null.hip)
 // What they share, each once:
 //   pssm_args_start, pssm_refuse with pssm_host_bad / pssm_rank_bad / pssm_id_start_bad / pssm_dev_check
 //                     what a call refuses: from its arguments, and from its values on the host or on the device
@@ -26,6 +29,7 @@
 #include "hs_pssm_counts.h"
 #include "hs_pssm_topk.h"
 #include "hs_pssm_rank.h"
+#include "hs_pssm_null.h"
 
 namespace {
 
@@ -704,6 +708,126 @@ hs_status pssm_refine(hs_handle* h, const double* S0, const double* t, const uin
   return HS_OK;
 }
 
+// ---- hs_pssm_pvalue, hs_pssm_pvalue_threshold: the null-model score distribution (kernels: hs_pssm_null.hip) -------
+// What both calls refuse from their arguments.  No index is needed unless the background is the index's composition.
+hs_status pssm_null_args(hs_handle* h, const void* S, const void* bg, uint64_t nm, const char* name) {
+  if (nm >= (1ull << 27)) return fail(h, HS_ERR_INVALID, "nm must be < 2^27 per call");
+  if (nm && !S) return fail(h, HS_ERR_INVALID, std::string(name) + ": S is null");
+  if (nm && !bg && (!h->built || !h->n))
+    return fail(h, !h->built ? HS_ERR_STATE : HS_ERR_INVALID,
+                std::string(name) + ": without bg the index must be built and hold k-mers");
+  return HS_OK;
+}
+
+hs_status pssm_null_refuse(hs_handle* h, uint32_t bad, const char* name) {
+  if (bad & BAD_S) return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
+  if (bad & BAD_T) return fail(h, HS_ERR_INVALID, std::string(name) + ": a t_lo is NaN or infinite");
+  if (bad & 16u) return fail(h, HS_ERR_INVALID, std::string(name) + ": bg must lie in 0 .. 1 with one entry positive");
+  if (bad & 32u) return fail(h, HS_ERR_INVALID, std::string(name) + ": a p is NaN or outside (0, 1]");
+  if (bad & 64u) return fail(h, HS_ERR_INVALID, std::string(name) + ": a hit's profile is >= nm");
+  if (bad & 128u) return fail(h, HS_ERR_INVALID, std::string(name) + ": a hit score is NaN");
+  return HS_OK;
+}
+
+// the values of a host-pointer call
+uint32_t pssm_null_host_bad(const hs_handle* h, const double* S, const double* bg, const double* t_lo, const double* p,
+                            uint64_t nm, const uint32_t* hit_m, const double* hit_score, uint64_t n) {
+  uint32_t bad = pssm_host_bad(h, S, t_lo, nm);
+  if (bg && nm && !hs_pssm_null_bg_ok(bg, (uint32_t)h->alphabet)) bad |= 16u;
+  for (uint64_t m = 0; p && m < nm; ++m)
+    if (!hs_pssm_null_p_ok(p[m])) bad |= 32u;
+  for (uint64_t i = 0; hit_m && i < n; ++i) {
+    if (hit_m[i] >= nm) bad |= 64u;
+    if (hit_score[i] != hit_score[i]) bad |= 128u;
+  }
+  return bad;
+}
+
+// ... of a device-pointer call: the reductions into pn_chk and one read-back
+hs_status pssm_null_dev_check(hs_handle* h, const double* d_S, const double* d_bg, const double* d_t_lo,
+                              const double* d_p, uint64_t nm, const uint32_t* d_hit_m, const double* d_hit_score,
+                              uint64_t n, const char* name) {
+  uint32_t bits = 0;
+  HS_HIP(h, h->pn_chk.reserve(64));
+  HS_HIP(h, hipMemsetAsync(h->pn_chk.p, 0, 64, h->stream));
+  uint32_t* const d_bits = h->pn_chk.as<uint32_t>();
+  HS_HIP(h, hs_launch_pssm_check(d_S, nm * h->p.k * h->alphabet, d_t_lo, d_t_lo ? nm : 0, d_bits, h->stream));
+  HS_HIP(h, hs_launch_pssm_null_check(d_bg, (uint32_t)h->alphabet, d_p, nm, d_hit_m, d_hit_score, n, d_bits, h->stream));
+  HS_HIP(h, hipMemcpyAsync(&bits, d_bits, 4, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return pssm_null_refuse(h, bits, name);
+}
+
+// bg == null: the index's residue composition as hs_pssm_refine takes it (one scan), into pn_bg; else *d_bg stays
+hs_status pssm_null_background(hs_handle* h, const double** d_bg) {
+  if (*d_bg) return HS_OK;
+  const uint32_t k = h->p.k, A = (uint32_t)h->alphabet;
+  double bgv[32];
+  try {
+    const std::vector<double> zero((size_t)k * A, 0.0);
+    std::vector<uint32_t> all((size_t)k * A);
+    const double t0 = 0.0;
+    uint64_t nh = 0;
+    HS_CHECK(pssm_counts_host(h, zero.data(), &t0, 1, nullptr, 0, false, all.data(), nullptr, nullptr, &nh));
+    if (hs_pssm_background_host(all.data(), k, A, bgv))
+      return fail(h, HS_ERR_INVALID, "hs_pssm_pvalue: an empty index has no background");
+  } catch (const std::bad_alloc&) {
+    return fail(h, HS_ERR_NOMEM, "hs_pssm_pvalue: out of host memory");
+  }
+  HS_HIP(h, h->pn_bg.reserve(32 * 8));
+  HS_HIP(h, hipMemcpyAsync(h->pn_bg.p, bgv, A * 8, hipMemcpyHostToDevice, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));  // (bgv leaves scope)
+  *d_bg = h->pn_bg.as<double>();
+  return HS_OK;
+}
+
+// Both calls with every array on the device, checked, the background resolved (pssm_null_background: BEFORE a
+// host-pointer call stages its S, as that scan stages its own).  d_p given: the thresholds (d_t_p, d_flag; d_p_hi / d_p_lo [nm]);
+// else the lookups of the n hits (d_p_hi / d_p_lo [n]).  d_p_lo null: the upper side alone.  Profiles per batch:
+// HS_OPT_QUERY_BATCH if set, else at most 4096 and few enough that the batch's cdf tables stay within 2^28 bytes.
+hs_status pssm_null_core(hs_handle* h, const double* d_S, const double* d_bg, const double* d_t_lo, uint64_t nm,
+                         const double* d_p, const uint32_t* d_hit_m, const double* d_hit_score, uint64_t n,
+                         double* d_t_p, double* d_p_hi, double* d_p_lo, uint32_t* d_flag) {
+  memset(&h->prof, 0, sizeof(h->prof));
+  const uint32_t k = h->p.k, A = (uint32_t)h->alphabet, B = h->knobs.pssm_null_bins;
+  const int sides = d_p_lo ? 2 : 1;
+  const size_t ka = (size_t)k * A;
+  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
+  const uint32_t MB = h->knobs.query_batch
+                          ? h->knobs.query_batch
+                          : (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4096, (1ull << 28) / ((uint64_t)sides * B * 8)));
+  for (uint64_t m0 = 0; m0 < nm; m0 += MB) {
+    const uint32_t mb = (uint32_t)std::min<uint64_t>(MB, nm - m0);
+    HS_HIP(h, h->pn_prof.reserve(hs_pssm_null_prof_bytes(mb)));
+    HS_HIP(h, h->pn_q.reserve(2 * (size_t)mb * ka * 2));
+    HS_HIP(h, h->pn_cdf.reserve((size_t)sides * mb * B * 8));
+    uint16_t* const q_dn = h->pn_q.as<uint16_t>();
+    HS_HIP(h, hipEventRecord(h->ev[10], h->stream));
+    HS_HIP(h, hs_launch_pssm_null_tables(d_S + m0 * ka, d_bg, d_t_lo ? d_t_lo + m0 : nullptr, mb, k, A, B, sides,
+                                         h->pn_prof.p, q_dn, q_dn + (size_t)mb * ka, h->pn_cdf.as<double>(),
+                                         h->stream));
+    HS_HIP(h, hipEventRecord(h->ev[11], h->stream));
+    HS_HIP(h, hipEventRecord(h->ev[6], h->stream));
+    if (d_p)
+      HS_HIP(h, hs_launch_pssm_null_threshold(h->pn_prof.p, h->pn_cdf.as<double>(), mb, k, A, B, sides,
+                                              d_t_lo ? d_t_lo + m0 : nullptr, d_p + m0, d_t_p + m0, d_p_hi + m0,
+                                              d_p_lo ? d_p_lo + m0 : nullptr, d_flag + m0, h->stream));
+    else
+      HS_HIP(h, hs_launch_pssm_null_lookup(h->pn_prof.p, h->pn_cdf.as<double>(), (uint32_t)m0, mb, k, A, B, sides,
+                                           d_hit_m, d_hit_score, n, d_p_hi, d_p_lo, h->stream));
+    HS_HIP(h, hipEventRecord(h->ev[7], h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    h->prof.ms_hash += ev_ms(h, 10, 11);
+    h->prof.ms_finalize += ev_ms(h, 6, 7);
+  }
+  HS_CHECK(pssm_call_end(h, 0));
+  h->prof.pssm_null_bins = B;
+  h->prof.pssm_null_profiles = nm;
+  return HS_OK;
+}
+
+hs_status pssm_null_status(int r) { return r == 0 ? HS_OK : r == 1 ? HS_ERR_INVALID : HS_ERR_NOMEM; }
+
 }  // namespace
 
 extern "C" {
@@ -918,6 +1042,126 @@ hs_status hs_pssm_refine_rank(hs_handle* h, const double* S0, const uint64_t* ra
                               uint32_t* converged) {
   return pssm_refine(h, S0, nullptr, rank, true, nm, id_start, n_seq, bg, pseudo, n_iter, S_out, t_out, counts, used,
                      iters, converged);
+}
+
+hs_status hs_pssm_pvalue_dev(hs_handle* h, const double* d_S, const double* d_bg, const double* d_t_lo, uint64_t nm,
+                             const uint32_t* d_hit_m, const double* d_hit_score, uint64_t n, double* d_p_hi,
+                             double* d_p_lo) {
+  if (!h) return HS_ERR_INVALID;
+  HS_CHECK(pssm_null_args(h, d_S, d_bg, n ? nm : 0, "hs_pssm_pvalue"));
+  if (n && (!d_hit_m || !d_hit_score || !d_p_hi)) return fail(h, HS_ERR_INVALID, "hs_pssm_pvalue: a hit array or p_hi is null");
+  if (!n) return HS_OK;
+  if (!nm) return fail(h, HS_ERR_INVALID, "hs_pssm_pvalue: a hit's profile is >= nm");
+  HS_CHECK(ensure_device(h));
+  HS_CHECK(pssm_null_dev_check(h, d_S, d_bg, d_t_lo, nullptr, nm, d_hit_m, d_hit_score, n, "hs_pssm_pvalue"));
+  HS_CHECK(pssm_null_background(h, &d_bg));
+  return pssm_null_core(h, d_S, d_bg, d_t_lo, nm, nullptr, d_hit_m, d_hit_score, n, nullptr, d_p_hi, d_p_lo, nullptr);
+}
+
+hs_status hs_pssm_pvalue(hs_handle* h, const double* S, const double* bg, const double* t_lo, uint64_t nm,
+                         const uint32_t* hit_m, const double* hit_score, uint64_t n, double* p_hi, double* p_lo) {
+  if (!h) return HS_ERR_INVALID;
+  HS_CHECK(pssm_null_args(h, S, bg, n ? nm : 0, "hs_pssm_pvalue"));
+  if (n && (!hit_m || !hit_score || !p_hi)) return fail(h, HS_ERR_INVALID, "hs_pssm_pvalue: a hit array or p_hi is null");
+  if (!n) return HS_OK;
+  if (!nm) return fail(h, HS_ERR_INVALID, "hs_pssm_pvalue: a hit's profile is >= nm");
+  HS_CHECK(pssm_null_refuse(h, pssm_null_host_bad(h, S, bg, t_lo, nullptr, nm, hit_m, hit_score, n), "hs_pssm_pvalue"));
+  HS_CHECK(ensure_device(h));
+  // in: t_lo [nm], bg [32], hit_score [n], hit_m [n]; out: p_hi [n], p_lo [n]
+  const size_t cb = std::max<size_t>(16, nm * 8), hb = std::max<size_t>(16, n * 8);
+  const double* d_bg0 = nullptr;
+  if (!bg) HS_CHECK(pssm_null_background(h, &d_bg0));
+  HS_CHECK(pssm_stage_in(h, S, nullptr, nm, h->pn_in));
+  HS_HIP(h, h->pn_in.reserve(cb + 256 + 2 * hb));
+  HS_HIP(h, h->pn_out.reserve(2 * hb));
+  char* const in = h->pn_in.as<char>();
+  double* const d_t_lo = t_lo ? reinterpret_cast<double*>(in) : nullptr;
+  const double* const d_bg = bg ? reinterpret_cast<double*>(in + cb) : d_bg0;
+  double* const d_score = reinterpret_cast<double*>(in + cb + 256);
+  uint32_t* const d_m = reinterpret_cast<uint32_t*>(in + cb + 256 + hb);
+  double* const d_hi = h->pn_out.as<double>();
+  double* const d_lo = p_lo ? reinterpret_cast<double*>(h->pn_out.as<char>() + hb) : nullptr;
+  if (t_lo) HS_HIP(h, hipMemcpyAsync(d_t_lo, t_lo, nm * 8, hipMemcpyHostToDevice, h->stream));
+  if (bg) HS_HIP(h, hipMemcpyAsync(in + cb, bg, (size_t)h->alphabet * 8, hipMemcpyHostToDevice, h->stream));
+  HS_HIP(h, hipMemcpyAsync(d_score, hit_score, n * 8, hipMemcpyHostToDevice, h->stream));
+  HS_HIP(h, hipMemcpyAsync(d_m, hit_m, n * 4, hipMemcpyHostToDevice, h->stream));
+  HS_CHECK(pssm_null_core(h, h->io_centers.as<double>(), d_bg, d_t_lo, nm, nullptr, d_m, d_score, n, nullptr, d_hi, d_lo,
+                          nullptr));
+  HS_HIP(h, hipMemcpyAsync(p_hi, d_hi, n * 8, hipMemcpyDeviceToHost, h->stream));
+  if (p_lo) HS_HIP(h, hipMemcpyAsync(p_lo, d_lo, n * 8, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return HS_OK;
+}
+
+hs_status hs_pssm_pvalue_threshold_dev(hs_handle* h, const double* d_S, const double* d_bg, const double* d_t_lo,
+                                       const double* d_p, uint64_t nm, double* d_t_p, double* d_p_hi, double* d_p_lo,
+                                       uint32_t* d_flag) {
+  if (!h) return HS_ERR_INVALID;
+  HS_CHECK(pssm_null_args(h, d_S, d_bg, nm, "hs_pssm_pvalue_threshold"));
+  if (nm && (!d_p || !d_t_p || !d_p_hi || !d_flag))
+    return fail(h, HS_ERR_INVALID, "hs_pssm_pvalue_threshold: p, t_p, p_hi or flag is null");
+  if (!nm) return HS_OK;
+  HS_CHECK(ensure_device(h));
+  HS_CHECK(pssm_null_dev_check(h, d_S, d_bg, d_t_lo, d_p, nm, nullptr, nullptr, 0, "hs_pssm_pvalue_threshold"));
+  HS_CHECK(pssm_null_background(h, &d_bg));
+  return pssm_null_core(h, d_S, d_bg, d_t_lo, nm, d_p, nullptr, nullptr, 0, d_t_p, d_p_hi, d_p_lo, d_flag);
+}
+
+hs_status hs_pssm_pvalue_threshold(hs_handle* h, const double* S, const double* bg, const double* t_lo, const double* p,
+                                   uint64_t nm, double* t_p, double* p_hi, double* p_lo, uint32_t* flag) {
+  if (!h) return HS_ERR_INVALID;
+  HS_CHECK(pssm_null_args(h, S, bg, nm, "hs_pssm_pvalue_threshold"));
+  if (nm && (!p || !t_p || !p_hi || !flag))
+    return fail(h, HS_ERR_INVALID, "hs_pssm_pvalue_threshold: p, t_p, p_hi or flag is null");
+  if (!nm) return HS_OK;
+  HS_CHECK(pssm_null_refuse(h, pssm_null_host_bad(h, S, bg, t_lo, p, nm, nullptr, nullptr, 0), "hs_pssm_pvalue_threshold"));
+  HS_CHECK(ensure_device(h));
+  // in: t_lo [nm], p [nm], bg [32]; out: t_p, p_hi, p_lo, flag [nm]: one double, two probabilities and a flag per profile
+  const size_t cb = std::max<size_t>(16, nm * 8);
+  const double* d_bg0 = nullptr;
+  if (!bg) HS_CHECK(pssm_null_background(h, &d_bg0));
+  HS_CHECK(pssm_stage_in(h, S, nullptr, nm, h->pn_in));
+  HS_HIP(h, h->pn_in.reserve(2 * cb + 256));
+  HS_HIP(h, h->pn_out.reserve(4 * cb));
+  char *const in = h->pn_in.as<char>(), *const out = h->pn_out.as<char>();
+  double* const d_t_lo = t_lo ? reinterpret_cast<double*>(in) : nullptr;
+  double* const d_p = reinterpret_cast<double*>(in + cb);
+  const double* const d_bg = bg ? reinterpret_cast<double*>(in + 2 * cb) : d_bg0;
+  double* const d_tp = reinterpret_cast<double*>(out);
+  double* const d_hi = reinterpret_cast<double*>(out + cb);
+  double* const d_lo = p_lo ? reinterpret_cast<double*>(out + 2 * cb) : nullptr;
+  uint32_t* const d_fl = reinterpret_cast<uint32_t*>(out + 3 * cb);
+  if (t_lo) HS_HIP(h, hipMemcpyAsync(d_t_lo, t_lo, nm * 8, hipMemcpyHostToDevice, h->stream));
+  HS_HIP(h, hipMemcpyAsync(d_p, p, nm * 8, hipMemcpyHostToDevice, h->stream));
+  if (bg) HS_HIP(h, hipMemcpyAsync(in + 2 * cb, bg, (size_t)h->alphabet * 8, hipMemcpyHostToDevice, h->stream));
+  HS_CHECK(pssm_null_core(h, h->io_centers.as<double>(), d_bg, d_t_lo, nm, d_p, nullptr, nullptr, 0, d_tp, d_hi, d_lo,
+                          d_fl));
+  HS_HIP(h, hipMemcpyAsync(t_p, d_tp, nm * 8, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipMemcpyAsync(p_hi, d_hi, nm * 8, hipMemcpyDeviceToHost, h->stream));
+  if (p_lo) HS_HIP(h, hipMemcpyAsync(p_lo, d_lo, nm * 8, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipMemcpyAsync(flag, d_fl, nm * 4, hipMemcpyDeviceToHost, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return HS_OK;
+}
+
+// The same rule on the host (hs_pssm_null.h): no GPU, no handle
+hs_status hs_pssm_null_tables(const double* S, uint64_t nm, uint32_t k, uint32_t alphabet, const double* bg,
+                              const double* t_lo, uint32_t bins, uint16_t* q_dn, uint16_t* q_up, double* delta,
+                              uint8_t* dead, double* cdf_dn, double* cdf_up) {
+  return pssm_null_status(hs_pssm_null_tables_host(S, nm, k, alphabet, bg, t_lo, bins, q_dn, q_up, delta, dead, cdf_dn,
+                                                   cdf_up));
+}
+
+hs_status hs_pssm_pvalue_host(const double* S, uint64_t nm, uint32_t k, uint32_t alphabet, const double* bg,
+                              const double* t_lo, uint32_t bins, const uint32_t* hit_m, const double* hit_score,
+                              uint64_t n, double* p_hi, double* p_lo) {
+  return pssm_null_status(hs_pssm_pvalue_host_rule(S, nm, k, alphabet, bg, t_lo, bins, hit_m, hit_score, n, p_hi, p_lo));
+}
+
+hs_status hs_pssm_threshold_host(const double* S, uint64_t nm, uint32_t k, uint32_t alphabet, const double* bg,
+                                 const double* t_lo, uint32_t bins, const double* p, double* t_p, double* p_hi,
+                                 double* p_lo, uint32_t* flag) {
+  return pssm_null_status(hs_pssm_threshold_host_rule(S, nm, k, alphabet, bg, t_lo, bins, p, t_p, p_hi, p_lo, flag));
 }
 
 }  // extern "C"

@@ -93,6 +93,7 @@ struct Knobs {
   uint32_t query_batch = 0;        // HS_OPT_QUERY_BATCH: queries per batch (0: by L and the free HBM)
   uint32_t pssm_topk_sample = 262144;  // HS_OPT_PSSM_TOPK_SAMPLE: k-mers the sample pass of hs_pssm_topk scores per profile
   uint32_t pssm_rank_sample = 262144;  // HS_OPT_PSSM_RANK_SAMPLE: k-mers the sample pass of hs_pssm_rank scores per profile
+  uint32_t pssm_null_bins = 4096;  // HS_OPT_PSSM_NULL_BINS: bins of hs_pssm_pvalue's score grid (64 .. 8192)
   uint32_t pssm_count_chunk = 0;   // HS_OPT_PSSM_COUNT_CHUNK: sites per work item of hs_pssm_counts.hip (0: by the batch)
   uint32_t summary_chunk = 0;      // HS_OPT_SUMMARY_CHUNK: member slots per work item of hs_summary.hip (0: 512)
   uint32_t summary_rows = 0;       // HS_OPT_SUMMARY_ROWS: rows per batch of hs_cluster_profile (0: by the scratch budget)
@@ -268,6 +269,9 @@ struct hs_handle {
   // sample keys, their segment offsets, the select's state; the call's resolved flags, scan thresholds, and the word
   // that counts a round's unresolved profiles; a host-pointer call's ranks in and outputs on their way out
   DevBuf pr_keys, pr_off, pr_state, pr_resolved, pr_tscan, pr_unres, pr_rank, pr_out;
+  // hs_pssm_pvalue / hs_pssm_pvalue_threshold (hs_pssm_null.hip): a batch's parameters, bin shifts (both sides) and cdf
+  // tables; the background and the check's words; a host-pointer call's arrays in and out
+  DevBuf pn_prof, pn_q, pn_cdf, pn_bg, pn_chk, pn_in, pn_out;
   // hs_pssm_hit_counts (hs_pssm_counts.hip): a batch's sites as (m, id) words and their copies sorted on m, the
   // profiles' run starts, chunk counts and their scan, the rows of the one-site-per-protein mode; a host-pointer
   // call's counts, cnt and used on their way out

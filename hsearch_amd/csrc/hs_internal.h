@@ -908,6 +908,29 @@ hipError_t hs_launch_pssm_rank_select(const uint64_t* d_key, const uint64_t* d_v
                                       uint32_t* d_resolved, uint32_t round, double* d_t_rank, uint64_t* d_cnt_ge,
                                       uint64_t* d_cnt_gt, uint32_t* d_rounds, uint32_t* d_unresolved, hipStream_t s);
 
+// ---- hs_pssm_pvalue (hs_pssm_null.hip: a batch's three steps are written at its head; the rule: hs_pssm_null.h) -------
+size_t hs_pssm_null_prof_bytes(uint32_t mb);  // the parameters of a batch's profiles
+// *d_flag |= 16: bg outside the rule; 32: a p outside (0, 1]; 64: a hit's profile >= nm; 128: a NaN hit score.  d_bg,
+// d_p, d_hit_m (with d_hit_score) may be null: not checked
+hipError_t hs_launch_pssm_null_check(const double* d_bg, uint32_t alphabet, const double* d_p, uint64_t nm,
+                                     const uint32_t* d_hit_m, const double* d_hit_score, uint64_t n, uint32_t* d_flag,
+                                     hipStream_t s);
+// the batch's mb profiles (d_S, d_t_lo -- may be null: 0 -- the batch's first) -> d_prof, the bin shifts d_q_dn / d_q_up
+// [mb][k][alphabet] (d_q_up untouched with sides == 1) and d_cdf [sides][mb][B]
+hipError_t hs_launch_pssm_null_tables(const double* d_S, const double* d_bg, const double* d_t_lo, uint32_t mb,
+                                      uint32_t k, uint32_t alphabet, uint32_t B, int sides, void* d_prof,
+                                      uint16_t* d_q_dn, uint16_t* d_q_up, double* d_cdf, hipStream_t s);
+// the call's n hits: those of profiles m0 .. m0 + mb - 1 get p_hi (and p_lo with sides == 2 and d_p_lo given)
+hipError_t hs_launch_pssm_null_lookup(const void* d_prof, const double* d_cdf, uint32_t m0, uint32_t mb, uint32_t k,
+                                      uint32_t alphabet, uint32_t B, int sides, const uint32_t* d_hit_m,
+                                      const double* d_hit_score, uint64_t n, double* d_p_hi, double* d_p_lo,
+                                      hipStream_t s);
+// every array the batch's: t_p, the bracket at t_p, flag
+hipError_t hs_launch_pssm_null_threshold(const void* d_prof, const double* d_cdf, uint32_t mb, uint32_t k,
+                                         uint32_t alphabet, uint32_t B, int sides, const double* d_t_lo,
+                                         const double* d_p, double* d_t_p, double* d_p_hi, double* d_p_lo,
+                                         uint32_t* d_flag, hipStream_t s);
+
 // ---- hs_pssm_seq_scan (hs_pssm_seq.hip: the passes over a batch's sorted hits are written at its head) -------------
 // head: the n hits sorted by m << 32 | id -> d_seq [n] (the sequence of every hit) and d_head [n + 1] (row starts)
 hipError_t hs_launch_pssm_seq_head(const uint64_t* d_key, uint32_t n, const uint64_t* d_id_start, uint64_t n_seq,

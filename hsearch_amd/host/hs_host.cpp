@@ -828,10 +828,12 @@ static int OpenWindowsIndex(const ProteinDB& db, uint32_t k, int device, hs_hand
 static int ScanProfilesAny(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
                            const std::vector<double>& S, const std::vector<double>& t, uint32_t topn,
                            const std::string& output_file, int device, std::string* err, uint64_t* n_windows,
-                           uint64_t* n_hits_out, uint64_t* n_rows_out = nullptr) {
+                           uint64_t* n_hits_out, uint64_t* n_rows_out = nullptr,
+                           const std::vector<double>* pvalue_floor = nullptr) {
   const uint32_t k = kmer_length;
   const size_t nm = t.size();
-  if (k < 2 || names.size() != nm || S.size() != nm * (size_t)k * HS_ALPHABET) {
+  if (k < 2 || names.size() != nm || S.size() != nm * (size_t)k * HS_ALPHABET ||
+      (pvalue_floor && pvalue_floor->size() != nm)) {
     if (err) *err = k < 2 ? "kmer length 1 is not supported on a FASTA database" : "the profiles do not match the kmer length";
     return HS_ERR_INVALID;
   }
@@ -912,9 +914,18 @@ static int ScanProfilesAny(const ProteinDB& db, uint32_t kmer_length, const std:
     return st;
   }
   if (n_hits_out) *n_hits_out = n_hits;
+  std::vector<double> p_hi;
+  if (pvalue_floor && n_hits) {  // the upper end of every hit's p-value under the database's residue composition
+    p_hi.resize(n_hits);
+    st = hs_pssm_pvalue(h, S.data(), nullptr, pvalue_floor->data(), nm, hm.data(), hs.data(), n_hits, p_hi.data(), nullptr);
+    if (st != HS_OK) {
+      if (err) *err = std::string("hs_pssm_pvalue: ") + hs_last_error(h);
+      return st;
+    }
+  }
   const char* letters = HS_CODE_TO_LETTER;
   std::ofstream fout(output_file.c_str());
-  char num[64];
+  char num[64], pnum[64];
   for (uint64_t i = 0; i < n_hits; ++i) {
     const uint64_t pos = win_pos[hid[i]];
     const size_t s = (size_t)(std::upper_bound(db.start.begin(), db.start.end() - 1, pos) - db.start.begin()) - 1;
@@ -922,9 +933,52 @@ static int ScanProfilesAny(const ProteinDB& db, uint32_t kmer_length, const std:
     for (uint32_t p = 0; p < k; ++p) kmer[p] = letters[db.residues[pos + p]];
     snprintf(num, sizeof(num), "%.17g", hs[i]);
     fout << names[hm[i]] << " " << ProteinLabel(db, s) << "$" << (pos - db.start[s]) << "@" << kmer << "*" << hid[i]
-         << " " << num << "\n";
+         << " " << num;
+    if (pvalue_floor) {
+      snprintf(pnum, sizeof(pnum), "%.17g", p_hi[i]);
+      fout << " " << pnum;
+    }
+    fout << "\n";
   }
   fout.close();
+  return HS_OK;
+}
+
+int HitPvalues(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
+               const std::vector<double>& S, const std::vector<double>& t, const std::vector<double>& t_lo,
+               const std::string& output_file, int device, std::string* err, uint64_t* n_windows, uint64_t* n_hits_out) {
+  return ScanProfilesAny(db, kmer_length, names, S, t, 0, output_file, device, err, n_windows, n_hits_out, nullptr, &t_lo);
+}
+
+int PvalueThresholds(const ProteinDB& db, uint32_t kmer_length, const std::vector<double>& S,
+                     const std::vector<double>& p, const std::vector<double>& t_lo, int device,
+                     std::vector<double>* t_out, std::vector<double>* p_hi, std::vector<double>* p_lo,
+                     std::vector<uint32_t>* flag, std::string* err) {
+  const uint32_t k = kmer_length;
+  const size_t nm = p.size();
+  if (k < 2 || S.size() != nm * (size_t)k * HS_ALPHABET || t_lo.size() != nm) {
+    if (err) *err = k < 2 ? "kmer length 1 is not supported on a FASTA database" : "the profiles do not match the kmer length";
+    return HS_ERR_INVALID;
+  }
+  hs_handle* h = nullptr;
+  uint64_t n_win = 0;
+  std::vector<uint32_t> win_pos;
+  std::vector<uint64_t> id_start;
+  hs_status st = (hs_status)OpenWindowsIndex(db, k, device, &h, &n_win, &win_pos, &id_start, err);
+  HandleCloser closer = {h};
+  if (st != HS_OK) return st;
+  std::vector<double> hi(nm), lo(nm);
+  std::vector<uint32_t> fl(nm);
+  t_out->assign(nm, 0.0);
+  st = hs_pssm_pvalue_threshold(h, S.data(), nullptr, t_lo.data(), p.data(), nm, t_out->data(), hi.data(), lo.data(),
+                                fl.data());
+  if (st != HS_OK) {
+    if (err) *err = std::string("hs_pssm_pvalue_threshold: ") + hs_last_error(h);
+    return st;
+  }
+  if (p_hi) p_hi->swap(hi);
+  if (p_lo) p_lo->swap(lo);
+  if (flag) flag->swap(fl);
   return HS_OK;
 }
 

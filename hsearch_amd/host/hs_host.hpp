@@ -228,6 +228,20 @@ int RefineProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<
                    const std::vector<uint64_t>& rank, uint32_t n_iter, bool one_per_protein, double pseudo, int device,
                    std::vector<double>* S_out, std::vector<double>* t_out, uint32_t* iters, bool* converged,
                    std::string* err);
+// `--pssm FILE --pssm-pvalue P`: per profile the threshold of the p-value p[m] in (0, 1] under the null model of the
+// database's residue composition (hs_pssm_pvalue_threshold with bg = NULL), on a score grid from t_lo[m] to the
+// profile's maximal score.  t_out [nm]; p_hi, p_lo (may be null): the bracket of the p-value at t_out; flag (may be
+// null): 0 exact on the grid, 1 clipped at t_lo, 2 nothing admissible (t_out = +DBL_MAX: a scan finds nothing).  One GPU.
+int PvalueThresholds(const ProteinDB& db, uint32_t kmer_length, const std::vector<double>& S,
+                     const std::vector<double>& p, const std::vector<double>& t_lo, int device,
+                     std::vector<double>* t_out, std::vector<double>* p_hi, std::vector<double>* p_lo,
+                     std::vector<uint32_t>* flag, std::string* err);
+// `--pssm FILE --pssm-pvalue-column 1`: ScanProfiles' lines with " <p_hi>" appended, the upper end of the hit's p-value
+// under the same null model (hs_pssm_pvalue), printed with 17 significant digits; t_lo [nm]: the grids' floors.
+int HitPvalues(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
+               const std::vector<double>& S, const std::vector<double>& t, const std::vector<double>& t_lo,
+               const std::string& output_file, int device, std::string* err, uint64_t* n_windows = nullptr,
+               uint64_t* n_hits = nullptr);
 // center_codes (CentersFromKmers): the centres are k-mers of the exact table -- the one a FASTA
 // database is embedded from -- and travel to the GPU as residue codes (hs_query_codes: k bytes per
 // centre instead of 64 k); the hits are those of the embedded centres, bit for bit.

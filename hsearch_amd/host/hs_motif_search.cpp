@@ -48,6 +48,15 @@
 // and -o holds exactly what --pssm FILE2 writes.  With --pssm-refine I beside it the loop scans at that threshold in
 // every iteration (hs_pssm_refine_rank) and FILE2 holds the final matrices and the last scan's thresholds.
 // --pssm-rank without --pssm or without --pssm-out is refused.
+// --pssm FILE --pssm-pvalue P --pssm-out FILE2: every threshold of FILE is replaced by the threshold of the p-value P
+// (0 < P <= 1) under the null model of the database's residue composition (hs_pssm_pvalue_threshold), on a score grid
+// from --pssm-null-floor X [0] to the profile's maximal score; FILE2 is FILE with those thresholds and -o holds exactly
+// what --pssm FILE2 writes (--pssm-top and --pssm-per-sequence included).  A profile on whose grid nothing is admissible
+// keeps +DBL_MAX and finds nothing; it and the profiles clipped at the floor are reported on stderr by name.  Refused:
+// --pssm-pvalue without --pssm or --pssm-out, with --pssm-rank or --pssm-refine, and a P that is no number in (0, 1].
+// --pssm-pvalue-column 1: every plain hit line gets " <p_hi>" appended, the upper end of the hit's p-value (hs_pssm_pvalue;
+// the grid's floor is the profile's threshold or --pssm-null-floor, whichever is lower); refused with --pssm-top and
+// --pssm-per-sequence.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -104,7 +113,10 @@ const Opt kOpts[] = {
     {"pssm-top", 'n', "with --pssm: per profile only its N best windows, 1..64, among those at or above the file's threshold, by descending score then window index [off: every hit]", false},
     {"pssm-per-sequence", 'e', "with --pssm: instead of the hits, one line per (profile, protein) with a hit: count, best window and its score, span; not with --pssm-top [0]", false},
     {"pssm-refine", 'R', "with --pssm and --pssm-out: first rebuild the profiles from their own hits, at most N scans, 1..100; -o then holds what --pssm with the refined file gives [off]", false},
-    {"pssm-out", 'O', "with --pssm-refine or --pssm-rank: write the profiles (refined, with the rank's thresholds) to this file", false},
+    {"pssm-out", 'O', "with --pssm-refine, --pssm-rank or --pssm-pvalue: write the profiles (refined, with the new thresholds) to this file", false},
+    {"pssm-pvalue", 'v', "with --pssm and --pssm-out: replace every threshold by the threshold of this p-value, 0 < P <= 1, under the null model of the database's residue composition; -o then holds what --pssm with that file gives [off]", false},
+    {"pssm-null-floor", 'f', "with --pssm-pvalue or --pssm-pvalue-column: the lowest score the null model's grid covers [0; for the column: the profile's threshold if that is lower]", false},
+    {"pssm-pvalue-column", 'C', "with --pssm: append the upper end of every hit's p-value to its line; not with --pssm-top or --pssm-per-sequence [0]", false},
     {"pssm-rank", 'k', "with --pssm and --pssm-out: replace every threshold by the score of the profile's N-th best window over the database, 1..windows; -o then holds what --pssm with that file gives [off]", false},
     {"pssm-one-per-protein", 'I', "with --pssm-refine: only the best window of every protein counts [0]", false},
     {"pssm-pseudo", 'u', "with --pssm-refine: pseudo-counts of the log-odds, > 0 [1]", false},
@@ -204,6 +216,45 @@ int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::str
       return EXIT_FAILURE;
     }
   }
+  double pvalue = 0.0, null_floor = 0.0;  // pvalue 0: the thresholds as the file gives them
+  const bool with_floor = val.count("pssm-null-floor") != 0;
+  const bool pvalue_column = val.count("pssm-pvalue-column") && atoi(val["pssm-pvalue-column"].c_str()) != 0;
+  if (val.count("pssm-pvalue")) {
+    const std::string& text = val["pssm-pvalue"];
+    char* end = nullptr;
+    pvalue = strtod(text.c_str(), &end);
+    if (text.empty() || end == text.c_str() || *end || !(pvalue > 0.0) || !(pvalue <= 1.0)) {
+      fprintf(stderr, "ERROR: --pssm-pvalue takes a probability, 0 < P <= 1\n");
+      return EXIT_FAILURE;
+    }
+    if (!val.count("pssm-out")) {
+      fprintf(stderr, "ERROR: --pssm-pvalue needs --pssm-out: the file the profiles and their new thresholds are written to\n");
+      return EXIT_FAILURE;
+    }
+    if (rank_n || refine) {
+      fprintf(stderr, "ERROR: --pssm-pvalue sets the thresholds from a null model: it cannot be combined with %s\n",
+              rank_n ? "--pssm-rank" : "--pssm-refine");
+      return EXIT_FAILURE;
+    }
+  }
+  if (pvalue_column && (top_n || per_sequence)) {
+    fprintf(stderr, "ERROR: --pssm-pvalue-column belongs to the plain hit lines: it cannot be combined with %s\n",
+            top_n ? "--pssm-top" : "--pssm-per-sequence");
+    return EXIT_FAILURE;
+  }
+  if (with_floor) {
+    const std::string& text = val["pssm-null-floor"];
+    char* end = nullptr;
+    null_floor = strtod(text.c_str(), &end);
+    if (text.empty() || end == text.c_str() || *end || !(fabs(null_floor) <= 1.7976931348623157e308)) {
+      fprintf(stderr, "ERROR: --pssm-null-floor takes a finite score\n");
+      return EXIT_FAILURE;
+    }
+    if (!(pvalue > 0.0) && !pvalue_column) {
+      fprintf(stderr, "ERROR: --pssm-null-floor belongs to --pssm-pvalue or --pssm-pvalue-column: it cannot be given without them\n");
+      return EXIT_FAILURE;
+    }
+  }
   const bool one_per_protein = val.count("pssm-one-per-protein") && atoi(val["pssm-one-per-protein"].c_str()) != 0;
   const uint32_t kmer_length = (uint32_t)strtoul(val["len"].c_str(), nullptr, 10);
   const int device = val.count("device") ? atoi(val["device"].c_str()) : 0;
@@ -245,6 +296,30 @@ int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::str
       }
       std::cout << "thresholds set to the score of rank " << rank_n << std::endl;
     }
+    if (pvalue > 0.0) {
+      const std::vector<double> ps(names.size(), pvalue), floors(names.size(), null_floor);
+      std::vector<double> t_p;
+      std::vector<uint32_t> flag;
+      const int pst = hsearch::PvalueThresholds(prodb, kmer_length, S, ps, floors, device, &t_p, nullptr, nullptr, &flag, &err);
+      if (pst != 0) {
+        fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), pst);
+        return EXIT_FAILURE;
+      }
+      t.swap(t_p);
+      for (size_t m = 0; m < names.size(); ++m) {
+        if (flag[m] == 1)
+          fprintf(stderr, "NOTE: profile %s: the threshold is clipped at the floor %.17g; a lower --pssm-null-floor may admit more\n",
+                  names[m].c_str(), null_floor);
+        if (flag[m] == 2)
+          fprintf(stderr, "NOTE: profile %s: no score has a p-value of at most %.17g; it keeps +DBL_MAX and finds nothing\n",
+                  names[m].c_str(), pvalue);
+      }
+      if (!hsearch::WritePssmFile(val["pssm-out"], kmer_length, names, S, t, &err)) {
+        fprintf(stderr, "ERROR: %s\n", err.c_str());
+        return EXIT_FAILURE;
+      }
+      std::cout << "thresholds set to the p-value " << pvalue << std::endl;
+    }
     if (refine) {
       std::vector<double> refined, t_last;
       uint32_t iters = 0;
@@ -268,8 +343,13 @@ int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::str
     struct timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     uint64_t n_windows = 0, n_hits = 0, n_rows = 0;
+    std::vector<double> column_floor(t);  // the column's grid: from the threshold, or from the floor if that is lower
+    for (double& f : column_floor)
+      if (with_floor && null_floor < f) f = null_floor;
     const int st = per_sequence ? hsearch::ScanProfilesPerSequence(prodb, kmer_length, names, S, t, val["output"], device,
                                                                    &err, &n_windows, &n_hits, &n_rows)
+                   : pvalue_column ? hsearch::HitPvalues(prodb, kmer_length, names, S, t, column_floor, val["output"], device,
+                                                         &err, &n_windows, &n_hits)
                    : top_n ? hsearch::ScanProfilesTopN(prodb, kmer_length, names, S, t, top_n, val["output"], device, &err,
                                                        &n_windows, &n_hits)
                            : hsearch::ScanProfiles(prodb, kmer_length, names, S, t, val["output"], device, &err,
@@ -340,13 +420,19 @@ int main(int argc, const char* argv[]) {
     fprintf(stderr, "ERROR: --pssm-per-sequence reduces the hits of --pssm: it cannot be given without it\n");
     return EXIT_FAILURE;
   }
+  for (const char* name : {"pssm-pvalue", "pssm-null-floor", "pssm-pvalue-column"})
+    if (val.count(name) && !with_pssm) {
+      fprintf(stderr, "ERROR: --%s belongs to --pssm FILE: it cannot be given without it\n", name);
+      return EXIT_FAILURE;
+    }
   if (val.count("pssm-rank") && !with_pssm) {
     fprintf(stderr, "ERROR: --pssm-rank sets the thresholds of --pssm FILE: it cannot be given without it\n");
     return EXIT_FAILURE;
   }
   for (const char* name : {"pssm-refine", "pssm-out", "pssm-one-per-protein", "pssm-pseudo"})
     if (val.count(name) && !(with_pssm && (val.count("pssm-refine") ||
-                                           (std::string(name) == "pssm-out" && val.count("pssm-rank"))))) {
+                                           (std::string(name) == "pssm-out" &&
+                                            (val.count("pssm-rank") || val.count("pssm-pvalue")))))) {
       fprintf(stderr, "ERROR: --%s belongs to --pssm FILE --pssm-refine N --pssm-out FILE2: it cannot be given without them\n",
               name);
       return EXIT_FAILURE;

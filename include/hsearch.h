@@ -116,6 +116,8 @@ typedef struct hs_profile {
   uint64_t pssm_seq_rows;      /* hs_pssm_seq_scan*: the (profile, sequence) rows the call found (its *n_out) */
   uint64_t pssm_count_sites;   /* hs_pssm_hit_counts*: the sites counted, the sum of used[] */
   uint64_t pssm_count_items;   /* hs_pssm_hit_counts*: the (profile run, chunk) work items of the counting kernel */
+  uint64_t pssm_null_bins;     /* hs_pssm_pvalue*: the bins B of the score grid the call used (HS_OPT_PSSM_NULL_BINS) */
+  uint64_t pssm_null_profiles; /* hs_pssm_pvalue*: profiles whose null distribution the call convolved */
   uint64_t pssm_rank_sample;   /* hs_pssm_rank*: the sample size n_s = min(n, HS_OPT_PSSM_RANK_SAMPLE) the call used */
   uint64_t pssm_rank_retries;  /* hs_pssm_rank*: the sum of rounds[]: profiles times the extra rounds they took */
   uint64_t pssm_topk_sample;   /* hs_pssm_topk*: the sample size n_s = min(n, HS_OPT_PSSM_TOPK_SAMPLE) the call used */
@@ -212,6 +214,8 @@ typedef enum hs_option {
                                 a batch's sites / 4096, within 256 .. 2048.  Never shows in a count */
   HS_OPT_PSSM_RANK_SAMPLE = 26, /* hs_pssm_rank: k-mers of the index the sample pass scores per profile (>= 1, default
                                 262144 = 2^18; the index's size where it is smaller).  Shows in t_scan and rounds only */
+  HS_OPT_PSSM_NULL_BINS = 27, /* hs_pssm_pvalue, hs_pssm_pvalue_threshold: bins of the score grid the null distribution
+                                 is convolved on (64 .. 8192, default 4096): more bins, a tighter p_hi / p_lo */
   HS_OPT_JOIN_XCD_RUN = 16  /* hs_join8x_kernel's work items dealt in runs of this many chunks per XCD, each XCD's
                                 waves on their own runs (a run's items stream the same query tiles: one L2 fetches
                                 them instead of eight).  0: one counter for the chip; -1 (default): by the size
@@ -1385,8 +1389,8 @@ HS_API hs_status hs_pssm_background(const uint32_t* counts_row, uint32_t k, uint
  * hs_profile after the call: the pssm_* scan fields and hits summed over every scan the call ran; pssm_rank_sample,
  * pssm_rank_retries; ms_hash (sample pass + its select), ms_verify (tables + filter), ms_finalize (exact pass +
  * select), ms_total.  Every other entry point runs as before, launch for launch.
- * Out of scope: per-protein ranks, thresholds from a null model, multi-GPU drivers -- ranks do NOT merge from per-GPU
- * thresholds (the rank-th best of a union is no function of the parts' rank-th bests). */
+ * Out of scope: per-protein ranks, multi-GPU drivers -- ranks do NOT merge from per-GPU thresholds (the rank-th best of
+ * a union is no function of the parts' rank-th bests).  Thresholds from a null model: hs_pssm_pvalue_threshold below. */
 HS_API hs_status hs_pssm_rank(hs_handle* h, const double* S, const uint64_t* rank, uint64_t nm, double* t_rank,
                               uint64_t* cnt_ge, uint64_t* cnt_gt, double* t_scan, uint32_t* rounds);
 /* ... every pointer in device memory (streams: as hs_pssm_scan_dev) */
@@ -1411,6 +1415,77 @@ HS_API hs_status hs_pssm_refine_rank(hs_handle* h, const double* S0, const uint6
                                      const uint64_t* id_start, uint64_t n_seq, const double* bg, double pseudo,
                                      uint32_t n_iter, double* S_out, double* t_out, uint32_t* counts, uint64_t* used,
                                      uint32_t* iters, uint32_t* converged);
+
+/* ---- PSSM p-values: thresholds and hit significance from a null model ------------------------------------------- */
+
+/* hs_pssm_topk and hs_pssm_rank read a threshold off the database.  This is the answer that does not depend on it: the
+ * probability that a random k-mer scores at least t, and the t that belongs to a probability.  Scores of two profiles
+ * become comparable, and a threshold can be carried from one database to the next.
+ *
+ * The null model: positions independent, residue a with weight bg[a].  bg [alphabet]: every entry finite and within
+ * 0 .. 1, at least one positive; it is NOT renormalised (hs_pssm_background's output does not sum to exactly 1), and P
+ * below is the product measure of these weights.  bg == NULL (handle forms): the index's residue composition exactly as
+ * hs_pssm_refine takes it -- one extra scan; the index must be built and hold k-mers then.  With bg given no index is
+ * needed.
+ * S [nm][k][alphabet]: as for hs_pssm_scan, with the same value checks.  t_lo [nm] (NULL: 0 for every profile; each
+ * finite): the lowest score the caller wants p-values for -- the grid of `bins` = B bins (HS_OPT_PSSM_NULL_BINS, default
+ * 4096, 64 .. 8192; an argument of the host forms) covers t_lo .. the profile's maximal score.  0 is the natural choice
+ * for log-odds.  A profile whose maximal score lies below t_lo is dead: p_hi = 0 at and above t_lo.
+ *
+ * THE INVARIANT: for every t,  p_lo(t) <= P{ x : fl(x) >= t } <= p_hi(t),  fl the contract's rounded score.  The rule,
+ * its explicit margins and the proof: hsearch_amd/csrc/hs_pssm_null.h.  In short: the entries
+ * are moved up (down) by the bound of the sum's rounding, the deficits below each position's maximum are rounded down
+ * (up) to multiples of delta >= (max score - t_lo) / (B - 1), the two integer distributions are convolved over the k
+ * positions in a fixed order of fp64 operations, summed to cdfs in a fixed blocked order, and looked up at J_hi(t) =
+ * floor((max - t) / delta) moved up, J_lo moved down, times (1 +- e) with e = (k (alphabet + 1) + 202) 2^-52, -+ 1e-300.
+ * A forbidden residue of -10^30 saturates its own bin shift and does not widen the grid.  t below the grid (J_hi >= B):
+ * p_hi = 1, which reads "not computed".  p_hi / p_lo tightens with B and widens with k; both are monotone in t.
+ *
+ * hs_pssm_pvalue: the bracket of n hits (hit_m[i] < nm, hit_score[i] anything but NaN) in any order -- what
+ * hs_pssm_scan returns, or any other list.  p_lo may be NULL: the upper side alone runs, which halves the work.
+ * hs_pssm_pvalue_threshold: per profile the threshold of p[m] in (0, 1]: with J* the largest bin whose p_hi is <= p[m],
+ * t_p[m] = the smallest double t with J_hi(t) <= J* and flag[m] = 0 -- then p_hi(t_p) <= p, and p_hi of the next double
+ * below t_p exceeds p; J* = B - 1: t_p = t_lo[m], flag 1 (clipped: a lower t_lo might admit more); no such bin: t_p =
+ * +DBL_MAX, flag 2 (nothing is admissible on this grid; a scan at t_p finds nothing).  p_hi [nm], p_lo [nm] (may be
+ * NULL): the bracket at t_p.  t_p is a threshold every profile call above accepts.
+ * Errors, reported before anything is written: nm >= 2^27; a null S, or a null bg without a built, non-empty index
+ * (HS_ERR_STATE for an unbuilt one); a profile entry NaN, infinite or beyond 2^100; a bg or t_lo outside the rule above;
+ * a p that is NaN or outside (0, 1]; hit_m >= nm; a NaN hit_score; null outputs (p_lo excepted) with work to do.  The
+ * _dev forms find the value errors on the device with one read-back.  nm == 0 (thresholds) and n == 0 (p-values) are
+ * HS_OK with nothing written.
+ * Purity: the outputs are a pure function of (S, bg, t_lo, bins, and the hits or p).  HS_OPT_QUERY_BATCH (profiles per
+ * batch here; default: at most 4096 and few enough that a batch's cdf tables stay within 2^28 bytes) and scheduling do
+ * not show.  The device's bits are the host forms' bits.
+ * hs_profile after the call: pssm_null_bins, pssm_null_profiles, ms_hash (the tables and the convolution), ms_finalize
+ * (the lookups or the threshold search), ms_total.  Every other entry point runs as before, launch for launch.
+ * Out of scope: more than 8192 bins, Markov backgrounds, E-values (a multiplication by n * nm the caller can do), a
+ * p-value form of hs_pssm_refine, per-protein p-values, multi-GPU drivers (the rule does not read the database). */
+HS_API hs_status hs_pssm_pvalue(hs_handle* h, const double* S, const double* bg, const double* t_lo, uint64_t nm,
+                                const uint32_t* hit_m, const double* hit_score, uint64_t n, double* p_hi, double* p_lo);
+/* ... every pointer in device memory (streams: as hs_pssm_scan_dev): the hit list of hs_pssm_scan_dev never crosses PCIe */
+HS_API hs_status hs_pssm_pvalue_dev(hs_handle* h, const double* d_S, const double* d_bg, const double* d_t_lo,
+                                    uint64_t nm, const uint32_t* d_hit_m, const double* d_hit_score, uint64_t n,
+                                    double* d_p_hi, double* d_p_lo);
+HS_API hs_status hs_pssm_pvalue_threshold(hs_handle* h, const double* S, const double* bg, const double* t_lo,
+                                          const double* p, uint64_t nm, double* t_p, double* p_hi, double* p_lo,
+                                          uint32_t* flag);
+HS_API hs_status hs_pssm_pvalue_threshold_dev(hs_handle* h, const double* d_S, const double* d_bg,
+                                              const double* d_t_lo, const double* d_p, uint64_t nm, double* d_t_p,
+                                              double* d_p_hi, double* d_p_lo, uint32_t* d_flag);
+/* The same rule on the host (no GPU, no handle); k within 1 .. 75, alphabet within 1 .. 32, bins within 64 .. 8192, bg
+ * required; everything else refused as above, HS_ERR_INVALID with nothing written.  hs_pssm_null_tables: the tables the
+ * device builds, bit for bit -- q_dn, q_up [nm][k][alphabet] the bin shifts (saturated at bins), delta [nm], dead [nm],
+ * cdf_dn, cdf_up [nm][bins]; any output may be NULL.  hs_pssm_pvalue_host and hs_pssm_threshold_host together are the
+ * whole rule. */
+HS_API hs_status hs_pssm_null_tables(const double* S, uint64_t nm, uint32_t k, uint32_t alphabet, const double* bg,
+                                     const double* t_lo, uint32_t bins, uint16_t* q_dn, uint16_t* q_up, double* delta,
+                                     uint8_t* dead, double* cdf_dn, double* cdf_up);
+HS_API hs_status hs_pssm_pvalue_host(const double* S, uint64_t nm, uint32_t k, uint32_t alphabet, const double* bg,
+                                     const double* t_lo, uint32_t bins, const uint32_t* hit_m, const double* hit_score,
+                                     uint64_t n, double* p_hi, double* p_lo);
+HS_API hs_status hs_pssm_threshold_host(const double* S, uint64_t nm, uint32_t k, uint32_t alphabet, const double* bg,
+                                        const double* t_lo, uint32_t bins, const double* p, double* t_p, double* p_hi,
+                                        double* p_lo, uint32_t* flag);
 
 /* Replaces Clustering() (hclust2.cpp:86-151) with explicit planes a[L][K][d], b[L][K]: table by
  * table, an LSH table over the not-yet-absorbed k-mers, then greedy leader clustering inside every
