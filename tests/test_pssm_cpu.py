@@ -4,7 +4,6 @@ THE INVARIANT: for every k-mer x, if the contract's ROUNDED fp64 score (pssm_ref
 t[m], then F(x) = sum_p E2M3[code[m][p][x_p]] >= tau[m]; dead[m] = 1 only if no k-mer hits.  F is a sum of multiples
 of 1/8 and is computed here exactly.  For k = 3 over 4 residues all 64 k-mers are checked, so "only if no k-mer hits"
 is checked exhaustively too."""
-import itertools
 import os
 import subprocess
 
@@ -13,42 +12,16 @@ import pytest
 
 from hsearch_amd import HsError, capi
 
+import pssm_cases
 import pssm_ref
+from pssm_cases import ALL64, check_invariant
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ALL64 = np.array(list(itertools.product(range(4), repeat=3)), dtype=np.uint8)
-
-
-def check_invariant(S, t, codes):
-    """Asserts the invariant for profiles S, thresholds t over the k-mers `codes`; returns (hits, passed) [nm]."""
-    T = capi.pssm_tables(S, t)
-    assert T["code"].max() < 64
-    sc = pssm_ref.scores(S, codes)
-    hit = sc >= np.asarray(t)[:, None]
-    F = pssm_ref.filter_values(T["code"], codes)
-    assert np.array_equal(F * 8, np.round(F * 8))
-    tau = T["tau"]
-    assert np.all((tau * 8 == np.round(tau * 8)) | np.isinf(tau))
-    passed = (F >= tau[:, None]) & (T["dead"] == 0)[:, None]
-    lost = hit & ~passed
-    assert not lost.any(), "profile %d loses k-mer %d" % tuple(np.argwhere(lost)[0])
-    assert np.all(np.isposinf(tau) == (T["dead"] == 1))
-    return hit.sum(axis=1), passed.sum(axis=1), T
 
 
 def test_exhaustive_random_profiles():
-    rng = np.random.default_rng(2301)
-    nm = 400
-    scale = 2.0 ** rng.integers(-20, 20, size=(nm, 1, 1))
-    S = rng.uniform(-1, 1, size=(nm, 3, 4)) * scale
-    S[::7, 1, 2] = -1e30                      # a forbidden residue beside entries of order 1
-    S[::11] = S[::11, :1, :1]                 # constant profiles
-    S[5::13] = np.round(S[5::13] / scale[5::13] * 4) / 4 * scale[5::13]   # dyadic: many ties
-    sc = pssm_ref.scores(S, ALL64)
-    t = rng.uniform(-3, 3, size=nm) * scale[:, 0, 0]
-    at = rng.integers(0, 64, size=nm)
-    t[::3] = sc[np.arange(nm), at][::3]      # thresholds equal to an attained score
-    t[1::17] = sc.max(axis=1)[1::17]         # ... the attainable maximum
+    S, t = pssm_cases.random_scales()
+    nm = len(S)
     hits, passed, T = check_invariant(S, t, ALL64)
     assert hits[::3].min() >= 1
     # the filter is worth something on this set as well: it does not simply pass everything
@@ -58,48 +31,34 @@ def test_exhaustive_random_profiles():
 
 
 def test_exhaustive_threshold_outside_the_range():
-    rng = np.random.default_rng(2302)
-    S = rng.normal(size=(60, 3, 4)) * 2.0 ** rng.integers(-8, 30, size=(60, 1, 1))
-    sc = pssm_ref.scores(S, ALL64)
-    span = np.abs(S).sum(axis=(1, 2))
-    above = sc.max(axis=1) + 1e-3 * span
+    S, above = pssm_cases.threshold_above()
     hits, passed, T = check_invariant(S, above, ALL64)
     assert not hits.any() and np.all(T["dead"] == 1) and not passed.any()
-    below = sc.min(axis=1) - 1e-3 * span
+    S, below = pssm_cases.threshold_below()
     hits, passed, T = check_invariant(S, below, ALL64)
     assert np.all(hits == 64) and np.all(passed == 64) and not T["dead"].any()
     # thresholds of any finite size
     for tt in (1e300, -1e300, 1.7e308, -1.7e308):
-        hits, passed, T = check_invariant(S, np.full(60, tt), ALL64)
+        S, t = pssm_cases.threshold_of_any_size(tt)
+        hits, passed, T = check_invariant(S, t, ALL64)
         assert np.all(T["dead"] == (1 if tt > 0 else 0))
         assert np.all(hits == (0 if tt > 0 else 64))
 
 
 def test_exhaustive_constant_profiles_and_zero():
-    S = np.zeros((4, 3, 4))
-    S[1] = 2.5
-    S[2] = -1e-310          # subnormal entries
-    S[3] = 2.0 ** 100       # the largest legal magnitude
-    for t in (np.array([0.0, 7.5, -3e-310, 3 * 2.0 ** 100]),     # exactly the one attainable score: all hit
-              np.array([-1.0, 7.0, -1.0, 2.0 ** 100])):
+    for S, t in (pssm_cases.constant_at_the_score(),     # exactly the one attainable score: all hit
+                 pssm_cases.constant_below_the_score()):
         hits, passed, T = check_invariant(S, t, ALL64)
         assert np.all(hits == 64) and np.all(passed == 64)
-    hits, passed, T = check_invariant(S, np.array([1.0, 8.0, 1.0, 2.0 ** 102]), ALL64)
+    S, t = pssm_cases.constant_above_the_score()
+    hits, passed, T = check_invariant(S, t, ALL64)
     assert not hits.any() and np.all(T["dead"] == 1)
 
 
 def test_cancellation_family():
     """{+-1, +-2^60} in every position order: -1 + 2^60 - 2^60 is 0 in fp64 and -1 over the reals; at t = -0.5 the
     rounded sum is a hit where the real sum is none, and the filter must keep it."""
-    big = 2.0 ** 60
-    prof, thr = [], []
-    for perm in itertools.permutations([1.0, big, big]):
-        for half in (1.0, 0.5):
-            S = np.array([[v, -v, half * v, -half * v] for v in perm])
-            for t in (0.5, -0.5):
-                prof.append(S)
-                thr.append(t)
-    S, t = np.array(prof), np.array(thr)
+    S, t = pssm_cases.cancellation()
     sc = pssm_ref.scores(S, ALL64)
     # the family does what it is here for: some rounded score reaches t where the exact sum does not
     from fractions import Fraction
