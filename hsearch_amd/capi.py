@@ -40,7 +40,8 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_pssm_rank", "hs_pssm_rank_dev", "hs_pssm_rank_scores", "hs_pssm_rank_plan", "hs_pssm_refine_rank",
            "hs_pssm_log_odds", "hs_pssm_background", "hs_pssm_pvalue", "hs_pssm_pvalue_dev",
            "hs_pssm_pvalue_threshold", "hs_pssm_pvalue_threshold_dev", "hs_pssm_null_tables", "hs_pssm_pvalue_host",
-           "hs_pssm_threshold_host"]
+           "hs_pssm_threshold_host", "hs_pssm_weighted_counts", "hs_pssm_weighted_counts_dev",
+           "hs_pssm_refine_weighted", "hs_pssm_weight_hits", "hs_pssm_log_odds_weighted", "hs_pssm_weight_u"]
 
 TOPK_MAX = 64        # HS_TOPK_MAX: the widest row of query_topk / self_knn / topk_merge
 NO_ID = 0xffffffff   # the id and table of an unused entry of such a row (its distance is +inf)
@@ -74,7 +75,8 @@ class _Profile(C.Structure):
                 ("remove_dead_buckets", C.c_uint64), ("remove_retupled", C.c_uint64),
                 ("pssm_pairs", C.c_uint64), ("pssm_survivors", C.c_uint64), ("pssm_dead", C.c_uint64),
                 ("pssm_mfma_steps", C.c_uint64), ("pssm_seq_rows", C.c_uint64), ("pssm_count_sites", C.c_uint64),
-                ("pssm_count_items", C.c_uint64), ("pssm_null_bins", C.c_uint64),
+                ("pssm_count_items", C.c_uint64), ("pssm_weight_sites", C.c_uint64),
+                ("pssm_weight_items", C.c_uint64), ("pssm_null_bins", C.c_uint64),
                 ("pssm_null_profiles", C.c_uint64), ("pssm_rank_sample", C.c_uint64),
                 ("pssm_rank_retries", C.c_uint64), ("pssm_topk_sample", C.c_uint64),
                 ("pssm_topk_raised", C.c_uint64)]
@@ -364,6 +366,27 @@ def load(hooks=False):
             lib.hs_pssm_refine_rank.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                                 C.c_void_p, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        # PSSM sequence weights: (h, S, t, nm, id_start, n_seq, counts, wcounts, wsum, distinct, cnt, used, &n_hits);
+        # refine_weighted, weight_hits, log_odds_weighted, weight_u: include/hsearch.h
+        if hasattr(lib, "hs_pssm_weighted_counts"):
+            for fn in (lib.hs_pssm_weighted_counts, lib.hs_pssm_weighted_counts_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64] + [
+                    C.c_void_p] * 6 + [C.POINTER(C.c_uint64)]
+            lib.hs_pssm_refine_weighted.restype = C.c_int
+            lib.hs_pssm_refine_weighted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                    C.c_void_p, C.c_uint64, C.c_void_p, C.c_double, C.c_uint32,
+                                                    C.c_uint32] + [C.c_void_p] * 7 + [C.POINTER(C.c_uint32),
+                                                                                     C.POINTER(C.c_uint32)]
+            lib.hs_pssm_weight_hits.restype = C.c_int
+            lib.hs_pssm_weight_hits.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64] + [
+                                                    C.c_void_p] * 5
+            lib.hs_pssm_log_odds_weighted.restype = C.c_int
+            lib.hs_pssm_log_odds_weighted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                                                      C.c_uint32, C.c_void_p, C.c_double, C.c_void_p]
+            lib.hs_pssm_weight_u.restype = C.c_uint64
+            lib.hs_pssm_weight_u.argtypes = [C.c_uint32, C.c_uint32]
         # PSSM p-values: (h, S, bg, t_lo, nm, hit_m, hit_score, n, p_hi, p_lo); (h, S, bg, t_lo, p, nm, t_p, p_hi, p_lo,
         # flag); the host forms: include/hsearch.h
         if hasattr(lib, "hs_pssm_pvalue"):
@@ -917,6 +940,58 @@ def pssm_count_hits(codes, alphabet, m, id, score, nm, id_start=None):
     if st:
         raise HsError(st, "hs_pssm_count_hits")
     return dict(counts=counts, used=used[:rows])
+
+
+def pssm_weight_hits(codes, alphabet, m, id, score, nm, id_start=None):
+    """hs_pssm_weight_hits (host only, no GPU): the rule of Engine.pssm_weighted_counts over ANY list of hits (m, id,
+    score) in any order over codes [n][k]: dict(counts uint32 [nm][k][alphabet], wcounts uint64 [nm][k][alphabet], wsum
+    uint64 [nm], distinct uint32 [nm], used uint64 [nm]).  The sites are capi.pssm_count_hits'.  The merge of several
+    GPUs' hit lists: weights do not merge from per-GPU wcounts."""
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    assert codes.ndim == 2
+    n, k = codes.shape
+    m = np.ascontiguousarray(m, dtype=np.uint32).ravel()
+    id = np.ascontiguousarray(id, dtype=np.uint32).ravel()
+    score = np.ascontiguousarray(score, dtype=np.float64).ravel()
+    assert id.shape == score.shape == m.shape
+    if id_start is not None:
+        id_start = np.ascontiguousarray(id_start, dtype=np.uint64)
+        assert id_start.ndim == 1 and len(id_start) >= 1
+    rows = max(int(nm), 0)
+    shape = (rows, k, max(int(alphabet), 1))
+    counts, wcounts = np.empty(shape, dtype=np.uint32), np.empty(shape, dtype=np.uint64)
+    wsum, used = np.empty(max(rows, 1), dtype=np.uint64), np.empty(max(rows, 1), dtype=np.uint64)
+    distinct = np.empty(max(rows, 1), dtype=np.uint32)
+    st = load().hs_pssm_weight_hits(_vp(codes), n, k, int(alphabet), _vp(m), _vp(id), _vp(score), len(m), int(nm),
+                                    None if id_start is None else _vp(id_start),
+                                    0 if id_start is None else len(id_start) - 1, _vp(counts), _vp(wcounts),
+                                    _vp(wsum), _vp(distinct), _vp(used))
+    if st:
+        raise HsError(st, "hs_pssm_weight_hits")
+    return dict(counts=counts, wcounts=wcounts, wsum=wsum[:rows], distinct=distinct[:rows], used=used[:rows])
+
+
+def pssm_weight_u(r, c):
+    """hs_pssm_weight_u: floor(2^56 / (r * c)), 0 where r == 0 or c == 0."""
+    return int(load().hs_pssm_weight_u(int(r), int(c)))
+
+
+def pssm_log_odds_weighted(wcounts, wsum, n_eff, background, pseudo=1.0):
+    """hs_pssm_log_odds_weighted (host only): S[m][p][a] = log2(((f * n_eff[m] + pseudo * bg[a]) / (n_eff[m] + pseudo))
+    / bg[a]) with f = wcounts[m][p][a] / wsum[m] (0 where wsum[m] == 0), every operation rounded to fp64 -- the function
+    Engine.pssm_refine_weighted applies, bit for bit."""
+    wcounts = np.ascontiguousarray(wcounts, dtype=np.uint64)
+    assert wcounts.ndim == 3
+    nm, k, A = wcounts.shape
+    wsum = np.ascontiguousarray(wsum, dtype=np.uint64)
+    n_eff = np.ascontiguousarray(n_eff, dtype=np.float64)
+    bg = np.ascontiguousarray(background, dtype=np.float64)
+    assert wsum.shape == (nm,) and n_eff.shape == (nm,) and bg.shape == (A,), (wsum.shape, n_eff.shape, bg.shape)
+    S = np.empty((nm, k, A), dtype=np.float64)
+    st = load().hs_pssm_log_odds_weighted(_vp(wcounts), _vp(wsum), _vp(n_eff), nm, k, A, _vp(bg), float(pseudo), _vp(S))
+    if st:
+        raise HsError(st, "hs_pssm_log_odds_weighted")
+    return S
 
 
 def pssm_rank_scores(codes, alphabet, S, rank):
@@ -2091,6 +2166,72 @@ class Engine:
                                                   C.byref(conv)))
         return dict(S=S_out, t=t_out[:nm], counts=counts, used=used[:nm], iters=int(iters.value),
                     converged=bool(conv.value))
+
+    def pssm_weighted_counts(self, S, t, id_start=None):
+        """hs_pssm_weighted_counts: pssm_hit_counts with position-based sequence weights (Henikoff and Henikoff 1994)
+        in integers, reduced on the device: dict(counts uint32 and wcounts uint64 [nm][k][alphabet], wsum uint64 [nm]
+        (every column of wcounts[m] sums to it; at most k * 2^56), distinct uint32 [nm] (the residues that occur,
+        summed over the positions), cnt, used, n_hits).  The sites are pssm_hit_counts'."""
+        S, t, nm, id_start, n_seq = self._pssm_args(S, t, id_start)
+        counts, wcounts = np.empty(S.shape, dtype=np.uint32), np.empty(S.shape, dtype=np.uint64)
+        wsum, cnt, used = (np.empty(max(nm, 1), dtype=np.uint64) for _ in range(3))
+        distinct = np.empty(max(nm, 1), dtype=np.uint32)
+        nh = C.c_uint64(0)
+        self._check(self._lib.hs_pssm_weighted_counts(self._h, _vp(S), _vp(t), nm,
+                                                      None if id_start is None else _vp(id_start), n_seq, _vp(counts),
+                                                      _vp(wcounts), _vp(wsum), _vp(distinct), _vp(cnt), _vp(used),
+                                                      C.byref(nh)))
+        return dict(counts=counts, wcounts=wcounts, wsum=wsum[:nm], distinct=distinct[:nm], cnt=cnt[:nm],
+                    used=used[:nm], n_hits=int(nh.value))
+
+    def pssm_weighted_counts_dev(self, d_S, d_t, nm, d_wcounts, d_id_start=None, n_seq=0, d_counts=None, d_wsum=None,
+                                 d_distinct=None, d_cnt=None, d_used=None):
+        """hs_pssm_weighted_counts_dev: device pointers (ints, e.g. tensor.data_ptr(); all but d_S, d_t and d_wcounts
+        may be None).  Returns n_hits."""
+        nh = C.c_uint64(0)
+        self._check(self._lib.hs_pssm_weighted_counts_dev(
+            self._h, d_S if d_S else None, d_t if d_t else None, int(nm), d_id_start if d_id_start else None,
+            int(n_seq), d_counts if d_counts else None, d_wcounts if d_wcounts else None, d_wsum if d_wsum else None,
+            d_distinct if d_distinct else None, d_cnt if d_cnt else None, d_used if d_used else None, C.byref(nh)))
+        return int(nh.value)
+
+    def pssm_refine_weighted(self, S, n_iter, t=None, rank=None, id_start=None, background=None, pseudo=1.0,
+                             neff="sites"):
+        """hs_pssm_refine_weighted: pssm_refine (t given) or pssm_refine_rank (rank given) -- exactly one of them --
+        with every scan's sites weighted (pssm_weighted_counts) and the log-odds taken from the weighted frequencies
+        at n_eff observations: neff="sites": used[m]; "columns": distinct[m] / k.  Converged when counts and wcounts
+        both repeat.  dict(S, t (rank given), counts, wcounts, wsum, distinct, used: of the last scan, iters,
+        converged)."""
+        assert (t is None) != (rank is None), "exactly one of t and rank"
+        rule = {"sites": 0, "columns": 1}[neff]
+        if rank is None:
+            S, v, nm = self._pssm_args(S, t, None)[:3]
+        else:
+            S, v, nm = self._pssm_rank_args(S, rank)
+        if id_start is not None:
+            id_start = np.ascontiguousarray(id_start, dtype=np.uint64)
+            assert id_start.ndim == 1 and len(id_start) >= 1
+        n_seq = 0 if id_start is None else len(id_start) - 1
+        bg = None
+        if background is not None:
+            bg = np.ascontiguousarray(background, dtype=np.float64)
+            assert bg.shape == (self._alphabet(),), bg.shape
+        S_out = np.empty(S.shape, dtype=np.float64)
+        t_out = np.empty(max(nm, 1), dtype=np.float64)
+        counts, wcounts = np.empty(S.shape, dtype=np.uint32), np.empty(S.shape, dtype=np.uint64)
+        wsum, used = np.empty(max(nm, 1), dtype=np.uint64), np.empty(max(nm, 1), dtype=np.uint64)
+        distinct = np.empty(max(nm, 1), dtype=np.uint32)
+        iters, conv = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.hs_pssm_refine_weighted(
+            self._h, _vp(S), None if rank is not None else _vp(v), None if rank is None else _vp(v), nm,
+            None if id_start is None else _vp(id_start), n_seq, None if bg is None else _vp(bg), float(pseudo), rule,
+            int(n_iter), _vp(S_out), _vp(t_out), _vp(counts), _vp(wcounts), _vp(wsum), _vp(distinct), _vp(used),
+            C.byref(iters), C.byref(conv)))
+        res = dict(S=S_out, counts=counts, wcounts=wcounts, wsum=wsum[:nm], distinct=distinct[:nm], used=used[:nm],
+                   iters=int(iters.value), converged=bool(conv.value))
+        if rank is not None:
+            res["t"] = t_out[:nm]
+        return res
 
     def bruteforce_radii(self, centers, radii, cap=None):
         """hs_bruteforce_radii: brute force with centre q searched at radii[q]."""

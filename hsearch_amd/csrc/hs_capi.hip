@@ -618,6 +618,7 @@ void hs_destroy(hs_handle* h) {
                     &h->dt_next, &h->dt_cnt, &h->knn_cnt, &h->knn_off, &h->knn_cur, &h->knn_total, &h->knn_io_count, &h->pt_tused, &h->pt_parts,
                     &h->pr_keys, &h->pr_off, &h->pr_state, &h->pr_resolved, &h->pr_tscan, &h->pr_unres, &h->pr_rank, &h->pr_out,
                     &h->pc_m, &h->pc_id, &h->pc_m2, &h->pc_id2, &h->pc_start, &h->pc_nitem, &h->pc_off, &h->pc_rows, &h->pc_out,
+                    &h->pw_u, &h->pw_counts, &h->pw_out,
                     &h->sq_key, &h->sq_idx, &h->sq_skey, &h->sq_sidx, &h->sq_head, &h->sq_excl, &h->sq_part, &h->sq_acc,
                     &h->sq_fin, &h->sq_chk, &h->sq_in, &h->sq_out,
                     &h->sm_size, &h->sm_tmp, &h->sm_row_of, &h->sm_off_of,

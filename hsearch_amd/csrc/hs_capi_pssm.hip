@@ -4,6 +4,8 @@
 //   hs_pssm_scan / _dev                  every hit (m, id, score) at the caller's thresholds        (hs_pssm.hip)
 //   hs_pssm_seq_scan / _dev              the hits reduced per (profile, sequence)                   (hs_pssm_seq.hip)
 //   hs_pssm_hit_counts / _dev            the position frequency matrices of the hits                (hs_pssm_counts.hip)
+//   hs_pssm_weighted_counts / _dev       ... with position-based sequence weights                   (hs_pssm_weights.hip)
+//   hs_pssm_refine_weighted              the refine loop on weighted counts, under either threshold rule
 //   hs_pssm_topk / _dev                  the topk best k-mers per profile, no threshold given       (hs_pssm_topk.hip)
 //   hs_pssm_rank / _dev                  the threshold that admits a profile's rank best k-mers     (hs_pssm_rank.hip)
 //   hs_pssm_refine, hs_pssm_refine_rank  profiles rebuilt from their own hits, iterated
@@ -27,6 +29,7 @@
 #include "hs_pssm_tables.h"
 #include "hs_pssm_seq.h"
 #include "hs_pssm_counts.h"
+#include "hs_pssm_weights.h"
 #include "hs_pssm_topk.h"
 #include "hs_pssm_rank.h"
 #include "hs_pssm_null.h"
@@ -377,12 +380,20 @@ uint32_t pssm_count_chunk(const hs_handle* h, uint32_t ns) {
   return std::min(2048u, std::max(256u, (ns + 4095u) / 4096u));
 }
 
+// The weighted outputs of hs_pssm_weighted_counts (hs_pssm_weights.hip), on the device or the host: wcounts
+// [nm][k][alphabet]; wsum [nm] and distinct [nm] may be null.
+struct PssmWeightOut {
+  uint64_t *wcounts = nullptr, *wsum = nullptr;
+  uint32_t* distinct = nullptr;
+};
+
 // The call with every array on the device; the callers have checked the arguments and the values.  d_id_start null:
 // every hit is a site; else the sites are the best ids of the batch's (profile, sequence) rows.  Every hit of a
-// profile lies in one batch, so a batch finishes its profiles' counts.
+// profile lies in one batch, so a batch finishes its profiles' counts -- and, with w given, the weights of its sites
+// follow from them in a second stage over the same sites and work items.  w null: hs_pssm_hit_counts, launch for launch.
 hs_status pssm_counts_core(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm, const uint64_t* d_id_start,
                            uint64_t n_seq, uint32_t* d_counts, uint64_t* d_cnt_out, uint64_t* d_used_out,
-                           uint64_t* n_hits) {
+                           uint64_t* n_hits, const PssmWeightOut* w = nullptr) {
   memset(&h->prof, 0, sizeof(h->prof));
   HS_HIP(h, h->counters.reserve(256));
   HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
@@ -391,6 +402,11 @@ hs_status pssm_counts_core(hs_handle* h, const double* d_S, const double* d_t, u
   if (nm) HS_HIP(h, hipMemsetAsync(d_counts, 0, nm * cells * 4, h->stream));
   if (d_cnt_out && nm) HS_HIP(h, hipMemsetAsync(d_cnt_out, 0, nm * 8, h->stream));
   if (d_used_out && nm) HS_HIP(h, hipMemsetAsync(d_used_out, 0, nm * 8, h->stream));
+  if (w && nm) {
+    HS_HIP(h, hipMemsetAsync(w->wcounts, 0, nm * cells * 8, h->stream));
+    if (w->wsum) HS_HIP(h, hipMemsetAsync(w->wsum, 0, nm * 8, h->stream));
+    if (w->distinct) HS_HIP(h, hipMemsetAsync(w->distinct, 0, nm * 4, h->stream));
+  }
   uint64_t sites = 0, items = 0;
   HS_CHECK(pssm_batches(h, d_S, d_t, nm, n_hits, [&](uint32_t m0, uint32_t mb, uint32_t nh) -> hs_status {
     const uint32_t *site_m = nullptr, *site_id = nullptr;
@@ -435,20 +451,36 @@ hs_status pssm_counts_core(hs_handle* h, const double* d_S, const double* d_t, u
     HS_HIP(h, hs_launch_pssm_counts_used(d_counts + (size_t)m0 * cells, mb, k, h->alphabet,
                                          d_used_out ? d_used_out + m0 : nullptr,
                                          d_cnt_out && !d_id_start ? d_cnt_out + m0 : nullptr, h->stream));
+    if (w) {  // the batch's counts are final: u from them, the sites' weights, their sums
+      HS_HIP(h, h->pw_u.reserve(hs_pssm_weights_table_bytes(mb, k, h->alphabet)));
+      HS_HIP(h, hs_launch_pssm_weights_table(d_counts + (size_t)m0 * cells, mb, k, h->alphabet, h->pw_u.as<uint64_t>(),
+                                             w->distinct ? w->distinct + m0 : nullptr, h->stream));
+      HS_HIP(h, hs_launch_pssm_weights(h->codes.as<uint8_t>(), k, h->alphabet, site_id, h->pc_start.as<uint32_t>(),
+                                       h->pc_off.as<uint32_t>(), m0, mb, ch, n_items, h->pw_u.as<uint64_t>(),
+                                       w->wcounts, h->stream));
+      HS_HIP(h, hs_launch_pssm_weights_sum(w->wcounts + (size_t)m0 * cells, mb, k, h->alphabet,
+                                           w->wsum ? w->wsum + m0 : nullptr, h->stream));
+    }
     sites += ns;
     items += n_items;
     return HS_OK;
   }));
   h->prof.pssm_count_sites = sites;
   h->prof.pssm_count_items = items;
+  if (w) {
+    h->prof.pssm_weight_sites = sites;
+    h->prof.pssm_weight_items = items;
+  }
   return HS_OK;
 }
 
 // what every form refuses from the arguments alone (hs_pssm_scan's refusals first); id_start null: every site counts
+// (counts: the array the call must be given -- wcounts for the weighted call, whose text is counts_null then)
 hs_status pssm_counts_args(hs_handle* h, const void* S, const void* t, uint64_t nm, const void* id_start,
-                           uint64_t n_seq, const void* counts) {
+                           uint64_t n_seq, const void* counts,
+                           const char* counts_null = "hs_pssm_hit_counts: counts is null") {
   HS_CHECK(pssm_args_start(h, nm, S && t ? nullptr : "hs_pssm_hit_counts: S or t is null"));
-  if (nm && !counts) return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: counts is null");
+  if (nm && !counts) return fail(h, HS_ERR_INVALID, counts_null);
   if (id_start && n_seq > (1ull << 32)) return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: more than 2^32 sequences");
   if (id_start && !n_seq && h->n)
     return fail(h, HS_ERR_INVALID, "hs_pssm_hit_counts: no sequence owns the index's k-mers");
@@ -463,28 +495,43 @@ hs_status pssm_counts_values(hs_handle* h, const double* S, const double* t, uin
 }
 
 // A checked host-pointer call: S and t up, counts (and cnt, used) down.  ids_resident: id_start already lies in sq_in
-// (the later iterations of a refinement).
+// (the later iterations of a refinement).  w (host arrays) given: the weighted call -- wcounts, wsum and distinct come
+// down too, and counts may be null.
 hs_status pssm_counts_host(hs_handle* h, const double* S, const double* t, uint64_t nm, const uint64_t* id_start,
                            uint64_t n_seq, bool ids_resident, uint32_t* counts, uint64_t* cnt, uint64_t* used,
-                           uint64_t* n_hits) {
+                           uint64_t* n_hits, const PssmWeightOut* w = nullptr) {
   HS_CHECK(ensure_device(h));
   const size_t ka = (size_t)h->p.k * h->alphabet;
   const size_t sb = ((size_t)n_seq + 1) * 8, cb = std::max<size_t>(16, nm * 8), ob = std::max<size_t>(16, nm * ka * 4);
   HS_CHECK(pssm_stage_in(h, S, t, nm, h->io_radii));
   if (id_start) HS_HIP(h, h->sq_in.reserve(sb));
   HS_HIP(h, h->pc_out.reserve(2 * cb + ob));
+  if (w) HS_HIP(h, h->pw_out.reserve(2 * cb + 2 * ob));
   if (id_start && !ids_resident)
     HS_HIP(h, hipMemcpyAsync(h->sq_in.p, id_start, sb, hipMemcpyHostToDevice, h->stream));
   char* const o = h->pc_out.as<char>();
   uint64_t* const d_cnt = cnt ? reinterpret_cast<uint64_t*>(o) : nullptr;
   uint64_t* const d_used = used ? reinterpret_cast<uint64_t*>(o + cb) : nullptr;
   uint32_t* const d_counts = reinterpret_cast<uint32_t*>(o + 2 * cb);
+  PssmWeightOut dw;
+  if (w) {  // wsum, distinct, wcounts in pw_out
+    char* const wo = h->pw_out.as<char>();
+    dw.wsum = w->wsum ? reinterpret_cast<uint64_t*>(wo) : nullptr;
+    dw.distinct = w->distinct ? reinterpret_cast<uint32_t*>(wo + cb) : nullptr;
+    dw.wcounts = reinterpret_cast<uint64_t*>(wo + 2 * cb);
+  }
   HS_CHECK(pssm_counts_core(h, h->io_centers.as<double>(), h->io_radii.as<double>(), nm,
-                            id_start ? h->sq_in.as<uint64_t>() : nullptr, n_seq, d_counts, d_cnt, d_used, n_hits));
+                            id_start ? h->sq_in.as<uint64_t>() : nullptr, n_seq, d_counts, d_cnt, d_used, n_hits,
+                            w ? &dw : nullptr));
   if (nm) {
-    HS_HIP(h, hipMemcpyAsync(counts, d_counts, nm * ka * 4, hipMemcpyDeviceToHost, h->stream));
+    if (counts) HS_HIP(h, hipMemcpyAsync(counts, d_counts, nm * ka * 4, hipMemcpyDeviceToHost, h->stream));
     if (cnt) HS_HIP(h, hipMemcpyAsync(cnt, d_cnt, nm * 8, hipMemcpyDeviceToHost, h->stream));
     if (used) HS_HIP(h, hipMemcpyAsync(used, d_used, nm * 8, hipMemcpyDeviceToHost, h->stream));
+    if (w) {
+      HS_HIP(h, hipMemcpyAsync(w->wcounts, dw.wcounts, nm * ka * 8, hipMemcpyDeviceToHost, h->stream));
+      if (w->wsum) HS_HIP(h, hipMemcpyAsync(w->wsum, dw.wsum, nm * 8, hipMemcpyDeviceToHost, h->stream));
+      if (w->distinct) HS_HIP(h, hipMemcpyAsync(w->distinct, dw.distinct, nm * 4, hipMemcpyDeviceToHost, h->stream));
+    }
   }
   HS_HIP(h, hipStreamSynchronize(h->stream));
   return HS_OK;
@@ -646,16 +693,21 @@ hs_status pssm_rank_args(hs_handle* h, const void* S, const void* rank, uint64_t
 // The refine loop of hs_pssm_refine (by_rank false: every iteration scans at the thresholds t) and
 // hs_pssm_refine_rank (by_rank: at the thresholds that admit rank[m] k-mers of the iteration's profiles, which
 // hs_pssm_rank finds and t_out hands out): counts of the hits, log-odds against the background, until the counts repeat.
+// neff_rule < 0: the sites count 1 each.  Else hs_pssm_refine_weighted: the scans are hs_pssm_weighted_counts', the
+// log-odds hs_pssm_log_odds_weighted's with n_eff = used (rule 0) or distinct / k (rule 1), and the loop has converged
+// when counts and wcounts both repeat; wo: where the last scan's wcounts, wsum and distinct go (each may be null).
 hs_status pssm_refine(hs_handle* h, const double* S0, const double* t, const uint64_t* rank, bool by_rank, uint64_t nm,
                       const uint64_t* id_start, uint64_t n_seq, const double* bg, double pseudo, uint32_t n_iter,
                       double* S_out, double* t_out, uint32_t* counts, uint64_t* used, uint32_t* iters,
-                      uint32_t* converged) {
+                      uint32_t* converged, int neff_rule = -1, const PssmWeightOut& wo = PssmWeightOut()) {
   if (!h || !iters || !converged) return HS_ERR_INVALID;
   *iters = 0;
   *converged = 0;
+  const bool weighted = neff_rule >= 0;
   HS_CHECK(pssm_counts_args(h, S0, by_rank ? (const void*)rank : t, nm, id_start, n_seq, S_out));
   if (by_rank && nm && !t_out) return fail(h, HS_ERR_INVALID, "hs_pssm_refine_rank: t_out is null");
   if (n_iter < 1 || n_iter > 100) return fail(h, HS_ERR_INVALID, "hs_pssm_refine: n_iter must be 1 .. 100");
+  if (neff_rule > 1) return fail(h, HS_ERR_INVALID, "hs_pssm_refine_weighted: neff_rule must be 0 or 1");
   const uint32_t k = h->p.k, A = (uint32_t)h->alphabet;
   double bgv[32];
   if (!(pseudo > 0.0 && pseudo <= 1.7976931348623157e308) || (bg && !hs_pssm_bg_ok(bg, A, pseudo)))
@@ -679,20 +731,37 @@ hs_status pssm_refine(hs_handle* h, const double* S0, const double* t, const uin
     std::vector<double> S(S0, S0 + nm * cells), T(by_rank ? nm : 0, 0.0);
     std::vector<uint32_t> C(nm * cells), prev;
     std::vector<uint64_t> U(nm), ge(T.size()), gt(T.size());
+    std::vector<uint64_t> WC(weighted ? nm * cells : 0), WS(weighted ? nm : 0), prev_w;
+    std::vector<uint32_t> D(weighted ? nm : 0);
+    PssmWeightOut wi;
+    wi.wcounts = WC.data();
+    wi.wsum = WS.data();
+    wi.distinct = D.data();
     const double* const ti = by_rank ? T.data() : t;
     uint32_t done = 0, conv = 0;
     for (uint32_t i = 0; i < n_iter; ++i) {
       if (by_rank) HS_CHECK(hs_pssm_rank(h, S.data(), rank, nm, T.data(), ge.data(), gt.data(), nullptr, nullptr));
-      HS_CHECK(pssm_counts_host(h, S.data(), ti, nm, id_start, n_seq, i > 0, C.data(), nullptr, U.data(), &nh));
+      HS_CHECK(pssm_counts_host(h, S.data(), ti, nm, id_start, n_seq, i > 0, C.data(), nullptr, U.data(), &nh,
+                                weighted ? &wi : nullptr));
       ++done;
-      if (i > 0 && C == prev) {
+      if (i > 0 && C == prev && WC == prev_w) {
         conv = 1;
         break;
       }
-      for (uint64_t m = 0; m < nm; ++m)
-        if (U[m] && hs_pssm_log_odds_host(C.data() + m * cells, 1, k, A, bgv, pseudo, S.data() + m * cells))
-          return fail(h, HS_ERR_INVALID, "hs_pssm_refine: a log-odds entry is not finite");
+      for (uint64_t m = 0; m < nm; ++m) {
+        if (!U[m]) continue;  // a profile that finds nothing keeps its matrix
+        int bad;
+        if (weighted) {
+          const double n_eff = neff_rule ? (double)D[m] / (double)k : (double)U[m];
+          bad = hs_pssm_log_odds_weighted_host(WC.data() + m * cells, WS.data() + m, &n_eff, 1, k, A, bgv, pseudo,
+                                               S.data() + m * cells);
+        } else {
+          bad = hs_pssm_log_odds_host(C.data() + m * cells, 1, k, A, bgv, pseudo, S.data() + m * cells);
+        }
+        if (bad) return fail(h, HS_ERR_INVALID, "hs_pssm_refine: a log-odds entry is not finite");
+      }
       prev = C;
+      prev_w = WC;
     }
     for (size_t i = 0; i < S.size(); ++i) S_out[i] = S[i];
     for (size_t m = 0; m < T.size(); ++m) t_out[m] = T[m];
@@ -700,6 +769,12 @@ hs_status pssm_refine(hs_handle* h, const double* S0, const double* t, const uin
       for (size_t i = 0; i < C.size(); ++i) counts[i] = C[i];
     if (used)
       for (uint64_t m = 0; m < nm; ++m) used[m] = U[m];
+    if (wo.wcounts)
+      for (size_t i = 0; i < WC.size(); ++i) wo.wcounts[i] = WC[i];
+    for (size_t m = 0; m < WS.size(); ++m) {
+      if (wo.wsum) wo.wsum[m] = WS[m];
+      if (wo.distinct) wo.distinct[m] = D[m];
+    }
     *iters = done;
     *converged = conv;
   } catch (const std::bad_alloc&) {
@@ -951,6 +1026,40 @@ hs_status hs_pssm_hit_counts(hs_handle* h, const double* S, const double* t, uin
   return pssm_counts_host(h, S, t, nm, id_start, n_seq, false, counts, cnt, used, n_hits);
 }
 
+hs_status hs_pssm_weighted_counts_dev(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm,
+                                      const uint64_t* d_id_start, uint64_t n_seq, uint32_t* d_counts,
+                                      uint64_t* d_wcounts, uint64_t* d_wsum, uint32_t* d_distinct, uint64_t* d_cnt,
+                                      uint64_t* d_used, uint64_t* n_hits) {
+  if (!h || !n_hits) return HS_ERR_INVALID;
+  *n_hits = 0;
+  HS_CHECK(pssm_counts_args(h, d_S, d_t, nm, d_id_start, n_seq, d_wcounts, "hs_pssm_weighted_counts: wcounts is null"));
+  HS_CHECK(ensure_device(h));
+  HS_CHECK(pssm_dev_check(h, d_S, d_t, nm, nullptr, d_id_start, n_seq, "threshold", "hs_pssm_hit_counts", nullptr));
+  if (!d_counts) {  // the raw counts stay in the handle's scratch
+    HS_HIP(h, h->pw_counts.reserve(std::max<size_t>(16, nm * h->p.k * h->alphabet * 4)));
+    d_counts = h->pw_counts.as<uint32_t>();
+  }
+  PssmWeightOut w;
+  w.wcounts = d_wcounts;
+  w.wsum = d_wsum;
+  w.distinct = d_distinct;
+  return pssm_counts_core(h, d_S, d_t, nm, d_id_start, n_seq, d_counts, d_cnt, d_used, n_hits, &w);
+}
+
+hs_status hs_pssm_weighted_counts(hs_handle* h, const double* S, const double* t, uint64_t nm, const uint64_t* id_start,
+                                  uint64_t n_seq, uint32_t* counts, uint64_t* wcounts, uint64_t* wsum,
+                                  uint32_t* distinct, uint64_t* cnt, uint64_t* used, uint64_t* n_hits) {
+  if (!h || !n_hits) return HS_ERR_INVALID;
+  *n_hits = 0;
+  HS_CHECK(pssm_counts_args(h, S, t, nm, id_start, n_seq, wcounts, "hs_pssm_weighted_counts: wcounts is null"));
+  HS_CHECK(pssm_counts_values(h, S, t, nm, id_start, n_seq));
+  PssmWeightOut w;
+  w.wcounts = wcounts;
+  w.wsum = wsum;
+  w.distinct = distinct;
+  return pssm_counts_host(h, S, t, nm, id_start, n_seq, false, counts, cnt, used, n_hits, &w);
+}
+
 hs_status hs_pssm_topk_dev(hs_handle* h, const double* d_S, const double* d_floor, uint64_t nm, uint32_t topk,
                            uint32_t* d_top_id, double* d_top_score, uint32_t* d_top_count, double* d_t_used) {
   if (!h) return HS_ERR_INVALID;
@@ -1042,6 +1151,26 @@ hs_status hs_pssm_refine_rank(hs_handle* h, const double* S0, const uint64_t* ra
                               uint32_t* converged) {
   return pssm_refine(h, S0, nullptr, rank, true, nm, id_start, n_seq, bg, pseudo, n_iter, S_out, t_out, counts, used,
                      iters, converged);
+}
+
+// hs_pssm_refine / hs_pssm_refine_rank (rank given) under sequence weights
+hs_status hs_pssm_refine_weighted(hs_handle* h, const double* S0, const double* t, const uint64_t* rank, uint64_t nm,
+                                  const uint64_t* id_start, uint64_t n_seq, const double* bg, double pseudo,
+                                  uint32_t neff_rule, uint32_t n_iter, double* S_out, double* t_out, uint32_t* counts,
+                                  uint64_t* wcounts, uint64_t* wsum, uint32_t* distinct, uint64_t* used,
+                                  uint32_t* iters, uint32_t* converged) {
+  if (!h || !iters || !converged) return HS_ERR_INVALID;
+  *iters = 0;
+  *converged = 0;
+  if ((t != nullptr) == (rank != nullptr))
+    return fail(h, HS_ERR_INVALID, "hs_pssm_refine_weighted: exactly one of t and rank must be given");
+  if (neff_rule > 1) return fail(h, HS_ERR_INVALID, "hs_pssm_refine_weighted: neff_rule must be 0 or 1");
+  PssmWeightOut wo;
+  wo.wcounts = wcounts;
+  wo.wsum = wsum;
+  wo.distinct = distinct;
+  return pssm_refine(h, S0, t, rank, rank != nullptr, nm, id_start, n_seq, bg, pseudo, n_iter, S_out, t_out, counts,
+                     used, iters, converged, (int)neff_rule, wo);
 }
 
 hs_status hs_pssm_pvalue_dev(hs_handle* h, const double* d_S, const double* d_bg, const double* d_t_lo, uint64_t nm,

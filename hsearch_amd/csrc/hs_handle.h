@@ -276,6 +276,9 @@ struct hs_handle {
   // profiles' run starts, chunk counts and their scan, the rows of the one-site-per-protein mode; a host-pointer
   // call's counts, cnt and used on their way out
   DevBuf pc_m, pc_id, pc_m2, pc_id2, pc_start, pc_nitem, pc_off, pc_rows, pc_out;
+  // hs_pssm_weighted_counts (hs_pssm_weights.hip): a batch's u tables; the raw counts of a call that does not ask for
+  // them; a host-pointer call's wcounts, wsum and distinct on their way out
+  DevBuf pw_u, pw_counts, pw_out;
   // hs_seq_match (hs_seqmatch.hip: the scratch listed at its head): a batch's keys and hit indices, their sorted
   // copies, the run heads and their scan, the waves' cut runs; the call's rows so far (sq_rows of them in a list of
   // sq_acc.cap / 40) and their final reduction; the argument check's words; a host-pointer call's arrays in and out

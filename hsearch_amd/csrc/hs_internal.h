@@ -964,4 +964,18 @@ hipError_t hs_launch_pssm_counts(const uint8_t* d_codes, int k, int alphabet, co
 hipError_t hs_launch_pssm_counts_used(const uint32_t* d_counts, uint32_t nm, int k, int alphabet, uint64_t* d_used,
                                       uint64_t* d_cnt, hipStream_t s);
 
+// ---- hs_pssm_weighted_counts (hs_pssm_weights.hip: the second sink stage of a batch is written at its head) --------
+size_t hs_pssm_weights_table_bytes(uint32_t mb, int k, int alphabet);  // d_u of a batch
+// the batch's finished d_counts [mb][k][alphabet] -> d_u [mb][k][alphabet], d_distinct [mb] (may be null)
+hipError_t hs_launch_pssm_weights_table(const uint32_t* d_counts, uint32_t mb, int k, int alphabet, uint64_t* d_u,
+                                        uint32_t* d_distinct, hipStream_t s);
+// the sites, runs and items of hs_launch_pssm_counts; d_wcounts [nm][k][alphabet] is the call's, zeroed before the
+// first batch
+hipError_t hs_launch_pssm_weights(const uint8_t* d_codes, int k, int alphabet, const uint32_t* d_site_id,
+                                  const uint32_t* d_start, const uint32_t* d_off, uint32_t m0, uint32_t mb, uint32_t ch,
+                                  uint32_t n_items, const uint64_t* d_u, uint64_t* d_wcounts, hipStream_t s);
+// d_wsum [nm] (may be null) from the finished d_wcounts
+hipError_t hs_launch_pssm_weights_sum(const uint64_t* d_wcounts, uint32_t nm, int k, int alphabet, uint64_t* d_wsum,
+                                      hipStream_t s);
+
 #endif

@@ -17,17 +17,18 @@
 
 #include "hs_pssm_seq.h"
 
-// Returns 0; 1 for an argument the contract refuses (nothing is written then); 2 when memory ran out.
+// The sites of a tuple list, each once, with everything the counting rule refuses about the list checked (the output
+// arrays are the caller's business).  Returns 0; 1 for a refused argument; 2 when memory ran out.
 // id_start == nullptr: every site counts (n_seq is not looked at); else id_start [n_seq + 1] must ascend from 0 to n.
-inline int hs_pssm_count_hits_host(const uint8_t* codes, uint64_t n, uint32_t k, uint32_t alphabet, const uint32_t* m,
-                                   const uint32_t* id, const double* score, uint64_t n_tuples, uint64_t nm,
-                                   const uint64_t* id_start, uint64_t n_seq, uint32_t* counts, uint64_t* used) {
+inline int hs_pssm_sites_host(const uint8_t* codes, uint64_t n, uint32_t k, uint32_t alphabet, const uint32_t* m,
+                              const uint32_t* id, const double* score, uint64_t n_tuples, uint64_t nm,
+                              const uint64_t* id_start, uint64_t n_seq, std::vector<uint32_t>& site_m,
+                              std::vector<uint32_t>& site_id) {
   if (!k || !alphabet || alphabet > 32 || n > (1ull << 32) || nm >= (1ull << 27)) return 1;
   if (n_tuples && (!m || !id || !score)) return 1;
-  if ((n && !codes) || (nm && !counts)) return 1;
+  if (n && !codes) return 1;
   if (id_start && (!hs_pssm_seq_id_start_ok(id_start, n_seq) || id_start[n_seq] != n)) return 1;
   try {
-    std::vector<uint32_t> site_m, site_id;
     if (id_start) {
       std::vector<uint32_t> seq(n_tuples), count(n_tuples), lo(n_tuples), hi(n_tuples);
       std::vector<double> best(n_tuples);
@@ -66,6 +67,21 @@ inline int hs_pssm_count_hits_host(const uint8_t* codes, uint64_t n, uint32_t k,
     for (size_t i = 0; i < site_id.size(); ++i)
       for (uint32_t p = 0; p < k; ++p)
         if (codes[(size_t)site_id[i] * k + p] >= alphabet) return 1;
+  } catch (const std::bad_alloc&) {
+    return 2;
+  }
+  return 0;
+}
+
+// Returns 0; 1 for an argument the contract refuses (nothing is written then); 2 when memory ran out.
+inline int hs_pssm_count_hits_host(const uint8_t* codes, uint64_t n, uint32_t k, uint32_t alphabet, const uint32_t* m,
+                                   const uint32_t* id, const double* score, uint64_t n_tuples, uint64_t nm,
+                                   const uint64_t* id_start, uint64_t n_seq, uint32_t* counts, uint64_t* used) {
+  if (nm && !counts) return 1;
+  try {
+    std::vector<uint32_t> site_m, site_id;
+    const int r = hs_pssm_sites_host(codes, n, k, alphabet, m, id, score, n_tuples, nm, id_start, n_seq, site_m, site_id);
+    if (r) return r;
     // everything is checked: the counts
     const size_t cells = (size_t)k * alphabet;
     if (nm) memset(counts, 0, (size_t)nm * cells * 4);

@@ -1034,11 +1034,14 @@ bool WritePssmFile(const std::string& path, uint32_t kmer_length, const std::vec
   return true;
 }
 
-int RefineProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<double>& S, const std::vector<double>& t,
-                   uint32_t n_iter, bool one_per_protein, double pseudo, int device, std::vector<double>* S_out,
-                   uint32_t* iters, bool* converged, std::string* err) {
+// The refine loop over the database's windows under either threshold rule (t or rank, exactly one) and either count
+// (neff_rule < 0: every site counts 1 -- hs_pssm_refine / hs_pssm_refine_rank; 0 or 1: hs_pssm_refine_weighted).
+static int RefineAny(const ProteinDB& db, uint32_t kmer_length, const std::vector<double>& S, const std::vector<double>* t,
+                     const std::vector<uint64_t>* rank, int neff_rule, uint32_t n_iter, bool one_per_protein,
+                     double pseudo, int device, std::vector<double>* S_out, std::vector<double>* t_out, uint32_t* iters,
+                     bool* converged, std::string* err) {
   const uint32_t k = kmer_length;
-  const size_t nm = t.size();
+  const size_t nm = rank ? rank->size() : t->size();
   if (k < 2 || S.size() != nm * (size_t)k * HS_ALPHABET) {
     if (err) *err = k < 2 ? "kmer length 1 is not supported on a FASTA database" : "the profiles do not match the kmer length";
     return HS_ERR_INVALID;
@@ -1052,16 +1055,46 @@ int RefineProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<
   HandleCloser closer = {h};
   if (st != HS_OK) return st;
   S_out->assign(S.size(), 0.0);
+  if (rank) t_out->assign(nm, 0.0);
+  const uint64_t* const ids = one_per_protein ? id_start.data() : nullptr;
   uint32_t done = 0, conv = 0;
-  st = hs_pssm_refine(h, S.data(), t.data(), nm, one_per_protein ? id_start.data() : nullptr, n_seq, nullptr, pseudo,
-                      n_iter, S_out->data(), nullptr, nullptr, &done, &conv);
+  const char* name = neff_rule >= 0 ? "hs_pssm_refine_weighted" : rank ? "hs_pssm_refine_rank" : "hs_pssm_refine";
+  if (neff_rule >= 0)
+    st = hs_pssm_refine_weighted(h, S.data(), rank ? nullptr : t->data(), rank ? rank->data() : nullptr, nm, ids, n_seq,
+                                 nullptr, pseudo, (uint32_t)neff_rule, n_iter, S_out->data(),
+                                 rank ? t_out->data() : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &done, &conv);
+  else if (rank)
+    st = hs_pssm_refine_rank(h, S.data(), rank->data(), nm, ids, n_seq, nullptr, pseudo, n_iter, S_out->data(),
+                             t_out->data(), nullptr, nullptr, &done, &conv);
+  else
+    st = hs_pssm_refine(h, S.data(), t->data(), nm, ids, n_seq, nullptr, pseudo, n_iter, S_out->data(), nullptr, nullptr,
+                        &done, &conv);
   if (st != HS_OK) {
-    if (err) *err = std::string("hs_pssm_refine: ") + hs_last_error(h);
+    if (err) *err = std::string(name) + ": " + hs_last_error(h);
     return st;
   }
   if (iters) *iters = done;
   if (converged) *converged = conv != 0;
   return HS_OK;
+}
+
+int RefineProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<double>& S, const std::vector<double>& t,
+                   uint32_t n_iter, bool one_per_protein, double pseudo, int device, std::vector<double>* S_out,
+                   uint32_t* iters, bool* converged, std::string* err) {
+  return RefineAny(db, kmer_length, S, &t, nullptr, -1, n_iter, one_per_protein, pseudo, device, S_out, nullptr, iters,
+                   converged, err);
+}
+
+int RefineProfilesWeighted(const ProteinDB& db, uint32_t kmer_length, const std::vector<double>& S,
+                           const std::vector<double>* t, const std::vector<uint64_t>* rank, bool neff_columns,
+                           uint32_t n_iter, bool one_per_protein, double pseudo, int device, std::vector<double>* S_out,
+                           std::vector<double>* t_out, uint32_t* iters, bool* converged, std::string* err) {
+  if ((t != nullptr) == (rank != nullptr) || (rank && !t_out)) {
+    if (err) *err = "exactly one of the thresholds and the ranks must be given, and t_out with the ranks";
+    return HS_ERR_INVALID;
+  }
+  return RefineAny(db, kmer_length, S, t, rank, neff_columns ? 1 : 0, n_iter, one_per_protein, pseudo, device, S_out, t_out,
+                   iters, converged, err);
 }
 
 int RankThresholds(const ProteinDB& db, uint32_t kmer_length, const std::vector<double>& S,
@@ -1096,32 +1129,8 @@ int RefineProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<
                    const std::vector<uint64_t>& rank, uint32_t n_iter, bool one_per_protein, double pseudo, int device,
                    std::vector<double>* S_out, std::vector<double>* t_out, uint32_t* iters, bool* converged,
                    std::string* err) {
-  const uint32_t k = kmer_length;
-  const size_t nm = rank.size();
-  if (k < 2 || S.size() != nm * (size_t)k * HS_ALPHABET) {
-    if (err) *err = k < 2 ? "kmer length 1 is not supported on a FASTA database" : "the profiles do not match the kmer length";
-    return HS_ERR_INVALID;
-  }
-  const size_t n_seq = db.start.empty() ? 0 : db.start.size() - 1;
-  hs_handle* h = nullptr;
-  uint64_t n_win = 0;
-  std::vector<uint32_t> win_pos;
-  std::vector<uint64_t> id_start;
-  hs_status st = (hs_status)OpenWindowsIndex(db, k, device, &h, &n_win, &win_pos, &id_start, err);
-  HandleCloser closer = {h};
-  if (st != HS_OK) return st;
-  S_out->assign(S.size(), 0.0);
-  t_out->assign(nm, 0.0);
-  uint32_t done = 0, conv = 0;
-  st = hs_pssm_refine_rank(h, S.data(), rank.data(), nm, one_per_protein ? id_start.data() : nullptr, n_seq, nullptr,
-                           pseudo, n_iter, S_out->data(), t_out->data(), nullptr, nullptr, &done, &conv);
-  if (st != HS_OK) {
-    if (err) *err = std::string("hs_pssm_refine_rank: ") + hs_last_error(h);
-    return st;
-  }
-  if (iters) *iters = done;
-  if (converged) *converged = conv != 0;
-  return HS_OK;
+  return RefineAny(db, kmer_length, S, nullptr, &rank, -1, n_iter, one_per_protein, pseudo, device, S_out, t_out, iters,
+                   converged, err);
 }
 
 // "<first token of the protein's name>#<its number>": how the search's k-mer names begin

@@ -228,6 +228,13 @@ int RefineProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<
                    const std::vector<uint64_t>& rank, uint32_t n_iter, bool one_per_protein, double pseudo, int device,
                    std::vector<double>* S_out, std::vector<double>* t_out, uint32_t* iters, bool* converged,
                    std::string* err);
+// `--pssm FILE --pssm-refine N --pssm-weights sites|columns`: RefineProfiles on Henikoff-weighted counts
+// (hs_pssm_refine_weighted).  Exactly one of t (fixed thresholds) and rank (the threshold rule; t_out is required then)
+// is given.  neff_columns: the log-odds take n_eff = distinct / k, else n_eff = the sites.
+int RefineProfilesWeighted(const ProteinDB& db, uint32_t kmer_length, const std::vector<double>& S,
+                           const std::vector<double>* t, const std::vector<uint64_t>* rank, bool neff_columns,
+                           uint32_t n_iter, bool one_per_protein, double pseudo, int device, std::vector<double>* S_out,
+                           std::vector<double>* t_out, uint32_t* iters, bool* converged, std::string* err);
 // `--pssm FILE --pssm-pvalue P`: per profile the threshold of the p-value p[m] in (0, 1] under the null model of the
 // database's residue composition (hs_pssm_pvalue_threshold with bg = NULL), on a score grid from t_lo[m] to the
 // profile's maximal score.  t_out [nm]; p_hi, p_lo (may be null): the bracket of the p-value at t_out; flag (may be

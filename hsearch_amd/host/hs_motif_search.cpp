@@ -48,6 +48,10 @@
 // and -o holds exactly what --pssm FILE2 writes.  With --pssm-refine I beside it the loop scans at that threshold in
 // every iteration (hs_pssm_refine_rank) and FILE2 holds the final matrices and the last scan's thresholds.
 // --pssm-rank without --pssm or without --pssm-out is refused.
+// --pssm-weights sites|columns beside --pssm-refine N (with or without --pssm-rank and --pssm-one-per-protein): the loop
+// weighs its sites with position-based sequence weights (hs_pssm_refine_weighted) and takes the log-odds at n_eff = the
+// sites or = the mean number of distinct residues per column; FILE2 and -o are written as --pssm-refine writes them.
+// --pssm-weights without --pssm-refine, and any other value, are refused.
 // --pssm FILE --pssm-pvalue P --pssm-out FILE2: every threshold of FILE is replaced by the threshold of the p-value P
 // (0 < P <= 1) under the null model of the database's residue composition (hs_pssm_pvalue_threshold), on a score grid
 // from --pssm-null-floor X [0] to the profile's maximal score; FILE2 is FILE with those thresholds and -o holds exactly
@@ -120,6 +124,7 @@ const Opt kOpts[] = {
     {"pssm-rank", 'k', "with --pssm and --pssm-out: replace every threshold by the score of the profile's N-th best window over the database, 1..windows; -o then holds what --pssm with that file gives [off]", false},
     {"pssm-one-per-protein", 'I', "with --pssm-refine: only the best window of every protein counts [0]", false},
     {"pssm-pseudo", 'u', "with --pssm-refine: pseudo-counts of the log-odds, > 0 [1]", false},
+    {"pssm-weights", 'w', "with --pssm-refine: weigh the sites with position-based sequence weights; the log-odds count 'sites' or 'columns' (distinct residues per column) as observations [off: every site counts 1]", false},
 };
 
 // A points file has a line of numbers after its first name line; a FASTA file has residue letters.
@@ -200,6 +205,14 @@ int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::str
       }
     }
   }
+  int weights = -1;  // -1: every site counts 1; 0: weighted, n_eff = the sites; 1: n_eff = distinct residues per column
+  if (val.count("pssm-weights")) {
+    weights = val["pssm-weights"] == "sites" ? 0 : val["pssm-weights"] == "columns" ? 1 : -1;
+    if (weights < 0) {
+      fprintf(stderr, "ERROR: --pssm-weights takes 'sites' or 'columns'\n");
+      return EXIT_FAILURE;
+    }
+  }  // (main has refused --pssm-weights without --pssm-refine)
   uint64_t rank_n = 0;  // 0: the thresholds as the file gives them
   if (val.count("pssm-rank")) {
     const std::string& text = val["pssm-rank"];
@@ -324,10 +337,14 @@ int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::str
       std::vector<double> refined, t_last;
       uint32_t iters = 0;
       bool converged = false;
-      const int rst = rank_n ? hsearch::RefineProfiles(prodb, kmer_length, S, ranks, refine, one_per_protein, pseudo,
-                                                       device, &refined, &t_last, &iters, &converged, &err)
-                             : hsearch::RefineProfiles(prodb, kmer_length, S, t, refine, one_per_protein, pseudo, device,
-                                                       &refined, &iters, &converged, &err);
+      const int rst = weights >= 0 ? hsearch::RefineProfilesWeighted(prodb, kmer_length, S, rank_n ? nullptr : &t,
+                                                                     rank_n ? &ranks : nullptr, weights == 1, refine,
+                                                                     one_per_protein, pseudo, device, &refined, &t_last,
+                                                                     &iters, &converged, &err)
+                      : rank_n ? hsearch::RefineProfiles(prodb, kmer_length, S, ranks, refine, one_per_protein, pseudo,
+                                                         device, &refined, &t_last, &iters, &converged, &err)
+                               : hsearch::RefineProfiles(prodb, kmer_length, S, t, refine, one_per_protein, pseudo, device,
+                                                         &refined, &iters, &converged, &err);
       if (rank_n && rst == 0) t.swap(t_last);
       if (rst != 0) {
         fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), rst);
@@ -429,7 +446,7 @@ int main(int argc, const char* argv[]) {
     fprintf(stderr, "ERROR: --pssm-rank sets the thresholds of --pssm FILE: it cannot be given without it\n");
     return EXIT_FAILURE;
   }
-  for (const char* name : {"pssm-refine", "pssm-out", "pssm-one-per-protein", "pssm-pseudo"})
+  for (const char* name : {"pssm-refine", "pssm-out", "pssm-one-per-protein", "pssm-pseudo", "pssm-weights"})
     if (val.count(name) && !(with_pssm && (val.count("pssm-refine") ||
                                            (std::string(name) == "pssm-out" &&
                                             (val.count("pssm-rank") || val.count("pssm-pvalue")))))) {

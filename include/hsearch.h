@@ -116,6 +116,8 @@ typedef struct hs_profile {
   uint64_t pssm_seq_rows;      /* hs_pssm_seq_scan*: the (profile, sequence) rows the call found (its *n_out) */
   uint64_t pssm_count_sites;   /* hs_pssm_hit_counts*: the sites counted, the sum of used[] */
   uint64_t pssm_count_items;   /* hs_pssm_hit_counts*: the (profile run, chunk) work items of the counting kernel */
+  uint64_t pssm_weight_sites;  /* hs_pssm_weighted_counts*: the sites weighted (pssm_count_sites; 0 after other calls) */
+  uint64_t pssm_weight_items;  /* hs_pssm_weighted_counts*: the work items of the weight kernel (pssm_count_items) */
   uint64_t pssm_null_bins;     /* hs_pssm_pvalue*: the bins B of the score grid the call used (HS_OPT_PSSM_NULL_BINS) */
   uint64_t pssm_null_profiles; /* hs_pssm_pvalue*: profiles whose null distribution the call convolved */
   uint64_t pssm_rank_sample;   /* hs_pssm_rank*: the sample size n_s = min(n, HS_OPT_PSSM_RANK_SAMPLE) the call used */
@@ -1325,8 +1327,8 @@ HS_API hs_status hs_pssm_seq_hits(const uint32_t* m, const uint32_t* id, const d
  * (S_i on convergence at i, else S_{n_iter}); counts, used (may be NULL): of the last scan; *iters: the scans run, not
  * counting the background's; *converged.  If it converged, hs_pssm_hit_counts(S_out, t) gives counts.  Per iteration
  * only counts (down) and S (up) cross PCIe.  Nothing is written when the arguments or S0's values are refused.
- * Out of scope: sequence weighting, a device log-odds (device log2 is not the host's bit for bit), multi-GPU drivers
- * (hs_pssm_count_hits is the merge).  (A threshold update rule: hs_pssm_refine_rank below.) */
+ * Out of scope: a device log-odds (device log2 is not the host's bit for bit), multi-GPU drivers (hs_pssm_count_hits is
+ * the merge).  (A threshold update rule: hs_pssm_refine_rank below; sequence weights: hs_pssm_refine_weighted below.) */
 HS_API hs_status hs_pssm_hit_counts(hs_handle* h, const double* S, const double* t, uint64_t nm,
                                     const uint64_t* id_start, uint64_t n_seq, uint32_t* counts, uint64_t* cnt,
                                     uint64_t* used, uint64_t* n_hits);
@@ -1415,6 +1417,79 @@ HS_API hs_status hs_pssm_refine_rank(hs_handle* h, const double* S0, const uint6
                                      const uint64_t* id_start, uint64_t n_seq, const double* bg, double pseudo,
                                      uint32_t n_iter, double* S_out, double* t_out, uint32_t* counts, uint64_t* used,
                                      uint32_t* iters, uint32_t* converged);
+
+/* ---- PSSM sequence weights: Henikoff-weighted counts and the weighted refine loop -------------------------------- */
+
+/* hs_pssm_hit_counts counts every site as 1, so a family present in hundreds of near-identical copies owns the profile
+ * rebuilt from it.  These calls weigh the sites with position-based sequence weights (Henikoff and Henikoff 1994), in
+ * integers, so that the result is as free of summation order as the raw counts are.
+ *
+ * The rule.  For profile m let its sites be exactly hs_pssm_hit_counts' (every hit, or with id_start the best hit of
+ * every (profile, protein) row), x_i the k-mer of site i and c[p][a] the raw counts.
+ *   r[p]        = the residues a with c[p][a] > 0;     distinct[m] = the sum over p of r[p]            (uint32)
+ *   u[p][a]     = floor(2^56 / (r[p] * c[p][a])) in 64-bit integers, 0 where c[p][a] == 0           (hs_pssm_weight_u)
+ *   W(i)        = the sum over p of u[p][x_ip]                                                       (uint64)
+ *   wcounts[m][p][a] = the sum of W(i) over the sites with x_ip == a;   wsum[m] = the sum of W(i) over the sites
+ * For every m and p the sum over a of wcounts[m][p][a] is wsum[m].  Nothing overflows: wsum = sum_p sum_a c[p][a] *
+ * u[p][a] and c * floor(2^56 / (r c)) <= 2^56 / r for each of the r residues that occur, so wsum[m] <= k * 2^56 <= 75 *
+ * 2^56 < 2^63, and every W(i) and wcounts entry is a partial sum of it.
+ *
+ * hs_pssm_weighted_counts.  S, t, id_start, n_seq, cnt, used, *n_hits: hs_pssm_hit_counts'.  counts (may be NULL: the
+ * handle's scratch holds them), wsum [nm], distinct [nm], cnt, used may be NULL; wcounts uint64 [nm][k][alphabet] is
+ * required with nm > 0.  Every array given is written whole (zeros for a profile without hits); the output is dense,
+ * there is no capacity protocol.  counts is what hs_pssm_hit_counts gives on the same handle.
+ * Errors, reported before anything is written: everything hs_pssm_hit_counts refuses (wcounts in the place of counts).
+ * The _dev form finds the value errors on the device with one read-back.
+ * Purity: a pure function of (codes, S, t, id_start).  HS_OPT_QUERY_BATCH, HS_OPT_PSSM_FILTER,
+ * HS_OPT_PSSM_COUNT_CHUNK, survivor splits and scheduling do not show in it.
+ * How (hsearch_amd/csrc/hs_pssm_weights.hip): hs_pssm_hit_counts' batches and count pass as they are; every hit of a
+ * profile lies in one batch, so after the count pass a small kernel turns the batch's counts into u tables and
+ * distinct, and a second pass over the same sites and work items reduces W(i) across the lanes of a site and adds it
+ * into a uint64 LDS histogram per wave -- stored plainly for a whole run, added with 64-bit integer atomics for a cut
+ * one.  hs_pssm_hit_counts itself launches what it launched.
+ * hs_profile after the call: as after hs_pssm_hit_counts, and pssm_weight_sites, pssm_weight_items.
+ *
+ * hs_pssm_refine_weighted (host pointers).  hs_pssm_refine's loop, refusals and outputs (t given, rank NULL) or
+ * hs_pssm_refine_rank's (rank given, t NULL; t_out required) -- exactly one of t and rank -- with these changes:
+ * iteration i computes (C_i, WC_i, wsum_i, distinct_i) = hs_pssm_weighted_counts(S_i, t_i); the loop has converged when
+ * C_i == C_{i-1} and WC_i == WC_{i-1} byte for byte; otherwise S_{i+1}[m] = hs_pssm_log_odds_weighted(WC_i[m], wsum_i[m],
+ * n_eff) where used_i[m] > 0, with n_eff = (double)used_i[m] (neff_rule 0: the weights only reshape the frequencies) or
+ * (double)distinct_i[m] / (double)k (neff_rule 1: the mean number of distinct residues per column, PSI-BLAST's measure
+ * of the independent evidence).  Another neff_rule is HS_ERR_INVALID.  counts, wcounts, wsum, distinct, used (each may
+ * be NULL): of the last scan.  hs_pssm_refine and hs_pssm_refine_rank are unchanged.
+ * Out of scope: weights for hs_cluster_profile, position-specific pseudo-counts, a device log-odds, multi-GPU drivers --
+ * weights do NOT merge from per-GPU wcounts (they depend on the global counts); hs_pssm_weight_hits over the merged hit
+ * list is the merge. */
+HS_API hs_status hs_pssm_weighted_counts(hs_handle* h, const double* S, const double* t, uint64_t nm,
+                                         const uint64_t* id_start, uint64_t n_seq, uint32_t* counts, uint64_t* wcounts,
+                                         uint64_t* wsum, uint32_t* distinct, uint64_t* cnt, uint64_t* used,
+                                         uint64_t* n_hits);
+/* ... every pointer but n_hits in device memory (streams: as hs_pssm_scan_dev) */
+HS_API hs_status hs_pssm_weighted_counts_dev(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm,
+                                             const uint64_t* d_id_start, uint64_t n_seq, uint32_t* d_counts,
+                                             uint64_t* d_wcounts, uint64_t* d_wsum, uint32_t* d_distinct,
+                                             uint64_t* d_cnt, uint64_t* d_used, uint64_t* n_hits);
+HS_API hs_status hs_pssm_refine_weighted(hs_handle* h, const double* S0, const double* t, const uint64_t* rank,
+                                         uint64_t nm, const uint64_t* id_start, uint64_t n_seq, const double* bg,
+                                         double pseudo, uint32_t neff_rule, uint32_t n_iter, double* S_out,
+                                         double* t_out, uint32_t* counts, uint64_t* wcounts, uint64_t* wsum,
+                                         uint32_t* distinct, uint64_t* used, uint32_t* iters, uint32_t* converged);
+/* The weighting rule on the host (no GPU, no handle) for any list of (m, id, score) tuples in any order: the site
+ * selection and every refusal are hs_pssm_count_hits'; k > 127 and a null wcounts with nm > 0 are HS_ERR_INVALID too.
+ * counts, wsum, distinct and used may be NULL.  Nothing is written when it refuses. */
+HS_API hs_status hs_pssm_weight_hits(const uint8_t* codes, uint64_t n, uint32_t k, uint32_t alphabet, const uint32_t* m,
+                                     const uint32_t* id, const double* score, uint64_t n_tuples, uint64_t nm,
+                                     const uint64_t* id_start, uint64_t n_seq, uint32_t* counts, uint64_t* wcounts,
+                                     uint64_t* wsum, uint32_t* distinct, uint64_t* used);
+/* S[m][p][a] = log2(((f * n_eff[m] + pseudo * bg[a]) / (n_eff[m] + pseudo)) / bg[a]), f = wsum[m] ? (double)wcounts[m][p][a]
+ * / (double)wsum[m] : 0.0; every operation rounded to fp64, no FMA contraction, log2 the C library's.  Everything
+ * hs_pssm_log_odds refuses, an n_eff that is not finite or below 0 and a wcounts entry above its wsum are
+ * HS_ERR_INVALID; nothing is written then. */
+HS_API hs_status hs_pssm_log_odds_weighted(const uint64_t* wcounts, const uint64_t* wsum, const double* n_eff,
+                                           uint64_t nm, uint32_t k, uint32_t alphabet, const double* bg, double pseudo,
+                                           double* S_out);
+/* u(r, c) = floor(2^56 / (r * c)), 0 where r == 0 or c == 0: r residues occur at the position, this one c times. */
+HS_API uint64_t hs_pssm_weight_u(uint32_t r, uint32_t c);
 
 /* ---- PSSM p-values: thresholds and hit significance from a null model ------------------------------------------- */
 
