@@ -1,9 +1,10 @@
 // hs_handle.h -- the handle behind include/hsearch.h, private to the host layer of the C ABI: the types struct hs_handle
 // is made of, the error macros and internal statuses of a call, and the survivor-capacity loop every batch runs under
 // (filter_passes: a template, so that the query path and the profile path each get their pass inlined).  Included by
-// hs_capi.hip (the handle's life, the index, the queries and what reduces their hits) and hs_capi_pssm.hip (the
-// profile calls).  The types have external linkage on purpose: both files must see ONE struct hs_handle.  Its layout
-// depends on -DHS_TEST_HOOKS (Knobs), so every file that includes this is compiled once with and once without it.
+// hs_capi.hip (the handle's life, the queries and what reduces their hits), hs_capi_index.hip (the index calls) and
+// hs_capi_pssm.hip (the profile calls).  The types have external linkage on purpose: all of them must see ONE struct
+// hs_handle.  Its layout depends on -DHS_TEST_HOOKS (Knobs), so every file that includes this is compiled once with
+// and once without it.
 #pragma once
 #include <stdio.h>
 #include <stdlib.h>
@@ -351,6 +352,13 @@ hs_status fail(hs_handle* h, hs_status st, const std::string& msg);
 float ev_ms(hs_handle* h, int i0, int i1);
 hs_status ensure_device(hs_handle* h);
 hs_status ensure_pin_cnt(hs_handle* h);
+// ... and what the index calls (hs_capi_index.hip) share with the rest.  drop_index: the index is about to change or go;
+// hash_dispatch: bucket ints of one table's functions (or all) for n points on a stream, set = which flag list and
+// counter pair; hash_account: the pass's statistics into the profile, after a synchronisation of that stream.
+void drop_index(hs_handle* h);
+hs_status hash_dispatch(hs_handle* h, const uint8_t* d_codes, const double* d_pts, uint64_t n, int table, int32_t* out,
+                        int out_stride, int set, hipStream_t s);
+hs_status hash_account(hs_handle* h, uint64_t n, int F, int set);
 
 #define HS_HIP(h, expr)                                                                      \
   do {                                                                                       \

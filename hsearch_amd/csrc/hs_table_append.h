@@ -1,5 +1,5 @@
 // hs_table_append.h -- hs_index_table_append (include/hsearch.h): one table of an index merged with the bucket ints
-// of an appended block, on the host.  Plain C++ (no HIP): hs_capi.hip wraps it, and the tests compile it with a
+// of an appended block, on the host.  Plain C++ (no HIP): hs_capi_index.hip wraps it, and the tests compile it with a
 // stand-alone main under the sanitizers.  The rule is hs_append.hip's: entries ordered by (fingerprint, id), the
 // block's ids all larger than the table's, an old bucket keeps its tuple.
 // Returns 0 (HS_OK), 1 (HS_ERR_INVALID) or 4 (HS_ERR_CAPACITY).

@@ -1,5 +1,5 @@
 // hs_table_remove.h -- hs_index_table_remove (include/hsearch.h): one table of an index without a set of its ids,
-// on the host.  Plain C++ (no HIP): hs_capi.hip wraps it, and the tests compile it with a stand-alone main under
+// on the host.  Plain C++ (no HIP): hs_capi_index.hip wraps it, and the tests compile it with a stand-alone main under
 // the sanitizers.  The rule is hs_remove.hip's: entries ordered by (fingerprint, id), survivors renumbered in
 // their old order, so the table over the remainder is a compaction of the entries and of the directory.  A bucket
 // keeps its fingerprint (it belongs to the HashKey string); its tuple is copied while its first member survives

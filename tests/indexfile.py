@@ -1,4 +1,4 @@
-"""Test helper: an index file (the format of hs_index_save, hsearch_amd/csrc/hs_capi.hip
+"""Test helper: an index file (the format of hs_index_save, hsearch_amd/csrc/hs_capi_index.hip
 IndexFileHeader + payload) written on the HOST from the oracle's bucket ints -- so the file checks
 can be tested without a GPU, and a GPU handle can be asked to load an index it did not build."""
 import struct
@@ -12,7 +12,7 @@ CHUNK = 64 << 20
 
 
 class PayloadHash:
-    """hs_capi.hip PayloadHash: order-dependent 64-bit hash over sections of at most 64 MiB."""
+    """hs_capi_index.hip PayloadHash: order-dependent 64-bit hash over sections of at most 64 MiB."""
 
     def __init__(self):
         self.h = 0x9e3779b97f4a7c15

@@ -16,7 +16,7 @@ def kernel_source_hash():
     """sha256 over the sources of the search's kernels, the multi-probe ones included"""
     h = hashlib.sha256()
     for f in ("hs_join8.hip", "hs_join.hip", "hs_kernels.hip", "hs_internal.h", "hs_multiprobe.hip", "hs_capi.hip",
-              "hs_handle.h"):
+              "hs_capi_index.hip", "hs_handle.h"):
         h.update(open(os.path.join(ROOT, "hsearch_amd", "csrc", f), "rb").read())
     return h.hexdigest()[:16]
 
