@@ -70,7 +70,8 @@ class _Profile(C.Structure):
                 ("hash_values", C.c_uint64), ("hash_flagged", C.c_uint64),
                 ("join_row_bytes", C.c_uint32), ("join_wide", C.c_uint32), ("join_items_resident", C.c_uint64),
                 ("join_async_retries", C.c_uint64), ("queries_recognised", C.c_uint64),
-                ("join_f6_batches", C.c_uint64), ("append_rebuilds", C.c_uint64),
+                ("join_f6_batches", C.c_uint64), ("join_f6_wide_items", C.c_uint64),
+                ("append_rebuilds", C.c_uint64),
                 ("append_new_buckets", C.c_uint64), ("remove_rebuilds", C.c_uint64),
                 ("remove_dead_buckets", C.c_uint64), ("remove_retupled", C.c_uint64),
                 ("pssm_pairs", C.c_uint64), ("pssm_survivors", C.c_uint64), ("pssm_dead", C.c_uint64),
@@ -1349,7 +1350,7 @@ class Engine:
                "join_min_q": 12, "join_min_m": 13, "sort_from_bit": 14, "build_serial": 15,
                "join_xcd_run": 16, "probe_records": 17, "join_chunk": 18, "summary_chunk": 19, "summary_rows": 20,
                "msf_edge_budget": 21, "join_f6": 22, "pssm_filter": 23, "pssm_topk_sample": 24, "pssm_rank_sample": 26,
-               "pssm_count_chunk": 25, "pssm_null_bins": 27}
+               "pssm_count_chunk": 25, "pssm_null_bins": 27, "join_f6_form": 28}
 
     def set_option(self, name, value):
         """hs_set_option (include/hsearch.h hs_option): path selection / batch sizing; never changes a result."""

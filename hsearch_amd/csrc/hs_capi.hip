@@ -228,7 +228,7 @@ const struct { const char* name; int option; } kOptionNames[] = {
     {"sort_hits", HS_OPT_SORT_HITS}, {"sync_items", HS_OPT_SYNC_ITEMS}, {"join_min_q", HS_OPT_JOIN_MIN_Q},
     {"join_min_m", HS_OPT_JOIN_MIN_M}, {"sort_from_bit", HS_OPT_SORT_FROM_BIT}, {"build_serial", HS_OPT_BUILD_SERIAL},
     {"join_xcd_run", HS_OPT_JOIN_XCD_RUN}, {"probe_records", HS_OPT_PROBE_RECORDS},
-    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"join_f6", HS_OPT_JOIN_F6}, {"pssm_filter", HS_OPT_PSSM_FILTER}, {"pssm_topk_sample", HS_OPT_PSSM_TOPK_SAMPLE}, {"pssm_rank_sample", HS_OPT_PSSM_RANK_SAMPLE}, {"pssm_null_bins", HS_OPT_PSSM_NULL_BINS}, {"pssm_count_chunk", HS_OPT_PSSM_COUNT_CHUNK}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS},
+    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"join_f6", HS_OPT_JOIN_F6}, {"join_f6_form", HS_OPT_JOIN_F6_FORM}, {"pssm_filter", HS_OPT_PSSM_FILTER}, {"pssm_topk_sample", HS_OPT_PSSM_TOPK_SAMPLE}, {"pssm_rank_sample", HS_OPT_PSSM_RANK_SAMPLE}, {"pssm_null_bins", HS_OPT_PSSM_NULL_BINS}, {"pssm_count_chunk", HS_OPT_PSSM_COUNT_CHUNK}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS},
     {"msf_edge_budget", HS_OPT_MSF_EDGE_BUDGET}};
 
 void read_knobs(hs_handle* h) {
@@ -242,6 +242,7 @@ void read_knobs(hs_handle* h) {
   kn.test_group_fallback = on("HS_TEST_GROUP_FALLBACK");
   kn.test_append_collision = on("HS_TEST_APPEND_COLLISION");
   kn.test_remove_reseed = on("HS_TEST_REMOVE_RESEED");
+  kn.test_rec6_no_room = on("HS_TEST_REC6_NO_ROOM");
 #endif
   if (const char* m = getenv("HS_HASH_MODE")) {
     if (!strcmp(m, "exact")) h->hash_mode = 1;
@@ -516,6 +517,10 @@ hs_status hs_set_option(hs_handle* h, int option, int64_t value) {
     }
     case HS_OPT_REFINE8: return flag(&kn.no_refine8, true);
     case HS_OPT_JOIN_F6: return flag(&kn.no_join_f6, true);
+    case HS_OPT_JOIN_F6_FORM:
+      if (value < -1 || value > 1) break;
+      kn.join_f6_form = (int)value;
+      return HS_OK;
     case HS_OPT_PSSM_FILTER: return flag(&kn.no_pssm_filter, true);
     case HS_OPT_PSSM_TOPK_SAMPLE:
       if (value < 1 || value > 0xffffffffll) break;
@@ -712,7 +717,7 @@ static inline int seg_shift_of(const hs_handle* h) {
 // hs_launch_item_desc leaves in seg_n[2..3] (hs_join8r_kernel's share) from the scan's last word.
 // clear_slices: the probes wrote slice counts although every segment is joined (bucket partition): cleared here.
 static hs_status cut_items(hs_handle* h, uint32_t nql, uint32_t jm, unsigned long long* d_jstats,
-                           uint32_t max_q_res, uint32_t n_probes, bool clear_slices) {
+                           uint32_t max_q_res, uint32_t n_probes, bool clear_slices, uint32_t jm_stream = 0) {
   const size_t n1 = (size_t)nql + 1;
   // every segment with a member goes to the join (the default): no probe keeps a slice for the streaming filter
   const bool all_joined = h->join_min_q == 1 && h->join_min_m == 1;
@@ -726,7 +731,8 @@ static hs_status cut_items(hs_handle* h, uint32_t nql, uint32_t jm, unsigned lon
                                 h->sorted_ql.as<uint32_t>(), h->qcount.as<uint32_t>(), nql,
                                 h->join_min_q, h->join_min_m, jm, (int)h->p.L, seg_shift_of(h), max_q_res, 512u,
                                 h->seg_items.as<uint32_t>(), cls, d_jstats,
-                                all_joined ? nullptr : h->nslices.as<uint32_t>(), h->seg_of.as<uint32_t>(), h->stream));
+                                all_joined ? nullptr : h->nslices.as<uint32_t>(), h->seg_of.as<uint32_t>(), h->stream,
+                                jm_stream));
   if (all_joined && clear_slices) HS_HIP(h, hipMemsetAsync(h->nslices.p, 0, (size_t)n_probes * 4, h->stream));
   HS_HIP(h, hs_exclusive_scan_u64(h->temp.p, h->temp.cap, cls, cls_pos, n1, h->stream));
   HS_HIP(h, hs_launch_seg_order(cls_pos, h->seg_items.as<uint32_t>(), nql, order, items_ord, h->stream));
@@ -869,6 +875,12 @@ static hs_status ensure_rec8w(hs_handle* h) {
 // error is cleared; the index keeps the int8 join)
 static bool ensure_rec6(hs_handle* h) {
   if (h->rec6_state) return h->rec6_state > 0;
+#ifdef HS_TEST_HOOKS
+  if (h->knobs.test_rec6_no_room) {
+    h->rec6_state = -1;
+    return false;
+  }
+#endif
   const size_t n = h->n;
   const int L = (int)h->p.L;
   if (h->t_rec6.reserve(((size_t)L * n + HS_JM_WAVE) * 16) != hipSuccess) {
@@ -921,6 +933,8 @@ struct BatchPlan {
   bool use_r = false;       // segments with few probing queries through hs_join8r_kernel
   bool f6 = false;          // the other segments through hs_join6x_kernel (FP6 rows) instead of hs_join8x_kernel
   uint32_t jm = HS_JM_BLOCK;  // members per join work item
+  uint32_t jm_stream = 0;     // ... of the segments outside the resident kernel's class, where it differs (f6 on
+                              // hs_join6w_kernel: 192); 0: jm
   bool async_items = false;   // the item count stays on the device; the descriptors are sized by item_cap
   uint32_t item_cap = 0;
   bool order_here = false;    // the batch orders its hits per query itself (no sort afterwards)
@@ -973,6 +987,8 @@ static BatchPlan plan_batch(const hs_handle* h, const QueryCall& c, uint32_t nq,
   // table over residue PAIRS, so centres that are no k-mers have none).  query_batch builds the member records.
   p.f6 = (p.self_codes || p.ext_codes) && !p.wide && k >= 21 && k <= 25 && h->alphabet <= 32 && h->PW == 1 &&
          h->join6_tables_ok && !h->knobs.no_join_f6 && h->rec6_state >= 0;
+  // ... on items of 192 members (hs_join6w_kernel) unless HS_OPT_JOIN_F6_FORM says 0
+  p.jm_stream = (p.f6 && h->knobs.join_f6_form != 0) ? hs_join6_wide_item() : 0u;
   // No host round trip when the int8 join takes every segment and the previous batch left a
   // capacity hint: the item count stays on the device (item_off[nqs]); join legality and the
   // capacity are checked with the batch's final read-back, a violation repeats the batch the
@@ -1063,7 +1079,7 @@ static hipError_t launch_probe(hs_handle* h, const QueryCall& c, const BatchPlan
 // Work items of the plan's size from the segments, the resident kernel's class as their tail
 static hs_status cut_plan_items(hs_handle* h, const BatchPlan& p, const Batch& b) {
   unsigned long long* const d_jstats = reinterpret_cast<unsigned long long*>(h->counters.as<uint32_t>() + 10);
-  return cut_items(h, b.nqs, p.jm, d_jstats, p.use_r ? HS_JR_MAXQ : 0u, b.nql, !p.no_slices);
+  return cut_items(h, b.nqs, p.jm, d_jstats, p.use_r ? HS_JR_MAXQ : 0u, b.nql, !p.no_slices, p.jm_stream);
 }
 
 // Where every probe's slices start in the streaming filter's grid (every segment joined -- the default --:
@@ -1217,6 +1233,7 @@ static hs_status demote(hs_handle* h, const QueryCall& c, BatchPlan& p, Batch& b
       HS_HIP(h, hipMemcpyAsync(&unsafe, d_cnt + 8, 4, hipMemcpyDeviceToHost, h->stream));
       if (p.jm != HS_JM_BLOCK) {  // the fp16 kernel works on 512-member items: cut the segments again
         p.jm = HS_JM_BLOCK;
+        p.jm_stream = 0;
         p.use_r = false;
         HS_HIP(h, hipMemsetAsync(d_cnt + 10, 0, 16, h->stream));
         HS_CHECK(cut_plan_items(h, p, b));
@@ -1265,7 +1282,8 @@ static hs_status read_items(hs_handle* h, const QueryCall& c, BatchPlan& p, Batc
                                   seg_shift_of(h), h->seg_vals.as<uint32_t>(), h->PW,
                                   p.async_items ? h->item_off.as<uint32_t>() + b.nqs : nullptr,
                                   h->seg_res.as<uint64_t>(), h->seg_n.as<uint32_t>() + 2,
-                                  h->counters.as<uint32_t>() + HS_CNT_SPLIT, h->item_desc.as<uint4>(), h->stream));
+                                  h->counters.as<uint32_t>() + HS_CNT_SPLIT, h->item_desc.as<uint4>(), h->stream,
+                                  p.jm_stream));
   }
   // segments routed away from the join (HS_OPT_JOIN_MIN_Q / _M; none by default) go through the streaming
   // filter and its per-query distance tables, on the side stream beside the join
@@ -1313,14 +1331,15 @@ static hs_status launch_filters(hs_handle* h, const BatchPlan& p, const Batch& b
     const uint32_t xcd_run = p.xcd_run >= 0 ? (uint32_t)p.xcd_run : (tile_bytes > (64ull << 20) ? 128u : 0u);
     const uint32_t* const d_n_items =
         p.use_r ? d_split : (p.async_items ? h->item_off.as<uint32_t>() + b.nqs : nullptr);
-    if (p.f6)
+    if (p.f6) {
+      uint32_t G = hs_join8_chunk_items(b.n_items, join_blocks, h->hist.pairs_per_item, h->knobs.join_chunk);
+      // items of 192 members take 1.5 times as long, and what is lost at the kernel's end is paid in chunks: half
+      // the items per chunk (bench.py's default workload: 8 -> 4 took 2 % off the kernel; 2 added 20 %)
+      if (p.jm_stream && !h->knobs.join_chunk) G = std::max(2u, (G + 1u) / 2u);
       HS_HIP(h, hs_launch_join6x(h->item_desc.as<uint4>(), b.n_items, h->tabs.t[0].packed, h->t_rec6.as<uint4>(),
                                  c6t_of(h, b), h->jtab6.p, d_cnt, prov_cap, h->prov.as<uint2>(), d_cnt + 32,
-                                 join_blocks, d_n_items,
-                                 hs_join8_chunk_items(b.n_items, join_blocks, h->hist.pairs_per_item,
-                                                      h->knobs.join_chunk),
-                                 xcd_run, h->stream));
-    else
+                                 join_blocks, d_n_items, G, xcd_run, h->stream, p.jm_stream ? 1 : 0));
+    } else
       HS_HIP(h, hs_launch_join8w(h->item_desc.as<uint4>(), b.n_items, h->tabs.t[0].packed, rec8, h->c16s.p, rows, k,
                                  p.wide, d_cnt, prov_cap, h->prov.as<uint2>(), d_cnt + 32, join_blocks, d_n_items,
                                  h->hist.pairs_per_item, xcd_run, h->stream, h->knobs.join_chunk));
@@ -1471,6 +1490,8 @@ static void account_batch(hs_handle* h, const BatchPlan& p, Batch& b) {
   h->prof.join_items += b.n_items;
   if (p.use_i8 && b.n_items && p.use_r && cnt[HS_CNT_SPLIT + 1])
     h->prof.join_items_resident += cnt[HS_CNT_SPLIT + 1] - cnt[HS_CNT_SPLIT];
+  if (p.use_i8 && b.n_items && p.f6 && p.jm_stream)  // (the items in front of the resident kernel's class)
+    h->prof.join_f6_wide_items += (p.use_r && cnt[HS_CNT_SPLIT + 1]) ? cnt[HS_CNT_SPLIT] : b.n_items;
   if (p.use_join) {
     unsigned long long js[2] = {0, 0};
     memcpy(js, cnt + 10, 16);  // the join statistics (d_cnt + 10), read back with the counters
@@ -1544,7 +1565,10 @@ static hs_status query_batch(hs_handle* h, const QueryCall& c, uint32_t nq, uint
   if (c.brute) return brute_batch(h, c, nq, q_base, n_hits);
   for (bool allow_async = true;; allow_async = false) {
     BatchPlan p = plan_batch(h, c, nq, allow_async, bout != nullptr);
-    if (p.f6 && !ensure_rec6(h)) p.f6 = false;
+    if (p.f6 && !ensure_rec6(h)) {  // the int8 kernel takes the batch, on ITS items: 128 members, not 192
+      p.f6 = false;
+      p.jm_stream = 0;
+    }
     const uint32_t nql = nq * (uint32_t)h->p.L;
     Batch b{nq, q_base, nql, nql, c.R * c.R, c.centers, d_cand};
     b.radii = c.radii;
@@ -1956,6 +1980,7 @@ static void add_profile(hs_profile& a, const hs_profile& b) {
   a.join_pairs_issued += b.join_pairs_issued;
   a.join_i8_batches += b.join_i8_batches;
   a.join_f6_batches += b.join_f6_batches;
+  a.join_f6_wide_items += b.join_f6_wide_items;
   a.hash_values += b.hash_values;
   a.hash_flagged += b.hash_flagged;
   a.join_row_bytes = b.join_row_bytes;

@@ -80,6 +80,7 @@ struct Knobs {
   bool no_wide_by_radius = false;  // HS_OPT_WIDE_ROWS >= 2: never choose 8-column rows by radius
   bool no_refine8 = false;         // HS_OPT_REFINE8 = 0: no 8-column refinement of the join's survivors
   bool no_join_f6 = false;         // HS_OPT_JOIN_F6 = 0: k-mer queries never through the FP6 join (hs_join6.hip)
+  int join_f6_form = -1;           // HS_OPT_JOIN_F6_FORM: 0 hs_join6x_kernel, 1 hs_join6w_kernel, -1 automatic
   bool no_pssm_filter = false;     // HS_OPT_PSSM_FILTER = 0: hs_pssm_scan sends every pair to the exact pass (hs_pssm.hip)
   bool no_self_codes = false;      // HS_OPT_SELF_CODES = 0: self-join from embedded centres, not from codes
   bool sort_hits = false;          // HS_OPT_SORT_HITS: order hits by the radix sort, not per query
@@ -104,6 +105,7 @@ struct Knobs {
   bool test_group_fallback = false;  // HS_TEST_GROUP_FALLBACK: the build's fingerprint table reports itself full
   bool test_append_collision = false;  // HS_TEST_APPEND_COLLISION: hs_index_append's match step reports a collision
   bool test_remove_reseed = false;     // HS_TEST_REMOVE_RESEED: hs_index_remove treats the index's seed as non-zero
+  bool test_rec6_no_room = false;      // HS_TEST_REC6_NO_ROOM: the FP6 member records report that they found no room
 #endif
 };
 

@@ -640,7 +640,9 @@ hipError_t hs_launch_seg_route(const uint64_t* d_seg_key, const uint32_t* d_seg_
                                16-query column tiles (hs_join8r_kernel); 0: none */,
                                uint32_t big_min_q, uint32_t* d_items, uint64_t* d_class,
                                unsigned long long* d_stats, uint32_t* d_nslices, const uint32_t* d_seg_of,
-                               hipStream_t s);
+                               hipStream_t s,
+                               uint32_t jm_stream = 0 /* members per item of the segments OUTSIDE the query-resident
+                               class (hs_join6w_kernel: 192); 0: jm.  The same value to hs_launch_item_desc */);
 hipError_t hs_launch_item_desc(const hs_tables_dev& tabs, const uint64_t* d_seg_key,
                                const uint32_t* d_seg_cnt,
                                const uint32_t* d_seg_qoff, const uint32_t* d_item_off, uint32_t n_max,
@@ -651,7 +653,7 @@ hipError_t hs_launch_item_desc(const hs_tables_dev& tabs, const uint64_t* d_seg_
                                const uint64_t* d_class_pos /* scan of the class flags, n_max + 1 entries */,
                                uint32_t* d_split /* [2]: first item of the query-resident class, items */,
                                uint32_t* d_split_copy /* null, or [2]: the same two words once more */,
-                               uint4* d_desc, hipStream_t s);
+                               uint4* d_desc, hipStream_t s, uint32_t jm_stream = 0);
 // item numbering order of the segments: many-query segments first (stable two-class partition):
 // class flags [n + 1] (last = 0; hs_launch_seg_route) -> hs_exclusive_scan_u64 -> d_class_pos [n + 1] ->
 // d_order[n], d_items_ordered[n + 1] (last = 0)
@@ -724,6 +726,7 @@ uint32_t hs_join8_chunk_items(uint32_t n_items, int n_blocks, double pairs_per_i
 size_t hs_join6_table_bytes();
 size_t hs_join6_ok_offset();  // of the int32 that says the tables are usable
 int hs_join6_row_bytes();
+uint32_t hs_join6_wide_item();
 hipError_t hs_launch_gather_c6t(const void* d_c6, const uint32_t* d_sorted_ql, const uint32_t* d_seg_qoff,
                                 const uint32_t* d_seg_of, uint32_t nql, int L, void* d_out, hipStream_t s);
 hipError_t hs_launch_jtables6(const double* d_coords, int alphabet, void* d_tab6, hipStream_t s);
@@ -734,7 +737,8 @@ hipError_t hs_launch_qprep6_codes(const uint8_t* d_qcodes, uint32_t nq, int k, d
 hipError_t hs_launch_join6x(const uint4* d_desc, uint32_t n_items, const uint4* d_packed_base,
                             const uint4* d_rec_base, const void* d_c6t, const void* d_tab6, uint32_t* d_prov_count,
                             uint32_t prov_cap, uint2* d_prov, uint32_t* d_item_counter, int n_blocks,
-                            const uint32_t* d_n_items, uint32_t G, uint32_t xcd_run, hipStream_t s);
+                            const uint32_t* d_n_items, uint32_t G, uint32_t xcd_run, hipStream_t s,
+                            int wide_items = 0 /* 1: hs_join6w_kernel, on items of hs_join6_wide_item() members */);
 hipError_t hs_launch_join8w(const uint4* d_desc, uint32_t n_items, const uint4* d_packed_base,
                             const uint4* d_rec_base, const void* d_c8t, const void* d_tab8, int k, int wide,
                             uint32_t* d_prov_count, uint32_t prov_cap, uint2* d_prov,

@@ -224,8 +224,8 @@ __global__ __launch_bounds__(256) void hs_seg_route_kernel(const uint64_t* __res
                                                            const uint32_t* __restrict__ sorted_ql,
                                                            const uint32_t* __restrict__ qcount,
                                                            uint32_t n_max, uint32_t min_q,
-                                                           uint32_t min_m, uint32_t jm, int L, int shift,
-                                                           uint32_t max_q_resident, uint32_t big_min_q,
+                                                           uint32_t min_m, uint32_t jm, uint32_t jm_stream, int L,
+                                                           int shift, uint32_t max_q_resident, uint32_t big_min_q,
                                                            uint32_t* __restrict__ items,
                                                            uint64_t* __restrict__ cls,
                                                            unsigned long long* __restrict__ stats) {
@@ -236,6 +236,8 @@ __global__ __launch_bounds__(256) void hs_seg_route_kernel(const uint64_t* __res
   if (j <= n_max && j < *n_seg && (seg_key[j] >> shift) < (uint64_t)L) {
     const uint32_t m = qcount[sorted_ql[seg_qoff[j]]];
     const uint32_t nq = c = seg_cnt[j];
+    // (the query-resident class, as `res` below, keeps jm; the other classes' items hold jm_stream members)
+    if (!(nq <= max_q_resident && nq < big_min_q)) jm = jm_stream;
     // thin segments (few probing queries or few members) go to the per-pair filter; a BIG bucket goes
     // to the join whatever its query count: its mostly empty query tile costs next to nothing there,
     // while the per-pair filter would walk its thousands of members in one chain of dependent loads
@@ -245,7 +247,10 @@ __global__ __launch_bounds__(256) void hs_seg_route_kernel(const uint64_t* __res
       const uint32_t rm = jm < HS_JM_BLOCK ? jm : 32u * JT;  // rows of one wave's member tile
       // (the query-resident kernel issues 16-query column tiles, the others 32-query tiles)
       const uint32_t cq = nq <= max_q_resident ? 16u : (uint32_t)JQ;
-      issued = (unsigned long long)((m + rm - 1) / rm * rm) * ((nq + cq - 1) / cq * cq);
+      // (an item of more than HS_JM_WAVE members whose bucket leaves it at most that many issues HS_JM_WAVE rows:
+      // hs_join6w_kernel's 8-row-tile body)
+      const uint32_t rest = m % rm, rest_rows = rm > HS_JM_WAVE && rest <= HS_JM_WAVE ? HS_JM_WAVE : rm;
+      issued = (unsigned long long)(m / rm * rm + (rest ? rest_rows : 0u)) * ((nq + cq - 1) / cq * cq);
       real = (unsigned long long)m * nq;
     }
   }
@@ -333,8 +338,8 @@ __global__ __launch_bounds__(256) void hs_item_desc_kernel(hs_tables_dev tabs,
                                                            uint32_t n_max,
                                                            const uint32_t* __restrict__ sorted_ql,
                                                            const uint32_t* __restrict__ qcount,
-                                                           uint32_t n_items, uint32_t jm, int shift,
-                                                           const uint32_t* __restrict__ order, int PW,
+                                                           uint32_t n_items, uint32_t jm, uint32_t jm_stream,
+                                                           int shift, const uint32_t* __restrict__ order, int PW,
                                                            const uint32_t* __restrict__ n_items_dev,
                                                            const uint64_t* __restrict__ class_pos,
                                                            uint32_t* __restrict__ split,
@@ -389,6 +394,8 @@ __global__ __launch_bounds__(256) void hs_item_desc_kernel(hs_tables_dev tabs,
   const uint32_t nQ = seg_cnt[seg], qoff = seg_qoff[seg];
   const uint32_t M = qcount[sorted_ql[qoff]];
   const uint32_t jqg = jm < HS_JM_BLOCK ? HS_JQG_WAVE : (uint32_t)JQG;
+  // (the query-resident class is the last class_pos[n_max] >> 32 positions of `order`: hs_seg_order_kernel)
+  if (lo < n_max - (uint32_t)(class_pos[n_max] >> 32)) jm = jm_stream;
   const uint32_t tiles_m = (M + jm - 1) / jm;
   const uint32_t local = item - item_off[lo];
   const uint32_t mt = local % tiles_m, qg = local / tiles_m;
@@ -750,10 +757,10 @@ hipError_t hs_launch_seg_route(const uint64_t* d_seg_key, const uint32_t* d_seg_
                                uint32_t min_q, uint32_t min_m, uint32_t jm, int L, int shift,
                                uint32_t max_q_resident, uint32_t big_min_q, uint32_t* d_items, uint64_t* d_class,
                                unsigned long long* d_stats, uint32_t* d_nslices, const uint32_t* d_seg_of,
-                               hipStream_t s) {
+                               hipStream_t s, uint32_t jm_stream) {
   hs_seg_route_kernel<<<blocks_for((uint64_t)n_max + 1), 256, 0, s>>>(
-      d_seg_key, d_seg_cnt, d_seg_qoff, d_n_seg, d_sorted_ql, d_qcount, n_max, min_q, min_m, jm, L,
-      shift, max_q_resident, big_min_q, d_items, d_class, d_stats);
+      d_seg_key, d_seg_cnt, d_seg_qoff, d_n_seg, d_sorted_ql, d_qcount, n_max, min_q, min_m, jm,
+      jm_stream ? jm_stream : jm, L, shift, max_q_resident, big_min_q, d_items, d_class, d_stats);
   // (d_nslices == null: every segment with a member goes to the join -- min_q = min_m = 1 -- and the caller
   // clears the slice counts of ALL probes with one memset instead of this kernel's scattered stores)
   if (d_nslices)
@@ -773,12 +780,12 @@ hipError_t hs_launch_item_desc(const hs_tables_dev& tabs, const uint64_t* d_seg_
                                const uint32_t* d_sorted_ql, const uint32_t* d_qcount, uint32_t n_items,
                                uint32_t jm, int shift, const uint32_t* d_order, int PW,
                                const uint32_t* d_n_items, const uint64_t* d_class_pos, uint32_t* d_split,
-                               uint32_t* d_split_copy, uint4* d_desc, hipStream_t s) {
+                               uint32_t* d_split_copy, uint4* d_desc, hipStream_t s, uint32_t jm_stream) {
   if (!n_items) return hipSuccess;
   hs_item_desc_kernel<<<blocks_for(n_items), 256, 0, s>>>(tabs, d_seg_key, d_seg_cnt, d_seg_qoff, d_item_off,
-                                                          n_max, d_sorted_ql, d_qcount, n_items, jm, shift,
-                                                          d_order, PW, d_n_items, d_class_pos, d_split, d_split_copy,
-                                                          d_desc);
+                                                          n_max, d_sorted_ql, d_qcount, n_items, jm,
+                                                          jm_stream ? jm_stream : jm, shift, d_order, PW, d_n_items,
+                                                          d_class_pos, d_split, d_split_copy, d_desc);
   return hipGetLastError();
 }
 

@@ -31,6 +31,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "hs_internal.h"
@@ -288,17 +289,31 @@ __device__ __forceinline__ void emit_survivors6(const floatx4 (&acc)[4][2], int 
   }
 }
 
-// The structure of hs_join8x_kernel (work items of 128 members owned by one wave, chunks of items from a global
-// counter or from per-XCD runs, three query tiles in flight, accumulator halves X / Y with the sign test of one in
-// the gaps of the other's MFMAs, the same survivor list), with 8 + 8 MFMAs per 32 queries instead of 16 + 16 and two
-// steps of the sign test behind each.
-__global__ __launch_bounds__(256, 2) void hs_join6x_kernel(
+// The structure of hs_join8x_kernel: work items owned by one wave, chunks of items from a global counter or from
+// per-XCD runs, NB query tiles in flight, the same survivor list.  A phase is 8 MFMAs -- 4 row tiles x 2 column
+// tiles -- with two steps of the sign test of the phase before it behind each; a query tile is RT / 4 phases.
+// Two instantiations (HS_OPT_JOIN_F6_FORM):
+//   hs_join6x_kernel = <8, 3, true>    items of 128 members, three tiles in flight, the next item's members
+//                                      prefetched into registers
+//   hs_join6w_kernel = <12, 2, false>  items of HS_J6_WIDE_ITEM = 192 members: the 4 KB of a query tile feed 24 MFMAs
+//                                      where they feed 16 above -- two thirds of the query bytes a CU pulls per MFMA,
+//                                      and the per-tile instructions that are no test spread over half as many MFMAs
+//                                      again.  What differs:
+//   - An item whose members fill at most 8 row tiles (a bucket's last item, a small bucket) runs the 8-tile body, a
+//     wave-uniform choice per item.
+//   - The members of the NEXT item are not prefetched (the registers hold four more row tiles' operands): an item
+//     loads its members when it starts, behind the first query tiles already in flight.  (Copied into LDS an item
+//     ahead instead -- global_load_lds_dwordx4, no register on the way -- the kernel ran 4 % SLOWER: loads return
+//     in order, so the next query tiles wait behind twelve copies that miss every cache.)
+//   - Two query tiles in flight, not three: a group of tiles must be an even number of phases (below); with four
+//     the compiler spills, and the kernel ran 25 % slower.
+template <int RT_MAX, int NB, bool PREFETCH>
+__device__ __forceinline__ void join6_items(
     const uint4* __restrict__ desc, uint32_t n_items, const uint4* __restrict__ packed_base,
     const uint4* __restrict__ rec_base, const char* __restrict__ c6t, const hs_j6_dev* __restrict__ T,
     uint32_t* __restrict__ prov_count, uint32_t prov_cap, uint2* __restrict__ prov,
     uint32_t* __restrict__ item_counter, uint32_t G, const uint32_t* __restrict__ n_items_dev, uint32_t xcd_run) {
   if (n_items_dev) n_items = min(n_items, __builtin_amdgcn_readfirstlane(*n_items_dev));
-  constexpr int RT = 8;  // row tiles of 16 members per wave
   __shared__ uint2 sPair[1024];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -352,31 +367,32 @@ __global__ __launch_bounds__(256, 2) void hs_join6x_kernel(
     nd0 = uniform4(desc[2 * (uint64_t)next_item]);
     nd1 = uniform4(desc[2 * (uint64_t)next_item + 1]);
   }
-  // lanes of quarters 0..2: packed member 16 t + n; quarter 3: its record
-  uint4 mk[RT];
-  constexpr int NB = 3;  // query tiles in flight per wave: the one in use + two prefetched
+  static_assert(RT_MAX == 8 || (RT_MAX == 12 && NB % 2 == 0),
+                "a group must be an even number of phases, for 2 and for 3 phases per tile");
+  constexpr uint32_t JM = 16 * RT_MAX;  // members per work item
+  // PREFETCH: lanes of quarters 0..2: packed member 16 t + n of the NEXT item; quarter 3: its record
+  uint4 mk_next[PREFETCH ? RT_MAX : 1];
+  auto load_members = [&](uint4* mk, int rt, const uint4& D0) {
+    const int64_t off = (int64_t)(((uint64_t)D0.y << 32) | (uint64_t)D0.x);
+    const uint4* src = (q == 3 ? rec_base : packed_base) + off;
+    const uint32_t idx = D0.w * JM + (uint32_t)n;
+#pragma unroll
+    for (int t = 0; t < RT_MAX; ++t)
+      if (t < rt) mk[t] = src[min(idx + 16 * t, D0.z - 1)];
+  };
+  if (PREFETCH) load_members(mk_next, RT_MAX, d0);
   constexpr uint32_t GQ = 32 * NB;
   intx8 Bq[NB][2];
-#define HS_LOAD_MEMBERS(D0)                                                              \
-  {                                                                                      \
-    const int64_t off_ = (int64_t)(((uint64_t)(D0).y << 32) | (uint64_t)(D0).x);         \
-    const uint4* src_ = (q == 3 ? rec_base : packed_base) + off_;                        \
-    const uint32_t idx_ = (D0).w * 128u + (uint32_t)n;                                   \
-    _Pragma("unroll") for (int t = 0; t < RT; ++t)                                       \
-      mk[t] = src_[min(idx_ + 16 * t, (D0).z - 1)];                                      \
-  }
   const uint32_t skew = ((blockIdx.x * 4u + (uint32_t)wave) * 40503u) & 0xffffu;
 #define HS_N_GROUPS(D1) (((D1).z - (D1).y + GQ - 1u) / GQ)
 #define HS_FIRST_Q(D1) ((D1).y + GQ * ((skew * HS_N_GROUPS(D1)) >> 16))
-#define HS_LOAD_GROUP(ROW, Q0, QEND)                                                             \
-  _Pragma("unroll") for (int u = 0; u < NB; ++u) {                                               \
-    const uint32_t qu_ = (Q0) + 32u * u < (QEND) ? (Q0) + 32u * u : (Q0);                        \
-    load_btile6(Bq[u], c6t, (ROW) + qu_, min(32u, (QEND) - qu_), lane);                          \
-  }
-  HS_LOAD_MEMBERS(d0)
   {
     const uint32_t q0 = HS_FIRST_Q(d1);
-    HS_LOAD_GROUP(d1.x, q0, d1.z)
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+      const uint32_t qu = q0 + 32u * u < d1.z ? q0 + 32u * u : q0;
+      load_btile6(Bq[u], c6t, d1.x + qu, min(32u, d1.z - qu), lane);
+    }
   }
   // bits 40 q .. 40 q + 39 of the packed word = positions 8 q .. 8 q + 7 of quarter q < 3: dwords (q, q + 1)
   // shifted down by 8 q (quarter 3 computes on its record and discards the result)
@@ -384,7 +400,7 @@ __global__ __launch_bounds__(256, 2) void hs_join6x_kernel(
   while (true) {
     const uint32_t M = d0.z, mt = d0.w;
     const uint32_t qoff = d1.x, q_begin = d1.y, q_end = d1.z, mstart = d1.w;
-    const uint32_t wbase = mt * 128u;
+    const uint32_t wbase = mt * JM;
     const bool has_next = next_item < n_items;
     HS_ADVANCE_PF()  // pf_item = the item after next
     uint4 nnd0 = nd0, nnd1 = nd1;
@@ -392,103 +408,116 @@ __global__ __launch_bounds__(256, 2) void hs_join6x_kernel(
       nnd0 = uniform4(desc[2 * (uint64_t)pf_item]);
       nnd1 = uniform4(desc[2 * (uint64_t)pf_item + 1]);
     }
-    // ---- A operands of the item's 128 members
-    intx6 A[RT];
+    auto run_item = [&](auto rt_tag) {
+      constexpr int RT = decltype(rt_tag)::value, PH = RT / 4;  // row tiles of 16 members; phases per query tile
+      // ---- the item's members (lanes of quarters 0..2: packed member 16 t + n; quarter 3: its record) and
+      // their A operands
+      intx6 A[RT];
+      {
+        uint4 mk_here[PREFETCH ? 1 : RT];
+        if (!PREFETCH) load_members(mk_here, RT, d0);
 #pragma unroll
-    for (int t = 0; t < RT; ++t) {
-      const uint4 m = mk[t];
-      const uint32_t a = q == 0 ? m.x : q == 1 ? m.y : m.z, b = q == 0 ? m.y : q == 1 ? m.z : m.w;
-      const uint32_t lo = __funnelshift_r(a, b, bs), hi = b >> bs;
-      const uint2 e0 = sPair[lo & 1023u], e1 = sPair[(lo >> 10) & 1023u];
-      const uint2 e2 = sPair[(lo >> 20) & 1023u], e3 = sPair[__funnelshift_r(lo, hi, 30) & 1023u];
-      const intx6 lk = intx6{(int)e0.x, (int)(e0.y | (e1.x << 16)), (int)__funnelshift_r(e1.x, e1.y, 16),
-                             (int)e2.x, (int)(e2.y | (e3.x << 16)), (int)__funnelshift_r(e3.x, e3.y, 16)};
-      const intx6 own = intx6{(int)m.x, (int)m.y, (int)m.z, (int)m.w, 0, 0};
-      A[t] = q == 3 ? own : lk;
-    }
-    HS_LOAD_MEMBERS(nd0)
-    floatx4 accX[4][2], accY[4][2];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) accY[t][c] = __builtin_nondeterministic_value(accY[t][c]);
-    bool y_live = false;
-    float Cy[2] = {0.0f, 0.0f};
-    uint32_t prev_qc = q_begin;
-    const uint32_t n_groups = HS_N_GROUPS(d1);
-    uint32_t qc0 = HS_FIRST_Q(d1);
-    auto do_group = [&](uint32_t gi) {
-      uint32_t nrow = qoff, nq0 = qc0 + GQ, nqend = q_end;
-      if (nq0 >= q_end) nq0 = q_begin;
-      if (gi + 1 == n_groups) {
-        nrow = nd1.x;
-        nq0 = HS_FIRST_Q(nd1);
-        nqend = nd1.z;
-      }
-#pragma unroll
-      for (int u = 0; u < NB; ++u) {
-        const uint32_t qc = qc0 + 32u * (uint32_t)u;
-        intx8 (&B)[2] = Bq[u];
-        if (u == 0 || qc < q_end) {
-          const floatx4 zero = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
-          const float Cx[2] = {__int_as_float(B[0][6]), __int_as_float(B[1][6])};
-          // ---- phase 1: X <- row tiles 0..3 x B, beside the test of Y (previous query tile, its C in Cy)
-          float wY[16];
-#pragma unroll
-          for (int g = 0; g < 8; ++g) {
-            const int t = g >> 1, c = g & 1;
-            accX[t][c] = tile_mfma6(A[t], B[c], zero);
-            if (y_live) {  // (the item's first tile: Y holds nothing yet)
-              sign_step6(2 * g, accY, wY);
-              sign_step6(2 * g + 1, accY, wY);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-          }
-          if (y_live) {
-            uint64_t pY[2];
-            group_pass6(wY, Cy, pY);
-            if (pY[0] | pY[1])
-              emit_survivors6(accY, 4, prev_qc, qoff, q_end, wbase, M, mstart, Cy, pY, lane, res_base, res_used,
-                              prov_count, prov_cap, prov);
-          }
-          y_live = true;
-          // ---- phase 2: Y <- row tiles 4..7 x B, beside the test of X
-          float wX[16];
-#pragma unroll
-          for (int g = 0; g < 8; ++g) {
-            const int t = g >> 1, c = g & 1;
-            accY[t][c] = tile_mfma6(A[4 + t], B[c], zero);
-            sign_step6(2 * g, accX, wX);
-            sign_step6(2 * g + 1, accX, wX);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-          uint64_t pX[2];
-          group_pass6(wX, Cx, pX);
-          if (pX[0] | pX[1])
-            emit_survivors6(accX, 0, qc, qoff, q_end, wbase, M, mstart, Cx, pX, lane, res_base, res_used, prov_count,
-                            prov_cap, prov);
-          prev_qc = qc;
-          // (the tile's registers are loaded anew below and Y is tested a phase later: its C moves out of them
-          // here, in so many words -- left to itself the compiler loads every tile elsewhere and copies it)
-          asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=&v"(Cy[0]), "=v"(Cy[1]) : "v"(Cx[0]), "v"(Cx[1]));
+        for (int t = 0; t < RT; ++t) {
+          const uint4 m = PREFETCH ? mk_next[t] : mk_here[t];
+          const uint32_t a = q == 0 ? m.x : q == 1 ? m.y : m.z, b = q == 0 ? m.y : q == 1 ? m.z : m.w;
+          const uint32_t lo = __funnelshift_r(a, b, bs), hi = b >> bs;
+          const uint2 e0 = sPair[lo & 1023u], e1 = sPair[(lo >> 10) & 1023u];
+          const uint2 e2 = sPair[(lo >> 20) & 1023u], e3 = sPair[__funnelshift_r(lo, hi, 30) & 1023u];
+          const intx6 lk = intx6{(int)e0.x, (int)(e0.y | (e1.x << 16)), (int)__funnelshift_r(e1.x, e1.y, 16),
+                                 (int)e2.x, (int)(e2.y | (e3.x << 16)), (int)__funnelshift_r(e3.x, e3.y, 16)};
+          const intx6 own = intx6{(int)m.x, (int)m.y, (int)m.z, (int)m.w, 0, 0};
+          A[t] = q == 3 ? own : lk;
         }
-        const uint32_t nb = nq0 + 32u * (uint32_t)u < nqend ? nq0 + 32u * (uint32_t)u : nq0;
-        load_btile6(B, c6t, nrow + nb, min(32u, nqend - nb), lane);
+        if (PREFETCH) load_members(mk_next, RT_MAX, nd0);
       }
-      qc0 = nq0;
-    };
-    do_group(0);
-    for (uint32_t gi = 1; gi < n_groups; ++gi) do_group(gi);
-    {  // the item's last Y group
-      float wY[16];
+      // Accumulators: TWO sets of 4 row tiles x 2 column tiles.  A tile is PH = RT / 4 phases; phase p of a group
+      // (counted over its tiles) writes set p & 1 from row tiles 4 ph .. 4 ph + 3 and tests the other set -- the
+      // phase before it -- in the gaps.  NB PH is even, so a group starts and ends with set 1 pending (written by a
+      // tile's last phase, tested in the next tile's first), whichever PH.  Three sets for RT = 12 would cost 32
+      // registers more than there are.
+      floatx4 acc[2][4][2];
 #pragma unroll
-      for (int g = 0; g < 16; ++g) sign_step6(g, accY, wY);
-      uint64_t pY[2];
-      group_pass6(wY, Cy, pY);
-      if (pY[0] | pY[1])
-        emit_survivors6(accY, 4, prev_qc, qoff, q_end, wbase, M, mstart, Cy, pY, lane, res_base, res_used, prov_count,
-                        prov_cap, prov);
-    }
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) acc[1][t][c] = __builtin_nondeterministic_value(acc[1][t][c]);
+      bool live = false;  // set 1 holds a tile's last phase (not so at the item's first tile)
+      float Cp[2] = {0.0f, 0.0f};
+      uint32_t prev_qc = q_begin;
+      const uint32_t n_groups = HS_N_GROUPS(d1);
+      uint32_t qc0 = HS_FIRST_Q(d1);
+      auto test_set = [&](const floatx4 (&set)[4][2], const float (&w)[16], int T0, uint32_t qct, const float (&Ct)[2]) {
+        uint64_t pp[2];
+        group_pass6(w, Ct, pp);
+        if (pp[0] | pp[1])
+          emit_survivors6(set, T0, qct, qoff, q_end, wbase, M, mstart, Ct, pp, lane, res_base, res_used, prov_count,
+                          prov_cap, prov);
+      };
+      auto do_group = [&](uint32_t gi) {
+        uint32_t nrow = qoff, nq0 = qc0 + GQ, nqend = q_end;
+        if (nq0 >= q_end) nq0 = q_begin;
+        if (gi + 1 == n_groups) {
+          nrow = nd1.x;
+          nq0 = HS_FIRST_Q(nd1);
+          nqend = nd1.z;
+        }
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+          const uint32_t qc = qc0 + 32u * (uint32_t)u;
+          intx8 (&B)[2] = Bq[u];
+          if (u == 0 || qc < q_end) {
+            const floatx4 zero = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
+            const float Cx[2] = {__int_as_float(B[0][6]), __int_as_float(B[1][6])};
+#pragma unroll
+            for (int ph = 0; ph < PH; ++ph) {
+              const int ws = (u * PH + ph) & 1, ts = ws ^ 1;
+              const bool test = ph > 0 || live;
+              float w[16];
+#pragma unroll
+              for (int g = 0; g < 8; ++g) {
+                acc[ws][g >> 1][g & 1] = tile_mfma6(A[4 * ph + (g >> 1)], B[g & 1], zero);
+                if (test) {
+                  sign_step6(2 * g, acc[ts], w);
+                  sign_step6(2 * g + 1, acc[ts], w);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+              }
+              if (test) {
+                if (ph == 0) test_set(acc[ts], w, 4 * (PH - 1), prev_qc, Cp);
+                else test_set(acc[ts], w, 4 * (ph - 1), qc, Cx);
+              }
+            }
+            live = true;
+            prev_qc = qc;
+            // (the tile's registers are loaded anew below and its last phase is tested a phase later: its C moves
+            // out of them here, in so many words -- left to itself the compiler loads every tile elsewhere and
+            // copies it)
+            asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3"
+                         : "=&v"(Cp[0]), "=v"(Cp[1])
+                         : "v"(Cx[0]), "v"(Cx[1]));
+          } else if (((u * PH - 1) & 1) == 0 && qc - 32u < q_end) {
+            // the group's first skipped tile (a segment's ragged last group) and the tile before it left SET 0
+            // pending: it moves to set 1, where the next phase expects it (at most once per item's walk)
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+              for (int c = 0; c < 2; ++c) acc[1][t][c] = acc[0][t][c];
+          }
+          const uint32_t nb = nq0 + 32u * (uint32_t)u < nqend ? nq0 + 32u * (uint32_t)u : nq0;
+          load_btile6(B, c6t, nrow + nb, min(32u, nqend - nb), lane);
+        }
+        qc0 = nq0;
+      };
+      do_group(0);
+      for (uint32_t gi = 1; gi < n_groups; ++gi) do_group(gi);
+      {  // the item's last pending phase
+        float w[16];
+#pragma unroll
+        for (int g = 0; g < 16; ++g) sign_step6(g, acc[1], w);
+        test_set(acc[1], w, 4 * (PH - 1), prev_qc, Cp);
+      }
+    };
+    if (RT_MAX > 8 && M - wbase > 128u) run_item(std::integral_constant<int, RT_MAX>{});
+    else run_item(std::integral_constant<int, 8>{});
     if (!has_next) break;
     item = next_item;
     next_item = pf_item;
@@ -499,12 +528,22 @@ __global__ __launch_bounds__(256, 2) void hs_join6x_kernel(
   }
 #undef HS_ADVANCE_PF
 #undef HS_TAKE_CHUNK
-#undef HS_LOAD_GROUP
 #undef HS_N_GROUPS
-#undef HS_LOAD_MEMBERS
 #undef HS_FIRST_Q
   close_reservation(prov, res_base, res_used, prov_cap, lane);
 }
+
+#define HS_JOIN6_PARAMS                                                                                          \
+  const uint4 *__restrict__ desc, uint32_t n_items, const uint4 *__restrict__ packed_base,                       \
+      const uint4 *__restrict__ rec_base, const char *__restrict__ c6t, const hs_j6_dev *__restrict__ T,         \
+      uint32_t *__restrict__ prov_count, uint32_t prov_cap, uint2 *__restrict__ prov,                            \
+      uint32_t *__restrict__ item_counter, uint32_t G, const uint32_t *__restrict__ n_items_dev, uint32_t xcd_run
+#define HS_JOIN6_ARGS \
+  desc, n_items, packed_base, rec_base, c6t, T, prov_count, prov_cap, prov, item_counter, G, n_items_dev, xcd_run
+__global__ __launch_bounds__(256, 2) void hs_join6x_kernel(HS_JOIN6_PARAMS) { join6_items<8, 3, true>(HS_JOIN6_ARGS); }
+__global__ __launch_bounds__(256, 2) void hs_join6w_kernel(HS_JOIN6_PARAMS) { join6_items<12, 2, false>(HS_JOIN6_ARGS); }
+#undef HS_JOIN6_PARAMS
+#undef HS_JOIN6_ARGS
 
 // ------------------------------------------------------------------------------------ self-test
 // Rows on the e2m3 grid, thresholds on the 2^-6 grid, through tile_mfma6 with the lane map the kernel relies on;
@@ -591,6 +630,7 @@ hipError_t hs_launch_jtables6(const double* d_coords, int alphabet, void* d_tab6
 size_t hs_join6_table_bytes() { return sizeof(hs_j6_dev); }
 size_t hs_join6_ok_offset() { return offsetof(hs_j6_dev, ok); }
 int hs_join6_row_bytes() { return HS_J6_ROW_BYTES; }
+uint32_t hs_join6_wide_item() { return HS_J6_WIDE_ITEM; }
 
 hipError_t hs_launch_gather_c6t(const void* d_c6, const uint32_t* d_sorted_ql, const uint32_t* d_seg_qoff,
                                 const uint32_t* d_seg_of, uint32_t nql, int L, void* d_out, hipStream_t s) {
@@ -619,11 +659,16 @@ hipError_t hs_launch_qprep6_codes(const uint8_t* d_qcodes, uint32_t nq, int k, d
 hipError_t hs_launch_join6x(const uint4* d_desc, uint32_t n_items, const uint4* d_packed_base,
                             const uint4* d_rec_base, const void* d_c6t, const void* d_tab6, uint32_t* d_prov_count,
                             uint32_t prov_cap, uint2* d_prov, uint32_t* d_item_counter, int n_blocks,
-                            const uint32_t* d_n_items, uint32_t G, uint32_t xcd_run, hipStream_t s) {
+                            const uint32_t* d_n_items, uint32_t G, uint32_t xcd_run, hipStream_t s, int wide_items) {
   if (!n_items) return hipSuccess;
-  hs_join6x_kernel<<<n_blocks, 256, 0, s>>>(d_desc, n_items, d_packed_base, d_rec_base, (const char*)d_c6t,
-                                            (const hs_j6_dev*)d_tab6, d_prov_count, prov_cap, d_prov, d_item_counter,
-                                            G, d_n_items, xcd_run);
+  if (wide_items)
+    hs_join6w_kernel<<<n_blocks, 256, 0, s>>>(d_desc, n_items, d_packed_base, d_rec_base, (const char*)d_c6t,
+                                              (const hs_j6_dev*)d_tab6, d_prov_count, prov_cap, d_prov, d_item_counter,
+                                              G, d_n_items, xcd_run);
+  else
+    hs_join6x_kernel<<<n_blocks, 256, 0, s>>>(d_desc, n_items, d_packed_base, d_rec_base, (const char*)d_c6t,
+                                              (const hs_j6_dev*)d_tab6, d_prov_count, prov_cap, d_prov, d_item_counter,
+                                              G, d_n_items, xcd_run);
   return hipGetLastError();
 }
 

@@ -207,6 +207,8 @@ __host__ __device__ inline int64_t hs_j6_query_c64(double sum_r, double s2_half,
 //                    column tile c at 16 lane + 1024 (2 c) and + 1024 (2 c + 1), with no address arithmetic
 //   ragged (nr < 32) piece-major, piece g of row j at 16 (g nr + j): the last tile of a segment, nr x 128 bytes
 #define HS_J6_ROW_BYTES 128
+// members per work item of hs_join6w_kernel (12 row tiles of 16; hs_join6x_kernel: 128, hs_join8_members_per_item)
+#define HS_J6_WIDE_ITEM 192u
 __host__ __device__ inline uint32_t hs_j6_tile_offset(uint32_t nr, uint32_t j, uint32_t g) {
   if (nr == 32u) return ((2u * (j >> 4) + (g >> 2)) << 10) + 16u * (16u * (g & 3u) + (j & 15u));
   return 16u * (g * nr + j);

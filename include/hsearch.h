@@ -100,6 +100,8 @@ typedef struct hs_profile {
   uint64_t join_f6_batches;    /* of join_i8_batches: those whose query-streaming kernel was the FP6 form
                                   (hs_join6x_kernel: queries that are k-mers, k = 21..25).  join_row_bytes stays
                                   128 for them: the depth of the GEMM, not the bytes of an FP6 row (96) */
+  uint64_t join_f6_wide_items; /* of join_items: those of 192 members, run by the FP6 form's 12-row-tile kernel
+                                  (hs_join6w_kernel, HS_OPT_JOIN_F6_FORM); 0 for a batch on hs_join6x_kernel */
   uint64_t append_rebuilds;    /* hs_index_append*: 1 if the last append fell back to the full build over the
                                   concatenated codes (a fingerprint shared by two HashKey strings), else 0 */
   uint64_t append_new_buckets; /* hs_index_append*: buckets the block created, summed over the tables */
@@ -218,6 +220,10 @@ typedef enum hs_option {
                                 262144 = 2^18; the index's size where it is smaller).  Shows in t_scan and rounds only */
   HS_OPT_PSSM_NULL_BINS = 27, /* hs_pssm_pvalue, hs_pssm_pvalue_threshold: bins of the score grid the null distribution
                                  is convolved on (64 .. 8192, default 4096): more bins, a tighter p_hi / p_lo */
+  HS_OPT_JOIN_F6_FORM = 28,  /* the FP6 join's kernel: 0: hs_join6x_kernel (work items of 128 members); 1:
+                                hs_join6w_kernel (items of 192 members: a query tile feeds 24 MFMAs, not 16); -1
+                                (default): automatic, which is 1 wherever HS_OPT_JOIN_F6 applies.  Never shows in
+                                a result */
   HS_OPT_JOIN_XCD_RUN = 16  /* hs_join8x_kernel's work items dealt in runs of this many chunks per XCD, each XCD's
                                 waves on their own runs (a run's items stream the same query tiles: one L2 fetches
                                 them instead of eight).  0: one counter for the chip; -1 (default): by the size
