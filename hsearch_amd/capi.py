@@ -41,7 +41,9 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_pssm_log_odds", "hs_pssm_background", "hs_pssm_pvalue", "hs_pssm_pvalue_dev",
            "hs_pssm_pvalue_threshold", "hs_pssm_pvalue_threshold_dev", "hs_pssm_null_tables", "hs_pssm_pvalue_host",
            "hs_pssm_threshold_host", "hs_pssm_weighted_counts", "hs_pssm_weighted_counts_dev",
-           "hs_pssm_refine_weighted", "hs_pssm_weight_hits", "hs_pssm_log_odds_weighted", "hs_pssm_weight_u"]
+           "hs_pssm_refine_weighted", "hs_pssm_weight_hits", "hs_pssm_log_odds_weighted", "hs_pssm_weight_u",
+           "hs_cluster_weighted_profile", "hs_cluster_weighted_profile_dev", "hs_cluster_pssm_cover",
+           "hs_cluster_pssm_cover_dev", "hs_cluster_weights_codes", "hs_cluster_cover_codes"]
 
 TOPK_MAX = 64        # HS_TOPK_MAX: the widest row of query_topk / self_knn / topk_merge
 NO_ID = 0xffffffff   # the id and table of an unused entry of such a row (its distance is +inf)
@@ -78,7 +80,8 @@ class _Profile(C.Structure):
                 ("pssm_mfma_steps", C.c_uint64), ("pssm_seq_rows", C.c_uint64), ("pssm_count_sites", C.c_uint64),
                 ("pssm_count_items", C.c_uint64), ("pssm_weight_sites", C.c_uint64),
                 ("pssm_weight_items", C.c_uint64), ("pssm_null_bins", C.c_uint64),
-                ("pssm_null_profiles", C.c_uint64), ("pssm_rank_sample", C.c_uint64),
+                ("pssm_null_profiles", C.c_uint64), ("summary_weight_rows", C.c_uint64),
+                ("summary_weight_items", C.c_uint64), ("pssm_rank_sample", C.c_uint64),
                 ("pssm_rank_retries", C.c_uint64), ("pssm_topk_sample", C.c_uint64),
                 ("pssm_topk_raised", C.c_uint64)]
 
@@ -388,6 +391,22 @@ def load(hooks=False):
                                                       C.c_uint32, C.c_void_p, C.c_double, C.c_void_p]
             lib.hs_pssm_weight_u.restype = C.c_uint64
             lib.hs_pssm_weight_u.argtypes = [C.c_uint32, C.c_uint32]
+        # clusters to profiles: weighted_profile (h, label, min_size, out_label, out_size, counts, wcounts, wsum,
+        # distinct, cap, n_out); pssm_cover (h, label, min_size, S, n_rows, min_score, argmin); the host rules (codes, n,
+        # k, alphabet, label, min_size, ...)
+        if hasattr(lib, "hs_cluster_weighted_profile"):
+            for fn in (lib.hs_cluster_weighted_profile, lib.hs_cluster_weighted_profile_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 6 + [C.c_uint64,
+                                                                                        C.POINTER(C.c_uint64)]
+            for fn in (lib.hs_cluster_pssm_cover, lib.hs_cluster_pssm_cover_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+            head = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]
+            lib.hs_cluster_weights_codes.restype = C.c_int
+            lib.hs_cluster_weights_codes.argtypes = head + [C.c_void_p] * 6 + [C.c_uint64, C.POINTER(C.c_uint64)]
+            lib.hs_cluster_cover_codes.restype = C.c_int
+            lib.hs_cluster_cover_codes.argtypes = head + [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         # PSSM p-values: (h, S, bg, t_lo, nm, hit_m, hit_score, n, p_hi, p_lo); (h, S, bg, t_lo, p, nm, t_p, p_hi, p_lo,
         # flag); the host forms: include/hsearch.h
         if hasattr(lib, "hs_pssm_pvalue"):
@@ -941,6 +960,56 @@ def pssm_count_hits(codes, alphabet, m, id, score, nm, id_start=None):
     if st:
         raise HsError(st, "hs_pssm_count_hits")
     return dict(counts=counts, used=used[:rows])
+
+
+def cluster_weights_codes(codes, alphabet, label, min_size=1, want_counts=False, cap=None):
+    """hs_cluster_weights_codes (host only, no GPU): the rule of Engine.cluster_weighted_profile for codes uint8 [n][k]
+    over `alphabet` residues and label uint32 [n] (NOISE or a value < n) -> dict(label, size, wcounts uint64
+    [rows][k][alphabet], wsum uint64 [rows], distinct uint32 [rows], counts uint32 [rows][k][alphabet] if asked).  Rows:
+    the clusters of at least min_size members in ascending label.  cap=None: as many rows as needed; a given cap that
+    is too small raises HsError(HS_ERR_CAPACITY) with the required size in .needed."""
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    label = np.ascontiguousarray(label, dtype=np.uint32)
+    assert codes.ndim == 2 and label.shape == (codes.shape[0],)
+    n, k = codes.shape
+    A = max(int(alphabet), 1)
+    room = n // max(1, int(min_size)) if cap is None else int(cap)
+    ol, osz = np.empty(room, dtype=np.uint32), np.empty(room, dtype=np.uint32)
+    wc = np.empty((room, k, A), dtype=np.uint64)
+    ws, di = np.empty(room, dtype=np.uint64), np.empty(room, dtype=np.uint32)
+    cnt = np.empty((room, k, A), dtype=np.uint32) if want_counts else None
+    n_out = C.c_uint64(0)
+    st = load().hs_cluster_weights_codes(_vp(codes), n, k, int(alphabet), _vp(label), int(min_size), _vp(ol), _vp(osz),
+                                         None if cnt is None else _vp(cnt), _vp(wc), _vp(ws), _vp(di), room,
+                                         C.byref(n_out))
+    if st != HS_OK:
+        e = HsError(st, "hs_cluster_weights_codes")
+        e.needed = int(n_out.value)
+        raise e
+    m = int(n_out.value)
+    res = dict(label=ol[:m], size=osz[:m], wcounts=wc[:m], wsum=ws[:m], distinct=di[:m])
+    if want_counts:
+        res["counts"] = cnt[:m]
+    return res
+
+
+def cluster_cover_codes(codes, alphabet, label, S, min_size=1):
+    """hs_cluster_cover_codes (host only, no GPU): the rule of Engine.cluster_pssm_cover for codes uint8 [n][k], label
+    uint32 [n] and profiles S [rows][k][alphabet], one per cluster of at least min_size members in ascending label ->
+    dict(min_score float64 [rows], argmin uint32 [rows])."""
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    label = np.ascontiguousarray(label, dtype=np.uint32)
+    S = np.ascontiguousarray(S, dtype=np.float64)
+    assert codes.ndim == 2 and label.shape == (codes.shape[0],)
+    n, k = codes.shape
+    rows = S.shape[0]
+    assert S.shape == (rows, k, int(alphabet)), S.shape
+    ms, am = np.empty(rows, dtype=np.float64), np.empty(rows, dtype=np.uint32)
+    st = load().hs_cluster_cover_codes(_vp(codes), n, k, int(alphabet), _vp(label), int(min_size), _vp(S), rows,
+                                       _vp(ms), _vp(am))
+    if st != HS_OK:
+        raise HsError(st, "hs_cluster_cover_codes")
+    return dict(min_score=ms, argmin=am)
 
 
 def pssm_weight_hits(codes, alphabet, m, id, score, nm, id_start=None):
@@ -2528,6 +2597,103 @@ class Engine:
         """hs_cluster_radii_dev (device pointers as ints)."""
         self._check(self._lib.hs_cluster_radii_dev(self._h, d_label_ptr, int(min_size), d_centers, int(n_rows),
                                                    d_max_d2, d_radius, d_medoid))
+
+    def cluster_weighted_profile(self, label, min_size=1, want_counts=False, cap=None):
+        """hs_cluster_weighted_profile: the rows of cluster_profile(label, min_size) with position-based sequence
+        weights (the rule of pssm_weighted_counts, the sites of a row being its members), reduced on the device:
+        dict(label, size, wcounts uint64 [rows][k][alphabet], wsum uint64 [rows] (every column of wcounts[row] sums to
+        it), distinct uint32 [rows], counts uint32 [rows][k][alphabet] if asked)."""
+        label = np.ascontiguousarray(label, dtype=np.uint32)
+        n = self._n()
+        assert label.shape == (n,)
+        A = self._alphabet()
+        cap = n // max(1, int(min_size)) if cap is None else int(cap)
+        ol, osz = np.empty(cap, dtype=np.uint32), np.empty(cap, dtype=np.uint32)
+        wc = np.empty((cap, self.k, A), dtype=np.uint64)
+        ws, di = np.empty(cap, dtype=np.uint64), np.empty(cap, dtype=np.uint32)
+        cnt = np.empty((cap, self.k, A), dtype=np.uint32) if want_counts else None
+        n_out = C.c_uint64(0)
+        st = self._lib.hs_cluster_weighted_profile(self._h, _vp(label), int(min_size), _vp(ol), _vp(osz),
+                                                   _vp(cnt) if want_counts else None, _vp(wc), _vp(ws), _vp(di), cap,
+                                                   C.byref(n_out))
+        if st == HS_ERR_CAPACITY:
+            e = HsError(st, self._lib.hs_last_error(self._h).decode())
+            e.needed = int(n_out.value)
+            raise e
+        self._check(st)
+        m = int(n_out.value)
+        res = dict(label=ol[:m], size=osz[:m], wcounts=wc[:m], wsum=ws[:m], distinct=di[:m])
+        if want_counts:
+            res["counts"] = cnt[:m]
+        return res
+
+    def cluster_weighted_profile_dev(self, d_label_ptr, min_size, d_out_label, d_out_size, d_counts, d_wcounts, d_wsum,
+                                     d_distinct, cap):
+        """hs_cluster_weighted_profile_dev (device pointers as ints; d_counts, d_wsum, d_distinct None or 0: not
+        wanted).  Returns the number of rows; raises HsError(HS_ERR_CAPACITY) with the required size in .needed when
+        cap is too small."""
+        n_out = C.c_uint64(0)
+        st = self._lib.hs_cluster_weighted_profile_dev(self._h, d_label_ptr, int(min_size), d_out_label, d_out_size,
+                                                       d_counts if d_counts else None, d_wcounts,
+                                                       d_wsum if d_wsum else None, d_distinct if d_distinct else None,
+                                                       cap, C.byref(n_out))
+        if st == HS_ERR_CAPACITY:
+            e = HsError(st, self._lib.hs_last_error(self._h).decode())
+            e.needed = int(n_out.value)
+            raise e
+        self._check(st)
+        return int(n_out.value)
+
+    def cluster_pssm_cover(self, label, S, min_size=1):
+        """hs_cluster_pssm_cover: per row of cluster_profile(label, min_size) and its profile S[row] ([rows][k][alphabet])
+        dict(min_score = the smallest pssm_scan score of the row's members under S[row], argmin = the member attaining
+        it, the smallest id among ties).  pssm_scan(S, min_score) returns every member of row r under profile r."""
+        label = np.ascontiguousarray(label, dtype=np.uint32)
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        rows = S.shape[0]
+        assert label.shape == (self._n(),) and S.shape == (rows, self.k, self._alphabet()), S.shape
+        ms, am = np.empty(rows, dtype=np.float64), np.empty(rows, dtype=np.uint32)
+        self._check(self._lib.hs_cluster_pssm_cover(self._h, _vp(label), int(min_size), _vp(S), rows, _vp(ms), _vp(am)))
+        return dict(min_score=ms, argmin=am)
+
+    def cluster_pssm_cover_dev(self, d_label_ptr, min_size, d_S, n_rows, d_min_score, d_argmin):
+        """hs_cluster_pssm_cover_dev (device pointers as ints)."""
+        self._check(self._lib.hs_cluster_pssm_cover_dev(self._h, d_label_ptr, int(min_size), d_S, int(n_rows),
+                                                        d_min_score, d_argmin))
+
+    def index_composition(self):
+        """The residue composition [alphabet] of the index as hs_pssm_refine takes it: the counts of one profile that
+        hits every k-mer (one scan), through hs_pssm_background."""
+        zero = np.zeros((1, self.k, self._alphabet()), dtype=np.float64)
+        return pssm_background(self.pssm_hit_counts(zero, np.zeros(1))["counts"][0])
+
+    def cluster_pssm(self, label, min_size=1, weights="sites", bg=None, pseudo=1.0, threshold="cover"):
+        """From clusters to profiles pssm_scan can be given, in one call: the rows of cluster_profile(label, min_size)
+        -> dict(label, size, counts, S float64 [rows][k][alphabet][, t [rows]][, wcounts, wsum, distinct]).
+        weights: "none": S = hs_pssm_log_odds(counts); "sites" / "columns": S = hs_pssm_log_odds_weighted(wcounts, wsum,
+        n_eff) of cluster_weighted_profile with n_eff = size / distinct / k.  bg [alphabet] (None: index_composition()),
+        pseudo: the log-odds'.  threshold: "cover": t = cluster_pssm_cover's min_score (every member of a row is a hit
+        of its profile at t); "rank": t = pssm_rank(S, rank = size); None: no t."""
+        assert weights in ("none", "sites", "columns") and threshold in ("cover", "rank", None)
+        if weights == "none":
+            res = self.cluster_profile(label, min_size, want_counts=True)
+            del res["centroid"]
+        else:
+            res = self.cluster_weighted_profile(label, min_size, want_counts=True)
+        bg = self.index_composition() if bg is None else np.ascontiguousarray(bg, dtype=np.float64)
+        if weights == "none":
+            res["S"] = pssm_log_odds_exact(res["counts"], bg, pseudo)
+        else:
+            n_eff = (res["size"].astype(np.float64) if weights == "sites"
+                     else res["distinct"].astype(np.float64) / np.float64(self.k))
+            res["S"] = pssm_log_odds_weighted(res["wcounts"], res["wsum"], n_eff, bg, pseudo)
+        rows = len(res["label"])
+        if threshold == "cover":
+            res["t"] = self.cluster_pssm_cover(label, res["S"], min_size)["min_score"]
+        elif threshold == "rank":
+            res["t"] = (self.pssm_rank(res["S"], res["size"].astype(np.uint64))["t"] if rows
+                        else np.empty(0, dtype=np.float64))
+        return res
 
 
 def clustering(k, K, L, W, a, b, codes, R, device=0, coords=None):

@@ -3364,8 +3364,10 @@ hs_status hs_density_tree_dev(hs_handle* h, double R, int sqrt_test, uint32_t mi
 // ---- hs_cluster_profile / hs_cluster_radii: clusters of a label array summarised (kernels and state: hs_summary.hip) ----
 // Steps 1-3: sizes and validation, rows, grouping.  d_label [n] (device).  HS_ERR_INVALID for a label that is neither
 // HS_NOISE nor < n, detected on the device and reported before anything else is written.
+// value_bits (hs_cluster_pssm_cover_dev; null: none): word 1 of sm_err, which the caller's own check kernel has
+// written on the stream, comes back in the same read-back.
 static hs_status summary_group(hs_handle* h, const uint32_t* d_label, uint32_t min_size, uint32_t* n_rows,
-                               uint32_t* n_kept) {
+                               uint32_t* n_kept, uint32_t* value_bits = nullptr) {
   const uint32_t n = (uint32_t)h->n;
   const size_t words = ((size_t)n + 1) * 4;
   HS_HIP(h, h->sm_size.reserve(words));
@@ -3384,6 +3386,8 @@ static hs_status summary_group(hs_handle* h, const uint32_t* d_label, uint32_t m
   HS_HIP(h, hipMemcpyAsync(&back[0], h->sm_err.p, 4, hipMemcpyDeviceToHost, h->stream));
   HS_HIP(h, hipMemcpyAsync(&back[1], h->sm_row_of.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, h->stream));
   HS_HIP(h, hipMemcpyAsync(&back[2], h->sm_off_of.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, h->stream));
+  if (value_bits)
+    HS_HIP(h, hipMemcpyAsync(value_bits, h->sm_err.as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, h->stream));
   HS_HIP(h, hipStreamSynchronize(h->stream));
   if (back[0]) return fail(h, HS_ERR_INVALID, "a label is neither HS_NOISE nor below the number of indexed k-mers");
   if (back[1] > n || back[2] > n) return fail(h, HS_ERR_HIP, "cluster summary: more rows or members than k-mers");
@@ -3514,6 +3518,150 @@ hs_status hs_cluster_radii(hs_handle* h, const uint32_t* label, uint32_t min_siz
     HS_HIP(h, hipMemcpyAsync(max_d2, h->sm_io_f64.p, n_rows * 8, hipMemcpyDeviceToHost, h->stream));
     HS_HIP(h, hipMemcpyAsync(radius, h->sm_io_f64b.p, n_rows * 8, hipMemcpyDeviceToHost, h->stream));
     HS_HIP(h, hipMemcpyAsync(medoid, h->sm_io_a.p, n_rows * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return HS_OK;
+}
+
+// ---- hs_cluster_weighted_profile / hs_cluster_pssm_cover: clusters to weighted, searchable profiles (kernels:
+// hs_cluster_pssm.hip; the grouping and its state are hs_cluster_profile's) ----
+hs_status hs_cluster_weighted_profile_dev(hs_handle* h, const uint32_t* d_label, uint32_t min_size,
+                                          uint32_t* d_out_label, uint32_t* d_out_size, uint32_t* d_counts,
+                                          uint64_t* d_wcounts, uint64_t* d_wsum, uint32_t* d_distinct, uint64_t cap,
+                                          uint64_t* n_out) {
+  if (!h || !n_out) return HS_ERR_INVALID;
+  *n_out = 0;
+  HS_CHECK(summary_check(h, d_label, min_size));
+  if (cap && (!d_out_label || !d_out_size || !d_wcounts)) return fail(h, HS_ERR_INVALID, "an output array is null");
+  memset(&h->prof, 0, sizeof(h->prof));
+  uint32_t n_rows = 0, n_kept = 0;
+  HS_CHECK(summary_group(h, d_label, min_size, &n_rows, &n_kept));
+  *n_out = n_rows;
+  if (n_rows > cap) return fail(h, HS_ERR_CAPACITY, "profile buffers too small; see *n_out");
+  const int k = (int)h->p.k;
+  const size_t cells = (size_t)k * h->alphabet;
+  // rows per batch: the u tables (8 bytes a cell) and, when nobody asked for them, the counts (4) of a batch share the
+  // 32 MB of scratch
+  uint32_t batch = h->knobs.summary_rows;
+  if (!batch) batch = (uint32_t)std::max<size_t>(1, ((size_t)32 << 20) / (cells * (d_counts ? 8 : 12)));
+  const size_t held = std::min<size_t>(batch, std::max<uint32_t>(n_rows, 1));
+  if (!d_counts) HS_HIP(h, h->sm_counts.reserve(held * cells * 4));
+  HS_HIP(h, h->pw_u.reserve(hs_pssm_weights_table_bytes((uint32_t)held, k, h->alphabet)));
+  HS_HIP(h, hs_launch_sm_head(h->sm_row_label.as<uint32_t>(), h->sm_row_off.as<uint32_t>(), n_rows, d_out_label,
+                              d_out_size, h->stream));
+  const uint32_t ch = summary_chunk(h);
+  const uint32_t* const row_off = h->sm_row_off.as<uint32_t>();
+  for (uint32_t r0 = 0; r0 < n_rows; r0 += batch) {
+    const uint32_t r1 = (uint32_t)std::min<uint64_t>(n_rows, (uint64_t)r0 + batch);
+    uint32_t* const cnt = d_counts ? d_counts + (size_t)r0 * cells : h->sm_counts.as<uint32_t>();
+    HS_HIP(h, hs_launch_sm_profile(h->codes.as<uint8_t>(), k, h->alphabet, d_label, h->sm_row_of.as<uint32_t>(), row_off,
+                                   h->sm_member.as<uint32_t>(), r0, r1, ch, n_kept, cnt, h->n_cu, h->stream));
+    HS_HIP(h, hs_launch_pssm_weights_table(cnt, r1 - r0, k, h->alphabet, h->pw_u.as<uint64_t>(),
+                                           d_distinct ? d_distinct + r0 : nullptr, h->stream));
+    HS_HIP(h, hs_launch_cp_weights(h->codes.as<uint8_t>(), k, h->alphabet, d_label, h->sm_row_of.as<uint32_t>(), row_off,
+                                   h->sm_member.as<uint32_t>(), r0, r1, ch, n_kept, h->pw_u.as<uint64_t>(),
+                                   d_wcounts + (size_t)r0 * cells, h->n_cu, h->stream));
+  }
+  HS_HIP(h, hs_launch_pssm_weights_sum(d_wcounts, n_rows, k, h->alphabet, d_wsum, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  h->prof.summary_weight_rows = n_rows;
+  if (n_rows) {  // the items of every batch: its member slots in chunks of ch (the rows' offsets are on the device)
+    const uint32_t nb = (n_rows + batch - 1) / batch;
+    if (nb == 1) {
+      h->prof.summary_weight_items = ((uint64_t)n_kept + ch - 1) / ch;
+    } else {
+      std::vector<uint32_t> edge((size_t)nb + 1, n_kept);
+      for (uint32_t b = 0; b < nb; ++b)
+        HS_HIP(h, hipMemcpyAsync(&edge[b], row_off + (size_t)b * batch, 4, hipMemcpyDeviceToHost, h->stream));
+      HS_HIP(h, hipStreamSynchronize(h->stream));
+      for (uint32_t b = 0; b < nb; ++b) h->prof.summary_weight_items += ((uint64_t)(edge[b + 1] - edge[b]) + ch - 1) / ch;
+    }
+  }
+  return HS_OK;
+}
+
+hs_status hs_cluster_pssm_cover_dev(hs_handle* h, const uint32_t* d_label, uint32_t min_size, const double* d_S,
+                                    uint64_t n_rows_given, double* d_min_score, uint32_t* d_argmin) {
+  if (!h) return HS_ERR_INVALID;
+  HS_CHECK(summary_check(h, d_label, min_size));
+  if (n_rows_given && (!d_S || !d_min_score || !d_argmin))
+    return fail(h, HS_ERR_INVALID, "the profiles or an output array is null");
+  if (n_rows_given > h->n / min_size)
+    return fail(h, HS_ERR_INVALID, "the labels do not give as many rows as there are profiles");
+  memset(&h->prof, 0, sizeof(h->prof));
+  const size_t cells = (size_t)h->p.k * h->alphabet;
+  // the value check of the profiles rides on the grouping's read-back: word 1 of sm_err
+  HS_HIP(h, h->sm_err.reserve(16));
+  HS_HIP(h, hipMemsetAsync(h->sm_err.as<uint32_t>() + 1, 0, 4, h->stream));
+  if (n_rows_given)
+    HS_HIP(h, hs_launch_pssm_check(d_S, n_rows_given * cells, nullptr, 0, h->sm_err.as<uint32_t>() + 1, h->stream));
+  uint32_t n_rows = 0, n_kept = 0, bad = 0;
+  HS_CHECK(summary_group(h, d_label, min_size, &n_rows, &n_kept, &bad));
+  if (n_rows != n_rows_given) return fail(h, HS_ERR_INVALID, "the labels do not give as many rows as there are profiles");
+  if (bad) return fail(h, HS_ERR_INVALID, "a profile entry is NaN, infinite or beyond 2^100");
+  HS_HIP(h, h->sm_d2.reserve(std::max<size_t>(16, (size_t)h->n * 8)));
+  HS_HIP(h, hs_launch_cp_cover(h->codes.as<uint8_t>(), (int)h->p.k, h->alphabet, d_S, d_label,
+                               h->sm_row_of.as<uint32_t>(), h->sm_row_off.as<uint32_t>(), h->sm_member.as<uint32_t>(),
+                               n_rows, n_kept, summary_chunk(h), h->sm_d2.as<uint64_t>(), d_min_score, d_argmin,
+                               h->n_cu, h->stream));
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return HS_OK;
+}
+
+hs_status hs_cluster_weighted_profile(hs_handle* h, const uint32_t* label, uint32_t min_size, uint32_t* out_label,
+                                      uint32_t* out_size, uint32_t* counts, uint64_t* wcounts, uint64_t* wsum,
+                                      uint32_t* distinct, uint64_t cap, uint64_t* n_out) {
+  if (!h || !n_out) return HS_ERR_INVALID;
+  *n_out = 0;
+  HS_CHECK(summary_check(h, label, min_size));
+  if (cap && (!out_label || !out_size || !wcounts)) return fail(h, HS_ERR_INVALID, "an output array is null");
+  HS_CHECK(summary_labels_in(h, label));
+  // the device arrays are sized by what the call can return: min(cap, n / min_size) rows; pw_out: wcounts, wsum, distinct
+  const uint64_t room = std::min<uint64_t>(cap, h->n / min_size);
+  const size_t cells = (size_t)h->p.k * h->alphabet;
+  HS_HIP(h, h->sm_io_a.reserve(std::max<size_t>(16, room * 4)));
+  HS_HIP(h, h->sm_io_b.reserve(std::max<size_t>(16, room * 4)));
+  HS_HIP(h, h->pw_out.reserve(std::max<size_t>(16, room * (cells * 8 + 16))));
+  if (counts) HS_HIP(h, h->sm_io_counts.reserve(std::max<size_t>(16, room * cells * 4)));
+  uint64_t* const d_wc = h->pw_out.as<uint64_t>();
+  uint64_t* const d_ws = d_wc + room * cells;
+  uint32_t* const d_di = reinterpret_cast<uint32_t*>(d_ws + room);
+  uint64_t rows = 0;
+  const hs_status st = hs_cluster_weighted_profile_dev(
+      h, h->sm_io_label.as<uint32_t>(), min_size, h->sm_io_a.as<uint32_t>(), h->sm_io_b.as<uint32_t>(),
+      counts ? h->sm_io_counts.as<uint32_t>() : nullptr, d_wc, d_ws, d_di, room, &rows);
+  *n_out = rows;
+  if (st == HS_ERR_CAPACITY && rows <= cap) return fail(h, HS_ERR_HIP, "cluster profile: more rows than n / min_size");
+  HS_CHECK(st);
+  if (rows) {
+    HS_HIP(h, hipMemcpyAsync(out_label, h->sm_io_a.p, rows * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(out_size, h->sm_io_b.p, rows * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(wcounts, d_wc, rows * cells * 8, hipMemcpyDeviceToHost, h->stream));
+    if (wsum) HS_HIP(h, hipMemcpyAsync(wsum, d_ws, rows * 8, hipMemcpyDeviceToHost, h->stream));
+    if (distinct) HS_HIP(h, hipMemcpyAsync(distinct, d_di, rows * 4, hipMemcpyDeviceToHost, h->stream));
+    if (counts) HS_HIP(h, hipMemcpyAsync(counts, h->sm_io_counts.p, rows * cells * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return HS_OK;
+}
+
+hs_status hs_cluster_pssm_cover(hs_handle* h, const uint32_t* label, uint32_t min_size, const double* S, uint64_t n_rows,
+                                double* min_score, uint32_t* argmin) {
+  if (!h) return HS_ERR_INVALID;
+  HS_CHECK(summary_check(h, label, min_size));
+  if (n_rows && (!S || !min_score || !argmin)) return fail(h, HS_ERR_INVALID, "the profiles or an output array is null");
+  if (n_rows > h->n / min_size) return fail(h, HS_ERR_INVALID, "the labels do not give as many rows as there are profiles");
+  HS_CHECK(summary_labels_in(h, label));
+  const size_t cells = (size_t)h->p.k * h->alphabet;
+  HS_HIP(h, h->io_centers.reserve(std::max<size_t>(16, n_rows * cells * 8)));
+  HS_HIP(h, h->sm_io_f64.reserve(std::max<size_t>(16, n_rows * 8)));
+  HS_HIP(h, h->sm_io_a.reserve(std::max<size_t>(16, n_rows * 4)));
+  if (n_rows) HS_HIP(h, hipMemcpyAsync(h->io_centers.p, S, n_rows * cells * 8, hipMemcpyHostToDevice, h->stream));
+  HS_CHECK(hs_cluster_pssm_cover_dev(h, h->sm_io_label.as<uint32_t>(), min_size, h->io_centers.as<double>(), n_rows,
+                                     h->sm_io_f64.as<double>(), h->sm_io_a.as<uint32_t>()));
+  if (n_rows) {
+    HS_HIP(h, hipMemcpyAsync(min_score, h->sm_io_f64.p, n_rows * 8, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(argmin, h->sm_io_a.p, n_rows * 4, hipMemcpyDeviceToHost, h->stream));
     HS_HIP(h, hipStreamSynchronize(h->stream));
   }
   return HS_OK;

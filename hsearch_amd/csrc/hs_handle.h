@@ -289,7 +289,10 @@ struct hs_handle {
   uint64_t sq_rows = 0;
   uint32_t sq_batches = 0;
   // hs_cluster_profile / hs_cluster_radii (hs_summary.hip: the state listed at its head), the counts of a row batch
-  // when the caller wants none, and the arrays of a host-pointer call on their way in and out
+  // when the caller wants none, and the arrays of a host-pointer call on their way in and out.  hs_cluster_weighted_profile
+  // / hs_cluster_pssm_cover (hs_cluster_pssm.hip) run on the same state: a row batch's u tables go to pw_u, the members'
+  // score keys to sm_d2, the profiles' value check to word 1 of sm_err; a host-pointer call's wcounts, wsum and distinct
+  // leave through pw_out, its profiles come in through io_centers, min_score / argmin leave through sm_io_f64 / sm_io_a
   DevBuf sm_size, sm_tmp, sm_row_of, sm_off_of, sm_row_label, sm_row_off, sm_member, sm_d2, sm_err, sm_counts;
   // host-pointer calls: the labels in; out, hs_cluster_profile: sm_io_a = out_label, sm_io_b = out_size, sm_io_counts,
   // sm_io_f64 = centroid; hs_cluster_radii (centres in through io_centers, as the searches' are): sm_io_f64 = max_d2,

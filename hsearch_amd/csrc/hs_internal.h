@@ -594,6 +594,34 @@ hipError_t hs_launch_dt_finish(const uint32_t* d_comp, const uint64_t* d_core, u
 // group: sizes, validation (*d_err |= 1: a label that is neither HS_NOISE nor < n) and the two scans -- the caller
 // reads d_err[0], d_row_of[n] (rows) and d_off_of[n] (kept members) back before it goes on; members: the rows' labels
 // and offsets and the ids grouped by row; head: out_label / out_size of the rows.
+//
+// What the item kernels of hs_summary.hip and hs_cluster_pssm.hip share.  Work items are ch consecutive member SLOTS;
+// the pieces of rows inside an item (segments) are dealt to the workgroup's HS_SM_WAVES waves in rounds, and an item
+// that lies inside one row is shared by the waves instead.  hs_sm_segment: the segment wave `wave` takes in round
+// `round` of the item [p0, p1) whose first row is rf and which holds nseg rows.
+#define HS_SM_WAVES 4u
+struct hs_sm_seg {
+  bool active, whole;  // whole: the segment is its whole row (plain stores); else it is added with atomics
+  uint32_t row, lo, hi;
+};
+__device__ __forceinline__ hs_sm_seg hs_sm_segment(const uint32_t* __restrict__ row_off, uint32_t rf, uint32_t nseg,
+                                                   uint32_t round, uint32_t wave, uint32_t p0, uint32_t p1) {
+  hs_sm_seg s;
+  const uint32_t t = nseg == 1 ? 0u : round * HS_SM_WAVES + wave;
+  s.active = t < nseg;
+  s.row = rf + (s.active ? t : 0u);
+  const uint32_t ro = row_off[s.row], rn = row_off[s.row + 1];
+  s.lo = ro > p0 ? ro : p0;
+  s.hi = rn < p1 ? rn : p1;
+  s.whole = ro >= p0 && rn <= p1;
+  return s;
+}
+// lanes per member of the histogram kernels: the power of two >= k, at most 64, as a shift
+inline uint32_t hs_sm_lpm_shift(int k) {
+  uint32_t s = 0;
+  while (s < 6 && (1 << s) < k) ++s;
+  return s;
+}
 hipError_t hs_launch_sm_group(const uint32_t* d_label, uint32_t n, uint32_t min_size, uint32_t* d_size, uint32_t* d_tmp,
                               uint32_t* d_row_of, uint32_t* d_off_of, void* d_temp, size_t temp_bytes, uint32_t* d_err,
                               hipStream_t s);
@@ -617,6 +645,19 @@ hipError_t hs_launch_sm_radii(const uint8_t* d_codes, int k, int alphabet, const
                               const uint32_t* d_member, uint32_t n_rows, uint32_t n_kept, uint32_t ch,
                               const double* d_centers, uint64_t* d_d2, double* d_max_d2, double* d_radius,
                               uint32_t* d_medoid, int n_cu, hipStream_t s);
+// weighted cluster profiles and covering thresholds (hs_cluster_pssm.hip; the passes are written at its head), on the
+// state hs_launch_sm_group / _members left.  weights: the batch of rows [r0, r1) whose raw counts are final and whose
+// tables d_u [(r1 - r0)][k][alphabet] hs_launch_pssm_weights_table has built -> d_wcounts [(r1 - r0)][k][alphabet]
+// (row r0 first).  cover: d_S [n_rows][k][alphabet] -> d_min_score, d_argmin [n_rows]; d_key [n_kept] u64 is scratch
+// (the members' score keys), d_min_score holds the rows' minimal keys on the way.
+hipError_t hs_launch_cp_weights(const uint8_t* d_codes, int k, int alphabet, const uint32_t* d_label,
+                                const uint32_t* d_row_of, const uint32_t* d_row_off, const uint32_t* d_member,
+                                uint32_t r0, uint32_t r1, uint32_t ch, uint32_t n_kept, const uint64_t* d_u,
+                                uint64_t* d_wcounts, int n_cu, hipStream_t s);
+hipError_t hs_launch_cp_cover(const uint8_t* d_codes, int k, int alphabet, const double* d_S, const uint32_t* d_label,
+                              const uint32_t* d_row_of, const uint32_t* d_row_off, const uint32_t* d_member,
+                              uint32_t n_rows, uint32_t n_kept, uint32_t ch, uint64_t* d_key, double* d_min_score,
+                              uint32_t* d_argmin, int n_cu, hipStream_t s);
 // brute force
 hipError_t hs_launch_bruteforce(const uint4* d_packed_all, uint32_t n, const float* d_tq,
                                 uint32_t nq, int k, float r2_hi, uint32_t* d_prov_count,

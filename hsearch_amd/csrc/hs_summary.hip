@@ -19,7 +19,8 @@
 // row of 10^6 members is 10^6 / CH items, and an item over small rows holds many of them.  The pieces of rows inside
 // an item (segments) are dealt to the workgroup's four waves, each with a histogram (a staged centre) of its own in
 // LDS; an item that lies inside one row is shared by the four waves instead.  A segment that is its whole row is
-// flushed with plain stores, any other with one global atomic per non-zero cell.
+// flushed with plain stores, any other with one global atomic per non-zero cell.  The decoding of an item's segments
+// (hs_sm_segment) lives in hs_internal.h: hs_cluster_pssm.hip walks the same items over the same state.
 //
 // All stores are vector stores; no inline assembly.
 #include <math.h>
@@ -35,7 +36,7 @@
 
 namespace {
 
-constexpr uint32_t SM_WAVES = 4;  // waves per workgroup of the item kernels
+constexpr uint32_t SM_WAVES = HS_SM_WAVES;  // waves per workgroup of the item kernels
 
 inline unsigned sm_blocks(uint64_t n) { return (unsigned)((n + 255u) / 256u); }
 
@@ -118,25 +119,6 @@ __global__ __launch_bounds__(256) void hs_sm_head_kernel(const uint32_t* __restr
   out_size[r] = row_off[r + 1] - row_off[r];
 }
 
-// The segment wave `wave` takes in round `round` of the item [p0, p1) whose first row is rf and which holds nseg
-// rows (nseg == 1: the four waves share it).
-struct SmSeg {
-  bool active, whole;
-  uint32_t row, lo, hi;
-};
-__device__ __forceinline__ SmSeg sm_segment(const uint32_t* __restrict__ row_off, uint32_t rf, uint32_t nseg,
-                                            uint32_t round, uint32_t wave, uint32_t p0, uint32_t p1) {
-  SmSeg s;
-  const uint32_t t = nseg == 1 ? 0u : round * SM_WAVES + wave;
-  s.active = t < nseg;
-  s.row = rf + (s.active ? t : 0u);
-  const uint32_t ro = row_off[s.row], rn = row_off[s.row + 1];
-  s.lo = ro > p0 ? ro : p0;
-  s.hi = rn < p1 ? rn : p1;
-  s.whole = ro >= p0 && rn <= p1;
-  return s;
-}
-
 // rows of the batch [r0, r1) that more than one item touches are summed with atomics: they start from zero
 __global__ __launch_bounds__(256) void hs_sm_zero_split_kernel(const uint32_t* __restrict__ row_off, uint32_t r0,
                                                                uint32_t r1, uint32_t ch, uint32_t cells,
@@ -173,7 +155,7 @@ __global__ __launch_bounds__(256) void hs_sm_profile_kernel(const uint8_t* __res
     const bool shared = nseg == 1u;
     const uint32_t rounds = shared ? 1u : (nseg + SM_WAVES - 1u) / SM_WAVES;
     for (uint32_t round = 0; round < rounds; ++round) {
-      const SmSeg s = sm_segment(row_off, rf, nseg, round, wave, p0, p1);
+      const hs_sm_seg s = hs_sm_segment(row_off, rf, nseg, round, wave, p0, p1);
       for (uint32_t c = lane; c < cells; c += 64u) mine[c] = 0u;
       __syncthreads();
       if (s.active) {
@@ -273,7 +255,7 @@ __global__ __launch_bounds__(256) void hs_sm_radii_kernel(const uint8_t* __restr
     const bool shared = nseg == 1u;
     const uint32_t rounds = shared ? 1u : (nseg + SM_WAVES - 1u) / SM_WAVES;
     for (uint32_t round = 0; round < rounds; ++round) {
-      const SmSeg s = sm_segment(row_off, rf, nseg, round, wave, p0, p1);
+      const hs_sm_seg s = hs_sm_segment(row_off, rf, nseg, round, wave, p0, p1);
       if (s.active)
         for (uint32_t t = lane; t < d; t += 64u) centre[t] = centers[(size_t)s.row * d + t];
       __syncthreads();
@@ -344,12 +326,6 @@ __global__ __launch_bounds__(256) void hs_sm_radius_kernel(const double* __restr
   if (r < n_rows) radius[r] = sm_radius_covering(max_d2[r]);
 }
 
-uint32_t sm_lpm_shift(int k) {
-  uint32_t s = 0;
-  while (s < 6 && (1 << s) < k) ++s;
-  return s;
-}
-
 }  // namespace
 
 hipError_t hs_launch_sm_group(const uint32_t* d_label, uint32_t n, uint32_t min_size, uint32_t* d_size, uint32_t* d_tmp,
@@ -393,7 +369,7 @@ hipError_t hs_launch_sm_profile(const uint8_t* d_codes, int k, int alphabet, con
   const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(items, (uint64_t)n_cu * 8));
   hs_sm_profile_kernel<<<grid, 256, (size_t)SM_WAVES * cells * 4, s>>>(d_codes, (uint32_t)k, (uint32_t)alphabet, d_label,
                                                                       d_row_of, d_row_off, d_member, r0, r1, ch,
-                                                                      sm_lpm_shift(k), d_counts);
+                                                                      hs_sm_lpm_shift(k), d_counts);
   return hipGetLastError();
 }
 

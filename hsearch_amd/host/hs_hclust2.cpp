@@ -19,6 +19,12 @@
 // -knn N (-n; 1..64, with -linkage single, dbscan or density) writes beside the clusters file the k-nearest-neighbour
 // graph within the threshold as <o>hclust.knn.txt (hsearch::KnnGraph): one line per k-mer -- its name, its degree, then
 // its at most N nearest neighbours as name / distance pairs.
+// -pssm 1 (-P; wherever -centers 1 works) writes beside the clusters file the profiles of the clusters of at least
+// -minsize m members as <o>hclust.pssm.txt (hsearch::ClusterProfiles): the --pssm input of hs_motif_both_points, which
+// then reports every member of every cluster under its cluster's name.  -pssm-weights none|sites|columns (-w, default
+// sites): raw counts, or position-based sequence weights scaled to the members / to the distinct residues per column;
+// -pssm-threshold cover|rank (-H, default cover): the covering threshold, or the score of the size-th best k-mer;
+// -pssm-pseudo x (-u, default 1): pseudo-counts of the log-odds.
 #include <stdio.h>
 #include <stdlib.h>
 #include <time.h>
@@ -54,7 +60,14 @@ const Opt kOpts[] = {
     {"minpts", 'p', "dbscan: neighbours within the threshold, the k-mer itself counted, that make a k-mer dense", false},
     {"centers", 'C', "1: also write <output>hclust.format.txt (centroids) and <output>hclust.radii.txt (covering radii) "
                      "of the clusters; with -linkage single or dbscan [0]", false},
-    {"minsize", 'm', "centers: members a cluster needs to get a centre [50]", false},
+    {"minsize", 'm', "centers, pssm: members a cluster needs to get a centre or a profile [50]", false},
+    {"pssm", 'P', "1: also write <output>hclust.pssm.txt, the clusters' profiles with thresholds (the --pssm input of "
+                  "hs_motif_both_points); with -linkage single, dbscan or density [0]", false},
+    {"pssm-weights", 'w', "pssm: none (raw counts) | sites | columns (position-based sequence weights, scaled to the "
+                          "members | to the distinct residues per column) [sites]", false},
+    {"pssm-threshold", 'H', "pssm: cover (every member of a cluster is a hit of its profile) | rank (the score of the "
+                            "profile's size-th best k-mer) [cover]", false},
+    {"pssm-pseudo", 'u', "pssm: pseudo-counts of the log-odds, > 0 [1]", false},
     {"tree", 't', "1: also write <output>hclust.tree.txt, the single-linkage tree up to the threshold, one line per "
                   "merge in merge order: two k-mer names and the distance; with -linkage single [0]", false},
     {"knn", 'n', "N (1..64): also write <output>hclust.knn.txt, per k-mer its name, its number of neighbours within the "
@@ -149,20 +162,58 @@ int main(int argc, const char* argv[]) {
     fprintf(stderr, "ERROR: -centers goes with -linkage single or dbscan, not with the greedy leader clusters\n");
     return EXIT_FAILURE;
   }
-  if (val.count("minsize") && !centers) {
+  if (val.count("pssm") && val["pssm"] != "0" && val["pssm"] != "1") {
+    fprintf(stderr, "ERROR: -pssm takes 0 or 1, not '%s'\n", val["pssm"].c_str());
+    return EXIT_FAILURE;
+  }
+  const bool pssm = val.count("pssm") && val["pssm"] == "1";
+  if (pssm && linkage == "greedy") {
+    fprintf(stderr, "ERROR: -pssm goes with -linkage single, dbscan or density, not with the greedy leader clusters\n");
+    return EXIT_FAILURE;
+  }
+  for (const char* name : {"pssm-weights", "pssm-threshold", "pssm-pseudo"})
+    if (val.count(name) && !pssm) {
+      fprintf(stderr, "ERROR: -%s goes with -pssm 1 only\n", name);
+      return EXIT_FAILURE;
+    }
+  if (val.count("minsize") && !centers && !pssm) {
     fprintf(stderr, "ERROR: -minsize goes with -centers 1 only\n");
     return EXIT_FAILURE;
   }
-  if (centers) {
-    centers_min_size = 50;  // MIN_SIZE_CLUSTER, centerDistanceSmapling.cpp:12
-    if (val.count("minsize")) {
+  uint32_t min_size = 50;  // MIN_SIZE_CLUSTER, centerDistanceSmapling.cpp:12
+  if (val.count("minsize")) {
+    char* end = nullptr;
+    const unsigned long long m = strtoull(val["minsize"].c_str(), &end, 10);
+    if (end == val["minsize"].c_str() || *end || m < 1 || m > 0xffffffffull || val["minsize"][0] == '-') {
+      fprintf(stderr, "ERROR: -minsize must be a whole number of at least 1, not '%s'\n", val["minsize"].c_str());
+      return EXIT_FAILURE;
+    }
+    min_size = (uint32_t)m;
+  }
+  if (centers) centers_min_size = min_size;
+  hsearch::ClusterProfileOptions profiles;  // min_size 0: no profiles
+  if (pssm) {
+    profiles.min_size = min_size;
+    const std::string w = val.count("pssm-weights") ? val["pssm-weights"] : "sites";
+    const std::string th = val.count("pssm-threshold") ? val["pssm-threshold"] : "cover";
+    if (w != "none" && w != "sites" && w != "columns") {
+      fprintf(stderr, "ERROR: -pssm-weights must be none, sites or columns, not '%s'\n", w.c_str());
+      return EXIT_FAILURE;
+    }
+    if (th != "cover" && th != "rank") {
+      fprintf(stderr, "ERROR: -pssm-threshold must be cover or rank, not '%s'\n", th.c_str());
+      return EXIT_FAILURE;
+    }
+    profiles.weights = w == "none" ? 0 : w == "sites" ? 1 : 2;
+    profiles.threshold = th == "cover" ? 0 : 1;
+    if (val.count("pssm-pseudo")) {
       char* end = nullptr;
-      const unsigned long long m = strtoull(val["minsize"].c_str(), &end, 10);
-      if (end == val["minsize"].c_str() || *end || m < 1 || m > 0xffffffffull || val["minsize"][0] == '-') {
-        fprintf(stderr, "ERROR: -minsize must be a whole number of at least 1, not '%s'\n", val["minsize"].c_str());
+      profiles.pseudo = strtod(val["pssm-pseudo"].c_str(), &end);
+      if (end == val["pssm-pseudo"].c_str() || *end || !(profiles.pseudo > 0.0) ||
+          !(profiles.pseudo <= 1.7976931348623157e308)) {
+        fprintf(stderr, "ERROR: -pssm-pseudo takes a finite number above 0\n");
         return EXIT_FAILURE;
       }
-      centers_min_size = (uint32_t)m;
     }
   }
   if (val.count("tree") && val["tree"] != "0" && val["tree"] != "1") {
@@ -210,16 +261,17 @@ int main(int argc, const char* argv[]) {
     uint64_t n_clusters = 0;
     const int st = density
                        ? hsearch::DensityTree(kmers, hash_K, hash_L, hash_W, hash_R, min_pts, val["output"], planes,
-                                              device, &err, tree, &n_clusters, nullptr, seed, centers_min_size)
+                                              device, &err, tree, &n_clusters, nullptr, seed, centers_min_size,
+                                              &profiles)
                    : linkage == "dbscan"
                        ? hsearch::Dbscan(kmers, hash_K, hash_L, hash_W, hash_R, min_pts, val["output"], planes, device,
-                                         &err, &n_clusters, seed, centers_min_size)
+                                         &err, &n_clusters, seed, centers_min_size, &profiles)
                    : tree
                        ? hsearch::SingleLinkageTree(kmers, hash_K, hash_L, hash_W, hash_R, val["output"], planes, device,
-                                                    &err, &n_clusters, nullptr, seed, centers_min_size)
+                                                    &err, &n_clusters, nullptr, seed, centers_min_size, &profiles)
                    : linkage == "single"
                        ? hsearch::Components(kmers, hash_K, hash_L, hash_W, hash_R, val["output"], planes, device, &err,
-                                             &n_clusters, seed, centers_min_size)
+                                             &n_clusters, seed, centers_min_size, &profiles)
                        : hsearch::Clustering(kmers, hash_K, hash_L, hash_W, hash_R, val["output"], planes, device, seed,
                                              &err, &n_clusters);
     if (st != 0) {

@@ -1556,12 +1556,111 @@ int ClusterCenters(hs_handle* h, const std::vector<Kmer>& kmers, const std::vect
   return HS_OK;
 }
 
+int ClusterProfiles(hs_handle* h, const std::vector<Kmer>& kmers, const std::vector<uint32_t>& label,
+                    const ClusterProfileOptions& opt, const std::string& output_file, std::string* err,
+                    uint64_t* n_profiles) {
+  hs_params prm;
+  if (!h || hs_get_params(h, &prm) != HS_OK || label.size() != kmers.size()) {
+    if (err) *err = "ClusterProfiles: no handle, or not one label per k-mer";
+    return HS_ERR_INVALID;
+  }
+  const bool pseudo_ok = opt.pseudo > 0.0 && opt.pseudo <= 1.7976931348623157e308;
+  if (!opt.min_size || opt.weights < 0 || opt.weights > 2 || opt.threshold < 0 || opt.threshold > 1 || !pseudo_ok) {
+    if (err) *err = "ClusterProfiles: min_size must be at least 1, weights 0 .. 2, threshold 0 or 1, pseudo finite and > 0";
+    return HS_ERR_INVALID;
+  }
+  const uint32_t k = prm.k, A = HS_ALPHABET;
+  const size_t cells = (size_t)k * A, n = label.size();
+  const uint64_t room = n / opt.min_size;
+  uint64_t rows = 0;
+  std::vector<uint32_t> row_label(room), row_size(room), counts(room * cells), distinct(room);
+  std::vector<uint64_t> wcounts, wsum;
+  hs_status st;
+  const char* what = "hs_cluster_weighted_profile";
+  if (opt.weights) {
+    wcounts.resize(room * cells);
+    wsum.resize(room);
+    st = hs_cluster_weighted_profile(h, label.data(), opt.min_size, row_label.data(), row_size.data(), counts.data(),
+                                     wcounts.data(), wsum.data(), distinct.data(), room, &rows);
+  } else {
+    what = "hs_cluster_profile";
+    std::vector<double> centroid(room * 8 * k);
+    st = hs_cluster_profile(h, label.data(), opt.min_size, row_label.data(), row_size.data(), counts.data(),
+                            centroid.data(), room, &rows);
+  }
+  std::vector<double> S(rows * cells), t(rows);
+  double bg[HS_ALPHABET];
+  if (st == HS_OK && rows) {
+    // the background: the residue composition of all n input k-mers -- the counts of one cluster that holds them all
+    what = "hs_cluster_profile (composition)";
+    const std::vector<uint32_t> everything(n, 0u);
+    std::vector<uint32_t> all_counts(cells), one(2);
+    std::vector<double> centroid(8 * k);
+    uint64_t one_row = 0;
+    st = hs_cluster_profile(h, everything.data(), 1, &one[0], &one[1], all_counts.data(), centroid.data(), 1, &one_row);
+    if (st == HS_OK && hs_pssm_background(all_counts.data(), k, A, bg) != HS_OK) {
+      if (err) *err = "ClusterProfiles: no background";
+      return HS_ERR_INVALID;
+    }
+  }
+  if (st == HS_OK && rows) {
+    if (opt.weights) {
+      std::vector<double> n_eff(rows);
+      for (uint64_t r = 0; r < rows; ++r)
+        n_eff[r] = opt.weights == 1 ? (double)row_size[r] : (double)distinct[r] / (double)k;
+      if (hs_pssm_log_odds_weighted(wcounts.data(), wsum.data(), n_eff.data(), rows, k, A, bg, opt.pseudo, S.data()) != HS_OK) {
+        if (err) *err = "hs_pssm_log_odds_weighted refused the weighted counts";
+        return HS_ERR_INVALID;
+      }
+    } else if (hs_pssm_log_odds(counts.data(), rows, k, A, bg, opt.pseudo, S.data()) != HS_OK) {
+      if (err) *err = "hs_pssm_log_odds refused the counts";
+      return HS_ERR_INVALID;
+    }
+    if (opt.threshold == 0) {
+      what = "hs_cluster_pssm_cover";
+      std::vector<uint32_t> argmin(rows);
+      st = hs_cluster_pssm_cover(h, label.data(), opt.min_size, S.data(), rows, t.data(), argmin.data());
+    } else {
+      what = "hs_pssm_rank";
+      std::vector<uint64_t> rank(rows), ge(rows), gt(rows);
+      for (uint64_t r = 0; r < rows; ++r) rank[r] = row_size[r];
+      st = hs_pssm_rank(h, S.data(), rank.data(), rows, t.data(), ge.data(), gt.data(), nullptr, nullptr);
+    }
+  }
+  if (st != HS_OK) {
+    if (err) *err = std::string(what) + ": " + hs_last_error(h);
+    return st;
+  }
+  std::vector<std::string> names(rows);
+  for (uint64_t r = 0; r < rows; ++r) names[r] = kmers[row_label[r]].name + ":size" + std::to_string(row_size[r]);
+  std::string werr;
+  if (!WritePssmFile(output_file + "hclust.pssm.txt", k, names, S, t, &werr)) {
+    if (err) *err = werr;
+    return HS_ERR_IO;
+  }
+  if (n_profiles) *n_profiles = rows;
+  return HS_OK;
+}
+
+// what the clustering functions write beside the clusters file: the centres, the profiles
+static int ClusterExtras(hs_handle* h, const std::vector<Kmer>& kmers, const std::vector<uint32_t>& label,
+                         uint32_t centers_min_size, const ClusterProfileOptions* profiles,
+                         const std::string& output_file, std::string* err) {
+  if (centers_min_size) {
+    const int cc = ClusterCenters(h, kmers, label, centers_min_size, output_file, err);
+    if (cc != HS_OK) return cc;
+  }
+  if (profiles && profiles->min_size) return ClusterProfiles(h, kmers, label, *profiles, output_file, err);
+  return HS_OK;
+}
+
 // Components and SingleLinkageTree: the same clusters file; tree: the labels come from hs_msf, whose tree edges go to
 // <output_file>hclust.tree.txt
 static int ComponentsOrTree(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L,
                             const double& hash_W, const double& hash_R, const std::string& output_file,
                             const Planes& planes, int device, std::string* err, uint64_t* n_clusters,
-                            uint32_t unknown_seed, uint32_t centers_min_size, bool tree, uint64_t* n_tree_edges) {
+                            uint32_t unknown_seed, uint32_t centers_min_size, bool tree, uint64_t* n_tree_edges,
+                            const ClusterProfileOptions* profiles) {
   std::vector<uint8_t> codes;
   const int cs = ClusterCodes(kmers, hash_K, hash_L, hash_W, planes, unknown_seed, &codes, err);
   if (cs != HS_OK) return cs;
@@ -1605,12 +1704,10 @@ static int ComponentsOrTree(const std::vector<Kmer>& kmers, const uint32_t& hash
     if (h) hs_destroy(h);
     return st;
   }
-  if (centers_min_size) {
-    const int cc = ClusterCenters(h, kmers, label, centers_min_size, output_file, err);
-    if (cc != HS_OK) {
-      hs_destroy(h);
-      return cc;
-    }
+  const int extras = ClusterExtras(h, kmers, label, centers_min_size, profiles, output_file, err);
+  if (extras != HS_OK) {
+    hs_destroy(h);
+    return extras;
   }
   hs_destroy(h);
   // a cluster per root in ascending id (= ascending smallest member), members in ascending id
@@ -1648,17 +1745,18 @@ static int ComponentsOrTree(const std::vector<Kmer>& kmers, const uint32_t& hash
 
 int Components(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
                const double& hash_R, const std::string& output_file, const Planes& planes, int device,
-               std::string* err, uint64_t* n_clusters, uint32_t unknown_seed, uint32_t centers_min_size) {
+               std::string* err, uint64_t* n_clusters, uint32_t unknown_seed, uint32_t centers_min_size,
+               const ClusterProfileOptions* profiles) {
   return ComponentsOrTree(kmers, hash_K, hash_L, hash_W, hash_R, output_file, planes, device, err, n_clusters,
-                          unknown_seed, centers_min_size, false, nullptr);
+                          unknown_seed, centers_min_size, false, nullptr, profiles);
 }
 
 int SingleLinkageTree(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L,
                       const double& hash_W, const double& hash_R, const std::string& output_file, const Planes& planes,
                       int device, std::string* err, uint64_t* n_clusters, uint64_t* n_tree_edges, uint32_t unknown_seed,
-                      uint32_t centers_min_size) {
+                      uint32_t centers_min_size, const ClusterProfileOptions* profiles) {
   return ComponentsOrTree(kmers, hash_K, hash_L, hash_W, hash_R, output_file, planes, device, err, n_clusters,
-                          unknown_seed, centers_min_size, true, n_tree_edges);
+                          unknown_seed, centers_min_size, true, n_tree_edges, profiles);
 }
 
 // Dbscan and DensityTree: the same clusters file; density: the labels come from hs_density_tree (border k-mers are
@@ -1668,7 +1766,7 @@ static int DbscanOrDensity(const std::vector<Kmer>& kmers, const uint32_t& hash_
                            const double& hash_W, const double& hash_R, const uint32_t& min_pts,
                            const std::string& output_file, const Planes& planes, int device, std::string* err,
                            uint64_t* n_clusters, uint32_t unknown_seed, uint32_t centers_min_size, bool density,
-                           bool tree, uint64_t* n_tree_edges) {
+                           bool tree, uint64_t* n_tree_edges, const ClusterProfileOptions* profiles) {
   std::vector<uint8_t> codes;
   const int cs = ClusterCodes(kmers, hash_K, hash_L, hash_W, planes, unknown_seed, &codes, err);
   if (cs != HS_OK) return cs;
@@ -1712,12 +1810,10 @@ static int DbscanOrDensity(const std::vector<Kmer>& kmers, const uint32_t& hash_
     if (h) hs_destroy(h);
     return st;
   }
-  if (centers_min_size) {
-    const int cc = ClusterCenters(h, kmers, label, centers_min_size, output_file, err);
-    if (cc != HS_OK) {
-      hs_destroy(h);
-      return cc;
-    }
+  const int extras = ClusterExtras(h, kmers, label, centers_min_size, profiles, output_file, err);
+  if (extras != HS_OK) {
+    hs_destroy(h);
+    return extras;
   }
   hs_destroy(h);
   // a cluster per label in ascending id (a label is a core k-mer of its cluster, not always its smallest member:
@@ -1785,17 +1881,18 @@ static int DbscanOrDensity(const std::vector<Kmer>& kmers, const uint32_t& hash_
 
 int Dbscan(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
            const double& hash_R, const uint32_t& min_pts, const std::string& output_file, const Planes& planes, int device,
-           std::string* err, uint64_t* n_clusters, uint32_t unknown_seed, uint32_t centers_min_size) {
+           std::string* err, uint64_t* n_clusters, uint32_t unknown_seed, uint32_t centers_min_size,
+           const ClusterProfileOptions* profiles) {
   return DbscanOrDensity(kmers, hash_K, hash_L, hash_W, hash_R, min_pts, output_file, planes, device, err, n_clusters,
-                         unknown_seed, centers_min_size, false, false, nullptr);
+                         unknown_seed, centers_min_size, false, false, nullptr, profiles);
 }
 
 int DensityTree(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
                 const double& hash_R, const uint32_t& min_pts, const std::string& output_file, const Planes& planes,
                 int device, std::string* err, bool tree, uint64_t* n_clusters, uint64_t* n_tree_edges,
-                uint32_t unknown_seed, uint32_t centers_min_size) {
+                uint32_t unknown_seed, uint32_t centers_min_size, const ClusterProfileOptions* profiles) {
   return DbscanOrDensity(kmers, hash_K, hash_L, hash_W, hash_R, min_pts, output_file, planes, device, err, n_clusters,
-                         unknown_seed, centers_min_size, true, tree, n_tree_edges);
+                         unknown_seed, centers_min_size, true, tree, n_tree_edges, profiles);
 }
 
 int KnnGraph(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,

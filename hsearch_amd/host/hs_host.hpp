@@ -300,6 +300,14 @@ int Clustering(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uin
                const double& hash_W, const double& hash_R, const std::string& output_file,
                const Planes& planes, int device, uint32_t unknown_seed, std::string* err,
                uint64_t* n_clusters = nullptr);
+// What ClusterProfiles writes (below); min_size == 0: no profiles.  Components, SingleLinkageTree, Dbscan and DensityTree
+// take a pointer to one (null: none) and then call ClusterProfiles on the labels they just found.
+struct ClusterProfileOptions {
+  uint32_t min_size = 0;  // members a cluster needs to get a profile
+  int weights = 1;        // 0 none (raw counts), 1 sites (n_eff = the members), 2 columns (n_eff = distinct / k)
+  int threshold = 0;      // 0 cover (hs_cluster_pssm_cover's min_score), 1 rank (hs_pssm_rank at rank = the members)
+  double pseudo = 1.0;    // pseudo-counts of the log-odds, finite and > 0
+};
 // Single linkage at radius R in place of the greedy leader pass: the clusters are the connected components of
 // the graph of all k-mer pairs that share a bucket in one of the L tables and lie within R (sqrt(d2) <= R, the
 // test of hclust2.cpp:64-71), which do not depend on the order of the k-mers.  One handle with all L tables, one
@@ -308,7 +316,7 @@ int Clustering(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uin
 int Components(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
                const double& hash_R, const std::string& output_file, const Planes& planes, int device,
                std::string* err, uint64_t* n_clusters = nullptr, uint32_t unknown_seed = 0,
-               uint32_t centers_min_size = 0);
+               uint32_t centers_min_size = 0, const ClusterProfileOptions* profiles = nullptr);
 // Components, and beside the clusters file the single-linkage tree up to R (hs_msf in include/hsearch.h: the minimum
 // spanning forest of the same graph under the order (distance, smaller index, larger index)) as
 // <output_file>hclust.tree.txt: one line per tree edge in merge order, "<name> <name> <distance>" -- the k-mer with
@@ -318,7 +326,8 @@ int Components(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uin
 int SingleLinkageTree(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L,
                       const double& hash_W, const double& hash_R, const std::string& output_file, const Planes& planes,
                       int device, std::string* err, uint64_t* n_clusters = nullptr, uint64_t* n_tree_edges = nullptr,
-                      uint32_t unknown_seed = 0, uint32_t centers_min_size = 0);
+                      uint32_t unknown_seed = 0, uint32_t centers_min_size = 0,
+                      const ClusterProfileOptions* profiles = nullptr);
 // Density clusters (DBSCAN, hs_dbscan in include/hsearch.h) of the same graph: only k-mers with at least min_pts
 // neighbours within R (themselves counted) join clusters together, so that one stray k-mer between two families no
 // longer fuses them; a sparse k-mer goes to the cluster of its dense neighbour with the smallest index or is noise.
@@ -327,7 +336,8 @@ int SingleLinkageTree(const std::vector<Kmer>& kmers, const uint32_t& hash_K, co
 // ascending index.  *n_clusters does not count that block.
 int Dbscan(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
            const double& hash_R, const uint32_t& min_pts, const std::string& output_file, const Planes& planes, int device,
-           std::string* err, uint64_t* n_clusters = nullptr, uint32_t unknown_seed = 0, uint32_t centers_min_size = 0);
+           std::string* err, uint64_t* n_clusters = nullptr, uint32_t unknown_seed = 0, uint32_t centers_min_size = 0,
+           const ClusterProfileOptions* profiles = nullptr);
 // The density tree (hs_density_tree in include/hsearch.h: DBSCAN at every radius up to R) of the same graph at min_pts.
 // The clusters file, in Dbscan's format, holds the DBSCAN* clusters at R: Dbscan's with their border k-mers moved to
 // the noise block.  <output_file>hclust.core.txt always: one line per k-mer, "<name> <core distance>", "inf" for none.
@@ -336,7 +346,8 @@ int Dbscan(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_
 int DensityTree(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint32_t& hash_L, const double& hash_W,
                 const double& hash_R, const uint32_t& min_pts, const std::string& output_file, const Planes& planes,
                 int device, std::string* err, bool tree = false, uint64_t* n_clusters = nullptr,
-                uint64_t* n_tree_edges = nullptr, uint32_t unknown_seed = 0, uint32_t centers_min_size = 0);
+                uint64_t* n_tree_edges = nullptr, uint32_t unknown_seed = 0, uint32_t centers_min_size = 0,
+                const ClusterProfileOptions* profiles = nullptr);
 // The k-nearest-neighbour graph within R of the same k-mers (hs_self_knn in include/hsearch.h; hclust2's test
 // sqrt(d2) <= R) as <output_file>hclust.knn.txt: one line per k-mer in input order, "<name> <degree>" and then, for its
 // min(topk, degree) nearest neighbours in ascending (distance, index), " <neighbour name> <distance>".  The degree is
@@ -356,6 +367,17 @@ int KnnGraph(const std::vector<Kmer>& kmers, const uint32_t& hash_K, const uint3
 // search given both files reports every member of every cluster.  Returns 0 or an hs_status with *err set.
 int ClusterCenters(hs_handle* h, const std::vector<Kmer>& kmers, const std::vector<uint32_t>& label, uint32_t min_size,
                    const std::string& output_file, std::string* err, uint64_t* n_centers = nullptr);
+// From cluster labels to the `--pssm` input of motif_both_points, on the handle that holds the k-mers' index: per
+// cluster of at least opt.min_size members, in ascending label, <output_file>hclust.pssm.txt receives a profile named
+// as ClusterCenters names the centre, through WritePssmFile (it reads back bit for bit).  The profile: the log-odds
+// (hs_pssm_log_odds_weighted of hs_cluster_weighted_profile's position-based sequence weights; with weights == 0
+// hs_pssm_log_odds of the raw counts) against hs_pssm_background of the composition of all n k-mers, pseudo-counts
+// opt.pseudo.  Its threshold: the covering threshold (hs_cluster_pssm_cover: the scan reports every member of the
+// cluster under its profile) or the score of its size-th best k-mer (hs_pssm_rank).  Returns 0 or an hs_status with
+// *err set.
+int ClusterProfiles(hs_handle* h, const std::vector<Kmer>& kmers, const std::vector<uint32_t>& label,
+                    const ClusterProfileOptions& opt, const std::string& output_file, std::string* err,
+                    uint64_t* n_profiles = nullptr);
 
 // evaulate() (:100-165) with weight() (:67-87): weighted recall of a hits file against a ground
 // truth file sorted by (motif, protein); also writes <output_file>.accuracy.txt.  Returns NaN

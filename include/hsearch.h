@@ -122,6 +122,9 @@ typedef struct hs_profile {
   uint64_t pssm_weight_items;  /* hs_pssm_weighted_counts*: the work items of the weight kernel (pssm_count_items) */
   uint64_t pssm_null_bins;     /* hs_pssm_pvalue*: the bins B of the score grid the call used (HS_OPT_PSSM_NULL_BINS) */
   uint64_t pssm_null_profiles; /* hs_pssm_pvalue*: profiles whose null distribution the call convolved */
+  uint64_t summary_weight_rows;  /* hs_cluster_weighted_profile*: the rows weighted (the call's *n_out; 0 after other calls) */
+  uint64_t summary_weight_items; /* hs_cluster_weighted_profile*: the work items of the weight kernel, summed over the
+                                    row batches */
   uint64_t pssm_rank_sample;   /* hs_pssm_rank*: the sample size n_s = min(n, HS_OPT_PSSM_RANK_SAMPLE) the call used */
   uint64_t pssm_rank_retries;  /* hs_pssm_rank*: the sum of rounds[]: profiles times the extra rounds they took */
   uint64_t pssm_topk_sample;   /* hs_pssm_topk*: the sample size n_s = min(n, HS_OPT_PSSM_TOPK_SAMPLE) the call used */
@@ -1148,6 +1151,66 @@ HS_API hs_status hs_cluster_summary_codes(const uint8_t* codes, uint64_t n, uint
                                           const double* centers, uint64_t n_center_rows, uint32_t* out_label,
                                           uint32_t* out_size, uint32_t* counts, double* centroid, double* max_d2,
                                           double* radius, uint32_t* medoid, uint64_t cap, uint64_t* n_out);
+
+/* ---- clusters to weighted, searchable profiles -------------------------------------------------------------- */
+
+/* The step from the clusters the engine discovers to profiles hs_pssm_scan can be given: per row of hs_cluster_profile
+ * the position-based sequence weights of its members (so that a family present in hundreds of near-identical copies
+ * does not own its cluster's profile) and, for a profile built from them, the threshold that covers the row -- the
+ * profile-side counterpart of hs_cluster_radii's covering radius.
+ *
+ * hs_cluster_weighted_profile.  Rows, out_label, out_size, cap, *n_out, the label rules and every refusal are
+ * hs_cluster_profile's (wcounts takes centroid's place among the arrays a call with cap > 0 must give).  Per row:
+ *   counts   [row][k][alphabet] uint32 (may be NULL): what hs_cluster_profile gives
+ *   wcounts  [row][k][alphabet] uint64: the sum of W(i) over the members i with residue a at position p
+ *   wsum     [row] uint64 (may be NULL): the sum of W(i) over the members
+ *   distinct [row] uint32 (may be NULL): the sum over p of r[p]
+ * under the rule of hs_pssm_weighted_counts with the sites of row r being the members of row r: r[p] = the residues
+ * that occur at p, u[p][a] = floor(2^56 / (r[p] counts[p][a])), W(i) = the sum over p of u[p][x_ip].  It is
+ * hs_pssm_weight_hits over the tuples (m = row, id = member) without id_start.  Every column of wcounts[row] sums to
+ * wsum[row] <= k 2^56.  All sums are integer sums: the result is a pure function of (codes, labels, min_size), whatever
+ * HS_OPT_SUMMARY_CHUNK, HS_OPT_SUMMARY_ROWS and the device's scheduling are.
+ * How: per batch of rows, behind the profile kernel, one wave per row builds the u tables, and a second pass over the
+ * same member slots, items and segments adds every member's weight into uint64 LDS histograms
+ * (hsearch_amd/csrc/hs_cluster_pssm.hip).  Scratch: the counts (when counts == NULL) and the tables of a row batch,
+ * together at most 32 MB.  hs_profile after the call: summary_weight_rows, summary_weight_items.
+ *
+ * hs_cluster_pssm_cover.  The same labels and min_size plus profiles S [n_rows][k][alphabet], held to hs_pssm_scan's
+ * value checks (a NaN or infinite entry, |S| > 2^100: HS_ERR_INVALID); n_rows must be the row count the labels give,
+ * else HS_ERR_INVALID.  Every refusal comes before anything is written; the _dev form finds the value errors on the
+ * device with one read-back.  Per row:
+ *   min_score  the smallest score of the row's profile over the row's members; the score is hs_pssm_scan's, bit for
+ *              bit: from +0.0, left to right in fp64
+ *   argmin     the member attaining it, the smallest id among ties
+ * THE CONTRACT: hs_pssm_scan(S, t = min_score) returns every member of row r among the hits of profile r -- score >= t
+ * on identical bits.
+ *
+ * hs_cluster_profile and hs_cluster_radii launch exactly what they launched before.  Out of scope: a p-value threshold
+ * mode, a device log-odds (hs_pssm_log_odds_weighted stays the host's), multi-GPU drivers (the host rules below are the
+ * route for label shares gathered from several GPUs), position-specific pseudo-counts. */
+HS_API hs_status hs_cluster_weighted_profile(hs_handle* h, const uint32_t* label, uint32_t min_size,
+                                             uint32_t* out_label, uint32_t* out_size, uint32_t* counts,
+                                             uint64_t* wcounts, uint64_t* wsum, uint32_t* distinct, uint64_t cap,
+                                             uint64_t* n_out);
+HS_API hs_status hs_cluster_pssm_cover(hs_handle* h, const uint32_t* label, uint32_t min_size, const double* S,
+                                       uint64_t n_rows, double* min_score, uint32_t* argmin);
+/* ... every array in device memory, the counts and statuses on the host (streams: as hs_query_dev) */
+HS_API hs_status hs_cluster_weighted_profile_dev(hs_handle* h, const uint32_t* d_label, uint32_t min_size,
+                                                 uint32_t* d_out_label, uint32_t* d_out_size, uint32_t* d_counts,
+                                                 uint64_t* d_wcounts, uint64_t* d_wsum, uint32_t* d_distinct,
+                                                 uint64_t cap, uint64_t* n_out);
+HS_API hs_status hs_cluster_pssm_cover_dev(hs_handle* h, const uint32_t* d_label, uint32_t min_size, const double* d_S,
+                                           uint64_t n_rows, double* d_min_score, uint32_t* d_argmin);
+/* Both rules on the host (no GPU, no handle) for codes [n][k] over `alphabet` residues (1 .. 32) and label [n]:
+ * bit-identical to the device forms.  A code >= alphabet, an illegal label, min_size 0, k outside 1 .. 75 are
+ * HS_ERR_INVALID, reported before anything is written (hs_cluster_weights_codes sets *n_out on HS_ERR_CAPACITY). */
+HS_API hs_status hs_cluster_weights_codes(const uint8_t* codes, uint64_t n, uint32_t k, uint32_t alphabet,
+                                          const uint32_t* label, uint32_t min_size, uint32_t* out_label,
+                                          uint32_t* out_size, uint32_t* counts, uint64_t* wcounts, uint64_t* wsum,
+                                          uint32_t* distinct, uint64_t cap, uint64_t* n_out);
+HS_API hs_status hs_cluster_cover_codes(const uint8_t* codes, uint64_t n, uint32_t k, uint32_t alphabet,
+                                        const uint32_t* label, uint32_t min_size, const double* S, uint64_t n_rows,
+                                        double* min_score, uint32_t* argmin);
 
 /* ---- PSSM scan: every indexed k-mer scored against position-specific score matrices ------------------------- */
 
