@@ -43,7 +43,9 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_pssm_threshold_host", "hs_pssm_weighted_counts", "hs_pssm_weighted_counts_dev",
            "hs_pssm_refine_weighted", "hs_pssm_weight_hits", "hs_pssm_log_odds_weighted", "hs_pssm_weight_u",
            "hs_cluster_weighted_profile", "hs_cluster_weighted_profile_dev", "hs_cluster_pssm_cover",
-           "hs_cluster_pssm_cover_dev", "hs_cluster_weights_codes", "hs_cluster_cover_codes"]
+           "hs_cluster_pssm_cover_dev", "hs_cluster_weights_codes", "hs_cluster_cover_codes",
+           "hs_pssm_compare", "hs_pssm_compare_dev", "hs_pssm_compare_host", "hs_pssm_compare_tables",
+           "hs_pssm_compare_pass", "hs_pssm_compare_columns"]
 
 TOPK_MAX = 64        # HS_TOPK_MAX: the widest row of query_topk / self_knn / topk_merge
 NO_ID = 0xffffffff   # the id and table of an unused entry of such a row (its distance is +inf)
@@ -81,7 +83,8 @@ class _Profile(C.Structure):
                 ("pssm_count_items", C.c_uint64), ("pssm_weight_sites", C.c_uint64),
                 ("pssm_weight_items", C.c_uint64), ("pssm_null_bins", C.c_uint64),
                 ("pssm_null_profiles", C.c_uint64), ("summary_weight_rows", C.c_uint64),
-                ("summary_weight_items", C.c_uint64), ("pssm_rank_sample", C.c_uint64),
+                ("summary_weight_items", C.c_uint64), ("pssm_cmp_pairs", C.c_uint64),
+                ("pssm_cmp_survivors", C.c_uint64), ("pssm_cmp_steps", C.c_uint64), ("pssm_rank_sample", C.c_uint64),
                 ("pssm_rank_retries", C.c_uint64), ("pssm_topk_sample", C.c_uint64),
                 ("pssm_topk_raised", C.c_uint64)]
 
@@ -314,6 +317,26 @@ def load(hooks=False):
             lib.hs_pssm_tables.restype = C.c_int
             lib.hs_pssm_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
                                            C.c_void_p, C.c_void_p]
+        # profile against profile: (h, X, nx, Y, ny, t, v, hit_x, hit_y, hit_d, hit_score, cap, &n_hits, cnt); the host
+        # rule takes (X, nx, Y, ny, k, alphabet, t, v, ...) instead; tables, pass, columns: include/hsearch.h
+        if hasattr(lib, "hs_pssm_compare"):
+            for fn in (lib.hs_pssm_compare, lib.hs_pssm_compare_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                               C.c_void_p]
+            lib.hs_pssm_compare_host.restype = C.c_int
+            lib.hs_pssm_compare_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                 C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
+            lib.hs_pssm_compare_tables.restype = C.c_int
+            lib.hs_pssm_compare_tables.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.hs_pssm_compare_pass.restype = C.c_int
+            lib.hs_pssm_compare_pass.argtypes = [C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                 C.c_uint32, C.c_uint32, C.c_double]
+            lib.hs_pssm_compare_columns.restype = C.c_int
+            lib.hs_pssm_compare_columns.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
         # PSSM top-N: (h, S, t_floor, nm, topk, top_id, top_score, top_count, t_used); hits: include/hsearch.h
         if hasattr(lib, "hs_pssm_topk"):
             for fn in (lib.hs_pssm_topk, lib.hs_pssm_topk_dev):
@@ -880,6 +903,89 @@ def pssm_tables(S, t):
     return dict(code=code, tau=tau, dead=dead)
 
 
+def _pssm_compare_args(X, t, Y):
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    assert X.ndim == 3, X.shape
+    nx, k, A = X.shape
+    t = np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.float64), (nx,)))
+    if Y is not None:
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        assert Y.ndim == 3 and Y.shape[1:] == (k, A), (X.shape, Y.shape)
+    return X, t, Y, nx, (Y.shape[0] if Y is not None else 0), k, A
+
+
+def _pssm_compare_call(call, nx, cap, want_counts):
+    """The capacity retry of the comparing calls: call(hx, hy, hd, hs, cap, &n, cnt) -> status"""
+    cap = int(cap) if cap is not None else max(1024, 16 * nx)
+    cnt = np.zeros(nx, dtype=np.uint64) if want_counts else None
+    while True:
+        hx = np.empty(cap, dtype=np.uint32)
+        hy = np.empty(cap, dtype=np.uint32)
+        hd = np.empty(cap, dtype=np.int32)
+        hs = np.empty(cap, dtype=np.float64)
+        n = C.c_uint64(0)
+        st = call(_vp(hx), _vp(hy), _vp(hd), _vp(hs), C.c_uint64(cap), C.byref(n), _vp(cnt) if want_counts else None)
+        if st == HS_ERR_CAPACITY:
+            cap = int(n.value)
+            continue
+        if st != HS_OK:
+            return st, None
+        n = int(n.value)
+        res = dict(x=hx[:n], y=hy[:n], d=hd[:n], score=hs[:n])
+        if want_counts:
+            res["cnt"] = cnt
+        return st, res
+
+
+def pssm_compare_host(X, t, Y=None, min_overlap=1, cap=None, want_counts=True):
+    """hs_pssm_compare_host: the rule of Engine.pssm_compare on one CPU thread (no GPU, no handle).  X [nx][k][alphabet],
+    t a scalar or [nx], Y [ny][k][alphabet] or None (X against itself, pairs x < y).  dict(x, y, d, score[, cnt])."""
+    X, t, Y, nx, ny, k, A = _pssm_compare_args(X, t, Y)
+    lib = load()
+    st, res = _pssm_compare_call(
+        lambda hx, hy, hd, hs, c, n, cnt: lib.hs_pssm_compare_host(
+            _vp(X), C.c_uint64(nx), _vp(Y) if Y is not None else None, C.c_uint64(ny), C.c_uint32(k), C.c_uint32(A),
+            _vp(t), C.c_uint32(min_overlap), hx, hy, hd, hs, c, n, cnt), nx, cap, want_counts)
+    if st != HS_OK:
+        raise HsError(st, "hs_pssm_compare_host refused its arguments")
+    return res
+
+
+def pssm_compare_tables(X):
+    """hs_pssm_compare_tables: the int8 filter's tables of the profiles X [nx][k][alphabet], the bits the device builds:
+    dict(q [nx][k][alphabet] int8, s [nx], l1 [nx], amax [nx])."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    nx, k, A = X.shape
+    q = np.zeros((nx, k, A), dtype=np.int8)
+    s = np.zeros(nx, dtype=np.float64)
+    l1 = np.zeros(nx, dtype=np.float64)
+    amax = np.zeros(nx, dtype=np.float64)
+    st = load().hs_pssm_compare_tables(_vp(X), C.c_uint64(nx), C.c_uint32(k), C.c_uint32(A), _vp(q), _vp(s), _vp(l1),
+                                       _vp(amax))
+    if st != HS_OK:
+        raise HsError(st, "hs_pssm_compare_tables refused its arguments")
+    return dict(q=q, s=s, l1=l1, amax=amax)
+
+
+def pssm_compare_pass(I, s_x, l1_x, amax_x, s_y, l1_y, k, alphabet, t):
+    """hs_pssm_compare_pass: the filter's test on one pair at the largest integer sum I over the allowed offsets."""
+    return bool(load().hs_pssm_compare_pass(int(I), float(s_x), float(l1_x), float(amax_x), float(s_y), float(l1_y),
+                                            int(k), int(alphabet), float(t)))
+
+
+def pssm_compare_columns(X, mode="pearson"):
+    """hs_pssm_compare_columns: the column transform applied before comparing.  mode "pearson" (0): every column
+    centred on its mean and divided by its Euclidean norm; "cosine" (1): divided by the norm only."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    nm, k, A = X.shape
+    mode = {"pearson": 0, "cosine": 1}.get(mode, mode)
+    out = np.empty_like(X)
+    st = load().hs_pssm_compare_columns(_vp(X), C.c_uint64(nm), C.c_uint32(k), C.c_uint32(A), C.c_int(int(mode)), _vp(out))
+    if st != HS_OK:
+        raise HsError(st, "hs_pssm_compare_columns refused its arguments")
+    return out
+
+
 def pssm_topk_hits(m, id, score, nm, topk):
     """hs_pssm_topk's rule on the host for any list of (m, id, score) tuples (hs_pssm_topk_hits; no GPU): dict(id
     uint32 [nm][topk] padded with NO_ID, score [nm][topk] padded with -inf, count uint32 [nm]).  Tuples with id == NO_ID
@@ -1419,7 +1525,8 @@ class Engine:
                "join_min_q": 12, "join_min_m": 13, "sort_from_bit": 14, "build_serial": 15,
                "join_xcd_run": 16, "probe_records": 17, "join_chunk": 18, "summary_chunk": 19, "summary_rows": 20,
                "msf_edge_budget": 21, "join_f6": 22, "pssm_filter": 23, "pssm_topk_sample": 24, "pssm_rank_sample": 26,
-               "pssm_count_chunk": 25, "pssm_null_bins": 27, "join_f6_form": 28}
+               "pssm_count_chunk": 25, "pssm_null_bins": 27, "join_f6_form": 28,
+               "pssm_cmp_filter": 29}
 
     def set_option(self, name, value):
         """hs_set_option (include/hsearch.h hs_option): path selection / batch sizing; never changes a result."""
@@ -1967,6 +2074,33 @@ class Engine:
         st = self._lib.hs_pssm_scan_dev(self._h, C.c_void_p(d_S), C.c_void_p(d_t), C.c_uint64(nm), C.c_void_p(d_m),
                                         C.c_void_p(d_id), C.c_void_p(d_score), C.c_uint64(cap), C.byref(n),
                                         C.c_void_p(d_cnt) if d_cnt else None)
+        if st != HS_OK:
+            err = HsError(st, self._lib.hs_last_error(self._h).decode())
+            err.n_hits = int(n.value)
+            raise err
+        return int(n.value)
+
+    def pssm_compare(self, X, t, Y=None, min_overlap=1, cap=None, want_counts=True):
+        """hs_pssm_compare: the profiles X [nx][k][alphabet] against Y [ny][k][alphabet] (None: X against itself, pairs
+        x < y) at every offset with at least min_overlap columns in common; t a scalar or [nx].  No index is needed.
+        dict(x, y, d, score[, cnt]): one hit per pair whose best offset scores >= t[x], in (x, y) order."""
+        X, t, Y, nx, ny, k, A = _pssm_compare_args(X, t, Y)
+        assert (k, A) == (self.k, self._alphabet()), X.shape
+        st, res = _pssm_compare_call(
+            lambda hx, hy, hd, hs, c, n, cnt: self._lib.hs_pssm_compare(
+                self._h, _vp(X), C.c_uint64(nx), _vp(Y) if Y is not None else None, C.c_uint64(ny), _vp(t),
+                C.c_uint32(min_overlap), hx, hy, hd, hs, c, n, cnt), nx, cap, want_counts)
+        self._check(st)
+        return res
+
+    def pssm_compare_dev(self, d_X, nx, d_Y, ny, d_t, min_overlap, d_x, d_y, d_d, d_score, cap, d_cnt=None):
+        """hs_pssm_compare_dev: device pointers (ints, e.g. tensor.data_ptr(); d_Y 0 / None: self mode); returns the hit
+        count.  Raises HsError with status HS_ERR_CAPACITY (its required capacity in .n_hits) when the hits exceed cap."""
+        n = C.c_uint64(0)
+        st = self._lib.hs_pssm_compare_dev(self._h, C.c_void_p(d_X), C.c_uint64(nx), C.c_void_p(d_Y) if d_Y else None,
+                                           C.c_uint64(ny), C.c_void_p(d_t), C.c_uint32(min_overlap), C.c_void_p(d_x),
+                                           C.c_void_p(d_y), C.c_void_p(d_d), C.c_void_p(d_score), C.c_uint64(cap),
+                                           C.byref(n), C.c_void_p(d_cnt) if d_cnt else None)
         if st != HS_OK:
             err = HsError(st, self._lib.hs_last_error(self._h).decode())
             err.n_hits = int(n.value)

@@ -228,7 +228,7 @@ const struct { const char* name; int option; } kOptionNames[] = {
     {"sort_hits", HS_OPT_SORT_HITS}, {"sync_items", HS_OPT_SYNC_ITEMS}, {"join_min_q", HS_OPT_JOIN_MIN_Q},
     {"join_min_m", HS_OPT_JOIN_MIN_M}, {"sort_from_bit", HS_OPT_SORT_FROM_BIT}, {"build_serial", HS_OPT_BUILD_SERIAL},
     {"join_xcd_run", HS_OPT_JOIN_XCD_RUN}, {"probe_records", HS_OPT_PROBE_RECORDS},
-    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"join_f6", HS_OPT_JOIN_F6}, {"join_f6_form", HS_OPT_JOIN_F6_FORM}, {"pssm_filter", HS_OPT_PSSM_FILTER}, {"pssm_topk_sample", HS_OPT_PSSM_TOPK_SAMPLE}, {"pssm_rank_sample", HS_OPT_PSSM_RANK_SAMPLE}, {"pssm_null_bins", HS_OPT_PSSM_NULL_BINS}, {"pssm_count_chunk", HS_OPT_PSSM_COUNT_CHUNK}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS},
+    {"join_chunk", HS_OPT_JOIN_CHUNK}, {"join_f6", HS_OPT_JOIN_F6}, {"join_f6_form", HS_OPT_JOIN_F6_FORM}, {"pssm_filter", HS_OPT_PSSM_FILTER}, {"pssm_cmp_filter", HS_OPT_PSSM_CMP_FILTER},{"pssm_topk_sample", HS_OPT_PSSM_TOPK_SAMPLE}, {"pssm_rank_sample", HS_OPT_PSSM_RANK_SAMPLE}, {"pssm_null_bins", HS_OPT_PSSM_NULL_BINS}, {"pssm_count_chunk", HS_OPT_PSSM_COUNT_CHUNK}, {"summary_chunk", HS_OPT_SUMMARY_CHUNK}, {"summary_rows", HS_OPT_SUMMARY_ROWS},
     {"msf_edge_budget", HS_OPT_MSF_EDGE_BUDGET}};
 
 void read_knobs(hs_handle* h) {
@@ -522,6 +522,7 @@ hs_status hs_set_option(hs_handle* h, int option, int64_t value) {
       kn.join_f6_form = (int)value;
       return HS_OK;
     case HS_OPT_PSSM_FILTER: return flag(&kn.no_pssm_filter, true);
+    case HS_OPT_PSSM_CMP_FILTER: return flag(&kn.no_pssm_cmp_filter, true);
     case HS_OPT_PSSM_TOPK_SAMPLE:
       if (value < 1 || value > 0xffffffffll) break;
       kn.pssm_topk_sample = (uint32_t)value;
@@ -617,6 +618,7 @@ void hs_destroy(hs_handle* h) {
                     &h->pr_keys, &h->pr_off, &h->pr_state, &h->pr_resolved, &h->pr_tscan, &h->pr_unres, &h->pr_rank, &h->pr_out,
                     &h->pc_m, &h->pc_id, &h->pc_m2, &h->pc_id2, &h->pc_start, &h->pc_nitem, &h->pc_off, &h->pc_rows, &h->pc_out,
                     &h->pw_u, &h->pw_counts, &h->pw_out,
+                    &h->pcm_xq, &h->pcm_yq, &h->pcm_xpar, &h->pcm_ypar, &h->pcm_y,
                     &h->sq_key, &h->sq_idx, &h->sq_skey, &h->sq_sidx, &h->sq_head, &h->sq_excl, &h->sq_part, &h->sq_acc,
                     &h->sq_fin, &h->sq_chk, &h->sq_in, &h->sq_out,
                     &h->sm_size, &h->sm_tmp, &h->sm_row_of, &h->sm_off_of,

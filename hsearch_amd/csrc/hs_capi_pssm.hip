@@ -13,6 +13,9 @@
 //   hs_pssm_pvalue / _dev, hs_pssm_pvalue_threshold / _dev   null-model p-values of hits and the thresholds of
 //                                        p-values; hs_pssm_null_tables, hs_pssm_pvalue_host, hs_pssm_threshold_host: the
 //                                        same rule on the host                                      (hs_pssm_null.hip)
+//   hs_pssm_compare / _dev               profile against profile at every offset, no index needed; hs_pssm_compare_host,
+//                                        _tables, _pass, _columns: the rule, the filter's tables and test, and the column
+//                                        transform on the host                                      (hs_pssm_compare.hip)
 // What they share, each once:
 //   pssm_args_start, pssm_refuse with pssm_host_bad / pssm_rank_bad / pssm_id_start_bad / pssm_dev_check
 //                     what a call refuses: from its arguments, and from its values on the host or on the device
@@ -33,6 +36,7 @@
 #include "hs_pssm_topk.h"
 #include "hs_pssm_rank.h"
 #include "hs_pssm_null.h"
+#include "hs_pssm_compare.h"
 
 namespace {
 
@@ -901,6 +905,137 @@ hs_status pssm_null_core(hs_handle* h, const double* d_S, const double* d_bg, co
   return HS_OK;
 }
 
+// ---- hs_pssm_compare: profile against profile at every offset (kernels: hs_pssm_compare.hip) ----------------------
+// what the call refuses from its arguments (no index is needed).  Y null: self mode, ny is not looked at
+hs_status pcmp_args(hs_handle* h, const void* X, uint64_t nx, const void* Y, uint64_t ny, const void* t, uint32_t v,
+                    const void* hit_x, const void* hit_y, const void* hit_d, const void* hit_score, uint64_t cap) {
+  if (nx >= (1ull << 27) || (Y && ny >= (1ull << 27)))
+    return fail(h, HS_ERR_INVALID, "hs_pssm_compare: nx and ny must be < 2^27 per call");
+  if (Y && (nx == 0) != (ny == 0)) return fail(h, HS_ERR_INVALID, "hs_pssm_compare: one of nx, ny is 0 and the other is not");
+  if (v < 1 || v > h->p.k) return fail(h, HS_ERR_INVALID, "hs_pssm_compare: min_overlap must lie in 1..k");
+  if (nx && (!X || !t)) return fail(h, HS_ERR_INVALID, "hs_pssm_compare: X or t is null");
+  if (cap && (!hit_x || !hit_y || !hit_d || !hit_score)) return fail(h, HS_ERR_INVALID, "an output array is null");
+  return HS_OK;
+}
+
+// the pairs a batch examines: profiles m0 .. m0 + mb - 1 of the call against ny (self: those with x < y, ny = nx)
+uint64_t pcmp_pairs(uint64_t m0, uint64_t mb, uint64_t ny, bool self) {
+  if (!self) return mb * ny;
+  uint64_t pairs = 0;
+  for (uint64_t x = m0; x < m0 + mb; ++x) pairs += ny - 1 - x;
+  return pairs;
+}
+
+// One batch of mb X profiles (d_X, d_t: the batch's first; number m0 of the call) against all ny profiles d_Y: the
+// tables and the int8 MFMA filter -- Y in chunks of 65536 profiles through one table buffer -- or, with the filter
+// off, nothing; then the exact pass, under filter_passes' survivor protocol.  On success the batch's nh hits lie
+// unordered in hit_key / hit_val.
+hs_status pcmp_batch(hs_handle* h, const double* d_X, const double* d_t, uint32_t m0, uint32_t mb, const double* d_Y,
+                     uint32_t ny, bool self, uint32_t v, bool filt, uint32_t* nh) {
+  const uint32_t k = h->p.k, A = (uint32_t)h->alphabet, YC = 65536u;
+  const hs_pcmp_shape sh = hs_pcmp_shape_of(k, A, v);
+  const size_t ka = (size_t)k * A;
+  uint32_t* const d_cnt = h->counters.as<uint32_t>();
+  if (filt) {
+    const size_t xr = (mb + 31u) & ~31u, yr = (std::min(ny, YC) + 31u) & ~31u;
+    HS_HIP(h, h->pcm_xq.reserve(xr * sh.xrow));
+    HS_HIP(h, h->pcm_xpar.reserve(xr * sizeof(hs_pcmp_par)));
+    HS_HIP(h, h->pcm_yq.reserve(yr * sh.yrow));
+    HS_HIP(h, h->pcm_ypar.reserve(yr * sizeof(hs_pcmp_par)));
+  }
+  HS_HIP(h, hipMemsetAsync(d_cnt, 0, 256, h->stream));
+  HS_HIP(h, hipEventRecord(h->ev[0], h->stream));
+  HS_HIP(h, hipEventRecord(h->ev[1], h->stream));
+  HS_HIP(h, hipEventRecord(h->ev[2], h->stream));
+  HS_CHECK(filter_passes(h, mb, 0, false, nh, [&](uint32_t prov_cap, uint32_t hit_cap, bool again) -> hs_status {
+    HS_HIP(h, hipEventRecord(h->ev[3], h->stream));
+    if (filt) {
+      if (!again)
+        HS_HIP(h, hs_launch_pcmp_tables(d_X, mb, k, A, sh.stride, sh.lead, sh.xrow, h->pcm_xq.p, h->pcm_xpar.p, h->stream));
+      for (uint32_t y0 = 0; y0 < ny; y0 += YC) {
+        const uint32_t nyc = std::min(YC, ny - y0);
+        if (self && y0 + nyc - 1u <= m0) continue;  // no y of the chunk above the batch's first x
+        HS_HIP(h, hs_launch_pcmp_tables(d_Y + y0 * ka, nyc, k, A, sh.stride, 0, sh.yrow, h->pcm_yq.p, h->pcm_ypar.p,
+                                        h->stream));
+        HS_HIP(h, hs_launch_pcmp_filter(h->pcm_xq.p, h->pcm_xpar.p, d_t, m0, mb, h->pcm_yq.p, h->pcm_ypar.p, y0, nyc, k, A,
+                                        v, self, d_cnt, prov_cap, h->prov.as<uint2>(), h->stream));
+      }
+    }
+    HS_HIP(h, hipEventRecord(h->ev[4], h->stream));
+    HS_HIP(h, hs_launch_pcmp_exact(d_X, d_Y, d_t, k, A, v, m0, mb, ny, self, h->prov.as<uint2>(), d_cnt, prov_cap, !filt,
+                                   hit_cap, h->hit_key.as<uint64_t>(), h->hit_val.as<uint64_t>(), h->n_cu, h->stream));
+    HS_HIP(h, hipEventRecord(h->ev[5], h->stream));
+    HS_HIP(h, hipMemcpyAsync(h->pin_cnt, d_cnt, HS_CNT_WORDS * 4, hipMemcpyDeviceToHost, h->stream));
+    return HS_OK;
+  }));
+  const uint64_t pairs = pcmp_pairs(m0, mb, ny, self);
+  h->prof.pssm_cmp_pairs += pairs;
+  h->prof.pssm_cmp_survivors += filt ? (uint64_t)h->pin_cnt[0] : pairs;
+  h->prof.pssm_cmp_steps = filt ? hs_pcmp_steps_issued(k, A, v) : 0;
+  return HS_OK;
+}
+
+// The comparison with every array on the device (d_Y null: self mode); the callers have checked the arguments and
+// the values.  X profiles per batch: 4096, or what HS_OPT_QUERY_BATCH says; a batch whose survivors overflow the
+// counter runs again in halves, as pssm_batch_loop's do.
+hs_status pcmp_core(hs_handle* h, const double* d_X, uint64_t nx, const double* d_Y, uint64_t ny, const double* d_t,
+                    uint32_t v, uint32_t* d_hit_x, uint32_t* d_hit_y, int32_t* d_hit_d, double* d_hit_score,
+                    uint64_t cap, uint64_t* n_hits, uint64_t* d_cnt_out) {
+  const bool self = !d_Y;
+  if (self) {
+    d_Y = d_X;
+    ny = nx;
+  }
+  const uint32_t k = h->p.k, A = (uint32_t)h->alphabet;
+  const bool filt = !h->knobs.no_pssm_cmp_filter && hs_pcmp_shape_of(k, A, v).steps > 0;
+  const size_t ka = (size_t)k * A;
+  memset(&h->prof, 0, sizeof(h->prof));
+  HS_HIP(h, h->counters.reserve(256));
+  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
+  if (d_cnt_out && nx) HS_HIP(h, hipMemsetAsync(d_cnt_out, 0, nx * 8, h->stream));
+  uint64_t total = 0;
+  uint32_t MB = h->knobs.query_batch ? h->knobs.query_batch : 4096u, mb = 0;
+  for (uint64_t m0 = 0; m0 < nx && ny; m0 += mb) {
+    mb = (uint32_t)std::min<uint64_t>(MB, nx - m0);
+    if (self && m0 + 1 >= nx) break;  // the last profile has no partner above it
+    uint32_t nh = 0;
+    const hs_status st = pcmp_batch(h, d_X + m0 * ka, d_t + m0, (uint32_t)m0, mb, d_Y, (uint32_t)ny, self, v, filt, &nh);
+    if (st == HS_SPLIT_BATCH) {
+      if (mb == 1) return fail(h, HS_ERR_CAPACITY, "the filter survivors of one profile exceed 2^32");
+      MB = (mb + 1) / 2;
+      mb = 0;
+      continue;
+    }
+    if (st) return st;
+    if (nh) {
+      HS_HIP(h, hipEventRecord(h->ev[6], h->stream));
+      const uint64_t at = std::min<uint64_t>(total, cap);
+      const bool fits = nh <= cap - at;
+      const uint64_t *key = h->hit_key.as<uint64_t>(), *val = h->hit_val.as<uint64_t>();
+      if (fits) {  // the order (x, y): the 64-bit sort on the key x << 35 | y << 8 | d + 128
+        HS_HIP(h, h->hit_key2.reserve((size_t)nh * 8));
+        HS_HIP(h, h->hit_val2.reserve((size_t)nh * 8));
+        HS_HIP(h, h->temp.reserve(hs_sort_pairs_u64_u64_temp(nh) + 256));
+        HS_HIP(h, hs_sort_pairs_u64_u64(h->temp.p, h->temp.cap, key, h->hit_key2.as<uint64_t>(), val,
+                                        h->hit_val2.as<uint64_t>(), nh, 35 + bit_width_u32((uint32_t)m0 + mb), h->stream));
+        key = h->hit_key2.as<uint64_t>();
+        val = h->hit_val2.as<uint64_t>();
+      }
+      HS_HIP(h, hs_launch_pcmp_emit(key, val, nh, fits, fits ? d_hit_x + at : nullptr, fits ? d_hit_y + at : nullptr,
+                                    fits ? d_hit_d + at : nullptr, fits ? d_hit_score + at : nullptr, d_cnt_out,
+                                    h->stream));
+      HS_HIP(h, hipEventRecord(h->ev[7], h->stream));
+      HS_HIP(h, hipStreamSynchronize(h->stream));
+      h->prof.ms_finalize += ev_ms(h, 6, 7);
+    }
+    total += nh;
+  }
+  HS_CHECK(pssm_call_end(h, total));
+  *n_hits = total;
+  if (total > cap) return fail(h, HS_ERR_CAPACITY, "hit buffers too small; see *n_hits");
+  return HS_OK;
+}
+
 hs_status pssm_null_status(int r) { return r == 0 ? HS_OK : r == 1 ? HS_ERR_INVALID : HS_ERR_NOMEM; }
 
 }  // namespace
@@ -1291,6 +1426,92 @@ hs_status hs_pssm_threshold_host(const double* S, uint64_t nm, uint32_t k, uint3
                                  const double* t_lo, uint32_t bins, const double* p, double* t_p, double* p_hi,
                                  double* p_lo, uint32_t* flag) {
   return pssm_null_status(hs_pssm_threshold_host_rule(S, nm, k, alphabet, bg, t_lo, bins, p, t_p, p_hi, p_lo, flag));
+}
+
+// ---- hs_pssm_compare ---------------------------------------------------------------------------------------------
+hs_status hs_pssm_compare_dev(hs_handle* h, const double* d_X, uint64_t nx, const double* d_Y, uint64_t ny,
+                              const double* d_t, uint32_t min_overlap, uint32_t* d_hit_x, uint32_t* d_hit_y,
+                              int32_t* d_hit_d, double* d_hit_score, uint64_t cap, uint64_t* n_hits, uint64_t* d_cnt) {
+  if (!h || !n_hits) return HS_ERR_INVALID;
+  *n_hits = 0;
+  HS_CHECK(pcmp_args(h, d_X, nx, d_Y, ny, d_t, min_overlap, d_hit_x, d_hit_y, d_hit_d, d_hit_score, cap));
+  HS_CHECK(ensure_device(h));
+  if (nx) {  // the value errors: one reduction per array, one read-back, before anything is written
+    uint32_t bits[2] = {0, 0};
+    const uint64_t ka = (uint64_t)h->p.k * h->alphabet;
+    HS_HIP(h, h->sq_chk.reserve(64));
+    HS_HIP(h, hipMemsetAsync(h->sq_chk.p, 0, 64, h->stream));
+    HS_HIP(h, hs_launch_pssm_check(d_X, nx * ka, d_t, nx, h->sq_chk.as<uint32_t>(), h->stream));
+    if (d_Y) HS_HIP(h, hs_launch_pssm_check(d_Y, ny * ka, nullptr, 0, h->sq_chk.as<uint32_t>() + 1, h->stream));
+    HS_HIP(h, hipMemcpyAsync(bits, h->sq_chk.p, sizeof(bits), hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipStreamSynchronize(h->stream));
+    HS_CHECK(pssm_refuse(h, bits[0] | bits[1], "threshold", "hs_pssm_compare"));
+  }
+  return pcmp_core(h, d_X, nx, d_Y, ny, d_t, min_overlap, d_hit_x, d_hit_y, d_hit_d, d_hit_score, cap, n_hits, d_cnt);
+}
+
+hs_status hs_pssm_compare(hs_handle* h, const double* X, uint64_t nx, const double* Y, uint64_t ny, const double* t,
+                          uint32_t min_overlap, uint32_t* hit_x, uint32_t* hit_y, int32_t* hit_d, double* hit_score,
+                          uint64_t cap, uint64_t* n_hits, uint64_t* cnt) {
+  if (!h || !n_hits) return HS_ERR_INVALID;
+  *n_hits = 0;
+  HS_CHECK(pcmp_args(h, X, nx, Y, ny, t, min_overlap, hit_x, hit_y, hit_d, hit_score, cap));
+  const size_t ka = (size_t)h->p.k * h->alphabet;
+  uint32_t bad = pssm_host_bad(h, X, t, nx);
+  for (uint64_t i = 0; Y && i < ny * ka && !bad; ++i)
+    if (hs_pcmp_bad_value(Y[i], HS_PCMP_MAX_ABS)) bad = BAD_S;
+  HS_CHECK(pssm_refuse(h, bad, "threshold", "hs_pssm_compare"));
+  HS_CHECK(ensure_device(h));
+  HS_CHECK(pssm_stage_in(h, X, t, nx, h->io_radii));
+  if (Y) {
+    HS_HIP(h, h->pcm_y.reserve(std::max<size_t>(16, ny * ka * 8)));
+    if (ny) HS_HIP(h, hipMemcpyAsync(h->pcm_y.p, Y, ny * ka * 8, hipMemcpyHostToDevice, h->stream));
+  }
+  HS_HIP(h, h->io_q.reserve(std::max<size_t>(16, cap * 4)));
+  HS_HIP(h, h->io_id.reserve(std::max<size_t>(16, cap * 4)));
+  HS_HIP(h, h->io_table.reserve(std::max<size_t>(16, cap * 4)));
+  HS_HIP(h, h->io_dist.reserve(std::max<size_t>(16, cap * 8)));
+  if (cnt) HS_HIP(h, h->io_cand.reserve(std::max<size_t>(16, nx * 8)));
+  const hs_status st = pcmp_core(h, h->io_centers.as<double>(), nx, Y ? h->pcm_y.as<double>() : nullptr, ny,
+                                 h->io_radii.as<double>(), min_overlap, h->io_q.as<uint32_t>(), h->io_id.as<uint32_t>(),
+                                 h->io_table.as<int32_t>(), h->io_dist.as<double>(), cap, n_hits,
+                                 cnt ? h->io_cand.as<uint64_t>() : nullptr);
+  if (st != HS_OK && st != HS_ERR_CAPACITY) return st;
+  if (cnt && nx) HS_HIP(h, hipMemcpyAsync(cnt, h->io_cand.p, nx * 8, hipMemcpyDeviceToHost, h->stream));
+  const uint64_t nh = *n_hits;
+  if (st == HS_OK && nh) {
+    HS_HIP(h, hipMemcpyAsync(hit_x, h->io_q.p, nh * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(hit_y, h->io_id.p, nh * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(hit_d, h->io_table.p, nh * 4, hipMemcpyDeviceToHost, h->stream));
+    HS_HIP(h, hipMemcpyAsync(hit_score, h->io_dist.p, nh * 8, hipMemcpyDeviceToHost, h->stream));
+  }
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return st;
+}
+
+// The same rule on the host (hs_pssm_compare.h): no GPU, no handle
+hs_status hs_pssm_compare_host(const double* X, uint64_t nx, const double* Y, uint64_t ny, uint32_t k, uint32_t alphabet,
+                               const double* t, uint32_t min_overlap, uint32_t* hit_x, uint32_t* hit_y, int32_t* hit_d,
+                               double* hit_score, uint64_t cap, uint64_t* n_hits, uint64_t* cnt) {
+  if (!n_hits) return HS_ERR_INVALID;
+  const int r = hs_pssm_compare_host_rule(X, nx, Y, ny, k, alphabet, t, min_overlap, hit_x, hit_y, hit_d, hit_score, cap,
+                                          n_hits, cnt);
+  return r == 0 ? HS_OK : r == 1 ? HS_ERR_INVALID : HS_ERR_CAPACITY;
+}
+
+hs_status hs_pssm_compare_tables(const double* X, uint64_t nx, uint32_t k, uint32_t alphabet, int8_t* q, double* s,
+                                 double* l1, double* amax) {
+  if (k < 1 || alphabet < 1 || (nx && !X)) return HS_ERR_INVALID;
+  return hs_pssm_compare_tables_host(X, nx, k, alphabet, q, s, l1, amax) ? HS_ERR_INVALID : HS_OK;
+}
+
+int hs_pssm_compare_pass(int64_t I, double s_x, double l1_x, double amax_x, double s_y, double l1_y, uint32_t k,
+                         uint32_t alphabet, double t) {
+  return hs_pcmp_pass(I, s_x, l1_x, amax_x, s_y, l1_y, k * alphabet, t);
+}
+
+hs_status hs_pssm_compare_columns(const double* X, uint64_t nm, uint32_t k, uint32_t alphabet, int mode, double* out) {
+  return hs_pssm_compare_columns_host(X, nm, k, alphabet, mode, out) ? HS_ERR_INVALID : HS_OK;
 }
 
 }  // extern "C"

@@ -82,6 +82,7 @@ struct Knobs {
   bool no_join_f6 = false;         // HS_OPT_JOIN_F6 = 0: k-mer queries never through the FP6 join (hs_join6.hip)
   int join_f6_form = -1;           // HS_OPT_JOIN_F6_FORM: 0 hs_join6x_kernel, 1 hs_join6w_kernel, -1 automatic
   bool no_pssm_filter = false;     // HS_OPT_PSSM_FILTER = 0: hs_pssm_scan sends every pair to the exact pass (hs_pssm.hip)
+  bool no_pssm_cmp_filter = false; // HS_OPT_PSSM_CMP_FILTER = 0: hs_pssm_compare sends every pair to the exact pass
   bool no_self_codes = false;      // HS_OPT_SELF_CODES = 0: self-join from embedded centres, not from codes
   bool sort_hits = false;          // HS_OPT_SORT_HITS: order hits by the radix sort, not per query
   bool sync_items = false;         // HS_OPT_SYNC_ITEMS: read the join's item count back before launching it
@@ -282,6 +283,9 @@ struct hs_handle {
   // hs_pssm_weighted_counts (hs_pssm_weights.hip): a batch's u tables; the raw counts of a call that does not ask for
   // them; a host-pointer call's wcounts, wsum and distinct on their way out
   DevBuf pw_u, pw_counts, pw_out;
+  // hs_pssm_compare (hs_pssm_compare.hip): the int8 rows of an X batch and of a Y chunk, their parameters
+  // {s, l1, amax} per profile; a host-pointer call's Y on its way up
+  DevBuf pcm_xq, pcm_yq, pcm_xpar, pcm_ypar, pcm_y;
   // hs_seq_match (hs_seqmatch.hip: the scratch listed at its head): a batch's keys and hit indices, their sorted
   // copies, the run heads and their scan, the waves' cut runs; the call's rows so far (sq_rows of them in a list of
   // sq_acc.cap / 40) and their final reduction; the argument check's words; a host-pointer call's arrays in and out

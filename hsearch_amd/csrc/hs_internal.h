@@ -906,6 +906,29 @@ hipError_t hs_launch_pssm_exact(const uint8_t* d_codes, const double* d_S, const
 hipError_t hs_launch_pssm_emit(const uint64_t* d_key, const uint64_t* d_val, uint32_t nh, bool write, uint32_t* d_out_m,
                                uint32_t* d_out_id, double* d_out_score, uint64_t* d_cnt, hipStream_t s);
 
+// ---- hs_pssm_compare (hs_pssm_compare.hip: the kernels are written at its head; shapes: hs_pssm_compare.h) ----------
+// np profiles d_P -> rows [ceil32(np)][row] (lead zero bytes, k columns of stride bytes, zeros) and their parameters
+// [ceil32(np)] {s, l1, amax}
+hipError_t hs_launch_pcmp_tables(const double* d_P, uint32_t np, uint32_t k, uint32_t alphabet, uint32_t stride,
+                                 uint32_t lead, uint32_t row, void* d_rows, void* d_par, hipStream_t s);
+size_t hs_pcmp_filter_lds(uint32_t k, uint32_t alphabet, uint32_t v);
+// the batch's mb X rows against a chunk's nyc Y rows: survivors {x of the batch, y of the call} into d_prov through
+// hs_reserve_survivors on d_prov_count.  x_base, y_base: the call's numbers of their first profiles; self: pairs with
+// x >= y are left out
+hipError_t hs_launch_pcmp_filter(const void* d_xq, const void* d_xpar, const double* d_t, uint32_t x_base, uint32_t mb,
+                                 const void* d_yq, const void* d_ypar, uint32_t y_base, uint32_t nyc, uint32_t k,
+                                 uint32_t alphabet, uint32_t v, bool self, uint32_t* d_prov_count, uint32_t prov_cap,
+                                 uint2* d_prov, hipStream_t s);
+// d_X, d_t: the batch's first; d_Y: the call's ny profiles.  d_counters: the batch's counter block ([0] survivors, [1]
+// hits); all_pairs: every pair of the batch, no list
+hipError_t hs_launch_pcmp_exact(const double* d_X, const double* d_Y, const double* d_t, uint32_t k, uint32_t alphabet,
+                                uint32_t v, uint32_t x_base, uint32_t mb, uint32_t ny, bool self, const uint2* d_prov,
+                                uint32_t* d_counters, uint32_t prov_cap, bool all_pairs, uint32_t hit_cap,
+                                uint64_t* d_hit_key, uint64_t* d_hit_val, int n_cu, hipStream_t s);
+hipError_t hs_launch_pcmp_emit(const uint64_t* d_key, const uint64_t* d_val, uint32_t nh, bool write, uint32_t* d_out_x,
+                               uint32_t* d_out_y, int32_t* d_out_d, double* d_out_score, uint64_t* d_cnt,
+                               hipStream_t s);
+
 // ---- hs_pssm_topk (hs_pssm_topk.hip: the three steps of a batch are written at its head) ---------------------------
 size_t hs_pssm_topk_temp(uint32_t count);    // the scan's workspace for a batch of `count` profiles
 // t_used [mb] = max(floor, the topk-th best exact score among the n_s sample k-mers floor(j * n / n_s)); d_S, d_floor

@@ -982,6 +982,66 @@ int PvalueThresholds(const ProteinDB& db, uint32_t kmer_length, const std::vecto
   return HS_OK;
 }
 
+int CompareProfiles(uint32_t kmer_length, const std::vector<std::string>& names_x, const std::vector<double>& X,
+                    const std::vector<double>& t, const std::vector<std::string>* names_y, const std::vector<double>* Y,
+                    uint32_t min_overlap, int columns, const std::string& output_file, int device, std::string* err,
+                    uint64_t* n_hits_out) {
+  const uint32_t k = kmer_length;
+  const size_t ka = (size_t)k * HS_ALPHABET, nx = names_x.size(), ny = names_y ? names_y->size() : 0;
+  if (k < 1 || X.size() != nx * ka || t.size() != nx || !names_y != !Y || (Y && Y->size() != ny * ka)) {
+    if (err) *err = "the profiles do not match the kmer length";
+    return HS_ERR_INVALID;
+  }
+  std::vector<double> Xc(X), Yc;
+  if (Y) Yc = *Y;
+  if (columns >= 0 && (hs_pssm_compare_columns(X.data(), nx, k, HS_ALPHABET, columns, Xc.data()) != HS_OK ||
+                       (Y && hs_pssm_compare_columns(Y->data(), ny, k, HS_ALPHABET, columns, Yc.data()) != HS_OK))) {
+    if (err) *err = "hs_pssm_compare_columns: a profile entry is NaN, infinite or beyond 2^100";
+    return HS_ERR_INVALID;
+  }
+  const Planes planes = DrawPlanes(8 * k, 1, 1, 1.0, 0);  // (no hash table takes part: the smallest family there is)
+  hs_params prm;
+  memset(&prm, 0, sizeof(prm));
+  prm.k = k;
+  prm.K = 1;
+  prm.L = 1;
+  prm.W = 1.0;
+  prm.alphabet = HS_ALPHABET;
+  prm.device = device;
+  hs_handle* h = nullptr;
+  hs_status st = hs_create(&prm, planes.a.data(), planes.b.data(), &HS_AA_COORDS[0][0], &h);
+  HandleCloser closer = {h};
+  if (st != HS_OK) {
+    if (err) *err = std::string("hs_create: ") + (h ? hs_last_error(h) : "no usable gfx950 device");
+    return st;
+  }
+  std::vector<uint32_t> hx, hy;
+  std::vector<int32_t> hd;
+  std::vector<double> hs;
+  uint64_t n_hits = 0, cap = std::max<uint64_t>(1024, 16 * nx);
+  for (;;) {
+    hx.resize(cap), hy.resize(cap), hd.resize(cap), hs.resize(cap);
+    st = hs_pssm_compare(h, Xc.data(), nx, Y ? Yc.data() : nullptr, ny, t.data(), min_overlap, hx.data(), hy.data(),
+                         hd.data(), hs.data(), cap, &n_hits, nullptr);
+    if (st != HS_ERR_CAPACITY) break;
+    cap = n_hits;
+  }
+  if (st != HS_OK) {
+    if (err) *err = std::string("hs_pssm_compare: ") + hs_last_error(h);
+    return st;
+  }
+  const std::vector<std::string>& ynames = names_y ? *names_y : names_x;
+  std::ofstream fout(output_file.c_str());
+  char num[64];
+  for (uint64_t i = 0; i < n_hits; ++i) {
+    snprintf(num, sizeof(num), "%.17g", hs[i]);
+    fout << names_x[hx[i]] << " " << ynames[hy[i]] << " " << hd[i] << " " << num << "\n";
+  }
+  fout.close();
+  if (n_hits_out) *n_hits_out = n_hits;
+  return HS_OK;
+}
+
 int ScanProfiles(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
                  const std::vector<double>& S, const std::vector<double>& t, const std::string& output_file,
                  int device, std::string* err, uint64_t* n_windows, uint64_t* n_hits_out) {

@@ -243,6 +243,14 @@ int PvalueThresholds(const ProteinDB& db, uint32_t kmer_length, const std::vecto
                      const std::vector<double>& p, const std::vector<double>& t_lo, int device,
                      std::vector<double>* t_out, std::vector<double>* p_hi, std::vector<double>* p_lo,
                      std::vector<uint32_t>* flag, std::string* err);
+// `--pssm FILE --pssm-compare FILE2|self`: profile against profile at every offset (hs_pssm_compare; no database, no
+// index).  X [nx][kmer_length][20] with names_x and thresholds t [nx]; Y / names_y null: X against itself (pairs
+// x < y).  columns: 0 Pearson, 1 cosine (hs_pssm_compare_columns applied to both sides first), -1 raw.  One line per
+// hit, "<nameX> <nameY> <d> <score>", the score with 17 significant digits, in (x, y) order.  One GPU.
+int CompareProfiles(uint32_t kmer_length, const std::vector<std::string>& names_x, const std::vector<double>& X,
+                    const std::vector<double>& t, const std::vector<std::string>* names_y, const std::vector<double>* Y,
+                    uint32_t min_overlap, int columns, const std::string& output_file, int device, std::string* err,
+                    uint64_t* n_hits = nullptr);
 // `--pssm FILE --pssm-pvalue-column 1`: ScanProfiles' lines with " <p_hi>" appended, the upper end of the hit's p-value
 // under the same null model (hs_pssm_pvalue), printed with 17 significant digits; t_lo [nm]: the grids' floors.
 int HitPvalues(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,

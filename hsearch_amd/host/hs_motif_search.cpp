@@ -58,6 +58,12 @@
 // what --pssm FILE2 writes (--pssm-top and --pssm-per-sequence included).  A profile on whose grid nothing is admissible
 // keeps +DBL_MAX and finds nothing; it and the profiles clipped at the floor are reported on stderr by name.  Refused:
 // --pssm-pvalue without --pssm or --pssm-out, with --pssm-rank or --pssm-refine, and a P that is no number in (0, 1].
+// --pssm FILE --pssm-compare FILE2|self --pssm-compare-threshold T [--pssm-compare-overlap V] [--pssm-compare-columns
+// pearson|cosine|raw]: no database at all (-d is not needed) -- the profiles of FILE against those of FILE2, or against
+// themselves (pairs x < y), at every offset that leaves V [1] columns in common (hs_pssm_compare), after the column
+// transform [pearson]; -o holds one line per hit, "<nameX> <nameY> <d> <score %.17g>", in hit order.  Refused:
+// --pssm-compare without --pssm or without a threshold, with --pssm-rank, --pssm-refine, --pssm-pvalue, --pssm-top or
+// --pssm-per-sequence, files of another -l or alphabet, a V outside 1..-l, any other columns value; and what --pssm refuses.
 // --pssm-pvalue-column 1: every plain hit line gets " <p_hi>" appended, the upper end of the hit's p-value (hs_pssm_pvalue;
 // the grid's floor is the profile's threshold or --pssm-null-floor, whichever is lower); refused with --pssm-top and
 // --pssm-per-sequence.
@@ -124,6 +130,10 @@ const Opt kOpts[] = {
     {"pssm-rank", 'k', "with --pssm and --pssm-out: replace every threshold by the score of the profile's N-th best window over the database, 1..windows; -o then holds what --pssm with that file gives [off]", false},
     {"pssm-one-per-protein", 'I', "with --pssm-refine: only the best window of every protein counts [0]", false},
     {"pssm-pseudo", 'u', "with --pssm-refine: pseudo-counts of the log-odds, > 0 [1]", false},
+    {"pssm-compare", 'x', "with --pssm and --pssm-compare-threshold: compare the profiles of --pssm with those of this file, or with themselves ('self': pairs x < y), at every offset; one line per hit '<nameX> <nameY> <d> <score>'; no -d", false},
+    {"pssm-compare-threshold", 'y', "with --pssm-compare: a pair is a hit when its best offset scores at least this", false},
+    {"pssm-compare-overlap", 'z', "with --pssm-compare: the columns two profiles must share at an offset, 1..-l [1]", false},
+    {"pssm-compare-columns", 'j', "with --pssm-compare: the column transform applied to both sides first: pearson, cosine or raw [pearson]", false},
     {"pssm-weights", 'w', "with --pssm-refine: weigh the sites with position-based sequence weights; the log-odds count 'sites' or 'columns' (distinct residues per column) as observations [off: every site counts 1]", false},
 };
 
@@ -150,7 +160,8 @@ void Help(const char* prog) {
 
 // --pssm: the scan of a FASTA database against position-specific score matrices (hsearch::ScanProfiles).  It is no
 // search: what selects, sizes or reduces a search is refused, not ignored.
-int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::string>& db_append) {
+// what --pssm refuses whatever else is asked
+bool PssmRefused(std::map<std::string, std::string>& val, const std::vector<std::string>& db_append) {
   static const struct { const char* name; const char* flag; } kRefused[] = {
       {"center", "-c"}, {"radii", "--radii"}, {"probes", "-M"}, {"topk", "--topk"}, {"per-sequence", "--per-sequence"},
       {"best-per-position", "--best-per-position"}, {"query-fasta", "--query-fasta"}};
@@ -158,16 +169,97 @@ int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::str
     if (val.count(r.name)) {
       fprintf(stderr, "ERROR: --pssm cannot be combined with %s: it scans every window against the profiles, it is "
                       "no search\n", r.flag);
-      return EXIT_FAILURE;
+      return true;
     }
   if (val.count("gpus") && atoi(val["gpus"].c_str()) > 1) {
     fprintf(stderr, "ERROR: --pssm runs on one GPU: it cannot be combined with --gpus %s\n", val["gpus"].c_str());
-    return EXIT_FAILURE;
+    return true;
   }
   if (!db_append.empty()) {
     fprintf(stderr, "ERROR: --pssm cannot be combined with --db-append\n");
+    return true;
+  }
+  return false;
+}
+
+// --pssm FILE --pssm-compare FILE2|self: profiles against profiles (hsearch::CompareProfiles); no database
+int CompareMain(std::map<std::string, std::string>& val, const std::vector<std::string>& db_append) {
+  if (PssmRefused(val, db_append)) return EXIT_FAILURE;
+  for (const char* name : {"pssm-rank", "pssm-refine", "pssm-pvalue", "pssm-top", "pssm-per-sequence", "pssm-out",
+                           "pssm-pvalue-column", "pssm-null-floor"})
+    if (val.count(name)) {
+      fprintf(stderr, "ERROR: --pssm-compare compares profiles with profiles: it cannot be combined with --%s\n", name);
+      return EXIT_FAILURE;
+    }
+  if (!val.count("pssm-compare-threshold")) {
+    fprintf(stderr, "ERROR: --pssm-compare needs --pssm-compare-threshold: the score a pair's best offset must reach\n");
     return EXIT_FAILURE;
   }
+  char* end = nullptr;
+  const std::string& ttext = val["pssm-compare-threshold"];
+  const double threshold = strtod(ttext.c_str(), &end);
+  if (ttext.empty() || end == ttext.c_str() || *end || !(fabs(threshold) <= 1.7976931348623157e308)) {
+    fprintf(stderr, "ERROR: --pssm-compare-threshold takes a finite score\n");
+    return EXIT_FAILURE;
+  }
+  const uint32_t kmer_length = (uint32_t)strtoul(val["len"].c_str(), nullptr, 10);
+  uint32_t overlap = 1;
+  if (val.count("pssm-compare-overlap")) {
+    const std::string& text = val["pssm-compare-overlap"];
+    const long v = strtol(text.c_str(), &end, 10);
+    if (text.empty() || end == text.c_str() || *end || v < 1 || v > (long)kmer_length) {
+      fprintf(stderr, "ERROR: --pssm-compare-overlap takes a number of columns, 1..%u\n", kmer_length);
+      return EXIT_FAILURE;
+    }
+    overlap = (uint32_t)v;
+  }
+  int columns = 0;
+  if (val.count("pssm-compare-columns")) {
+    const std::string& text = val["pssm-compare-columns"];
+    if (text != "pearson" && text != "cosine" && text != "raw") {
+      fprintf(stderr, "ERROR: --pssm-compare-columns takes 'pearson', 'cosine' or 'raw'\n");
+      return EXIT_FAILURE;
+    }
+    columns = text == "pearson" ? 0 : text == "cosine" ? 1 : -1;
+  }
+  const int device = val.count("device") ? atoi(val["device"].c_str()) : 0;
+  try {
+    std::vector<std::string> names_x, names_y;
+    std::vector<double> X, Y, t_file;
+    std::string err;
+    if (!hsearch::ReadPssmFile(val["pssm"], kmer_length, &names_x, &X, &t_file, &err)) {
+      fprintf(stderr, "ERROR: %s\n", err.c_str());
+      return EXIT_FAILURE;
+    }
+    const bool self = val["pssm-compare"] == "self";
+    if (!self && !hsearch::ReadPssmFile(val["pssm-compare"], kmer_length, &names_y, &Y, &t_file, &err)) {
+      fprintf(stderr, "ERROR: %s\n", err.c_str());
+      return EXIT_FAILURE;
+    }
+    std::cout << "number of profiles " << names_x.size();
+    if (!self) std::cout << " against " << names_y.size();
+    std::cout << std::endl;
+    const std::vector<double> t(names_x.size(), threshold);
+    uint64_t n_hits = 0;
+    const int st = hsearch::CompareProfiles(kmer_length, names_x, X, t, self ? nullptr : &names_y, self ? nullptr : &Y,
+                                            overlap, columns, val["output"], device, &err, &n_hits);
+    if (st != 0) {
+      fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), st);
+      return EXIT_FAILURE;
+    }
+    std::cout << "number of hits " << n_hits << std::endl;
+  } catch (const std::bad_alloc&) {
+    fprintf(stderr, "ERROR: could not allocate memory\n");
+    return EXIT_FAILURE;
+  } catch (const std::exception& e) {
+    fprintf(stderr, "%s\n", e.what());
+    return EXIT_FAILURE;
+  }
+  return EXIT_SUCCESS;
+}
+
+int PssmMain(std::map<std::string, std::string>& val, const std::vector<std::string>& db_append) {
+  if (PssmRefused(val, db_append)) return EXIT_FAILURE;
   uint32_t top_n = 0;  // 0: every hit
   if (val.count("pssm-top")) {
     char* end = nullptr;
@@ -442,6 +534,16 @@ int main(int argc, const char* argv[]) {
       fprintf(stderr, "ERROR: --%s belongs to --pssm FILE: it cannot be given without it\n", name);
       return EXIT_FAILURE;
     }
+  const bool with_compare = val.count("pssm-compare") != 0;
+  if (with_compare && !with_pssm) {
+    fprintf(stderr, "ERROR: --pssm-compare compares the profiles of --pssm FILE: it cannot be given without it\n");
+    return EXIT_FAILURE;
+  }
+  for (const char* name : {"pssm-compare-threshold", "pssm-compare-overlap", "pssm-compare-columns"})
+    if (val.count(name) && !with_compare) {
+      fprintf(stderr, "ERROR: --%s belongs to --pssm-compare: it cannot be given without it\n", name);
+      return EXIT_FAILURE;
+    }
   if (val.count("pssm-rank") && !with_pssm) {
     fprintf(stderr, "ERROR: --pssm-rank sets the thresholds of --pssm FILE: it cannot be given without it\n");
     return EXIT_FAILURE;
@@ -457,11 +559,13 @@ int main(int argc, const char* argv[]) {
   const bool per_sequence = query_fasta || (val.count("per-sequence") && atoi(val["per-sequence"].c_str()) != 0);
   for (const Opt& o : kOpts)
     if (o.required && !val.count(o.long_name) && !(query_fasta && std::string(o.long_name) == "center") &&
-        !(with_pssm && (std::string(o.long_name) == "center" || std::string(o.long_name) == "window"))) {
+        !(with_pssm && (std::string(o.long_name) == "center" || std::string(o.long_name) == "window")) &&
+        !(with_compare && std::string(o.long_name) == "db")) {
       fprintf(stderr, "missing required option -%c\n", o.short_name);
       Help(argv[0]);
       return EXIT_SUCCESS;  // as the reference: option_missing() -> message, EXIT_SUCCESS
     }
+  if (with_compare) return CompareMain(val, db_append);
   if (with_pssm) return PssmMain(val, db_append);
   const bool with_radii = val.count("radii") != 0;
   if (!with_radii && !val.count("threshold")) {

@@ -125,7 +125,11 @@ typedef struct hs_profile {
   uint64_t summary_weight_rows;  /* hs_cluster_weighted_profile*: the rows weighted (the call's *n_out; 0 after other calls) */
   uint64_t summary_weight_items; /* hs_cluster_weighted_profile*: the work items of the weight kernel, summed over the
                                     row batches */
-  uint64_t pssm_rank_sample;   /* hs_pssm_rank*: the sample size n_s = min(n, HS_OPT_PSSM_RANK_SAMPLE) the call used */
+  uint64_t pssm_cmp_pairs;     /* hs_pssm_compare*: the (x, y) pairs the call examined (self mode: those with x < y) */
+  uint64_t pssm_cmp_survivors; /* ... of which this many passed the int8 MFMA filter and went to the exact pass (with
+                                  HS_OPT_PSSM_CMP_FILTER = 0, or a shape the filter does not run on: all of them) */
+  uint64_t pssm_cmp_steps;     /* ... 64-byte MFMA depth steps per 16 x 16 tile, summed over the offsets (0: no filter) */
+  uint64_t pssm_rank_sample;  /* hs_pssm_rank*: the sample size n_s = min(n, HS_OPT_PSSM_RANK_SAMPLE) the call used */
   uint64_t pssm_rank_retries;  /* hs_pssm_rank*: the sum of rounds[]: profiles times the extra rounds they took */
   uint64_t pssm_topk_sample;   /* hs_pssm_topk*: the sample size n_s = min(n, HS_OPT_PSSM_TOPK_SAMPLE) the call used */
   uint64_t pssm_topk_raised;   /* hs_pssm_topk*: profiles scanned at a threshold above their floor (t_used > floor) */
@@ -227,7 +231,9 @@ typedef enum hs_option {
                                 hs_join6w_kernel (items of 192 members: a query tile feeds 24 MFMAs, not 16); -1
                                 (default): automatic, which is 1 wherever HS_OPT_JOIN_F6 applies.  Never shows in
                                 a result */
-  HS_OPT_JOIN_XCD_RUN = 16  /* hs_join8x_kernel's work items dealt in runs of this many chunks per XCD, each XCD's
+  HS_OPT_PSSM_CMP_FILTER = 29, /* hs_pssm_compare: 1 (default): the int8 MFMA filter in front of the exact pass
+                                  wherever its shape allows; 0: every pair to the exact pass.  Never shows in a result */
+  HS_OPT_JOIN_XCD_RUN = 16 /* hs_join8x_kernel's work items dealt in runs of this many chunks per XCD, each XCD's
                                 waves on their own runs (a run's items stream the same query tiles: one L2 fetches
                                 them instead of eight).  0: one counter for the chip; -1 (default): by the size
                                 of the batch's query-tile array */
@@ -1630,6 +1636,58 @@ HS_API hs_status hs_pssm_pvalue_host(const double* S, uint64_t nm, uint32_t k, u
 HS_API hs_status hs_pssm_threshold_host(const double* S, uint64_t nm, uint32_t k, uint32_t alphabet, const double* bg,
                                         const double* t_lo, uint32_t bins, const double* p, double* t_p, double* p_hi,
                                         double* p_lo, uint32_t* flag);
+
+/* ---- hs_pssm_compare: profile against profile, at every offset -----------------------------
+ * X [nx][k][alphabet] and Y [ny][k][alphabet] are fp64 profiles of the handle's k and alphabet (a narrower motif is
+ * passed zero-padded to k columns: zero columns add +0.0), t [nx] one threshold per X profile, min_overlap = v in
+ * 1..k.  No index is needed: the call works on a handle that was never built.
+ *   col(x, i, y, j)  = sum over r = 0 .. alphabet - 1 of X[x][i][r] * Y[y][j][r], from +0.0, left to right, every
+ *                      product and every sum rounded to fp64 on its own (no FMA);
+ *   score(x, y, d)   = sum of col(x, p + d, y, p) over p ascending from max(0, -d) to min(k, k - d) - 1, from +0.0,
+ *                      every sum rounded: column p of Y meets column p + d of X, d in -(k - v) .. k - v;
+ *   best(x, y)       = the largest score over the allowed d; among equal scores the first in the order (|d|, d)
+ *                      ascending (0, -1, +1, -2, +2, ...) wins;
+ *   (x, y) is a hit  iff best(x, y) >= t[x].
+ * One hit per pair in (x, y) ascending order: hit_x, hit_y, hit_d (int32: the winning offset), hit_score (bit for
+ * bit).  cnt [nx] (may be NULL) = the hits of every X profile, valid on HS_OK and on HS_ERR_CAPACITY; the two-call
+ * capacity pattern is hs_pssm_scan's (cap = 0 with null outputs counts).  Y == NULL: X against itself -- only pairs
+ * x < y are examined and reported, under t[x]; score(x, y, d) and score(y, x, -d) are the same bits.
+ * Refused with HS_ERR_INVALID before anything is written: nx or ny at or above 2^27, or 0 beside a non-zero other;
+ * v outside 1..k; a NaN, an infinity or |entry| > 2^100 in X or Y; a NaN or infinite threshold; null outputs with
+ * cap > 0.  The _dev form (every pointer but n_hits on the device) finds the value errors on the device with one
+ * read-back.
+ * The result is a pure function of (X, Y, t, v): neither HS_OPT_QUERY_BATCH (X profiles per batch), nor
+ * HS_OPT_PSSM_CMP_FILTER, nor the survivors' order shows in it.  The filter (hsearch_amd/csrc/hs_pssm_compare.h:
+ * int8 codes on v_mfma_i32_16x16x64_i8, one chain per offset) never decides a hit; it runs wherever
+ * k * stride <= 1024 bytes, stride = the alphabet rounded up to 16; other shapes go through the exact pass alone
+ * (pssm_cmp_steps = 0).  hs_profile after the call: pssm_cmp_pairs, pssm_cmp_survivors, pssm_cmp_steps, hits,
+ * ms_verify (tables + filter), ms_finalize (exact pass + ordering), ms_total. */
+HS_API hs_status hs_pssm_compare(hs_handle* h, const double* X, uint64_t nx, const double* Y, uint64_t ny,
+                                 const double* t, uint32_t min_overlap, uint32_t* hit_x, uint32_t* hit_y,
+                                 int32_t* hit_d, double* hit_score, uint64_t cap, uint64_t* n_hits, uint64_t* cnt);
+HS_API hs_status hs_pssm_compare_dev(hs_handle* h, const double* d_X, uint64_t nx, const double* d_Y, uint64_t ny,
+                                     const double* d_t, uint32_t min_overlap, uint32_t* d_hit_x, uint32_t* d_hit_y,
+                                     int32_t* d_hit_d, double* d_hit_score, uint64_t cap, uint64_t* n_hits,
+                                     uint64_t* d_cnt);
+/* The same rule on the host, no GPU and no handle: hs_pssm_compare_host is the contract on one CPU thread (same
+ * outputs, same refusals; HS_ERR_CAPACITY with *n_hits when cap is short).  hs_pssm_compare_tables: the filter's
+ * tables per profile, the bits the device builds -- q [nx][k][alphabet] int8 codes rint(x / s), s [nx] the scale
+ * amax / 127, l1 [nx] an upper bound of the profile's sum of |x|, amax [nx]; any output may be NULL.
+ * hs_pssm_compare_pass: the filter's test on a pair from those tables and I = the largest exact integer sum of code
+ * products over the allowed offsets (1: the pair goes to the exact pass).  hs_pssm_compare_columns: the column
+ * transform a user applies before comparing, out [nm][k][alphabet] -- mode 0: every column centred on its mean and
+ * divided by its Euclidean norm (the score is then a sum of column Pearson correlations; a constant column becomes
+ * zeros), mode 1: divided by the norm only (cosine).  The order of operations: hs_pssm_compare.h. */
+HS_API hs_status hs_pssm_compare_host(const double* X, uint64_t nx, const double* Y, uint64_t ny, uint32_t k,
+                                      uint32_t alphabet, const double* t, uint32_t min_overlap, uint32_t* hit_x,
+                                      uint32_t* hit_y, int32_t* hit_d, double* hit_score, uint64_t cap,
+                                      uint64_t* n_hits, uint64_t* cnt);
+HS_API hs_status hs_pssm_compare_tables(const double* X, uint64_t nx, uint32_t k, uint32_t alphabet, int8_t* q,
+                                        double* s, double* l1, double* amax);
+HS_API int hs_pssm_compare_pass(int64_t I, double s_x, double l1_x, double amax_x, double s_y, double l1_y,
+                                uint32_t k, uint32_t alphabet, double t);
+HS_API hs_status hs_pssm_compare_columns(const double* X, uint64_t nm, uint32_t k, uint32_t alphabet, int mode,
+                                         double* out);
 
 /* Replaces Clustering() (hclust2.cpp:86-151) with explicit planes a[L][K][d], b[L][K]: table by
  * table, an LSH table over the not-yet-absorbed k-mers, then greedy leader clustering inside every
