@@ -45,7 +45,8 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_cluster_weighted_profile", "hs_cluster_weighted_profile_dev", "hs_cluster_pssm_cover",
            "hs_cluster_pssm_cover_dev", "hs_cluster_weights_codes", "hs_cluster_cover_codes",
            "hs_pssm_compare", "hs_pssm_compare_dev", "hs_pssm_compare_host", "hs_pssm_compare_tables",
-           "hs_pssm_compare_pass", "hs_pssm_compare_columns"]
+           "hs_pssm_compare_pass", "hs_pssm_compare_columns", "hs_pssm_family_scan", "hs_pssm_family_scan_dev",
+           "hs_pssm_family_hits", "hs_pssm_family_layout"]
 
 TOPK_MAX = 64        # HS_TOPK_MAX: the widest row of query_topk / self_knn / topk_merge
 NO_ID = 0xffffffff   # the id and table of an unused entry of such a row (its distance is +inf)
@@ -79,7 +80,8 @@ class _Profile(C.Structure):
                 ("append_new_buckets", C.c_uint64), ("remove_rebuilds", C.c_uint64),
                 ("remove_dead_buckets", C.c_uint64), ("remove_retupled", C.c_uint64),
                 ("pssm_pairs", C.c_uint64), ("pssm_survivors", C.c_uint64), ("pssm_dead", C.c_uint64),
-                ("pssm_mfma_steps", C.c_uint64), ("pssm_seq_rows", C.c_uint64), ("pssm_count_sites", C.c_uint64),
+                ("pssm_mfma_steps", C.c_uint64), ("pssm_seq_rows", C.c_uint64), ("pssm_fam_rows", C.c_uint64),
+                ("pssm_fam_kept", C.c_uint64), ("pssm_count_sites", C.c_uint64),
                 ("pssm_count_items", C.c_uint64), ("pssm_weight_sites", C.c_uint64),
                 ("pssm_weight_items", C.c_uint64), ("pssm_null_bins", C.c_uint64),
                 ("pssm_null_profiles", C.c_uint64), ("summary_weight_rows", C.c_uint64),
@@ -357,6 +359,23 @@ def load(hooks=False):
             lib.hs_pssm_seq_hits.restype = C.c_int
             lib.hs_pssm_seq_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                                              C.c_uint64] + rows7 + [C.c_uint64, C.POINTER(C.c_uint64)]
+        # PSSM families: (h, S, t, nm, m_group, n_groups, m_off, id_start, n_seq, min_count, t_group, 10 row arrays,
+        # cap, &n_out, &n_hits, cnt, grp_rows); hits: (m, id, score, n_tuples, nm, m_group, ..., t_group, 10 row arrays,
+        # cap, &n_out); layout: (x, y, d, n_hits, nm, group, off, order, &n_groups, &n_conflicts)
+        if hasattr(lib, "hs_pssm_family_scan"):
+            rows10 = [C.c_void_p] * 10
+            fam = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
+            for fn in (lib.hs_pssm_family_scan, lib.hs_pssm_family_scan_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64] + fam + rows10 + [
+                    C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]
+            lib.hs_pssm_family_hits.restype = C.c_int
+            lib.hs_pssm_family_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64] + fam + \
+                rows10 + [C.c_uint64, C.POINTER(C.c_uint64)]
+            lib.hs_pssm_family_layout.restype = C.c_int
+            lib.hs_pssm_family_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_uint64)]
         # PSSM hit counts: (h, S, t, nm, id_start, n_seq, counts, cnt, used, &n_hits); refine, count_hits, log_odds,
         # background: include/hsearch.h
         if hasattr(lib, "hs_pssm_hit_counts"):
@@ -1041,6 +1060,86 @@ def pssm_seq_hits(m, id, score, nm, id_start, cap=None, out=None):
         e.needed = int(n_out.value)
         raise e
     return _pssm_seq_dict(arrs, int(n_out.value))
+
+
+PSSM_FAMILY_FIELDS = (("group", np.uint32), ("seq", np.uint32), ("diag", np.int32), ("count", np.uint32),
+                      ("sum", np.float64), ("best_score", np.float64), ("best_m", np.uint32), ("best_id", np.uint32),
+                      ("lo", np.uint32), ("hi", np.uint32))
+
+
+def _pssm_family_rows(cap):
+    return [np.empty(cap, dtype=t) for _, t in PSSM_FAMILY_FIELDS]
+
+
+def _pssm_family_dict(arrs, n):
+    return {name: a[:n] for (name, _), a in zip(PSSM_FAMILY_FIELDS, arrs)}
+
+
+def _pssm_family_args(nm, m_group, n_groups, m_off, id_start, min_count, t_group):
+    """the family arguments as contiguous arrays (None stays None) and their ctypes values, in the C order"""
+    if m_group is not None:
+        m_group = np.ascontiguousarray(m_group, dtype=np.uint32)
+        assert m_group.shape == (nm,), m_group.shape
+    if n_groups is None:
+        n_groups = nm if m_group is None else (int(m_group.max()) + 1 if nm else 0)
+    if m_off is not None:
+        m_off = np.ascontiguousarray(m_off, dtype=np.uint32)
+        assert m_off.shape == (nm,), m_off.shape
+    if id_start is not None:
+        id_start = np.ascontiguousarray(id_start, dtype=np.uint64)
+        assert id_start.ndim == 1 and len(id_start) >= 1
+    if t_group is not None:
+        t_group = np.ascontiguousarray(t_group, dtype=np.float64)
+        assert t_group.shape == (int(n_groups),), t_group.shape
+    keep = (m_group, m_off, id_start, t_group)
+    vals = [None if m_group is None else _vp(m_group), int(n_groups), None if m_off is None else _vp(m_off),
+            None if id_start is None else _vp(id_start), 0 if id_start is None else len(id_start) - 1,
+            C.c_uint32(int(min_count)), None if t_group is None else _vp(t_group)]
+    return keep, vals, int(n_groups)
+
+
+def pssm_family_hits(m, id, score, nm, id_start, m_group=None, n_groups=None, m_off=None, min_count=1, t_group=None,
+                     cap=None, out=None):
+    """hs_pssm_family_hits (host only, no GPU): the rule of Engine.pssm_family_scan over ANY list of hits (m, id,
+    score) in any order -- one row per distinct (family, sequence, diagonal) that passes the filters: dict(group, seq,
+    diag, count, sum, best_score, best_m, best_id, lo, hi).  A (m, id) given twice with one score counts once.
+    n_groups=None: nm without m_group, else its largest value + 1.  cap=None: as many rows as needed; a given cap that
+    is too small raises HsError(HS_ERR_CAPACITY) with the required size in .needed.  out: a list of the ten arrays."""
+    m = np.ascontiguousarray(m, dtype=np.uint32).ravel()
+    id = np.ascontiguousarray(id, dtype=np.uint32).ravel()
+    score = np.ascontiguousarray(score, dtype=np.float64).ravel()
+    n = len(m)
+    assert id.shape == score.shape == (n,)
+    keep, vals, _ = _pssm_family_args(int(nm), m_group, n_groups, m_off, id_start, min_count, t_group)
+    room = n if cap is None else int(cap)
+    arrs = _pssm_family_rows(room) if out is None else out
+    n_out = C.c_uint64(0)
+    st = load().hs_pssm_family_hits(_vp(m), _vp(id), _vp(score), n, int(nm), *vals, *[_vp(a) for a in arrs], room,
+                                    C.byref(n_out))
+    if st != HS_OK:
+        e = HsError(st, "hs_pssm_family_hits")
+        e.needed = int(n_out.value)
+        raise e
+    return _pssm_family_dict(arrs, int(n_out.value))
+
+
+def pssm_family_layout(hit_x, hit_y, hit_d, nm):
+    """hs_pssm_family_layout (host only, no GPU): the hits (x, y, d) of Engine.pssm_compare's self mode, in their
+    order, to families: dict(group uint32 [nm], off uint32 [nm], order uint32 [nm] -- the profiles sorted by (group,
+    off, m), the order in which to pass them to pssm_family_scan --, n_groups, n_conflicts).  A hit says that profile y
+    lies d columns to the right of profile x; one that disagrees with the positions fixed before it only counts."""
+    x = np.ascontiguousarray(hit_x, dtype=np.uint32).ravel()
+    y = np.ascontiguousarray(hit_y, dtype=np.uint32).ravel()
+    d = np.ascontiguousarray(hit_d, dtype=np.int32).ravel()
+    assert x.shape == y.shape == d.shape, (x.shape, y.shape, d.shape)
+    nm = int(nm)
+    group, off, order = (np.empty(max(nm, 1), dtype=np.uint32) for _ in range(3))
+    ng, nc = C.c_uint64(0), C.c_uint64(0)
+    st = load().hs_pssm_family_layout(_vp(x), _vp(y), _vp(d), len(x), nm, _vp(group), _vp(off), _vp(order),
+                                      C.byref(ng), C.byref(nc))
+    if st != HS_OK:
+        raise HsError(st, "hs_pssm_family_layout refused its arguments")
+    return dict(group=group[:nm], off=off[:nm], order=order[:nm], n_groups=int(ng.value), n_conflicts=int(nc.value))
 
 
 def pssm_count_hits(codes, alphabet, m, id, score, nm, id_start=None):
@@ -2186,6 +2285,66 @@ class Engine:
                                             d_id_start if d_id_start else None, int(n_seq),
                                             *[p if p else None for p in d_rows], int(cap), C.byref(n), C.byref(nh),
                                             d_cnt if d_cnt else None, d_seq_cnt if d_seq_cnt else None)
+        if st == HS_ERR_CAPACITY:
+            e = HsError(st, self._lib.hs_last_error(self._h).decode())
+            e.needed, e.n_hits = int(n.value), int(nh.value)
+            raise e
+        self._check(st)
+        return int(n.value), int(nh.value)
+
+    def pssm_family_scan(self, S, t, id_start, m_group=None, m_off=None, min_count=1, t_group=None, cap=None,
+                         want_counts=True, n_groups=None):
+        """hs_pssm_family_scan: the hits of pssm_scan(S, t) reduced on the device per (family, database sequence,
+        diagonal): dict(group, seq, diag, count, sum, best_score, best_m, best_id, lo, hi -- one row per distinct
+        (group, seq, diag) that passes the filters, ascending --, n_hits[, cnt [nm] the hits per profile and grp_rows
+        [n_groups] the reported rows per family]).  m_group [nm] non-decreasing (None: every profile its own family);
+        m_off [nm]: a profile's offset inside its family, diag = (id - id_start[seq]) - m_off (None: no diagonals);
+        a row is reported iff count >= min_count and sum >= t_group[group] (None: no sum filter).  cap=None: two
+        calls, the row count then the rows; a given cap that is too small raises HsError(HS_ERR_CAPACITY) with
+        .needed, .n_hits and, with want_counts, .cnt and .grp_rows."""
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        nm = S.shape[0]
+        assert S.shape == (nm, self.k, self._alphabet()) and t.shape == (nm,), (S.shape, t.shape)
+        keep, vals, n_groups = _pssm_family_args(nm, m_group, n_groups, m_off, id_start, min_count, t_group)
+        cnt = np.zeros(nm, dtype=np.uint64) if want_counts else None
+        grp_rows = np.zeros(n_groups, dtype=np.uint64) if want_counts else None
+        room = 0 if cap is None else int(cap)
+        while True:
+            arrs = _pssm_family_rows(room)
+            n, nh = C.c_uint64(0), C.c_uint64(0)
+            st = self._lib.hs_pssm_family_scan(self._h, _vp(S), _vp(t), nm, *vals,
+                                               *[_vp(a) if room else None for a in arrs], room, C.byref(n),
+                                               C.byref(nh), _vp(cnt) if want_counts else None,
+                                               _vp(grp_rows) if want_counts else None)
+            if st == HS_ERR_CAPACITY:
+                if cap is None and int(n.value) > room:
+                    room = int(n.value)
+                    continue
+                e = HsError(st, self._lib.hs_last_error(self._h).decode())
+                e.needed, e.n_hits, e.cnt, e.grp_rows = int(n.value), int(nh.value), cnt, grp_rows
+                raise e
+            self._check(st)
+            res = _pssm_family_dict(arrs, int(n.value))
+            res["n_hits"] = int(nh.value)
+            if want_counts:
+                res["cnt"], res["grp_rows"] = cnt, grp_rows
+            return res
+
+    def pssm_family_scan_dev(self, d_S, d_t, nm, d_m_group, n_groups, d_m_off, d_id_start, n_seq, min_count,
+                             d_t_group, d_rows, cap, d_cnt=None, d_grp_rows=None):
+        """hs_pssm_family_scan_dev: device pointers (ints, e.g. tensor.data_ptr(); d_m_group, d_m_off, d_t_group,
+        d_cnt and d_grp_rows may be None; d_rows: the ten row arrays in the order of capi.PSSM_FAMILY_FIELDS).
+        Returns (rows, n_hits); raises HsError(HS_ERR_CAPACITY) with the required size in .needed and the hit count
+        in .n_hits when cap is too small."""
+        n, nh = C.c_uint64(0), C.c_uint64(0)
+        st = self._lib.hs_pssm_family_scan_dev(self._h, d_S if d_S else None, d_t if d_t else None, int(nm),
+                                               d_m_group if d_m_group else None, int(n_groups),
+                                               d_m_off if d_m_off else None, d_id_start if d_id_start else None,
+                                               int(n_seq), C.c_uint32(int(min_count)),
+                                               d_t_group if d_t_group else None, *[p if p else None for p in d_rows],
+                                               int(cap), C.byref(n), C.byref(nh), d_cnt if d_cnt else None,
+                                               d_grp_rows if d_grp_rows else None)
         if st == HS_ERR_CAPACITY:
             e = HsError(st, self._lib.hs_last_error(self._h).decode())
             e.needed, e.n_hits = int(n.value), int(nh.value)

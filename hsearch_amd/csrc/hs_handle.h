@@ -292,6 +292,10 @@ struct hs_handle {
   DevBuf sq_key, sq_idx, sq_skey, sq_sidx, sq_head, sq_excl, sq_part, sq_acc, sq_fin, sq_chk, sq_in, sq_out;
   uint64_t sq_rows = 0;
   uint32_t sq_batches = 0;
+  // hs_pssm_family_scan (hs_pssm_family.hip; the keys, heads and scans of a batch's hits are the sq_ buffers above): the
+  // hit indices sorted on the row key, the rows' run starts, the rows before the filters, the filters' flags and their
+  // scan; a host-pointer call's m_group, m_off and t_group on their way up
+  DevBuf pf_sidx, pf_start, pf_rows, pf_keep, pf_pos, pf_in;
   // hs_cluster_profile / hs_cluster_radii (hs_summary.hip: the state listed at its head), the counts of a row batch
   // when the caller wants none, and the arrays of a host-pointer call on their way in and out.  hs_cluster_weighted_profile
   // / hs_cluster_pssm_cover (hs_cluster_pssm.hip) run on the same state: a row batch's u tables go to pw_u, the members'

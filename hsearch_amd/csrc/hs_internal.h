@@ -1003,6 +1003,9 @@ hipError_t hs_launch_pssm_null_threshold(const void* d_prof, const double* d_cdf
 // head: the n hits sorted by m << 32 | id -> d_seq [n] (the sequence of every hit) and d_head [n + 1] (row starts)
 hipError_t hs_launch_pssm_seq_head(const uint64_t* d_key, uint32_t n, const uint64_t* d_id_start, uint64_t n_seq,
                                    uint32_t* d_seq, uint32_t* d_head, hipStream_t s);
+// the search alone: d_seq [n]
+hipError_t hs_launch_pssm_seq_of(const uint64_t* d_key, uint32_t n, const uint64_t* d_id_start, uint64_t n_seq,
+                                 uint32_t* d_seq, hipStream_t s);
 size_t hs_pssm_seq_part_bytes(uint32_t n);
 // rows: d_excl = the exclusive scan of d_head over n + 1 elements, n_rows its total.  Scratch: d_row_start [n_rows + 1],
 // d_row_key / d_row_id [n_rows], d_part of hs_pssm_seq_part_bytes(n) bytes.  write: the rows go to the seven output
@@ -1015,6 +1018,31 @@ hipError_t hs_launch_pssm_seq_rows(const uint64_t* d_key, const uint64_t* d_val,
                                    uint32_t* d_out_count, double* d_out_best_score, uint32_t* d_out_best_id,
                                    uint32_t* d_out_lo, uint32_t* d_out_hi, uint64_t* d_cnt, uint64_t* d_seq_cnt,
                                    hipStream_t s);
+
+// ---- hs_pssm_family_scan (hs_pssm_family.hip: the passes over a batch's sorted hits are written at its head) --------
+struct HsFamilyOut;  // hs_pssm_family.h: the ten row arrays
+// *d_flag |= the HS_FAM_BAD_* bits of d_m_group [nm], d_m_off [nm], d_t_group [n_groups] (each may be null)
+hipError_t hs_launch_pssm_family_check(const uint32_t* d_m_group, const uint32_t* d_m_off, const double* d_t_group,
+                                       uint64_t nm, uint64_t n_groups, uint32_t* d_flag, hipStream_t s);
+// the n hits sorted by m << 32 | id and their sequences -> d_row_key [n], d_idx [n] = 0 .. n - 1; d_cnt [m] += the
+// hits of every profile (may be null)
+hipError_t hs_launch_pssm_family_key(const uint64_t* d_key, const uint32_t* d_seq, uint32_t n, const uint32_t* d_m_group,
+                                     const uint32_t* d_m_off, const uint64_t* d_id_start, int ws, int wd,
+                                     uint64_t max_off, uint64_t* d_row_key, uint32_t* d_idx, uint64_t* d_cnt,
+                                     hipStream_t s);
+// d_skey / d_sidx: the pairs sorted on the row key; d_head [n + 1] their run heads, d_excl its exclusive scan, n_rows
+// its total.  Scratch: d_row_start [n_rows + 1], d_rows of 48 n_rows bytes (HsFamilyOut::in), d_keep [n_rows + 1]: the
+// filters' flags
+hipError_t hs_launch_pssm_family_rows(const uint64_t* d_skey, const uint32_t* d_sidx, const uint32_t* d_head,
+                                      const uint32_t* d_excl, uint32_t n, uint32_t n_rows, const uint64_t* d_key,
+                                      const uint64_t* d_val, const uint64_t* d_id_start, int ws, int wd,
+                                      uint64_t max_off, uint32_t min_count, const double* d_t_group,
+                                      uint32_t* d_row_start, void* d_rows, uint32_t* d_keep, hipStream_t s);
+// d_pos = the exclusive scan of d_keep.  write: the kept rows go to out (the batch's: already at the call's running
+// offset); d_grp_rows [g] += the kept rows of every group (may be null)
+hipError_t hs_launch_pssm_family_write(const void* d_rows, const uint32_t* d_keep, const uint32_t* d_pos,
+                                       uint32_t n_rows, bool write, const HsFamilyOut& out, uint64_t* d_grp_rows,
+                                       hipStream_t s);
 
 // ---- hs_pssm_hit_counts (hs_pssm_counts.hip: the passes over a batch's sites are written at its head) --------------
 // the batch's n hits m << 32 | id -> d_m [n], d_id [n]

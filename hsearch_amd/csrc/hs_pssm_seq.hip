@@ -206,6 +206,15 @@ hipError_t hs_launch_pssm_seq_head(const uint64_t* d_key, uint32_t n, const uint
   return hipGetLastError();
 }
 
+// the search alone (hs_pssm_family.hip keys its rows on more than the sequence and finds its own heads)
+hipError_t hs_launch_pssm_seq_of(const uint64_t* d_key, uint32_t n, const uint64_t* d_id_start, uint64_t n_seq,
+                                 uint32_t* d_seq, hipStream_t s) {
+  if (!n) return hipSuccess;
+  const uint32_t stride = (uint32_t)((n_seq + PS_SAMPLES) / PS_SAMPLES);
+  hs_pssm_seq_kernel<<<ps_blocks(n), 256, 0, s>>>(d_key, n, d_id_start, n_seq, stride, d_seq);
+  return hipGetLastError();
+}
+
 size_t hs_pssm_seq_part_bytes(uint32_t n) { return (size_t)2 * ((n + 63u) / 64u) * 16 + 16; }
 
 hipError_t hs_launch_pssm_seq_rows(const uint64_t* d_key, const uint64_t* d_val, const uint32_t* d_seq,

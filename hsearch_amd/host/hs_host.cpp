@@ -982,14 +982,23 @@ int PvalueThresholds(const ProteinDB& db, uint32_t kmer_length, const std::vecto
   return HS_OK;
 }
 
+static int FamilyLayoutText(const std::vector<std::string>& names, const std::vector<uint32_t>& hit_x,
+                            const std::vector<uint32_t>& hit_y, const std::vector<int32_t>& hit_d, size_t n_hits,
+                            std::string* text, std::string* err, uint64_t* n_families, uint64_t* n_conflicts);
+
 int CompareProfiles(uint32_t kmer_length, const std::vector<std::string>& names_x, const std::vector<double>& X,
                     const std::vector<double>& t, const std::vector<std::string>* names_y, const std::vector<double>* Y,
                     uint32_t min_overlap, int columns, const std::string& output_file, int device, std::string* err,
-                    uint64_t* n_hits_out) {
+                    uint64_t* n_hits_out, const std::string* families_out, uint64_t* n_families,
+                    uint64_t* n_conflicts) {
   const uint32_t k = kmer_length;
   const size_t ka = (size_t)k * HS_ALPHABET, nx = names_x.size(), ny = names_y ? names_y->size() : 0;
   if (k < 1 || X.size() != nx * ka || t.size() != nx || !names_y != !Y || (Y && Y->size() != ny * ka)) {
     if (err) *err = "the profiles do not match the kmer length";
+    return HS_ERR_INVALID;
+  }
+  if (families_out && Y) {
+    if (err) *err = "families are laid out from a self comparison only";
     return HS_ERR_INVALID;
   }
   std::vector<double> Xc(X), Yc;
@@ -1030,6 +1039,11 @@ int CompareProfiles(uint32_t kmer_length, const std::vector<std::string>& names_
     if (err) *err = std::string("hs_pssm_compare: ") + hs_last_error(h);
     return st;
   }
+  std::string families_text;  // laid out before anything is written: a refused layout leaves no output file behind
+  if (families_out) {
+    const int lst = FamilyLayoutText(names_x, hx, hy, hd, n_hits, &families_text, err, n_families, n_conflicts);
+    if (lst != HS_OK) return lst;
+  }
   const std::vector<std::string>& ynames = names_y ? *names_y : names_x;
   std::ofstream fout(output_file.c_str());
   char num[64];
@@ -1039,6 +1053,132 @@ int CompareProfiles(uint32_t kmer_length, const std::vector<std::string>& names_
   }
   fout.close();
   if (n_hits_out) *n_hits_out = n_hits;
+  if (families_out) {
+    std::ofstream ffam(families_out->c_str());
+    ffam << families_text;
+    ffam.close();
+  }
+  return HS_OK;
+}
+
+// the lines of FamilyLayout's file, nothing written yet
+static int FamilyLayoutText(const std::vector<std::string>& names, const std::vector<uint32_t>& hit_x,
+                            const std::vector<uint32_t>& hit_y, const std::vector<int32_t>& hit_d, size_t n_hits,
+                            std::string* text, std::string* err, uint64_t* n_families, uint64_t* n_conflicts) {
+  const size_t nm = names.size();
+  if (hit_x.size() < n_hits || hit_y.size() < n_hits || hit_d.size() < n_hits) {
+    if (err) *err = "the hit lists differ in length";
+    return HS_ERR_INVALID;
+  }
+  std::vector<uint32_t> group(nm), off(nm), order(nm);
+  uint64_t groups = 0, conflicts = 0;
+  const hs_status st = hs_pssm_family_layout(hit_x.data(), hit_y.data(), hit_d.data(), n_hits, nm, group.data(),
+                                             off.data(), order.data(), &groups, &conflicts);
+  if (st != HS_OK) {
+    if (err)
+      *err = "hs_pssm_family_layout: a hit names a profile twice or none, a distance of 2^30 or more, an offset beyond "
+             "2^31 - 1 or a family of more than 4096 profiles";
+    return st;
+  }
+  std::vector<uint32_t> first(groups, 0);  // the first profile of every family in the order of the file
+  for (size_t i = nm; i-- > 0;) first[group[order[i]]] = order[i];
+  std::ostringstream out;
+  for (size_t i = 0; i < nm; ++i) {
+    const uint32_t m = order[i];
+    out << names[first[group[m]]] << " " << names[m] << " " << off[m] << "\n";
+  }
+  *text = out.str();
+  if (n_families) *n_families = groups;
+  if (n_conflicts) *n_conflicts = conflicts;
+  return HS_OK;
+}
+
+int FamilyLayout(const std::vector<std::string>& names, const std::vector<uint32_t>& hit_x,
+                 const std::vector<uint32_t>& hit_y, const std::vector<int32_t>& hit_d, const std::string& families_file,
+                 std::string* err, uint64_t* n_families, uint64_t* n_conflicts) {
+  if (hit_y.size() != hit_x.size() || hit_d.size() != hit_x.size()) {
+    if (err) *err = "the hit lists differ in length";
+    return HS_ERR_INVALID;
+  }
+  std::string text;
+  const int st = FamilyLayoutText(names, hit_x, hit_y, hit_d, hit_x.size(), &text, err, n_families, n_conflicts);
+  if (st != HS_OK) return st;
+  std::ofstream fout(families_file.c_str());
+  fout << text;
+  fout.close();
+  return HS_OK;
+}
+
+int FamilyScan(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
+               const std::vector<double>& S, const std::vector<double>& t, const std::vector<std::string>& family,
+               const std::vector<uint32_t>& offset, uint32_t min_blocks, const double* threshold,
+               const std::string& output_file, int device, std::string* err, uint64_t* n_windows, uint64_t* n_hits_out,
+               uint64_t* n_rows_out) {
+  const uint32_t k = kmer_length;
+  const size_t nm = t.size();
+  if (k < 2 || names.size() != nm || S.size() != nm * (size_t)k * HS_ALPHABET || family.size() != nm ||
+      offset.size() != nm) {
+    if (err) *err = k < 2 ? "kmer length 1 is not supported on a FASTA database" : "the profiles do not match the kmer length";
+    return HS_ERR_INVALID;
+  }
+  // families numbered in the given order; one that comes back after another is refused
+  std::vector<uint32_t> m_group(nm);
+  std::vector<std::string> fam_names;
+  for (size_t m = 0; m < nm; ++m) {
+    if (!m || family[m] != family[m - 1]) {
+      if (std::find(fam_names.begin(), fam_names.end(), family[m]) != fam_names.end()) {
+        if (err) *err = "the profiles of family " + family[m] + " do not stand next to each other";
+        return HS_ERR_INVALID;
+      }
+      fam_names.push_back(family[m]);
+    }
+    m_group[m] = (uint32_t)fam_names.size() - 1;
+  }
+  const size_t n_seq = db.start.empty() ? 0 : db.start.size() - 1;
+  hs_handle* h = nullptr;
+  uint64_t n_win = 0;
+  std::vector<uint32_t> win_pos;
+  std::vector<uint64_t> id_start;
+  hs_status st = (hs_status)OpenWindowsIndex(db, k, device, &h, &n_win, &win_pos, &id_start, err);
+  HandleCloser closer = {h};
+  if (st != HS_OK) return st;
+  if (n_windows) *n_windows = n_win;
+  const std::vector<double> t_group(fam_names.size(), threshold ? *threshold : 0.0);
+  std::vector<uint32_t> rg, rs, rc, rbm, rid, rlo, rhi;
+  std::vector<int32_t> rd;
+  std::vector<double> rsum, rsc;
+  uint64_t n_rows = 0, n_hits = 0;
+  for (uint64_t cap = 0;;) {  // the row count, then the rows
+    for (std::vector<uint32_t>* v : {&rg, &rs, &rc, &rbm, &rid, &rlo, &rhi}) v->resize(cap);
+    rd.resize(cap), rsum.resize(cap), rsc.resize(cap);
+    st = hs_pssm_family_scan(h, S.data(), t.data(), nm, m_group.data(), fam_names.size(), offset.data(), id_start.data(),
+                             n_seq, min_blocks, threshold ? t_group.data() : nullptr, rg.data(), rs.data(), rd.data(),
+                             rc.data(), rsum.data(), rsc.data(), rbm.data(), rid.data(), rlo.data(), rhi.data(), cap,
+                             &n_rows, &n_hits, nullptr, nullptr);
+    if (st == HS_ERR_CAPACITY && n_rows > cap) {
+      cap = n_rows;
+      continue;
+    }
+    break;
+  }
+  if (st != HS_OK) {
+    if (err) *err = std::string("hs_pssm_family_scan: ") + hs_last_error(h);
+    return st;
+  }
+  if (n_hits_out) *n_hits_out = n_hits;
+  if (n_rows_out) *n_rows_out = n_rows;
+  std::ofstream fout(output_file.c_str());
+  char sum[64], num[64];
+  for (uint64_t i = 0; i < n_rows; ++i) {  // offsets are residue offsets in the protein, as the scan's window names
+    const size_t s = rs[i];
+    const uint64_t at = db.start[s], w0 = id_start[s];
+    snprintf(sum, sizeof(sum), "%.17g", rsum[i]);
+    snprintf(num, sizeof(num), "%.17g", rsc[i]);
+    fout << fam_names[rg[i]] << " " << ProteinLabel(db, s) << " " << rd[i] << " " << rc[i] << " " << sum << " "
+         << names[rbm[i]] << " " << (win_pos[rid[i]] - at) << " " << num << " " << (win_pos[w0 + rlo[i]] - at) << " "
+         << (win_pos[w0 + rhi[i]] - at) << "\n";
+  }
+  fout.close();
   return HS_OK;
 }
 

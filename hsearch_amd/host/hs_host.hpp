@@ -250,7 +250,29 @@ int PvalueThresholds(const ProteinDB& db, uint32_t kmer_length, const std::vecto
 int CompareProfiles(uint32_t kmer_length, const std::vector<std::string>& names_x, const std::vector<double>& X,
                     const std::vector<double>& t, const std::vector<std::string>* names_y, const std::vector<double>* Y,
                     uint32_t min_overlap, int columns, const std::string& output_file, int device, std::string* err,
-                    uint64_t* n_hits = nullptr);
+                    uint64_t* n_hits = nullptr, const std::string* families_out = nullptr,
+                    uint64_t* n_families = nullptr, uint64_t* n_conflicts = nullptr);
+// (families_out, self mode only: the hits are also laid out as families as FamilyLayout does and written to that
+// file; the layout is computed before either file is written, so a refused layout leaves no output behind)
+// `--pssm-compare self --pssm-families-out FAM`: the hits of a self comparison, in their order, to families
+// (hs_pssm_family_layout): FAM gets one line per profile, "<family> <profile name> <offset>", in the order in which to
+// pass the profiles to FamilyScan -- by (family, offset, profile) --, the family named after its first profile in that
+// order.  *n_conflicts: the hits that disagreed with the positions fixed before them.  Host only.
+int FamilyLayout(const std::vector<std::string>& names, const std::vector<uint32_t>& hit_x,
+                 const std::vector<uint32_t>& hit_y, const std::vector<int32_t>& hit_d, const std::string& families_file,
+                 std::string* err, uint64_t* n_families = nullptr, uint64_t* n_conflicts = nullptr);
+// `--pssm FILE --pssm-families FAM`: the hits of the profiles reduced per (family, protein, diagonal) on the device
+// (hs_pssm_family_scan).  family [nm], offset [nm]: every profile's family name and offset in it; the profiles of one
+// family stand next to each other (HS_ERR_INVALID otherwise).  A row is written when at least min_blocks profiles hit
+// on the diagonal and (threshold given) their scores add up to *threshold.  One line per row, "<family> <protein>#<number>
+// <diag> <blocks> <sum> <best profile> <offset of the best window> <its score> <first> <last matched offset>": diag in
+// windows, the offsets in residues from the protein's start, sum and score with 17 significant digits; families in the
+// given order, proteins in database order.  *n_hits: the hits behind the rows, *n_rows: the lines.  One GPU.
+int FamilyScan(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
+               const std::vector<double>& S, const std::vector<double>& t, const std::vector<std::string>& family,
+               const std::vector<uint32_t>& offset, uint32_t min_blocks, const double* threshold,
+               const std::string& output_file, int device, std::string* err, uint64_t* n_windows = nullptr,
+               uint64_t* n_hits = nullptr, uint64_t* n_rows = nullptr);
 // `--pssm FILE --pssm-pvalue-column 1`: ScanProfiles' lines with " <p_hi>" appended, the upper end of the hit's p-value
 // under the same null model (hs_pssm_pvalue), printed with 17 significant digits; t_lo [nm]: the grids' floors.
 int HitPvalues(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,

@@ -64,6 +64,17 @@
 // transform [pearson]; -o holds one line per hit, "<nameX> <nameY> <d> <score %.17g>", in hit order.  Refused:
 // --pssm-compare without --pssm or without a threshold, with --pssm-rank, --pssm-refine, --pssm-pvalue, --pssm-top or
 // --pssm-per-sequence, files of another -l or alphabet, a V outside 1..-l, any other columns value; and what --pssm refuses.
+// --pssm FILE --pssm-families FAM [--pssm-family-blocks C] [--pssm-family-threshold T]: FAM holds one line per profile
+// of FILE, "<family> <profile name> <offset>"; the profiles are ordered by (family in order of first appearance, offset,
+// file order) and their hits reduced per (family, protein, diagonal) on the device (hs_pssm_family_scan): one line per
+// row with at least C [1] profiles in register whose scores add up to T [no such filter], "<family> <protein> <diag>
+// <blocks> <sum> <best profile> <best window offset> <best score> <lo> <hi>"; families in FAM order, proteins in
+// database order.  Refused: a profile of FILE missing from FAM, one named twice, an unknown name, a malformed line;
+// --pssm-top, --pssm-per-sequence, --pssm-compare, --pssm-pvalue-column, --pssm-refine, --pssm-rank or --pssm-pvalue
+// beside it; the two companion options without it; a C below 1; a T that is no finite number.
+// --pssm-compare self ... --pssm-families-out FAM: that file, written from the comparison's hits (hs_pssm_family_layout);
+// the family is named after its first profile; hits that contradict earlier ones are counted on stderr.  Refused
+// without --pssm-compare self.
 // --pssm-pvalue-column 1: every plain hit line gets " <p_hi>" appended, the upper end of the hit's p-value (hs_pssm_pvalue;
 // the grid's floor is the profile's threshold or --pssm-null-floor, whichever is lower); refused with --pssm-top and
 // --pssm-per-sequence.
@@ -79,6 +90,7 @@
 #include <iostream>
 #include <map>
 #include <random>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -134,6 +146,10 @@ const Opt kOpts[] = {
     {"pssm-compare-threshold", 'y', "with --pssm-compare: a pair is a hit when its best offset scores at least this", false},
     {"pssm-compare-overlap", 'z', "with --pssm-compare: the columns two profiles must share at an offset, 1..-l [1]", false},
     {"pssm-compare-columns", 'j', "with --pssm-compare: the column transform applied to both sides first: pearson, cosine or raw [pearson]", false},
+    {"pssm-families", 'F', "with --pssm: a file of '<family> <profile name> <offset>' lines, one per profile; instead of the hits, one line per (family, protein, diagonal): blocks in register, the sum of their scores, best block, span (one GPU)", false},
+    {"pssm-family-blocks", 'b', "with --pssm-families: report a row only when at least this many of the family's profiles hit on the diagonal, >= 1 [1]", false},
+    {"pssm-family-threshold", 'H', "with --pssm-families: report a row only when the scores on the diagonal add up to at least this [off]", false},
+    {"pssm-families-out", 'J', "with --pssm-compare self: also write the families the hits imply, one '<family> <profile name> <offset>' line per profile, the file --pssm-families reads", false},
     {"pssm-weights", 'w', "with --pssm-refine: weigh the sites with position-based sequence weights; the log-odds count 'sites' or 'columns' (distinct residues per column) as observations [off: every site counts 1]", false},
 };
 
@@ -240,14 +256,170 @@ int CompareMain(std::map<std::string, std::string>& val, const std::vector<std::
     if (!self) std::cout << " against " << names_y.size();
     std::cout << std::endl;
     const std::vector<double> t(names_x.size(), threshold);
-    uint64_t n_hits = 0;
+    uint64_t n_hits = 0, n_families = 0, n_conflicts = 0;
+    const bool families = val.count("pssm-families-out") != 0;
+    if (families && !self) {
+      fprintf(stderr, "ERROR: --pssm-families-out lays out the profiles of one file: it needs --pssm-compare self\n");
+      return EXIT_FAILURE;
+    }
     const int st = hsearch::CompareProfiles(kmer_length, names_x, X, t, self ? nullptr : &names_y, self ? nullptr : &Y,
-                                            overlap, columns, val["output"], device, &err, &n_hits);
+                                            overlap, columns, val["output"], device, &err, &n_hits,
+                                            families ? &val["pssm-families-out"] : nullptr, &n_families, &n_conflicts);
     if (st != 0) {
       fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), st);
       return EXIT_FAILURE;
     }
     std::cout << "number of hits " << n_hits << std::endl;
+    if (families) {
+      std::cout << "number of families " << n_families << std::endl;
+      if (n_conflicts) fprintf(stderr, "NOTE: %llu hits contradict the offsets fixed by earlier hits\n", (unsigned long long)n_conflicts);
+    }
+  } catch (const std::bad_alloc&) {
+    fprintf(stderr, "ERROR: could not allocate memory\n");
+    return EXIT_FAILURE;
+  } catch (const std::exception& e) {
+    fprintf(stderr, "%s\n", e.what());
+    return EXIT_FAILURE;
+  }
+  return EXIT_SUCCESS;
+}
+
+// --pssm FILE --pssm-families FAM: the profiles' hits per (family, protein, diagonal) (hsearch::FamilyScan)
+int FamilyMain(std::map<std::string, std::string>& val, const std::vector<std::string>& db_append) {
+  if (PssmRefused(val, db_append)) return EXIT_FAILURE;
+  for (const char* name : {"pssm-top", "pssm-per-sequence", "pssm-compare", "pssm-pvalue-column", "pssm-refine",
+                           "pssm-rank", "pssm-pvalue", "pssm-out", "pssm-null-floor", "pssm-families-out"})
+    if (val.count(name)) {
+      fprintf(stderr, "ERROR: --pssm-families reduces the hits per family: it cannot be combined with --%s\n", name);
+      return EXIT_FAILURE;
+    }
+  char* end = nullptr;
+  uint32_t blocks = 1;
+  if (val.count("pssm-family-blocks")) {
+    const std::string& text = val["pssm-family-blocks"];
+    const long long v = strtoll(text.c_str(), &end, 10);
+    if (text.empty() || end == text.c_str() || *end || v < 1 || v > 0xffffffffll) {
+      fprintf(stderr, "ERROR: --pssm-family-blocks takes a number of profiles, 1 or more\n");
+      return EXIT_FAILURE;
+    }
+    blocks = (uint32_t)v;
+  }
+  double threshold = 0.0;
+  const bool with_threshold = val.count("pssm-family-threshold") != 0;
+  if (with_threshold) {
+    const std::string& text = val["pssm-family-threshold"];
+    threshold = strtod(text.c_str(), &end);
+    if (text.empty() || end == text.c_str() || *end || !(fabs(threshold) <= 1.7976931348623157e308)) {
+      fprintf(stderr, "ERROR: --pssm-family-threshold takes a finite score\n");
+      return EXIT_FAILURE;
+    }
+  }
+  const uint32_t kmer_length = (uint32_t)strtoul(val["len"].c_str(), nullptr, 10);
+  const int device = val.count("device") ? atoi(val["device"].c_str()) : 0;
+  try {
+    if (!LooksLikeFasta(val["db"])) {
+      fprintf(stderr, "ERROR: --pssm needs a FASTA database: a points database holds no residues\n");
+      return EXIT_FAILURE;
+    }
+    std::vector<std::string> names;
+    std::vector<double> S, t;
+    std::string err;
+    if (!hsearch::ReadPssmFile(val["pssm"], kmer_length, &names, &S, &t, &err)) {
+      fprintf(stderr, "ERROR: %s\n", err.c_str());
+      return EXIT_FAILURE;
+    }
+    // FAM: every profile of FILE once, with its family and offset
+    const size_t nm = names.size();
+    std::map<std::string, size_t> index_of;
+    for (size_t m = 0; m < nm; ++m) index_of[names[m]] = m;
+    std::vector<std::string> family(nm), fam_order;
+    std::vector<uint32_t> offset(nm, 0);
+    std::vector<char> seen(nm, 0);
+    std::ifstream fam(val["pssm-families"].c_str());
+    if (!fam) {
+      fprintf(stderr, "ERROR: cannot open %s\n", val["pssm-families"].c_str());
+      return EXIT_FAILURE;
+    }
+    std::string line;
+    for (size_t ln = 1; std::getline(fam, line); ++ln) {
+      std::istringstream in(line);
+      std::string f, name, off, rest;
+      if (!(in >> f)) continue;  // an empty line
+      const bool three = bool(in >> name >> off) && !(in >> rest);
+      const unsigned long long v = three ? strtoull(off.c_str(), &end, 10) : 0;
+      if (!three || off[0] == '-' || end == off.c_str() || *end || v > 0x7fffffffull) {
+        fprintf(stderr, "ERROR: %s line %zu: expected '<family> <profile name> <offset>', the offset 0 .. 2^31 - 1\n",
+                val["pssm-families"].c_str(), ln);
+        return EXIT_FAILURE;
+      }
+      const auto it = index_of.find(name);
+      if (it == index_of.end()) {
+        fprintf(stderr, "ERROR: %s line %zu: %s names no profile of %s\n", val["pssm-families"].c_str(), ln,
+                name.c_str(), val["pssm"].c_str());
+        return EXIT_FAILURE;
+      }
+      if (seen[it->second]) {
+        fprintf(stderr, "ERROR: %s line %zu: profile %s is named twice\n", val["pssm-families"].c_str(), ln, name.c_str());
+        return EXIT_FAILURE;
+      }
+      seen[it->second] = 1;
+      family[it->second] = f;
+      offset[it->second] = (uint32_t)v;
+      if (std::find(fam_order.begin(), fam_order.end(), f) == fam_order.end()) fam_order.push_back(f);
+    }
+    for (size_t m = 0; m < nm; ++m)
+      if (!seen[m]) {
+        fprintf(stderr, "ERROR: profile %s of %s is missing from %s\n", names[m].c_str(), val["pssm"].c_str(),
+                val["pssm-families"].c_str());
+        return EXIT_FAILURE;
+      }
+    // by (family in order of first appearance, offset, file order)
+    std::map<std::string, size_t> fam_rank;
+    for (size_t i = 0; i < fam_order.size(); ++i) fam_rank[fam_order[i]] = i;
+    std::vector<size_t> order(nm);
+    for (size_t m = 0; m < nm; ++m) order[m] = m;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+      if (fam_rank[family[a]] != fam_rank[family[b]]) return fam_rank[family[a]] < fam_rank[family[b]];
+      if (offset[a] != offset[b]) return offset[a] < offset[b];
+      return a < b;
+    });
+    const size_t ka = (size_t)kmer_length * 20;
+    std::vector<std::string> names2(nm), family2(nm);
+    std::vector<double> S2(S.size()), t2(nm);
+    std::vector<uint32_t> offset2(nm);
+    for (size_t i = 0; i < nm; ++i) {
+      const size_t m = order[i];
+      names2[i] = names[m];
+      family2[i] = family[m];
+      offset2[i] = offset[m];
+      t2[i] = t[m];
+      std::copy(S.begin() + m * ka, S.begin() + (m + 1) * ka, S2.begin() + i * ka);
+    }
+    hsearch::ProteinDB prodb;
+    std::cout << "Read protein sequences from " << val["db"] << std::endl;
+    const bool swap = val.count("ref-compat-eq-swap") && atoi(val["ref-compat-eq-swap"].c_str()) != 0;
+    if (!hsearch::ReadProteinFasta(val["db"], swap, &prodb)) {
+      fprintf(stderr, "cannot open %s\n", val["db"].c_str());
+      return EXIT_FAILURE;
+    }
+    std::cout << "number of proteins " << prodb.start.size() - 1 << std::endl;
+    std::cout << "total length " << prodb.residues.size() << std::endl;
+    std::cout << "number of profiles " << nm << " in " << fam_order.size() << " families" << std::endl;
+    struct timespec t0, t1;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    uint64_t n_windows = 0, n_hits = 0, n_rows = 0;
+    const int st = hsearch::FamilyScan(prodb, kmer_length, names2, S2, t2, family2, offset2, blocks,
+                                       with_threshold ? &threshold : nullptr, val["output"], device, &err, &n_windows,
+                                       &n_hits, &n_rows);
+    if (st != 0) {
+      fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), st);
+      return EXIT_FAILURE;
+    }
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    std::cout << "number of kmers " << n_windows << std::endl;
+    std::cout << "number of hits " << n_hits << std::endl;
+    std::cout << "number of rows " << n_rows << std::endl;
+    printf("SCAN: %lf seconds\n", (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec));
   } catch (const std::bad_alloc&) {
     fprintf(stderr, "ERROR: could not allocate memory\n");
     return EXIT_FAILURE;
@@ -544,6 +716,20 @@ int main(int argc, const char* argv[]) {
       fprintf(stderr, "ERROR: --%s belongs to --pssm-compare: it cannot be given without it\n", name);
       return EXIT_FAILURE;
     }
+  const bool with_families = val.count("pssm-families") != 0;
+  if (with_families && !with_pssm) {
+    fprintf(stderr, "ERROR: --pssm-families groups the profiles of --pssm FILE: it cannot be given without it\n");
+    return EXIT_FAILURE;
+  }
+  for (const char* name : {"pssm-family-blocks", "pssm-family-threshold"})
+    if (val.count(name) && !with_families) {
+      fprintf(stderr, "ERROR: --%s belongs to --pssm-families: it cannot be given without it\n", name);
+      return EXIT_FAILURE;
+    }
+  if (val.count("pssm-families-out") && !with_compare) {
+    fprintf(stderr, "ERROR: --pssm-families-out belongs to --pssm-compare self: it cannot be given without it\n");
+    return EXIT_FAILURE;
+  }
   if (val.count("pssm-rank") && !with_pssm) {
     fprintf(stderr, "ERROR: --pssm-rank sets the thresholds of --pssm FILE: it cannot be given without it\n");
     return EXIT_FAILURE;
@@ -565,6 +751,7 @@ int main(int argc, const char* argv[]) {
       Help(argv[0]);
       return EXIT_SUCCESS;  // as the reference: option_missing() -> message, EXIT_SUCCESS
     }
+  if (with_families) return FamilyMain(val, db_append);
   if (with_compare) return CompareMain(val, db_append);
   if (with_pssm) return PssmMain(val, db_append);
   const bool with_radii = val.count("radii") != 0;

@@ -116,6 +116,8 @@ typedef struct hs_profile {
   uint64_t pssm_dead;          /* ... profiles skipped because no k-mer can reach their threshold (filter on only) */
   uint64_t pssm_mfma_steps;    /* ... MFMA depth steps per 16 x 16 tile: ceil(k * alphabet / 128) (0: filter off) */
   uint64_t pssm_seq_rows;      /* hs_pssm_seq_scan*: the (profile, sequence) rows the call found (its *n_out) */
+  uint64_t pssm_fam_rows;      /* hs_pssm_family_scan*: the (family, sequence, diagonal) rows before the row filters */
+  uint64_t pssm_fam_kept;      /* ... of which this many passed min_count and t_group (the call's *n_out) */
   uint64_t pssm_count_sites;   /* hs_pssm_hit_counts*: the sites counted, the sum of used[] */
   uint64_t pssm_count_items;   /* hs_pssm_hit_counts*: the (profile run, chunk) work items of the counting kernel */
   uint64_t pssm_weight_sites;  /* hs_pssm_weighted_counts*: the sites weighted (pssm_count_sites; 0 after other calls) */
@@ -1344,8 +1346,8 @@ HS_API hs_status hs_pssm_topk_hits(const uint32_t* m, const uint32_t* id, const 
  * list on the handle, no merge.  Scratch is sized by a batch's hits and rows.
  * hs_profile after the call: the pssm_* fields as after a scan, pssm_seq_rows, hits; ms_finalize covers the exact
  * pass, the sort and the reduction.  Every other entry point runs as before, launch for launch.
- * Out of scope: diagonals and query groups for profiles, top-N per (profile, protein), multi-GPU drivers
- * (hs_pssm_seq_hits is the merge). */
+ * Out of scope: top-N per (profile, protein), multi-GPU drivers (hs_pssm_seq_hits is the merge).  Diagonals and
+ * groups for profiles: hs_pssm_family_scan. */
 HS_API hs_status hs_pssm_seq_scan(hs_handle* h, const double* S, const double* t, uint64_t nm,
                                   const uint64_t* id_start, uint64_t n_seq, uint32_t* out_m, uint32_t* out_seq,
                                   uint32_t* out_count, double* out_best_score, uint32_t* out_best_id, uint32_t* out_lo,
@@ -1366,6 +1368,105 @@ HS_API hs_status hs_pssm_seq_hits(const uint32_t* m, const uint32_t* id, const d
                                   uint64_t nm, const uint64_t* id_start, uint64_t n_seq, uint32_t* out_m,
                                   uint32_t* out_seq, uint32_t* out_count, double* out_best_score, uint32_t* out_best_id,
                                   uint32_t* out_lo, uint32_t* out_hi, uint64_t cap, uint64_t* n_out);
+
+/* ---- PSSM families: the hits of related profiles reduced per family, sequence and diagonal ---------------------- */
+
+/* A motif longer than k, or a protein family described by ordered blocks at fixed spacing, is several profiles.  Each
+ * is scanned at a permissive threshold; a protein counts when several of them hit in register -- on one diagonal --
+ * and their scores add up to a family threshold.  hs_seq_match does this reduction for k-mer queries; this is its
+ * counterpart for profiles.  The hit list, large at permissive thresholds, never crosses PCIe.
+ *
+ * Underlying hits: S, t, the score and the hit rule are hs_pssm_scan's, bit for bit; H is the hit list hs_pssm_scan
+ * returns for the same arguments on the same handle.  id_start [n_seq + 1] follows hs_pssm_seq_scan's rules (an id at
+ * equal neighbours belongs to the LAST sequence that starts at or below it).
+ * Key of a hit (m, id): g = m_group[m] (m_group == NULL: g = m, and n_groups must equal nm); s = the sequence that
+ * owns id; off = id - id_start[s]; diag = off - m_off[m] as a signed number, of which out_diag holds the low 32 bits.
+ * m_off == NULL: no diagonals are kept, diag is 0 for every hit (as in hs_seq_match).
+ * Rows: one per distinct (g, s, diag) of H, ascending in that order (diag as the signed number).
+ *   out_count       the row's hits.  On a diagonal a profile contributes at most one hit to a row, so with m_off given
+ *                   the count is the number of the family's profiles that hit in register.
+ *   out_sum         the sum of the row's hit_score: it starts from +0.0, the hits are added in ascending (m, id)
+ *                   order, every partial sum is rounded to fp64; no FMA, no re-association.  The order is part of
+ *                   the contract.
+ *   out_best_score, out_best_m, out_best_id   the best hit under (score descending, m ascending, id ascending),
+ *                   through the key transform of hsearch_amd/csrc/hs_pssm_topk.h; the score keeps the hit's bits.
+ *   out_lo, out_hi  the smallest and the largest off among the row's hits.
+ * Row filters, applied on the device: a row is reported iff count >= min_count and (t_group == NULL or
+ * sum >= t_group[g]); t_group [n_groups].  *n_out, the capacity protocol and grp_rows [n_groups] (may be NULL: the
+ * reported rows per group) count reported rows only.  *n_hits and cnt [nm] (may be NULL) are the scan's.
+ * Capacity: counted in reported rows, the two-call pattern of hs_pssm_seq_scan: HS_ERR_CAPACITY comes with *n_out set
+ * (cap = 0 with NULL arrays asks for the count); cnt and grp_rows are valid then.  hs_pssm_family_scan writes no row
+ * then; the _dev form may have written the rows of the batches that still fitted.
+ * Groups and batches: m_group must not decrease (a family's profiles are passed next to each other; a group may be
+ * empty) and a group holds at most 4096 profiles, the scan's default batch.  Batches are cut at group starts, so every
+ * row lies in one batch and the batches' rows follow one another in output order.  HS_OPT_QUERY_BATCH below a group's
+ * size is raised to that group for the batch that holds it.  A batch whose survivors overflow the counter runs again
+ * in smaller batches, still cut at group starts; a single group that overflows on its own is HS_ERR_CAPACITY with the
+ * cause in hs_last_error, *n_out = 0, and nothing written by the host form.
+ * Key width (hs_seq_match's rule): bits(n_groups - 1) + bits(n_seq - 1) + bits(max_len + max_off - 1) <= 64, where
+ * max_len is the most ids of one sequence and max_off the largest m_off (0 without m_off); n_groups and n_seq are at
+ * most 2^32, an m_off at most 2^31 - 1.
+ * Errors, reported before anything is written: everything hs_pssm_scan and hs_pssm_seq_scan refuse; an m_group that
+ * decreases or holds a value >= n_groups; a group above 4096 profiles; n_groups != nm with m_group == NULL;
+ * min_count == 0; a NaN or infinite t_group entry; an m_off above 2^31 - 1; the width rule; null outputs with
+ * cap > 0.  All HS_ERR_INVALID but the unbuilt index (HS_ERR_STATE).  The _dev form finds the value errors on the
+ * device: the scan's reduction over the profiles, hs_seq_match's over m_group, m_off and id_start, one more over the
+ * family arguments, and one read-back (which also brings m_group, nm words, for the cut points).
+ * Purity: the rows are a pure function of (codes, S, t, m_group, m_off, id_start, min_count, t_group).  The profile
+ * batch, HS_OPT_PSSM_FILTER, survivor splits and scheduling do not show in them.
+ *
+ * How (hsearch_amd/csrc/hs_pssm_family.hip): per batch, after the scan's own (m, id) sort, the sequence of every hit
+ * (hs_pssm_seq.hip's search), a 64-bit row key, one stable radix sort of (row key, hit index), run heads and their
+ * scan, one lane per row walking its run in order, the filters, a scan of their flags, and the kept rows written at the
+ * call's running offset.  A row of L hits costs L dependent fp64 adds in one lane: the order of the sum is kept.
+ * hs_profile after the call: the pssm_* fields as after a scan, hits, pssm_fam_rows (rows before the filters),
+ * pssm_fam_kept (*n_out); ms_finalize covers the exact pass, the sorts and the reduction.  Every other entry point
+ * runs as before, launch for launch.
+ * Out of scope: chains with variable spacing between blocks, groups that span batches, multi-GPU drivers
+ * (hs_pssm_family_hits is the merge), per-row p-values. */
+HS_API hs_status hs_pssm_family_scan(hs_handle* h, const double* S, const double* t, uint64_t nm,
+                                     const uint32_t* m_group, uint64_t n_groups, const uint32_t* m_off,
+                                     const uint64_t* id_start, uint64_t n_seq, uint32_t min_count,
+                                     const double* t_group, uint32_t* out_group, uint32_t* out_seq, int32_t* out_diag,
+                                     uint32_t* out_count, double* out_sum, double* out_best_score,
+                                     uint32_t* out_best_m, uint32_t* out_best_id, uint32_t* out_lo, uint32_t* out_hi,
+                                     uint64_t cap, uint64_t* n_out, uint64_t* n_hits, uint64_t* cnt,
+                                     uint64_t* grp_rows);
+/* ... every pointer but n_out / n_hits in device memory (streams: as hs_pssm_scan_dev) */
+HS_API hs_status hs_pssm_family_scan_dev(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm,
+                                         const uint32_t* d_m_group, uint64_t n_groups, const uint32_t* d_m_off,
+                                         const uint64_t* d_id_start, uint64_t n_seq, uint32_t min_count,
+                                         const double* d_t_group, uint32_t* d_out_group, uint32_t* d_out_seq,
+                                         int32_t* d_out_diag, uint32_t* d_out_count, double* d_out_sum,
+                                         double* d_out_best_score, uint32_t* d_out_best_m, uint32_t* d_out_best_id,
+                                         uint32_t* d_out_lo, uint32_t* d_out_hi, uint64_t cap, uint64_t* n_out,
+                                         uint64_t* n_hits, uint64_t* d_cnt, uint64_t* d_grp_rows);
+/* The same rule on the host (no GPU, no handle) over any list of (m, id, score) tuples in any order: the merge of
+ * several GPUs' hit lists and the reference the device is held to.  A repeated (m, id) with equal score bits counts
+ * once, with different bits it is HS_ERR_INVALID.  The other refusals are hs_pssm_seq_hits' and the family arguments'
+ * above (id_start's end is not compared with an index here).  A score of -0.0 in a tuple is read as +0.0 (no scan
+ * produces it), so for such a tuple out_best_score does not keep the sign bit.  HS_ERR_CAPACITY: *n_out set, no row
+ * written. */
+HS_API hs_status hs_pssm_family_hits(const uint32_t* m, const uint32_t* id, const double* score, uint64_t n_tuples,
+                                     uint64_t nm, const uint32_t* m_group, uint64_t n_groups, const uint32_t* m_off,
+                                     const uint64_t* id_start, uint64_t n_seq, uint32_t min_count,
+                                     const double* t_group, uint32_t* out_group, uint32_t* out_seq, int32_t* out_diag,
+                                     uint32_t* out_count, double* out_sum, double* out_best_score,
+                                     uint32_t* out_best_m, uint32_t* out_best_id, uint32_t* out_lo, uint32_t* out_hi,
+                                     uint64_t cap, uint64_t* n_out);
+/* The grouping call over hs_pssm_compare's self-mode hits (host only): families and offsets for hs_pssm_family_scan.
+ * A hit (x, y, d) follows hs_pssm_compare's convention -- column p of Y meets column p + d of X, so Y lies d to the
+ * right of X: pos[y] - pos[x] = d.  The hits are taken in the given order through a union-find that carries a position
+ * relative to the root: a hit that joins two components fixes that distance; a hit inside one component that disagrees
+ * with the positions already fixed is counted in *n_conflicts and changes nothing.  Components are numbered by their
+ * smallest member, ascending (*n_groups of them; a profile without hits is a group of one).  out_group [nm];
+ * out_off [nm] = pos[m] minus its component's minimum; out_order [nm] = the profiles sorted by (group, off, m): the
+ * order in which to pass them to the scan.  The result depends on the order of the hits; hs_pssm_compare's (x, y)
+ * ascending order makes it canonical.  HS_ERR_INVALID, before anything is written: x == y, an index >= nm,
+ * |d| >= 2^30, an offset that passes 2^31 - 1, a component above 4096 members, a null array that is needed. */
+HS_API hs_status hs_pssm_family_layout(const uint32_t* hit_x, const uint32_t* hit_y, const int32_t* hit_d,
+                                       uint64_t n_hits, uint64_t nm, uint32_t* out_group, uint32_t* out_off,
+                                       uint32_t* out_order, uint64_t* n_groups, uint64_t* n_conflicts);
 
 /* ---- PSSM hit counts and refinement: from a profile's hits back to a profile ------------------------------------- */
 
