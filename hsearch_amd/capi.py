@@ -46,7 +46,8 @@ EXPORTS = ["hs_create", "hs_destroy", "hs_last_error", "hs_get_profile", "hs_get
            "hs_cluster_pssm_cover_dev", "hs_cluster_weights_codes", "hs_cluster_cover_codes",
            "hs_pssm_compare", "hs_pssm_compare_dev", "hs_pssm_compare_host", "hs_pssm_compare_tables",
            "hs_pssm_compare_pass", "hs_pssm_compare_columns", "hs_pssm_family_scan", "hs_pssm_family_scan_dev",
-           "hs_pssm_family_hits", "hs_pssm_family_layout"]
+           "hs_pssm_family_hits", "hs_pssm_family_layout", "hs_pssm_family_chain", "hs_pssm_family_chain_dev",
+           "hs_pssm_family_chain_hits"]
 
 TOPK_MAX = 64        # HS_TOPK_MAX: the widest row of query_topk / self_knn / topk_merge
 NO_ID = 0xffffffff   # the id and table of an unused entry of such a row (its distance is +inf)
@@ -81,7 +82,8 @@ class _Profile(C.Structure):
                 ("remove_dead_buckets", C.c_uint64), ("remove_retupled", C.c_uint64),
                 ("pssm_pairs", C.c_uint64), ("pssm_survivors", C.c_uint64), ("pssm_dead", C.c_uint64),
                 ("pssm_mfma_steps", C.c_uint64), ("pssm_seq_rows", C.c_uint64), ("pssm_fam_rows", C.c_uint64),
-                ("pssm_fam_kept", C.c_uint64), ("pssm_count_sites", C.c_uint64),
+                ("pssm_fam_kept", C.c_uint64), ("pssm_chain_segs", C.c_uint64), ("pssm_chain_kept", C.c_uint64),
+                ("pssm_count_sites", C.c_uint64),
                 ("pssm_count_items", C.c_uint64), ("pssm_weight_sites", C.c_uint64),
                 ("pssm_weight_items", C.c_uint64), ("pssm_null_bins", C.c_uint64),
                 ("pssm_null_profiles", C.c_uint64), ("summary_weight_rows", C.c_uint64),
@@ -376,6 +378,20 @@ def load(hooks=False):
             lib.hs_pssm_family_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                                   C.POINTER(C.c_uint64)]
+        # PSSM family chains: the family scan's arguments with (max_shift, gap_open, gap_ext) in front of min_count;
+        # hits: ..., 10 row arrays, cap, &n_out, path_start, path_m, path_id, path_cap, &n_path
+        if hasattr(lib, "hs_pssm_family_chain"):
+            rows10 = [C.c_void_p] * 10
+            chain = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, C.c_double,
+                     C.c_uint32, C.c_void_p]
+            for fn in (lib.hs_pssm_family_chain, lib.hs_pssm_family_chain_dev):
+                fn.restype = C.c_int
+                fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64] + chain + rows10 + [
+                    C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]
+            lib.hs_pssm_family_chain_hits.restype = C.c_int
+            lib.hs_pssm_family_chain_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64] + \
+                chain + rows10 + [C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                  C.POINTER(C.c_uint64)]
         # PSSM hit counts: (h, S, t, nm, id_start, n_seq, counts, cnt, used, &n_hits); refine, count_hits, log_odds,
         # background: include/hsearch.h
         if hasattr(lib, "hs_pssm_hit_counts"):
@@ -1121,6 +1137,60 @@ def pssm_family_hits(m, id, score, nm, id_start, m_group=None, n_groups=None, m_
         e.needed = int(n_out.value)
         raise e
     return _pssm_family_dict(arrs, int(n_out.value))
+
+
+PSSM_CHAIN_FIELDS = (("group", np.uint32), ("seq", np.uint32), ("count", np.uint32), ("gaps", np.uint32),
+                     ("score", np.float64), ("first_m", np.uint32), ("first_id", np.uint32), ("last_m", np.uint32),
+                     ("last_id", np.uint32), ("shift", np.int32))
+
+
+def _pssm_chain_rows(cap):
+    return [np.empty(cap, dtype=t) for _, t in PSSM_CHAIN_FIELDS]
+
+
+def _pssm_chain_dict(arrs, n):
+    return {name: a[:n] for (name, _), a in zip(PSSM_CHAIN_FIELDS, arrs)}
+
+
+def _pssm_chain_vals(vals, max_shift, gap_open, gap_ext):
+    """_pssm_family_args' values with the chain's three in front of min_count (the C order)"""
+    return vals[:5] + [C.c_uint32(int(max_shift)), C.c_double(float(gap_open)), C.c_double(float(gap_ext))] + vals[5:]
+
+
+def pssm_family_chain_hits(m, id, score, nm, id_start, m_group, m_off, max_shift, gap_open=0.0, gap_ext=0.0,
+                           min_count=1, t_group=None, n_groups=None, cap=None, out=None, want_path=False,
+                           path_cap=None):
+    """hs_pssm_family_chain_hits (host only, no GPU): the rule of Engine.pssm_family_chain over ANY list of hits (m,
+    id, score) in any order -- per (family, sequence) the best gapped chain that passes the filters: dict(group, seq,
+    count, gaps, score, first_m, first_id, last_m, last_id, shift).  want_path: also path_start [rows + 1], path_m,
+    path_id, the chains' hits from first to last.  cap / path_cap=None: as much room as can be needed; a given one that
+    is too small raises HsError(HS_ERR_CAPACITY) with the required sizes in .needed and .needed_path."""
+    m = np.ascontiguousarray(m, dtype=np.uint32).ravel()
+    id = np.ascontiguousarray(id, dtype=np.uint32).ravel()
+    score = np.ascontiguousarray(score, dtype=np.float64).ravel()
+    n = len(m)
+    assert id.shape == score.shape == (n,)
+    keep, vals, _ = _pssm_family_args(int(nm), m_group, n_groups, m_off, id_start, min_count, t_group)
+    vals = _pssm_chain_vals(vals, max_shift, gap_open, gap_ext)
+    room = n if cap is None else int(cap)
+    arrs = _pssm_chain_rows(room) if out is None else out
+    n_out, n_path = C.c_uint64(0), C.c_uint64(0)
+    proom = (n if path_cap is None else int(path_cap)) if want_path else 0
+    pstart = np.empty(room + 1, dtype=np.uint64) if want_path else None
+    pm, pid = (np.empty(max(proom, 1), dtype=np.uint32) for _ in range(2)) if want_path else (None, None)
+    st = load().hs_pssm_family_chain_hits(_vp(m), _vp(id), _vp(score), n, int(nm), *vals, *[_vp(a) for a in arrs], room,
+                                          C.byref(n_out), _vp(pstart) if want_path else None,
+                                          _vp(pm) if want_path else None, _vp(pid) if want_path else None, proom,
+                                          C.byref(n_path) if want_path else None)
+    if st != HS_OK:
+        e = HsError(st, "hs_pssm_family_chain_hits")
+        e.needed, e.needed_path = int(n_out.value), int(n_path.value)
+        raise e
+    res = _pssm_chain_dict(arrs, int(n_out.value))
+    if want_path:
+        res["path_start"] = pstart[:int(n_out.value) + 1]
+        res["path_m"], res["path_id"] = pm[:int(n_path.value)], pid[:int(n_path.value)]
+    return res
 
 
 def pssm_family_layout(hit_x, hit_y, hit_d, nm):
@@ -2345,6 +2415,69 @@ class Engine:
                                                d_t_group if d_t_group else None, *[p if p else None for p in d_rows],
                                                int(cap), C.byref(n), C.byref(nh), d_cnt if d_cnt else None,
                                                d_grp_rows if d_grp_rows else None)
+        if st == HS_ERR_CAPACITY:
+            e = HsError(st, self._lib.hs_last_error(self._h).decode())
+            e.needed, e.n_hits = int(n.value), int(nh.value)
+            raise e
+        self._check(st)
+        return int(n.value), int(nh.value)
+
+    def pssm_family_chain(self, S, t, id_start, m_group, m_off, max_shift, gap_open=0.0, gap_ext=0.0, min_count=1,
+                          t_group=None, cap=None, want_counts=True, n_groups=None):
+        """hs_pssm_family_chain: the hits of pssm_scan(S, t) linked on the device into the best gapped chain per
+        (family, database sequence): dict(group, seq, count, gaps, score, first_m, first_id, last_m, last_id, shift --
+        at most one row per (group, seq), ascending --, n_hits[, cnt [nm] the hits per profile and grp_rows [n_groups]
+        the reported rows per family]).  m_group [nm] non-decreasing (None: every profile its own family); m_off [nm],
+        required, non-decreasing inside a family; hits of later profiles at later offsets link when their diagonals
+        differ by d <= max_shift, at the cost gap_open + gap_ext * d for d >= 1; a chain is reported iff it holds
+        min_count blocks and its score reaches t_group[group] (None: no score filter).  cap=None: two calls, the row
+        count then the rows; a given cap that is too small raises HsError(HS_ERR_CAPACITY) with .needed, .n_hits and,
+        with want_counts, .cnt and .grp_rows."""
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        nm = S.shape[0]
+        assert S.shape == (nm, self.k, self._alphabet()) and t.shape == (nm,), (S.shape, t.shape)
+        keep, vals, n_groups = _pssm_family_args(nm, m_group, n_groups, m_off, id_start, min_count, t_group)
+        vals = _pssm_chain_vals(vals, max_shift, gap_open, gap_ext)
+        cnt = np.zeros(nm, dtype=np.uint64) if want_counts else None
+        grp_rows = np.zeros(n_groups, dtype=np.uint64) if want_counts else None
+        room = 0 if cap is None else int(cap)
+        while True:
+            arrs = _pssm_chain_rows(room)
+            n, nh = C.c_uint64(0), C.c_uint64(0)
+            st = self._lib.hs_pssm_family_chain(self._h, _vp(S), _vp(t), nm, *vals,
+                                                *[_vp(a) if room else None for a in arrs], room, C.byref(n),
+                                                C.byref(nh), _vp(cnt) if want_counts else None,
+                                                _vp(grp_rows) if want_counts else None)
+            if st == HS_ERR_CAPACITY:
+                if cap is None and int(n.value) > room:
+                    room = int(n.value)
+                    continue
+                e = HsError(st, self._lib.hs_last_error(self._h).decode())
+                e.needed, e.n_hits, e.cnt, e.grp_rows = int(n.value), int(nh.value), cnt, grp_rows
+                raise e
+            self._check(st)
+            res = _pssm_chain_dict(arrs, int(n.value))
+            res["n_hits"] = int(nh.value)
+            if want_counts:
+                res["cnt"], res["grp_rows"] = cnt, grp_rows
+            return res
+
+    def pssm_family_chain_dev(self, d_S, d_t, nm, d_m_group, n_groups, d_m_off, d_id_start, n_seq, max_shift, gap_open,
+                              gap_ext, min_count, d_t_group, d_rows, cap, d_cnt=None, d_grp_rows=None):
+        """hs_pssm_family_chain_dev: device pointers (ints, e.g. tensor.data_ptr(); d_m_group, d_t_group, d_cnt and
+        d_grp_rows may be None; d_rows: the ten row arrays in the order of capi.PSSM_CHAIN_FIELDS).  Returns (rows,
+        n_hits); raises HsError(HS_ERR_CAPACITY) with the required size in .needed and the hit count in .n_hits when
+        cap is too small."""
+        n, nh = C.c_uint64(0), C.c_uint64(0)
+        st = self._lib.hs_pssm_family_chain_dev(self._h, d_S if d_S else None, d_t if d_t else None, int(nm),
+                                                d_m_group if d_m_group else None, int(n_groups),
+                                                d_m_off if d_m_off else None, d_id_start if d_id_start else None,
+                                                int(n_seq), C.c_uint32(int(max_shift)), C.c_double(float(gap_open)),
+                                                C.c_double(float(gap_ext)), C.c_uint32(int(min_count)),
+                                                d_t_group if d_t_group else None, *[p if p else None for p in d_rows],
+                                                int(cap), C.byref(n), C.byref(nh), d_cnt if d_cnt else None,
+                                                d_grp_rows if d_grp_rows else None)
         if st == HS_ERR_CAPACITY:
             e = HsError(st, self._lib.hs_last_error(self._h).decode())
             e.needed, e.n_hits = int(n.value), int(nh.value)

@@ -622,6 +622,7 @@ void hs_destroy(hs_handle* h) {
                     &h->sq_key, &h->sq_idx, &h->sq_skey, &h->sq_sidx, &h->sq_head, &h->sq_excl, &h->sq_part, &h->sq_acc,
                     &h->sq_fin, &h->sq_chk, &h->sq_in, &h->sq_out,
                     &h->pf_sidx, &h->pf_start, &h->pf_rows, &h->pf_keep, &h->pf_pos, &h->pf_in,
+                    &h->pch_state, &h->pch_rows,
                     &h->sm_size, &h->sm_tmp, &h->sm_row_of, &h->sm_off_of,
                     &h->sm_row_label, &h->sm_row_off, &h->sm_member, &h->sm_d2, &h->sm_err, &h->sm_counts,
                     &h->sm_io_label, &h->sm_io_a, &h->sm_io_b, &h->sm_io_counts, &h->sm_io_f64, &h->sm_io_f64b};

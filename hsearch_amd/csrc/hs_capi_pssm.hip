@@ -4,6 +4,7 @@
 //   hs_pssm_scan / _dev                  every hit (m, id, score) at the caller's thresholds        (hs_pssm.hip)
 //   hs_pssm_seq_scan / _dev              the hits reduced per (profile, sequence)                   (hs_pssm_seq.hip)
 //   hs_pssm_family_scan / _dev           the hits reduced per (family, sequence, diagonal)          (hs_pssm_family.hip)
+//   hs_pssm_family_chain / _dev          the best gapped chain per (family, sequence)               (hs_pssm_chain.hip)
 //   hs_pssm_hit_counts / _dev            the position frequency matrices of the hits                (hs_pssm_counts.hip)
 //   hs_pssm_weighted_counts / _dev       ... with position-based sequence weights                   (hs_pssm_weights.hip)
 //   hs_pssm_refine_weighted              the refine loop on weighted counts, under either threshold rule
@@ -22,17 +23,20 @@
 //                     what a call refuses: from its arguments, and from its values on the host or on the device
 //   pssm_stage_in     S and a per-profile array of a host-pointer call on their way up
 //   pssm_batch        one batch of profiles through the tables, the FP6 MFMA filter and the exact pass
-//   pssm_batch_loop   the call's profiles cut into batches by the call's rule (the fixed stride; group starts for
-//                     hs_pssm_family_scan), a batch halved when its survivors overflow; a step before
+//   pssm_batch_loop   the call's profiles cut into batches by the call's rule (the fixed stride; group starts,
+//                     pssm_family_cut, for hs_pssm_family_scan and hs_pssm_family_chain), a batch halved when its survivors overflow; a step before
 //                     each scan and a sink after it.  pssm_call_end closes the call's profile; pssm_batches is the
 //                     two together for the calls that scan at thresholds given
 //   pssm_row_pass     a batch's hits reduced to (profile, sequence) rows
+//   pssm_family_args, pssm_family_refuse, pssm_family_dev_check / pssm_family_host_check, pssm_family_stage
+//                     the two family calls' refusals, their cut points, and a host-pointer call's arrays on their way up
 //   pssm_refine       the refine loop under either threshold rule
 #include <vector>
 
 #include "hs_handle.h"
 #include "hs_pssm_tables.h"
 #include "hs_pssm_seq.h"
+#include "hs_pssm_chain.h"
 #include "hs_pssm_family.h"
 #include "hs_pssm_counts.h"
 #include "hs_pssm_weights.h"
@@ -424,32 +428,45 @@ std::vector<uint32_t> pssm_family_cuts(const uint32_t* m_group, uint64_t nm) {
   return cuts;
 }
 
-// what both forms refuse from the arguments alone (hs_pssm_seq_scan's refusals first)
-hs_status pssm_family_args(hs_handle* h, const void* S, const void* t, uint64_t nm, bool has_group, uint64_t n_groups,
-                           const void* id_start, uint64_t n_seq, uint32_t min_count, const HsFamilyOut& out,
+// what both forms refuse from the arguments alone (hs_pssm_seq_scan's refusals first); name: the call, for the texts
+hs_status pssm_family_args(hs_handle* h, const char* name, const void* S, const void* t, uint64_t nm, bool has_group,
+                           uint64_t n_groups, const void* id_start, uint64_t n_seq, uint32_t min_count, bool out_all,
                            uint64_t cap) {
-  HS_CHECK(pssm_args_start(h, nm, S && t ? nullptr : "hs_pssm_family_scan: S or t is null"));
-  if (cap && !out.all()) return fail(h, HS_ERR_INVALID, "an output array is null");
-  if (!id_start) return fail(h, HS_ERR_INVALID, "hs_pssm_family_scan: id_start is null");
-  if (n_seq > (1ull << 32)) return fail(h, HS_ERR_INVALID, "hs_pssm_family_scan: more than 2^32 sequences");
-  if (!n_seq && h->n) return fail(h, HS_ERR_INVALID, "hs_pssm_family_scan: no sequence owns the index's k-mers");
-  if (min_count < 1) return fail(h, HS_ERR_INVALID, "hs_pssm_family_scan: min_count must be at least 1");
-  if (n_groups > (1ull << 32)) return fail(h, HS_ERR_INVALID, "hs_pssm_family_scan: more than 2^32 groups");
-  if (!has_group && n_groups != nm)
-    return fail(h, HS_ERR_INVALID, "hs_pssm_family_scan: without m_group n_groups must equal nm");
+  const std::string at = std::string(name) + ": ";
+  const std::string null_text = at + "S or t is null";
+  HS_CHECK(pssm_args_start(h, nm, S && t ? nullptr : null_text.c_str()));
+  if (cap && !out_all) return fail(h, HS_ERR_INVALID, "an output array is null");
+  if (!id_start) return fail(h, HS_ERR_INVALID, at + "id_start is null");
+  if (n_seq > (1ull << 32)) return fail(h, HS_ERR_INVALID, at + "more than 2^32 sequences");
+  if (!n_seq && h->n) return fail(h, HS_ERR_INVALID, at + "no sequence owns the index's k-mers");
+  if (min_count < 1) return fail(h, HS_ERR_INVALID, at + "min_count must be at least 1");
+  if (n_groups > (1ull << 32)) return fail(h, HS_ERR_INVALID, at + "more than 2^32 groups");
+  if (!has_group && n_groups != nm) return fail(h, HS_ERR_INVALID, at + "without m_group n_groups must equal nm");
   return HS_OK;
 }
 
-// the value errors of the family arguments (HS_FAM_BAD_* bits) and the width rule, after the scan's own refusals
-hs_status pssm_family_refuse(hs_handle* h, uint32_t bad, uint64_t max_len, PssmFamily* f) {
-  if (bad & HS_FAM_BAD_GROUP_ORDER) return fail(h, HS_ERR_INVALID, "hs_pssm_family_scan: m_group must not decrease");
-  if (bad & HS_FAM_BAD_GROUP_VALUE) return fail(h, HS_ERR_INVALID, "hs_pssm_family_scan: a group is >= n_groups");
-  if (bad & HS_FAM_BAD_GROUP_SIZE) return fail(h, HS_ERR_INVALID, "hs_pssm_family_scan: a group holds more than 4096 profiles");
-  if (bad & HS_FAM_BAD_OFF) return fail(h, HS_ERR_INVALID, "hs_pssm_family_scan: an m_off is above 2^31 - 1");
-  if (bad & HS_FAM_BAD_T_GROUP) return fail(h, HS_ERR_INVALID, "hs_pssm_family_scan: a t_group entry is NaN or infinite");
+// the value errors of the family arguments (HS_FAM_BAD_* bits; HS_FAM_BAD_OFF_ORDER only where the caller passes it
+// on) and the width rule, after the scan's own refusals
+hs_status pssm_family_refuse(hs_handle* h, const char* name, uint32_t bad, uint64_t max_len, PssmFamily* f) {
+  const std::string at = std::string(name) + ": ";
+  if (bad & HS_FAM_BAD_GROUP_ORDER) return fail(h, HS_ERR_INVALID, at + "m_group must not decrease");
+  if (bad & HS_FAM_BAD_GROUP_VALUE) return fail(h, HS_ERR_INVALID, at + "a group is >= n_groups");
+  if (bad & HS_FAM_BAD_GROUP_SIZE) return fail(h, HS_ERR_INVALID, at + "a group holds more than 4096 profiles");
+  if (bad & HS_FAM_BAD_OFF) return fail(h, HS_ERR_INVALID, at + "an m_off is above 2^31 - 1");
+  if (bad & HS_FAM_BAD_T_GROUP) return fail(h, HS_ERR_INVALID, at + "a t_group entry is NaN or infinite");
+  if (bad & HS_FAM_BAD_OFF_ORDER) return fail(h, HS_ERR_INVALID, at + "m_off decreases inside a group");
   if (!hs_pssm_family_widths(f->n_groups, f->n_seq, max_len, f->max_off, &f->wg, &f->ws, &f->wd))
-    return fail(h, HS_ERR_INVALID, "hs_pssm_family_scan: group, sequence and diagonal do not fit a 64-bit key");
+    return fail(h, HS_ERR_INVALID, at + "group, sequence and diagonal do not fit a 64-bit key");
   return HS_OK;
+}
+
+// the batch at m0 ends at the last group start within `size`, or, where the first group is larger, at that group's end
+uint32_t pssm_family_cut(const PssmFamily& f, uint64_t nm, uint64_t m0, uint32_t size) {
+  if (!f.cuts) return (uint32_t)std::min<uint64_t>(size, nm - m0);
+  const std::vector<uint32_t>& c = *f.cuts;
+  auto it = std::upper_bound(c.begin(), c.end(), (uint32_t)std::min<uint64_t>(m0 + size, nm));
+  const uint32_t end = *(it - 1);  // (c holds m0 itself, so it - 1 exists)
+  return end > m0 ? end - (uint32_t)m0 : *it - (uint32_t)m0;
 }
 
 // The call with every array on the device; the callers have checked the arguments and the values.  Batches are cut at
@@ -462,14 +479,7 @@ hs_status pssm_family_core(hs_handle* h, const double* d_S, const double* d_t, u
   HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
   if (d_cnt_out && nm) HS_HIP(h, hipMemsetAsync(d_cnt_out, 0, nm * 8, h->stream));
   if (d_grp_rows && f.n_groups) HS_HIP(h, hipMemsetAsync(d_grp_rows, 0, f.n_groups * 8, h->stream));
-  // the batch at m0 ends at the last group start within `size`, or, where the first group is larger, at that group's end
-  const auto cut = [&](uint64_t m0, uint32_t size) -> uint32_t {
-    if (!f.cuts) return (uint32_t)std::min<uint64_t>(size, nm - m0);
-    const std::vector<uint32_t>& c = *f.cuts;
-    auto it = std::upper_bound(c.begin(), c.end(), (uint32_t)std::min<uint64_t>(m0 + size, nm));
-    const uint32_t end = *(it - 1);  // (c holds m0 itself, so it - 1 exists)
-    return end > m0 ? end - (uint32_t)m0 : *it - (uint32_t)m0;
-  };
+  const auto cut = [&](uint64_t m0, uint32_t size) -> uint32_t { return pssm_family_cut(f, nm, m0, size); };
   uint64_t all_rows = 0, kept_rows = 0;
   const int key_bits = std::max(1, f.wg + f.ws + f.wd);
   HS_CHECK(pssm_batches(
@@ -529,6 +539,204 @@ hs_status pssm_family_core(hs_handle* h, const double* d_S, const double* d_t, u
   h->prof.pssm_fam_kept = kept_rows;
   *n_out = kept_rows;
   if (kept_rows > cap) return fail(h, HS_ERR_CAPACITY, "row buffers too small; see *n_out");
+  return HS_OK;
+}
+
+// ---- hs_pssm_family_chain: the best gapped chain per (family, sequence) (kernels: hs_pssm_chain.hip) ----------------
+struct PssmChain {
+  uint32_t max_shift = 0;
+  double gap_open = 0.0, gap_ext = 0.0;
+};
+
+const char* const CHAIN_NAME = "hs_pssm_family_chain";
+
+// what both forms refuse beside the family scan's argument refusals
+hs_status pssm_chain_args(hs_handle* h, const void* m_off, const PssmChain& c) {
+  if (!m_off) return fail(h, HS_ERR_INVALID, "hs_pssm_family_chain: m_off is null");
+  if (c.max_shift > HS_PSSM_CHAIN_MAX_SHIFT) return fail(h, HS_ERR_INVALID, "hs_pssm_family_chain: max_shift is above 65535");
+  if (!hs_pssm_chain_params_ok(c.max_shift, c.gap_open, c.gap_ext))
+    return fail(h, HS_ERR_INVALID, "hs_pssm_family_chain: gap_open and gap_ext must be finite and not negative");
+  return HS_OK;
+}
+
+// The call with every array on the device; the callers have checked the arguments and the values.  Batches are cut at
+// group starts, so a batch's segments are final and their rows follow the rows of the batches before it.
+hs_status pssm_chain_core(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm, const PssmFamily& f,
+                          const PssmChain& c, const HsChainOut& out, uint64_t cap, uint64_t* n_out, uint64_t* n_hits,
+                          uint64_t* d_cnt_out, uint64_t* d_grp_rows) {
+  memset(&h->prof, 0, sizeof(h->prof));
+  HS_HIP(h, h->counters.reserve(256));
+  HS_HIP(h, hipEventRecord(h->ev[8], h->stream));
+  if (d_cnt_out && nm) HS_HIP(h, hipMemsetAsync(d_cnt_out, 0, nm * 8, h->stream));
+  if (d_grp_rows && f.n_groups) HS_HIP(h, hipMemsetAsync(d_grp_rows, 0, f.n_groups * 8, h->stream));
+  const auto cut = [&](uint64_t m0, uint32_t size) -> uint32_t { return pssm_family_cut(f, nm, m0, size); };
+  uint64_t all_segs = 0, kept_rows = 0;
+  const int key_bits = std::max(1, f.wg + f.ws);
+  HS_CHECK(pssm_batches(
+      h, d_S, d_t, nm, n_hits, cut, "hs_pssm_family_chain: the filter survivors of one group exceed 2^32",
+      [&](uint32_t m0, uint32_t mb, uint32_t nh) -> hs_status {
+        HS_CHECK(pssm_sort_hits(h, m0, mb, nh,
+                                std::max(hs_scan_u32_temp((size_t)nh + 1), hs_sort_pairs_u64_u32_temp(nh))));
+        const uint64_t *key = h->hit_key2.as<uint64_t>(), *val = h->hit_val2.as<uint64_t>();
+        HS_HIP(h, h->sq_sidx.reserve((size_t)nh * 4));  // the sequence of every hit
+        HS_HIP(h, h->sq_key.reserve((size_t)nh * 8));   // the segment keys and the hit indices ...
+        HS_HIP(h, h->sq_idx.reserve((size_t)nh * 4));
+        HS_HIP(h, h->sq_skey.reserve((size_t)nh * 8));  // ... and their sorted copies
+        HS_HIP(h, h->pf_sidx.reserve((size_t)nh * 4));
+        HS_HIP(h, h->sq_head.reserve(((size_t)nh + 1) * 4));
+        HS_HIP(h, h->sq_excl.reserve(((size_t)nh + 1) * 4));
+        HS_HIP(h, hs_launch_pssm_seq_of(key, nh, f.d_id_start, f.n_seq, h->sq_sidx.as<uint32_t>(), h->stream));
+        // the family's key kernel without a diagonal field: g << ws | s
+        HS_HIP(h, hs_launch_pssm_family_key(key, h->sq_sidx.as<uint32_t>(), nh, f.d_m_group, nullptr, f.d_id_start, f.ws,
+                                            0, 0, h->sq_key.as<uint64_t>(), h->sq_idx.as<uint32_t>(), d_cnt_out,
+                                            h->stream));
+        HS_HIP(h, hs_sort_pairs_u64_u32(h->temp.p, h->temp.cap, h->sq_key.as<uint64_t>(), h->sq_skey.as<uint64_t>(),
+                                        h->sq_idx.as<uint32_t>(), h->pf_sidx.as<uint32_t>(), nh, 0, key_bits,
+                                        h->stream));
+        HS_HIP(h, hs_launch_sm_head(h->sq_skey.as<uint64_t>(), nh, h->sq_head.as<uint32_t>(), h->stream));
+        HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, h->sq_head.as<uint32_t>(), h->sq_excl.as<uint32_t>(),
+                                        (size_t)nh + 1, h->stream));
+        uint32_t segs = 0;
+        HS_HIP(h, hipMemcpyAsync(&segs, h->sq_excl.as<uint32_t>() + nh, 4, hipMemcpyDeviceToHost, h->stream));
+        HS_HIP(h, hipStreamSynchronize(h->stream));
+        if (!segs || segs > nh)
+          return fail(h, HS_ERR_HIP, std::string(CHAIN_NAME) + ": the segment count of a batch is out of range");
+        HS_HIP(h, h->pf_start.reserve(((size_t)segs + 1) * 4));
+        HS_HIP(h, h->pch_state.reserve(hs_pssm_chain_state_bytes(nh)));
+        HS_HIP(h, h->pch_rows.reserve((size_t)segs * 44));
+        HS_HIP(h, h->pf_keep.reserve(((size_t)segs + 1) * 4));
+        HS_HIP(h, h->pf_pos.reserve(((size_t)segs + 1) * 4));
+        HS_HIP(h, hs_launch_pssm_chain(h->sq_skey.as<uint64_t>(), h->pf_sidx.as<uint32_t>(), h->sq_head.as<uint32_t>(),
+                                       h->sq_excl.as<uint32_t>(), nh, segs, key, val, f.d_id_start, f.d_m_off, f.ws,
+                                       c.max_shift, c.gap_open, c.gap_ext, f.min_count, f.d_t_group,
+                                       h->pf_start.as<uint32_t>(), h->pch_state.p, h->pch_rows.p,
+                                       h->pf_keep.as<uint32_t>(), h->stream));
+        HS_HIP(h, hs_exclusive_scan_u32(h->temp.p, h->temp.cap, h->pf_keep.as<uint32_t>(), h->pf_pos.as<uint32_t>(),
+                                        (size_t)segs + 1, h->stream));
+        uint32_t kept = 0;
+        HS_HIP(h, hipMemcpyAsync(&kept, h->pf_pos.as<uint32_t>() + segs, 4, hipMemcpyDeviceToHost, h->stream));
+        HS_HIP(h, hipStreamSynchronize(h->stream));
+        if (kept > segs)
+          return fail(h, HS_ERR_HIP, std::string(CHAIN_NAME) + ": the kept rows of a batch are out of range");
+        const uint64_t at = std::min<uint64_t>(kept_rows, cap);
+        const bool fits = kept <= cap - at;
+        HS_HIP(h, hs_launch_pssm_chain_write(h->pch_rows.p, h->pf_keep.as<uint32_t>(), h->pf_pos.as<uint32_t>(), segs,
+                                             fits && kept, fits && kept ? out.at(at) : HsChainOut(), d_grp_rows,
+                                             h->stream));
+        all_segs += segs;
+        kept_rows += kept;
+        return HS_OK;
+      }));
+  h->prof.pssm_chain_segs = all_segs;
+  h->prof.pssm_chain_kept = kept_rows;
+  *n_out = kept_rows;
+  if (kept_rows > cap) return fail(h, HS_ERR_CAPACITY, "row buffers too small; see *n_out");
+  return HS_OK;
+}
+
+// The value errors of a family call's device arrays (the argument refusals are behind it): the words of sq_chk --
+// [0..2] hs_sm_check_kernel's {flags, largest m_off, most ids of a sequence}, [4] the BAD_* bits of S and t, [6] the
+// HS_FAM_BAD_* bits, of which the call refuses those in `refused` -- and, in the same read-back, m_group for the cut
+// points.  f and cuts are filled.
+hs_status pssm_family_dev_check(hs_handle* h, const char* name, const double* d_S, const double* d_t, uint64_t nm,
+                                const uint32_t* d_m_group, uint64_t n_groups, const uint32_t* d_m_off,
+                                const uint64_t* d_id_start, uint64_t n_seq, uint32_t min_count, const double* d_t_group,
+                                uint32_t refused, PssmFamily* f, std::vector<uint32_t>* cuts) {
+  HS_CHECK(ensure_device(h));
+  uint64_t chk[7] = {0, 0, 0, 0, 0, 0, 0};
+  std::vector<uint32_t> groups;
+  HS_HIP(h, h->sq_chk.reserve(64));
+  HS_HIP(h, hipMemsetAsync(h->sq_chk.p, 0, 64, h->stream));
+  if (nm) HS_HIP(h, hs_launch_pssm_check(d_S, nm * h->p.k * h->alphabet, d_t, nm, h->sq_chk.as<uint32_t>() + 8, h->stream));
+  HS_HIP(h, hs_launch_sm_check(d_m_group, d_m_off, nm, n_groups, d_id_start, n_seq, h->n, h->sq_chk.as<uint64_t>(),
+                               h->stream));
+  HS_HIP(h, hs_launch_pssm_family_check(d_m_group, d_m_off, d_t_group, nm, n_groups, h->sq_chk.as<uint32_t>() + 12,
+                                        h->stream));
+  HS_HIP(h, hipMemcpyAsync(chk, h->sq_chk.p, sizeof(chk), hipMemcpyDeviceToHost, h->stream));
+  if (d_m_group && nm) {
+    try {
+      groups.resize(nm);
+    } catch (const std::bad_alloc&) {
+      return fail(h, HS_ERR_NOMEM, std::string(name) + ": no memory for the groups");
+    }
+    HS_HIP(h, hipMemcpyAsync(groups.data(), d_m_group, nm * 4, hipMemcpyDeviceToHost, h->stream));
+  }
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  HS_CHECK(pssm_refuse(h, (uint32_t)chk[4] | (chk[0] & 7 ? (uint32_t)BAD_ID_START : 0u), "threshold", name));
+  f->d_m_group = d_m_group;
+  f->n_groups = n_groups;
+  f->d_m_off = d_m_off;
+  f->d_id_start = d_id_start;
+  f->n_seq = n_seq;
+  f->min_count = min_count;
+  f->d_t_group = d_t_group;
+  f->max_off = d_m_off ? chk[1] : 0;
+  HS_CHECK(pssm_family_refuse(
+      h, name, ((uint32_t)chk[6] & refused) | (chk[0] & 8 ? (uint32_t)HS_FAM_BAD_GROUP_VALUE : 0u), chk[2], f));
+  if (d_m_group) {
+    try {
+      *cuts = pssm_family_cuts(groups.data(), nm);
+    } catch (const std::bad_alloc&) {
+      return fail(h, HS_ERR_NOMEM, std::string(name) + ": no memory for the groups");
+    }
+    f->cuts = cuts;
+  }
+  return HS_OK;
+}
+
+// ... and of a call's host arrays
+hs_status pssm_family_host_check(hs_handle* h, const char* name, const double* S, const double* t, uint64_t nm,
+                                 const uint32_t* m_group, uint64_t n_groups, const uint32_t* m_off,
+                                 const uint64_t* id_start, uint64_t n_seq, uint32_t min_count, const double* t_group,
+                                 uint32_t refused, PssmFamily* f, std::vector<uint32_t>* cuts) {
+  HS_CHECK(pssm_refuse(h, pssm_host_bad(h, S, t, nm) | pssm_id_start_bad(h, id_start, n_seq), "threshold", name));
+  f->n_groups = n_groups;
+  f->n_seq = n_seq;
+  f->min_count = min_count;
+  uint64_t max_len = 0;
+  for (uint64_t s = 0; s < n_seq; ++s) max_len = std::max(max_len, id_start[s + 1] - id_start[s]);
+  HS_CHECK(pssm_family_refuse(
+      h, name, hs_pssm_family_values_bad(nm, m_group, n_groups, m_off, t_group, &f->max_off) & refused, max_len, f));
+  if (m_group) {
+    try {
+      *cuts = pssm_family_cuts(m_group, nm);
+    } catch (const std::bad_alloc&) {
+      return fail(h, HS_ERR_NOMEM, std::string(name) + ": no memory for the groups");
+    }
+    f->cuts = cuts;
+  }
+  return HS_OK;
+}
+
+// A host-pointer family call's arrays on their way up: S and t (io_centers, io_radii), id_start (sq_in), m_group,
+// m_off, t_group (pf_in), room for out_bytes of rows (sq_out) and, where the caller wants them, for cnt and grp_rows
+// (io_cand).  f receives the device pointers.  (The per-group arrays only where the caller has them: n_groups may be
+// 2^32 with neither.)
+hs_status pssm_family_stage(hs_handle* h, const double* S, const double* t, uint64_t nm, const uint32_t* m_group,
+                            uint64_t n_groups, const uint32_t* m_off, const uint64_t* id_start, uint64_t n_seq,
+                            const double* t_group, bool want_cnt, bool want_grp, size_t out_bytes, PssmFamily* f,
+                            uint64_t** d_cnt, uint64_t** d_grp) {
+  HS_CHECK(ensure_device(h));
+  const size_t sb = ((size_t)n_seq + 1) * 8, cb = std::max<size_t>(16, nm * 8);
+  const size_t tb = t_group ? std::max<size_t>(16, n_groups * 8) : 16, gb = want_grp ? std::max<size_t>(16, n_groups * 8) : 16;
+  const size_t mb4 = (std::max<size_t>(16, nm * 4) + 15) & ~(size_t)15;
+  HS_CHECK(pssm_stage_in(h, S, t, nm, h->io_radii));
+  HS_HIP(h, h->sq_in.reserve(sb));
+  HS_HIP(h, h->pf_in.reserve(2 * mb4 + tb));  // m_group, m_off, t_group
+  HS_HIP(h, h->sq_out.reserve(std::max<size_t>(64, out_bytes)));
+  if (want_cnt || want_grp) HS_HIP(h, h->io_cand.reserve(cb + gb));
+  HS_HIP(h, hipMemcpyAsync(h->sq_in.p, id_start, sb, hipMemcpyHostToDevice, h->stream));
+  char* const in = h->pf_in.as<char>();
+  if (m_group && nm) HS_HIP(h, hipMemcpyAsync(in, m_group, nm * 4, hipMemcpyHostToDevice, h->stream));
+  if (m_off && nm) HS_HIP(h, hipMemcpyAsync(in + mb4, m_off, nm * 4, hipMemcpyHostToDevice, h->stream));
+  if (t_group && n_groups)
+    HS_HIP(h, hipMemcpyAsync(in + 2 * mb4, t_group, n_groups * 8, hipMemcpyHostToDevice, h->stream));
+  f->d_m_group = m_group ? reinterpret_cast<const uint32_t*>(in) : nullptr;
+  f->d_m_off = m_off ? reinterpret_cast<const uint32_t*>(in + mb4) : nullptr;
+  f->d_t_group = t_group ? reinterpret_cast<const double*>(in + 2 * mb4) : nullptr;
+  f->d_id_start = h->sq_in.as<uint64_t>();
+  *d_cnt = want_cnt ? h->io_cand.as<uint64_t>() : nullptr;
+  *d_grp = want_grp ? reinterpret_cast<uint64_t*>(h->io_cand.as<char>() + cb) : nullptr;
   return HS_OK;
 }
 
@@ -1312,46 +1520,12 @@ hs_status hs_pssm_family_scan_dev(hs_handle* h, const double* d_S, const double*
   *n_hits = 0;
   const HsFamilyOut out{d_out_group,      d_out_seq,    d_out_diag,    d_out_count, d_out_sum,
                         d_out_best_score, d_out_best_m, d_out_best_id, d_out_lo,    d_out_hi};
-  HS_CHECK(pssm_family_args(h, d_S, d_t, nm, d_m_group != nullptr, n_groups, d_id_start, n_seq, min_count, out, cap));
-  HS_CHECK(ensure_device(h));
-  // The value errors on the device: the words of sq_chk -- [0..2] hs_sm_check_kernel's {flags, largest m_off, most ids
-  // of a sequence}, [4] the BAD_* bits of S and t, [6] the HS_FAM_BAD_* bits -- and, in the same read-back, m_group
-  // for the cut points
-  uint64_t chk[7] = {0, 0, 0, 0, 0, 0, 0};
-  std::vector<uint32_t> groups;
-  HS_HIP(h, h->sq_chk.reserve(64));
-  HS_HIP(h, hipMemsetAsync(h->sq_chk.p, 0, 64, h->stream));
-  if (nm) HS_HIP(h, hs_launch_pssm_check(d_S, nm * h->p.k * h->alphabet, d_t, nm, h->sq_chk.as<uint32_t>() + 8, h->stream));
-  HS_HIP(h, hs_launch_sm_check(d_m_group, d_m_off, nm, n_groups, d_id_start, n_seq, h->n, h->sq_chk.as<uint64_t>(),
-                               h->stream));
-  HS_HIP(h, hs_launch_pssm_family_check(d_m_group, d_m_off, d_t_group, nm, n_groups, h->sq_chk.as<uint32_t>() + 12,
-                                        h->stream));
-  HS_HIP(h, hipMemcpyAsync(chk, h->sq_chk.p, sizeof(chk), hipMemcpyDeviceToHost, h->stream));
-  if (d_m_group && nm) {
-    try {
-      groups.resize(nm);
-    } catch (const std::bad_alloc&) {
-      return fail(h, HS_ERR_NOMEM, "hs_pssm_family_scan: no memory for the groups");
-    }
-    HS_HIP(h, hipMemcpyAsync(groups.data(), d_m_group, nm * 4, hipMemcpyDeviceToHost, h->stream));
-  }
-  HS_HIP(h, hipStreamSynchronize(h->stream));
-  HS_CHECK(pssm_refuse(h, (uint32_t)chk[4] | (chk[0] & 7 ? (uint32_t)BAD_ID_START : 0u), "threshold", FAMILY_NAME));
+  HS_CHECK(pssm_family_args(h, FAMILY_NAME, d_S, d_t, nm, d_m_group != nullptr, n_groups, d_id_start, n_seq, min_count,
+                            out.all(), cap));
   PssmFamily f;
-  f.d_m_group = d_m_group;
-  f.n_groups = n_groups;
-  f.d_m_off = d_m_off;
-  f.d_id_start = d_id_start;
-  f.n_seq = n_seq;
-  f.min_count = min_count;
-  f.d_t_group = d_t_group;
-  f.max_off = d_m_off ? chk[1] : 0;
-  HS_CHECK(pssm_family_refuse(h, (uint32_t)chk[6] | (chk[0] & 8 ? (uint32_t)HS_FAM_BAD_GROUP_VALUE : 0u), chk[2], &f));
   std::vector<uint32_t> cuts;
-  if (d_m_group) {
-    cuts = pssm_family_cuts(groups.data(), nm);
-    f.cuts = &cuts;
-  }
+  HS_CHECK(pssm_family_dev_check(h, FAMILY_NAME, d_S, d_t, nm, d_m_group, n_groups, d_m_off, d_id_start, n_seq,
+                                 min_count, d_t_group, ~(uint32_t)HS_FAM_BAD_OFF_ORDER, &f, &cuts));
   return pssm_family_core(h, d_S, d_t, nm, f, out, cap, n_out, n_hits, d_cnt, d_grp_rows);
 }
 
@@ -1366,49 +1540,17 @@ hs_status hs_pssm_family_scan(hs_handle* h, const double* S, const double* t, ui
   *n_hits = 0;
   const HsFamilyOut out{out_group, out_seq, out_diag, out_count, out_sum, out_best_score, out_best_m, out_best_id,
                         out_lo,    out_hi};
-  HS_CHECK(pssm_family_args(h, S, t, nm, m_group != nullptr, n_groups, id_start, n_seq, min_count, out, cap));
-  HS_CHECK(pssm_refuse(h, pssm_host_bad(h, S, t, nm) | pssm_id_start_bad(h, id_start, n_seq), "threshold", FAMILY_NAME));
+  HS_CHECK(pssm_family_args(h, FAMILY_NAME, S, t, nm, m_group != nullptr, n_groups, id_start, n_seq, min_count, out.all(),
+                            cap));
   PssmFamily f;
-  f.n_groups = n_groups;
-  f.n_seq = n_seq;
-  f.min_count = min_count;
-  uint64_t max_len = 0;
-  for (uint64_t s = 0; s < n_seq; ++s) max_len = std::max(max_len, id_start[s + 1] - id_start[s]);
-  HS_CHECK(pssm_family_refuse(h, hs_pssm_family_values_bad(nm, m_group, n_groups, m_off, t_group, &f.max_off), max_len,
-                              &f));
   std::vector<uint32_t> cuts;
-  if (m_group) {
-    try {
-      cuts = pssm_family_cuts(m_group, nm);
-    } catch (const std::bad_alloc&) {
-      return fail(h, HS_ERR_NOMEM, "hs_pssm_family_scan: no memory for the groups");
-    }
-    f.cuts = &cuts;
-  }
-  HS_CHECK(ensure_device(h));
+  HS_CHECK(pssm_family_host_check(h, FAMILY_NAME, S, t, nm, m_group, n_groups, m_off, id_start, n_seq, min_count, t_group,
+                                  ~(uint32_t)HS_FAM_BAD_OFF_ORDER, &f, &cuts));
   // the rows are staged on the device at the caller's capacity: 48 bytes per row cross PCIe, never the hits
-  // (the per-group arrays only where the caller has them: n_groups may be 2^32 with neither)
-  const size_t sb = ((size_t)n_seq + 1) * 8, cb = std::max<size_t>(16, nm * 8);
-  const size_t tb = t_group ? std::max<size_t>(16, n_groups * 8) : 16, gb = grp_rows ? std::max<size_t>(16, n_groups * 8) : 16;
-  const size_t mb4 = (std::max<size_t>(16, nm * 4) + 15) & ~(size_t)15;
-  HS_CHECK(pssm_stage_in(h, S, t, nm, h->io_radii));
-  HS_HIP(h, h->sq_in.reserve(sb));
-  HS_HIP(h, h->pf_in.reserve(2 * mb4 + tb));  // m_group, m_off, t_group
-  HS_HIP(h, h->sq_out.reserve(std::max<size_t>(64, (size_t)cap * 48)));
-  if (cnt || grp_rows) HS_HIP(h, h->io_cand.reserve(cb + gb));
-  HS_HIP(h, hipMemcpyAsync(h->sq_in.p, id_start, sb, hipMemcpyHostToDevice, h->stream));
-  char* const in = h->pf_in.as<char>();
-  if (m_group && nm) HS_HIP(h, hipMemcpyAsync(in, m_group, nm * 4, hipMemcpyHostToDevice, h->stream));
-  if (m_off && nm) HS_HIP(h, hipMemcpyAsync(in + mb4, m_off, nm * 4, hipMemcpyHostToDevice, h->stream));
-  if (t_group && n_groups)
-    HS_HIP(h, hipMemcpyAsync(in + 2 * mb4, t_group, n_groups * 8, hipMemcpyHostToDevice, h->stream));
-  f.d_m_group = m_group ? reinterpret_cast<const uint32_t*>(in) : nullptr;
-  f.d_m_off = m_off ? reinterpret_cast<const uint32_t*>(in + mb4) : nullptr;
-  f.d_t_group = t_group ? reinterpret_cast<const double*>(in + 2 * mb4) : nullptr;
-  f.d_id_start = h->sq_in.as<uint64_t>();
+  uint64_t *d_cnt = nullptr, *d_grp = nullptr;
+  HS_CHECK(pssm_family_stage(h, S, t, nm, m_group, n_groups, m_off, id_start, n_seq, t_group, cnt != nullptr,
+                             grp_rows != nullptr, (size_t)cap * 48, &f, &d_cnt, &d_grp));
   const HsFamilyOut dev = HsFamilyOut::in(h->sq_out.as<char>(), cap);
-  uint64_t* const d_cnt = cnt ? h->io_cand.as<uint64_t>() : nullptr;
-  uint64_t* const d_grp = grp_rows ? reinterpret_cast<uint64_t*>(h->io_cand.as<char>() + cb) : nullptr;
   const hs_status st = pssm_family_core(h, h->io_centers.as<double>(), h->io_radii.as<double>(), nm, f, dev, cap, n_out,
                                         n_hits, d_cnt, d_grp);
   if (st != HS_OK && st != HS_ERR_CAPACITY) return st;
@@ -1427,6 +1569,84 @@ hs_status hs_pssm_family_scan(hs_handle* h, const double* S, const double* t, ui
     HS_HIP(h, hipMemcpyAsync(out_best_id, dev.best_id, r * 4, hipMemcpyDeviceToHost, h->stream));
     HS_HIP(h, hipMemcpyAsync(out_lo, dev.lo, r * 4, hipMemcpyDeviceToHost, h->stream));
     HS_HIP(h, hipMemcpyAsync(out_hi, dev.hi, r * 4, hipMemcpyDeviceToHost, h->stream));
+  }
+  HS_HIP(h, hipStreamSynchronize(h->stream));
+  return st;
+}
+
+hs_status hs_pssm_family_chain_dev(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm,
+                                   const uint32_t* d_m_group, uint64_t n_groups, const uint32_t* d_m_off,
+                                   const uint64_t* d_id_start, uint64_t n_seq, uint32_t max_shift, double gap_open,
+                                   double gap_ext, uint32_t min_count, const double* d_t_group, uint32_t* d_out_group,
+                                   uint32_t* d_out_seq, uint32_t* d_out_count, uint32_t* d_out_gaps, double* d_out_score,
+                                   uint32_t* d_out_first_m, uint32_t* d_out_first_id, uint32_t* d_out_last_m,
+                                   uint32_t* d_out_last_id, int32_t* d_out_shift, uint64_t cap, uint64_t* n_out,
+                                   uint64_t* n_hits, uint64_t* d_cnt, uint64_t* d_grp_rows) {
+  if (!h || !n_out || !n_hits) return HS_ERR_INVALID;
+  *n_out = 0;
+  *n_hits = 0;
+  const HsChainOut out{d_out_group,   d_out_seq,      d_out_count,  d_out_gaps,    d_out_score,
+                       d_out_first_m, d_out_first_id, d_out_last_m, d_out_last_id, d_out_shift};
+  PssmChain c;
+  c.max_shift = max_shift;
+  c.gap_open = gap_open;
+  c.gap_ext = gap_ext;
+  HS_CHECK(pssm_family_args(h, CHAIN_NAME, d_S, d_t, nm, d_m_group != nullptr, n_groups, d_id_start, n_seq, min_count,
+                            out.all(), cap));
+  HS_CHECK(pssm_chain_args(h, d_m_off, c));
+  PssmFamily f;
+  std::vector<uint32_t> cuts;
+  HS_CHECK(pssm_family_dev_check(h, CHAIN_NAME, d_S, d_t, nm, d_m_group, n_groups, d_m_off, d_id_start, n_seq, min_count,
+                                 d_t_group, ~0u, &f, &cuts));
+  return pssm_chain_core(h, d_S, d_t, nm, f, c, out, cap, n_out, n_hits, d_cnt, d_grp_rows);
+}
+
+hs_status hs_pssm_family_chain(hs_handle* h, const double* S, const double* t, uint64_t nm, const uint32_t* m_group,
+                               uint64_t n_groups, const uint32_t* m_off, const uint64_t* id_start, uint64_t n_seq,
+                               uint32_t max_shift, double gap_open, double gap_ext, uint32_t min_count,
+                               const double* t_group, uint32_t* out_group, uint32_t* out_seq, uint32_t* out_count,
+                               uint32_t* out_gaps, double* out_score, uint32_t* out_first_m, uint32_t* out_first_id,
+                               uint32_t* out_last_m, uint32_t* out_last_id, int32_t* out_shift, uint64_t cap,
+                               uint64_t* n_out, uint64_t* n_hits, uint64_t* cnt, uint64_t* grp_rows) {
+  if (!h || !n_out || !n_hits) return HS_ERR_INVALID;
+  *n_out = 0;
+  *n_hits = 0;
+  const HsChainOut out{out_group,   out_seq,      out_count,  out_gaps,    out_score,
+                       out_first_m, out_first_id, out_last_m, out_last_id, out_shift};
+  PssmChain c;
+  c.max_shift = max_shift;
+  c.gap_open = gap_open;
+  c.gap_ext = gap_ext;
+  HS_CHECK(pssm_family_args(h, CHAIN_NAME, S, t, nm, m_group != nullptr, n_groups, id_start, n_seq, min_count, out.all(),
+                            cap));
+  HS_CHECK(pssm_chain_args(h, m_off, c));
+  PssmFamily f;
+  std::vector<uint32_t> cuts;
+  HS_CHECK(pssm_family_host_check(h, CHAIN_NAME, S, t, nm, m_group, n_groups, m_off, id_start, n_seq, min_count, t_group,
+                                  ~0u, &f, &cuts));
+  // the rows are staged on the device at the caller's capacity: 44 bytes per row cross PCIe, never the hits
+  uint64_t *d_cnt = nullptr, *d_grp = nullptr;
+  HS_CHECK(pssm_family_stage(h, S, t, nm, m_group, n_groups, m_off, id_start, n_seq, t_group, cnt != nullptr,
+                             grp_rows != nullptr, (size_t)cap * 44, &f, &d_cnt, &d_grp));
+  const HsChainOut dev = HsChainOut::in(h->sq_out.as<char>(), cap);
+  const hs_status st = pssm_chain_core(h, h->io_centers.as<double>(), h->io_radii.as<double>(), nm, f, c, dev, cap, n_out,
+                                       n_hits, d_cnt, d_grp);
+  if (st != HS_OK && st != HS_ERR_CAPACITY) return st;
+  if (st == HS_ERR_CAPACITY && *n_out <= cap) return st;  // (one group's survivors: no count is valid)
+  if (cnt && nm) HS_HIP(h, hipMemcpyAsync(cnt, d_cnt, nm * 8, hipMemcpyDeviceToHost, h->stream));
+  if (grp_rows && n_groups) HS_HIP(h, hipMemcpyAsync(grp_rows, d_grp, n_groups * 8, hipMemcpyDeviceToHost, h->stream));
+  const size_t r = (size_t)*n_out;
+  if (st == HS_OK && r) {
+    const struct {
+      void* to;
+      const void* from;
+      size_t bytes;
+    } copies[10] = {{out_group, dev.group, 4},       {out_seq, dev.seq, 4},         {out_count, dev.count, 4},
+                    {out_gaps, dev.gaps, 4},         {out_score, dev.score, 8},     {out_first_m, dev.first_m, 4},
+                    {out_first_id, dev.first_id, 4}, {out_last_m, dev.last_m, 4},   {out_last_id, dev.last_id, 4},
+                    {out_shift, dev.shift, 4}};
+    for (const auto& cp : copies)
+      HS_HIP(h, hipMemcpyAsync(cp.to, cp.from, r * cp.bytes, hipMemcpyDeviceToHost, h->stream));
   }
   HS_HIP(h, hipStreamSynchronize(h->stream));
   return st;

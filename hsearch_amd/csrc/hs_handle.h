@@ -296,6 +296,9 @@ struct hs_handle {
   // hit indices sorted on the row key, the rows' run starts, the rows before the filters, the filters' flags and their
   // scan; a host-pointer call's m_group, m_off and t_group on their way up
   DevBuf pf_sidx, pf_start, pf_rows, pf_keep, pf_pos, pf_in;
+  // hs_pssm_family_chain (hs_pssm_chain.hip; keys, sorts, starts, flags and inputs are the sq_ and pf_ buffers above):
+  // the chain state of a batch's hits by sorted position, the segments' rows before the filters
+  DevBuf pch_state, pch_rows;
   // hs_cluster_profile / hs_cluster_radii (hs_summary.hip: the state listed at its head), the counts of a row batch
   // when the caller wants none, and the arrays of a host-pointer call on their way in and out.  hs_cluster_weighted_profile
   // / hs_cluster_pssm_cover (hs_cluster_pssm.hip) run on the same state: a row batch's u tables go to pw_u, the members'

@@ -1044,6 +1044,23 @@ hipError_t hs_launch_pssm_family_write(const void* d_rows, const uint32_t* d_kee
                                        uint32_t n_rows, bool write, const HsFamilyOut& out, uint64_t* d_grp_rows,
                                        hipStream_t s);
 
+// ---- hs_pssm_family_chain (hs_pssm_chain.hip: the passes over a batch's sorted hits are written at its head) --------
+struct HsChainOut;  // hs_pssm_chain.h: the ten row arrays
+size_t hs_pssm_chain_state_bytes(uint32_t n);  // d_state of a batch of n hits
+// d_skey / d_sidx: the (g << ws | s, hit index) pairs sorted on the key; d_head [n + 1] their run heads, d_excl its
+// exclusive scan, n_segs its total.  Scratch: d_seg_start [n_segs + 1], d_state, d_rows of 44 n_segs bytes
+// (HsChainOut::in), d_keep [n_segs + 1]: whether a segment reports a row
+hipError_t hs_launch_pssm_chain(const uint64_t* d_skey, const uint32_t* d_sidx, const uint32_t* d_head,
+                                const uint32_t* d_excl, uint32_t n, uint32_t n_segs, const uint64_t* d_key,
+                                const uint64_t* d_val, const uint64_t* d_id_start, const uint32_t* d_m_off, int ws,
+                                uint32_t max_shift, double gap_open, double gap_ext, uint32_t min_count,
+                                const double* d_t_group, uint32_t* d_seg_start, void* d_state, void* d_rows,
+                                uint32_t* d_keep, hipStream_t s);
+// d_pos = the exclusive scan of d_keep.  write: the kept rows go to out (the batch's: already at the call's running
+// offset); d_grp_rows [g] += the kept rows of every group (may be null)
+hipError_t hs_launch_pssm_chain_write(const void* d_rows, const uint32_t* d_keep, const uint32_t* d_pos, uint32_t n_segs,
+                                      bool write, const HsChainOut& out, uint64_t* d_grp_rows, hipStream_t s);
+
 // ---- hs_pssm_hit_counts (hs_pssm_counts.hip: the passes over a batch's sites are written at its head) --------------
 // the batch's n hits m << 32 | id -> d_m [n], d_id [n]
 hipError_t hs_launch_pssm_counts_split(const uint64_t* d_key, uint32_t n, uint32_t* d_m, uint32_t* d_id, hipStream_t s);

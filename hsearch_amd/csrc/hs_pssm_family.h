@@ -37,7 +37,9 @@ enum {
   HS_FAM_BAD_GROUP_VALUE = 2,  // a value >= n_groups
   HS_FAM_BAD_GROUP_SIZE = 4,   // a group above HS_PSSM_FAMILY_MAX_GROUP profiles
   HS_FAM_BAD_OFF = 8,          // an m_off above 2^31 - 1
-  HS_FAM_BAD_T_GROUP = 16      // a t_group entry NaN or infinite
+  HS_FAM_BAD_T_GROUP = 16,     // a t_group entry NaN or infinite
+  HS_FAM_BAD_OFF_ORDER = 32    // an m_off below its predecessor's inside one group: refused by hs_pssm_family_chain
+                               // (hs_pssm_chain.h) only; the family scan takes any order
 };
 
 inline int hs_pssm_family_bits(uint64_t x) {
@@ -78,6 +80,7 @@ inline uint32_t hs_pssm_family_values_bad(uint64_t nm, const uint32_t* m_group, 
   }
   for (uint64_t m = 0; m_off && m < nm; ++m) {
     if (m_off[m] > HS_PSSM_FAMILY_MAX_OFF) bad |= HS_FAM_BAD_OFF;
+    if (m_group && m && m_group[m] == m_group[m - 1] && m_off[m] < m_off[m - 1]) bad |= HS_FAM_BAD_OFF_ORDER;
     *max_off = std::max<uint64_t>(*max_off, m_off[m]);
   }
   for (uint64_t g = 0; t_group && g < n_groups; ++g)
@@ -118,7 +121,8 @@ inline int hs_pssm_family_hits_host(const uint32_t* m, const uint32_t* id, const
   if (!hs_pssm_seq_id_start_ok(id_start, n_seq) || id_start[n_seq] > (1ull << 32)) return 1;
   if (!hs_pssm_family_counts_ok(nm, m_group != nullptr, n_groups, min_count)) return 1;
   uint64_t max_off = 0, max_len = 0;
-  if (hs_pssm_family_values_bad(nm, m_group, n_groups, m_off, t_group, &max_off)) return 1;
+  if (hs_pssm_family_values_bad(nm, m_group, n_groups, m_off, t_group, &max_off) & ~(uint32_t)HS_FAM_BAD_OFF_ORDER)
+    return 1;
   for (uint64_t s = 0; s < n_seq; ++s) max_len = std::max(max_len, id_start[s + 1] - id_start[s]);
   int wg, ws, wd;
   if (!hs_pssm_family_widths(n_groups, n_seq, max_len, max_off, &wg, &ws, &wd)) return 1;

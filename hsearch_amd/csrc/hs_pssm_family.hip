@@ -52,6 +52,7 @@ __global__ __launch_bounds__(256) void hs_pssm_family_check_kernel(const uint32_
       if (m >= HS_PSSM_FAMILY_MAX_GROUP && g == m_group[m - HS_PSSM_FAMILY_MAX_GROUP]) bad |= HS_FAM_BAD_GROUP_SIZE;
     }
     if (m_off && m_off[m] > HS_PSSM_FAMILY_MAX_OFF) bad |= HS_FAM_BAD_OFF;
+    if (m_off && m_group && m && m_group[m] == m_group[m - 1] && m_off[m] < m_off[m - 1]) bad |= HS_FAM_BAD_OFF_ORDER;
   }
   for (uint64_t g = t0; t_group && g < n_groups; g += step) {
     const double t = t_group[g];

@@ -1109,6 +1109,23 @@ int FamilyLayout(const std::vector<std::string>& names, const std::vector<uint32
   return HS_OK;
 }
 
+// families numbered in the given order; one that comes back after another is refused
+static bool FamilyGroups(const std::vector<std::string>& family, std::vector<uint32_t>* m_group,
+                         std::vector<std::string>* fam_names, std::string* err) {
+  m_group->resize(family.size());
+  for (size_t m = 0; m < family.size(); ++m) {
+    if (!m || family[m] != family[m - 1]) {
+      if (std::find(fam_names->begin(), fam_names->end(), family[m]) != fam_names->end()) {
+        if (err) *err = "the profiles of family " + family[m] + " do not stand next to each other";
+        return false;
+      }
+      fam_names->push_back(family[m]);
+    }
+    (*m_group)[m] = (uint32_t)fam_names->size() - 1;
+  }
+  return true;
+}
+
 int FamilyScan(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
                const std::vector<double>& S, const std::vector<double>& t, const std::vector<std::string>& family,
                const std::vector<uint32_t>& offset, uint32_t min_blocks, const double* threshold,
@@ -1121,19 +1138,9 @@ int FamilyScan(const ProteinDB& db, uint32_t kmer_length, const std::vector<std:
     if (err) *err = k < 2 ? "kmer length 1 is not supported on a FASTA database" : "the profiles do not match the kmer length";
     return HS_ERR_INVALID;
   }
-  // families numbered in the given order; one that comes back after another is refused
-  std::vector<uint32_t> m_group(nm);
+  std::vector<uint32_t> m_group;
   std::vector<std::string> fam_names;
-  for (size_t m = 0; m < nm; ++m) {
-    if (!m || family[m] != family[m - 1]) {
-      if (std::find(fam_names.begin(), fam_names.end(), family[m]) != fam_names.end()) {
-        if (err) *err = "the profiles of family " + family[m] + " do not stand next to each other";
-        return HS_ERR_INVALID;
-      }
-      fam_names.push_back(family[m]);
-    }
-    m_group[m] = (uint32_t)fam_names.size() - 1;
-  }
+  if (!FamilyGroups(family, &m_group, &fam_names, err)) return HS_ERR_INVALID;
   const size_t n_seq = db.start.empty() ? 0 : db.start.size() - 1;
   hs_handle* h = nullptr;
   uint64_t n_win = 0;
@@ -1177,6 +1184,73 @@ int FamilyScan(const ProteinDB& db, uint32_t kmer_length, const std::vector<std:
     fout << fam_names[rg[i]] << " " << ProteinLabel(db, s) << " " << rd[i] << " " << rc[i] << " " << sum << " "
          << names[rbm[i]] << " " << (win_pos[rid[i]] - at) << " " << num << " " << (win_pos[w0 + rlo[i]] - at) << " "
          << (win_pos[w0 + rhi[i]] - at) << "\n";
+  }
+  fout.close();
+  return HS_OK;
+}
+
+int FamilyChain(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
+                const std::vector<double>& S, const std::vector<double>& t, const std::vector<std::string>& family,
+                const std::vector<uint32_t>& offset, uint32_t max_shift, double gap_open, double gap_ext,
+                uint32_t min_blocks, const double* threshold, const std::string& output_file, int device,
+                std::string* err, uint64_t* n_windows, uint64_t* n_hits_out, uint64_t* n_rows_out) {
+  const uint32_t k = kmer_length;
+  const size_t nm = t.size();
+  if (k < 2 || names.size() != nm || S.size() != nm * (size_t)k * HS_ALPHABET || family.size() != nm ||
+      offset.size() != nm) {
+    if (err) *err = k < 2 ? "kmer length 1 is not supported on a FASTA database" : "the profiles do not match the kmer length";
+    return HS_ERR_INVALID;
+  }
+  std::vector<uint32_t> m_group;
+  std::vector<std::string> fam_names;
+  if (!FamilyGroups(family, &m_group, &fam_names, err)) return HS_ERR_INVALID;
+  for (size_t m = 1; m < nm; ++m)
+    if (m_group[m] == m_group[m - 1] && offset[m] < offset[m - 1]) {
+      if (err) *err = "the offsets of family " + family[m] + " decrease: a chain takes a family's profiles in block order";
+      return HS_ERR_INVALID;
+    }
+  const size_t n_seq = db.start.empty() ? 0 : db.start.size() - 1;
+  hs_handle* h = nullptr;
+  uint64_t n_win = 0;
+  std::vector<uint32_t> win_pos;
+  std::vector<uint64_t> id_start;
+  hs_status st = (hs_status)OpenWindowsIndex(db, k, device, &h, &n_win, &win_pos, &id_start, err);
+  HandleCloser closer = {h};
+  if (st != HS_OK) return st;
+  if (n_windows) *n_windows = n_win;
+  const std::vector<double> t_group(fam_names.size(), threshold ? *threshold : 0.0);
+  std::vector<uint32_t> rg, rs, rc, rgap, rfm, rfi, rlm, rli;
+  std::vector<int32_t> rshift;
+  std::vector<double> rsc;
+  uint64_t n_rows = 0, n_hits = 0;
+  for (uint64_t cap = 0;;) {  // the row count, then the rows
+    for (std::vector<uint32_t>* v : {&rg, &rs, &rc, &rgap, &rfm, &rfi, &rlm, &rli}) v->resize(cap);
+    rshift.resize(cap), rsc.resize(cap);
+    st = hs_pssm_family_chain(h, S.data(), t.data(), nm, m_group.data(), fam_names.size(), offset.data(), id_start.data(),
+                              n_seq, max_shift, gap_open, gap_ext, min_blocks, threshold ? t_group.data() : nullptr,
+                              rg.data(), rs.data(), rc.data(), rgap.data(), rsc.data(), rfm.data(), rfi.data(),
+                              rlm.data(), rli.data(), rshift.data(), cap, &n_rows, &n_hits, nullptr, nullptr);
+    if (st == HS_ERR_CAPACITY && n_rows > cap) {
+      cap = n_rows;
+      continue;
+    }
+    break;
+  }
+  if (st != HS_OK) {
+    if (err) *err = std::string("hs_pssm_family_chain: ") + hs_last_error(h);
+    return st;
+  }
+  if (n_hits_out) *n_hits_out = n_hits;
+  if (n_rows_out) *n_rows_out = n_rows;
+  std::ofstream fout(output_file.c_str());
+  char num[64];
+  for (uint64_t i = 0; i < n_rows; ++i) {  // offsets are residue offsets in the protein, as the scan's window names
+    const size_t s = rs[i];
+    const uint64_t at = db.start[s];
+    snprintf(num, sizeof(num), "%.17g", rsc[i]);
+    fout << fam_names[rg[i]] << " " << ProteinLabel(db, s) << " " << rc[i] << " " << rgap[i] << " " << num << " "
+         << names[rfm[i]] << " " << (win_pos[rfi[i]] - at) << " " << names[rlm[i]] << " " << (win_pos[rli[i]] - at) << " "
+         << rshift[i] << "\n";
   }
   fout.close();
   return HS_OK;

@@ -273,6 +273,19 @@ int FamilyScan(const ProteinDB& db, uint32_t kmer_length, const std::vector<std:
                const std::vector<uint32_t>& offset, uint32_t min_blocks, const double* threshold,
                const std::string& output_file, int device, std::string* err, uint64_t* n_windows = nullptr,
                uint64_t* n_hits = nullptr, uint64_t* n_rows = nullptr);
+// `--pssm FILE --pssm-families FAM --pssm-family-shift G`: per (family, protein) the best gapped chain of the family's
+// hits on the device (hs_pssm_family_chain): hits of later profiles at later offsets link when their diagonals differ by
+// at most max_shift, at the cost gap_open + gap_ext * d for d >= 1.  family, offset: as for FamilyScan, and the offsets
+// must not decrease inside a family (HS_ERR_INVALID otherwise).  A chain is written when it holds at least min_blocks
+// hits and (threshold given) scores at least *threshold.  One line per chain, "<family> <protein>#<number> <blocks>
+// <gaps> <score> <first profile> <first offset> <last profile> <last offset> <shift>": the offsets in residues from the
+// protein's start, the score with 17 significant digits, shift = the last hit's diagonal minus the first's; families in
+// the given order, proteins in database order.  *n_hits: the hits behind the chains, *n_rows: the lines.  One GPU.
+int FamilyChain(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,
+                const std::vector<double>& S, const std::vector<double>& t, const std::vector<std::string>& family,
+                const std::vector<uint32_t>& offset, uint32_t max_shift, double gap_open, double gap_ext,
+                uint32_t min_blocks, const double* threshold, const std::string& output_file, int device,
+                std::string* err, uint64_t* n_windows = nullptr, uint64_t* n_hits = nullptr, uint64_t* n_rows = nullptr);
 // `--pssm FILE --pssm-pvalue-column 1`: ScanProfiles' lines with " <p_hi>" appended, the upper end of the hit's p-value
 // under the same null model (hs_pssm_pvalue), printed with 17 significant digits; t_lo [nm]: the grids' floors.
 int HitPvalues(const ProteinDB& db, uint32_t kmer_length, const std::vector<std::string>& names,

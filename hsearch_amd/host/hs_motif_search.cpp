@@ -72,6 +72,13 @@
 // database order.  Refused: a profile of FILE missing from FAM, one named twice, an unknown name, a malformed line;
 // --pssm-top, --pssm-per-sequence, --pssm-compare, --pssm-pvalue-column, --pssm-refine, --pssm-rank or --pssm-pvalue
 // beside it; the two companion options without it; a C below 1; a T that is no finite number.
+// ... --pssm-families FAM --pssm-family-shift G [--pssm-family-gap-open X] [--pssm-family-gap-extend Y]: instead of the
+// rows per diagonal, per (family, protein) the best gapped chain of the family's hits (hs_pssm_family_chain): later
+// profiles at later offsets link when their diagonals differ by at most G, at the cost X + Y * d for d >= 1 [0, 0];
+// --pssm-family-blocks counts the chain's hits, --pssm-family-threshold bounds its score; "<family> <protein> <blocks>
+// <gaps> <score> <first profile> <first offset> <last profile> <last offset> <shift>".  Refused: the two gap options
+// without the shift; a G that is no whole number in 0..65535; a penalty that is negative or no finite number; a FAM
+// whose offsets decrease inside a family in line order (--pssm-families-out writes an ordered file).
 // --pssm-compare self ... --pssm-families-out FAM: that file, written from the comparison's hits (hs_pssm_family_layout);
 // the family is named after its first profile; hits that contradict earlier ones are counted on stderr.  Refused
 // without --pssm-compare self.
@@ -149,6 +156,9 @@ const Opt kOpts[] = {
     {"pssm-families", 'F', "with --pssm: a file of '<family> <profile name> <offset>' lines, one per profile; instead of the hits, one line per (family, protein, diagonal): blocks in register, the sum of their scores, best block, span (one GPU)", false},
     {"pssm-family-blocks", 'b', "with --pssm-families: report a row only when at least this many of the family's profiles hit on the diagonal, >= 1 [1]", false},
     {"pssm-family-threshold", 'H', "with --pssm-families: report a row only when the scores on the diagonal add up to at least this [off]", false},
+    {"pssm-family-shift", 'i', "with --pssm-families: instead of the rows per diagonal, per (family, protein) the best chain of the family's hits whose diagonals differ by at most this between neighbours, 0..65535: '<family> <protein> <blocks> <gaps> <score> <first profile> <first offset> <last profile> <last offset> <shift>' [off]", false},
+    {"pssm-family-gap-open", 'a', "with --pssm-family-shift: what a link between two diagonals costs, >= 0 [0]", false},
+    {"pssm-family-gap-extend", 'V', "with --pssm-family-shift: ... plus this per diagonal of distance, >= 0 [0]", false},
     {"pssm-families-out", 'J', "with --pssm-compare self: also write the families the hits imply, one '<family> <profile name> <offset>' line per profile, the file --pssm-families reads", false},
     {"pssm-weights", 'w', "with --pssm-refine: weigh the sites with position-based sequence weights; the log-odds count 'sites' or 'columns' (distinct residues per column) as observations [off: every site counts 1]", false},
 };
@@ -314,6 +324,29 @@ int FamilyMain(std::map<std::string, std::string>& val, const std::vector<std::s
       return EXIT_FAILURE;
     }
   }
+  const bool with_chain = val.count("pssm-family-shift") != 0;
+  uint32_t max_shift = 0;
+  double gap_open = 0.0, gap_ext = 0.0;
+  if (with_chain) {
+    const std::string& text = val["pssm-family-shift"];
+    const long long v = strtoll(text.c_str(), &end, 10);
+    if (text.empty() || end == text.c_str() || *end || text[0] == '+' || v < 0 || v > 65535) {
+      fprintf(stderr, "ERROR: --pssm-family-shift takes a whole number of diagonals, 0 .. 65535\n");
+      return EXIT_FAILURE;
+    }
+    max_shift = (uint32_t)v;
+    const std::pair<const char*, double*> gaps[2] = {{"pssm-family-gap-open", &gap_open},
+                                                     {"pssm-family-gap-extend", &gap_ext}};
+    for (const auto& g : gaps) {
+      if (!val.count(g.first)) continue;
+      const std::string& gt = val[g.first];
+      *g.second = strtod(gt.c_str(), &end);
+      if (gt.empty() || end == gt.c_str() || *end || !(*g.second >= 0.0) || !(*g.second <= 1.7976931348623157e308)) {
+        fprintf(stderr, "ERROR: --%s takes a finite penalty, 0 or more\n", g.first);
+        return EXIT_FAILURE;
+      }
+    }
+  }
   const uint32_t kmer_length = (uint32_t)strtoul(val["len"].c_str(), nullptr, 10);
   const int device = val.count("device") ? atoi(val["device"].c_str()) : 0;
   try {
@@ -328,6 +361,7 @@ int FamilyMain(std::map<std::string, std::string>& val, const std::vector<std::s
       fprintf(stderr, "ERROR: %s\n", err.c_str());
       return EXIT_FAILURE;
     }
+    std::map<std::string, uint32_t> last_offset;  // per family, in line order
     // FAM: every profile of FILE once, with its family and offset
     const size_t nm = names.size();
     std::map<std::string, size_t> index_of;
@@ -362,6 +396,14 @@ int FamilyMain(std::map<std::string, std::string>& val, const std::vector<std::s
         fprintf(stderr, "ERROR: %s line %zu: profile %s is named twice\n", val["pssm-families"].c_str(), ln, name.c_str());
         return EXIT_FAILURE;
       }
+      if (with_chain && last_offset.count(f) && (uint32_t)v < last_offset[f]) {
+        fprintf(stderr,
+                "ERROR: %s line %zu: the offsets of family %s decrease; --pssm-family-shift takes a family's profiles "
+                "in block order (--pssm-compare self --pssm-families-out writes an ordered file)\n",
+                val["pssm-families"].c_str(), ln, f.c_str());
+        return EXIT_FAILURE;
+      }
+      last_offset[f] = (uint32_t)v;
       seen[it->second] = 1;
       family[it->second] = f;
       offset[it->second] = (uint32_t)v;
@@ -408,9 +450,13 @@ int FamilyMain(std::map<std::string, std::string>& val, const std::vector<std::s
     struct timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     uint64_t n_windows = 0, n_hits = 0, n_rows = 0;
-    const int st = hsearch::FamilyScan(prodb, kmer_length, names2, S2, t2, family2, offset2, blocks,
-                                       with_threshold ? &threshold : nullptr, val["output"], device, &err, &n_windows,
-                                       &n_hits, &n_rows);
+    const int st =
+        with_chain ? hsearch::FamilyChain(prodb, kmer_length, names2, S2, t2, family2, offset2, max_shift, gap_open,
+                                          gap_ext, blocks, with_threshold ? &threshold : nullptr, val["output"], device,
+                                          &err, &n_windows, &n_hits, &n_rows)
+                   : hsearch::FamilyScan(prodb, kmer_length, names2, S2, t2, family2, offset2, blocks,
+                                         with_threshold ? &threshold : nullptr, val["output"], device, &err, &n_windows,
+                                         &n_hits, &n_rows);
     if (st != 0) {
       fprintf(stderr, "ERROR: %s (status %d)\n", err.c_str(), st);
       return EXIT_FAILURE;
@@ -726,6 +772,15 @@ int main(int argc, const char* argv[]) {
       fprintf(stderr, "ERROR: --%s belongs to --pssm-families: it cannot be given without it\n", name);
       return EXIT_FAILURE;
     }
+  for (const char* name : {"pssm-family-gap-open", "pssm-family-gap-extend"})
+    if (val.count(name) && !val.count("pssm-family-shift")) {
+      fprintf(stderr, "ERROR: --%s belongs to --pssm-family-shift: it cannot be given without it\n", name);
+      return EXIT_FAILURE;
+    }
+  if (val.count("pssm-family-shift") && !with_families) {
+    fprintf(stderr, "ERROR: --pssm-family-shift belongs to --pssm-families: it cannot be given without it\n");
+    return EXIT_FAILURE;
+  }
   if (val.count("pssm-families-out") && !with_compare) {
     fprintf(stderr, "ERROR: --pssm-families-out belongs to --pssm-compare self: it cannot be given without it\n");
     return EXIT_FAILURE;

@@ -118,6 +118,8 @@ typedef struct hs_profile {
   uint64_t pssm_seq_rows;      /* hs_pssm_seq_scan*: the (profile, sequence) rows the call found (its *n_out) */
   uint64_t pssm_fam_rows;      /* hs_pssm_family_scan*: the (family, sequence, diagonal) rows before the row filters */
   uint64_t pssm_fam_kept;      /* ... of which this many passed min_count and t_group (the call's *n_out) */
+  uint64_t pssm_chain_segs;    /* hs_pssm_family_chain*: the (family, sequence) segments before the filters */
+  uint64_t pssm_chain_kept;    /* ... of which this many report a chain (the call's *n_out) */
   uint64_t pssm_count_sites;   /* hs_pssm_hit_counts*: the sites counted, the sum of used[] */
   uint64_t pssm_count_items;   /* hs_pssm_hit_counts*: the (profile run, chunk) work items of the counting kernel */
   uint64_t pssm_weight_sites;  /* hs_pssm_weighted_counts*: the sites weighted (pssm_count_sites; 0 after other calls) */
@@ -1422,8 +1424,8 @@ HS_API hs_status hs_pssm_seq_hits(const uint32_t* m, const uint32_t* id, const d
  * hs_profile after the call: the pssm_* fields as after a scan, hits, pssm_fam_rows (rows before the filters),
  * pssm_fam_kept (*n_out); ms_finalize covers the exact pass, the sorts and the reduction.  Every other entry point
  * runs as before, launch for launch.
- * Out of scope: chains with variable spacing between blocks, groups that span batches, multi-GPU drivers
- * (hs_pssm_family_hits is the merge), per-row p-values. */
+ * Out of scope: groups that span batches, multi-GPU drivers (hs_pssm_family_hits is the merge), per-row p-values.
+ * Chains with variable spacing between blocks (a gap penalty between diagonals): hs_pssm_family_chain below. */
 HS_API hs_status hs_pssm_family_scan(hs_handle* h, const double* S, const double* t, uint64_t nm,
                                      const uint32_t* m_group, uint64_t n_groups, const uint32_t* m_off,
                                      const uint64_t* id_start, uint64_t n_seq, uint32_t min_count,
@@ -1467,6 +1469,100 @@ HS_API hs_status hs_pssm_family_hits(const uint32_t* m, const uint32_t* id, cons
 HS_API hs_status hs_pssm_family_layout(const uint32_t* hit_x, const uint32_t* hit_y, const int32_t* hit_d,
                                        uint64_t n_hits, uint64_t nm, uint32_t* out_group, uint32_t* out_off,
                                        uint32_t* out_order, uint64_t* n_groups, uint64_t* n_conflicts);
+
+/* ---- PSSM family chains: the best gapped chain of a family's hits per sequence ----------------------------------- */
+
+/* hs_pssm_family_scan sees blocks at FIXED spacing: one inserted or deleted residue between two blocks moves the later
+ * blocks onto another diagonal, and the protein falls apart into rows that each miss min_count.  This call links a
+ * family's hits across neighbouring diagonals at a gap penalty and reports, per (family, sequence), the best chain.
+ * Arguments, stream rules, host and device pointer rules and the capacity protocol are hs_pssm_family_scan's; new are
+ * max_shift, gap_open, gap_ext, and the ten output arrays.
+ *
+ * Underlying hits: H is the hit list hs_pssm_scan(S, t) returns on the same handle, bit for bit.  A hit i = (m_i, id_i,
+ * score_i) has g, s, off and diag = off - m_off[m] (a signed 64-bit number) as in hs_pssm_family_scan.  m_off is
+ * REQUIRED here and must not decrease inside a group: a family's profiles are passed in block order, which is what
+ * hs_pssm_family_layout's out_order produces.
+ * Links: hit j may precede hit i iff both have the same g and the same s, m_j < m_i, off_j < off_i and
+ * d = |diag_i - diag_j| <= max_shift.  Blocks may be skipped.  The penalty of a link, every operation a rounded fp64
+ * operation, no FMA, no re-association: pen(0) = +0.0, and the link's value is then C(j) itself;
+ * pen(d) = gap_open + gap_ext * (double)d for d >= 1, the product rounded first, then the sum.
+ * Chain score: with the hits of a (g, s) segment in ascending (m, id), and v(j) = C(j) - pen(d) over the predecessors
+ * of hit i, the best predecessor is the first under (v descending, n(j) descending, m_j descending, id_j ascending).
+ * It is taken iff its v > +0.0:  C(i) = v + score_i, n(i) = n(j) + 1, first(i) = first(j), gaps(i) = gaps(j) + (d != 0).
+ * Otherwise the chain starts at i:  C(i) = +0.0 + score_i, n(i) = 1, first(i) = i, gaps(i) = 0.  A local chain: a
+ * non-positive prefix is dropped.  The maximum over predecessors is an exact comparison, so its order of evaluation
+ * does not show; only the depth (the blocks of a family, at most 4096) is sequential.
+ * No NaN arises: a predecessor is taken only at v > 0, scores are finite, pen is finite or, where gap_ext * d
+ * overflows, +inf (v = -inf is not taken), and +inf + score is +inf.  No C is -0.0.
+ * Rows: at most one per (g, s), ascending in (g, s).  Candidate ends are the hits i of the segment with
+ * n(i) >= min_count and (t_group == NULL or C(i) >= t_group[g]); the row is the first candidate under (C descending,
+ * n descending, m ascending, id ascending); a segment without a candidate reports nothing.
+ *   out_group, out_seq           g, s
+ *   out_count                    n: the blocks in the chain
+ *   out_gaps                     its links with d != 0
+ *   out_score                    C, its bits
+ *   out_first_m, out_first_id    the chain's first hit
+ *   out_last_m, out_last_id      the chain's last hit
+ *   out_shift                    diag_last - diag_first (|shift| <= 4096 * 65535 fits)
+ * *n_out, grp_rows [n_groups] and the capacity protocol count reported rows only; *n_hits and cnt [nm] are the scan's.
+ * Purity: the rows are a pure function of (codes, S, t, m_group, m_off, id_start, max_shift, gap_open, gap_ext,
+ * min_count, t_group).  Profile batch, HS_OPT_PSSM_FILTER, survivor splits and scheduling do not show.
+ * Errors, reported before anything is written, all HS_ERR_INVALID but the unbuilt index (HS_ERR_STATE): everything
+ * hs_pssm_family_scan refuses (its width rule included); m_off == NULL; an m_off that decreases inside a group (the
+ * _dev form finds it in the family arguments' check kernel); max_shift > 65535 (HS_PSSM_CHAIN_MAX_SHIFT in
+ * hsearch_amd/csrc/hs_pssm_chain.h: the cost of a hit is linear in it); gap_open or gap_ext NaN, infinite or negative
+ * (-0.0 is read as +0.0).  Batches are cut at group starts as in hs_pssm_family_scan; a single group that overflows the
+ * survivor counter is HS_ERR_CAPACITY with the cause in hs_last_error.
+ *
+ * How (hsearch_amd/csrc/hs_pssm_chain.hip): per batch, after the scan's own (m, id) sort, the sequence of every hit, a
+ * segment key g << ws | s, one stable radix sort of (key, hit index) -- a segment's hits come out as runs by profile,
+ * off ascending inside a run --, segment starts, then one wave per segment: a run is one DP level, its hits go to the
+ * lanes, every lane bisects the admissible range of each earlier run and takes the maximum of at most 2 max_shift + 1
+ * entries; the state lies in LDS for small segments and in global scratch otherwise; the wave then reduces the
+ * candidate ends with shuffles.  A segment of H hits over r runs costs about H r (log H + 2 max_shift + 1) / 64 steps of
+ * ONE wave: a huge segment (an everything-hits threshold on one long protein) is slow by design.
+ * hs_profile after the call: the pssm_* fields as after a scan, hits, pssm_chain_segs (segments before the filters),
+ * pssm_chain_kept (*n_out); ms_finalize covers the exact pass, the sorts and the chain.  Every other entry point runs
+ * as before, launch for launch.
+ * Out of scope: several non-overlapping chains per protein, the path from the device form (hs_pssm_family_chain_hits
+ * gives it), families above 4096 profiles, per-chain p-values, multi-GPU drivers (the host rule is the merge). */
+HS_API hs_status hs_pssm_family_chain(hs_handle* h, const double* S, const double* t, uint64_t nm,
+                                      const uint32_t* m_group, uint64_t n_groups, const uint32_t* m_off,
+                                      const uint64_t* id_start, uint64_t n_seq, uint32_t max_shift, double gap_open,
+                                      double gap_ext, uint32_t min_count, const double* t_group, uint32_t* out_group,
+                                      uint32_t* out_seq, uint32_t* out_count, uint32_t* out_gaps, double* out_score,
+                                      uint32_t* out_first_m, uint32_t* out_first_id, uint32_t* out_last_m,
+                                      uint32_t* out_last_id, int32_t* out_shift, uint64_t cap, uint64_t* n_out,
+                                      uint64_t* n_hits, uint64_t* cnt, uint64_t* grp_rows);
+/* ... every pointer but n_out / n_hits in device memory (streams: as hs_pssm_scan_dev) */
+HS_API hs_status hs_pssm_family_chain_dev(hs_handle* h, const double* d_S, const double* d_t, uint64_t nm,
+                                          const uint32_t* d_m_group, uint64_t n_groups, const uint32_t* d_m_off,
+                                          const uint64_t* d_id_start, uint64_t n_seq, uint32_t max_shift,
+                                          double gap_open, double gap_ext, uint32_t min_count, const double* d_t_group,
+                                          uint32_t* d_out_group, uint32_t* d_out_seq, uint32_t* d_out_count,
+                                          uint32_t* d_out_gaps, double* d_out_score, uint32_t* d_out_first_m,
+                                          uint32_t* d_out_first_id, uint32_t* d_out_last_m, uint32_t* d_out_last_id,
+                                          int32_t* d_out_shift, uint64_t cap, uint64_t* n_out, uint64_t* n_hits,
+                                          uint64_t* d_cnt, uint64_t* d_grp_rows);
+/* The same rule on the host (no GPU, no handle) over any list of (m, id, score) tuples in any order: the merge of
+ * several GPUs' hit lists and the reference the device is held to.  A repeated (m, id) and a score of -0.0 are handled
+ * as hs_pssm_family_hits handles them; a tuple with an infinite score is HS_ERR_INVALID here (no scan produces one, and
+ * the rule's freedom from NaN rests on it).  The three path arrays may all be NULL (n_path too, then).  When given,
+ * out_path_start [*n_out + 1] delimits, per reported row, the chain's hits (out_path_m, out_path_id) from first to
+ * last, and *n_path is their total.  HS_ERR_CAPACITY: the rows exceed cap or the paths exceed path_cap; *n_out and
+ * *n_path are set, nothing else is written.  Not quadratic in a segment's hits at a small max_shift: inside a segment
+ * the hits of one profile are ascending in off, so the predecessors of a hit among one earlier profile's hits are one
+ * contiguous range found by bisection: O(hits x profiles present x (log + 2 max_shift + 1)). */
+HS_API hs_status hs_pssm_family_chain_hits(const uint32_t* m, const uint32_t* id, const double* score,
+                                           uint64_t n_tuples, uint64_t nm, const uint32_t* m_group, uint64_t n_groups,
+                                           const uint32_t* m_off, const uint64_t* id_start, uint64_t n_seq,
+                                           uint32_t max_shift, double gap_open, double gap_ext, uint32_t min_count,
+                                           const double* t_group, uint32_t* out_group, uint32_t* out_seq,
+                                           uint32_t* out_count, uint32_t* out_gaps, double* out_score,
+                                           uint32_t* out_first_m, uint32_t* out_first_id, uint32_t* out_last_m,
+                                           uint32_t* out_last_id, int32_t* out_shift, uint64_t cap, uint64_t* n_out,
+                                           uint64_t* out_path_start, uint32_t* out_path_m, uint32_t* out_path_id,
+                                           uint64_t path_cap, uint64_t* n_path);
 
 /* ---- PSSM hit counts and refinement: from a profile's hits back to a profile ------------------------------------- */
 
